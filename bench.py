@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- MCMC iterations/second of the bWGR Gibbs hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c4|c3|c2]
+    python bench.py --gpus N --steps K --warmup W [--workload c4|c3|c2] [--dump-outputs DIR] [--full]
 
 One "step" = one MCMC iteration of the fused sampler: the full marker sweep plus that model's intercept / variance
 draws and posterior sums (everything inside for(i...) of src/Rcpp20260726ai.cpp:666-688), with X, y and all chain
@@ -12,7 +12,9 @@ collective, `"scaling": "weak"` (the exact sweep is a recur
 the marker-sharded partitioned sampler instead (one chain over N GPUs, RCCL residual all-reduce; strong scaling), which runs on
 CENTRED columns -- where it is statistically sound -- unless `--uncentred` is given.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and, at N=1, `cpu_baseline`.
+Prints ONE JSON line on rank 0 with `roofline`.  A plain run times the headline chain and nothing else;
+`--full` adds, at N=1, the legs that take runs of their own: BASELINE configs 2 and 3 (`workloads`), chains side by side and in pairs,
+`cpu_baseline` and `intra_gpu_shards`.  `--dump-outputs DIR` writes what the timed chain returns after its last step as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -156,9 +158,29 @@ def pmc_traffic(workload, n, p, kernel):
     return None, None
 
 
-def single_leg(workload, K, W, dev, args, keep):
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(ch, st, out_dir):
+    """What a caller of the timed chain receives after its last step, as out_dir/<name>.npy (float32, whole arrays): the last sample
+    (Chain.state(): state_*) and the posterior means over the timed steps (Chain.result(), the reference's return list: result_*)."""
+    import numpy as np
+    arrays = {}
+    for prefix, d in (("state", st), ("result", ch.result())):
+        for k, v in d.items():
+            arrays["%s_%s" % (prefix, k)] = np.atleast_1d(np.asarray(v, dtype=np.float32))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of outputs exceed the %d byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
+def single_leg(workload, K, W, dev, args, keep, dump_dir=None):
     """One exact chain of `workload` alone on the GPU: W untimed iterations, K timed between synchronizes, the sweep kernel's mean launch
-    time from hipEvents on its stream.  keep: return the panel and inputs for the legs that follow (the caller closes them)."""
+    time from hipEvents on its stream.  keep: return the panel and inputs for the legs that follow (the caller closes them).  dump_dir: write the
+    chain's outputs there after the timed steps (dump_outputs)."""
     import torch
     import bwgr_amd
     from bwgr_amd import synth
@@ -168,7 +190,7 @@ def single_leg(workload, K, W, dev, args, keep):
     g = synth.phenotype(X, n)
     y = synth.scale_phenotype(g)
     Xs_host = None
-    if keep and not args.no_cpu:
+    if keep and args.full and not args.no_cpu:
         ps = min(args.cpu_slice, p)
         Xs_host = X[:ps, :n].cpu().numpy().T   # (n, ps) view, column-major
     P = bwgr_amd.Panel(X, n=n, device=dev, block=args.block, nwg=args.nwg)
@@ -187,6 +209,8 @@ def single_leg(workload, K, W, dev, args, keep):
     t1 = time.perf_counter()
     sweep_ms, launches = ch.sweep_ms()
     st = ch.state()
+    if dump_dir:
+        dump_outputs(ch, st, dump_dir)
     elapsed = t1 - t0
     alg_bytes = float(n) * float(p) * 1.0      # every genotype byte read once per sweep
     pl = P.pipeline(bool(pi) or model in ("BayesCpi", "BayesDpi"))
@@ -267,7 +291,11 @@ def main():
     ap.add_argument("--block", type=int, default=0)
     ap.add_argument("--nwg", type=int, default=0)
     ap.add_argument("--sync-every", type=int, default=0, help="markers per rank between residual all-reduces (N>1)")
-    ap.add_argument("--chains", type=int, default=0, help="extra leg at N=1: this many chains side by side on the one "
+    ap.add_argument("--full", action="store_true", help="N=1: after the headline, every leg that takes runs of its own (c2 / c3 workloads, chains "
+                    "side by side and in pairs, the CPU baseline, shards side by side); the options below switch single legs off again")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed chain returns after its last step (Chain.state(), Chain.result()) "
+                    "as DIR/<name>.npy, float32 (bench_outputs/ in the repository is git-ignored for this)")
+    ap.add_argument("--chains", type=int, default=0, help="--full leg at N=1: this many chains side by side on the one "
                     "resident panel (0 = as many as fit the chip, 1 = skip the leg); reported as concurrent_chains")
     ap.add_argument("--sharded", action="store_true", help="N > 1: the marker-sharded partitioned sampler (one chain over N GPUs, RCCL "
                     "residual all-reduce) instead of N replica chains; statistically unsound on uncentred genotypes, see DESIGN.md section 8")
@@ -275,11 +303,11 @@ def main():
                     "kept for measurements)")
     ap.add_argument("--centre-explicit", action="store_true", help="--sharded: centre into a float32 copy of the shard (round 3's path, 4 bytes per genotype) instead of "
                     "sweeping the int8 shard as implicitly centred columns")
-    ap.add_argument("--shards", type=int, default=3, help="extra leg at N=1: the partitioned sampler's marker shards side by side on the one GPU, implicitly centred "
+    ap.add_argument("--shards", type=int, default=3, help="--full leg at N=1: the partitioned sampler's marker shards side by side on the one GPU, implicitly centred "
                     "int8 (reported as intra_gpu_shards; 0 or 1 = skip)")
-    ap.add_argument("--pairs", type=int, default=0, help="pairs of chains in the paired-chains leg (0: as many as fit)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the c2 / c3 legs that follow the headline workload (`workloads` in the JSON line)")
+    ap.add_argument("--pairs", type=int, default=0, help="pairs of chains in the paired-chains leg of --full (0: as many as fit)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the c2 / c3 legs that follow the headline workload (`workloads` in the JSON line)")
     ap.add_argument("--cpu-slice", type=int, default=20000)
     args = ap.parse_args()
 
@@ -304,6 +332,8 @@ def main():
     torch.cuda.set_device(dev)
 
     if (world > 1 and args.sharded) or os.environ.get("BWGR_FORCE_DIST"):   # BWGR_FORCE_DIST=1: rehearse the sharded leg with one rank
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs covers the exact chain, not the sharded sampler")
         from bwgr_amd import dist as bdist
         out = bdist.bench_sharded(args, n, p, model, pi, K, W, rank, world, dev)
         if rank == 0:
@@ -335,6 +365,8 @@ def main():
         elapsed = float(el.item())
         sweep_ms, launches = ch.sweep_ms()
         st = ch.state()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(ch, st, args.dump_outputs)
         mean_d = float(st["d"].mean())
         pl = P.pipeline(bool(pi))
         kernel = {4: "k_sweep2w", 3: "k_sweep3<uint16>", 2: "k_sweep2<int8>", 1: "k_sweep<int8>"}[pl["generation"]]
@@ -360,7 +392,11 @@ def main():
         return
 
     # ---- single GPU ----
-    out, P, y, Xs_host, pl = single_leg(args.workload, K, W, dev, args, keep=True)
+    out, P, y, Xs_host, pl = single_leg(args.workload, K, W, dev, args, keep=True, dump_dir=args.dump_outputs)
+    if not args.full:   # a plain run: the headline chain alone
+        P.close()
+        print(json.dumps(out))
+        return
     # BASELINE configs 2 and 3 on the same box, same timing discipline (a barrier-free single GPU: synchronize on both sides, K steps
     # timed exactly, kernel time by hipEvents on the kernel's stream): driver-visible beside the headline, each with its own roofline.
     # (Before the legs that open further streams: c2 is about 1 ms and fifteen launches a step, and once the process holds several hardware

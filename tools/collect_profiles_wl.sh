@@ -10,7 +10,7 @@ REPO=$PWD
 mkdir -p $OUT
 export TMPDIR=/tmp
 if [ -z "$PMC_ONLY" ]; then
-python3 bench.py --workload $WL --chains 1 --no-extra --shards 0 ${BENCH_EXTRA} > $OUT/${TAG}_bench_${WL}.json 2> $OUT/${TAG}_bench_${WL}.err
+python3 bench.py --full --workload $WL --chains 1 --no-extra --shards 0 ${BENCH_EXTRA} > $OUT/${TAG}_bench_${WL}.json 2> $OUT/${TAG}_bench_${WL}.err
 echo "$WL bench done"
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $OUT/prof_stats_${WL} -o ${TAG}${WL} --output-format csv -- python3 $REPO/bench.py --workload $WL --steps 10 --warmup 2 --no-cpu --no-extra --shards 0 --chains 1 > $OUT/${TAG}_bench_${WL}_under_rocprof.json 2> $OUT/${TAG}_rocprof_${WL}.err
