@@ -931,6 +931,50 @@ __global__ void k_redo_clear(ChainScalars *sc) { sc->redo = 0u; }
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
+// The environment switches, every one the library reads, read once: when a root panel is made.  Clones copy the
+// root's; the scratch panels of KMUP2, bagging and the EM family, and groups take the panels' they are made for.  First-character switches
+// hold that character (-1: unset); numeric ones hold their value as parsed (0: unset); the rest their parsed meaning.
+struct Switches {
+  int sweep = -1, lag = -1, solo3 = -1, stream3 = -1, pf3 = -1;                  // BWGR_SWEEP, BWGR_LAG, BWGR_SOLO3, BWGR_STREAM3, BWGR_PF3
+  int r3 = 0, d3 = 0, nfeed = 0, sh_add = 0, max_concurrent = 0, max_pairs = 0;  // BWGR_R3, BWGR_D3, BWGR_NFEED, BWGR_DEBUG_SH_ADD, BWGR_MAX_CONCURRENT, BWGR_MAX_PAIRS
+  // BWGR_ENG3_THR: k_sweep3 takes the sweeps whose chains hold fewer than this share of markers in the model; measured crossover at n = 10 000:
+  // us per block at 1.4 / 3.7 / 5.8 / 10.9 % inclusion: k_sweep3 2.26 / 3.73 / 5.56 / 12.1, k_sweep2 3.07 / 3.29 / 3.60 / 4.69
+  float eng3_thr = 0.03f;
+  bool occ_guard = true, pf3b = true, draws = true, gram16 = true;   // BWGR_OCC_GUARD=0, BWGR_PF3B=0, BWGR_DRAWS=0, BWGR_GRAM16=0 switch these off
+  // BWGR_WINV=0: the serial recurrence of k_sweep2's sequencer instead of k_sweep2w; BWGR_WFX=0: k_sweep2's streamers under its product sequencer
+  // instead of the fixed-point ones; BWGR_WPF / BWGR_WAHEAD / BWGR_WNQ (0: by the streamer count) / BWGR_WLAG (=5|6: distances 4 / 5 through LDS
+  // planes -- measured slower: C4-shape BayesA 22.3 / 23.0 / 24.9 ms per sweep at depth 4 / 5 / 6)
+  bool winv = true, wfx = true;
+  int wpf = 4, wahead = 5, wnq = 0, wlag_cap = 4;
+  bool group_allow_uncentred = false, group_force_comm = false, em_debug = false;   // BWGR_GROUP_ALLOW_UNCENTRED=1, BWGR_GROUP_FORCE_COMM=1, BWGR_EM_DEBUG
+#ifdef BWGR_EXPERIMENTS
+  int dbg3 = 0, dbgw = 0, wlag_timing = 0; bool no_recover = false;   // BWGR_DBG3, BWGR_DBGW, BWGR_WLAG_TIMING, BWGR_NO_RECOVER
+#endif
+};
+static Switches read_switches() {
+  const auto chr = [](const char *v) { return v ? (int)(unsigned char)v[0] : -1; };
+  const auto num = [](const char *v) { return v ? atoi(v) : 0; };
+  Switches s;
+  s.sweep = chr(getenv("BWGR_SWEEP")); s.lag = chr(getenv("BWGR_LAG")); s.solo3 = chr(getenv("BWGR_SOLO3"));
+  s.stream3 = chr(getenv("BWGR_STREAM3")); s.pf3 = chr(getenv("BWGR_PF3"));
+  s.r3 = num(getenv("BWGR_R3")); s.d3 = num(getenv("BWGR_D3")); s.nfeed = num(getenv("BWGR_NFEED")); s.sh_add = num(getenv("BWGR_DEBUG_SH_ADD"));
+  s.max_concurrent = num(getenv("BWGR_MAX_CONCURRENT")); s.max_pairs = num(getenv("BWGR_MAX_PAIRS"));
+  if (const char *v = getenv("BWGR_ENG3_THR")) { const float t = (float)atof(v); if (t > 0.0f) s.eng3_thr = t; }
+  s.occ_guard = chr(getenv("BWGR_OCC_GUARD")) != '0'; s.pf3b = chr(getenv("BWGR_PF3B")) != '0'; s.draws = chr(getenv("BWGR_DRAWS")) != '0';
+  s.gram16 = chr(getenv("BWGR_GRAM16")) != '0'; s.winv = chr(getenv("BWGR_WINV")) != '0'; s.wfx = chr(getenv("BWGR_WFX")) != '0';
+  if (const char *v = getenv("BWGR_WPF")) s.wpf = std::max(0, std::min(8, atoi(v)));
+  if (const char *v = getenv("BWGR_WAHEAD")) s.wahead = std::max(1, atoi(v));
+  { const int v = num(getenv("BWGR_WNQ")), c = chr(getenv("BWGR_WLAG")); if (v == 1 || v == 2 || v == 4) s.wnq = v; if (c >= '2' && c <= '6') s.wlag_cap = c - '0'; }
+  s.group_allow_uncentred = chr(getenv("BWGR_GROUP_ALLOW_UNCENTRED")) == '1'; s.group_force_comm = chr(getenv("BWGR_GROUP_FORCE_COMM")) == '1';
+  s.em_debug = getenv("BWGR_EM_DEBUG") != nullptr;
+#ifdef BWGR_EXPERIMENTS
+  s.dbg3 = num(getenv("BWGR_DBG3")); s.dbgw = num(getenv("BWGR_DBGW")); s.wlag_timing = num(getenv("BWGR_WLAG_TIMING"));
+  s.no_recover = getenv("BWGR_NO_RECOVER") != nullptr;
+#endif
+  return s;
+}
+
+// ------------------------------------------------------------------------------------------------
 struct bwgr_panel {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -965,6 +1009,8 @@ struct bwgr_panel {
   bwgr_panel *parent = nullptr;   // a clone shares the parent's read-only arrays (X, Gram, xx, vx) and owns only the scratch
   int nclones = 0;
   int nchains = 0;                // live chains on this handle: panel_destroy refuses while any is alive
+  int nchains_all = 0;            // root panel: live chains on it and on its clones (bwgr_panel_set_centred refuses while any is alive)
+  Switches sw;                    // read when the root panel is made
   int debug_withhold = 0;         // test hook: the next sweeps run with slab workgroup 0 missing (bwgr_debug_withhold)
   // k_sweep3 (selection models on int8 panels, sweep3.hip.h)
   bool want3 = false;             // build what k_sweep3 needs with the panel (off for the per-iteration scratch panels of bagging and the EM family)
@@ -982,18 +1028,13 @@ struct bwgr_panel {
   size_t lds3_bytes = 0;
   double *snap_e = nullptr; float *snap_b = nullptr, *snap_d = nullptr, *snap_vb = nullptr;   // state before a fixed-point sweep (range recovery)
   // the affine models' block solve as a triangular product (sweep2w.hip.h)
-  bool winv_on = true;            // BWGR_WINV=0: the serial recurrence of k_sweep2's sequencer instead
   double *winv = nullptr;         // per handle: [nblocks][S2W_WDOUBLES], written by k_affine_inv before every affine sweep
   unsigned char *gxt[S2W_MAXDIST] = {};   // the cross Gram blocks as the sequencer's MFMA operand (k_gx_planes); shared with clones
   unsigned long long *qsumw = nullptr;    // per handle: the fixed-point streamers' slab-dot sums [nblocks][SW_MAXM][2]
-  int wpf = 4, wahead = 5, wnq = 0, wlag_cap = 4;   // (BWGR_WLAG=5|6: distances 4 / 5 through LDS planes -- measured slower: C4-shape BayesA 22.3 / 23.0 / 24.9 ms per sweep at depth 4 / 5 / 6)   // BWGR_WPF / BWGR_WAHEAD / BWGR_WNQ (0: by the streamer count) / BWGR_WLAG, read when the panel is made
-  bool wfx_on = true;             // BWGR_WFX=0: k_sweep2's streamers under the product sequencer instead of the fixed-point ones
   int winv_nd = 0;                // distances built = the deepest lag the affine sweeps can run, minus one
   size_t ldsw_bytes = 0;
   std::vector<hipStream_t> pair_streams;   // root panel: the streams pairs of chains run on (bwgr_chain_run_pair); owned here, so that they outlive every clone
   bool force3 = false;            // a pair run (bwgr_chain_run_pair): every selection sweep is k_sweep3's, whatever the inclusion rate
-  float eng3_thr = 0.03f;         // k_sweep3 takes the sweeps whose chains hold fewer than this share of markers in the model (BWGR_ENG3_THR);
-                                  // measured crossover at n = 10 000: us per block at 1.4 / 3.7 / 5.8 / 10.9 % inclusion: k_sweep3 2.26 / 3.73 / 5.56 / 12.1, k_sweep2 3.07 / 3.29 / 3.60 / 4.69
   // implicitly centred columns (bwgr_panel_set_centred; int8 panels with k_sweep3): the column sums, the centred |x_j - mean_j|^2 as floats (what
   // a chain's xx is then), both owned by the root panel; per handle the running block sums of s_k * drej_k of the current iteration
   bool cen = false;
@@ -1074,22 +1115,30 @@ static hipError_t alloc_exchange(bwgr_panel *P) {
   return hipSuccess;
 }
 // polled words are zeroed before every launch (epochs count within a launch)
+// ---- the sweep plan -----------------------------------------------------------------------------------------------------------
+// Which engine a sweep runs, how deep, and in what launch shape is one decision, made by plan_sweep (below) from the panel -- its geometry,
+// its Gram range, its clones and pairs, its switches -- and the sweep's flags.  The launch code executes a plan and decides nothing of its own;
+// the occupancy guard prices the plan's spin launches.
+// resident: the workgroups of the grid that stay for the sweep (L2 prefetch workgroups beyond the first few leave at once)
+struct SpinLaunch { const void *fn; int grid, resident, threads; size_t lds; };
+struct SweepPlan {
+  int engine = 1;          // bwgr_panel_pipeline's generation: 1 k_sweep, 2 k_sweep2, 3 k_sweep3 (k_sweep2 beside it while the gate is finite), 4 k_sweep2w
+  float gate3 = 0.0f;      // k_sweep3 takes the sweeps of chains below this inclusion rate (decided on the device); 0: never, INFINITY: every one
+  int lag = 2, nfeed = 0;  // pipeline depth; q feeder workgroups of k_sweep2
+  bool g16 = false;        // k_sweep2 on the 16-bit Gram copies
+  int R3 = 0, K3 = 0, sub = 0, pf = -1, pf2 = -1, dbg3 = 0, qsplit = 0, skip_vb = 0;   // k_sweep3 (dbg3: the DMA streamer bits, and BWGR_DBG3)
+  int fx = 0, nd = 0, npf = 0, ahead = 0, nq = 0, wsub = 0, wK3 = 0;                  // k_sweep2w
+  bool guarded = false;    // the range snapshot in front, the fp64 redo (plan_sweep(P, a, true)) behind
+  bool draws = false;      // the next iteration's variates drawn beside the sweep (draws_ahead)
+  int nspins = 0; SpinLaunch spins[3];   // the launches whose workgroups wait for one another: the primary's, then the redo's
+};
+static void spin_launch(const SpinLaunch &L, hipStream_t st, void **args) { (void)hipLaunchKernel(L.fn, dim3(L.grid), dim3(L.threads), args, L.lds, st); }
+
 // ---- occupancy guard -------------------------------------------------------------------------------------------------------------
 // The sweep kernels' workgroups wait for one another (slab-dot exchanges, the sequencer's decisions), so every workgroup of a launch has
 // to be resident at once -- beside the workgroups of whatever other handles' sweeps are in flight on the same device.  A launch that would
-// not fit spins to its wall-clock bound and ends in BWGR_ETIMEOUT; the guard refuses it up front with BWGR_EINVAL instead.  The sweep's
-// launch code runs twice: once "dry" (g_plan set: SPIN_LAUNCH records kernel, grid, threads and LDS instead of launching, and nothing
-// else is enqueued or allocated), then for real.
-struct SpinLaunch { const void *fn; int grid, threads; size_t lds; };
-static thread_local std::vector<SpinLaunch> *g_plan = nullptr;
-#define SWEEP_DRY (g_plan != nullptr)
-// resident: the workgroups of the grid that stay for the sweep (L2 prefetch workgroups beyond the first few leave at once)
-#define SPIN_LAUNCH_N(resident, kern, grid, blk, lds, stream, ...)                                                                   \
-  do {                                                                                                                             \
-    if (g_plan) g_plan->push_back(SpinLaunch{reinterpret_cast<const void *>(kern), (int)(resident), (int)dim3(blk).x, (size_t)(lds)}); \
-    else hipLaunchKernelGGL(kern, grid, blk, lds, stream, __VA_ARGS__);                                                             \
-  } while (0)
-#define SPIN_LAUNCH(kern, grid, blk, lds, stream, ...) SPIN_LAUNCH_N(dim3(grid).x, kern, grid, blk, lds, stream, __VA_ARGS__)
+// not fit spins to its wall-clock bound and ends in BWGR_ETIMEOUT; the guard refuses it up front with BWGR_EINVAL instead, from the
+// spin launches of the sweep's plan.
 static std::mutex g_guard_mu;
 static std::vector<bwgr_panel *> g_guard_panels;   // handles with a guard event (any device)
 // the arithmetic (also bwgr_debug_occupancy_fits, which the CPU tests call): a launch of `grid` workgroups, `per_cu` of which fit one
@@ -1103,7 +1152,6 @@ static int occupancy_fits(int grid, int per_cu, int cus, int busy, int *need) {
   return (nd + busy <= cus) ? BWGR_OK : BWGR_EINVAL;
 }
 extern "C" int bwgr_debug_occupancy_fits(int grid, int per_cu, int cus, int busy, int *need) { return occupancy_fits(grid, per_cu, cus, busy, need); }
-static bool guard_on() { const char *g = getenv("BWGR_OCC_GUARD"); return !(g && g[0] == '0'); }
 static int guard_per_cu(const SpinLaunch &L) {
   static std::mutex mu; static std::vector<std::pair<SpinLaunch, int>> cache;
   std::lock_guard<std::mutex> lk(mu);
@@ -1120,17 +1168,18 @@ static int device_cus(int device) {
   if (!cus[device]) { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device) == hipSuccess) cus[device] = prop.multiProcessorCount; else (void)hipGetLastError(); }
   return cus[device];
 }
-// compute units the recorded launches hold: launches of one sweep follow one another on one stream, so the largest of them
-static int plan_cus(const std::vector<SpinLaunch> &plan, int cus, int busy, int *need_out) {
+// compute units the plan's spin launches hold: launches of one sweep follow one another on one stream, so the largest of them
+static int plan_cus(const SweepPlan &pl, int cus, int busy, int *need_out) {
   int need = 0;
-  for (const SpinLaunch &L : plan) {
+  for (int i = 0; i < pl.nspins; ++i) {
+    const SpinLaunch &L = pl.spins[i];
     const int per = guard_per_cu(L);
     int nd = 0;
     if (per < 1) return fail(BWGR_EINVAL, "occupancy guard: a sweep kernel (%d threads, %zu bytes of LDS) does not fit a compute unit", L.threads, L.lds);
-    if (occupancy_fits(L.grid, per, cus, busy, &nd) != BWGR_OK)
+    if (occupancy_fits(L.resident, per, cus, busy, &nd) != BWGR_OK)
       return fail(BWGR_EINVAL, "occupancy guard: a sweep launch of %d workgroups (%d per compute unit) needs %d compute units; %d of %d are held by other handles' sweeps "
                   "in flight (their workgroups wait for one another, so all must be resident at once: run fewer chains side by side -- bwgr_panel_max_concurrent -- or "
-                  "wait for the others)", L.grid, per, nd, busy, cus);
+                  "wait for the others)", L.resident, per, nd, busy, cus);
     need = std::max(need, nd);
   }
   *need_out = need;
@@ -1152,6 +1201,16 @@ static int guard_busy(const bwgr_panel *P, hipStream_t mine, const bwgr_panel *p
   for (auto &ps : per_stream) busy += ps.second;
   return busy;
 }
+// The compute units the plan's spin launches hold on stream st; refused with BWGR_EINVAL when they cannot be resident beside the sweeps
+// other handles (but partner) have in flight on this device.  BWGR_OCC_GUARD=0 switches the guard off.
+static int sweep_guard(const bwgr_panel *P, const SweepPlan &pl, hipStream_t st, const bwgr_panel *partner, int *need) {
+  *need = 0;
+  if (!P->sw.occ_guard) return BWGR_OK;
+  const int cus = device_cus(P->device);
+  if (cus < 1) return BWGR_OK;
+  std::lock_guard<std::mutex> lk(g_guard_mu);
+  return plan_cus(pl, cus, guard_busy(P, st, partner), need);
+}
 // after the real launches: this handle holds `need` units until the event behind them completes
 static void guard_mark(bwgr_panel *P, hipStream_t st, int need) {
   if (need <= 0) return;
@@ -1170,7 +1229,6 @@ static void guard_forget(bwgr_panel *P) {
 }
 
 static int reset_exchange(bwgr_panel *P) {
-  if (SWEEP_DRY) return BWGR_OK;
   if (P->sweep_version >= 2) {
     HIPCHK(hipMemsetAsync(P->xchg, 0, P->xchg_bytes, P->stream));
   } else if (P->K > 1) {
@@ -1180,11 +1238,7 @@ static int reset_exchange(bwgr_panel *P) {
 }
 
 static void launch_gramx_i8(bwgr_panel *P, int32_t *g, int dist);
-// ---- k_sweep3 (sweep3.hip.h): which launches take it, and what it needs beside the panel ----
-static int sweep3_lag(const bwgr_panel *P) { return P->e3_D; }
-static bool use_sweep3(const bwgr_panel *P, int flags) {
-  return P->sweep_version == 3 && P->e3_ready && (flags & SWF_SELECT) != 0 && (flags & SWF_EM_ANY) == 0;
-}
+// ---- k_sweep3 (sweep3.hip.h): what it needs beside the panel ----
 // geometry, scratch and attributes (every handle: panels and clones)
 static int sweep3_alloc_scratch(bwgr_panel *P) {
   HIPCHK(hipMalloc(&P->qsum3, sizeof(unsigned long long) * 2 * SW_MAXM * (size_t)P->nblocks));
@@ -1198,11 +1252,11 @@ static int sweep3_build(bwgr_panel *P) {
   if (P->is_f32 || !P->want3 || P->sweep_version != 3) return BWGR_OK;
   const int m = P->m;
   int R3 = (P->R % 256 == 0) ? 256 : 128;
-  if (const char *rv = getenv("BWGR_R3")) { const int v = atoi(rv); if ((v == 64 || v == 128 || v == 256) && P->R % v == 0) { R3 = v; P->solo3 = false; } }   // (an explicit height holds for every launch)
+  { const int v = P->sw.r3; if ((v == 64 || v == 128 || v == 256) && P->R % v == 0) { R3 = v; P->solo3 = false; } }   // (an explicit height holds for every launch)
   const int sub = P->R / R3, K3 = P->K * sub;
   int D = 12;   // (the streamers fold a list whose words they saw a step ahead: more lag than the fold itself needs -- C4: 12.45 ms at 8, 11.27 at 9, 10.78 at 10, 10.41 at 11, 10.37 at 12, 10.48 at 13)
   // (at least 2: a block's list leaves the sequencer while the next block is in its rounds)
-  if (const char *dv = getenv("BWGR_D3")) { const int v = atoi(dv); if (v >= 2 && v <= S3_MAXD) D = v; }
+  if (P->sw.d3 >= 2 && P->sw.d3 <= S3_MAXD) D = P->sw.d3;
   D = (int)std::min<int64_t>(D, std::max<int64_t>(2, P->nblocks));
   const size_t lds = std::max(std::max(s3_streamer_lds(R3), std::max(s3_streamer_dma_lds(128), R3 == 256 ? s3_streamer_dma_lds(256) : (size_t)0)), s3_seq_lds(D, P->gram16));
   // the slab dots are summed as integers: sum over all rows of |x| * 128 per digit, four digits of 8 bits, 8 bits of arrival count
@@ -1211,8 +1265,7 @@ static int sweep3_build(bwgr_panel *P) {
     return BWGR_OK;
   }
   P->R3 = R3; P->sub3 = sub; P->K3 = K3; P->e3_D = D; P->lds3_bytes = lds;
-  if (const char *sv3 = getenv("BWGR_SOLO3")) P->solo3 = sv3[0] != '0';
-  if (const char *tv = getenv("BWGR_ENG3_THR")) { const float v = (float)atof(tv); if (v > 0.0f) P->eng3_thr = v; }
+  if (P->sw.solo3 >= 0) P->solo3 = P->sw.solo3 != '0';
   const size_t blk_elems = (size_t)P->nblocks * m * m;
   const bool g16 = P->gram16;
   const int Dbuild = D;
@@ -1255,96 +1308,17 @@ static int sweep3_build(bwgr_panel *P) {
     }
   }
   CHK(sweep3_alloc_scratch(P));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep3<uint16_t, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep3<int32_t, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep3<uint16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep3<int32_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep3p<uint16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep3p<int32_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  for (const void *f : {reinterpret_cast<const void *>(k_sweep3<uint16_t, false>), reinterpret_cast<const void *>(k_sweep3<int32_t, false>), reinterpret_cast<const void *>(k_sweep3<uint16_t, true>),
+                        reinterpret_cast<const void *>(k_sweep3<int32_t, true>), reinterpret_cast<const void *>(k_sweep3p<uint16_t>), reinterpret_cast<const void *>(k_sweep3p<int32_t>)})
+    HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   P->e3_ready = true;
   return BWGR_OK;
 }
 // the DMA streamer's lane offsets are 32-bit: (columns of the launch) * (rows of a slab) bytes must stay below 4 GiB
 static bool stream3_dma_fits(int64_t ncols, int64_t R) { return ncols >= 0 && R > 0 && (uint64_t)ncols * (uint64_t)R < (1ull << 32); }
 extern "C" int bwgr_debug_stream3_dma(int64_t ncols, int64_t R) { return stream3_dma_fits(ncols, R) ? 1 : 0; }
-// what one launch of k_sweep3 / k_sweep3p needs beside the sweep's own arguments; zeroes the launch's slab-dot sums, takes a new epoch
-static void sweep3_args(bwgr_panel *P, const SweepArgs &a, Sweep3Args &A) {
-  memset(&A, 0, sizeof(A));
-  A.a = a;
-  const bwgr_panel *root = P->parent ? P->parent : P;
-  for (int d = 0; d < S3_MAXD; ++d) A.gx[d] = root->g3x[d];
-  A.gp = root->gram16 ? (const void *)root->gramp16 : root->gramp;
-  A.D = P->e3_D; A.K3 = P->K3; A.R3 = P->R3; A.sub = P->sub3; A.g16 = root->gram16 ? 1 : 0;
-  A.qsum = P->qsum3; A.lists = P->lists3;
-  A.gx12 = root->gram16 ? root->gx12 : nullptr;
-  A.pf = -1; A.pf2 = -1;
-#ifdef BWGR_EXPERIMENTS
-  if (const char *dv = getenv("BWGR_DBG3")) A.dbg = atoi(dv);   // (timing switches, some of which break the chain: the experiment build only)
-#endif
-  {   // 128-row streamers land their tiles by LDS-DMA (s3_streamer_dma; C4 15.0 -> 13.65 ms per sweep); BWGR_STREAM3=reg: through registers, as the 256-row ones do
-    // The DMA streamer forms a tile piece's source as a 32-bit lane offset from the launch's first column (no 64-bit vector arithmetic): only
-    // launches whose column range spans less than 4 GiB of one slab take it (p * R < 2^32: 16.7 M markers at R = 256); wider ones keep the
-    // register path, whose offsets are size_t.  bwgr_debug_stream3_dma() exposes the rule to the CPU tests.
-    const char *sv = getenv("BWGR_STREAM3");
-    const int64_t j_lo = (int64_t)a.blk_begin * a.m, j_hi = std::min<int64_t>(P->p, (int64_t)a.blk_end * a.m);
-    const bool fits32 = stream3_dma_fits(j_hi - j_lo, P->R);
-    if (!(sv && sv[0] == 'r') && fits32) A.dbg |= (1 << 22);
-    if (sv && sv[0] == 'd' && fits32) A.dbg |= (1 << 23);   // (EXPERIMENT: the 256-row streamers too, three tile buffers)
-  }
-  if (SWEEP_DRY) return;
-  P->epoch3 = (P->epoch3 + 1) & 0xFFFFFFu; if (P->epoch3 == 0) P->epoch3 = 1;
-  A.epoch = P->epoch3;
-  (void)hipMemsetAsync(P->qsum3 + (size_t)a.blk_begin * 2 * SW_MAXM, 0, sizeof(unsigned long long) * 2 * SW_MAXM * (size_t)(a.blk_end - a.blk_begin), P->stream);
-}
-static void launch_sweep3(bwgr_panel *P, const SweepArgs &a) {
-  Sweep3Args A;
-  sweep3_args(P, a, A);
-  // one more workgroup, on the sequencer's XCD (workgroups with equal index mod 8 share an XCD), warms that XCD's L2 with what the
-  // staging waves load; BWGR_PF3=1 switches it on
-  // A chain that has the GPU to itself (a root panel without clones) runs 128-row streamers, two to a slab: 80 compute units instead
-  // of 41, 15.98-16.18 against 16.49 ms per sweep at C4 (the same chain bit for bit: the slab dots are integer sums).  With clones
-  // alive -- chains side by side, pairs -- every chain keeps the 256-row streamers the concurrency counts assume.  BWGR_SOLO3=0: never.
-  const bool solo = P->solo3 && !P->parent && P->nclones == 0;
-  if (solo && P->R3 == 256 && 2 * P->K3 + 1 <= 256) { A.R3 = 128; A.sub = P->R / 128; A.K3 = P->K * A.sub; }
-  const char *pv = getenv("BWGR_PF3");
-  // (on for a chain alone on the GPU: 15.61 -> 15.37 ms per sweep at C4 on the steadied kernel; beside other chains the workgroup is
-  // not counted by bwgr_panel_max_concurrent, so it stays off there; BWGR_PF3=0|1 decides otherwise)
-  const bool pf_on = (pv ? pv[0] == '1' : solo) && A.K3 + 2 <= 256;
-  A.pf = pf_on ? ((A.K3 + 2 > 8) ? 8 : A.K3 + 1) : -1;
-  A.qsplit = 1;
-  { const char *sv = getenv("BWGR_SKIPVB"); A.skip_vb = ((a.flags & SWF_VB_VEC) && !(sv && sv[0] == '0')) ? 1 : 0; }
-  const char *p2v = getenv("BWGR_PF3B");
-  const bool pf2_on = pf_on && A.pf == 8 && A.gx12 && A.K3 + 3 > 16 && A.K3 + 3 <= 256 && !(p2v && p2v[0] == '0');
-  A.pf2 = pf2_on ? 16 : -1;
-  const dim3 grid(A.K3 + 1 + (pf_on ? 1 : 0) + (pf2_on ? 1 : 0)), blk(SW_THREADS);
-  const bool cen = (a.flags & SWF_CENTRE) != 0;
-  if (cen && !SWEEP_DRY) hipLaunchKernelGGL(k_cen_begin, dim3(1), dim3(1024), 0, P->stream, a, 0);
-  if (A.g16) { if (cen) SPIN_LAUNCH((k_sweep3<uint16_t, true>), grid, blk, P->lds3_bytes, P->stream, A); else SPIN_LAUNCH((k_sweep3<uint16_t, false>), grid, blk, P->lds3_bytes, P->stream, A); }
-  else { if (cen) SPIN_LAUNCH((k_sweep3<int32_t, true>), grid, blk, P->lds3_bytes, P->stream, A); else SPIN_LAUNCH((k_sweep3<int32_t, false>), grid, blk, P->lds3_bytes, P->stream, A); }
-  if (cen && !SWEEP_DRY) hipLaunchKernelGGL(k_cen_end, dim3(64), dim3(256), 0, P->stream, a, 0);
-  if (A.skip_vb && !SWEEP_DRY) {   // (every launch: idempotent -- after a range redo the fp64 engine has written the same values from the same expression)
-    const int j0 = a.blk_begin * a.m, j1 = (int)std::min<int64_t>(P->p, (int64_t)a.blk_end * a.m);
-    hipLaunchKernelGGL(k_vb_fill, dim3((unsigned)std::min<int64_t>(1024, (j1 - j0 + 255) / 256)), dim3(256), 0, P->stream, a, j0, j1);
-  }
-}
-
-// The selection models' sweeps on a panel that has k_sweep3: the device picks the engine from the chain's current inclusion
-// rate (ChainScalars::inc_rate against the panel's threshold), so both engines' kernels are enqueued and one side leaves at once
-// (a few microseconds per iteration); a threshold >= 1 means k_sweep3 always and the other side is not enqueued at all.
-static float sweep3_gate(const bwgr_panel *P, int flags) {
-  if (!use_sweep3(P, flags)) return 0.0f;
-  return (P->eng3_thr >= 1.0f || P->force3) ? INFINITY : P->eng3_thr;
-}
-
 // The affine sweeps of an int8 panel with 16-bit Gram staging run k_sweep2w: the block solve as a product with the inverse
 // k_affine_inv forms before the sweep (sweep2w.hip.h).
-static bool use_winv(const bwgr_panel *P, int flags) {
-  if (!P->winv_on || P->sweep_version < 2 || P->is_f32 || !P->gramp || P->winv_nd < 1 || P->K > 2 * (S2W_QW + S2W_QX)) return false;
-  if (flags & (SWF_SELECT | SWF_EM_ANY | SWF_SERIAL)) return false;
-  return P->ldsw_bytes > 0 && P->ldsw_bytes <= (size_t)160 * 1024;
-}
-// ... with its own streamers (s2w_streamer_fx: 128 rows each, fixed-point residual) where the slab count allows
-static bool use_wfx(const bwgr_panel *P) { return P->wfx_on && (P->R % S2W_FXR) == 0 && P->K * (P->R / S2W_FXR) <= 255; }
 static int winv_alloc(bwgr_panel *P) {
   if (P->winv) return BWGR_OK;
   HIPCHK(hipMalloc(&P->winv, sizeof(double) * (size_t)S2W_WDOUBLES * (size_t)P->nblocks));
@@ -1352,19 +1326,19 @@ static int winv_alloc(bwgr_panel *P) {
   return BWGR_OK;
 }
 
-static void launch_prestage(bwgr_panel *P, const SweepArgs &a_in) {
+static void launch_prestage(bwgr_panel *P, const SweepArgs &a_in, const SweepPlan &pl) {
   SweepArgs a = a_in;
-  a.gate3 = sweep3_gate(P, a.flags);
+  a.gate3 = pl.gate3;
   const int j0 = a.blk_begin * a.m, j1 = (int)std::min<int64_t>(P->p, (int64_t)a.blk_end * a.m);
   const int64_t tasks = 4ll * (j1 - j0);
   const bool s3 = a.gate3 > 0.0f;
-  const bool fxa = !s3 && use_winv(P, a.flags) && P->winv && use_wfx(P);   // an affine sweep on the fixed-point streamers
-  int sh_add = 0;
-  if (const char *dv = getenv("BWGR_DEBUG_SH_ADD")) sh_add = atoi(dv);   // test hook: less headroom, to leave the range on purpose
+  const bool fxa = pl.engine == 4 && pl.fx;   // an affine sweep on the fixed-point streamers
+  const int sh_add = P->sw.sh_add;   // test hook: less headroom, to leave the range on purpose
+  int xbits = 0; while ((1 << xbits) < std::max(1, (P->parent ? P->parent : P)->xmax)) ++xbits;   // (the fixed-point scales: the residual, and what k_prestage knows of the steps times the largest |x|)
   if (s3 || fxa) hipLaunchKernelGGL(k_escale_reset, dim3(1), dim3(1), 0, P->stream, a.sc);
   // the variates drawn ahead (draws_ahead, below) when they are this very iteration's: same streams, same counters, same flags, this range inside theirs
   const int dflags = a.flags & (SWF_SELECT | SWF_VB_VEC);
-  const bool have_draws = !SWEEP_DRY && P->draws_valid && P->draws_iter == a.iter && P->draws_marker0 == a.marker0 && P->draws_flags == dflags &&
+  const bool have_draws = P->draws_valid && P->draws_iter == a.iter && P->draws_marker0 == a.marker0 && P->draws_flags == dflags &&
                           P->draws_sc == (const void *)a.sc && P->draws_j0 <= j0 && P->draws_j1 >= j1 && memcmp(&P->draws_rng, &a.rng, sizeof(Rng)) == 0 &&
                           !(a.flags & (SWF_MH | SWF_EM_ANY));
   a.draws = nullptr;
@@ -1375,7 +1349,6 @@ static void launch_prestage(bwgr_panel *P, const SweepArgs &a_in) {
     P->draws_valid = false;   // (consumed: the buffer is the next iteration's from here)
   } else hipLaunchKernelGGL(k_prestage, dim3((unsigned)std::min<int64_t>(4096, (tasks + 255) / 256)), dim3(256), 0, P->stream, a, j0, j1);
   if (s3) {   // the sweep's fixed-point scale, then the in-block speculative terms on that grid
-    int xbits = 0; while ((1 << xbits) < std::max(1, (P->parent ? P->parent : P)->xmax)) ++xbits;
     hipLaunchKernelGGL(k_escale, dim3(1), dim3(1024), 0, P->stream, a.e, P->ld, a.sc, xbits, a.gate3, sh_add);
     if (a.flags & SWF_CENTRE) {   // the rejected steps' share of sum(e_stored), block by block (the whole panel: launch_prestage is called with every block)
       hipLaunchKernelGGL(k_cen_tot, dim3((unsigned)(a.blk_end - a.blk_begin)), dim3(128), 0, P->stream, a, a.blk_begin, 0);
@@ -1385,11 +1358,8 @@ static void launch_prestage(bwgr_panel *P, const SweepArgs &a_in) {
       hipLaunchKernelGGL(k_spec3, dim3((unsigned)(a.blk_end - a.blk_begin)), dim3(128), 0, P->stream, a, a.blk_begin, root->gram16 ? (const uint16_t *)root->gramp16 : (const uint16_t *)nullptr); }
     if (std::isinf(a.gate3)) return;
   }
-  if (use_winv(P, a.flags) && P->winv) {
-    if (use_wfx(P)) {   // the sweep's fixed-point scale: the residual, and what k_prestage knows of the steps (|b0|, the noise terms) times the largest |x|
-      int xbits = 0; while ((1 << xbits) < std::max(1, (P->parent ? P->parent : P)->xmax)) ++xbits;
-      hipLaunchKernelGGL(k_escale, dim3(1), dim3(1024), 0, P->stream, a.e, P->ld, a.sc, xbits, INFINITY, sh_add);
-    }
+  if (pl.engine == 4) {
+    if (pl.fx) hipLaunchKernelGGL(k_escale, dim3(1), dim3(1024), 0, P->stream, a.e, P->ld, a.sc, xbits, INFINITY, sh_add);   // (|b0|, the noise terms)
     hipLaunchKernelGGL(k_affine_inv, dim3((unsigned)(a.blk_end - a.blk_begin)), dim3(512), S2W_INV_LDS, P->stream, a, P->winv, (a.flags & SWF_DELTA2) ? 2.0 : 1.0);
     return;
   }
@@ -1405,16 +1375,10 @@ static void launch_prestage(bwgr_panel *P, const SweepArgs &a_in) {
   }
 }
 
-// The next iteration's variates, enqueued beside this iteration's sweep (see k_draws).  `a` = this iteration's arguments over the whole panel.  Selection
-// models with the logistic step on panels whose sweeps leave most of the chip idle; BWGR_DRAWS=0 switches it off.  Failing to set it up is not an error:
-// k_prestage draws for itself whenever the buffer is not this iteration's.
-static void draws_ahead(bwgr_panel *P, const SweepArgs &a, hipEvent_t before_sweep) {
-  if (SWEEP_DRY || !(a.flags & SWF_SELECT) || (a.flags & (SWF_MH | SWF_EM_ANY))) return;
-  // only for a chain that has the GPU to itself (as the 128-row streamers and the prefetcher workgroups): beside other chains or shards the idle
-  // compute units it would run on are theirs (five chains side by side 255 -> 226 chain-iter/s, three shards 163 -> 119 iter/s with it)
-  if (!(P->solo3 && !P->parent && P->nclones == 0)) return;
-  static const bool off = [] { const char *v = getenv("BWGR_DRAWS"); return v && v[0] == '0'; }();
-  if (off) return;
+// The next iteration's variates, enqueued beside this iteration's sweep (see k_draws) where the plan says so.  `a` = this iteration's arguments
+// over the whole panel.  Failing to set it up is not an error: k_prestage draws for itself whenever the buffer is not this iteration's.
+static void draws_ahead(bwgr_panel *P, const SweepArgs &a, const SweepPlan &pl, hipEvent_t before_sweep) {
+  if (!pl.draws) return;
   if (!P->draws) {
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);   // (lo: the numerically largest = the lowest priority)
@@ -1440,138 +1404,211 @@ static void draws_ahead(bwgr_panel *P, const SweepArgs &a, hipEvent_t before_swe
   P->draws_j0 = j0; P->draws_j1 = j1; P->draws_sc = (const void *)a.sc;
 }
 
-static void launch_sweep_kernel_inner(bwgr_panel *P, const SweepArgs &a_in, bool redo);
-// The fixed-point engines between a snapshot of the state they start from and the fp64 engine that redoes the sweep if they left
-// their range (the reference's update cannot fail, src/Rcpp20260726ai.cpp:681).  Off for the debug abort hook (its launches must time out).
-static bool range_snapshot(bwgr_panel *P, const SweepArgs &a, SnapArgs &sn) {
-  if (SWEEP_DRY) return true;
-  const size_t p = (size_t)P->p;
-  if (!P->snap_e) {
-    if (hipMalloc(&P->snap_e, sizeof(double) * (size_t)P->ld) != hipSuccess || hipMalloc(&P->snap_b, sizeof(float) * p) != hipSuccess ||
-        hipMalloc(&P->snap_d, sizeof(float) * p) != hipSuccess || hipMalloc(&P->snap_vb, sizeof(float) * p) != hipSuccess) { (void)hipGetLastError(); return false; }
-  }
-  sn.e = a.e; sn.se = P->snap_e; sn.b = a.b; sn.d = a.d; sn.vb = (a.flags & SWF_VB_VEC) ? a.vb : nullptr; sn.sb = P->snap_b; sn.sd = P->snap_d; sn.svb = P->snap_vb;
-  sn.ld = P->ld; sn.j0 = a.blk_begin * a.m; sn.j1 = (int)std::min<int64_t>(P->p, (int64_t)a.blk_end * a.m); sn.sc = a.sc;
-  hipLaunchKernelGGL(k_range_snapshot, dim3(256), dim3(256), 0, P->stream, sn);
-  return true;
-}
-static void launch_sweep_kernel(bwgr_panel *P, const SweepArgs &a_in) {
-  SweepArgs a = a_in;
-  a.gate3 = sweep3_gate(P, a.flags);
-  const bool fx = (a.gate3 > 0.0f) || (use_winv(P, a.flags) && P->winv && use_wfx(P));
-  SnapArgs sn;
-#ifdef BWGR_EXPERIMENTS
-  static const bool no_recover = getenv("BWGR_NO_RECOVER") != nullptr;   // (timing experiments that break the chain on purpose: the experiment build only)
-#else
-  constexpr bool no_recover = false;
-#endif
-  const bool guarded = fx && !P->debug_withhold && !no_recover && range_snapshot(P, a, sn);
-  launch_sweep_kernel_inner(P, a_in, false);
-  if (guarded) {
-    if (!SWEEP_DRY) {
-      hipLaunchKernelGGL(k_range_recover, dim3(256), dim3(256), 0, P->stream, sn);
-      hipLaunchKernelGGL(k_range_flag, dim3(1), dim3(1), 0, P->stream, a.sc);
-    }
-    (void)reset_exchange(P);
-    launch_sweep_kernel_inner(P, a_in, true);
-    if (!SWEEP_DRY) hipLaunchKernelGGL(k_redo_clear, dim3(1), dim3(1), 0, P->stream, a.sc);
-  }
-}
-static void launch_sweep_kernel_inner(bwgr_panel *P, const SweepArgs &a_in, bool redo) {
-  SweepArgs a = a_in;
-  if (P->debug_withhold) a.flags |= SWF_DEBUG_WITHHOLD;
-  a.gate3 = redo ? 0.0f : sweep3_gate(P, a.flags);
-  a.redo_only = redo ? 1 : 0;
-  if (redo && P->sweep_version >= 2 && !use_winv(P, a.flags)) {   // the fp64 engine's speculative terms (k_spec) of the state just restored
-    const int sel = (a.flags & SWF_SELECT) ? 1 : 0;
-    if (!SWEEP_DRY && (a.flags & SWF_CENTRE) && sel) {   // the running block sums on the float steps (the fixed-point launch left them on its grid): every block, then the scan
-      SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->nblocks;
-      hipLaunchKernelGGL(k_cen_tot, dim3((unsigned)P->nblocks), dim3(128), 0, P->stream, all, 0, 2);
-      hipLaunchKernelGGL(k_cen_scan, dim3(1), dim3(1024), 0, P->stream, all, (int)P->nblocks, 2);
-    }
-    if (!SWEEP_DRY) hipLaunchKernelGGL(k_spec<int32_t>, dim3((unsigned)(a.blk_end - a.blk_begin)), dim3(128), 0, P->stream, a, a.blk_begin, sel);
-  }
-  if (a.gate3 > 0.0f) { launch_sweep3(P, a); if (std::isinf(a.gate3)) return; }
-  const bool sel = (a.flags & SWF_SELECT) != 0;
-  // streamers, sequencer, and for the selection models the q feeders (the affine recurrence is compute-bound: its
-  // sequencer gathers q itself under the recurrence, and a feeder hop in its lag-2 chain measured 15 % slower)
-  a.nfeed = (P->sweep_version >= 2 && sel) ? P->nfeed : 0;
-  if (use_winv(P, a.flags) && P->winv) {
-    S2WArgs A;
-    memset(&A, 0, sizeof(A));
-    A.winv = P->winv;
-    A.fx = (use_wfx(P) && !redo) ? 1 : 0;
-    if (!A.fx) a.lag = std::min(a.lag, 4);   // (k_sweep2's streamers -- the range-recovery launch, BWGR_WFX=0 -- hold four tiles)
-    A.nd = std::min(a.lag - 1, (int)S2W_MAXDIST);
-#ifdef BWGR_EXPERIMENTS
-    if (const char *dv = getenv("BWGR_DBGW")) A.dbg = atoi(dv);
-#endif
-    for (int d = 0; d < S2W_MAXDIST; ++d) A.gxt[d] = P->gxt[d < P->winv_nd ? d : 0];
-    A.npf = P->wpf;      // measured at C2: 0 -> 540, 2 -> 636, 4 -> 685 iter/s (6 and 8 no better)
-    A.ahead = P->wahead;
-    A.qsum = P->qsumw; A.sub = P->R / S2W_FXR; A.K3 = P->K * A.sub;
-    A.nq = P->wnq ? P->wnq : (A.K3 > 48 ? 2 : 1);   // (C2, 40 streamers: one copy 1.10 ms, two 1.21; C4 shape, 80 streamers: 27.8 / 25.6 / 27.6 ms with 1 / 2 / 4)
-    if (A.fx && !SWEEP_DRY) (void)hipMemsetAsync(P->qsumw + (size_t)a.blk_begin * A.nq * 2 * SW_MAXM, 0, sizeof(unsigned long long) * A.nq * 2 * SW_MAXM * (size_t)(a.blk_end - a.blk_begin), P->stream);
-    // (of the 8 npf workgroups past the sequencer, the npf on its XCD prefetch; the others leave at once)
-    if (A.fx) SPIN_LAUNCH_N(A.K3 + 1 + A.npf, k_sweep2w<true>, dim3(A.K3 + 1 + 8 * A.npf), dim3(S2W_THREADS), P->ldsw_bytes, P->stream, a, A);
-    else SPIN_LAUNCH_N(P->K + 1 + A.npf, k_sweep2w<false>, dim3(P->K + 1 + 8 * A.npf), dim3(S2W_THREADS), P->ldsw_bytes, P->stream, a, A);
-    return;
-  }
-  if (P->sweep_version >= 2) {
-    const dim3 grid(P->K + 1 + a.nfeed), blk(SW_THREADS);
-    const bool cen2 = (a.flags & SWF_CENTRE) && sel && !P->is_f32 && !SWEEP_DRY;
-    struct CenEnd { bool on; hipStream_t st; SweepArgs a; int mode; ~CenEnd() { if (on) hipLaunchKernelGGL(k_cen_end, dim3(64), dim3(256), 0, st, a, mode); } } cen_end{cen2, P->stream, a, redo ? 2 : 1};
-    if (cen2) hipLaunchKernelGGL(k_cen_begin, dim3(1), dim3(1024), 0, P->stream, a, redo ? 2 : 1);
-    if (P->is_f32) {
-      if (sel) SPIN_LAUNCH((k_sweep2<float, true>), grid, blk, P->lds2_bytes, P->stream, a);
-      else SPIN_LAUNCH((k_sweep2<float, false>), grid, blk, P->lds2_bytes, P->stream, a);
-    } else {
-      if (P->gram16 && sel) {   // selection models: 16-bit staging and the single-barrier sequencer (the affine recurrence is
-                                // compute-bound and measured faster on the 32-bit blocks: no conversion in its inner loop)
-        SweepArgs a16 = a;
-        a16.gramp = P->gramp16; a16.gramx = P->gramx16;
-        SPIN_LAUNCH((k_sweep2<int8_t, true, uint16_t>), grid, blk, P->lds2_bytes, P->stream, a16);
-      } else if (sel) SPIN_LAUNCH((k_sweep2<int8_t, true>), grid, blk, P->lds2_bytes, P->stream, a);
-      else SPIN_LAUNCH((k_sweep2<int8_t, false>), grid, blk, P->lds2_bytes, P->stream, a);
-    }
-    return;
-  }
-  if (P->is_f32) {
-    if (sel) SPIN_LAUNCH((k_sweep<float, true>), dim3(P->K), dim3(SW_THREADS), P->lds_bytes, P->stream, a);
-    else SPIN_LAUNCH((k_sweep<float, false>), dim3(P->K), dim3(SW_THREADS), P->lds_bytes, P->stream, a);
-  } else {
-    if (sel) SPIN_LAUNCH((k_sweep<int8_t, true>), dim3(P->K), dim3(SW_THREADS), P->lds_bytes, P->stream, a);
-    else SPIN_LAUNCH((k_sweep<int8_t, false>), dim3(P->K), dim3(SW_THREADS), P->lds_bytes, P->stream, a);
-  }
-}
-
-// selection models run the deeper pipelines (their cross terms are sparse)
-static bool use_winv(const bwgr_panel *P, int flags);
-static void choose_lag(const bwgr_panel *P, SweepArgs &a) {
-  const char *lv = getenv("BWGR_LAG");
+// The plan of one sweep of blocks [a.blk_begin, a.blk_end) with a.flags over P (redo: the fp64 launch that redoes a fixed-point sweep
+// which left its range).  Reads the panel only: nothing is enqueued or allocated.
+static SweepPlan plan_sweep(const bwgr_panel *P, const SweepArgs &a, bool redo) {
+  SweepPlan pl;
+  const Switches &sw = P->sw;
+  const bwgr_panel *root = P->parent ? P->parent : P;
+  const bool sel = (a.flags & SWF_SELECT) != 0, cen = (a.flags & SWF_CENTRE) != 0;
+  const auto spin = [&](const void *fn, int grid, int resident, int threads, size_t lds) { pl.spins[pl.nspins++] = SpinLaunch{fn, grid, resident, threads, lds}; };
+  // The selection models' sweeps on a panel that has k_sweep3: the device picks the engine from the chain's current inclusion rate
+  // (ChainScalars::inc_rate against the panel's threshold), so both engines' kernels are enqueued and one side leaves at once (a few
+  // microseconds per iteration); a threshold >= 1, or a pair run, means k_sweep3 always and the other side is not enqueued at all.
+  if (P->e3_ready && sel && !(a.flags & SWF_EM_ANY) && !redo) pl.gate3 = (sw.eng3_thr >= 1.0f || P->force3) ? INFINITY : sw.eng3_thr;
+  // The affine sweeps of an int8 panel with 16-bit Gram staging: k_sweep2w, with its own streamers (s2w_streamer_fx: 128 rows each,
+  // fixed-point residual) where the slab count allows
+  const bool winv = sw.winv && P->sweep_version >= 2 && !P->is_f32 && P->gramp && P->winv_nd >= 1 && P->K <= 2 * (S2W_QW + S2W_QX) &&
+                    !(a.flags & (SWF_SELECT | SWF_EM_ANY | SWF_SERIAL)) && P->ldsw_bytes > 0 && P->ldsw_bytes <= (size_t)160 * 1024;
+  const bool wfx = sw.wfx && (P->R % S2W_FXR) == 0 && P->K * (P->R / S2W_FXR) <= 255;
+  pl.engine = pl.gate3 > 0.0f ? 3 : winv ? 4 : std::min(P->sweep_version, 2);
   // Selection sweeps of k_sweep2: three blocks deep.  (The single-barrier sequencer also knows a fourth level, BWGR_LAG=4: it was
   // the default while k_sweep2 also ran the sparse chains; those are k_sweep3's now, and from 5 % of the markers in the model upwards
   // the third cross term's row fetches cost more than the depth gives -- C4-size BayesC at 5 / 19 / 36 % inclusion: 31.4 / 21.3 /
   // 14.5 iter/s at depth 3 against 30.9 / 19.4 / 9.4 at depth 4; BayesCpi at 51 %: 11.1 against 6.7.)  BWGR_LAG=2|3|4 sets it (A/B tests).
-  const int cap = (lv && lv[0] >= '2' && lv[0] <= '4') ? lv[0] - '0' : 3;
   int lag = 2;
-  if (P->sweep_version >= 2 && (a.flags & SWF_SELECT)) {
+  if (P->sweep_version >= 2 && sel) {
     // the generic sequencer (32-bit Gram entries, fp32 panels) reads a distance-2 row per accepted marker straight from global memory on
     // one wave: two blocks deep unless asked (us per block at n = 10 000, depth 2 / 3: 1.4 % inclusion 4.53 / 4.67, 10.9 % 5.29 / 14.5,
     // BayesCpi at 52 % 12.7 / 58.0); the 16-bit / single-barrier sequencer stages those rows and knows a third cross term as well
-    if (P->gramx2 && lv) lag = 3;
+    if (P->gramx2 && sw.lag >= 0) lag = 3;
     if (!P->is_f32 && P->gramx2 && P->gram16) lag = 3;
     if (!P->is_f32 && P->gramx3 && P->gram16 && P->lag4_ok) lag = 4;
   }
-  a.lag = lag < cap ? lag : cap;
-  if (use_winv(P, a.flags)) {   // the affine sweeps' product sequencer: as deep as the panel's cross Gram planes reach (BWGR_WLAG caps it)
-    a.lag = std::min(P->winv_nd + 1, P->wlag_cap);
-    if (!use_wfx(P)) a.lag = std::min(a.lag, 4);   // (k_sweep2's streamers hold four tiles)
+  pl.lag = std::min(lag, (sw.lag >= '2' && sw.lag <= '4') ? sw.lag - '0' : 3);
+  if (winv) {   // the affine sweeps' product sequencer: as deep as the panel's cross Gram planes reach (BWGR_WLAG caps it)
+    pl.lag = std::min(P->winv_nd + 1, sw.wlag_cap);
+    if (!wfx) pl.lag = std::min(pl.lag, 4);   // (k_sweep2's streamers hold four tiles)
 #ifdef BWGR_EXPERIMENTS
-    if (const char *tl = getenv("BWGR_WLAG_TIMING")) a.lag = atoi(tl);   // TIMING ONLY: deeper than the cross terms reach (wrong chain)
+    if (sw.wlag_timing) pl.lag = sw.wlag_timing;   // TIMING ONLY: deeper than the cross terms reach (wrong chain)
 #endif
   }
+  // streamers, sequencer, and for the selection models the q feeders (the affine recurrence is compute-bound: its
+  // sequencer gathers q itself under the recurrence, and a feeder hop in its lag-2 chain measured 15 % slower)
+  pl.nfeed = (P->sweep_version >= 2 && sel) ? P->nfeed : 0;
+  // selection models: 16-bit staging and the single-barrier sequencer (the affine recurrence is compute-bound and measured faster on
+  // the 32-bit blocks: no conversion in its inner loop)
+  pl.g16 = P->sweep_version >= 2 && !P->is_f32 && P->gram16 && sel;
+  // A chain that has the GPU to itself (a root panel without clones) runs 128-row streamers, two to a slab: 80 compute units instead
+  // of 41, 15.98-16.18 against 16.49 ms per sweep at C4 (the same chain bit for bit: the slab dots are integer sums).  With clones
+  // alive -- chains side by side, pairs -- every chain keeps the 256-row streamers the concurrency counts assume.  BWGR_SOLO3=0: never.
+  const bool alone = P->solo3 && !P->parent && P->nclones == 0;
+  // The next iteration's variates beside the sweep (draws_ahead): selection models with the logistic step, only for a chain alone (beside
+  // other chains or shards the idle compute units it would run on are theirs: five chains side by side 255 -> 226 chain-iter/s, three
+  // shards 163 -> 119 iter/s with it); BWGR_DRAWS=0 switches it off
+  pl.draws = sel && !(a.flags & (SWF_MH | SWF_EM_ANY)) && alone && sw.draws;
+  if (pl.gate3 > 0.0f) {
+    pl.R3 = P->R3; pl.sub = P->sub3; pl.K3 = P->K3;
+#ifdef BWGR_EXPERIMENTS
+    pl.dbg3 = sw.dbg3;   // (timing switches, some of which break the chain: the experiment build only)
+#endif
+    {   // 128-row streamers land their tiles by LDS-DMA (s3_streamer_dma; C4 15.0 -> 13.65 ms per sweep); BWGR_STREAM3=reg: through registers, as the 256-row ones do
+      // The DMA streamer forms a tile piece's source as a 32-bit lane offset from the launch's first column (no 64-bit vector arithmetic): only
+      // launches whose column range spans less than 4 GiB of one slab take it (p * R < 2^32: 16.7 M markers at R = 256); wider ones keep the
+      // register path, whose offsets are size_t.  bwgr_debug_stream3_dma() exposes the rule to the CPU tests.
+      const int64_t j_lo = (int64_t)a.blk_begin * a.m, j_hi = std::min<int64_t>(P->p, (int64_t)a.blk_end * a.m);
+      const bool fits32 = stream3_dma_fits(j_hi - j_lo, P->R);
+      if (sw.stream3 != 'r' && fits32) pl.dbg3 |= (1 << 22);
+      if (sw.stream3 == 'd' && fits32) pl.dbg3 |= (1 << 23);   // (EXPERIMENT: the 256-row streamers too, three tile buffers)
+    }
+    if (P->force3) {   // a pair run (bwgr_chain_run_pair): one k_sweep3p launch, K3 streamers and two sequencers, serves both chains; no redo
+      const size_t lds = std::max(s3p_streamer_lds(pl.R3), s3_seq_lds(P->e3_D, root->gram16));
+      spin(root->gram16 ? reinterpret_cast<const void *>(k_sweep3p<uint16_t>) : reinterpret_cast<const void *>(k_sweep3p<int32_t>), pl.K3 + 2, pl.K3 + 2, SW_THREADS, lds);
+      return pl;
+    }
+    if (alone && pl.R3 == 256 && 2 * pl.K3 + 1 <= 256) { pl.R3 = 128; pl.sub = P->R / 128; pl.K3 = P->K * pl.sub; }
+    // one more workgroup, on the sequencer's XCD (workgroups with equal index mod 8 share an XCD), warms that XCD's L2 with what the
+    // staging waves load (on for a chain alone on the GPU: 15.61 -> 15.37 ms per sweep at C4 on the steadied kernel; beside other chains
+    // the workgroup is not counted by bwgr_panel_max_concurrent, so it stays off there; BWGR_PF3=0|1 decides otherwise)
+    const bool pf_on = (sw.pf3 >= 0 ? sw.pf3 == '1' : alone) && pl.K3 + 2 <= 256;
+    pl.pf = pf_on ? ((pl.K3 + 2 > 8) ? 8 : pl.K3 + 1) : -1;
+    const bool pf2_on = pf_on && pl.pf == 8 && root->gram16 && root->gx12 && pl.K3 + 3 > 16 && pl.K3 + 3 <= 256 && sw.pf3b;
+    pl.pf2 = pf2_on ? 16 : -1; pl.qsplit = 1; pl.skip_vb = (a.flags & SWF_VB_VEC) ? 1 : 0;
+    const int grid = pl.K3 + 1 + (pf_on ? 1 : 0) + (pf2_on ? 1 : 0);
+    const void *fn = root->gram16 ? (cen ? reinterpret_cast<const void *>(k_sweep3<uint16_t, true>) : reinterpret_cast<const void *>(k_sweep3<uint16_t, false>))
+                                  : (cen ? reinterpret_cast<const void *>(k_sweep3<int32_t, true>) : reinterpret_cast<const void *>(k_sweep3<int32_t, false>));
+    spin(fn, grid, grid, SW_THREADS, P->lds3_bytes);
+  }
+  if (!std::isinf(pl.gate3)) {
+    if (winv) {
+      pl.fx = (wfx && !redo) ? 1 : 0;
+      if (!pl.fx) pl.lag = std::min(pl.lag, 4);   // (k_sweep2's streamers -- the range-recovery launch, BWGR_WFX=0 -- hold four tiles)
+      pl.nd = std::min(pl.lag - 1, (int)S2W_MAXDIST);
+      pl.npf = sw.wpf; pl.ahead = sw.wahead;   // (npf measured at C2: 0 -> 540, 2 -> 636, 4 -> 685 iter/s; 6 and 8 no better)
+      pl.wsub = P->R / S2W_FXR; pl.wK3 = P->K * pl.wsub;
+      pl.nq = sw.wnq ? sw.wnq : (pl.wK3 > 48 ? 2 : 1);   // (C2, 40 streamers: one copy 1.10 ms, two 1.21; C4 shape, 80 streamers: 27.8 / 25.6 / 27.6 ms with 1 / 2 / 4)
+      // (of the 8 npf workgroups past the sequencer, the npf on its XCD prefetch; the others leave at once)
+      const int wgs = pl.fx ? pl.wK3 : P->K;
+      spin(pl.fx ? reinterpret_cast<const void *>(k_sweep2w<true>) : reinterpret_cast<const void *>(k_sweep2w<false>), wgs + 1 + 8 * pl.npf, wgs + 1 + pl.npf, S2W_THREADS, P->ldsw_bytes);
+    } else if (P->sweep_version >= 2) {
+      const void *fn = P->is_f32 ? (sel ? reinterpret_cast<const void *>(k_sweep2<float, true>) : reinterpret_cast<const void *>(k_sweep2<float, false>))
+                       : pl.g16  ? reinterpret_cast<const void *>(k_sweep2<int8_t, true, uint16_t>)
+                       : sel     ? reinterpret_cast<const void *>(k_sweep2<int8_t, true>) : reinterpret_cast<const void *>(k_sweep2<int8_t, false>);
+      spin(fn, P->K + 1 + pl.nfeed, P->K + 1 + pl.nfeed, SW_THREADS, P->lds2_bytes);
+    } else {
+      const void *fn = P->is_f32 ? (sel ? reinterpret_cast<const void *>(k_sweep<float, true>) : reinterpret_cast<const void *>(k_sweep<float, false>))
+                                 : (sel ? reinterpret_cast<const void *>(k_sweep<int8_t, true>) : reinterpret_cast<const void *>(k_sweep<int8_t, false>));
+      spin(fn, P->K, P->K, SW_THREADS, P->lds_bytes);
+    }
+  }
+  // The fixed-point engines between a snapshot of the state they start from and the fp64 engine that redoes the sweep if they left
+  // their range (the reference's update cannot fail, src/Rcpp20260726ai.cpp:681).  Off for the debug abort hook (its launches must time out).
+#ifdef BWGR_EXPERIMENTS
+  const bool no_recover = sw.no_recover;   // (timing experiments that break the chain on purpose: the experiment build only)
+#else
+  constexpr bool no_recover = false;
+#endif
+  if (!redo && (pl.gate3 > 0.0f || (winv && wfx)) && !P->debug_withhold && !no_recover) {
+    const SweepPlan r = plan_sweep(P, a, true);
+    for (int i = 0; i < r.nspins; ++i) pl.spins[pl.nspins++] = r.spins[i];
+    pl.guarded = true;
+  }
+  return pl;
 }
+
+// what one launch of k_sweep3 / k_sweep3p needs beside the sweep's own arguments; zeroes the launch's slab-dot sums, takes a new epoch
+static void sweep3_args(bwgr_panel *P, const SweepArgs &a, const SweepPlan &pl, Sweep3Args &A) {
+  memset(&A, 0, sizeof(A)); A.a = a;
+  const bwgr_panel *root = P->parent ? P->parent : P;
+  for (int d = 0; d < S3_MAXD; ++d) A.gx[d] = root->g3x[d];
+  A.gp = root->gram16 ? (const void *)root->gramp16 : root->gramp;
+  A.D = P->e3_D; A.K3 = pl.K3; A.R3 = pl.R3; A.sub = pl.sub; A.g16 = root->gram16 ? 1 : 0;
+  A.qsum = P->qsum3; A.lists = P->lists3;
+  A.gx12 = root->gram16 ? root->gx12 : nullptr;
+  A.dbg = pl.dbg3; A.pf = pl.pf; A.pf2 = pl.pf2; A.qsplit = pl.qsplit; A.skip_vb = pl.skip_vb;
+  P->epoch3 = (P->epoch3 + 1) & 0xFFFFFFu; if (P->epoch3 == 0) P->epoch3 = 1;
+  A.epoch = P->epoch3;
+  (void)hipMemsetAsync(P->qsum3 + (size_t)a.blk_begin * 2 * SW_MAXM, 0, sizeof(unsigned long long) * 2 * SW_MAXM * (size_t)(a.blk_end - a.blk_begin), P->stream);
+}
+// one engine's launch of the plan (redo: the fp64 launch behind a fixed-point one that left its range)
+static void launch_sweep_engine(bwgr_panel *P, const SweepArgs &a_in, const SweepPlan &pl, bool redo) {
+  SweepArgs a = a_in;
+  if (P->debug_withhold) a.flags |= SWF_DEBUG_WITHHOLD;
+  a.gate3 = pl.gate3; a.redo_only = redo ? 1 : 0;
+  const bool sel = (a.flags & SWF_SELECT) != 0;
+  if (redo && pl.engine == 2) {   // the fp64 engine's speculative terms (k_spec) of the state just restored
+    if ((a.flags & SWF_CENTRE) && sel) {   // the running block sums on the float steps (the fixed-point launch left them on its grid): every block, then the scan
+      SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->nblocks;
+      hipLaunchKernelGGL(k_cen_tot, dim3((unsigned)P->nblocks), dim3(128), 0, P->stream, all, 0, 2);
+      hipLaunchKernelGGL(k_cen_scan, dim3(1), dim3(1024), 0, P->stream, all, (int)P->nblocks, 2);
+    }
+    hipLaunchKernelGGL(k_spec<int32_t>, dim3((unsigned)(a.blk_end - a.blk_begin)), dim3(128), 0, P->stream, a, a.blk_begin, sel ? 1 : 0);
+  }
+  if (a.gate3 > 0.0f) {   // k_sweep3 (for the implicitly centred columns between its scalar terms' kernels), then the per-marker variances
+    Sweep3Args A3;
+    sweep3_args(P, a, pl, A3);
+    const bool cen = (a.flags & SWF_CENTRE) != 0;
+    if (cen) hipLaunchKernelGGL(k_cen_begin, dim3(1), dim3(1024), 0, P->stream, a, 0);
+    void *args[] = {&A3};
+    spin_launch(pl.spins[0], P->stream, args);
+    if (cen) hipLaunchKernelGGL(k_cen_end, dim3(64), dim3(256), 0, P->stream, a, 0);
+    if (pl.skip_vb) {   // (every launch: idempotent -- after a range redo the fp64 engine has written the same values from the same expression)
+      const int j0 = a.blk_begin * a.m, j1 = (int)std::min<int64_t>(P->p, (int64_t)a.blk_end * a.m);
+      hipLaunchKernelGGL(k_vb_fill, dim3((unsigned)std::min<int64_t>(1024, (j1 - j0 + 255) / 256)), dim3(256), 0, P->stream, a, j0, j1);
+    }
+    if (std::isinf(a.gate3)) return;
+  }
+  const SpinLaunch &L = pl.spins[a.gate3 > 0.0f ? 1 : 0];
+  a.nfeed = pl.nfeed; a.lag = pl.lag;
+  if (pl.engine == 4) {
+    S2WArgs A; memset(&A, 0, sizeof(A));
+    A.winv = P->winv; A.qsum = P->qsumw; A.fx = pl.fx; A.nd = pl.nd; A.npf = pl.npf; A.ahead = pl.ahead; A.sub = pl.wsub; A.K3 = pl.wK3; A.nq = pl.nq;
+#ifdef BWGR_EXPERIMENTS
+    A.dbg = P->sw.dbgw;
+#endif
+    for (int d = 0; d < S2W_MAXDIST; ++d) A.gxt[d] = P->gxt[d < P->winv_nd ? d : 0];
+    if (A.fx) (void)hipMemsetAsync(P->qsumw + (size_t)a.blk_begin * A.nq * 2 * SW_MAXM, 0, sizeof(unsigned long long) * A.nq * 2 * SW_MAXM * (size_t)(a.blk_end - a.blk_begin), P->stream);
+    void *args[] = {&a, &A}; spin_launch(L, P->stream, args);
+    return;
+  }
+  const bool cen2 = P->sweep_version >= 2 && (a.flags & SWF_CENTRE) && sel && !P->is_f32;
+  if (cen2) hipLaunchKernelGGL(k_cen_begin, dim3(1), dim3(1024), 0, P->stream, a, redo ? 2 : 1);
+  SweepArgs ak = a;
+  if (pl.g16) { ak.gramp = P->gramp16; ak.gramx = P->gramx16; }
+  void *args[] = {&ak}; spin_launch(L, P->stream, args);
+  if (cen2) hipLaunchKernelGGL(k_cen_end, dim3(64), dim3(256), 0, P->stream, a, redo ? 2 : 1);
+}
+// the plan's sweep: the fixed-point engines between a snapshot of the state they start from and the fp64 redo (plan_sweep); no redo
+// when the snapshot's scratch cannot be had
+static void launch_sweep_kernel(bwgr_panel *P, const SweepArgs &a, const SweepPlan &pl) {
+  const size_t p = (size_t)P->p;
+  bool guarded = pl.guarded;
+  if (guarded && !P->snap_e && (hipMalloc(&P->snap_e, sizeof(double) * (size_t)P->ld) != hipSuccess || hipMalloc(&P->snap_b, sizeof(float) * p) != hipSuccess ||
+                                hipMalloc(&P->snap_d, sizeof(float) * p) != hipSuccess || hipMalloc(&P->snap_vb, sizeof(float) * p) != hipSuccess)) { (void)hipGetLastError(); guarded = false; }
+  SnapArgs sn;
+  sn.e = a.e; sn.se = P->snap_e; sn.b = a.b; sn.d = a.d; sn.vb = (a.flags & SWF_VB_VEC) ? a.vb : nullptr; sn.sb = P->snap_b; sn.sd = P->snap_d; sn.svb = P->snap_vb;
+  sn.ld = P->ld; sn.j0 = a.blk_begin * a.m; sn.j1 = (int)std::min<int64_t>(P->p, (int64_t)a.blk_end * a.m); sn.sc = a.sc;
+  if (guarded) hipLaunchKernelGGL(k_range_snapshot, dim3(256), dim3(256), 0, P->stream, sn);
+  launch_sweep_engine(P, a, pl, false);
+  if (guarded) {
+    hipLaunchKernelGGL(k_range_recover, dim3(256), dim3(256), 0, P->stream, sn);
+    hipLaunchKernelGGL(k_range_flag, dim3(1), dim3(1), 0, P->stream, a.sc);
+    (void)reset_exchange(P);
+    launch_sweep_engine(P, a, plan_sweep(P, a, true), true);
+    hipLaunchKernelGGL(k_redo_clear, dim3(1), dim3(1), 0, P->stream, a.sc);
+  }
+}
+
 // A handle that a pair run moved onto the pair's stream goes back to the stream it had (its own, or the caller's) when it next sweeps alone:
 // one wait, on the handle's stream -- nothing is enqueued on the pair stream, which other pairs' hardware queue shares
 static int leave_pair_stream(bwgr_panel *P) {
@@ -1585,28 +1622,21 @@ static int leave_pair_stream(bwgr_panel *P) {
   P->stream = P->pre_pair_stream; P->pre_pair_set = false;
   return BWGR_OK;
 }
-// A dry run of the sweep's launch code (nothing is enqueued) gives the compute units its kernels hold; refused with BWGR_EINVAL when they
-// cannot be resident beside the sweeps other handles have in flight on this device.  BWGR_OCC_GUARD=0 switches the guard off.
-static int sweep_guard(bwgr_panel *P, const SweepArgs &a, int *need) {
-  *need = 0;
-  if (!guard_on()) return BWGR_OK;
-  std::vector<SpinLaunch> plan;
-  g_plan = &plan; launch_sweep_kernel(P, a); g_plan = nullptr;
-  const int cus = device_cus(P->device);
-  if (cus < 1) return BWGR_OK;
-  std::lock_guard<std::mutex> lk(g_guard_mu);
-  return plan_cus(plan, cus, guard_busy(P, P->stream), need);
+// What a sweep alone does before anything of it is enqueued (a refused sweep leaves the chain as it was): back from a pair's stream, the
+// plan and its depth, the affine engine's scratch, the occupancy guard, then the zeroed exchange words
+static int sweep_begin(bwgr_panel *P, SweepArgs &a, SweepPlan &pl, int *need) {
+  CHK(leave_pair_stream(P));
+  pl = plan_sweep(P, a, false); a.lag = pl.lag;
+  if (pl.engine == 4) CHK(winv_alloc(P));
+  CHK(sweep_guard(P, pl, P->stream, nullptr, need));
+  return reset_exchange(P);
 }
 static int launch_sweep(bwgr_panel *P, SweepArgs &a) {
-  CHK(leave_pair_stream(P));
-  choose_lag(P, a);
-  if (use_winv(P, a.flags)) CHK(winv_alloc(P));
-  int need = 0;
-  CHK(sweep_guard(P, a, &need));
-  CHK(reset_exchange(P));
+  SweepPlan pl; int need = 0;
+  CHK(sweep_begin(P, a, pl, &need));
   P->ps_owner = nullptr;   // the scratch is about to hold this sweep's constants, nobody's iteration
-  launch_prestage(P, a);
-  launch_sweep_kernel(P, a);
+  launch_prestage(P, a, pl);
+  launch_sweep_kernel(P, a, pl);
   HIPCHK(hipGetLastError());
   guard_mark(P, P->stream, need);
   return BWGR_OK;
@@ -1711,8 +1741,7 @@ static int panel_setup(bwgr_panel *P) {
   }
   CHK(panel_build_gram(P));
   // the trajectory engine for the selection models (int8 panels that asked for it; BWGR_SWEEP=2 keeps k_sweep2)
-  const char *sv = getenv("BWGR_SWEEP");
-  if (P->want3 && !P->is_f32 && P->sweep_version == 2 && !(sv && sv[0] == '2')) {
+  if (P->want3 && !P->is_f32 && P->sweep_version == 2 && P->sw.sweep != '2') {
     P->sweep_version = 3;
     CHK(sweep3_build(P));
   }
@@ -1797,19 +1826,18 @@ static int panel_build_gram(bwgr_panel *P) {
     int bad = 1;
     HIPCHK(hipMemcpyAsync(&bad, P->gram16_bad, sizeof(int), hipMemcpyDeviceToHost, P->stream));
     HIPCHK(hipStreamSynchronize(P->stream));
-    const char *gv = getenv("BWGR_GRAM16");   // BWGR_GRAM16=0 forces the 32-bit staging (A/B tests)
-    P->gram16 = (bad == 0) && !(gv && gv[0] == '0');
+    P->gram16 = (bad == 0) && P->sw.gram16;   // BWGR_GRAM16=0 forces the 32-bit staging (A/B tests)
   }
   // the affine sweeps' sequencer (sweep2w.hip.h) takes the cross blocks as biased byte planes: built where every entry fits 16 bits
   P->winv_nd = 0;
-  if (!P->is_f32 && P->gram16 && P->winv_on && m <= SW_MAXM) {
+  if (!P->is_f32 && P->gram16 && P->sw.winv && m <= SW_MAXM) {
     HIPCHK(hipMemsetAsync(P->gram16_bad, 0, sizeof(int), P->stream));
     int nd = 0;
     int32_t *tmpx = nullptr;   // distances 4 and 5 (pipelines five and six blocks deep; main panels only): built here, kept as planes only
     for (int dist = 1; dist <= S2W_MAXDIST; ++dist) {
       const int32_t *src = (const int32_t *)(dist == 1 ? P->gramx : dist == 2 ? P->gramx2 : dist == 3 ? P->gramx3 : nullptr);
       if (dist > S2W_NEARD) {
-        if (!P->want3 || P->gram_maxdist < S2W_NEARD || P->nblocks <= dist || dist > P->wlag_cap - 1) break;
+        if (!P->want3 || P->gram_maxdist < S2W_NEARD || P->nblocks <= dist || dist > P->sw.wlag_cap - 1) break;
         if (!tmpx && hipMalloc(&tmpx, (size_t)P->nblocks * m * m * 4) != hipSuccess) { (void)hipGetLastError(); tmpx = nullptr; break; }
         launch_gramx_i8(P, tmpx, dist);
         src = tmpx;
@@ -1831,13 +1859,13 @@ static int panel_build_gram(bwgr_panel *P) {
 }
 
 // geometry + every device allocation of a panel of n rows x p markers (no data yet)
-static int panel_alloc(bwgr_panel **out, int is_f32, int64_t n, int64_t p, int device, int block, int nwg) {
+static int panel_alloc(bwgr_panel **out, int is_f32, int64_t n, int64_t p, int device, int block, int nwg, const Switches &sw) {
   *out = nullptr;
   if (n < 2 || p < 1) return fail(BWGR_EINVAL, "panel: need n >= 2, p >= 1 (n=%lld p=%lld)", (long long)n, (long long)p);
   if (n > 0x7FFFFF00ll || p > 0x7FFFFF00ll) return fail(BWGR_EINVAL, "panel: n and p must fit 31 bits");
   CHK(require_device(device));
   bwgr_panel *P = new bwgr_panel();
-  P->device = device; P->n = n; P->p = p; P->is_f32 = is_f32;
+  P->device = device; P->n = n; P->p = p; P->is_f32 = is_f32; P->sw = sw;
   const int mmax = P->is_f32 ? 64 : SW_MAXM;
   int m = block > 0 ? block : mmax;
   if (m > mmax) { delete P; return fail(BWGR_EINVAL, "panel_create: block %d > %d (limit for this genotype type)", m, mmax); }
@@ -1849,12 +1877,11 @@ static int panel_alloc(bwgr_panel **out, int is_f32, int64_t n, int64_t p, int d
   // prefer the largest slab it fits (unless that needs more workgroups than the chip has CUs, or k_sweep is forced)
   int Rpick = Rmax;
   {
-    const char *sv = getenv("BWGR_SWEEP");
     int R2 = 0;
     for (int Rt = 128; Rt <= Rmax; Rt += 128)
       if ((P->is_f32 ? sweep2_lds_bytes<float>(m, Rt) : sweep2_lds_bytes<int8_t>(m, Rt)) <= (size_t)160 * 1024 &&
           (P->is_f32 || (size_t)m * Rt <= S2I_TILE_BYTES_MAX)) R2 = Rt;   // (an int8 tile must fit its movers' registers)
-    if (!(sv && sv[0] == '1') && R2 > 0 && (n + R2 - 1) / R2 + 1 + 6 <= 256) Rpick = R2;
+    if (sw.sweep != '1' && R2 > 0 && (n + R2 - 1) / R2 + 1 + 6 <= 256) Rpick = R2;
   }
   int K = nwg > 0 ? nwg : (int)((n + Rpick - 1) / Rpick);
   int R = (int)((((n + K - 1) / K) + 127) / 128) * 128;
@@ -1872,10 +1899,9 @@ static int panel_alloc(bwgr_panel **out, int is_f32, int64_t n, int64_t p, int d
     P->lds2_bytes = std::max(P->lds2_bytes, s2i_lds_bytes(m, R, 4));
   }
   {
-    const char *sv = getenv("BWGR_SWEEP");   // A/B switch for tests and profiling
-    P->sweep_version = (sv && sv[0] == '1') ? 1 : 2;
+    P->sweep_version = (sw.sweep == '1') ? 1 : 2;   // A/B switch for tests and profiling
     P->nfeed = std::min(6, std::max(2, (K + 39) / 40 + 1));   // K = 40: 2, K = 79: 3, K >= 161: 6
-    if (const char *nf = getenv("BWGR_NFEED")) { const int v = atoi(nf); if (v >= 1 && v <= 6) P->nfeed = v; }   // experiments
+    if (sw.nfeed >= 1 && sw.nfeed <= 6) P->nfeed = sw.nfeed;   // experiments
     if (P->lds2_bytes > (size_t)160 * 1024 || K + 1 + P->nfeed > 256) P->sweep_version = 1;
     if (!P->is_f32 && (size_t)m * R > S2I_TILE_BYTES_MAX) P->sweep_version = 1;
   }
@@ -1891,8 +1917,7 @@ static int panel_alloc(bwgr_panel **out, int is_f32, int64_t n, int64_t p, int d
     PCHK(hipMalloc(&P->gramx2, P->gram_bytes));
     PCHK(hipMalloc(&P->xspec2, sizeof(double) * (size_t)P->nblocks * SW_MAXM));
   }
-  const char *lagenv = getenv("BWGR_LAG");
-  if (P->sweep_version >= 2 && !P->is_f32 && P->nblocks > 3 && P->lag4_ok && !(lagenv && (lagenv[0] == '2' || lagenv[0] == '3'))) {   // distance-3 blocks: the lag-4 pipeline
+  if (P->sweep_version >= 2 && !P->is_f32 && P->nblocks > 3 && P->lag4_ok && sw.lag != '2' && sw.lag != '3') {   // distance-3 blocks: the lag-4 pipeline
     PCHK(hipMalloc(&P->gramx3, P->gram_bytes));
     PCHK(hipMalloc(&P->xspec3, sizeof(double) * (size_t)P->nblocks * SW_MAXM));
   }
@@ -1915,29 +1940,16 @@ static int panel_alloc(bwgr_panel **out, int is_f32, int64_t n, int64_t p, int d
   PCHK(hipMalloc(&P->stamps, sizeof(unsigned long long) * 256));
   PCHK(hipMemset(P->stamps, 0, sizeof(unsigned long long) * 256));
 #endif
-  PCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep<int8_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  PCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep<int8_t, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  PCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep<float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  PCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep<float, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  PCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep2<int8_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  PCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep2<int8_t, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  PCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep2<int8_t, true, uint16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  PCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep2<float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  PCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep2<float, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  PCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep2w<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  PCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep2w<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  PCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_affine_inv), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  for (const void *f : {reinterpret_cast<const void *>(k_sweep<int8_t, true>), reinterpret_cast<const void *>(k_sweep<int8_t, false>), reinterpret_cast<const void *>(k_sweep<float, true>),
+                        reinterpret_cast<const void *>(k_sweep<float, false>), reinterpret_cast<const void *>(k_sweep2<int8_t, true>), reinterpret_cast<const void *>(k_sweep2<int8_t, false>),
+                        reinterpret_cast<const void *>(k_sweep2<int8_t, true, uint16_t>), reinterpret_cast<const void *>(k_sweep2<float, true>), reinterpret_cast<const void *>(k_sweep2<float, false>),
+                        reinterpret_cast<const void *>(k_sweep2w<true>), reinterpret_cast<const void *>(k_sweep2w<false>), reinterpret_cast<const void *>(k_affine_inv)})
+    PCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #ifdef BWGR_EXPERIMENTS
-  if (!P->is_f32) P->ldsw_bytes = s2w_lds_bytes(m, R, getenv("BWGR_WLAG_TIMING") ? atoi(getenv("BWGR_WLAG_TIMING")) : 6);
+  if (!P->is_f32) P->ldsw_bytes = s2w_lds_bytes(m, R, sw.wlag_timing ? sw.wlag_timing : 6);
 #else
   if (!P->is_f32) P->ldsw_bytes = s2w_lds_bytes(m, R, 6);
 #endif   // (room for the deepest pipeline BWGR_WLAG can ask for)
-  if (const char *wv = getenv("BWGR_WINV")) P->winv_on = !(wv[0] == '0');
-  if (const char *wv = getenv("BWGR_WFX")) P->wfx_on = !(wv[0] == '0');
-  if (const char *pv = getenv("BWGR_WPF")) P->wpf = std::max(0, std::min(8, atoi(pv)));
-  if (const char *pv = getenv("BWGR_WAHEAD")) P->wahead = std::max(1, atoi(pv));
-  if (const char *qv = getenv("BWGR_WNQ")) { const int v = atoi(qv); if (v == 1 || v == 2 || v == 4) P->wnq = v; }
-  if (const char *wl = getenv("BWGR_WLAG")) if (wl[0] >= '2' && wl[0] <= '6') P->wlag_cap = wl[0] - '0';
 #undef PCHK
   (void)rc;
   *out = P;
@@ -1952,7 +1964,7 @@ extern "C" int bwgr_panel_create(bwgr_panel **out, const void *X, int xtype, int
   if (xtype != BWGR_X_I8 && xtype != BWGR_X_F32 && xtype != BWGR_X_F64) return fail(BWGR_EINVAL, "panel_create: bad xtype %d", xtype);
   if (memloc != BWGR_HOST && memloc != BWGR_DEVICE) return fail(BWGR_EINVAL, "panel_create: bad memloc %d", memloc);
   bwgr_panel *P = nullptr;
-  CHK(panel_alloc(&P, xtype != BWGR_X_I8, n, p, device, block, nwg));
+  CHK(panel_alloc(&P, xtype != BWGR_X_I8, n, p, device, block, nwg, read_switches()));
   P->want3 = true;
   int rc;
   if (xtype == BWGR_X_I8) rc = upload<int8_t, int8_t>(P, X, memloc, ldx);
@@ -1982,12 +1994,12 @@ extern "C" int bwgr_panel_clone(bwgr_panel **out, bwgr_panel *src) {
   HIPCHK(hipSetDevice(root->device));
   HIPCHK(hipStreamSynchronize(root->stream));   // the shared arrays are complete
   bwgr_panel *P = new bwgr_panel(*root);
-  P->parent = root; P->nclones = 0; P->nchains = 0; P->own_stream = nullptr; P->stream = nullptr; P->ps_owner = nullptr; P->ps_iter = -1;
+  P->parent = root; P->nclones = 0; P->nchains = P->nchains_all = 0; P->own_stream = nullptr; P->stream = nullptr; P->ps_owner = nullptr; P->ps_iter = -1;
   P->pair_streams.clear();   // (the root's: a clone owns none)
   P->draws = nullptr; P->draws_stream = nullptr; P->draws_ready = nullptr; P->draws_free = nullptr; P->draws_valid = false;   // (its own, made on first use)
   P->pre_pair_stream = nullptr; P->pre_pair_set = false; P->guard_ev = nullptr; P->guard_cus = 0; P->guard_stream = nullptr; P->guard_listed = false;
   P->qsum3 = P->lists3 = nullptr; P->epoch3 = 0;
-  P->snap_e = nullptr; P->snap_b = P->snap_d = P->snap_vb = nullptr; P->xmax_dev = nullptr; P->winv = nullptr; P->qsumw = nullptr;
+  P->snap_e = nullptr; P->snap_b = P->snap_d = P->snap_vb = nullptr; P->xmax_dev = nullptr; P->winv = nullptr; P->qsumw = nullptr; P->cpre = nullptr;
   P->xspec2 = P->xspec3 = nullptr; P->ps = {}; P->xpart = P->qpart = nullptr; P->dgran = nullptr; P->xflags = nullptr; P->xchg = nullptr; P->stamps = nullptr;
   root->nclones++;
   auto bail = [&](int code) { bwgr_panel_destroy(P); return code; };
@@ -2017,14 +2029,16 @@ extern "C" int bwgr_panel_max_concurrent(const bwgr_panel *P, int selection, int
   if (!P || !count) return fail(BWGR_EINVAL, "null pointer");
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, P->device));
+  SweepArgs a{}; a.flags = selection ? SWF_SELECT : 0u;
+  const SweepPlan pl = plan_sweep(P, a, false);
   // selection on a panel with k_sweep3: the device sends a chain above the engine threshold to k_sweep2 (K + 1 + feeders), and a sweep that
-  // leaves the fixed-point range is redone there: the larger of the two
-  const int wgs2 = P->K + 1 + ((P->sweep_version >= 2 && selection) ? P->nfeed : 0);
-  int wgs = (selection && P->sweep_version == 3 && P->e3_ready) ? std::max(P->K3 + 1, wgs2) : wgs2;
-  if (!selection && use_winv(P, 0)) wgs = (use_wfx(P) ? P->K * (P->R / S2W_FXR) : P->K) + 1 + P->wpf;   // streamers, sequencer, L2 prefetchers (the launch's other workgroups leave at once)
+  // leaves the fixed-point range is redone there: the larger of the two (K3 + 1: the streamers of chains side by side, never the solo ones)
+  int wgs = P->K + 1 + pl.nfeed;
+  if (pl.engine == 3) wgs = std::max(P->K3 + 1, wgs);
+  if (pl.engine == 4) wgs = pl.spins[0].resident;   // streamers, sequencer, L2 prefetchers (the launch's other workgroups leave at once)
   // one sweep workgroup per CU even where the LDS would admit two (small blocks): measured, sharing a CU costs more than it adds
   *count = std::max(1, prop.multiProcessorCount / wgs);
-  if (const char *ov = getenv("BWGR_MAX_CONCURRENT")) { const int v = atoi(ov); if (v > 0) *count = v; }   // experiments
+  if (P->sw.max_concurrent > 0) *count = P->sw.max_concurrent;   // experiments
   return BWGR_OK;
 }
 
@@ -2033,11 +2047,11 @@ extern "C" int bwgr_panel_max_concurrent(const bwgr_panel *P, int selection, int
 extern "C" int bwgr_panel_max_pairs(const bwgr_panel *P, int *pairs) {
   if (!P || !pairs) return fail(BWGR_EINVAL, "null pointer");
   *pairs = 0;
-  if (!(P->sweep_version == 3 && P->e3_ready) || s3p_streamer_lds(P->R3) > (size_t)160 * 1024) return BWGR_OK;
+  if (!P->e3_ready || s3p_streamer_lds(P->R3) > (size_t)160 * 1024) return BWGR_OK;
   const int cus = device_cus(P->device);
   if (cus < 1) return fail(BWGR_EHIP, "panel_max_pairs: no device properties");
   *pairs = std::max(1, (cus - 40) / (P->K3 + 2));
-  if (const char *ov = getenv("BWGR_MAX_PAIRS")) { const int v = atoi(ov); if (v > 0) *pairs = v; }
+  if (P->sw.max_pairs > 0) *pairs = P->sw.max_pairs;
   return BWGR_OK;
 }
 
@@ -2065,14 +2079,11 @@ extern "C" int bwgr_panel_info(const bwgr_panel *P, int64_t info[8]) {
 
 extern "C" int bwgr_panel_pipeline(const bwgr_panel *P, int selection, int info[4]) {
   if (!P || !info) return fail(BWGR_EINVAL, "null pointer");
-  SweepArgs a{};
-  a.flags = selection ? SWF_SELECT : 0u;
-  choose_lag(P, a);
-  const bool s3 = selection && P->sweep_version == 3 && P->e3_ready;
-  const bool w4 = !selection && use_winv(P, 0);
-  info[0] = s3 ? 3 : w4 ? 4 : std::min(P->sweep_version, 2);
-  info[1] = s3 ? P->e3_D : a.lag;
-  info[2] = s3 ? 0 : ((P->sweep_version >= 2 && selection) ? P->nfeed : 0);
+  SweepArgs a{}; a.flags = selection ? SWF_SELECT : 0u;
+  const SweepPlan pl = plan_sweep(P, a, false);
+  info[0] = pl.engine;
+  info[1] = pl.engine == 3 ? P->e3_D : pl.lag;
+  info[2] = pl.engine == 3 ? 0 : pl.nfeed;
   info[3] = P->is_f32 ? 0 : (P->gram16 ? 16 : 32);
   return BWGR_OK;
 }
@@ -2174,7 +2185,7 @@ extern "C" int bwgr_kmup2(bwgr_panel *P, const int *Use, int64_t nuse, float *b,
     if (Use[k] < 0 || Use[k] >= P->n) return fail(BWGR_EINVAL, "kmup2: Use[%lld] = %d is outside 0..%lld", (long long)k, Use[k], (long long)P->n - 1);
   HIPCHK(hipSetDevice(P->device));
   bwgr_panel *PB = nullptr;
-  CHK(panel_alloc(&PB, P->is_f32, nuse, P->p, P->device, P->m, 0));
+  CHK(panel_alloc(&PB, P->is_f32, nuse, P->p, P->device, P->m, 0, P->sw));
   PB->stream = P->stream;
   struct Drop { bwgr_panel *q; ~Drop() { if (q) bwgr_panel_destroy(q); } } drop{PB};
   DevBufs bufs;
@@ -2210,7 +2221,7 @@ extern "C" int bwgr_chain_destroy(bwgr_chain *C) {
     if (C->P->draws_stream) (void)hipStreamSynchronize(C->P->draws_stream);   // (k_draws reads the chain's df from them)
     C->P->draws_valid = false; C->P->draws_sc = nullptr;
   }
-  if (C->P) { C->P->nchains--; (void)hipSetDevice(C->P->device); }
+  if (C->P) { C->P->nchains--; (C->P->parent ? C->P->parent : C->P)->nchains_all--; (void)hipSetDevice(C->P->device); }
   for (hipEvent_t ev : C->ev) hipEventDestroy(ev);
   hipFree(C->e0); hipFree(C->y); if (C->e_owned) hipFree(C->e); hipFree(C->b); hipFree(C->d); hipFree(C->vb); hipFree(C->lam);
   hipFree(C->B); hipFree(C->D); hipFree(C->VB); hipFree(C->sc);
@@ -2227,12 +2238,12 @@ extern "C" int bwgr_chain_create_sharded(bwgr_chain **out, bwgr_panel *P, int mo
   if (marker0 < 0 || p_total < marker0 + P->p || p_total > 0xFFFFFFF0ll) return fail(BWGR_EINVAL, "chain_create: bad shard [%lld,+%lld) of %lld", (long long)marker0, (long long)P->p, (long long)p_total);
   HIPCHK(hipSetDevice(P->device));
   if (panel_cen(P)) {
-    if (!has_d(model) || !use_sweep3(P, SWF_SELECT))
+    if (!has_d(model) || !P->e3_ready)
       return fail(BWGR_EINVAL, "chain_create: an implicitly centred panel (bwgr_panel_set_centred) runs the selection models BayesB / C / Cpi / Dpi only");
     if (!P->cpre) HIPCHK(hipMalloc(&P->cpre, sizeof(double) * ((size_t)P->nblocks + 1)));
   }
   bwgr_chain *C = new bwgr_chain();
-  C->P = P; P->nchains++; C->model = model; C->itf = it; C->bif = bi; C->iit = (int)it; C->ibi = (int)bi;
+  C->P = P; P->nchains++; (P->parent ? P->parent : P)->nchains_all++; C->model = model; C->itf = it; C->bif = bi; C->iit = (int)it; C->ibi = (int)bi;
   C->pi = pi; C->df = df; C->R2 = R2; C->seed = seed; C->rng_mode = rng_mode;
   C->marker0 = marker0; C->p_total = p_total; C->MSx_eff = MSx_total;
   C->Phi = MSx_total * (1 - R2) / R2;
@@ -2286,14 +2297,10 @@ extern "C" int bwgr_chain_sweep_blocks(bwgr_chain *C, int blk_begin, int blk_end
   if (blk_begin < 0 || blk_end > P->nblocks || blk_begin >= blk_end) return fail(BWGR_EINVAL, "sweep_blocks: bad range [%d,%d) of %lld", blk_begin, blk_end, (long long)P->nblocks);
   if (C->done >= C->iit) return fail(BWGR_EINVAL, "sweep_blocks: all %d iterations already run", C->iit);
   HIPCHK(hipSetDevice(P->device));
-  CHK(leave_pair_stream(P));
   SweepArgs a;
   chain_args(C, blk_begin, blk_end, a);
-  choose_lag(P, a);
-  if (use_winv(P, a.flags)) CHK(winv_alloc(P));
-  int need = 0;
-  CHK(sweep_guard(P, a, &need));   // (before anything of this sweep is enqueued: a refused sweep leaves the chain as it was)
-  CHK(reset_exchange(P));
+  SweepPlan pl; int need = 0;
+  CHK(sweep_begin(P, a, pl, &need));
   hipEvent_t e0, e1;
   HIPCHK(hipEventCreate(&e0));
   if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail(BWGR_EHIP, "sweep_blocks: hipEventCreate failed"); }
@@ -2303,15 +2310,15 @@ extern "C" int bwgr_chain_sweep_blocks(bwgr_chain *C, int blk_begin, int blk_end
   bool prestaged = false;
   if (P->ps_owner != C || P->ps_iter != C->done) {
     SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->nblocks;
-    launch_prestage(P, all);
+    launch_prestage(P, all, pl);
     P->ps_owner = C; P->ps_iter = C->done;
     prestaged = true;
   }
   hipError_t he = hipEventRecord(e0, P->stream);
-  if (he == hipSuccess) { launch_sweep_kernel(P, a); he = hipGetLastError(); }
+  if (he == hipSuccess) { launch_sweep_kernel(P, a, pl); he = hipGetLastError(); }
   if (he == hipSuccess && prestaged && C->done + 1 < C->iit) {   // the next iteration's variates, beside this sweep
     SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->nblocks;
-    draws_ahead(P, all, e0);
+    draws_ahead(P, all, pl, e0);
   }
   if (he == hipSuccess) he = hipEventRecord(e1, P->stream);
   if (he != hipSuccess) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return fail(BWGR_EHIP, "sweep_blocks: %s", hipGetErrorString(he)); }
@@ -2433,7 +2440,7 @@ extern "C" int bwgr_chain_run_pair(bwgr_chain *C0, bwgr_chain *C1, int iters) {
   if (iters < 0 || C0->done + iters > C0->iit || C1->done + iters > C1->iit) return fail(BWGR_EINVAL, "chain_run_pair: %d more iterations exceed it", iters);
   SweepArgs t0, t1;
   chain_args(C0, 0, (int)P0->nblocks, t0); chain_args(C1, 0, (int)P1->nblocks, t1);
-  if (!use_sweep3(P0, t0.flags) || !use_sweep3(P1, t1.flags) || !P0->qsum3 || !P1->qsum3)
+  if (plan_sweep(P0, t0, false).engine != 3 || plan_sweep(P1, t1, false).engine != 3 || !P0->qsum3 || !P1->qsum3)
     return fail(BWGR_EINVAL, "chain_run_pair: both chains must be selection models on a panel with k_sweep3");
   if (s3p_streamer_lds(P0->R3) > (size_t)160 * 1024) return fail(BWGR_EINVAL, "chain_run_pair: the paired streamers' LDS does not fit");
   HIPCHK(hipSetDevice(P0->device));
@@ -2455,35 +2462,29 @@ extern "C" int bwgr_chain_run_pair(bwgr_chain *C0, bwgr_chain *C1, int iters) {
     if (!PX->pre_pair_set) { PX->pre_pair_stream = PX->stream; PX->pre_pair_set = true; }   // (leave_pair_stream takes the handle back)
     PX->stream = s0;
   }
-  int rc = BWGR_OK;
-  const size_t lds = std::max(s3p_streamer_lds(P0->R3), s3_seq_lds(P0->e3_D, r0->gram16));
+  // the pair's one launch, resident beside the other streams' sweeps
+  P0->force3 = P1->force3 = true;   // (while the pair runs, every plan of either handle is that launch)
   int need = 0;
-  if (guard_on() && device_cus(P0->device) > 0) {   // the pair's one launch: K3 streamers and two sequencers, resident beside the other streams' sweeps
-    std::vector<SpinLaunch> plan;
-    plan.push_back(SpinLaunch{r0->gram16 ? reinterpret_cast<const void *>(k_sweep3p<uint16_t>) : reinterpret_cast<const void *>(k_sweep3p<int32_t>), P0->K3 + 2, SW_THREADS, lds});
-    std::lock_guard<std::mutex> lk(g_guard_mu);
-    CHK(plan_cus(plan, device_cus(P0->device), guard_busy(P0, s0, P1), &need));
-  }
-  P0->force3 = P1->force3 = true;
+  int rc = sweep_guard(P0, plan_sweep(P0, t0, false), s0, P1, &need);
   for (int k = 0; k < iters && rc == BWGR_OK; ++k) {
     SweepArgs a0, a1;
     chain_args(C0, 0, (int)P0->nblocks, a0); chain_args(C1, 0, (int)P1->nblocks, a1);
-    choose_lag(P0, a0); choose_lag(P1, a1);
+    const SweepPlan pl0 = plan_sweep(P0, a0, false), pl1 = plan_sweep(P1, a1, false);
+    a0.lag = pl0.lag; a1.lag = pl1.lag;
     if ((rc = reset_exchange(P0)) != BWGR_OK || (rc = reset_exchange(P1)) != BWGR_OK) break;
-    launch_prestage(P0, a0); launch_prestage(P1, a1);
+    launch_prestage(P0, a0, pl0); launch_prestage(P1, a1, pl1);
     P0->ps_owner = C0; P0->ps_iter = C0->done; P1->ps_owner = C1; P1->ps_iter = C1->done;
-    a0.gate3 = a1.gate3 = INFINITY;
+    a0.gate3 = pl0.gate3; a1.gate3 = pl1.gate3;
     if (P0->debug_withhold || P1->debug_withhold) { a0.flags |= SWF_DEBUG_WITHHOLD; a1.flags |= SWF_DEBUG_WITHHOLD; }
     Sweep3Args A0, A1;
-    sweep3_args(P0, a0, A0); sweep3_args(P1, a1, A1);
-    const dim3 grid(P0->K3 + 2), blk(SW_THREADS);
+    sweep3_args(P0, a0, pl0, A0); sweep3_args(P1, a1, pl1, A1);
     hipEvent_t evs[4] = {nullptr, nullptr, nullptr, nullptr};   // both chains time the launch they share
     bool ev_ok = true;
     for (int q = 0; q < 4 && ev_ok; ++q) ev_ok = hipEventCreate(&evs[q]) == hipSuccess;
     if (!ev_ok) { for (hipEvent_t q : evs) if (q) (void)hipEventDestroy(q); rc = fail(BWGR_EHIP, "chain_run_pair: hipEventCreate failed"); break; }
     (void)hipEventRecord(evs[0], s0); (void)hipEventRecord(evs[2], s0);
-    if (A0.g16) hipLaunchKernelGGL(k_sweep3p<uint16_t>, grid, blk, lds, s0, A0, A1);
-    else hipLaunchKernelGGL(k_sweep3p<int32_t>, grid, blk, lds, s0, A0, A1);
+    void *args[] = {&A0, &A1};
+    spin_launch(pl0.spins[0], s0, args);
     (void)hipEventRecord(evs[1], s0); (void)hipEventRecord(evs[3], s0);
     C0->ev.push_back(evs[0]); C0->ev.push_back(evs[1]); C1->ev.push_back(evs[2]); C1->ev.push_back(evs[3]);
     guard_mark(P0, s0, need);
@@ -2856,7 +2857,7 @@ extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int t
   std::vector<int> use_h;
   auto drop_panels = [&]() { if (PU) bwgr_panel_destroy(PU); if (PB) bwgr_panel_destroy(PB); hipFree(use_d); PU = PB = nullptr; use_d = nullptr; };
   if (bagging) {
-    int rcb = panel_alloc(&PB, P->is_f32, nbag, P->p, P->device, P->m, 0);
+    int rcb = panel_alloc(&PB, P->is_f32, nbag, P->p, P->device, P->m, 0, P->sw);
     if (rcb != BWGR_OK) { drop_panels(); return rcb; }
     PB->stream = P->stream;
     if (hipMalloc(&use_d, sizeof(int) * (size_t)nbag) != hipSuccess) { drop_panels(); return fail(BWGR_ENOMEM, "wgr: device allocation failed"); }
@@ -3090,11 +3091,11 @@ __global__ void k_uncentred(const float *xx, const float *vx, int64_t p, double 
 extern "C" int bwgr_panel_set_centred(bwgr_panel *P, int on) {
   if (!P) return fail(BWGR_EINVAL, "null panel");
   if (P->parent) return fail(BWGR_EINVAL, "panel_set_centred: set it on the root panel (clones follow it)");
-  if (P->nchains > 0) return fail(BWGR_EINVAL, "panel_set_centred: %d chains are alive on this panel", P->nchains);
+  if (P->nchains_all > 0) return fail(BWGR_EINVAL, "panel_set_centred: %d chains are alive on this panel and its clones", P->nchains_all);
   HIPCHK(hipSetDevice(P->device));
   if (!on) { P->cen = false; return BWGR_OK; }
   if (P->is_f32) return fail(BWGR_EINVAL, "panel_set_centred: float panels are swept as given (centre the columns before the upload)");
-  if (!use_sweep3(P, SWF_SELECT)) return fail(BWGR_EINVAL, "panel_set_centred: this panel has no k_sweep3 (geometry or Gram range): the implicitly centred sweep is k_sweep3's");
+  if (!P->e3_ready) return fail(BWGR_EINVAL, "panel_set_centred: this panel has no k_sweep3 (geometry or Gram range): the implicitly centred sweep is k_sweep3's");
   if (!P->csum) {
     HIPCHK(hipMalloc(&P->csum, sizeof(int32_t) * (size_t)P->p));
     HIPCHK(hipMalloc(&P->xxc, sizeof(float) * (size_t)P->p));
@@ -3158,7 +3159,7 @@ static int group_create_impl(bwgr_group **out, int ndev, const int *devices, con
       if (hipStreamCreateWithFlags(&q, hipStreamNonBlocking) != hipSuccess) return bail(fail(BWGR_EHIP, "group_create: hipStreamCreate failed"));
       Gp->streams.push_back(q);
       Gp->P[g]->stream = q;
-      if (ndev > 2 && !getenv("BWGR_SOLO3")) Gp->P[g]->solo3 = false;   // (an explicit BWGR_SOLO3 decides otherwise: experiments)
+      if (ndev > 2 && Gp->P[g]->sw.solo3 < 0) Gp->P[g]->solo3 = false;   // (an explicit BWGR_SOLO3 decides otherwise: experiments)
     }
     if (centre) { rc = bwgr_panel_set_centred(Gp->P[g], 1); if (rc != BWGR_OK) return bail(rc); }   // the shard's own column means (rows are not sharded)
     msx += (double)Gp->P[g]->MSx;
@@ -3169,8 +3170,7 @@ static int group_create_impl(bwgr_group **out, int ndev, const int *devices, con
   }
   Gp->MSx_total = (float)msx;
   if (ndev > 1 && !Gp->centred) {
-    const char *ok = getenv("BWGR_GROUP_ALLOW_UNCENTRED");
-    if (!(ok && ok[0] == '1'))
+    if (!Gp->P[0]->sw.group_allow_uncentred)
       return bail(fail(BWGR_EINVAL, "group_create: the columns of X are not centred, and on uncentred columns the marker-sharded sampler of %d devices is "
                                     "statistically unsound (every shard corrects the same stale residual mean: DESIGN.md section 8).  Pass centred columns "
                                     "(x_j - mean(x_j), float: the posterior of b and hat is the same under the sampler's flat intercept prior), use one "
@@ -3190,8 +3190,7 @@ static int group_create_impl(bwgr_group **out, int ndev, const int *devices, con
   int64_t nbmax = 0;
   for (int g = 0; g < ndev; ++g) nbmax = std::max<int64_t>(nbmax, Gp->P[g]->nblocks);
   Gp->rounds = (int)((nbmax + Gp->bps - 1) / Gp->bps);
-  const char *fc = getenv("BWGR_GROUP_FORCE_COMM");   // (tests: exercise the RCCL path with a single device)
-  Gp->use_comm = (ndev > 1 && !Gp->same_dev) || (fc && fc[0] == '1' && !Gp->same_dev);
+  Gp->use_comm = (ndev > 1 && !Gp->same_dev) || (Gp->P[0]->sw.group_force_comm && !Gp->same_dev);   // (BWGR_GROUP_FORCE_COMM=1, tests: exercise the RCCL path with a single device)
   if (Gp->same_dev) {
     if (hipSetDevice(devices[0]) != hipSuccess) return bail(fail(BWGR_EHIP, "group_create: hipSetDevice failed"));
     Gp->ev_sweep.assign(ndev, nullptr);
@@ -3562,7 +3561,7 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
   // scratch panel: same geometry, its own X and Gram; only the diagonal and distance-1 blocks are ever built (lag 2)
   bwgr_panel *Q = nullptr;
   if (shuffled) {
-    CHK(panel_alloc(&Q, P->is_f32, n, p, P->device, P->m, P->K));
+    CHK(panel_alloc(&Q, P->is_f32, n, p, P->device, P->m, P->K, P->sw));
     Q->stream = st; Q->gram_maxdist = 1;
     hipFree(Q->gramx2); hipFree(Q->gramx3); hipFree(Q->xspec2); hipFree(Q->xspec3); hipFree(Q->gramp16); hipFree(Q->gramx16);
     Q->gramx2 = Q->gramx3 = nullptr; Q->xspec2 = Q->xspec3 = nullptr; Q->gramp16 = Q->gramx16 = nullptr;
@@ -3681,7 +3680,7 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
   if (model == BWGR_EM_BL) flags |= SWF_EM_BL;
   if (lasso) flags |= SWF_EM_LASSO;
   int numit = 0;
-  const bool emdbg = getenv("BWGR_EM_DEBUG") != nullptr;
+  const bool emdbg = P->sw.em_debug;
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   for (int i = 0; i < maxit; ++i) {
     const double t_0 = now();

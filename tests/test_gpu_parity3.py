@@ -261,8 +261,18 @@ def test_centred_panel_refuses_what_it_cannot_sweep(tpod):
     with pytest.raises(bwgr_amd.BwgrError):
         P.set_centred(False)                                         # not while a chain is alive
     ch.close()
+    Q = P.clone()
+    cq = bwgr_amd.Chain(Q, "BayesB", y, it=4, bi=1, pi=0.9, seed=2)
+    with pytest.raises(bwgr_amd.BwgrError):
+        P.set_centred(False)                                         # ... nor a chain on a clone
+    cq.close()
     P.set_centred(False)
     assert not P.centred()
+    cq = bwgr_amd.Chain(Q, "BayesB", y, it=4, bi=1, pi=0.9, seed=2)
+    with pytest.raises(bwgr_amd.BwgrError):
+        P.set_centred(True)                                          # the other way round too
+    cq.close()
+    Q.close()
     g = bwgr_amd.BayesA(y, P, it=4, bi=1, seed=1)                    # the raw columns again
     assert np.isfinite(g["b"]).all()
     P.close()
