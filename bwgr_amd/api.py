@@ -908,3 +908,74 @@ def debug_variates(seed, kind, marker0, count, it=0, purpose=0, nu=0.0, device=0
     check(_lib.lib().bwgr_debug_variates(device, C.c_uint64(seed), kinds[kind], float(nu), C.c_uint32(marker0), C.c_uint32(it),
                                           C.c_uint32(purpose), int(count), _dp(out)))
     return out
+
+
+# ---- multi-trait ridge regression: MRR3 / MRR3F, mrr / mrr_float (bwgr_mrr, include/bwgr.h) ----
+_MRR_OPTS = ["maxit", "tol", "TH", "NLfactor", "InnerGS", "NoInv", "HCS", "XFA", "ACS", "NumXFA", "R2", "gc0", "df0", "updateMu",
+             "weight_prior_h2", "weight_prior_gc", "PenCor", "MinCor", "uncorH2below", "roundGCupFrom", "roundGCupTo", "roundGCdownFrom",
+             "roundGCdownTo", "bucketGCfrom", "bucketGCto", "DeflateMax", "DeflateBy", "OneVarB", "OneVarE", "verbose"]   # BWGR_MRR_* order
+MRR_KEYS = ("mu", "b", "hat", "h2", "GC", "vb", "ve", "MSx", "cnvB", "cnvH2", "cnvV", "b_Weights", "Its")
+
+
+def _mrr(Y, X, single, opts, panel_kw):
+    """bwgr_mrr: Y is n x k (NaN = missing) or a vector (k = 1); returns the reference's list as a dict, in its order."""
+    P, own = _as_panel(X, **panel_kw)
+    try:
+        Ym = np.asarray(Y, np.float64)
+        if Ym.ndim == 1:
+            Ym = Ym[:, None]
+        if single:   # MRR3F receives float matrices (src/RcppEigen20230423.cpp:704)
+            Ym = Ym.astype(np.float32).astype(np.float64)
+        assert Ym.ndim == 2 and Ym.shape[0] == P.n, "nrow(Y) must equal nrow(X)"
+        k = Ym.shape[1]
+        Yf = np.asfortranarray(Ym)
+        o = np.array([float(opts[name]) for name in _MRR_OPTS], np.float64)
+        if single:
+            o = o.astype(np.float32).astype(np.float64)
+            o[_MRR_OPTS.index("maxit")] = int(opts["maxit"])
+        maxit = max(int(opts["maxit"]), 0)
+        kk = max(k, 1)
+        mu = np.zeros(kk); b = np.zeros((P.p, kk), order="F"); hat = np.zeros((P.n, kk), order="F")
+        h2 = np.zeros(kk); GC = np.zeros((kk, kk), order="F"); vb = np.zeros((kk, kk), order="F"); ve = np.zeros(kk); MSx = np.zeros(kk)
+        c1 = np.zeros(max(maxit, 1)); c2 = np.zeros(max(maxit, 1)); c3 = np.zeros(max(maxit, 1)); its = C.c_int()
+        check(_lib.lib().bwgr_mrr(P._h, _dp(Yf), int(k), _dp(o), len(o), _dp(mu), _dp(b), _dp(hat), _dp(h2), _dp(GC), _dp(vb), _dp(ve),
+                                  _dp(MSx), _dp(c1), _dp(c2), _dp(c3), C.byref(its)))
+        n_it = int(its.value)
+        vals = (mu, b, hat, h2, GC, vb, ve, MSx, c1[:n_it].copy(), c2[:n_it].copy(), c3[:n_it].copy(), np.ones((P.p, k)), n_it)
+        return dict(zip(MRR_KEYS, vals))
+    finally:
+        if own:
+            P.close()
+
+
+def MRR3(Y, X, maxit=500, tol=10e-9, cores=1, TH=False, NLfactor=0.0, InnerGS=False, NoInv=False, HCS=False, XFA=False, ACS=False,
+         NumXFA=3, R2=0.5, gc0=0.5, df0=1.0, updateMu=False, weight_prior_h2=0.01, weight_prior_gc=0.01, PenCor=0.0, MinCor=1.0,
+         uncorH2below=0.0, roundGCupFrom=1.0, roundGCupTo=1.0, roundGCdownFrom=1.0, roundGCdownTo=0.0, bucketGCfrom=1.0, bucketGCto=1.0,
+         DeflateMax=0.9, DeflateBy=0.0, OneVarB=False, OneVarE=False, verbose=False, **kw):
+    """MRR3(Y, X, ...), src/RcppEigen20230423.cpp:318-700 (R/RcppExports.R:180): multi-trait ridge regression by randomized
+    Gauss-Seidel; NaN in Y = missing.  list(mu, b, hat, h2, GC, vb, ve, MSx, cnvB, cnvH2, cnvV, b_Weights, Its).  `cores` is
+    ignored; InnerGS, NoInv, NLfactor, PenCor, MinCor, uncorH2below, round*, bucket* and DeflateBy are refused (BWGR_EINVAL) away
+    from their defaults.  X is centred by its column means, as in the reference."""
+    opts = dict(locals()); opts.pop("Y"); opts.pop("X"); opts.pop("kw"); opts.pop("cores")
+    return _mrr(Y, X, False, opts, kw)
+
+
+def MRR3F(Y, X, maxit=500, tol=10e-9, cores=1, TH=False, NonLinearFactor=0.0, InnerGS=False, NoInv=False, HCS=False, XFA=False, ACS=False,
+          NumXFA=3, R2=0.5, gc0=0.5, df0=1.0, updateMu=False, weight_prior_h2=0.01, weight_prior_gc=0.01, PenCor=0.0, MinCor=1.0,
+          uncorH2below=0.0, roundGCupFrom=1.0, roundGCupTo=1.0, roundGCdownFrom=1.0, roundGCdownTo=0.0, bucketGCfrom=1.0, bucketGCto=1.0,
+          DeflateMax=0.9, DeflateBy=0.0, OneVarB=False, OneVarE=False, verbose=False, **kw):
+    """MRR3F(Y, X, ...), src/RcppEigen20230423.cpp:704-1080 (R/RcppExports.R:184): MRR3's algorithm on float inputs.  Y and the
+    real options are rounded to float as the reference receives them; the engine itself is fp64."""
+    opts = dict(locals()); opts.pop("Y"); opts.pop("X"); opts.pop("kw"); opts.pop("cores")
+    opts["NLfactor"] = opts.pop("NonLinearFactor")
+    return _mrr(Y, X, True, opts, kw)
+
+
+def mrr(Y, X, **kw):
+    """mrr(Y, X, ...) = MRR3(Y, X, ...), R/mix.R:1271."""
+    return MRR3(Y, X, **kw)
+
+
+def mrr_float(Y, X, **kw):
+    """mrr_float(Y, X, ...) = MRR3F(Y, X, ...), R/mix.R:1273."""
+    return MRR3F(Y, X, **kw)

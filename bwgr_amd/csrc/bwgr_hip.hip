@@ -19,6 +19,7 @@
 #include "sweep3.hip.h"
 #include "sweep2w.hip.h"
 #include "sweep3p.hip.h"
+#include "mrr.hip.h"
 #include <stdlib.h>
 
 using namespace bwgr;
@@ -3783,6 +3784,267 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
   if (lasso) { scal[0] = h.Lmb1; scal[1] = 0.0f; }                                   // Lmb, :1497
   if (iters) *iters = numit;
 #undef ECHK
+  return done(BWGR_OK);
+}
+
+// ------------------------------------------------------------------------------------------------
+// mrr / mrr_float (MRR3 / MRR3F, src/RcppEigen20230423.cpp:318-1080): the engine of mrr.hip.h as a per-block launch train
+//   per sweep:  order (host std::shuffle, cumulative) -> k_permute_cols -> k_mrr_gram -> k_mrr_linv ->
+//               [k_mrr_pass(b-1 | b), k_mrr_solve(b)] for every block -> k_mrr_pass(last | -) -> k_mrr_ey -> (host: ve) ->
+//               k_mrr_tilde -> (host: vb, GC, bending, pinv) -> k_mrr_mu_shift (updateMu)
+// ------------------------------------------------------------------------------------------------
+extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opts, int nopts, double *mu_out, double *b_out, double *hat_out,
+                        double *h2_out, double *GC_out, double *vb_out, double *ve_out, double *MSx_out, double *cnvB, double *cnvH2, double *cnvV,
+                        int *its) {
+  if (!P || !Y || !b_out || !its) return fail(BWGR_EINVAL, "mrr: null pointer");
+  if (k < 1 || k > BWGR_MRR_MAXK) return fail(BWGR_EINVAL, "mrr: k = %d traits; this engine takes 1 <= k <= %d", k, BWGR_MRR_MAXK);
+  if (nopts < 0 || nopts > BWGR_MRR_NOPTS || (nopts > 0 && !opts)) return fail(BWGR_EINVAL, "mrr: nopts = %d (at most %d)", nopts, BWGR_MRR_NOPTS);
+  if (P->is_f32) return fail(BWGR_EINVAL, "mrr: the panel holds fp32 genotypes; mrr takes int8 panels only");
+  double O[BWGR_MRR_NOPTS] = BWGR_MRR_DEFAULTS;
+  const double D0[BWGR_MRR_NOPTS] = BWGR_MRR_DEFAULTS;
+  for (int i = 0; i < nopts; ++i) O[i] = opts[i];
+  {
+    static const struct { int id; const char *name; } refused[] = {
+      {BWGR_MRR_NLFACTOR, "NLfactor / NonLinearFactor"}, {BWGR_MRR_INNERGS, "InnerGS"}, {BWGR_MRR_NOINV, "NoInv"}, {BWGR_MRR_PENCOR, "PenCor"},
+      {BWGR_MRR_MINCOR, "MinCor"}, {BWGR_MRR_UNCORH2BELOW, "uncorH2below"}, {BWGR_MRR_ROUNDGCUPFROM, "roundGCupFrom"}, {BWGR_MRR_ROUNDGCUPTO, "roundGCupTo"},
+      {BWGR_MRR_ROUNDGCDOWNFROM, "roundGCdownFrom"}, {BWGR_MRR_ROUNDGCDOWNTO, "roundGCdownTo"}, {BWGR_MRR_BUCKETGCFROM, "bucketGCfrom"},
+      {BWGR_MRR_BUCKETGCTO, "bucketGCto"}, {BWGR_MRR_DEFLATEBY, "DeflateBy"}};
+    for (const auto &r : refused)
+      if (O[r.id] != D0[r.id]) return fail(BWGR_EINVAL, "mrr: option %s = %g is not supported (only its default, %g)", r.name, O[r.id], D0[r.id]);
+  }
+  MrrOpts o;
+  o.maxit = (int)O[BWGR_MRR_MAXIT]; o.tol = O[BWGR_MRR_TOL]; o.TH = O[BWGR_MRR_TH] != 0; o.HCS = O[BWGR_MRR_HCS] != 0; o.XFA = O[BWGR_MRR_XFA] != 0;
+  o.ACS = O[BWGR_MRR_ACS] != 0; o.NumXFA = (int)O[BWGR_MRR_NUMXFA]; o.R2 = O[BWGR_MRR_R2]; o.gc0 = O[BWGR_MRR_GC0]; o.df0 = O[BWGR_MRR_DF0];
+  o.updateMu = O[BWGR_MRR_UPDATEMU] != 0; o.wph2 = O[BWGR_MRR_WEIGHT_PRIOR_H2]; o.wpgc = O[BWGR_MRR_WEIGHT_PRIOR_GC];
+  o.OneVarB = O[BWGR_MRR_ONEVARB] != 0; o.OneVarE = O[BWGR_MRR_ONEVARE] != 0; o.verbose = O[BWGR_MRR_VERBOSE] != 0;
+  if (o.maxit < 0) return fail(BWGR_EINVAL, "mrr: maxit = %d", o.maxit);
+  if ((o.XFA || o.ACS) && (o.NumXFA < 1 || o.NumXFA > k))
+    return fail(BWGR_EINVAL, "mrr: NumXFA = %d with XFA / ACS needs 1 <= NumXFA <= k = %d (the reference indexes eigenvalue k - NumXFA)", o.NumXFA, k);
+  HIPCHK(hipSetDevice(P->device));
+  bwgr_panel *root = P->parent ? P->parent : P;
+  const int64_t n = P->n, p = P->p, ld = P->ld;
+  const int R = P->R;
+  {
+    const int64_t xm = std::max(root->xmax, 1);
+    if ((int64_t)n * xm * xm >= (1ll << 31)) return fail(BWGR_EINVAL, "mrr: n * max|x|^2 = %lld does not fit the int32 Gram", (long long)(n * xm * xm));
+  }
+  // ---- host set-up (:742-816) ----
+  std::vector<double> y((size_t)k * ld, 0.0), nt(k, 0.0), mu(k, 0.0);
+  std::vector<uint32_t> zt((size_t)ld, 0u);     // bit t: row observed for trait t
+  for (int t = 0; t < k; ++t)
+    for (int64_t r = 0; r < n; ++r) {
+      const double v = Y[(size_t)t * n + r];
+      if (!std::isnan(v)) { zt[r] |= 1u << t; nt[t] += 1.0; mu[t] += v; }                                  // :746-750, :754
+    }
+  for (int t = 0; t < k; ++t) {
+    if (nt[t] < 2) return fail(BWGR_EINVAL, "mrr: trait %d has %g observed rows (needs 2)", t, nt[t]);
+    mu[t] /= nt[t];                                                                                        // :758-759
+    for (int64_t r = 0; r < n; ++r) if ((zt[r] >> t) & 1u) y[(size_t)t * ld + r] = Y[(size_t)t * n + r] - mu[t];   // :761
+  }
+  // missingness patterns: traits with the same observed rows share one masked Gram
+  MrrConst mc; memset(&mc, 0, sizeof(mc));
+  mc.k = k;
+  std::vector<int> rep;   // a trait of each pattern
+  for (int t = 0; t < k; ++t) {
+    int g = -1;
+    for (int q = 0; q < (int)rep.size() && g < 0; ++q) {
+      bool same = true;
+      for (int64_t r = 0; r < n && same; ++r) same = (((zt[r] >> t) ^ (zt[r] >> rep[q])) & 1u) == 0;
+      if (same) g = q;
+    }
+    if (g < 0) { g = (int)rep.size(); rep.push_back(t); }
+    mc.pt[t] = g; mc.nt[t] = nt[t];
+  }
+  const int npat = (int)rep.size();
+  mc.npat = npat;
+  std::vector<uint32_t> zb((size_t)ld, 0u);      // bit g: row observed in pattern g (k_mrr_setup_cols)
+  std::vector<uint8_t> zm((size_t)npat * ld, 0);
+  for (int g = 0; g < npat; ++g)
+    for (int64_t r = 0; r < n; ++r) if ((zt[r] >> rep[g]) & 1u) { zb[r] |= 1u << g; zm[(size_t)g * ld + r] = 0xFF; }
+  std::vector<double> sumy(k, 0.0), vy(k, 0.0);
+  for (int t = 0; t < k; ++t)
+    for (int64_t r = 0; r < n; ++r) { const double v = y[(size_t)t * ld + r]; sumy[t] += v; vy[t] += v * v; }
+  for (int t = 0; t < k; ++t) vy[t] /= (nt[t] - 1.0);                                                     // iN = 1/(n-1), :781-782
+
+  hipStream_t st = P->stream;
+  std::vector<void *> owned;
+  auto done = [&](int code) { (void)hipStreamSynchronize(st); for (void *q : owned) hipFree(q); return code; };
+#define MCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return done(fail(BWGR_EHIP, "%s failed: %s", #x, hipGetErrorString(e_))); } while (0)
+  auto dmalloc = [&](void **q, size_t bytes) { hipError_t e_ = hipMalloc(q, bytes); if (e_ == hipSuccess) owned.push_back(*q); return e_; };
+  const int64_t nblk = (p + MRR_MB - 1) / MRR_MB, ntiles = ld / 64;
+  const int G = (int)std::min<int64_t>(ntiles, MRR_PASS_WG);
+  const int NP = 64;                                   // partials of the tail reductions
+  const int nch = (int)std::min<int64_t>(64, p);       // marker chunks of the fitted values
+  const int64_t cpc = (p + nch - 1) / nch;
+  int8_t *Xs = nullptr; uint32_t *zbd = nullptr, *ztd = nullptr; uint8_t *zmd = nullptr; int32_t *ordd = nullptr, *gram = nullptr;
+  double *yd = nullptr, *ed = nullptr, *xbar = nullptr, *Sd = nullptr, *XXd = nullptr, *XSXd = nullptr, *tilde = nullptr, *bd = nullptr, *Linv = nullptr;
+  double *part = nullptr, *dB = nullptr, *db2 = nullptr, *small = nullptr, *tpart = nullptr, *sumyd = nullptr, *hpart = nullptr, *hatd = nullptr;
+  MCHK(dmalloc((void **)&Xs, P->x_bytes));
+  MCHK(dmalloc((void **)&zbd, sizeof(uint32_t) * ld)); MCHK(dmalloc((void **)&ztd, sizeof(uint32_t) * ld));
+  MCHK(dmalloc((void **)&zmd, (size_t)npat * ld));
+  MCHK(dmalloc((void **)&ordd, sizeof(int32_t) * p));
+  MCHK(dmalloc((void **)&gram, sizeof(int32_t) * (size_t)nblk * npat * MRR_MB * MRR_MB));
+  MCHK(dmalloc((void **)&yd, sizeof(double) * k * ld)); MCHK(dmalloc((void **)&ed, sizeof(double) * k * ld));
+  MCHK(dmalloc((void **)&xbar, sizeof(double) * p)); MCHK(dmalloc((void **)&Sd, sizeof(double) * npat * p));
+  MCHK(dmalloc((void **)&XXd, sizeof(double) * p * k)); MCHK(dmalloc((void **)&XSXd, sizeof(double) * p * k));
+  MCHK(dmalloc((void **)&tilde, sizeof(double) * p * k)); MCHK(dmalloc((void **)&bd, sizeof(double) * p * k));
+  MCHK(dmalloc((void **)&Linv, sizeof(double) * p * k * k));
+  MCHK(dmalloc((void **)&part, sizeof(double) * G * (MRR_MB + 1) * MRR_KMAX));
+  MCHK(dmalloc((void **)&dB, sizeof(double) * (MRR_MB * MRR_KMAX + MRR_KMAX)));
+  MCHK(dmalloc((void **)&db2, sizeof(double) * MRR_KMAX));
+  MCHK(dmalloc((void **)&small, sizeof(double) * 1024));            // [0, 512): reduction results; [512, 768): iG; [768, ...): mu shift
+  MCHK(dmalloc((void **)&tpart, sizeof(double) * NP * (MRR_KMAX * MRR_KMAX + MRR_KMAX)));
+  MCHK(dmalloc((void **)&sumyd, sizeof(double) * MRR_KMAX));
+  MCHK(hipMemcpyAsync(zbd, zb.data(), sizeof(uint32_t) * ld, hipMemcpyHostToDevice, st));
+  MCHK(hipMemcpyAsync(ztd, zt.data(), sizeof(uint32_t) * ld, hipMemcpyHostToDevice, st));
+  MCHK(hipMemcpyAsync(zmd, zm.data(), (size_t)npat * ld, hipMemcpyHostToDevice, st));
+  MCHK(hipMemcpyAsync(yd, y.data(), sizeof(double) * k * ld, hipMemcpyHostToDevice, st));
+  MCHK(hipMemcpyAsync(ed, y.data(), sizeof(double) * k * ld, hipMemcpyHostToDevice, st));          // e = y, :825
+  MCHK(hipMemcpyAsync(sumyd, sumy.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
+  MCHK(hipMemsetAsync(bd, 0, sizeof(double) * p * k, st));                                         // b = 0, :823
+  MCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_linv), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  MCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_solve), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  hipLaunchKernelGGL(k_mrr_setup_cols, dim3((unsigned)std::min<int64_t>((p + 3) / 4, 8192)), dim3(256), 0, st, (const int8_t *)P->X, R, (int)n, p, ld,
+                     (const uint32_t *)zbd, (const double *)yd, (const double *)sumyd, mc, xbar, Sd, XXd, XSXd, tilde);
+  MCHK(hipGetLastError());
+  // a reduction over p of the k^2 (+k) products, partials in a fixed order
+  auto reduce_pk = [&](int mode, int nout, const double *iGd, std::vector<double> &out) -> hipError_t {
+    hipLaunchKernelGGL(k_mrr_tilde, dim3(NP, nout), dim3(256), 0, st, (const double *)bd, (const double *)tilde, (const double *)XSXd, p, mode, mc, iGd, tpart);
+    hipLaunchKernelGGL(k_mrr_finish, dim3(1), dim3(256), 0, st, (const double *)tpart, NP, nout, small);
+    hipError_t e_ = hipGetLastError();
+    if (e_ != hipSuccess) return e_;
+    out.resize(nout);
+    return d2h(st, out.data(), small, sizeof(double) * nout);
+  };
+  std::vector<double> MSx;
+  MCHK(reduce_pk(2, k, nullptr, MSx));                                                             // MSx = colSums(XSX), :777
+  // ---- start values (:784-816) ----
+  std::vector<double> ve(k), vbInit(k), veInit(k), h2(k), TrXSX(k), Se(k), iNp(k), iN(k);
+  std::vector<double> vb((size_t)k * k, 0.0), iG((size_t)k * k, 0.0), Sb((size_t)k * k), GC((size_t)k * k, 0.0), TH_((size_t)k * k), Tr(k);
+  for (int t = 0; t < k; ++t) {
+    TrXSX[t] = nt[t] * MSx[t];                                                                     // :778
+    ve[t] = vy[t] * (1 - o.R2); veInit[t] = ve[t];                                                 // :784, :788
+    vbInit[t] = vy[t] * o.R2 / MSx[t];                                                             // :787
+    vb[t * k + t] = vbInit[t]; iG[t * k + t] = 1.0 / vbInit[t];                                    // :789-790 (iG before the covariances)
+    h2[t] = 1 - ve[t] / vy[t];                                                                     // :791
+    Se[t] = ve[t] * o.df0; iNp[t] = 1.0 / (nt[t] + o.df0 - 1); iN[t] = 1.0 / (nt[t] - 1);          // :817-818, :781
+  }
+  for (int i = 0; i < k; ++i) for (int j = 0; j < i; ++j) vb[i * k + j] = vb[j * k + i] = o.gc0 * sqrt(vb[i * k + i] * vb[j * k + j]);   // :796-804
+  for (int i = 0; i < k * k; ++i) Sb[i] = vb[i] * o.df0;                                           // :816
+  for (int i = 0; i < k * k; ++i) GC[i] = vb[i];
+  // ---- iterations ----
+  std::vector<int> order((size_t)p);
+  for (int64_t j = 0; j < p; ++j) order[(size_t)j] = (int)j;
+  const int cps = (int)((size_t)R / 16);
+  const double logtol = log10(o.tol);
+  std::vector<double> ey, db2h(k), vb0, h20, d(k);
+  int numit = 0;
+  const size_t lds_linv = sizeof(double) * 64 * k * k;
+  // the solve's LDS: the markers' inverses when they fit, then as many block Gram matrices as the rest holds
+  const size_t lds_max = 160 * 1024, lds_fixed = mrr_solve_lds(0, 0), linv_b = sizeof(double) * MRR_MB * k * k;
+  const int linv_lds = lds_fixed + linv_b <= lds_max ? 1 : 0;
+  const int ngl = (int)std::min<size_t>((size_t)npat, (lds_max - lds_fixed - (linv_lds ? linv_b : 0)) / (MRR_MB * MRR_MB * 4));
+  const size_t lds_solve = mrr_solve_lds(ngl, linv_lds ? MRR_MB * k * k : 0);
+  while (numit < o.maxit) {
+    vb0 = vb; h20 = h2;
+    std::shuffle(order.begin(), order.end(), std::mt19937(numit));                                 // :869 (cumulative, as there)
+    MCHK(hipMemcpyAsync(ordd, order.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)P->X, (uint4 *)Xs, (const int32_t *)ordd, p, P->K, cps);
+    hipLaunchKernelGGL(k_mrr_gram, dim3((unsigned)nblk, (unsigned)((npat + 3) / 4)), dim3(256), 0, st, (const int8_t *)Xs, R, p, ld, (const uint8_t *)zmd, npat, gram);
+    for (int t = 0; t < k; ++t) mc.iVe[t] = 1.0 / ve[t];
+    MCHK(hipMemcpyAsync(small + 512, iG.data(), sizeof(double) * k * k, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_mrr_linv, dim3((unsigned)((p + 63) / 64)), dim3(64), lds_linv, st, (const double *)XXd, (const double *)(small + 512), mc, p, Linv);
+    MCHK(hipMemsetAsync(db2, 0, sizeof(double) * MRR_KMAX, st));
+    MCHK(hipGetLastError());
+    for (int64_t blk = 0; blk <= nblk; ++blk) {
+      MrrPassArgs pa; pa.Xs = Xs; pa.R = R; pa.p = p; pa.ld = ld; pa.nblk = (int)nblk; pa.zb = ztd; pa.e = ed; pa.dB = dB; pa.part = part;
+      pa.prev = blk > 0 ? (int)(blk - 1) : -1; pa.next = blk < nblk ? (int)blk : -1; pa.k = k;
+      hipLaunchKernelGGL(k_mrr_pass, dim3(G), dim3(256), 0, st, pa);
+      if (blk == nblk) break;
+      MrrSolveArgs sa; sa.part = part; sa.G = G; sa.order = ordd; sa.blk = (int)blk; sa.p = p; sa.gram = gram; sa.xbar = xbar; sa.S = Sd; sa.XX = XXd;
+      sa.Linv = Linv; sa.b = bd; sa.dB = dB; sa.db2 = db2; sa.ngl = ngl; sa.linv_lds = linv_lds;
+
+      hipLaunchKernelGGL(k_mrr_solve, dim3(1), dim3(256), lds_solve, st, sa, mc);
+    }
+    MCHK(hipGetLastError());
+    // residual variance (:916-924)
+    hipLaunchKernelGGL(k_mrr_ey, dim3(NP, k), dim3(256), 0, st, (const double *)ed, (const double *)yd, ld, k, tpart);
+    hipLaunchKernelGGL(k_mrr_finish, dim3(1), dim3(256), 0, st, (const double *)tpart, NP, 2 * k, small);
+    MCHK(hipGetLastError());
+    ey.resize(2 * k);
+    MCHK(d2h(st, ey.data(), small, sizeof(double) * 2 * k));
+    MCHK(d2h(st, db2h.data(), db2, sizeof(double) * k));
+    for (int t = 0; t < k; ++t) {
+      ve[t] = (ey[t] + Se[t]) * iNp[t];                                                            // :916-917
+      h2[t] = 1 - ve[t] / vy[t];                                                                   // :918 (before the prior)
+      if (o.wph2 > 0) ve[t] = ve[t] * (1 - o.wph2) + o.wph2 * veInit[t];                           // :920
+    }
+    if (o.OneVarE) { double m = 0; for (int t = 0; t < k; ++t) m += ve[t]; m /= k; for (int t = 0; t < k; ++t) ve[t] = m; }   // :922
+    // TildeHat (:928-936): the TH form reads this iteration's ve and the sweep's iG
+    for (int t = 0; t < k; ++t) { mc.iVe[t] = 1.0 / ve[t]; d[t] = iG[t * k + t]; }
+    std::vector<double> th;
+    if (o.TH) {
+      MCHK(hipMemcpyAsync(small + 768, d.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
+      MCHK(reduce_pk(1, k * k + k, small + 768, th));
+      for (int t = 0; t < k; ++t) Tr[t] = th[k * k + t];
+    } else {
+      MCHK(reduce_pk(0, k * k, nullptr, th));
+      for (int t = 0; t < k; ++t) Tr[t] = TrXSX[t];
+    }
+    // th[s * k + t] = sum_j b_js tilde_jt = TildeHat(s, t)
+    for (int i = 0; i < k * k; ++i) TH_[i] = th[i];
+    int bent = 0;
+    mrr_tail_vb(k, o, TH_.data(), Tr.data(), Sb.data(), vbInit.data(), vb.data(), GC.data(), iG.data(), &bent);
+    if (bent && o.verbose) printf("Inflate (it=%d)\n", numit);
+    if (o.updateMu) {                                                                              // :1030-1036
+      for (int t = 0; t < k; ++t) { d[t] = ey[k + t] * iN[t]; mu[t] += d[t]; }
+      MCHK(hipMemcpyAsync(small + 768, d.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(k_mrr_mu_shift, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st, ed, (const uint32_t *)ztd, ld, (int)n, k, (const double *)(small + 768));
+      MCHK(hipGetLastError());
+    }
+    double mx = -INFINITY;
+    for (int t = 0; t < k; ++t) mx = std::max(mx, db2h[t]);
+    const double cnv = log10(mx);                                                                  // :1040-1041
+    if (cnvB) cnvB[numit] = cnv;
+    if (std::isnan(cnv)) { if (o.verbose) printf("Numerical issue! Job aborted (it=%d)\n", numit); break; }
+    double s2 = 0, s3 = 0;
+    for (int t = 0; t < k; ++t) s2 += (h20[t] - h2[t]) * (h20[t] - h2[t]);
+    for (int i = 0; i < k * k; ++i) s3 += (vb0[i] - vb[i]) * (vb0[i] - vb[i]);
+    if (cnvH2) cnvH2[numit] = log10(s2);                                                           // :1042
+    if (cnvV) cnvV[numit] = log10(s3);                                                             // :1043
+    ++numit;
+    if (o.verbose && numit % 100 == 0) printf("Iter: %d || Conv: %g\n", numit, cnv);
+    if (cnv < logtol) { if (o.verbose) printf("Model coverged in %d iterations\n", numit); break; }
+    if (numit == o.maxit && o.verbose) printf("Model did not converge\n");
+  }
+  // ---- fitted values for every row, the missing ones included (:1054-1055) ----
+  std::vector<double> bh((size_t)p * k), xb((size_t)p), off(k);
+  MCHK(d2h(st, bh.data(), bd, sizeof(double) * p * k));
+  MCHK(d2h(st, xb.data(), xbar, sizeof(double) * p));
+  for (int t = 0; t < k; ++t) { double s = 0; for (int64_t j = 0; j < p; ++j) s += xb[(size_t)j] * bh[(size_t)j * k + t]; off[t] = mu[t] - s; }
+  if (hat_out) {
+    MCHK(dmalloc((void **)&hpart, sizeof(double) * nch * k * ld)); MCHK(dmalloc((void **)&hatd, sizeof(double) * n * k));
+    MCHK(hipMemcpyAsync(small, off.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_mrr_hat_part, dim3((unsigned)((ld + 255) / 256), nch), dim3(256), 0, st, (const int8_t *)P->X, R, p, ld, (int)n, k, (const double *)bd, cpc, hpart);
+    hipLaunchKernelGGL(k_mrr_hat_finish, dim3((unsigned)std::min<int64_t>((n * k + 255) / 256, 4096)), dim3(256), 0, st, (const double *)hpart, nch, ld, (int)n, k,
+                       (const double *)small, hatd);
+    MCHK(hipGetLastError());
+    MCHK(d2h(st, hat_out, hatd, sizeof(double) * n * k));
+  }
+  for (int t = 0; t < k; ++t) for (int64_t j = 0; j < p; ++j) b_out[(size_t)t * p + j] = bh[(size_t)j * k + t];   // p x k column-major
+  for (int t = 0; t < k; ++t) {
+    if (mu_out) mu_out[t] = mu[t];
+    if (h2_out) h2_out[t] = h2[t];
+    if (ve_out) ve_out[t] = ve[t];
+    if (MSx_out) MSx_out[t] = MSx[t];
+  }
+  for (int i = 0; i < k; ++i)
+    for (int j = 0; j < k; ++j) {   // column-major, as R's matrices (both are symmetric)
+      if (GC_out) GC_out[j * k + i] = GC[i * k + j];
+      if (vb_out) vb_out[j * k + i] = vb[i * k + j];
+    }
+  *its = numit;
+#undef MCHK
   return done(BWGR_OK);
 }
 

@@ -245,6 +245,30 @@ int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float R2, float 
 /* the marker order of sweep `upto` (0-based): the identity shuffled with std::mt19937(0), (1), ... (upto) (host only) */
 int bwgr_em_order(int64_t p, int upto, int32_t *order);
 
+/* ---- multi-trait ridge regression (mrr / mrr_float) ------------------------------------------------------
+ * Replaces SEXP MRR3(Y,X,maxit,tol,...) src/RcppEigen20230423.cpp:318-700 and MRR3F :704-1080 (R/mix.R:1271-1273: mrr = MRR3,
+ * mrr_float = MRR3F).  With the non-linear factor at 0 the two are one algorithm; one fp64 engine serves both.  Y: n x k column-major
+ * doubles, NaN = missing (Z = 0, :745-749); 1 <= k <= 16.  X: the panel's int8 genotypes, centred by their all-rows column means as
+ * the reference does (:763-765), so an uncentred and a centred copy of the same genotypes give the same fit; a panel switched to
+ * implicit centring (bwgr_panel_set_centred) gives the same result as before the switch.  fp32 panels are refused.
+ * opts[BWGR_MRR_*] (nopts of them; the rest take the reference's defaults, which BWGR_MRR_DEFAULTS lists in order).  Supported:
+ * maxit, tol, TH, HCS, XFA, ACS, NumXFA, R2, gc0, df0, updateMu, weight_prior_h2, weight_prior_gc, OneVarB, OneVarE, DeflateMax
+ * (read only with DeflateBy), verbose (host prints); cores is not an option (ignored by the R front-ends).  Refused with
+ * BWGR_EINVAL when not at their default: InnerGS, NoInv, NLfactor / NonLinearFactor, PenCor, MinCor, uncorH2below, roundGCupFrom,
+ * roundGCupTo, roundGCdownFrom, roundGCdownTo, bucketGCfrom, bucketGCto, DeflateBy.
+ * Outputs (host, caller-allocated, in the reference's order :1066-1078): mu[k], b[p x k], hat[n x k] (X_c b + mu for every row, the
+ * missing ones included), h2[k], GC[k x k], vb[k x k], ve[k], MSx[k], cnvB / cnvH2 / cnvV [maxit] (the first *its are set), its.
+ * b_Weights is all ones (no non-linear factor) and left to the caller. */
+enum { BWGR_MRR_MAXIT = 0, BWGR_MRR_TOL, BWGR_MRR_TH, BWGR_MRR_NLFACTOR, BWGR_MRR_INNERGS, BWGR_MRR_NOINV, BWGR_MRR_HCS, BWGR_MRR_XFA,
+       BWGR_MRR_ACS, BWGR_MRR_NUMXFA, BWGR_MRR_R2, BWGR_MRR_GC0, BWGR_MRR_DF0, BWGR_MRR_UPDATEMU, BWGR_MRR_WEIGHT_PRIOR_H2,
+       BWGR_MRR_WEIGHT_PRIOR_GC, BWGR_MRR_PENCOR, BWGR_MRR_MINCOR, BWGR_MRR_UNCORH2BELOW, BWGR_MRR_ROUNDGCUPFROM, BWGR_MRR_ROUNDGCUPTO,
+       BWGR_MRR_ROUNDGCDOWNFROM, BWGR_MRR_ROUNDGCDOWNTO, BWGR_MRR_BUCKETGCFROM, BWGR_MRR_BUCKETGCTO, BWGR_MRR_DEFLATEMAX,
+       BWGR_MRR_DEFLATEBY, BWGR_MRR_ONEVARB, BWGR_MRR_ONEVARE, BWGR_MRR_VERBOSE, BWGR_MRR_NOPTS };
+#define BWGR_MRR_MAXK 16
+#define BWGR_MRR_DEFAULTS {500, 10e-9, 0, 0, 0, 0, 0, 0, 0, 3, 0.5, 0.5, 1.0, 0, 0.01, 0.01, 0, 1.0, 0, 1.0, 1.0, 1.0, 0, 1.0, 1.0, 0.9, 0, 0, 0, 0}
+int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opts, int nopts, double *mu, double *b, double *hat, double *h2,
+             double *GC, double *vb, double *ve, double *MSx, double *cnvB, double *cnvH2, double *cnvV, int *its);
+
 /* ---- synthetic panels ----------------------------------------------------------
  * X_ij ~ Binomial(2, f_j), f_j ~ U(0.05,0.5), int8 column-major written to device memory Xdev
  * (ldx >= n); freq (p floats, device, may be NULL) receives f_j.  The p columns written are columns

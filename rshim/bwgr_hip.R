@@ -67,3 +67,15 @@ emBCpi <- function(y, gen, df = 10, R2 = 0.5, Pi = 0.75) .bwgr_em(6L, y, gen, df
 emBL   <- function(y, gen, R2 = 0.5, alpha = 0.02) .bwgr_em(7L, y, gen, 0, R2, alpha)
 emEN   <- function(y, gen, R2 = 0.5, alpha = 0.02) .bwgr_em(8L, y, gen, 0, R2, alpha)
 lasso  <- function(y, gen) .bwgr_em(9L, y, gen, 0, 0.5, 0)
+# multi-trait ridge regression, R/RcppExports.R:180-186 (MRR3, MRR3F) and R/mix.R:1271-1273 (mrr, mrr_float): same names, argument
+# order, defaults and return list.  `cores` is ignored; InnerGS, NoInv, NLfactor / NonLinearFactor, PenCor, MinCor, uncorH2below,
+# round*, bucket* and DeflateBy are refused away from their defaults (include/bwgr.h).  Y: NA = missing.
+.bwgr_mrr_opts <- function(maxit, tol, TH, NLfactor, InnerGS, NoInv, HCS, XFA, ACS, NumXFA, R2, gc0, df0, updateMu, weight_prior_h2, weight_prior_gc, PenCor, MinCor, uncorH2below, roundGCupFrom, roundGCupTo, roundGCdownFrom, roundGCdownTo, bucketGCfrom, bucketGCto, DeflateMax, DeflateBy, OneVarB, OneVarE, verbose)
+  as.double(c(maxit, tol, TH, NLfactor, InnerGS, NoInv, HCS, XFA, ACS, NumXFA, R2, gc0, df0, updateMu, weight_prior_h2, weight_prior_gc, PenCor, MinCor, uncorH2below, roundGCupFrom, roundGCupTo, roundGCdownFrom, roundGCdownTo, bucketGCfrom, bucketGCto, DeflateMax, DeflateBy, OneVarB, OneVarE, verbose))
+.bwgr_f32 <- function(x) { storage.mode(x) <- "double"; x[] <- as.double(sprintf("%.9g", x)); x }   # float-rounded, as MRR3F receives its inputs
+MRR3 <- function(Y, X, maxit = 500L, tol = 10e-9, cores = 1L, TH = FALSE, NLfactor = 0.0, InnerGS = FALSE, NoInv = FALSE, HCS = FALSE, XFA = FALSE, ACS = FALSE, NumXFA = 3L, R2 = 0.5, gc0 = 0.5, df0 = 1.0, updateMu = FALSE, weight_prior_h2 = 0.01, weight_prior_gc = 0.01, PenCor = 0.0, MinCor = 1.0, uncorH2below = 0.0, roundGCupFrom = 1.0, roundGCupTo = 1.0, roundGCdownFrom = 1.0, roundGCdownTo = 0.0, bucketGCfrom = 1.0, bucketGCto = 1.0, DeflateMax = 0.9, DeflateBy = 0.0, OneVarB = FALSE, OneVarE = FALSE, verbose = FALSE)
+  .Call("bwgrhip_MRR3", as.matrix(Y) * 1.0, .bwgr_panel(X), .bwgr_mrr_opts(maxit, tol, TH, NLfactor, InnerGS, NoInv, HCS, XFA, ACS, NumXFA, R2, gc0, df0, updateMu, weight_prior_h2, weight_prior_gc, PenCor, MinCor, uncorH2below, roundGCupFrom, roundGCupTo, roundGCdownFrom, roundGCdownTo, bucketGCfrom, bucketGCto, DeflateMax, DeflateBy, OneVarB, OneVarE, verbose))
+MRR3F <- function(Y, X, maxit = 500L, tol = 10e-9, cores = 1L, TH = FALSE, NonLinearFactor = 0.0, InnerGS = FALSE, NoInv = FALSE, HCS = FALSE, XFA = FALSE, ACS = FALSE, NumXFA = 3L, R2 = 0.5, gc0 = 0.5, df0 = 1.0, updateMu = FALSE, weight_prior_h2 = 0.01, weight_prior_gc = 0.01, PenCor = 0.0, MinCor = 1.0, uncorH2below = 0.0, roundGCupFrom = 1.0, roundGCupTo = 1.0, roundGCdownFrom = 1.0, roundGCdownTo = 0.0, bucketGCfrom = 1.0, bucketGCto = 1.0, DeflateMax = 0.9, DeflateBy = 0.0, OneVarB = FALSE, OneVarE = FALSE, verbose = FALSE)
+  .Call("bwgrhip_MRR3F", .bwgr_f32(as.matrix(Y)), .bwgr_panel(X), .bwgr_mrr_opts(maxit, tol, TH, NonLinearFactor, InnerGS, NoInv, HCS, XFA, ACS, NumXFA, R2, gc0, df0, updateMu, weight_prior_h2, weight_prior_gc, PenCor, MinCor, uncorH2below, roundGCupFrom, roundGCupTo, roundGCdownFrom, roundGCdownTo, bucketGCfrom, bucketGCto, DeflateMax, DeflateBy, OneVarB, OneVarE, verbose))
+mrr <- function(Y, X, ...) MRR3(Y, X, ...)
+mrr_float <- function(Y, X, ...) MRR3F(Y, X, ...)

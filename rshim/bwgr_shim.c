@@ -271,10 +271,44 @@ SEXP bwgrhip_KMUP2(SEXP panel, SEXP Use, SEXP b, SEXP d, SEXP xx, SEXP E, SEXP L
   return out;
 }
 
+/* multi-trait ridge regression: MRR3 / MRR3F(Y, X, maxit, tol, ...)  src/RcppEigen20230423.cpp:318-700, :704-1080 (R/mix.R:1271-1273:
+ * mrr, mrr_float) -> list(mu, b, hat, h2, GC, vb, ve, MSx, cnvB, cnvH2, cnvV, b_Weights, Its), :1066-1078.  Y: numeric n x k matrix, NA =
+ * missing; opts: the BWGR_MRR_* values in order (bwgr_hip.R builds them from the reference's arguments).  MRR3F's float inputs are
+ * rounded by the R front-end; the engine is the same. */
+static SEXP mrr_call(SEXP Y, SEXP panel, SEXP opts) {
+  bwgr_panel *P = panel_of(panel);
+  int64_t info[8]; chk(bwgr_panel_info(P, info));
+  const R_xlen_t n = info[0], p = info[1];
+  SEXP dim = Rf_getAttrib(Y, R_DimSymbol);
+  if (Rf_length(dim) != 2 || INTEGER(dim)[0] != n) Rf_error("Y must be a matrix with nrow(X) rows");
+  const int k = INTEGER(dim)[1], nopts = (int)XLENGTH(opts), maxit = (int)REAL(opts)[BWGR_MRR_MAXIT];
+  SEXP mu = PROTECT(Rf_allocVector(REALSXP, k)), b = PROTECT(Rf_allocMatrix(REALSXP, (int)p, k)), hat = PROTECT(Rf_allocMatrix(REALSXP, (int)n, k));
+  SEXP h2 = PROTECT(Rf_allocVector(REALSXP, k)), GC = PROTECT(Rf_allocMatrix(REALSXP, k, k)), vb = PROTECT(Rf_allocMatrix(REALSXP, k, k));
+  SEXP ve = PROTECT(Rf_allocVector(REALSXP, k)), MSx = PROTECT(Rf_allocVector(REALSXP, k)), W = PROTECT(Rf_allocMatrix(REALSXP, (int)p, k));
+  double *c1 = (double *)R_alloc(maxit > 0 ? maxit : 1, sizeof(double)), *c2 = (double *)R_alloc(maxit > 0 ? maxit : 1, sizeof(double));
+  double *c3 = (double *)R_alloc(maxit > 0 ? maxit : 1, sizeof(double));
+  int its = 0;
+  chk(bwgr_mrr(P, REAL(Y), k,   /* R's NA is a NaN: both mark a missing value */
+                REAL(opts), nopts, REAL(mu), REAL(b), REAL(hat), REAL(h2), REAL(GC), REAL(vb), REAL(ve), REAL(MSx), c1, c2, c3, &its));
+  SEXP cB = PROTECT(Rf_allocVector(REALSXP, its)), cH = PROTECT(Rf_allocVector(REALSXP, its)), cV = PROTECT(Rf_allocVector(REALSXP, its));
+  for (int i = 0; i < its; i++) { REAL(cB)[i] = c1[i]; REAL(cH)[i] = c2[i]; REAL(cV)[i] = c3[i]; }
+  for (R_xlen_t i = 0; i < p * k; i++) REAL(W)[i] = 1.0;                                /* b_Weights: no non-linear factor */
+  const char *nm[] = {"mu", "b", "hat", "h2", "GC", "vb", "ve", "MSx", "cnvB", "cnvH2", "cnvV", "b_Weights", "Its"};
+  SEXP out = PROTECT(named_list(13, nm));
+  SEXP v[] = {mu, b, hat, h2, GC, vb, ve, MSx, cB, cH, cV, W};
+  for (int i = 0; i < 12; i++) SET_VECTOR_ELT(out, i, v[i]);
+  SET_VECTOR_ELT(out, 12, Rf_ScalarReal((double)its));
+  UNPROTECT(13);
+  return out;
+}
+SEXP bwgrhip_MRR3(SEXP Y, SEXP panel, SEXP opts) { return mrr_call(Y, panel, opts); }
+SEXP bwgrhip_MRR3F(SEXP Y, SEXP panel, SEXP opts) { return mrr_call(Y, panel, opts); }
+
 static const R_CallMethodDef CallEntries[] = {   /* as src/RcppExports.cpp:1152-1228 registers _bWGR_* */
   {"bwgrhip_panel", (DL_FUNC)&bwgrhip_panel, 2}, {"bwgrhip_KMUP", (DL_FUNC)&bwgrhip_KMUP, 9}, {"bwgrhip_KMUP2", (DL_FUNC)&bwgrhip_KMUP2, 10},
   {"bwgrhip_Bayes", (DL_FUNC)&bwgrhip_Bayes, 8}, {"bwgrhip_Bayes2", (DL_FUNC)&bwgrhip_Bayes2, 9},
-  {"bwgrhip_wgr", (DL_FUNC)&bwgrhip_wgr, 14}, {"bwgrhip_em", (DL_FUNC)&bwgrhip_em, 7}, {NULL, NULL, 0}};
+  {"bwgrhip_wgr", (DL_FUNC)&bwgrhip_wgr, 14}, {"bwgrhip_em", (DL_FUNC)&bwgrhip_em, 7},
+  {"bwgrhip_MRR3", (DL_FUNC)&bwgrhip_MRR3, 3}, {"bwgrhip_MRR3F", (DL_FUNC)&bwgrhip_MRR3F, 3}, {NULL, NULL, 0}};
 
 void R_init_bwgrhip(DllInfo *dll) {              /* as R_init_bWGR, src/RcppExports.cpp:1230-1233 */
   R_registerRoutines(dll, NULL, CallEntries, NULL, NULL);
