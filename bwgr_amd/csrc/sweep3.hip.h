@@ -352,7 +352,7 @@ __device__ __forceinline__ void s3_streamer(const Sweep3Args &A) {
   int8_t *edig0 = reinterpret_cast<int8_t *>(smem + off); off += (size_t)2 * 16 * Rp;     // [parity][n][row]
   int8_t *ddig0 = reinterpret_cast<int8_t *>(smem + off); off += (size_t)2 * 16 * S2_DP;  // [parity][n][marker]
   int *outu = reinterpret_cast<int *>(smem + off); off += (size_t)64 * S3_OS * 4 * 4;     // [update wave][row 64][n]
-  int *outd = reinterpret_cast<int *>(smem + off); off += (size_t)8 * 32 * S3_OS * 4;     // [wave][marker 32][n]
+  off += (size_t)8 * 32 * S3_OS * 4;                                                    // (unused [wave][marker 32][n] scratch: kept, the layout and the LDS sizes count it)
   uint32_t *ctl_s = reinterpret_cast<uint32_t *>(smem + off);                            // [0] failure, [1] overflow
   const int sh = a.sc->e3_sh;
   const double S = s3_pow2(sh), invS = s3_pow2(-sh);
@@ -444,7 +444,7 @@ __device__ __forceinline__ void s3_streamer(const Sweep3Args &A) {
   unsigned long long lpre = 0ull;
   __syncthreads();
   S3ST_DECL;
-  const bool st_u = (w == 0 && tid == 0), st_d = (w == 0 && tid == 64 * NU);
+  [[maybe_unused]] const bool st_u = (w == 0 && tid == 0), st_d = (w == 0 && tid == 64 * NU);
 
   // one block; tp0..tp3: the register set of tile b+1 (committed here) and then of tile b+3 (requested here)
   auto step = [&](int b, s3_u4 &tp0, s3_u4 &tp1, s3_u4 &tp2, s3_u4 &tp3) -> bool {
@@ -610,7 +610,7 @@ __device__ __forceinline__ void s3_streamer_dma(const Sweep3Args &A) {
   static_assert(R3 == 128 || R3 == 256, "sixteen or thirty-two pieces");
   const int slab = w / A.sub, hsub = w - slab * A.sub;
   const int nb = a.blk_end - a.blk_begin;
-  constexpr int NU = R3 >> 6, ND = 8 - NU;   // update waves (64 rows each); the other waves form the dots
+  constexpr int NU = R3 >> 6;   // update waves (64 rows each); the other waves form the dots
   const int8_t *Xs = reinterpret_cast<const int8_t *>(a.X) + (size_t)slab * a.p * R + (size_t)hsub * R3;   // marker j: Xs + j * R
   const int64_t row0 = (int64_t)slab * R + (int64_t)hsub * R3;
   uint32_t *abortw = a.xflags + (size_t)a.K * SW_FLAG_STRIDE;
@@ -621,7 +621,7 @@ __device__ __forceinline__ void s3_streamer_dma(const Sweep3Args &A) {
   int8_t *edig0 = reinterpret_cast<int8_t *>(smem + off); off += (size_t)2 * 16 * Rp;     // [parity][n][row]
   int8_t *ddig0 = reinterpret_cast<int8_t *>(smem + off); off += (size_t)2 * 16 * S2_DP;  // [parity][n][marker]
   int *outu = reinterpret_cast<int *>(smem + off); off += (size_t)64 * S3_OS * 4 * 4;     // [update wave][row 64][n]
-  int *outd = reinterpret_cast<int *>(smem + off); off += (size_t)8 * 32 * S3_OS * 4;     // [wave][marker 32][n]
+  off += (size_t)8 * 32 * S3_OS * 4;                                                    // (unused [wave][marker 32][n] scratch: kept, the layout and the LDS sizes count it)
   uint32_t *ctl_s = reinterpret_cast<uint32_t *>(smem + off); off += 64;                 // [0] failure, [1] overflow
   float *drej_s = reinterpret_cast<float *>(smem + off);                                 // [block % NTB][marker]: the blocks' rejected steps, landed by DMA with the tiles
   const uint32_t drej_la = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) const unsigned char *)drej_s);
@@ -650,6 +650,7 @@ __device__ __forceinline__ void s3_streamer_dma(const Sweep3Args &A) {
   // drained the pieces a wave had just issued -- streamers alone 1.34 us per block, 1.03 with the atomics switched off.
   static_assert(NU == 2, "waves 0-1 update, 2-5 dots, 6-7 DMA");
   constexpr int NDOT = 4, PPW = NPC / 2;       // pieces per DMA wave and tile
+  static_assert(NU + NDOT == 6 && SW_THREADS - SW_MAXM == 64 * (NU + NDOT), "the DMA waves (role 2) are the last two: they digitise the rejected steps");
   constexpr int LPS = PPW + 2;                 // DMA requests per DMA wave and step: the tile's pieces and two 256-byte halves of a block's rejected steps
   const uint32_t lane_mk = (uint32_t)(lane / CH), lane_cr = (uint32_t)(lane % CH);
   const int j_lo = a.blk_begin * m, j_hi = min(a.p, a.blk_end * m);
@@ -790,27 +791,30 @@ __device__ __forceinline__ void s3_streamer_dma(const Sweep3Args &A) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   S3ST_DECL;
-  const bool st_u = (w == 0 && tid == 0), st_d = (w == 0 && tid == 64 * NU);
+  [[maybe_unused]] const bool st_u = (w == 0 && tid == 0), st_d = (w == 0 && tid == 64 * NU);
 
   // Before a step's barrier the tile the step reads must have landed.  Loads (the DMA requests are loads) return in order among themselves,
   // so "at most WN outstanding", with WN = the loads a dots wave issues in NTB - 2 steps (per step: two small requests and PPW pieces), holds only
   // once every load older than those -- the step's tile among them -- is back, whatever the atomics (no order against loads) are doing; and it
   // leaves the younger tiles in flight.  (The update waves issue no pieces: the count is harmless there.)
   constexpr int WN = (NTB - 2) * LPS;
-#define S3_DMA_BARRIER() do { if (wvs >= 6) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(WN) : "memory"); asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); } while (0)
-  auto step = [&](int b, auto par_c) -> bool {
+#define S3_DMA_BARRIER() do { if constexpr (DMA) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(WN) : "memory"); asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); } while (0)
+  // A step of one role: RL 0 the update waves, 1 the dots waves, 2 the DMA waves (each role runs a loop of its own: no role's state is live in another's)
+  auto step = [&](int b, auto par_c, auto role_c) -> bool {
     constexpr int PP = decltype(par_c)::value;   // b & 1 (BWGR_WORDS2)
+    constexpr int RL = decltype(role_c)::value;
+    constexpr bool UPD = RL == 0, DMA = RL == 2;
     const int mB = blk_m(b), par = b & 1;
     S3ST(0, st_u || st_d);
     int8_t *tile = tile0 + (size_t)(b % NTB) * tile_b;
     int8_t *edig = edig0 + (size_t)par * 16 * Rp;
     int8_t *ddig = ddig0 + (size_t)par * 16 * S2_DP;
     // A: what the included markers of block b - D changed
-    if (b >= D && upd && !(SDBG & 512)) { if (!fold_pre(b - D)) ctl_s[0] = 1u; }
+    if (b >= D && UPD && !(SDBG & 512)) { if (!fold_pre(b - D)) ctl_s[0] = 1u; }
 #ifndef BWGR_FOLD_EARLY
 #define BWGR_FOLD_EARLY 1
 #endif
-    if (BWGR_FOLD_EARLY && wvs < NU) {   // (the update waves only: no other wave keeps a compiler-visible load)
+    if (BWGR_FOLD_EARLY && UPD) {   // (the update waves only: no other wave keeps a compiler-visible load)
       // right behind this step's fold: the words of the list step b + 1 folds were requested a step ago -- look at them, request its columns (they
       // get the whole step to land); then the words for step b + 2
       if (!(SDBG & 512)) fold_prefetch((b + 1 < nb) ? b + 1 - D : -1, par_c);
@@ -818,10 +822,10 @@ __device__ __forceinline__ void s3_streamer_dma(const Sweep3Args &A) {
     }
     S3ST(1, st_u);
     // B: digits of the residual rows and of this block's rejected steps
-    if (upd) {
+    if constexpr (UPD) {
       if ((unsigned long long)(e_own + (1ll << 54)) >> 55) ctl_s[1] = 1u;       // left the 55-bit range
       s3_put_digits7(e_own, edig + 64 * wave + lane, Rp);
-    } else if (tid >= SW_THREADS - SW_MAXM) {                                    // the last two waves (never update waves)
+    } else if constexpr (DMA) {                                                  // the last two waves: tid >= SW_THREADS - SW_MAXM
       const double qd = (tid - (SW_THREADS - SW_MAXM) < mB) ? rint((double)drej_s[(b % NTB) * SW_MAXM + (tid - (SW_THREADS - SW_MAXM))] * S) : 0.0;   // (unused markers: zero steps; set b - 1 landed behind the last barrier)
       if (!(fabs(qd) < 18014398509481984.0)) ctl_s[1] = 1u;                      // 2^54
       s3_put_digits7((long long)qd, ddig + (tid - (SW_THREADS - SW_MAXM)), S2_DP);
@@ -836,13 +840,13 @@ __device__ __forceinline__ void s3_streamer_dma(const Sweep3Args &A) {
     S3ST(3, st_u || st_d);
 #endif
     if (ctl_s[0]) { if (tid == 0) a.sc->error = 1u; return false; }
-    tile_issue(b + NTB - 1);   // (always: the wait counts rely on it; past the end the last tile again)
+    if constexpr (DMA) tile_issue(b + NTB - 1);   // (always: the wait counts rely on it; past the end the last tile again)
     // C: tile b+1 (in registers for two iterations) lands in the other buffer, whose last reader was block b-1; the loads of
     // tile b+3 go out into the registers just freed; the list of block b+1-D and the rejected steps of block b+1 are requested
     S3ST(6, st_u || st_d);
     {   // the small requests first (older than the tile loads on the in-order memory counter, so waiting for them does not wait
         // for the tile), every one unconditional: a load under a branch makes the compiler drain the counter in front of it
-      if (!BWGR_FOLD_EARLY && wvs < NU) {   // (the update waves only: no other wave keeps a compiler-visible load)
+      if (!BWGR_FOLD_EARLY && UPD) {   // (the update waves only: no other wave keeps a compiler-visible load)
         // the words of the list step b + 1 folds were requested a step ago: look at them, request its columns; then the words for step b + 2
         if (!(SDBG & 512)) fold_prefetch((b + 1 < nb) ? b + 1 - D : -1, par_c);
         S3_PAR(lmid, lw1) = ld_agent_raw64(lists_w + (size_t)(a.blk_begin + max(min(b + 2 + BWGR_WORDS2, nb - 1) - D, 0)) * S3_LSTRIDE + lane);
@@ -850,7 +854,7 @@ __device__ __forceinline__ void s3_streamer_dma(const Sweep3Args &A) {
     }
     S3ST(7, st_u || st_d);
     S3ST(4, st_u || st_d);
-    if (upd) {
+    if constexpr (UPD) {
       // ---- slab update with the rejected steps: out[row][n] = sum_markers x[row][marker] * digit_n(drej[marker]) ----
       // lane (m16, grp): row quad 16 wave + m16 (rows 4 * that + k for accumulator k); k slots (dword u, byte q) of step s0 are the
       // markers s0 + 16 u + 4 grp + q (the interleave keeps the four lane groups on different LDS banks)
@@ -902,10 +906,10 @@ __device__ __forceinline__ void s3_streamer_dma(const Sweep3Args &A) {
         e_own -= v;
       }
       S3ST(5, st_u);
-    } else {
-      // ---- slab dots of block b against the digits of e: markers in groups of 16, groups gm and gm + ND together on wave
+    } else if constexpr (RL == 1) {
+      // ---- slab dots of block b against the digits of e: markers in groups of 16, groups gm and gm + NDOT together on wave
       // NU + gm (the two groups' MFMAs, LDS round trips and atomics overlap) ----
-      for (int gm = wave - NU; wvs < NU + NDOT && 16 * gm < m; gm += 2 * NDOT) {
+      for (int gm = wave - NU; 16 * gm < m; gm += 2 * NDOT) {
         const int gm2 = gm + NDOT;
         const bool two = 16 * gm2 < m;
         const int8_t *bp = edig + (size_t)m16 * Rp + 16 * grp;
@@ -934,10 +938,18 @@ __device__ __forceinline__ void s3_streamer_dma(const Sweep3Args &A) {
     }
     return true;
   };
-  for (int b = 0; b < nb; b += 2) {
-    if (!step(b, std::integral_constant<int, 0>{})) return;
-    if (b + 1 < nb && !step(b + 1, std::integral_constant<int, 1>{})) return;
-  }
+  auto run = [&](auto role_c) -> bool {
+    for (int b = 0; b < nb; b += 2) {
+      if (!step(b, std::integral_constant<int, 0>{}, role_c)) return false;
+      if (b + 1 < nb && !step(b + 1, std::integral_constant<int, 1>{}, role_c)) return false;
+    }
+    return true;
+  };
+  bool ok;
+  if (wvs < NU) ok = run(std::integral_constant<int, 0>{});
+  else if (wvs < NU + NDOT) ok = run(std::integral_constant<int, 1>{});
+  else ok = run(std::integral_constant<int, 2>{});
+  if (!ok) return;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the requests past the end)
 #undef S3_DMA_BARRIER
 #undef S3_PAR
@@ -1291,37 +1303,6 @@ __device__ __forceinline__ void s3_sequencer(const Sweep3Args &A) {
   // wave waits for those requests anyway.
 #define S3_ROLE_BARRIER() do { if (BWGR_ROLEBAR) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); } while (0)
   const int wvu = __builtin_amdgcn_readfirstlane(wave);   // the role as a scalar: real branches, every wave runs its own role's code (and barrier) only
-  auto helper_phase = [&](int c) {   // block c >= 1, while wave 0 runs block c-1
-    if (wvu == 1) { if (!(SDBG & 32768)) { if (!poll_q(c)) ctrl_s[0] = 0; } S3ST(2, tid == 64); S3_ROLE_BARRIER(); }
-    else if (wvu <= 3) { if (!(SDBG & 8192)) {
-      // the requests for block c + 1 (always: past the end the last block again, the wait counts rely on it), then the wait for block c's, which were
-      // issued a phase ago and are used by wave 0 after this phase's barrier
-      const int o_p0 = f_p0, o_cnt = f_cnt, o_n = f_n; const double o_cf = f_cf;
-      far_plan_a(c + 1);             // (far-field shares 2 and 3: the plan's LDS round trips under the requests' issue)
-      stage_issue(c + 1, 0);
-      far_plan_b(c + 1, wave);
-      stage_issue(c + 1, 1);
-      far_plan_c(c + 1);
-      stage_issue(c + 1, 2);
-      S3_STG_WAIT();                 // ... whose rows, requested at the end of the last phase, are older than the pieces just requested: landed too
-      far_consume(c, wave, o_p0, o_cnt, o_n, o_cf);
-      far_request(c + 1, wave);
-    } S3ST(2, tid == 128 || tid == 192); S3_ROLE_BARRIER(); }
-    else if (wvu == 4) { far_touch(c); S3_ROLE_BARRIER(); }   // (the fourth SIMD's other wave is wave 0, whose dependent chain wants the issue slots: a handful of instructions only)
-    else if (wvu <= 6) {
-      const int o_p0 = f_p0, o_cnt = f_cnt, o_n = f_n; const double o_cf = f_cf;
-      far_plan(c + 1, wave - 5);
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      S3ST(5, tid == 320);
-      far_consume(c, wave - 5, o_p0, o_cnt, o_n, o_cf);
-      S3ST(6, tid == 320);
-      far_request(c + 1, wave - 5);
-      S3ST(7, tid == 320);
-      S3ST(2, tid == 384);
-      S3_ROLE_BARRIER();
-    }
-    else { if (c >= 2 && !(SDBG & 4096)) finish_block(c - 2); touch(c + PF); S3ST(2, tid == 448); S3_ROLE_BARRIER(); }
-  };
 
   // ---- prologue: block 0 ----
   if (tid < 40) ctrl_s[tid] = (tid == 0) ? 1 : 0;   // (pos_s: block 0's entries begin at ring position 0)
@@ -1333,38 +1314,57 @@ __device__ __forceinline__ void s3_sequencer(const Sweep3Args &A) {
   else if (wave == 7) { for (int c = 0; c < PF; ++c) touch(c); if ((a.flags & SWF_VB_VEC) && !A.skip_vb) chi_request(0); }
   __syncthreads();
   if (ctrl_s[0] == 0) { if (tid == 0) a.sc->error = 1u; asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); return; }
-
-  const bool sq0 = (tid == 0), sq1 = (tid == 64), sq2 = (tid == 128), sq4 = (tid == 320), sq3 = (tid == 192), sq6 = (tid == 384), sq7 = (tid == 448);
-  // wave 0's included-marker path, counted in instructions: the packed row's byte offset from a lane-indexed table by one v_readlane
-  // (lane = the marker within its group; entry j of packed row k sits at prow(k) + j - k - 1), the lane's dword of a cross row, and the
-  // LDS addresses of the packed blocks and of the row slots as scalars
-  const int tabp0 = 2 * (lane * (m - 1) - lane * (lane - 1) / 2 - lane - 1);
-  const int tabp1 = 2 * ((64 + lane) * (m - 1) - (64 + lane) * (63 + lane) / 2 - (64 + lane) - 1);
-  const uint32_t rolane = (uint32_t)min(lane * 4, rowbytes - 4);
-  const uint32_t rolane16 = (uint32_t)min(lane * 16, 2 * rowbytes - 16);   // (gx12: a marker's two rows are 2 * rowbytes contiguous bytes, a multiple of 16)
-  constexpr bool near12 = G16;   // (16-bit panels always carry gx12; block sizes are multiples of 16)
-  const unsigned char *gpd_lane = gpd_s + 2 * lane;   // this lane's entry of a packed row, before the row's and the buffer's offsets
-  int gpd_off = 0;                                     // (b % 3) * S3_GPD_BYTES, stepped once per block
-  const uint32_t rowx_la = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) const unsigned char *)rowx_s);
-  const bool altb2 = (a.flags & SWF_ALT_B2) != 0;
-  if (wave == 0 && !(SDBG & 1)) __builtin_amdgcn_s_setprio(3);   // the chain's wave goes first wherever it shares an issue port
-  // wave 0: what the included markers of block b change in blocks b+1 and b+2 (distances 1 and 2), accumulated as they appear
-  double rnext0 = 0.0, rnext1 = 0.0, rnxt20 = 0.0, rnxt21 = 0.0;
-  int pend_n = 0, pend_p = 0;              // row slots requested by the block before and not applied yet; ring position of their first entry
-  bool pend_u1 = false, pend_u2 = false;   // ... and whether that block had a block at distance 1 / 2
-  // implicitly centred columns (CEN): wave 0 carries U = -(E_0 + cpre[first block]) / n + sum over the included markers so far of (s_k / n) corr_k;
-  // a lane's centred dot is its raw one plus s_j * U (the rejected steps' share sits in the staged spec), an included marker's row G_kj becomes
-  // G_kj - s_j s_k / n for the later lanes of its own block, and every later block sees it through U
-  const double ninv = a.ninv;
-  const double cen_u0 = CEN ? a.sc->cen_u0 : 0.0;
-  double cenU = cen_u0;
-  const GT *gx0_w0 = reinterpret_cast<const GT *>(A.gx[0]) + (size_t)a.blk_begin * m * m, *gx1_w0 = reinterpret_cast<const GT *>(A.gx[1]) + (size_t)a.blk_begin * m * m;
-  const unsigned char *g12_w0 = A.gx12 + (size_t)a.blk_begin * m * 2 * rowbytes;
-  for (int b = 0; b < nb; ++b) {
-    const int mB = blk_m(b), blk = a.blk_begin + b;
-    const bool have_next = (b + 1 < nb);
-    S3ST(0, sq0 || sq1 || sq2 || sq4 || sq3 || sq6 || sq7);
-    if (wvu == 0 && !(SDBG & 16384)) {
+  // ---- the block loops: one per role ----
+  // Every wave branches once on its role and runs a block loop of its own, so that a role's loop-carried state is live in that loop only.  (One
+  // loop with the roles as branches of each block kept the union of every role's state live through every role's code: 99 SGPRs spilled to VGPR
+  // lanes, read back by v_readlane on every wave, and register copies at the join behind the barrier.)  The barrier schedule is the same in
+  // every role: one barrier per block (S3_ROLE_BARRIER, at the end of the role's work), then the abort check.
+  [[maybe_unused]] const bool sq0 = (tid == 0), sq1 = (tid == 64), sq2 = (tid == 128), sq4 = (tid == 320), sq3 = (tid == 192), sq6 = (tid == 384), sq7 = (tid == 448);
+  // block b's rounds are done, its list is in LDS; everything block b+1 needs from the helpers is in LDS.  (A bare barrier:
+  // __syncthreads() would drain the far-field rows that are meant to stay in flight across it.)
+#define S3_BLOCK_END(SQ_, ABORT_) \
+    if (!BWGR_ROLEBAR) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
+    S3ST(4, SQ_); \
+    if (ctrl_s[0] == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); ABORT_; }   /* (no DMA may land after the workgroup has gone) */
+  // a helper's loop: its phase for block b + 1 (ending in the role's barrier) while wave 0 runs block b, a bare barrier in the last block;
+  // false: the workgroup aborts
+  auto helper_loop = [&](auto &&phase, const bool sq) -> bool {
+    for (int b = 0; b < nb; ++b) {
+      S3ST(0, sq);
+      if (b + 1 < nb) { phase(b + 1); S3ST(1, sq); }
+      else S3_ROLE_BARRIER();
+      S3_BLOCK_END(sq, return false)
+    }
+    return true;
+  };
+  if (wvu == 0) {
+    // wave 0's included-marker path, counted in instructions: the packed row's byte offset from a lane-indexed table by one v_readlane
+    // (lane = the marker within its group; entry j of packed row k sits at prow(k) + j - k - 1), the lane's dword of a cross row, and the
+    // LDS addresses of the packed blocks and of the row slots as scalars
+    const int tabp0 = 2 * (lane * (m - 1) - lane * (lane - 1) / 2 - lane - 1);
+    const int tabp1 = 2 * ((64 + lane) * (m - 1) - (64 + lane) * (63 + lane) / 2 - (64 + lane) - 1);
+    const uint32_t rolane16 = (uint32_t)min(lane * 16, 2 * rowbytes - 16);   // (gx12: a marker's two rows are 2 * rowbytes contiguous bytes, a multiple of 16)
+    const unsigned char *gpd_lane = gpd_s + 2 * lane;   // this lane's entry of a packed row, before the row's and the buffer's offsets
+    int gpd_off = 0;                                     // (b % 3) * S3_GPD_BYTES, stepped once per block
+    const uint32_t rowx_la = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) const unsigned char *)rowx_s);
+    const bool altb2 = (a.flags & SWF_ALT_B2) != 0;
+    if (wave == 0 && !(SDBG & 1)) __builtin_amdgcn_s_setprio(3);   // the chain's wave goes first wherever it shares an issue port
+    // wave 0: what the included markers of block b change in blocks b+1 and b+2 (distances 1 and 2), accumulated as they appear
+    double rnext0 = 0.0, rnext1 = 0.0, rnxt20 = 0.0, rnxt21 = 0.0;
+    int pend_n = 0, pend_p = 0;              // row slots requested by the block before and not applied yet; ring position of their first entry
+    bool pend_u1 = false, pend_u2 = false;   // ... and whether that block had a block at distance 1 / 2
+    // implicitly centred columns (CEN): wave 0 carries U = -(E_0 + cpre[first block]) / n + sum over the included markers so far of (s_k / n) corr_k;
+    // a lane's centred dot is its raw one plus s_j * U (the rejected steps' share sits in the staged spec), an included marker's row G_kj becomes
+    // G_kj - s_j s_k / n for the later lanes of its own block, and every later block sees it through U
+    const double ninv = a.ninv;
+    const double cen_u0 = CEN ? a.sc->cen_u0 : 0.0;
+    double cenU = cen_u0;
+    const GT *gx0_w0 = reinterpret_cast<const GT *>(A.gx[0]) + (size_t)a.blk_begin * m * m, *gx1_w0 = reinterpret_cast<const GT *>(A.gx[1]) + (size_t)a.blk_begin * m * m;
+    const unsigned char *g12_w0 = A.gx12 + (size_t)a.blk_begin * m * 2 * rowbytes;
+    if (!(SDBG & 1)) __builtin_amdgcn_s_setprio(3);   // the chain's wave goes first wherever it shares an issue port
+    auto block = [&](int b) {
+      const int mB = blk_m(b), blk = a.blk_begin + b;
+      const bool have_next = (b + 1 < nb);
       // Wave 0 is one long dependent chain, so everything here is counted in instructions.  Dead lanes of a ragged last block need
       // no masks: k_prestage fills their constants so that they reject for certain, and their q, spec and far terms are zero.
       const StageBuf &st = stage[b % 3];
@@ -1545,26 +1545,65 @@ __device__ __forceinline__ void s3_sequencer(const Sweep3Args &A) {
       S3ST(3, sq0);
       gpd_off = (gpd_off == 2 * S3_GPD_BYTES) ? 0 : gpd_off + S3_GPD_BYTES;
       S3_ROLE_BARRIER();
-    } else if (have_next && wvu != 0) {
-      helper_phase(b + 1);
-      S3ST(1, sq1 || sq2 || sq4 || sq3 || sq6 || sq7);
-    } else S3_ROLE_BARRIER();
-    // block b's rounds are done, its list is in LDS; everything block b+1 needs from the helpers is in LDS.  (A bare barrier:
-    // __syncthreads() would drain the far-field rows that are meant to stay in flight across it.)
-    if (!BWGR_ROLEBAR) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    S3ST(4, sq0 || sq1 || sq2 || sq4 || sq3 || sq6 || sq7);
-    if (ctrl_s[0] == 0) { if (tid == 0) a.sc->error = 1u; asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); return; }   // (no DMA may land after the workgroup has gone)
-  }
-  S3ST_FLUSH(16, sq0); S3ST_FLUSH(24, sq1); S3ST_FLUSH(32, sq2); S3ST_FLUSH(40, sq4); S3ST_FLUSH(48, sq3); S3ST_FLUSH(56, sq6); S3ST_FLUSH(64, sq7);
-  if constexpr (CEN) { if (tid == 0) a.sc->cen_c = cenU - cen_u0; }   // the included markers' share of the shift (k_cen_end)
-  if (wave >= 1 && wave <= 4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the poll and staging waves' requests past the end; wave 4's touches)
-  if (wave == 7) {   // the last two blocks
+    };
+    for (int b = 0; b < nb; ++b) {
+      S3ST(0, sq0);
+      if (!(SDBG & 16384)) block(b);
+      else S3_ROLE_BARRIER();
+      S3_BLOCK_END(sq0, if (tid == 0) a.sc->error = 1u; return)
+    }
+    S3ST_FLUSH(16, sq0);
+    if constexpr (CEN) { if (tid == 0) a.sc->cen_c = cenU - cen_u0; }   // the included markers' share of the shift (k_cen_end)
+  } else if (wvu == 1) {   // the slab dots of block c
+    if (!helper_loop([&](int c) { if (!(SDBG & 32768)) { if (!poll_q(c)) ctrl_s[0] = 0; } S3ST(2, tid == 64); S3_ROLE_BARRIER(); }, sq1)) return;
+    S3ST_FLUSH(24, sq1);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the requests past the end)
+  } else if (wvu <= 3) {   // staging, and far-field shares 2 and 3
+    if (!helper_loop([&](int c) {
+      if (!(SDBG & 8192)) {
+        // the requests for block c + 1 (always: past the end the last block again, the wait counts rely on it), then the wait for block c's, which were
+        // issued a phase ago and are used by wave 0 after this phase's barrier
+        const int o_p0 = f_p0, o_cnt = f_cnt, o_n = f_n; const double o_cf = f_cf;
+        far_plan_a(c + 1);             // (far-field shares 2 and 3: the plan's LDS round trips under the requests' issue)
+        stage_issue(c + 1, 0);
+        far_plan_b(c + 1, wave);
+        stage_issue(c + 1, 1);
+        far_plan_c(c + 1);
+        stage_issue(c + 1, 2);
+        S3_STG_WAIT();                 // ... whose rows, requested at the end of the last phase, are older than the pieces just requested: landed too
+        far_consume(c, wave, o_p0, o_cnt, o_n, o_cf);
+        far_request(c + 1, wave);
+      }
+      S3ST(2, tid == 128 || tid == 192); S3_ROLE_BARRIER(); }, sq2 || sq3)) return;
+    S3ST_FLUSH(32, sq2); S3ST_FLUSH(48, sq3);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  } else if (wvu == 4) {   // far-field touches (the fourth SIMD's other wave is wave 0, whose dependent chain wants the issue slots: a handful of instructions only)
+    if (!helper_loop([&](int c) { far_touch(c); S3_ROLE_BARRIER(); }, false)) return;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  } else if (wvu <= 6) {   // far-field shares 0 and 1
+    if (!helper_loop([&](int c) {
+      const int o_p0 = f_p0, o_cnt = f_cnt, o_n = f_n; const double o_cf = f_cf;
+      far_plan(c + 1, wave - 5);
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      S3ST(5, tid == 320);
+      far_consume(c, wave - 5, o_p0, o_cnt, o_n, o_cf);
+      S3ST(6, tid == 320);
+      far_request(c + 1, wave - 5);
+      S3ST(7, tid == 320);
+      S3ST(2, tid == 384);
+      S3_ROLE_BARRIER(); }, sq4 || sq6)) return;
+    S3ST_FLUSH(40, sq4); S3ST_FLUSH(56, sq6);
+  } else {   // wave 7: the finished blocks' outputs, two blocks behind; the touches
+    if (!helper_loop([&](int c) { if (c >= 2 && !(SDBG & 4096)) finish_block(c - 2); touch(c + PF); S3ST(2, tid == 448); S3_ROLE_BARRIER(); }, sq7)) return;
+    S3ST_FLUSH(64, sq7);
+    // the last two blocks
     if (nb >= 2) finish_block(nb - 2);
     finish_block(nb - 1);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { sum_d += __shfl_down(sum_d, o, 64); sum_b2 += __shfl_down(sum_b2, o, 64); }
     if (lane == 0) { a.sc->sum_d += sum_d; a.sc->sum_b2 += sum_b2; }
   }
+#undef S3_BLOCK_END
 }
 
 // ------------------------------------------------------------------------------------------------------------------
