@@ -3793,6 +3793,31 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
 //               [k_mrr_pass(b-1 | b), k_mrr_solve(b)] for every block -> k_mrr_pass(last | -) -> k_mrr_ey -> (host: ve) ->
 //               k_mrr_tilde -> (host: vb, GC, bending, pinv) -> k_mrr_mu_shift (updateMu)
 // ------------------------------------------------------------------------------------------------
+// The LDS plan of k_mrr_solve and k_mrr_linv for k traits and npat missingness patterns, decided here and nowhere else: the solve stages
+// the markers' k x k inverses (64 k^2 doubles) when they fit beside its fixed arrays, then as many of the block's per-pattern Gram matrices
+// as the rest of the budget holds (ngl); it reads patterns ngl.. from global memory, and without linv_lds fetches each marker's row of
+// its inverse one marker ahead.  bwgr_debug_mrr_plan exposes it to the CPU tests.
+static constexpr size_t MRR_LDS_MAX = 160 * 1024;
+struct MrrPlan { int linv_lds, ngl; size_t lds_solve, lds_linv; };
+static MrrPlan mrr_plan(int k, int npat) {
+  MrrPlan pl;
+  const size_t lds_fixed = mrr_solve_lds(0, 0), linv_b = sizeof(double) * MRR_MB * k * k;
+  pl.linv_lds = lds_fixed + linv_b <= MRR_LDS_MAX ? 1 : 0;
+  pl.ngl = (int)std::min<size_t>((size_t)npat, (MRR_LDS_MAX - lds_fixed - (pl.linv_lds ? linv_b : 0)) / (MRR_MB * MRR_MB * 4));
+  pl.lds_solve = mrr_solve_lds(pl.ngl, pl.linv_lds ? MRR_MB * k * k : 0);
+  pl.lds_linv = linv_b;
+  return pl;
+}
+extern "C" int bwgr_debug_mrr_plan(int k, int npat, int *linv_lds, int *ngl, int64_t *solve_lds_bytes, int64_t *linv_lds_bytes) {
+  if (k < 1 || k > MRR_KMAX || npat < 1 || npat > k) return BWGR_EINVAL;
+  const MrrPlan pl = mrr_plan(k, npat);
+  if (linv_lds) *linv_lds = pl.linv_lds;
+  if (ngl) *ngl = pl.ngl;
+  if (solve_lds_bytes) *solve_lds_bytes = (int64_t)pl.lds_solve;
+  if (linv_lds_bytes) *linv_lds_bytes = (int64_t)pl.lds_linv;
+  return BWGR_OK;
+}
+
 extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opts, int nopts, double *mu_out, double *b_out, double *hat_out,
                         double *h2_out, double *GC_out, double *vb_out, double *ve_out, double *MSx_out, double *cnvB, double *cnvH2, double *cnvV,
                         int *its) {
@@ -3902,8 +3927,8 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   MCHK(hipMemcpyAsync(ed, y.data(), sizeof(double) * k * ld, hipMemcpyHostToDevice, st));          // e = y, :825
   MCHK(hipMemcpyAsync(sumyd, sumy.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
   MCHK(hipMemsetAsync(bd, 0, sizeof(double) * p * k, st));                                         // b = 0, :823
-  MCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_linv), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  MCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_solve), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  MCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_linv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
+  MCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
   hipLaunchKernelGGL(k_mrr_setup_cols, dim3((unsigned)std::min<int64_t>((p + 3) / 4, 8192)), dim3(256), 0, st, (const int8_t *)P->X, R, (int)n, p, ld,
                      (const uint32_t *)zbd, (const double *)yd, (const double *)sumyd, mc, xbar, Sd, XXd, XSXd, tilde);
   MCHK(hipGetLastError());
@@ -3939,12 +3964,7 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   const double logtol = log10(o.tol);
   std::vector<double> ey, db2h(k), vb0, h20, d(k);
   int numit = 0;
-  const size_t lds_linv = sizeof(double) * 64 * k * k;
-  // the solve's LDS: the markers' inverses when they fit, then as many block Gram matrices as the rest holds
-  const size_t lds_max = 160 * 1024, lds_fixed = mrr_solve_lds(0, 0), linv_b = sizeof(double) * MRR_MB * k * k;
-  const int linv_lds = lds_fixed + linv_b <= lds_max ? 1 : 0;
-  const int ngl = (int)std::min<size_t>((size_t)npat, (lds_max - lds_fixed - (linv_lds ? linv_b : 0)) / (MRR_MB * MRR_MB * 4));
-  const size_t lds_solve = mrr_solve_lds(ngl, linv_lds ? MRR_MB * k * k : 0);
+  const MrrPlan plan = mrr_plan(k, npat);
   while (numit < o.maxit) {
     vb0 = vb; h20 = h2;
     std::shuffle(order.begin(), order.end(), std::mt19937(numit));                                 // :869 (cumulative, as there)
@@ -3953,7 +3973,7 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
     hipLaunchKernelGGL(k_mrr_gram, dim3((unsigned)nblk, (unsigned)((npat + 3) / 4)), dim3(256), 0, st, (const int8_t *)Xs, R, p, ld, (const uint8_t *)zmd, npat, gram);
     for (int t = 0; t < k; ++t) mc.iVe[t] = 1.0 / ve[t];
     MCHK(hipMemcpyAsync(small + 512, iG.data(), sizeof(double) * k * k, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_mrr_linv, dim3((unsigned)((p + 63) / 64)), dim3(64), lds_linv, st, (const double *)XXd, (const double *)(small + 512), mc, p, Linv);
+    hipLaunchKernelGGL(k_mrr_linv, dim3((unsigned)((p + 63) / 64)), dim3(64), plan.lds_linv, st, (const double *)XXd, (const double *)(small + 512), mc, p, Linv);
     MCHK(hipMemsetAsync(db2, 0, sizeof(double) * MRR_KMAX, st));
     MCHK(hipGetLastError());
     for (int64_t blk = 0; blk <= nblk; ++blk) {
@@ -3962,9 +3982,9 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
       hipLaunchKernelGGL(k_mrr_pass, dim3(G), dim3(256), 0, st, pa);
       if (blk == nblk) break;
       MrrSolveArgs sa; sa.part = part; sa.G = G; sa.order = ordd; sa.blk = (int)blk; sa.p = p; sa.gram = gram; sa.xbar = xbar; sa.S = Sd; sa.XX = XXd;
-      sa.Linv = Linv; sa.b = bd; sa.dB = dB; sa.db2 = db2; sa.ngl = ngl; sa.linv_lds = linv_lds;
+      sa.Linv = Linv; sa.b = bd; sa.dB = dB; sa.db2 = db2; sa.ngl = plan.ngl; sa.linv_lds = plan.linv_lds;
 
-      hipLaunchKernelGGL(k_mrr_solve, dim3(1), dim3(256), lds_solve, st, sa, mc);
+      hipLaunchKernelGGL(k_mrr_solve, dim3(1), dim3(256), plan.lds_solve, st, sa, mc);
     }
     MCHK(hipGetLastError());
     // residual variance (:916-924)

@@ -268,6 +268,12 @@ enum { BWGR_MRR_MAXIT = 0, BWGR_MRR_TOL, BWGR_MRR_TH, BWGR_MRR_NLFACTOR, BWGR_MR
 #define BWGR_MRR_DEFAULTS {500, 10e-9, 0, 0, 0, 0, 0, 0, 0, 3, 0.5, 0.5, 1.0, 0, 0.01, 0.01, 0, 1.0, 0, 1.0, 1.0, 1.0, 0, 1.0, 1.0, 0.9, 0, 0, 0, 0}
 int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opts, int nopts, double *mu, double *b, double *hat, double *h2,
              double *GC, double *vb, double *ve, double *MSx, double *cnvB, double *cnvH2, double *cnvV, int *its);
+/* host arithmetic of bwgr_mrr's LDS plan for k traits with npat distinct missingness patterns (1 <= npat <= k <= 16, else
+ * BWGR_EINVAL; needs no GPU): linv_lds = 1 when the per-block solve keeps the markers' k x k inverses in LDS (else it fetches each
+ * marker's row of its inverse from global memory, one marker ahead); ngl = how many of the block's per-pattern Gram matrices it stages
+ * in LDS (patterns ngl..npat-1 are read from global memory); the dynamic LDS bytes of the solve and of the inverses' kernel.  Any
+ * output may be NULL. */
+int bwgr_debug_mrr_plan(int k, int npat, int *linv_lds, int *ngl, int64_t *solve_lds_bytes, int64_t *linv_lds_bytes);
 
 /* ---- synthetic panels ----------------------------------------------------------
  * X_ij ~ Binomial(2, f_j), f_j ~ U(0.05,0.5), int8 column-major written to device memory Xdev
