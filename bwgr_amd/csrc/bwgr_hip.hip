@@ -932,7 +932,7 @@ __global__ void k_redo_clear(ChainScalars *sc) { sc->redo = 0u; }
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
-// The environment switches, every one the library reads, read once: when a root panel is made.  Clones copy the
+// The environment switches, every one the library reads, read once: when a root panel is made.  Clones share the
 // root's; the scratch panels of KMUP2, bagging and the EM family, and groups take the panels' they are made for.  First-character switches
 // hold that character (-1: unset); numeric ones hold their value as parsed (0: unset); the rest their parsed meaning.
 struct Switches {
@@ -976,78 +976,81 @@ static Switches read_switches() {
 }
 
 // ------------------------------------------------------------------------------------------------
-struct bwgr_panel {
+// A resident panel is its data (PanelData) and the handles on it (bwgr_panel).  The root handle is made with the data -- by
+// bwgr_panel_create, or as a scratch panel of KMUP2, wgr or bwgr_em -- and frees it; a clone (bwgr_panel_clone) is another handle on the
+// same data.  Every handle owns its streams and the scratch its sweeps write.  The data does not change while a clone is alive: it is
+// built with the root, and bwgr_panel_set_centred refuses on a clone and while any chain is alive.
+struct PanelData {
   int device = 0;
-  hipStream_t stream = nullptr;
   int64_t n = 0, p = 0, ld = 0;
   int is_f32 = 0;
   int m = 0, K = 0, R = 0;
   int64_t nblocks = 0;
-  void *X = nullptr, *gram = nullptr, *gramx = nullptr, *gramx2 = nullptr, *gramx3 = nullptr, *gramp = nullptr;
-  double *xspec2 = nullptr, *xspec3 = nullptr;   // [nblocks][SW_MAXM]: speculative cross terms of the lag-3 / lag-4 pipelines (k_spec)
-  bool lag4_ok = false;       // the lag-4 streamer (ring of four tiles) fits the LDS at this geometry
-  int nfeed = 2;              // q feeder workgroups of k_sweep2 (one gather + sum of K KB takes about a block period at K = 40)
-  uint16_t *gramp16 = nullptr, *gramx16 = nullptr;   // 16-bit copies for the sequencer (int8 panels)
-  int *gram16_bad = nullptr;
-  bool gram16 = false;        // the copies are exact: every entry in 0..65535
   int pstride = 0;
   size_t x_bytes = 0, gram_bytes = 0;
+  size_t lds_bytes = 0, lds2_bytes = 0, lds3_bytes = 0, ldsw_bytes = 0;
+  int sweep_version = 2;      // 3: k_sweep3 beside k_sweep2; 2: streamer/sequencer pipeline (k_sweep2); 1: replicated recurrence (k_sweep)
+  bool lag4_ok = false;       // the lag-4 streamer (ring of four tiles) fits the LDS at this geometry
+  int nfeed = 2;              // q feeder workgroups of k_sweep2 (one gather + sum of K KB takes about a block period at K = 40)
+  // k_sweep3 (selection models on int8 panels, sweep3.hip.h)
+  bool want3 = false;         // build what k_sweep3 needs with the panel (off for the per-iteration scratch panels of bagging and the EM family)
+  bool e3_ready = false;
+  int e3_D = 0;               // fold-in lag in blocks; cross Gram arrays reach D-1 blocks back
+  int K3 = 0, R3 = 0, sub3 = 0;   // streamer workgroups, rows of each, streamers per slab
+  bool solo3 = true;          // a chain alone on the GPU runs 128-row streamers (BWGR_SOLO3=0: never)
+  bool gram16 = false;        // the 16-bit copies are exact: every entry in 0..65535
+  int gram_maxdist = 3;       // panel_build_gram stops at this block distance (the EM scratch panel needs 1)
+  int winv_nd = 0;            // gxt distances built = the deepest lag the affine sweeps can run, minus one
+  void *X = nullptr, *gram = nullptr, *gramx = nullptr, *gramx2 = nullptr, *gramx3 = nullptr, *gramp = nullptr;
+  uint16_t *gramp16 = nullptr, *gramx16 = nullptr;   // 16-bit copies for the sequencer (int8 panels)
+  int *gram16_bad = nullptr;
+  void *g3x[S3_MAXD] = {};    // g3x[d-1]: cross Gram blocks of distance d in the element type k_sweep3 reads (aliases the older arrays where they fit)
+  bool g3own[S3_MAXD] = {};   // allocated here (not an alias)
+  unsigned char *gx12 = nullptr;   // 16-bit panels: an included marker's distance-1 and distance-2 rows side by side (k_near_rows)
+  unsigned char *gxt[S2W_MAXDIST] = {};   // the affine models' cross Gram blocks as the sequencer's MFMA operand (k_gx_planes, sweep2w.hip.h)
   float *xx = nullptr, *vx = nullptr, *msx_dev = nullptr;
   float MSx = 0;
+  int xmax = 0;               // largest |x| of an int8 panel
+  int *xmax_dev = nullptr;
+  // implicitly centred columns (bwgr_panel_set_centred; int8 panels with k_sweep3): the column sums, the centred |x_j - mean_j|^2 as floats (what
+  // a chain's xx is then)
+  bool cen = false;
+  int32_t *csum = nullptr; float *xxc = nullptr;
+  Switches sw;                // read when the root panel is made
+  int nclones = 0;            // live clones: the root's bwgr_panel_destroy refuses while any is alive
+  int nchains_all = 0;        // live chains on every handle (bwgr_panel_set_centred refuses while any is alive)
+  std::vector<hipStream_t> pair_streams;   // the streams pairs of chains run on (bwgr_chain_run_pair); here, so that they outlive every clone
+};
+
+struct bwgr_panel {
+  PanelData *data = nullptr;
+  bool is_root = false;       // made with the data, which it frees; false: a clone
+  hipStream_t stream = nullptr, own_stream = nullptr;
+  hipStream_t pre_pair_stream = nullptr; bool pre_pair_set = false;   // the stream this handle ran on before a pair run moved it (restored by its next sweep alone)
+  // the sweep scratch (scratch_alloc / scratch_free)
+  double *xspec2 = nullptr, *xspec3 = nullptr;   // [nblocks][SW_MAXM]: speculative cross terms of the lag-3 / lag-4 pipelines (k_spec)
+  PreStage ps = {};
+  const void *ps_owner = nullptr; int ps_iter = -1;   // whose sweep constants the scratch holds (a chain pre-stages a whole iteration once)
   double *xpart = nullptr, *qpart = nullptr;
   unsigned long long *dgran = nullptr;
   uint32_t *xflags = nullptr;
   unsigned char *xchg = nullptr; size_t xchg_bytes = 0;   // xflags | dgran | qpart in one allocation: one memset per launch
-  size_t lds_bytes = 0, lds2_bytes = 0;
-  int sweep_version = 2;   // 2: streamer/sequencer pipeline (k_sweep2); 1: replicated recurrence (k_sweep)
   unsigned long long *stamps = nullptr;   // diagnostic build only
-  PreStage ps = {};
-  const void *ps_owner = nullptr; int ps_iter = -1;   // whose sweep constants the scratch holds (a chain pre-stages a whole iteration once)
+  unsigned long long *qsum3 = nullptr, *lists3 = nullptr;   // k_sweep3's slab-dot sums and block lists
+  uint32_t epoch3 = 0;
+  double *snap_e = nullptr; float *snap_b = nullptr, *snap_d = nullptr, *snap_vb = nullptr;   // state before a fixed-point sweep (range recovery)
+  double *winv = nullptr;     // [nblocks][S2W_WDOUBLES], written by k_affine_inv before every affine sweep (sweep2w.hip.h)
+  unsigned long long *qsumw = nullptr;   // the fixed-point streamers' slab-dot sums [nblocks][SW_MAXM][2]
+  double *cpre = nullptr;     // implicitly centred columns: the running block sums of s_k * drej_k of the current iteration
   // k_draws: the next iteration's state-independent variates, drawn on a second (low-priority) stream beside this iteration's sweep
   double *draws = nullptr; hipStream_t draws_stream = nullptr; hipEvent_t draws_ready = nullptr, draws_free = nullptr;
   bool draws_valid = false; Rng draws_rng = {}; uint32_t draws_iter = 0, draws_marker0 = 0; int draws_flags = 0, draws_j0 = 0, draws_j1 = 0; const void *draws_sc = nullptr;
-  int gram_maxdist = 3;           // panel_build_gram stops at this block distance (the EM scratch panel needs 1)
-  bwgr_panel *parent = nullptr;   // a clone shares the parent's read-only arrays (X, Gram, xx, vx) and owns only the scratch
-  int nclones = 0;
-  int nchains = 0;                // live chains on this handle: panel_destroy refuses while any is alive
-  int nchains_all = 0;            // root panel: live chains on it and on its clones (bwgr_panel_set_centred refuses while any is alive)
-  Switches sw;                    // read when the root panel is made
-  int debug_withhold = 0;         // test hook: the next sweeps run with slab workgroup 0 missing (bwgr_debug_withhold)
-  // k_sweep3 (selection models on int8 panels, sweep3.hip.h)
-  bool want3 = false;             // build what k_sweep3 needs with the panel (off for the per-iteration scratch panels of bagging and the EM family)
-  bool e3_ready = false;
-  int e3_D = 0;                   // fold-in lag in blocks; cross Gram arrays reach D-1 blocks back
-  int K3 = 0, R3 = 0, sub3 = 0;   // streamer workgroups, rows of each, streamers per slab
-  bool solo3 = true;              // a chain alone on the GPU runs 128-row streamers (BWGR_SOLO3=0: never)
-  unsigned char *gx12 = nullptr;  // 16-bit panels: an included marker's distance-1 and distance-2 rows side by side (k_near_rows); root panels own it
-  void *g3x[S3_MAXD] = {};        // g3x[d-1]: cross Gram blocks of distance d in the element type k_sweep3 reads (aliases the older arrays where they fit)
-  bool g3own[S3_MAXD] = {};       // allocated here (not an alias)
-  int xmax = 0;                   // largest |x| of an int8 panel
-  int *xmax_dev = nullptr;
-  unsigned long long *qsum3 = nullptr, *lists3 = nullptr;   // per handle (clones have their own)
-  uint32_t epoch3 = 0;
-  size_t lds3_bytes = 0;
-  double *snap_e = nullptr; float *snap_b = nullptr, *snap_d = nullptr, *snap_vb = nullptr;   // state before a fixed-point sweep (range recovery)
-  // the affine models' block solve as a triangular product (sweep2w.hip.h)
-  double *winv = nullptr;         // per handle: [nblocks][S2W_WDOUBLES], written by k_affine_inv before every affine sweep
-  unsigned char *gxt[S2W_MAXDIST] = {};   // the cross Gram blocks as the sequencer's MFMA operand (k_gx_planes); shared with clones
-  unsigned long long *qsumw = nullptr;    // per handle: the fixed-point streamers' slab-dot sums [nblocks][SW_MAXM][2]
-  int winv_nd = 0;                // distances built = the deepest lag the affine sweeps can run, minus one
-  size_t ldsw_bytes = 0;
-  std::vector<hipStream_t> pair_streams;   // root panel: the streams pairs of chains run on (bwgr_chain_run_pair); owned here, so that they outlive every clone
-  bool force3 = false;            // a pair run (bwgr_chain_run_pair): every selection sweep is k_sweep3's, whatever the inclusion rate
-  // implicitly centred columns (bwgr_panel_set_centred; int8 panels with k_sweep3): the column sums, the centred |x_j - mean_j|^2 as floats (what
-  // a chain's xx is then), both owned by the root panel; per handle the running block sums of s_k * drej_k of the current iteration
-  bool cen = false;
-  int32_t *csum = nullptr; float *xxc = nullptr;
-  double *cpre = nullptr;
-  hipStream_t own_stream = nullptr;
   // occupancy guard: the compute units this handle's enqueued sweeps hold while they run, the stream they run on, and an event behind the last of them
-  hipStream_t pre_pair_stream = nullptr; bool pre_pair_set = false;   // the stream this handle ran on before a pair run moved it (restored by its next sweep alone)
   hipEvent_t guard_ev = nullptr; int guard_cus = 0; hipStream_t guard_stream = nullptr; bool guard_listed = false;
+  bool force3 = false;        // a pair run (bwgr_chain_run_pair): every selection sweep is k_sweep3's, whatever the inclusion rate
+  int debug_withhold = 0;     // test hook: the next sweeps run with slab workgroup 0 missing (bwgr_debug_withhold)
+  int nchains = 0;            // live chains on this handle: panel_destroy refuses while any is alive
 };
-
-static bool panel_cen(const bwgr_panel *P) { return (P->parent ? P->parent : P)->cen; }
 
 struct bwgr_chain {
   bwgr_panel *P = nullptr;
@@ -1103,7 +1106,7 @@ template <typename XT> static int max_slab_rows(int m) {
 
 // the words the workgroups poll (flags, delta granules, q words and the feeders' sums) live in one allocation
 static hipError_t alloc_exchange(bwgr_panel *P) {
-  const size_t K = (size_t)P->K;
+  const size_t K = (size_t)P->data->K;
   const size_t fb = (sizeof(uint32_t) * (K + 1) * SW_FLAG_STRIDE + 255) & ~(size_t)255;
   const size_t gb = (sizeof(unsigned long long) * S2_NSLOT * SW_MAXM + 255) & ~(size_t)255;
   const size_t qb = sizeof(double) * S2_NSLOT * (K + 1) * SW_MAXM;
@@ -1190,7 +1193,7 @@ static int plan_cus(const SweepPlan &pl, int cus, int busy, int *need_out) {
 static int guard_busy(const bwgr_panel *P, hipStream_t mine, const bwgr_panel *partner = nullptr) {
   std::vector<std::pair<hipStream_t, int>> per_stream;
   for (bwgr_panel *Q : g_guard_panels) {
-    if (Q == P || Q == partner || Q->device != P->device || Q->guard_cus == 0) continue;   // (a pair's stream waits for both handles' earlier sweeps)
+    if (Q == P || Q == partner || Q->data->device != P->data->device || Q->guard_cus == 0) continue;   // (a pair's stream waits for both handles' earlier sweeps)
     if (hipEventQuery(Q->guard_ev) == hipSuccess) { Q->guard_cus = 0; continue; }
     (void)hipGetLastError();   // (hipErrorNotReady)
     if (Q->guard_stream == mine) continue;   // the same stream: one after the other
@@ -1206,8 +1209,8 @@ static int guard_busy(const bwgr_panel *P, hipStream_t mine, const bwgr_panel *p
 // other handles (but partner) have in flight on this device.  BWGR_OCC_GUARD=0 switches the guard off.
 static int sweep_guard(const bwgr_panel *P, const SweepPlan &pl, hipStream_t st, const bwgr_panel *partner, int *need) {
   *need = 0;
-  if (!P->sw.occ_guard) return BWGR_OK;
-  const int cus = device_cus(P->device);
+  if (!P->data->sw.occ_guard) return BWGR_OK;
+  const int cus = device_cus(P->data->device);
   if (cus < 1) return BWGR_OK;
   std::lock_guard<std::mutex> lk(g_guard_mu);
   return plan_cus(pl, cus, guard_busy(P, st, partner), need);
@@ -1230,89 +1233,81 @@ static void guard_forget(bwgr_panel *P) {
 }
 
 static int reset_exchange(bwgr_panel *P) {
-  if (P->sweep_version >= 2) {
+  if (P->data->sweep_version >= 2) {
     HIPCHK(hipMemsetAsync(P->xchg, 0, P->xchg_bytes, P->stream));
-  } else if (P->K > 1) {
-    HIPCHK(hipMemsetAsync(P->xflags, 0, sizeof(uint32_t) * ((size_t)P->K + 1) * SW_FLAG_STRIDE, P->stream));
+  } else if (P->data->K > 1) {
+    HIPCHK(hipMemsetAsync(P->xflags, 0, sizeof(uint32_t) * ((size_t)P->data->K + 1) * SW_FLAG_STRIDE, P->stream));
   }
   return BWGR_OK;
 }
 
 static void launch_gramx_i8(bwgr_panel *P, int32_t *g, int dist);
 // ---- k_sweep3 (sweep3.hip.h): what it needs beside the panel ----
-// geometry, scratch and attributes (every handle: panels and clones)
-static int sweep3_alloc_scratch(bwgr_panel *P) {
-  HIPCHK(hipMalloc(&P->qsum3, sizeof(unsigned long long) * 2 * SW_MAXM * (size_t)P->nblocks));
-  HIPCHK(hipMalloc(&P->lists3, sizeof(unsigned long long) * S3_LSTRIDE * (size_t)P->nblocks));
-  HIPCHK(hipMemsetAsync(P->lists3, 0, sizeof(unsigned long long) * S3_LSTRIDE * (size_t)P->nblocks, P->stream));
-  return BWGR_OK;
-}
 // the cross Gram arrays of distance 2 .. D-1 in the element type of the 16-bit (or, failing that, 32-bit) staging
 static int sweep3_build(bwgr_panel *P) {
-  P->e3_ready = false;
-  if (P->is_f32 || !P->want3 || P->sweep_version != 3) return BWGR_OK;
-  const int m = P->m;
-  int R3 = (P->R % 256 == 0) ? 256 : 128;
-  { const int v = P->sw.r3; if ((v == 64 || v == 128 || v == 256) && P->R % v == 0) { R3 = v; P->solo3 = false; } }   // (an explicit height holds for every launch)
-  const int sub = P->R / R3, K3 = P->K * sub;
+  P->data->e3_ready = false;
+  if (P->data->is_f32 || !P->data->want3 || P->data->sweep_version != 3) return BWGR_OK;
+  const int m = P->data->m;
+  int R3 = (P->data->R % 256 == 0) ? 256 : 128;
+  { const int v = P->data->sw.r3; if ((v == 64 || v == 128 || v == 256) && P->data->R % v == 0) { R3 = v; P->data->solo3 = false; } }   // (an explicit height holds for every launch)
+  const int sub = P->data->R / R3, K3 = P->data->K * sub;
   int D = 12;   // (the streamers fold a list whose words they saw a step ahead: more lag than the fold itself needs -- C4: 12.45 ms at 8, 11.27 at 9, 10.78 at 10, 10.41 at 11, 10.37 at 12, 10.48 at 13)
   // (at least 2: a block's list leaves the sequencer while the next block is in its rounds)
-  if (P->sw.d3 >= 2 && P->sw.d3 <= S3_MAXD) D = P->sw.d3;
-  D = (int)std::min<int64_t>(D, std::max<int64_t>(2, P->nblocks));
-  const size_t lds = std::max(std::max(s3_streamer_lds(R3), std::max(s3_streamer_dma_lds(128), R3 == 256 ? s3_streamer_dma_lds(256) : (size_t)0)), s3_seq_lds(D, P->gram16));
+  if (P->data->sw.d3 >= 2 && P->data->sw.d3 <= S3_MAXD) D = P->data->sw.d3;
+  D = (int)std::min<int64_t>(D, std::max<int64_t>(2, P->data->nblocks));
+  const size_t lds = std::max(std::max(s3_streamer_lds(R3), std::max(s3_streamer_dma_lds(128), R3 == 256 ? s3_streamer_dma_lds(256) : (size_t)0)), s3_seq_lds(D, P->data->gram16));
   // the slab dots are summed as integers: sum over all rows of |x| * 128 per digit, four digits of 8 bits, 8 bits of arrival count
-  if (K3 > 255 || K3 + 1 > 256 || lds > (size_t)160 * 1024 || (int64_t)P->ld * std::max(P->xmax, 1) >= (1ll << 23) || (size_t)m * R3 > (size_t)4 * 16 * SW_THREADS) {
-    P->sweep_version = 2;
+  if (K3 > 255 || K3 + 1 > 256 || lds > (size_t)160 * 1024 || (int64_t)P->data->ld * std::max(P->data->xmax, 1) >= (1ll << 23) || (size_t)m * R3 > (size_t)4 * 16 * SW_THREADS) {
+    P->data->sweep_version = 2;
     return BWGR_OK;
   }
-  P->R3 = R3; P->sub3 = sub; P->K3 = K3; P->e3_D = D; P->lds3_bytes = lds;
-  if (P->sw.solo3 >= 0) P->solo3 = P->sw.solo3 != '0';
-  const size_t blk_elems = (size_t)P->nblocks * m * m;
-  const bool g16 = P->gram16;
+  P->data->R3 = R3; P->data->sub3 = sub; P->data->K3 = K3; P->data->e3_D = D; P->data->lds3_bytes = lds;
+  if (P->data->sw.solo3 >= 0) P->data->solo3 = P->data->sw.solo3 != '0';
+  const size_t blk_elems = (size_t)P->data->nblocks * m * m;
+  const bool g16 = P->data->gram16;
   const int Dbuild = D;
   int32_t *tmp = nullptr;
   for (int d = 1; d < Dbuild; ++d) {
-    if (P->nblocks <= d) { P->g3x[d - 1] = nullptr; continue; }
-    if (d == 1) { P->g3x[0] = g16 ? (void *)P->gramx16 : P->gramx; continue; }
-    if (!g16 && d == 2 && P->gramx2) { P->g3x[1] = P->gramx2; continue; }
-    if (!g16 && d == 3 && P->gramx3) { P->g3x[2] = P->gramx3; continue; }
+    if (P->data->nblocks <= d) { P->data->g3x[d - 1] = nullptr; continue; }
+    if (d == 1) { P->data->g3x[0] = g16 ? (void *)P->data->gramx16 : P->data->gramx; continue; }
+    if (!g16 && d == 2 && P->data->gramx2) { P->data->g3x[1] = P->data->gramx2; continue; }
+    if (!g16 && d == 3 && P->data->gramx3) { P->data->g3x[2] = P->data->gramx3; continue; }
     void *arr = nullptr;
     HIPCHK(hipMalloc(&arr, blk_elems * (g16 ? 2 : 4)));
-    P->g3x[d - 1] = arr; P->g3own[d - 1] = true;
+    P->data->g3x[d - 1] = arr; P->data->g3own[d - 1] = true;
     if (g16) {
       const int32_t *src;
-      if (d == 2 && P->gramx2) src = (const int32_t *)P->gramx2;
-      else if (d == 3 && P->gramx3) src = (const int32_t *)P->gramx3;
+      if (d == 2 && P->data->gramx2) src = (const int32_t *)P->data->gramx2;
+      else if (d == 3 && P->data->gramx3) src = (const int32_t *)P->data->gramx3;
       else {
         if (!tmp) HIPCHK(hipMalloc(&tmp, blk_elems * 4));
         launch_gramx_i8(P, tmp, d);
         src = tmp;
       }
-      hipLaunchKernelGGL(k_gram_narrow, dim3(2048), dim3(256), 0, P->stream, src + (size_t)d * m * m, (uint16_t *)arr + (size_t)d * m * m, (int64_t)(P->nblocks - d) * m * m, P->gram16_bad);
+      hipLaunchKernelGGL(k_gram_narrow, dim3(2048), dim3(256), 0, P->stream, src + (size_t)d * m * m, (uint16_t *)arr + (size_t)d * m * m, (int64_t)(P->data->nblocks - d) * m * m, P->data->gram16_bad);
     } else launch_gramx_i8(P, (int32_t *)arr, d);
     HIPCHK(hipGetLastError());
   }
   int bad = 0;
-  if (g16) HIPCHK(hipMemcpyAsync(&bad, P->gram16_bad, sizeof(int), hipMemcpyDeviceToHost, P->stream));
+  if (g16) HIPCHK(hipMemcpyAsync(&bad, P->data->gram16_bad, sizeof(int), hipMemcpyDeviceToHost, P->stream));
   HIPCHK(hipStreamSynchronize(P->stream));
   if (tmp) hipFree(tmp);
   if (bad) {   // an entry of a far block left the 16-bit range although the near blocks fit: rare; leave the panel to k_sweep2
-    for (int d = 1; d < S3_MAXD; ++d) if (P->g3own[d - 1]) { hipFree(P->g3x[d - 1]); P->g3x[d - 1] = nullptr; P->g3own[d - 1] = false; }
-    P->sweep_version = 2;
+    for (int d = 1; d < S3_MAXD; ++d) if (P->data->g3own[d - 1]) { hipFree(P->data->g3x[d - 1]); P->data->g3x[d - 1] = nullptr; P->data->g3own[d - 1] = false; }
+    P->data->sweep_version = 2;
     return BWGR_OK;
   }
   {   // 16-bit panels: an included marker's distance-1 / 2 rows in one piece
     if (g16) {
-      HIPCHK(hipMalloc(&P->gx12, (size_t)P->nblocks * m * 2 * m * 2));
-      hipLaunchKernelGGL(k_near_rows, dim3(4096), dim3(256), 0, P->stream, (const uint16_t *)P->g3x[0], (const uint16_t *)(D >= 3 ? P->g3x[1] : nullptr), (uint16_t *)P->gx12, m, (int64_t)P->nblocks);
+      HIPCHK(hipMalloc(&P->data->gx12, (size_t)P->data->nblocks * m * 2 * m * 2));
+      hipLaunchKernelGGL(k_near_rows, dim3(4096), dim3(256), 0, P->stream, (const uint16_t *)P->data->g3x[0], (const uint16_t *)(D >= 3 ? P->data->g3x[1] : nullptr), (uint16_t *)P->data->gx12, m, (int64_t)P->data->nblocks);
       HIPCHK(hipGetLastError());
     }
   }
-  CHK(sweep3_alloc_scratch(P));
   for (const void *f : {reinterpret_cast<const void *>(k_sweep3<uint16_t, false>), reinterpret_cast<const void *>(k_sweep3<int32_t, false>), reinterpret_cast<const void *>(k_sweep3<uint16_t, true>),
                         reinterpret_cast<const void *>(k_sweep3<int32_t, true>), reinterpret_cast<const void *>(k_sweep3p<uint16_t>), reinterpret_cast<const void *>(k_sweep3p<int32_t>)})
     HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  P->e3_ready = true;
+  P->data->e3_ready = true;
   return BWGR_OK;
 }
 // the DMA streamer's lane offsets are 32-bit: (columns of the launch) * (rows of a slab) bytes must stay below 4 GiB
@@ -1322,20 +1317,20 @@ extern "C" int bwgr_debug_stream3_dma(int64_t ncols, int64_t R) { return stream3
 // k_affine_inv forms before the sweep (sweep2w.hip.h).
 static int winv_alloc(bwgr_panel *P) {
   if (P->winv) return BWGR_OK;
-  HIPCHK(hipMalloc(&P->winv, sizeof(double) * (size_t)S2W_WDOUBLES * (size_t)P->nblocks));
-  HIPCHK(hipMalloc(&P->qsumw, sizeof(unsigned long long) * 4 * 2 * SW_MAXM * (size_t)P->nblocks));   // (up to four copies)
+  HIPCHK(hipMalloc(&P->winv, sizeof(double) * (size_t)S2W_WDOUBLES * (size_t)P->data->nblocks));
+  HIPCHK(hipMalloc(&P->qsumw, sizeof(unsigned long long) * 4 * 2 * SW_MAXM * (size_t)P->data->nblocks));   // (up to four copies)
   return BWGR_OK;
 }
 
 static void launch_prestage(bwgr_panel *P, const SweepArgs &a_in, const SweepPlan &pl) {
   SweepArgs a = a_in;
   a.gate3 = pl.gate3;
-  const int j0 = a.blk_begin * a.m, j1 = (int)std::min<int64_t>(P->p, (int64_t)a.blk_end * a.m);
+  const int j0 = a.blk_begin * a.m, j1 = (int)std::min<int64_t>(P->data->p, (int64_t)a.blk_end * a.m);
   const int64_t tasks = 4ll * (j1 - j0);
   const bool s3 = a.gate3 > 0.0f;
   const bool fxa = pl.engine == 4 && pl.fx;   // an affine sweep on the fixed-point streamers
-  const int sh_add = P->sw.sh_add;   // test hook: less headroom, to leave the range on purpose
-  int xbits = 0; while ((1 << xbits) < std::max(1, (P->parent ? P->parent : P)->xmax)) ++xbits;   // (the fixed-point scales: the residual, and what k_prestage knows of the steps times the largest |x|)
+  const int sh_add = P->data->sw.sh_add;   // test hook: less headroom, to leave the range on purpose
+  int xbits = 0; while ((1 << xbits) < std::max(1, P->data->xmax)) ++xbits;   // (the fixed-point scales: the residual, and what k_prestage knows of the steps times the largest |x|)
   if (s3 || fxa) hipLaunchKernelGGL(k_escale_reset, dim3(1), dim3(1), 0, P->stream, a.sc);
   // the variates drawn ahead (draws_ahead, below) when they are this very iteration's: same streams, same counters, same flags, this range inside theirs
   const int dflags = a.flags & (SWF_SELECT | SWF_VB_VEC);
@@ -1350,28 +1345,27 @@ static void launch_prestage(bwgr_panel *P, const SweepArgs &a_in, const SweepPla
     P->draws_valid = false;   // (consumed: the buffer is the next iteration's from here)
   } else hipLaunchKernelGGL(k_prestage, dim3((unsigned)std::min<int64_t>(4096, (tasks + 255) / 256)), dim3(256), 0, P->stream, a, j0, j1);
   if (s3) {   // the sweep's fixed-point scale, then the in-block speculative terms on that grid
-    hipLaunchKernelGGL(k_escale, dim3(1), dim3(1024), 0, P->stream, a.e, P->ld, a.sc, xbits, a.gate3, sh_add);
+    hipLaunchKernelGGL(k_escale, dim3(1), dim3(1024), 0, P->stream, a.e, P->data->ld, a.sc, xbits, a.gate3, sh_add);
     if (a.flags & SWF_CENTRE) {   // the rejected steps' share of sum(e_stored), block by block (the whole panel: launch_prestage is called with every block)
       hipLaunchKernelGGL(k_cen_tot, dim3((unsigned)(a.blk_end - a.blk_begin)), dim3(128), 0, P->stream, a, a.blk_begin, 0);
-      hipLaunchKernelGGL(k_cen_scan, dim3(1), dim3(1024), 0, P->stream, a, (int)P->nblocks, 0);
+      hipLaunchKernelGGL(k_cen_scan, dim3(1), dim3(1024), 0, P->stream, a, (int)P->data->nblocks, 0);
     }
-    { const bwgr_panel *root = P->parent ? P->parent : P;
-      hipLaunchKernelGGL(k_spec3, dim3((unsigned)(a.blk_end - a.blk_begin)), dim3(128), 0, P->stream, a, a.blk_begin, root->gram16 ? (const uint16_t *)root->gramp16 : (const uint16_t *)nullptr); }
+    hipLaunchKernelGGL(k_spec3, dim3((unsigned)(a.blk_end - a.blk_begin)), dim3(128), 0, P->stream, a, a.blk_begin, P->data->gram16 ? (const uint16_t *)P->data->gramp16 : (const uint16_t *)nullptr);
     if (std::isinf(a.gate3)) return;
   }
   if (pl.engine == 4) {
-    if (pl.fx) hipLaunchKernelGGL(k_escale, dim3(1), dim3(1024), 0, P->stream, a.e, P->ld, a.sc, xbits, INFINITY, sh_add);   // (|b0|, the noise terms)
+    if (pl.fx) hipLaunchKernelGGL(k_escale, dim3(1), dim3(1024), 0, P->stream, a.e, P->data->ld, a.sc, xbits, INFINITY, sh_add);   // (|b0|, the noise terms)
     hipLaunchKernelGGL(k_affine_inv, dim3((unsigned)(a.blk_end - a.blk_begin)), dim3(512), S2W_INV_LDS, P->stream, a, P->winv, (a.flags & SWF_DELTA2) ? 2.0 : 1.0);
     return;
   }
-  if (P->sweep_version >= 2) {
+  if (P->data->sweep_version >= 2) {
     const int sel = (a.flags & SWF_SELECT) ? 1 : 0;
     const unsigned nb = (unsigned)(a.blk_end - a.blk_begin);
     if ((a.flags & SWF_CENTRE) && sel) {   // the fp64 engine's share of an implicitly centred iteration (the float steps themselves; runs on k_sweep2's side of the gate)
       hipLaunchKernelGGL(k_cen_tot, dim3(nb), dim3(128), 0, P->stream, a, a.blk_begin, 1);
-      hipLaunchKernelGGL(k_cen_scan, dim3(1), dim3(1024), 0, P->stream, a, (int)P->nblocks, 1);
+      hipLaunchKernelGGL(k_cen_scan, dim3(1), dim3(1024), 0, P->stream, a, (int)P->data->nblocks, 1);
     }
-    if (P->is_f32) hipLaunchKernelGGL(k_spec<double>, dim3(nb), dim3(128), 0, P->stream, a, a.blk_begin, sel);
+    if (P->data->is_f32) hipLaunchKernelGGL(k_spec<double>, dim3(nb), dim3(128), 0, P->stream, a, a.blk_begin, sel);
     else hipLaunchKernelGGL(k_spec<int32_t>, dim3(nb), dim3(128), 0, P->stream, a, a.blk_begin, sel);
   }
 }
@@ -1383,7 +1377,7 @@ static void draws_ahead(bwgr_panel *P, const SweepArgs &a, const SweepPlan &pl, 
   if (!P->draws) {
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);   // (lo: the numerically largest = the lowest priority)
-    if (hipMalloc(&P->draws, sizeof(double) * 5 * (size_t)P->p) != hipSuccess || hipStreamCreateWithPriority(&P->draws_stream, hipStreamNonBlocking, lo) != hipSuccess ||
+    if (hipMalloc(&P->draws, sizeof(double) * 5 * (size_t)P->data->p) != hipSuccess || hipStreamCreateWithPriority(&P->draws_stream, hipStreamNonBlocking, lo) != hipSuccess ||
         hipEventCreateWithFlags(&P->draws_ready, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&P->draws_free, hipEventDisableTiming) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void *>(k_draws), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) {
       (void)hipGetLastError();
@@ -1392,13 +1386,13 @@ static void draws_ahead(bwgr_panel *P, const SweepArgs &a, const SweepPlan &pl, 
     }
     (void)hipEventRecord(P->draws_free, P->stream);
   }
-  const int j0 = a.blk_begin * a.m, j1 = (int)std::min<int64_t>(P->p, (int64_t)a.blk_end * a.m);
+  const int j0 = a.blk_begin * a.m, j1 = (int)std::min<int64_t>(P->data->p, (int64_t)a.blk_end * a.m);
   // after this iteration's k_prestage has read the buffer (draws_free) -- or, the first time, after what is enqueued so far; 160 workgroups with 96 KB of
   // LDS each: at most 160 compute units, none of them one that runs a workgroup of the sweep
   // (... and after the iteration's speculative terms, which are bandwidth-bound and would share the chip with it: the event in front of the sweep)
   { const hipError_t h1 = hipStreamWaitEvent(P->draws_stream, P->draws_free, 0), h2 = hipStreamWaitEvent(P->draws_stream, before_sweep, 0);
     if (h1 != hipSuccess || h2 != hipSuccess) { fprintf(stderr, "bwgr: draws_ahead waits failed: %s / %s\n", hipGetErrorString(h1), hipGetErrorString(h2)); (void)hipGetLastError(); return; } }
-  hipLaunchKernelGGL(k_draws, dim3(160), dim3(1024), 96 * 1024, P->draws_stream, a.rng, a.marker0, a.iter + 1u, a.flags, (const ChainScalars *)a.sc, (int64_t)P->p, j0, j1, P->draws);
+  hipLaunchKernelGGL(k_draws, dim3(160), dim3(1024), 96 * 1024, P->draws_stream, a.rng, a.marker0, a.iter + 1u, a.flags, (const ChainScalars *)a.sc, (int64_t)P->data->p, j0, j1, P->draws);
   { const hipError_t h1 = hipGetLastError(); const hipError_t h2 = (h1 == hipSuccess) ? hipEventRecord(P->draws_ready, P->draws_stream) : hipSuccess;
     if (h1 != hipSuccess || h2 != hipSuccess) { fprintf(stderr, "bwgr: k_draws launch / record failed: %s / %s\n", hipGetErrorString(h1), hipGetErrorString(h2)); (void)hipGetLastError(); P->draws_valid = false; return; } }
   P->draws_valid = true; P->draws_rng = a.rng; P->draws_iter = a.iter + 1u; P->draws_marker0 = a.marker0; P->draws_flags = a.flags & (SWF_SELECT | SWF_VB_VEC);
@@ -1409,36 +1403,35 @@ static void draws_ahead(bwgr_panel *P, const SweepArgs &a, const SweepPlan &pl, 
 // which left its range).  Reads the panel only: nothing is enqueued or allocated.
 static SweepPlan plan_sweep(const bwgr_panel *P, const SweepArgs &a, bool redo) {
   SweepPlan pl;
-  const Switches &sw = P->sw;
-  const bwgr_panel *root = P->parent ? P->parent : P;
+  const Switches &sw = P->data->sw;
   const bool sel = (a.flags & SWF_SELECT) != 0, cen = (a.flags & SWF_CENTRE) != 0;
   const auto spin = [&](const void *fn, int grid, int resident, int threads, size_t lds) { pl.spins[pl.nspins++] = SpinLaunch{fn, grid, resident, threads, lds}; };
   // The selection models' sweeps on a panel that has k_sweep3: the device picks the engine from the chain's current inclusion rate
   // (ChainScalars::inc_rate against the panel's threshold), so both engines' kernels are enqueued and one side leaves at once (a few
   // microseconds per iteration); a threshold >= 1, or a pair run, means k_sweep3 always and the other side is not enqueued at all.
-  if (P->e3_ready && sel && !(a.flags & SWF_EM_ANY) && !redo) pl.gate3 = (sw.eng3_thr >= 1.0f || P->force3) ? INFINITY : sw.eng3_thr;
+  if (P->data->e3_ready && sel && !(a.flags & SWF_EM_ANY) && !redo) pl.gate3 = (sw.eng3_thr >= 1.0f || P->force3) ? INFINITY : sw.eng3_thr;
   // The affine sweeps of an int8 panel with 16-bit Gram staging: k_sweep2w, with its own streamers (s2w_streamer_fx: 128 rows each,
   // fixed-point residual) where the slab count allows
-  const bool winv = sw.winv && P->sweep_version >= 2 && !P->is_f32 && P->gramp && P->winv_nd >= 1 && P->K <= 2 * (S2W_QW + S2W_QX) &&
-                    !(a.flags & (SWF_SELECT | SWF_EM_ANY | SWF_SERIAL)) && P->ldsw_bytes > 0 && P->ldsw_bytes <= (size_t)160 * 1024;
-  const bool wfx = sw.wfx && (P->R % S2W_FXR) == 0 && P->K * (P->R / S2W_FXR) <= 255;
-  pl.engine = pl.gate3 > 0.0f ? 3 : winv ? 4 : std::min(P->sweep_version, 2);
+  const bool winv = sw.winv && P->data->sweep_version >= 2 && !P->data->is_f32 && P->data->gramp && P->data->winv_nd >= 1 && P->data->K <= 2 * (S2W_QW + S2W_QX) &&
+                    !(a.flags & (SWF_SELECT | SWF_EM_ANY | SWF_SERIAL)) && P->data->ldsw_bytes > 0 && P->data->ldsw_bytes <= (size_t)160 * 1024;
+  const bool wfx = sw.wfx && (P->data->R % S2W_FXR) == 0 && P->data->K * (P->data->R / S2W_FXR) <= 255;
+  pl.engine = pl.gate3 > 0.0f ? 3 : winv ? 4 : std::min(P->data->sweep_version, 2);
   // Selection sweeps of k_sweep2: three blocks deep.  (The single-barrier sequencer also knows a fourth level, BWGR_LAG=4: it was
   // the default while k_sweep2 also ran the sparse chains; those are k_sweep3's now, and from 5 % of the markers in the model upwards
   // the third cross term's row fetches cost more than the depth gives -- C4-size BayesC at 5 / 19 / 36 % inclusion: 31.4 / 21.3 /
   // 14.5 iter/s at depth 3 against 30.9 / 19.4 / 9.4 at depth 4; BayesCpi at 51 %: 11.1 against 6.7.)  BWGR_LAG=2|3|4 sets it (A/B tests).
   int lag = 2;
-  if (P->sweep_version >= 2 && sel) {
+  if (P->data->sweep_version >= 2 && sel) {
     // the generic sequencer (32-bit Gram entries, fp32 panels) reads a distance-2 row per accepted marker straight from global memory on
     // one wave: two blocks deep unless asked (us per block at n = 10 000, depth 2 / 3: 1.4 % inclusion 4.53 / 4.67, 10.9 % 5.29 / 14.5,
     // BayesCpi at 52 % 12.7 / 58.0); the 16-bit / single-barrier sequencer stages those rows and knows a third cross term as well
-    if (P->gramx2 && sw.lag >= 0) lag = 3;
-    if (!P->is_f32 && P->gramx2 && P->gram16) lag = 3;
-    if (!P->is_f32 && P->gramx3 && P->gram16 && P->lag4_ok) lag = 4;
+    if (P->data->gramx2 && sw.lag >= 0) lag = 3;
+    if (!P->data->is_f32 && P->data->gramx2 && P->data->gram16) lag = 3;
+    if (!P->data->is_f32 && P->data->gramx3 && P->data->gram16 && P->data->lag4_ok) lag = 4;
   }
   pl.lag = std::min(lag, (sw.lag >= '2' && sw.lag <= '4') ? sw.lag - '0' : 3);
   if (winv) {   // the affine sweeps' product sequencer: as deep as the panel's cross Gram planes reach (BWGR_WLAG caps it)
-    pl.lag = std::min(P->winv_nd + 1, sw.wlag_cap);
+    pl.lag = std::min(P->data->winv_nd + 1, sw.wlag_cap);
     if (!wfx) pl.lag = std::min(pl.lag, 4);   // (k_sweep2's streamers hold four tiles)
 #ifdef BWGR_EXPERIMENTS
     if (sw.wlag_timing) pl.lag = sw.wlag_timing;   // TIMING ONLY: deeper than the cross terms reach (wrong chain)
@@ -1446,20 +1439,20 @@ static SweepPlan plan_sweep(const bwgr_panel *P, const SweepArgs &a, bool redo) 
   }
   // streamers, sequencer, and for the selection models the q feeders (the affine recurrence is compute-bound: its
   // sequencer gathers q itself under the recurrence, and a feeder hop in its lag-2 chain measured 15 % slower)
-  pl.nfeed = (P->sweep_version >= 2 && sel) ? P->nfeed : 0;
+  pl.nfeed = (P->data->sweep_version >= 2 && sel) ? P->data->nfeed : 0;
   // selection models: 16-bit staging and the single-barrier sequencer (the affine recurrence is compute-bound and measured faster on
   // the 32-bit blocks: no conversion in its inner loop)
-  pl.g16 = P->sweep_version >= 2 && !P->is_f32 && P->gram16 && sel;
+  pl.g16 = P->data->sweep_version >= 2 && !P->data->is_f32 && P->data->gram16 && sel;
   // A chain that has the GPU to itself (a root panel without clones) runs 128-row streamers, two to a slab: 80 compute units instead
   // of 41, 15.98-16.18 against 16.49 ms per sweep at C4 (the same chain bit for bit: the slab dots are integer sums).  With clones
   // alive -- chains side by side, pairs -- every chain keeps the 256-row streamers the concurrency counts assume.  BWGR_SOLO3=0: never.
-  const bool alone = P->solo3 && !P->parent && P->nclones == 0;
+  const bool alone = P->data->solo3 && P->is_root && P->data->nclones == 0;
   // The next iteration's variates beside the sweep (draws_ahead): selection models with the logistic step, only for a chain alone (beside
   // other chains or shards the idle compute units it would run on are theirs: five chains side by side 255 -> 226 chain-iter/s, three
   // shards 163 -> 119 iter/s with it); BWGR_DRAWS=0 switches it off
   pl.draws = sel && !(a.flags & (SWF_MH | SWF_EM_ANY)) && alone && sw.draws;
   if (pl.gate3 > 0.0f) {
-    pl.R3 = P->R3; pl.sub = P->sub3; pl.K3 = P->K3;
+    pl.R3 = P->data->R3; pl.sub = P->data->sub3; pl.K3 = P->data->K3;
 #ifdef BWGR_EXPERIMENTS
     pl.dbg3 = sw.dbg3;   // (timing switches, some of which break the chain: the experiment build only)
 #endif
@@ -1467,28 +1460,28 @@ static SweepPlan plan_sweep(const bwgr_panel *P, const SweepArgs &a, bool redo) 
       // The DMA streamer forms a tile piece's source as a 32-bit lane offset from the launch's first column (no 64-bit vector arithmetic): only
       // launches whose column range spans less than 4 GiB of one slab take it (p * R < 2^32: 16.7 M markers at R = 256); wider ones keep the
       // register path, whose offsets are size_t.  bwgr_debug_stream3_dma() exposes the rule to the CPU tests.
-      const int64_t j_lo = (int64_t)a.blk_begin * a.m, j_hi = std::min<int64_t>(P->p, (int64_t)a.blk_end * a.m);
-      const bool fits32 = stream3_dma_fits(j_hi - j_lo, P->R);
+      const int64_t j_lo = (int64_t)a.blk_begin * a.m, j_hi = std::min<int64_t>(P->data->p, (int64_t)a.blk_end * a.m);
+      const bool fits32 = stream3_dma_fits(j_hi - j_lo, P->data->R);
       if (sw.stream3 != 'r' && fits32) pl.dbg3 |= (1 << 22);
       if (sw.stream3 == 'd' && fits32) pl.dbg3 |= (1 << 23);   // (EXPERIMENT: the 256-row streamers too, three tile buffers)
     }
     if (P->force3) {   // a pair run (bwgr_chain_run_pair): one k_sweep3p launch, K3 streamers and two sequencers, serves both chains; no redo
-      const size_t lds = std::max(s3p_streamer_lds(pl.R3), s3_seq_lds(P->e3_D, root->gram16));
-      spin(root->gram16 ? reinterpret_cast<const void *>(k_sweep3p<uint16_t>) : reinterpret_cast<const void *>(k_sweep3p<int32_t>), pl.K3 + 2, pl.K3 + 2, SW_THREADS, lds);
+      const size_t lds = std::max(s3p_streamer_lds(pl.R3), s3_seq_lds(P->data->e3_D, P->data->gram16));
+      spin(P->data->gram16 ? reinterpret_cast<const void *>(k_sweep3p<uint16_t>) : reinterpret_cast<const void *>(k_sweep3p<int32_t>), pl.K3 + 2, pl.K3 + 2, SW_THREADS, lds);
       return pl;
     }
-    if (alone && pl.R3 == 256 && 2 * pl.K3 + 1 <= 256) { pl.R3 = 128; pl.sub = P->R / 128; pl.K3 = P->K * pl.sub; }
+    if (alone && pl.R3 == 256 && 2 * pl.K3 + 1 <= 256) { pl.R3 = 128; pl.sub = P->data->R / 128; pl.K3 = P->data->K * pl.sub; }
     // one more workgroup, on the sequencer's XCD (workgroups with equal index mod 8 share an XCD), warms that XCD's L2 with what the
     // staging waves load (on for a chain alone on the GPU: 15.61 -> 15.37 ms per sweep at C4 on the steadied kernel; beside other chains
     // the workgroup is not counted by bwgr_panel_max_concurrent, so it stays off there; BWGR_PF3=0|1 decides otherwise)
     const bool pf_on = (sw.pf3 >= 0 ? sw.pf3 == '1' : alone) && pl.K3 + 2 <= 256;
     pl.pf = pf_on ? ((pl.K3 + 2 > 8) ? 8 : pl.K3 + 1) : -1;
-    const bool pf2_on = pf_on && pl.pf == 8 && root->gram16 && root->gx12 && pl.K3 + 3 > 16 && pl.K3 + 3 <= 256 && sw.pf3b;
+    const bool pf2_on = pf_on && pl.pf == 8 && P->data->gram16 && P->data->gx12 && pl.K3 + 3 > 16 && pl.K3 + 3 <= 256 && sw.pf3b;
     pl.pf2 = pf2_on ? 16 : -1; pl.qsplit = 1; pl.skip_vb = (a.flags & SWF_VB_VEC) ? 1 : 0;
     const int grid = pl.K3 + 1 + (pf_on ? 1 : 0) + (pf2_on ? 1 : 0);
-    const void *fn = root->gram16 ? (cen ? reinterpret_cast<const void *>(k_sweep3<uint16_t, true>) : reinterpret_cast<const void *>(k_sweep3<uint16_t, false>))
+    const void *fn = P->data->gram16 ? (cen ? reinterpret_cast<const void *>(k_sweep3<uint16_t, true>) : reinterpret_cast<const void *>(k_sweep3<uint16_t, false>))
                                   : (cen ? reinterpret_cast<const void *>(k_sweep3<int32_t, true>) : reinterpret_cast<const void *>(k_sweep3<int32_t, false>));
-    spin(fn, grid, grid, SW_THREADS, P->lds3_bytes);
+    spin(fn, grid, grid, SW_THREADS, P->data->lds3_bytes);
   }
   if (!std::isinf(pl.gate3)) {
     if (winv) {
@@ -1496,20 +1489,20 @@ static SweepPlan plan_sweep(const bwgr_panel *P, const SweepArgs &a, bool redo) 
       if (!pl.fx) pl.lag = std::min(pl.lag, 4);   // (k_sweep2's streamers -- the range-recovery launch, BWGR_WFX=0 -- hold four tiles)
       pl.nd = std::min(pl.lag - 1, (int)S2W_MAXDIST);
       pl.npf = sw.wpf; pl.ahead = sw.wahead;   // (npf measured at C2: 0 -> 540, 2 -> 636, 4 -> 685 iter/s; 6 and 8 no better)
-      pl.wsub = P->R / S2W_FXR; pl.wK3 = P->K * pl.wsub;
+      pl.wsub = P->data->R / S2W_FXR; pl.wK3 = P->data->K * pl.wsub;
       pl.nq = sw.wnq ? sw.wnq : (pl.wK3 > 48 ? 2 : 1);   // (C2, 40 streamers: one copy 1.10 ms, two 1.21; C4 shape, 80 streamers: 27.8 / 25.6 / 27.6 ms with 1 / 2 / 4)
       // (of the 8 npf workgroups past the sequencer, the npf on its XCD prefetch; the others leave at once)
-      const int wgs = pl.fx ? pl.wK3 : P->K;
-      spin(pl.fx ? reinterpret_cast<const void *>(k_sweep2w<true>) : reinterpret_cast<const void *>(k_sweep2w<false>), wgs + 1 + 8 * pl.npf, wgs + 1 + pl.npf, S2W_THREADS, P->ldsw_bytes);
-    } else if (P->sweep_version >= 2) {
-      const void *fn = P->is_f32 ? (sel ? reinterpret_cast<const void *>(k_sweep2<float, true>) : reinterpret_cast<const void *>(k_sweep2<float, false>))
+      const int wgs = pl.fx ? pl.wK3 : P->data->K;
+      spin(pl.fx ? reinterpret_cast<const void *>(k_sweep2w<true>) : reinterpret_cast<const void *>(k_sweep2w<false>), wgs + 1 + 8 * pl.npf, wgs + 1 + pl.npf, S2W_THREADS, P->data->ldsw_bytes);
+    } else if (P->data->sweep_version >= 2) {
+      const void *fn = P->data->is_f32 ? (sel ? reinterpret_cast<const void *>(k_sweep2<float, true>) : reinterpret_cast<const void *>(k_sweep2<float, false>))
                        : pl.g16  ? reinterpret_cast<const void *>(k_sweep2<int8_t, true, uint16_t>)
                        : sel     ? reinterpret_cast<const void *>(k_sweep2<int8_t, true>) : reinterpret_cast<const void *>(k_sweep2<int8_t, false>);
-      spin(fn, P->K + 1 + pl.nfeed, P->K + 1 + pl.nfeed, SW_THREADS, P->lds2_bytes);
+      spin(fn, P->data->K + 1 + pl.nfeed, P->data->K + 1 + pl.nfeed, SW_THREADS, P->data->lds2_bytes);
     } else {
-      const void *fn = P->is_f32 ? (sel ? reinterpret_cast<const void *>(k_sweep<float, true>) : reinterpret_cast<const void *>(k_sweep<float, false>))
+      const void *fn = P->data->is_f32 ? (sel ? reinterpret_cast<const void *>(k_sweep<float, true>) : reinterpret_cast<const void *>(k_sweep<float, false>))
                                  : (sel ? reinterpret_cast<const void *>(k_sweep<int8_t, true>) : reinterpret_cast<const void *>(k_sweep<int8_t, false>));
-      spin(fn, P->K, P->K, SW_THREADS, P->lds_bytes);
+      spin(fn, P->data->K, P->data->K, SW_THREADS, P->data->lds_bytes);
     }
   }
   // The fixed-point engines between a snapshot of the state they start from and the fp64 engine that redoes the sweep if they left
@@ -1530,12 +1523,11 @@ static SweepPlan plan_sweep(const bwgr_panel *P, const SweepArgs &a, bool redo) 
 // what one launch of k_sweep3 / k_sweep3p needs beside the sweep's own arguments; zeroes the launch's slab-dot sums, takes a new epoch
 static void sweep3_args(bwgr_panel *P, const SweepArgs &a, const SweepPlan &pl, Sweep3Args &A) {
   memset(&A, 0, sizeof(A)); A.a = a;
-  const bwgr_panel *root = P->parent ? P->parent : P;
-  for (int d = 0; d < S3_MAXD; ++d) A.gx[d] = root->g3x[d];
-  A.gp = root->gram16 ? (const void *)root->gramp16 : root->gramp;
-  A.D = P->e3_D; A.K3 = pl.K3; A.R3 = pl.R3; A.sub = pl.sub; A.g16 = root->gram16 ? 1 : 0;
+  for (int d = 0; d < S3_MAXD; ++d) A.gx[d] = P->data->g3x[d];
+  A.gp = P->data->gram16 ? (const void *)P->data->gramp16 : P->data->gramp;
+  A.D = P->data->e3_D; A.K3 = pl.K3; A.R3 = pl.R3; A.sub = pl.sub; A.g16 = P->data->gram16 ? 1 : 0;
   A.qsum = P->qsum3; A.lists = P->lists3;
-  A.gx12 = root->gram16 ? root->gx12 : nullptr;
+  A.gx12 = P->data->gram16 ? P->data->gx12 : nullptr;
   A.dbg = pl.dbg3; A.pf = pl.pf; A.pf2 = pl.pf2; A.qsplit = pl.qsplit; A.skip_vb = pl.skip_vb;
   P->epoch3 = (P->epoch3 + 1) & 0xFFFFFFu; if (P->epoch3 == 0) P->epoch3 = 1;
   A.epoch = P->epoch3;
@@ -1549,9 +1541,9 @@ static void launch_sweep_engine(bwgr_panel *P, const SweepArgs &a_in, const Swee
   const bool sel = (a.flags & SWF_SELECT) != 0;
   if (redo && pl.engine == 2) {   // the fp64 engine's speculative terms (k_spec) of the state just restored
     if ((a.flags & SWF_CENTRE) && sel) {   // the running block sums on the float steps (the fixed-point launch left them on its grid): every block, then the scan
-      SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->nblocks;
-      hipLaunchKernelGGL(k_cen_tot, dim3((unsigned)P->nblocks), dim3(128), 0, P->stream, all, 0, 2);
-      hipLaunchKernelGGL(k_cen_scan, dim3(1), dim3(1024), 0, P->stream, all, (int)P->nblocks, 2);
+      SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->data->nblocks;
+      hipLaunchKernelGGL(k_cen_tot, dim3((unsigned)P->data->nblocks), dim3(128), 0, P->stream, all, 0, 2);
+      hipLaunchKernelGGL(k_cen_scan, dim3(1), dim3(1024), 0, P->stream, all, (int)P->data->nblocks, 2);
     }
     hipLaunchKernelGGL(k_spec<int32_t>, dim3((unsigned)(a.blk_end - a.blk_begin)), dim3(128), 0, P->stream, a, a.blk_begin, sel ? 1 : 0);
   }
@@ -1564,7 +1556,7 @@ static void launch_sweep_engine(bwgr_panel *P, const SweepArgs &a_in, const Swee
     spin_launch(pl.spins[0], P->stream, args);
     if (cen) hipLaunchKernelGGL(k_cen_end, dim3(64), dim3(256), 0, P->stream, a, 0);
     if (pl.skip_vb) {   // (every launch: idempotent -- after a range redo the fp64 engine has written the same values from the same expression)
-      const int j0 = a.blk_begin * a.m, j1 = (int)std::min<int64_t>(P->p, (int64_t)a.blk_end * a.m);
+      const int j0 = a.blk_begin * a.m, j1 = (int)std::min<int64_t>(P->data->p, (int64_t)a.blk_end * a.m);
       hipLaunchKernelGGL(k_vb_fill, dim3((unsigned)std::min<int64_t>(1024, (j1 - j0 + 255) / 256)), dim3(256), 0, P->stream, a, j0, j1);
     }
     if (std::isinf(a.gate3)) return;
@@ -1575,30 +1567,30 @@ static void launch_sweep_engine(bwgr_panel *P, const SweepArgs &a_in, const Swee
     S2WArgs A; memset(&A, 0, sizeof(A));
     A.winv = P->winv; A.qsum = P->qsumw; A.fx = pl.fx; A.nd = pl.nd; A.npf = pl.npf; A.ahead = pl.ahead; A.sub = pl.wsub; A.K3 = pl.wK3; A.nq = pl.nq;
 #ifdef BWGR_EXPERIMENTS
-    A.dbg = P->sw.dbgw;
+    A.dbg = P->data->sw.dbgw;
 #endif
-    for (int d = 0; d < S2W_MAXDIST; ++d) A.gxt[d] = P->gxt[d < P->winv_nd ? d : 0];
+    for (int d = 0; d < S2W_MAXDIST; ++d) A.gxt[d] = P->data->gxt[d < P->data->winv_nd ? d : 0];
     if (A.fx) (void)hipMemsetAsync(P->qsumw + (size_t)a.blk_begin * A.nq * 2 * SW_MAXM, 0, sizeof(unsigned long long) * A.nq * 2 * SW_MAXM * (size_t)(a.blk_end - a.blk_begin), P->stream);
     void *args[] = {&a, &A}; spin_launch(L, P->stream, args);
     return;
   }
-  const bool cen2 = P->sweep_version >= 2 && (a.flags & SWF_CENTRE) && sel && !P->is_f32;
+  const bool cen2 = P->data->sweep_version >= 2 && (a.flags & SWF_CENTRE) && sel && !P->data->is_f32;
   if (cen2) hipLaunchKernelGGL(k_cen_begin, dim3(1), dim3(1024), 0, P->stream, a, redo ? 2 : 1);
   SweepArgs ak = a;
-  if (pl.g16) { ak.gramp = P->gramp16; ak.gramx = P->gramx16; }
+  if (pl.g16) { ak.gramp = P->data->gramp16; ak.gramx = P->data->gramx16; }
   void *args[] = {&ak}; spin_launch(L, P->stream, args);
   if (cen2) hipLaunchKernelGGL(k_cen_end, dim3(64), dim3(256), 0, P->stream, a, redo ? 2 : 1);
 }
 // the plan's sweep: the fixed-point engines between a snapshot of the state they start from and the fp64 redo (plan_sweep); no redo
 // when the snapshot's scratch cannot be had
 static void launch_sweep_kernel(bwgr_panel *P, const SweepArgs &a, const SweepPlan &pl) {
-  const size_t p = (size_t)P->p;
+  const size_t p = (size_t)P->data->p;
   bool guarded = pl.guarded;
-  if (guarded && !P->snap_e && (hipMalloc(&P->snap_e, sizeof(double) * (size_t)P->ld) != hipSuccess || hipMalloc(&P->snap_b, sizeof(float) * p) != hipSuccess ||
+  if (guarded && !P->snap_e && (hipMalloc(&P->snap_e, sizeof(double) * (size_t)P->data->ld) != hipSuccess || hipMalloc(&P->snap_b, sizeof(float) * p) != hipSuccess ||
                                 hipMalloc(&P->snap_d, sizeof(float) * p) != hipSuccess || hipMalloc(&P->snap_vb, sizeof(float) * p) != hipSuccess)) { (void)hipGetLastError(); guarded = false; }
   SnapArgs sn;
   sn.e = a.e; sn.se = P->snap_e; sn.b = a.b; sn.d = a.d; sn.vb = (a.flags & SWF_VB_VEC) ? a.vb : nullptr; sn.sb = P->snap_b; sn.sd = P->snap_d; sn.svb = P->snap_vb;
-  sn.ld = P->ld; sn.j0 = a.blk_begin * a.m; sn.j1 = (int)std::min<int64_t>(P->p, (int64_t)a.blk_end * a.m); sn.sc = a.sc;
+  sn.ld = P->data->ld; sn.j0 = a.blk_begin * a.m; sn.j1 = (int)std::min<int64_t>(P->data->p, (int64_t)a.blk_end * a.m); sn.sc = a.sc;
   if (guarded) hipLaunchKernelGGL(k_range_snapshot, dim3(256), dim3(256), 0, P->stream, sn);
   launch_sweep_engine(P, a, pl, false);
   if (guarded) {
@@ -1644,11 +1636,11 @@ static int launch_sweep(bwgr_panel *P, SweepArgs &a) {
 }
 
 static void fill_panel_args(const bwgr_panel *P, SweepArgs &a) {
-  a.X = P->X; a.ld = P->ld; a.gram = P->gram;
-  a.n = (int)P->n; a.p = (int)P->p; a.m = P->m; a.K = P->K; a.R = P->R;
-  a.blk_begin = 0; a.blk_end = (int)P->nblocks;
+  a.X = P->data->X; a.ld = P->data->ld; a.gram = P->data->gram;
+  a.n = (int)P->data->n; a.p = (int)P->data->p; a.m = P->data->m; a.K = P->data->K; a.R = P->data->R;
+  a.blk_begin = 0; a.blk_end = (int)P->data->nblocks;
   a.xpart = P->xpart; a.xflags = P->xflags; a.stamps = P->stamps; a.ps = P->ps;
-  a.gramx = P->gramx; a.gramx2 = P->gramx2; a.xspec2 = P->xspec2; a.gramx3 = P->gramx3; a.xspec3 = P->xspec3; a.lag = 2; a.nfeed = P->nfeed; a.gramp = P->gramp; a.pstride = P->pstride; a.qpart = P->qpart; a.dgran = P->dgran;
+  a.gramx = P->data->gramx; a.gramx2 = P->data->gramx2; a.xspec2 = P->xspec2; a.gramx3 = P->data->gramx3; a.xspec3 = P->xspec3; a.lag = 2; a.nfeed = P->data->nfeed; a.gramp = P->data->gramp; a.pstride = P->data->pstride; a.qpart = P->qpart; a.dgran = P->dgran;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1656,10 +1648,10 @@ static void fill_panel_args(const bwgr_panel *P, SweepArgs &a) {
 // ------------------------------------------------------------------------------------------------
 template <typename ST, typename XT>
 static int upload(bwgr_panel *P, const void *X, int memloc, int64_t ldx) {
-  const int64_t n = P->n, p = P->p;
-  XT *dst = reinterpret_cast<XT *>(P->X);
+  const int64_t n = P->data->n, p = P->data->p;
+  XT *dst = reinterpret_cast<XT *>(P->data->X);
   if (memloc == BWGR_DEVICE) {
-    hipLaunchKernelGGL((k_convert<ST, XT>), dim3(4096), dim3(256), 0, P->stream, reinterpret_cast<const ST *>(X), ldx, dst, P->ld, (int)n, (int64_t)0, p, P->R, p);
+    hipLaunchKernelGGL((k_convert<ST, XT>), dim3(4096), dim3(256), 0, P->stream, reinterpret_cast<const ST *>(X), ldx, dst, P->data->ld, (int)n, (int64_t)0, p, P->data->R, p);
     HIPCHK(hipGetLastError());
     return BWGR_OK;
   }
@@ -1675,7 +1667,7 @@ static int upload(bwgr_panel *P, const void *X, int memloc, int64_t ldx) {
     const size_t bytes = (size_t)((nc - 1) * col_bytes + n * (int64_t)sizeof(ST));
     hipError_t e = hipMemcpyAsync(stage, reinterpret_cast<const ST *>(X) + j0 * ldx, bytes, hipMemcpyHostToDevice, P->stream);
     if (e != hipSuccess) { hipFree(stage); return fail(BWGR_EHIP, "upload memcpy failed: %s", hipGetErrorString(e)); }
-    hipLaunchKernelGGL((k_convert<ST, XT>), dim3(2048), dim3(256), 0, P->stream, stage, ldx, dst, P->ld, (int)n, j0, nc, P->R, p);
+    hipLaunchKernelGGL((k_convert<ST, XT>), dim3(2048), dim3(256), 0, P->stream, stage, ldx, dst, P->data->ld, (int)n, j0, nc, P->data->R, p);
     e = hipStreamSynchronize(P->stream);
     if (e != hipSuccess) { hipFree(stage); return fail(BWGR_EHIP, "upload convert failed: %s", hipGetErrorString(e)); }
   }
@@ -1683,67 +1675,94 @@ static int upload(bwgr_panel *P, const void *X, int memloc, int64_t ldx) {
   return BWGR_OK;
 }
 
-extern "C" int bwgr_panel_destroy(bwgr_panel *P) {
-  if (!P) return BWGR_OK;
-  if (P->nclones > 0) return fail(BWGR_EINVAL, "panel_destroy: %d clone(s) of this panel are still alive", P->nclones);
-  if (P->nchains > 0) return fail(BWGR_EINVAL, "panel_destroy: %d chain(s) on this panel are still alive (destroy them first)", P->nchains);
-  (void)hipSetDevice(P->device);
-  if (!P->parent) {
-    for (int d = 0; d < S3_MAXD; ++d) if (P->g3own[d]) hipFree(P->g3x[d]);
-    hipFree(P->gx12);
-    hipFree(P->xmax_dev);
-    for (int d = 0; d < S2W_MAXDIST; ++d) hipFree(P->gxt[d]);
-    hipFree(P->X); hipFree(P->gram); hipFree(P->gramx); hipFree(P->gramx2); hipFree(P->gramx3); hipFree(P->gramp16); hipFree(P->gramx16); hipFree(P->gram16_bad); hipFree(P->gramp); hipFree(P->xx); hipFree(P->vx); hipFree(P->msx_dev);
-  } else {
-    P->parent->nclones--;
+// A handle's sweep scratch, made once its data is built (the root's by whoever makes the data, a clone's by bwgr_panel_clone): the
+// speculative cross terms of the distances whose Gram blocks the data has, the pre-staged constants, the exchange words, and k_sweep3's
+// sums and lists where the data has k_sweep3.  The rest of the scratch comes with the first sweep that needs it; scratch_free frees all.
+static int scratch_alloc(bwgr_panel *P) {
+  const PanelData *D = P->data;
+  const size_t nb = (size_t)D->nblocks;
+  if (D->gramx2) HIPCHK(hipMalloc(&P->xspec2, sizeof(double) * nb * SW_MAXM));
+  if (D->gramx3) HIPCHK(hipMalloc(&P->xspec3, sizeof(double) * nb * SW_MAXM));
+  HIPCHK(hipMalloc(&P->ps.spec, sizeof(SpecBuf) * nb));
+  if (D->sweep_version >= 2) HIPCHK(hipMalloc(&P->ps.quick, sizeof(QuickBuf) * nb));
+  HIPCHK(hipMalloc(&P->ps.blocks, sizeof(StageBuf) * nb));
+  HIPCHK(hipMalloc(&P->xpart, sizeof(double) * 2 * (size_t)D->K * SW_MAXM));
+  HIPCHK(alloc_exchange(P));
+#if defined(BWGR_STAMPS) || defined(BWGR_EXPERIMENTS)
+  HIPCHK(hipMalloc(&P->stamps, sizeof(unsigned long long) * 256));
+  HIPCHK(hipMemset(P->stamps, 0, sizeof(unsigned long long) * 256));
+#endif
+  if (D->e3_ready) {
+    HIPCHK(hipMalloc(&P->qsum3, sizeof(unsigned long long) * 2 * SW_MAXM * nb));
+    HIPCHK(hipMalloc(&P->lists3, sizeof(unsigned long long) * S3_LSTRIDE * nb));
+    HIPCHK(hipMemsetAsync(P->lists3, 0, sizeof(unsigned long long) * S3_LSTRIDE * nb, P->stream));
   }
-  // the scratch a sweep writes: speculative cross terms, pre-staged constants, exchange words
-  hipFree(P->qsum3); hipFree(P->lists3); hipFree(P->winv); hipFree(P->qsumw);
-  hipFree(P->snap_e); hipFree(P->snap_b); hipFree(P->snap_d); hipFree(P->snap_vb);
-  hipFree(P->cpre); if (!P->parent) { hipFree(P->csum); hipFree(P->xxc); }
+  return BWGR_OK;
+}
+static void scratch_free(bwgr_panel *P) {
   hipFree(P->xspec2); hipFree(P->xspec3); hipFree(P->ps.spec); hipFree(P->ps.blocks); hipFree(P->ps.quick); hipFree(P->xpart); hipFree(P->xchg); hipFree(P->stamps);
+  hipFree(P->qsum3); hipFree(P->lists3); hipFree(P->winv); hipFree(P->qsumw); hipFree(P->cpre);
+  hipFree(P->snap_e); hipFree(P->snap_b); hipFree(P->snap_d); hipFree(P->snap_vb);
   guard_forget(P);
   if (P->draws_stream) { (void)hipStreamSynchronize(P->draws_stream); hipStreamDestroy(P->draws_stream); }
   if (P->draws_ready) hipEventDestroy(P->draws_ready);
   if (P->draws_free) hipEventDestroy(P->draws_free);
   hipFree(P->draws);
+}
+
+extern "C" int bwgr_panel_destroy(bwgr_panel *P) {
+  if (!P) return BWGR_OK;
+  PanelData *D = P->data;
+  if (P->is_root && D->nclones > 0) return fail(BWGR_EINVAL, "panel_destroy: %d clone(s) of this panel are still alive", D->nclones);
+  if (P->nchains > 0) return fail(BWGR_EINVAL, "panel_destroy: %d chain(s) on this panel are still alive (destroy them first)", P->nchains);
+  (void)hipSetDevice(D->device);
+  scratch_free(P);
   if (P->own_stream) hipStreamDestroy(P->own_stream);
-  for (hipStream_t q : P->pair_streams) hipStreamDestroy(q);
+  if (P->is_root) {
+    for (int d = 0; d < S3_MAXD; ++d) if (D->g3own[d]) hipFree(D->g3x[d]);
+    for (int d = 0; d < S2W_MAXDIST; ++d) hipFree(D->gxt[d]);
+    hipFree(D->X); hipFree(D->gram); hipFree(D->gramx); hipFree(D->gramx2); hipFree(D->gramx3); hipFree(D->gramp16); hipFree(D->gramx16); hipFree(D->gram16_bad); hipFree(D->gramp);
+    hipFree(D->gx12); hipFree(D->xx); hipFree(D->vx); hipFree(D->msx_dev); hipFree(D->xmax_dev); hipFree(D->csum); hipFree(D->xxc);
+    for (hipStream_t q : D->pair_streams) hipStreamDestroy(q);
+    delete D;
+  } else {
+    D->nclones--;
+  }
   delete P;
   return BWGR_OK;
 }
 
 static int panel_build_gram(bwgr_panel *P);
 static int panel_setup(bwgr_panel *P) {
-  const int p = (int)P->p, n = (int)P->n;
+  const int p = (int)P->data->p, n = (int)P->data->n;
   // a10: xx, vx, MSx
   const int wpb = 4;
-  if (P->is_f32) hipLaunchKernelGGL(k_stats<float>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const float *)P->X, P->R, n, p, P->xx, P->vx);
-  else hipLaunchKernelGGL(k_stats<int8_t>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const int8_t *)P->X, P->R, n, p, P->xx, P->vx);
+  if (P->data->is_f32) hipLaunchKernelGGL(k_stats<float>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const float *)P->data->X, P->data->R, n, p, P->data->xx, P->data->vx);
+  else hipLaunchKernelGGL(k_stats<int8_t>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const int8_t *)P->data->X, P->data->R, n, p, P->data->xx, P->data->vx);
   HIPCHK(hipGetLastError());
   {
     const int nparts = 256;
     double *part = nullptr;
     HIPCHK(hipMalloc(&part, sizeof(double) * nparts));
-    hipLaunchKernelGGL(k_sum_stage1, dim3(nparts), dim3(256), 0, P->stream, P->vx, (int64_t)p, part);
-    hipLaunchKernelGGL(k_sum_stage2, dim3(1), dim3(256), 0, P->stream, part, nparts, P->msx_dev);
+    hipLaunchKernelGGL(k_sum_stage1, dim3(nparts), dim3(256), 0, P->stream, P->data->vx, (int64_t)p, part);
+    hipLaunchKernelGGL(k_sum_stage2, dim3(1), dim3(256), 0, P->stream, part, nparts, P->data->msx_dev);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&P->MSx, P->msx_dev, sizeof(float), hipMemcpyDeviceToHost, P->stream));
+    HIPCHK(hipMemcpyAsync(&P->data->MSx, P->data->msx_dev, sizeof(float), hipMemcpyDeviceToHost, P->stream));
     HIPCHK(hipStreamSynchronize(P->stream));
     HIPCHK(hipFree(part));
   }
-  if (!P->is_f32) {
-    if (!P->xmax_dev) HIPCHK(hipMalloc(&P->xmax_dev, sizeof(int)));
-    HIPCHK(hipMemsetAsync(P->xmax_dev, 0, sizeof(int), P->stream));
-    hipLaunchKernelGGL(k_absmax_i8, dim3(2048), dim3(256), 0, P->stream, (const int8_t *)P->X, P->x_bytes, P->xmax_dev);
+  if (!P->data->is_f32) {
+    if (!P->data->xmax_dev) HIPCHK(hipMalloc(&P->data->xmax_dev, sizeof(int)));
+    HIPCHK(hipMemsetAsync(P->data->xmax_dev, 0, sizeof(int), P->stream));
+    hipLaunchKernelGGL(k_absmax_i8, dim3(2048), dim3(256), 0, P->stream, (const int8_t *)P->data->X, P->data->x_bytes, P->data->xmax_dev);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&P->xmax, P->xmax_dev, sizeof(int), hipMemcpyDeviceToHost, P->stream));
+    HIPCHK(hipMemcpyAsync(&P->data->xmax, P->data->xmax_dev, sizeof(int), hipMemcpyDeviceToHost, P->stream));
     HIPCHK(hipStreamSynchronize(P->stream));
   }
   CHK(panel_build_gram(P));
   // the trajectory engine for the selection models (int8 panels that asked for it; BWGR_SWEEP=2 keeps k_sweep2)
-  if (P->want3 && !P->is_f32 && P->sweep_version == 2 && P->sw.sweep != '2') {
-    P->sweep_version = 3;
+  if (P->data->want3 && !P->data->is_f32 && P->data->sweep_version == 2 && P->data->sw.sweep != '2') {
+    P->data->sweep_version = 3;
     CHK(sweep3_build(P));
   }
   return BWGR_OK;
@@ -1751,205 +1770,195 @@ static int panel_setup(bwgr_panel *P) {
 
 // cross Gram blocks X_{b-dist}' X_b of an int8 panel, b = dist .. nblocks-1, into g[b][m][m] (int32, exact)
 static void launch_gramx_i8(bwgr_panel *P, int32_t *g, int dist) {
-  const int p = (int)P->p, m = P->m, TJ = m / 16;
-  const unsigned nbx = (unsigned)(P->nblocks - dist);
+  const int p = (int)P->data->p, m = P->data->m, TJ = m / 16;
+  const unsigned nbx = (unsigned)(P->data->nblocks - dist);
   const size_t lds = (size_t)2 * m * 33 * sizeof(int32_t);
-  const int8_t *X = (const int8_t *)P->X;
-  if (m == 128) hipLaunchKernelGGL(k_gram_mfma_i8, dim3(nbx), dim3(256), 0, P->stream, X, P->ld, P->R, p, g, dist);
+  const int8_t *X = (const int8_t *)P->data->X;
+  if (m == 128) hipLaunchKernelGGL(k_gram_mfma_i8, dim3(nbx), dim3(256), 0, P->stream, X, P->data->ld, P->data->R, p, g, dist);
   else switch (TJ) {
-    case 1: hipLaunchKernelGGL(k_gramx_i8<1>, dim3(nbx), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g, dist); break;
-    case 2: hipLaunchKernelGGL(k_gramx_i8<2>, dim3(nbx), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g, dist); break;
-    case 3: hipLaunchKernelGGL(k_gramx_i8<3>, dim3(nbx), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g, dist); break;
-    case 4: hipLaunchKernelGGL(k_gramx_i8<4>, dim3(nbx), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g, dist); break;
-    case 5: hipLaunchKernelGGL(k_gramx_i8<5>, dim3(nbx), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g, dist); break;
-    case 6: hipLaunchKernelGGL(k_gramx_i8<6>, dim3(nbx), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g, dist); break;
-    case 7: hipLaunchKernelGGL(k_gramx_i8<7>, dim3(nbx), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g, dist); break;
-    default: hipLaunchKernelGGL(k_gramx_i8<8>, dim3(nbx), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g, dist); break;
+    case 1: hipLaunchKernelGGL(k_gramx_i8<1>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
+    case 2: hipLaunchKernelGGL(k_gramx_i8<2>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
+    case 3: hipLaunchKernelGGL(k_gramx_i8<3>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
+    case 4: hipLaunchKernelGGL(k_gramx_i8<4>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
+    case 5: hipLaunchKernelGGL(k_gramx_i8<5>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
+    case 6: hipLaunchKernelGGL(k_gramx_i8<6>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
+    case 7: hipLaunchKernelGGL(k_gramx_i8<7>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
+    default: hipLaunchKernelGGL(k_gramx_i8<8>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
   }
 }
 
 // diagonal, off-diagonal and packed Gram blocks of the resident X
 static int panel_build_gram(bwgr_panel *P) {
-  const int p = (int)P->p;
-  const int m = P->m, TJ = m / 16;
-  if (P->is_f32) {
+  const int p = (int)P->data->p;
+  const int m = P->data->m, TJ = m / 16;
+  if (P->data->is_f32) {
     const size_t lds = (size_t)m * 65 * sizeof(float);
-    double *g = (double *)P->gram; const float *X = (const float *)P->X;
+    double *g = (double *)P->data->gram; const float *X = (const float *)P->data->X;
     switch (TJ) {
-      case 1: hipLaunchKernelGGL(k_gram_f32<1>, dim3(P->nblocks), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g); break;
-      case 2: hipLaunchKernelGGL(k_gram_f32<2>, dim3(P->nblocks), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g); break;
-      case 3: hipLaunchKernelGGL(k_gram_f32<3>, dim3(P->nblocks), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g); break;
-      default: hipLaunchKernelGGL(k_gram_f32<4>, dim3(P->nblocks), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g); break;
+      case 1: hipLaunchKernelGGL(k_gram_f32<1>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
+      case 2: hipLaunchKernelGGL(k_gram_f32<2>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
+      case 3: hipLaunchKernelGGL(k_gram_f32<3>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
+      default: hipLaunchKernelGGL(k_gram_f32<4>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
     }
   } else {
     const size_t lds = (size_t)m * 33 * sizeof(int32_t);
-    int32_t *g = (int32_t *)P->gram; const int8_t *X = (const int8_t *)P->X;
-    if (m == 128) hipLaunchKernelGGL(k_gram_mfma_i8, dim3(P->nblocks), dim3(256), 0, P->stream, X, P->ld, P->R, p, g, 0);
+    int32_t *g = (int32_t *)P->data->gram; const int8_t *X = (const int8_t *)P->data->X;
+    if (m == 128) hipLaunchKernelGGL(k_gram_mfma_i8, dim3(P->data->nblocks), dim3(256), 0, P->stream, X, P->data->ld, P->data->R, p, g, 0);
     else switch (TJ) {
-      case 1: hipLaunchKernelGGL(k_gram_i8<1>, dim3(P->nblocks), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g); break;
-      case 2: hipLaunchKernelGGL(k_gram_i8<2>, dim3(P->nblocks), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g); break;
-      case 3: hipLaunchKernelGGL(k_gram_i8<3>, dim3(P->nblocks), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g); break;
-      case 4: hipLaunchKernelGGL(k_gram_i8<4>, dim3(P->nblocks), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g); break;
-      case 5: hipLaunchKernelGGL(k_gram_i8<5>, dim3(P->nblocks), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g); break;
-      case 6: hipLaunchKernelGGL(k_gram_i8<6>, dim3(P->nblocks), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g); break;
-      case 7: hipLaunchKernelGGL(k_gram_i8<7>, dim3(P->nblocks), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g); break;
-      default: hipLaunchKernelGGL(k_gram_i8<8>, dim3(P->nblocks), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g); break;
+      case 1: hipLaunchKernelGGL(k_gram_i8<1>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
+      case 2: hipLaunchKernelGGL(k_gram_i8<2>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
+      case 3: hipLaunchKernelGGL(k_gram_i8<3>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
+      case 4: hipLaunchKernelGGL(k_gram_i8<4>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
+      case 5: hipLaunchKernelGGL(k_gram_i8<5>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
+      case 6: hipLaunchKernelGGL(k_gram_i8<6>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
+      case 7: hipLaunchKernelGGL(k_gram_i8<7>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
+      default: hipLaunchKernelGGL(k_gram_i8<8>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
     }
   }
   HIPCHK(hipGetLastError());
   for (int dist = 1; dist <= 3; ++dist) {   // off-diagonal blocks (blk-dist, blk): the cross terms of the lag-2 / 3 / 4 pipelines
-    if (P->nblocks <= dist || dist > P->gram_maxdist || (dist == 2 && !P->gramx2) || (dist == 3 && !P->gramx3)) continue;
-    const unsigned nbx = (unsigned)(P->nblocks - dist);
-    if (P->is_f32) {
+    if (P->data->nblocks <= dist || dist > P->data->gram_maxdist || (dist == 2 && !P->data->gramx2) || (dist == 3 && !P->data->gramx3)) continue;
+    const unsigned nbx = (unsigned)(P->data->nblocks - dist);
+    if (P->data->is_f32) {
       const size_t lds = (size_t)2 * m * 65 * sizeof(float);
-      double *g = (double *)(dist == 1 ? P->gramx : dist == 2 ? P->gramx2 : P->gramx3); const float *X = (const float *)P->X;
+      double *g = (double *)(dist == 1 ? P->data->gramx : dist == 2 ? P->data->gramx2 : P->data->gramx3); const float *X = (const float *)P->data->X;
       switch (TJ) {
-        case 1: hipLaunchKernelGGL(k_gramx_f32<1>, dim3(nbx), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g, dist); break;
-        case 2: hipLaunchKernelGGL(k_gramx_f32<2>, dim3(nbx), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g, dist); break;
-        case 3: hipLaunchKernelGGL(k_gramx_f32<3>, dim3(nbx), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g, dist); break;
-        default: hipLaunchKernelGGL(k_gramx_f32<4>, dim3(nbx), dim3(256), lds, P->stream, X, P->ld, P->R, p, m, g, dist); break;
+        case 1: hipLaunchKernelGGL(k_gramx_f32<1>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
+        case 2: hipLaunchKernelGGL(k_gramx_f32<2>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
+        case 3: hipLaunchKernelGGL(k_gramx_f32<3>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
+        default: hipLaunchKernelGGL(k_gramx_f32<4>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
       }
     } else {
-      launch_gramx_i8(P, (int32_t *)(dist == 1 ? P->gramx : dist == 2 ? P->gramx2 : P->gramx3), dist);
+      launch_gramx_i8(P, (int32_t *)(dist == 1 ? P->data->gramx : dist == 2 ? P->data->gramx2 : P->data->gramx3), dist);
     }
     HIPCHK(hipGetLastError());
   }
-  if (P->is_f32) hipLaunchKernelGGL(k_gram_pack<double>, dim3((unsigned)P->nblocks), dim3(256), 0, P->stream, (const double *)P->gram, (double *)P->gramp, m, P->pstride, P->nblocks);
-  else hipLaunchKernelGGL(k_gram_pack<int32_t>, dim3((unsigned)P->nblocks), dim3(256), 0, P->stream, (const int32_t *)P->gram, (int32_t *)P->gramp, m, P->pstride, P->nblocks);
+  if (P->data->is_f32) hipLaunchKernelGGL(k_gram_pack<double>, dim3((unsigned)P->data->nblocks), dim3(256), 0, P->stream, (const double *)P->data->gram, (double *)P->data->gramp, m, P->data->pstride, P->data->nblocks);
+  else hipLaunchKernelGGL(k_gram_pack<int32_t>, dim3((unsigned)P->data->nblocks), dim3(256), 0, P->stream, (const int32_t *)P->data->gram, (int32_t *)P->data->gramp, m, P->data->pstride, P->data->nblocks);
   HIPCHK(hipGetLastError());
-  P->gram16 = false;
-  if (P->gramp16) {
-    HIPCHK(hipMemsetAsync(P->gram16_bad, 0, sizeof(int), P->stream));
-    hipLaunchKernelGGL(k_gram_narrow, dim3(2048), dim3(256), 0, P->stream, (const int32_t *)P->gramp, P->gramp16, (int64_t)P->nblocks * P->pstride, P->gram16_bad);
-    if (P->nblocks > 1)
-      hipLaunchKernelGGL(k_gram_narrow, dim3(2048), dim3(256), 0, P->stream, (const int32_t *)P->gramx + (size_t)m * m, P->gramx16 + (size_t)m * m, (int64_t)(P->nblocks - 1) * m * m, P->gram16_bad);
+  P->data->gram16 = false;
+  if (P->data->gramp16) {
+    HIPCHK(hipMemsetAsync(P->data->gram16_bad, 0, sizeof(int), P->stream));
+    hipLaunchKernelGGL(k_gram_narrow, dim3(2048), dim3(256), 0, P->stream, (const int32_t *)P->data->gramp, P->data->gramp16, (int64_t)P->data->nblocks * P->data->pstride, P->data->gram16_bad);
+    if (P->data->nblocks > 1)
+      hipLaunchKernelGGL(k_gram_narrow, dim3(2048), dim3(256), 0, P->stream, (const int32_t *)P->data->gramx + (size_t)m * m, P->data->gramx16 + (size_t)m * m, (int64_t)(P->data->nblocks - 1) * m * m, P->data->gram16_bad);
     HIPCHK(hipGetLastError());
     int bad = 1;
-    HIPCHK(hipMemcpyAsync(&bad, P->gram16_bad, sizeof(int), hipMemcpyDeviceToHost, P->stream));
+    HIPCHK(hipMemcpyAsync(&bad, P->data->gram16_bad, sizeof(int), hipMemcpyDeviceToHost, P->stream));
     HIPCHK(hipStreamSynchronize(P->stream));
-    P->gram16 = (bad == 0) && P->sw.gram16;   // BWGR_GRAM16=0 forces the 32-bit staging (A/B tests)
+    P->data->gram16 = (bad == 0) && P->data->sw.gram16;   // BWGR_GRAM16=0 forces the 32-bit staging (A/B tests)
   }
   // the affine sweeps' sequencer (sweep2w.hip.h) takes the cross blocks as biased byte planes: built where every entry fits 16 bits
-  P->winv_nd = 0;
-  if (!P->is_f32 && P->gram16 && P->sw.winv && m <= SW_MAXM) {
-    HIPCHK(hipMemsetAsync(P->gram16_bad, 0, sizeof(int), P->stream));
+  P->data->winv_nd = 0;
+  if (!P->data->is_f32 && P->data->gram16 && P->data->sw.winv && m <= SW_MAXM) {
+    HIPCHK(hipMemsetAsync(P->data->gram16_bad, 0, sizeof(int), P->stream));
     int nd = 0;
     int32_t *tmpx = nullptr;   // distances 4 and 5 (pipelines five and six blocks deep; main panels only): built here, kept as planes only
     for (int dist = 1; dist <= S2W_MAXDIST; ++dist) {
-      const int32_t *src = (const int32_t *)(dist == 1 ? P->gramx : dist == 2 ? P->gramx2 : dist == 3 ? P->gramx3 : nullptr);
+      const int32_t *src = (const int32_t *)(dist == 1 ? P->data->gramx : dist == 2 ? P->data->gramx2 : dist == 3 ? P->data->gramx3 : nullptr);
       if (dist > S2W_NEARD) {
-        if (!P->want3 || P->gram_maxdist < S2W_NEARD || P->nblocks <= dist || dist > P->sw.wlag_cap - 1) break;
-        if (!tmpx && hipMalloc(&tmpx, (size_t)P->nblocks * m * m * 4) != hipSuccess) { (void)hipGetLastError(); tmpx = nullptr; break; }
+        if (!P->data->want3 || P->data->gram_maxdist < S2W_NEARD || P->data->nblocks <= dist || dist > P->data->sw.wlag_cap - 1) break;
+        if (!tmpx && hipMalloc(&tmpx, (size_t)P->data->nblocks * m * m * 4) != hipSuccess) { (void)hipGetLastError(); tmpx = nullptr; break; }
         launch_gramx_i8(P, tmpx, dist);
         src = tmpx;
       }
-      if (P->nblocks <= dist || (dist <= S2W_NEARD && dist > P->gram_maxdist) || !src) break;
-      if (!P->gxt[dist - 1]) HIPCHK(hipMalloc(&P->gxt[dist - 1], (size_t)P->nblocks * S2W_PBYTES));
-      hipLaunchKernelGGL(k_gx_planes, dim3(4096), dim3(256), 0, P->stream, src, P->gxt[dist - 1], m, (int64_t)P->nblocks, dist, P->gram16_bad);
+      if (P->data->nblocks <= dist || (dist <= S2W_NEARD && dist > P->data->gram_maxdist) || !src) break;
+      if (!P->data->gxt[dist - 1]) HIPCHK(hipMalloc(&P->data->gxt[dist - 1], (size_t)P->data->nblocks * S2W_PBYTES));
+      hipLaunchKernelGGL(k_gx_planes, dim3(4096), dim3(256), 0, P->stream, src, P->data->gxt[dist - 1], m, (int64_t)P->data->nblocks, dist, P->data->gram16_bad);
       HIPCHK(hipGetLastError());
       nd = dist;
     }
     int bad = 1;
-    HIPCHK(hipMemcpyAsync(&bad, P->gram16_bad, sizeof(int), hipMemcpyDeviceToHost, P->stream));
+    HIPCHK(hipMemcpyAsync(&bad, P->data->gram16_bad, sizeof(int), hipMemcpyDeviceToHost, P->stream));
     HIPCHK(hipStreamSynchronize(P->stream));
     if (tmpx) hipFree(tmpx);
-    P->winv_nd = bad ? 0 : nd;
+    P->data->winv_nd = bad ? 0 : nd;
   }
   HIPCHK(hipStreamSynchronize(P->stream));
   return BWGR_OK;
 }
 
-// geometry + every device allocation of a panel of n rows x p markers (no data yet)
-static int panel_alloc(bwgr_panel **out, int is_f32, int64_t n, int64_t p, int device, int block, int nwg, const Switches &sw) {
+// The data of a panel of n rows x p markers -- its geometry and every device array, no values yet -- and its root handle, without the sweep
+// scratch (scratch_alloc, once the data is built).  near_only: bwgr_em's scratch panel, which sweeps at lag 2 on the 32-bit Gram blocks (no
+// blocks beyond distance 1, no 16-bit copies).
+static int panel_alloc(bwgr_panel **out, int is_f32, int64_t n, int64_t p, int device, int block, int nwg, const Switches &sw, bool near_only = false) {
   *out = nullptr;
   if (n < 2 || p < 1) return fail(BWGR_EINVAL, "panel: need n >= 2, p >= 1 (n=%lld p=%lld)", (long long)n, (long long)p);
   if (n > 0x7FFFFF00ll || p > 0x7FFFFF00ll) return fail(BWGR_EINVAL, "panel: n and p must fit 31 bits");
   CHK(require_device(device));
   bwgr_panel *P = new bwgr_panel();
-  P->device = device; P->n = n; P->p = p; P->is_f32 = is_f32; P->sw = sw;
-  const int mmax = P->is_f32 ? 64 : SW_MAXM;
+  P->data = new PanelData(); P->is_root = true;
+  P->data->device = device; P->data->n = n; P->data->p = p; P->data->is_f32 = is_f32; P->data->sw = sw; P->data->gram_maxdist = near_only ? 1 : 3;
+  const int mmax = P->data->is_f32 ? 64 : SW_MAXM;
   int m = block > 0 ? block : mmax;
-  if (m > mmax) { delete P; return fail(BWGR_EINVAL, "panel_create: block %d > %d (limit for this genotype type)", m, mmax); }
+  if (m > mmax) { delete P->data; delete P; return fail(BWGR_EINVAL, "panel_create: block %d > %d (limit for this genotype type)", m, mmax); }
   m = (int)std::min<int64_t>(m, ((p + 15) / 16) * 16);
   m = ((m + 15) / 16) * 16;
-  P->m = m;
-  const int Rmax = P->is_f32 ? max_slab_rows<float>(m) : max_slab_rows<int8_t>(m);
+  P->data->m = m;
+  const int Rmax = P->data->is_f32 ? max_slab_rows<float>(m) : max_slab_rows<int8_t>(m);
   // the pipelined engine keeps three tiles per streamer, so it takes fewer rows per slab than k_sweep at small blocks:
   // prefer the largest slab it fits (unless that needs more workgroups than the chip has CUs, or k_sweep is forced)
   int Rpick = Rmax;
   {
     int R2 = 0;
     for (int Rt = 128; Rt <= Rmax; Rt += 128)
-      if ((P->is_f32 ? sweep2_lds_bytes<float>(m, Rt) : sweep2_lds_bytes<int8_t>(m, Rt)) <= (size_t)160 * 1024 &&
-          (P->is_f32 || (size_t)m * Rt <= S2I_TILE_BYTES_MAX)) R2 = Rt;   // (an int8 tile must fit its movers' registers)
+      if ((P->data->is_f32 ? sweep2_lds_bytes<float>(m, Rt) : sweep2_lds_bytes<int8_t>(m, Rt)) <= (size_t)160 * 1024 &&
+          (P->data->is_f32 || (size_t)m * Rt <= S2I_TILE_BYTES_MAX)) R2 = Rt;   // (an int8 tile must fit its movers' registers)
     if (sw.sweep != '1' && R2 > 0 && (n + R2 - 1) / R2 + 1 + 6 <= 256) Rpick = R2;
   }
   int K = nwg > 0 ? nwg : (int)((n + Rpick - 1) / Rpick);
   int R = (int)((((n + K - 1) / K) + 127) / 128) * 128;
   if (K > 256 || R > Rmax) {
-    delete P;
+    delete P->data; delete P;
     return fail(BWGR_EINVAL, "panel_create: n=%lld needs %d slab workgroups of %d rows (limits: 256 workgroups, %d rows)", (long long)n, K, R, Rmax);
   }
-  P->K = K; P->R = R; P->ld = (int64_t)K * R;
-  P->nblocks = (p + m - 1) / m;
-  if (P->nblocks >= (1ll << 24)) { delete P; return fail(BWGR_EINVAL, "panel_create: %lld marker blocks; the delta granules carry a 24-bit block epoch", (long long)P->nblocks); }
-  P->lds_bytes = P->is_f32 ? sweep_lds_bytes<float>(m, R) : sweep_lds_bytes<int8_t>(m, R);
-  P->lds2_bytes = P->is_f32 ? sweep2_lds_bytes<float>(m, R) : sweep2_lds_bytes<int8_t>(m, R);
-  if (!P->is_f32 && s2i_lds_bytes(m, R, 4) <= (size_t)160 * 1024) {
-    P->lag4_ok = true;
-    P->lds2_bytes = std::max(P->lds2_bytes, s2i_lds_bytes(m, R, 4));
+  P->data->K = K; P->data->R = R; P->data->ld = (int64_t)K * R;
+  P->data->nblocks = (p + m - 1) / m;
+  if (P->data->nblocks >= (1ll << 24)) { delete P->data; delete P; return fail(BWGR_EINVAL, "panel_create: %lld marker blocks; the delta granules carry a 24-bit block epoch", (long long)P->data->nblocks); }
+  P->data->lds_bytes = P->data->is_f32 ? sweep_lds_bytes<float>(m, R) : sweep_lds_bytes<int8_t>(m, R);
+  P->data->lds2_bytes = P->data->is_f32 ? sweep2_lds_bytes<float>(m, R) : sweep2_lds_bytes<int8_t>(m, R);
+  if (!P->data->is_f32 && s2i_lds_bytes(m, R, 4) <= (size_t)160 * 1024) {
+    P->data->lag4_ok = true;
+    P->data->lds2_bytes = std::max(P->data->lds2_bytes, s2i_lds_bytes(m, R, 4));
   }
   {
-    P->sweep_version = (sw.sweep == '1') ? 1 : 2;   // A/B switch for tests and profiling
-    P->nfeed = std::min(6, std::max(2, (K + 39) / 40 + 1));   // K = 40: 2, K = 79: 3, K >= 161: 6
-    if (sw.nfeed >= 1 && sw.nfeed <= 6) P->nfeed = sw.nfeed;   // experiments
-    if (P->lds2_bytes > (size_t)160 * 1024 || K + 1 + P->nfeed > 256) P->sweep_version = 1;
-    if (!P->is_f32 && (size_t)m * R > S2I_TILE_BYTES_MAX) P->sweep_version = 1;
+    P->data->sweep_version = (sw.sweep == '1') ? 1 : 2;   // A/B switch for tests and profiling
+    P->data->nfeed = std::min(6, std::max(2, (K + 39) / 40 + 1));   // K = 40: 2, K = 79: 3, K >= 161: 6
+    if (sw.nfeed >= 1 && sw.nfeed <= 6) P->data->nfeed = sw.nfeed;   // experiments
+    if (P->data->lds2_bytes > (size_t)160 * 1024 || K + 1 + P->data->nfeed > 256) P->data->sweep_version = 1;
+    if (!P->data->is_f32 && (size_t)m * R > S2I_TILE_BYTES_MAX) P->data->sweep_version = 1;
   }
-  P->x_bytes = (size_t)P->ld * (size_t)p * (P->is_f32 ? 4 : 1);
-  P->gram_bytes = (size_t)P->nblocks * m * m * (P->is_f32 ? 8 : 4);   // per Gram array (diagonal blocks; off-diagonal blocks)
+  P->data->x_bytes = (size_t)P->data->ld * (size_t)p * (P->data->is_f32 ? 4 : 1);
+  P->data->gram_bytes = (size_t)P->data->nblocks * m * m * (P->data->is_f32 ? 8 : 4);   // per Gram array (diagonal blocks; off-diagonal blocks)
   int rc = BWGR_OK;
   auto bail = [&](int code) { bwgr_panel_destroy(P); return code; };
 #define PCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return bail(fail(BWGR_EHIP, "%s failed: %s", #x, hipGetErrorString(e_))); } while (0)
-  PCHK(hipMalloc(&P->X, P->x_bytes));
-  PCHK(hipMalloc(&P->gram, P->gram_bytes));
-  PCHK(hipMalloc(&P->gramx, P->gram_bytes));
-  if (P->sweep_version >= 2 && P->nblocks > 2) {   // distance-2 blocks: the selection models' lag-3 pipeline
-    PCHK(hipMalloc(&P->gramx2, P->gram_bytes));
-    PCHK(hipMalloc(&P->xspec2, sizeof(double) * (size_t)P->nblocks * SW_MAXM));
+  PCHK(hipMalloc(&P->data->X, P->data->x_bytes));
+  PCHK(hipMalloc(&P->data->gram, P->data->gram_bytes));
+  PCHK(hipMalloc(&P->data->gramx, P->data->gram_bytes));
+  if (P->data->sweep_version >= 2 && P->data->nblocks > 2 && !near_only)   // distance-2 blocks: the selection models' lag-3 pipeline
+    PCHK(hipMalloc(&P->data->gramx2, P->data->gram_bytes));
+  if (P->data->sweep_version >= 2 && !P->data->is_f32 && P->data->nblocks > 3 && P->data->lag4_ok && sw.lag != '2' && sw.lag != '3' && !near_only)   // distance-3 blocks: the lag-4 pipeline
+    PCHK(hipMalloc(&P->data->gramx3, P->data->gram_bytes));
+  P->data->pstride = ((m * (m - 1) / 2 + 7) / 8) * 8;
+  PCHK(hipMalloc(&P->data->gramp, (size_t)P->data->nblocks * std::max(P->data->pstride, 8) * (P->data->is_f32 ? 8 : 4)));
+  if (!P->data->is_f32 && P->data->sweep_version >= 2 && !near_only) {
+    PCHK(hipMalloc(&P->data->gramp16, (size_t)P->data->nblocks * std::max(P->data->pstride, 8) * 2));
+    PCHK(hipMalloc(&P->data->gramx16, (size_t)P->data->nblocks * m * m * 2));
+    PCHK(hipMalloc(&P->data->gram16_bad, sizeof(int)));
   }
-  if (P->sweep_version >= 2 && !P->is_f32 && P->nblocks > 3 && P->lag4_ok && sw.lag != '2' && sw.lag != '3') {   // distance-3 blocks: the lag-4 pipeline
-    PCHK(hipMalloc(&P->gramx3, P->gram_bytes));
-    PCHK(hipMalloc(&P->xspec3, sizeof(double) * (size_t)P->nblocks * SW_MAXM));
-  }
-  P->pstride = ((m * (m - 1) / 2 + 7) / 8) * 8;
-  PCHK(hipMalloc(&P->gramp, (size_t)P->nblocks * std::max(P->pstride, 8) * (P->is_f32 ? 8 : 4)));
-  if (!P->is_f32 && P->sweep_version >= 2) {
-    PCHK(hipMalloc(&P->gramp16, (size_t)P->nblocks * std::max(P->pstride, 8) * 2));
-    PCHK(hipMalloc(&P->gramx16, (size_t)P->nblocks * m * m * 2));
-    PCHK(hipMalloc(&P->gram16_bad, sizeof(int)));
-  }
-  PCHK(hipMalloc(&P->ps.spec, sizeof(SpecBuf) * (size_t)P->nblocks));
-  if (P->sweep_version >= 2) PCHK(hipMalloc(&P->ps.quick, sizeof(QuickBuf) * (size_t)P->nblocks));
-  PCHK(hipMalloc(&P->xx, sizeof(float) * p));
-  PCHK(hipMalloc(&P->vx, sizeof(float) * p));
-  PCHK(hipMalloc(&P->msx_dev, sizeof(float)));
-  PCHK(hipMalloc(&P->xpart, sizeof(double) * 2 * (size_t)K * SW_MAXM));
-  PCHK(alloc_exchange(P));
-  PCHK(hipMalloc(&P->ps.blocks, sizeof(StageBuf) * (size_t)P->nblocks));
-#if defined(BWGR_STAMPS) || defined(BWGR_EXPERIMENTS)
-  PCHK(hipMalloc(&P->stamps, sizeof(unsigned long long) * 256));
-  PCHK(hipMemset(P->stamps, 0, sizeof(unsigned long long) * 256));
-#endif
+  PCHK(hipMalloc(&P->data->xx, sizeof(float) * p));
+  PCHK(hipMalloc(&P->data->vx, sizeof(float) * p));
+  PCHK(hipMalloc(&P->data->msx_dev, sizeof(float)));
   for (const void *f : {reinterpret_cast<const void *>(k_sweep<int8_t, true>), reinterpret_cast<const void *>(k_sweep<int8_t, false>), reinterpret_cast<const void *>(k_sweep<float, true>),
                         reinterpret_cast<const void *>(k_sweep<float, false>), reinterpret_cast<const void *>(k_sweep2<int8_t, true>), reinterpret_cast<const void *>(k_sweep2<int8_t, false>),
                         reinterpret_cast<const void *>(k_sweep2<int8_t, true, uint16_t>), reinterpret_cast<const void *>(k_sweep2<float, true>), reinterpret_cast<const void *>(k_sweep2<float, false>),
                         reinterpret_cast<const void *>(k_sweep2w<true>), reinterpret_cast<const void *>(k_sweep2w<false>), reinterpret_cast<const void *>(k_affine_inv)})
     PCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #ifdef BWGR_EXPERIMENTS
-  if (!P->is_f32) P->ldsw_bytes = s2w_lds_bytes(m, R, sw.wlag_timing ? sw.wlag_timing : 6);
+  if (!P->data->is_f32) P->data->ldsw_bytes = s2w_lds_bytes(m, R, sw.wlag_timing ? sw.wlag_timing : 6);
 #else
-  if (!P->is_f32) P->ldsw_bytes = s2w_lds_bytes(m, R, 6);
+  if (!P->data->is_f32) P->data->ldsw_bytes = s2w_lds_bytes(m, R, 6);
 #endif   // (room for the deepest pipeline BWGR_WLAG can ask for)
 #undef PCHK
   (void)rc;
@@ -1966,12 +1975,13 @@ extern "C" int bwgr_panel_create(bwgr_panel **out, const void *X, int xtype, int
   if (memloc != BWGR_HOST && memloc != BWGR_DEVICE) return fail(BWGR_EINVAL, "panel_create: bad memloc %d", memloc);
   bwgr_panel *P = nullptr;
   CHK(panel_alloc(&P, xtype != BWGR_X_I8, n, p, device, block, nwg, read_switches()));
-  P->want3 = true;
+  P->data->want3 = true;
   int rc;
   if (xtype == BWGR_X_I8) rc = upload<int8_t, int8_t>(P, X, memloc, ldx);
   else if (xtype == BWGR_X_F32) rc = upload<float, float>(P, X, memloc, ldx);
   else rc = upload<double, float>(P, X, memloc, ldx);
   if (rc == BWGR_OK) rc = panel_setup(P);
+  if (rc == BWGR_OK) rc = scratch_alloc(P);
   if (rc != BWGR_OK) { bwgr_panel_destroy(P); return rc; }
   *out = P;
   return BWGR_OK;
@@ -1986,41 +1996,20 @@ extern "C" int bwgr_debug_stamps(bwgr_panel *P, unsigned long long out[256]) {
 }
 #endif
 
-// A clone: the same genotypes and Gram arrays (shared, read-only during sweeps), its own sweep scratch and its own
-// stream, so that chains on the parent and on its clones run concurrently on disjoint CUs.
+// A clone: a second handle on the same data (the genotypes and Gram arrays are read-only during sweeps) with its own sweep scratch and its
+// own stream, so that chains on the root panel and on its clones run concurrently on disjoint CUs.
 extern "C" int bwgr_panel_clone(bwgr_panel **out, bwgr_panel *src) {
   if (!out || !src) return fail(BWGR_EINVAL, "panel_clone: null pointer");
   *out = nullptr;
-  bwgr_panel *root = src->parent ? src->parent : src;
-  HIPCHK(hipSetDevice(root->device));
-  HIPCHK(hipStreamSynchronize(root->stream));   // the shared arrays are complete
-  bwgr_panel *P = new bwgr_panel(*root);
-  P->parent = root; P->nclones = 0; P->nchains = P->nchains_all = 0; P->own_stream = nullptr; P->stream = nullptr; P->ps_owner = nullptr; P->ps_iter = -1;
-  P->pair_streams.clear();   // (the root's: a clone owns none)
-  P->draws = nullptr; P->draws_stream = nullptr; P->draws_ready = nullptr; P->draws_free = nullptr; P->draws_valid = false;   // (its own, made on first use)
-  P->pre_pair_stream = nullptr; P->pre_pair_set = false; P->guard_ev = nullptr; P->guard_cus = 0; P->guard_stream = nullptr; P->guard_listed = false;
-  P->qsum3 = P->lists3 = nullptr; P->epoch3 = 0;
-  P->snap_e = nullptr; P->snap_b = P->snap_d = P->snap_vb = nullptr; P->xmax_dev = nullptr; P->winv = nullptr; P->qsumw = nullptr; P->cpre = nullptr;
-  P->xspec2 = P->xspec3 = nullptr; P->ps = {}; P->xpart = P->qpart = nullptr; P->dgran = nullptr; P->xflags = nullptr; P->xchg = nullptr; P->stamps = nullptr;
-  root->nclones++;
-  auto bail = [&](int code) { bwgr_panel_destroy(P); return code; };
-#define PCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return bail(fail(BWGR_EHIP, "%s failed: %s", #x, hipGetErrorString(e_))); } while (0)
-  const int K = P->K;
-  if (root->xspec2) PCHK(hipMalloc(&P->xspec2, sizeof(double) * (size_t)P->nblocks * SW_MAXM));
-  if (root->xspec3) PCHK(hipMalloc(&P->xspec3, sizeof(double) * (size_t)P->nblocks * SW_MAXM));
-  PCHK(hipMalloc(&P->ps.spec, sizeof(SpecBuf) * (size_t)P->nblocks));
-  if (P->sweep_version >= 2) PCHK(hipMalloc(&P->ps.quick, sizeof(QuickBuf) * (size_t)P->nblocks));
-  PCHK(hipMalloc(&P->ps.blocks, sizeof(StageBuf) * (size_t)P->nblocks));
-  PCHK(hipMalloc(&P->xpart, sizeof(double) * 2 * (size_t)K * SW_MAXM));
-  PCHK(alloc_exchange(P));
-#if defined(BWGR_STAMPS) || defined(BWGR_EXPERIMENTS)
-  PCHK(hipMalloc(&P->stamps, sizeof(unsigned long long) * 256));
-  PCHK(hipMemset(P->stamps, 0, sizeof(unsigned long long) * 256));
-#endif
-  PCHK(hipStreamCreateWithFlags(&P->own_stream, hipStreamNonBlocking));
-#undef PCHK
+  HIPCHK(hipSetDevice(src->data->device));
+  HIPCHK(hipStreamSynchronize(src->stream));   // the shared arrays are complete
+  bwgr_panel *P = new bwgr_panel();
+  P->data = src->data; P->data->nclones++;
+  const hipError_t e = hipStreamCreateWithFlags(&P->own_stream, hipStreamNonBlocking);
   P->stream = P->own_stream;
-  if (P->e3_ready) { int rc3 = sweep3_alloc_scratch(P); if (rc3 != BWGR_OK) return bail(rc3); HIPCHK(hipStreamSynchronize(P->stream)); }
+  const int rc = e != hipSuccess ? fail(BWGR_EHIP, "panel_clone: hipStreamCreateWithFlags failed: %s", hipGetErrorString(e)) : scratch_alloc(P);
+  if (rc != BWGR_OK) { bwgr_panel_destroy(P); return rc; }
+  HIPCHK(hipStreamSynchronize(P->stream));   // (k_sweep3's lists are zeroed on it)
   *out = P;
   return BWGR_OK;
 }
@@ -2029,17 +2018,17 @@ extern "C" int bwgr_panel_clone(bwgr_panel **out, bwgr_panel *src) {
 extern "C" int bwgr_panel_max_concurrent(const bwgr_panel *P, int selection, int *count) {
   if (!P || !count) return fail(BWGR_EINVAL, "null pointer");
   hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, P->device));
+  HIPCHK(hipGetDeviceProperties(&prop, P->data->device));
   SweepArgs a{}; a.flags = selection ? SWF_SELECT : 0u;
   const SweepPlan pl = plan_sweep(P, a, false);
   // selection on a panel with k_sweep3: the device sends a chain above the engine threshold to k_sweep2 (K + 1 + feeders), and a sweep that
   // leaves the fixed-point range is redone there: the larger of the two (K3 + 1: the streamers of chains side by side, never the solo ones)
-  int wgs = P->K + 1 + pl.nfeed;
-  if (pl.engine == 3) wgs = std::max(P->K3 + 1, wgs);
+  int wgs = P->data->K + 1 + pl.nfeed;
+  if (pl.engine == 3) wgs = std::max(P->data->K3 + 1, wgs);
   if (pl.engine == 4) wgs = pl.spins[0].resident;   // streamers, sequencer, L2 prefetchers (the launch's other workgroups leave at once)
   // one sweep workgroup per CU even where the LDS would admit two (small blocks): measured, sharing a CU costs more than it adds
   *count = std::max(1, prop.multiProcessorCount / wgs);
-  if (P->sw.max_concurrent > 0) *count = P->sw.max_concurrent;   // experiments
+  if (P->data->sw.max_concurrent > 0) *count = P->data->sw.max_concurrent;   // experiments
   return BWGR_OK;
 }
 
@@ -2048,11 +2037,11 @@ extern "C" int bwgr_panel_max_concurrent(const bwgr_panel *P, int selection, int
 extern "C" int bwgr_panel_max_pairs(const bwgr_panel *P, int *pairs) {
   if (!P || !pairs) return fail(BWGR_EINVAL, "null pointer");
   *pairs = 0;
-  if (!P->e3_ready || s3p_streamer_lds(P->R3) > (size_t)160 * 1024) return BWGR_OK;
-  const int cus = device_cus(P->device);
+  if (!P->data->e3_ready || s3p_streamer_lds(P->data->R3) > (size_t)160 * 1024) return BWGR_OK;
+  const int cus = device_cus(P->data->device);
   if (cus < 1) return fail(BWGR_EHIP, "panel_max_pairs: no device properties");
-  *pairs = std::max(1, (cus - 40) / (P->K3 + 2));
-  if (P->sw.max_pairs > 0) *pairs = P->sw.max_pairs;
+  *pairs = std::max(1, (cus - 40) / (P->data->K3 + 2));
+  if (P->data->sw.max_pairs > 0) *pairs = P->data->sw.max_pairs;
   return BWGR_OK;
 }
 
@@ -2073,8 +2062,8 @@ extern "C" int bwgr_panel_set_stream(bwgr_panel *P, void *hip_stream) {
 
 extern "C" int bwgr_panel_info(const bwgr_panel *P, int64_t info[8]) {
   if (!P || !info) return fail(BWGR_EINVAL, "null pointer");
-  info[0] = P->n; info[1] = P->p; info[2] = P->ld; info[3] = P->m; info[4] = P->K; info[5] = P->R;
-  info[6] = (int64_t)P->x_bytes; info[7] = (int64_t)(2 * P->gram_bytes);
+  info[0] = P->data->n; info[1] = P->data->p; info[2] = P->data->ld; info[3] = P->data->m; info[4] = P->data->K; info[5] = P->data->R;
+  info[6] = (int64_t)P->data->x_bytes; info[7] = (int64_t)(2 * P->data->gram_bytes);
   return BWGR_OK;
 }
 
@@ -2083,18 +2072,18 @@ extern "C" int bwgr_panel_pipeline(const bwgr_panel *P, int selection, int info[
   SweepArgs a{}; a.flags = selection ? SWF_SELECT : 0u;
   const SweepPlan pl = plan_sweep(P, a, false);
   info[0] = pl.engine;
-  info[1] = pl.engine == 3 ? P->e3_D : pl.lag;
+  info[1] = pl.engine == 3 ? P->data->e3_D : pl.lag;
   info[2] = pl.engine == 3 ? 0 : pl.nfeed;
-  info[3] = P->is_f32 ? 0 : (P->gram16 ? 16 : 32);
+  info[3] = P->data->is_f32 ? 0 : (P->data->gram16 ? 16 : 32);
   return BWGR_OK;
 }
 
 extern "C" int bwgr_panel_stats(bwgr_panel *P, float *xx, float *vx, float *MSx) {
   if (!P) return fail(BWGR_EINVAL, "null panel");
-  HIPCHK(hipSetDevice(P->device));
-  if (xx) HIPCHK(d2h(P->stream, xx, panel_cen(P) ? (P->parent ? P->parent : P)->xxc : P->xx, sizeof(float) * P->p));   // (centred panel: the centred columns' norms)
-  if (vx) HIPCHK(d2h(P->stream, vx, P->vx, sizeof(float) * P->p));
-  if (MSx) *MSx = P->MSx;
+  HIPCHK(hipSetDevice(P->data->device));
+  if (xx) HIPCHK(d2h(P->stream, xx, P->data->cen ? P->data->xxc : P->data->xx, sizeof(float) * P->data->p));   // (centred panel: the centred columns' norms)
+  if (vx) HIPCHK(d2h(P->stream, vx, P->data->vx, sizeof(float) * P->data->p));
+  if (MSx) *MSx = P->data->MSx;
   return BWGR_OK;
 }
 
@@ -2117,19 +2106,19 @@ struct DevBufs {
 
 // row gather of the resident panel P into the subsample panel PB (rows use_d[0..nbag), device array); KMUP2's H = X(Use, j)
 static void launch_gather_rows(bwgr_panel *P, bwgr_panel *PB, const int *use_d, int64_t nbag) {
-  if (P->is_f32) hipLaunchKernelGGL(k_gather_rows<float>, dim3(4096), dim3(256), 0, P->stream, (const float *)P->X, P->R, use_d, (int)nbag, (float *)PB->X, PB->R, PB->ld, P->p);
-  else if (P->ld <= 64 * 1024) {   // a column fits the LDS: stage, pick, write in 16-byte pieces
-    const int mpw = (int)std::max<int64_t>(1, std::min<int64_t>(8, (32 * 1024) / P->ld));   // ~30 KB of LDS per workgroup: five of them per CU
-    hipLaunchKernelGGL(k_gather_rows_i8, dim3((unsigned)((P->p + mpw - 1) / mpw)), dim3(256), (size_t)mpw * P->ld, P->stream, (const int8_t *)P->X, P->R, P->ld,
-                       use_d, (int)nbag, (int8_t *)PB->X, PB->R, PB->ld, P->p, mpw);
-  } else hipLaunchKernelGGL(k_gather_rows<int8_t>, dim3(4096), dim3(256), 0, P->stream, (const int8_t *)P->X, P->R, use_d, (int)nbag, (int8_t *)PB->X, PB->R, PB->ld, P->p);
+  if (P->data->is_f32) hipLaunchKernelGGL(k_gather_rows<float>, dim3(4096), dim3(256), 0, P->stream, (const float *)P->data->X, P->data->R, use_d, (int)nbag, (float *)PB->data->X, PB->data->R, PB->data->ld, P->data->p);
+  else if (P->data->ld <= 64 * 1024) {   // a column fits the LDS: stage, pick, write in 16-byte pieces
+    const int mpw = (int)std::max<int64_t>(1, std::min<int64_t>(8, (32 * 1024) / P->data->ld));   // ~30 KB of LDS per workgroup: five of them per CU
+    hipLaunchKernelGGL(k_gather_rows_i8, dim3((unsigned)((P->data->p + mpw - 1) / mpw)), dim3(256), (size_t)mpw * P->data->ld, P->stream, (const int8_t *)P->data->X, P->data->R, P->data->ld,
+                       use_d, (int)nbag, (int8_t *)PB->data->X, PB->data->R, PB->data->ld, P->data->p, mpw);
+  } else hipLaunchKernelGGL(k_gather_rows<int8_t>, dim3(4096), dim3(256), 0, P->stream, (const int8_t *)P->data->X, P->data->R, use_d, (int)nbag, (int8_t *)PB->data->X, PB->data->R, PB->data->ld, P->data->p);
 }
 
 // one sweep over panel PS with host-side b, d, xx, L and a device residual e64 (ld doubles, padding zero); KMUP and KMUP2
 static int kmup_sweep(bwgr_panel *PS, float *b, float *d, const float *xx, const float *L, double *e64, float Ve, float pi, float bg,
                       int kmup2, uint64_t seed, uint32_t iter, int rng_mode, const char *who) {
   DevBufs bufs;
-  const size_t p = (size_t)PS->p, pb = sizeof(float) * p;
+  const size_t p = (size_t)PS->data->p, pb = sizeof(float) * p;
   float *db = bufs.get<float>(p), *dd = bufs.get<float>(p), *dxx = bufs.get<float>(p), *dL = bufs.get<float>(p), *dvb = bufs.get<float>(p);
   ChainScalars *sc = bufs.get<ChainScalars>(1);
   if (!db || !dd || !dxx || !dL || !dvb || !sc) return fail(BWGR_ENOMEM, "%s: device allocation failed", who);
@@ -2157,19 +2146,19 @@ static int kmup_sweep(bwgr_panel *PS, float *b, float *d, const float *xx, const
 
 extern "C" int bwgr_kmup(bwgr_panel *P, float *b, float *d, const float *xx, float *e, const float *L, float Ve,
                          float pi, uint64_t seed, uint32_t iter, int rng_mode) {
-  if (P && panel_cen(P)) return fail(BWGR_EINVAL, "kmup: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
+  if (P && P->data->cen) return fail(BWGR_EINVAL, "kmup: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
   if (!P || !b || !d || !xx || !e || !L) return fail(BWGR_EINVAL, "kmup: null pointer");
-  HIPCHK(hipSetDevice(P->device));
+  HIPCHK(hipSetDevice(P->data->device));
   DevBufs bufs;
-  float *de = bufs.get<float>((size_t)P->n);
-  double *de64 = bufs.get<double>((size_t)P->ld);
+  float *de = bufs.get<float>((size_t)P->data->n);
+  double *de64 = bufs.get<double>((size_t)P->data->ld);
   if (!de || !de64) return fail(BWGR_ENOMEM, "kmup: device allocation failed");
-  HIPCHK(hipMemcpyAsync(de, e, sizeof(float) * P->n, hipMemcpyHostToDevice, P->stream));
-  hipLaunchKernelGGL(k_f2d, dim3(64), dim3(256), 0, P->stream, de, de64, P->n, P->ld);
+  HIPCHK(hipMemcpyAsync(de, e, sizeof(float) * P->data->n, hipMemcpyHostToDevice, P->stream));
+  hipLaunchKernelGGL(k_f2d, dim3(64), dim3(256), 0, P->stream, de, de64, P->data->n, P->data->ld);
   CHK(kmup_sweep(P, b, d, xx, L, de64, Ve, pi, 0.0f, 0, seed, iter, rng_mode, "kmup"));
-  hipLaunchKernelGGL(k_d2f, dim3(64), dim3(256), 0, P->stream, de64, de, P->n);
+  hipLaunchKernelGGL(k_d2f, dim3(64), dim3(256), 0, P->stream, de64, de, P->data->n);
   HIPCHK(hipGetLastError());
-  HIPCHK(d2h(P->stream, e, de, sizeof(float) * P->n));
+  HIPCHK(d2h(P->stream, e, de, sizeof(float) * P->data->n));
   return BWGR_OK;
 }
 
@@ -2179,30 +2168,31 @@ extern "C" int bwgr_kmup(bwgr_panel *P, float *b, float *d, const float *xx, flo
 // e_out receives the nuse residuals of the subsample (:76); E (n0 entries) is not modified.
 extern "C" int bwgr_kmup2(bwgr_panel *P, const int *Use, int64_t nuse, float *b, float *d, const float *xx, const float *E,
                           float *e_out, const float *L, float Ve, float pi, uint64_t seed, uint32_t iter, int rng_mode) {
-  if (P && panel_cen(P)) return fail(BWGR_EINVAL, "kmup2: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
+  if (P && P->data->cen) return fail(BWGR_EINVAL, "kmup2: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
   if (!P || !Use || !b || !d || !xx || !E || !e_out || !L) return fail(BWGR_EINVAL, "kmup2: null pointer");
   if (nuse < 2 || nuse > 0x7FFFFF00ll) return fail(BWGR_EINVAL, "kmup2: need 2 <= length(Use) < 2^31 (got %lld)", (long long)nuse);
   for (int64_t k = 0; k < nuse; ++k)
-    if (Use[k] < 0 || Use[k] >= P->n) return fail(BWGR_EINVAL, "kmup2: Use[%lld] = %d is outside 0..%lld", (long long)k, Use[k], (long long)P->n - 1);
-  HIPCHK(hipSetDevice(P->device));
+    if (Use[k] < 0 || Use[k] >= P->data->n) return fail(BWGR_EINVAL, "kmup2: Use[%lld] = %d is outside 0..%lld", (long long)k, Use[k], (long long)P->data->n - 1);
+  HIPCHK(hipSetDevice(P->data->device));
   bwgr_panel *PB = nullptr;
-  CHK(panel_alloc(&PB, P->is_f32, nuse, P->p, P->device, P->m, 0, P->sw));
+  CHK(panel_alloc(&PB, P->data->is_f32, nuse, P->data->p, P->data->device, P->data->m, 0, P->data->sw));
   PB->stream = P->stream;
   struct Drop { bwgr_panel *q; ~Drop() { if (q) bwgr_panel_destroy(q); } } drop{PB};
+  CHK(scratch_alloc(PB));
   DevBufs bufs;
   int *use_d = bufs.get<int>((size_t)nuse);
-  float *dE = bufs.get<float>((size_t)P->n), *deo = bufs.get<float>((size_t)nuse);
-  double *dE64 = bufs.get<double>((size_t)P->n), *e64 = bufs.get<double>((size_t)PB->ld);
+  float *dE = bufs.get<float>((size_t)P->data->n), *deo = bufs.get<float>((size_t)nuse);
+  double *dE64 = bufs.get<double>((size_t)P->data->n), *e64 = bufs.get<double>((size_t)PB->data->ld);
   if (!use_d || !dE || !deo || !dE64 || !e64) return fail(BWGR_ENOMEM, "kmup2: device allocation failed");
   HIPCHK(hipMemcpyAsync(use_d, Use, sizeof(int) * (size_t)nuse, hipMemcpyHostToDevice, P->stream));
-  HIPCHK(hipMemcpyAsync(dE, E, sizeof(float) * P->n, hipMemcpyHostToDevice, P->stream));
+  HIPCHK(hipMemcpyAsync(dE, E, sizeof(float) * P->data->n, hipMemcpyHostToDevice, P->stream));
   launch_gather_rows(P, PB, use_d, nuse);
   HIPCHK(hipGetLastError());
   CHK(panel_build_gram(PB));
-  hipLaunchKernelGGL(k_f2d, dim3(64), dim3(256), 0, P->stream, dE, dE64, P->n, P->n);
-  hipLaunchKernelGGL(k_gather_e, dim3(64), dim3(256), 0, P->stream, dE64, use_d, (int)nuse, PB->ld, e64);   // e0[k] = E[Use[k]], :49-53
+  hipLaunchKernelGGL(k_f2d, dim3(64), dim3(256), 0, P->stream, dE, dE64, P->data->n, P->data->n);
+  hipLaunchKernelGGL(k_gather_e, dim3(64), dim3(256), 0, P->stream, dE64, use_d, (int)nuse, PB->data->ld, e64);   // e0[k] = E[Use[k]], :49-53
   HIPCHK(hipGetLastError());
-  CHK(kmup_sweep(PB, b, d, xx, L, e64, Ve, pi, (float)P->n / (float)nuse, 1, seed, iter, rng_mode, "kmup2"));
+  CHK(kmup_sweep(PB, b, d, xx, L, e64, Ve, pi, (float)P->data->n / (float)nuse, 1, seed, iter, rng_mode, "kmup2"));
   hipLaunchKernelGGL(k_d2f, dim3(64), dim3(256), 0, P->stream, e64, deo, nuse);
   HIPCHK(hipGetLastError());
   HIPCHK(d2h(P->stream, e_out, deo, sizeof(float) * (size_t)nuse));
@@ -2222,7 +2212,7 @@ extern "C" int bwgr_chain_destroy(bwgr_chain *C) {
     if (C->P->draws_stream) (void)hipStreamSynchronize(C->P->draws_stream);   // (k_draws reads the chain's df from them)
     C->P->draws_valid = false; C->P->draws_sc = nullptr;
   }
-  if (C->P) { C->P->nchains--; (C->P->parent ? C->P->parent : C->P)->nchains_all--; (void)hipSetDevice(C->P->device); }
+  if (C->P) { C->P->nchains--; C->P->data->nchains_all--; (void)hipSetDevice(C->P->data->device); }
   for (hipEvent_t ev : C->ev) hipEventDestroy(ev);
   hipFree(C->e0); hipFree(C->y); if (C->e_owned) hipFree(C->e); hipFree(C->b); hipFree(C->d); hipFree(C->vb); hipFree(C->lam);
   hipFree(C->B); hipFree(C->D); hipFree(C->VB); hipFree(C->sc);
@@ -2236,30 +2226,30 @@ extern "C" int bwgr_chain_create_sharded(bwgr_chain **out, bwgr_panel *P, int mo
   if (!out || !P || !y) return fail(BWGR_EINVAL, "chain_create: null pointer");
   *out = nullptr;
   if (model < BWGR_BAYESA || model > BWGR_BAYESDPI) return fail(BWGR_EINVAL, "chain_create: bad model %d", model);
-  if (marker0 < 0 || p_total < marker0 + P->p || p_total > 0xFFFFFFF0ll) return fail(BWGR_EINVAL, "chain_create: bad shard [%lld,+%lld) of %lld", (long long)marker0, (long long)P->p, (long long)p_total);
-  HIPCHK(hipSetDevice(P->device));
-  if (panel_cen(P)) {
-    if (!has_d(model) || !P->e3_ready)
+  if (marker0 < 0 || p_total < marker0 + P->data->p || p_total > 0xFFFFFFF0ll) return fail(BWGR_EINVAL, "chain_create: bad shard [%lld,+%lld) of %lld", (long long)marker0, (long long)P->data->p, (long long)p_total);
+  HIPCHK(hipSetDevice(P->data->device));
+  if (P->data->cen) {
+    if (!has_d(model) || !P->data->e3_ready)
       return fail(BWGR_EINVAL, "chain_create: an implicitly centred panel (bwgr_panel_set_centred) runs the selection models BayesB / C / Cpi / Dpi only");
-    if (!P->cpre) HIPCHK(hipMalloc(&P->cpre, sizeof(double) * ((size_t)P->nblocks + 1)));
+    if (!P->cpre) HIPCHK(hipMalloc(&P->cpre, sizeof(double) * ((size_t)P->data->nblocks + 1)));
   }
   bwgr_chain *C = new bwgr_chain();
-  C->P = P; P->nchains++; (P->parent ? P->parent : P)->nchains_all++; C->model = model; C->itf = it; C->bif = bi; C->iit = (int)it; C->ibi = (int)bi;
+  C->P = P; P->nchains++; P->data->nchains_all++; C->model = model; C->itf = it; C->bif = bi; C->iit = (int)it; C->ibi = (int)bi;
   C->pi = pi; C->df = df; C->R2 = R2; C->seed = seed; C->rng_mode = rng_mode;
   C->marker0 = marker0; C->p_total = p_total; C->MSx_eff = MSx_total;
   C->Phi = MSx_total * (1 - R2) / R2;
-  const size_t pb = sizeof(float) * P->p;
+  const size_t pb = sizeof(float) * P->data->p;
   auto bail = [&](int code) { bwgr_chain_destroy(C); return code; };
 #define CCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return bail(fail(BWGR_EHIP, "%s failed: %s", #x, hipGetErrorString(e_))); } while (0)
-  CCHK(hipMalloc(&C->y, sizeof(float) * P->n));
-  if (e_ext) { C->e = e_ext; C->e_owned = false; } else CCHK(hipMalloc(&C->e, sizeof(double) * P->ld));
+  CCHK(hipMalloc(&C->y, sizeof(float) * P->data->n));
+  if (e_ext) { C->e = e_ext; C->e_owned = false; } else CCHK(hipMalloc(&C->e, sizeof(double) * P->data->ld));
   CCHK(hipMalloc(&C->b, pb)); CCHK(hipMalloc(&C->d, pb)); CCHK(hipMalloc(&C->vb, pb)); CCHK(hipMalloc(&C->lam, pb));
   CCHK(hipMalloc(&C->B, pb)); CCHK(hipMalloc(&C->D, pb)); CCHK(hipMalloc(&C->VB, pb)); CCHK(hipMalloc(&C->sc, sizeof(ChainScalars)));
-  CCHK(hipMemcpyAsync(C->y, y, sizeof(float) * P->n, memloc == BWGR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, P->stream));
-  InitArgs ia; ia.y = C->y; ia.e = C->e; ia.n = (int)P->n; ia.p = (int)P->p; ia.ld = P->ld; ia.model = model;
+  CCHK(hipMemcpyAsync(C->y, y, sizeof(float) * P->data->n, memloc == BWGR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, P->stream));
+  InitArgs ia; ia.y = C->y; ia.e = C->e; ia.n = (int)P->data->n; ia.p = (int)P->data->p; ia.ld = P->data->ld; ia.model = model;
   ia.pi = pi; ia.df = df; ia.R2 = R2; ia.MSx = MSx_total; ia.sc = C->sc;
   hipLaunchKernelGGL(k_chain_init, dim3(1), dim3(1024), 0, P->stream, ia);
-  hipLaunchKernelGGL(k_marker_init, dim3(1024), dim3(256), 0, P->stream, C->b, C->d, C->vb, C->lam, C->B, C->D, C->VB, (int)P->p, C->sc);
+  hipLaunchKernelGGL(k_marker_init, dim3(1024), dim3(256), 0, P->stream, C->b, C->d, C->vb, C->lam, C->B, C->D, C->VB, (int)P->data->p, C->sc);
   CCHK(hipGetLastError());
   CCHK(hipStreamSynchronize(P->stream));
 #undef CCHK
@@ -2270,7 +2260,7 @@ extern "C" int bwgr_chain_create_sharded(bwgr_chain **out, bwgr_panel *P, int mo
 extern "C" int bwgr_chain_create(bwgr_chain **out, bwgr_panel *P, int model, const float *y, int memloc, float it,
                                  float bi, float pi, float df, float R2, uint64_t seed, int rng_mode) {
   if (!P) return fail(BWGR_EINVAL, "chain_create: null pointer");
-  return bwgr_chain_create_sharded(out, P, model, y, memloc, it, bi, pi, df, R2, seed, rng_mode, 0, P->p, P->MSx, nullptr);
+  return bwgr_chain_create_sharded(out, P, model, y, memloc, it, bi, pi, df, R2, seed, rng_mode, 0, P->data->p, P->data->MSx, nullptr);
 }
 
 static void chain_args(const bwgr_chain *C, int blk_begin, int blk_end, SweepArgs &a) {
@@ -2284,10 +2274,9 @@ static void chain_args(const bwgr_chain *C, int blk_begin, int blk_end, SweepArg
   if (model == BWGR_BAYESDPI) fl |= SWF_ALT_B2 | SWF_MH;
   if (per_marker_vb(model)) fl |= SWF_LAM_VEC | SWF_VB_VEC;
   a.flags = fl | C->flags_extra;
-  a.e = C->e; a.b = C->b; a.d = C->d; a.vb = C->vb; a.xx = P->xx; a.lam = C->lam; a.sc = C->sc;
-  if (panel_cen(P)) {   // implicitly centred columns: the centred squared norms, the column sums, this handle's running block sums
-    const bwgr_panel *root = P->parent ? P->parent : P;
-    a.flags |= SWF_CENTRE; a.xx = root->xxc; a.csum = root->csum; a.cpre = P->cpre; a.ninv = 1.0 / (double)P->n;
+  a.e = C->e; a.b = C->b; a.d = C->d; a.vb = C->vb; a.xx = P->data->xx; a.lam = C->lam; a.sc = C->sc;
+  if (P->data->cen) {   // implicitly centred columns: the centred squared norms, the column sums, this handle's running block sums
+    a.flags |= SWF_CENTRE; a.xx = P->data->xxc; a.csum = P->data->csum; a.cpre = P->cpre; a.ninv = 1.0 / (double)P->data->n;
   }
   a.iter = (uint32_t)C->done; a.marker0 = (uint32_t)C->marker0; a.rng = make_rng(C->seed, C->rng_mode);
 }
@@ -2295,9 +2284,9 @@ static void chain_args(const bwgr_chain *C, int blk_begin, int blk_end, SweepArg
 extern "C" int bwgr_chain_sweep_blocks(bwgr_chain *C, int blk_begin, int blk_end) {
   if (!C) return fail(BWGR_EINVAL, "null chain");
   bwgr_panel *P = C->P;
-  if (blk_begin < 0 || blk_end > P->nblocks || blk_begin >= blk_end) return fail(BWGR_EINVAL, "sweep_blocks: bad range [%d,%d) of %lld", blk_begin, blk_end, (long long)P->nblocks);
+  if (blk_begin < 0 || blk_end > P->data->nblocks || blk_begin >= blk_end) return fail(BWGR_EINVAL, "sweep_blocks: bad range [%d,%d) of %lld", blk_begin, blk_end, (long long)P->data->nblocks);
   if (C->done >= C->iit) return fail(BWGR_EINVAL, "sweep_blocks: all %d iterations already run", C->iit);
-  HIPCHK(hipSetDevice(P->device));
+  HIPCHK(hipSetDevice(P->data->device));
   SweepArgs a;
   chain_args(C, blk_begin, blk_end, a);
   SweepPlan pl; int need = 0;
@@ -2310,7 +2299,7 @@ extern "C" int bwgr_chain_sweep_blocks(bwgr_chain *C, int blk_begin, int blk_end
   // marker-sharded sampler -- pre-stages all of them with the first range
   bool prestaged = false;
   if (P->ps_owner != C || P->ps_iter != C->done) {
-    SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->nblocks;
+    SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->data->nblocks;
     launch_prestage(P, all, pl);
     P->ps_owner = C; P->ps_iter = C->done;
     prestaged = true;
@@ -2318,7 +2307,7 @@ extern "C" int bwgr_chain_sweep_blocks(bwgr_chain *C, int blk_begin, int blk_end
   hipError_t he = hipEventRecord(e0, P->stream);
   if (he == hipSuccess) { launch_sweep_kernel(P, a, pl); he = hipGetLastError(); }
   if (he == hipSuccess && prestaged && C->done + 1 < C->iit) {   // the next iteration's variates, beside this sweep
-    SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->nblocks;
+    SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->data->nblocks;
     draws_ahead(P, all, pl, e0);
   }
   if (he == hipSuccess) he = hipEventRecord(e1, P->stream);
@@ -2347,11 +2336,11 @@ __global__ void k_round_apply(double *__restrict__ e, const double *__restrict__
 extern "C" int bwgr_chain_round_sweep(bwgr_chain *C, int blk_begin, int blk_end, double *delta_dev) {
   if (!C || !delta_dev) return fail(BWGR_EINVAL, "round_sweep: null pointer");
   bwgr_panel *P = C->P;
-  HIPCHK(hipSetDevice(P->device));
-  if (!C->e0) HIPCHK(hipMalloc(&C->e0, sizeof(double) * P->ld));
-  HIPCHK(hipMemcpyAsync(C->e0, C->e, sizeof(double) * P->ld, hipMemcpyDeviceToDevice, P->stream));
+  HIPCHK(hipSetDevice(P->data->device));
+  if (!C->e0) HIPCHK(hipMalloc(&C->e0, sizeof(double) * P->data->ld));
+  HIPCHK(hipMemcpyAsync(C->e0, C->e, sizeof(double) * P->data->ld, hipMemcpyDeviceToDevice, P->stream));
   if (blk_begin < blk_end) CHK(bwgr_chain_sweep_blocks(C, blk_begin, blk_end));
-  hipLaunchKernelGGL(k_round_delta, dim3(64), dim3(256), 0, P->stream, C->e, C->e0, delta_dev, P->ld);
+  hipLaunchKernelGGL(k_round_delta, dim3(64), dim3(256), 0, P->stream, C->e, C->e0, delta_dev, P->data->ld);
   HIPCHK(hipGetLastError());
   return BWGR_OK;
 }
@@ -2359,15 +2348,15 @@ extern "C" int bwgr_chain_round_apply(bwgr_chain *C, const double *delta_dev) {
   if (!C || !delta_dev) return fail(BWGR_EINVAL, "round_apply: null pointer");
   if (!C->e0) return fail(BWGR_EINVAL, "round_apply: no round_sweep before it");
   bwgr_panel *P = C->P;
-  HIPCHK(hipSetDevice(P->device));
-  hipLaunchKernelGGL(k_round_apply, dim3(64), dim3(256), 0, P->stream, C->e, C->e0, delta_dev, P->ld);
+  HIPCHK(hipSetDevice(P->data->device));
+  hipLaunchKernelGGL(k_round_apply, dim3(64), dim3(256), 0, P->stream, C->e, C->e0, delta_dev, P->data->ld);
   HIPCHK(hipGetLastError());
   return BWGR_OK;
 }
 
 extern "C" int bwgr_chain_get_sums(bwgr_chain *C, double sums[2]) {
   if (!C || !sums) return fail(BWGR_EINVAL, "null pointer");
-  HIPCHK(hipSetDevice(C->P->device));
+  HIPCHK(hipSetDevice(C->P->data->device));
   ChainScalars h;
   HIPCHK(hipMemcpyAsync(&h, C->sc, sizeof(h), hipMemcpyDeviceToHost, C->P->stream));
   HIPCHK(hipStreamSynchronize(C->P->stream));
@@ -2382,15 +2371,15 @@ extern "C" int bwgr_chain_end_iteration(bwgr_chain *C, const double sums_total[2
   if (!C) return fail(BWGR_EINVAL, "null chain");
   if (C->done >= C->iit) return fail(BWGR_EINVAL, "end_iteration: all %d iterations already run", C->iit);
   bwgr_panel *P = C->P;
-  HIPCHK(hipSetDevice(P->device));
+  HIPCHK(hipSetDevice(P->data->device));
   const int model = C->model, i = C->done;
   if (sums_total) hipLaunchKernelGGL(k_set_sums, dim3(1), dim3(1), 0, P->stream, C->sc, sums_total[0], sums_total[1]);
   const int accumulate = (i > C->ibi) ? 1 : 0;   // if(i>ibi), src/Rcpp20260726ai.cpp:624
-  TailArgs t; t.e = C->e; t.n = (int)P->n; t.p = (int)C->p_total; t.model = model; t.df = C->df; t.R2 = C->R2; t.Phi = C->Phi;
+  TailArgs t; t.e = C->e; t.n = (int)P->data->n; t.p = (int)C->p_total; t.model = model; t.df = C->df; t.R2 = C->R2; t.Phi = C->Phi;
   t.accumulate = accumulate; t.iter = (uint32_t)i; t.rng = make_rng(C->seed, C->rng_mode); t.sc = C->sc;
   hipLaunchKernelGGL(k_tail, dim3(1), dim3(1024), 0, P->stream, t);
-  hipLaunchKernelGGL(k_marker_tail, dim3((unsigned)std::min<int64_t>(2048, (P->p + 255) / 256)), dim3(256), 0, P->stream,
-                     C->b, C->d, C->vb, C->lam, C->B, C->D, C->VB, (int)P->p, model, C->Phi, accumulate, C->sc);
+  hipLaunchKernelGGL(k_marker_tail, dim3((unsigned)std::min<int64_t>(2048, (P->data->p + 255) / 256)), dim3(256), 0, P->stream,
+                     C->b, C->d, C->vb, C->lam, C->B, C->D, C->VB, (int)P->data->p, model, C->Phi, accumulate, C->sc);
   HIPCHK(hipGetLastError());
   C->done++;
   return BWGR_OK;
@@ -2404,14 +2393,14 @@ __global__ void k_set_sums_dev(ChainScalars *sc, const double *in2) { sc->sum_d 
 // caller all-reduces sums_dev, two doubles, in place), so an iteration needs no host round trip
 extern "C" int bwgr_chain_get_sums_dev(bwgr_chain *C, double *sums_dev) {
   if (!C || !sums_dev) return fail(BWGR_EINVAL, "null pointer");
-  HIPCHK(hipSetDevice(C->P->device));
+  HIPCHK(hipSetDevice(C->P->data->device));
   hipLaunchKernelGGL(k_get_sums_dev, dim3(1), dim3(1), 0, C->P->stream, C->sc, sums_dev);
   HIPCHK(hipGetLastError());
   return BWGR_OK;
 }
 extern "C" int bwgr_chain_end_iteration_dev(bwgr_chain *C, const double *sums_total_dev) {
   if (!C || !sums_total_dev) return fail(BWGR_EINVAL, "null pointer");
-  HIPCHK(hipSetDevice(C->P->device));
+  HIPCHK(hipSetDevice(C->P->data->device));
   hipLaunchKernelGGL(k_set_sums_dev, dim3(1), dim3(1), 0, C->P->stream, C->sc, sums_total_dev);
   HIPCHK(hipGetLastError());
   return bwgr_chain_end_iteration(C, nullptr);
@@ -2421,7 +2410,7 @@ extern "C" int bwgr_chain_run(bwgr_chain *C, int iters) {
   if (!C) return fail(BWGR_EINVAL, "null chain");
   if (iters < 0 || C->done + iters > C->iit) return fail(BWGR_EINVAL, "chain_run: %d more iterations would exceed it=%d (done %d)", iters, C->iit, C->done);
   for (int k = 0; k < iters; ++k) {
-    CHK(bwgr_chain_sweep_blocks(C, 0, (int)C->P->nblocks));
+    CHK(bwgr_chain_sweep_blocks(C, 0, (int)C->P->data->nblocks));
     CHK(bwgr_chain_end_iteration(C, nullptr));
   }
   return BWGR_OK;
@@ -2433,27 +2422,25 @@ extern "C" int bwgr_chain_run(bwgr_chain *C, int iters) {
 // bit-identical to a run of its own.  (No reference counterpart: the callers that fit many models on one X -- mcmcCV's loop,
 // /root/reference/R/cv.R:113-216 -- are where it plugs in.)
 extern "C" int bwgr_chain_run_pair(bwgr_chain *C0, bwgr_chain *C1, int iters) {
-  if (C0 && C0->P && panel_cen(C0->P)) return fail(BWGR_EINVAL, "chain_run_pair: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
+  if (C0 && C0->P && C0->P->data->cen) return fail(BWGR_EINVAL, "chain_run_pair: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
   if (!C0 || !C1 || C0 == C1) return fail(BWGR_EINVAL, "chain_run_pair: two distinct chains");
   bwgr_panel *P0 = C0->P, *P1 = C1->P;
-  const bwgr_panel *r0 = P0->parent ? P0->parent : P0, *r1 = P1->parent ? P1->parent : P1;
-  if (r0 != r1 || P0 == P1) return fail(BWGR_EINVAL, "chain_run_pair: the chains must sit on two handles (panel and clone) of one resident panel");
+  if (P0->data != P1->data || P0 == P1) return fail(BWGR_EINVAL, "chain_run_pair: the chains must sit on two handles (panel and clone) of one resident panel");
   if (iters < 0 || C0->done + iters > C0->iit || C1->done + iters > C1->iit) return fail(BWGR_EINVAL, "chain_run_pair: %d more iterations exceed it", iters);
   SweepArgs t0, t1;
-  chain_args(C0, 0, (int)P0->nblocks, t0); chain_args(C1, 0, (int)P1->nblocks, t1);
+  chain_args(C0, 0, (int)P0->data->nblocks, t0); chain_args(C1, 0, (int)P1->data->nblocks, t1);
   if (plan_sweep(P0, t0, false).engine != 3 || plan_sweep(P1, t1, false).engine != 3 || !P0->qsum3 || !P1->qsum3)
     return fail(BWGR_EINVAL, "chain_run_pair: both chains must be selection models on a panel with k_sweep3");
-  if (s3p_streamer_lds(P0->R3) > (size_t)160 * 1024) return fail(BWGR_EINVAL, "chain_run_pair: the paired streamers' LDS does not fit");
-  HIPCHK(hipSetDevice(P0->device));
+  if (s3p_streamer_lds(P0->data->R3) > (size_t)160 * 1024) return fail(BWGR_EINVAL, "chain_run_pair: the paired streamers' LDS does not fit");
+  HIPCHK(hipSetDevice(P0->data->device));
   // everything of the pair runs on ONE stream, owned by the root panel (it outlives both handles), and both handles move onto it
   // for as long as they run in pairs -- one cross-stream wait each, the first time: a wait per call would sit in a hardware queue
   // that other pairs' streams share, and stall them.  A handle's next sweep alone takes it back (leave_pair_stream).
-  bwgr_panel *root = P0->parent ? P0->parent : P0;
-  auto is_pair_stream = [&](hipStream_t st) { for (hipStream_t q : root->pair_streams) if (q == st) return true; return false; };
+  auto is_pair_stream = [&](hipStream_t st) { for (hipStream_t q : P0->data->pair_streams) if (q == st) return true; return false; };
   hipStream_t s0 = nullptr;
   if (is_pair_stream(P0->stream)) s0 = P0->stream;
   else if (is_pair_stream(P1->stream)) s0 = P1->stream;
-  else { HIPCHK(hipStreamCreateWithFlags(&s0, hipStreamNonBlocking)); root->pair_streams.push_back(s0); }
+  else { HIPCHK(hipStreamCreateWithFlags(&s0, hipStreamNonBlocking)); P0->data->pair_streams.push_back(s0); }
   for (bwgr_panel *PX : {P0, P1}) {
     if (PX->stream == s0) continue;
     hipEvent_t ev;
@@ -2469,7 +2456,7 @@ extern "C" int bwgr_chain_run_pair(bwgr_chain *C0, bwgr_chain *C1, int iters) {
   int rc = sweep_guard(P0, plan_sweep(P0, t0, false), s0, P1, &need);
   for (int k = 0; k < iters && rc == BWGR_OK; ++k) {
     SweepArgs a0, a1;
-    chain_args(C0, 0, (int)P0->nblocks, a0); chain_args(C1, 0, (int)P1->nblocks, a1);
+    chain_args(C0, 0, (int)P0->data->nblocks, a0); chain_args(C1, 0, (int)P1->data->nblocks, a1);
     const SweepPlan pl0 = plan_sweep(P0, a0, false), pl1 = plan_sweep(P1, a1, false);
     a0.lag = pl0.lag; a1.lag = pl1.lag;
     if ((rc = reset_exchange(P0)) != BWGR_OK || (rc = reset_exchange(P1)) != BWGR_OK) break;
@@ -2501,7 +2488,7 @@ extern "C" int bwgr_chain_run_pair(bwgr_chain *C0, bwgr_chain *C1, int iters) {
 
 extern "C" int bwgr_chain_sync(bwgr_chain *C) {
   if (!C) return fail(BWGR_EINVAL, "null chain");
-  HIPCHK(hipSetDevice(C->P->device));
+  HIPCHK(hipSetDevice(C->P->data->device));
   HIPCHK(hipStreamSynchronize(C->P->stream));
   ChainScalars h;
   HIPCHK(d2h(C->P->stream, &h, C->sc, sizeof(h)));
@@ -2517,7 +2504,7 @@ extern "C" int bwgr_chain_iterations(const bwgr_chain *C, int *done) {
 
 extern "C" int bwgr_chain_sweep_ms(bwgr_chain *C, float *avg_ms, int *launches) {
   if (!C) return fail(BWGR_EINVAL, "null chain");
-  HIPCHK(hipSetDevice(C->P->device));
+  HIPCHK(hipSetDevice(C->P->data->device));
   HIPCHK(hipStreamSynchronize(C->P->stream));
   float total = 0; int nl = 0;
   for (size_t k = 0; k + 1 < C->ev.size(); k += 2) {
@@ -2549,37 +2536,37 @@ extern "C" int bwgr_chain_state(bwgr_chain *C, float *b, float *d, float *e, flo
   if (!C) return fail(BWGR_EINVAL, "null chain");
   CHK(bwgr_chain_sync(C));
   bwgr_panel *P = C->P;
-  const size_t pb = sizeof(float) * P->p;
+  const size_t pb = sizeof(float) * P->data->p;
   ChainScalars h;
   HIPCHK(d2h(P->stream, &h, C->sc, sizeof(h)));
   if (b) HIPCHK(d2h(P->stream, b, C->b, pb));
   if (d) HIPCHK(d2h(P->stream, d, C->d, pb));
   if (e) {
     float *ef = nullptr;
-    HIPCHK(hipMalloc(&ef, sizeof(float) * P->n));
-    hipLaunchKernelGGL(k_d2f, dim3(64), dim3(256), 0, P->stream, C->e, ef, P->n);
-    HIPCHK(hipMemcpyAsync(e, ef, sizeof(float) * P->n, hipMemcpyDeviceToHost, P->stream));
+    HIPCHK(hipMalloc(&ef, sizeof(float) * P->data->n));
+    hipLaunchKernelGGL(k_d2f, dim3(64), dim3(256), 0, P->stream, C->e, ef, P->data->n);
+    HIPCHK(hipMemcpyAsync(e, ef, sizeof(float) * P->data->n, hipMemcpyDeviceToHost, P->stream));
     HIPCHK(hipStreamSynchronize(P->stream));
     hipFree(ef);
   }
   if (vb) {
     if (per_marker_vb(C->model)) HIPCHK(d2h(P->stream, vb, C->vb, pb));
-    else for (int64_t j = 0; j < P->p; ++j) vb[j] = h.vb;
+    else for (int64_t j = 0; j < P->data->p; ++j) vb[j] = h.vb;
   }
   if (scal) { scal[0] = h.mu; scal[1] = h.ve; scal[2] = h.vb; scal[3] = h.pi; }
   return BWGR_OK;
 }
 
 // column chunks of the two-stage GEMV: enough workgroups to fill the chip at 16 rows per thread (int8) or 4 (float)
-static int gemv_chunks(const bwgr_panel *P) { return (int)std::min<int64_t>(P->is_f32 ? 64 : 512, std::max<int64_t>(1, P->p / 512)); }
+static int gemv_chunks(const bwgr_panel *P) { return (int)std::min<int64_t>(P->data->is_f32 ? 64 : 512, std::max<int64_t>(1, P->data->p / 512)); }
 template <typename CT>
 static void gemv_launch(bwgr_panel *P, const CT *coef_dev, int nchunks, int cpc, double *part) {
-  if (P->is_f32) {
-    dim3 grid((unsigned)((P->ld / 4 + 255) / 256), (unsigned)nchunks);
-    hipLaunchKernelGGL((k_gemv_part<float, CT>), grid, dim3(256), 0, P->stream, (const float *)P->X, P->ld, P->R, (int)P->p, coef_dev, cpc, part);
+  if (P->data->is_f32) {
+    dim3 grid((unsigned)((P->data->ld / 4 + 255) / 256), (unsigned)nchunks);
+    hipLaunchKernelGGL((k_gemv_part<float, CT>), grid, dim3(256), 0, P->stream, (const float *)P->data->X, P->data->ld, P->data->R, (int)P->data->p, coef_dev, cpc, part);
   } else {
-    dim3 grid((unsigned)((P->ld / 16 + 255) / 256), (unsigned)nchunks);
-    hipLaunchKernelGGL((k_gemv_part_i8<CT>), grid, dim3(256), 0, P->stream, (const int8_t *)P->X, P->ld, P->R, (int)P->p, coef_dev, cpc, part);
+    dim3 grid((unsigned)((P->data->ld / 16 + 255) / 256), (unsigned)nchunks);
+    hipLaunchKernelGGL((k_gemv_part_i8<CT>), grid, dim3(256), 0, P->stream, (const int8_t *)P->data->X, P->data->ld, P->data->R, (int)P->data->p, coef_dev, cpc, part);
   }
 }
 
@@ -2587,18 +2574,18 @@ static void gemv_launch(bwgr_panel *P, const CT *coef_dev, int nchunks, int cpc,
 template <typename CT>
 static int gemv_hat(bwgr_panel *P, const CT *coef_dev, float MU, float *hat_dev, bool centred = false) {
   const int nchunks = gemv_chunks(P);
-  const int cpc = (int)((P->p + nchunks - 1) / nchunks);
+  const int cpc = (int)((P->data->p + nchunks - 1) / nchunks);
   double *part = nullptr;
-  HIPCHK(hipMalloc(&part, sizeof(double) * ((size_t)nchunks * P->ld + 1)));
+  HIPCHK(hipMalloc(&part, sizeof(double) * ((size_t)nchunks * P->data->ld + 1)));
   gemv_launch<CT>(P, coef_dev, nchunks, cpc, part);
   double *cen_off = nullptr;
   if constexpr (std::is_same<CT, float>::value) {
     if (centred) {   // X_c B = X B - sum_j mean_j B_j
-      cen_off = part + (size_t)nchunks * P->ld;
-      hipLaunchKernelGGL(k_cen_dot, dim3(1), dim3(1024), 0, P->stream, (P->parent ? P->parent : P)->csum, coef_dev, P->p, 1.0 / (double)P->n, cen_off);
+      cen_off = part + (size_t)nchunks * P->data->ld;
+      hipLaunchKernelGGL(k_cen_dot, dim3(1), dim3(1024), 0, P->stream, P->data->csum, coef_dev, P->data->p, 1.0 / (double)P->data->n, cen_off);
     }
   }
-  hipLaunchKernelGGL(k_hat_finish, dim3((unsigned)((P->n + 255) / 256)), dim3(256), 0, P->stream, part, P->ld, nchunks, (int)P->n, MU, hat_dev, (const double *)cen_off);
+  hipLaunchKernelGGL(k_hat_finish, dim3((unsigned)((P->data->n + 255) / 256)), dim3(256), 0, P->stream, part, P->data->ld, nchunks, (int)P->data->n, MU, hat_dev, (const double *)cen_off);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(P->stream));
   HIPCHK(hipFree(part));
@@ -2611,18 +2598,18 @@ extern "C" int bwgr_chain_result(bwgr_chain *C, float *mu, float *b, float *d, f
   if (C->done != C->iit) return fail(BWGR_EINVAL, "chain_result: %d of %d iterations run", C->done, C->iit);
   CHK(bwgr_chain_sync(C));
   bwgr_panel *P = C->P;
-  const size_t pb = sizeof(float) * P->p;
+  const size_t pb = sizeof(float) * P->data->p;
   const bool per = per_marker_vb(C->model);
   const float MCMC = C->itf - C->bif;                                              // :626
   DevBufs bufs;
   float *pval_dev = nullptr;
-  if (pval && !(pval_dev = bufs.get<float>((size_t)P->p))) return fail(BWGR_ENOMEM, "chain_result: device allocation failed");
+  if (pval && !(pval_dev = bufs.get<float>((size_t)P->data->p))) return fail(BWGR_ENOMEM, "chain_result: device allocation failed");
   if (!C->finalized) {
-    hipLaunchKernelGGL(k_final_markers, dim3(1024), dim3(256), 0, P->stream, C->B, C->D, C->VB, pval_dev, (int)P->p, MCMC, per ? 1 : 0);
+    hipLaunchKernelGGL(k_final_markers, dim3(1024), dim3(256), 0, P->stream, C->B, C->D, C->VB, pval_dev, (int)P->data->p, MCMC, per ? 1 : 0);
     HIPCHK(hipGetLastError());
     C->finalized = true;
   } else if (pval_dev) {
-    hipLaunchKernelGGL(k_final_markers, dim3(1024), dim3(256), 0, P->stream, C->B, C->D, C->VB, pval_dev, (int)P->p, 1.0f, per ? 1 : 0);
+    hipLaunchKernelGGL(k_final_markers, dim3(1024), dim3(256), 0, P->stream, C->B, C->D, C->VB, pval_dev, (int)P->data->p, 1.0f, per ? 1 : 0);
   }
   ChainScalars h;
   HIPCHK(hipMemcpyAsync(&h, C->sc, sizeof(h), hipMemcpyDeviceToHost, P->stream));
@@ -2634,7 +2621,7 @@ extern "C" int bwgr_chain_result(bwgr_chain *C, float *mu, float *b, float *d, f
     // vg = VB.sum()
     double *part = nullptr; float *sdev = nullptr;
     HIPCHK(hipMalloc(&part, sizeof(double) * 256)); HIPCHK(hipMalloc(&sdev, sizeof(float)));
-    hipLaunchKernelGGL(k_sum_stage1, dim3(256), dim3(256), 0, P->stream, C->VB, (int64_t)P->p, part);
+    hipLaunchKernelGGL(k_sum_stage1, dim3(256), dim3(256), 0, P->stream, C->VB, (int64_t)P->data->p, part);
     hipLaunchKernelGGL(k_sum_stage2, dim3(1), dim3(256), 0, P->stream, part, 256, sdev);
     HIPCHK(d2h(P->stream, &vg, sdev, sizeof(float)));
     hipFree(part); hipFree(sdev);
@@ -2653,9 +2640,9 @@ extern "C" int bwgr_chain_result(bwgr_chain *C, float *mu, float *b, float *d, f
   if (pval) HIPCHK(d2h(P->stream, pval, pval_dev, pb));
   if (hat) {
     float *hat_dev = nullptr;
-    HIPCHK(hipMalloc(&hat_dev, sizeof(float) * P->n));
-    int rc = gemv_hat<float>(P, C->B, MU, hat_dev, panel_cen(P));
-    if (rc == BWGR_OK) HIPCHK(d2h(P->stream, hat, hat_dev, sizeof(float) * P->n));
+    HIPCHK(hipMalloc(&hat_dev, sizeof(float) * P->data->n));
+    int rc = gemv_hat<float>(P, C->B, MU, hat_dev, P->data->cen);
+    if (rc == BWGR_OK) HIPCHK(d2h(P->stream, hat, hat_dev, sizeof(float) * P->data->n));
     hipFree(hat_dev);
     CHK(rc);
   }
@@ -2677,22 +2664,22 @@ extern "C" int bwgr_bayes(bwgr_panel *P, int model, const float *y, float it, fl
 extern "C" int bwgr_bayes2(bwgr_panel *P1, bwgr_panel *P2, int base_model, const float *y, float it, float bi, float pi, float df,
                            float R2, uint64_t seed, int rng_mode, float *mu, float *b1, float *d1, float *vb1, float *b2,
                            float *d2, float *vb2, float *ve, float *hat, float *h2) {
-  if ((P1 && panel_cen(P1)) || (P2 && panel_cen(P2))) return fail(BWGR_EINVAL, "bayes2: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
+  if ((P1 && P1->data->cen) || (P2 && P2->data->cen)) return fail(BWGR_EINVAL, "bayes2: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
   if (!P1 || !P2 || !y) return fail(BWGR_EINVAL, "bayes2: null pointer");
   if (base_model != BWGR_BAYESA && base_model != BWGR_BAYESB && base_model != BWGR_BAYESRR)
     return fail(BWGR_EINVAL, "bayes2: base model must be BayesA, BayesB or BayesRR (got %d)", base_model);
-  if (P1->device != P2->device || P1->n != P2->n || P1->ld != P2->ld || P1->K != P2->K || P1->R != P2->R)
+  if (P1->data->device != P2->data->device || P1->data->n != P2->data->n || P1->data->ld != P2->data->ld || P1->data->K != P2->data->K || P1->data->R != P2->data->R)
     return fail(BWGR_EINVAL, "bayes2: the two panels must share device, rows and slab geometry (n %lld/%lld, %d x %d vs %d x %d rows)",
-                (long long)P1->n, (long long)P2->n, P1->K, P1->R, P2->K, P2->R);
-  const int64_t p1 = P1->p, p2 = P2->p, n = P1->n;
+                (long long)P1->data->n, (long long)P2->data->n, P1->data->K, P1->data->R, P2->data->K, P2->data->R);
+  const int64_t p1 = P1->data->p, p2 = P2->data->p, n = P1->data->n;
   if (p1 + p2 > 0xFFFFFFF0ll - 2) return fail(BWGR_EINVAL, "bayes2: p1 + p2 too large");
-  HIPCHK(hipSetDevice(P1->device));
+  HIPCHK(hipSetDevice(P1->data->device));
   hipStream_t s2_saved = P2->stream;
   P2->stream = P1->stream;   // one stream orders the two chains' kernels
   bwgr_chain *C1 = nullptr, *C2 = nullptr;
   float *h1d = nullptr, *h2d = nullptr, *hatd = nullptr, *sdev = nullptr; double *part = nullptr;
-  int rc = bwgr_chain_create_sharded(&C1, P1, base_model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode, 0, p1 + p2, P1->MSx, nullptr);
-  if (rc == BWGR_OK) rc = bwgr_chain_create_sharded(&C2, P2, base_model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode, p1, p1 + p2, P2->MSx, C1->e);
+  int rc = bwgr_chain_create_sharded(&C1, P1, base_model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode, 0, p1 + p2, P1->data->MSx, nullptr);
+  if (rc == BWGR_OK) rc = bwgr_chain_create_sharded(&C2, P2, base_model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode, p1, p1 + p2, P2->data->MSx, C1->e);
   auto done = [&](int code) {
     if (C2) bwgr_chain_destroy(C2);
     if (C1) bwgr_chain_destroy(C1);
@@ -2710,8 +2697,8 @@ extern "C" int bwgr_bayes2(bwgr_panel *P1, bwgr_panel *P2, int base_model, const
   }
   const int iit = (int)it, ibi = (int)bi;
   for (int i = 0; i < iit; ++i) {
-    rc = bwgr_chain_sweep_blocks(C1, 0, (int)P1->nblocks);
-    if (rc == BWGR_OK) rc = bwgr_chain_sweep_blocks(C2, 0, (int)P2->nblocks);
+    rc = bwgr_chain_sweep_blocks(C1, 0, (int)P1->data->nblocks);
+    if (rc == BWGR_OK) rc = bwgr_chain_sweep_blocks(C2, 0, (int)P2->data->nblocks);
     if (rc != BWGR_OK) return done(rc);
     const int accumulate = (i > ibi) ? 1 : 0;                                        // if(i>ibi), :1047
     Tail2Args t; t.e = C1->e; t.n = (int)n; t.p1 = (int)p1; t.p2 = (int)p2; t.rr = rr ? 1 : 0; t.df = df;
@@ -2747,7 +2734,7 @@ extern "C" int bwgr_bayes2(bwgr_panel *P1, bwgr_panel *P2, int base_model, const
     hipLaunchKernelGGL(k_sum_stage2, dim3(1), dim3(256), 0, P1->stream, part, 256, sdev);
     BCHK(d2h(P1->stream, &v2, sdev, sizeof(float)));
     vg = v1 + v2;
-  } else vg = VB1s * P1->MSx + VB2s * P2->MSx;                                       // :1213
+  } else vg = VB1s * P1->data->MSx + VB2s * P2->data->MSx;                                       // :1213
   if (mu) *mu = MU;
   if (ve) *ve = VE;
   if (h2) *h2 = vg / (vg + VE);
@@ -2806,9 +2793,9 @@ extern "C" int bwgr_sample_rows(uint64_t seed, uint32_t iter, int64_t n, int64_t
 template <typename CT>
 static int gemv_parts(bwgr_panel *P, const CT *coef_dev, double **part_out, int *nchunks_out) {
   const int nchunks = gemv_chunks(P);
-  const int cpc = (int)((P->p + nchunks - 1) / nchunks);
+  const int cpc = (int)((P->data->p + nchunks - 1) / nchunks);
   double *part = *part_out;
-  if (!part) HIPCHK(hipMalloc(&part, sizeof(double) * (size_t)nchunks * P->ld));
+  if (!part) HIPCHK(hipMalloc(&part, sizeof(double) * (size_t)nchunks * P->data->ld));
   gemv_launch<CT>(P, coef_dev, nchunks, cpc, part);
   HIPCHK(hipGetLastError());
   *part_out = part; *nchunks_out = nchunks;
@@ -2824,22 +2811,22 @@ extern "C" int bwgr_wgr(bwgr_panel *P, const double *y, int it, int bi, int th, 
 extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int th, int iv, int de, double pi, double df, double R2,
                            uint64_t seed, int rng_mode, const double *U, const double *V, int64_t pk, double bag, int rp,
                            double *mu, double *b, double *Vb, double *d, double *Ve, double *hat, double *cxx, double *u, double *Vk) {
-  if (P && panel_cen(P)) return fail(BWGR_EINVAL, "wgr: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
+  if (P && P->data->cen) return fail(BWGR_EINVAL, "wgr: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
   if (!P || !y) return fail(BWGR_EINVAL, "wgr: null pointer");
   if (!U || pk <= 0) { U = nullptr; pk = 0; }
   if (U && !V) return fail(BWGR_EINVAL, "wgr: eigenvalues missing");
   const bool bagging = (bag != 1.0);
   if (bagging && U) return fail(BWGR_EINVAL, "wgr: bag != 1 with eigK is undefined in the reference (R/wgr.R:73-79 index a subsampled e with full row ids)");
   if (bagging && !(bag > 0.0)) return fail(BWGR_EINVAL, "wgr: bag must be > 0");
-  const int64_t nbag = bagging ? (int64_t)((double)P->n * bag) : P->n;
+  const int64_t nbag = bagging ? (int64_t)((double)P->data->n * bag) : P->data->n;
   if (bagging && nbag < 2) return fail(BWGR_EINVAL, "wgr: n*bag < 2");
   // sample(n, n*bag, FALSE) cannot take more than the population (R errors out, R/wgr.R:68)
-  if (bagging && !rp && nbag > P->n) return fail(BWGR_EINVAL, "wgr: bag > 1 needs rp = TRUE (cannot take %lld of %lld rows without replacement)", (long long)nbag, (long long)P->n);
+  if (bagging && !rp && nbag > P->data->n) return fail(BWGR_EINVAL, "wgr: bag > 1 needs rp = TRUE (cannot take %lld of %lld rows without replacement)", (long long)nbag, (long long)P->data->n);
   if (bagging) df = df / (bag * bag);                                              // R/wgr.R:20
   if (it < 1 || bi < 0 || th < 1) return fail(BWGR_EINVAL, "wgr: need it >= 1, bi >= 0, th >= 1");
   if (de) iv = 1;                                                                  // R/wgr.R:9
-  HIPCHK(hipSetDevice(P->device));
-  const int p = (int)P->p, n = (int)P->n;
+  HIPCHK(hipSetDevice(P->data->device));
+  const int p = (int)P->data->p, n = (int)P->data->n;
   const size_t pd = sizeof(double) * p, pf = sizeof(float) * p;
   const Rng rng = make_rng(seed, rng_mode);
   int mc = 0; for (int q = bi; q <= it; q += th) mc++;                             // post = seq(bi,it,th)
@@ -2849,7 +2836,7 @@ extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int t
   auto cleanup = [&]() { for (void *q : owned) hipFree(q); };
   bwgr_panel *PU = nullptr;   // eigenvectors as an fp32 panel (KMUP narrows U to float like any other X)
   if (U) {
-    int rcu = bwgr_panel_create(&PU, U, BWGR_X_F64, BWGR_HOST, n, pk, n, P->device, 0, 0);
+    int rcu = bwgr_panel_create(&PU, U, BWGR_X_F64, BWGR_HOST, n, pk, n, P->data->device, 0, 0);
     if (rcu != BWGR_OK) return rcu;
     PU->stream = P->stream;
   }
@@ -2858,12 +2845,12 @@ extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int t
   std::vector<int> use_h;
   auto drop_panels = [&]() { if (PU) bwgr_panel_destroy(PU); if (PB) bwgr_panel_destroy(PB); hipFree(use_d); PU = PB = nullptr; use_d = nullptr; };
   if (bagging) {
-    int rcb = panel_alloc(&PB, P->is_f32, nbag, P->p, P->device, P->m, 0, P->sw);
+    int rcb = panel_alloc(&PB, P->data->is_f32, nbag, P->data->p, P->data->device, P->data->m, 0, P->data->sw);
+    if (rcb == BWGR_OK) { PB->stream = P->stream; rcb = scratch_alloc(PB); }
     if (rcb != BWGR_OK) { drop_panels(); return rcb; }
-    PB->stream = P->stream;
     if (hipMalloc(&use_d, sizeof(int) * (size_t)nbag) != hipSuccess) { drop_panels(); return fail(BWGR_ENOMEM, "wgr: device allocation failed"); }
   }
-  const int64_t ldmax = std::max<int64_t>(std::max<int64_t>(P->ld, PU ? PU->ld : 0), PB ? PB->ld : 0);
+  const int64_t ldmax = std::max<int64_t>(std::max<int64_t>(P->data->ld, PU ? PU->data->ld : 0), PB ? PB->data->ld : 0);
   const size_t kd = sizeof(double) * (size_t)std::max<int64_t>(pk, 1), kf = sizeof(float) * (size_t)std::max<int64_t>(pk, 1);
   double *yd = (double *)dalloc(sizeof(double) * n), *eR = (double *)dalloc(sizeof(double) * ldmax), *e64 = (double *)dalloc(sizeof(double) * ldmax);
   double *Ud = (double *)dalloc(sizeof(double) * (size_t)std::max<int64_t>(n * pk, 1)), *Vd = (double *)dalloc(kd), *hR = (double *)dalloc(kd), *Hk = (double *)dalloc(kd), *uhd = (double *)dalloc(sizeof(double) * n);
@@ -2890,15 +2877,15 @@ extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int t
       WCHK(hipMemsetAsync(hR, 0, kd, P->stream)); WCHK(hipMemsetAsync(Hk, 0, kd, P->stream));
     }
     const int wpb = 4;
-    if (P->is_f32) hipLaunchKernelGGL(k_stats64<float>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const float *)P->X, P->R, n, p, xx64, vx64);
-    else hipLaunchKernelGGL(k_stats64<int8_t>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const int8_t *)P->X, P->R, n, p, xx64, vx64);
+    if (P->data->is_f32) hipLaunchKernelGGL(k_stats64<float>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const float *)P->data->X, P->data->R, n, p, xx64, vx64);
+    else hipLaunchKernelGGL(k_stats64<int8_t>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const int8_t *)P->data->X, P->data->R, n, p, xx64, vx64);
     hipLaunchKernelGGL(k_dsum_stage1, dim3(256), dim3(256), 0, P->stream, vx64, (int64_t)p, part1, 0);
     hipLaunchKernelGGL(k_dsum_stage1, dim3(256), dim3(256), 0, P->stream, xx64, (int64_t)p, part2, 0);
     hipLaunchKernelGGL(k_wgr_init, dim3(1), dim3(1024), 0, P->stream, yd, eR, n, ldmax, part1, part2, p, df, R2, ws);
     hipLaunchKernelGGL(k_wgr_marker_init, dim3(1024), dim3(256), 0, P->stream, bR, dR, VbR, LR, B, D, VB, p, ws);
     if (bagging) hipLaunchKernelGGL(k_scale_d, dim3(256), dim3(256), 0, P->stream, xx64, (int64_t)p, bag);     // xx = crossprod * bag, R/wgr.R:46
     WCHK(hipGetLastError());
-    const unsigned pg = (unsigned)std::min<int64_t>(2048, (P->p + 255) / 256);
+    const unsigned pg = (unsigned)std::min<int64_t>(2048, (P->data->p + 255) / 256);
     for (int i = 1; i <= it; ++i) {                                                // R/wgr.R:66
       const uint32_t itx = (uint32_t)(i - 1);
       const int accumulate = (i >= bi && ((i - bi) % th) == 0) ? 1 : 0;            // i %in% post
@@ -2936,7 +2923,7 @@ extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int t
       hipLaunchKernelGGL(k_wgr_L, dim3(pg), dim3(256), 0, P->stream, bR, dR, VbR, LR, B, D, VB, p, iv, accumulate, ws);
       rc = gemv_parts<double>(P, bR, &gpart, &nchunks);
       if (rc != BWGR_OK) goto done;
-      hipLaunchKernelGGL(k_wgr_efinish, dim3((n + 255) / 256), dim3(256), 0, P->stream, gpart, P->ld, nchunks, n, yd, eR, ws);
+      hipLaunchKernelGGL(k_wgr_efinish, dim3((n + 255) / 256), dim3(256), 0, P->stream, gpart, P->data->ld, nchunks, n, yd, eR, ws);
       if (pk > 0) hipLaunchKernelGGL(k_uh, dim3((n + 255) / 256), dim3(256), 0, P->stream, Ud, hR, n, (int)pk, 1.0, eR, 1);   // - U %*% h
       hipLaunchKernelGGL(k_wgr_mu, dim3(1), dim3(1024), 0, P->stream, eR, n, iv, accumulate, itx, rng, ws);
       if (pk > 0 && accumulate) hipLaunchKernelGGL(k_wgr_accum_k, dim3(8), dim3(256), 0, P->stream, hR, Hk, (int)pk, ws);
@@ -2953,7 +2940,7 @@ extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int t
     const double B0 = h.B0 / mc;
     rc = gemv_parts<double>(P, B, &gpart, &nchunks);                               // HAT = B0 + gen0 %*% B, R/wgr.R:152
     if (rc != BWGR_OK) goto done;
-    hipLaunchKernelGGL(k_hat64_finish, dim3((n + 255) / 256), dim3(256), 0, P->stream, gpart, P->ld, nchunks, n, B0, hatd);
+    hipLaunchKernelGGL(k_hat64_finish, dim3((n + 255) / 256), dim3(256), 0, P->stream, gpart, P->data->ld, nchunks, n, B0, hatd);
     if (pk > 0) {                                                                  // poly = U0 %*% H; HAT += poly, R/wgr.R:148-150
       hipLaunchKernelGGL(k_uh, dim3((n + 255) / 256), dim3(256), 0, P->stream, Ud, Hk, n, (int)pk, 1.0 / (double)mc, uhd, 0);
       hipLaunchKernelGGL(k_add_vec, dim3((n + 255) / 256), dim3(256), 0, P->stream, hatd, uhd, n);
@@ -3091,32 +3078,32 @@ __global__ void k_uncentred(const float *xx, const float *vx, int64_t p, double 
 // what makes the marker-sharded sampler of several devices sound without a float copy of the panel.  Refused while chains are alive.
 extern "C" int bwgr_panel_set_centred(bwgr_panel *P, int on) {
   if (!P) return fail(BWGR_EINVAL, "null panel");
-  if (P->parent) return fail(BWGR_EINVAL, "panel_set_centred: set it on the root panel (clones follow it)");
-  if (P->nchains_all > 0) return fail(BWGR_EINVAL, "panel_set_centred: %d chains are alive on this panel and its clones", P->nchains_all);
-  HIPCHK(hipSetDevice(P->device));
-  if (!on) { P->cen = false; return BWGR_OK; }
-  if (P->is_f32) return fail(BWGR_EINVAL, "panel_set_centred: float panels are swept as given (centre the columns before the upload)");
-  if (!P->e3_ready) return fail(BWGR_EINVAL, "panel_set_centred: this panel has no k_sweep3 (geometry or Gram range): the implicitly centred sweep is k_sweep3's");
-  if (!P->csum) {
-    HIPCHK(hipMalloc(&P->csum, sizeof(int32_t) * (size_t)P->p));
-    HIPCHK(hipMalloc(&P->xxc, sizeof(float) * (size_t)P->p));
+  if (!P->is_root) return fail(BWGR_EINVAL, "panel_set_centred: set it on the root panel (clones follow it)");
+  if (P->data->nchains_all > 0) return fail(BWGR_EINVAL, "panel_set_centred: %d chains are alive on this panel and its clones", P->data->nchains_all);
+  HIPCHK(hipSetDevice(P->data->device));
+  if (!on) { P->data->cen = false; return BWGR_OK; }
+  if (P->data->is_f32) return fail(BWGR_EINVAL, "panel_set_centred: float panels are swept as given (centre the columns before the upload)");
+  if (!P->data->e3_ready) return fail(BWGR_EINVAL, "panel_set_centred: this panel has no k_sweep3 (geometry or Gram range): the implicitly centred sweep is k_sweep3's");
+  if (!P->data->csum) {
+    HIPCHK(hipMalloc(&P->data->csum, sizeof(int32_t) * (size_t)P->data->p));
+    HIPCHK(hipMalloc(&P->data->xxc, sizeof(float) * (size_t)P->data->p));
     const int wpb = 4;
-    hipLaunchKernelGGL(k_colsum_i8, dim3((unsigned)((P->p + wpb - 1) / wpb)), dim3(64 * wpb), 0, P->stream, (const int8_t *)P->X, P->R, (int)P->n, (int)P->p, P->csum, P->xxc);
+    hipLaunchKernelGGL(k_colsum_i8, dim3((unsigned)((P->data->p + wpb - 1) / wpb)), dim3(64 * wpb), 0, P->stream, (const int8_t *)P->data->X, P->data->R, (int)P->data->n, (int)P->data->p, P->data->csum, P->data->xxc);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(P->stream));
   }
-  P->cen = true;
+  P->data->cen = true;
   return BWGR_OK;
 }
 
 extern "C" int bwgr_panel_centred(bwgr_panel *P, int *centred) {
   if (!P || !centred) return fail(BWGR_EINVAL, "null pointer");
-  if (panel_cen(P)) { *centred = 1; return BWGR_OK; }   // implicitly centred: exactly
-  HIPCHK(hipSetDevice(P->device));
+  if (P->data->cen) { *centred = 1; return BWGR_OK; }   // implicitly centred: exactly
+  HIPCHK(hipSetDevice(P->data->device));
   int *flag = nullptr, h = 0;
   HIPCHK(hipMalloc(&flag, sizeof(int)));
   HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), P->stream));
-  hipLaunchKernelGGL(k_uncentred, dim3(256), dim3(256), 0, P->stream, P->xx, P->vx, P->p, (double)P->n, flag);
+  hipLaunchKernelGGL(k_uncentred, dim3(256), dim3(256), 0, P->stream, P->data->xx, P->data->vx, P->data->p, (double)P->data->n, flag);
   HIPCHK(d2h(P->stream, &h, flag, sizeof(int)));
   HIPCHK(hipFree(flag));
   *centred = h ? 0 : 1;
@@ -3160,10 +3147,10 @@ static int group_create_impl(bwgr_group **out, int ndev, const int *devices, con
       if (hipStreamCreateWithFlags(&q, hipStreamNonBlocking) != hipSuccess) return bail(fail(BWGR_EHIP, "group_create: hipStreamCreate failed"));
       Gp->streams.push_back(q);
       Gp->P[g]->stream = q;
-      if (ndev > 2 && Gp->P[g]->sw.solo3 < 0) Gp->P[g]->solo3 = false;   // (an explicit BWGR_SOLO3 decides otherwise: experiments)
+      if (ndev > 2 && Gp->P[g]->data->sw.solo3 < 0) Gp->P[g]->data->solo3 = false;   // (an explicit BWGR_SOLO3 decides otherwise: experiments)
     }
     if (centre) { rc = bwgr_panel_set_centred(Gp->P[g], 1); if (rc != BWGR_OK) return bail(rc); }   // the shard's own column means (rows are not sharded)
-    msx += (double)Gp->P[g]->MSx;
+    msx += (double)Gp->P[g]->data->MSx;
     int cen = 1;
     rc = bwgr_panel_centred(Gp->P[g], &cen);
     if (rc != BWGR_OK) return bail(rc);
@@ -3171,7 +3158,7 @@ static int group_create_impl(bwgr_group **out, int ndev, const int *devices, con
   }
   Gp->MSx_total = (float)msx;
   if (ndev > 1 && !Gp->centred) {
-    if (!Gp->P[0]->sw.group_allow_uncentred)
+    if (!Gp->P[0]->data->sw.group_allow_uncentred)
       return bail(fail(BWGR_EINVAL, "group_create: the columns of X are not centred, and on uncentred columns the marker-sharded sampler of %d devices is "
                                     "statistically unsound (every shard corrects the same stale residual mean: DESIGN.md section 8).  Pass centred columns "
                                     "(x_j - mean(x_j), float: the posterior of b and hat is the same under the sampler's flat intercept prior), use one "
@@ -3180,24 +3167,24 @@ static int group_create_impl(bwgr_group **out, int ndev, const int *devices, con
   for (int g = 0; g < ndev; ++g) {
     int rc = bwgr_chain_create_sharded(&Gp->C[g], Gp->P[g], model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode, Gp->lo[g], p, Gp->MSx_total, nullptr);
     if (rc != BWGR_OK) return bail(rc);
-    if (hipSetDevice(devices[g]) != hipSuccess || hipMalloc(&Gp->delta[g], sizeof(double) * (size_t)Gp->P[g]->ld) != hipSuccess ||
+    if (hipSetDevice(devices[g]) != hipSuccess || hipMalloc(&Gp->delta[g], sizeof(double) * (size_t)Gp->P[g]->data->ld) != hipSuccess ||
         hipMalloc(&Gp->sums[g], sizeof(double) * 2) != hipSuccess) return bail(fail(BWGR_ENOMEM, "group_create: device allocation failed"));
-    if (Gp->P[g]->ld != Gp->P[0]->ld) return bail(fail(BWGR_EINVAL, "group_create: shards disagree on the padded row count"));
+    if (Gp->P[g]->data->ld != Gp->P[0]->data->ld) return bail(fail(BWGR_EINVAL, "group_create: shards disagree on the padded row count"));
   }
   // (shards side by side exchange through one kernel on the same card, not a ring over xGMI, but every exchange is a launch boundary for all of
   // them: 131072 markers per shard between two exchanges there)
   const int64_t mps = markers_per_sync > 0 ? markers_per_sync : std::max<int64_t>(m, Gp->same_dev ? 131072 : 131072 / ndev);
   Gp->bps = (int)std::max<int64_t>(1, mps / m);
   int64_t nbmax = 0;
-  for (int g = 0; g < ndev; ++g) nbmax = std::max<int64_t>(nbmax, Gp->P[g]->nblocks);
+  for (int g = 0; g < ndev; ++g) nbmax = std::max<int64_t>(nbmax, Gp->P[g]->data->nblocks);
   Gp->rounds = (int)((nbmax + Gp->bps - 1) / Gp->bps);
-  Gp->use_comm = (ndev > 1 && !Gp->same_dev) || (Gp->P[0]->sw.group_force_comm && !Gp->same_dev);   // (BWGR_GROUP_FORCE_COMM=1, tests: exercise the RCCL path with a single device)
+  Gp->use_comm = (ndev > 1 && !Gp->same_dev) || (Gp->P[0]->data->sw.group_force_comm && !Gp->same_dev);   // (BWGR_GROUP_FORCE_COMM=1, tests: exercise the RCCL path with a single device)
   if (Gp->same_dev) {
     if (hipSetDevice(devices[0]) != hipSuccess) return bail(fail(BWGR_EHIP, "group_create: hipSetDevice failed"));
     Gp->ev_sweep.assign(ndev, nullptr);
     for (int g = 0; g < ndev; ++g) if (hipEventCreateWithFlags(&Gp->ev_sweep[g], hipEventDisableTiming) != hipSuccess) return bail(fail(BWGR_EHIP, "group_create: hipEventCreate failed"));
     for (int k = 0; k < 2; ++k) {
-      if (hipEventCreateWithFlags(&Gp->ev_sum[k], hipEventDisableTiming) != hipSuccess || hipMalloc(&Gp->total[k], sizeof(double) * (size_t)Gp->P[0]->ld) != hipSuccess ||
+      if (hipEventCreateWithFlags(&Gp->ev_sum[k], hipEventDisableTiming) != hipSuccess || hipMalloc(&Gp->total[k], sizeof(double) * (size_t)Gp->P[0]->data->ld) != hipSuccess ||
           hipMalloc(&Gp->total_sums[k], sizeof(double) * 2) != hipSuccess) return bail(fail(BWGR_ENOMEM, "group_create: device allocation failed"));
     }
   }
@@ -3268,12 +3255,12 @@ static int group_run_same_device(bwgr_group *Gp, int iters) {
   for (int k = 0; k < iters; ++k) {
     for (int r = 0; r < Gp->rounds; ++r) {
       for (int g = 0; g < Gp->G; ++g) {
-        const int nb = (int)Gp->P[g]->nblocks;
+        const int nb = (int)Gp->P[g]->data->nblocks;
         const int lo = std::min(nb, r * Gp->bps), hi = std::min(nb, (r + 1) * Gp->bps);
         CHK(bwgr_chain_round_sweep(Gp->C[g], lo, hi, Gp->delta[g]));
       }
       double *tot = nullptr;
-      CHK(group_local_sum(Gp, Gp->delta, (size_t)Gp->P[0]->ld, Gp->total, &tot));
+      CHK(group_local_sum(Gp, Gp->delta, (size_t)Gp->P[0]->data->ld, Gp->total, &tot));
       for (int g = 0; g < Gp->G; ++g) CHK(bwgr_chain_round_apply(Gp->C[g], tot));
     }
     for (int g = 0; g < Gp->G; ++g) CHK(bwgr_chain_get_sums_dev(Gp->C[g], Gp->sums[g]));
@@ -3292,11 +3279,11 @@ extern "C" int bwgr_group_run(bwgr_group *Gp, int iters) {
   for (int k = 0; k < iters; ++k) {
     for (int r = 0; r < Gp->rounds; ++r) {
       for (int g = 0; g < Gp->G; ++g) {
-        const int nb = (int)Gp->P[g]->nblocks;
+        const int nb = (int)Gp->P[g]->data->nblocks;
         const int lo = std::min(nb, r * Gp->bps), hi = std::min(nb, (r + 1) * Gp->bps);   // (lo == hi: a device that has run out of blocks still takes part)
         CHK(bwgr_chain_round_sweep(Gp->C[g], lo, hi, Gp->delta[g]));
       }
-      CHK(group_allreduce(Gp, Gp->delta, (size_t)Gp->P[0]->ld));
+      CHK(group_allreduce(Gp, Gp->delta, (size_t)Gp->P[0]->data->ld));
       for (int g = 0; g < Gp->G; ++g) CHK(bwgr_chain_round_apply(Gp->C[g], Gp->delta[g]));
     }
     for (int g = 0; g < Gp->G; ++g) CHK(bwgr_chain_get_sums_dev(Gp->C[g], Gp->sums[g]));
@@ -3544,34 +3531,33 @@ extern "C" int bwgr_em_order(int64_t p, int upto, int32_t *order) {
 
 extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float R2, float par, const float *D, int maxit_in,
                        float *mu, float *b, float *d, float *hat, float *vbvec, float *scal, int *iters) {
-  if (P && panel_cen(P)) return fail(BWGR_EINVAL, "em: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
+  if (P && P->data->cen) return fail(BWGR_EINVAL, "em: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
   if (!P || !y || !b || !scal) return fail(BWGR_EINVAL, "em: null pointer");
   if (model < BWGR_EM_RR || model > BWGR_EM_LASSO) return fail(BWGR_EINVAL, "em: bad model %d", model);
   if (D && model != BWGR_EM_ML) return fail(BWGR_EINVAL, "em: marker weights D belong to emML only");
   const bool soft = (model == BWGR_EM_BB || model == BWGR_EM_BC || model == BWGR_EM_BCPI);
   const bool lasso = (model == BWGR_EM_LASSO);
   const bool nonaffine = soft || lasso || model == BWGR_EM_BL || model == BWGR_EM_EN;
-  if (nonaffine && P->sweep_version < 2) return fail(BWGR_EINVAL, "em: this member needs the pipelined sweep engine (k_sweep2), which this panel's geometry does not fit");
-  HIPCHK(hipSetDevice(P->device));
-  const int64_t p = P->p, n = P->n;
+  if (nonaffine && P->data->sweep_version < 2) return fail(BWGR_EINVAL, "em: this member needs the pipelined sweep engine (k_sweep2), which this panel's geometry does not fit");
+  HIPCHK(hipSetDevice(P->data->device));
+  const int64_t p = P->data->p, n = P->data->n;
   const bool conv = (model == BWGR_EM_DE || model == BWGR_EM_ML || model == BWGR_EM_EN || lasso);
   const bool shuffled = (model != BWGR_EM_BCPI && !lasso);                            // emBCpi and lasso sweep in natural order, :1523, :1476
   const int maxit = maxit_in > 0 ? maxit_in : (conv ? 300 : 200);                     // :81, :251, :309, :401, :465
   const float tol = (model == BWGR_EM_DE) ? 10e-6f : (model == BWGR_EM_EN) ? 10e-11f : 10e-8f;   // :252, :402, :466
   hipStream_t st = P->stream;
-  // scratch panel: same geometry, its own X and Gram; only the diagonal and distance-1 blocks are ever built (lag 2)
+  // scratch panel: same geometry, its own X and Gram; only the diagonal and distance-1 blocks are ever built (lag 2, 32-bit staging)
   bwgr_panel *Q = nullptr;
   if (shuffled) {
-    CHK(panel_alloc(&Q, P->is_f32, n, p, P->device, P->m, P->K, P->sw));
-    Q->stream = st; Q->gram_maxdist = 1;
-    hipFree(Q->gramx2); hipFree(Q->gramx3); hipFree(Q->xspec2); hipFree(Q->xspec3); hipFree(Q->gramp16); hipFree(Q->gramx16);
-    Q->gramx2 = Q->gramx3 = nullptr; Q->xspec2 = Q->xspec3 = nullptr; Q->gramp16 = Q->gramx16 = nullptr;
+    CHK(panel_alloc(&Q, P->data->is_f32, n, p, P->data->device, P->data->m, P->data->K, P->data->sw, true));
+    Q->stream = st;
   }
   std::vector<void *> owned;
   int rc = BWGR_OK;
   auto done = [&](int code) { (void)hipStreamSynchronize(st); for (void *q : owned) hipFree(q); if (Q) bwgr_panel_destroy(Q); return code; };
 #define ECHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return done(fail(BWGR_EHIP, "%s failed: %s", #x, hipGetErrorString(e_))); } while (0)
-  if (Q && (Q->K != P->K || Q->R != P->R || Q->m != P->m || std::min(Q->sweep_version, 2) != std::min(P->sweep_version, 2))) return done(fail(BWGR_EINVAL, "em: scratch panel geometry differs"));
+  if (Q && (Q->data->K != P->data->K || Q->data->R != P->data->R || Q->data->m != P->data->m || std::min(Q->data->sweep_version, 2) != std::min(P->data->sweep_version, 2))) return done(fail(BWGR_EINVAL, "em: scratch panel geometry differs"));
+  if (Q && (rc = scratch_alloc(Q)) != BWGR_OK) return done(rc);
   bwgr_panel *S = Q ? Q : P;                                                          // the panel the sweeps run on
   const size_t pb = sizeof(float) * (size_t)p;
   float *yd = nullptr, *bd = nullptr, *bcd = nullptr, *dd = nullptr, *lamd = nullptr, *vbd = nullptr, *xxd = nullptr, *Dd = nullptr;
@@ -3581,26 +3567,26 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
   ECHK(dmalloc((void **)&yd, sizeof(float) * n)); ECHK(dmalloc((void **)&bd, pb)); ECHK(dmalloc((void **)&bcd, pb)); ECHK(dmalloc((void **)&dd, pb));
   ECHK(dmalloc((void **)&lamd, pb)); ECHK(dmalloc((void **)&vbd, pb)); ECHK(dmalloc((void **)&xxd, pb));
   ECHK(dmalloc((void **)&bq, pb)); ECHK(dmalloc((void **)&xxq, pb)); ECHK(dmalloc((void **)&lamq, pb)); ECHK(dmalloc((void **)&dq, pb)); ECHK(dmalloc((void **)&vq, pb));
-  ECHK(dmalloc((void **)&ed, sizeof(double) * P->ld)); ECHK(dmalloc((void **)&ordd, sizeof(int32_t) * p));
+  ECHK(dmalloc((void **)&ed, sizeof(double) * P->data->ld)); ECHK(dmalloc((void **)&ordd, sizeof(int32_t) * p));
   ECHK(dmalloc((void **)&std_, sizeof(EmState))); ECHK(dmalloc((void **)&sc, sizeof(ChainScalars)));
   ECHK(dmalloc((void **)&hatd, sizeof(float) * n));
   if (D) { ECHK(dmalloc((void **)&Dd, pb)); ECHK(hipMemcpyAsync(Dd, D, pb, hipMemcpyHostToDevice, st)); }
   ECHK(hipMemcpyAsync(yd, y, sizeof(float) * n, hipMemcpyHostToDevice, st));
   ECHK(hipMemsetAsync(bd, 0, pb, st)); ECHK(hipMemsetAsync(dd, 0, pb, st));
-  ECHK(hipMemcpyAsync(xxd, P->xx, pb, hipMemcpyDeviceToDevice, st));
+  ECHK(hipMemcpyAsync(xxd, P->data->xx, pb, hipMemcpyDeviceToDevice, st));
   // vy = fvar(y) with the library's reduction (float result of fp64 sums, like the fused samplers' setup)
   float vy = 0;
   {
     InitArgs ia; memset(&ia, 0, sizeof(ia));
     ChainScalars h0; memset(&h0, 0, sizeof(h0));
     ECHK(hipMemcpyAsync(sc, &h0, sizeof(h0), hipMemcpyHostToDevice, st));
-    ia.y = yd; ia.e = ed; ia.n = (int)n; ia.p = (int)p; ia.ld = P->ld; ia.model = BWGR_BAYESRR; ia.pi = 0; ia.df = df; ia.R2 = R2; ia.MSx = P->MSx; ia.sc = sc;
+    ia.y = yd; ia.e = ed; ia.n = (int)n; ia.p = (int)p; ia.ld = P->data->ld; ia.model = BWGR_BAYESRR; ia.pi = 0; ia.df = df; ia.R2 = R2; ia.MSx = P->data->MSx; ia.sc = sc;
     hipLaunchKernelGGL(k_chain_init, dim3(1), dim3(1024), 0, st, ia);
     ECHK(hipGetLastError());
     ECHK(d2h(st, &h0, sc, sizeof(h0)));
     vy = h0.vy;
   }
-  const float sumvx = P->MSx;                                                        // vx.sum()
+  const float sumvx = P->data->MSx;                                                        // vx.sum()
   EmState h; memset(&h, 0, sizeof(h));
   h.df = df; h.vy = vy; h.MSx = sumvx; h.sumvx = sumvx; h.R2 = R2; h.ve = 1.0f;
   std::vector<float> hostv, xxh, yxh, bh;
@@ -3660,7 +3646,7 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
     }
   }
   ECHK(hipMemcpyAsync(std_, &h, sizeof(h), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_em_init, dim3(1), dim3(1024), 0, st, yd, ed, (int)n, P->ld, std_);   // mu, e (overwrites k_chain_init's e)
+  hipLaunchKernelGGL(k_em_init, dim3(1), dim3(1024), 0, st, yd, ed, (int)n, P->data->ld, std_);   // mu, e (overwrites k_chain_init's e)
   ECHK(hipGetLastError());
   {
     ChainScalars h0; memset(&h0, 0, sizeof(h0));
@@ -3673,7 +3659,7 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
   for (int64_t j = 0; j < p; ++j) order[(size_t)j] = (int)j;
   if (shuffled) std::shuffle(order.begin(), order.end(), std::mt19937(0));            // sweep 0's order
   if (!shuffled) ECHK(hipMemcpyAsync(ordd, order.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice, st));
-  const int cps = (int)((size_t)P->R * (P->is_f32 ? 4 : 1) / 16);
+  const int cps = (int)((size_t)P->data->R * (P->data->is_f32 ? 4 : 1) / 16);
   uint32_t flags = SWF_LAM_VEC;
   if (model == BWGR_EM_BA) flags |= SWF_DELTA2;
   if (soft) flags |= SWF_EM_SEL;
@@ -3681,7 +3667,7 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
   if (model == BWGR_EM_BL) flags |= SWF_EM_BL;
   if (lasso) flags |= SWF_EM_LASSO;
   int numit = 0;
-  const bool emdbg = P->sw.em_debug;
+  const bool emdbg = P->data->sw.em_debug;
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   for (int i = 0; i < maxit; ++i) {
     const double t_0 = now();
@@ -3690,7 +3676,7 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
       // the reference's own call -- was made for sweep 0 before the loop and is made for sweep i+1 below, while the GPU
       // runs sweep i (10-15 ms of host time per sweep at p = 10^6)
       ECHK(hipMemcpyAsync(ordd, order.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)P->X, (uint4 *)Q->X, ordd, p, P->K, cps);
+      hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)P->data->X, (uint4 *)Q->data->X, ordd, p, P->data->K, cps);
     }
     if (conv) ECHK(hipMemcpyAsync(bcd, bd, pb, hipMemcpyDeviceToDevice, st));        // bc = b
     hipLaunchKernelGGL(k_em_stage, dim3(1024), dim3(256), 0, st, ordd, p, model, D ? 1 : 0, bd, xxd, lamd, Dd, std_, bq, xxq, lamq);
@@ -3824,7 +3810,7 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   if (!P || !Y || !b_out || !its) return fail(BWGR_EINVAL, "mrr: null pointer");
   if (k < 1 || k > BWGR_MRR_MAXK) return fail(BWGR_EINVAL, "mrr: k = %d traits; this engine takes 1 <= k <= %d", k, BWGR_MRR_MAXK);
   if (nopts < 0 || nopts > BWGR_MRR_NOPTS || (nopts > 0 && !opts)) return fail(BWGR_EINVAL, "mrr: nopts = %d (at most %d)", nopts, BWGR_MRR_NOPTS);
-  if (P->is_f32) return fail(BWGR_EINVAL, "mrr: the panel holds fp32 genotypes; mrr takes int8 panels only");
+  if (P->data->is_f32) return fail(BWGR_EINVAL, "mrr: the panel holds fp32 genotypes; mrr takes int8 panels only");
   double O[BWGR_MRR_NOPTS] = BWGR_MRR_DEFAULTS;
   const double D0[BWGR_MRR_NOPTS] = BWGR_MRR_DEFAULTS;
   for (int i = 0; i < nopts; ++i) O[i] = opts[i];
@@ -3845,12 +3831,11 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   if (o.maxit < 0) return fail(BWGR_EINVAL, "mrr: maxit = %d", o.maxit);
   if ((o.XFA || o.ACS) && (o.NumXFA < 1 || o.NumXFA > k))
     return fail(BWGR_EINVAL, "mrr: NumXFA = %d with XFA / ACS needs 1 <= NumXFA <= k = %d (the reference indexes eigenvalue k - NumXFA)", o.NumXFA, k);
-  HIPCHK(hipSetDevice(P->device));
-  bwgr_panel *root = P->parent ? P->parent : P;
-  const int64_t n = P->n, p = P->p, ld = P->ld;
-  const int R = P->R;
+  HIPCHK(hipSetDevice(P->data->device));
+  const int64_t n = P->data->n, p = P->data->p, ld = P->data->ld;
+  const int R = P->data->R;
   {
-    const int64_t xm = std::max(root->xmax, 1);
+    const int64_t xm = std::max(P->data->xmax, 1);
     if ((int64_t)n * xm * xm >= (1ll << 31)) return fail(BWGR_EINVAL, "mrr: n * max|x|^2 = %lld does not fit the int32 Gram", (long long)(n * xm * xm));
   }
   // ---- host set-up (:742-816) ----
@@ -3904,7 +3889,7 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   int8_t *Xs = nullptr; uint32_t *zbd = nullptr, *ztd = nullptr; uint8_t *zmd = nullptr; int32_t *ordd = nullptr, *gram = nullptr;
   double *yd = nullptr, *ed = nullptr, *xbar = nullptr, *Sd = nullptr, *XXd = nullptr, *XSXd = nullptr, *tilde = nullptr, *bd = nullptr, *Linv = nullptr;
   double *part = nullptr, *dB = nullptr, *db2 = nullptr, *small = nullptr, *tpart = nullptr, *sumyd = nullptr, *hpart = nullptr, *hatd = nullptr;
-  MCHK(dmalloc((void **)&Xs, P->x_bytes));
+  MCHK(dmalloc((void **)&Xs, P->data->x_bytes));
   MCHK(dmalloc((void **)&zbd, sizeof(uint32_t) * ld)); MCHK(dmalloc((void **)&ztd, sizeof(uint32_t) * ld));
   MCHK(dmalloc((void **)&zmd, (size_t)npat * ld));
   MCHK(dmalloc((void **)&ordd, sizeof(int32_t) * p));
@@ -3929,7 +3914,7 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   MCHK(hipMemsetAsync(bd, 0, sizeof(double) * p * k, st));                                         // b = 0, :823
   MCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_linv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
   MCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
-  hipLaunchKernelGGL(k_mrr_setup_cols, dim3((unsigned)std::min<int64_t>((p + 3) / 4, 8192)), dim3(256), 0, st, (const int8_t *)P->X, R, (int)n, p, ld,
+  hipLaunchKernelGGL(k_mrr_setup_cols, dim3((unsigned)std::min<int64_t>((p + 3) / 4, 8192)), dim3(256), 0, st, (const int8_t *)P->data->X, R, (int)n, p, ld,
                      (const uint32_t *)zbd, (const double *)yd, (const double *)sumyd, mc, xbar, Sd, XXd, XSXd, tilde);
   MCHK(hipGetLastError());
   // a reduction over p of the k^2 (+k) products, partials in a fixed order
@@ -3969,7 +3954,7 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
     vb0 = vb; h20 = h2;
     std::shuffle(order.begin(), order.end(), std::mt19937(numit));                                 // :869 (cumulative, as there)
     MCHK(hipMemcpyAsync(ordd, order.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)P->X, (uint4 *)Xs, (const int32_t *)ordd, p, P->K, cps);
+    hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)P->data->X, (uint4 *)Xs, (const int32_t *)ordd, p, P->data->K, cps);
     hipLaunchKernelGGL(k_mrr_gram, dim3((unsigned)nblk, (unsigned)((npat + 3) / 4)), dim3(256), 0, st, (const int8_t *)Xs, R, p, ld, (const uint8_t *)zmd, npat, gram);
     for (int t = 0; t < k; ++t) mc.iVe[t] = 1.0 / ve[t];
     MCHK(hipMemcpyAsync(small + 512, iG.data(), sizeof(double) * k * k, hipMemcpyHostToDevice, st));
@@ -4045,7 +4030,7 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   if (hat_out) {
     MCHK(dmalloc((void **)&hpart, sizeof(double) * nch * k * ld)); MCHK(dmalloc((void **)&hatd, sizeof(double) * n * k));
     MCHK(hipMemcpyAsync(small, off.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_mrr_hat_part, dim3((unsigned)((ld + 255) / 256), nch), dim3(256), 0, st, (const int8_t *)P->X, R, p, ld, (int)n, k, (const double *)bd, cpc, hpart);
+    hipLaunchKernelGGL(k_mrr_hat_part, dim3((unsigned)((ld + 255) / 256), nch), dim3(256), 0, st, (const int8_t *)P->data->X, R, p, ld, (int)n, k, (const double *)bd, cpc, hpart);
     hipLaunchKernelGGL(k_mrr_hat_finish, dim3((unsigned)std::min<int64_t>((n * k + 255) / 256, 4096)), dim3(256), 0, st, (const double *)hpart, nch, ld, (int)n, k,
                        (const double *)small, hatd);
     MCHK(hipGetLastError());

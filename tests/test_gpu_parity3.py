@@ -278,6 +278,30 @@ def test_centred_panel_refuses_what_it_cannot_sweep(tpod):
     P.close()
 
 
+def test_a_centred_chain_on_a_clone_is_the_chain_on_its_panel(tpod):
+    """A clone made before bwgr_panel_set_centred follows its panel: it is centred, has the panel's statistics, and a centred BayesB chain on it
+    is the chain on the panel, bit for bit (what test_fit_many_runs_the_same_chains_side_by_side asks of uncentred chains)."""
+    import bwgr_amd
+    X, y = tpod["gen"], tpod["y"]
+    P = bwgr_amd.Panel(X)
+    Q = P.clone()
+    P.set_centred(True)
+    assert Q.centred()
+    (qxx, qvx, qmsx), (pxx, pvx, pmsx) = Q.stats(), P.stats()
+    assert np.array_equal(qxx, pxx) and np.array_equal(qvx, pvx) and qmsx == pmsx
+    got = []
+    for H in (Q, P):
+        ch = bwgr_amd.Chain(H, "BayesB", y, it=10, bi=2, pi=0.9, seed=41)
+        ch.run(10)
+        got.append((ch.result(), ch.state()))
+        ch.close()
+    Q.close(); P.close()
+    for on_q, on_p in zip(*got):
+        assert list(on_q) == list(on_p)
+        for k in on_p:
+            np.testing.assert_array_equal(np.asarray(on_q[k]), np.asarray(on_p[k]), err_msg=k)
+
+
 def test_partitioned_sampler_on_centred_columns():
     """VERDICT r2 item 2.  The marker-sharded sampler is a different chain from the reference for more than one shard, so its
     parity is statistical.  On the uncentred genotypes bWGR sweeps it is unsound (test_gpu_parity2.py::
