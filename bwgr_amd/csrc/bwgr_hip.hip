@@ -1085,6 +1085,55 @@ static Rng make_rng(uint64_t seed, int mode) {
   Rng g; g.k0 = (uint32_t)seed; g.k1 = (uint32_t)(seed >> 32); g.degenerate = (mode == BWGR_RNG_DEGENERATE); return g;
 }
 
+// The temporary device buffers of one call (or of one block of it), freed when the scope ends, on every path out of it.  Given a stream, it
+// waits for that stream first, so that no kernel or asynchronous copy still uses a buffer or a host local of the frame that goes away (a
+// host vector that is copied from asynchronously is declared before the holder, and so outlives that wait).
+// get() returns nullptr where the allocation fails: the caller reports BWGR_ENOMEM, "<entry>: device allocation failed".
+namespace {
+struct DevBufs {
+  std::vector<void *> v;
+  hipStream_t stream = nullptr;
+  bool sync = false;
+  DevBufs() = default;
+  explicit DevBufs(hipStream_t st) : stream(st), sync(true) {}
+  DevBufs(const DevBufs &) = delete;
+  ~DevBufs() {
+    if (sync) (void)hipStreamSynchronize(stream);
+    for (void *q : v) hipFree(q);
+  }
+  template <typename T> T *get(size_t count) {
+    void *q = nullptr;
+    if (hipMalloc(&q, sizeof(T) * (count ? count : 1)) != hipSuccess) return nullptr;
+    v.push_back(q);
+    return reinterpret_cast<T *>(q);
+  }
+};
+// Runs f when the scope ends, unless release()d: destroys the object a function is making on its error returns, a call's scratch panels and
+// chains on every return, and gives a borrowed stream back.  Declared before the call's DevBufs, so that it runs after the buffers are freed.
+template <typename F> struct Guard {
+  F f;
+  bool armed = true;
+  explicit Guard(F f_) : f(f_) {}
+  Guard(const Guard &) = delete;
+  ~Guard() { if (armed) f(); }
+  void release() { armed = false; }
+};
+}  // namespace
+
+// sum of n floats (fp64 partial sums in a fixed order, rounded to float once) into *sum_dev and from there into *sum; part: 256 doubles
+static int sum_floats(hipStream_t st, const float *v, int64_t n, double *part, float *sum_dev, float *sum) {
+  hipLaunchKernelGGL(k_sum_stage1, dim3(256), dim3(256), 0, st, v, n, part);
+  hipLaunchKernelGGL(k_sum_stage2, dim3(1), dim3(256), 0, st, part, 256, sum_dev);
+  HIPCHK(hipGetLastError());
+  HIPCHK(d2h(st, sum, sum_dev, sizeof(float)));
+  return BWGR_OK;
+}
+
+// the refusal of every entry point that sweeps the columns as stored
+static int refuse_centred(const char *who) {
+  return fail(BWGR_EINVAL, "%s: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first", who);
+}
+
 static int require_device(int device) {
   int c = 0; bwgr_device_count(&c);
   if (c <= 0) return fail(BWGR_ENODEV, "no HIP device visible: libbwgr_hip has no CPU fallback");
@@ -1266,32 +1315,34 @@ static int sweep3_build(bwgr_panel *P) {
   const size_t blk_elems = (size_t)P->data->nblocks * m * m;
   const bool g16 = P->data->gram16;
   const int Dbuild = D;
-  int32_t *tmp = nullptr;
-  for (int d = 1; d < Dbuild; ++d) {
-    if (P->data->nblocks <= d) { P->data->g3x[d - 1] = nullptr; continue; }
-    if (d == 1) { P->data->g3x[0] = g16 ? (void *)P->data->gramx16 : P->data->gramx; continue; }
-    if (!g16 && d == 2 && P->data->gramx2) { P->data->g3x[1] = P->data->gramx2; continue; }
-    if (!g16 && d == 3 && P->data->gramx3) { P->data->g3x[2] = P->data->gramx3; continue; }
-    void *arr = nullptr;
-    HIPCHK(hipMalloc(&arr, blk_elems * (g16 ? 2 : 4)));
-    P->data->g3x[d - 1] = arr; P->data->g3own[d - 1] = true;
-    if (g16) {
-      const int32_t *src;
-      if (d == 2 && P->data->gramx2) src = (const int32_t *)P->data->gramx2;
-      else if (d == 3 && P->data->gramx3) src = (const int32_t *)P->data->gramx3;
-      else {
-        if (!tmp) HIPCHK(hipMalloc(&tmp, blk_elems * 4));
-        launch_gramx_i8(P, tmp, d);
-        src = tmp;
-      }
-      hipLaunchKernelGGL(k_gram_narrow, dim3(2048), dim3(256), 0, P->stream, src + (size_t)d * m * m, (uint16_t *)arr + (size_t)d * m * m, (int64_t)(P->data->nblocks - d) * m * m, P->data->gram16_bad);
-    } else launch_gramx_i8(P, (int32_t *)arr, d);
-    HIPCHK(hipGetLastError());
-  }
   int bad = 0;
-  if (g16) HIPCHK(hipMemcpyAsync(&bad, P->data->gram16_bad, sizeof(int), hipMemcpyDeviceToHost, P->stream));
-  HIPCHK(hipStreamSynchronize(P->stream));
-  if (tmp) hipFree(tmp);
+  {   // the far blocks; tmp, a whole Gram array, goes once they are built and before the 16-bit verdict is acted on
+    DevBufs bufs;
+    int32_t *tmp = nullptr;
+    for (int d = 1; d < Dbuild; ++d) {
+      if (P->data->nblocks <= d) { P->data->g3x[d - 1] = nullptr; continue; }
+      if (d == 1) { P->data->g3x[0] = g16 ? (void *)P->data->gramx16 : P->data->gramx; continue; }
+      if (!g16 && d == 2 && P->data->gramx2) { P->data->g3x[1] = P->data->gramx2; continue; }
+      if (!g16 && d == 3 && P->data->gramx3) { P->data->g3x[2] = P->data->gramx3; continue; }
+      HIPCHK(hipMalloc(&P->data->g3x[d - 1], blk_elems * (g16 ? 2 : 4)));
+      P->data->g3own[d - 1] = true;
+      void *arr = P->data->g3x[d - 1];
+      if (g16) {
+        const int32_t *src;
+        if (d == 2 && P->data->gramx2) src = (const int32_t *)P->data->gramx2;
+        else if (d == 3 && P->data->gramx3) src = (const int32_t *)P->data->gramx3;
+        else {
+          if (!tmp && !(tmp = bufs.get<int32_t>(blk_elems))) return fail(BWGR_ENOMEM, "panel_create: device allocation failed");
+          launch_gramx_i8(P, tmp, d);
+          src = tmp;
+        }
+        hipLaunchKernelGGL(k_gram_narrow, dim3(2048), dim3(256), 0, P->stream, src + (size_t)d * m * m, (uint16_t *)arr + (size_t)d * m * m, (int64_t)(P->data->nblocks - d) * m * m, P->data->gram16_bad);
+      } else launch_gramx_i8(P, (int32_t *)arr, d);
+      HIPCHK(hipGetLastError());
+    }
+    if (g16) HIPCHK(hipMemcpyAsync(&bad, P->data->gram16_bad, sizeof(int), hipMemcpyDeviceToHost, P->stream));
+    HIPCHK(hipStreamSynchronize(P->stream));
+  }
   if (bad) {   // an entry of a far block left the 16-bit range although the near blocks fit: rare; leave the panel to k_sweep2
     for (int d = 1; d < S3_MAXD; ++d) if (P->data->g3own[d - 1]) { hipFree(P->data->g3x[d - 1]); P->data->g3x[d - 1] = nullptr; P->data->g3own[d - 1] = false; }
     P->data->sweep_version = 2;
@@ -1659,19 +1710,17 @@ static int upload(bwgr_panel *P, const void *X, int memloc, int64_t ldx) {
   const int64_t col_bytes = ldx * (int64_t)sizeof(ST);
   int64_t cols = std::max<int64_t>(1, ((int64_t)256 << 20) / std::max<int64_t>(1, col_bytes));
   cols = std::min(cols, p);
-  ST *stage = nullptr;
-  HIPCHK(hipMalloc(&stage, (size_t)(cols * col_bytes)));
+  DevBufs bufs;
+  ST *stage = bufs.get<ST>((size_t)(cols * ldx));
+  if (!stage) return fail(BWGR_ENOMEM, "panel_create: device allocation failed");
   for (int64_t j0 = 0; j0 < p; j0 += cols) {
     const int64_t nc = std::min(cols, p - j0);
     // the last column may be shorter than ldx in the caller's allocation: copy n rows of it separately
     const size_t bytes = (size_t)((nc - 1) * col_bytes + n * (int64_t)sizeof(ST));
-    hipError_t e = hipMemcpyAsync(stage, reinterpret_cast<const ST *>(X) + j0 * ldx, bytes, hipMemcpyHostToDevice, P->stream);
-    if (e != hipSuccess) { hipFree(stage); return fail(BWGR_EHIP, "upload memcpy failed: %s", hipGetErrorString(e)); }
+    HIPCHK(hipMemcpyAsync(stage, reinterpret_cast<const ST *>(X) + j0 * ldx, bytes, hipMemcpyHostToDevice, P->stream));
     hipLaunchKernelGGL((k_convert<ST, XT>), dim3(2048), dim3(256), 0, P->stream, stage, ldx, dst, P->data->ld, (int)n, j0, nc, P->data->R, p);
-    e = hipStreamSynchronize(P->stream);
-    if (e != hipSuccess) { hipFree(stage); return fail(BWGR_EHIP, "upload convert failed: %s", hipGetErrorString(e)); }
+    HIPCHK(hipStreamSynchronize(P->stream));
   }
-  HIPCHK(hipFree(stage));
   return BWGR_OK;
 }
 
@@ -1741,15 +1790,10 @@ static int panel_setup(bwgr_panel *P) {
   else hipLaunchKernelGGL(k_stats<int8_t>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const int8_t *)P->data->X, P->data->R, n, p, P->data->xx, P->data->vx);
   HIPCHK(hipGetLastError());
   {
-    const int nparts = 256;
-    double *part = nullptr;
-    HIPCHK(hipMalloc(&part, sizeof(double) * nparts));
-    hipLaunchKernelGGL(k_sum_stage1, dim3(nparts), dim3(256), 0, P->stream, P->data->vx, (int64_t)p, part);
-    hipLaunchKernelGGL(k_sum_stage2, dim3(1), dim3(256), 0, P->stream, part, nparts, P->data->msx_dev);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&P->data->MSx, P->data->msx_dev, sizeof(float), hipMemcpyDeviceToHost, P->stream));
-    HIPCHK(hipStreamSynchronize(P->stream));
-    HIPCHK(hipFree(part));
+    DevBufs bufs;
+    double *part = bufs.get<double>(256);
+    if (!part) return fail(BWGR_ENOMEM, "panel_create: device allocation failed");
+    CHK(sum_floats(P->stream, P->data->vx, (int64_t)p, part, P->data->msx_dev, &P->data->MSx));
   }
   if (!P->data->is_f32) {
     if (!P->data->xmax_dev) HIPCHK(hipMalloc(&P->data->xmax_dev, sizeof(int)));
@@ -1853,12 +1897,13 @@ static int panel_build_gram(bwgr_panel *P) {
   if (!P->data->is_f32 && P->data->gram16 && P->data->sw.winv && m <= SW_MAXM) {
     HIPCHK(hipMemsetAsync(P->data->gram16_bad, 0, sizeof(int), P->stream));
     int nd = 0;
+    DevBufs bufs;
     int32_t *tmpx = nullptr;   // distances 4 and 5 (pipelines five and six blocks deep; main panels only): built here, kept as planes only
     for (int dist = 1; dist <= S2W_MAXDIST; ++dist) {
       const int32_t *src = (const int32_t *)(dist == 1 ? P->data->gramx : dist == 2 ? P->data->gramx2 : dist == 3 ? P->data->gramx3 : nullptr);
       if (dist > S2W_NEARD) {
         if (!P->data->want3 || P->data->gram_maxdist < S2W_NEARD || P->data->nblocks <= dist || dist > P->data->sw.wlag_cap - 1) break;
-        if (!tmpx && hipMalloc(&tmpx, (size_t)P->data->nblocks * m * m * 4) != hipSuccess) { (void)hipGetLastError(); tmpx = nullptr; break; }
+        if (!tmpx && !(tmpx = bufs.get<int32_t>((size_t)P->data->nblocks * m * m))) { (void)hipGetLastError(); break; }
         launch_gramx_i8(P, tmpx, dist);
         src = tmpx;
       }
@@ -1871,7 +1916,6 @@ static int panel_build_gram(bwgr_panel *P) {
     int bad = 1;
     HIPCHK(hipMemcpyAsync(&bad, P->data->gram16_bad, sizeof(int), hipMemcpyDeviceToHost, P->stream));
     HIPCHK(hipStreamSynchronize(P->stream));
-    if (tmpx) hipFree(tmpx);
     P->data->winv_nd = bad ? 0 : nd;
   }
   HIPCHK(hipStreamSynchronize(P->stream));
@@ -1888,10 +1932,11 @@ static int panel_alloc(bwgr_panel **out, int is_f32, int64_t n, int64_t p, int d
   CHK(require_device(device));
   bwgr_panel *P = new bwgr_panel();
   P->data = new PanelData(); P->is_root = true;
+  Guard drop([&] { bwgr_panel_destroy(P); });   // until the panel is handed over
   P->data->device = device; P->data->n = n; P->data->p = p; P->data->is_f32 = is_f32; P->data->sw = sw; P->data->gram_maxdist = near_only ? 1 : 3;
   const int mmax = P->data->is_f32 ? 64 : SW_MAXM;
   int m = block > 0 ? block : mmax;
-  if (m > mmax) { delete P->data; delete P; return fail(BWGR_EINVAL, "panel_create: block %d > %d (limit for this genotype type)", m, mmax); }
+  if (m > mmax) return fail(BWGR_EINVAL, "panel_create: block %d > %d (limit for this genotype type)", m, mmax);
   m = (int)std::min<int64_t>(m, ((p + 15) / 16) * 16);
   m = ((m + 15) / 16) * 16;
   P->data->m = m;
@@ -1908,13 +1953,11 @@ static int panel_alloc(bwgr_panel **out, int is_f32, int64_t n, int64_t p, int d
   }
   int K = nwg > 0 ? nwg : (int)((n + Rpick - 1) / Rpick);
   int R = (int)((((n + K - 1) / K) + 127) / 128) * 128;
-  if (K > 256 || R > Rmax) {
-    delete P->data; delete P;
+  if (K > 256 || R > Rmax)
     return fail(BWGR_EINVAL, "panel_create: n=%lld needs %d slab workgroups of %d rows (limits: 256 workgroups, %d rows)", (long long)n, K, R, Rmax);
-  }
   P->data->K = K; P->data->R = R; P->data->ld = (int64_t)K * R;
   P->data->nblocks = (p + m - 1) / m;
-  if (P->data->nblocks >= (1ll << 24)) { delete P->data; delete P; return fail(BWGR_EINVAL, "panel_create: %lld marker blocks; the delta granules carry a 24-bit block epoch", (long long)P->data->nblocks); }
+  if (P->data->nblocks >= (1ll << 24)) return fail(BWGR_EINVAL, "panel_create: %lld marker blocks; the delta granules carry a 24-bit block epoch", (long long)P->data->nblocks);
   P->data->lds_bytes = P->data->is_f32 ? sweep_lds_bytes<float>(m, R) : sweep_lds_bytes<int8_t>(m, R);
   P->data->lds2_bytes = P->data->is_f32 ? sweep2_lds_bytes<float>(m, R) : sweep2_lds_bytes<int8_t>(m, R);
   if (!P->data->is_f32 && s2i_lds_bytes(m, R, 4) <= (size_t)160 * 1024) {
@@ -1930,38 +1973,34 @@ static int panel_alloc(bwgr_panel **out, int is_f32, int64_t n, int64_t p, int d
   }
   P->data->x_bytes = (size_t)P->data->ld * (size_t)p * (P->data->is_f32 ? 4 : 1);
   P->data->gram_bytes = (size_t)P->data->nblocks * m * m * (P->data->is_f32 ? 8 : 4);   // per Gram array (diagonal blocks; off-diagonal blocks)
-  int rc = BWGR_OK;
-  auto bail = [&](int code) { bwgr_panel_destroy(P); return code; };
-#define PCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return bail(fail(BWGR_EHIP, "%s failed: %s", #x, hipGetErrorString(e_))); } while (0)
-  PCHK(hipMalloc(&P->data->X, P->data->x_bytes));
-  PCHK(hipMalloc(&P->data->gram, P->data->gram_bytes));
-  PCHK(hipMalloc(&P->data->gramx, P->data->gram_bytes));
+  HIPCHK(hipMalloc(&P->data->X, P->data->x_bytes));
+  HIPCHK(hipMalloc(&P->data->gram, P->data->gram_bytes));
+  HIPCHK(hipMalloc(&P->data->gramx, P->data->gram_bytes));
   if (P->data->sweep_version >= 2 && P->data->nblocks > 2 && !near_only)   // distance-2 blocks: the selection models' lag-3 pipeline
-    PCHK(hipMalloc(&P->data->gramx2, P->data->gram_bytes));
+    HIPCHK(hipMalloc(&P->data->gramx2, P->data->gram_bytes));
   if (P->data->sweep_version >= 2 && !P->data->is_f32 && P->data->nblocks > 3 && P->data->lag4_ok && sw.lag != '2' && sw.lag != '3' && !near_only)   // distance-3 blocks: the lag-4 pipeline
-    PCHK(hipMalloc(&P->data->gramx3, P->data->gram_bytes));
+    HIPCHK(hipMalloc(&P->data->gramx3, P->data->gram_bytes));
   P->data->pstride = ((m * (m - 1) / 2 + 7) / 8) * 8;
-  PCHK(hipMalloc(&P->data->gramp, (size_t)P->data->nblocks * std::max(P->data->pstride, 8) * (P->data->is_f32 ? 8 : 4)));
+  HIPCHK(hipMalloc(&P->data->gramp, (size_t)P->data->nblocks * std::max(P->data->pstride, 8) * (P->data->is_f32 ? 8 : 4)));
   if (!P->data->is_f32 && P->data->sweep_version >= 2 && !near_only) {
-    PCHK(hipMalloc(&P->data->gramp16, (size_t)P->data->nblocks * std::max(P->data->pstride, 8) * 2));
-    PCHK(hipMalloc(&P->data->gramx16, (size_t)P->data->nblocks * m * m * 2));
-    PCHK(hipMalloc(&P->data->gram16_bad, sizeof(int)));
+    HIPCHK(hipMalloc(&P->data->gramp16, (size_t)P->data->nblocks * std::max(P->data->pstride, 8) * 2));
+    HIPCHK(hipMalloc(&P->data->gramx16, (size_t)P->data->nblocks * m * m * 2));
+    HIPCHK(hipMalloc(&P->data->gram16_bad, sizeof(int)));
   }
-  PCHK(hipMalloc(&P->data->xx, sizeof(float) * p));
-  PCHK(hipMalloc(&P->data->vx, sizeof(float) * p));
-  PCHK(hipMalloc(&P->data->msx_dev, sizeof(float)));
+  HIPCHK(hipMalloc(&P->data->xx, sizeof(float) * p));
+  HIPCHK(hipMalloc(&P->data->vx, sizeof(float) * p));
+  HIPCHK(hipMalloc(&P->data->msx_dev, sizeof(float)));
   for (const void *f : {reinterpret_cast<const void *>(k_sweep<int8_t, true>), reinterpret_cast<const void *>(k_sweep<int8_t, false>), reinterpret_cast<const void *>(k_sweep<float, true>),
                         reinterpret_cast<const void *>(k_sweep<float, false>), reinterpret_cast<const void *>(k_sweep2<int8_t, true>), reinterpret_cast<const void *>(k_sweep2<int8_t, false>),
                         reinterpret_cast<const void *>(k_sweep2<int8_t, true, uint16_t>), reinterpret_cast<const void *>(k_sweep2<float, true>), reinterpret_cast<const void *>(k_sweep2<float, false>),
                         reinterpret_cast<const void *>(k_sweep2w<true>), reinterpret_cast<const void *>(k_sweep2w<false>), reinterpret_cast<const void *>(k_affine_inv)})
-    PCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #ifdef BWGR_EXPERIMENTS
   if (!P->data->is_f32) P->data->ldsw_bytes = s2w_lds_bytes(m, R, sw.wlag_timing ? sw.wlag_timing : 6);
 #else
   if (!P->data->is_f32) P->data->ldsw_bytes = s2w_lds_bytes(m, R, 6);
 #endif   // (room for the deepest pipeline BWGR_WLAG can ask for)
-#undef PCHK
-  (void)rc;
+  drop.release();
   *out = P;
   return BWGR_OK;
 }
@@ -1975,14 +2014,14 @@ extern "C" int bwgr_panel_create(bwgr_panel **out, const void *X, int xtype, int
   if (memloc != BWGR_HOST && memloc != BWGR_DEVICE) return fail(BWGR_EINVAL, "panel_create: bad memloc %d", memloc);
   bwgr_panel *P = nullptr;
   CHK(panel_alloc(&P, xtype != BWGR_X_I8, n, p, device, block, nwg, read_switches()));
+  Guard drop([&] { bwgr_panel_destroy(P); });
   P->data->want3 = true;
-  int rc;
-  if (xtype == BWGR_X_I8) rc = upload<int8_t, int8_t>(P, X, memloc, ldx);
-  else if (xtype == BWGR_X_F32) rc = upload<float, float>(P, X, memloc, ldx);
-  else rc = upload<double, float>(P, X, memloc, ldx);
-  if (rc == BWGR_OK) rc = panel_setup(P);
-  if (rc == BWGR_OK) rc = scratch_alloc(P);
-  if (rc != BWGR_OK) { bwgr_panel_destroy(P); return rc; }
+  if (xtype == BWGR_X_I8) CHK((upload<int8_t, int8_t>(P, X, memloc, ldx)));
+  else if (xtype == BWGR_X_F32) CHK((upload<float, float>(P, X, memloc, ldx)));
+  else CHK((upload<double, float>(P, X, memloc, ldx)));
+  CHK(panel_setup(P));
+  CHK(scratch_alloc(P));
+  drop.release();
   *out = P;
   return BWGR_OK;
 }
@@ -2005,11 +2044,12 @@ extern "C" int bwgr_panel_clone(bwgr_panel **out, bwgr_panel *src) {
   HIPCHK(hipStreamSynchronize(src->stream));   // the shared arrays are complete
   bwgr_panel *P = new bwgr_panel();
   P->data = src->data; P->data->nclones++;
-  const hipError_t e = hipStreamCreateWithFlags(&P->own_stream, hipStreamNonBlocking);
+  Guard drop([&] { bwgr_panel_destroy(P); });
+  HIPCHK(hipStreamCreateWithFlags(&P->own_stream, hipStreamNonBlocking));
   P->stream = P->own_stream;
-  const int rc = e != hipSuccess ? fail(BWGR_EHIP, "panel_clone: hipStreamCreateWithFlags failed: %s", hipGetErrorString(e)) : scratch_alloc(P);
-  if (rc != BWGR_OK) { bwgr_panel_destroy(P); return rc; }
+  CHK(scratch_alloc(P));
   HIPCHK(hipStreamSynchronize(P->stream));   // (k_sweep3's lists are zeroed on it)
+  drop.release();
   *out = P;
   return BWGR_OK;
 }
@@ -2090,20 +2130,6 @@ extern "C" int bwgr_panel_stats(bwgr_panel *P, float *xx, float *vx, float *MSx)
 // ------------------------------------------------------------------------------------------------
 // KMUP
 // ------------------------------------------------------------------------------------------------
-// device buffers of one call, released on every exit path
-namespace {
-struct DevBufs {
-  std::vector<void *> v;
-  ~DevBufs() { for (void *q : v) hipFree(q); }
-  template <typename T> T *get(size_t count) {
-    void *q = nullptr;
-    if (hipMalloc(&q, sizeof(T) * (count ? count : 1)) != hipSuccess) return nullptr;
-    v.push_back(q);
-    return reinterpret_cast<T *>(q);
-  }
-};
-}  // namespace
-
 // row gather of the resident panel P into the subsample panel PB (rows use_d[0..nbag), device array); KMUP2's H = X(Use, j)
 static void launch_gather_rows(bwgr_panel *P, bwgr_panel *PB, const int *use_d, int64_t nbag) {
   if (P->data->is_f32) hipLaunchKernelGGL(k_gather_rows<float>, dim3(4096), dim3(256), 0, P->stream, (const float *)P->data->X, P->data->R, use_d, (int)nbag, (float *)PB->data->X, PB->data->R, PB->data->ld, P->data->p);
@@ -2146,7 +2172,7 @@ static int kmup_sweep(bwgr_panel *PS, float *b, float *d, const float *xx, const
 
 extern "C" int bwgr_kmup(bwgr_panel *P, float *b, float *d, const float *xx, float *e, const float *L, float Ve,
                          float pi, uint64_t seed, uint32_t iter, int rng_mode) {
-  if (P && P->data->cen) return fail(BWGR_EINVAL, "kmup: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
+  if (P && P->data->cen) return refuse_centred("kmup");
   if (!P || !b || !d || !xx || !e || !L) return fail(BWGR_EINVAL, "kmup: null pointer");
   HIPCHK(hipSetDevice(P->data->device));
   DevBufs bufs;
@@ -2168,7 +2194,7 @@ extern "C" int bwgr_kmup(bwgr_panel *P, float *b, float *d, const float *xx, flo
 // e_out receives the nuse residuals of the subsample (:76); E (n0 entries) is not modified.
 extern "C" int bwgr_kmup2(bwgr_panel *P, const int *Use, int64_t nuse, float *b, float *d, const float *xx, const float *E,
                           float *e_out, const float *L, float Ve, float pi, uint64_t seed, uint32_t iter, int rng_mode) {
-  if (P && P->data->cen) return fail(BWGR_EINVAL, "kmup2: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
+  if (P && P->data->cen) return refuse_centred("kmup2");
   if (!P || !Use || !b || !d || !xx || !E || !e_out || !L) return fail(BWGR_EINVAL, "kmup2: null pointer");
   if (nuse < 2 || nuse > 0x7FFFFF00ll) return fail(BWGR_EINVAL, "kmup2: need 2 <= length(Use) < 2^31 (got %lld)", (long long)nuse);
   for (int64_t k = 0; k < nuse; ++k)
@@ -2177,7 +2203,7 @@ extern "C" int bwgr_kmup2(bwgr_panel *P, const int *Use, int64_t nuse, float *b,
   bwgr_panel *PB = nullptr;
   CHK(panel_alloc(&PB, P->data->is_f32, nuse, P->data->p, P->data->device, P->data->m, 0, P->data->sw));
   PB->stream = P->stream;
-  struct Drop { bwgr_panel *q; ~Drop() { if (q) bwgr_panel_destroy(q); } } drop{PB};
+  Guard drop([&] { bwgr_panel_destroy(PB); });
   CHK(scratch_alloc(PB));
   DevBufs bufs;
   int *use_d = bufs.get<int>((size_t)nuse);
@@ -2239,20 +2265,19 @@ extern "C" int bwgr_chain_create_sharded(bwgr_chain **out, bwgr_panel *P, int mo
   C->marker0 = marker0; C->p_total = p_total; C->MSx_eff = MSx_total;
   C->Phi = MSx_total * (1 - R2) / R2;
   const size_t pb = sizeof(float) * P->data->p;
-  auto bail = [&](int code) { bwgr_chain_destroy(C); return code; };
-#define CCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return bail(fail(BWGR_EHIP, "%s failed: %s", #x, hipGetErrorString(e_))); } while (0)
-  CCHK(hipMalloc(&C->y, sizeof(float) * P->data->n));
-  if (e_ext) { C->e = e_ext; C->e_owned = false; } else CCHK(hipMalloc(&C->e, sizeof(double) * P->data->ld));
-  CCHK(hipMalloc(&C->b, pb)); CCHK(hipMalloc(&C->d, pb)); CCHK(hipMalloc(&C->vb, pb)); CCHK(hipMalloc(&C->lam, pb));
-  CCHK(hipMalloc(&C->B, pb)); CCHK(hipMalloc(&C->D, pb)); CCHK(hipMalloc(&C->VB, pb)); CCHK(hipMalloc(&C->sc, sizeof(ChainScalars)));
-  CCHK(hipMemcpyAsync(C->y, y, sizeof(float) * P->data->n, memloc == BWGR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, P->stream));
+  Guard drop([&] { bwgr_chain_destroy(C); });
+  HIPCHK(hipMalloc(&C->y, sizeof(float) * P->data->n));
+  if (e_ext) { C->e = e_ext; C->e_owned = false; } else HIPCHK(hipMalloc(&C->e, sizeof(double) * P->data->ld));
+  HIPCHK(hipMalloc(&C->b, pb)); HIPCHK(hipMalloc(&C->d, pb)); HIPCHK(hipMalloc(&C->vb, pb)); HIPCHK(hipMalloc(&C->lam, pb));
+  HIPCHK(hipMalloc(&C->B, pb)); HIPCHK(hipMalloc(&C->D, pb)); HIPCHK(hipMalloc(&C->VB, pb)); HIPCHK(hipMalloc(&C->sc, sizeof(ChainScalars)));
+  HIPCHK(hipMemcpyAsync(C->y, y, sizeof(float) * P->data->n, memloc == BWGR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, P->stream));
   InitArgs ia; ia.y = C->y; ia.e = C->e; ia.n = (int)P->data->n; ia.p = (int)P->data->p; ia.ld = P->data->ld; ia.model = model;
   ia.pi = pi; ia.df = df; ia.R2 = R2; ia.MSx = MSx_total; ia.sc = C->sc;
   hipLaunchKernelGGL(k_chain_init, dim3(1), dim3(1024), 0, P->stream, ia);
   hipLaunchKernelGGL(k_marker_init, dim3(1024), dim3(256), 0, P->stream, C->b, C->d, C->vb, C->lam, C->B, C->D, C->VB, (int)P->data->p, C->sc);
-  CCHK(hipGetLastError());
-  CCHK(hipStreamSynchronize(P->stream));
-#undef CCHK
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(P->stream));
+  drop.release();
   *out = C;
   return BWGR_OK;
 }
@@ -2422,7 +2447,7 @@ extern "C" int bwgr_chain_run(bwgr_chain *C, int iters) {
 // bit-identical to a run of its own.  (No reference counterpart: the callers that fit many models on one X -- mcmcCV's loop,
 // /root/reference/R/cv.R:113-216 -- are where it plugs in.)
 extern "C" int bwgr_chain_run_pair(bwgr_chain *C0, bwgr_chain *C1, int iters) {
-  if (C0 && C0->P && C0->P->data->cen) return fail(BWGR_EINVAL, "chain_run_pair: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
+  if (C0 && C0->P && C0->P->data->cen) return refuse_centred("chain_run_pair");
   if (!C0 || !C1 || C0 == C1) return fail(BWGR_EINVAL, "chain_run_pair: two distinct chains");
   bwgr_panel *P0 = C0->P, *P1 = C1->P;
   if (P0->data != P1->data || P0 == P1) return fail(BWGR_EINVAL, "chain_run_pair: the chains must sit on two handles (panel and clone) of one resident panel");
@@ -2542,12 +2567,11 @@ extern "C" int bwgr_chain_state(bwgr_chain *C, float *b, float *d, float *e, flo
   if (b) HIPCHK(d2h(P->stream, b, C->b, pb));
   if (d) HIPCHK(d2h(P->stream, d, C->d, pb));
   if (e) {
-    float *ef = nullptr;
-    HIPCHK(hipMalloc(&ef, sizeof(float) * P->data->n));
+    DevBufs bufs;
+    float *ef = bufs.get<float>((size_t)P->data->n);
+    if (!ef) return fail(BWGR_ENOMEM, "chain_state: device allocation failed");
     hipLaunchKernelGGL(k_d2f, dim3(64), dim3(256), 0, P->stream, C->e, ef, P->data->n);
-    HIPCHK(hipMemcpyAsync(e, ef, sizeof(float) * P->data->n, hipMemcpyDeviceToHost, P->stream));
-    HIPCHK(hipStreamSynchronize(P->stream));
-    hipFree(ef);
+    HIPCHK(d2h(P->stream, e, ef, sizeof(float) * P->data->n));
   }
   if (vb) {
     if (per_marker_vb(C->model)) HIPCHK(d2h(P->stream, vb, C->vb, pb));
@@ -2572,11 +2596,12 @@ static void gemv_launch(bwgr_panel *P, const CT *coef_dev, int nchunks, int cpc,
 
 // hat = X*B + MU   (src/Rcpp20260726ai.cpp:629-630), fp64 accumulation, deterministic two-stage
 template <typename CT>
-static int gemv_hat(bwgr_panel *P, const CT *coef_dev, float MU, float *hat_dev, bool centred = false) {
+static int gemv_hat(bwgr_panel *P, const CT *coef_dev, float MU, float *hat_dev, const char *who, bool centred = false) {
   const int nchunks = gemv_chunks(P);
   const int cpc = (int)((P->data->p + nchunks - 1) / nchunks);
-  double *part = nullptr;
-  HIPCHK(hipMalloc(&part, sizeof(double) * ((size_t)nchunks * P->data->ld + 1)));
+  DevBufs bufs;
+  double *part = bufs.get<double>((size_t)nchunks * P->data->ld + 1);
+  if (!part) return fail(BWGR_ENOMEM, "%s: device allocation failed", who);
   gemv_launch<CT>(P, coef_dev, nchunks, cpc, part);
   double *cen_off = nullptr;
   if constexpr (std::is_same<CT, float>::value) {
@@ -2588,7 +2613,6 @@ static int gemv_hat(bwgr_panel *P, const CT *coef_dev, float MU, float *hat_dev,
   hipLaunchKernelGGL(k_hat_finish, dim3((unsigned)((P->data->n + 255) / 256)), dim3(256), 0, P->stream, part, P->data->ld, nchunks, (int)P->data->n, MU, hat_dev, (const double *)cen_off);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(P->stream));
-  HIPCHK(hipFree(part));
   return BWGR_OK;
 }
 
@@ -2619,12 +2643,10 @@ extern "C" int bwgr_chain_result(bwgr_chain *C, float *mu, float *b, float *d, f
   if (C->model == BWGR_BAYESCPI || C->model == BWGR_BAYESDPI) Pi = 1 - h.Pi / MCMC;   // :911
   if (per) {
     // vg = VB.sum()
-    double *part = nullptr; float *sdev = nullptr;
-    HIPCHK(hipMalloc(&part, sizeof(double) * 256)); HIPCHK(hipMalloc(&sdev, sizeof(float)));
-    hipLaunchKernelGGL(k_sum_stage1, dim3(256), dim3(256), 0, P->stream, C->VB, (int64_t)P->data->p, part);
-    hipLaunchKernelGGL(k_sum_stage2, dim3(1), dim3(256), 0, P->stream, part, 256, sdev);
-    HIPCHK(d2h(P->stream, &vg, sdev, sizeof(float)));
-    hipFree(part); hipFree(sdev);
+    DevBufs sum;
+    double *part = sum.get<double>(256); float *sdev = sum.get<float>(1);
+    if (!part || !sdev) return fail(BWGR_ENOMEM, "chain_result: device allocation failed");
+    CHK(sum_floats(P->stream, C->VB, (int64_t)P->data->p, part, sdev, &vg));
   } else {
     vg = VBs * C->MSx_eff;
     if (C->model == BWGR_BAYESCPI) vg = VBs * C->MSx_eff / Pi;                         // :913
@@ -2639,12 +2661,11 @@ extern "C" int bwgr_chain_result(bwgr_chain *C, float *mu, float *b, float *d, f
   if (vb) { if (per) HIPCHK(d2h(P->stream, vb, C->VB, pb)); else vb[0] = VBs; }
   if (pval) HIPCHK(d2h(P->stream, pval, pval_dev, pb));
   if (hat) {
-    float *hat_dev = nullptr;
-    HIPCHK(hipMalloc(&hat_dev, sizeof(float) * P->data->n));
-    int rc = gemv_hat<float>(P, C->B, MU, hat_dev, P->data->cen);
-    if (rc == BWGR_OK) HIPCHK(d2h(P->stream, hat, hat_dev, sizeof(float) * P->data->n));
-    hipFree(hat_dev);
-    CHK(rc);
+    DevBufs fit;
+    float *hat_dev = fit.get<float>((size_t)P->data->n);
+    if (!hat_dev) return fail(BWGR_ENOMEM, "chain_result: device allocation failed");
+    CHK(gemv_hat<float>(P, C->B, MU, hat_dev, "chain_result", P->data->cen));
+    HIPCHK(d2h(P->stream, hat, hat_dev, sizeof(float) * P->data->n));
   }
   return BWGR_OK;
 }
@@ -2654,17 +2675,16 @@ extern "C" int bwgr_bayes(bwgr_panel *P, int model, const float *y, float it, fl
                           float *h2, float *MSx, float *pi_out, float *pval) {
   bwgr_chain *C = nullptr;
   CHK(bwgr_chain_create(&C, P, model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode));
-  int rc = bwgr_chain_run(C, (int)it);
-  if (rc == BWGR_OK) rc = bwgr_chain_result(C, mu, b, d, hat, vb, ve, h2, MSx, pi_out, pval);
-  bwgr_chain_destroy(C);
-  return rc;
+  Guard drop([&] { bwgr_chain_destroy(C); });
+  CHK(bwgr_chain_run(C, (int)it));
+  return bwgr_chain_result(C, mu, b, d, hat, vb, ve, h2, MSx, pi_out, pval);
 }
 
 // BayesA2 / BayesB2 / BayesRR2, src/Rcpp20260726ai.cpp:990-1218: two chains over two panels sharing the residual
 extern "C" int bwgr_bayes2(bwgr_panel *P1, bwgr_panel *P2, int base_model, const float *y, float it, float bi, float pi, float df,
                            float R2, uint64_t seed, int rng_mode, float *mu, float *b1, float *d1, float *vb1, float *b2,
                            float *d2, float *vb2, float *ve, float *hat, float *h2) {
-  if ((P1 && P1->data->cen) || (P2 && P2->data->cen)) return fail(BWGR_EINVAL, "bayes2: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
+  if ((P1 && P1->data->cen) || (P2 && P2->data->cen)) return refuse_centred("bayes2");
   if (!P1 || !P2 || !y) return fail(BWGR_EINVAL, "bayes2: null pointer");
   if (base_model != BWGR_BAYESA && base_model != BWGR_BAYESB && base_model != BWGR_BAYESRR)
     return fail(BWGR_EINVAL, "bayes2: base model must be BayesA, BayesB or BayesRR (got %d)", base_model);
@@ -2676,19 +2696,12 @@ extern "C" int bwgr_bayes2(bwgr_panel *P1, bwgr_panel *P2, int base_model, const
   HIPCHK(hipSetDevice(P1->data->device));
   hipStream_t s2_saved = P2->stream;
   P2->stream = P1->stream;   // one stream orders the two chains' kernels
+  Guard restore([&] { P2->stream = s2_saved; });
   bwgr_chain *C1 = nullptr, *C2 = nullptr;
-  float *h1d = nullptr, *h2d = nullptr, *hatd = nullptr, *sdev = nullptr; double *part = nullptr;
-  int rc = bwgr_chain_create_sharded(&C1, P1, base_model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode, 0, p1 + p2, P1->data->MSx, nullptr);
-  if (rc == BWGR_OK) rc = bwgr_chain_create_sharded(&C2, P2, base_model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode, p1, p1 + p2, P2->data->MSx, C1->e);
-  auto done = [&](int code) {
-    if (C2) bwgr_chain_destroy(C2);
-    if (C1) bwgr_chain_destroy(C1);
-    hipFree(h1d); hipFree(h2d); hipFree(hatd); hipFree(sdev); hipFree(part);
-    P2->stream = s2_saved;
-    return code;
-  };
-  if (rc != BWGR_OK) return done(rc);
-#define BCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return done(fail(BWGR_EHIP, "%s failed: %s", #x, hipGetErrorString(e_))); } while (0)
+  Guard drop([&] { bwgr_chain_destroy(C2); bwgr_chain_destroy(C1); });
+  DevBufs bufs;
+  CHK(bwgr_chain_create_sharded(&C1, P1, base_model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode, 0, p1 + p2, P1->data->MSx, nullptr));
+  CHK(bwgr_chain_create_sharded(&C2, P2, base_model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode, p1, p1 + p2, P2->data->MSx, C1->e));
   const bool rr = (base_model == BWGR_BAYESRR), per = !rr;
   if (base_model == BWGR_BAYESB) { C1->flags_extra = SWF_ALT_B2; C2->flags_extra = SWF_ALT_B2; }
   if (rr) {
@@ -2697,9 +2710,8 @@ extern "C" int bwgr_bayes2(bwgr_panel *P1, bwgr_panel *P2, int base_model, const
   }
   const int iit = (int)it, ibi = (int)bi;
   for (int i = 0; i < iit; ++i) {
-    rc = bwgr_chain_sweep_blocks(C1, 0, (int)P1->data->nblocks);
-    if (rc == BWGR_OK) rc = bwgr_chain_sweep_blocks(C2, 0, (int)P2->data->nblocks);
-    if (rc != BWGR_OK) return done(rc);
+    CHK(bwgr_chain_sweep_blocks(C1, 0, (int)P1->data->nblocks));
+    CHK(bwgr_chain_sweep_blocks(C2, 0, (int)P2->data->nblocks));
     const int accumulate = (i > ibi) ? 1 : 0;                                        // if(i>ibi), :1047
     Tail2Args t; t.e = C1->e; t.n = (int)n; t.p1 = (int)p1; t.p2 = (int)p2; t.rr = rr ? 1 : 0; t.df = df;
     t.accumulate = accumulate; t.iter = (uint32_t)i; t.rng = make_rng(seed, rng_mode); t.sc1 = C1->sc; t.sc2 = C2->sc;
@@ -2708,53 +2720,48 @@ extern "C" int bwgr_bayes2(bwgr_panel *P1, bwgr_panel *P2, int base_model, const
                        C1->b, C1->d, C1->vb, C1->lam, C1->B, C1->D, C1->VB, (int)p1, base_model, 0.0f, accumulate, C1->sc);
     hipLaunchKernelGGL(k_marker_tail, dim3((unsigned)std::min<int64_t>(2048, (p2 + 255) / 256)), dim3(256), 0, P1->stream,
                        C2->b, C2->d, C2->vb, C2->lam, C2->B, C2->D, C2->VB, (int)p2, base_model, 0.0f, accumulate, C2->sc);
-    BCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     C1->done++; C2->done++;
   }
-  rc = bwgr_chain_sync(C1);
-  if (rc == BWGR_OK) rc = bwgr_chain_sync(C2);
-  if (rc != BWGR_OK) return done(rc);
+  CHK(bwgr_chain_sync(C1));
+  CHK(bwgr_chain_sync(C2));
   const float MCMC = it - bi;                                                        // :1049
   hipLaunchKernelGGL(k_final_markers, dim3(1024), dim3(256), 0, P1->stream, C1->B, C1->D, C1->VB, (float *)nullptr, (int)p1, MCMC, per ? 1 : 0);
   hipLaunchKernelGGL(k_final_markers, dim3(1024), dim3(256), 0, P1->stream, C2->B, C2->D, C2->VB, (float *)nullptr, (int)p2, MCMC, per ? 1 : 0);
-  BCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   ChainScalars g1, g2;
-  BCHK(hipMemcpyAsync(&g1, C1->sc, sizeof(g1), hipMemcpyDeviceToHost, P1->stream));
-  BCHK(hipMemcpyAsync(&g2, C2->sc, sizeof(g2), hipMemcpyDeviceToHost, P1->stream));
-  BCHK(hipStreamSynchronize(P1->stream));
+  HIPCHK(hipMemcpyAsync(&g1, C1->sc, sizeof(g1), hipMemcpyDeviceToHost, P1->stream));
+  HIPCHK(hipMemcpyAsync(&g2, C2->sc, sizeof(g2), hipMemcpyDeviceToHost, P1->stream));
+  HIPCHK(hipStreamSynchronize(P1->stream));
   const float MU = g1.MU / MCMC, VE = g1.VE / MCMC, VB1s = g1.VBs / MCMC, VB2s = g2.VBs / MCMC;
   float vg;
   if (per) {                                                                         // vg = VB1.sum() + VB2.sum(), :1051
     float v1 = 0, v2 = 0;
-    BCHK(hipMalloc(&part, sizeof(double) * 256)); BCHK(hipMalloc(&sdev, sizeof(float)));
-    hipLaunchKernelGGL(k_sum_stage1, dim3(256), dim3(256), 0, P1->stream, C1->VB, (int64_t)p1, part);
-    hipLaunchKernelGGL(k_sum_stage2, dim3(1), dim3(256), 0, P1->stream, part, 256, sdev);
-    BCHK(d2h(P1->stream, &v1, sdev, sizeof(float)));
-    hipLaunchKernelGGL(k_sum_stage1, dim3(256), dim3(256), 0, P1->stream, C2->VB, (int64_t)p2, part);
-    hipLaunchKernelGGL(k_sum_stage2, dim3(1), dim3(256), 0, P1->stream, part, 256, sdev);
-    BCHK(d2h(P1->stream, &v2, sdev, sizeof(float)));
+    double *part = bufs.get<double>(256); float *sdev = bufs.get<float>(1);
+    if (!part || !sdev) return fail(BWGR_ENOMEM, "bayes2: device allocation failed");
+    CHK(sum_floats(P1->stream, C1->VB, (int64_t)p1, part, sdev, &v1));
+    CHK(sum_floats(P1->stream, C2->VB, (int64_t)p2, part, sdev, &v2));
     vg = v1 + v2;
   } else vg = VB1s * P1->data->MSx + VB2s * P2->data->MSx;                                       // :1213
   if (mu) *mu = MU;
   if (ve) *ve = VE;
   if (h2) *h2 = vg / (vg + VE);
-  if (b1) BCHK(d2h(P1->stream, b1, C1->B, sizeof(float) * p1));
-  if (b2) BCHK(d2h(P1->stream, b2, C2->B, sizeof(float) * p2));
-  if (d1) BCHK(d2h(P1->stream, d1, C1->D, sizeof(float) * p1));
-  if (d2) BCHK(d2h(P1->stream, d2, C2->D, sizeof(float) * p2));
-  if (vb1) { if (per) BCHK(d2h(P1->stream, vb1, C1->VB, sizeof(float) * p1)); else vb1[0] = VB1s; }
-  if (vb2) { if (per) BCHK(d2h(P1->stream, vb2, C2->VB, sizeof(float) * p2)); else vb2[0] = VB2s; }
+  if (b1) HIPCHK(d2h(P1->stream, b1, C1->B, sizeof(float) * p1));
+  if (b2) HIPCHK(d2h(P1->stream, b2, C2->B, sizeof(float) * p2));
+  if (d1) HIPCHK(d2h(P1->stream, d1, C1->D, sizeof(float) * p1));
+  if (d2) HIPCHK(d2h(P1->stream, d2, C2->D, sizeof(float) * p2));
+  if (vb1) { if (per) HIPCHK(d2h(P1->stream, vb1, C1->VB, sizeof(float) * p1)); else vb1[0] = VB1s; }
+  if (vb2) { if (per) HIPCHK(d2h(P1->stream, vb2, C2->VB, sizeof(float) * p2)); else vb2[0] = VB2s; }
   if (hat) {                                                                         // fit = X1*B1 + X2*B2; fit += MU, :1052-1053
-    BCHK(hipMalloc(&h1d, sizeof(float) * n)); BCHK(hipMalloc(&h2d, sizeof(float) * n)); BCHK(hipMalloc(&hatd, sizeof(float) * n));
-    rc = gemv_hat<float>(P1, C1->B, 0.0f, h1d);
-    if (rc == BWGR_OK) rc = gemv_hat<float>(P2, C2->B, 0.0f, h2d);
-    if (rc != BWGR_OK) return done(rc);
+    float *h1d = bufs.get<float>((size_t)n), *h2d = bufs.get<float>((size_t)n), *hatd = bufs.get<float>((size_t)n);
+    if (!h1d || !h2d || !hatd) return fail(BWGR_ENOMEM, "bayes2: device allocation failed");
+    CHK(gemv_hat<float>(P1, C1->B, 0.0f, h1d, "bayes2"));
+    CHK(gemv_hat<float>(P2, C2->B, 0.0f, h2d, "bayes2"));
     hipLaunchKernelGGL(k_hat2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, P1->stream, h1d, h2d, MU, hatd, (int)n);
-    BCHK(hipGetLastError());
-    BCHK(d2h(P1->stream, hat, hatd, sizeof(float) * n));
+    HIPCHK(hipGetLastError());
+    HIPCHK(d2h(P1->stream, hat, hatd, sizeof(float) * n));
   }
-#undef BCHK
-  return done(BWGR_OK);
+  return BWGR_OK;
 }
 
 // host side of the RNG contract for wgr's row resampling, R/wgr.R:68: Use = sort(sample(n, n*bag, rp)) - 1
@@ -2789,19 +2796,6 @@ extern "C" int bwgr_sample_rows(uint64_t seed, uint32_t iter, int64_t n, int64_t
   return BWGR_OK;
 }
 
-// X * coef (fp64 partial products per column chunk); caller finishes.  Returns nchunks and the device buffer.
-template <typename CT>
-static int gemv_parts(bwgr_panel *P, const CT *coef_dev, double **part_out, int *nchunks_out) {
-  const int nchunks = gemv_chunks(P);
-  const int cpc = (int)((P->data->p + nchunks - 1) / nchunks);
-  double *part = *part_out;
-  if (!part) HIPCHK(hipMalloc(&part, sizeof(double) * (size_t)nchunks * P->data->ld));
-  gemv_launch<CT>(P, coef_dev, nchunks, cpc, part);
-  HIPCHK(hipGetLastError());
-  *part_out = part; *nchunks_out = nchunks;
-  return BWGR_OK;
-}
-
 extern "C" int bwgr_wgr(bwgr_panel *P, const double *y, int it, int bi, int th, int iv, int de, double pi, double df, double R2,
                         uint64_t seed, int rng_mode, double *mu, double *b, double *Vb, double *d, double *Ve, double *hat,
                         double *cxx) {
@@ -2811,7 +2805,7 @@ extern "C" int bwgr_wgr(bwgr_panel *P, const double *y, int it, int bi, int th, 
 extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int th, int iv, int de, double pi, double df, double R2,
                            uint64_t seed, int rng_mode, const double *U, const double *V, int64_t pk, double bag, int rp,
                            double *mu, double *b, double *Vb, double *d, double *Ve, double *hat, double *cxx, double *u, double *Vk) {
-  if (P && P->data->cen) return fail(BWGR_EINVAL, "wgr: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
+  if (P && P->data->cen) return refuse_centred("wgr");
   if (!P || !y) return fail(BWGR_EINVAL, "wgr: null pointer");
   if (!U || pk <= 0) { U = nullptr; pk = 0; }
   if (U && !V) return fail(BWGR_EINVAL, "wgr: eigenvalues missing");
@@ -2827,144 +2821,124 @@ extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int t
   if (de) iv = 1;                                                                  // R/wgr.R:9
   HIPCHK(hipSetDevice(P->data->device));
   const int p = (int)P->data->p, n = (int)P->data->n;
-  const size_t pd = sizeof(double) * p, pf = sizeof(float) * p;
+  const size_t pd = sizeof(double) * p;
   const Rng rng = make_rng(seed, rng_mode);
   int mc = 0; for (int q = bi; q <= it; q += th) mc++;                             // post = seq(bi,it,th)
   if (mc < 1) return fail(BWGR_EINVAL, "wgr: seq(bi,it,th) is empty");
-  std::vector<void *> owned;
-  auto dalloc = [&](size_t bytes) -> void * { void *q = nullptr; if (hipMalloc(&q, bytes) != hipSuccess) return nullptr; owned.push_back(q); return q; };
-  auto cleanup = [&]() { for (void *q : owned) hipFree(q); };
   bwgr_panel *PU = nullptr;   // eigenvectors as an fp32 panel (KMUP narrows U to float like any other X)
+  bwgr_panel *PB = nullptr;   // the row subsample of this iteration (bag != 1): same markers, nbag rows
+  Guard drop([&] { bwgr_panel_destroy(PU); bwgr_panel_destroy(PB); });
+  std::vector<int> use_h;     // (copied from asynchronously: declared before the holder, which waits for the stream)
+  DevBufs bufs(P->stream);
   if (U) {
-    int rcu = bwgr_panel_create(&PU, U, BWGR_X_F64, BWGR_HOST, n, pk, n, P->data->device, 0, 0);
-    if (rcu != BWGR_OK) return rcu;
+    CHK(bwgr_panel_create(&PU, U, BWGR_X_F64, BWGR_HOST, n, pk, n, P->data->device, 0, 0));
     PU->stream = P->stream;
   }
-  bwgr_panel *PB = nullptr;   // the row subsample of this iteration (bag != 1): same markers, nbag rows
   int *use_d = nullptr;
-  std::vector<int> use_h;
-  auto drop_panels = [&]() { if (PU) bwgr_panel_destroy(PU); if (PB) bwgr_panel_destroy(PB); hipFree(use_d); PU = PB = nullptr; use_d = nullptr; };
   if (bagging) {
-    int rcb = panel_alloc(&PB, P->data->is_f32, nbag, P->data->p, P->data->device, P->data->m, 0, P->data->sw);
-    if (rcb == BWGR_OK) { PB->stream = P->stream; rcb = scratch_alloc(PB); }
-    if (rcb != BWGR_OK) { drop_panels(); return rcb; }
-    if (hipMalloc(&use_d, sizeof(int) * (size_t)nbag) != hipSuccess) { drop_panels(); return fail(BWGR_ENOMEM, "wgr: device allocation failed"); }
+    CHK(panel_alloc(&PB, P->data->is_f32, nbag, P->data->p, P->data->device, P->data->m, 0, P->data->sw));
+    PB->stream = P->stream;
+    CHK(scratch_alloc(PB));
+    if (!(use_d = bufs.get<int>((size_t)nbag))) return fail(BWGR_ENOMEM, "wgr: device allocation failed");
   }
   const int64_t ldmax = std::max<int64_t>(std::max<int64_t>(P->data->ld, PU ? PU->data->ld : 0), PB ? PB->data->ld : 0);
-  const size_t kd = sizeof(double) * (size_t)std::max<int64_t>(pk, 1), kf = sizeof(float) * (size_t)std::max<int64_t>(pk, 1);
-  double *yd = (double *)dalloc(sizeof(double) * n), *eR = (double *)dalloc(sizeof(double) * ldmax), *e64 = (double *)dalloc(sizeof(double) * ldmax);
-  double *Ud = (double *)dalloc(sizeof(double) * (size_t)std::max<int64_t>(n * pk, 1)), *Vd = (double *)dalloc(kd), *hR = (double *)dalloc(kd), *Hk = (double *)dalloc(kd), *uhd = (double *)dalloc(sizeof(double) * n);
-  float *hf = (float *)dalloc(kf), *dhf = (float *)dalloc(kf), *xxKf = (float *)dalloc(kf), *Lkf = (float *)dalloc(kf), *vbk = (float *)dalloc(kf);
-  ChainScalars *sck = (ChainScalars *)dalloc(sizeof(ChainScalars));
-  double *xx64 = (double *)dalloc(pd), *vx64 = (double *)dalloc(pd), *bR = (double *)dalloc(pd), *dR = (double *)dalloc(pd);
-  double *VbR = (double *)dalloc(pd), *LR = (double *)dalloc(pd), *B = (double *)dalloc(pd), *D = (double *)dalloc(pd), *VB = (double *)dalloc(pd);
-  float *bf = (float *)dalloc(pf), *dfl = (float *)dalloc(pf), *Lf = (float *)dalloc(pf), *xxf = (float *)dalloc(pf), *vbf = (float *)dalloc(pf);
-  double *part1 = (double *)dalloc(sizeof(double) * 256), *part2 = (double *)dalloc(sizeof(double) * 256), *hatd = (double *)dalloc(sizeof(double) * n);
-  WgrScalars *ws = (WgrScalars *)dalloc(sizeof(WgrScalars));
-  ChainScalars *sc = (ChainScalars *)dalloc(sizeof(ChainScalars));
-  if (!Ud || !Vd || !hR || !Hk || !uhd || !hf || !dhf || !xxKf || !Lkf || !vbk || !sck ||
-      !yd || !eR || !e64 || !xx64 || !vx64 || !bR || !dR || !VbR || !LR || !B || !D || !VB || !bf || !dfl || !Lf || !xxf || !vbf || !part1 || !part2 || !hatd || !ws || !sc) {
-    cleanup(); drop_panels(); return fail(BWGR_ENOMEM, "wgr: device allocation failed");
+  const size_t nk = (size_t)std::max<int64_t>(pk, 1), np = (size_t)p, kd = sizeof(double) * nk;
+  const int nchunks = gemv_chunks(P), cpc = (p + nchunks - 1) / nchunks;   // X * coef: fp64 partial products per column chunk
+  double *yd = bufs.get<double>(n), *eR = bufs.get<double>(ldmax), *e64 = bufs.get<double>(ldmax);
+  double *Ud = bufs.get<double>((size_t)std::max<int64_t>(n * pk, 1)), *Vd = bufs.get<double>(nk), *hR = bufs.get<double>(nk), *Hk = bufs.get<double>(nk), *uhd = bufs.get<double>(n);
+  float *hf = bufs.get<float>(nk), *dhf = bufs.get<float>(nk), *xxKf = bufs.get<float>(nk), *Lkf = bufs.get<float>(nk), *vbk = bufs.get<float>(nk);
+  ChainScalars *sck = bufs.get<ChainScalars>(1);
+  double *xx64 = bufs.get<double>(np), *vx64 = bufs.get<double>(np), *bR = bufs.get<double>(np), *dR = bufs.get<double>(np);
+  double *VbR = bufs.get<double>(np), *LR = bufs.get<double>(np), *B = bufs.get<double>(np), *D = bufs.get<double>(np), *VB = bufs.get<double>(np);
+  float *bf = bufs.get<float>(np), *dfl = bufs.get<float>(np), *Lf = bufs.get<float>(np), *xxf = bufs.get<float>(np), *vbf = bufs.get<float>(np);
+  double *part1 = bufs.get<double>(256), *part2 = bufs.get<double>(256), *hatd = bufs.get<double>(n);
+  WgrScalars *ws = bufs.get<WgrScalars>(1);
+  ChainScalars *sc = bufs.get<ChainScalars>(1);
+  double *gpart = bufs.get<double>((size_t)nchunks * P->data->ld);
+  if (!Ud || !Vd || !hR || !Hk || !uhd || !hf || !dhf || !xxKf || !Lkf || !vbk || !sck || !gpart ||
+      !yd || !eR || !e64 || !xx64 || !vx64 || !bR || !dR || !VbR || !LR || !B || !D || !VB || !bf || !dfl || !Lf || !xxf || !vbf || !part1 || !part2 || !hatd || !ws || !sc)
+    return fail(BWGR_ENOMEM, "wgr: device allocation failed");
+  HIPCHK(hipMemcpyAsync(yd, y, sizeof(double) * n, hipMemcpyHostToDevice, P->stream));
+  if (pk > 0) {
+    HIPCHK(hipMemcpyAsync(Ud, U, sizeof(double) * (size_t)n * pk, hipMemcpyHostToDevice, P->stream));
+    HIPCHK(hipMemcpyAsync(Vd, V, kd, hipMemcpyHostToDevice, P->stream));
+    HIPCHK(hipMemsetAsync(hR, 0, kd, P->stream)); HIPCHK(hipMemsetAsync(Hk, 0, kd, P->stream));
   }
-  int rc = BWGR_OK;
-  double *gpart = nullptr; int nchunks = 0;
-#define WCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rc = fail(BWGR_EHIP, "%s failed: %s", #x, hipGetErrorString(e_)); goto done; } } while (0)
-  {
-    WCHK(hipMemcpyAsync(yd, y, sizeof(double) * n, hipMemcpyHostToDevice, P->stream));
-    if (pk > 0) {
-      WCHK(hipMemcpyAsync(Ud, U, sizeof(double) * (size_t)n * pk, hipMemcpyHostToDevice, P->stream));
-      WCHK(hipMemcpyAsync(Vd, V, kd, hipMemcpyHostToDevice, P->stream));
-      WCHK(hipMemsetAsync(hR, 0, kd, P->stream)); WCHK(hipMemsetAsync(Hk, 0, kd, P->stream));
+  const int wpb = 4;
+  if (P->data->is_f32) hipLaunchKernelGGL(k_stats64<float>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const float *)P->data->X, P->data->R, n, p, xx64, vx64);
+  else hipLaunchKernelGGL(k_stats64<int8_t>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const int8_t *)P->data->X, P->data->R, n, p, xx64, vx64);
+  hipLaunchKernelGGL(k_dsum_stage1, dim3(256), dim3(256), 0, P->stream, vx64, (int64_t)p, part1, 0);
+  hipLaunchKernelGGL(k_dsum_stage1, dim3(256), dim3(256), 0, P->stream, xx64, (int64_t)p, part2, 0);
+  hipLaunchKernelGGL(k_wgr_init, dim3(1), dim3(1024), 0, P->stream, yd, eR, n, ldmax, part1, part2, p, df, R2, ws);
+  hipLaunchKernelGGL(k_wgr_marker_init, dim3(1024), dim3(256), 0, P->stream, bR, dR, VbR, LR, B, D, VB, p, ws);
+  if (bagging) hipLaunchKernelGGL(k_scale_d, dim3(256), dim3(256), 0, P->stream, xx64, (int64_t)p, bag);     // xx = crossprod * bag, R/wgr.R:46
+  HIPCHK(hipGetLastError());
+  const unsigned pg = (unsigned)std::min<int64_t>(2048, (P->data->p + 255) / 256);
+  for (int i = 1; i <= it; ++i) {                                                // R/wgr.R:66
+    const uint32_t itx = (uint32_t)(i - 1);
+    const int accumulate = (i >= bi && ((i - bi) % th) == 0) ? 1 : 0;            // i %in% post
+    if (pk > 0) {                                                                // R/wgr.R:70-76
+      hipLaunchKernelGGL(k_wgr_pre_k, dim3(64), dim3(256), 0, P->stream, hR, Vd, eR, hf, dhf, xxKf, Lkf, e64, (int)pk, n, ldmax, ws, sck);
+      SweepArgs ak; memset(&ak, 0, sizeof(ak));
+      fill_panel_args(PU, ak);
+      ak.flags = SWF_LAM_VEC;
+      ak.e = e64; ak.b = hf; ak.d = dhf; ak.vb = vbk; ak.xx = xxKf; ak.lam = Lkf; ak.sc = sck; ak.iter = itx; ak.marker0 = 0x80000000u; ak.rng = rng;
+      CHK(launch_sweep(PU, ak));
+      hipLaunchKernelGGL(k_wgr_post_k, dim3(64), dim3(256), 0, P->stream, hf, hR, e64, eR, (int)pk, n);
     }
-    const int wpb = 4;
-    if (P->data->is_f32) hipLaunchKernelGGL(k_stats64<float>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const float *)P->data->X, P->data->R, n, p, xx64, vx64);
-    else hipLaunchKernelGGL(k_stats64<int8_t>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const int8_t *)P->data->X, P->data->R, n, p, xx64, vx64);
-    hipLaunchKernelGGL(k_dsum_stage1, dim3(256), dim3(256), 0, P->stream, vx64, (int64_t)p, part1, 0);
-    hipLaunchKernelGGL(k_dsum_stage1, dim3(256), dim3(256), 0, P->stream, xx64, (int64_t)p, part2, 0);
-    hipLaunchKernelGGL(k_wgr_init, dim3(1), dim3(1024), 0, P->stream, yd, eR, n, ldmax, part1, part2, p, df, R2, ws);
-    hipLaunchKernelGGL(k_wgr_marker_init, dim3(1024), dim3(256), 0, P->stream, bR, dR, VbR, LR, B, D, VB, p, ws);
-    if (bagging) hipLaunchKernelGGL(k_scale_d, dim3(256), dim3(256), 0, P->stream, xx64, (int64_t)p, bag);     // xx = crossprod * bag, R/wgr.R:46
-    WCHK(hipGetLastError());
-    const unsigned pg = (unsigned)std::min<int64_t>(2048, (P->data->p + 255) / 256);
-    for (int i = 1; i <= it; ++i) {                                                // R/wgr.R:66
-      const uint32_t itx = (uint32_t)(i - 1);
-      const int accumulate = (i >= bi && ((i - bi) % th) == 0) ? 1 : 0;            // i %in% post
-      if (pk > 0) {                                                                // R/wgr.R:70-76
-        hipLaunchKernelGGL(k_wgr_pre_k, dim3(64), dim3(256), 0, P->stream, hR, Vd, eR, hf, dhf, xxKf, Lkf, e64, (int)pk, n, ldmax, ws, sck);
-        SweepArgs ak; memset(&ak, 0, sizeof(ak));
-        fill_panel_args(PU, ak);
-        ak.flags = SWF_LAM_VEC;
-        ak.e = e64; ak.b = hf; ak.d = dhf; ak.vb = vbk; ak.xx = xxKf; ak.lam = Lkf; ak.sc = sck; ak.iter = itx; ak.marker0 = 0x80000000u; ak.rng = rng;
-        rc = launch_sweep(PU, ak);
-        if (rc != BWGR_OK) goto done;
-        hipLaunchKernelGGL(k_wgr_post_k, dim3(64), dim3(256), 0, P->stream, hf, hR, e64, eR, (int)pk, n);
-      }
-      hipLaunchKernelGGL(k_wgr_pre, dim3(pg), dim3(256), 0, P->stream, bR, dR, LR, xx64, eR, bf, dfl, Lf, xxf, e64, p, n, ldmax, (float)pi, ws, sc);
-      SweepArgs a; memset(&a, 0, sizeof(a));
-      bwgr_panel *PS = bagging ? PB : P;                                           // the panel this iteration sweeps
-      if (bagging) {                                                               // R/wgr.R:68 + KMUP2's gathers
-        bag_rows(seed, itx, n, nbag, rp, use_h);
-        WCHK(hipMemcpyAsync(use_d, use_h.data(), sizeof(int) * (size_t)nbag, hipMemcpyHostToDevice, P->stream));
-        launch_gather_rows(P, PB, use_d, nbag);
-        rc = panel_build_gram(PB);                                                  // syncs the stream (use_h stays valid)
-        if (rc != BWGR_OK) goto done;
-        hipLaunchKernelGGL(k_gather_e, dim3(64), dim3(256), 0, P->stream, eR, use_d, (int)nbag, ldmax, e64);
-        hipLaunchKernelGGL(k_set_bg, dim3(1), dim3(1), 0, P->stream, sc, (float)n / (float)nbag);
-      }
-      fill_panel_args(PS, a);
-      a.flags = SWF_LAM_VEC | (pi > 0 ? (SWF_SELECT | SWF_ALT_B2) : 0) | (bagging ? SWF_KMUP2 : 0) | (de ? SWF_SERIAL : 0);
-      a.e = e64; a.b = bf; a.d = dfl; a.vb = vbf; a.xx = xxf; a.lam = Lf; a.sc = sc; a.iter = itx; a.rng = rng;
-      rc = launch_sweep(PS, a);                                                    // KMUP / KMUP2, R/wgr.R:85
-      if (rc != BWGR_OK) goto done;
-      hipLaunchKernelGGL(k_wgr_post, dim3(pg), dim3(256), 0, P->stream, bf, dfl, bR, dR, VbR, p, pi > 0 ? 1 : 0, iv, de, df, itx, rng, ws);
-      hipLaunchKernelGGL(k_dsum_stage1, dim3(256), dim3(256), 0, P->stream, bR, (int64_t)p, part1, 1);
-      if (pk > 0) hipLaunchKernelGGL(k_wgr_vp, dim3(1), dim3(1024), 0, P->stream, hR, Vd, (int)pk, df, itx, rng, ws);   // R/wgr.R:116-119
-      hipLaunchKernelGGL(k_wgr_scal, dim3(1), dim3(1024), 0, P->stream, e64, (int)nbag, (double)n * bag, p, part1, iv, df, itx, rng, ws);
-      hipLaunchKernelGGL(k_wgr_L, dim3(pg), dim3(256), 0, P->stream, bR, dR, VbR, LR, B, D, VB, p, iv, accumulate, ws);
-      rc = gemv_parts<double>(P, bR, &gpart, &nchunks);
-      if (rc != BWGR_OK) goto done;
-      hipLaunchKernelGGL(k_wgr_efinish, dim3((n + 255) / 256), dim3(256), 0, P->stream, gpart, P->data->ld, nchunks, n, yd, eR, ws);
-      if (pk > 0) hipLaunchKernelGGL(k_uh, dim3((n + 255) / 256), dim3(256), 0, P->stream, Ud, hR, n, (int)pk, 1.0, eR, 1);   // - U %*% h
-      hipLaunchKernelGGL(k_wgr_mu, dim3(1), dim3(1024), 0, P->stream, eR, n, iv, accumulate, itx, rng, ws);
-      if (pk > 0 && accumulate) hipLaunchKernelGGL(k_wgr_accum_k, dim3(8), dim3(256), 0, P->stream, hR, Hk, (int)pk, ws);
-      WCHK(hipGetLastError());
-      if ((i & 63) == 0) WCHK(hipStreamSynchronize(P->stream));                    // bound the launch queue
+    hipLaunchKernelGGL(k_wgr_pre, dim3(pg), dim3(256), 0, P->stream, bR, dR, LR, xx64, eR, bf, dfl, Lf, xxf, e64, p, n, ldmax, (float)pi, ws, sc);
+    SweepArgs a; memset(&a, 0, sizeof(a));
+    bwgr_panel *PS = bagging ? PB : P;                                           // the panel this iteration sweeps
+    if (bagging) {                                                               // R/wgr.R:68 + KMUP2's gathers
+      bag_rows(seed, itx, n, nbag, rp, use_h);
+      HIPCHK(hipMemcpyAsync(use_d, use_h.data(), sizeof(int) * (size_t)nbag, hipMemcpyHostToDevice, P->stream));
+      launch_gather_rows(P, PB, use_d, nbag);
+      CHK(panel_build_gram(PB));                                                 // syncs the stream (use_h stays valid)
+      hipLaunchKernelGGL(k_gather_e, dim3(64), dim3(256), 0, P->stream, eR, use_d, (int)nbag, ldmax, e64);
+      hipLaunchKernelGGL(k_set_bg, dim3(1), dim3(1), 0, P->stream, sc, (float)n / (float)nbag);
     }
-    hipLaunchKernelGGL(k_dsum_stage1, dim3(256), dim3(256), 0, P->stream, D, (int64_t)p, part1, 0);
-    hipLaunchKernelGGL(k_wgr_final, dim3(1), dim3(1024), 0, P->stream, B, D, VB, p, (double)mc, part1, iv, ws);
-    WgrScalars h; ChainScalars hc;
-    WCHK(hipMemcpyAsync(&h, ws, sizeof(h), hipMemcpyDeviceToHost, P->stream));
-    WCHK(hipMemcpyAsync(&hc, sc, sizeof(hc), hipMemcpyDeviceToHost, P->stream));
-    WCHK(hipStreamSynchronize(P->stream));
-    if (hc.error) { rc = sweep_error(hc.error, "wgr"); goto done; }
-    const double B0 = h.B0 / mc;
-    rc = gemv_parts<double>(P, B, &gpart, &nchunks);                               // HAT = B0 + gen0 %*% B, R/wgr.R:152
-    if (rc != BWGR_OK) goto done;
-    hipLaunchKernelGGL(k_hat64_finish, dim3((n + 255) / 256), dim3(256), 0, P->stream, gpart, P->data->ld, nchunks, n, B0, hatd);
-    if (pk > 0) {                                                                  // poly = U0 %*% H; HAT += poly, R/wgr.R:148-150
-      hipLaunchKernelGGL(k_uh, dim3((n + 255) / 256), dim3(256), 0, P->stream, Ud, Hk, n, (int)pk, 1.0 / (double)mc, uhd, 0);
-      hipLaunchKernelGGL(k_add_vec, dim3((n + 255) / 256), dim3(256), 0, P->stream, hatd, uhd, n);
-    }
-    WCHK(hipGetLastError());
-    if (mu) *mu = B0;
-    if (Ve) *Ve = h.VE / mc;
-    if (cxx) *cxx = h.cxx * bag;                                                   // mean(xx), xx = crossprod * bag
-    if (b) WCHK(d2h(P->stream, b, B, pd));
-    if (d) WCHK(d2h(P->stream, d, D, pd));
-    if (Vb) { if (iv) WCHK(d2h(P->stream, Vb, VB, pd)); else Vb[0] = h.VA / mc; }
-    if (hat) WCHK(d2h(P->stream, hat, hatd, sizeof(double) * n));
-    if (pk > 0 && u) WCHK(d2h(P->stream, u, uhd, sizeof(double) * n));
-    if (pk > 0 && Vk) *Vk = h.VP / mc;
+    fill_panel_args(PS, a);
+    a.flags = SWF_LAM_VEC | (pi > 0 ? (SWF_SELECT | SWF_ALT_B2) : 0) | (bagging ? SWF_KMUP2 : 0) | (de ? SWF_SERIAL : 0);
+    a.e = e64; a.b = bf; a.d = dfl; a.vb = vbf; a.xx = xxf; a.lam = Lf; a.sc = sc; a.iter = itx; a.rng = rng;
+    CHK(launch_sweep(PS, a));                                                    // KMUP / KMUP2, R/wgr.R:85
+    hipLaunchKernelGGL(k_wgr_post, dim3(pg), dim3(256), 0, P->stream, bf, dfl, bR, dR, VbR, p, pi > 0 ? 1 : 0, iv, de, df, itx, rng, ws);
+    hipLaunchKernelGGL(k_dsum_stage1, dim3(256), dim3(256), 0, P->stream, bR, (int64_t)p, part1, 1);
+    if (pk > 0) hipLaunchKernelGGL(k_wgr_vp, dim3(1), dim3(1024), 0, P->stream, hR, Vd, (int)pk, df, itx, rng, ws);   // R/wgr.R:116-119
+    hipLaunchKernelGGL(k_wgr_scal, dim3(1), dim3(1024), 0, P->stream, e64, (int)nbag, (double)n * bag, p, part1, iv, df, itx, rng, ws);
+    hipLaunchKernelGGL(k_wgr_L, dim3(pg), dim3(256), 0, P->stream, bR, dR, VbR, LR, B, D, VB, p, iv, accumulate, ws);
+    gemv_launch<double>(P, bR, nchunks, cpc, gpart);
+    hipLaunchKernelGGL(k_wgr_efinish, dim3((n + 255) / 256), dim3(256), 0, P->stream, gpart, P->data->ld, nchunks, n, yd, eR, ws);
+    if (pk > 0) hipLaunchKernelGGL(k_uh, dim3((n + 255) / 256), dim3(256), 0, P->stream, Ud, hR, n, (int)pk, 1.0, eR, 1);   // - U %*% h
+    hipLaunchKernelGGL(k_wgr_mu, dim3(1), dim3(1024), 0, P->stream, eR, n, iv, accumulate, itx, rng, ws);
+    if (pk > 0 && accumulate) hipLaunchKernelGGL(k_wgr_accum_k, dim3(8), dim3(256), 0, P->stream, hR, Hk, (int)pk, ws);
+    HIPCHK(hipGetLastError());
+    if ((i & 63) == 0) HIPCHK(hipStreamSynchronize(P->stream));                  // bound the launch queue
   }
-done:
-#undef WCHK
-  (void)hipStreamSynchronize(P->stream);
-  if (gpart) hipFree(gpart);
-  cleanup();
-  if (PU) bwgr_panel_destroy(PU);
-  if (PB) bwgr_panel_destroy(PB);
-  if (use_d) hipFree(use_d);
-  return rc;
+  hipLaunchKernelGGL(k_dsum_stage1, dim3(256), dim3(256), 0, P->stream, D, (int64_t)p, part1, 0);
+  hipLaunchKernelGGL(k_wgr_final, dim3(1), dim3(1024), 0, P->stream, B, D, VB, p, (double)mc, part1, iv, ws);
+  WgrScalars h; ChainScalars hc;
+  HIPCHK(hipMemcpyAsync(&h, ws, sizeof(h), hipMemcpyDeviceToHost, P->stream));
+  HIPCHK(hipMemcpyAsync(&hc, sc, sizeof(hc), hipMemcpyDeviceToHost, P->stream));
+  HIPCHK(hipStreamSynchronize(P->stream));
+  if (hc.error) return sweep_error(hc.error, "wgr");
+  const double B0 = h.B0 / mc;
+  gemv_launch<double>(P, B, nchunks, cpc, gpart);                                // HAT = B0 + gen0 %*% B, R/wgr.R:152
+  hipLaunchKernelGGL(k_hat64_finish, dim3((n + 255) / 256), dim3(256), 0, P->stream, gpart, P->data->ld, nchunks, n, B0, hatd);
+  if (pk > 0) {                                                                  // poly = U0 %*% H; HAT += poly, R/wgr.R:148-150
+    hipLaunchKernelGGL(k_uh, dim3((n + 255) / 256), dim3(256), 0, P->stream, Ud, Hk, n, (int)pk, 1.0 / (double)mc, uhd, 0);
+    hipLaunchKernelGGL(k_add_vec, dim3((n + 255) / 256), dim3(256), 0, P->stream, hatd, uhd, n);
+  }
+  HIPCHK(hipGetLastError());
+  if (mu) *mu = B0;
+  if (Ve) *Ve = h.VE / mc;
+  if (cxx) *cxx = h.cxx * bag;                                                   // mean(xx), xx = crossprod * bag
+  if (b) HIPCHK(d2h(P->stream, b, B, pd));
+  if (d) HIPCHK(d2h(P->stream, d, D, pd));
+  if (Vb) { if (iv) HIPCHK(d2h(P->stream, Vb, VB, pd)); else Vb[0] = h.VA / mc; }
+  if (hat) HIPCHK(d2h(P->stream, hat, hatd, sizeof(double) * n));
+  if (pk > 0 && u) HIPCHK(d2h(P->stream, u, uhd, sizeof(double) * n));
+  if (pk > 0 && Vk) *Vk = h.VP / mc;
+  return BWGR_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3100,12 +3074,12 @@ extern "C" int bwgr_panel_centred(bwgr_panel *P, int *centred) {
   if (!P || !centred) return fail(BWGR_EINVAL, "null pointer");
   if (P->data->cen) { *centred = 1; return BWGR_OK; }   // implicitly centred: exactly
   HIPCHK(hipSetDevice(P->data->device));
-  int *flag = nullptr, h = 0;
-  HIPCHK(hipMalloc(&flag, sizeof(int)));
+  DevBufs bufs;
+  int *flag = bufs.get<int>(1), h = 0;
+  if (!flag) return fail(BWGR_ENOMEM, "panel_centred: device allocation failed");
   HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), P->stream));
   hipLaunchKernelGGL(k_uncentred, dim3(256), dim3(256), 0, P->stream, P->data->xx, P->data->vx, P->data->p, (double)P->data->n, flag);
   HIPCHK(d2h(P->stream, &h, flag, sizeof(int)));
-  HIPCHK(hipFree(flag));
   *centred = h ? 0 : 1;
   return BWGR_OK;
 }
@@ -3134,42 +3108,39 @@ static int group_create_impl(bwgr_group **out, int ndev, const int *devices, con
   Gp->dev.assign(devices, devices + ndev);
   Gp->same_dev = ndev > 1 && std::all_of(devices, devices + ndev, [&](int d) { return d == devices[0]; });
   Gp->P.assign(ndev, nullptr); Gp->C.assign(ndev, nullptr); Gp->delta.assign(ndev, nullptr); Gp->sums.assign(ndev, nullptr);
-  auto bail = [&](int code) { bwgr_group_destroy(Gp); return code; };
+  Guard drop([&] { bwgr_group_destroy(Gp); });
   const size_t esz = (xtype == BWGR_X_I8) ? 1 : (xtype == BWGR_X_F32 ? 4 : 8);
   double msx = 0.0;
   for (int g = 0; g < ndev; ++g) {
     const int64_t lo = std::min<int64_t>(p, (int64_t)g * per * m), hi = std::min<int64_t>(p, (int64_t)(g + 1) * per * m);
     Gp->lo.push_back(lo); Gp->hi.push_back(hi);
-    int rc = bwgr_panel_create(&Gp->P[g], reinterpret_cast<const unsigned char *>(X) + (size_t)lo * (size_t)ldx * esz, xtype, memloc, n, hi - lo, ldx, devices[g], m, 0);
-    if (rc != BWGR_OK) return bail(rc);
+    CHK(bwgr_panel_create(&Gp->P[g], reinterpret_cast<const unsigned char *>(X) + (size_t)lo * (size_t)ldx * esz, xtype, memloc, n, hi - lo, ldx, devices[g], m, 0));
     if (Gp->same_dev) {   // shards of one device: each on a stream of its own; from three shards on, 256-row streamers (K3 + 1 units a shard instead of 2 K3 + 2)
       hipStream_t q = nullptr;
-      if (hipStreamCreateWithFlags(&q, hipStreamNonBlocking) != hipSuccess) return bail(fail(BWGR_EHIP, "group_create: hipStreamCreate failed"));
+      if (hipStreamCreateWithFlags(&q, hipStreamNonBlocking) != hipSuccess) return fail(BWGR_EHIP, "group_create: hipStreamCreate failed");
       Gp->streams.push_back(q);
       Gp->P[g]->stream = q;
       if (ndev > 2 && Gp->P[g]->data->sw.solo3 < 0) Gp->P[g]->data->solo3 = false;   // (an explicit BWGR_SOLO3 decides otherwise: experiments)
     }
-    if (centre) { rc = bwgr_panel_set_centred(Gp->P[g], 1); if (rc != BWGR_OK) return bail(rc); }   // the shard's own column means (rows are not sharded)
+    if (centre) CHK(bwgr_panel_set_centred(Gp->P[g], 1));   // the shard's own column means (rows are not sharded)
     msx += (double)Gp->P[g]->data->MSx;
     int cen = 1;
-    rc = bwgr_panel_centred(Gp->P[g], &cen);
-    if (rc != BWGR_OK) return bail(rc);
+    CHK(bwgr_panel_centred(Gp->P[g], &cen));
     if (!cen) Gp->centred = false;
   }
   Gp->MSx_total = (float)msx;
   if (ndev > 1 && !Gp->centred) {
     if (!Gp->P[0]->data->sw.group_allow_uncentred)
-      return bail(fail(BWGR_EINVAL, "group_create: the columns of X are not centred, and on uncentred columns the marker-sharded sampler of %d devices is "
-                                    "statistically unsound (every shard corrects the same stale residual mean: DESIGN.md section 8).  Pass centred columns "
-                                    "(x_j - mean(x_j), float: the posterior of b and hat is the same under the sampler's flat intercept prior), use one "
-                                    "device, or set BWGR_GROUP_ALLOW_UNCENTRED=1 to run it knowingly", ndev));
+      return fail(BWGR_EINVAL, "group_create: the columns of X are not centred, and on uncentred columns the marker-sharded sampler of %d devices is "
+                               "statistically unsound (every shard corrects the same stale residual mean: DESIGN.md section 8).  Pass centred columns "
+                               "(x_j - mean(x_j), float: the posterior of b and hat is the same under the sampler's flat intercept prior), use one "
+                               "device, or set BWGR_GROUP_ALLOW_UNCENTRED=1 to run it knowingly", ndev);
   }
   for (int g = 0; g < ndev; ++g) {
-    int rc = bwgr_chain_create_sharded(&Gp->C[g], Gp->P[g], model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode, Gp->lo[g], p, Gp->MSx_total, nullptr);
-    if (rc != BWGR_OK) return bail(rc);
+    CHK(bwgr_chain_create_sharded(&Gp->C[g], Gp->P[g], model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode, Gp->lo[g], p, Gp->MSx_total, nullptr));
     if (hipSetDevice(devices[g]) != hipSuccess || hipMalloc(&Gp->delta[g], sizeof(double) * (size_t)Gp->P[g]->data->ld) != hipSuccess ||
-        hipMalloc(&Gp->sums[g], sizeof(double) * 2) != hipSuccess) return bail(fail(BWGR_ENOMEM, "group_create: device allocation failed"));
-    if (Gp->P[g]->data->ld != Gp->P[0]->data->ld) return bail(fail(BWGR_EINVAL, "group_create: shards disagree on the padded row count"));
+        hipMalloc(&Gp->sums[g], sizeof(double) * 2) != hipSuccess) return fail(BWGR_ENOMEM, "group_create: device allocation failed");
+    if (Gp->P[g]->data->ld != Gp->P[0]->data->ld) return fail(BWGR_EINVAL, "group_create: shards disagree on the padded row count");
   }
   // (shards side by side exchange through one kernel on the same card, not a ring over xGMI, but every exchange is a launch boundary for all of
   // them: 131072 markers per shard between two exchanges there)
@@ -3180,21 +3151,21 @@ static int group_create_impl(bwgr_group **out, int ndev, const int *devices, con
   Gp->rounds = (int)((nbmax + Gp->bps - 1) / Gp->bps);
   Gp->use_comm = (ndev > 1 && !Gp->same_dev) || (Gp->P[0]->data->sw.group_force_comm && !Gp->same_dev);   // (BWGR_GROUP_FORCE_COMM=1, tests: exercise the RCCL path with a single device)
   if (Gp->same_dev) {
-    if (hipSetDevice(devices[0]) != hipSuccess) return bail(fail(BWGR_EHIP, "group_create: hipSetDevice failed"));
+    if (hipSetDevice(devices[0]) != hipSuccess) return fail(BWGR_EHIP, "group_create: hipSetDevice failed");
     Gp->ev_sweep.assign(ndev, nullptr);
-    for (int g = 0; g < ndev; ++g) if (hipEventCreateWithFlags(&Gp->ev_sweep[g], hipEventDisableTiming) != hipSuccess) return bail(fail(BWGR_EHIP, "group_create: hipEventCreate failed"));
+    for (int g = 0; g < ndev; ++g) if (hipEventCreateWithFlags(&Gp->ev_sweep[g], hipEventDisableTiming) != hipSuccess) return fail(BWGR_EHIP, "group_create: hipEventCreate failed");
     for (int k = 0; k < 2; ++k) {
       if (hipEventCreateWithFlags(&Gp->ev_sum[k], hipEventDisableTiming) != hipSuccess || hipMalloc(&Gp->total[k], sizeof(double) * (size_t)Gp->P[0]->data->ld) != hipSuccess ||
-          hipMalloc(&Gp->total_sums[k], sizeof(double) * 2) != hipSuccess) return bail(fail(BWGR_ENOMEM, "group_create: device allocation failed"));
+          hipMalloc(&Gp->total_sums[k], sizeof(double) * 2) != hipSuccess) return fail(BWGR_ENOMEM, "group_create: device allocation failed");
     }
   }
   if (Gp->use_comm) {
-    int rc = rccl_load();
-    if (rc != BWGR_OK) return bail(rc);
+    CHK(rccl_load());
     Gp->comm.assign(ndev, nullptr);
     const int nr = g_rccl.CommInitAll(Gp->comm.data(), ndev, devices);
-    if (nr != 0) return bail(fail(BWGR_EHIP, "group_create: ncclCommInitAll failed: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(nr) : "?"));
+    if (nr != 0) return fail(BWGR_EHIP, "group_create: ncclCommInitAll failed: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(nr) : "?");
   }
+  drop.release();
   *out = Gp;
   return BWGR_OK;
 }
@@ -3531,7 +3502,7 @@ extern "C" int bwgr_em_order(int64_t p, int upto, int32_t *order) {
 
 extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float R2, float par, const float *D, int maxit_in,
                        float *mu, float *b, float *d, float *hat, float *vbvec, float *scal, int *iters) {
-  if (P && P->data->cen) return fail(BWGR_EINVAL, "em: this panel sweeps implicitly centred columns (bwgr_panel_set_centred), which only the fused chains do; call bwgr_panel_set_centred(P, 0) first");
+  if (P && P->data->cen) return refuse_centred("em");
   if (!P || !y || !b || !scal) return fail(BWGR_EINVAL, "em: null pointer");
   if (model < BWGR_EM_RR || model > BWGR_EM_LASSO) return fail(BWGR_EINVAL, "em: bad model %d", model);
   if (D && model != BWGR_EM_ML) return fail(BWGR_EINVAL, "em: marker weights D belong to emML only");
@@ -3548,42 +3519,39 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
   hipStream_t st = P->stream;
   // scratch panel: same geometry, its own X and Gram; only the diagonal and distance-1 blocks are ever built (lag 2, 32-bit staging)
   bwgr_panel *Q = nullptr;
+  Guard drop([&] { bwgr_panel_destroy(Q); });
+  std::vector<int> order((size_t)p), order_next;   // (copied from asynchronously: declared before the holder, which waits for the stream)
+  DevBufs bufs(st);
   if (shuffled) {
     CHK(panel_alloc(&Q, P->data->is_f32, n, p, P->data->device, P->data->m, P->data->K, P->data->sw, true));
     Q->stream = st;
+    if (Q->data->K != P->data->K || Q->data->R != P->data->R || Q->data->m != P->data->m || std::min(Q->data->sweep_version, 2) != std::min(P->data->sweep_version, 2)) return fail(BWGR_EINVAL, "em: scratch panel geometry differs");
+    CHK(scratch_alloc(Q));
   }
-  std::vector<void *> owned;
-  int rc = BWGR_OK;
-  auto done = [&](int code) { (void)hipStreamSynchronize(st); for (void *q : owned) hipFree(q); if (Q) bwgr_panel_destroy(Q); return code; };
-#define ECHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return done(fail(BWGR_EHIP, "%s failed: %s", #x, hipGetErrorString(e_))); } while (0)
-  if (Q && (Q->data->K != P->data->K || Q->data->R != P->data->R || Q->data->m != P->data->m || std::min(Q->data->sweep_version, 2) != std::min(P->data->sweep_version, 2))) return done(fail(BWGR_EINVAL, "em: scratch panel geometry differs"));
-  if (Q && (rc = scratch_alloc(Q)) != BWGR_OK) return done(rc);
   bwgr_panel *S = Q ? Q : P;                                                          // the panel the sweeps run on
-  const size_t pb = sizeof(float) * (size_t)p;
-  float *yd = nullptr, *bd = nullptr, *bcd = nullptr, *dd = nullptr, *lamd = nullptr, *vbd = nullptr, *xxd = nullptr, *Dd = nullptr;
-  float *bq = nullptr, *xxq = nullptr, *lamq = nullptr, *dq = nullptr, *vq = nullptr, *hatd = nullptr;
-  double *ed = nullptr; int32_t *ordd = nullptr; EmState *std_ = nullptr; ChainScalars *sc = nullptr;
-  auto dmalloc = [&](void **q, size_t bytes) { hipError_t e_ = hipMalloc(q, bytes); if (e_ == hipSuccess) owned.push_back(*q); return e_; };
-  ECHK(dmalloc((void **)&yd, sizeof(float) * n)); ECHK(dmalloc((void **)&bd, pb)); ECHK(dmalloc((void **)&bcd, pb)); ECHK(dmalloc((void **)&dd, pb));
-  ECHK(dmalloc((void **)&lamd, pb)); ECHK(dmalloc((void **)&vbd, pb)); ECHK(dmalloc((void **)&xxd, pb));
-  ECHK(dmalloc((void **)&bq, pb)); ECHK(dmalloc((void **)&xxq, pb)); ECHK(dmalloc((void **)&lamq, pb)); ECHK(dmalloc((void **)&dq, pb)); ECHK(dmalloc((void **)&vq, pb));
-  ECHK(dmalloc((void **)&ed, sizeof(double) * P->data->ld)); ECHK(dmalloc((void **)&ordd, sizeof(int32_t) * p));
-  ECHK(dmalloc((void **)&std_, sizeof(EmState))); ECHK(dmalloc((void **)&sc, sizeof(ChainScalars)));
-  ECHK(dmalloc((void **)&hatd, sizeof(float) * n));
-  if (D) { ECHK(dmalloc((void **)&Dd, pb)); ECHK(hipMemcpyAsync(Dd, D, pb, hipMemcpyHostToDevice, st)); }
-  ECHK(hipMemcpyAsync(yd, y, sizeof(float) * n, hipMemcpyHostToDevice, st));
-  ECHK(hipMemsetAsync(bd, 0, pb, st)); ECHK(hipMemsetAsync(dd, 0, pb, st));
-  ECHK(hipMemcpyAsync(xxd, P->data->xx, pb, hipMemcpyDeviceToDevice, st));
+  const size_t np = (size_t)p, pb = sizeof(float) * np;
+  float *yd = bufs.get<float>((size_t)n), *bd = bufs.get<float>(np), *bcd = bufs.get<float>(np), *dd = bufs.get<float>(np);
+  float *lamd = bufs.get<float>(np), *vbd = bufs.get<float>(np), *xxd = bufs.get<float>(np);
+  float *bq = bufs.get<float>(np), *xxq = bufs.get<float>(np), *lamq = bufs.get<float>(np), *dq = bufs.get<float>(np), *vq = bufs.get<float>(np);
+  double *ed = bufs.get<double>((size_t)P->data->ld); int32_t *ordd = bufs.get<int32_t>(np);
+  EmState *std_ = bufs.get<EmState>(1); ChainScalars *sc = bufs.get<ChainScalars>(1);
+  float *hatd = bufs.get<float>((size_t)n), *Dd = D ? bufs.get<float>(np) : nullptr;
+  if (!yd || !bd || !bcd || !dd || !lamd || !vbd || !xxd || !bq || !xxq || !lamq || !dq || !vq || !ed || !ordd || !std_ || !sc || !hatd || (D && !Dd))
+    return fail(BWGR_ENOMEM, "em: device allocation failed");
+  if (D) HIPCHK(hipMemcpyAsync(Dd, D, pb, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(yd, y, sizeof(float) * n, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(bd, 0, pb, st)); HIPCHK(hipMemsetAsync(dd, 0, pb, st));
+  HIPCHK(hipMemcpyAsync(xxd, P->data->xx, pb, hipMemcpyDeviceToDevice, st));
   // vy = fvar(y) with the library's reduction (float result of fp64 sums, like the fused samplers' setup)
   float vy = 0;
   {
     InitArgs ia; memset(&ia, 0, sizeof(ia));
     ChainScalars h0; memset(&h0, 0, sizeof(h0));
-    ECHK(hipMemcpyAsync(sc, &h0, sizeof(h0), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sc, &h0, sizeof(h0), hipMemcpyHostToDevice, st));
     ia.y = yd; ia.e = ed; ia.n = (int)n; ia.p = (int)p; ia.ld = P->data->ld; ia.model = BWGR_BAYESRR; ia.pi = 0; ia.df = df; ia.R2 = R2; ia.MSx = P->data->MSx; ia.sc = sc;
     hipLaunchKernelGGL(k_chain_init, dim3(1), dim3(1024), 0, st, ia);
-    ECHK(hipGetLastError());
-    ECHK(d2h(st, &h0, sc, sizeof(h0)));
+    HIPCHK(hipGetLastError());
+    HIPCHK(d2h(st, &h0, sc, sizeof(h0)));
     vy = h0.vy;
   }
   const float sumvx = P->data->MSx;                                                        // vx.sum()
@@ -3600,7 +3568,7 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
     }
     h.Sb = R2 * (df + 2) * vy / h.MSx;                                               // :96, :148
     h.Se = (1 - R2) * (df + 2) * vy;                                                 // :97, :149
-    ECHK(fill(lamd, 1.0f)); ECHK(fill(vbd, 1.0f));                                   // vb = 1, Lmb = ve * vb^-1 = 1, :87-88
+    HIPCHK(fill(lamd, 1.0f)); HIPCHK(fill(vbd, 1.0f));                               // vb = 1, Lmb = ve * vb^-1 = 1, :87-88
   } else if (model == BWGR_EM_RR) {
     h.Lmb = sumvx;                                                                   // :319
     h.Rho = sumvx * (1 - R2) / R2;                                                   // :320
@@ -3611,7 +3579,7 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
   } else if (model == BWGR_EM_DE) {
     hipLaunchKernelGGL(k_em_fix_xx, dim3(1024), dim3(256), 0, st, xxd, p);           // :261
     h.cxx = sumvx * (1 - R2) / R2;                                                   // :265
-    ECHK(fill(lamd, (float)p + h.cxx));                                              // :269
+    HIPCHK(fill(lamd, (float)p + h.cxx));                                            // :269
   } else if (model == BWGR_EM_ML) {
     h.Lmb = sumvx;                                                                   // :486
   } else if (model == BWGR_EM_BC || model == BWGR_EM_BCPI) {
@@ -3624,7 +3592,7 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
     h.Pi0 = (1 - Pi) / Pi;                                                           // :213
   } else if (model == BWGR_EM_BL || model == BWGR_EM_EN || lasso) {
     xxh.resize((size_t)p);
-    ECHK(d2h(st, xxh.data(), xxd, pb));
+    HIPCHK(d2h(st, xxh.data(), xxd, pb));
     h.alpha = par;
     if (lasso) {
       double sx = 0; for (int64_t j = 0; j < p; ++j) sx += (double)xxh[(size_t)j];
@@ -3645,20 +3613,19 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
       h.trAC22 = tr;
     }
   }
-  ECHK(hipMemcpyAsync(std_, &h, sizeof(h), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(std_, &h, sizeof(h), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_em_init, dim3(1), dim3(1024), 0, st, yd, ed, (int)n, P->data->ld, std_);   // mu, e (overwrites k_chain_init's e)
-  ECHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   {
     ChainScalars h0; memset(&h0, 0, sizeof(h0));
     h0.ve = 1.0f; h0.pi = 0.0f; h0.dfp1 = 1.0f;                                      // the sweep's variates are switched off
     h0.C = -0.5f / sqrtf(h.ve);                                                      // :157, :216, :1522
     h0.odds = h.Pi0; h0.lam = h.Lmb1; h0.Sb = h.cxx;                                 // Pi0; Lmb1; emBL's cxx (k_prestage)
-    ECHK(hipMemcpyAsync(sc, &h0, sizeof(h0), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sc, &h0, sizeof(h0), hipMemcpyHostToDevice, st));
   }
-  std::vector<int> order((size_t)p), order_next;
   for (int64_t j = 0; j < p; ++j) order[(size_t)j] = (int)j;
   if (shuffled) std::shuffle(order.begin(), order.end(), std::mt19937(0));            // sweep 0's order
-  if (!shuffled) ECHK(hipMemcpyAsync(ordd, order.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice, st));
+  if (!shuffled) HIPCHK(hipMemcpyAsync(ordd, order.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice, st));
   const int cps = (int)((size_t)P->data->R * (P->data->is_f32 ? 4 : 1) / 16);
   uint32_t flags = SWF_LAM_VEC;
   if (model == BWGR_EM_BA) flags |= SWF_DELTA2;
@@ -3675,50 +3642,46 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
       // order = sweep i's marker order.  std::shuffle(order.begin(), order.end(), std::mt19937(i)) -- :103, :277, :331, :491 ...,
       // the reference's own call -- was made for sweep 0 before the loop and is made for sweep i+1 below, while the GPU
       // runs sweep i (10-15 ms of host time per sweep at p = 10^6)
-      ECHK(hipMemcpyAsync(ordd, order.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(ordd, order.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)P->data->X, (uint4 *)Q->data->X, ordd, p, P->data->K, cps);
     }
-    if (conv) ECHK(hipMemcpyAsync(bcd, bd, pb, hipMemcpyDeviceToDevice, st));        // bc = b
+    if (conv) HIPCHK(hipMemcpyAsync(bcd, bd, pb, hipMemcpyDeviceToDevice, st));      // bc = b
     hipLaunchKernelGGL(k_em_stage, dim3(1024), dim3(256), 0, st, ordd, p, model, D ? 1 : 0, bd, xxd, lamd, Dd, std_, bq, xxq, lamq);
-    ECHK(hipGetLastError());
-    if (shuffled) {
-      rc = panel_build_gram(Q);
-      if (rc != BWGR_OK) return done(rc);
-    }
+    HIPCHK(hipGetLastError());
+    if (shuffled) CHK(panel_build_gram(Q));
     SweepArgs a; memset(&a, 0, sizeof(a));
     fill_panel_args(S, a);
     a.flags = flags;
     a.e = ed; a.b = bq; a.d = dq; a.vb = vq; a.xx = xxq; a.lam = lamq; a.sc = sc;
     a.iter = (uint32_t)i; a.rng = make_rng(0, BWGR_RNG_DEGENERATE);
-    rc = launch_sweep(S, a);
-    if (rc != BWGR_OK) return done(rc);
+    CHK(launch_sweep(S, a));
     hipLaunchKernelGGL(k_em_unstage, dim3(1024), dim3(256), 0, st, ordd, p, bq, bd, (soft || lasso) ? dq : nullptr, (soft || lasso) ? dd : nullptr);
     EmTailArgs t; t.model = model; t.n = (int)n; t.conv = conv ? 1 : 0; t.p = p; t.e = ed; t.y = yd; t.b = bd; t.bc = bcd; t.d = dd;
     t.lam = lamd; t.vbv = vbd; t.xx = xxd; t.st = std_; t.sc = sc;
     hipLaunchKernelGGL(k_em_tail, dim3(1), dim3(1024), 0, st, t);
-    ECHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     ++numit;
     const double t_1 = now();
     if (shuffled && i + 1 < maxit) { order_next = order; std::shuffle(order_next.begin(), order_next.end(), std::mt19937(i + 1)); }
     const double t_2 = now();
     // the convergence test needs cnv (and the sweep's status word)
     ChainScalars hc;
-    ECHK(hipMemcpyAsync(&h, std_, sizeof(h), hipMemcpyDeviceToHost, st));
-    ECHK(hipMemcpyAsync(&hc, sc, sizeof(hc), hipMemcpyDeviceToHost, st));
-    ECHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(&h, std_, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&hc, sc, sizeof(hc), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     if (emdbg) fprintf(stderr, "em sweep %d: launches %.2f ms, host shuffle %.2f ms, wait %.2f ms\n", i, t_1 - t_0, t_2 - t_1, now() - t_2);
-    if (hc.error) return done(sweep_error(hc.error, "em"));
+    if (hc.error) return sweep_error(hc.error, "em");
     if (lasso) {   // Lmb from the sweep's yx and b: the reference's own sequential float loop, :1487-1490
       yxh.resize((size_t)p); bh.resize((size_t)p);
-      ECHK(d2h(st, yxh.data(), dd, pb)); ECHK(d2h(st, bh.data(), bd, pb));
+      HIPCHK(d2h(st, yxh.data(), dd, pb)); HIPCHK(d2h(st, bh.data(), bd, pb));
       float tmp = 0.0f;
       for (int64_t j = 0; j < p; ++j) tmp += fabsf(yxh[(size_t)j]) - fabsf(bh[(size_t)j] * xxh[(size_t)j]);
       float L = 2.0f * tmp / (float)p;
       L = 2.0f * sqrtf(fabsf(L));
       h.Lmb1 = L;
-      ECHK(hipMemcpyAsync(std_, &h, sizeof(h), hipMemcpyHostToDevice, st));
-      ECHK(hipMemcpyAsync(&sc->lam, &h.Lmb1, sizeof(float), hipMemcpyHostToDevice, st));
-      ECHK(hipStreamSynchronize(st));
+      HIPCHK(hipMemcpyAsync(std_, &h, sizeof(h), hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(&sc->lam, &h.Lmb1, sizeof(float), hipMemcpyHostToDevice, st));
+      HIPCHK(hipStreamSynchronize(st));
     }
     if (conv && h.cnv < tol) break;                                                  // :296, :452, :510, :1492
     if (shuffled) order.swap(order_next);
@@ -3730,22 +3693,19 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
   } else if (lasso) {
     hipLaunchKernelGGL(k_em_fit_ml, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, yd, ed, hatd, (int)n);   // fit = y - e, :1493
     std::vector<double> eh((size_t)n);
-    ECHK(d2h(st, eh.data(), ed, sizeof(double) * n));
+    HIPCHK(d2h(st, eh.data(), ed, sizeof(double) * n));
     double s = 0; for (int64_t k = 0; k < n; ++k) s = fma(eh[(size_t)k], (double)y[k], s);
     h2 = 1.0f - ((float)s / (float)(n - 1)) / vy;                                    // :1494
   } else {
-    rc = gemv_hat<float>(P, bd, h.mu, hatd);                                         // fit = gen*b + mu, :120-121
-    if (rc != BWGR_OK) return done(rc);
+    CHK(gemv_hat<float>(P, bd, h.mu, hatd, "em"));                                   // fit = gen*b + mu, :120-121
     if (model == BWGR_EM_DE) {                                                       // h2 = Vb.sum()/(Vb.sum()+Ve), :304
-      double *part = nullptr; float *sdev = nullptr; float sv = 0;
-      ECHK(dmalloc((void **)&part, sizeof(double) * 256)); ECHK(dmalloc((void **)&sdev, sizeof(float)));
-      hipLaunchKernelGGL(k_sum_stage1, dim3(256), dim3(256), 0, st, vbd, p, part);
-      hipLaunchKernelGGL(k_sum_stage2, dim3(1), dim3(256), 0, st, part, 256, sdev);
-      ECHK(d2h(st, &sv, sdev, sizeof(float)));
+      double *part = bufs.get<double>(256); float *sdev = bufs.get<float>(1); float sv = 0;
+      if (!part || !sdev) return fail(BWGR_ENOMEM, "em: device allocation failed");
+      CHK(sum_floats(st, vbd, p, part, sdev, &sv));
       h2 = sv / (sv + h.ve);
     } else if (model == BWGR_EM_BL) {                                                // h2 = 1 - fvar(e)/fvar(y), :396
       std::vector<double> eh((size_t)n);
-      ECHK(d2h(st, eh.data(), ed, sizeof(double) * n));
+      HIPCHK(d2h(st, eh.data(), ed, sizeof(double) * n));
       double s = 0; for (int64_t k = 0; k < n; ++k) s += (double)(float)eh[(size_t)k];
       const float m = (float)(s / (double)n);
       double sv = 0; for (int64_t k = 0; k < n; ++k) { const float dev = (float)eh[(size_t)k] - m; const float sq = dev * dev; sv += (double)sq; }
@@ -3753,12 +3713,12 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
     } else if (model == BWGR_EM_EN) h2 = h.va * h.cxx / (h.va * h.cxx + h.ve);       // :459
     else h2 = 1 - h.ve / vy;                                                         // :119, :178, :237, :344, :1542
   }
-  ECHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   if (mu) *mu = h.mu;
-  ECHK(d2h(st, b, bd, pb));
-  if (d && soft) ECHK(d2h(st, d, dd, pb));
-  if (hat) ECHK(d2h(st, hat, hatd, sizeof(float) * n));
-  if (vbvec && (model == BWGR_EM_BA || model == BWGR_EM_DE || model == BWGR_EM_BB)) ECHK(d2h(st, vbvec, vbd, pb));
+  HIPCHK(d2h(st, b, bd, pb));
+  if (d && soft) HIPCHK(d2h(st, d, dd, pb));
+  if (hat) HIPCHK(d2h(st, hat, hatd, sizeof(float) * n));
+  if (vbvec && (model == BWGR_EM_BA || model == BWGR_EM_DE || model == BWGR_EM_BB)) HIPCHK(d2h(st, vbvec, vbd, pb));
   for (int k = 0; k < 6; ++k) scal[k] = 0.0f;
   scal[1] = h.ve; scal[2] = h2;
   if (model == BWGR_EM_RR || model == BWGR_EM_ML) scal[0] = h.vb;
@@ -3769,8 +3729,7 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
   if (model == BWGR_EM_BL) scal[1] = 0.0f;
   if (lasso) { scal[0] = h.Lmb1; scal[1] = 0.0f; }                                   // Lmb, :1497
   if (iters) *iters = numit;
-#undef ECHK
-  return done(BWGR_OK);
+  return BWGR_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3877,46 +3836,38 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   for (int t = 0; t < k; ++t) vy[t] /= (nt[t] - 1.0);                                                     // iN = 1/(n-1), :781-782
 
   hipStream_t st = P->stream;
-  std::vector<void *> owned;
-  auto done = [&](int code) { (void)hipStreamSynchronize(st); for (void *q : owned) hipFree(q); return code; };
-#define MCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return done(fail(BWGR_EHIP, "%s failed: %s", #x, hipGetErrorString(e_))); } while (0)
-  auto dmalloc = [&](void **q, size_t bytes) { hipError_t e_ = hipMalloc(q, bytes); if (e_ == hipSuccess) owned.push_back(*q); return e_; };
+  std::vector<int> order((size_t)p);
+  std::vector<double> iG((size_t)k * k, 0.0), d(k), off(k);   // (these four are copied from asynchronously: declared before the holder, which waits for the stream)
+  DevBufs bufs(st);
   const int64_t nblk = (p + MRR_MB - 1) / MRR_MB, ntiles = ld / 64;
   const int G = (int)std::min<int64_t>(ntiles, MRR_PASS_WG);
   const int NP = 64;                                   // partials of the tail reductions
   const int nch = (int)std::min<int64_t>(64, p);       // marker chunks of the fitted values
   const int64_t cpc = (p + nch - 1) / nch;
-  int8_t *Xs = nullptr; uint32_t *zbd = nullptr, *ztd = nullptr; uint8_t *zmd = nullptr; int32_t *ordd = nullptr, *gram = nullptr;
-  double *yd = nullptr, *ed = nullptr, *xbar = nullptr, *Sd = nullptr, *XXd = nullptr, *XSXd = nullptr, *tilde = nullptr, *bd = nullptr, *Linv = nullptr;
-  double *part = nullptr, *dB = nullptr, *db2 = nullptr, *small = nullptr, *tpart = nullptr, *sumyd = nullptr, *hpart = nullptr, *hatd = nullptr;
-  MCHK(dmalloc((void **)&Xs, P->data->x_bytes));
-  MCHK(dmalloc((void **)&zbd, sizeof(uint32_t) * ld)); MCHK(dmalloc((void **)&ztd, sizeof(uint32_t) * ld));
-  MCHK(dmalloc((void **)&zmd, (size_t)npat * ld));
-  MCHK(dmalloc((void **)&ordd, sizeof(int32_t) * p));
-  MCHK(dmalloc((void **)&gram, sizeof(int32_t) * (size_t)nblk * npat * MRR_MB * MRR_MB));
-  MCHK(dmalloc((void **)&yd, sizeof(double) * k * ld)); MCHK(dmalloc((void **)&ed, sizeof(double) * k * ld));
-  MCHK(dmalloc((void **)&xbar, sizeof(double) * p)); MCHK(dmalloc((void **)&Sd, sizeof(double) * npat * p));
-  MCHK(dmalloc((void **)&XXd, sizeof(double) * p * k)); MCHK(dmalloc((void **)&XSXd, sizeof(double) * p * k));
-  MCHK(dmalloc((void **)&tilde, sizeof(double) * p * k)); MCHK(dmalloc((void **)&bd, sizeof(double) * p * k));
-  MCHK(dmalloc((void **)&Linv, sizeof(double) * p * k * k));
-  MCHK(dmalloc((void **)&part, sizeof(double) * G * (MRR_MB + 1) * MRR_KMAX));
-  MCHK(dmalloc((void **)&dB, sizeof(double) * (MRR_MB * MRR_KMAX + MRR_KMAX)));
-  MCHK(dmalloc((void **)&db2, sizeof(double) * MRR_KMAX));
-  MCHK(dmalloc((void **)&small, sizeof(double) * 1024));            // [0, 512): reduction results; [512, 768): iG; [768, ...): mu shift
-  MCHK(dmalloc((void **)&tpart, sizeof(double) * NP * (MRR_KMAX * MRR_KMAX + MRR_KMAX)));
-  MCHK(dmalloc((void **)&sumyd, sizeof(double) * MRR_KMAX));
-  MCHK(hipMemcpyAsync(zbd, zb.data(), sizeof(uint32_t) * ld, hipMemcpyHostToDevice, st));
-  MCHK(hipMemcpyAsync(ztd, zt.data(), sizeof(uint32_t) * ld, hipMemcpyHostToDevice, st));
-  MCHK(hipMemcpyAsync(zmd, zm.data(), (size_t)npat * ld, hipMemcpyHostToDevice, st));
-  MCHK(hipMemcpyAsync(yd, y.data(), sizeof(double) * k * ld, hipMemcpyHostToDevice, st));
-  MCHK(hipMemcpyAsync(ed, y.data(), sizeof(double) * k * ld, hipMemcpyHostToDevice, st));          // e = y, :825
-  MCHK(hipMemcpyAsync(sumyd, sumy.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
-  MCHK(hipMemsetAsync(bd, 0, sizeof(double) * p * k, st));                                         // b = 0, :823
-  MCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_linv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
-  MCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
+  const size_t np = (size_t)p, nl = (size_t)ld, pk = np * k;
+  int8_t *Xs = bufs.get<int8_t>(P->data->x_bytes);
+  uint32_t *zbd = bufs.get<uint32_t>(nl), *ztd = bufs.get<uint32_t>(nl);
+  uint8_t *zmd = bufs.get<uint8_t>((size_t)npat * nl);
+  int32_t *ordd = bufs.get<int32_t>(np), *gram = bufs.get<int32_t>((size_t)nblk * npat * MRR_MB * MRR_MB);
+  double *yd = bufs.get<double>(k * nl), *ed = bufs.get<double>(k * nl), *xbar = bufs.get<double>(np), *Sd = bufs.get<double>(npat * np);
+  double *XXd = bufs.get<double>(pk), *XSXd = bufs.get<double>(pk), *tilde = bufs.get<double>(pk), *bd = bufs.get<double>(pk), *Linv = bufs.get<double>(pk * k);
+  double *part = bufs.get<double>((size_t)G * (MRR_MB + 1) * MRR_KMAX), *dB = bufs.get<double>(MRR_MB * MRR_KMAX + MRR_KMAX), *db2 = bufs.get<double>(MRR_KMAX);
+  double *small = bufs.get<double>(1024);            // [0, 512): reduction results; [512, 768): iG; [768, ...): mu shift
+  double *tpart = bufs.get<double>((size_t)NP * (MRR_KMAX * MRR_KMAX + MRR_KMAX)), *sumyd = bufs.get<double>(MRR_KMAX);
+  if (!Xs || !zbd || !ztd || !zmd || !ordd || !gram || !yd || !ed || !xbar || !Sd || !XXd || !XSXd || !tilde || !bd || !Linv || !part || !dB || !db2 || !small || !tpart || !sumyd)
+    return fail(BWGR_ENOMEM, "mrr: device allocation failed");
+  HIPCHK(hipMemcpyAsync(zbd, zb.data(), sizeof(uint32_t) * ld, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(ztd, zt.data(), sizeof(uint32_t) * ld, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(zmd, zm.data(), (size_t)npat * ld, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(yd, y.data(), sizeof(double) * k * ld, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(ed, y.data(), sizeof(double) * k * ld, hipMemcpyHostToDevice, st));        // e = y, :825
+  HIPCHK(hipMemcpyAsync(sumyd, sumy.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(bd, 0, sizeof(double) * p * k, st));                                       // b = 0, :823
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_linv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
   hipLaunchKernelGGL(k_mrr_setup_cols, dim3((unsigned)std::min<int64_t>((p + 3) / 4, 8192)), dim3(256), 0, st, (const int8_t *)P->data->X, R, (int)n, p, ld,
                      (const uint32_t *)zbd, (const double *)yd, (const double *)sumyd, mc, xbar, Sd, XXd, XSXd, tilde);
-  MCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   // a reduction over p of the k^2 (+k) products, partials in a fixed order
   auto reduce_pk = [&](int mode, int nout, const double *iGd, std::vector<double> &out) -> hipError_t {
     hipLaunchKernelGGL(k_mrr_tilde, dim3(NP, nout), dim3(256), 0, st, (const double *)bd, (const double *)tilde, (const double *)XSXd, p, mode, mc, iGd, tpart);
@@ -3927,10 +3878,10 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
     return d2h(st, out.data(), small, sizeof(double) * nout);
   };
   std::vector<double> MSx;
-  MCHK(reduce_pk(2, k, nullptr, MSx));                                                             // MSx = colSums(XSX), :777
+  HIPCHK(reduce_pk(2, k, nullptr, MSx));                                                           // MSx = colSums(XSX), :777
   // ---- start values (:784-816) ----
   std::vector<double> ve(k), vbInit(k), veInit(k), h2(k), TrXSX(k), Se(k), iNp(k), iN(k);
-  std::vector<double> vb((size_t)k * k, 0.0), iG((size_t)k * k, 0.0), Sb((size_t)k * k), GC((size_t)k * k, 0.0), TH_((size_t)k * k), Tr(k);
+  std::vector<double> vb((size_t)k * k, 0.0), Sb((size_t)k * k), GC((size_t)k * k, 0.0), TH_((size_t)k * k), Tr(k);
   for (int t = 0; t < k; ++t) {
     TrXSX[t] = nt[t] * MSx[t];                                                                     // :778
     ve[t] = vy[t] * (1 - o.R2); veInit[t] = ve[t];                                                 // :784, :788
@@ -3943,24 +3894,23 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   for (int i = 0; i < k * k; ++i) Sb[i] = vb[i] * o.df0;                                           // :816
   for (int i = 0; i < k * k; ++i) GC[i] = vb[i];
   // ---- iterations ----
-  std::vector<int> order((size_t)p);
   for (int64_t j = 0; j < p; ++j) order[(size_t)j] = (int)j;
   const int cps = (int)((size_t)R / 16);
   const double logtol = log10(o.tol);
-  std::vector<double> ey, db2h(k), vb0, h20, d(k);
+  std::vector<double> ey, db2h(k), vb0, h20;
   int numit = 0;
   const MrrPlan plan = mrr_plan(k, npat);
   while (numit < o.maxit) {
     vb0 = vb; h20 = h2;
     std::shuffle(order.begin(), order.end(), std::mt19937(numit));                                 // :869 (cumulative, as there)
-    MCHK(hipMemcpyAsync(ordd, order.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ordd, order.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)P->data->X, (uint4 *)Xs, (const int32_t *)ordd, p, P->data->K, cps);
     hipLaunchKernelGGL(k_mrr_gram, dim3((unsigned)nblk, (unsigned)((npat + 3) / 4)), dim3(256), 0, st, (const int8_t *)Xs, R, p, ld, (const uint8_t *)zmd, npat, gram);
     for (int t = 0; t < k; ++t) mc.iVe[t] = 1.0 / ve[t];
-    MCHK(hipMemcpyAsync(small + 512, iG.data(), sizeof(double) * k * k, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(small + 512, iG.data(), sizeof(double) * k * k, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_mrr_linv, dim3((unsigned)((p + 63) / 64)), dim3(64), plan.lds_linv, st, (const double *)XXd, (const double *)(small + 512), mc, p, Linv);
-    MCHK(hipMemsetAsync(db2, 0, sizeof(double) * MRR_KMAX, st));
-    MCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(db2, 0, sizeof(double) * MRR_KMAX, st));
+    HIPCHK(hipGetLastError());
     for (int64_t blk = 0; blk <= nblk; ++blk) {
       MrrPassArgs pa; pa.Xs = Xs; pa.R = R; pa.p = p; pa.ld = ld; pa.nblk = (int)nblk; pa.zb = ztd; pa.e = ed; pa.dB = dB; pa.part = part;
       pa.prev = blk > 0 ? (int)(blk - 1) : -1; pa.next = blk < nblk ? (int)blk : -1; pa.k = k;
@@ -3971,14 +3921,14 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
 
       hipLaunchKernelGGL(k_mrr_solve, dim3(1), dim3(256), plan.lds_solve, st, sa, mc);
     }
-    MCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     // residual variance (:916-924)
     hipLaunchKernelGGL(k_mrr_ey, dim3(NP, k), dim3(256), 0, st, (const double *)ed, (const double *)yd, ld, k, tpart);
     hipLaunchKernelGGL(k_mrr_finish, dim3(1), dim3(256), 0, st, (const double *)tpart, NP, 2 * k, small);
-    MCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     ey.resize(2 * k);
-    MCHK(d2h(st, ey.data(), small, sizeof(double) * 2 * k));
-    MCHK(d2h(st, db2h.data(), db2, sizeof(double) * k));
+    HIPCHK(d2h(st, ey.data(), small, sizeof(double) * 2 * k));
+    HIPCHK(d2h(st, db2h.data(), db2, sizeof(double) * k));
     for (int t = 0; t < k; ++t) {
       ve[t] = (ey[t] + Se[t]) * iNp[t];                                                            // :916-917
       h2[t] = 1 - ve[t] / vy[t];                                                                   // :918 (before the prior)
@@ -3989,11 +3939,11 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
     for (int t = 0; t < k; ++t) { mc.iVe[t] = 1.0 / ve[t]; d[t] = iG[t * k + t]; }
     std::vector<double> th;
     if (o.TH) {
-      MCHK(hipMemcpyAsync(small + 768, d.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
-      MCHK(reduce_pk(1, k * k + k, small + 768, th));
+      HIPCHK(hipMemcpyAsync(small + 768, d.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
+      HIPCHK(reduce_pk(1, k * k + k, small + 768, th));
       for (int t = 0; t < k; ++t) Tr[t] = th[k * k + t];
     } else {
-      MCHK(reduce_pk(0, k * k, nullptr, th));
+      HIPCHK(reduce_pk(0, k * k, nullptr, th));
       for (int t = 0; t < k; ++t) Tr[t] = TrXSX[t];
     }
     // th[s * k + t] = sum_j b_js tilde_jt = TildeHat(s, t)
@@ -4003,9 +3953,9 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
     if (bent && o.verbose) printf("Inflate (it=%d)\n", numit);
     if (o.updateMu) {                                                                              // :1030-1036
       for (int t = 0; t < k; ++t) { d[t] = ey[k + t] * iN[t]; mu[t] += d[t]; }
-      MCHK(hipMemcpyAsync(small + 768, d.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(small + 768, d.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(k_mrr_mu_shift, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st, ed, (const uint32_t *)ztd, ld, (int)n, k, (const double *)(small + 768));
-      MCHK(hipGetLastError());
+      HIPCHK(hipGetLastError());
     }
     double mx = -INFINITY;
     for (int t = 0; t < k; ++t) mx = std::max(mx, db2h[t]);
@@ -4023,18 +3973,19 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
     if (numit == o.maxit && o.verbose) printf("Model did not converge\n");
   }
   // ---- fitted values for every row, the missing ones included (:1054-1055) ----
-  std::vector<double> bh((size_t)p * k), xb((size_t)p), off(k);
-  MCHK(d2h(st, bh.data(), bd, sizeof(double) * p * k));
-  MCHK(d2h(st, xb.data(), xbar, sizeof(double) * p));
+  std::vector<double> bh((size_t)p * k), xb((size_t)p);
+  HIPCHK(d2h(st, bh.data(), bd, sizeof(double) * p * k));
+  HIPCHK(d2h(st, xb.data(), xbar, sizeof(double) * p));
   for (int t = 0; t < k; ++t) { double s = 0; for (int64_t j = 0; j < p; ++j) s += xb[(size_t)j] * bh[(size_t)j * k + t]; off[t] = mu[t] - s; }
   if (hat_out) {
-    MCHK(dmalloc((void **)&hpart, sizeof(double) * nch * k * ld)); MCHK(dmalloc((void **)&hatd, sizeof(double) * n * k));
-    MCHK(hipMemcpyAsync(small, off.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
+    double *hpart = bufs.get<double>((size_t)nch * k * nl), *hatd = bufs.get<double>((size_t)n * k);
+    if (!hpart || !hatd) return fail(BWGR_ENOMEM, "mrr: device allocation failed");
+    HIPCHK(hipMemcpyAsync(small, off.data(), sizeof(double) * k, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_mrr_hat_part, dim3((unsigned)((ld + 255) / 256), nch), dim3(256), 0, st, (const int8_t *)P->data->X, R, p, ld, (int)n, k, (const double *)bd, cpc, hpart);
     hipLaunchKernelGGL(k_mrr_hat_finish, dim3((unsigned)std::min<int64_t>((n * k + 255) / 256, 4096)), dim3(256), 0, st, (const double *)hpart, nch, ld, (int)n, k,
                        (const double *)small, hatd);
-    MCHK(hipGetLastError());
-    MCHK(d2h(st, hat_out, hatd, sizeof(double) * n * k));
+    HIPCHK(hipGetLastError());
+    HIPCHK(d2h(st, hat_out, hatd, sizeof(double) * n * k));
   }
   for (int t = 0; t < k; ++t) for (int64_t j = 0; j < p; ++j) b_out[(size_t)t * p + j] = bh[(size_t)j * k + t];   // p x k column-major
   for (int t = 0; t < k; ++t) {
@@ -4049,8 +4000,7 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
       if (vb_out) vb_out[j * k + i] = vb[i * k + j];
     }
   *its = numit;
-#undef MCHK
-  return done(BWGR_OK);
+  return BWGR_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4070,11 +4020,11 @@ extern "C" int bwgr_debug_variates(int device, uint64_t seed, int kind, double n
                                    uint32_t purpose, int count, double *out_host) {
   if (!out_host || count < 1) return fail(BWGR_EINVAL, "debug_variates: bad arguments");
   CHK(require_device(device));
-  double *dev = nullptr;
-  HIPCHK(hipMalloc(&dev, sizeof(double) * count));
+  DevBufs bufs;
+  double *dev = bufs.get<double>((size_t)count);
+  if (!dev) return fail(BWGR_ENOMEM, "debug_variates: device allocation failed");
   hipLaunchKernelGGL(k_debug_variates, dim3((count + 255) / 256), dim3(256), 0, 0, make_rng(seed, 0), kind, nu, marker0, iter, purpose, count, dev);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(out_host, dev, sizeof(double) * count, hipMemcpyDeviceToHost));
-  HIPCHK(hipFree(dev));
   return BWGR_OK;
 }
