@@ -975,42 +975,155 @@ static Switches read_switches() {
   return s;
 }
 
+// ---- the panel plan ----------------------------------------------------------------------------------------------------------
+// What a panel is -- its block and slab geometry, whether the pipelined engine fits it, which Gram arrays it carries -- is one decision, made by
+// plan_panel from the shape, the kind of panel and the switches: host arithmetic, no device (bwgr_debug_panel_plan() exposes it to the CPU
+// tests).  panel_alloc allocates what the plan lists; nothing writes to a plan afterwards.  Kinds -- main: bwgr_panel_create's; rows: a row subset
+// of one, refilled per call or per iteration (KMUP2, wgr's bagging): no k_sweep3, no far byte planes; em: bwgr_em's shuffled copy: lag 2 on the 32-bit blocks
+enum PanelKind { PANEL_MAIN = 0, PANEL_ROWS = 1, PANEL_EM = 2 };
+struct PanelPlan {
+  int m = 0, K = 0, R = 0;    // markers per block; slab workgroups, rows of each
+  int64_t ld = 0, nblocks = 0;
+  int pstride = 0, nfeed = 2; // nfeed: q feeder workgroups of k_sweep2 (one gather + sum of K KB takes about a block period at K = 40)
+  bool lag4_ok = false;       // the lag-4 streamer (ring of four tiles) fits the LDS at this geometry
+  size_t lds = 0, lds2 = 0, ldsw = 0;   // dynamic LDS of k_sweep, k_sweep2, k_sweep2w
+  size_t x_bytes = 0, gram_bytes = 0;   // (gram_bytes: per Gram array -- the diagonal blocks, the cross blocks of one distance)
+  bool pipelined = false;     // the streamer / sequencer pipeline (k_sweep2 and what builds on it); false: the replicated recurrence (k_sweep)
+  int xdist = 1;              // cross Gram arrays gx[1..xdist]: distance 2 for the lag-3 pipeline, 3 for the lag-4 one
+  bool has16 = false;         // the 16-bit copies gramp16 / gramx16 for the sequencer (int8 panels)
+  int wdist = 0;              // the affine engine's byte planes gxt[] may reach this distance (where every near entry fits 16 bits)
+  bool try3 = false;          // k_sweep3 is attempted once the data is there (plan_panel3)
+};
+template <typename XT> static int max_slab_rows(int m) {
+  int best = 0;
+  for (int R = 128; R <= 4096; R += 128)
+    if (sweep_lds_bytes<XT>(m, R) <= (size_t)160 * 1024 && (size_t)m * R * sizeof(XT) <= (size_t)SW_TCH * 16 * (SW_THREADS - 64)) best = R;
+  return best;
+}
+static int panel_range(int64_t n, int64_t p) {
+  if (n < 2 || p < 1) return fail(BWGR_EINVAL, "panel: need n >= 2, p >= 1 (n=%lld p=%lld)", (long long)n, (long long)p);
+  if (n > 0x7FFFFF00ll || p > 0x7FFFFF00ll) return fail(BWGR_EINVAL, "panel: n and p must fit 31 bits");
+  return BWGR_OK;
+}
+static int plan_panel(PanelPlan &pl, bool is_f32, int64_t n, int64_t p, int block, int nwg, PanelKind kind, const Switches &sw) {
+  pl = PanelPlan();
+  CHK(panel_range(n, p));
+  const auto lds2_of = [&](int m, int R) { return is_f32 ? sweep2_lds_bytes<float>(m, R) : sweep2_lds_bytes<int8_t>(m, R); };
+  const int mmax = is_f32 ? 64 : SW_MAXM;
+  int m = block > 0 ? block : mmax;
+  if (m > mmax) return fail(BWGR_EINVAL, "panel_create: block %d > %d (limit for this genotype type)", m, mmax);
+  m = ((int)std::min<int64_t>(m, ((p + 15) / 16) * 16) + 15) / 16 * 16;
+  const int Rmax = is_f32 ? max_slab_rows<float>(m) : max_slab_rows<int8_t>(m);
+  // the pipelined engine keeps three tiles per streamer, so it takes fewer rows per slab than k_sweep at small blocks:
+  // prefer the largest slab it fits (unless that needs more workgroups than the chip has CUs, or k_sweep is forced)
+  int Rpick = Rmax, R2 = 0;
+  for (int Rt = 128; Rt <= Rmax; Rt += 128)
+    if (lds2_of(m, Rt) <= (size_t)160 * 1024 && (is_f32 || (size_t)m * Rt <= S2I_TILE_BYTES_MAX)) R2 = Rt;   // (an int8 tile must fit its movers' registers)
+  if (sw.sweep != '1' && R2 > 0 && (n + R2 - 1) / R2 + 1 + 6 <= 256) Rpick = R2;
+  const int K = nwg > 0 ? nwg : (int)((n + Rpick - 1) / Rpick);
+  const int R = (int)((((n + K - 1) / K) + 127) / 128) * 128;
+  if (K > 256 || R > Rmax) return fail(BWGR_EINVAL, "panel_create: n=%lld needs %d slab workgroups of %d rows (limits: 256 workgroups, %d rows)", (long long)n, K, R, Rmax);
+  pl.m = m; pl.K = K; pl.R = R; pl.ld = (int64_t)K * R;
+  pl.nblocks = (p + m - 1) / m;
+  if (pl.nblocks >= (1ll << 24)) return fail(BWGR_EINVAL, "panel_create: %lld marker blocks; the delta granules carry a 24-bit block epoch", (long long)pl.nblocks);
+  pl.pstride = ((m * (m - 1) / 2 + 7) / 8) * 8;
+  pl.lds = is_f32 ? sweep_lds_bytes<float>(m, R) : sweep_lds_bytes<int8_t>(m, R);
+  pl.lds2 = lds2_of(m, R);
+  pl.lag4_ok = !is_f32 && s2i_lds_bytes(m, R, 4) <= (size_t)160 * 1024;
+  if (pl.lag4_ok) pl.lds2 = std::max(pl.lds2, s2i_lds_bytes(m, R, 4));
+#ifdef BWGR_EXPERIMENTS
+  if (!is_f32) pl.ldsw = s2w_lds_bytes(m, R, sw.wlag_timing ? sw.wlag_timing : 6);
+#else
+  if (!is_f32) pl.ldsw = s2w_lds_bytes(m, R, 6);
+#endif   // (room for the deepest pipeline BWGR_WLAG can ask for)
+  pl.nfeed = std::min(6, std::max(2, (K + 39) / 40 + 1));   // K = 40: 2, K = 79: 3, K >= 161: 6
+  if (sw.nfeed >= 1 && sw.nfeed <= 6) pl.nfeed = sw.nfeed;   // experiments
+  // BWGR_SWEEP=1: the A/B switch for tests and profiling; else the pipeline wherever its LDS, its grid and (int8) its movers' registers fit
+  pl.pipelined = sw.sweep != '1' && pl.lds2 <= (size_t)160 * 1024 && K + 1 + pl.nfeed <= 256 && (is_f32 || (size_t)m * R <= S2I_TILE_BYTES_MAX);
+  pl.x_bytes = (size_t)pl.ld * (size_t)p * (is_f32 ? 4 : 1);
+  pl.gram_bytes = (size_t)pl.nblocks * m * m * (is_f32 ? 8 : 4);
+  if (pl.pipelined && kind != PANEL_EM) {
+    if (pl.nblocks > 2) pl.xdist = 2;
+    if (!is_f32 && pl.nblocks > 3 && pl.lag4_ok && sw.lag != '2' && sw.lag != '3') pl.xdist = 3;
+    pl.has16 = !is_f32;
+  }
+  // the byte planes: the near distances from the arrays above, distances 4 and 5 (pipelines five and six blocks deep, BWGR_WLAG) on main panels only
+  if (pl.has16 && sw.winv && m <= SW_MAXM)
+    for (int d = 1; d <= S2W_MAXDIST && d < pl.nblocks; ++d) {
+      if (d <= S2W_NEARD ? d > pl.xdist : (kind != PANEL_MAIN || d > sw.wlag_cap - 1)) break;
+      pl.wdist = d;
+    }
+  pl.try3 = kind == PANEL_MAIN && !is_f32 && pl.pipelined && sw.sweep != '2';   // (BWGR_SWEEP=2 keeps k_sweep2)
+  return BWGR_OK;
+}
+
+// k_sweep3's share (selection models on int8 panels, sweep3.hip.h), planned once the data is on the device: from the panel plan, the largest
+// |x| (the slab dots are integer sums sized by it) and whether every near Gram entry fits 16 bits
+struct Panel3Plan {
+  bool fits = false;
+  int R3 = 0, sub3 = 0, K3 = 0;   // rows of a streamer workgroup, streamers per slab, streamer workgroups
+  int D = 0;                  // fold-in lag in blocks; cross Gram arrays reach D-1 blocks back
+  size_t lds3 = 0;
+  bool solo3 = true;          // a chain alone on the GPU runs 128-row streamers (BWGR_SOLO3=0: never)
+};
+static Panel3Plan plan_panel3(const PanelPlan &pp, const Switches &sw, int xmax, bool gram16) {
+  Panel3Plan q;
+  if (!pp.try3) return q;
+  q.R3 = (pp.R % 256 == 0) ? 256 : 128;
+  if ((sw.r3 == 64 || sw.r3 == 128 || sw.r3 == 256) && pp.R % sw.r3 == 0) { q.R3 = sw.r3; q.solo3 = false; }   // (an explicit height holds for every launch)
+  q.sub3 = pp.R / q.R3; q.K3 = pp.K * q.sub3;
+  q.D = 12;   // (the streamers fold a list whose words they saw a step ahead: more lag than the fold itself needs -- C4: 12.45 ms at 8, 11.27 at 9, 10.78 at 10, 10.41 at 11, 10.37 at 12, 10.48 at 13)
+  // (at least 2: a block's list leaves the sequencer while the next block is in its rounds)
+  if (sw.d3 >= 2 && sw.d3 <= S3_MAXD) q.D = sw.d3;
+  q.D = (int)std::min<int64_t>(q.D, std::max<int64_t>(2, pp.nblocks));
+  q.lds3 = std::max(std::max(s3_streamer_lds(q.R3), std::max(s3_streamer_dma_lds(128), q.R3 == 256 ? s3_streamer_dma_lds(256) : (size_t)0)), s3_seq_lds(q.D, gram16));
+  // the slab dots are summed as integers: sum over all rows of |x| * 128 per digit, four digits of 8 bits, 8 bits of arrival count
+  q.fits = q.K3 <= 255 && q.lds3 <= (size_t)160 * 1024 && pp.ld * std::max(xmax, 1) < (1ll << 23) && (size_t)pp.m * q.R3 <= (size_t)4 * 16 * SW_THREADS;
+  if (q.fits && sw.solo3 >= 0) q.solo3 = sw.solo3 != '0';
+  return q;
+}
+
+// The plans without a device (test hook): plan_panel with the switches of the environment, as bwgr_panel_create reads them, and -- given an
+// assumed xmax >= 0 and 16-bit verdict -- plan_panel3.  out: see include/bwgr.h.
+extern "C" int bwgr_debug_panel_plan(int is_f32, int64_t n, int64_t p, int block, int nwg, int kind, int xmax, int gram16, int64_t out[BWGR_PANEL_PLAN_NOUT]) {
+  if (!out || kind < PANEL_MAIN || kind > PANEL_EM) return fail(BWGR_EINVAL, "debug_panel_plan: null pointer or bad kind");
+  const Switches sw = read_switches();
+  PanelPlan pl;
+  CHK(plan_panel(pl, is_f32 != 0, n, p, block, nwg, (PanelKind)kind, sw));
+  const Panel3Plan q = xmax >= 0 ? plan_panel3(pl, sw, xmax, gram16 != 0) : Panel3Plan();
+  const int64_t v[BWGR_PANEL_PLAN_NOUT] = {pl.m, pl.K, pl.R, pl.ld, pl.nblocks, pl.pstride, pl.nfeed, pl.lag4_ok, (int64_t)pl.lds, (int64_t)pl.lds2, (int64_t)pl.ldsw,
+                                           (int64_t)pl.x_bytes, (int64_t)pl.gram_bytes, pl.pipelined, pl.xdist, pl.has16, pl.wdist, pl.try3,
+                                           q.fits, q.R3, q.sub3, q.K3, q.D, (int64_t)q.lds3, q.solo3};
+  std::copy(v, v + BWGR_PANEL_PLAN_NOUT, out);
+  return BWGR_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // A resident panel is its data (PanelData) and the handles on it (bwgr_panel).  The root handle is made with the data -- by
 // bwgr_panel_create, or as a scratch panel of KMUP2, wgr or bwgr_em -- and frees it; a clone (bwgr_panel_clone) is another handle on the
 // same data.  Every handle owns its streams and the scratch its sweeps write.  The data does not change while a clone is alive: it is
 // built with the root, and bwgr_panel_set_centred refuses on a clone and while any chain is alive.
 struct PanelData {
-  int device = 0;
-  int64_t n = 0, p = 0, ld = 0;
-  int is_f32 = 0;
-  int m = 0, K = 0, R = 0;
-  int64_t nblocks = 0;
-  int pstride = 0;
-  size_t x_bytes = 0, gram_bytes = 0;
-  size_t lds_bytes = 0, lds2_bytes = 0, lds3_bytes = 0, ldsw_bytes = 0;
-  int sweep_version = 2;      // 3: k_sweep3 beside k_sweep2; 2: streamer/sequencer pipeline (k_sweep2); 1: replicated recurrence (k_sweep)
-  bool lag4_ok = false;       // the lag-4 streamer (ring of four tiles) fits the LDS at this geometry
-  int nfeed = 2;              // q feeder workgroups of k_sweep2 (one gather + sum of K KB takes about a block period at K = 40)
-  // k_sweep3 (selection models on int8 panels, sweep3.hip.h)
-  bool want3 = false;         // build what k_sweep3 needs with the panel (off for the per-iteration scratch panels of bagging and the EM family)
-  bool e3_ready = false;
-  int e3_D = 0;               // fold-in lag in blocks; cross Gram arrays reach D-1 blocks back
-  int K3 = 0, R3 = 0, sub3 = 0;   // streamer workgroups, rows of each, streamers per slab
-  bool solo3 = true;          // a chain alone on the GPU runs 128-row streamers (BWGR_SOLO3=0: never)
+  int device = 0, is_f32 = 0;
+  int64_t n = 0, p = 0;
+  PanelPlan plan;             // made with the data (plan_panel)
+  Panel3Plan plan3;           // made when the data is built (sweep3_build)
+  // what the build found in the data (panel_setup once; panel_build_gram again wherever a scratch panel's rows or columns change)
+  float MSx = 0;
+  int xmax = 0;               // largest |x| of an int8 panel
   bool gram16 = false;        // the 16-bit copies are exact: every entry in 0..65535
-  int gram_maxdist = 3;       // panel_build_gram stops at this block distance (the EM scratch panel needs 1)
   int winv_nd = 0;            // gxt distances built = the deepest lag the affine sweeps can run, minus one
-  void *X = nullptr, *gram = nullptr, *gramx = nullptr, *gramx2 = nullptr, *gramx3 = nullptr, *gramp = nullptr;
-  uint16_t *gramp16 = nullptr, *gramx16 = nullptr;   // 16-bit copies for the sequencer (int8 panels)
+  bool e3_ready = false;      // this panel has k_sweep3: plan3 fits and every far Gram block fits the staging's element type
+  bool crowded = false;       // a shard among three or more on one device: never the solo streamers (bwgr_group_create)
+  void *X = nullptr, *gram = nullptr, *gramp = nullptr;
+  void *gx[S2W_NEARD + 1] = {};   // gx[d], d = 1 .. plan.xdist: cross Gram blocks X_{b-d}' X_b, int32 (fp64 for float panels)
+  uint16_t *gramp16 = nullptr, *gramx16 = nullptr;   // 16-bit copies of gramp and gx[1] (plan.has16)
   int *gram16_bad = nullptr;
-  void *g3x[S3_MAXD] = {};    // g3x[d-1]: cross Gram blocks of distance d in the element type k_sweep3 reads (aliases the older arrays where they fit)
-  bool g3own[S3_MAXD] = {};   // allocated here (not an alias)
+  // g3x[d-1]: cross Gram blocks of distance d in the element type k_sweep3 reads: the panel's array of that distance and type, or one of its own
+  struct { void *a; bool own; } g3x[S3_MAXD] = {};
   unsigned char *gx12 = nullptr;   // 16-bit panels: an included marker's distance-1 and distance-2 rows side by side (k_near_rows)
   unsigned char *gxt[S2W_MAXDIST] = {};   // the affine models' cross Gram blocks as the sequencer's MFMA operand (k_gx_planes, sweep2w.hip.h)
   float *xx = nullptr, *vx = nullptr, *msx_dev = nullptr;
-  float MSx = 0;
-  int xmax = 0;               // largest |x| of an int8 panel
   int *xmax_dev = nullptr;
   // implicitly centred columns (bwgr_panel_set_centred; int8 panels with k_sweep3): the column sums, the centred |x_j - mean_j|^2 as floats (what
   // a chain's xx is then)
@@ -1146,16 +1259,9 @@ static int require_device(int device) {
   return BWGR_OK;
 }
 
-template <typename XT> static int max_slab_rows(int m) {
-  int best = 0;
-  for (int R = 128; R <= 4096; R += 128)
-    if (sweep_lds_bytes<XT>(m, R) <= (size_t)160 * 1024 && (size_t)m * R * sizeof(XT) <= (size_t)SW_TCH * 16 * (SW_THREADS - 64)) best = R;
-  return best;
-}
-
 // the words the workgroups poll (flags, delta granules, q words and the feeders' sums) live in one allocation
 static hipError_t alloc_exchange(bwgr_panel *P) {
-  const size_t K = (size_t)P->data->K;
+  const size_t K = (size_t)P->data->plan.K;
   const size_t fb = (sizeof(uint32_t) * (K + 1) * SW_FLAG_STRIDE + 255) & ~(size_t)255;
   const size_t gb = (sizeof(unsigned long long) * S2_NSLOT * SW_MAXM + 255) & ~(size_t)255;
   const size_t qb = sizeof(double) * S2_NSLOT * (K + 1) * SW_MAXM;
@@ -1282,83 +1388,60 @@ static void guard_forget(bwgr_panel *P) {
 }
 
 static int reset_exchange(bwgr_panel *P) {
-  if (P->data->sweep_version >= 2) {
+  if (P->data->plan.pipelined) {
     HIPCHK(hipMemsetAsync(P->xchg, 0, P->xchg_bytes, P->stream));
-  } else if (P->data->K > 1) {
-    HIPCHK(hipMemsetAsync(P->xflags, 0, sizeof(uint32_t) * ((size_t)P->data->K + 1) * SW_FLAG_STRIDE, P->stream));
+  } else if (P->data->plan.K > 1) {
+    HIPCHK(hipMemsetAsync(P->xflags, 0, sizeof(uint32_t) * ((size_t)P->data->plan.K + 1) * SW_FLAG_STRIDE, P->stream));
   }
   return BWGR_OK;
 }
 
-static void launch_gramx_i8(bwgr_panel *P, int32_t *g, int dist);
+static void launch_gram(bwgr_panel *P, void *g, int dist);   // (with the panel's other Gram launches, below)
 // ---- k_sweep3 (sweep3.hip.h): what it needs beside the panel ----
-// the cross Gram arrays of distance 2 .. D-1 in the element type of the 16-bit (or, failing that, 32-bit) staging
+// plan3, then the cross Gram arrays of distance 1 .. D-1 in the element type of the 16-bit (or, failing that, 32-bit) staging
 static int sweep3_build(bwgr_panel *P) {
-  P->data->e3_ready = false;
-  if (P->data->is_f32 || !P->data->want3 || P->data->sweep_version != 3) return BWGR_OK;
-  const int m = P->data->m;
-  int R3 = (P->data->R % 256 == 0) ? 256 : 128;
-  { const int v = P->data->sw.r3; if ((v == 64 || v == 128 || v == 256) && P->data->R % v == 0) { R3 = v; P->data->solo3 = false; } }   // (an explicit height holds for every launch)
-  const int sub = P->data->R / R3, K3 = P->data->K * sub;
-  int D = 12;   // (the streamers fold a list whose words they saw a step ahead: more lag than the fold itself needs -- C4: 12.45 ms at 8, 11.27 at 9, 10.78 at 10, 10.41 at 11, 10.37 at 12, 10.48 at 13)
-  // (at least 2: a block's list leaves the sequencer while the next block is in its rounds)
-  if (P->data->sw.d3 >= 2 && P->data->sw.d3 <= S3_MAXD) D = P->data->sw.d3;
-  D = (int)std::min<int64_t>(D, std::max<int64_t>(2, P->data->nblocks));
-  const size_t lds = std::max(std::max(s3_streamer_lds(R3), std::max(s3_streamer_dma_lds(128), R3 == 256 ? s3_streamer_dma_lds(256) : (size_t)0)), s3_seq_lds(D, P->data->gram16));
-  // the slab dots are summed as integers: sum over all rows of |x| * 128 per digit, four digits of 8 bits, 8 bits of arrival count
-  if (K3 > 255 || K3 + 1 > 256 || lds > (size_t)160 * 1024 || (int64_t)P->data->ld * std::max(P->data->xmax, 1) >= (1ll << 23) || (size_t)m * R3 > (size_t)4 * 16 * SW_THREADS) {
-    P->data->sweep_version = 2;
-    return BWGR_OK;
-  }
-  P->data->R3 = R3; P->data->sub3 = sub; P->data->K3 = K3; P->data->e3_D = D; P->data->lds3_bytes = lds;
-  if (P->data->sw.solo3 >= 0) P->data->solo3 = P->data->sw.solo3 != '0';
-  const size_t blk_elems = (size_t)P->data->nblocks * m * m;
-  const bool g16 = P->data->gram16;
-  const int Dbuild = D;
+  PanelData *D = P->data; const PanelPlan &pl = D->plan;
+  D->e3_ready = false;
+  D->plan3 = plan_panel3(pl, D->sw, D->xmax, D->gram16);
+  if (!D->plan3.fits) return BWGR_OK;
+  const int m = pl.m; const bool g16 = D->gram16;
+  const size_t blk_elems = (size_t)pl.nblocks * m * m;
   int bad = 0;
   {   // the far blocks; tmp, a whole Gram array, goes once they are built and before the 16-bit verdict is acted on
     DevBufs bufs;
     int32_t *tmp = nullptr;
-    for (int d = 1; d < Dbuild; ++d) {
-      if (P->data->nblocks <= d) { P->data->g3x[d - 1] = nullptr; continue; }
-      if (d == 1) { P->data->g3x[0] = g16 ? (void *)P->data->gramx16 : P->data->gramx; continue; }
-      if (!g16 && d == 2 && P->data->gramx2) { P->data->g3x[1] = P->data->gramx2; continue; }
-      if (!g16 && d == 3 && P->data->gramx3) { P->data->g3x[2] = P->data->gramx3; continue; }
-      HIPCHK(hipMalloc(&P->data->g3x[d - 1], blk_elems * (g16 ? 2 : 4)));
-      P->data->g3own[d - 1] = true;
-      void *arr = P->data->g3x[d - 1];
+    for (int d = 1; d < D->plan3.D && d < pl.nblocks; ++d) {
+      void *have32 = d <= pl.xdist ? D->gx[d] : nullptr, *have = g16 ? (d == 1 ? (void *)D->gramx16 : nullptr) : have32;
+      if (have) { D->g3x[d - 1] = {have, false}; continue; }
+      void *arr = nullptr;
+      HIPCHK(hipMalloc(&arr, blk_elems * (g16 ? 2 : 4)));
+      D->g3x[d - 1] = {arr, true};
       if (g16) {
-        const int32_t *src;
-        if (d == 2 && P->data->gramx2) src = (const int32_t *)P->data->gramx2;
-        else if (d == 3 && P->data->gramx3) src = (const int32_t *)P->data->gramx3;
-        else {
+        if (!have32) {
           if (!tmp && !(tmp = bufs.get<int32_t>(blk_elems))) return fail(BWGR_ENOMEM, "panel_create: device allocation failed");
-          launch_gramx_i8(P, tmp, d);
-          src = tmp;
+          launch_gram(P, tmp, d);
+          have32 = tmp;
         }
-        hipLaunchKernelGGL(k_gram_narrow, dim3(2048), dim3(256), 0, P->stream, src + (size_t)d * m * m, (uint16_t *)arr + (size_t)d * m * m, (int64_t)(P->data->nblocks - d) * m * m, P->data->gram16_bad);
-      } else launch_gramx_i8(P, (int32_t *)arr, d);
+        hipLaunchKernelGGL(k_gram_narrow, dim3(2048), dim3(256), 0, P->stream, (const int32_t *)have32 + (size_t)d * m * m, (uint16_t *)arr + (size_t)d * m * m, (int64_t)(pl.nblocks - d) * m * m, D->gram16_bad);
+      } else launch_gram(P, arr, d);
       HIPCHK(hipGetLastError());
     }
-    if (g16) HIPCHK(hipMemcpyAsync(&bad, P->data->gram16_bad, sizeof(int), hipMemcpyDeviceToHost, P->stream));
+    if (g16) HIPCHK(hipMemcpyAsync(&bad, D->gram16_bad, sizeof(int), hipMemcpyDeviceToHost, P->stream));
     HIPCHK(hipStreamSynchronize(P->stream));
   }
   if (bad) {   // an entry of a far block left the 16-bit range although the near blocks fit: rare; leave the panel to k_sweep2
-    for (int d = 1; d < S3_MAXD; ++d) if (P->data->g3own[d - 1]) { hipFree(P->data->g3x[d - 1]); P->data->g3x[d - 1] = nullptr; P->data->g3own[d - 1] = false; }
-    P->data->sweep_version = 2;
+    for (auto &g : D->g3x) { if (g.own) hipFree(g.a); g = {nullptr, false}; }
     return BWGR_OK;
   }
-  {   // 16-bit panels: an included marker's distance-1 / 2 rows in one piece
-    if (g16) {
-      HIPCHK(hipMalloc(&P->data->gx12, (size_t)P->data->nblocks * m * 2 * m * 2));
-      hipLaunchKernelGGL(k_near_rows, dim3(4096), dim3(256), 0, P->stream, (const uint16_t *)P->data->g3x[0], (const uint16_t *)(D >= 3 ? P->data->g3x[1] : nullptr), (uint16_t *)P->data->gx12, m, (int64_t)P->data->nblocks);
-      HIPCHK(hipGetLastError());
-    }
+  if (g16) {   // 16-bit panels: an included marker's distance-1 / 2 rows in one piece
+    HIPCHK(hipMalloc(&D->gx12, (size_t)pl.nblocks * m * 2 * m * 2));
+    hipLaunchKernelGGL(k_near_rows, dim3(4096), dim3(256), 0, P->stream, (const uint16_t *)D->g3x[0].a, (const uint16_t *)(D->plan3.D >= 3 ? D->g3x[1].a : nullptr), (uint16_t *)D->gx12, m, (int64_t)pl.nblocks);
+    HIPCHK(hipGetLastError());
   }
   for (const void *f : {reinterpret_cast<const void *>(k_sweep3<uint16_t, false>), reinterpret_cast<const void *>(k_sweep3<int32_t, false>), reinterpret_cast<const void *>(k_sweep3<uint16_t, true>),
                         reinterpret_cast<const void *>(k_sweep3<int32_t, true>), reinterpret_cast<const void *>(k_sweep3p<uint16_t>), reinterpret_cast<const void *>(k_sweep3p<int32_t>)})
     HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  P->data->e3_ready = true;
+  D->e3_ready = true;
   return BWGR_OK;
 }
 // the DMA streamer's lane offsets are 32-bit: (columns of the launch) * (rows of a slab) bytes must stay below 4 GiB
@@ -1368,8 +1451,8 @@ extern "C" int bwgr_debug_stream3_dma(int64_t ncols, int64_t R) { return stream3
 // k_affine_inv forms before the sweep (sweep2w.hip.h).
 static int winv_alloc(bwgr_panel *P) {
   if (P->winv) return BWGR_OK;
-  HIPCHK(hipMalloc(&P->winv, sizeof(double) * (size_t)S2W_WDOUBLES * (size_t)P->data->nblocks));
-  HIPCHK(hipMalloc(&P->qsumw, sizeof(unsigned long long) * 4 * 2 * SW_MAXM * (size_t)P->data->nblocks));   // (up to four copies)
+  HIPCHK(hipMalloc(&P->winv, sizeof(double) * (size_t)S2W_WDOUBLES * (size_t)P->data->plan.nblocks));
+  HIPCHK(hipMalloc(&P->qsumw, sizeof(unsigned long long) * 4 * 2 * SW_MAXM * (size_t)P->data->plan.nblocks));   // (up to four copies)
   return BWGR_OK;
 }
 
@@ -1396,25 +1479,25 @@ static void launch_prestage(bwgr_panel *P, const SweepArgs &a_in, const SweepPla
     P->draws_valid = false;   // (consumed: the buffer is the next iteration's from here)
   } else hipLaunchKernelGGL(k_prestage, dim3((unsigned)std::min<int64_t>(4096, (tasks + 255) / 256)), dim3(256), 0, P->stream, a, j0, j1);
   if (s3) {   // the sweep's fixed-point scale, then the in-block speculative terms on that grid
-    hipLaunchKernelGGL(k_escale, dim3(1), dim3(1024), 0, P->stream, a.e, P->data->ld, a.sc, xbits, a.gate3, sh_add);
+    hipLaunchKernelGGL(k_escale, dim3(1), dim3(1024), 0, P->stream, a.e, P->data->plan.ld, a.sc, xbits, a.gate3, sh_add);
     if (a.flags & SWF_CENTRE) {   // the rejected steps' share of sum(e_stored), block by block (the whole panel: launch_prestage is called with every block)
       hipLaunchKernelGGL(k_cen_tot, dim3((unsigned)(a.blk_end - a.blk_begin)), dim3(128), 0, P->stream, a, a.blk_begin, 0);
-      hipLaunchKernelGGL(k_cen_scan, dim3(1), dim3(1024), 0, P->stream, a, (int)P->data->nblocks, 0);
+      hipLaunchKernelGGL(k_cen_scan, dim3(1), dim3(1024), 0, P->stream, a, (int)P->data->plan.nblocks, 0);
     }
     hipLaunchKernelGGL(k_spec3, dim3((unsigned)(a.blk_end - a.blk_begin)), dim3(128), 0, P->stream, a, a.blk_begin, P->data->gram16 ? (const uint16_t *)P->data->gramp16 : (const uint16_t *)nullptr);
     if (std::isinf(a.gate3)) return;
   }
   if (pl.engine == 4) {
-    if (pl.fx) hipLaunchKernelGGL(k_escale, dim3(1), dim3(1024), 0, P->stream, a.e, P->data->ld, a.sc, xbits, INFINITY, sh_add);   // (|b0|, the noise terms)
+    if (pl.fx) hipLaunchKernelGGL(k_escale, dim3(1), dim3(1024), 0, P->stream, a.e, P->data->plan.ld, a.sc, xbits, INFINITY, sh_add);   // (|b0|, the noise terms)
     hipLaunchKernelGGL(k_affine_inv, dim3((unsigned)(a.blk_end - a.blk_begin)), dim3(512), S2W_INV_LDS, P->stream, a, P->winv, (a.flags & SWF_DELTA2) ? 2.0 : 1.0);
     return;
   }
-  if (P->data->sweep_version >= 2) {
+  if (P->data->plan.pipelined) {
     const int sel = (a.flags & SWF_SELECT) ? 1 : 0;
     const unsigned nb = (unsigned)(a.blk_end - a.blk_begin);
     if ((a.flags & SWF_CENTRE) && sel) {   // the fp64 engine's share of an implicitly centred iteration (the float steps themselves; runs on k_sweep2's side of the gate)
       hipLaunchKernelGGL(k_cen_tot, dim3(nb), dim3(128), 0, P->stream, a, a.blk_begin, 1);
-      hipLaunchKernelGGL(k_cen_scan, dim3(1), dim3(1024), 0, P->stream, a, (int)P->data->nblocks, 1);
+      hipLaunchKernelGGL(k_cen_scan, dim3(1), dim3(1024), 0, P->stream, a, (int)P->data->plan.nblocks, 1);
     }
     if (P->data->is_f32) hipLaunchKernelGGL(k_spec<double>, dim3(nb), dim3(128), 0, P->stream, a, a.blk_begin, sel);
     else hipLaunchKernelGGL(k_spec<int32_t>, dim3(nb), dim3(128), 0, P->stream, a, a.blk_begin, sel);
@@ -1463,22 +1546,21 @@ static SweepPlan plan_sweep(const bwgr_panel *P, const SweepArgs &a, bool redo) 
   if (P->data->e3_ready && sel && !(a.flags & SWF_EM_ANY) && !redo) pl.gate3 = (sw.eng3_thr >= 1.0f || P->force3) ? INFINITY : sw.eng3_thr;
   // The affine sweeps of an int8 panel with 16-bit Gram staging: k_sweep2w, with its own streamers (s2w_streamer_fx: 128 rows each,
   // fixed-point residual) where the slab count allows
-  const bool winv = sw.winv && P->data->sweep_version >= 2 && !P->data->is_f32 && P->data->gramp && P->data->winv_nd >= 1 && P->data->K <= 2 * (S2W_QW + S2W_QX) &&
-                    !(a.flags & (SWF_SELECT | SWF_EM_ANY | SWF_SERIAL)) && P->data->ldsw_bytes > 0 && P->data->ldsw_bytes <= (size_t)160 * 1024;
-  const bool wfx = sw.wfx && (P->data->R % S2W_FXR) == 0 && P->data->K * (P->data->R / S2W_FXR) <= 255;
-  pl.engine = pl.gate3 > 0.0f ? 3 : winv ? 4 : std::min(P->data->sweep_version, 2);
+  const bool winv = sw.winv && P->data->plan.pipelined && !P->data->is_f32 && P->data->winv_nd >= 1 && P->data->plan.K <= 2 * (S2W_QW + S2W_QX) &&
+                    !(a.flags & (SWF_SELECT | SWF_EM_ANY | SWF_SERIAL)) && P->data->plan.ldsw > 0 && P->data->plan.ldsw <= (size_t)160 * 1024;
+  const bool wfx = sw.wfx && (P->data->plan.R % S2W_FXR) == 0 && P->data->plan.K * (P->data->plan.R / S2W_FXR) <= 255;
+  pl.engine = pl.gate3 > 0.0f ? 3 : winv ? 4 : P->data->plan.pipelined ? 2 : 1;
   // Selection sweeps of k_sweep2: three blocks deep.  (The single-barrier sequencer also knows a fourth level, BWGR_LAG=4: it was
   // the default while k_sweep2 also ran the sparse chains; those are k_sweep3's now, and from 5 % of the markers in the model upwards
   // the third cross term's row fetches cost more than the depth gives -- C4-size BayesC at 5 / 19 / 36 % inclusion: 31.4 / 21.3 /
   // 14.5 iter/s at depth 3 against 30.9 / 19.4 / 9.4 at depth 4; BayesCpi at 51 %: 11.1 against 6.7.)  BWGR_LAG=2|3|4 sets it (A/B tests).
   int lag = 2;
-  if (P->data->sweep_version >= 2 && sel) {
+  if (P->data->plan.pipelined && sel) {
     // the generic sequencer (32-bit Gram entries, fp32 panels) reads a distance-2 row per accepted marker straight from global memory on
     // one wave: two blocks deep unless asked (us per block at n = 10 000, depth 2 / 3: 1.4 % inclusion 4.53 / 4.67, 10.9 % 5.29 / 14.5,
     // BayesCpi at 52 % 12.7 / 58.0); the 16-bit / single-barrier sequencer stages those rows and knows a third cross term as well
-    if (P->data->gramx2 && sw.lag >= 0) lag = 3;
-    if (!P->data->is_f32 && P->data->gramx2 && P->data->gram16) lag = 3;
-    if (!P->data->is_f32 && P->data->gramx3 && P->data->gram16 && P->data->lag4_ok) lag = 4;
+    if (P->data->plan.xdist >= 2 && (sw.lag >= 0 || P->data->gram16)) lag = 3;
+    if (P->data->plan.xdist >= 3 && P->data->gram16) lag = 4;   // (a panel with distance-3 blocks fits the lag-4 streamer: plan_panel)
   }
   pl.lag = std::min(lag, (sw.lag >= '2' && sw.lag <= '4') ? sw.lag - '0' : 3);
   if (winv) {   // the affine sweeps' product sequencer: as deep as the panel's cross Gram planes reach (BWGR_WLAG caps it)
@@ -1490,20 +1572,20 @@ static SweepPlan plan_sweep(const bwgr_panel *P, const SweepArgs &a, bool redo) 
   }
   // streamers, sequencer, and for the selection models the q feeders (the affine recurrence is compute-bound: its
   // sequencer gathers q itself under the recurrence, and a feeder hop in its lag-2 chain measured 15 % slower)
-  pl.nfeed = (P->data->sweep_version >= 2 && sel) ? P->data->nfeed : 0;
+  pl.nfeed = (P->data->plan.pipelined && sel) ? P->data->plan.nfeed : 0;
   // selection models: 16-bit staging and the single-barrier sequencer (the affine recurrence is compute-bound and measured faster on
   // the 32-bit blocks: no conversion in its inner loop)
-  pl.g16 = P->data->sweep_version >= 2 && !P->data->is_f32 && P->data->gram16 && sel;
+  pl.g16 = P->data->plan.pipelined && P->data->gram16 && sel;
   // A chain that has the GPU to itself (a root panel without clones) runs 128-row streamers, two to a slab: 80 compute units instead
   // of 41, 15.98-16.18 against 16.49 ms per sweep at C4 (the same chain bit for bit: the slab dots are integer sums).  With clones
   // alive -- chains side by side, pairs -- every chain keeps the 256-row streamers the concurrency counts assume.  BWGR_SOLO3=0: never.
-  const bool alone = P->data->solo3 && P->is_root && P->data->nclones == 0;
+  const bool alone = P->data->plan3.solo3 && !P->data->crowded && P->is_root && P->data->nclones == 0;
   // The next iteration's variates beside the sweep (draws_ahead): selection models with the logistic step, only for a chain alone (beside
   // other chains or shards the idle compute units it would run on are theirs: five chains side by side 255 -> 226 chain-iter/s, three
   // shards 163 -> 119 iter/s with it); BWGR_DRAWS=0 switches it off
   pl.draws = sel && !(a.flags & (SWF_MH | SWF_EM_ANY)) && alone && sw.draws;
   if (pl.gate3 > 0.0f) {
-    pl.R3 = P->data->R3; pl.sub = P->data->sub3; pl.K3 = P->data->K3;
+    pl.R3 = P->data->plan3.R3; pl.sub = P->data->plan3.sub3; pl.K3 = P->data->plan3.K3;
 #ifdef BWGR_EXPERIMENTS
     pl.dbg3 = sw.dbg3;   // (timing switches, some of which break the chain: the experiment build only)
 #endif
@@ -1512,16 +1594,16 @@ static SweepPlan plan_sweep(const bwgr_panel *P, const SweepArgs &a, bool redo) 
       // launches whose column range spans less than 4 GiB of one slab take it (p * R < 2^32: 16.7 M markers at R = 256); wider ones keep the
       // register path, whose offsets are size_t.  bwgr_debug_stream3_dma() exposes the rule to the CPU tests.
       const int64_t j_lo = (int64_t)a.blk_begin * a.m, j_hi = std::min<int64_t>(P->data->p, (int64_t)a.blk_end * a.m);
-      const bool fits32 = stream3_dma_fits(j_hi - j_lo, P->data->R);
+      const bool fits32 = stream3_dma_fits(j_hi - j_lo, P->data->plan.R);
       if (sw.stream3 != 'r' && fits32) pl.dbg3 |= (1 << 22);
       if (sw.stream3 == 'd' && fits32) pl.dbg3 |= (1 << 23);   // (EXPERIMENT: the 256-row streamers too, three tile buffers)
     }
     if (P->force3) {   // a pair run (bwgr_chain_run_pair): one k_sweep3p launch, K3 streamers and two sequencers, serves both chains; no redo
-      const size_t lds = std::max(s3p_streamer_lds(pl.R3), s3_seq_lds(P->data->e3_D, P->data->gram16));
+      const size_t lds = std::max(s3p_streamer_lds(pl.R3), s3_seq_lds(P->data->plan3.D, P->data->gram16));
       spin(P->data->gram16 ? reinterpret_cast<const void *>(k_sweep3p<uint16_t>) : reinterpret_cast<const void *>(k_sweep3p<int32_t>), pl.K3 + 2, pl.K3 + 2, SW_THREADS, lds);
       return pl;
     }
-    if (alone && pl.R3 == 256 && 2 * pl.K3 + 1 <= 256) { pl.R3 = 128; pl.sub = P->data->R / 128; pl.K3 = P->data->K * pl.sub; }
+    if (alone && pl.R3 == 256 && 2 * pl.K3 + 1 <= 256) { pl.R3 = 128; pl.sub = P->data->plan.R / 128; pl.K3 = P->data->plan.K * pl.sub; }
     // one more workgroup, on the sequencer's XCD (workgroups with equal index mod 8 share an XCD), warms that XCD's L2 with what the
     // staging waves load (on for a chain alone on the GPU: 15.61 -> 15.37 ms per sweep at C4 on the steadied kernel; beside other chains
     // the workgroup is not counted by bwgr_panel_max_concurrent, so it stays off there; BWGR_PF3=0|1 decides otherwise)
@@ -1532,7 +1614,7 @@ static SweepPlan plan_sweep(const bwgr_panel *P, const SweepArgs &a, bool redo) 
     const int grid = pl.K3 + 1 + (pf_on ? 1 : 0) + (pf2_on ? 1 : 0);
     const void *fn = P->data->gram16 ? (cen ? reinterpret_cast<const void *>(k_sweep3<uint16_t, true>) : reinterpret_cast<const void *>(k_sweep3<uint16_t, false>))
                                   : (cen ? reinterpret_cast<const void *>(k_sweep3<int32_t, true>) : reinterpret_cast<const void *>(k_sweep3<int32_t, false>));
-    spin(fn, grid, grid, SW_THREADS, P->data->lds3_bytes);
+    spin(fn, grid, grid, SW_THREADS, P->data->plan3.lds3);
   }
   if (!std::isinf(pl.gate3)) {
     if (winv) {
@@ -1540,20 +1622,20 @@ static SweepPlan plan_sweep(const bwgr_panel *P, const SweepArgs &a, bool redo) 
       if (!pl.fx) pl.lag = std::min(pl.lag, 4);   // (k_sweep2's streamers -- the range-recovery launch, BWGR_WFX=0 -- hold four tiles)
       pl.nd = std::min(pl.lag - 1, (int)S2W_MAXDIST);
       pl.npf = sw.wpf; pl.ahead = sw.wahead;   // (npf measured at C2: 0 -> 540, 2 -> 636, 4 -> 685 iter/s; 6 and 8 no better)
-      pl.wsub = P->data->R / S2W_FXR; pl.wK3 = P->data->K * pl.wsub;
+      pl.wsub = P->data->plan.R / S2W_FXR; pl.wK3 = P->data->plan.K * pl.wsub;
       pl.nq = sw.wnq ? sw.wnq : (pl.wK3 > 48 ? 2 : 1);   // (C2, 40 streamers: one copy 1.10 ms, two 1.21; C4 shape, 80 streamers: 27.8 / 25.6 / 27.6 ms with 1 / 2 / 4)
       // (of the 8 npf workgroups past the sequencer, the npf on its XCD prefetch; the others leave at once)
-      const int wgs = pl.fx ? pl.wK3 : P->data->K;
-      spin(pl.fx ? reinterpret_cast<const void *>(k_sweep2w<true>) : reinterpret_cast<const void *>(k_sweep2w<false>), wgs + 1 + 8 * pl.npf, wgs + 1 + pl.npf, S2W_THREADS, P->data->ldsw_bytes);
-    } else if (P->data->sweep_version >= 2) {
+      const int wgs = pl.fx ? pl.wK3 : P->data->plan.K;
+      spin(pl.fx ? reinterpret_cast<const void *>(k_sweep2w<true>) : reinterpret_cast<const void *>(k_sweep2w<false>), wgs + 1 + 8 * pl.npf, wgs + 1 + pl.npf, S2W_THREADS, P->data->plan.ldsw);
+    } else if (P->data->plan.pipelined) {
       const void *fn = P->data->is_f32 ? (sel ? reinterpret_cast<const void *>(k_sweep2<float, true>) : reinterpret_cast<const void *>(k_sweep2<float, false>))
                        : pl.g16  ? reinterpret_cast<const void *>(k_sweep2<int8_t, true, uint16_t>)
                        : sel     ? reinterpret_cast<const void *>(k_sweep2<int8_t, true>) : reinterpret_cast<const void *>(k_sweep2<int8_t, false>);
-      spin(fn, P->data->K + 1 + pl.nfeed, P->data->K + 1 + pl.nfeed, SW_THREADS, P->data->lds2_bytes);
+      spin(fn, P->data->plan.K + 1 + pl.nfeed, P->data->plan.K + 1 + pl.nfeed, SW_THREADS, P->data->plan.lds2);
     } else {
       const void *fn = P->data->is_f32 ? (sel ? reinterpret_cast<const void *>(k_sweep<float, true>) : reinterpret_cast<const void *>(k_sweep<float, false>))
                                  : (sel ? reinterpret_cast<const void *>(k_sweep<int8_t, true>) : reinterpret_cast<const void *>(k_sweep<int8_t, false>));
-      spin(fn, P->data->K, P->data->K, SW_THREADS, P->data->lds_bytes);
+      spin(fn, P->data->plan.K, P->data->plan.K, SW_THREADS, P->data->plan.lds);
     }
   }
   // The fixed-point engines between a snapshot of the state they start from and the fp64 engine that redoes the sweep if they left
@@ -1574,9 +1656,9 @@ static SweepPlan plan_sweep(const bwgr_panel *P, const SweepArgs &a, bool redo) 
 // what one launch of k_sweep3 / k_sweep3p needs beside the sweep's own arguments; zeroes the launch's slab-dot sums, takes a new epoch
 static void sweep3_args(bwgr_panel *P, const SweepArgs &a, const SweepPlan &pl, Sweep3Args &A) {
   memset(&A, 0, sizeof(A)); A.a = a;
-  for (int d = 0; d < S3_MAXD; ++d) A.gx[d] = P->data->g3x[d];
+  for (int d = 0; d < S3_MAXD; ++d) A.gx[d] = P->data->g3x[d].a;
   A.gp = P->data->gram16 ? (const void *)P->data->gramp16 : P->data->gramp;
-  A.D = P->data->e3_D; A.K3 = pl.K3; A.R3 = pl.R3; A.sub = pl.sub; A.g16 = P->data->gram16 ? 1 : 0;
+  A.D = P->data->plan3.D; A.K3 = pl.K3; A.R3 = pl.R3; A.sub = pl.sub; A.g16 = P->data->gram16 ? 1 : 0;
   A.qsum = P->qsum3; A.lists = P->lists3;
   A.gx12 = P->data->gram16 ? P->data->gx12 : nullptr;
   A.dbg = pl.dbg3; A.pf = pl.pf; A.pf2 = pl.pf2; A.qsplit = pl.qsplit; A.skip_vb = pl.skip_vb;
@@ -1592,9 +1674,9 @@ static void launch_sweep_engine(bwgr_panel *P, const SweepArgs &a_in, const Swee
   const bool sel = (a.flags & SWF_SELECT) != 0;
   if (redo && pl.engine == 2) {   // the fp64 engine's speculative terms (k_spec) of the state just restored
     if ((a.flags & SWF_CENTRE) && sel) {   // the running block sums on the float steps (the fixed-point launch left them on its grid): every block, then the scan
-      SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->data->nblocks;
-      hipLaunchKernelGGL(k_cen_tot, dim3((unsigned)P->data->nblocks), dim3(128), 0, P->stream, all, 0, 2);
-      hipLaunchKernelGGL(k_cen_scan, dim3(1), dim3(1024), 0, P->stream, all, (int)P->data->nblocks, 2);
+      SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->data->plan.nblocks;
+      hipLaunchKernelGGL(k_cen_tot, dim3((unsigned)P->data->plan.nblocks), dim3(128), 0, P->stream, all, 0, 2);
+      hipLaunchKernelGGL(k_cen_scan, dim3(1), dim3(1024), 0, P->stream, all, (int)P->data->plan.nblocks, 2);
     }
     hipLaunchKernelGGL(k_spec<int32_t>, dim3((unsigned)(a.blk_end - a.blk_begin)), dim3(128), 0, P->stream, a, a.blk_begin, sel ? 1 : 0);
   }
@@ -1625,7 +1707,7 @@ static void launch_sweep_engine(bwgr_panel *P, const SweepArgs &a_in, const Swee
     void *args[] = {&a, &A}; spin_launch(L, P->stream, args);
     return;
   }
-  const bool cen2 = P->data->sweep_version >= 2 && (a.flags & SWF_CENTRE) && sel && !P->data->is_f32;
+  const bool cen2 = P->data->plan.pipelined && (a.flags & SWF_CENTRE) && sel && !P->data->is_f32;
   if (cen2) hipLaunchKernelGGL(k_cen_begin, dim3(1), dim3(1024), 0, P->stream, a, redo ? 2 : 1);
   SweepArgs ak = a;
   if (pl.g16) { ak.gramp = P->data->gramp16; ak.gramx = P->data->gramx16; }
@@ -1637,11 +1719,11 @@ static void launch_sweep_engine(bwgr_panel *P, const SweepArgs &a_in, const Swee
 static void launch_sweep_kernel(bwgr_panel *P, const SweepArgs &a, const SweepPlan &pl) {
   const size_t p = (size_t)P->data->p;
   bool guarded = pl.guarded;
-  if (guarded && !P->snap_e && (hipMalloc(&P->snap_e, sizeof(double) * (size_t)P->data->ld) != hipSuccess || hipMalloc(&P->snap_b, sizeof(float) * p) != hipSuccess ||
+  if (guarded && !P->snap_e && (hipMalloc(&P->snap_e, sizeof(double) * (size_t)P->data->plan.ld) != hipSuccess || hipMalloc(&P->snap_b, sizeof(float) * p) != hipSuccess ||
                                 hipMalloc(&P->snap_d, sizeof(float) * p) != hipSuccess || hipMalloc(&P->snap_vb, sizeof(float) * p) != hipSuccess)) { (void)hipGetLastError(); guarded = false; }
   SnapArgs sn;
   sn.e = a.e; sn.se = P->snap_e; sn.b = a.b; sn.d = a.d; sn.vb = (a.flags & SWF_VB_VEC) ? a.vb : nullptr; sn.sb = P->snap_b; sn.sd = P->snap_d; sn.svb = P->snap_vb;
-  sn.ld = P->data->ld; sn.j0 = a.blk_begin * a.m; sn.j1 = (int)std::min<int64_t>(P->data->p, (int64_t)a.blk_end * a.m); sn.sc = a.sc;
+  sn.ld = P->data->plan.ld; sn.j0 = a.blk_begin * a.m; sn.j1 = (int)std::min<int64_t>(P->data->p, (int64_t)a.blk_end * a.m); sn.sc = a.sc;
   if (guarded) hipLaunchKernelGGL(k_range_snapshot, dim3(256), dim3(256), 0, P->stream, sn);
   launch_sweep_engine(P, a, pl, false);
   if (guarded) {
@@ -1687,11 +1769,11 @@ static int launch_sweep(bwgr_panel *P, SweepArgs &a) {
 }
 
 static void fill_panel_args(const bwgr_panel *P, SweepArgs &a) {
-  a.X = P->data->X; a.ld = P->data->ld; a.gram = P->data->gram;
-  a.n = (int)P->data->n; a.p = (int)P->data->p; a.m = P->data->m; a.K = P->data->K; a.R = P->data->R;
-  a.blk_begin = 0; a.blk_end = (int)P->data->nblocks;
+  a.X = P->data->X; a.ld = P->data->plan.ld; a.gram = P->data->gram;
+  a.n = (int)P->data->n; a.p = (int)P->data->p; a.m = P->data->plan.m; a.K = P->data->plan.K; a.R = P->data->plan.R;
+  a.blk_begin = 0; a.blk_end = (int)P->data->plan.nblocks;
   a.xpart = P->xpart; a.xflags = P->xflags; a.stamps = P->stamps; a.ps = P->ps;
-  a.gramx = P->data->gramx; a.gramx2 = P->data->gramx2; a.xspec2 = P->xspec2; a.gramx3 = P->data->gramx3; a.xspec3 = P->xspec3; a.lag = 2; a.nfeed = P->data->nfeed; a.gramp = P->data->gramp; a.pstride = P->data->pstride; a.qpart = P->qpart; a.dgran = P->dgran;
+  a.gramx = P->data->gx[1]; a.gramx2 = P->data->gx[2]; a.xspec2 = P->xspec2; a.gramx3 = P->data->gx[3]; a.xspec3 = P->xspec3; a.lag = 2; a.nfeed = P->data->plan.nfeed; a.gramp = P->data->gramp; a.pstride = P->data->plan.pstride; a.qpart = P->qpart; a.dgran = P->dgran;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1702,7 +1784,7 @@ static int upload(bwgr_panel *P, const void *X, int memloc, int64_t ldx) {
   const int64_t n = P->data->n, p = P->data->p;
   XT *dst = reinterpret_cast<XT *>(P->data->X);
   if (memloc == BWGR_DEVICE) {
-    hipLaunchKernelGGL((k_convert<ST, XT>), dim3(4096), dim3(256), 0, P->stream, reinterpret_cast<const ST *>(X), ldx, dst, P->data->ld, (int)n, (int64_t)0, p, P->data->R, p);
+    hipLaunchKernelGGL((k_convert<ST, XT>), dim3(4096), dim3(256), 0, P->stream, reinterpret_cast<const ST *>(X), ldx, dst, P->data->plan.ld, (int)n, (int64_t)0, p, P->data->plan.R, p);
     HIPCHK(hipGetLastError());
     return BWGR_OK;
   }
@@ -1718,7 +1800,7 @@ static int upload(bwgr_panel *P, const void *X, int memloc, int64_t ldx) {
     // the last column may be shorter than ldx in the caller's allocation: copy n rows of it separately
     const size_t bytes = (size_t)((nc - 1) * col_bytes + n * (int64_t)sizeof(ST));
     HIPCHK(hipMemcpyAsync(stage, reinterpret_cast<const ST *>(X) + j0 * ldx, bytes, hipMemcpyHostToDevice, P->stream));
-    hipLaunchKernelGGL((k_convert<ST, XT>), dim3(2048), dim3(256), 0, P->stream, stage, ldx, dst, P->data->ld, (int)n, j0, nc, P->data->R, p);
+    hipLaunchKernelGGL((k_convert<ST, XT>), dim3(2048), dim3(256), 0, P->stream, stage, ldx, dst, P->data->plan.ld, (int)n, j0, nc, P->data->plan.R, p);
     HIPCHK(hipStreamSynchronize(P->stream));
   }
   return BWGR_OK;
@@ -1729,13 +1811,13 @@ static int upload(bwgr_panel *P, const void *X, int memloc, int64_t ldx) {
 // sums and lists where the data has k_sweep3.  The rest of the scratch comes with the first sweep that needs it; scratch_free frees all.
 static int scratch_alloc(bwgr_panel *P) {
   const PanelData *D = P->data;
-  const size_t nb = (size_t)D->nblocks;
-  if (D->gramx2) HIPCHK(hipMalloc(&P->xspec2, sizeof(double) * nb * SW_MAXM));
-  if (D->gramx3) HIPCHK(hipMalloc(&P->xspec3, sizeof(double) * nb * SW_MAXM));
+  const size_t nb = (size_t)D->plan.nblocks;
+  if (D->plan.xdist >= 2) HIPCHK(hipMalloc(&P->xspec2, sizeof(double) * nb * SW_MAXM));
+  if (D->plan.xdist >= 3) HIPCHK(hipMalloc(&P->xspec3, sizeof(double) * nb * SW_MAXM));
   HIPCHK(hipMalloc(&P->ps.spec, sizeof(SpecBuf) * nb));
-  if (D->sweep_version >= 2) HIPCHK(hipMalloc(&P->ps.quick, sizeof(QuickBuf) * nb));
+  if (D->plan.pipelined) HIPCHK(hipMalloc(&P->ps.quick, sizeof(QuickBuf) * nb));
   HIPCHK(hipMalloc(&P->ps.blocks, sizeof(StageBuf) * nb));
-  HIPCHK(hipMalloc(&P->xpart, sizeof(double) * 2 * (size_t)D->K * SW_MAXM));
+  HIPCHK(hipMalloc(&P->xpart, sizeof(double) * 2 * (size_t)D->plan.K * SW_MAXM));
   HIPCHK(alloc_exchange(P));
 #if defined(BWGR_STAMPS) || defined(BWGR_EXPERIMENTS)
   HIPCHK(hipMalloc(&P->stamps, sizeof(unsigned long long) * 256));
@@ -1768,9 +1850,10 @@ extern "C" int bwgr_panel_destroy(bwgr_panel *P) {
   scratch_free(P);
   if (P->own_stream) hipStreamDestroy(P->own_stream);
   if (P->is_root) {
-    for (int d = 0; d < S3_MAXD; ++d) if (D->g3own[d]) hipFree(D->g3x[d]);
+    for (auto &g : D->g3x) if (g.own) hipFree(g.a);
+    for (void *g : D->gx) hipFree(g);
     for (int d = 0; d < S2W_MAXDIST; ++d) hipFree(D->gxt[d]);
-    hipFree(D->X); hipFree(D->gram); hipFree(D->gramx); hipFree(D->gramx2); hipFree(D->gramx3); hipFree(D->gramp16); hipFree(D->gramx16); hipFree(D->gram16_bad); hipFree(D->gramp);
+    hipFree(D->X); hipFree(D->gram); hipFree(D->gramp16); hipFree(D->gramx16); hipFree(D->gram16_bad); hipFree(D->gramp);
     hipFree(D->gx12); hipFree(D->xx); hipFree(D->vx); hipFree(D->msx_dev); hipFree(D->xmax_dev); hipFree(D->csum); hipFree(D->xxc);
     for (hipStream_t q : D->pair_streams) hipStreamDestroy(q);
     delete D;
@@ -1781,225 +1864,142 @@ extern "C" int bwgr_panel_destroy(bwgr_panel *P) {
   return BWGR_OK;
 }
 
-static int panel_build_gram(bwgr_panel *P);
-static int panel_setup(bwgr_panel *P) {
-  const int p = (int)P->data->p, n = (int)P->data->n;
-  // a10: xx, vx, MSx
-  const int wpb = 4;
-  if (P->data->is_f32) hipLaunchKernelGGL(k_stats<float>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const float *)P->data->X, P->data->R, n, p, P->data->xx, P->data->vx);
-  else hipLaunchKernelGGL(k_stats<int8_t>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const int8_t *)P->data->X, P->data->R, n, p, P->data->xx, P->data->vx);
+// a10's xx, vx and MSx, and an int8 panel's largest |x|
+static int panel_measure(bwgr_panel *P) {
+  PanelData *D = P->data;
+  const int p = (int)D->p, n = (int)D->n, wpb = 4;
+  if (D->is_f32) hipLaunchKernelGGL(k_stats<float>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const float *)D->X, D->plan.R, n, p, D->xx, D->vx);
+  else hipLaunchKernelGGL(k_stats<int8_t>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const int8_t *)D->X, D->plan.R, n, p, D->xx, D->vx);
   HIPCHK(hipGetLastError());
   {
     DevBufs bufs;
     double *part = bufs.get<double>(256);
     if (!part) return fail(BWGR_ENOMEM, "panel_create: device allocation failed");
-    CHK(sum_floats(P->stream, P->data->vx, (int64_t)p, part, P->data->msx_dev, &P->data->MSx));
+    CHK(sum_floats(P->stream, D->vx, (int64_t)p, part, D->msx_dev, &D->MSx));
   }
-  if (!P->data->is_f32) {
-    if (!P->data->xmax_dev) HIPCHK(hipMalloc(&P->data->xmax_dev, sizeof(int)));
-    HIPCHK(hipMemsetAsync(P->data->xmax_dev, 0, sizeof(int), P->stream));
-    hipLaunchKernelGGL(k_absmax_i8, dim3(2048), dim3(256), 0, P->stream, (const int8_t *)P->data->X, P->data->x_bytes, P->data->xmax_dev);
+  if (!D->is_f32) {
+    if (!D->xmax_dev) HIPCHK(hipMalloc(&D->xmax_dev, sizeof(int)));
+    HIPCHK(hipMemsetAsync(D->xmax_dev, 0, sizeof(int), P->stream));
+    hipLaunchKernelGGL(k_absmax_i8, dim3(2048), dim3(256), 0, P->stream, (const int8_t *)D->X, D->plan.x_bytes, D->xmax_dev);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&P->data->xmax, P->data->xmax_dev, sizeof(int), hipMemcpyDeviceToHost, P->stream));
+    HIPCHK(hipMemcpyAsync(&D->xmax, D->xmax_dev, sizeof(int), hipMemcpyDeviceToHost, P->stream));
     HIPCHK(hipStreamSynchronize(P->stream));
-  }
-  CHK(panel_build_gram(P));
-  // the trajectory engine for the selection models (int8 panels that asked for it; BWGR_SWEEP=2 keeps k_sweep2)
-  if (P->data->want3 && !P->data->is_f32 && P->data->sweep_version == 2 && P->data->sw.sweep != '2') {
-    P->data->sweep_version = 3;
-    CHK(sweep3_build(P));
   }
   return BWGR_OK;
 }
 
-// cross Gram blocks X_{b-dist}' X_b of an int8 panel, b = dist .. nblocks-1, into g[b][m][m] (int32, exact)
-static void launch_gramx_i8(bwgr_panel *P, int32_t *g, int dist) {
-  const int p = (int)P->data->p, m = P->data->m, TJ = m / 16;
-  const unsigned nbx = (unsigned)(P->data->nblocks - dist);
-  const size_t lds = (size_t)2 * m * 33 * sizeof(int32_t);
-  const int8_t *X = (const int8_t *)P->data->X;
-  if (m == 128) hipLaunchKernelGGL(k_gram_mfma_i8, dim3(nbx), dim3(256), 0, P->stream, X, P->data->ld, P->data->R, p, g, dist);
-  else switch (TJ) {
-    case 1: hipLaunchKernelGGL(k_gramx_i8<1>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
-    case 2: hipLaunchKernelGGL(k_gramx_i8<2>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
-    case 3: hipLaunchKernelGGL(k_gramx_i8<3>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
-    case 4: hipLaunchKernelGGL(k_gramx_i8<4>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
-    case 5: hipLaunchKernelGGL(k_gramx_i8<5>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
-    case 6: hipLaunchKernelGGL(k_gramx_i8<6>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
-    case 7: hipLaunchKernelGGL(k_gramx_i8<7>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
-    default: hipLaunchKernelGGL(k_gramx_i8<8>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
-  }
+// f(std::integral_constant<int, TJ>()) with TJ = tj, 1 <= tj <= MAXTJ (beyond: MAXTJ): the Gram kernels' block width in sixteens as a template parameter
+template <int MAXTJ, typename F> static void with_tj(int tj, F f) {
+  if constexpr (MAXTJ > 1) { if (tj < MAXTJ) return with_tj<MAXTJ - 1>(tj, f); }
+  f(std::integral_constant<int, MAXTJ>());
+}
+// Gram blocks X_{b-dist}' X_b of the resident X, b = dist .. nblocks-1, into g[b][m][m]: int32, exact (fp64 for float panels); dist = 0: the diagonal blocks
+static void launch_gram(bwgr_panel *P, void *g, int dist) {
+  const PanelPlan &pl = P->data->plan;
+  const int p = (int)P->data->p, m = pl.m, R = pl.R, tiles = dist ? 2 : 1;
+  const dim3 grid((unsigned)(pl.nblocks - dist)), block(256);
+  const int64_t ld = pl.ld; hipStream_t st = P->stream;
+  const size_t ldsf = (size_t)tiles * m * 65 * sizeof(float), ldsi = (size_t)tiles * m * 33 * sizeof(int32_t);   // the kernels' LDS tiles
+  const float *Xf = (const float *)P->data->X; double *gd = (double *)g;
+  const int8_t *Xi = (const int8_t *)P->data->X; int32_t *gi = (int32_t *)g;
+  const bool f32 = P->data->is_f32 != 0;
+  if (!f32 && m == 128) hipLaunchKernelGGL(k_gram_mfma_i8, grid, block, 0, st, Xi, ld, R, p, gi, dist);
+  else if (!f32 && dist) with_tj<8>(m / 16, [&](auto tj) { hipLaunchKernelGGL(k_gramx_i8<decltype(tj)::value>, grid, block, ldsi, st, Xi, ld, R, p, m, gi, dist); });
+  else if (f32 && !dist) with_tj<4>(m / 16, [&](auto tj) { hipLaunchKernelGGL(k_gram_f32<decltype(tj)::value>, grid, block, ldsf, st, Xf, ld, R, p, m, gd); });
+  else if (!dist) with_tj<8>(m / 16, [&](auto tj) { hipLaunchKernelGGL(k_gram_i8<decltype(tj)::value>, grid, block, ldsi, st, Xi, ld, R, p, m, gi); });
+  else with_tj<4>(m / 16, [&](auto tj) { hipLaunchKernelGGL(k_gramx_f32<decltype(tj)::value>, grid, block, ldsf, st, Xf, ld, R, p, m, gd, dist); });
 }
 
-// diagonal, off-diagonal and packed Gram blocks of the resident X
+// The Gram arrays the plan lists, from the resident X, and what they say: whether the 16-bit copies are exact (gram16) and how far the affine
+// engine's byte planes reach (winv_nd).  Runs again wherever a scratch panel's rows or columns change.
 static int panel_build_gram(bwgr_panel *P) {
-  const int p = (int)P->data->p;
-  const int m = P->data->m, TJ = m / 16;
-  if (P->data->is_f32) {
-    const size_t lds = (size_t)m * 65 * sizeof(float);
-    double *g = (double *)P->data->gram; const float *X = (const float *)P->data->X;
-    switch (TJ) {
-      case 1: hipLaunchKernelGGL(k_gram_f32<1>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
-      case 2: hipLaunchKernelGGL(k_gram_f32<2>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
-      case 3: hipLaunchKernelGGL(k_gram_f32<3>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
-      default: hipLaunchKernelGGL(k_gram_f32<4>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
-    }
-  } else {
-    const size_t lds = (size_t)m * 33 * sizeof(int32_t);
-    int32_t *g = (int32_t *)P->data->gram; const int8_t *X = (const int8_t *)P->data->X;
-    if (m == 128) hipLaunchKernelGGL(k_gram_mfma_i8, dim3(P->data->nblocks), dim3(256), 0, P->stream, X, P->data->ld, P->data->R, p, g, 0);
-    else switch (TJ) {
-      case 1: hipLaunchKernelGGL(k_gram_i8<1>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
-      case 2: hipLaunchKernelGGL(k_gram_i8<2>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
-      case 3: hipLaunchKernelGGL(k_gram_i8<3>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
-      case 4: hipLaunchKernelGGL(k_gram_i8<4>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
-      case 5: hipLaunchKernelGGL(k_gram_i8<5>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
-      case 6: hipLaunchKernelGGL(k_gram_i8<6>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
-      case 7: hipLaunchKernelGGL(k_gram_i8<7>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
-      default: hipLaunchKernelGGL(k_gram_i8<8>, dim3(P->data->nblocks), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g); break;
-    }
-  }
+  PanelData *D = P->data; const PanelPlan &pl = D->plan;
+  const int m = pl.m;
+  launch_gram(P, D->gram, 0);
   HIPCHK(hipGetLastError());
-  for (int dist = 1; dist <= 3; ++dist) {   // off-diagonal blocks (blk-dist, blk): the cross terms of the lag-2 / 3 / 4 pipelines
-    if (P->data->nblocks <= dist || dist > P->data->gram_maxdist || (dist == 2 && !P->data->gramx2) || (dist == 3 && !P->data->gramx3)) continue;
-    const unsigned nbx = (unsigned)(P->data->nblocks - dist);
-    if (P->data->is_f32) {
-      const size_t lds = (size_t)2 * m * 65 * sizeof(float);
-      double *g = (double *)(dist == 1 ? P->data->gramx : dist == 2 ? P->data->gramx2 : P->data->gramx3); const float *X = (const float *)P->data->X;
-      switch (TJ) {
-        case 1: hipLaunchKernelGGL(k_gramx_f32<1>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
-        case 2: hipLaunchKernelGGL(k_gramx_f32<2>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
-        case 3: hipLaunchKernelGGL(k_gramx_f32<3>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
-        default: hipLaunchKernelGGL(k_gramx_f32<4>, dim3(nbx), dim3(256), lds, P->stream, X, P->data->ld, P->data->R, p, m, g, dist); break;
-      }
-    } else {
-      launch_gramx_i8(P, (int32_t *)(dist == 1 ? P->data->gramx : dist == 2 ? P->data->gramx2 : P->data->gramx3), dist);
-    }
+  for (int dist = 1; dist <= pl.xdist && dist < pl.nblocks; ++dist) {   // off-diagonal blocks (blk-dist, blk): the cross terms of the lag-2 / 3 / 4 pipelines
+    launch_gram(P, D->gx[dist], dist);
     HIPCHK(hipGetLastError());
   }
-  if (P->data->is_f32) hipLaunchKernelGGL(k_gram_pack<double>, dim3((unsigned)P->data->nblocks), dim3(256), 0, P->stream, (const double *)P->data->gram, (double *)P->data->gramp, m, P->data->pstride, P->data->nblocks);
-  else hipLaunchKernelGGL(k_gram_pack<int32_t>, dim3((unsigned)P->data->nblocks), dim3(256), 0, P->stream, (const int32_t *)P->data->gram, (int32_t *)P->data->gramp, m, P->data->pstride, P->data->nblocks);
+  if (D->is_f32) hipLaunchKernelGGL(k_gram_pack<double>, dim3((unsigned)pl.nblocks), dim3(256), 0, P->stream, (const double *)D->gram, (double *)D->gramp, m, pl.pstride, pl.nblocks);
+  else hipLaunchKernelGGL(k_gram_pack<int32_t>, dim3((unsigned)pl.nblocks), dim3(256), 0, P->stream, (const int32_t *)D->gram, (int32_t *)D->gramp, m, pl.pstride, pl.nblocks);
   HIPCHK(hipGetLastError());
-  P->data->gram16 = false;
-  if (P->data->gramp16) {
-    HIPCHK(hipMemsetAsync(P->data->gram16_bad, 0, sizeof(int), P->stream));
-    hipLaunchKernelGGL(k_gram_narrow, dim3(2048), dim3(256), 0, P->stream, (const int32_t *)P->data->gramp, P->data->gramp16, (int64_t)P->data->nblocks * P->data->pstride, P->data->gram16_bad);
-    if (P->data->nblocks > 1)
-      hipLaunchKernelGGL(k_gram_narrow, dim3(2048), dim3(256), 0, P->stream, (const int32_t *)P->data->gramx + (size_t)m * m, P->data->gramx16 + (size_t)m * m, (int64_t)(P->data->nblocks - 1) * m * m, P->data->gram16_bad);
+  D->gram16 = false;
+  if (pl.has16) {
+    HIPCHK(hipMemsetAsync(D->gram16_bad, 0, sizeof(int), P->stream));
+    hipLaunchKernelGGL(k_gram_narrow, dim3(2048), dim3(256), 0, P->stream, (const int32_t *)D->gramp, D->gramp16, (int64_t)pl.nblocks * pl.pstride, D->gram16_bad);
+    if (pl.nblocks > 1)
+      hipLaunchKernelGGL(k_gram_narrow, dim3(2048), dim3(256), 0, P->stream, (const int32_t *)D->gx[1] + (size_t)m * m, D->gramx16 + (size_t)m * m, (int64_t)(pl.nblocks - 1) * m * m, D->gram16_bad);
     HIPCHK(hipGetLastError());
     int bad = 1;
-    HIPCHK(hipMemcpyAsync(&bad, P->data->gram16_bad, sizeof(int), hipMemcpyDeviceToHost, P->stream));
+    HIPCHK(hipMemcpyAsync(&bad, D->gram16_bad, sizeof(int), hipMemcpyDeviceToHost, P->stream));
     HIPCHK(hipStreamSynchronize(P->stream));
-    P->data->gram16 = (bad == 0) && P->data->sw.gram16;   // BWGR_GRAM16=0 forces the 32-bit staging (A/B tests)
+    D->gram16 = (bad == 0) && D->sw.gram16;   // BWGR_GRAM16=0 forces the 32-bit staging (A/B tests)
   }
   // the affine sweeps' sequencer (sweep2w.hip.h) takes the cross blocks as biased byte planes: built where every entry fits 16 bits
-  P->data->winv_nd = 0;
-  if (!P->data->is_f32 && P->data->gram16 && P->data->sw.winv && m <= SW_MAXM) {
-    HIPCHK(hipMemsetAsync(P->data->gram16_bad, 0, sizeof(int), P->stream));
+  D->winv_nd = 0;
+  if (D->gram16 && pl.wdist > 0) {
+    HIPCHK(hipMemsetAsync(D->gram16_bad, 0, sizeof(int), P->stream));
     int nd = 0;
     DevBufs bufs;
-    int32_t *tmpx = nullptr;   // distances 4 and 5 (pipelines five and six blocks deep; main panels only): built here, kept as planes only
-    for (int dist = 1; dist <= S2W_MAXDIST; ++dist) {
-      const int32_t *src = (const int32_t *)(dist == 1 ? P->data->gramx : dist == 2 ? P->data->gramx2 : dist == 3 ? P->data->gramx3 : nullptr);
+    int32_t *tmpx = nullptr;   // the distances beyond the panel's own arrays: built here, kept as planes only
+    for (int dist = 1; dist <= pl.wdist; ++dist) {
       if (dist > S2W_NEARD) {
-        if (!P->data->want3 || P->data->gram_maxdist < S2W_NEARD || P->data->nblocks <= dist || dist > P->data->sw.wlag_cap - 1) break;
-        if (!tmpx && !(tmpx = bufs.get<int32_t>((size_t)P->data->nblocks * m * m))) { (void)hipGetLastError(); break; }
-        launch_gramx_i8(P, tmpx, dist);
-        src = tmpx;
+        if (!tmpx && !(tmpx = bufs.get<int32_t>((size_t)pl.nblocks * m * m))) { (void)hipGetLastError(); break; }
+        launch_gram(P, tmpx, dist);
       }
-      if (P->data->nblocks <= dist || (dist <= S2W_NEARD && dist > P->data->gram_maxdist) || !src) break;
-      if (!P->data->gxt[dist - 1]) HIPCHK(hipMalloc(&P->data->gxt[dist - 1], (size_t)P->data->nblocks * S2W_PBYTES));
-      hipLaunchKernelGGL(k_gx_planes, dim3(4096), dim3(256), 0, P->stream, src, P->data->gxt[dist - 1], m, (int64_t)P->data->nblocks, dist, P->data->gram16_bad);
+      const int32_t *src = dist > S2W_NEARD ? tmpx : (const int32_t *)D->gx[dist];
+      if (!D->gxt[dist - 1]) HIPCHK(hipMalloc(&D->gxt[dist - 1], (size_t)pl.nblocks * S2W_PBYTES));
+      hipLaunchKernelGGL(k_gx_planes, dim3(4096), dim3(256), 0, P->stream, src, D->gxt[dist - 1], m, (int64_t)pl.nblocks, dist, D->gram16_bad);
       HIPCHK(hipGetLastError());
       nd = dist;
     }
     int bad = 1;
-    HIPCHK(hipMemcpyAsync(&bad, P->data->gram16_bad, sizeof(int), hipMemcpyDeviceToHost, P->stream));
+    HIPCHK(hipMemcpyAsync(&bad, D->gram16_bad, sizeof(int), hipMemcpyDeviceToHost, P->stream));
     HIPCHK(hipStreamSynchronize(P->stream));
-    P->data->winv_nd = bad ? 0 : nd;
+    D->winv_nd = bad ? 0 : nd;
   }
   HIPCHK(hipStreamSynchronize(P->stream));
   return BWGR_OK;
 }
 
-// The data of a panel of n rows x p markers -- its geometry and every device array, no values yet -- and its root handle, without the sweep
-// scratch (scratch_alloc, once the data is built).  near_only: bwgr_em's scratch panel, which sweeps at lag 2 on the 32-bit Gram blocks (no
-// blocks beyond distance 1, no 16-bit copies).
-static int panel_alloc(bwgr_panel **out, int is_f32, int64_t n, int64_t p, int device, int block, int nwg, const Switches &sw, bool near_only = false) {
+// what only the data can say, each from the last: the columns' statistics, the Gram arrays and their verdicts, k_sweep3's share where the plan tries it
+static int panel_setup(bwgr_panel *P) {
+  CHK(panel_measure(P));
+  CHK(panel_build_gram(P));
+  return sweep3_build(P);
+}
+
+// The data of a panel of n rows x p markers -- its plan and every device array the plan lists, no values yet -- and its root handle, without
+// the sweep scratch (scratch_alloc, once the data is built)
+static int panel_alloc(bwgr_panel **out, int is_f32, int64_t n, int64_t p, int device, int block, int nwg, PanelKind kind, const Switches &sw) {
   *out = nullptr;
-  if (n < 2 || p < 1) return fail(BWGR_EINVAL, "panel: need n >= 2, p >= 1 (n=%lld p=%lld)", (long long)n, (long long)p);
-  if (n > 0x7FFFFF00ll || p > 0x7FFFFF00ll) return fail(BWGR_EINVAL, "panel: n and p must fit 31 bits");
+  CHK(panel_range(n, p));
   CHK(require_device(device));
+  PanelPlan pl;
+  CHK(plan_panel(pl, is_f32 != 0, n, p, block, nwg, kind, sw));
   bwgr_panel *P = new bwgr_panel();
-  P->data = new PanelData(); P->is_root = true;
+  PanelData *D = P->data = new PanelData(); P->is_root = true;
   Guard drop([&] { bwgr_panel_destroy(P); });   // until the panel is handed over
-  P->data->device = device; P->data->n = n; P->data->p = p; P->data->is_f32 = is_f32; P->data->sw = sw; P->data->gram_maxdist = near_only ? 1 : 3;
-  const int mmax = P->data->is_f32 ? 64 : SW_MAXM;
-  int m = block > 0 ? block : mmax;
-  if (m > mmax) return fail(BWGR_EINVAL, "panel_create: block %d > %d (limit for this genotype type)", m, mmax);
-  m = (int)std::min<int64_t>(m, ((p + 15) / 16) * 16);
-  m = ((m + 15) / 16) * 16;
-  P->data->m = m;
-  const int Rmax = P->data->is_f32 ? max_slab_rows<float>(m) : max_slab_rows<int8_t>(m);
-  // the pipelined engine keeps three tiles per streamer, so it takes fewer rows per slab than k_sweep at small blocks:
-  // prefer the largest slab it fits (unless that needs more workgroups than the chip has CUs, or k_sweep is forced)
-  int Rpick = Rmax;
-  {
-    int R2 = 0;
-    for (int Rt = 128; Rt <= Rmax; Rt += 128)
-      if ((P->data->is_f32 ? sweep2_lds_bytes<float>(m, Rt) : sweep2_lds_bytes<int8_t>(m, Rt)) <= (size_t)160 * 1024 &&
-          (P->data->is_f32 || (size_t)m * Rt <= S2I_TILE_BYTES_MAX)) R2 = Rt;   // (an int8 tile must fit its movers' registers)
-    if (sw.sweep != '1' && R2 > 0 && (n + R2 - 1) / R2 + 1 + 6 <= 256) Rpick = R2;
+  D->device = device; D->n = n; D->p = p; D->is_f32 = is_f32; D->sw = sw; D->plan = pl;
+  const size_t packed = (size_t)pl.nblocks * std::max(pl.pstride, 8);
+  HIPCHK(hipMalloc(&D->X, pl.x_bytes));
+  HIPCHK(hipMalloc(&D->gram, pl.gram_bytes));
+  for (int d = 1; d <= pl.xdist; ++d) HIPCHK(hipMalloc(&D->gx[d], pl.gram_bytes));
+  HIPCHK(hipMalloc(&D->gramp, packed * (is_f32 ? 8 : 4)));
+  if (pl.has16) {
+    HIPCHK(hipMalloc(&D->gramp16, packed * 2));
+    HIPCHK(hipMalloc(&D->gramx16, (size_t)pl.nblocks * pl.m * pl.m * 2));
+    HIPCHK(hipMalloc(&D->gram16_bad, sizeof(int)));
   }
-  int K = nwg > 0 ? nwg : (int)((n + Rpick - 1) / Rpick);
-  int R = (int)((((n + K - 1) / K) + 127) / 128) * 128;
-  if (K > 256 || R > Rmax)
-    return fail(BWGR_EINVAL, "panel_create: n=%lld needs %d slab workgroups of %d rows (limits: 256 workgroups, %d rows)", (long long)n, K, R, Rmax);
-  P->data->K = K; P->data->R = R; P->data->ld = (int64_t)K * R;
-  P->data->nblocks = (p + m - 1) / m;
-  if (P->data->nblocks >= (1ll << 24)) return fail(BWGR_EINVAL, "panel_create: %lld marker blocks; the delta granules carry a 24-bit block epoch", (long long)P->data->nblocks);
-  P->data->lds_bytes = P->data->is_f32 ? sweep_lds_bytes<float>(m, R) : sweep_lds_bytes<int8_t>(m, R);
-  P->data->lds2_bytes = P->data->is_f32 ? sweep2_lds_bytes<float>(m, R) : sweep2_lds_bytes<int8_t>(m, R);
-  if (!P->data->is_f32 && s2i_lds_bytes(m, R, 4) <= (size_t)160 * 1024) {
-    P->data->lag4_ok = true;
-    P->data->lds2_bytes = std::max(P->data->lds2_bytes, s2i_lds_bytes(m, R, 4));
-  }
-  {
-    P->data->sweep_version = (sw.sweep == '1') ? 1 : 2;   // A/B switch for tests and profiling
-    P->data->nfeed = std::min(6, std::max(2, (K + 39) / 40 + 1));   // K = 40: 2, K = 79: 3, K >= 161: 6
-    if (sw.nfeed >= 1 && sw.nfeed <= 6) P->data->nfeed = sw.nfeed;   // experiments
-    if (P->data->lds2_bytes > (size_t)160 * 1024 || K + 1 + P->data->nfeed > 256) P->data->sweep_version = 1;
-    if (!P->data->is_f32 && (size_t)m * R > S2I_TILE_BYTES_MAX) P->data->sweep_version = 1;
-  }
-  P->data->x_bytes = (size_t)P->data->ld * (size_t)p * (P->data->is_f32 ? 4 : 1);
-  P->data->gram_bytes = (size_t)P->data->nblocks * m * m * (P->data->is_f32 ? 8 : 4);   // per Gram array (diagonal blocks; off-diagonal blocks)
-  HIPCHK(hipMalloc(&P->data->X, P->data->x_bytes));
-  HIPCHK(hipMalloc(&P->data->gram, P->data->gram_bytes));
-  HIPCHK(hipMalloc(&P->data->gramx, P->data->gram_bytes));
-  if (P->data->sweep_version >= 2 && P->data->nblocks > 2 && !near_only)   // distance-2 blocks: the selection models' lag-3 pipeline
-    HIPCHK(hipMalloc(&P->data->gramx2, P->data->gram_bytes));
-  if (P->data->sweep_version >= 2 && !P->data->is_f32 && P->data->nblocks > 3 && P->data->lag4_ok && sw.lag != '2' && sw.lag != '3' && !near_only)   // distance-3 blocks: the lag-4 pipeline
-    HIPCHK(hipMalloc(&P->data->gramx3, P->data->gram_bytes));
-  P->data->pstride = ((m * (m - 1) / 2 + 7) / 8) * 8;
-  HIPCHK(hipMalloc(&P->data->gramp, (size_t)P->data->nblocks * std::max(P->data->pstride, 8) * (P->data->is_f32 ? 8 : 4)));
-  if (!P->data->is_f32 && P->data->sweep_version >= 2 && !near_only) {
-    HIPCHK(hipMalloc(&P->data->gramp16, (size_t)P->data->nblocks * std::max(P->data->pstride, 8) * 2));
-    HIPCHK(hipMalloc(&P->data->gramx16, (size_t)P->data->nblocks * m * m * 2));
-    HIPCHK(hipMalloc(&P->data->gram16_bad, sizeof(int)));
-  }
-  HIPCHK(hipMalloc(&P->data->xx, sizeof(float) * p));
-  HIPCHK(hipMalloc(&P->data->vx, sizeof(float) * p));
-  HIPCHK(hipMalloc(&P->data->msx_dev, sizeof(float)));
+  HIPCHK(hipMalloc(&D->xx, sizeof(float) * p));
+  HIPCHK(hipMalloc(&D->vx, sizeof(float) * p));
+  HIPCHK(hipMalloc(&D->msx_dev, sizeof(float)));
   for (const void *f : {reinterpret_cast<const void *>(k_sweep<int8_t, true>), reinterpret_cast<const void *>(k_sweep<int8_t, false>), reinterpret_cast<const void *>(k_sweep<float, true>),
                         reinterpret_cast<const void *>(k_sweep<float, false>), reinterpret_cast<const void *>(k_sweep2<int8_t, true>), reinterpret_cast<const void *>(k_sweep2<int8_t, false>),
                         reinterpret_cast<const void *>(k_sweep2<int8_t, true, uint16_t>), reinterpret_cast<const void *>(k_sweep2<float, true>), reinterpret_cast<const void *>(k_sweep2<float, false>),
                         reinterpret_cast<const void *>(k_sweep2w<true>), reinterpret_cast<const void *>(k_sweep2w<false>), reinterpret_cast<const void *>(k_affine_inv)})
     HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#ifdef BWGR_EXPERIMENTS
-  if (!P->data->is_f32) P->data->ldsw_bytes = s2w_lds_bytes(m, R, sw.wlag_timing ? sw.wlag_timing : 6);
-#else
-  if (!P->data->is_f32) P->data->ldsw_bytes = s2w_lds_bytes(m, R, 6);
-#endif   // (room for the deepest pipeline BWGR_WLAG can ask for)
   drop.release();
   *out = P;
   return BWGR_OK;
@@ -2013,9 +2013,8 @@ extern "C" int bwgr_panel_create(bwgr_panel **out, const void *X, int xtype, int
   if (xtype != BWGR_X_I8 && xtype != BWGR_X_F32 && xtype != BWGR_X_F64) return fail(BWGR_EINVAL, "panel_create: bad xtype %d", xtype);
   if (memloc != BWGR_HOST && memloc != BWGR_DEVICE) return fail(BWGR_EINVAL, "panel_create: bad memloc %d", memloc);
   bwgr_panel *P = nullptr;
-  CHK(panel_alloc(&P, xtype != BWGR_X_I8, n, p, device, block, nwg, read_switches()));
+  CHK(panel_alloc(&P, xtype != BWGR_X_I8, n, p, device, block, nwg, PANEL_MAIN, read_switches()));
   Guard drop([&] { bwgr_panel_destroy(P); });
-  P->data->want3 = true;
   if (xtype == BWGR_X_I8) CHK((upload<int8_t, int8_t>(P, X, memloc, ldx)));
   else if (xtype == BWGR_X_F32) CHK((upload<float, float>(P, X, memloc, ldx)));
   else CHK((upload<double, float>(P, X, memloc, ldx)));
@@ -2063,8 +2062,8 @@ extern "C" int bwgr_panel_max_concurrent(const bwgr_panel *P, int selection, int
   const SweepPlan pl = plan_sweep(P, a, false);
   // selection on a panel with k_sweep3: the device sends a chain above the engine threshold to k_sweep2 (K + 1 + feeders), and a sweep that
   // leaves the fixed-point range is redone there: the larger of the two (K3 + 1: the streamers of chains side by side, never the solo ones)
-  int wgs = P->data->K + 1 + pl.nfeed;
-  if (pl.engine == 3) wgs = std::max(P->data->K3 + 1, wgs);
+  int wgs = P->data->plan.K + 1 + pl.nfeed;
+  if (pl.engine == 3) wgs = std::max(P->data->plan3.K3 + 1, wgs);
   if (pl.engine == 4) wgs = pl.spins[0].resident;   // streamers, sequencer, L2 prefetchers (the launch's other workgroups leave at once)
   // one sweep workgroup per CU even where the LDS would admit two (small blocks): measured, sharing a CU costs more than it adds
   *count = std::max(1, prop.multiProcessorCount / wgs);
@@ -2077,10 +2076,10 @@ extern "C" int bwgr_panel_max_concurrent(const bwgr_panel *P, int selection, int
 extern "C" int bwgr_panel_max_pairs(const bwgr_panel *P, int *pairs) {
   if (!P || !pairs) return fail(BWGR_EINVAL, "null pointer");
   *pairs = 0;
-  if (!P->data->e3_ready || s3p_streamer_lds(P->data->R3) > (size_t)160 * 1024) return BWGR_OK;
+  if (!P->data->e3_ready || s3p_streamer_lds(P->data->plan3.R3) > (size_t)160 * 1024) return BWGR_OK;
   const int cus = device_cus(P->data->device);
   if (cus < 1) return fail(BWGR_EHIP, "panel_max_pairs: no device properties");
-  *pairs = std::max(1, (cus - 40) / (P->data->K3 + 2));
+  *pairs = std::max(1, (cus - 40) / (P->data->plan3.K3 + 2));
   if (P->data->sw.max_pairs > 0) *pairs = P->data->sw.max_pairs;
   return BWGR_OK;
 }
@@ -2102,8 +2101,8 @@ extern "C" int bwgr_panel_set_stream(bwgr_panel *P, void *hip_stream) {
 
 extern "C" int bwgr_panel_info(const bwgr_panel *P, int64_t info[8]) {
   if (!P || !info) return fail(BWGR_EINVAL, "null pointer");
-  info[0] = P->data->n; info[1] = P->data->p; info[2] = P->data->ld; info[3] = P->data->m; info[4] = P->data->K; info[5] = P->data->R;
-  info[6] = (int64_t)P->data->x_bytes; info[7] = (int64_t)(2 * P->data->gram_bytes);
+  info[0] = P->data->n; info[1] = P->data->p; info[2] = P->data->plan.ld; info[3] = P->data->plan.m; info[4] = P->data->plan.K; info[5] = P->data->plan.R;
+  info[6] = (int64_t)P->data->plan.x_bytes; info[7] = (int64_t)(2 * P->data->plan.gram_bytes);
   return BWGR_OK;
 }
 
@@ -2112,7 +2111,7 @@ extern "C" int bwgr_panel_pipeline(const bwgr_panel *P, int selection, int info[
   SweepArgs a{}; a.flags = selection ? SWF_SELECT : 0u;
   const SweepPlan pl = plan_sweep(P, a, false);
   info[0] = pl.engine;
-  info[1] = pl.engine == 3 ? P->data->e3_D : pl.lag;
+  info[1] = pl.engine == 3 ? P->data->plan3.D : pl.lag;
   info[2] = pl.engine == 3 ? 0 : pl.nfeed;
   info[3] = P->data->is_f32 ? 0 : (P->data->gram16 ? 16 : 32);
   return BWGR_OK;
@@ -2132,12 +2131,12 @@ extern "C" int bwgr_panel_stats(bwgr_panel *P, float *xx, float *vx, float *MSx)
 // ------------------------------------------------------------------------------------------------
 // row gather of the resident panel P into the subsample panel PB (rows use_d[0..nbag), device array); KMUP2's H = X(Use, j)
 static void launch_gather_rows(bwgr_panel *P, bwgr_panel *PB, const int *use_d, int64_t nbag) {
-  if (P->data->is_f32) hipLaunchKernelGGL(k_gather_rows<float>, dim3(4096), dim3(256), 0, P->stream, (const float *)P->data->X, P->data->R, use_d, (int)nbag, (float *)PB->data->X, PB->data->R, PB->data->ld, P->data->p);
-  else if (P->data->ld <= 64 * 1024) {   // a column fits the LDS: stage, pick, write in 16-byte pieces
-    const int mpw = (int)std::max<int64_t>(1, std::min<int64_t>(8, (32 * 1024) / P->data->ld));   // ~30 KB of LDS per workgroup: five of them per CU
-    hipLaunchKernelGGL(k_gather_rows_i8, dim3((unsigned)((P->data->p + mpw - 1) / mpw)), dim3(256), (size_t)mpw * P->data->ld, P->stream, (const int8_t *)P->data->X, P->data->R, P->data->ld,
-                       use_d, (int)nbag, (int8_t *)PB->data->X, PB->data->R, PB->data->ld, P->data->p, mpw);
-  } else hipLaunchKernelGGL(k_gather_rows<int8_t>, dim3(4096), dim3(256), 0, P->stream, (const int8_t *)P->data->X, P->data->R, use_d, (int)nbag, (int8_t *)PB->data->X, PB->data->R, PB->data->ld, P->data->p);
+  if (P->data->is_f32) hipLaunchKernelGGL(k_gather_rows<float>, dim3(4096), dim3(256), 0, P->stream, (const float *)P->data->X, P->data->plan.R, use_d, (int)nbag, (float *)PB->data->X, PB->data->plan.R, PB->data->plan.ld, P->data->p);
+  else if (P->data->plan.ld <= 64 * 1024) {   // a column fits the LDS: stage, pick, write in 16-byte pieces
+    const int mpw = (int)std::max<int64_t>(1, std::min<int64_t>(8, (32 * 1024) / P->data->plan.ld));   // ~30 KB of LDS per workgroup: five of them per CU
+    hipLaunchKernelGGL(k_gather_rows_i8, dim3((unsigned)((P->data->p + mpw - 1) / mpw)), dim3(256), (size_t)mpw * P->data->plan.ld, P->stream, (const int8_t *)P->data->X, P->data->plan.R, P->data->plan.ld,
+                       use_d, (int)nbag, (int8_t *)PB->data->X, PB->data->plan.R, PB->data->plan.ld, P->data->p, mpw);
+  } else hipLaunchKernelGGL(k_gather_rows<int8_t>, dim3(4096), dim3(256), 0, P->stream, (const int8_t *)P->data->X, P->data->plan.R, use_d, (int)nbag, (int8_t *)PB->data->X, PB->data->plan.R, PB->data->plan.ld, P->data->p);
 }
 
 // one sweep over panel PS with host-side b, d, xx, L and a device residual e64 (ld doubles, padding zero); KMUP and KMUP2
@@ -2177,10 +2176,10 @@ extern "C" int bwgr_kmup(bwgr_panel *P, float *b, float *d, const float *xx, flo
   HIPCHK(hipSetDevice(P->data->device));
   DevBufs bufs;
   float *de = bufs.get<float>((size_t)P->data->n);
-  double *de64 = bufs.get<double>((size_t)P->data->ld);
+  double *de64 = bufs.get<double>((size_t)P->data->plan.ld);
   if (!de || !de64) return fail(BWGR_ENOMEM, "kmup: device allocation failed");
   HIPCHK(hipMemcpyAsync(de, e, sizeof(float) * P->data->n, hipMemcpyHostToDevice, P->stream));
-  hipLaunchKernelGGL(k_f2d, dim3(64), dim3(256), 0, P->stream, de, de64, P->data->n, P->data->ld);
+  hipLaunchKernelGGL(k_f2d, dim3(64), dim3(256), 0, P->stream, de, de64, P->data->n, P->data->plan.ld);
   CHK(kmup_sweep(P, b, d, xx, L, de64, Ve, pi, 0.0f, 0, seed, iter, rng_mode, "kmup"));
   hipLaunchKernelGGL(k_d2f, dim3(64), dim3(256), 0, P->stream, de64, de, P->data->n);
   HIPCHK(hipGetLastError());
@@ -2201,14 +2200,14 @@ extern "C" int bwgr_kmup2(bwgr_panel *P, const int *Use, int64_t nuse, float *b,
     if (Use[k] < 0 || Use[k] >= P->data->n) return fail(BWGR_EINVAL, "kmup2: Use[%lld] = %d is outside 0..%lld", (long long)k, Use[k], (long long)P->data->n - 1);
   HIPCHK(hipSetDevice(P->data->device));
   bwgr_panel *PB = nullptr;
-  CHK(panel_alloc(&PB, P->data->is_f32, nuse, P->data->p, P->data->device, P->data->m, 0, P->data->sw));
+  CHK(panel_alloc(&PB, P->data->is_f32, nuse, P->data->p, P->data->device, P->data->plan.m, 0, PANEL_ROWS, P->data->sw));
   PB->stream = P->stream;
   Guard drop([&] { bwgr_panel_destroy(PB); });
   CHK(scratch_alloc(PB));
   DevBufs bufs;
   int *use_d = bufs.get<int>((size_t)nuse);
   float *dE = bufs.get<float>((size_t)P->data->n), *deo = bufs.get<float>((size_t)nuse);
-  double *dE64 = bufs.get<double>((size_t)P->data->n), *e64 = bufs.get<double>((size_t)PB->data->ld);
+  double *dE64 = bufs.get<double>((size_t)P->data->n), *e64 = bufs.get<double>((size_t)PB->data->plan.ld);
   if (!use_d || !dE || !deo || !dE64 || !e64) return fail(BWGR_ENOMEM, "kmup2: device allocation failed");
   HIPCHK(hipMemcpyAsync(use_d, Use, sizeof(int) * (size_t)nuse, hipMemcpyHostToDevice, P->stream));
   HIPCHK(hipMemcpyAsync(dE, E, sizeof(float) * P->data->n, hipMemcpyHostToDevice, P->stream));
@@ -2216,7 +2215,7 @@ extern "C" int bwgr_kmup2(bwgr_panel *P, const int *Use, int64_t nuse, float *b,
   HIPCHK(hipGetLastError());
   CHK(panel_build_gram(PB));
   hipLaunchKernelGGL(k_f2d, dim3(64), dim3(256), 0, P->stream, dE, dE64, P->data->n, P->data->n);
-  hipLaunchKernelGGL(k_gather_e, dim3(64), dim3(256), 0, P->stream, dE64, use_d, (int)nuse, PB->data->ld, e64);   // e0[k] = E[Use[k]], :49-53
+  hipLaunchKernelGGL(k_gather_e, dim3(64), dim3(256), 0, P->stream, dE64, use_d, (int)nuse, PB->data->plan.ld, e64);   // e0[k] = E[Use[k]], :49-53
   HIPCHK(hipGetLastError());
   CHK(kmup_sweep(PB, b, d, xx, L, e64, Ve, pi, (float)P->data->n / (float)nuse, 1, seed, iter, rng_mode, "kmup2"));
   hipLaunchKernelGGL(k_d2f, dim3(64), dim3(256), 0, P->stream, e64, deo, nuse);
@@ -2257,7 +2256,7 @@ extern "C" int bwgr_chain_create_sharded(bwgr_chain **out, bwgr_panel *P, int mo
   if (P->data->cen) {
     if (!has_d(model) || !P->data->e3_ready)
       return fail(BWGR_EINVAL, "chain_create: an implicitly centred panel (bwgr_panel_set_centred) runs the selection models BayesB / C / Cpi / Dpi only");
-    if (!P->cpre) HIPCHK(hipMalloc(&P->cpre, sizeof(double) * ((size_t)P->data->nblocks + 1)));
+    if (!P->cpre) HIPCHK(hipMalloc(&P->cpre, sizeof(double) * ((size_t)P->data->plan.nblocks + 1)));
   }
   bwgr_chain *C = new bwgr_chain();
   C->P = P; P->nchains++; P->data->nchains_all++; C->model = model; C->itf = it; C->bif = bi; C->iit = (int)it; C->ibi = (int)bi;
@@ -2267,11 +2266,11 @@ extern "C" int bwgr_chain_create_sharded(bwgr_chain **out, bwgr_panel *P, int mo
   const size_t pb = sizeof(float) * P->data->p;
   Guard drop([&] { bwgr_chain_destroy(C); });
   HIPCHK(hipMalloc(&C->y, sizeof(float) * P->data->n));
-  if (e_ext) { C->e = e_ext; C->e_owned = false; } else HIPCHK(hipMalloc(&C->e, sizeof(double) * P->data->ld));
+  if (e_ext) { C->e = e_ext; C->e_owned = false; } else HIPCHK(hipMalloc(&C->e, sizeof(double) * P->data->plan.ld));
   HIPCHK(hipMalloc(&C->b, pb)); HIPCHK(hipMalloc(&C->d, pb)); HIPCHK(hipMalloc(&C->vb, pb)); HIPCHK(hipMalloc(&C->lam, pb));
   HIPCHK(hipMalloc(&C->B, pb)); HIPCHK(hipMalloc(&C->D, pb)); HIPCHK(hipMalloc(&C->VB, pb)); HIPCHK(hipMalloc(&C->sc, sizeof(ChainScalars)));
   HIPCHK(hipMemcpyAsync(C->y, y, sizeof(float) * P->data->n, memloc == BWGR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, P->stream));
-  InitArgs ia; ia.y = C->y; ia.e = C->e; ia.n = (int)P->data->n; ia.p = (int)P->data->p; ia.ld = P->data->ld; ia.model = model;
+  InitArgs ia; ia.y = C->y; ia.e = C->e; ia.n = (int)P->data->n; ia.p = (int)P->data->p; ia.ld = P->data->plan.ld; ia.model = model;
   ia.pi = pi; ia.df = df; ia.R2 = R2; ia.MSx = MSx_total; ia.sc = C->sc;
   hipLaunchKernelGGL(k_chain_init, dim3(1), dim3(1024), 0, P->stream, ia);
   hipLaunchKernelGGL(k_marker_init, dim3(1024), dim3(256), 0, P->stream, C->b, C->d, C->vb, C->lam, C->B, C->D, C->VB, (int)P->data->p, C->sc);
@@ -2309,7 +2308,7 @@ static void chain_args(const bwgr_chain *C, int blk_begin, int blk_end, SweepArg
 extern "C" int bwgr_chain_sweep_blocks(bwgr_chain *C, int blk_begin, int blk_end) {
   if (!C) return fail(BWGR_EINVAL, "null chain");
   bwgr_panel *P = C->P;
-  if (blk_begin < 0 || blk_end > P->data->nblocks || blk_begin >= blk_end) return fail(BWGR_EINVAL, "sweep_blocks: bad range [%d,%d) of %lld", blk_begin, blk_end, (long long)P->data->nblocks);
+  if (blk_begin < 0 || blk_end > P->data->plan.nblocks || blk_begin >= blk_end) return fail(BWGR_EINVAL, "sweep_blocks: bad range [%d,%d) of %lld", blk_begin, blk_end, (long long)P->data->plan.nblocks);
   if (C->done >= C->iit) return fail(BWGR_EINVAL, "sweep_blocks: all %d iterations already run", C->iit);
   HIPCHK(hipSetDevice(P->data->device));
   SweepArgs a;
@@ -2324,7 +2323,7 @@ extern "C" int bwgr_chain_sweep_blocks(bwgr_chain *C, int blk_begin, int blk_end
   // marker-sharded sampler -- pre-stages all of them with the first range
   bool prestaged = false;
   if (P->ps_owner != C || P->ps_iter != C->done) {
-    SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->data->nblocks;
+    SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->data->plan.nblocks;
     launch_prestage(P, all, pl);
     P->ps_owner = C; P->ps_iter = C->done;
     prestaged = true;
@@ -2332,7 +2331,7 @@ extern "C" int bwgr_chain_sweep_blocks(bwgr_chain *C, int blk_begin, int blk_end
   hipError_t he = hipEventRecord(e0, P->stream);
   if (he == hipSuccess) { launch_sweep_kernel(P, a, pl); he = hipGetLastError(); }
   if (he == hipSuccess && prestaged && C->done + 1 < C->iit) {   // the next iteration's variates, beside this sweep
-    SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->data->nblocks;
+    SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->data->plan.nblocks;
     draws_ahead(P, all, pl, e0);
   }
   if (he == hipSuccess) he = hipEventRecord(e1, P->stream);
@@ -2362,10 +2361,10 @@ extern "C" int bwgr_chain_round_sweep(bwgr_chain *C, int blk_begin, int blk_end,
   if (!C || !delta_dev) return fail(BWGR_EINVAL, "round_sweep: null pointer");
   bwgr_panel *P = C->P;
   HIPCHK(hipSetDevice(P->data->device));
-  if (!C->e0) HIPCHK(hipMalloc(&C->e0, sizeof(double) * P->data->ld));
-  HIPCHK(hipMemcpyAsync(C->e0, C->e, sizeof(double) * P->data->ld, hipMemcpyDeviceToDevice, P->stream));
+  if (!C->e0) HIPCHK(hipMalloc(&C->e0, sizeof(double) * P->data->plan.ld));
+  HIPCHK(hipMemcpyAsync(C->e0, C->e, sizeof(double) * P->data->plan.ld, hipMemcpyDeviceToDevice, P->stream));
   if (blk_begin < blk_end) CHK(bwgr_chain_sweep_blocks(C, blk_begin, blk_end));
-  hipLaunchKernelGGL(k_round_delta, dim3(64), dim3(256), 0, P->stream, C->e, C->e0, delta_dev, P->data->ld);
+  hipLaunchKernelGGL(k_round_delta, dim3(64), dim3(256), 0, P->stream, C->e, C->e0, delta_dev, P->data->plan.ld);
   HIPCHK(hipGetLastError());
   return BWGR_OK;
 }
@@ -2374,7 +2373,7 @@ extern "C" int bwgr_chain_round_apply(bwgr_chain *C, const double *delta_dev) {
   if (!C->e0) return fail(BWGR_EINVAL, "round_apply: no round_sweep before it");
   bwgr_panel *P = C->P;
   HIPCHK(hipSetDevice(P->data->device));
-  hipLaunchKernelGGL(k_round_apply, dim3(64), dim3(256), 0, P->stream, C->e, C->e0, delta_dev, P->data->ld);
+  hipLaunchKernelGGL(k_round_apply, dim3(64), dim3(256), 0, P->stream, C->e, C->e0, delta_dev, P->data->plan.ld);
   HIPCHK(hipGetLastError());
   return BWGR_OK;
 }
@@ -2435,7 +2434,7 @@ extern "C" int bwgr_chain_run(bwgr_chain *C, int iters) {
   if (!C) return fail(BWGR_EINVAL, "null chain");
   if (iters < 0 || C->done + iters > C->iit) return fail(BWGR_EINVAL, "chain_run: %d more iterations would exceed it=%d (done %d)", iters, C->iit, C->done);
   for (int k = 0; k < iters; ++k) {
-    CHK(bwgr_chain_sweep_blocks(C, 0, (int)C->P->data->nblocks));
+    CHK(bwgr_chain_sweep_blocks(C, 0, (int)C->P->data->plan.nblocks));
     CHK(bwgr_chain_end_iteration(C, nullptr));
   }
   return BWGR_OK;
@@ -2453,10 +2452,10 @@ extern "C" int bwgr_chain_run_pair(bwgr_chain *C0, bwgr_chain *C1, int iters) {
   if (P0->data != P1->data || P0 == P1) return fail(BWGR_EINVAL, "chain_run_pair: the chains must sit on two handles (panel and clone) of one resident panel");
   if (iters < 0 || C0->done + iters > C0->iit || C1->done + iters > C1->iit) return fail(BWGR_EINVAL, "chain_run_pair: %d more iterations exceed it", iters);
   SweepArgs t0, t1;
-  chain_args(C0, 0, (int)P0->data->nblocks, t0); chain_args(C1, 0, (int)P1->data->nblocks, t1);
+  chain_args(C0, 0, (int)P0->data->plan.nblocks, t0); chain_args(C1, 0, (int)P1->data->plan.nblocks, t1);
   if (plan_sweep(P0, t0, false).engine != 3 || plan_sweep(P1, t1, false).engine != 3 || !P0->qsum3 || !P1->qsum3)
     return fail(BWGR_EINVAL, "chain_run_pair: both chains must be selection models on a panel with k_sweep3");
-  if (s3p_streamer_lds(P0->data->R3) > (size_t)160 * 1024) return fail(BWGR_EINVAL, "chain_run_pair: the paired streamers' LDS does not fit");
+  if (s3p_streamer_lds(P0->data->plan3.R3) > (size_t)160 * 1024) return fail(BWGR_EINVAL, "chain_run_pair: the paired streamers' LDS does not fit");
   HIPCHK(hipSetDevice(P0->data->device));
   // everything of the pair runs on ONE stream, owned by the root panel (it outlives both handles), and both handles move onto it
   // for as long as they run in pairs -- one cross-stream wait each, the first time: a wait per call would sit in a hardware queue
@@ -2481,7 +2480,7 @@ extern "C" int bwgr_chain_run_pair(bwgr_chain *C0, bwgr_chain *C1, int iters) {
   int rc = sweep_guard(P0, plan_sweep(P0, t0, false), s0, P1, &need);
   for (int k = 0; k < iters && rc == BWGR_OK; ++k) {
     SweepArgs a0, a1;
-    chain_args(C0, 0, (int)P0->data->nblocks, a0); chain_args(C1, 0, (int)P1->data->nblocks, a1);
+    chain_args(C0, 0, (int)P0->data->plan.nblocks, a0); chain_args(C1, 0, (int)P1->data->plan.nblocks, a1);
     const SweepPlan pl0 = plan_sweep(P0, a0, false), pl1 = plan_sweep(P1, a1, false);
     a0.lag = pl0.lag; a1.lag = pl1.lag;
     if ((rc = reset_exchange(P0)) != BWGR_OK || (rc = reset_exchange(P1)) != BWGR_OK) break;
@@ -2586,11 +2585,11 @@ static int gemv_chunks(const bwgr_panel *P) { return (int)std::min<int64_t>(P->d
 template <typename CT>
 static void gemv_launch(bwgr_panel *P, const CT *coef_dev, int nchunks, int cpc, double *part) {
   if (P->data->is_f32) {
-    dim3 grid((unsigned)((P->data->ld / 4 + 255) / 256), (unsigned)nchunks);
-    hipLaunchKernelGGL((k_gemv_part<float, CT>), grid, dim3(256), 0, P->stream, (const float *)P->data->X, P->data->ld, P->data->R, (int)P->data->p, coef_dev, cpc, part);
+    dim3 grid((unsigned)((P->data->plan.ld / 4 + 255) / 256), (unsigned)nchunks);
+    hipLaunchKernelGGL((k_gemv_part<float, CT>), grid, dim3(256), 0, P->stream, (const float *)P->data->X, P->data->plan.ld, P->data->plan.R, (int)P->data->p, coef_dev, cpc, part);
   } else {
-    dim3 grid((unsigned)((P->data->ld / 16 + 255) / 256), (unsigned)nchunks);
-    hipLaunchKernelGGL((k_gemv_part_i8<CT>), grid, dim3(256), 0, P->stream, (const int8_t *)P->data->X, P->data->ld, P->data->R, (int)P->data->p, coef_dev, cpc, part);
+    dim3 grid((unsigned)((P->data->plan.ld / 16 + 255) / 256), (unsigned)nchunks);
+    hipLaunchKernelGGL((k_gemv_part_i8<CT>), grid, dim3(256), 0, P->stream, (const int8_t *)P->data->X, P->data->plan.ld, P->data->plan.R, (int)P->data->p, coef_dev, cpc, part);
   }
 }
 
@@ -2600,17 +2599,17 @@ static int gemv_hat(bwgr_panel *P, const CT *coef_dev, float MU, float *hat_dev,
   const int nchunks = gemv_chunks(P);
   const int cpc = (int)((P->data->p + nchunks - 1) / nchunks);
   DevBufs bufs;
-  double *part = bufs.get<double>((size_t)nchunks * P->data->ld + 1);
+  double *part = bufs.get<double>((size_t)nchunks * P->data->plan.ld + 1);
   if (!part) return fail(BWGR_ENOMEM, "%s: device allocation failed", who);
   gemv_launch<CT>(P, coef_dev, nchunks, cpc, part);
   double *cen_off = nullptr;
   if constexpr (std::is_same<CT, float>::value) {
     if (centred) {   // X_c B = X B - sum_j mean_j B_j
-      cen_off = part + (size_t)nchunks * P->data->ld;
+      cen_off = part + (size_t)nchunks * P->data->plan.ld;
       hipLaunchKernelGGL(k_cen_dot, dim3(1), dim3(1024), 0, P->stream, P->data->csum, coef_dev, P->data->p, 1.0 / (double)P->data->n, cen_off);
     }
   }
-  hipLaunchKernelGGL(k_hat_finish, dim3((unsigned)((P->data->n + 255) / 256)), dim3(256), 0, P->stream, part, P->data->ld, nchunks, (int)P->data->n, MU, hat_dev, (const double *)cen_off);
+  hipLaunchKernelGGL(k_hat_finish, dim3((unsigned)((P->data->n + 255) / 256)), dim3(256), 0, P->stream, part, P->data->plan.ld, nchunks, (int)P->data->n, MU, hat_dev, (const double *)cen_off);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(P->stream));
   return BWGR_OK;
@@ -2688,9 +2687,9 @@ extern "C" int bwgr_bayes2(bwgr_panel *P1, bwgr_panel *P2, int base_model, const
   if (!P1 || !P2 || !y) return fail(BWGR_EINVAL, "bayes2: null pointer");
   if (base_model != BWGR_BAYESA && base_model != BWGR_BAYESB && base_model != BWGR_BAYESRR)
     return fail(BWGR_EINVAL, "bayes2: base model must be BayesA, BayesB or BayesRR (got %d)", base_model);
-  if (P1->data->device != P2->data->device || P1->data->n != P2->data->n || P1->data->ld != P2->data->ld || P1->data->K != P2->data->K || P1->data->R != P2->data->R)
+  if (P1->data->device != P2->data->device || P1->data->n != P2->data->n || P1->data->plan.ld != P2->data->plan.ld || P1->data->plan.K != P2->data->plan.K || P1->data->plan.R != P2->data->plan.R)
     return fail(BWGR_EINVAL, "bayes2: the two panels must share device, rows and slab geometry (n %lld/%lld, %d x %d vs %d x %d rows)",
-                (long long)P1->data->n, (long long)P2->data->n, P1->data->K, P1->data->R, P2->data->K, P2->data->R);
+                (long long)P1->data->n, (long long)P2->data->n, P1->data->plan.K, P1->data->plan.R, P2->data->plan.K, P2->data->plan.R);
   const int64_t p1 = P1->data->p, p2 = P2->data->p, n = P1->data->n;
   if (p1 + p2 > 0xFFFFFFF0ll - 2) return fail(BWGR_EINVAL, "bayes2: p1 + p2 too large");
   HIPCHK(hipSetDevice(P1->data->device));
@@ -2710,8 +2709,8 @@ extern "C" int bwgr_bayes2(bwgr_panel *P1, bwgr_panel *P2, int base_model, const
   }
   const int iit = (int)it, ibi = (int)bi;
   for (int i = 0; i < iit; ++i) {
-    CHK(bwgr_chain_sweep_blocks(C1, 0, (int)P1->data->nblocks));
-    CHK(bwgr_chain_sweep_blocks(C2, 0, (int)P2->data->nblocks));
+    CHK(bwgr_chain_sweep_blocks(C1, 0, (int)P1->data->plan.nblocks));
+    CHK(bwgr_chain_sweep_blocks(C2, 0, (int)P2->data->plan.nblocks));
     const int accumulate = (i > ibi) ? 1 : 0;                                        // if(i>ibi), :1047
     Tail2Args t; t.e = C1->e; t.n = (int)n; t.p1 = (int)p1; t.p2 = (int)p2; t.rr = rr ? 1 : 0; t.df = df;
     t.accumulate = accumulate; t.iter = (uint32_t)i; t.rng = make_rng(seed, rng_mode); t.sc1 = C1->sc; t.sc2 = C2->sc;
@@ -2836,12 +2835,12 @@ extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int t
   }
   int *use_d = nullptr;
   if (bagging) {
-    CHK(panel_alloc(&PB, P->data->is_f32, nbag, P->data->p, P->data->device, P->data->m, 0, P->data->sw));
+    CHK(panel_alloc(&PB, P->data->is_f32, nbag, P->data->p, P->data->device, P->data->plan.m, 0, PANEL_ROWS, P->data->sw));
     PB->stream = P->stream;
     CHK(scratch_alloc(PB));
     if (!(use_d = bufs.get<int>((size_t)nbag))) return fail(BWGR_ENOMEM, "wgr: device allocation failed");
   }
-  const int64_t ldmax = std::max<int64_t>(std::max<int64_t>(P->data->ld, PU ? PU->data->ld : 0), PB ? PB->data->ld : 0);
+  const int64_t ldmax = std::max<int64_t>(std::max<int64_t>(P->data->plan.ld, PU ? PU->data->plan.ld : 0), PB ? PB->data->plan.ld : 0);
   const size_t nk = (size_t)std::max<int64_t>(pk, 1), np = (size_t)p, kd = sizeof(double) * nk;
   const int nchunks = gemv_chunks(P), cpc = (p + nchunks - 1) / nchunks;   // X * coef: fp64 partial products per column chunk
   double *yd = bufs.get<double>(n), *eR = bufs.get<double>(ldmax), *e64 = bufs.get<double>(ldmax);
@@ -2854,7 +2853,7 @@ extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int t
   double *part1 = bufs.get<double>(256), *part2 = bufs.get<double>(256), *hatd = bufs.get<double>(n);
   WgrScalars *ws = bufs.get<WgrScalars>(1);
   ChainScalars *sc = bufs.get<ChainScalars>(1);
-  double *gpart = bufs.get<double>((size_t)nchunks * P->data->ld);
+  double *gpart = bufs.get<double>((size_t)nchunks * P->data->plan.ld);
   if (!Ud || !Vd || !hR || !Hk || !uhd || !hf || !dhf || !xxKf || !Lkf || !vbk || !sck || !gpart ||
       !yd || !eR || !e64 || !xx64 || !vx64 || !bR || !dR || !VbR || !LR || !B || !D || !VB || !bf || !dfl || !Lf || !xxf || !vbf || !part1 || !part2 || !hatd || !ws || !sc)
     return fail(BWGR_ENOMEM, "wgr: device allocation failed");
@@ -2865,8 +2864,8 @@ extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int t
     HIPCHK(hipMemsetAsync(hR, 0, kd, P->stream)); HIPCHK(hipMemsetAsync(Hk, 0, kd, P->stream));
   }
   const int wpb = 4;
-  if (P->data->is_f32) hipLaunchKernelGGL(k_stats64<float>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const float *)P->data->X, P->data->R, n, p, xx64, vx64);
-  else hipLaunchKernelGGL(k_stats64<int8_t>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const int8_t *)P->data->X, P->data->R, n, p, xx64, vx64);
+  if (P->data->is_f32) hipLaunchKernelGGL(k_stats64<float>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const float *)P->data->X, P->data->plan.R, n, p, xx64, vx64);
+  else hipLaunchKernelGGL(k_stats64<int8_t>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const int8_t *)P->data->X, P->data->plan.R, n, p, xx64, vx64);
   hipLaunchKernelGGL(k_dsum_stage1, dim3(256), dim3(256), 0, P->stream, vx64, (int64_t)p, part1, 0);
   hipLaunchKernelGGL(k_dsum_stage1, dim3(256), dim3(256), 0, P->stream, xx64, (int64_t)p, part2, 0);
   hipLaunchKernelGGL(k_wgr_init, dim3(1), dim3(1024), 0, P->stream, yd, eR, n, ldmax, part1, part2, p, df, R2, ws);
@@ -2907,7 +2906,7 @@ extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int t
     hipLaunchKernelGGL(k_wgr_scal, dim3(1), dim3(1024), 0, P->stream, e64, (int)nbag, (double)n * bag, p, part1, iv, df, itx, rng, ws);
     hipLaunchKernelGGL(k_wgr_L, dim3(pg), dim3(256), 0, P->stream, bR, dR, VbR, LR, B, D, VB, p, iv, accumulate, ws);
     gemv_launch<double>(P, bR, nchunks, cpc, gpart);
-    hipLaunchKernelGGL(k_wgr_efinish, dim3((n + 255) / 256), dim3(256), 0, P->stream, gpart, P->data->ld, nchunks, n, yd, eR, ws);
+    hipLaunchKernelGGL(k_wgr_efinish, dim3((n + 255) / 256), dim3(256), 0, P->stream, gpart, P->data->plan.ld, nchunks, n, yd, eR, ws);
     if (pk > 0) hipLaunchKernelGGL(k_uh, dim3((n + 255) / 256), dim3(256), 0, P->stream, Ud, hR, n, (int)pk, 1.0, eR, 1);   // - U %*% h
     hipLaunchKernelGGL(k_wgr_mu, dim3(1), dim3(1024), 0, P->stream, eR, n, iv, accumulate, itx, rng, ws);
     if (pk > 0 && accumulate) hipLaunchKernelGGL(k_wgr_accum_k, dim3(8), dim3(256), 0, P->stream, hR, Hk, (int)pk, ws);
@@ -2923,7 +2922,7 @@ extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int t
   if (hc.error) return sweep_error(hc.error, "wgr");
   const double B0 = h.B0 / mc;
   gemv_launch<double>(P, B, nchunks, cpc, gpart);                                // HAT = B0 + gen0 %*% B, R/wgr.R:152
-  hipLaunchKernelGGL(k_hat64_finish, dim3((n + 255) / 256), dim3(256), 0, P->stream, gpart, P->data->ld, nchunks, n, B0, hatd);
+  hipLaunchKernelGGL(k_hat64_finish, dim3((n + 255) / 256), dim3(256), 0, P->stream, gpart, P->data->plan.ld, nchunks, n, B0, hatd);
   if (pk > 0) {                                                                  // poly = U0 %*% H; HAT += poly, R/wgr.R:148-150
     hipLaunchKernelGGL(k_uh, dim3((n + 255) / 256), dim3(256), 0, P->stream, Ud, Hk, n, (int)pk, 1.0 / (double)mc, uhd, 0);
     hipLaunchKernelGGL(k_add_vec, dim3((n + 255) / 256), dim3(256), 0, P->stream, hatd, uhd, n);
@@ -3062,7 +3061,7 @@ extern "C" int bwgr_panel_set_centred(bwgr_panel *P, int on) {
     HIPCHK(hipMalloc(&P->data->csum, sizeof(int32_t) * (size_t)P->data->p));
     HIPCHK(hipMalloc(&P->data->xxc, sizeof(float) * (size_t)P->data->p));
     const int wpb = 4;
-    hipLaunchKernelGGL(k_colsum_i8, dim3((unsigned)((P->data->p + wpb - 1) / wpb)), dim3(64 * wpb), 0, P->stream, (const int8_t *)P->data->X, P->data->R, (int)P->data->n, (int)P->data->p, P->data->csum, P->data->xxc);
+    hipLaunchKernelGGL(k_colsum_i8, dim3((unsigned)((P->data->p + wpb - 1) / wpb)), dim3(64 * wpb), 0, P->stream, (const int8_t *)P->data->X, P->data->plan.R, (int)P->data->n, (int)P->data->p, P->data->csum, P->data->xxc);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(P->stream));
   }
@@ -3120,7 +3119,7 @@ static int group_create_impl(bwgr_group **out, int ndev, const int *devices, con
       if (hipStreamCreateWithFlags(&q, hipStreamNonBlocking) != hipSuccess) return fail(BWGR_EHIP, "group_create: hipStreamCreate failed");
       Gp->streams.push_back(q);
       Gp->P[g]->stream = q;
-      if (ndev > 2 && Gp->P[g]->data->sw.solo3 < 0) Gp->P[g]->data->solo3 = false;   // (an explicit BWGR_SOLO3 decides otherwise: experiments)
+      if (ndev > 2 && Gp->P[g]->data->sw.solo3 < 0) Gp->P[g]->data->crowded = true;   // (an explicit BWGR_SOLO3 decides otherwise: experiments)
     }
     if (centre) CHK(bwgr_panel_set_centred(Gp->P[g], 1));   // the shard's own column means (rows are not sharded)
     msx += (double)Gp->P[g]->data->MSx;
@@ -3138,16 +3137,16 @@ static int group_create_impl(bwgr_group **out, int ndev, const int *devices, con
   }
   for (int g = 0; g < ndev; ++g) {
     CHK(bwgr_chain_create_sharded(&Gp->C[g], Gp->P[g], model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode, Gp->lo[g], p, Gp->MSx_total, nullptr));
-    if (hipSetDevice(devices[g]) != hipSuccess || hipMalloc(&Gp->delta[g], sizeof(double) * (size_t)Gp->P[g]->data->ld) != hipSuccess ||
+    if (hipSetDevice(devices[g]) != hipSuccess || hipMalloc(&Gp->delta[g], sizeof(double) * (size_t)Gp->P[g]->data->plan.ld) != hipSuccess ||
         hipMalloc(&Gp->sums[g], sizeof(double) * 2) != hipSuccess) return fail(BWGR_ENOMEM, "group_create: device allocation failed");
-    if (Gp->P[g]->data->ld != Gp->P[0]->data->ld) return fail(BWGR_EINVAL, "group_create: shards disagree on the padded row count");
+    if (Gp->P[g]->data->plan.ld != Gp->P[0]->data->plan.ld) return fail(BWGR_EINVAL, "group_create: shards disagree on the padded row count");
   }
   // (shards side by side exchange through one kernel on the same card, not a ring over xGMI, but every exchange is a launch boundary for all of
   // them: 131072 markers per shard between two exchanges there)
   const int64_t mps = markers_per_sync > 0 ? markers_per_sync : std::max<int64_t>(m, Gp->same_dev ? 131072 : 131072 / ndev);
   Gp->bps = (int)std::max<int64_t>(1, mps / m);
   int64_t nbmax = 0;
-  for (int g = 0; g < ndev; ++g) nbmax = std::max<int64_t>(nbmax, Gp->P[g]->data->nblocks);
+  for (int g = 0; g < ndev; ++g) nbmax = std::max<int64_t>(nbmax, Gp->P[g]->data->plan.nblocks);
   Gp->rounds = (int)((nbmax + Gp->bps - 1) / Gp->bps);
   Gp->use_comm = (ndev > 1 && !Gp->same_dev) || (Gp->P[0]->data->sw.group_force_comm && !Gp->same_dev);   // (BWGR_GROUP_FORCE_COMM=1, tests: exercise the RCCL path with a single device)
   if (Gp->same_dev) {
@@ -3155,7 +3154,7 @@ static int group_create_impl(bwgr_group **out, int ndev, const int *devices, con
     Gp->ev_sweep.assign(ndev, nullptr);
     for (int g = 0; g < ndev; ++g) if (hipEventCreateWithFlags(&Gp->ev_sweep[g], hipEventDisableTiming) != hipSuccess) return fail(BWGR_EHIP, "group_create: hipEventCreate failed");
     for (int k = 0; k < 2; ++k) {
-      if (hipEventCreateWithFlags(&Gp->ev_sum[k], hipEventDisableTiming) != hipSuccess || hipMalloc(&Gp->total[k], sizeof(double) * (size_t)Gp->P[0]->data->ld) != hipSuccess ||
+      if (hipEventCreateWithFlags(&Gp->ev_sum[k], hipEventDisableTiming) != hipSuccess || hipMalloc(&Gp->total[k], sizeof(double) * (size_t)Gp->P[0]->data->plan.ld) != hipSuccess ||
           hipMalloc(&Gp->total_sums[k], sizeof(double) * 2) != hipSuccess) return fail(BWGR_ENOMEM, "group_create: device allocation failed");
     }
   }
@@ -3226,12 +3225,12 @@ static int group_run_same_device(bwgr_group *Gp, int iters) {
   for (int k = 0; k < iters; ++k) {
     for (int r = 0; r < Gp->rounds; ++r) {
       for (int g = 0; g < Gp->G; ++g) {
-        const int nb = (int)Gp->P[g]->data->nblocks;
+        const int nb = (int)Gp->P[g]->data->plan.nblocks;
         const int lo = std::min(nb, r * Gp->bps), hi = std::min(nb, (r + 1) * Gp->bps);
         CHK(bwgr_chain_round_sweep(Gp->C[g], lo, hi, Gp->delta[g]));
       }
       double *tot = nullptr;
-      CHK(group_local_sum(Gp, Gp->delta, (size_t)Gp->P[0]->data->ld, Gp->total, &tot));
+      CHK(group_local_sum(Gp, Gp->delta, (size_t)Gp->P[0]->data->plan.ld, Gp->total, &tot));
       for (int g = 0; g < Gp->G; ++g) CHK(bwgr_chain_round_apply(Gp->C[g], tot));
     }
     for (int g = 0; g < Gp->G; ++g) CHK(bwgr_chain_get_sums_dev(Gp->C[g], Gp->sums[g]));
@@ -3250,11 +3249,11 @@ extern "C" int bwgr_group_run(bwgr_group *Gp, int iters) {
   for (int k = 0; k < iters; ++k) {
     for (int r = 0; r < Gp->rounds; ++r) {
       for (int g = 0; g < Gp->G; ++g) {
-        const int nb = (int)Gp->P[g]->data->nblocks;
+        const int nb = (int)Gp->P[g]->data->plan.nblocks;
         const int lo = std::min(nb, r * Gp->bps), hi = std::min(nb, (r + 1) * Gp->bps);   // (lo == hi: a device that has run out of blocks still takes part)
         CHK(bwgr_chain_round_sweep(Gp->C[g], lo, hi, Gp->delta[g]));
       }
-      CHK(group_allreduce(Gp, Gp->delta, (size_t)Gp->P[0]->data->ld));
+      CHK(group_allreduce(Gp, Gp->delta, (size_t)Gp->P[0]->data->plan.ld));
       for (int g = 0; g < Gp->G; ++g) CHK(bwgr_chain_round_apply(Gp->C[g], Gp->delta[g]));
     }
     for (int g = 0; g < Gp->G; ++g) CHK(bwgr_chain_get_sums_dev(Gp->C[g], Gp->sums[g]));
@@ -3509,7 +3508,7 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
   const bool soft = (model == BWGR_EM_BB || model == BWGR_EM_BC || model == BWGR_EM_BCPI);
   const bool lasso = (model == BWGR_EM_LASSO);
   const bool nonaffine = soft || lasso || model == BWGR_EM_BL || model == BWGR_EM_EN;
-  if (nonaffine && P->data->sweep_version < 2) return fail(BWGR_EINVAL, "em: this member needs the pipelined sweep engine (k_sweep2), which this panel's geometry does not fit");
+  if (nonaffine && !P->data->plan.pipelined) return fail(BWGR_EINVAL, "em: this member needs the pipelined sweep engine (k_sweep2), which this panel's geometry does not fit");
   HIPCHK(hipSetDevice(P->data->device));
   const int64_t p = P->data->p, n = P->data->n;
   const bool conv = (model == BWGR_EM_DE || model == BWGR_EM_ML || model == BWGR_EM_EN || lasso);
@@ -3523,9 +3522,9 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
   std::vector<int> order((size_t)p), order_next;   // (copied from asynchronously: declared before the holder, which waits for the stream)
   DevBufs bufs(st);
   if (shuffled) {
-    CHK(panel_alloc(&Q, P->data->is_f32, n, p, P->data->device, P->data->m, P->data->K, P->data->sw, true));
+    CHK(panel_alloc(&Q, P->data->is_f32, n, p, P->data->device, P->data->plan.m, P->data->plan.K, PANEL_EM, P->data->sw));
     Q->stream = st;
-    if (Q->data->K != P->data->K || Q->data->R != P->data->R || Q->data->m != P->data->m || std::min(Q->data->sweep_version, 2) != std::min(P->data->sweep_version, 2)) return fail(BWGR_EINVAL, "em: scratch panel geometry differs");
+    if (Q->data->plan.K != P->data->plan.K || Q->data->plan.R != P->data->plan.R || Q->data->plan.m != P->data->plan.m || Q->data->plan.pipelined != P->data->plan.pipelined) return fail(BWGR_EINVAL, "em: scratch panel geometry differs");
     CHK(scratch_alloc(Q));
   }
   bwgr_panel *S = Q ? Q : P;                                                          // the panel the sweeps run on
@@ -3533,7 +3532,7 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
   float *yd = bufs.get<float>((size_t)n), *bd = bufs.get<float>(np), *bcd = bufs.get<float>(np), *dd = bufs.get<float>(np);
   float *lamd = bufs.get<float>(np), *vbd = bufs.get<float>(np), *xxd = bufs.get<float>(np);
   float *bq = bufs.get<float>(np), *xxq = bufs.get<float>(np), *lamq = bufs.get<float>(np), *dq = bufs.get<float>(np), *vq = bufs.get<float>(np);
-  double *ed = bufs.get<double>((size_t)P->data->ld); int32_t *ordd = bufs.get<int32_t>(np);
+  double *ed = bufs.get<double>((size_t)P->data->plan.ld); int32_t *ordd = bufs.get<int32_t>(np);
   EmState *std_ = bufs.get<EmState>(1); ChainScalars *sc = bufs.get<ChainScalars>(1);
   float *hatd = bufs.get<float>((size_t)n), *Dd = D ? bufs.get<float>(np) : nullptr;
   if (!yd || !bd || !bcd || !dd || !lamd || !vbd || !xxd || !bq || !xxq || !lamq || !dq || !vq || !ed || !ordd || !std_ || !sc || !hatd || (D && !Dd))
@@ -3548,7 +3547,7 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
     InitArgs ia; memset(&ia, 0, sizeof(ia));
     ChainScalars h0; memset(&h0, 0, sizeof(h0));
     HIPCHK(hipMemcpyAsync(sc, &h0, sizeof(h0), hipMemcpyHostToDevice, st));
-    ia.y = yd; ia.e = ed; ia.n = (int)n; ia.p = (int)p; ia.ld = P->data->ld; ia.model = BWGR_BAYESRR; ia.pi = 0; ia.df = df; ia.R2 = R2; ia.MSx = P->data->MSx; ia.sc = sc;
+    ia.y = yd; ia.e = ed; ia.n = (int)n; ia.p = (int)p; ia.ld = P->data->plan.ld; ia.model = BWGR_BAYESRR; ia.pi = 0; ia.df = df; ia.R2 = R2; ia.MSx = P->data->MSx; ia.sc = sc;
     hipLaunchKernelGGL(k_chain_init, dim3(1), dim3(1024), 0, st, ia);
     HIPCHK(hipGetLastError());
     HIPCHK(d2h(st, &h0, sc, sizeof(h0)));
@@ -3614,7 +3613,7 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
     }
   }
   HIPCHK(hipMemcpyAsync(std_, &h, sizeof(h), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_em_init, dim3(1), dim3(1024), 0, st, yd, ed, (int)n, P->data->ld, std_);   // mu, e (overwrites k_chain_init's e)
+  hipLaunchKernelGGL(k_em_init, dim3(1), dim3(1024), 0, st, yd, ed, (int)n, P->data->plan.ld, std_);   // mu, e (overwrites k_chain_init's e)
   HIPCHK(hipGetLastError());
   {
     ChainScalars h0; memset(&h0, 0, sizeof(h0));
@@ -3626,7 +3625,7 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
   for (int64_t j = 0; j < p; ++j) order[(size_t)j] = (int)j;
   if (shuffled) std::shuffle(order.begin(), order.end(), std::mt19937(0));            // sweep 0's order
   if (!shuffled) HIPCHK(hipMemcpyAsync(ordd, order.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice, st));
-  const int cps = (int)((size_t)P->data->R * (P->data->is_f32 ? 4 : 1) / 16);
+  const int cps = (int)((size_t)P->data->plan.R * (P->data->is_f32 ? 4 : 1) / 16);
   uint32_t flags = SWF_LAM_VEC;
   if (model == BWGR_EM_BA) flags |= SWF_DELTA2;
   if (soft) flags |= SWF_EM_SEL;
@@ -3643,7 +3642,7 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
       // the reference's own call -- was made for sweep 0 before the loop and is made for sweep i+1 below, while the GPU
       // runs sweep i (10-15 ms of host time per sweep at p = 10^6)
       HIPCHK(hipMemcpyAsync(ordd, order.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)P->data->X, (uint4 *)Q->data->X, ordd, p, P->data->K, cps);
+      hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)P->data->X, (uint4 *)Q->data->X, ordd, p, P->data->plan.K, cps);
     }
     if (conv) HIPCHK(hipMemcpyAsync(bcd, bd, pb, hipMemcpyDeviceToDevice, st));      // bc = b
     hipLaunchKernelGGL(k_em_stage, dim3(1024), dim3(256), 0, st, ordd, p, model, D ? 1 : 0, bd, xxd, lamd, Dd, std_, bq, xxq, lamq);
@@ -3791,8 +3790,8 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   if ((o.XFA || o.ACS) && (o.NumXFA < 1 || o.NumXFA > k))
     return fail(BWGR_EINVAL, "mrr: NumXFA = %d with XFA / ACS needs 1 <= NumXFA <= k = %d (the reference indexes eigenvalue k - NumXFA)", o.NumXFA, k);
   HIPCHK(hipSetDevice(P->data->device));
-  const int64_t n = P->data->n, p = P->data->p, ld = P->data->ld;
-  const int R = P->data->R;
+  const int64_t n = P->data->n, p = P->data->p, ld = P->data->plan.ld;
+  const int R = P->data->plan.R;
   {
     const int64_t xm = std::max(P->data->xmax, 1);
     if ((int64_t)n * xm * xm >= (1ll << 31)) return fail(BWGR_EINVAL, "mrr: n * max|x|^2 = %lld does not fit the int32 Gram", (long long)(n * xm * xm));
@@ -3845,7 +3844,7 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   const int nch = (int)std::min<int64_t>(64, p);       // marker chunks of the fitted values
   const int64_t cpc = (p + nch - 1) / nch;
   const size_t np = (size_t)p, nl = (size_t)ld, pk = np * k;
-  int8_t *Xs = bufs.get<int8_t>(P->data->x_bytes);
+  int8_t *Xs = bufs.get<int8_t>(P->data->plan.x_bytes);
   uint32_t *zbd = bufs.get<uint32_t>(nl), *ztd = bufs.get<uint32_t>(nl);
   uint8_t *zmd = bufs.get<uint8_t>((size_t)npat * nl);
   int32_t *ordd = bufs.get<int32_t>(np), *gram = bufs.get<int32_t>((size_t)nblk * npat * MRR_MB * MRR_MB);
@@ -3904,7 +3903,7 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
     vb0 = vb; h20 = h2;
     std::shuffle(order.begin(), order.end(), std::mt19937(numit));                                 // :869 (cumulative, as there)
     HIPCHK(hipMemcpyAsync(ordd, order.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)P->data->X, (uint4 *)Xs, (const int32_t *)ordd, p, P->data->K, cps);
+    hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)P->data->X, (uint4 *)Xs, (const int32_t *)ordd, p, P->data->plan.K, cps);
     hipLaunchKernelGGL(k_mrr_gram, dim3((unsigned)nblk, (unsigned)((npat + 3) / 4)), dim3(256), 0, st, (const int8_t *)Xs, R, p, ld, (const uint8_t *)zmd, npat, gram);
     for (int t = 0; t < k; ++t) mc.iVe[t] = 1.0 / ve[t];
     HIPCHK(hipMemcpyAsync(small + 512, iG.data(), sizeof(double) * k * k, hipMemcpyHostToDevice, st));

@@ -274,6 +274,16 @@ int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opts, int nopt
  * in LDS (patterns ngl..npat-1 are read from global memory); the dynamic LDS bytes of the solve and of the inverses' kernel.  Any
  * output may be NULL. */
 int bwgr_debug_mrr_plan(int k, int npat, int *linv_lds, int *ngl, int64_t *solve_lds_bytes, int64_t *linv_lds_bytes);
+/* host arithmetic of a panel's plan (needs no GPU): what bwgr_panel_create would decide for an int8 (is_f32 = 0) or float panel of n x p
+ * with these block / nwg arguments under the BWGR_* switches of the environment; kind 0: a main panel, 1: the row-subset scratch panel of
+ * KMUP2 and wgr's bagging, 2: bwgr_em's scratch panel.  A shape bwgr_panel_create refuses returns its code and leaves its message in
+ * bwgr_last_error.  out[0..17]: m, K, R, ld, nblocks, pstride, nfeed, lag-4 streamer fits, LDS bytes of k_sweep / k_sweep2 / k_sweep2w,
+ * x_bytes, bytes per Gram array, pipelined engine (0: the first-generation k_sweep), farthest distance of the cross Gram arrays, 16-bit
+ * copies carried, farthest distance the affine engine's byte planes may reach, k_sweep3 attempted.  out[18..24], k_sweep3's share for an
+ * assumed largest |x| (xmax >= 0; xmax < 0: left at their defaults) and 16-bit verdict gram16: fits, R3, streamers per slab, K3, D, LDS
+ * bytes, solo streamer height allowed. */
+#define BWGR_PANEL_PLAN_NOUT 25
+int bwgr_debug_panel_plan(int is_f32, int64_t n, int64_t p, int block, int nwg, int kind, int xmax, int gram16, int64_t out[BWGR_PANEL_PLAN_NOUT]);
 
 /* ---- synthetic panels ----------------------------------------------------------
  * X_ij ~ Binomial(2, f_j), f_j ~ U(0.05,0.5), int8 column-major written to device memory Xdev
