@@ -19,6 +19,7 @@ from ._lib import BwgrError, c_f, c_d, check
 
 MODELS = {"BayesA": 0, "BayesB": 1, "BayesC": 2, "BayesL": 3, "BayesRR": 4, "BayesCpi": 5, "BayesDpi": 6}
 _PER_MARKER_VB = {"BayesA", "BayesB", "BayesL", "BayesDpi"}
+KERNELS = {"GRM": 0, "GAU": 1, "EigenGRM": 2, "EigenGAU": 3, "EigenARC": 4}
 X_I8, X_F32, X_F64 = 0, 1, 2
 HOST, DEVICE = 0, 1
 
@@ -134,6 +135,36 @@ class Panel:
         xx = np.empty(self.p, np.float32); vx = np.empty(self.p, np.float32); msx = C.c_float()
         check(_lib.lib().bwgr_panel_stats(self._h, _fp(xx), _fp(vx), C.byref(msx)))
         return xx, vx, float(msx.value)
+
+    def _nxn(self, dtype, device_out, call):
+        """An n x n result of the relationship kernels: a numpy array, or (device_out) a torch tensor on the panel's device."""
+        n = self.n
+        if device_out:
+            import sys
+            torch = sys.modules.get("torch")
+            if torch is None:
+                raise RuntimeError("device_out=True: import torch before calling (the result is a torch tensor)")
+            out = torch.empty((n, n), dtype=torch.int64 if dtype == np.int64 else torch.float64, device="cuda:%d" % self.device)
+            torch.cuda.synchronize(out.device)
+            check(call(C.c_void_p(out.data_ptr()), n, DEVICE))
+            return out
+        out = np.empty((n, n), dtype)
+        check(call(out.ctypes.data_as(C.c_void_p), n, HOST))
+        return out
+
+    def crossprod(self, *, device_out=False):
+        """The exact X X' over the panel's rows as n x n int64 (bwgr_panel_crossprod)."""
+        L = _lib.lib()
+        return self._nxn(np.int64, device_out, lambda ptr, ld, loc: L.bwgr_panel_crossprod(self._h, ptr, ld, loc))
+
+    def kernel(self, kind, par=1.0, flag=None, *, device_out=False):
+        """A relationship kernel of the panel's genotypes, n x n float64 (bwgr_panel_kernel).  kind: "GRM" (flag = Code012, default False),
+        "GAU", "EigenGRM" (flag = centralizeZ, default True), "EigenGAU" (par = phi), "EigenARC" (flag = centralizeX, default True)."""
+        k = KERNELS[kind] if isinstance(kind, str) else int(kind)
+        if flag is None:
+            flag = k in (KERNELS["EigenGRM"], KERNELS["EigenARC"])
+        L = _lib.lib()
+        return self._nxn(np.float64, device_out, lambda ptr, ld, loc: L.bwgr_panel_kernel(self._h, k, float(par), int(bool(flag)), ptr, ld, loc))
 
     def close(self):
         if self._h:
@@ -979,3 +1010,65 @@ def mrr(Y, X, **kw):
 def mrr_float(Y, X, **kw):
     """mrr_float(Y, X, ...) = MRR3F(Y, X, ...), R/mix.R:1273."""
     return MRR3F(Y, X, **kw)
+
+
+# ---- relationship kernels: GRM / GAU (R/RcppExports.R:100-106), EigenARC / EigenGAU / EigenGRM (:140-150) ----
+def _kernel_panel(X, panel_kw):
+    """X as an int8 panel.  The int8 product is the feature: a float matrix must hold integers in -128..127 (checked here, before the library is
+    touched); float panels are out of scope."""
+    if isinstance(X, Panel):
+        return X, False
+    if hasattr(X, "data_ptr"):
+        if "int8" not in str(X.dtype):
+            raise ValueError("relationship kernels take int8 genotypes; got a %s tensor" % (X.dtype,))
+        return Panel(X, **panel_kw), True
+    X = np.asarray(X)
+    if X.dtype != np.int8:
+        if not (X.size and np.all(np.isfinite(X)) and np.all(X == np.rint(X)) and X.min() >= -128 and X.max() <= 127):
+            raise ValueError("relationship kernels take integer genotypes in -128..127 (the int8 panel); float panels are not supported")
+        X = X.astype(np.int8)
+    return Panel(X, **panel_kw), True
+
+
+def _kernel(kind, X, par, flag, device_out, panel_kw):
+    P, own = _kernel_panel(X, panel_kw)
+    try:
+        return P.kernel(kind, par, flag, device_out=device_out)
+    finally:
+        if own:
+            P.close()
+
+
+def GRM(X, Code012=False, *, device_out=False, **kw):
+    """GRM(X, Code012), src/Rcpp20260726ai.cpp:1363-1383: ZZ' / sum_j var(x_j) (Code012: / sum_j mean_j^2 / 2, as written there)."""
+    return _kernel("GRM", X, 1.0, Code012, device_out, kw)
+
+
+def GAU(X, *, device_out=False, **kw):
+    """GAU(X), src/Rcpp20260726ai.cpp:1338-1360: exp(-d2 / mean off-diagonal d2)."""
+    return _kernel("GAU", X, 1.0, False, device_out, kw)
+
+
+def EigenGRM(X, centralizeZ=True, cores=1, *, device_out=False, **kw):
+    """EigenGRM(X, centralizeZ, cores), src/RcppEigen20230423.cpp:41-51 (cores is accepted and ignored)."""
+    return _kernel("EigenGRM", X, 1.0, centralizeZ, device_out, kw)
+
+
+def EigenGAU(X, phi=1.0, cores=1, *, device_out=False, **kw):
+    """EigenGAU(X, phi, cores), src/RcppEigen20230423.cpp:29-38 (cores is accepted and ignored)."""
+    return _kernel("EigenGAU", X, phi, False, device_out, kw)
+
+
+def EigenARC(X, centralizeX=True, cores=1, *, device_out=False, **kw):
+    """EigenARC(X, centralizeX, cores), src/RcppEigen20230423.cpp:8-26 (cores is accepted and ignored)."""
+    return _kernel("EigenARC", X, 1.0, centralizeX, device_out, kw)
+
+
+def crossprod(X, *, device_out=False, **kw):
+    """The exact X X' of integer genotypes, n x n int64 (no reference counterpart of its own: the product inside the five kernels)."""
+    P, own = _kernel_panel(X, kw)
+    try:
+        return P.crossprod(device_out=device_out)
+    finally:
+        if own:
+            P.close()

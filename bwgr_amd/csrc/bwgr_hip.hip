@@ -20,6 +20,7 @@
 #include "sweep2w.hip.h"
 #include "sweep3p.hip.h"
 #include "mrr.hip.h"
+#include "kernels.hip.h"
 #include <stdlib.h>
 
 using namespace bwgr;
@@ -948,6 +949,7 @@ struct Switches {
   bool winv = true, wfx = true;
   int wpf = 4, wahead = 5, wnq = 0, wlag_cap = 4;
   bool group_allow_uncentred = false, group_force_comm = false, em_debug = false;   // BWGR_GROUP_ALLOW_UNCENTRED=1, BWGR_GROUP_FORCE_COMM=1, BWGR_EM_DEBUG
+  int64_t kchunk = 0;   // BWGR_KCHUNK: markers per int32 chunk of the X X' product (0: the largest that keeps the int32 sums exact, plan_xxt)
 #ifdef BWGR_EXPERIMENTS
   int dbg3 = 0, dbgw = 0, wlag_timing = 0; bool no_recover = false;   // BWGR_DBG3, BWGR_DBGW, BWGR_WLAG_TIMING, BWGR_NO_RECOVER
 #endif
@@ -968,6 +970,7 @@ static Switches read_switches() {
   { const int v = num(getenv("BWGR_WNQ")), c = chr(getenv("BWGR_WLAG")); if (v == 1 || v == 2 || v == 4) s.wnq = v; if (c >= '2' && c <= '6') s.wlag_cap = c - '0'; }
   s.group_allow_uncentred = chr(getenv("BWGR_GROUP_ALLOW_UNCENTRED")) == '1'; s.group_force_comm = chr(getenv("BWGR_GROUP_FORCE_COMM")) == '1';
   s.em_debug = getenv("BWGR_EM_DEBUG") != nullptr;
+  if (const char *v = getenv("BWGR_KCHUNK")) s.kchunk = std::max<long long>(0, atoll(v));
 #ifdef BWGR_EXPERIMENTS
   s.dbg3 = num(getenv("BWGR_DBG3")); s.dbgw = num(getenv("BWGR_DBGW")); s.wlag_timing = num(getenv("BWGR_WLAG_TIMING"));
   s.no_recover = getenv("BWGR_NO_RECOVER") != nullptr;
@@ -3999,6 +4002,184 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
       if (vb_out) vb_out[j * k + i] = vb[i * k + j];
     }
   *its = numit;
+  return BWGR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// relationship kernels: the exact X X' of an int8 panel and its fp64 finishes (kernels.hip.h)
+// ------------------------------------------------------------------------------------------------
+// The product's plan, decided here and nowhere else (bwgr_debug_xxt_plan exposes it to the CPU tests): the chunk of markers whose int32
+// sums are exact for the panel's largest |x|, the upper-triangle tiles, and how far a chunk is split again so that small n still fills
+// the chip -- integer sums make every split give the same bits.
+struct XxtPlan {
+  int64_t chunk = 0, nchunks = 0;   // markers per int32 chunk (the rule's, or the forced one); chunks
+  int64_t T = 0, tiles = 0;         // row tiles of XXT_TILE rows; tiles on and above the diagonal
+  int64_t sub = 1, piece = 0;       // pieces per chunk; markers per piece (whole MFMA steps)
+  int64_t wgs = 0;                  // workgroups launched: tiles x chunks x pieces
+  bool accumulate = false;          // more than one workgroup per tile: they add into the zeroed int64 tile
+  size_t ws_bytes = 0;              // device temporaries of a kernel call with a host output: the n x n array, s, q, X s, the diagonal, the partial sums
+};
+static constexpr int XXT_SUMD_PARTS = 1024;
+static int plan_xxt(XxtPlan &pl, int64_t n, int64_t p, int xmax, int64_t kchunk) {
+  pl = XxtPlan();
+  CHK(panel_range(n, p));
+  if (xmax < 0 || xmax > 128) return fail(BWGR_EINVAL, "xxt: largest |x| = %d is not an int8 panel's", xmax);
+  if (kchunk < 0) return fail(BWGR_EINVAL, "xxt: forced chunk %lld < 0", (long long)kchunk);
+  const int64_t x2 = (int64_t)std::max(xmax, 1) * std::max(xmax, 1);
+  if ((long double)x2 * (long double)p >= 9007199254740992.0L)
+    return fail(BWGR_EINVAL, "xxt: max|x|^2 * p = %.3Lg reaches 2^53: the entries of X X' would not be exact doubles", (long double)x2 * (long double)p);
+  if ((long double)x2 * (long double)n * (long double)p >= 9223372036854775808.0L)
+    return fail(BWGR_EINVAL, "xxt: max|x|^2 * n * p = %.3Lg reaches 2^63: X s would not fit int64", (long double)x2 * (long double)n * (long double)p);
+  const int64_t rule = 2147483647ll / x2;
+  pl.chunk = kchunk > 0 ? std::min(kchunk, rule) : rule;   // (a forced chunk beyond the rule would not be exact)
+  pl.nchunks = (p + pl.chunk - 1) / pl.chunk;
+  pl.T = (n + XXT_TILE - 1) / XXT_TILE;
+  pl.tiles = pl.T * (pl.T + 1) / 2;
+  // pieces: about four workgroups per compute unit where the tiles and chunks alone give fewer, never shorter than sixteen steps
+  const int64_t span = std::min(pl.chunk, p), steps = (span + XXT_KSTEP - 1) / XXT_KSTEP;
+  const int64_t want = (1024 + pl.tiles * pl.nchunks - 1) / (pl.tiles * pl.nchunks);
+  const int64_t sub0 = std::max<int64_t>(1, std::min(want, steps / 16));
+  pl.piece = (steps + sub0 - 1) / sub0 * XXT_KSTEP;
+  pl.sub = (span + pl.piece - 1) / pl.piece;
+  if (pl.nchunks * pl.sub > 65535) return fail(BWGR_EINVAL, "xxt: %lld chunks of %lld markers exceed the launch grid (65535); use a longer BWGR_KCHUNK", (long long)pl.nchunks, (long long)pl.chunk);
+  if (pl.tiles > 0x7FFFFFFFll) return fail(BWGR_EINVAL, "xxt: %lld output tiles exceed the launch grid", (long long)pl.tiles);
+  pl.wgs = pl.tiles * pl.nchunks * pl.sub;
+  pl.accumulate = pl.nchunks * pl.sub > 1;
+  const int64_t ld = (n + 127) / 128 * 128;   // (at least; the panel's own padding may be larger)
+  pl.ws_bytes = (size_t)n * n * 8 + (size_t)p * 12 + (size_t)ld * 8 + (size_t)n * 8 + (size_t)(XXT_SUMD_PARTS + 1) * 8;
+  return BWGR_OK;
+}
+extern "C" int bwgr_debug_xxt_plan(int64_t n, int64_t p, int xmax, int64_t kchunk, int64_t out[BWGR_XXT_PLAN_NOUT]) {
+  if (!out) return fail(BWGR_EINVAL, "debug_xxt_plan: null pointer");
+  XxtPlan pl;
+  CHK(plan_xxt(pl, n, p, xmax, kchunk));
+  const int64_t v[BWGR_XXT_PLAN_NOUT] = {pl.chunk, pl.nchunks, pl.tiles, pl.wgs, (int64_t)pl.ws_bytes, pl.T, pl.sub, pl.piece};
+  std::copy(v, v + BWGR_XXT_PLAN_NOUT, out);
+  return BWGR_OK;
+}
+
+// what the two entry points check alike; leaves the device set
+static int xxt_accept(bwgr_panel *P, const void *out, int64_t ldo, int memloc, const char *who, XxtPlan &pl) {
+  if (!P || !out) return fail(BWGR_EINVAL, "%s: null pointer", who);
+  if (memloc != BWGR_HOST && memloc != BWGR_DEVICE) return fail(BWGR_EINVAL, "%s: bad memloc %d", who, memloc);
+  const PanelData *D = P->data;
+  if (D->is_f32) return fail(BWGR_EINVAL, "%s: the panel holds fp32 genotypes; the relationship kernels take int8 panels only", who);
+  if (D->n < 2) return fail(BWGR_EINVAL, "%s: n = %lld (needs 2 rows)", who, (long long)D->n);
+  if (ldo < D->n) return fail(BWGR_EINVAL, "%s: leading dimension %lld < n = %lld", who, (long long)ldo, (long long)D->n);
+  CHK(plan_xxt(pl, D->n, D->p, D->xmax, D->sw.kchunk));
+  HIPCHK(hipSetDevice(D->device));
+  // these launches fill the chip: nothing is enqueued while sweeps of other handles, whose workgroups must stay co-resident, are in flight
+  if (D->sw.occ_guard) {
+    std::lock_guard<std::mutex> lk(g_guard_mu);
+    const int busy = guard_busy(P, P->stream);
+    if (busy > 0) return fail(BWGR_EINVAL, "%s: sweeps of other handles hold %d compute units on this device; wait for them (bwgr_chain_sync) and call again", who, busy);
+  }
+  return BWGR_OK;
+}
+// G = X X' over the panel's n rows into the device array Gd (n x n int64, row stride ldg), both triangles; enqueued on the panel's stream
+static int xxt_product(bwgr_panel *P, const XxtPlan &pl, long long *Gd, int64_t ldg) {
+  const PanelData *D = P->data;
+  hipStream_t st = P->stream;
+  XxtArgs a;
+  a.X = (const int8_t *)D->X; a.p = D->p; a.R = D->plan.R; a.n = (int)D->n; a.T = (int)pl.T; a.chunk = pl.chunk; a.piece = pl.piece;
+  a.sub = (int)pl.sub; a.accumulate = pl.accumulate ? 1 : 0; a.G = Gd; a.ldg = ldg;
+  if (pl.accumulate) hipLaunchKernelGGL(k_xxt_zero, dim3(2048), dim3(256), 0, st, Gd, ldg, (int)D->n);
+  hipLaunchKernelGGL(k_xxt_mfma_i8, dim3((unsigned)pl.tiles, (unsigned)(pl.nchunks * pl.sub)), dim3(256), 0, st, a);
+  const unsigned t32 = (unsigned)((D->n + 31) / 32);
+  hipLaunchKernelGGL(k_xxt_mirror, dim3(t32, t32), dim3(32, 8), 0, st, Gd, ldg, (int)D->n);
+  HIPCHK(hipGetLastError());
+  return BWGR_OK;
+}
+// the n x n 8-byte result to the caller's host array
+static int xxt_to_host(hipStream_t st, void *dst, int64_t ldo, const void *src, int64_t n) {
+  HIPCHK(hipMemcpy2DAsync(dst, (size_t)ldo * 8, src, (size_t)n * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return BWGR_OK;
+}
+
+extern "C" int bwgr_panel_crossprod(bwgr_panel *P, int64_t *G, int64_t ldg, int memloc) {
+  XxtPlan pl;
+  CHK(xxt_accept(P, G, ldg, memloc, "panel_crossprod", pl));
+  const int64_t n = P->data->n;
+  DevBufs bufs(P->stream);
+  long long *Gd = reinterpret_cast<long long *>(G); int64_t ldd = ldg;
+  if (memloc == BWGR_HOST) {
+    Gd = bufs.get<long long>((size_t)n * n); ldd = n;
+    if (!Gd) return fail(BWGR_ENOMEM, "panel_crossprod: device allocation failed");
+  }
+  CHK(xxt_product(P, pl, Gd, ldd));
+  if (memloc == BWGR_HOST) return xxt_to_host(P->stream, G, ldg, Gd, n);
+  HIPCHK(hipStreamSynchronize(P->stream));
+  return BWGR_OK;
+}
+
+extern "C" int bwgr_panel_kernel(bwgr_panel *P, int kind, double par, int flag, double *K, int64_t ldk, int memloc) {
+  if (kind < BWGR_K_GRM || kind > BWGR_K_EIGEN_ARC) return fail(BWGR_EINVAL, "panel_kernel: unknown kind %d", kind);
+  XxtPlan pl;
+  CHK(xxt_accept(P, K, ldk, memloc, "panel_kernel", pl));
+  const PanelData *D = P->data;
+  const int64_t n = D->n, p = D->p, ld = D->plan.ld;
+  hipStream_t st = P->stream;
+  // which inputs the kind needs: the centred product (GRM; EigenGRM / EigenARC with their flag), the column sums (those, and GAU's mean)
+  const bool cen = kind == BWGR_K_GRM || ((kind == BWGR_K_EIGEN_GRM || kind == BWGR_K_EIGEN_ARC) && flag != 0);
+  const bool cols = cen || kind == BWGR_K_GAU;
+  std::vector<long long> diag((size_t)n), rs, q;
+  std::vector<int32_t> s;
+  DevBufs bufs(st);
+  long long *Gd = reinterpret_cast<long long *>(K); int64_t ldd = ldk;
+  if (memloc == BWGR_HOST) { Gd = bufs.get<long long>((size_t)n * n); ldd = n; }
+  long long *diag_d = bufs.get<long long>((size_t)n), *rs_d = cen ? bufs.get<long long>((size_t)ld) : nullptr, *q_d = cols ? bufs.get<long long>((size_t)p) : nullptr;
+  int32_t *s_d = cols ? bufs.get<int32_t>((size_t)p) : nullptr;
+  double *part = kind == BWGR_K_EIGEN_GAU ? bufs.get<double>(XXT_SUMD_PARTS + 1) : nullptr;
+  if (!Gd || !diag_d || (cen && !rs_d) || (cols && (!q_d || !s_d)) || (kind == BWGR_K_EIGEN_GAU && !part)) return fail(BWGR_ENOMEM, "panel_kernel: device allocation failed");
+  CHK(xxt_product(P, pl, Gd, ldd));
+  hipLaunchKernelGGL(k_kfin_diag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, Gd, ldd, (int)n, diag_d);
+  if (cols) hipLaunchKernelGGL(k_kfin_colstats, dim3((unsigned)((p + 3) / 4)), dim3(256), 0, st, (const int8_t *)D->X, D->plan.R, (int)n, p, s_d, q_d);
+  if (cen) {
+    HIPCHK(hipMemsetAsync(rs_d, 0, sizeof(long long) * ld, st));
+    const int64_t ysplit = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(65535, (p + 511) / 512), 2048 / (ld / 128) + 1)), cpw = (p + ysplit - 1) / ysplit;
+    hipLaunchKernelGGL(k_kfin_xs, dim3((unsigned)(ld / 128), (unsigned)((p + cpw - 1) / cpw)), dim3(256), 0, st, (const int8_t *)D->X, D->plan.R, p, s_d, cpw, rs_d);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(diag.data(), diag_d, sizeof(long long) * n, hipMemcpyDeviceToHost, st));
+  if (cols) { s.resize((size_t)p); q.resize((size_t)p); HIPCHK(hipMemcpyAsync(s.data(), s_d, sizeof(int32_t) * p, hipMemcpyDeviceToHost, st)); HIPCHK(hipMemcpyAsync(q.data(), q_d, sizeof(long long) * p, hipMemcpyDeviceToHost, st)); }
+  if (cen) { rs.resize((size_t)n); HIPCHK(hipMemcpyAsync(rs.data(), rs_d, sizeof(long long) * n, hipMemcpyDeviceToHost, st)); }
+  HIPCHK(hipStreamSynchronize(st));
+  // ---- the global scalars, on the host in a fixed order from the exact integers ----
+  const double nd = (double)n, ninv = 1.0 / nd;
+  double c = 0.0, sumvar = 0.0;      // sum_j mean_j^2; sum_j fvar(x_j) = sum_j (q_j - s_j^2 / n) / (n - 1)
+  __int128 ss = 0, tr = 0;           // sum_j s_j^2 = the sum of all entries of G; its trace
+  for (int64_t j = 0; j < (cols ? p : 0); ++j) {
+    const double m = (double)s[j] * ninv;
+    c += m * m;
+    sumvar += ((double)q[j] - (double)s[j] * (double)s[j] / nd) / (nd - 1.0);
+    ss += (__int128)s[j] * s[j];
+  }
+  for (int64_t i = 0; i < n; ++i) tr += diag[i];
+  const auto zz_diag = [&](int64_t i) { double v = (double)diag[i]; if (cen) v = v - ((double)rs[i] * ninv + (double)rs[i] * ninv) + c; return v; };
+  KfinArgs a;
+  a.G = Gd; a.ldg = ldd; a.n = (int)n; a.kind = kind; a.cen = cen ? 1 : 0; a.diag = diag_d; a.rs = rs_d; a.ninv = ninv; a.c = c; a.scale = 1.0;
+  switch (kind) {
+    case BWGR_K_GRM: a.scale = flag ? c / 2.0 : sumvar; break;                                          // Sum2pq, :1369-1373
+    case BWGR_K_GAU: a.scale = (double)(2 * ((__int128)n * tr - ss)) / (nd * (nd - 1.0)); break;        // md, :1351-1353
+    case BWGR_K_EIGEN_GRM: case BWGR_K_EIGEN_ARC: {
+      double sd = 0.0;
+      for (int64_t i = 0; i < n; ++i) sd += zz_diag(i) + (kind == BWGR_K_EIGEN_GRM ? 1.0 : 0.0);
+      a.scale = 1.0 / (sd / nd);                                                                        // tmp, RcppEigen20230423.cpp:18, :50
+    } break;
+    default: {                                                                                          // EigenGAU's tmp, :37
+      double sumd = 0.0;
+      hipLaunchKernelGGL(k_kfin_sumd_stage1, dim3(XXT_SUMD_PARTS), dim3(256), 0, st, Gd, ldd, diag_d, (int)n, part);
+      hipLaunchKernelGGL(k_kfin_sumd_stage2, dim3(1), dim3(256), 0, st, part, XXT_SUMD_PARTS, part + XXT_SUMD_PARTS);
+      HIPCHK(hipGetLastError());
+      HIPCHK(d2h(st, &sumd, part + XXT_SUMD_PARTS, sizeof(double)));
+      a.scale = par * (-(nd * (nd - 1.0))) / sumd;
+    }
+  }
+  hipLaunchKernelGGL(k_kfin_apply, dim3(4096), dim3(256), 0, st, a);
+  HIPCHK(hipGetLastError());
+  if (memloc == BWGR_HOST) return xxt_to_host(st, K, ldk, Gd, n);
+  HIPCHK(hipStreamSynchronize(st));
   return BWGR_OK;
 }
 

@@ -285,6 +285,34 @@ int bwgr_debug_mrr_plan(int k, int npat, int *linv_lds, int *ngl, int64_t *solve
 #define BWGR_PANEL_PLAN_NOUT 25
 int bwgr_debug_panel_plan(int is_f32, int64_t n, int64_t p, int block, int nwg, int kind, int xmax, int gram16, int64_t out[BWGR_PANEL_PLAN_NOUT]);
 
+/* ---- relationship kernels on the resident panel --------------------------------------------------------------
+ * Replaces the functions with which bWGR's users make the K of wgr(eigK = eigen(K)): SEXP GAU(X) src/Rcpp20260726ai.cpp:1338-1360,
+ * GRM(X, Code012) :1363-1383 (R/RcppExports.R:100-106), EigenARC(X, centralizeX, cores) src/RcppEigen20230423.cpp:8-26, EigenGAU(X, phi,
+ * cores) :29-38, EigenGRM(X, centralizeZ, cores) :41-51 (R/RcppExports.R:140-150).  All five are one X X' over the panel's n rows -- exact in
+ * integers on the int8 matrix cores, int32 sums over chunks of at most floor((2^31 - 1) / max|x|^2) markers added in int64 -- and an
+ * element-wise finish in fp64 from the exact integers (the reference computes in float; the library returns the fp64 value of the
+ * reference's formulas, its literals 3.1416 and 1.001 and the `m_j^2 / 2` of GRM's Code012 included).  int8 panels only, root or clone, any
+ * geometry; a panel switched to implicit centring gives the same results as before the switch (all five are defined on the raw genotypes).
+ * Both entry points run on the panel's stream, return when the result is complete, and return BWGR_EINVAL without enqueuing anything while
+ * sweeps of other handles are in flight on the device (occupancy guard, above).  Also BWGR_EINVAL: fp32 panels, an unknown kind, a leading
+ * dimension below n, max|x|^2 * p >= 2^53 or max|x|^2 * n * p >= 2^63.  BWGR_KCHUNK (read when the root panel is made) forces a shorter chunk.
+ * Not here: fp32 panels, EigenEVD / K2X / mkr / mkr2X (the eigendecomposition stays with the caller), EigenArcZ / EigenGauZ, CNT / IMP / SPC /
+ * SPM, and a product sharded over GPUs. */
+enum { BWGR_K_GRM = 0, BWGR_K_GAU = 1, BWGR_K_EIGEN_GRM = 2, BWGR_K_EIGEN_GAU = 3, BWGR_K_EIGEN_ARC = 4 };
+/* exact X X' over the panel's n rows (the Eigen product of src/RcppEigen20230423.cpp:17, :32, :48, in integers): G is n x n int64, ldg >= n,
+ * host or device per memloc */
+int bwgr_panel_crossprod(bwgr_panel *P, int64_t *G, int64_t ldg, int memloc);
+/* K (n x n doubles, column-major = row-major: exactly symmetric, ldk >= n, host or device per memloc; entries beyond column n of a row are
+ * not touched).  par: phi for EIGEN_GAU (reference default 1.0), ignored otherwise.  flag: Code012 for GRM (default 0); centralizeZ /
+ * centralizeX for EIGEN_GRM / EIGEN_ARC (default 1); ignored otherwise.  A device K serves as the call's own n x n workspace. */
+int bwgr_panel_kernel(bwgr_panel *P, int kind, double par, int flag, double *K, int64_t ldk, int memloc);
+/* host arithmetic of the product's plan (needs no GPU), in the style of bwgr_debug_panel_plan: for n, p, the panel's largest |x| and a
+ * forced chunk (0 = the rule above; a forced chunk beyond the rule is cut to it) out[0..7] = markers per chunk, chunks, output tiles
+ * computed (upper triangle of 128-row tiles), workgroups launched, workspace bytes of a kernel call with a host output, row tiles, pieces
+ * a chunk is split into, markers per piece.  Refused shapes return their code with the message in bwgr_last_error. */
+#define BWGR_XXT_PLAN_NOUT 8
+int bwgr_debug_xxt_plan(int64_t n, int64_t p, int xmax, int64_t kchunk, int64_t out[BWGR_XXT_PLAN_NOUT]);
+
 /* ---- synthetic panels ----------------------------------------------------------
  * X_ij ~ Binomial(2, f_j), f_j ~ U(0.05,0.5), int8 column-major written to device memory Xdev
  * (ldx >= n); freq (p floats, device, may be NULL) receives f_j.  The p columns written are columns

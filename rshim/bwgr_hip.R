@@ -79,3 +79,14 @@ MRR3F <- function(Y, X, maxit = 500L, tol = 10e-9, cores = 1L, TH = FALSE, NonLi
   .Call("bwgrhip_MRR3F", .bwgr_f32(as.matrix(Y)), .bwgr_panel(X), .bwgr_mrr_opts(maxit, tol, TH, NonLinearFactor, InnerGS, NoInv, HCS, XFA, ACS, NumXFA, R2, gc0, df0, updateMu, weight_prior_h2, weight_prior_gc, PenCor, MinCor, uncorH2below, roundGCupFrom, roundGCupTo, roundGCdownFrom, roundGCdownTo, bucketGCfrom, bucketGCto, DeflateMax, DeflateBy, OneVarB, OneVarE, verbose))
 mrr <- function(Y, X, ...) MRR3(Y, X, ...)
 mrr_float <- function(Y, X, ...) MRR3F(Y, X, ...)
+# relationship kernels, R/RcppExports.R:100-106 (GAU, GRM) and :140-150 (EigenARC, EigenGAU, EigenGRM): same names, argument order and defaults;
+# integer genotypes only (an int8 panel); `cores` is ignored.  Their result feeds wgr(eigK = eigen(K)).
+# (a numeric matrix of whole numbers is staged as integers, so that it becomes an int8 panel)
+.bwgr_ipanel <- function(X) { if (is.matrix(X) && is.double(X) && !anyNA(X) && all(X == round(X))) storage.mode(X) <- "integer"; .bwgr_panel(X) }
+.bwgr_kernel <- function(kind, X, par = 1.0, flag = FALSE) .Call("bwgrhip_kernel", .bwgr_ipanel(X), as.integer(kind), as.double(par), as.integer(flag))
+GRM      <- function(X, Code012 = FALSE) .bwgr_kernel(0L, X, 1.0, Code012)
+GAU      <- function(X) .bwgr_kernel(1L, X)
+EigenGRM <- function(X, centralizeZ = TRUE, cores = 1L) .bwgr_kernel(2L, X, 1.0, centralizeZ)
+EigenGAU <- function(X, phi = 1.0, cores = 1L) .bwgr_kernel(3L, X, phi)
+EigenARC <- function(X, centralizeX = TRUE, cores = 1L) .bwgr_kernel(4L, X, 1.0, centralizeX)
+.bwgr_crossprod <- function(X) .Call("bwgrhip_crossprod", .bwgr_ipanel(X))   # the exact X X' (tcrossprod) of integer genotypes

@@ -8,6 +8,7 @@
  *     _bWGR_KMUP      src/RcppExports.cpp:16-31      -> bwgrhip_KMUP     (8 args)
  *     _bWGR_KMUP2     src/RcppExports.cpp:34-50      -> bwgrhip_KMUP2    (9 args)
  *     _bWGR_BayesA..  src/RcppExports.cpp:177-290    -> bwgrhip_Bayes    (model + 7 args)
+ *     _bWGR_GRM, _bWGR_GAU, _bWGR_EigenGRM / GAU / ARC      -> bwgrhip_kernel   (kind + 2 args)
  * and adds bwgrhip_wgr (R/wgr.R:2-169 as one device-resident call) plus panel handles so that X is staged in HBM
  * once instead of being converted SEXP -> Eigen::MatrixXf on every call (src/RcppExports.cpp:20).
  *
@@ -304,11 +305,36 @@ static SEXP mrr_call(SEXP Y, SEXP panel, SEXP opts) {
 SEXP bwgrhip_MRR3(SEXP Y, SEXP panel, SEXP opts) { return mrr_call(Y, panel, opts); }
 SEXP bwgrhip_MRR3F(SEXP Y, SEXP panel, SEXP opts) { return mrr_call(Y, panel, opts); }
 
+/* relationship kernels: GRM(X, Code012) / GAU(X) src/Rcpp20260726ai.cpp:1338-1383, EigenARC / EigenGAU / EigenGRM(X, ., cores)
+ * src/RcppEigen20230423.cpp:8-51 -> an n x n numeric matrix.  kind: BWGR_K_*; par: phi; flag: Code012 / centralizeZ / centralizeX. */
+SEXP bwgrhip_kernel(SEXP panel, SEXP kind, SEXP par, SEXP flag) {
+  bwgr_panel *P = panel_of(panel);
+  int64_t info[8]; chk(bwgr_panel_info(P, info));
+  const int n = (int)info[0];
+  SEXP K = PROTECT(Rf_allocMatrix(REALSXP, n, n));
+  chk(bwgr_panel_kernel(P, Rf_asInteger(kind), Rf_asReal(par), Rf_asInteger(flag), REAL(K), (int64_t)n, BWGR_HOST));
+  UNPROTECT(1);
+  return K;
+}
+/* the exact X X' (tcrossprod(X) on integer genotypes) as a numeric matrix: every entry is an integer below 2^53 */
+SEXP bwgrhip_crossprod(SEXP panel) {
+  bwgr_panel *P = panel_of(panel);
+  int64_t info[8]; chk(bwgr_panel_info(P, info));
+  const int n = (int)info[0];
+  int64_t *g = (int64_t *)R_alloc((size_t)n * n, sizeof(int64_t));
+  chk(bwgr_panel_crossprod(P, g, (int64_t)n, BWGR_HOST));
+  SEXP G = PROTECT(Rf_allocMatrix(REALSXP, n, n));
+  for (R_xlen_t k = 0; k < (R_xlen_t)n * n; k++) REAL(G)[k] = (double)g[k];
+  UNPROTECT(1);
+  return G;
+}
+
 static const R_CallMethodDef CallEntries[] = {   /* as src/RcppExports.cpp:1152-1228 registers _bWGR_* */
   {"bwgrhip_panel", (DL_FUNC)&bwgrhip_panel, 2}, {"bwgrhip_KMUP", (DL_FUNC)&bwgrhip_KMUP, 9}, {"bwgrhip_KMUP2", (DL_FUNC)&bwgrhip_KMUP2, 10},
   {"bwgrhip_Bayes", (DL_FUNC)&bwgrhip_Bayes, 8}, {"bwgrhip_Bayes2", (DL_FUNC)&bwgrhip_Bayes2, 9},
   {"bwgrhip_wgr", (DL_FUNC)&bwgrhip_wgr, 14}, {"bwgrhip_em", (DL_FUNC)&bwgrhip_em, 7},
-  {"bwgrhip_MRR3", (DL_FUNC)&bwgrhip_MRR3, 3}, {"bwgrhip_MRR3F", (DL_FUNC)&bwgrhip_MRR3F, 3}, {NULL, NULL, 0}};
+  {"bwgrhip_MRR3", (DL_FUNC)&bwgrhip_MRR3, 3}, {"bwgrhip_MRR3F", (DL_FUNC)&bwgrhip_MRR3F, 3},
+  {"bwgrhip_kernel", (DL_FUNC)&bwgrhip_kernel, 4}, {"bwgrhip_crossprod", (DL_FUNC)&bwgrhip_crossprod, 1}, {NULL, NULL, 0}};
 
 void R_init_bwgrhip(DllInfo *dll) {              /* as R_init_bWGR, src/RcppExports.cpp:1230-1233 */
   R_registerRoutines(dll, NULL, CallEntries, NULL, NULL);
