@@ -2132,12 +2132,19 @@ extern "C" int bwgr_panel_stats(bwgr_panel *P, float *xx, float *vx, float *MSx)
 // ------------------------------------------------------------------------------------------------
 // KMUP
 // ------------------------------------------------------------------------------------------------
+// The row gather's path, decided here and nowhere else (bwgr_debug_aux_plan exposes it to the CPU tests): 0 = element-wise (float panels, int8
+// columns longer than 64 KB), else the columns an int8 workgroup stages in LDS -- ~30 KB of LDS per workgroup: five of them per CU
+static int gather_mpw(bool is_f32, int64_t ld) {
+  if (is_f32 || ld > 64 * 1024) return 0;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(8, (32 * 1024) / ld));
+}
+static size_t gather_lds(int mpw, int64_t ld) { return (size_t)mpw * (size_t)ld; }   // the staged columns
 // row gather of the resident panel P into the subsample panel PB (rows use_d[0..nbag), device array); KMUP2's H = X(Use, j)
 static void launch_gather_rows(bwgr_panel *P, bwgr_panel *PB, const int *use_d, int64_t nbag) {
+  const int mpw = gather_mpw(P->data->is_f32, P->data->plan.ld);
   if (P->data->is_f32) hipLaunchKernelGGL(k_gather_rows<float>, dim3(4096), dim3(256), 0, P->stream, (const float *)P->data->X, P->data->plan.R, use_d, (int)nbag, (float *)PB->data->X, PB->data->plan.R, PB->data->plan.ld, P->data->p);
-  else if (P->data->plan.ld <= 64 * 1024) {   // a column fits the LDS: stage, pick, write in 16-byte pieces
-    const int mpw = (int)std::max<int64_t>(1, std::min<int64_t>(8, (32 * 1024) / P->data->plan.ld));   // ~30 KB of LDS per workgroup: five of them per CU
-    hipLaunchKernelGGL(k_gather_rows_i8, dim3((unsigned)((P->data->p + mpw - 1) / mpw)), dim3(256), (size_t)mpw * P->data->plan.ld, P->stream, (const int8_t *)P->data->X, P->data->plan.R, P->data->plan.ld,
+  else if (mpw > 0) {   // a column fits the LDS: stage, pick, write in 16-byte pieces
+    hipLaunchKernelGGL(k_gather_rows_i8, dim3((unsigned)((P->data->p + mpw - 1) / mpw)), dim3(256), gather_lds(mpw, P->data->plan.ld), P->stream, (const int8_t *)P->data->X, P->data->plan.R, P->data->plan.ld,
                        use_d, (int)nbag, (int8_t *)PB->data->X, PB->data->plan.R, PB->data->plan.ld, P->data->p, mpw);
   } else hipLaunchKernelGGL(k_gather_rows<int8_t>, dim3(4096), dim3(256), 0, P->stream, (const int8_t *)P->data->X, P->data->plan.R, use_d, (int)nbag, (int8_t *)PB->data->X, PB->data->plan.R, PB->data->plan.ld, P->data->p);
 }
@@ -2584,14 +2591,26 @@ extern "C" int bwgr_chain_state(bwgr_chain *C, float *b, float *d, float *e, flo
 }
 
 // column chunks of the two-stage GEMV: enough workgroups to fill the chip at 16 rows per thread (int8) or 4 (float)
-static int gemv_chunks(const bwgr_panel *P) { return (int)std::min<int64_t>(P->data->is_f32 ? 64 : 512, std::max<int64_t>(1, P->data->p / 512)); }
+// (the rule, the columns of a chunk and the row workgroups live in the three functions below and nowhere else: bwgr_debug_aux_plan exposes them)
+static int gemv_chunks_of(bool is_f32, int64_t p) { return (int)std::min<int64_t>(is_f32 ? 64 : 512, std::max<int64_t>(1, p / 512)); }
+static int gemv_cpc_of(int64_t p, int nchunks) { return (int)((p + nchunks - 1) / nchunks); }
+static unsigned gemv_row_wgs(bool is_f32, int64_t ld) { return (unsigned)((ld / (is_f32 ? 4 : 16) + 255) / 256); }
+static int gemv_chunks(const bwgr_panel *P) { return gemv_chunks_of(P->data->is_f32, P->data->p); }
+// The two launch rules without a device (test hook).  out: see include/bwgr.h.
+extern "C" int bwgr_debug_aux_plan(int is_f32, int64_t p, int64_t ld, int64_t out[BWGR_AUX_PLAN_NOUT]) {
+  if (!out || p < 1 || ld < 128 || ld % 128) return fail(BWGR_EINVAL, "debug_aux_plan: null pointer, p < 1 or ld not a positive multiple of 128");
+  const int nchunks = gemv_chunks_of(is_f32 != 0, p), mpw = gather_mpw(is_f32 != 0, ld);
+  const int64_t v[BWGR_AUX_PLAN_NOUT] = {nchunks, gemv_cpc_of(p, nchunks), (int64_t)gemv_row_wgs(is_f32 != 0, ld), mpw, (int64_t)gather_lds(mpw, ld)};
+  std::copy(v, v + BWGR_AUX_PLAN_NOUT, out);
+  return BWGR_OK;
+}
 template <typename CT>
 static void gemv_launch(bwgr_panel *P, const CT *coef_dev, int nchunks, int cpc, double *part) {
   if (P->data->is_f32) {
-    dim3 grid((unsigned)((P->data->plan.ld / 4 + 255) / 256), (unsigned)nchunks);
+    dim3 grid(gemv_row_wgs(true, P->data->plan.ld), (unsigned)nchunks);
     hipLaunchKernelGGL((k_gemv_part<float, CT>), grid, dim3(256), 0, P->stream, (const float *)P->data->X, P->data->plan.ld, P->data->plan.R, (int)P->data->p, coef_dev, cpc, part);
   } else {
-    dim3 grid((unsigned)((P->data->plan.ld / 16 + 255) / 256), (unsigned)nchunks);
+    dim3 grid(gemv_row_wgs(false, P->data->plan.ld), (unsigned)nchunks);
     hipLaunchKernelGGL((k_gemv_part_i8<CT>), grid, dim3(256), 0, P->stream, (const int8_t *)P->data->X, P->data->plan.ld, P->data->plan.R, (int)P->data->p, coef_dev, cpc, part);
   }
 }
@@ -2600,7 +2619,7 @@ static void gemv_launch(bwgr_panel *P, const CT *coef_dev, int nchunks, int cpc,
 template <typename CT>
 static int gemv_hat(bwgr_panel *P, const CT *coef_dev, float MU, float *hat_dev, const char *who, bool centred = false) {
   const int nchunks = gemv_chunks(P);
-  const int cpc = (int)((P->data->p + nchunks - 1) / nchunks);
+  const int cpc = gemv_cpc_of(P->data->p, nchunks);
   DevBufs bufs;
   double *part = bufs.get<double>((size_t)nchunks * P->data->plan.ld + 1);
   if (!part) return fail(BWGR_ENOMEM, "%s: device allocation failed", who);
@@ -2845,7 +2864,7 @@ extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int t
   }
   const int64_t ldmax = std::max<int64_t>(std::max<int64_t>(P->data->plan.ld, PU ? PU->data->plan.ld : 0), PB ? PB->data->plan.ld : 0);
   const size_t nk = (size_t)std::max<int64_t>(pk, 1), np = (size_t)p, kd = sizeof(double) * nk;
-  const int nchunks = gemv_chunks(P), cpc = (p + nchunks - 1) / nchunks;   // X * coef: fp64 partial products per column chunk
+  const int nchunks = gemv_chunks(P), cpc = gemv_cpc_of(p, nchunks);   // X * coef: fp64 partial products per column chunk
   double *yd = bufs.get<double>(n), *eR = bufs.get<double>(ldmax), *e64 = bufs.get<double>(ldmax);
   double *Ud = bufs.get<double>((size_t)std::max<int64_t>(n * pk, 1)), *Vd = bufs.get<double>(nk), *hR = bufs.get<double>(nk), *Hk = bufs.get<double>(nk), *uhd = bufs.get<double>(n);
   float *hf = bufs.get<float>(nk), *dhf = bufs.get<float>(nk), *xxKf = bufs.get<float>(nk), *Lkf = bufs.get<float>(nk), *vbk = bufs.get<float>(nk);

@@ -284,6 +284,13 @@ int bwgr_debug_mrr_plan(int k, int npat, int *linv_lds, int *ngl, int64_t *solve
  * bytes, solo streamer height allowed. */
 #define BWGR_PANEL_PLAN_NOUT 25
 int bwgr_debug_panel_plan(int is_f32, int64_t n, int64_t p, int block, int nwg, int kind, int xmax, int gram16, int64_t out[BWGR_PANEL_PLAN_NOUT]);
+/* host arithmetic of the two launch rules around the sweep (needs no GPU), in the style of bwgr_debug_panel_plan, for an int8 (is_f32 = 0) or
+ * float panel of p markers and ld padded rows (a positive multiple of 128, else BWGR_EINVAL).  out[0..2], the two-stage product X * coef behind
+ * every hat and wgr's residual: column chunks, columns per chunk (the last chunk takes what is left), row workgroups.  out[3..4], the row
+ * gather of KMUP2 and wgr's bagging: its path (0: element-wise; else the columns an int8 workgroup stages in LDS) and that workgroup's LDS
+ * bytes. */
+#define BWGR_AUX_PLAN_NOUT 5
+int bwgr_debug_aux_plan(int is_f32, int64_t p, int64_t ld, int64_t out[BWGR_AUX_PLAN_NOUT]);
 
 /* ---- relationship kernels on the resident panel --------------------------------------------------------------
  * Replaces the functions with which bWGR's users make the K of wgr(eigK = eigen(K)): SEXP GAU(X) src/Rcpp20260726ai.cpp:1338-1360,

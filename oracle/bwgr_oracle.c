@@ -673,7 +673,7 @@ int FN(oracle_wgr)(const double *y, const double *X, int64_t n, int64_t p, int64
   float *bf = (float *)malloc(sizeof(float) * p), *dfl = (float *)malloc(sizeof(float) * p), *xxf = (float *)malloc(sizeof(float) * p);
   float *Lf = (float *)malloc(sizeof(float) * p), *ef = (float *)malloc(sizeof(float) * n);
   double *xx = (double *)malloc(sizeof(double) * p), *b = (double *)calloc(p, sizeof(double)), *d = (double *)malloc(sizeof(double) * p);
-  double *Vb = (double *)malloc(sizeof(double) * p), *L = (double *)malloc(sizeof(double) * p), *e = (double *)malloc(sizeof(double) * n);
+  double *Vb = (double *)malloc(sizeof(double) * p), *L = (double *)malloc(sizeof(double) * p), *e = (double *)malloc(sizeof(double) * (nbag > n ? nbag : n));   /* (bag > 1: KMUP2 returns nbag > n residuals, wgr.R:88) */
   double *B = (double *)calloc(p, sizeof(double)), *D = (double *)calloc(p, sizeof(double)), *VB = (double *)calloc(p, sizeof(double));
   float *Uf = (float *)malloc(sizeof(float) * (n * pk + 1)), *hf = (float *)malloc(sizeof(float) * (pk + 1)), *dhf = (float *)malloc(sizeof(float) * (pk + 1));
   float *xxKf = (float *)malloc(sizeof(float) * (pk + 1)), *Lkf = (float *)malloc(sizeof(float) * (pk + 1));
