@@ -1012,6 +1012,87 @@ def mrr_float(Y, X, **kw):
     return MRR3F(Y, X, **kw)
 
 
+# ---- per-trait ridge fits: solver1x / UVBETA, solver1xF / FUVBETA, XFUVBETA, ZFUVBETA (bwgr_uvbeta, include/bwgr.h) ----
+UVB_VARIANTS = {"D": 0, "F": 1, "X": 2, "Z": 3}   # BWGR_UVB_*
+UVB_KEYS = ("b", "mu", "h2", "ve", "vb", "its", "cnv")
+
+
+def uvb_plan(n, p, k):
+    """bwgr_debug_uvb_plan (host arithmetic, no GPU): dict(W, groups, solve_traits, ngl, solve_lds, pass_lds, pass_wg, ws_bytes)."""
+    out = (C.c_int64 * 8)()
+    check(_lib.lib().bwgr_debug_uvb_plan(int(n), int(p), int(k), out))
+    return dict(zip(("W", "groups", "solve_traits", "ngl", "solve_lds", "pass_lds", "pass_wg", "ws_bytes"), [int(v) for v in out]))
+
+
+def uvbeta(Y, X, variant="D", maxit=100, tol=10e-7, df0=20.0, xb=False, **kw):
+    """One ridge fit per column of Y on one X (bwgr_uvbeta): Y is n x k (NaN = missing) or a vector; variant "D" solver1x / UVBETA,
+    "F" solver1xF / FUVBETA, "X" xsolver1xF / XFUVBETA, "Z" zsolver1xF / ZFUVBETA (src/RcppEigen20230423.cpp:1410-1816).  The float
+    variants receive Y, tol and df0 rounded to float, as the reference does; the engine is fp64.  Returns dict(b [p x k], mu, h2, ve, vb,
+    its, cnv[, xb [n x k] = X b on the raw genotypes]).  X is an array or a Panel."""
+    if isinstance(variant, str) and variant not in UVB_VARIANTS:
+        raise BwgrError(1, "uvbeta: unknown variant %r (one of D, F, X, Z)" % (variant,))
+    v = UVB_VARIANTS[variant] if isinstance(variant, str) else int(variant)   # (an integer is passed on: the library checks it)
+    P, own = _as_panel(X, **kw)
+    try:
+        Ym = np.asarray(Y, np.float64)
+        if Ym.ndim == 1:
+            Ym = Ym[:, None]
+        if Ym.ndim != 2 or Ym.shape[0] != P.n:
+            raise BwgrError(1, "uvbeta: Y has shape %s; nrow(Y) must equal nrow(X) = %d" % (Ym.shape, P.n))
+        if v != 0:
+            Ym = Ym.astype(np.float32).astype(np.float64)
+            tol = float(np.float32(tol)); df0 = float(np.float32(df0))
+        k = Ym.shape[1]
+        Yf = np.asfortranarray(Ym)
+        kk = max(k, 1)
+        b = np.zeros((P.p, kk), order="F"); mu = np.zeros(kk); h2 = np.zeros(kk); ve = np.zeros(kk); vb = np.zeros(kk); cnv = np.zeros(kk)
+        its = np.zeros(kk, np.int32)
+        xbm = np.zeros((P.n, kk), order="F") if xb else None
+        check(_lib.lib().bwgr_uvbeta(P._h, _dp(Yf), int(k), int(v), int(maxit), float(tol), float(df0), _dp(b), _dp(mu), _dp(h2), _dp(ve), _dp(vb),
+                                     its.ctypes.data_as(C.POINTER(C.c_int)), _dp(cnv), _dp(xbm) if xb else None))
+        out = dict(zip(UVB_KEYS, (b, mu, h2, ve, vb, its, cnv)))
+        if xb:
+            out["xb"] = xbm
+        return out
+    finally:
+        if own:
+            P.close()
+
+
+def solver1x(Y, X, maxit=100, tol=10e-7, df0=20.0, **kw):
+    """solver1x(Y, X, maxit, tol, df0), src/RcppEigen20230423.cpp:1410-1443 (R/RcppExports.R:196): the p effects of one ridge fit.  NaN rows
+    of Y are treated as unobserved."""
+    return uvbeta(np.asarray(Y, np.float64).reshape(-1), X, "D", maxit, tol, df0, **kw)["b"][:, 0]
+
+
+def solver1xF(Y, X, maxit=100, tol=10e-7, df0=20.0, **kw):
+    """solver1xF(Y, X, maxit, tol, df0), src/RcppEigen20230423.cpp:1613-1646 (R/RcppExports.R:216): solver1x on float inputs, with its test
+    XX_j > 1e-5."""
+    return uvbeta(np.asarray(Y, np.float64).reshape(-1), X, "F", maxit, tol, df0, **kw)["b"][:, 0]
+
+
+def UVBETA(Y, X, **kw):
+    """UVBETA(Y, X), src/RcppEigen20230423.cpp:1506-1515 (R/RcppExports.R:204): p x k, solver1x per trait on the trait's observed rows."""
+    return uvbeta(Y, X, "D", **kw)["b"]
+
+
+def FUVBETA(Y, X, **kw):
+    """FUVBETA(Y, X), src/RcppEigen20230423.cpp:1709-1718 (R/RcppExports.R:224): p x k, solver1xF per trait."""
+    return uvbeta(Y, X, "F", **kw)["b"]
+
+
+def XFUVBETA(Y, X, **kw):
+    """XFUVBETA(Y, X), src/RcppEigen20230423.cpp:1746-1753 (R/RcppExports.R:228): p x k, xsolver1xF per trait (lambda = mean XX_j).  A trait
+    with no observed row gives a zero column (the reference has no such test there and returns NaN)."""
+    return uvbeta(Y, X, "X", **kw)["b"]
+
+
+def ZFUVBETA(Y, X, **kw):
+    """ZFUVBETA(Y, X), src/RcppEigen20230423.cpp:1807-1816 (R/RcppExports.R:236): (p + 2) x k; row 0 is 1 - ve / vy, row 1 mu, then b."""
+    r = uvbeta(Y, X, "Z", **kw)
+    return np.vstack([r["h2"][None, :], r["mu"][None, :], r["b"]])
+
+
 # ---- relationship kernels: GRM / GAU (R/RcppExports.R:100-106), EigenARC / EigenGAU / EigenGRM (:140-150) ----
 def _kernel_panel(X, panel_kw):
     """X as an int8 panel.  The int8 product is the feature: a float matrix must hold integers in -128..127 (checked here, before the library is

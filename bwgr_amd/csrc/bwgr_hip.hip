@@ -20,6 +20,7 @@
 #include "sweep2w.hip.h"
 #include "sweep3p.hip.h"
 #include "mrr.hip.h"
+#include "uvb.hip.h"
 #include "kernels.hip.h"
 #include <stdlib.h>
 
@@ -4021,6 +4022,298 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
       if (vb_out) vb_out[j * k + i] = vb[i * k + j];
     }
   *its = numit;
+  return BWGR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// per-trait ridge fits: solver1x / UVBETA, solver1xF / FUVBETA, xsolver1xF / XFUVBETA, zsolver1xF / ZFUVBETA
+// (src/RcppEigen20230423.cpp:1410-1443, :1506-1515, :1613-1646, :1709-1753, :1771-1816): the engine of uvb.hip.h
+//   once:       k_uvb_setup, k_uvb_cols(TrXSX) per group of 64 traits
+//   per sweep:  order (host std::shuffle, cumulative) -> k_permute_cols, then for every group with a trait still running:
+//               k_mrr_gram -> [k_uvb_pass(b-1 | b), k_uvb_solve(b)] for every block -> k_uvb_pass(last | -) -> k_uvb_rows, k_uvb_cols;
+//               one copy of every group's sums -> (host: mu, ve, vb, lambda, cnv, who stops) -> k_uvb_mu_shift
+// ------------------------------------------------------------------------------------------------
+// The plan, decided here and nowhere else (bwgr_debug_uvb_plan exposes it to the CPU tests): the groups, the solve's LDS (as many of a
+// solve workgroup's Gram matrices as fit beside u), the pass's grid, and the element counts of the call's device arrays.
+struct UvbPlan {
+  int64_t groups, nblk, kpad; int ngl, G, nsolve; size_t lds_solve, lds_pass;
+  size_t x_bytes, n_gram, n_zm, n_rows, n_cols, n_part, n_dB, n_tpart, n_res, n_slot, n_bout, n_xb;   // element counts
+  size_t ws_bytes;
+};
+// npat_max: the most patterns any group has; npat_total: the patterns of all groups.  Negative: their bounds (every trait its own pattern),
+// which is what is known before Y has been read.
+static UvbPlan uvb_plan(int64_t n, int64_t ld, int64_t p, int64_t k, size_t x_bytes, int64_t npat_max, int64_t npat_total, bool want_xb) {
+  UvbPlan pl;
+  if (npat_max < 0) npat_max = std::min<int64_t>(k, UVB_W);
+  if (npat_total < 0) npat_total = k;
+  pl.groups = (k + UVB_W - 1) / UVB_W; pl.kpad = pl.groups * UVB_W; pl.nblk = (p + MRR_MB - 1) / MRR_MB;
+  pl.nsolve = UVB_W / UVB_ST;
+  pl.ngl = (int)std::min<size_t>((size_t)UVB_ST, (MRR_LDS_MAX - uvb_solve_lds(0)) / ((size_t)UVB_GSTR * 4));
+  pl.lds_solve = uvb_solve_lds(pl.ngl); pl.lds_pass = UVB_PASS_LDS;
+  pl.G = (int)std::min<int64_t>(ld / 64, UVB_PASS_WG);
+  pl.x_bytes = x_bytes;
+  pl.n_gram = (size_t)pl.nblk * (size_t)npat_max * MRR_MB * MRR_MB;      // int32: one group's block Gram matrices, rebuilt per sweep and group
+  pl.n_zm = (size_t)npat_total * ld;                                      // bytes: the row masks k_mrr_gram ANDs with
+  pl.n_rows = (size_t)pl.kpad * ld;                                       // doubles: y, e
+  pl.n_cols = (size_t)pl.kpad * p;                                        // doubles: S, XX, tilde, b
+  pl.n_part = (size_t)pl.G * (MRR_MB + 1) * UVB_W; pl.n_dB = (size_t)(MRR_MB + 1) * UVB_W;
+  pl.n_tpart = (size_t)UVB_NP * 3 * UVB_W; pl.n_res = (size_t)pl.kpad * 6;
+  pl.n_slot = (size_t)pl.groups * pl.nsolve * pl.ngl;
+  pl.n_bout = (size_t)p * k; pl.n_xb = want_xb ? (size_t)n * k : 0;
+  pl.ws_bytes = x_bytes + 4 * (size_t)p + 4 * std::max<size_t>(pl.n_gram, 1) + std::max<size_t>(pl.n_zm, 1) + 8 * (size_t)pl.groups * ld + 8 * (2 * pl.n_rows + 4 * pl.n_cols + pl.n_part + pl.n_dB + pl.n_tpart + pl.n_res) +
+                8 * 2 * (size_t)pl.kpad /* db2, mu0 */ + sizeof(UvbTrait) * (size_t)pl.kpad + 4 * pl.n_slot + 8 * (pl.n_bout + pl.n_xb);
+  return pl;
+}
+extern "C" int bwgr_debug_uvb_plan(int64_t n, int64_t p, int64_t k, int64_t out[BWGR_UVB_PLAN_NOUT]) {
+  if (!out) return fail(BWGR_EINVAL, "uvb plan: null pointer");
+  if (n < 1 || p < 1 || k < 1) return fail(BWGR_EINVAL, "uvb plan: n = %lld, p = %lld, k = %lld (each at least 1)", (long long)n, (long long)p, (long long)k);
+  const int64_t ld = (n + 127) / 128 * 128;
+  const UvbPlan pl = uvb_plan(n, ld, p, k, (size_t)ld * p, -1, -1, true);
+  out[0] = UVB_W; out[1] = pl.groups; out[2] = UVB_ST; out[3] = pl.ngl; out[4] = (int64_t)pl.lds_solve; out[5] = (int64_t)pl.lds_pass;
+  out[6] = pl.G; out[7] = (int64_t)pl.ws_bytes;
+  return BWGR_OK;
+}
+
+extern "C" int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int variant, int maxit, double tol, double df0, double *b_out, double *mu_out,
+                           double *h2_out, double *ve_out, double *vb_out, int *its_out, double *cnv_out, double *xb_out) {
+  if (!P || !Y || !b_out || !its_out) return fail(BWGR_EINVAL, "uvbeta: null pointer");
+  if (k < 1) return fail(BWGR_EINVAL, "uvbeta: k = %lld traits (at least 1)", (long long)k);
+  if (variant < BWGR_UVB_D || variant > BWGR_UVB_Z) return fail(BWGR_EINVAL, "uvbeta: unknown variant %d (0 solver1x, 1 solver1xF, 2 xsolver1xF, 3 zsolver1xF)", variant);
+  if (maxit < 0) return fail(BWGR_EINVAL, "uvbeta: maxit = %d", maxit);
+  if (P->data->is_f32) return fail(BWGR_EINVAL, "uvbeta: the panel holds fp32 genotypes; uvbeta takes int8 panels only");
+  HIPCHK(hipSetDevice(P->data->device));
+  const int64_t n = P->data->n, p = P->data->p, ld = P->data->plan.ld;
+  const int R = P->data->plan.R;
+  {
+    const int64_t xm = std::max(P->data->xmax, 1);
+    if ((int64_t)n * xm * xm >= (1ll << 31)) return fail(BWGR_EINVAL, "uvbeta: n * max|x|^2 = %lld does not fit the int32 Gram", (long long)(n * xm * xm));
+  }
+  UvbPlan pl = uvb_plan(n, ld, p, k, P->data->plan.x_bytes, -1, -1, xb_out != nullptr);   // (the pattern counts follow once Y has been read)
+  const int64_t groups = pl.groups, kpad = pl.kpad;
+  // ---- host set-up (:1413-1423 on the trait's own rows, as submat_f / subvec_f select them, :1495-1503) ----
+  struct Trait { double nt = 0, mu = 0, sumy = 0, vy = 0, TrXSX = 0, ve = NAN, vb = NAN, ve0 = 0, vb0 = 0, cnv = NAN; int its = 0; bool active = false; };
+  std::vector<Trait> T((size_t)k);
+  std::vector<double> y((size_t)kpad * ld, 0.0);
+  std::vector<unsigned long long> zb((size_t)groups * ld, 0ull);
+  for (int64_t t = 0; t < k; ++t) {
+    Trait &q = T[(size_t)t];
+    unsigned long long *zg = zb.data() + (size_t)(t / UVB_W) * ld;
+    for (int64_t r = 0; r < n; ++r) {
+      const double v = Y[(size_t)t * n + r];
+      if (!std::isnan(v)) { zg[r] |= 1ull << (t % UVB_W); q.nt += 1.0; q.mu += v; }
+    }
+    if (q.nt == 1.0) return fail(BWGR_EINVAL, "uvbeta: trait %lld has one observed row (the variances divide by n - 1)", (long long)t);
+    if (q.nt == 0.0) continue;   // an all-NaN trait: a zero column, no sweeps (:1510, :1713, :1811)
+    q.mu /= q.nt;                                                                                          // :1413
+    double *yt = y.data() + (size_t)t * ld;
+    for (int64_t r = 0; r < n; ++r)
+      if ((zg[r] >> (t % UVB_W)) & 1ull) { yt[r] = Y[(size_t)t * n + r] - q.mu; q.sumy += yt[r]; q.vy += yt[r] * yt[r]; }   // :1414
+    q.vy /= (q.nt - 1.0);                                                                                  // :1419 (y'Y = y'y: sum y = 0)
+    q.active = maxit > 0;
+  }
+  // missingness patterns per group: traits with the same observed rows share one masked Gram
+  std::vector<UvbTrait> tr((size_t)kpad);
+  std::vector<uint8_t> zm;
+  std::vector<int> npat((size_t)groups, 0);
+  std::vector<size_t> zm_off((size_t)groups, 0);
+  {
+    std::vector<uint8_t> col((size_t)ld);
+    for (int64_t g = 0; g < groups; ++g) {
+      zm_off[(size_t)g] = zm.size();
+      for (int tl = 0; tl < UVB_W; ++tl) {
+        const int64_t t = g * UVB_W + tl;
+        UvbTrait &u = tr[(size_t)t];
+        u.lam = 0.0; u.nt = 0.0; u.pat = 0; u.slot = -1; u.active = 0; u.pad_ = 0;
+        if (t >= k || T[(size_t)t].nt == 0.0) continue;
+        u.nt = T[(size_t)t].nt;
+        for (int64_t r = 0; r < ld; ++r) col[(size_t)r] = ((zb[(size_t)g * ld + r] >> tl) & 1ull) ? 0xFF : 0;
+        int f = -1;
+        for (int q = 0; q < npat[(size_t)g] && f < 0; ++q)
+          if (memcmp(zm.data() + zm_off[(size_t)g] + (size_t)q * ld, col.data(), (size_t)ld) == 0) f = q;
+        if (f < 0) { f = npat[(size_t)g]++; zm.insert(zm.end(), col.begin(), col.end()); }
+        u.pat = f;
+      }
+    }
+  }
+  {
+    int64_t npat_total = 0;
+    for (int v : npat) npat_total += v;
+    pl = uvb_plan(n, ld, p, k, P->data->plan.x_bytes, *std::max_element(npat.begin(), npat.end()), npat_total, xb_out != nullptr);
+  }
+  // the LDS slots of every solve workgroup: the first ngl distinct patterns among its 16 traits
+  std::vector<int> slotpat(pl.n_slot, -1);
+  for (int64_t g = 0; g < groups; ++g)
+    for (int sb = 0; sb < pl.nsolve; ++sb) {
+      int *sp = slotpat.data() + ((size_t)g * pl.nsolve + sb) * pl.ngl;
+      int used = 0;
+      for (int tl = 0; tl < UVB_ST; ++tl) {
+        UvbTrait &u = tr[(size_t)(g * UVB_W + sb * UVB_ST + tl)];
+        if (u.nt == 0.0) continue;
+        for (int s = 0; s < used && u.slot < 0; ++s) if (sp[s] == u.pat) u.slot = s;
+        if (u.slot < 0 && used < pl.ngl) { sp[used] = u.pat; u.slot = used++; }
+      }
+    }
+  hipStream_t st = P->stream;
+  std::vector<int> order((size_t)p);
+  std::vector<double> res(pl.n_res), db2h((size_t)kpad), mu0((size_t)kpad, 0.0);   // (copied to and from asynchronously: declared before the holder)
+  DevBufs bufs(st);
+  const int64_t nblk = pl.nblk;
+  const size_t nl = (size_t)ld, np = (size_t)p;
+  int8_t *Xs = bufs.get<int8_t>(pl.x_bytes);
+  int32_t *ordd = bufs.get<int32_t>(np), *gram = bufs.get<int32_t>(pl.n_gram);
+  uint8_t *zmd = bufs.get<uint8_t>(pl.n_zm);   // (= zm.size())
+  unsigned long long *zbd = bufs.get<unsigned long long>((size_t)groups * nl);
+  double *yd = bufs.get<double>(pl.n_rows), *ed = bufs.get<double>(pl.n_rows);
+  double *Sd = bufs.get<double>(pl.n_cols), *XXd = bufs.get<double>(pl.n_cols), *tilde = bufs.get<double>(pl.n_cols), *bd = bufs.get<double>(pl.n_cols);
+  double *part = bufs.get<double>(pl.n_part), *dB = bufs.get<double>(pl.n_dB), *tpart = bufs.get<double>(pl.n_tpart), *resd = bufs.get<double>(pl.n_res);
+  double *db2 = bufs.get<double>((size_t)kpad), *mu0d = bufs.get<double>((size_t)kpad);
+  UvbTrait *trd = bufs.get<UvbTrait>((size_t)kpad);
+  int *slotd = bufs.get<int>(pl.n_slot);
+  double *bout = bufs.get<double>(pl.n_bout), *xbd = xb_out ? bufs.get<double>(pl.n_xb) : nullptr;
+  if (!Xs || !ordd || !gram || !zmd || !zbd || !yd || !ed || !Sd || !XXd || !tilde || !bd || !part || !dB || !tpart || !resd || !db2 || !mu0d || !trd || !slotd || !bout ||
+      (xb_out && !xbd))
+    return fail(BWGR_ENOMEM, "uvbeta: device allocation failed");
+  if (!zm.empty()) HIPCHK(hipMemcpyAsync(zmd, zm.data(), zm.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(zbd, zb.data(), sizeof(unsigned long long) * groups * nl, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(yd, y.data(), sizeof(double) * pl.n_rows, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(ed, y.data(), sizeof(double) * pl.n_rows, hipMemcpyHostToDevice, st));        // e = y, :1422
+  HIPCHK(hipMemcpyAsync(trd, tr.data(), sizeof(UvbTrait) * kpad, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(slotd, slotpat.data(), sizeof(int) * pl.n_slot, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(bd, 0, sizeof(double) * pl.n_cols, st));                                      // b = 0, :1421
+  HIPCHK(hipMemsetAsync(dB, 0, sizeof(double) * pl.n_dB, st));
+  HIPCHK(hipMemsetAsync(part, 0, sizeof(double) * pl.n_part, st));
+  HIPCHK(hipMemsetAsync(tpart, 0, sizeof(double) * pl.n_tpart, st));
+  HIPCHK(hipMemsetAsync(resd, 0, sizeof(double) * pl.n_res, st));
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_uvb_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_uvb_pass), hipFuncAttributeMaxDynamicSharedMemorySize, (int)UVB_PASS_LDS));
+  // the traits of group g that have rows / that still run
+  auto mask_of = [&](int64_t g, bool running) {
+    unsigned long long m = 0;
+    for (int tl = 0; tl < UVB_W; ++tl) {
+      const int64_t t = g * UVB_W + tl;
+      if (t < k && (running ? T[(size_t)t].active : T[(size_t)t].nt > 0)) m |= 1ull << tl;
+    }
+    return m;
+  };
+  // sums over the markers of a group, partials in a fixed order, into resd[g][3 .. 4]
+  auto cols = [&](int64_t g, int mode, unsigned long long act) {
+    const size_t oc = (size_t)g * UVB_W * np;
+    hipLaunchKernelGGL(k_uvb_cols, dim3(UVB_NP), dim3(256), 0, st, (const double *)(bd + oc), (const double *)(tilde + oc), (const double *)(XXd + oc), p, mode, act, tpart);
+    hipLaunchKernelGGL(k_mrr_finish, dim3(1), dim3(256), 0, st, (const double *)tpart, UVB_NP, 2 * UVB_W, resd + (size_t)g * 6 * UVB_W + 3 * UVB_W);
+  };
+  for (int64_t g = 0; g < groups; ++g) {
+    const unsigned long long have = mask_of(g, false);
+    if (!have) continue;
+    const int kg = (int)std::min<int64_t>(UVB_W, k - g * UVB_W);
+    const size_t oc = (size_t)g * UVB_W * np, orow = (size_t)g * UVB_W * nl;
+    hipLaunchKernelGGL(k_uvb_setup, dim3((unsigned)nblk), dim3(256), 0, st, (const int8_t *)P->data->X, R, p, ld, (const unsigned long long *)(zbd + (size_t)g * nl),
+                       (const double *)(yd + orow), (const UvbTrait *)(trd + g * UVB_W), kg, Sd + oc, XXd + oc, tilde + oc);
+    cols(g, 1, have);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(d2h(st, res.data(), resd, sizeof(double) * pl.n_res));
+  for (int64_t t = 0; t < k; ++t) {
+    Trait &q = T[(size_t)t];
+    if (q.nt == 0.0) continue;
+    q.TrXSX = res[(size_t)(t / UVB_W) * 6 * UVB_W + 3 * UVB_W + (size_t)(t % UVB_W)];                    // :1418
+    const double MSx = q.TrXSX / (q.nt - 1.0);                                                             // :1419
+    if (variant == BWGR_UVB_X) { tr[(size_t)t].lam = q.TrXSX / (double)p; continue; }                      // lambda = XX.mean(), :1730
+    q.ve = q.vy * 0.5; q.vb = (q.vy * 0.5) / MSx;                                                          // :1420
+    tr[(size_t)t].lam = q.ve / q.vb; q.vb0 = q.vb * df0; q.ve0 = q.ve * df0;                               // :1423
+  }
+  // ---- sweeps ----
+  for (int64_t j = 0; j < p; ++j) order[(size_t)j] = (int)j;
+  const int cps = (int)((size_t)R / 16);
+  const double logtol = log10(tol), thr = variant == BWGR_UVB_F ? 0.00001 : 0.0;
+  for (int sweep = 0; sweep < maxit; ++sweep) {
+    bool any = false;
+    for (int64_t t = 0; t < k; ++t) { tr[(size_t)t].active = T[(size_t)t].active ? 1 : 0; any = any || T[(size_t)t].active; }
+    if (!any) break;
+    std::shuffle(order.begin(), order.end(), std::mt19937(sweep));                                         // :1428 (cumulative, as there)
+    HIPCHK(hipMemcpyAsync(ordd, order.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(trd, tr.data(), sizeof(UvbTrait) * kpad, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)P->data->X, (uint4 *)Xs, (const int32_t *)ordd, p, P->data->plan.K, cps);
+    HIPCHK(hipMemsetAsync(db2, 0, sizeof(double) * kpad, st));
+    for (int64_t g = 0; g < groups; ++g) {
+      const unsigned long long act = mask_of(g, true);
+      if (!act) continue;
+      const size_t oc = (size_t)g * UVB_W * np, orow = (size_t)g * UVB_W * nl;
+      const int ng = npat[(size_t)g];
+      int nsolve = 0;
+      for (int sb = 0; sb < pl.nsolve; ++sb) if ((act >> (sb * UVB_ST)) & 0xFFFFull) nsolve = sb + 1;
+      hipLaunchKernelGGL(k_mrr_gram, dim3((unsigned)nblk, (unsigned)((ng + 3) / 4)), dim3(256), 0, st, (const int8_t *)Xs, R, p, ld, (const uint8_t *)(zmd + zm_off[(size_t)g]), ng, gram);
+      for (int64_t blk = 0; blk <= nblk; ++blk) {
+        UvbPassArgs pa; pa.Xs = Xs; pa.R = R; pa.p = p; pa.ld = ld; pa.zb = zbd + (size_t)g * nl; pa.e = ed + orow; pa.dB = dB; pa.part = part;
+        pa.prev = blk > 0 ? (int)(blk - 1) : -1; pa.next = blk < nblk ? (int)blk : -1; pa.act = act;
+        hipLaunchKernelGGL(k_uvb_pass, dim3(pl.G), dim3(256), pl.lds_pass, st, pa);
+        if (blk == nblk) break;
+        UvbSolveArgs sa; sa.part = part; sa.G = pl.G; sa.order = ordd; sa.blk = (int)blk; sa.p = p; sa.gram = gram; sa.npat = ng; sa.S = Sd + oc; sa.XX = XXd + oc;
+        sa.b = bd + oc; sa.dB = dB; sa.db2 = db2 + g * UVB_W; sa.tr = trd + g * UVB_W; sa.slotpat = slotd + (size_t)g * pl.nsolve * pl.ngl; sa.ngl = pl.ngl; sa.thr = thr;
+        hipLaunchKernelGGL(k_uvb_solve, dim3(nsolve), dim3(256), pl.lds_solve, st, sa);
+      }
+      hipLaunchKernelGGL(k_uvb_rows, dim3(UVB_NP, UVB_W), dim3(256), 0, st, (const double *)(ed + orow), (const double *)(yd + orow), ld, act, tpart);
+      hipLaunchKernelGGL(k_mrr_finish, dim3(1), dim3(256), 0, st, (const double *)tpart, UVB_NP, 3 * UVB_W, resd + (size_t)g * 6 * UVB_W);
+      cols(g, 0, act);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(db2h.data(), db2, sizeof(double) * kpad, hipMemcpyDeviceToHost, st));
+    HIPCHK(d2h(st, res.data(), resd, sizeof(double) * pl.n_res));
+    // the tail of every trait that ran (:1433-1441, :1636-1644, :1739-1741, :1794-1801)
+    for (int64_t t = 0; t < k; ++t) {
+      Trait &q = T[(size_t)t];
+      mu0[(size_t)t] = 0.0;
+      if (!q.active) continue;
+      const double *rg = res.data() + (size_t)(t / UVB_W) * 6 * UVB_W + (size_t)(t % UVB_W);
+      const double se = rg[0], ey = rg[UVB_W], ee = rg[2 * UVB_W], bb = rg[3 * UVB_W], tb = rg[4 * UVB_W];
+      const double m0 = se / q.nt;                                             // mu0 = mean(e); the sums below are those of e - mu0
+      mu0[(size_t)t] = m0; q.mu += m0;
+      const double ey1 = ey - m0 * q.sumy, ee1 = ee - 2.0 * m0 * se + q.nt * m0 * m0;
+      if (variant == BWGR_UVB_D || variant == BWGR_UVB_F) {
+        q.ve = (ey1 + ee1 + q.ve0) / (2.0 * q.nt - 1.0 + df0);                 // :1434-1436
+        q.vb = (bb + tb + q.vb0) / (q.TrXSX + (double)p + df0);                // :1437-1439
+        tr[(size_t)t].lam = q.ve / q.vb;
+      } else if (variant == BWGR_UVB_Z) {
+        q.ve = (ey1 + q.ve0) / (q.nt + df0);                                   // :1795-1796
+        q.vb = (tb + q.vb0) / (q.TrXSX + df0);                                 // :1797-1798
+        tr[(size_t)t].lam = q.ve / q.vb;
+      }
+      q.cnv = log10(db2h[(size_t)t]);                                          // :1440
+      ++q.its;
+      if (q.cnv < logtol || q.its == maxit || std::isnan(q.cnv)) q.active = false;   // :1441
+    }
+    HIPCHK(hipMemcpyAsync(mu0d, mu0.data(), sizeof(double) * kpad, hipMemcpyHostToDevice, st));
+    for (int64_t g = 0; g < groups; ++g) {
+      unsigned long long ran = 0;
+      for (int tl = 0; tl < UVB_W; ++tl) if (tr[(size_t)(g * UVB_W + tl)].active) ran |= 1ull << tl;   // (tr.active still says who ran this sweep)
+      if (!ran) continue;
+      hipLaunchKernelGGL(k_uvb_mu_shift, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024), UVB_W), dim3(256), 0, st, ed + (size_t)g * UVB_W * nl,
+                         (const unsigned long long *)(zbd + (size_t)g * nl), ld, (int)n, ran, (const double *)(mu0d + g * UVB_W));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));   // mu0 is rewritten by the next sweep's tail
+  }
+  // ---- results ----
+  for (int64_t g = 0; g < groups; ++g) {
+    const int kg = (int)std::min<int64_t>(UVB_W, k - g * UVB_W);
+    const size_t oc = (size_t)g * UVB_W * np;
+    hipLaunchKernelGGL(k_uvb_b_out, dim3((unsigned)std::min<int64_t>((p * kg + 255) / 256, 4096)), dim3(256), 0, st, (const double *)(bd + oc), p, kg, bout + (size_t)g * UVB_W * np);
+    if (xb_out)
+      hipLaunchKernelGGL(k_uvb_xb, dim3((unsigned)((n + 255) / 256), (unsigned)((kg + 15) / 16)), dim3(256), 0, st, (const int8_t *)P->data->X, R, p, (int)n, (const double *)(bd + oc), kg,
+                         xbd + (size_t)g * UVB_W * n);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(d2h(st, b_out, bout, sizeof(double) * pl.n_bout));
+  if (xb_out) HIPCHK(d2h(st, xb_out, xbd, sizeof(double) * pl.n_xb));
+  for (int64_t t = 0; t < k; ++t) {
+    const Trait &q = T[(size_t)t];
+    const bool none = q.nt == 0.0, noVar = variant == BWGR_UVB_X;
+    if (mu_out) mu_out[t] = none ? 0.0 : q.mu;
+    if (h2_out) h2_out[t] = none ? 0.0 : (noVar ? NAN : 1.0 - q.ve / q.vy);                                // :1802
+    if (ve_out) ve_out[t] = (none || noVar) ? NAN : q.ve;
+    if (vb_out) vb_out[t] = (none || noVar) ? NAN : q.vb;
+    if (cnv_out) cnv_out[t] = q.cnv;
+    its_out[t] = q.its;
+  }
   return BWGR_OK;
 }
 

@@ -274,6 +274,45 @@ int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opts, int nopt
  * in LDS (patterns ngl..npat-1 are read from global memory); the dynamic LDS bytes of the solve and of the inverses' kernel.  Any
  * output may be NULL. */
 int bwgr_debug_mrr_plan(int k, int npat, int *linv_lds, int *ngl, int64_t *solve_lds_bytes, int64_t *linv_lds_bytes);
+/* ---- per-trait ridge fits (UVBETA / FUVBETA family) -------------------------------------------------------
+ * Replaces VectorXd solver1x(Y,X,maxit,tol,df0) src/RcppEigen20230423.cpp:1410-1443 and MatrixXd UVBETA(Y,X) :1506-1515; solver1xF :1613-1646 and
+ * FUVBETA :1709-1718; xsolver1xF :1721-1743 and XFUVBETA :1746-1753; zsolver1xF :1771-1804 and ZFUVBETA :1807-1816 (R/RcppExports.R:196-238).
+ * One randomized Gauss-Seidel ridge fit per column of Y, all on the panel's X: each trait is fitted on its own observed rows (NaN = missing;
+ * the reference subsets X and Y per trait, :1495-1503), with its own column means over those rows, its own lambda and its own stopping sweep.
+ * The marker order of sweep s is the EM family's (bwgr_em_order), so all traits share one gathered panel per sweep.  Y: n x k column-major
+ * doubles; k >= 1 has no upper limit (the engine takes the traits 64 at a time).  variant: BWGR_UVB_D solver1x / UVBETA; BWGR_UVB_F solver1xF /
+ * FUVBETA (the test XX_j > 1e-5, else b_j = 0, :1633-1635); BWGR_UVB_X xsolver1xF / XFUVBETA (lambda = mean XX_j, fixed; no variances: ve, vb
+ * and h2 return NaN); BWGR_UVB_Z zsolver1xF / ZFUVBETA (its own variance updates, h2 = 1 - ve / vy).  The float variants run the fp64 engine;
+ * the caller rounds Y (and tol, df0) to float, as for bwgr_mrr.  maxit, tol, df0: the solvers' arguments (reference defaults 100, 10e-7, 20;
+ * xsolver1xF and zsolver1xF have them built in).  A trait stops when its own log10 sum (delta b)^2 < log10(tol), at maxit, or on NaN; a
+ * stopped trait's state is not touched again.  tol = 0 never stops early; maxit = 0 returns b = 0.
+ * Outputs (host; only b and its are required): b[p x k] column-major, mu[k], h2[k] (1 - ve / vy), ve[k], vb[k], its[k] (sweeps each trait
+ * ran), cnv[k] (each trait's last convergence value), xb[n x k] = X b on the raw genotypes for every row, the unobserved ones included (what
+ * GSEM / XSEMF / ZSEMF form next, :1586, :1758, :1822).  A trait with no observed row gives a zero column of b, its = 0, mu = h2 = 0 and NaN
+ * elsewhere, for every variant (XFUVBETA has no such test and would return NaN there).  A panel switched to implicit centring gives
+ * bit-identical results (the fit reads the raw genotypes and centres per trait).
+ * BWGR_EINVAL: an fp32 panel, an unknown variant, maxit < 0, k < 1, a trait with exactly one observed row (the reference divides by n - 1;
+ * the message names the trait), n * max|x|^2 >= 2^31 (the int32 block Gram).
+ * Degenerate traits are not refused and follow the reference's arithmetic: a trait that is constant on its observed rows has vy = 0, hence
+ * ve = vb = 0 and lambda = 0 / 0, and its column comes back NaN with its = 1 (the NaN convergence value stops it, as in the reference); a trait
+ * whose markers are all monomorphic on its rows has TrXSX = 0, hence vb = inf and lambda = 0: every marker takes the XX_j = 0 path and b stays
+ * 0 (the reference's D and Z give 0 / 0 = NaN there).  For BWGR_UVB_X with TrXSX = 0 the library likewise returns b = 0 where the reference
+ * returns NaN.  Neither affects the other traits of the call.
+ * Not here: MEGA, GSEM, XSEMF, ZSEMF, YSEMF (their second stage fits on a dense latent matrix, which needs non-int8 panels); solver2x /
+ * solver2xF (two panels); fp32 panels; groups of traits sharded over GPUs. */
+enum { BWGR_UVB_D = 0 /* solver1x  / UVBETA   */, BWGR_UVB_F = 1 /* solver1xF / FUVBETA  */,
+       BWGR_UVB_X = 2 /* xsolver1xF/ XFUVBETA */, BWGR_UVB_Z = 3 /* zsolver1xF/ ZFUVBETA */ };
+int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int variant, int maxit, double tol, double df0,
+                double *b /* p x k, column-major */, double *mu, double *h2, double *ve, double *vb,
+                int *its /* k: sweeps each trait ran */, double *cnv /* k: each trait's last value */,
+                double *xb /* n x k = X b on the raw genotypes, every row; may be NULL */);
+/* host arithmetic of bwgr_uvbeta's plan (needs no GPU), in the style of bwgr_debug_mrr_plan, for n rows, p markers and k traits (each at
+ * least 1, else BWGR_EINVAL): out[0..7] = W (traits per group), groups = ceil(k / W), traits per solve workgroup, Gram matrices a solve
+ * workgroup stages in LDS (the patterns of its other traits are read from global memory), the solve's dynamic LDS bytes, the pass's, the
+ * pass's workgroups, and an upper bound of the call's device workspace in bytes (rows padded to 128, every trait its own pattern, xb
+ * requested). */
+#define BWGR_UVB_PLAN_NOUT 8
+int bwgr_debug_uvb_plan(int64_t n, int64_t p, int64_t k, int64_t out[BWGR_UVB_PLAN_NOUT]);
 /* host arithmetic of a panel's plan (needs no GPU): what bwgr_panel_create would decide for an int8 (is_f32 = 0) or float panel of n x p
  * with these block / nwg arguments under the BWGR_* switches of the environment; kind 0: a main panel, 1: the row-subset scratch panel of
  * KMUP2 and wgr's bagging, 2: bwgr_em's scratch panel.  A shape bwgr_panel_create refuses returns its code and leaves its message in

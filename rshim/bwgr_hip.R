@@ -79,6 +79,17 @@ MRR3F <- function(Y, X, maxit = 500L, tol = 10e-9, cores = 1L, TH = FALSE, NonLi
   .Call("bwgrhip_MRR3F", .bwgr_f32(as.matrix(Y)), .bwgr_panel(X), .bwgr_mrr_opts(maxit, tol, TH, NonLinearFactor, InnerGS, NoInv, HCS, XFA, ACS, NumXFA, R2, gc0, df0, updateMu, weight_prior_h2, weight_prior_gc, PenCor, MinCor, uncorH2below, roundGCupFrom, roundGCupTo, roundGCdownFrom, roundGCdownTo, bucketGCfrom, bucketGCto, DeflateMax, DeflateBy, OneVarB, OneVarE, verbose))
 mrr <- function(Y, X, ...) MRR3(Y, X, ...)
 mrr_float <- function(Y, X, ...) MRR3F(Y, X, ...)
+# per-trait ridge fits, R/RcppExports.R:196-238 (solver1x, UVBETA, solver1xF, FUVBETA, XFUVBETA, ZFUVBETA): same names, argument order,
+# defaults and return shapes.  Integer genotypes only (an int8 panel).  Y: NA = missing; every trait is fitted on its own observed rows.
+# A trait without observed rows gives a zero column (XFUVBETA too).  The float solvers receive float-rounded Y, tol and df0.
+solver1x <- function(Y, X, maxit = 100L, tol = 10e-7, df0 = 20.0)
+  .Call("bwgrhip_solver1x", as.double(Y), .bwgr_ipanel(X), 0L, as.integer(maxit), as.double(tol), as.double(df0))
+solver1xF <- function(Y, X, maxit = 100L, tol = 10e-7, df0 = 20.0)
+  .Call("bwgrhip_solver1x", .bwgr_f32(as.double(Y)), .bwgr_ipanel(X), 1L, as.integer(maxit), .bwgr_f32(tol), .bwgr_f32(df0))
+UVBETA <- function(Y, X) .Call("bwgrhip_UVBETA", as.matrix(Y) * 1.0, .bwgr_ipanel(X), 0L)
+FUVBETA <- function(Y, X) .Call("bwgrhip_UVBETA", .bwgr_f32(as.matrix(Y)), .bwgr_ipanel(X), 1L)
+XFUVBETA <- function(Y, X) .Call("bwgrhip_UVBETA", .bwgr_f32(as.matrix(Y)), .bwgr_ipanel(X), 2L)
+ZFUVBETA <- function(Y, X) .Call("bwgrhip_UVBETA", .bwgr_f32(as.matrix(Y)), .bwgr_ipanel(X), 3L)
 # relationship kernels, R/RcppExports.R:100-106 (GAU, GRM) and :140-150 (EigenARC, EigenGAU, EigenGRM): same names, argument order and defaults;
 # integer genotypes only (an int8 panel); `cores` is ignored.  Their result feeds wgr(eigK = eigen(K)).
 # (a numeric matrix of whole numbers is staged as integers, so that it becomes an int8 panel)

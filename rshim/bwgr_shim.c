@@ -305,6 +305,43 @@ static SEXP mrr_call(SEXP Y, SEXP panel, SEXP opts) {
 SEXP bwgrhip_MRR3(SEXP Y, SEXP panel, SEXP opts) { return mrr_call(Y, panel, opts); }
 SEXP bwgrhip_MRR3F(SEXP Y, SEXP panel, SEXP opts) { return mrr_call(Y, panel, opts); }
 
+/* per-trait ridge fits: solver1x / solver1xF(Y, X, maxit, tol, df0) src/RcppEigen20230423.cpp:1410-1443, :1613-1646 -> the p effects;
+ * UVBETA / FUVBETA / XFUVBETA(Y, X) :1506-1515, :1709-1753 -> p x k; ZFUVBETA(Y, X) :1807-1816 -> (p + 2) x k, rows 1 - ve / vy, mu, b.
+ * variant: BWGR_UVB_*.  Y: NA = missing (solver1x: those rows are left out).  The float variants' inputs are rounded by the R front-end. */
+SEXP bwgrhip_solver1x(SEXP Y, SEXP panel, SEXP variant, SEXP maxit, SEXP tol, SEXP df0) {
+  bwgr_panel *P = panel_of(panel);
+  int64_t info[8]; chk(bwgr_panel_info(P, info));
+  const R_xlen_t n = info[0], p = info[1];
+  if (XLENGTH(Y) != n) Rf_error("Y must have nrow(X) entries");
+  SEXP b = PROTECT(Rf_allocVector(REALSXP, p));
+  int its = 0;
+  chk(bwgr_uvbeta(P, REAL(Y), 1, Rf_asInteger(variant), Rf_asInteger(maxit), Rf_asReal(tol), Rf_asReal(df0), REAL(b), NULL, NULL, NULL, NULL, &its, NULL, NULL));
+  UNPROTECT(1);
+  return b;
+}
+SEXP bwgrhip_UVBETA(SEXP Y, SEXP panel, SEXP variant) {
+  bwgr_panel *P = panel_of(panel);
+  int64_t info[8]; chk(bwgr_panel_info(P, info));
+  const R_xlen_t n = info[0], p = info[1];
+  SEXP dim = Rf_getAttrib(Y, R_DimSymbol);
+  if (Rf_length(dim) != 2 || INTEGER(dim)[0] != n) Rf_error("Y must be a matrix with nrow(X) rows");
+  const int k = INTEGER(dim)[1], v = Rf_asInteger(variant);
+  const float tol = 10e-7f, df0 = 20.0f;                      /* the float solvers' arguments, as they receive them (:1614, :1723, :1772) */
+  double *b = (double *)R_alloc((size_t)p * (k > 0 ? k : 1), sizeof(double)), *mu = (double *)R_alloc(k > 0 ? k : 1, sizeof(double));
+  double *h2 = (double *)R_alloc(k > 0 ? k : 1, sizeof(double));
+  int *its = (int *)R_alloc(k > 0 ? k : 1, sizeof(int));
+  chk(bwgr_uvbeta(P, REAL(Y), k, v, 100, v == BWGR_UVB_D ? 10e-7 : (double)tol, (double)df0, b, mu, h2, NULL, NULL, its, NULL, NULL));
+  const int head = v == BWGR_UVB_Z ? 2 : 0;
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, (int)p + head, k));
+  for (int t = 0; t < k; t++) {
+    double *o = REAL(out) + (size_t)t * (p + head);
+    if (head) { o[0] = h2[t]; o[1] = mu[t]; }
+    for (R_xlen_t j = 0; j < p; j++) o[head + j] = b[(size_t)t * p + j];
+  }
+  UNPROTECT(1);
+  return out;
+}
+
 /* relationship kernels: GRM(X, Code012) / GAU(X) src/Rcpp20260726ai.cpp:1338-1383, EigenARC / EigenGAU / EigenGRM(X, ., cores)
  * src/RcppEigen20230423.cpp:8-51 -> an n x n numeric matrix.  kind: BWGR_K_*; par: phi; flag: Code012 / centralizeZ / centralizeX. */
 SEXP bwgrhip_kernel(SEXP panel, SEXP kind, SEXP par, SEXP flag) {
@@ -334,6 +371,7 @@ static const R_CallMethodDef CallEntries[] = {   /* as src/RcppExports.cpp:1152-
   {"bwgrhip_Bayes", (DL_FUNC)&bwgrhip_Bayes, 8}, {"bwgrhip_Bayes2", (DL_FUNC)&bwgrhip_Bayes2, 9},
   {"bwgrhip_wgr", (DL_FUNC)&bwgrhip_wgr, 14}, {"bwgrhip_em", (DL_FUNC)&bwgrhip_em, 7},
   {"bwgrhip_MRR3", (DL_FUNC)&bwgrhip_MRR3, 3}, {"bwgrhip_MRR3F", (DL_FUNC)&bwgrhip_MRR3F, 3},
+  {"bwgrhip_solver1x", (DL_FUNC)&bwgrhip_solver1x, 6}, {"bwgrhip_UVBETA", (DL_FUNC)&bwgrhip_UVBETA, 3},
   {"bwgrhip_kernel", (DL_FUNC)&bwgrhip_kernel, 4}, {"bwgrhip_crossprod", (DL_FUNC)&bwgrhip_crossprod, 1}, {NULL, NULL, 0}};
 
 void R_init_bwgrhip(DllInfo *dll) {              /* as R_init_bWGR, src/RcppExports.cpp:1230-1233 */
