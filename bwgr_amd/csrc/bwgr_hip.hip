@@ -948,6 +948,13 @@ struct Switches {
   // instead of the fixed-point ones; BWGR_WPF / BWGR_WAHEAD / BWGR_WNQ (0: by the streamer count) / BWGR_WLAG (=5|6: distances 4 / 5 through LDS
   // planes -- measured slower: C4-shape BayesA 22.3 / 23.0 / 24.9 ms per sweep at depth 4 / 5 / 6)
   bool winv = true, wfx = true;
+  // BWGR_FIXED3=0: k_sweep3 also where a launch matches k_sweep3f, the fixed-shape instantiation (plan_sweep).  The experiment build (-DBWGR_EXPERIMENTS)
+  // takes k_sweep3f only when asked, BWGR_FIXED3=1: tools/ab3_probe.py times either one under the BWGR_DBG3 switches.
+#ifdef BWGR_EXPERIMENTS
+  bool fixed3 = false;
+#else
+  bool fixed3 = true;
+#endif
   int wpf = 4, wahead = 5, wnq = 0, wlag_cap = 4;
   bool group_allow_uncentred = false, group_force_comm = false, em_debug = false;   // BWGR_GROUP_ALLOW_UNCENTRED=1, BWGR_GROUP_FORCE_COMM=1, BWGR_EM_DEBUG
   int64_t kchunk = 0;   // BWGR_KCHUNK: markers per int32 chunk of the X X' product (0: the largest that keeps the int32 sums exact, plan_xxt)
@@ -965,7 +972,9 @@ static Switches read_switches() {
   s.max_concurrent = num(getenv("BWGR_MAX_CONCURRENT")); s.max_pairs = num(getenv("BWGR_MAX_PAIRS"));
   if (const char *v = getenv("BWGR_ENG3_THR")) { const float t = (float)atof(v); if (t > 0.0f) s.eng3_thr = t; }
   s.occ_guard = chr(getenv("BWGR_OCC_GUARD")) != '0'; s.pf3b = chr(getenv("BWGR_PF3B")) != '0'; s.draws = chr(getenv("BWGR_DRAWS")) != '0';
-  s.gram16 = chr(getenv("BWGR_GRAM16")) != '0'; s.winv = chr(getenv("BWGR_WINV")) != '0'; s.wfx = chr(getenv("BWGR_WFX")) != '0';
+  s.gram16 = chr(getenv("BWGR_GRAM16")) != '0';
+  { const int c = chr(getenv("BWGR_FIXED3")); if (c == '0') s.fixed3 = false; else if (c == '1') s.fixed3 = true; }
+  s.winv = chr(getenv("BWGR_WINV")) != '0'; s.wfx = chr(getenv("BWGR_WFX")) != '0';
   if (const char *v = getenv("BWGR_WPF")) s.wpf = std::max(0, std::min(8, atoi(v)));
   if (const char *v = getenv("BWGR_WAHEAD")) s.wahead = std::max(1, atoi(v));
   { const int v = num(getenv("BWGR_WNQ")), c = chr(getenv("BWGR_WLAG")); if (v == 1 || v == 2 || v == 4) s.wnq = v; if (c >= '2' && c <= '6') s.wlag_cap = c - '0'; }
@@ -1290,6 +1299,7 @@ struct SweepPlan {
   int lag = 2, nfeed = 0;  // pipeline depth; q feeder workgroups of k_sweep2
   bool g16 = false;        // k_sweep2 on the 16-bit Gram copies
   int R3 = 0, K3 = 0, sub = 0, pf = -1, pf2 = -1, dbg3 = 0, qsplit = 0, skip_vb = 0;   // k_sweep3 (dbg3: the DMA streamer bits, and BWGR_DBG3)
+  bool fixed3 = false;     // ... as k_sweep3f, the fixed-shape instantiation
   int fx = 0, nd = 0, npf = 0, ahead = 0, nq = 0, wsub = 0, wK3 = 0;                  // k_sweep2w
   bool guarded = false;    // the range snapshot in front, the fp64 redo (plan_sweep(P, a, true)) behind
   bool draws = false;      // the next iteration's variates drawn beside the sweep (draws_ahead)
@@ -1443,7 +1453,8 @@ static int sweep3_build(bwgr_panel *P) {
     HIPCHK(hipGetLastError());
   }
   for (const void *f : {reinterpret_cast<const void *>(k_sweep3<uint16_t, false>), reinterpret_cast<const void *>(k_sweep3<int32_t, false>), reinterpret_cast<const void *>(k_sweep3<uint16_t, true>),
-                        reinterpret_cast<const void *>(k_sweep3<int32_t, true>), reinterpret_cast<const void *>(k_sweep3p<uint16_t>), reinterpret_cast<const void *>(k_sweep3p<int32_t>)})
+                        reinterpret_cast<const void *>(k_sweep3<int32_t, true>), reinterpret_cast<const void *>(k_sweep3p<uint16_t>), reinterpret_cast<const void *>(k_sweep3p<int32_t>),
+                        reinterpret_cast<const void *>(k_sweep3f)})
     HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   D->e3_ready = true;
   return BWGR_OK;
@@ -1618,7 +1629,13 @@ static SweepPlan plan_sweep(const bwgr_panel *P, const SweepArgs &a, bool redo) 
     const int grid = pl.K3 + 1 + (pf_on ? 1 : 0) + (pf2_on ? 1 : 0);
     const void *fn = P->data->gram16 ? (cen ? reinterpret_cast<const void *>(k_sweep3<uint16_t, true>) : reinterpret_cast<const void *>(k_sweep3<uint16_t, false>))
                                   : (cen ? reinterpret_cast<const void *>(k_sweep3<int32_t, true>) : reinterpret_cast<const void *>(k_sweep3<int32_t, false>));
-    spin(fn, grid, grid, SW_THREADS, P->data->plan3.lds3);
+    // k_sweep3f (sweep3.hip.h, S3Shape128) is this launch with its geometry as constants and no other role compiled in: taken where the launch is exactly
+    // that -- 128 markers a block and their packed stride, 16-bit Gram entries with the distance-1 / 2 records, columns as stored, 128-row DMA streamers
+    // with four tile buffers and nothing else asked of dbg3 (the experiment build keeps BWGR_DBG3: the same switches in both kernels), the 4 + 3 digit
+    // split; not under the abort hook, whose absent streamer is k_sweep3's.  The same chain bit for bit; bwgr_debug_sweep3_kernel() tells which one runs.
+    pl.fixed3 = sw.fixed3 && P->data->gram16 && !cen && P->data->gx12 && P->data->plan.m == S3Shape128::m && P->data->plan.pstride == S3Shape128::pstride &&
+                pl.R3 == 128 && (pl.dbg3 & (3 << 22)) == (1 << 22) && pl.qsplit == 1 && !P->debug_withhold;
+    spin(pl.fixed3 ? reinterpret_cast<const void *>(k_sweep3f) : fn, grid, grid, SW_THREADS, P->data->plan3.lds3);
   }
   if (!std::isinf(pl.gate3)) {
     if (winv) {
@@ -2107,6 +2124,17 @@ extern "C" int bwgr_panel_info(const bwgr_panel *P, int64_t info[8]) {
   if (!P || !info) return fail(BWGR_EINVAL, "null pointer");
   info[0] = P->data->n; info[1] = P->data->p; info[2] = P->data->plan.ld; info[3] = P->data->plan.m; info[4] = P->data->plan.K; info[5] = P->data->plan.R;
   info[6] = (int64_t)P->data->plan.x_bytes; info[7] = (int64_t)(2 * P->data->plan.gram_bytes);
+  return BWGR_OK;
+}
+
+// Which instantiation of the trajectory engine a selection sweep of the whole panel, as it stands now (clones alive, centred or not), is launched as:
+// 0 none (the panel's selection sweeps are not k_sweep3's), 1 k_sweep3 / k_sweep3p, 2 k_sweep3f.  For the tests.
+extern "C" int bwgr_debug_sweep3_kernel(const bwgr_panel *P, int *which) {
+  if (!P || !which) return fail(BWGR_EINVAL, "null pointer");
+  SweepArgs a{}; a.flags = SWF_SELECT | (P->data->cen ? SWF_CENTRE : 0u);
+  a.m = P->data->plan.m; a.pstride = P->data->plan.pstride; a.blk_begin = 0; a.blk_end = (int)P->data->plan.nblocks;
+  const SweepPlan pl = plan_sweep(P, a, false);
+  *which = pl.engine != 3 ? 0 : (pl.fixed3 ? 2 : 1);
   return BWGR_OK;
 }
 

@@ -51,6 +51,17 @@ static constexpr int S3_NFW = 4;                      // far-field waves of the 
 static constexpr int S3_NFL = 8;                      // rows a far-field wave keeps in flight (the rest of a dense block's rows are read in place)
 static constexpr int S3_QRAW_BYTES = SW_MAXM * 16;    // a block's slab-dot sums as the streamers' atomics leave them: two 8-byte words per marker
 
+// ---- the launch's shape as a compile-time parameter of the role functions ----
+// S3ShapeAny: everything about the panel's geometry is read from the arguments (k_sweep3, k_sweep3p: every launch).
+// S3Shape128: what every int8 panel with the default block runs when a chain has 128-row DMA streamers -- m = 128 markers a block (256-byte rows of
+// 16-bit Gram entries, packed diagonal blocks of 8 128 entries), the two slab-dot words split 4 + 3 digits -- as constants (k_sweep3f).  The depth D,
+// the streamer counts, the block range and the model flags stay arguments.  plan_sweep selects it; the arithmetic and every hand-off are the same code.
+struct S3ShapeAny { static constexpr bool fixed = false; };
+struct S3Shape128 { static constexpr bool fixed = true; static constexpr int m = SW_MAXM, pstride = SW_MAXM * (SW_MAXM - 1) / 2; };
+static_assert(S3Shape128::m == 128 && S3Shape128::pstride == 8128 && S3Shape128::pstride % 8 == 0, "the packed block's stride needs no padding at m = 128");
+template <typename SH, typename ARGS> __device__ __forceinline__ int s3_m(const ARGS &a) { if constexpr (SH::fixed) return SH::m; else return a.m; }
+template <typename SH, typename ARGS> __device__ __forceinline__ int s3_pstride(const ARGS &a) { if constexpr (SH::fixed) return SH::pstride; else return a.pstride; }
+
 struct Sweep3Args {
   SweepArgs a;
   const void *gx[S3_MAXD];       // gx[d-1], d = 1..D-1: [nblocks][m][m] cross Gram blocks X_{b-d}' X_b (uint16 or int32)
@@ -589,7 +600,7 @@ __device__ __forceinline__ void s3_streamer(const Sweep3Args &A) {
 }
 
 // The same streamer with its tiles landed by LDS-DMA (128-row streamers; BWGR_STREAM3=dma)
-template <int R3, int NTB>
+template <int R3, int NTB, typename SH = S3ShapeAny>
 __device__ __forceinline__ void s3_streamer_dma(const Sweep3Args &A) {
 #ifdef BWGR_EXPERIMENTS
   const int SDBG = A.dbg;
@@ -602,7 +613,7 @@ __device__ __forceinline__ void s3_streamer_dma(const Sweep3Args &A) {
   const int m16 = lane & 15, grp = lane >> 4;
   const int w = s3_stream_index(A);
   const unsigned long long *lists_w = A.lists;
-  const int m = a.m, R = a.R, D = A.D;
+  const int m = s3_m<SH>(a), R = a.R, D = A.D;
   constexpr int Rp = R3 + 16;         // (the digit rows' stride; the tiles are unpadded)
   constexpr int CH = R3 / 16;         // 16-byte chunks per marker
   constexpr int MPP = 1024 / R3;      // markers per 1 KiB piece
@@ -869,7 +880,10 @@ __device__ __forceinline__ void s3_streamer_dma(const Sweep3Args &A) {
       const uint32_t tile_lds = tile_la + (uint32_t)((b % NTB) * (int)tile_b);
       const uint32_t q8 = (uint32_t)((lane & 15) >> 1), p8 = (uint32_t)(lane & 1);
       const uint32_t cw = (uint32_t)(4 * wave);
-      for (int s0 = 0; s0 < ((SDBG & 256) ? 0 : mB); s0 += 64) {
+      // (the fixed shape runs both halves of every block: a ragged block's unused markers have zero digits (B, above) and their tile rows hold
+      // the launch's last column (tile_issue's clamp), so the int32 sums are the same and the loop has no trip count)
+      const int mU = SH::fixed ? m : mB;
+      for (int s0 = 0; s0 < ((SDBG & 256) ? 0 : mU); s0 += 64) {
         const uint32_t rowA = tile_lds + (uint32_t)(s0 + 16 * grp + (int)q8) * (uint32_t)R3 + 8u * p8;   // markers s0 + 16 grp + q8 and + 8 (both have marker & 7 = q8)
         const uint32_t a0 = rowA + ((((cw + 0u) ^ q8) & (uint32_t)(CH - 1)) << 4), a1 = rowA + ((((cw + 1u) ^ q8) & (uint32_t)(CH - 1)) << 4);
         const uint32_t a2 = rowA + ((((cw + 2u) ^ q8) & (uint32_t)(CH - 1)) << 4), a3 = rowA + ((((cw + 3u) ^ q8) & (uint32_t)(CH - 1)) << 4);
@@ -968,7 +982,7 @@ __device__ __forceinline__ void s3_streamer_dma(const Sweep3Args &A) {
 // ------------------------------------------------------------------------------------------------------------------
 // sequencer
 // ------------------------------------------------------------------------------------------------------------------
-template <typename GT, bool CEN = false>
+template <typename GT, bool CEN = false, typename SH = S3ShapeAny>
 __device__ __forceinline__ void s3_sequencer(const Sweep3Args &A) {
   // the experiment switches (BWGR_DBG3) cost instructions and branches inside the rounds: compiled in only with -DBWGR_EXPERIMENTS (tools/ab3_probe.py builds that library)
 #ifdef BWGR_EXPERIMENTS
@@ -979,7 +993,8 @@ __device__ __forceinline__ void s3_sequencer(const Sweep3Args &A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const SweepArgs &a = A.a;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int m = a.m, nb = a.blk_end - a.blk_begin, D = A.D, pstride = a.pstride;
+  static_assert(!SH::fixed || (sizeof(GT) == 2 && !CEN), "the fixed shape: 16-bit Gram entries, columns as stored");
+  const int m = s3_m<SH>(a), nb = a.blk_end - a.blk_begin, D = A.D, pstride = s3_pstride<SH>(a);
   size_t off = 0;
   StageBuf *stage = reinterpret_cast<StageBuf *>(smem + off); off += 3 * sizeof(StageBuf);                        // [block % 3]
   double *spec_s = reinterpret_cast<double *>(smem + off); off += (size_t)3 * 2 * SW_MAXM * sizeof(double);   // [block % 3][spec | gjj][marker]
@@ -1061,7 +1076,7 @@ __device__ __forceinline__ void s3_sequencer(const Sweep3Args &A) {
   // atomics are performed there), and every helper role's request -> consume chain was one phase long (profiles/NOTES.md, round 4).  The counted
   // wait leaves the younger block's two pieces in flight; an incomplete sum (the streamers are D blocks ahead: rare) falls back to polling.
   const uint32_t qraw_la = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) const unsigned char *)qraw_s);
-  const double qweight = A.qsplit ? 4294967296.0 : 16777216.0;   // the second word's weight: digits 4-6 (k_sweep3's streamers) or 3-6 (k_sweep3p's)
+  const double qweight = (SH::fixed || A.qsplit) ? 4294967296.0 : 16777216.0;   // the second word's weight: digits 4-6 (k_sweep3's streamers) or 3-6 (k_sweep3p's)
   auto poll_request = [&](int c) {   // (clamped block: the requests past the end re-read the last block)
     const unsigned char *g = reinterpret_cast<const unsigned char *>(A.qsum + (size_t)(a.blk_begin + min(c, nb - 1)) * SW_MAXM * 2);
     const uint32_t la = qraw_la + (uint32_t)((c % 3) * S3_QRAW_BYTES);
@@ -1612,7 +1627,7 @@ __device__ __forceinline__ void s3_sequencer(const Sweep3Args &A) {
 // blocks of distance 1 and 2, 80 KB per block -- so that those reads are L2 hits (a few hundred cycles) instead of HBM misses
 // (about 2 us on a loaded chip, on the chain's critical path).  Paced by the lists the sequencer publishes; speed only.
 // ------------------------------------------------------------------------------------------------------------------
-template <typename GT, bool ROWS>
+template <typename GT, bool ROWS, typename SH = S3ShapeAny>
 __device__ __forceinline__ void s3_prefetcher(const Sweep3Args &A) {
   const SweepArgs &a = A.a;
   const int tid = threadIdx.x, nb = a.blk_end - a.blk_begin;
@@ -1621,7 +1636,7 @@ __device__ __forceinline__ void s3_prefetcher(const Sweep3Args &A) {
   // took about 2 us a block: the prefetcher fell behind the sequencer it serves, whose staging loads then missed L2 again.)
   constexpr int AHEAD = 16, NPB = 4;
   uint32_t *abortw = a.xflags + (size_t)a.K * SW_FLAG_STRIDE;
-  const size_t gpbytes = (size_t)a.pstride * sizeof(GT);
+  const size_t gpbytes = (size_t)s3_pstride<SH>(a) * sizeof(GT);
   uint32_t sink = 0u;
   const size_t o = (size_t)tid * 128;
   for (int c0 = 0; c0 < nb; c0 += NPB) {
@@ -1639,7 +1654,7 @@ __device__ __forceinline__ void s3_prefetcher(const Sweep3Args &A) {
     // what the staging waves will ask for: the blocks' constants, speculative terms and packed diagonal Gram blocks, one dword per 128-byte line
     // (their loads are HBM misses ~2 us away on the sequencer's CU, and they must be back within one block period)
     uint32_t v[NPB][3];
-    const size_t g12bytes = (size_t)a.m * 2 * a.m * sizeof(GT);
+    const size_t g12bytes = (size_t)s3_m<SH>(a) * 2 * s3_m<SH>(a) * sizeof(GT);
 #pragma unroll
     for (int u = 0; u < NPB; ++u) {
       const int blk = a.blk_begin + min(c0 + u, nb - 1);
@@ -1674,6 +1689,21 @@ __global__ __launch_bounds__(SW_THREADS) void k_sweep3(const Sweep3Args A) {
   else if ((A.dbg & (1 << 22)) && !(A.dbg & (1 << 23)) && A.R3 == 128) s3_streamer_dma<128, 4>(A);
   else if ((A.dbg & (1 << 23)) && A.R3 == 128) s3_streamer_dma<128, 3>(A);
   else s3_streamer(A);   // (a second streamer whose every load was inline asm with hand-counted waits measured no faster and was removed: DESIGN 9.0)
+}
+
+// The fixed-shape instantiation (S3Shape128): the sequencer, the 128-row DMA streamers with four tile buffers and the two prefetchers -- the roles of a
+// chain that has 128-row streamers on an int8 panel with the default block and 16-bit Gram entries, columns as stored.  No other role shares its
+// register allocation, and the block geometry is folded into every role's loop.  plan_sweep selects it where the launch matches (BWGR_FIXED3=0: never);
+// k_sweep3 serves every other launch, and this one too, with the same bits.
+__global__ __launch_bounds__(SW_THREADS) void k_sweep3f(const Sweep3Args A) {
+  if (!(A.a.sc->inc_rate < A.a.gate3)) return;   // this sweep is k_sweep2's
+  if ((int)blockIdx.x == A.pf) { s3_prefetcher<uint16_t, false, S3Shape128>(A); return; }
+  if ((int)blockIdx.x == A.pf2) { s3_prefetcher<uint16_t, true, S3Shape128>(A); return; }
+#ifdef BWGR_EXPERIMENTS
+  if (blockIdx.x == 0 ? (A.dbg & 1024) != 0 : (A.dbg & 2048) != 0) return;   // (tools/ab3_probe.py: the streamers, or the sequencer, alone)
+#endif
+  if (blockIdx.x == 0) s3_sequencer<uint16_t, false, S3Shape128>(A);
+  else s3_streamer_dma<128, 4, S3Shape128>(A);
 }
 
 }  // namespace bwgr

@@ -94,6 +94,10 @@ int bwgr_debug_occupancy_fits(int grid, int per_cu, int cus, int busy, int *need
  * launch over `ncols` columns of `slab_rows`-row slabs takes them only while ncols * slab_rows < 2^32 (else the register-path streamers
  * with 64-bit offsets).  Returns 1 / 0. */
 int bwgr_debug_stream3_dma(int64_t ncols, int64_t slab_rows);
+/* which instantiation of the trajectory engine a selection sweep of the whole panel is launched as, the panel as it stands (clones alive, centred or
+ * not): *which = 0 none (another engine's), 1 k_sweep3 (any shape), 2 k_sweep3f (the fixed shape: 128-marker blocks, 16-bit Gram entries, 128-row DMA
+ * streamers; BWGR_FIXED3=0 when the root panel is made: never).  Both run the same chain bit for bit. */
+int bwgr_debug_sweep3_kernel(const bwgr_panel *P, int *which);
 /* geometry actually chosen: info[0]=n, [1]=p, [2]=ld (padded rows), [3]=block, [4]=nwg, [5]=slab rows,
  * [6]=bytes of X resident, [7]=bytes of Gram resident */
 int bwgr_panel_info(const bwgr_panel *P, int64_t info[8]);

@@ -1,5 +1,7 @@
 """Diagnostic: sweep time of k_sweep3 under the BWGR_DBG3 experiment switches (some of them break the chain on purpose:
-timing only; they are compiled into a library of their own, built here with -DBWGR_EXPERIMENTS) and under BWGR_D3 / BWGR_R3.  Usage: ab3_probe.py "VAR=val,VAR=val" ... (each argument one configuration)."""
+timing only; they are compiled into a library of their own, built here with -DBWGR_EXPERIMENTS) and under BWGR_D3 / BWGR_R3.  Usage: ab3_probe.py "VAR=val,VAR=val" ... (each argument one configuration).
+The experiment library runs the any-shape kernel k_sweep3 unless a configuration says BWGR_FIXED3=1, which takes the fixed-shape k_sweep3f where the
+launch matches it (the same BWGR_DBG3 switches are compiled into both); each line ends with the instantiation the panel's selection sweeps ran as."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -52,7 +54,12 @@ for cfg in sys.argv[1:] or [""]:
             ev = " ev[poll incomplete %d spins %d | folds %d late %d]" % (out[200], out[201], out[203], out[202])
         except Exception as ex:
             ev = " ev[%r]" % (ex,)
-        print("%-40s sweep %8.3f ms  %6.3f us/block  mean_d %s  %s redo %s ve %s" % (cfg, ms, 1e3 * ms / nb, "%.4f" % st["d"].mean() if st else "n/a", P.pipeline(sel), nredo, st["ve"] if st else "n/a") + ev, flush=True)
+        try:
+            wk = C.c_int(-1); _lib.lib().bwgr_debug_sweep3_kernel(P._h, C.byref(wk))
+            kn = {0: "none", 1: "k_sweep3", 2: "k_sweep3f"}.get(wk.value, "?")
+        except Exception as ex:
+            kn = "%r" % (ex,)
+        print("%-40s sweep %8.3f ms  %6.3f us/block  mean_d %s  %s redo %s ve %s" % (cfg, ms, 1e3 * ms / nb, "%.4f" % st["d"].mean() if st else "n/a", P.pipeline(sel), nredo, st["ve"] if st else "n/a") + ev + " " + kn, flush=True)
     finally:
         try:
             ch.close(); P.close()
