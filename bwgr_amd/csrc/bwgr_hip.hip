@@ -697,6 +697,7 @@ __global__ void k_wgr_pre(const double *bR, const double *dR, const double *LR, 
     const float Ve = (float)ws->Ve;
     c.ve = Ve; c.pi = pi; c.C = -0.5f / sqrtf(Ve); c.odds = pi / (1.0f - pi); c.dfp1 = 1.0f;
     c.inc_rate = 1.0f - pi;
+    c.nredo = sc->nredo;   // (the call's count so far: zeroed before the first iteration)
     *sc = c;
   }
 }
@@ -1070,8 +1071,8 @@ static int plan_panel(PanelPlan &pl, bool is_f32, int64_t n, int64_t p, int bloc
   return BWGR_OK;
 }
 
-// k_sweep3's share (selection models on int8 panels, sweep3.hip.h), planned once the data is on the device: from the panel plan, the largest
-// |x| (the slab dots are integer sums sized by it) and whether every near Gram entry fits 16 bits
+// k_sweep3's share (selection models on int8 panels, sweep3.hip.h), planned once the data is on the device: from the panel plan and whether
+// every near Gram entry fits 16 bits (the largest |x| sizes the integer slab-dot sums, which every int8 panel the geometry takes fits: see below)
 struct Panel3Plan {
   bool fits = false;
   int R3 = 0, sub3 = 0, K3 = 0;   // rows of a streamer workgroup, streamers per slab, streamer workgroups
@@ -1079,7 +1080,7 @@ struct Panel3Plan {
   size_t lds3 = 0;
   bool solo3 = true;          // a chain alone on the GPU runs 128-row streamers (BWGR_SOLO3=0: never)
 };
-static Panel3Plan plan_panel3(const PanelPlan &pp, const Switches &sw, int xmax, bool gram16) {
+static Panel3Plan plan_panel3(const PanelPlan &pp, const Switches &sw, bool gram16) {
   Panel3Plan q;
   if (!pp.try3) return q;
   q.R3 = (pp.R % 256 == 0) ? 256 : 128;
@@ -1090,8 +1091,9 @@ static Panel3Plan plan_panel3(const PanelPlan &pp, const Switches &sw, int xmax,
   if (sw.d3 >= 2 && sw.d3 <= S3_MAXD) q.D = sw.d3;
   q.D = (int)std::min<int64_t>(q.D, std::max<int64_t>(2, pp.nblocks));
   q.lds3 = std::max(std::max(s3_streamer_lds(q.R3), std::max(s3_streamer_dma_lds(128), q.R3 == 256 ? s3_streamer_dma_lds(256) : (size_t)0)), s3_seq_lds(q.D, gram16));
-  // the slab dots are summed as integers: sum over all rows of |x| * 128 per digit, four digits of 8 bits, 8 bits of arrival count
-  q.fits = q.K3 <= 255 && q.lds3 <= (size_t)160 * 1024 && pp.ld * std::max(xmax, 1) < (1ll << 23) && (size_t)pp.m * q.R3 <= (size_t)4 * 16 * SW_THREADS;
+  // the slab dots are summed as integers: sum over all rows of |x| * 128 per digit, four digits of 8 bits, 8 bits of arrival count, which
+  // asks for ld * xmax < 2^23.  No condition on xmax: K3 <= 255 streamers of R3 <= 256 rows are ld <= 65 280 rows, and 65 280 * 128 < 2^23
+  q.fits = q.K3 <= 255 && q.lds3 <= (size_t)160 * 1024 && (size_t)pp.m * q.R3 <= (size_t)4 * 16 * SW_THREADS;
   if (q.fits && sw.solo3 >= 0) q.solo3 = sw.solo3 != '0';
   return q;
 }
@@ -1103,7 +1105,7 @@ extern "C" int bwgr_debug_panel_plan(int is_f32, int64_t n, int64_t p, int block
   const Switches sw = read_switches();
   PanelPlan pl;
   CHK(plan_panel(pl, is_f32 != 0, n, p, block, nwg, (PanelKind)kind, sw));
-  const Panel3Plan q = xmax >= 0 ? plan_panel3(pl, sw, xmax, gram16 != 0) : Panel3Plan();
+  const Panel3Plan q = xmax >= 0 ? plan_panel3(pl, sw, gram16 != 0) : Panel3Plan();   // (xmax: only whether the data is assumed known)
   const int64_t v[BWGR_PANEL_PLAN_NOUT] = {pl.m, pl.K, pl.R, pl.ld, pl.nblocks, pl.pstride, pl.nfeed, pl.lag4_ok, (int64_t)pl.lds, (int64_t)pl.lds2, (int64_t)pl.ldsw,
                                            (int64_t)pl.x_bytes, (int64_t)pl.gram_bytes, pl.pipelined, pl.xdist, pl.has16, pl.wdist, pl.try3,
                                            q.fits, q.R3, q.sub3, q.K3, q.D, (int64_t)q.lds3, q.solo3};
@@ -1416,7 +1418,7 @@ static void launch_gram(bwgr_panel *P, void *g, int dist);   // (with the panel'
 static int sweep3_build(bwgr_panel *P) {
   PanelData *D = P->data; const PanelPlan &pl = D->plan;
   D->e3_ready = false;
-  D->plan3 = plan_panel3(pl, D->sw, D->xmax, D->gram16);
+  D->plan3 = plan_panel3(pl, D->sw, D->gram16);
   if (!D->plan3.fits) return BWGR_OK;
   const int m = pl.m; const bool g16 = D->gram16;
   const size_t blk_elems = (size_t)pl.nblocks * m * m;
@@ -1931,11 +1933,18 @@ static void launch_gram(bwgr_panel *P, void *g, int dist) {
   else with_tj<4>(m / 16, [&](auto tj) { hipLaunchKernelGGL(k_gramx_f32<decltype(tj)::value>, grid, block, ldsf, st, Xf, ld, R, p, m, gd, dist); });
 }
 
+// the Gram kernels sum a column pair of an int8 panel over every row in int32 (include/bwgr.h, at bwgr_panel_create)
+static int gram_range(bool is_f32, int64_t rows, int xmax) {
+  const int64_t xm = std::max(xmax, 1);
+  if (!is_f32 && rows * xm * xm >= (1ll << 31)) return fail(BWGR_EINVAL, "panel: n * max|x|^2 = %lld does not fit the int32 Gram", (long long)(rows * xm * xm));
+  return BWGR_OK;
+}
 // The Gram arrays the plan lists, from the resident X, and what they say: whether the 16-bit copies are exact (gram16) and how far the affine
 // engine's byte planes reach (winv_nd).  Runs again wherever a scratch panel's rows or columns change.
 static int panel_build_gram(bwgr_panel *P) {
   PanelData *D = P->data; const PanelPlan &pl = D->plan;
   const int m = pl.m;
+  CHK(gram_range(D->is_f32 != 0, D->n, D->xmax));   // (a main panel's largest |x| is known only now; a scratch panel was checked before it was allocated)
   launch_gram(P, D->gram, 0);
   HIPCHK(hipGetLastError());
   for (int dist = 1; dist <= pl.xdist && dist < pl.nblocks; ++dist) {   // off-diagonal blocks (blk-dist, blk): the cross terms of the lag-2 / 3 / 4 pipelines
@@ -2023,6 +2032,18 @@ static int panel_alloc(bwgr_panel **out, int is_f32, int64_t n, int64_t p, int d
     HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   drop.release();
   *out = P;
+  return BWGR_OK;
+}
+// A scratch panel of P on P's stream: `rows` rows of P's markers (KMUP2, wgr's bagging) or P's columns in another order (bwgr_em).  Either's largest
+// |x| is at most P's, so the scratch panel carries P's: panel_build_gram's int32 bound and the fixed-point scales of its sweeps (launch_prestage) are
+// then those of the main panel, without a pass over the data.
+static int scratch_panel_alloc(bwgr_panel **out, const bwgr_panel *P, int64_t rows, int nwg, PanelKind kind) {
+  const PanelData *D = P->data;
+  *out = nullptr;
+  CHK(gram_range(D->is_f32 != 0, rows, D->xmax));   // refused before anything is allocated or enqueued
+  CHK(panel_alloc(out, D->is_f32, rows, D->p, D->device, D->plan.m, nwg, kind, D->sw));
+  (*out)->stream = P->stream;
+  (*out)->data->xmax = D->xmax;
   return BWGR_OK;
 }
 
@@ -2178,6 +2199,15 @@ static void launch_gather_rows(bwgr_panel *P, bwgr_panel *PB, const int *use_d, 
   } else hipLaunchKernelGGL(k_gather_rows<int8_t>, dim3(4096), dim3(256), 0, P->stream, (const int8_t *)P->data->X, P->data->plan.R, use_d, (int)nbag, (int8_t *)PB->data->X, PB->data->plan.R, PB->data->plan.ld, P->data->p);
 }
 
+// Sweeps that the calling thread's last bwgr_kmup / bwgr_kmup2 / bwgr_wgr / bwgr_wgr_ex call redid on the fp64 residual after they left the
+// fixed-point range (test hook: those entry points have no chain to ask, bwgr_chain_redo_count)
+static thread_local int g_last_redo = 0;
+extern "C" int bwgr_debug_last_redo(int *count) {
+  if (!count) return fail(BWGR_EINVAL, "null pointer");
+  *count = g_last_redo;
+  return BWGR_OK;
+}
+
 // one sweep over panel PS with host-side b, d, xx, L and a device residual e64 (ld doubles, padding zero); KMUP and KMUP2
 static int kmup_sweep(bwgr_panel *PS, float *b, float *d, const float *xx, const float *L, double *e64, float Ve, float pi, float bg,
                       int kmup2, uint64_t seed, uint32_t iter, int rng_mode, const char *who) {
@@ -2204,6 +2234,7 @@ static int kmup_sweep(bwgr_panel *PS, float *b, float *d, const float *xx, const
   HIPCHK(hipMemcpyAsync(d, dd, pb, hipMemcpyDeviceToHost, PS->stream));
   HIPCHK(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, PS->stream));
   HIPCHK(hipStreamSynchronize(PS->stream));
+  g_last_redo = (int)h.nredo;
   if (h.error) return sweep_error(h.error, who);
   return BWGR_OK;
 }
@@ -2239,8 +2270,7 @@ extern "C" int bwgr_kmup2(bwgr_panel *P, const int *Use, int64_t nuse, float *b,
     if (Use[k] < 0 || Use[k] >= P->data->n) return fail(BWGR_EINVAL, "kmup2: Use[%lld] = %d is outside 0..%lld", (long long)k, Use[k], (long long)P->data->n - 1);
   HIPCHK(hipSetDevice(P->data->device));
   bwgr_panel *PB = nullptr;
-  CHK(panel_alloc(&PB, P->data->is_f32, nuse, P->data->p, P->data->device, P->data->plan.m, 0, PANEL_ROWS, P->data->sw));
-  PB->stream = P->stream;
+  CHK(scratch_panel_alloc(&PB, P, nuse, 0, PANEL_ROWS));
   Guard drop([&] { bwgr_panel_destroy(PB); });
   CHK(scratch_alloc(PB));
   DevBufs bufs;
@@ -2886,8 +2916,7 @@ extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int t
   }
   int *use_d = nullptr;
   if (bagging) {
-    CHK(panel_alloc(&PB, P->data->is_f32, nbag, P->data->p, P->data->device, P->data->plan.m, 0, PANEL_ROWS, P->data->sw));
-    PB->stream = P->stream;
+    CHK(scratch_panel_alloc(&PB, P, nbag, 0, PANEL_ROWS));
     CHK(scratch_alloc(PB));
     if (!(use_d = bufs.get<int>((size_t)nbag))) return fail(BWGR_ENOMEM, "wgr: device allocation failed");
   }
@@ -2923,6 +2952,7 @@ extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int t
   hipLaunchKernelGGL(k_wgr_marker_init, dim3(1024), dim3(256), 0, P->stream, bR, dR, VbR, LR, B, D, VB, p, ws);
   if (bagging) hipLaunchKernelGGL(k_scale_d, dim3(256), dim3(256), 0, P->stream, xx64, (int64_t)p, bag);     // xx = crossprod * bag, R/wgr.R:46
   HIPCHK(hipGetLastError());
+  HIPCHK(hipMemsetAsync(sc, 0, sizeof(ChainScalars), P->stream));
   const unsigned pg = (unsigned)std::min<int64_t>(2048, (P->data->p + 255) / 256);
   for (int i = 1; i <= it; ++i) {                                                // R/wgr.R:66
     const uint32_t itx = (uint32_t)(i - 1);
@@ -2970,6 +3000,7 @@ extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int t
   HIPCHK(hipMemcpyAsync(&h, ws, sizeof(h), hipMemcpyDeviceToHost, P->stream));
   HIPCHK(hipMemcpyAsync(&hc, sc, sizeof(hc), hipMemcpyDeviceToHost, P->stream));
   HIPCHK(hipStreamSynchronize(P->stream));
+  g_last_redo = (int)hc.nredo;
   if (hc.error) return sweep_error(hc.error, "wgr");
   const double B0 = h.B0 / mc;
   gemv_launch<double>(P, B, nchunks, cpc, gpart);                                // HAT = B0 + gen0 %*% B, R/wgr.R:152
@@ -3573,8 +3604,7 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
   std::vector<int> order((size_t)p), order_next;   // (copied from asynchronously: declared before the holder, which waits for the stream)
   DevBufs bufs(st);
   if (shuffled) {
-    CHK(panel_alloc(&Q, P->data->is_f32, n, p, P->data->device, P->data->plan.m, P->data->plan.K, PANEL_EM, P->data->sw));
-    Q->stream = st;
+    CHK(scratch_panel_alloc(&Q, P, n, P->data->plan.K, PANEL_EM));
     if (Q->data->plan.K != P->data->plan.K || Q->data->plan.R != P->data->plan.R || Q->data->plan.m != P->data->plan.m || Q->data->plan.pipelined != P->data->plan.pipelined) return fail(BWGR_EINVAL, "em: scratch panel geometry differs");
     CHK(scratch_alloc(Q));
   }
@@ -3843,10 +3873,7 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   HIPCHK(hipSetDevice(P->data->device));
   const int64_t n = P->data->n, p = P->data->p, ld = P->data->plan.ld;
   const int R = P->data->plan.R;
-  {
-    const int64_t xm = std::max(P->data->xmax, 1);
-    if ((int64_t)n * xm * xm >= (1ll << 31)) return fail(BWGR_EINVAL, "mrr: n * max|x|^2 = %lld does not fit the int32 Gram", (long long)(n * xm * xm));
-  }
+  // (the int32 pattern Grams sum over at most n rows: n * max|x|^2 < 2^31 holds for every int8 panel, panel_build_gram)
   // ---- host set-up (:742-816) ----
   std::vector<double> y((size_t)k * ld, 0.0), nt(k, 0.0), mu(k, 0.0);
   std::vector<uint32_t> zt((size_t)ld, 0u);     // bit t: row observed for trait t
@@ -4112,10 +4139,7 @@ extern "C" int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int varian
   HIPCHK(hipSetDevice(P->data->device));
   const int64_t n = P->data->n, p = P->data->p, ld = P->data->plan.ld;
   const int R = P->data->plan.R;
-  {
-    const int64_t xm = std::max(P->data->xmax, 1);
-    if ((int64_t)n * xm * xm >= (1ll << 31)) return fail(BWGR_EINVAL, "uvbeta: n * max|x|^2 = %lld does not fit the int32 Gram", (long long)(n * xm * xm));
-  }
+  // (the int32 pattern Grams sum over at most n rows: n * max|x|^2 < 2^31 holds for every int8 panel, panel_build_gram)
   UvbPlan pl = uvb_plan(n, ld, p, k, P->data->plan.x_bytes, -1, -1, xb_out != nullptr);   // (the pattern counts follow once Y has been read)
   const int64_t groups = pl.groups, kpad = pl.kpad;
   // ---- host set-up (:1413-1423 on the trait's own rows, as submat_f / subvec_f select them, :1495-1503) ----

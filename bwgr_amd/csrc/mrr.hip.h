@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void k_mrr_setup_cols(const int8_t *__restrict
 // Workgroup (block b, pattern group): wave w builds G[b][g], g = 4 * blockIdx.y + w, as k_gram_mfma_i8 does for the plain Gram: lane
 // (m16, grp) feeds the 16 bytes of marker 16a + m16 at rows r0 + 16grp .. +15; the B operand is the same bytes ANDed with the pattern's
 // row mask zm[g][r] (0 or 0xFF), so the product sums over the pattern's observed rows only.  Exact in int32 (n |x|^2 < 2^31, checked
-// by the host).  Out: G[(b * npat + g) * 4096 + i * 64 + j].
+// by the host when the panel is made).  Out: G[(b * npat + g) * 4096 + i * 64 + j].
 __global__ __launch_bounds__(256) void k_mrr_gram(const int8_t *__restrict__ Xs, int R, int64_t p, int64_t ld, const uint8_t *__restrict__ zm,
                                                   int npat, int32_t *__restrict__ G) {
   const int b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, m16 = lane & 15, grp = lane >> 4;

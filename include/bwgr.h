@@ -66,7 +66,12 @@ int bwgr_device_count(int *count);
  * Replaces the per-call SEXP -> Eigen::MatrixXf conversion of X (src/RcppExports.cpp:20, :198 ...).
  * block = markers per exact block (0 = auto, <= 128); nwg = row-slab workgroups (0 = auto).
  * Builds xx, vx, MSx (src/Rcpp20260726ai.cpp:593-598) and the block-diagonal Gram used by the
- * blocked sweep. */
+ * blocked sweep.
+ * The Gram arrays of an int8 panel are exact int32 sums over all rows, so an int8 panel needs
+ * n * max(max|x|, 1)^2 < 2^31 (131 071 rows at |x| = 128, 536 870 911 on 0/1/2 codes); one that does not is
+ * refused with BWGR_EINVAL ("... does not fit the int32 Gram").  The same bound, with the rows of the
+ * subsample and the panel's max|x|, holds for the scratch panels of bwgr_kmup2 and of bwgr_wgr's bagging,
+ * whose row count may exceed n, and refuses those calls the same way. */
 int bwgr_panel_create(bwgr_panel **out, const void *X, int xtype, int memloc, int64_t n, int64_t p, int64_t ldx,
                       int device, int block, int nwg);
 int bwgr_panel_destroy(bwgr_panel *P);
@@ -296,7 +301,7 @@ int bwgr_debug_mrr_plan(int k, int npat, int *linv_lds, int *ngl, int64_t *solve
  * elsewhere, for every variant (XFUVBETA has no such test and would return NaN there).  A panel switched to implicit centring gives
  * bit-identical results (the fit reads the raw genotypes and centres per trait).
  * BWGR_EINVAL: an fp32 panel, an unknown variant, maxit < 0, k < 1, a trait with exactly one observed row (the reference divides by n - 1;
- * the message names the trait), n * max|x|^2 >= 2^31 (the int32 block Gram).
+ * the message names the trait).  (The int32 pattern Grams are within bwgr_panel_create's bound n * max|x|^2 < 2^31.)
  * Degenerate traits are not refused and follow the reference's arithmetic: a trait that is constant on its observed rows has vy = 0, hence
  * ve = vb = 0 and lambda = 0 / 0, and its column comes back NaN with its = 1 (the NaN convergence value stops it, as in the reference); a trait
  * whose markers are all monomorphic on its rows has TrXSX = 0, hence vb = inf and lambda = 0: every marker takes the XX_j = 0 path and b stays
@@ -428,6 +433,9 @@ int bwgr_debug_variates(int device, uint64_t seed, int kind, double nu, uint32_t
  * for it reaches its wall-clock bound (4 s), the shared abort word ends the launch and the call reports BWGR_ETIMEOUT.  The
  * panel stays usable: switch the hook off and launch again. */
 int bwgr_debug_withhold(bwgr_panel *P, int on);
+/* the sweeps that the calling thread's last bwgr_kmup / bwgr_kmup2 / bwgr_wgr / bwgr_wgr_ex call redid on the fp64 residual because they left
+ * the fixed-point range of their engine: what bwgr_chain_redo_count is for a chain, for the entry points that have none. */
+int bwgr_debug_last_redo(int *count);
 
 #ifdef __cplusplus
 }

@@ -379,7 +379,8 @@ def test_full_range_int8_panel():
 
 def test_int32_gram_bound():
     """Columns of +-127 and a fully observed trait: the diagonal of that trait's pattern Gram is n 127^2 in every block.  At the largest
-    n the host accepts (n max|x|^2 < 2^31) the int32 Gram is exact and the fit matches; one more row is refused."""
+    n the host accepts (n max|x|^2 < 2^31) the int32 Gram is exact and the fit matches; one more row is refused -- where the panel's own Gram
+    arrays are built, so before mrr sees the panel."""
     import bwgr_amd
     n = ((1 << 31) - 1) // (127 * 127)
     assert n * 127 * 127 < (1 << 31) <= (n + 1) * 127 * 127
@@ -396,12 +397,8 @@ def test_int32_gram_bound():
     o = MR.mrr(Y, X[:n], maxit=2, tol=0)
     _check(g, o)
     Y1 = _traits(X, 2, 0.1, seed=103)
-    P = bwgr_amd.Panel(X, block=16)
-    try:
-        with pytest.raises(bwgr_amd.BwgrError) as ei:
-            bwgr_amd.mrr(Y1, P, maxit=2, tol=0)
-    finally:
-        P.close()
+    with pytest.raises(bwgr_amd.BwgrError) as ei:
+        bwgr_amd.mrr(Y1, X, maxit=2, tol=0, block=16)
     assert ei.value.code == 1 and "int32 Gram" in str(ei.value)
 
 

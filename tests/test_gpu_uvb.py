@@ -400,16 +400,12 @@ def test_int32_gram_bound():
         P.close()
     _check(g, UR.uvbeta(Y, X[:n], "D", maxit=2, tol=0))
     Y1 = _traits(X, 2, 0.1, seed=103)
-    P = bwgr_amd.Panel(X, block=16)
-    try:
-        with pytest.raises(bwgr_amd.BwgrError) as ei:
-            bwgr_amd.uvbeta(Y1, P, "D", maxit=2, tol=0)
-        assert ei.value.code == 1 and "int32 Gram" in str(ei.value)
-        X2 = _tpod()
-        Y2 = _traits(X2, 2, 0.1, seed=104)
-        assert bwgr_amd.uvbeta(Y2, X2, "D", maxit=1)["its"].tolist() == [1, 1]   # the device is left usable
-    finally:
-        P.close()
+    with pytest.raises(bwgr_amd.BwgrError) as ei:      # (refused where the panel's own Gram arrays are built: before uvbeta sees the panel)
+        bwgr_amd.uvbeta(Y1, X, "D", maxit=2, tol=0, block=16)
+    assert ei.value.code == 1 and "int32 Gram" in str(ei.value)
+    X2 = _tpod()
+    Y2 = _traits(X2, 2, 0.1, seed=104)
+    assert bwgr_amd.uvbeta(Y2, X2, "D", maxit=1)["its"].tolist() == [1, 1]   # the device is left usable
 
 
 # ---- 14 ----
