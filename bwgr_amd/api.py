@@ -941,6 +941,13 @@ def debug_variates(seed, kind, marker0, count, it=0, purpose=0, nu=0.0, device=0
     return out
 
 
+def debug_live():
+    """bwgr_debug_live: the (device arrays, streams, events) that the library's handles and running calls own in this process."""
+    out = (C.c_int64 * 3)()
+    check(_lib.lib().bwgr_debug_live(out))
+    return tuple(out)
+
+
 # ---- multi-trait ridge regression: MRR3 / MRR3F, mrr / mrr_float (bwgr_mrr, include/bwgr.h) ----
 _MRR_OPTS = ["maxit", "tol", "TH", "NLfactor", "InnerGS", "NoInv", "HCS", "XFA", "ACS", "NumXFA", "R2", "gc0", "df0", "updateMu",
              "weight_prior_h2", "weight_prior_gc", "PenCor", "MinCor", "uncorH2below", "roundGCupFrom", "roundGCupTo", "roundGCdownFrom",

@@ -11,9 +11,12 @@
 #include <chrono>
 #include <algorithm>
 #include <mutex>
+#include <atomic>
+#include <memory>
 #include <utility>
 #include <type_traits>
 #include "../../include/bwgr.h"
+#include "devbufs.h"
 #include "rng.hip.h"
 #include "sweep.hip.h"
 #include "sweep3.hip.h"
@@ -1113,12 +1116,70 @@ extern "C" int bwgr_debug_panel_plan(int is_f32, int64_t n, int64_t p, int block
   return BWGR_OK;
 }
 
+// The HIP backend of the holder (devbufs.h), and the only place of this library that allocates or frees device memory.  Its counts are what
+// bwgr_debug_live reports: the arrays, streams and events that holders own in this process.
+namespace {
+struct HipBackend {
+  using stream_t = hipStream_t;
+  using event_t = hipEvent_t;
+  static inline std::atomic<int64_t> live[3];
+  static inline thread_local hipError_t last = hipSuccess;   // what the calling thread's last alloc() got: the text of its failure
+  static void *alloc(size_t bytes) {
+    void *q = nullptr;
+    if ((last = hipMalloc(&q, bytes)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    ++live[0];
+    return q;
+  }
+  static void free(void *q) { (void)hipFree(q); --live[0]; }
+  static bool stream_create(hipStream_t *s, unsigned flags, int priority) {
+    if ((priority ? hipStreamCreateWithPriority(s, flags, priority) : hipStreamCreateWithFlags(s, flags)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    ++live[1];
+    return true;
+  }
+  static void stream_sync(hipStream_t s) { (void)hipStreamSynchronize(s); }
+  static void stream_destroy(hipStream_t s) { (void)hipStreamDestroy(s); --live[1]; }
+  static bool event_create(hipEvent_t *e, unsigned flags) {
+    if (hipEventCreateWithFlags(e, flags) != hipSuccess) { (void)hipGetLastError(); return false; }
+    ++live[2];
+    return true;
+  }
+  static void event_destroy(hipEvent_t e) { (void)hipEventDestroy(e); --live[2]; }
+};
+// The device arrays, streams and events of one call (or of one block of it), or of one handle.  get() returns nullptr where the allocation
+// fails: the caller reports BWGR_ENOMEM, "<entry>: device allocation failed" (own_array below does).
+using DevBufs = DevHolder<HipBackend>;
+// Runs f when the scope ends, unless release()d: destroys the object a function is making on its error returns, a call's scratch panels and
+// chains on every return, and gives a borrowed stream back.  Declared before the call's DevBufs, so that it runs after the buffers are freed.
+template <typename F> struct Guard {
+  F f;
+  bool armed = true;
+  explicit Guard(F f_) : f(f_) {}
+  Guard(const Guard &) = delete;
+  ~Guard() { if (armed) f(); }
+  void release() { armed = false; }
+};
+}  // namespace
+extern "C" int bwgr_debug_live(int64_t out[3]) {
+  if (!out) return fail(BWGR_EINVAL, "debug_live: null pointer");
+  for (int i = 0; i < 3; ++i) out[i] = HipBackend::live[i].load();
+  return BWGR_OK;
+}
+// a handle's allocation failed: BWGR_ENOMEM, with what the runtime said
+static int no_memory(const char *who) { return fail(BWGR_ENOMEM, "%s: device allocation failed (%s)", who, hipGetErrorString(HipBackend::last)); }
+// ptr = count elements (bytes, of a void pointer) that `own` owns from now on
+template <typename T> static int own_array(DevBufs &own, T *&ptr, size_t count, const char *who) {
+  return (ptr = own.get<std::conditional_t<std::is_void<T>::value, unsigned char, T>>(count)) ? BWGR_OK : no_memory(who);
+}
+
 // ------------------------------------------------------------------------------------------------
 // A resident panel is its data (PanelData) and the handles on it (bwgr_panel).  The root handle is made with the data -- by
 // bwgr_panel_create, or as a scratch panel of KMUP2, wgr or bwgr_em -- and frees it; a clone (bwgr_panel_clone) is another handle on the
 // same data.  Every handle owns its streams and the scratch its sweeps write.  The data does not change while a clone is alive: it is
 // built with the root, and bwgr_panel_set_centred refuses on a clone and while any chain is alive.
+// Each of PanelData, bwgr_panel, bwgr_chain and bwgr_group owns its device arrays, streams and long-lived events through a holder (`own`);
+// the typed pointers below are aliases, and deleting the struct releases them.  What is allocated lazily as a group is one take().
 struct PanelData {
+  DevBufs own;                // the genotypes, the Gram family, the statistics, csum / xxc and the pair streams
   int device = 0, is_f32 = 0;
   int64_t n = 0, p = 0;
   PanelPlan plan;             // made with the data (plan_panel)
@@ -1134,8 +1195,8 @@ struct PanelData {
   void *gx[S2W_NEARD + 1] = {};   // gx[d], d = 1 .. plan.xdist: cross Gram blocks X_{b-d}' X_b, int32 (fp64 for float panels)
   uint16_t *gramp16 = nullptr, *gramx16 = nullptr;   // 16-bit copies of gramp and gx[1] (plan.has16)
   int *gram16_bad = nullptr;
-  // g3x[d-1]: cross Gram blocks of distance d in the element type k_sweep3 reads: the panel's array of that distance and type, or one of its own
-  struct { void *a; bool own; } g3x[S3_MAXD] = {};
+  // g3x[d-1]: cross Gram blocks of distance d in the element type k_sweep3 reads: an alias of the panel's array of that distance and type, or an array of its own
+  void *g3x[S3_MAXD] = {};
   unsigned char *gx12 = nullptr;   // 16-bit panels: an included marker's distance-1 and distance-2 rows side by side (k_near_rows)
   unsigned char *gxt[S2W_MAXDIST] = {};   // the affine models' cross Gram blocks as the sequencer's MFMA operand (k_gx_planes, sweep2w.hip.h)
   float *xx = nullptr, *vx = nullptr, *msx_dev = nullptr;
@@ -1153,9 +1214,10 @@ struct PanelData {
 struct bwgr_panel {
   PanelData *data = nullptr;
   bool is_root = false;       // made with the data, which it frees; false: a clone
-  hipStream_t stream = nullptr, own_stream = nullptr;
+  DevBufs own;                // the sweep scratch, the exchange words, the lazy groups, a clone's stream, the draws stream and events
+  hipStream_t stream = nullptr;
   hipStream_t pre_pair_stream = nullptr; bool pre_pair_set = false;   // the stream this handle ran on before a pair run moved it (restored by its next sweep alone)
-  // the sweep scratch (scratch_alloc / scratch_free)
+  // the sweep scratch (scratch_alloc, and what the first sweep that needs it takes)
   double *xspec2 = nullptr, *xspec3 = nullptr;   // [nblocks][SW_MAXM]: speculative cross terms of the lag-3 / lag-4 pipelines (k_spec)
   PreStage ps = {};
   const void *ps_owner = nullptr; int ps_iter = -1;   // whose sweep constants the scratch holds (a chain pre-stages a whole iteration once)
@@ -1182,6 +1244,7 @@ struct bwgr_panel {
 
 struct bwgr_chain {
   bwgr_panel *P = nullptr;
+  DevBufs own;                        // the state arrays (e: unless the caller gave one)
   int model = 0, iit = 0, ibi = 0, done = 0, rng_mode = 0;
   float itf = 0, bif = 0, pi = 0, df = 0, R2 = 0, Phi = 0;
   uint64_t seed = 0;
@@ -1191,7 +1254,6 @@ struct bwgr_chain {
   ChainScalars *sc = nullptr;
   int64_t marker0 = 0, p_total = 0;   // sharding: global id of local marker 0, markers over all ranks
   float MSx_eff = 0;                  // MSx over all ranks
-  bool e_owned = true;
   double *e0 = nullptr;               // residual at the start of the current exchange round (sharded stepping)
   int flags_extra = 0;                // two-effect BayesB2: SWF_ALT_B2 (the likelihood comparison uses the drawn alternative)
   std::vector<hipEvent_t> ev;  // pairs around each sweep launch since the last query
@@ -1212,41 +1274,6 @@ static hipError_t d2h(hipStream_t st, void *dst, const void *src, size_t bytes) 
 static Rng make_rng(uint64_t seed, int mode) {
   Rng g; g.k0 = (uint32_t)seed; g.k1 = (uint32_t)(seed >> 32); g.degenerate = (mode == BWGR_RNG_DEGENERATE); return g;
 }
-
-// The temporary device buffers of one call (or of one block of it), freed when the scope ends, on every path out of it.  Given a stream, it
-// waits for that stream first, so that no kernel or asynchronous copy still uses a buffer or a host local of the frame that goes away (a
-// host vector that is copied from asynchronously is declared before the holder, and so outlives that wait).
-// get() returns nullptr where the allocation fails: the caller reports BWGR_ENOMEM, "<entry>: device allocation failed".
-namespace {
-struct DevBufs {
-  std::vector<void *> v;
-  hipStream_t stream = nullptr;
-  bool sync = false;
-  DevBufs() = default;
-  explicit DevBufs(hipStream_t st) : stream(st), sync(true) {}
-  DevBufs(const DevBufs &) = delete;
-  ~DevBufs() {
-    if (sync) (void)hipStreamSynchronize(stream);
-    for (void *q : v) hipFree(q);
-  }
-  template <typename T> T *get(size_t count) {
-    void *q = nullptr;
-    if (hipMalloc(&q, sizeof(T) * (count ? count : 1)) != hipSuccess) return nullptr;
-    v.push_back(q);
-    return reinterpret_cast<T *>(q);
-  }
-};
-// Runs f when the scope ends, unless release()d: destroys the object a function is making on its error returns, a call's scratch panels and
-// chains on every return, and gives a borrowed stream back.  Declared before the call's DevBufs, so that it runs after the buffers are freed.
-template <typename F> struct Guard {
-  F f;
-  bool armed = true;
-  explicit Guard(F f_) : f(f_) {}
-  Guard(const Guard &) = delete;
-  ~Guard() { if (armed) f(); }
-  void release() { armed = false; }
-};
-}  // namespace
 
 // sum of n floats (fp64 partial sums in a fixed order, rounded to float once) into *sum_dev and from there into *sum; part: 256 doubles
 static int sum_floats(hipStream_t st, const float *v, int64_t n, double *part, float *sum_dev, float *sum) {
@@ -1275,18 +1302,17 @@ static int require_device(int device) {
 }
 
 // the words the workgroups poll (flags, delta granules, q words and the feeders' sums) live in one allocation
-static hipError_t alloc_exchange(bwgr_panel *P) {
+static int alloc_exchange(bwgr_panel *P) {
   const size_t K = (size_t)P->data->plan.K;
   const size_t fb = (sizeof(uint32_t) * (K + 1) * SW_FLAG_STRIDE + 255) & ~(size_t)255;
   const size_t gb = (sizeof(unsigned long long) * S2_NSLOT * SW_MAXM + 255) & ~(size_t)255;
   const size_t qb = sizeof(double) * S2_NSLOT * (K + 1) * SW_MAXM;
   P->xchg_bytes = fb + gb + qb;
-  hipError_t e = hipMalloc(&P->xchg, P->xchg_bytes);
-  if (e != hipSuccess) return e;
+  CHK(own_array(P->own, P->xchg, P->xchg_bytes, "panel scratch"));
   P->xflags = reinterpret_cast<uint32_t *>(P->xchg);
   P->dgran = reinterpret_cast<unsigned long long *>(P->xchg + fb);
   P->qpart = reinterpret_cast<double *>(P->xchg + fb + gb);
-  return hipSuccess;
+  return BWGR_OK;
 }
 // polled words are zeroed before every launch (epochs count within a launch)
 // ---- the sweep plan -----------------------------------------------------------------------------------------------------------
@@ -1423,15 +1449,16 @@ static int sweep3_build(bwgr_panel *P) {
   const int m = pl.m; const bool g16 = D->gram16;
   const size_t blk_elems = (size_t)pl.nblocks * m * m;
   int bad = 0;
+  std::vector<void *> far;   // the arrays made here
   {   // the far blocks; tmp, a whole Gram array, goes once they are built and before the 16-bit verdict is acted on
     DevBufs bufs;
     int32_t *tmp = nullptr;
     for (int d = 1; d < D->plan3.D && d < pl.nblocks; ++d) {
       void *have32 = d <= pl.xdist ? D->gx[d] : nullptr, *have = g16 ? (d == 1 ? (void *)D->gramx16 : nullptr) : have32;
-      if (have) { D->g3x[d - 1] = {have, false}; continue; }
+      if (have) { D->g3x[d - 1] = have; continue; }
       void *arr = nullptr;
-      HIPCHK(hipMalloc(&arr, blk_elems * (g16 ? 2 : 4)));
-      D->g3x[d - 1] = {arr, true};
+      CHK(own_array(D->own, arr, blk_elems * (g16 ? 2 : 4), "panel_create"));
+      D->g3x[d - 1] = arr; far.push_back(arr);
       if (g16) {
         if (!have32) {
           if (!tmp && !(tmp = bufs.get<int32_t>(blk_elems))) return fail(BWGR_ENOMEM, "panel_create: device allocation failed");
@@ -1446,12 +1473,13 @@ static int sweep3_build(bwgr_panel *P) {
     HIPCHK(hipStreamSynchronize(P->stream));
   }
   if (bad) {   // an entry of a far block left the 16-bit range although the near blocks fit: rare; leave the panel to k_sweep2
-    for (auto &g : D->g3x) { if (g.own) hipFree(g.a); g = {nullptr, false}; }
+    for (void *q : far) D->own.drop(q);
+    for (void *&g : D->g3x) g = nullptr;
     return BWGR_OK;
   }
   if (g16) {   // 16-bit panels: an included marker's distance-1 / 2 rows in one piece
-    HIPCHK(hipMalloc(&D->gx12, (size_t)pl.nblocks * m * 2 * m * 2));
-    hipLaunchKernelGGL(k_near_rows, dim3(4096), dim3(256), 0, P->stream, (const uint16_t *)D->g3x[0].a, (const uint16_t *)(D->plan3.D >= 3 ? D->g3x[1].a : nullptr), (uint16_t *)D->gx12, m, (int64_t)pl.nblocks);
+    CHK(own_array(D->own, D->gx12, (size_t)pl.nblocks * m * 2 * m * 2, "panel_create"));
+    hipLaunchKernelGGL(k_near_rows, dim3(4096), dim3(256), 0, P->stream, (const uint16_t *)D->g3x[0], (const uint16_t *)(D->plan3.D >= 3 ? D->g3x[1] : nullptr), (uint16_t *)D->gx12, m, (int64_t)pl.nblocks);
     HIPCHK(hipGetLastError());
   }
   for (const void *f : {reinterpret_cast<const void *>(k_sweep3<uint16_t, false>), reinterpret_cast<const void *>(k_sweep3<int32_t, false>), reinterpret_cast<const void *>(k_sweep3<uint16_t, true>),
@@ -1467,9 +1495,9 @@ extern "C" int bwgr_debug_stream3_dma(int64_t ncols, int64_t R) { return stream3
 // The affine sweeps of an int8 panel with 16-bit Gram staging run k_sweep2w: the block solve as a product with the inverse
 // k_affine_inv forms before the sweep (sweep2w.hip.h).
 static int winv_alloc(bwgr_panel *P) {
-  if (P->winv) return BWGR_OK;
-  HIPCHK(hipMalloc(&P->winv, sizeof(double) * (size_t)S2W_WDOUBLES * (size_t)P->data->plan.nblocks));
-  HIPCHK(hipMalloc(&P->qsumw, sizeof(unsigned long long) * 4 * 2 * SW_MAXM * (size_t)P->data->plan.nblocks));   // (up to four copies)
+  const size_t nb = (size_t)P->data->plan.nblocks;
+  if (!P->winv && !P->own.take({{&P->winv, sizeof(double) * S2W_WDOUBLES * nb}, {&P->qsumw, sizeof(unsigned long long) * 4 * 2 * SW_MAXM * nb}}))   // (up to four copies)
+    return no_memory("affine sweep");
   return BWGR_OK;
 }
 
@@ -1528,13 +1556,9 @@ static void draws_ahead(bwgr_panel *P, const SweepArgs &a, const SweepPlan &pl, 
   if (!P->draws) {
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);   // (lo: the numerically largest = the lowest priority)
-    if (hipMalloc(&P->draws, sizeof(double) * 5 * (size_t)P->data->p) != hipSuccess || hipStreamCreateWithPriority(&P->draws_stream, hipStreamNonBlocking, lo) != hipSuccess ||
-        hipEventCreateWithFlags(&P->draws_ready, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&P->draws_free, hipEventDisableTiming) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k_draws), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) {
-      (void)hipGetLastError();
-      hipFree(P->draws); P->draws = nullptr;
-      return;
-    }
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_draws), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) { (void)hipGetLastError(); return; }
+    if (!P->own.take({{&P->draws, sizeof(double) * 5 * (size_t)P->data->p}, DevBufs::want_stream(&P->draws_stream, hipStreamNonBlocking, lo),
+                      DevBufs::want_event(&P->draws_ready, hipEventDisableTiming), DevBufs::want_event(&P->draws_free, hipEventDisableTiming)})) return;
     (void)hipEventRecord(P->draws_free, P->stream);
   }
   const int j0 = a.blk_begin * a.m, j1 = (int)std::min<int64_t>(P->data->p, (int64_t)a.blk_end * a.m);
@@ -1679,7 +1703,7 @@ static SweepPlan plan_sweep(const bwgr_panel *P, const SweepArgs &a, bool redo) 
 // what one launch of k_sweep3 / k_sweep3p needs beside the sweep's own arguments; zeroes the launch's slab-dot sums, takes a new epoch
 static void sweep3_args(bwgr_panel *P, const SweepArgs &a, const SweepPlan &pl, Sweep3Args &A) {
   memset(&A, 0, sizeof(A)); A.a = a;
-  for (int d = 0; d < S3_MAXD; ++d) A.gx[d] = P->data->g3x[d].a;
+  for (int d = 0; d < S3_MAXD; ++d) A.gx[d] = P->data->g3x[d];
   A.gp = P->data->gram16 ? (const void *)P->data->gramp16 : P->data->gramp;
   A.D = P->data->plan3.D; A.K3 = pl.K3; A.R3 = pl.R3; A.sub = pl.sub; A.g16 = P->data->gram16 ? 1 : 0;
   A.qsum = P->qsum3; A.lists = P->lists3;
@@ -1742,8 +1766,7 @@ static void launch_sweep_engine(bwgr_panel *P, const SweepArgs &a_in, const Swee
 static void launch_sweep_kernel(bwgr_panel *P, const SweepArgs &a, const SweepPlan &pl) {
   const size_t p = (size_t)P->data->p;
   bool guarded = pl.guarded;
-  if (guarded && !P->snap_e && (hipMalloc(&P->snap_e, sizeof(double) * (size_t)P->data->plan.ld) != hipSuccess || hipMalloc(&P->snap_b, sizeof(float) * p) != hipSuccess ||
-                                hipMalloc(&P->snap_d, sizeof(float) * p) != hipSuccess || hipMalloc(&P->snap_vb, sizeof(float) * p) != hipSuccess)) { (void)hipGetLastError(); guarded = false; }
+  if (guarded && !P->snap_e && !P->own.take({{&P->snap_e, sizeof(double) * (size_t)P->data->plan.ld}, {&P->snap_b, sizeof(float) * p}, {&P->snap_d, sizeof(float) * p}, {&P->snap_vb, sizeof(float) * p}})) guarded = false;
   SnapArgs sn;
   sn.e = a.e; sn.se = P->snap_e; sn.b = a.b; sn.d = a.d; sn.vb = (a.flags & SWF_VB_VEC) ? a.vb : nullptr; sn.sb = P->snap_b; sn.sd = P->snap_d; sn.svb = P->snap_vb;
   sn.ld = P->data->plan.ld; sn.j0 = a.blk_begin * a.m; sn.j1 = (int)std::min<int64_t>(P->data->p, (int64_t)a.blk_end * a.m); sn.sc = a.sc;
@@ -1831,37 +1854,25 @@ static int upload(bwgr_panel *P, const void *X, int memloc, int64_t ldx) {
 
 // A handle's sweep scratch, made once its data is built (the root's by whoever makes the data, a clone's by bwgr_panel_clone): the
 // speculative cross terms of the distances whose Gram blocks the data has, the pre-staged constants, the exchange words, and k_sweep3's
-// sums and lists where the data has k_sweep3.  The rest of the scratch comes with the first sweep that needs it; scratch_free frees all.
+// sums and lists where the data has k_sweep3.  The rest of the scratch comes with the first sweep that needs it; the handle's holder owns all of it.
 static int scratch_alloc(bwgr_panel *P) {
   const PanelData *D = P->data;
   const size_t nb = (size_t)D->plan.nblocks;
-  if (D->plan.xdist >= 2) HIPCHK(hipMalloc(&P->xspec2, sizeof(double) * nb * SW_MAXM));
-  if (D->plan.xdist >= 3) HIPCHK(hipMalloc(&P->xspec3, sizeof(double) * nb * SW_MAXM));
-  HIPCHK(hipMalloc(&P->ps.spec, sizeof(SpecBuf) * nb));
-  if (D->plan.pipelined) HIPCHK(hipMalloc(&P->ps.quick, sizeof(QuickBuf) * nb));
-  HIPCHK(hipMalloc(&P->ps.blocks, sizeof(StageBuf) * nb));
-  HIPCHK(hipMalloc(&P->xpart, sizeof(double) * 2 * (size_t)D->plan.K * SW_MAXM));
-  HIPCHK(alloc_exchange(P));
+  const char *who = "panel scratch";
+  if (D->plan.xdist >= 2) CHK(own_array(P->own, P->xspec2, nb * SW_MAXM, who));
+  if (D->plan.xdist >= 3) CHK(own_array(P->own, P->xspec3, nb * SW_MAXM, who));
+  if (D->plan.pipelined) CHK(own_array(P->own, P->ps.quick, nb, who));
+  if (!P->own.take({{&P->ps.spec, sizeof(SpecBuf) * nb}, {&P->ps.blocks, sizeof(StageBuf) * nb}, {&P->xpart, sizeof(double) * 2 * (size_t)D->plan.K * SW_MAXM}})) return no_memory(who);
+  CHK(alloc_exchange(P));
 #if defined(BWGR_STAMPS) || defined(BWGR_EXPERIMENTS)
-  HIPCHK(hipMalloc(&P->stamps, sizeof(unsigned long long) * 256));
+  CHK(own_array(P->own, P->stamps, 256, who));
   HIPCHK(hipMemset(P->stamps, 0, sizeof(unsigned long long) * 256));
 #endif
   if (D->e3_ready) {
-    HIPCHK(hipMalloc(&P->qsum3, sizeof(unsigned long long) * 2 * SW_MAXM * nb));
-    HIPCHK(hipMalloc(&P->lists3, sizeof(unsigned long long) * S3_LSTRIDE * nb));
+    if (!P->own.take({{&P->qsum3, sizeof(unsigned long long) * 2 * SW_MAXM * nb}, {&P->lists3, sizeof(unsigned long long) * S3_LSTRIDE * nb}})) return no_memory(who);
     HIPCHK(hipMemsetAsync(P->lists3, 0, sizeof(unsigned long long) * S3_LSTRIDE * nb, P->stream));
   }
   return BWGR_OK;
-}
-static void scratch_free(bwgr_panel *P) {
-  hipFree(P->xspec2); hipFree(P->xspec3); hipFree(P->ps.spec); hipFree(P->ps.blocks); hipFree(P->ps.quick); hipFree(P->xpart); hipFree(P->xchg); hipFree(P->stamps);
-  hipFree(P->qsum3); hipFree(P->lists3); hipFree(P->winv); hipFree(P->qsumw); hipFree(P->cpre);
-  hipFree(P->snap_e); hipFree(P->snap_b); hipFree(P->snap_d); hipFree(P->snap_vb);
-  guard_forget(P);
-  if (P->draws_stream) { (void)hipStreamSynchronize(P->draws_stream); hipStreamDestroy(P->draws_stream); }
-  if (P->draws_ready) hipEventDestroy(P->draws_ready);
-  if (P->draws_free) hipEventDestroy(P->draws_free);
-  hipFree(P->draws);
 }
 
 extern "C" int bwgr_panel_destroy(bwgr_panel *P) {
@@ -1870,20 +1881,11 @@ extern "C" int bwgr_panel_destroy(bwgr_panel *P) {
   if (P->is_root && D->nclones > 0) return fail(BWGR_EINVAL, "panel_destroy: %d clone(s) of this panel are still alive", D->nclones);
   if (P->nchains > 0) return fail(BWGR_EINVAL, "panel_destroy: %d chain(s) on this panel are still alive (destroy them first)", P->nchains);
   (void)hipSetDevice(D->device);
-  scratch_free(P);
-  if (P->own_stream) hipStreamDestroy(P->own_stream);
-  if (P->is_root) {
-    for (auto &g : D->g3x) if (g.own) hipFree(g.a);
-    for (void *g : D->gx) hipFree(g);
-    for (int d = 0; d < S2W_MAXDIST; ++d) hipFree(D->gxt[d]);
-    hipFree(D->X); hipFree(D->gram); hipFree(D->gramp16); hipFree(D->gramx16); hipFree(D->gram16_bad); hipFree(D->gramp);
-    hipFree(D->gx12); hipFree(D->xx); hipFree(D->vx); hipFree(D->msx_dev); hipFree(D->xmax_dev); hipFree(D->csum); hipFree(D->xxc);
-    for (hipStream_t q : D->pair_streams) hipStreamDestroy(q);
-    delete D;
-  } else {
-    D->nclones--;
-  }
-  delete P;
+  guard_forget(P);
+  const bool root = P->is_root;
+  delete P;   // the handle's scratch and streams, then the data's arrays and the pair streams
+  if (root) delete D;
+  else D->nclones--;
   return BWGR_OK;
 }
 
@@ -1901,7 +1903,7 @@ static int panel_measure(bwgr_panel *P) {
     CHK(sum_floats(P->stream, D->vx, (int64_t)p, part, D->msx_dev, &D->MSx));
   }
   if (!D->is_f32) {
-    if (!D->xmax_dev) HIPCHK(hipMalloc(&D->xmax_dev, sizeof(int)));
+    if (!D->xmax_dev) CHK(own_array(D->own, D->xmax_dev, 1, "panel_create"));
     HIPCHK(hipMemsetAsync(D->xmax_dev, 0, sizeof(int), P->stream));
     hipLaunchKernelGGL(k_absmax_i8, dim3(2048), dim3(256), 0, P->stream, (const int8_t *)D->X, D->plan.x_bytes, D->xmax_dev);
     HIPCHK(hipGetLastError());
@@ -1979,7 +1981,7 @@ static int panel_build_gram(bwgr_panel *P) {
         launch_gram(P, tmpx, dist);
       }
       const int32_t *src = dist > S2W_NEARD ? tmpx : (const int32_t *)D->gx[dist];
-      if (!D->gxt[dist - 1]) HIPCHK(hipMalloc(&D->gxt[dist - 1], (size_t)pl.nblocks * S2W_PBYTES));
+      if (!D->gxt[dist - 1]) CHK(own_array(D->own, D->gxt[dist - 1], (size_t)pl.nblocks * S2W_PBYTES, "panel_create"));
       hipLaunchKernelGGL(k_gx_planes, dim3(4096), dim3(256), 0, P->stream, src, D->gxt[dist - 1], m, (int64_t)pl.nblocks, dist, D->gram16_bad);
       HIPCHK(hipGetLastError());
       nd = dist;
@@ -2013,18 +2015,10 @@ static int panel_alloc(bwgr_panel **out, int is_f32, int64_t n, int64_t p, int d
   Guard drop([&] { bwgr_panel_destroy(P); });   // until the panel is handed over
   D->device = device; D->n = n; D->p = p; D->is_f32 = is_f32; D->sw = sw; D->plan = pl;
   const size_t packed = (size_t)pl.nblocks * std::max(pl.pstride, 8);
-  HIPCHK(hipMalloc(&D->X, pl.x_bytes));
-  HIPCHK(hipMalloc(&D->gram, pl.gram_bytes));
-  for (int d = 1; d <= pl.xdist; ++d) HIPCHK(hipMalloc(&D->gx[d], pl.gram_bytes));
-  HIPCHK(hipMalloc(&D->gramp, packed * (is_f32 ? 8 : 4)));
-  if (pl.has16) {
-    HIPCHK(hipMalloc(&D->gramp16, packed * 2));
-    HIPCHK(hipMalloc(&D->gramx16, (size_t)pl.nblocks * pl.m * pl.m * 2));
-    HIPCHK(hipMalloc(&D->gram16_bad, sizeof(int)));
-  }
-  HIPCHK(hipMalloc(&D->xx, sizeof(float) * p));
-  HIPCHK(hipMalloc(&D->vx, sizeof(float) * p));
-  HIPCHK(hipMalloc(&D->msx_dev, sizeof(float)));
+  if (!D->own.take({{&D->X, pl.x_bytes}, {&D->gram, pl.gram_bytes}, {&D->gramp, packed * (is_f32 ? 8 : 4)}, {&D->xx, sizeof(float) * p}, {&D->vx, sizeof(float) * p}, {&D->msx_dev, sizeof(float)}}))
+    return no_memory("panel_create");
+  for (int d = 1; d <= pl.xdist; ++d) CHK(own_array(D->own, D->gx[d], pl.gram_bytes, "panel_create"));
+  if (pl.has16 && !D->own.take({{&D->gramp16, packed * 2}, {&D->gramx16, (size_t)pl.nblocks * pl.m * pl.m * 2}, {&D->gram16_bad, sizeof(int)}})) return no_memory("panel_create");
   for (const void *f : {reinterpret_cast<const void *>(k_sweep<int8_t, true>), reinterpret_cast<const void *>(k_sweep<int8_t, false>), reinterpret_cast<const void *>(k_sweep<float, true>),
                         reinterpret_cast<const void *>(k_sweep<float, false>), reinterpret_cast<const void *>(k_sweep2<int8_t, true>), reinterpret_cast<const void *>(k_sweep2<int8_t, false>),
                         reinterpret_cast<const void *>(k_sweep2<int8_t, true, uint16_t>), reinterpret_cast<const void *>(k_sweep2<float, true>), reinterpret_cast<const void *>(k_sweep2<float, false>),
@@ -2086,8 +2080,7 @@ extern "C" int bwgr_panel_clone(bwgr_panel **out, bwgr_panel *src) {
   bwgr_panel *P = new bwgr_panel();
   P->data = src->data; P->data->nclones++;
   Guard drop([&] { bwgr_panel_destroy(P); });
-  HIPCHK(hipStreamCreateWithFlags(&P->own_stream, hipStreamNonBlocking));
-  P->stream = P->own_stream;
+  if (!(P->stream = P->own.stream(hipStreamNonBlocking, 0))) return fail(BWGR_EHIP, "panel_clone: hipStreamCreate failed");
   CHK(scratch_alloc(P));
   HIPCHK(hipStreamSynchronize(P->stream));   // (k_sweep3's lists are zeroed on it)
   drop.release();
@@ -2308,8 +2301,6 @@ extern "C" int bwgr_chain_destroy(bwgr_chain *C) {
   }
   if (C->P) { C->P->nchains--; C->P->data->nchains_all--; (void)hipSetDevice(C->P->data->device); }
   for (hipEvent_t ev : C->ev) hipEventDestroy(ev);
-  hipFree(C->e0); hipFree(C->y); if (C->e_owned) hipFree(C->e); hipFree(C->b); hipFree(C->d); hipFree(C->vb); hipFree(C->lam);
-  hipFree(C->B); hipFree(C->D); hipFree(C->VB); hipFree(C->sc);
   delete C;
   return BWGR_OK;
 }
@@ -2325,19 +2316,19 @@ extern "C" int bwgr_chain_create_sharded(bwgr_chain **out, bwgr_panel *P, int mo
   if (P->data->cen) {
     if (!has_d(model) || !P->data->e3_ready)
       return fail(BWGR_EINVAL, "chain_create: an implicitly centred panel (bwgr_panel_set_centred) runs the selection models BayesB / C / Cpi / Dpi only");
-    if (!P->cpre) HIPCHK(hipMalloc(&P->cpre, sizeof(double) * ((size_t)P->data->plan.nblocks + 1)));
+    if (!P->cpre) CHK(own_array(P->own, P->cpre, (size_t)P->data->plan.nblocks + 1, "chain_create"));
   }
   bwgr_chain *C = new bwgr_chain();
   C->P = P; P->nchains++; P->data->nchains_all++; C->model = model; C->itf = it; C->bif = bi; C->iit = (int)it; C->ibi = (int)bi;
   C->pi = pi; C->df = df; C->R2 = R2; C->seed = seed; C->rng_mode = rng_mode;
   C->marker0 = marker0; C->p_total = p_total; C->MSx_eff = MSx_total;
   C->Phi = MSx_total * (1 - R2) / R2;
-  const size_t pb = sizeof(float) * P->data->p;
   Guard drop([&] { bwgr_chain_destroy(C); });
-  HIPCHK(hipMalloc(&C->y, sizeof(float) * P->data->n));
-  if (e_ext) { C->e = e_ext; C->e_owned = false; } else HIPCHK(hipMalloc(&C->e, sizeof(double) * P->data->plan.ld));
-  HIPCHK(hipMalloc(&C->b, pb)); HIPCHK(hipMalloc(&C->d, pb)); HIPCHK(hipMalloc(&C->vb, pb)); HIPCHK(hipMalloc(&C->lam, pb));
-  HIPCHK(hipMalloc(&C->B, pb)); HIPCHK(hipMalloc(&C->D, pb)); HIPCHK(hipMalloc(&C->VB, pb)); HIPCHK(hipMalloc(&C->sc, sizeof(ChainScalars)));
+  const size_t pb = sizeof(float) * P->data->p;
+  if (!C->own.take({{&C->y, sizeof(float) * P->data->n}, {&C->b, pb}, {&C->d, pb}, {&C->vb, pb}, {&C->lam, pb}, {&C->B, pb}, {&C->D, pb}, {&C->VB, pb}, {&C->sc, sizeof(ChainScalars)}}))
+    return no_memory("chain_create");
+  if (e_ext) C->e = e_ext;   // (borrowed)
+  else CHK(own_array(C->own, C->e, (size_t)P->data->plan.ld, "chain_create"));
   HIPCHK(hipMemcpyAsync(C->y, y, sizeof(float) * P->data->n, memloc == BWGR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, P->stream));
   InitArgs ia; ia.y = C->y; ia.e = C->e; ia.n = (int)P->data->n; ia.p = (int)P->data->p; ia.ld = P->data->plan.ld; ia.model = model;
   ia.pi = pi; ia.df = df; ia.R2 = R2; ia.MSx = MSx_total; ia.sc = C->sc;
@@ -2430,7 +2421,7 @@ extern "C" int bwgr_chain_round_sweep(bwgr_chain *C, int blk_begin, int blk_end,
   if (!C || !delta_dev) return fail(BWGR_EINVAL, "round_sweep: null pointer");
   bwgr_panel *P = C->P;
   HIPCHK(hipSetDevice(P->data->device));
-  if (!C->e0) HIPCHK(hipMalloc(&C->e0, sizeof(double) * P->data->plan.ld));
+  if (!C->e0) CHK(own_array(C->own, C->e0, (size_t)P->data->plan.ld, "round_sweep"));
   HIPCHK(hipMemcpyAsync(C->e0, C->e, sizeof(double) * P->data->plan.ld, hipMemcpyDeviceToDevice, P->stream));
   if (blk_begin < blk_end) CHK(bwgr_chain_sweep_blocks(C, blk_begin, blk_end));
   hipLaunchKernelGGL(k_round_delta, dim3(64), dim3(256), 0, P->stream, C->e, C->e0, delta_dev, P->data->plan.ld);
@@ -2533,7 +2524,8 @@ extern "C" int bwgr_chain_run_pair(bwgr_chain *C0, bwgr_chain *C1, int iters) {
   hipStream_t s0 = nullptr;
   if (is_pair_stream(P0->stream)) s0 = P0->stream;
   else if (is_pair_stream(P1->stream)) s0 = P1->stream;
-  else { HIPCHK(hipStreamCreateWithFlags(&s0, hipStreamNonBlocking)); P0->data->pair_streams.push_back(s0); }
+  else if ((s0 = P0->data->own.stream(hipStreamNonBlocking, 0))) P0->data->pair_streams.push_back(s0);
+  else return fail(BWGR_EHIP, "chain_run_pair: hipStreamCreate failed");
   for (bwgr_panel *PX : {P0, P1}) {
     if (PX->stream == s0) continue;
     hipEvent_t ev;
@@ -3071,6 +3063,7 @@ struct bwgr_group {
   std::vector<int64_t> lo, hi;
   std::vector<bwgr_panel *> P;
   std::vector<bwgr_chain *> C;
+  std::vector<std::unique_ptr<DevBufs>> own;   // [g], on shard g's device: delta, sums, and of shards side by side the stream and ev_sweep (own[0]: ev_sum, total, total_sums)
   std::vector<double *> delta, sums;
   std::vector<bwgr_ncclComm_t> comm;
   bool use_comm = false;
@@ -3080,7 +3073,7 @@ struct bwgr_group {
   // compute units, and an exchange round is a sum kernel between events -- no RCCL.  One exact chain is a latency-bound pipeline that fills a
   // third of the chip; the partitioned sampler's shards fill the rest.
   bool same_dev = false;
-  std::vector<hipStream_t> streams;      // owned
+  std::vector<hipStream_t> streams;
   std::vector<hipEvent_t> ev_sweep;      // [g]: shard g's round_sweep (or sums) is enqueued up to here
   hipEvent_t ev_sum[2] = {nullptr, nullptr};
   double *total[2] = {nullptr, nullptr}; // the summed residual deltas of a round, by round parity (ld doubles each); total_sums likewise (2 doubles)
@@ -3092,17 +3085,11 @@ extern "C" int bwgr_group_destroy(bwgr_group *Gp) {
   if (!Gp) return BWGR_OK;
   for (size_t g = 0; g < Gp->C.size(); ++g) if (Gp->C[g]) bwgr_chain_destroy(Gp->C[g]);
   for (size_t g = 0; g < Gp->P.size(); ++g) {
-    if (g < Gp->dev.size()) (void)hipSetDevice(Gp->dev[g]);
-    if (g < Gp->delta.size()) hipFree(Gp->delta[g]);
-    if (g < Gp->sums.size()) hipFree(Gp->sums[g]);
+    (void)hipSetDevice(Gp->dev[g]);
     if (Gp->P[g]) bwgr_panel_destroy(Gp->P[g]);
   }
   if (Gp->use_comm) for (bwgr_ncclComm_t c : Gp->comm) if (c) g_rccl.CommDestroy(c);
-  if (Gp->same_dev) {
-    for (hipEvent_t e : Gp->ev_sweep) if (e) (void)hipEventDestroy(e);
-    for (int k = 0; k < 2; ++k) { if (Gp->ev_sum[k]) (void)hipEventDestroy(Gp->ev_sum[k]); hipFree(Gp->total[k]); hipFree(Gp->total_sums[k]); }
-    for (hipStream_t q : Gp->streams) if (q) (void)hipStreamDestroy(q);
-  }
+  for (size_t g = 0; g < Gp->own.size(); ++g) { (void)hipSetDevice(Gp->dev[g]); Gp->own[g].reset(); }
   delete Gp;
   return BWGR_OK;
 }
@@ -3139,13 +3126,16 @@ extern "C" int bwgr_panel_set_centred(bwgr_panel *P, int on) {
   if (!on) { P->data->cen = false; return BWGR_OK; }
   if (P->data->is_f32) return fail(BWGR_EINVAL, "panel_set_centred: float panels are swept as given (centre the columns before the upload)");
   if (!P->data->e3_ready) return fail(BWGR_EINVAL, "panel_set_centred: this panel has no k_sweep3 (geometry or Gram range): the implicitly centred sweep is k_sweep3's");
-  if (!P->data->csum) {
-    HIPCHK(hipMalloc(&P->data->csum, sizeof(int32_t) * (size_t)P->data->p));
-    HIPCHK(hipMalloc(&P->data->xxc, sizeof(float) * (size_t)P->data->p));
+  if (!P->data->csum) {   // the panel gets the pair once both arrays exist and are filled
+    int32_t *csum = nullptr; float *xxc = nullptr;
+    if (!P->data->own.take({{&csum, sizeof(int32_t) * (size_t)P->data->p}, {&xxc, sizeof(float) * (size_t)P->data->p}})) return no_memory("panel_set_centred");
+    Guard drop([&] { P->data->own.drop(csum); P->data->own.drop(xxc); });
     const int wpb = 4;
-    hipLaunchKernelGGL(k_colsum_i8, dim3((unsigned)((P->data->p + wpb - 1) / wpb)), dim3(64 * wpb), 0, P->stream, (const int8_t *)P->data->X, P->data->plan.R, (int)P->data->n, (int)P->data->p, P->data->csum, P->data->xxc);
+    hipLaunchKernelGGL(k_colsum_i8, dim3((unsigned)((P->data->p + wpb - 1) / wpb)), dim3(64 * wpb), 0, P->stream, (const int8_t *)P->data->X, P->data->plan.R, (int)P->data->n, (int)P->data->p, csum, xxc);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(P->stream));
+    drop.release();
+    P->data->csum = csum; P->data->xxc = xxc;
   }
   P->data->cen = true;
   return BWGR_OK;
@@ -3189,6 +3179,7 @@ static int group_create_impl(bwgr_group **out, int ndev, const int *devices, con
   Gp->dev.assign(devices, devices + ndev);
   Gp->same_dev = ndev > 1 && std::all_of(devices, devices + ndev, [&](int d) { return d == devices[0]; });
   Gp->P.assign(ndev, nullptr); Gp->C.assign(ndev, nullptr); Gp->delta.assign(ndev, nullptr); Gp->sums.assign(ndev, nullptr);
+  for (int g = 0; g < ndev; ++g) Gp->own.emplace_back(new DevBufs());
   Guard drop([&] { bwgr_group_destroy(Gp); });
   const size_t esz = (xtype == BWGR_X_I8) ? 1 : (xtype == BWGR_X_F32 ? 4 : 8);
   double msx = 0.0;
@@ -3197,8 +3188,8 @@ static int group_create_impl(bwgr_group **out, int ndev, const int *devices, con
     Gp->lo.push_back(lo); Gp->hi.push_back(hi);
     CHK(bwgr_panel_create(&Gp->P[g], reinterpret_cast<const unsigned char *>(X) + (size_t)lo * (size_t)ldx * esz, xtype, memloc, n, hi - lo, ldx, devices[g], m, 0));
     if (Gp->same_dev) {   // shards of one device: each on a stream of its own; from three shards on, 256-row streamers (K3 + 1 units a shard instead of 2 K3 + 2)
-      hipStream_t q = nullptr;
-      if (hipStreamCreateWithFlags(&q, hipStreamNonBlocking) != hipSuccess) return fail(BWGR_EHIP, "group_create: hipStreamCreate failed");
+      hipStream_t q = Gp->own[g]->stream(hipStreamNonBlocking, 0);
+      if (!q) return fail(BWGR_EHIP, "group_create: hipStreamCreate failed");
       Gp->streams.push_back(q);
       Gp->P[g]->stream = q;
       if (ndev > 2 && Gp->P[g]->data->sw.solo3 < 0) Gp->P[g]->data->crowded = true;   // (an explicit BWGR_SOLO3 decides otherwise: experiments)
@@ -3219,8 +3210,8 @@ static int group_create_impl(bwgr_group **out, int ndev, const int *devices, con
   }
   for (int g = 0; g < ndev; ++g) {
     CHK(bwgr_chain_create_sharded(&Gp->C[g], Gp->P[g], model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode, Gp->lo[g], p, Gp->MSx_total, nullptr));
-    if (hipSetDevice(devices[g]) != hipSuccess || hipMalloc(&Gp->delta[g], sizeof(double) * (size_t)Gp->P[g]->data->plan.ld) != hipSuccess ||
-        hipMalloc(&Gp->sums[g], sizeof(double) * 2) != hipSuccess) return fail(BWGR_ENOMEM, "group_create: device allocation failed");
+    if (hipSetDevice(devices[g]) != hipSuccess || !Gp->own[g]->take({{&Gp->delta[g], sizeof(double) * (size_t)Gp->P[g]->data->plan.ld}, {&Gp->sums[g], sizeof(double) * 2}}))
+      return no_memory("group_create");
     if (Gp->P[g]->data->plan.ld != Gp->P[0]->data->plan.ld) return fail(BWGR_EINVAL, "group_create: shards disagree on the padded row count");
   }
   // (shards side by side exchange through one kernel on the same card, not a ring over xGMI, but every exchange is a launch boundary for all of
@@ -3234,10 +3225,10 @@ static int group_create_impl(bwgr_group **out, int ndev, const int *devices, con
   if (Gp->same_dev) {
     if (hipSetDevice(devices[0]) != hipSuccess) return fail(BWGR_EHIP, "group_create: hipSetDevice failed");
     Gp->ev_sweep.assign(ndev, nullptr);
-    for (int g = 0; g < ndev; ++g) if (hipEventCreateWithFlags(&Gp->ev_sweep[g], hipEventDisableTiming) != hipSuccess) return fail(BWGR_EHIP, "group_create: hipEventCreate failed");
+    for (int g = 0; g < ndev; ++g) if (!(Gp->ev_sweep[g] = Gp->own[g]->event(hipEventDisableTiming))) return fail(BWGR_EHIP, "group_create: hipEventCreate failed");
     for (int k = 0; k < 2; ++k) {
-      if (hipEventCreateWithFlags(&Gp->ev_sum[k], hipEventDisableTiming) != hipSuccess || hipMalloc(&Gp->total[k], sizeof(double) * (size_t)Gp->P[0]->data->plan.ld) != hipSuccess ||
-          hipMalloc(&Gp->total_sums[k], sizeof(double) * 2) != hipSuccess) return fail(BWGR_ENOMEM, "group_create: device allocation failed");
+      if (!Gp->own[0]->take({DevBufs::want_event(&Gp->ev_sum[k], hipEventDisableTiming), {&Gp->total[k], sizeof(double) * (size_t)Gp->P[0]->data->plan.ld}, {&Gp->total_sums[k], sizeof(double) * 2}}))
+        return no_memory("group_create");
     }
   }
   if (Gp->use_comm) {

@@ -436,6 +436,9 @@ int bwgr_debug_withhold(bwgr_panel *P, int on);
 /* the sweeps that the calling thread's last bwgr_kmup / bwgr_kmup2 / bwgr_wgr / bwgr_wgr_ex call redid on the fp64 residual because they left
  * the fixed-point range of their engine: what bwgr_chain_redo_count is for a chain, for the entry points that have none. */
 int bwgr_debug_last_redo(int *count);
+/* the device arrays, streams and events that the library's holders (csrc/devbufs.h) own in this process right now -- every handle's and every
+ * running call's: out[0..2].  What a destroyed handle or a finished call took is gone from the counts. */
+int bwgr_debug_live(int64_t out[3]);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,163 @@
+"""GPU: what the handles and the one-call entry points own on the device comes and goes with them.
+
+Every handle (panel data, panel, chain, group) and every call holds its device arrays, streams and long-lived events in one holder
+(bwgr_amd/csrc/devbufs.h); bwgr_amd.debug_live() counts what the holders of this process own.  These tests assert on those counts and on
+status codes only -- on the tpod panel (196 x 376 int8: three 128-marker blocks, one slab); the parity of the results is the other GPU
+tests' job, and the failure paths of the holder run on the CPU (test_devbufs_cpu.py)."""
+import gc
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+EINVAL = 1
+
+
+def live():
+    import bwgr_amd
+    gc.collect()   # (a handle some earlier test dropped without closing goes now, not in the middle of a count)
+    return bwgr_amd.debug_live()
+
+
+def _above(now, start):
+    return all(a > b for a, b in zip(now, start))
+
+
+def _family(tpod, monkeypatch):
+    """Root panel, BayesB chain alone on it (k_sweep3 at the shipped gate, its range snapshot, the variates drawn ahead on their stream
+    between their two events); then a clone with a BayesA chain (the affine engine's winv / qsumw); then a fresh panel, implicitly centred,
+    with a BayesC chain (csum / xxc, cpre).  Returns the counts at the start, while everything is alive, and after the teardown."""
+    import bwgr_amd
+    monkeypatch.delenv("BWGR_ENG3_THR", raising=False)   # the shipped engine gate (read when a panel is made)
+    y, X = tpod["y"], tpod["gen"]
+    start = live()
+    root = bwgr_amd.Panel(X)
+    c_root = bwgr_amd.Chain(root, "BayesB", y, it=3, bi=1, seed=11)
+    before_run = live()
+    c_root.run(3)
+    c_root.sync()
+    after_run = live()
+    # the range snapshot (e, b, d, vb: four arrays) and the draws group (one array, one stream, two events), each taken whole
+    assert after_run == (before_run[0] + 5, before_run[1] + 1, before_run[2] + 2), (before_run, after_run)
+    clone = root.clone()
+    c_clone = bwgr_amd.Chain(clone, "BayesA", y, it=3, bi=1, seed=12)
+    before_run = live()
+    c_clone.run(3)
+    c_clone.sync()
+    # winv and qsumw, and the range snapshot of the fixed-point streamers; no draws ahead beside another handle
+    assert live() == (before_run[0] + 6, before_run[1], before_run[2]), (before_run, live())
+    cen = bwgr_amd.Panel(X)
+    before_cen = live()
+    cen.set_centred(True)
+    assert live()[0] == before_cen[0] + 2   # csum and xxc, together
+    cen.set_centred(True)
+    assert live()[0] == before_cen[0] + 2   # ... once
+    c_cen = bwgr_amd.Chain(cen, "BayesC", y, it=3, bi=1, seed=13)
+    c_cen.run(3)
+    c_cen.sync()
+    peak = live()
+    assert _above(peak, start), (start, peak)
+    for c in (c_root, c_clone, c_cen):
+        c.close()
+    clone.close()
+    root.close()
+    assert _above(live(), start)   # (the centred panel is still there)
+    cen.close()
+    return start, peak, live()
+
+
+def test_family_made_run_and_torn_down(tpod, monkeypatch):
+    start, peak, end = _family(tpod, monkeypatch)
+    assert end == start, (start, peak, end)
+    start2, peak2, end2 = _family(tpod, monkeypatch)
+    assert start2 == start and peak2 == peak and end2 == start, (start, peak, end, start2, peak2, end2)
+
+
+def test_refused_call_owns_nothing_new(tpod):
+    import bwgr_amd
+    y, X = tpod["y"], tpod["gen"]
+    rng = np.random.default_rng(5)
+    start = live()
+    P = bwgr_amd.Panel(X)
+    ch = bwgr_amd.Chain(P, "BayesB", y, it=3, bi=1, seed=3)
+    held = live()
+    with pytest.raises(bwgr_amd.BwgrError) as ei:
+        P.close()
+    assert ei.value.code == EINVAL and live() == held
+    with pytest.raises(bwgr_amd.BwgrError) as ei:
+        bwgr_amd.mrr(rng.standard_normal((X.shape[0], 17)), P, maxit=2)
+    assert ei.value.code == EINVAL and live() == held
+    with pytest.raises(bwgr_amd.BwgrError) as ei:
+        bwgr_amd.uvbeta(rng.standard_normal((X.shape[0], 2)), P, 7, maxit=2)   # (an integer variant reaches the library)
+    assert ei.value.code == EINVAL and "variant" in str(ei.value) and live() == held
+    ch.close()
+    P.close()
+    assert live() == start
+
+
+def test_one_call_entry_points_give_back_what_they_took(tpod):
+    import bwgr_amd
+    y, X = tpod["y"], tpod["gen"]
+    n, p = X.shape
+    rng = np.random.default_rng(6)
+    use = np.sort(rng.choice(n, 120, replace=False))
+    e = (y - y.mean()).astype(np.float32)
+    xx_use = (X[use].astype(np.float64) ** 2).sum(0)
+    start = live()
+    P = bwgr_amd.Panel(X)
+    calls = {
+        "emRR": lambda: bwgr_amd.emRR(y, P, maxit=2),
+        "emBB": lambda: bwgr_amd.emBB(y, P, maxit=2),
+        "mrr": lambda: bwgr_amd.mrr(rng.standard_normal((n, 2)), P, maxit=2),
+        "uvbeta": lambda: bwgr_amd.uvbeta(rng.standard_normal((n, 3)), P, "D", maxit=2, xb=True),
+        "GRM": lambda: bwgr_amd.GRM(P),
+        "KMUP2": lambda: bwgr_amd.KMUP2(P, use, np.zeros(p), np.ones(p), xx_use, e, np.ones(p), 1.0, 0.0, seed=7, it=1),
+        "wgr": lambda: bwgr_amd.wgr(y, P, it=6, bi=2, bag=0.8, seed=8),
+    }
+    # The calls that do not sweep on P itself give everything back the first time.  A sweep on P may leave the PANEL arrays that it keeps (the
+    # scratch that comes with the first sweep that needs it: never a stream or an event here, where P is not alone in a chain of its own), so
+    # those calls are counted exactly the second time.
+    for name, call in calls.items():
+        before = live()
+        call()
+        first = live()
+        if name in ("emRR", "mrr", "uvbeta", "GRM"):
+            assert first == before, (name, before, first)
+        assert first[0] >= before[0] and first[1:] == before[1:], (name, before, first)
+        call()
+        assert live() == first, (name, first, live())
+    P.close()
+    assert live() == start
+
+
+def test_pair_run(tpod):
+    import bwgr_amd
+    y, X = tpod["y"], tpod["gen"]
+    start = live()
+    root = bwgr_amd.Panel(X)
+    clone = root.clone()
+    c0 = bwgr_amd.Chain(root, "BayesC", y, it=3, bi=1, seed=21)
+    c1 = bwgr_amd.Chain(clone, "BayesC", y, it=3, bi=1, seed=22)
+    before = live()
+    c0.run_pair(c1, 3)
+    c0.sync(); c1.sync()
+    assert live()[1] == before[1] + 1, (before, live())   # the pair stream, which lives in the data
+    c0.close(); c1.close()
+    clone.close()
+    assert live()[1] >= start[1] + 1   # ... and outlives the clone
+    root.close()
+    assert live() == start
+
+
+def test_group_of_two_shards_on_one_device(tpod):
+    import bwgr_amd
+    y, X = tpod["y"], tpod["gen"]
+    start = live()
+    g = bwgr_amd.Group("BayesB", y.astype(np.float32), X, devices=[0, 0], it=3, bi=1, pi=0.95, seed=31, centre=True)
+    assert g.implicit_centring and g.info()["rccl"] == 0 and g.info()["devices"] == 2
+    g.run(3)
+    g.sync()
+    assert _above(live(), start)
+    g.close()
+    assert live() == start
