@@ -166,6 +166,19 @@ class Panel:
         L = _lib.lib()
         return self._nxn(np.float64, device_out, lambda ptr, ld, loc: L.bwgr_panel_kernel(self._h, k, float(par), int(bool(flag)), ptr, ld, loc))
 
+    def xb(self, B):
+        """X B on the raw int8 genotypes for every row, n x k float64 (bwgr_panel_xb); B is p x k or a vector of p."""
+        Bm = np.asarray(B, np.float64)
+        if Bm.ndim == 1:
+            Bm = Bm[:, None]
+        if Bm.ndim != 2 or Bm.shape[0] != self.p:
+            raise BwgrError(1, "panel_xb: B has shape %s; nrow(B) must equal ncol(X) = %d" % (Bm.shape, self.p))
+        Bf = np.asfortranarray(Bm)
+        k = Bf.shape[1]
+        out = np.zeros((self.n, max(k, 1)), order="F")
+        check(_lib.lib().bwgr_panel_xb(self._h, _dp(Bf), int(k), _dp(out)))
+        return out
+
     def close(self):
         if self._h:
             for q in list(getattr(self, "_clones", ())):
@@ -1031,39 +1044,177 @@ def uvb_plan(n, p, k):
     return dict(zip(("W", "groups", "solve_traits", "ngl", "solve_lds", "pass_lds", "pass_wg", "ws_bytes"), [int(v) for v in out]))
 
 
+def _uvb_variant(variant, who):
+    if isinstance(variant, str) and variant not in UVB_VARIANTS:
+        raise BwgrError(1, "%s: unknown variant %r (one of D, F, X, Z)" % (who, variant))
+    return UVB_VARIANTS[variant] if isinstance(variant, str) else int(variant)   # (an integer is passed on: the library checks it)
+
+
+def _uvb_inputs(Y, nrow, v, tol, df0, who):
+    """Y as an n x k float64 matrix; for the float variants Y, tol and df0 rounded to float, as the reference receives them."""
+    Ym = np.asarray(Y, np.float64)
+    if Ym.ndim == 1:
+        Ym = Ym[:, None]
+    if Ym.ndim != 2 or Ym.shape[0] != nrow:
+        raise BwgrError(1, "%s: Y has shape %s; nrow(Y) must equal nrow(X) = %d" % (who, Ym.shape, nrow))
+    if v != 0:
+        Ym = Ym.astype(np.float32).astype(np.float64)
+        tol = float(np.float32(tol)); df0 = float(np.float32(df0))
+    return Ym, tol, df0
+
+
+def _uvb_outputs(ncoef, k):
+    kk = max(k, 1)
+    return (np.zeros((ncoef, kk), order="F"), np.zeros(kk), np.zeros(kk), np.zeros(kk), np.zeros(kk), np.zeros(kk, np.int32), np.zeros(kk))
+
+
+def _uvb_panel(P, Ym, v, maxit, tol, df0, xb=False):
+    """bwgr_uvbeta on exactly what it is given (n x k float64 Y): no rounding."""
+    k = Ym.shape[1]
+    Yf = np.asfortranarray(Ym)
+    b, mu, h2, ve, vb, its, cnv = _uvb_outputs(P.p, k)
+    xbm = np.zeros((P.n, max(k, 1)), order="F") if xb else None
+    check(_lib.lib().bwgr_uvbeta(P._h, _dp(Yf), int(k), int(v), int(maxit), float(tol), float(df0), _dp(b), _dp(mu), _dp(h2), _dp(ve), _dp(vb),
+                                 its.ctypes.data_as(C.POINTER(C.c_int)), _dp(cnv), _dp(xbm) if xb else None))
+    out = dict(zip(UVB_KEYS, (b, mu, h2, ve, vb, its, cnv)))
+    if xb:
+        out["xb"] = xbm
+    return out
+
+
+def _uvb_dense(Ym, Z, v, maxit, tol, df0, device=0):
+    """bwgr_uvbeta_dense on exactly what it is given (n x k float64 Y, n x q float64 Z): no rounding."""
+    Zf = np.asarray(Z, np.float64)
+    n, q = Zf.shape
+    if q < 2 or Zf.strides[0] != 8 or Zf.strides[1] % 8 or Zf.strides[1] < 8 * n:   # (the rows of a column-major matrix are passed as they lie: ldz > n)
+        Zf = np.asfortranarray(Zf)
+    ldz = Zf.strides[1] // 8 if q > 1 else max(n, 1)
+    k = Ym.shape[1]
+    Yf = np.asfortranarray(Ym)
+    b, mu, h2, ve, vb, its, cnv = _uvb_outputs(q, k)
+    check(_lib.lib().bwgr_uvbeta_dense(int(device), _dp(Zf), int(n), int(q), int(ldz), _dp(Yf), int(k), int(v), int(maxit), float(tol), float(df0),
+                                       _dp(b), _dp(mu), _dp(h2), _dp(ve), _dp(vb), its.ctypes.data_as(C.POINTER(C.c_int)), _dp(cnv)))
+    return dict(zip(UVB_KEYS, (b, mu, h2, ve, vb, its, cnv)))
+
+
 def uvbeta(Y, X, variant="D", maxit=100, tol=10e-7, df0=20.0, xb=False, **kw):
     """One ridge fit per column of Y on one X (bwgr_uvbeta): Y is n x k (NaN = missing) or a vector; variant "D" solver1x / UVBETA,
     "F" solver1xF / FUVBETA, "X" xsolver1xF / XFUVBETA, "Z" zsolver1xF / ZFUVBETA (src/RcppEigen20230423.cpp:1410-1816).  The float
     variants receive Y, tol and df0 rounded to float, as the reference does; the engine is fp64.  Returns dict(b [p x k], mu, h2, ve, vb,
     its, cnv[, xb [n x k] = X b on the raw genotypes]).  X is an array or a Panel."""
-    if isinstance(variant, str) and variant not in UVB_VARIANTS:
-        raise BwgrError(1, "uvbeta: unknown variant %r (one of D, F, X, Z)" % (variant,))
-    v = UVB_VARIANTS[variant] if isinstance(variant, str) else int(variant)   # (an integer is passed on: the library checks it)
+    v = _uvb_variant(variant, "uvbeta")
     P, own = _as_panel(X, **kw)
     try:
-        Ym = np.asarray(Y, np.float64)
-        if Ym.ndim == 1:
-            Ym = Ym[:, None]
-        if Ym.ndim != 2 or Ym.shape[0] != P.n:
-            raise BwgrError(1, "uvbeta: Y has shape %s; nrow(Y) must equal nrow(X) = %d" % (Ym.shape, P.n))
-        if v != 0:
-            Ym = Ym.astype(np.float32).astype(np.float64)
-            tol = float(np.float32(tol)); df0 = float(np.float32(df0))
-        k = Ym.shape[1]
-        Yf = np.asfortranarray(Ym)
-        kk = max(k, 1)
-        b = np.zeros((P.p, kk), order="F"); mu = np.zeros(kk); h2 = np.zeros(kk); ve = np.zeros(kk); vb = np.zeros(kk); cnv = np.zeros(kk)
-        its = np.zeros(kk, np.int32)
-        xbm = np.zeros((P.n, kk), order="F") if xb else None
-        check(_lib.lib().bwgr_uvbeta(P._h, _dp(Yf), int(k), int(v), int(maxit), float(tol), float(df0), _dp(b), _dp(mu), _dp(h2), _dp(ve), _dp(vb),
-                                     its.ctypes.data_as(C.POINTER(C.c_int)), _dp(cnv), _dp(xbm) if xb else None))
-        out = dict(zip(UVB_KEYS, (b, mu, h2, ve, vb, its, cnv)))
-        if xb:
-            out["xb"] = xbm
-        return out
+        Ym, tol, df0 = _uvb_inputs(Y, P.n, v, tol, df0, "uvbeta")
+        return _uvb_panel(P, Ym, v, maxit, tol, df0, xb)
     finally:
         if own:
             P.close()
+
+
+def uvbd_plan(n, q, k):
+    """bwgr_debug_uvbd_plan (host arithmetic, no GPU): dict(lds_rows, e_in_lds, threads, lds_bytes, ws_bytes)."""
+    out = (C.c_int64 * 5)()
+    check(_lib.lib().bwgr_debug_uvbd_plan(int(n), int(q), int(k), out))
+    return dict(zip(("lds_rows", "e_in_lds", "threads", "lds_bytes", "ws_bytes"), [int(v) for v in out]))
+
+
+def uvbeta_dense(Y, Z, variant="D", maxit=100, tol=10e-7, df0=20.0, *, device=0):
+    """uvbeta's fits on a small dense real-valued design Z (n x q float64; bwgr_uvbeta_dense): one workgroup per trait runs the trait's whole
+    fit.  Same variants, rounding of Y, tol and df0, rules and return dict (b is q x k) as uvbeta."""
+    v = _uvb_variant(variant, "uvbeta_dense")
+    Zm = np.asarray(Z, np.float64)
+    if Zm.ndim == 1:
+        Zm = Zm[:, None]
+    if Zm.ndim != 2:
+        raise BwgrError(1, "uvbeta_dense: Z has shape %s; it must be n x q" % (Zm.shape,))
+    Ym, tol, df0 = _uvb_inputs(Y, Zm.shape[0], v, tol, df0, "uvbeta_dense")
+    return _uvb_dense(Ym, Zm, v, maxit, tol, df0, device)
+
+
+def panel_xb(X, B, **kw):
+    """X B on the raw int8 genotypes, n x k float64 (bwgr_panel_xb); X is an array or a Panel."""
+    P, own = _as_panel(X, **kw)
+    try:
+        return P.xb(B)
+    finally:
+        if own:
+            P.close()
+
+
+# ---- latent-space fits: XSEMF / ZSEMF / YSEMF (src/RcppEigen20230423.cpp:1756-1769, :1819-1874; R/RcppExports.R:232, 240, 244) ----
+# Y is rounded to float once, as the reference receives it; everything after runs in fp64 on unrounded intermediates (G, Z, Y - G), where the
+# reference computes in float throughout (DESIGN.md section 4.8).  The thin SVD of G (n x k) is numpy's, on the host.  The results do not
+# depend on the sign of a singular pair: the sign flips Z's column, V's column and the fitted coefficient together.
+def _sem_npc(npc, m, who):
+    """The latent columns kept of m = min(n, k) (:1760-1761).  npc < 0: round(2 sqrt(m)), which never lies on a tie ((x + 1/2)^2 is no
+    integer); 0: m.  More than m is refused: leftCols(npc) would leave the matrix."""
+    npc = int(npc)
+    if npc < 0:
+        npc = int(np.floor(2.0 * np.sqrt(m) + 0.5))                  # :1760
+    if npc == 0:
+        npc = m                                                      # :1761
+    if npc > m:
+        raise BwgrError(1, "%s: npc = %d exceeds min(nrow(Y), ncol(Y)) = %d" % (who, npc, m))
+    return npc
+
+
+def _sem_latent(G, npc, who):
+    """Z = (U diag(s)).leftCols(npc) and V.leftCols(npc) of G = U diag(s) V' (:1759-1762)."""
+    U, s, Vt = np.linalg.svd(G, full_matrices=False)
+    npc = _sem_npc(npc, s.shape[0], who)
+    return (U * s)[:, :npc], Vt.T[:, :npc]
+
+
+def _sem_gc(G):
+    """(:1765-1768) the columns centred and scaled to unit population variance, and their correlations; a zero column gives NaN, as there."""
+    N = G.shape[0]
+    G = G - G.mean(0)
+    with np.errstate(all="ignore"):
+        G = G / np.sqrt((G ** 2).sum(0) / N)
+        return G, (G.T @ G) / N
+
+
+def _sem(which, Y, X, npc, maxit, tol, df0, panel_kw):
+    v = UVB_VARIANTS["X" if which == "XSEMF" else "Z"]
+    P, own = _as_panel(X, **panel_kw)
+    try:
+        Ym, tol, df0 = _uvb_inputs(Y, P.n, v, tol, df0, which)
+        npc = _sem_npc(npc, min(Ym.shape), which)                    # (refused before anything runs)
+        s1 = _uvb_panel(P, Ym, v, maxit, tol, df0)                   # BETA = XFUVBETA / ZFUVBETA(Y, X)
+        Z, V = _sem_latent(P.xb(s1["b"]), npc, which)                # G = X BETA and its latent design
+        s2 = _uvb_dense(Ym, Z, v, maxit, tol, df0, P.device)         # ALPHA / Coef = XFUVBETA / ZFUVBETA(Y, Z)
+        b = s1["b"] @ (V @ s2["b"])
+        G = P.xb(b)
+        if which == "XSEMF":
+            hat, GC = _sem_gc(G)
+            return dict(zip(("b", "GC", "hat"), (b, GC, hat)))
+        if which == "ZSEMF":
+            return dict(zip(("mu", "b", "hat", "h2", "GC"), (s2["mu"], b, G + s2["mu"], s2["h2"], _sem_gc(G)[1])))
+        s3 = _uvb_panel(P, Ym - G, v, maxit, tol, df0)               # beta_Xd = ZFUVBETA(Y - G, X), :1859
+        b = b + s3["b"]
+        G = P.xb(b)
+        return dict(zip(("mu", "b", "hat", "h2", "GC"), (s3["mu"], b, G + s3["mu"], s2["h2"] + s3["h2"], _sem_gc(G)[1])))
+    finally:
+        if own:
+            P.close()
+
+
+def XSEMF(Y, X, npc=0, *, maxit=100, tol=10e-7, df0=20.0, **kw):
+    """XSEMF(Y, X, npc), src/RcppEigen20230423.cpp:1756-1769 (R/RcppExports.R:232): XFUVBETA on the panel, the SVD of X BETA, XFUVBETA on its
+    first npc latent columns, the coefficients mapped back.  list(b, GC, hat); hat is the standardised X b.  X is an array or a Panel."""
+    return _sem("XSEMF", Y, X, npc, maxit, tol, df0, kw)
+
+
+def ZSEMF(Y, X, npc=0, *, maxit=100, tol=10e-7, df0=20.0, **kw):
+    """ZSEMF(Y, X, npc), src/RcppEigen20230423.cpp:1819-1845 (R/RcppExports.R:240): XSEMF's steps with ZFUVBETA.  list(mu, b, hat, h2, GC)."""
+    return _sem("ZSEMF", Y, X, npc, maxit, tol, df0, kw)
+
+
+def YSEMF(Y, X, npc=-1, *, maxit=100, tol=10e-7, df0=20.0, **kw):
+    """YSEMF(Y, X, npc), src/RcppEigen20230423.cpp:1848-1874 (R/RcppExports.R:244): ZSEMF's latent fit, then ZFUVBETA(Y - X b, X) on the
+    panel for what the latent space left.  list(mu, b, hat, h2, GC); npc = -1: round(2 sqrt(min(n, k))) latent columns."""
+    return _sem("YSEMF", Y, X, npc, maxit, tol, df0, kw)
 
 
 def solver1x(Y, X, maxit=100, tol=10e-7, df0=20.0, **kw):

@@ -24,6 +24,7 @@
 #include "sweep3p.hip.h"
 #include "mrr.hip.h"
 #include "uvb.hip.h"
+#include "uvbd.hip.h"
 #include "kernels.hip.h"
 #include <stdlib.h>
 
@@ -4357,6 +4358,144 @@ extern "C" int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int varian
     if (cnv_out) cnv_out[t] = q.cnv;
     its_out[t] = q.its;
   }
+  return BWGR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the same fits on a small dense design, and X B on the panel: the second stage and the products of XSEMF / ZSEMF / YSEMF
+// (src/RcppEigen20230423.cpp:1756-1769, :1819-1874): the kernels of uvbd.hip.h
+// ------------------------------------------------------------------------------------------------
+// The plan, decided here and nowhere else (bwgr_debug_uvbd_plan exposes it to the CPU tests): whether a trait's residual lives in its
+// workgroup's LDS or in a global workspace, the workgroup size, the dynamic LDS bytes and the bytes of that workspace.
+struct UvbdPlan { int64_t lds_rows; bool e_in_lds; int threads; size_t lds_bytes, ws_bytes; };
+static UvbdPlan uvbd_plan(int64_t n, int64_t q, int64_t k) {
+  (void)q;   // (the per-column values live in global memory: the LDS carve-up does not depend on q)
+  UvbdPlan pl;
+  pl.lds_rows = (int64_t)((UVBD_LDS_MAX - UVBD_LDS_FIXED) / sizeof(double));
+  pl.e_in_lds = n <= pl.lds_rows;
+  pl.threads = (int)std::min<int64_t>(UVBD_TMAX, (n + 63) / 64 * 64);   // one row per thread up to 1024 rows, whole waves
+  pl.lds_bytes = UVBD_LDS_FIXED + (pl.e_in_lds ? sizeof(double) * (size_t)n : 0);
+  pl.ws_bytes = pl.e_in_lds ? 0 : sizeof(double) * (size_t)n * (size_t)k;
+  return pl;
+}
+extern "C" int bwgr_debug_uvbd_plan(int64_t n, int64_t q, int64_t k, int64_t out[BWGR_UVBD_PLAN_NOUT]) {
+  if (!out) return fail(BWGR_EINVAL, "uvbd plan: null pointer");
+  if (n < 1 || q < 1 || k < 1) return fail(BWGR_EINVAL, "uvbd plan: n = %lld, q = %lld, k = %lld (each at least 1)", (long long)n, (long long)q, (long long)k);
+  const UvbdPlan pl = uvbd_plan(n, q, k);
+  out[0] = pl.lds_rows; out[1] = pl.e_in_lds ? 1 : 0; out[2] = pl.threads; out[3] = (int64_t)pl.lds_bytes; out[4] = (int64_t)pl.ws_bytes;
+  return BWGR_OK;
+}
+
+extern "C" int bwgr_uvbeta_dense(int device, const double *Z, int64_t n, int64_t q, int64_t ldz, const double *Y, int64_t k, int variant, int maxit,
+                                 double tol, double df0, double *b_out, double *mu_out, double *h2_out, double *ve_out, double *vb_out, int *its_out,
+                                 double *cnv_out) {
+  if (!Z || !Y || !b_out || !its_out) return fail(BWGR_EINVAL, "uvbeta_dense: null pointer");
+  if (n < 1 || q < 1 || q > 0x7FFFFF00ll || ldz < n) return fail(BWGR_EINVAL, "uvbeta_dense: n = %lld rows, q = %lld columns, ldz = %lld (n, q at least 1, ldz at least n)", (long long)n, (long long)q, (long long)ldz);
+  if (k < 1 || k > 0x7FFFFFFFll) return fail(BWGR_EINVAL, "uvbeta_dense: k = %lld traits (at least 1)", (long long)k);
+  if (variant < BWGR_UVB_D || variant > BWGR_UVB_Z) return fail(BWGR_EINVAL, "uvbeta_dense: unknown variant %d (0 solver1x, 1 solver1xF, 2 xsolver1xF, 3 zsolver1xF)", variant);
+  if (maxit < 0) return fail(BWGR_EINVAL, "uvbeta_dense: maxit = %d", maxit);
+  CHK(require_device(device));
+  const UvbdPlan pl = uvbd_plan(n, q, k);
+  const size_t nn = (size_t)n, nq = (size_t)q, nk = (size_t)k;
+  // ---- host set-up (:1413-1414, :1419 on the trait's own rows); Z without its padding ----
+  std::vector<double> Zc(nn * nq);
+  for (int64_t j = 0; j < q; ++j)
+    for (int64_t r = 0; r < n; ++r) {
+      const double v = Z[(size_t)j * ldz + r];
+      if (!std::isfinite(v)) return fail(BWGR_EINVAL, "uvbeta_dense: Z[%lld, %lld] is not finite", (long long)r, (long long)j);
+      Zc[(size_t)j * nn + r] = v;
+    }
+  std::vector<UvbdTrait> tr(nk);
+  std::vector<double> y(nk * nn, 0.0);
+  std::vector<uint8_t> m(nk * nn, 0);
+  for (int64_t t = 0; t < k; ++t) {
+    UvbdTrait &u = tr[(size_t)t];
+    u.nt = 0.0; u.mu = 0.0; u.vy = 0.0;
+    const double *Yt = Y + (size_t)t * nn;
+    for (int64_t r = 0; r < n; ++r)
+      if (!std::isnan(Yt[r])) { m[(size_t)t * nn + r] = 1; u.nt += 1.0; u.mu += Yt[r]; }
+    if (u.nt == 1.0) return fail(BWGR_EINVAL, "uvbeta_dense: trait %lld has one observed row (the variances divide by n - 1)", (long long)t);
+    if (u.nt == 0.0) continue;
+    u.mu /= u.nt;
+    double *yt = y.data() + (size_t)t * nn;
+    for (int64_t r = 0; r < n; ++r)
+      if (m[(size_t)t * nn + r]) { yt[r] = Yt[r] - u.mu; u.vy += yt[r] * yt[r]; }
+    u.vy /= (u.nt - 1.0);
+  }
+  std::vector<int32_t> order(std::max<size_t>((size_t)maxit * nq, 1));
+  {
+    std::vector<int> ord(nq);
+    for (int64_t j = 0; j < q; ++j) ord[(size_t)j] = (int)j;
+    for (int s = 0; s < maxit; ++s) {
+      std::shuffle(ord.begin(), ord.end(), std::mt19937(s));                                               // :1428 (cumulative, as there)
+      std::copy(ord.begin(), ord.end(), order.begin() + (size_t)s * nq);
+    }
+  }
+  std::vector<double> res(nk * UVBD_NRES);
+  DevBufs bufs;
+  double *Zd = bufs.get<double>(nn * nq), *yd = bufs.get<double>(nk * nn), *cols = bufs.get<double>(nk * 3 * nq), *bd = bufs.get<double>(nq * nk);
+  double *resd = bufs.get<double>(nk * UVBD_NRES), *ews = pl.e_in_lds ? nullptr : bufs.get<double>(pl.ws_bytes / sizeof(double));
+  uint8_t *md = bufs.get<uint8_t>(nk * nn);
+  UvbdTrait *trd = bufs.get<UvbdTrait>(nk);
+  int32_t *ordd = bufs.get<int32_t>(order.size());
+  if (!Zd || !yd || !cols || !bd || !resd || (!pl.e_in_lds && !ews) || !md || !trd || !ordd) return fail(BWGR_ENOMEM, "uvbeta_dense: device allocation failed");
+  HIPCHK(hipMemcpy(Zd, Zc.data(), sizeof(double) * nn * nq, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(yd, y.data(), sizeof(double) * nk * nn, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(md, m.data(), nk * nn, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(trd, tr.data(), sizeof(UvbdTrait) * nk, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ordd, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(bd, 0, sizeof(double) * nq * nk));                                                      // b = 0, :1421
+  UvbdArgs A;
+  A.Z = Zd; A.n = n; A.q = q; A.y = yd; A.m = md; A.tr = trd; A.order = ordd; A.variant = variant; A.maxit = maxit;
+  A.logtol = log10(tol); A.df0 = df0; A.thr = variant == BWGR_UVB_F ? 0.00001 : 0.0;
+  A.cols = cols; A.e_ws = ews; A.b = bd; A.res = resd;
+  if (pl.e_in_lds) {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_uvbd_fit<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)UVBD_LDS_MAX));
+    hipLaunchKernelGGL(k_uvbd_fit<true>, dim3((unsigned)k), dim3(pl.threads), pl.lds_bytes, 0, A);
+  } else {
+    hipLaunchKernelGGL(k_uvbd_fit<false>, dim3((unsigned)k), dim3(pl.threads), pl.lds_bytes, 0, A);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(b_out, bd, sizeof(double) * nq * nk, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(res.data(), resd, sizeof(double) * nk * UVBD_NRES, hipMemcpyDeviceToHost));
+  for (int64_t t = 0; t < k; ++t) {
+    const double *rt = res.data() + (size_t)t * UVBD_NRES;
+    const bool none = tr[(size_t)t].nt == 0.0, noVar = variant == BWGR_UVB_X;
+    if (mu_out) mu_out[t] = none ? 0.0 : rt[0];
+    if (h2_out) h2_out[t] = none ? 0.0 : (noVar ? NAN : 1.0 - rt[1] / tr[(size_t)t].vy);                  // :1802
+    if (ve_out) ve_out[t] = (none || noVar) ? NAN : rt[1];
+    if (vb_out) vb_out[t] = (none || noVar) ? NAN : rt[2];
+    if (cnv_out) cnv_out[t] = rt[3];
+    its_out[t] = (int)rt[4];
+  }
+  return BWGR_OK;
+}
+
+// out = X B on the raw int8 genotypes, every row: k_pxb over (row tiles, marker chunks, 16-trait slices), then the chunks' partials in order.
+// The chunks: as many as bring the grid to about four workgroups per compute unit, at most 64 and never shorter than one staged tile of B.
+extern "C" int bwgr_panel_xb(bwgr_panel *P, const double *B, int64_t k, double *out) {
+  if (!P || !B || !out) return fail(BWGR_EINVAL, "panel_xb: null pointer");
+  if (k < 1 || k > 0x7FFFFFFFll) return fail(BWGR_EINVAL, "panel_xb: k = %lld columns (at least 1)", (long long)k);
+  if (P->data->is_f32) return fail(BWGR_EINVAL, "panel_xb: the panel holds fp32 genotypes; panel_xb takes int8 panels only");
+  HIPCHK(hipSetDevice(P->data->device));
+  const int64_t n = P->data->n, p = P->data->p, ld = P->data->plan.ld;
+  const int R = P->data->plan.R;
+  const int64_t tiles = (ld + PXB_ROWS - 1) / PXB_ROWS, slices = (k + PXB_TS - 1) / PXB_TS;
+  if (slices > 65535) return fail(BWGR_EINVAL, "panel_xb: k = %lld columns (at most %d per call)", (long long)k, 65535 * PXB_TS);
+  int64_t chunks = std::min<int64_t>(std::min<int64_t>(64, (p + PXB_MT - 1) / PXB_MT), std::max<int64_t>(1, (1024 + tiles * slices - 1) / (tiles * slices)));
+  const int64_t chunk = ((p + chunks - 1) / chunks + PXB_MT - 1) / PXB_MT * PXB_MT;
+  chunks = (p + chunk - 1) / chunk;
+  hipStream_t st = P->stream;
+  DevBufs bufs(st);
+  const size_t nk = (size_t)n * (size_t)k;
+  double *Bd = bufs.get<double>((size_t)p * (size_t)k), *part = bufs.get<double>((size_t)chunks * nk), *outd = bufs.get<double>(nk);
+  if (!Bd || !part || !outd) return fail(BWGR_ENOMEM, "panel_xb: device allocation failed");
+  HIPCHK(hipMemcpyAsync(Bd, B, sizeof(double) * (size_t)p * (size_t)k, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_pxb, dim3((unsigned)tiles, (unsigned)chunks, (unsigned)slices), dim3(256), 0, st, (const int8_t *)P->data->X, R, p, ld, n, (const double *)Bd, (int)k,
+                     chunk, part);
+  hipLaunchKernelGGL(k_pxb_finish, dim3((unsigned)std::min<int64_t>(((int64_t)nk + 255) / 256, 4096)), dim3(256), 0, st, (const double *)part, (int64_t)nk, (int)chunks, outd);
+  HIPCHK(hipGetLastError());
+  HIPCHK(d2h(st, out, outd, sizeof(double) * nk));
   return BWGR_OK;
 }
 

@@ -297,7 +297,7 @@ int bwgr_debug_mrr_plan(int k, int npat, int *linv_lds, int *ngl, int64_t *solve
  * stopped trait's state is not touched again.  tol = 0 never stops early; maxit = 0 returns b = 0.
  * Outputs (host; only b and its are required): b[p x k] column-major, mu[k], h2[k] (1 - ve / vy), ve[k], vb[k], its[k] (sweeps each trait
  * ran), cnv[k] (each trait's last convergence value), xb[n x k] = X b on the raw genotypes for every row, the unobserved ones included (what
- * GSEM / XSEMF / ZSEMF form next, :1586, :1758, :1822).  A trait with no observed row gives a zero column of b, its = 0, mu = h2 = 0 and NaN
+ * GSEM / XSEMF / ZSEMF form next, :1586, :1758, :1822; bwgr_panel_xb forms it for any B).  A trait with no observed row gives a zero column of b, its = 0, mu = h2 = 0 and NaN
  * elsewhere, for every variant (XFUVBETA has no such test and would return NaN there).  A panel switched to implicit centring gives
  * bit-identical results (the fit reads the raw genotypes and centres per trait).
  * BWGR_EINVAL: an fp32 panel, an unknown variant, maxit < 0, k < 1, a trait with exactly one observed row (the reference divides by n - 1;
@@ -307,8 +307,8 @@ int bwgr_debug_mrr_plan(int k, int npat, int *linv_lds, int *ngl, int64_t *solve
  * whose markers are all monomorphic on its rows has TrXSX = 0, hence vb = inf and lambda = 0: every marker takes the XX_j = 0 path and b stays
  * 0 (the reference's D and Z give 0 / 0 = NaN there).  For BWGR_UVB_X with TrXSX = 0 the library likewise returns b = 0 where the reference
  * returns NaN.  Neither affects the other traits of the call.
- * Not here: MEGA, GSEM, XSEMF, ZSEMF, YSEMF (their second stage fits on a dense latent matrix, which needs non-int8 panels); solver2x /
- * solver2xF (two panels); fp32 panels; groups of traits sharded over GPUs. */
+ * Not here: MEGA, GSEM, solver2x / solver2xF (two designs inside one sweep, each with its own lambda); fp32 panels; groups of traits sharded
+ * over GPUs.  XSEMF, ZSEMF and YSEMF are compositions of this entry, bwgr_uvbeta_dense and bwgr_panel_xb (below) made by the host layers. */
 enum { BWGR_UVB_D = 0 /* solver1x  / UVBETA   */, BWGR_UVB_F = 1 /* solver1xF / FUVBETA  */,
        BWGR_UVB_X = 2 /* xsolver1xF/ XFUVBETA */, BWGR_UVB_Z = 3 /* zsolver1xF/ ZFUVBETA */ };
 int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int variant, int maxit, double tol, double df0,
@@ -322,6 +322,27 @@ int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int variant, int maxi
  * requested). */
 #define BWGR_UVB_PLAN_NOUT 8
 int bwgr_debug_uvb_plan(int64_t n, int64_t p, int64_t k, int64_t out[BWGR_UVB_PLAN_NOUT]);
+/* ---- the same fits on a small dense design, and X B on the panel: what XSEMF / ZSEMF / YSEMF are made of ---------------
+ * SEXP XSEMF(Y,X,npc) src/RcppEigen20230423.cpp:1756-1769, ZSEMF :1819-1845, YSEMF :1848-1874 (R/RcppExports.R:232, 240, 244) fit every trait on the
+ * panel (XFUVBETA / ZFUVBETA), form G = X BETA, take its thin SVD, fit every trait again on the latent design Z = (U diag(s)).leftCols(npc) and
+ * map the coefficients back.  The SVD of the n x k matrix stays with the caller (the host layers: bwgr_amd.XSEMF ..., rshim/bwgr_hip.R).
+ * bwgr_uvbeta_dense: bwgr_uvbeta's fits, all four variants and every rule of the comment above (own observed rows, own column means over them,
+ * tilde on the raw columns, per-trait stopping with stopped traits left alone, tol = 0, maxit = 0, all-NaN traits, F's test XX_j > 1e-5 and
+ * b_j = 0 where XX_j == 0 otherwise, the marker orders of bwgr_em_order(q, s)), on a dense design Z of n x q doubles, column-major with leading
+ * dimension ldz, q small (npc <= k there; any q >= 1 is taken).  One workgroup per trait runs the trait's whole fit in one launch.  Y: n x k
+ * column-major, NaN = missing.  Outputs as bwgr_uvbeta's (b is q x k; only b and its are required).  BWGR_EINVAL: a null pointer, n < 1,
+ * q < 1, ldz < n, k < 1, an unknown variant, maxit < 0, a trait with exactly one observed row, an entry of Z that is not finite. */
+int bwgr_uvbeta_dense(int device, const double *Z, int64_t n, int64_t q, int64_t ldz, const double *Y, int64_t k, int variant, int maxit,
+                      double tol, double df0, double *b /* q x k */, double *mu, double *h2, double *ve, double *vb, int *its, double *cnv);
+/* host arithmetic of bwgr_uvbeta_dense's plan (needs no GPU; n, q, k at least 1, else BWGR_EINVAL): out[0..4] = lds_rows (the largest n whose
+ * residual stays in the workgroup's LDS), e_in_lds (1: n <= lds_rows; 0: the residuals live in a global workspace of n x k doubles), threads
+ * per workgroup, dynamic LDS bytes, bytes of that workspace (0 when e is in LDS). */
+#define BWGR_UVBD_PLAN_NOUT 5
+int bwgr_debug_uvbd_plan(int64_t n, int64_t q, int64_t k, int64_t out[BWGR_UVBD_PLAN_NOUT]);
+/* out (n x k, host, column-major) = X B on the raw int8 genotypes for every row; B: p x k, host, column-major.  fp64 sums; the markers are
+ * split over workgroups and the partial sums added in a fixed order, so two calls give the same bits, and so does a panel switched to implicit
+ * centring.  BWGR_EINVAL: a null pointer, k < 1, an fp32 panel.  (bwgr_uvbeta's own xb output is a different summation order.) */
+int bwgr_panel_xb(bwgr_panel *P, const double *B, int64_t k, double *out /* n x k */);
 /* host arithmetic of a panel's plan (needs no GPU): what bwgr_panel_create would decide for an int8 (is_f32 = 0) or float panel of n x p
  * with these block / nwg arguments under the BWGR_* switches of the environment; kind 0: a main panel, 1: the row-subset scratch panel of
  * KMUP2 and wgr's bagging, 2: bwgr_em's scratch panel.  A shape bwgr_panel_create refuses returns its code and leaves its message in

@@ -90,6 +90,49 @@ UVBETA <- function(Y, X) .Call("bwgrhip_UVBETA", as.matrix(Y) * 1.0, .bwgr_ipane
 FUVBETA <- function(Y, X) .Call("bwgrhip_UVBETA", .bwgr_f32(as.matrix(Y)), .bwgr_ipanel(X), 1L)
 XFUVBETA <- function(Y, X) .Call("bwgrhip_UVBETA", .bwgr_f32(as.matrix(Y)), .bwgr_ipanel(X), 2L)
 ZFUVBETA <- function(Y, X) .Call("bwgrhip_UVBETA", .bwgr_f32(as.matrix(Y)), .bwgr_ipanel(X), 3L)
+# latent-space fits, R/RcppExports.R:232, 240, 244 (XSEMF, ZSEMF, YSEMF; src/RcppEigen20230423.cpp:1756-1769, :1819-1874): same names, argument
+# order, defaults and return lists.  Composed from the per-trait fits on the panel, X %*% B on the panel, base R's svd() of the n x k matrix
+# G and the per-trait fits on the dense latent design.  Y is rounded to float once; everything after runs on unrounded doubles (the reference
+# computes in float throughout).  The results do not depend on the signs svd() gives the singular pairs.
+.bwgr_uvb <- function(Y, P, variant) {      # list(b, mu, h2) of the panel fit
+  r <- .Call("bwgrhip_UVBETA", Y, P, variant)
+  if (variant == 3L) list(b = r[-(1:2), , drop = FALSE], mu = r[2, ], h2 = r[1, ]) else list(b = r)
+}
+.bwgr_uvbd <- function(Y, Z, variant) .Call("bwgrhip_uvbeta_dense", Y, Z, variant, 100L, .bwgr_f32(10e-7), .bwgr_f32(20.0))
+.bwgr_xb <- function(P, B) .Call("bwgrhip_panel_xb", P, B * 1.0)
+.bwgr_latent <- function(G, npc) {          # Z = (U diag(s)).leftCols(npc), V.leftCols(npc), :1759-1762
+  s <- svd(G); m <- length(s$d)
+  if (npc < 0) npc <- floor(2 * sqrt(m) + 0.5)
+  if (npc == 0) npc <- m
+  if (npc > m) stop("npc exceeds min(nrow(Y), ncol(Y))")
+  i <- seq_len(npc)
+  list(Z = s$u[, i, drop = FALSE] %*% diag(s$d[i], npc), V = s$v[, i, drop = FALSE])
+}
+.bwgr_gc <- function(G) {                   # :1765-1768: list(hat = standardised columns, GC)
+  G <- sweep(G, 2, colMeans(G)); G <- sweep(G, 2, sqrt(colSums(G^2) / nrow(G)), "/")
+  list(hat = G, GC = crossprod(G) / nrow(G))
+}
+.bwgr_sem <- function(Y, X, npc, variant) {
+  P <- .bwgr_ipanel(X); Y <- .bwgr_f32(as.matrix(Y))
+  s1 <- .bwgr_uvb(Y, P, variant)
+  L <- .bwgr_latent(.bwgr_xb(P, s1$b), npc)
+  s2 <- .bwgr_uvbd(Y, L$Z, variant)
+  list(P = P, Y = Y, s2 = s2, b = s1$b %*% (L$V %*% s2$b))
+}
+XSEMF <- function(Y, X, npc = 0L) {
+  f <- .bwgr_sem(Y, X, npc, 2L); g <- .bwgr_gc(.bwgr_xb(f$P, f$b))
+  list(b = f$b, GC = g$GC, hat = g$hat)
+}
+ZSEMF <- function(Y, X, npc = 0L) {
+  f <- .bwgr_sem(Y, X, npc, 3L); G <- .bwgr_xb(f$P, f$b)
+  list(mu = f$s2$mu, b = f$b, hat = sweep(G, 2, f$s2$mu, "+"), h2 = f$s2$h2, GC = .bwgr_gc(G)$GC)
+}
+YSEMF <- function(Y, X, npc = -1L) {
+  f <- .bwgr_sem(Y, X, npc, 3L)
+  s3 <- .bwgr_uvb(f$Y - .bwgr_xb(f$P, f$b), f$P, 3L)
+  b <- f$b + s3$b; G <- .bwgr_xb(f$P, b)
+  list(mu = s3$mu, b = b, hat = sweep(G, 2, s3$mu, "+"), h2 = f$s2$h2 + s3$h2, GC = .bwgr_gc(G)$GC)
+}
 # relationship kernels, R/RcppExports.R:100-106 (GAU, GRM) and :140-150 (EigenARC, EigenGAU, EigenGRM): same names, argument order and defaults;
 # integer genotypes only (an int8 panel); `cores` is ignored.  Their result feeds wgr(eigK = eigen(K)).
 # (a numeric matrix of whole numbers is staged as integers, so that it becomes an int8 panel)

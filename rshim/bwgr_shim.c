@@ -342,6 +342,36 @@ SEXP bwgrhip_UVBETA(SEXP Y, SEXP panel, SEXP variant) {
   return out;
 }
 
+/* the pieces of XSEMF / ZSEMF / YSEMF(Y, X, npc) src/RcppEigen20230423.cpp:1756-1769, :1819-1874, which bwgr_hip.R composes with base R's svd():
+ * the per-trait fits on a dense latent design Z (n x q numeric) -> list(b = q x k, mu, h2), and X %*% B on the panel's integer genotypes.
+ * variant: BWGR_UVB_*; Y: NA = missing, already float-rounded by the R front-end (once: the later stages run on unrounded doubles). */
+SEXP bwgrhip_uvbeta_dense(SEXP Y, SEXP Z, SEXP variant, SEXP maxit, SEXP tol, SEXP df0) {
+  SEXP dz = Rf_getAttrib(Z, R_DimSymbol), dy = Rf_getAttrib(Y, R_DimSymbol);
+  if (Rf_length(dz) != 2 || Rf_length(dy) != 2 || INTEGER(dy)[0] != INTEGER(dz)[0]) Rf_error("Y and Z must be matrices with the same number of rows");
+  const int n = INTEGER(dz)[0], q = INTEGER(dz)[1], k = INTEGER(dy)[1];
+  SEXP b = PROTECT(Rf_allocMatrix(REALSXP, q, k)), mu = PROTECT(Rf_allocVector(REALSXP, k)), h2 = PROTECT(Rf_allocVector(REALSXP, k));
+  int *its = (int *)R_alloc(k > 0 ? k : 1, sizeof(int));
+  chk(bwgr_uvbeta_dense(0, REAL(Z), (int64_t)n, (int64_t)q, (int64_t)n, REAL(Y), (int64_t)k, Rf_asInteger(variant), Rf_asInteger(maxit), Rf_asReal(tol),
+                        Rf_asReal(df0), REAL(b), REAL(mu), REAL(h2), NULL, NULL, its, NULL));
+  const char *nm[] = {"b", "mu", "h2"};
+  SEXP out = PROTECT(named_list(3, nm));
+  SET_VECTOR_ELT(out, 0, b); SET_VECTOR_ELT(out, 1, mu); SET_VECTOR_ELT(out, 2, h2);
+  UNPROTECT(4);
+  return out;
+}
+SEXP bwgrhip_panel_xb(SEXP panel, SEXP B) {
+  bwgr_panel *P = panel_of(panel);
+  int64_t info[8]; chk(bwgr_panel_info(P, info));
+  const R_xlen_t n = info[0], p = info[1];
+  SEXP dim = Rf_getAttrib(B, R_DimSymbol);
+  if (Rf_length(dim) != 2 || INTEGER(dim)[0] != p) Rf_error("B must be a matrix with ncol(X) rows");
+  const int k = INTEGER(dim)[1];
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, (int)n, k));
+  chk(bwgr_panel_xb(P, REAL(B), (int64_t)k, REAL(out)));
+  UNPROTECT(1);
+  return out;
+}
+
 /* relationship kernels: GRM(X, Code012) / GAU(X) src/Rcpp20260726ai.cpp:1338-1383, EigenARC / EigenGAU / EigenGRM(X, ., cores)
  * src/RcppEigen20230423.cpp:8-51 -> an n x n numeric matrix.  kind: BWGR_K_*; par: phi; flag: Code012 / centralizeZ / centralizeX. */
 SEXP bwgrhip_kernel(SEXP panel, SEXP kind, SEXP par, SEXP flag) {
@@ -372,6 +402,7 @@ static const R_CallMethodDef CallEntries[] = {   /* as src/RcppExports.cpp:1152-
   {"bwgrhip_wgr", (DL_FUNC)&bwgrhip_wgr, 14}, {"bwgrhip_em", (DL_FUNC)&bwgrhip_em, 7},
   {"bwgrhip_MRR3", (DL_FUNC)&bwgrhip_MRR3, 3}, {"bwgrhip_MRR3F", (DL_FUNC)&bwgrhip_MRR3F, 3},
   {"bwgrhip_solver1x", (DL_FUNC)&bwgrhip_solver1x, 6}, {"bwgrhip_UVBETA", (DL_FUNC)&bwgrhip_UVBETA, 3},
+  {"bwgrhip_uvbeta_dense", (DL_FUNC)&bwgrhip_uvbeta_dense, 6}, {"bwgrhip_panel_xb", (DL_FUNC)&bwgrhip_panel_xb, 2},
   {"bwgrhip_kernel", (DL_FUNC)&bwgrhip_kernel, 4}, {"bwgrhip_crossprod", (DL_FUNC)&bwgrhip_crossprod, 1}, {NULL, NULL, 0}};
 
 void R_init_bwgrhip(DllInfo *dll) {              /* as R_init_bWGR, src/RcppExports.cpp:1230-1233 */
