@@ -94,6 +94,7 @@ def lib():
     L.bwgr_debug_withhold.argtypes = [vp, i32]
     L.bwgr_debug_last_redo.argtypes = [C.POINTER(i32)]
     L.bwgr_debug_live.argtypes = [C.POINTER(i64)]
+    L.bwgr_debug_launch_plan.argtypes = [i64, i64, i64, i64, C.POINTER(i64)]
     L.bwgr_group_create.argtypes = [C.POINTER(vp), i32, C.POINTER(i32), vp, i32, i64, i64, i64, i32, c_f, i32, f32, f32, f32, f32, f32, u64, i32, i64]
     L.bwgr_group_create_centred.argtypes = list(L.bwgr_group_create.argtypes) + [i32]
     L.bwgr_group_run.argtypes = [vp, i32]
@@ -123,5 +124,5 @@ EXPORTS = ["bwgr_abi_version", "bwgr_last_error", "bwgr_device_count", "bwgr_pan
            "bwgr_chain_create_sharded", "bwgr_chain_sweep_blocks", "bwgr_chain_round_sweep", "bwgr_chain_round_apply", "bwgr_chain_get_sums_dev", "bwgr_chain_end_iteration_dev", "bwgr_chain_get_sums", "bwgr_chain_end_iteration",
            "bwgr_chain_destroy", "bwgr_chain_run", "bwgr_chain_run_pair", "bwgr_chain_sync", "bwgr_chain_iterations", "bwgr_chain_result",
            "bwgr_chain_state", "bwgr_chain_sweep_ms", "bwgr_chain_redo_count", "bwgr_group_sound", "bwgr_panel_centred", "bwgr_panel_set_centred", "bwgr_bayes", "bwgr_bayes2", "bwgr_wgr", "bwgr_wgr_ex", "bwgr_synth_genotypes",
-           "bwgr_debug_variates", "bwgr_debug_withhold", "bwgr_debug_last_redo", "bwgr_debug_live", "bwgr_sample_rows", "bwgr_group_create", "bwgr_group_create_centred", "bwgr_group_run", "bwgr_group_sync",
+           "bwgr_debug_variates", "bwgr_debug_withhold", "bwgr_debug_last_redo", "bwgr_debug_live", "bwgr_debug_launch_plan", "bwgr_sample_rows", "bwgr_group_create", "bwgr_group_create_centred", "bwgr_group_run", "bwgr_group_sync",
            "bwgr_group_info", "bwgr_group_result", "bwgr_group_destroy"]

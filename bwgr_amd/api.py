@@ -201,16 +201,19 @@ class Chain:
     """One MCMC chain of a fused sampler, stepping interface over bwgr_chain_* (state stays on the GPU)."""
 
     def __init__(self, panel, model, y, it=1500, bi=500, pi=0.95, df=5.0, R2=0.5, seed=None, rng_mode=0, shard=None,
-                 e_ext=None):
+                 e_ext=None, wait_for_y=True):
         """shard = (marker0, p_total, MSx_total) makes this the chain of one marker shard (bwgr_chain_create_sharded);
-        e_ext = a torch float64 CUDA tensor of panel.ld entries that will hold the (replicated) residual."""
+        e_ext = a torch float64 CUDA tensor of panel.ld entries that will hold the (replicated) residual.  A device y is waited for
+        (the whole device) before the library copies it; wait_for_y=False leaves that out for a caller who wrote y on the panel's
+        own stream (Panel.set_stream), where the library's copy is ordered behind it."""
         self.panel, self.model = panel, model
         self._h = C.c_void_p()
         self.it, self.bi = int(it), int(bi)
         if hasattr(y, "data_ptr"):
             import torch
             assert y.is_cuda and y.dtype == torch.float32 and y.is_contiguous() and y.numel() == panel.n
-            torch.cuda.synchronize(y.device)
+            if wait_for_y:
+                torch.cuda.synchronize(y.device)
             yptr, loc = C.c_void_p(y.data_ptr()), DEVICE
         else:
             self._y = np.ascontiguousarray(y, np.float32)

@@ -3815,6 +3815,12 @@ extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float
 // as the rest of the budget holds (ngl); it reads patterns ngl.. from global memory, and without linv_lds fetches each marker's row of
 // its inverse one marker ahead.  bwgr_debug_mrr_plan exposes it to the CPU tests.
 static constexpr size_t MRR_LDS_MAX = 160 * 1024;
+static constexpr int MRR_NP = 64;             // workgroups (= partials) of the tail reductions k_mrr_ey and k_mrr_tilde, 256 rows or markers each per trip
+static constexpr int MRR_SETUP_WG = 8192;     // workgroups of k_mrr_setup_cols at most, four markers (one per wave) each per trip
+static constexpr int TAIL_THREADS = 256;      // threads per workgroup of the tail, product and finish kernels of the fp64 families
+// the grids the launch sites below and bwgr_debug_launch_plan share
+static inline int64_t mrr_setup_grid(int64_t p) { return std::min<int64_t>((p + 3) / 4, MRR_SETUP_WG); }
+static inline int64_t mrr_pass_grid(int64_t ld) { return std::min<int64_t>(ld / 64, MRR_PASS_WG); }
 struct MrrPlan { int linv_lds, ngl; size_t lds_solve, lds_linv; };
 static MrrPlan mrr_plan(int k, int npat) {
   MrrPlan pl;
@@ -3908,9 +3914,9 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   std::vector<int> order((size_t)p);
   std::vector<double> iG((size_t)k * k, 0.0), d(k), off(k);   // (these four are copied from asynchronously: declared before the holder, which waits for the stream)
   DevBufs bufs(st);
-  const int64_t nblk = (p + MRR_MB - 1) / MRR_MB, ntiles = ld / 64;
-  const int G = (int)std::min<int64_t>(ntiles, MRR_PASS_WG);
-  const int NP = 64;                                   // partials of the tail reductions
+  const int64_t nblk = (p + MRR_MB - 1) / MRR_MB;
+  const int G = (int)mrr_pass_grid(ld);
+  const int NP = MRR_NP;                               // partials of the tail reductions
   const int nch = (int)std::min<int64_t>(64, p);       // marker chunks of the fitted values
   const int64_t cpc = (p + nch - 1) / nch;
   const size_t np = (size_t)p, nl = (size_t)ld, pk = np * k;
@@ -3934,7 +3940,7 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   HIPCHK(hipMemsetAsync(bd, 0, sizeof(double) * p * k, st));                                       // b = 0, :823
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_linv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
-  hipLaunchKernelGGL(k_mrr_setup_cols, dim3((unsigned)std::min<int64_t>((p + 3) / 4, 8192)), dim3(256), 0, st, (const int8_t *)P->data->X, R, (int)n, p, ld,
+  hipLaunchKernelGGL(k_mrr_setup_cols, dim3((unsigned)mrr_setup_grid(p)), dim3(TAIL_THREADS), 0, st, (const int8_t *)P->data->X, R, (int)n, p, ld,
                      (const uint32_t *)zbd, (const double *)yd, (const double *)sumyd, mc, xbar, Sd, XXd, XSXd, tilde);
   HIPCHK(hipGetLastError());
   // a reduction over p of the k^2 (+k) products, partials in a fixed order
@@ -4082,6 +4088,10 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
 // ------------------------------------------------------------------------------------------------
 // The plan, decided here and nowhere else (bwgr_debug_uvb_plan exposes it to the CPU tests): the groups, the solve's LDS (as many of a
 // solve workgroup's Gram matrices as fit beside u), the pass's grid, and the element counts of the call's device arrays.
+static constexpr int UVB_SHIFT_WG = 1024;     // workgroups of k_uvb_mu_shift per trait at most, 256 rows each per trip
+static inline int64_t uvb_pass_grid(int64_t ld) { return std::min<int64_t>(ld / 64, UVB_PASS_WG); }
+static inline int64_t uvb_shift_grid(int64_t n) { return std::min<int64_t>((n + TAIL_THREADS - 1) / TAIL_THREADS, UVB_SHIFT_WG); }
+static inline int64_t uvb_xb_grid(int64_t n) { return (n + TAIL_THREADS - 1) / TAIL_THREADS; }
 struct UvbPlan {
   int64_t groups, nblk, kpad; int ngl, G, nsolve; size_t lds_solve, lds_pass;
   size_t x_bytes, n_gram, n_zm, n_rows, n_cols, n_part, n_dB, n_tpart, n_res, n_slot, n_bout, n_xb;   // element counts
@@ -4097,7 +4107,7 @@ static UvbPlan uvb_plan(int64_t n, int64_t ld, int64_t p, int64_t k, size_t x_by
   pl.nsolve = UVB_W / UVB_ST;
   pl.ngl = (int)std::min<size_t>((size_t)UVB_ST, (MRR_LDS_MAX - uvb_solve_lds(0)) / ((size_t)UVB_GSTR * 4));
   pl.lds_solve = uvb_solve_lds(pl.ngl); pl.lds_pass = UVB_PASS_LDS;
-  pl.G = (int)std::min<int64_t>(ld / 64, UVB_PASS_WG);
+  pl.G = (int)uvb_pass_grid(ld);
   pl.x_bytes = x_bytes;
   pl.n_gram = (size_t)pl.nblk * (size_t)npat_max * MRR_MB * MRR_MB;      // int32: one group's block Gram matrices, rebuilt per sweep and group
   pl.n_zm = (size_t)npat_total * ld;                                      // bytes: the row masks k_mrr_gram ANDs with
@@ -4330,7 +4340,7 @@ extern "C" int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int varian
       unsigned long long ran = 0;
       for (int tl = 0; tl < UVB_W; ++tl) if (tr[(size_t)(g * UVB_W + tl)].active) ran |= 1ull << tl;   // (tr.active still says who ran this sweep)
       if (!ran) continue;
-      hipLaunchKernelGGL(k_uvb_mu_shift, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024), UVB_W), dim3(256), 0, st, ed + (size_t)g * UVB_W * nl,
+      hipLaunchKernelGGL(k_uvb_mu_shift, dim3((unsigned)uvb_shift_grid(n), UVB_W), dim3(TAIL_THREADS), 0, st, ed + (size_t)g * UVB_W * nl,
                          (const unsigned long long *)(zbd + (size_t)g * nl), ld, (int)n, ran, (const double *)(mu0d + g * UVB_W));
     }
     HIPCHK(hipGetLastError());
@@ -4342,7 +4352,7 @@ extern "C" int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int varian
     const size_t oc = (size_t)g * UVB_W * np;
     hipLaunchKernelGGL(k_uvb_b_out, dim3((unsigned)std::min<int64_t>((p * kg + 255) / 256, 4096)), dim3(256), 0, st, (const double *)(bd + oc), p, kg, bout + (size_t)g * UVB_W * np);
     if (xb_out)
-      hipLaunchKernelGGL(k_uvb_xb, dim3((unsigned)((n + 255) / 256), (unsigned)((kg + 15) / 16)), dim3(256), 0, st, (const int8_t *)P->data->X, R, p, (int)n, (const double *)(bd + oc), kg,
+      hipLaunchKernelGGL(k_uvb_xb, dim3((unsigned)uvb_xb_grid(n), (unsigned)((kg + 15) / 16)), dim3(TAIL_THREADS), 0, st, (const int8_t *)P->data->X, R, p, (int)n, (const double *)(bd + oc), kg,
                          xbd + (size_t)g * UVB_W * n);
   }
   HIPCHK(hipGetLastError());
@@ -4473,6 +4483,18 @@ extern "C" int bwgr_uvbeta_dense(int device, const double *Z, int64_t n, int64_t
 
 // out = X B on the raw int8 genotypes, every row: k_pxb over (row tiles, marker chunks, 16-trait slices), then the chunks' partials in order.
 // The chunks: as many as bring the grid to about four workgroups per compute unit, at most 64 and never shorter than one staged tile of B.
+static constexpr int PXB_CHUNKS_MAX = 64;     // marker chunks at most (before the chunk is rounded up to whole staged tiles of B)
+static constexpr int PXB_FINISH_WG = 4096;    // workgroups of k_pxb_finish at most, 256 entries each per trip
+static inline int64_t pxb_finish_grid(int64_t nk) { return std::min<int64_t>((nk + TAIL_THREADS - 1) / TAIL_THREADS, PXB_FINISH_WG); }
+struct PxbPlan { int64_t tiles, slices, chunks, chunk; };
+static PxbPlan pxb_plan(int64_t ld, int64_t p, int64_t k) {
+  PxbPlan pl;
+  pl.tiles = (ld + PXB_ROWS - 1) / PXB_ROWS; pl.slices = (k + PXB_TS - 1) / PXB_TS;
+  pl.chunks = std::min<int64_t>(std::min<int64_t>(PXB_CHUNKS_MAX, (p + PXB_MT - 1) / PXB_MT), std::max<int64_t>(1, (1024 + pl.tiles * pl.slices - 1) / (pl.tiles * pl.slices)));
+  pl.chunk = ((p + pl.chunks - 1) / pl.chunks + PXB_MT - 1) / PXB_MT * PXB_MT;
+  pl.chunks = (p + pl.chunk - 1) / pl.chunk;
+  return pl;
+}
 extern "C" int bwgr_panel_xb(bwgr_panel *P, const double *B, int64_t k, double *out) {
   if (!P || !B || !out) return fail(BWGR_EINVAL, "panel_xb: null pointer");
   if (k < 1 || k > 0x7FFFFFFFll) return fail(BWGR_EINVAL, "panel_xb: k = %lld columns (at least 1)", (long long)k);
@@ -4480,11 +4502,9 @@ extern "C" int bwgr_panel_xb(bwgr_panel *P, const double *B, int64_t k, double *
   HIPCHK(hipSetDevice(P->data->device));
   const int64_t n = P->data->n, p = P->data->p, ld = P->data->plan.ld;
   const int R = P->data->plan.R;
-  const int64_t tiles = (ld + PXB_ROWS - 1) / PXB_ROWS, slices = (k + PXB_TS - 1) / PXB_TS;
+  const PxbPlan xp = pxb_plan(ld, p, k);
+  const int64_t tiles = xp.tiles, slices = xp.slices, chunks = xp.chunks, chunk = xp.chunk;
   if (slices > 65535) return fail(BWGR_EINVAL, "panel_xb: k = %lld columns (at most %d per call)", (long long)k, 65535 * PXB_TS);
-  int64_t chunks = std::min<int64_t>(std::min<int64_t>(64, (p + PXB_MT - 1) / PXB_MT), std::max<int64_t>(1, (1024 + tiles * slices - 1) / (tiles * slices)));
-  const int64_t chunk = ((p + chunks - 1) / chunks + PXB_MT - 1) / PXB_MT * PXB_MT;
-  chunks = (p + chunk - 1) / chunk;
   hipStream_t st = P->stream;
   DevBufs bufs(st);
   const size_t nk = (size_t)n * (size_t)k;
@@ -4493,7 +4513,7 @@ extern "C" int bwgr_panel_xb(bwgr_panel *P, const double *B, int64_t k, double *
   HIPCHK(hipMemcpyAsync(Bd, B, sizeof(double) * (size_t)p * (size_t)k, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_pxb, dim3((unsigned)tiles, (unsigned)chunks, (unsigned)slices), dim3(256), 0, st, (const int8_t *)P->data->X, R, p, ld, n, (const double *)Bd, (int)k,
                      chunk, part);
-  hipLaunchKernelGGL(k_pxb_finish, dim3((unsigned)std::min<int64_t>(((int64_t)nk + 255) / 256, 4096)), dim3(256), 0, st, (const double *)part, (int64_t)nk, (int)chunks, outd);
+  hipLaunchKernelGGL(k_pxb_finish, dim3((unsigned)pxb_finish_grid((int64_t)nk)), dim3(TAIL_THREADS), 0, st, (const double *)part, (int64_t)nk, (int)chunks, outd);
   HIPCHK(hipGetLastError());
   HIPCHK(d2h(st, out, outd, sizeof(double) * nk));
   return BWGR_OK;
@@ -4514,6 +4534,8 @@ struct XxtPlan {
   size_t ws_bytes = 0;              // device temporaries of a kernel call with a host output: the n x n array, s, q, X s, the diagonal, the partial sums
 };
 static constexpr int XXT_SUMD_PARTS = 1024;
+static constexpr int XXT_ZERO_WG = 2048;      // workgroups of k_xxt_zero, 256 entries each per trip
+static constexpr int KFIN_APPLY_WG = 4096;    // workgroups of k_kfin_apply, 256 entries each per trip
 static int plan_xxt(XxtPlan &pl, int64_t n, int64_t p, int xmax, int64_t kchunk) {
   pl = XxtPlan();
   CHK(panel_range(n, p));
@@ -4577,7 +4599,7 @@ static int xxt_product(bwgr_panel *P, const XxtPlan &pl, long long *Gd, int64_t 
   XxtArgs a;
   a.X = (const int8_t *)D->X; a.p = D->p; a.R = D->plan.R; a.n = (int)D->n; a.T = (int)pl.T; a.chunk = pl.chunk; a.piece = pl.piece;
   a.sub = (int)pl.sub; a.accumulate = pl.accumulate ? 1 : 0; a.G = Gd; a.ldg = ldg;
-  if (pl.accumulate) hipLaunchKernelGGL(k_xxt_zero, dim3(2048), dim3(256), 0, st, Gd, ldg, (int)D->n);
+  if (pl.accumulate) hipLaunchKernelGGL(k_xxt_zero, dim3(XXT_ZERO_WG), dim3(TAIL_THREADS), 0, st, Gd, ldg, (int)D->n);
   hipLaunchKernelGGL(k_xxt_mfma_i8, dim3((unsigned)pl.tiles, (unsigned)(pl.nchunks * pl.sub)), dim3(256), 0, st, a);
   const unsigned t32 = (unsigned)((D->n + 31) / 32);
   hipLaunchKernelGGL(k_xxt_mirror, dim3(t32, t32), dim3(32, 8), 0, st, Gd, ldg, (int)D->n);
@@ -4670,7 +4692,7 @@ extern "C" int bwgr_panel_kernel(bwgr_panel *P, int kind, double par, int flag, 
       a.scale = par * (-(nd * (nd - 1.0))) / sumd;
     }
   }
-  hipLaunchKernelGGL(k_kfin_apply, dim3(4096), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_kfin_apply, dim3(KFIN_APPLY_WG), dim3(TAIL_THREADS), 0, st, a);
   HIPCHK(hipGetLastError());
   if (memloc == BWGR_HOST) return xxt_to_host(st, K, ldk, Gd, n);
   HIPCHK(hipStreamSynchronize(st));
@@ -4687,6 +4709,22 @@ extern "C" int bwgr_synth_genotypes(void *Xdev, int64_t n, int64_t p, int64_t ld
   hipLaunchKernelGGL(k_synth, dim3(8192), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), (int8_t *)Xdev, ldx, (int)n, p, col0,
                      (uint32_t)seed, (uint32_t)(seed >> 32), freq_dev);
   HIPCHK(hipGetLastError());
+  return BWGR_OK;
+}
+
+// The grids of the tail, product and finish kernels of the fp64 families for a panel of n rows (ld padded), p markers and k columns of B: what
+// the launch sites above use, by name, so that the tests' shape table (tests/tall_cases.py) fails when a grid changes.  Host arithmetic only.
+extern "C" int bwgr_debug_launch_plan(int64_t n, int64_t ld, int64_t p, int64_t k, int64_t out[BWGR_LAUNCH_PLAN_NOUT]) {
+  if (!out) return fail(BWGR_EINVAL, "launch plan: null pointer");
+  if (n < 1 || p < 1 || k < 1 || ld < n || ld % 128 != 0)
+    return fail(BWGR_EINVAL, "launch plan: n = %lld, ld = %lld, p = %lld, k = %lld (each at least 1, ld >= n a multiple of 128)", (long long)n, (long long)ld, (long long)p, (long long)k);
+  const PxbPlan xp = pxb_plan(ld, p, k);
+  const int64_t v[BWGR_LAUNCH_PLAN_NOUT] = {
+    MRR_NP, mrr_setup_grid(p), mrr_pass_grid(ld),
+    UVB_NP, uvb_pass_grid(ld), uvb_shift_grid(n), uvb_xb_grid(n),
+    PXB_ROWS, xp.tiles, xp.slices, xp.chunks, xp.chunk, pxb_finish_grid(n * k),
+    XXT_ZERO_WG, KFIN_APPLY_WG, TAIL_THREADS, PXB_CHUNKS_MAX, PXB_MT};
+  std::copy(v, v + BWGR_LAUNCH_PLAN_NOUT, out);
   return BWGR_OK;
 }
 

@@ -457,6 +457,19 @@ int bwgr_debug_withhold(bwgr_panel *P, int on);
 /* the sweeps that the calling thread's last bwgr_kmup / bwgr_kmup2 / bwgr_wgr / bwgr_wgr_ex call redid on the fp64 residual because they left
  * the fixed-point range of their engine: what bwgr_chain_redo_count is for a chain, for the entry points that have none. */
 int bwgr_debug_last_redo(int *count);
+/* host arithmetic of the launch grids of the fp64 families' tail, product and finish kernels (needs no GPU), in the style of
+ * bwgr_debug_panel_plan, for a panel of n rows padded to ld (a multiple of 128, ld >= n), p markers and k columns of B (each at least 1, else
+ * BWGR_EINVAL).  Every such kernel runs 256 threads per workgroup and strides over its rows, markers or entries by its grid.  out[0..2], mrr:
+ * workgroups of the tail reductions k_mrr_ey (256 rows per trip) and k_mrr_tilde (256 markers per trip); of k_mrr_setup_cols (4 markers per
+ * trip); of k_mrr_pass (one 64-row tile per trip).  out[3..6], uvbeta: workgroups of the tail reductions k_uvb_rows (256 rows per trip) and
+ * k_uvb_cols; of k_uvb_pass (one 64-row tile per trip); of k_uvb_mu_shift per trait (256 rows per trip); of k_uvb_xb along the rows.
+ * out[7..12], bwgr_panel_xb: rows per workgroup of k_pxb, then its row tiles, 16-column slices, marker chunks and markers per chunk (the last
+ * chunk takes what is left), and the workgroups of k_pxb_finish (256 entries per trip).  out[13..14], the relationship kernels: workgroups
+ * of k_xxt_zero and of k_kfin_apply (256 of the n x n entries per trip).  out[15]: the threads per workgroup of all of these.  out[16..17],
+ * the constants of bwgr_panel_xb's chunk rule: the most chunks it asks for before it rounds the chunk up to whole staged tiles of B, and the
+ * markers of such a tile. */
+#define BWGR_LAUNCH_PLAN_NOUT 18
+int bwgr_debug_launch_plan(int64_t n, int64_t ld, int64_t p, int64_t k, int64_t out[BWGR_LAUNCH_PLAN_NOUT]);
 /* the device arrays, streams and events that the library's holders (csrc/devbufs.h) own in this process right now -- every handle's and every
  * running call's: out[0..2].  What a destroyed handle or a finished call took is gone from the counts. */
 int bwgr_debug_live(int64_t out[3]);

@@ -1,0 +1,459 @@
+"""GPU: every entry point on every kind of handle -- the root panel on the default stream, a clone (its own non-blocking stream), the root on
+a caller's stream (bwgr_panel_set_stream) and the root back on the default stream -- must give the same bits, and the first must pass the
+entry's existing comparison with the oracle or its restatement.  tpod (196 x 376) and the 700 x 900 three-slab panel: size is not the point.
+
+On the default (null) stream every stray hipMemcpy, hipMemset or launch on stream 0 is ordered for free; on a non-blocking stream it is a
+race.  To make such a race lose, the caller's stream is kept busy: before each call on it a spin kernel (torch.cuda._sleep) is enqueued
+there that lasts at least five times the entry's own time on the default stream (both measured with events and printed).  Whatever the
+library issues off the caller's stream without an event dependency then runs before its inputs exist and shows as wrong bits.
+
+What this does and does not prove.  It is believed, not measured, that this runtime makes a host-to-device copy from pageable memory
+host-synchronous; if so, an entry's first such copy on the caller's stream waits for the filler, and operations mis-ordered after that copy
+are caught only by the natural durations of the work they race with.  These tests catch what runs on the null stream cannot catch at all;
+they are not a proof of ordering."""
+import functools
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kernels_restatement as KR  # noqa: E402
+import mrr_restatement as MR  # noqa: E402
+import sem_restatement as SR  # noqa: E402
+import uvb_restatement as UR  # noqa: E402
+from conftest import scaled_err  # noqa: E402
+from test_gpu_mrr import _check as _mrr_check, _traits  # noqa: E402
+from test_gpu_parity import _em_check, _rel  # noqa: E402
+from test_gpu_sem import _check as _sem_check, _strong, _well_posed  # noqa: E402
+from test_gpu_uvb import _check as _uvb_check, _slabs900  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TOL = 1e-6
+FILL = 5.0      # the filler lasts at least this many times the entry's own time
+# While ALT["on"], every entry's call runs on other inputs (another phenotype, other traits, another B).  One such call goes before the call on
+# the caller's stream: the library's freed temporaries then hold another problem's numbers, not -- from the call before -- this one's results,
+# which an operation that runs too early would otherwise find ready-made.
+ALT = {"on": False}
+
+
+def _y():
+    y = _tpod()[1]
+    return 0.5 * y + 1.0 if ALT["on"] else y
+
+
+def _Y(which):
+    Y = _slab_traits(which)
+    return np.ascontiguousarray(Y[:, ::-1]) if ALT["on"] else Y
+
+
+@functools.lru_cache(None)
+def _tpod():
+    d = np.load(os.path.join(ROOT, "tests", "golden", "tpod.npz"))
+    X = np.asfortranarray(d["gen"])
+    X.setflags(write=False)
+    return X, d["y"].astype(np.float64)
+
+
+@functools.lru_cache(None)
+def _kmup_inputs():
+    """b, d, xx, e, L of test_kmup_sweep_tpod and the rows and xx of test_kmup2_tpod"""
+    X, y = _tpod()
+    n, p = X.shape
+    rs = np.random.RandomState(5)
+    Xd = X.astype(np.float64)
+    xx = (Xd ** 2).sum(0)
+    b = rs.normal(size=p) * 0.01
+    e = y - y.mean() - Xd @ b
+    L = np.full(p, 120.0) * rs.uniform(0.5, 2.0, p)
+    use = np.sort(np.random.RandomState(9).choice(n, 120, replace=True)).astype(np.int32)
+    return dict(b=b, d=np.ones(p), xx=xx, e=e, L=L, use=use, xx2=xx * (120.0 / n))
+
+
+@functools.lru_cache(None)
+def _eigk():
+    Z = _tpod()[0].astype(np.float64); Z = Z - Z.mean(0)
+    K = Z @ Z.T; K = K / np.mean(np.diag(K))
+    w, v = np.linalg.eigh(K); o = np.argsort(-w)
+    return {"values": w[o], "vectors": v[:, o]}
+
+
+BAYES2_KW = dict(it=12, bi=3, pi=0.7, seed=21)
+
+
+@functools.lru_cache(None)
+def _x2():
+    """the second, fp32 panel's matrix of BayesB2 and the phenotype that depends on it"""
+    X, y = _tpod()
+    X2 = np.random.default_rng(5).normal(size=(X.shape[0], 90)).astype(np.float32)
+    return X2, (y + 0.7 * float(np.std(y)) * X2[:, 0]).astype(np.float32)
+
+
+@functools.lru_cache(None)
+def _slab_traits(which):
+    X = _slabs900()
+    if which == "mrr":
+        return _traits(X, 3, 0, seed=5, patterns=[0.1, 0.0, 0.25])
+    if which == "uvb":
+        return _traits(X, 5, 0, seed=5, patterns=[0.1, 0.0, 0.25, 0.05, 0.4])
+    return _strong(X, 3, seed=302)      # test_gpu_sem's: gaps 0.278 and 0.243
+
+
+# ---- the entries: (panel, call(P, aux) -> dict of arrays, check(result) against the oracle or the restatement) ----
+def _wgr_check(g, o):
+    assert scaled_err(g["b"], o["b"]) < TOL and scaled_err(g["hat"], o["hat"]) < TOL
+    assert scaled_err(np.atleast_1d(g["Vb"]), np.atleast_1d(o["Vb"])) < 5 * TOL and scaled_err(g["d"], o["d"]) < 1e-12
+    assert _rel(g["Ve"], o["Ve"]) < TOL and _rel(g["mu"], o["mu"]) < TOL and _rel(g["cxx"], o["cxx"]) < 1e-12
+    if "u" in o:
+        assert scaled_err(g["u"], o["u"]) < 5 * TOL and _rel(g["Vk"], o["Vk"]) < TOL
+
+
+def _kmup(P, aux):
+    import bwgr_amd
+    k = _kmup_inputs()
+    return bwgr_amd.KMUP(P, k["b"], k["d"], k["xx"], k["e"] * (0.7 if ALT["on"] else 1.0), k["L"], 0.03, 0.3, seed=77, it=3)
+
+
+def _kmup_ok(g):
+    from oracle import oracle as O
+    k = _kmup_inputs()
+    o = O.kmup(_tpod()[0], k["b"], k["d"], k["xx"], k["e"], k["L"], 0.03, 0.3, seed=77, it=3)
+    assert scaled_err(g["b"], o["b"]) < TOL and scaled_err(g["e"], o["e"]) < TOL and np.array_equal(g["d"], o["d"])
+
+
+def _kmup2(P, aux):
+    import bwgr_amd
+    k = _kmup_inputs()
+    return bwgr_amd.KMUP2(P, k["use"], k["b"], k["d"], k["xx2"], k["e"] * (0.7 if ALT["on"] else 1.0), k["L"], 0.03, 0.3, seed=78, it=4)
+
+
+def _kmup2_ok(g):
+    from oracle import oracle as O
+    k = _kmup_inputs()
+    o = O.kmup2(_tpod()[0], k["use"], k["b"], k["d"], k["xx2"], k["e"], k["L"], 0.03, 0.3, seed=78, it=4)
+    assert scaled_err(g["b"], o["b"]) < TOL and scaled_err(g["e"], o["e"]) < TOL and np.array_equal(g["d"], o["d"])
+
+
+WGR = {"wgr": dict(it=25, bi=5, seed=21), "wgr_bag": dict(it=20, bi=5, seed=17, bag=0.7, pi=0.3),
+       "wgr_eigK": dict(it=25, bi=5, VarK=0.9, seed=13)}
+
+
+def _wgr(name):
+    def call(P, aux):
+        import bwgr_amd
+        return bwgr_amd.wgr(_y(), P, **WGR[name], **({"eigK": _eigk()} if name == "wgr_eigK" else {}))
+
+    def ok(g):
+        from oracle import oracle as O
+        X, y = _tpod()
+        _wgr_check(g, O.wgr(y, X, **WGR[name], **({"eigK": _eigk()} if name == "wgr_eigK" else {})))
+    return call, ok
+
+
+def _em(model):
+    def call(P, aux):
+        import bwgr_amd
+        return getattr(bwgr_amd, model)(_y(), P)
+
+    def ok(g):
+        from oracle import oracle as O
+        X, y = _tpod()
+        _em_check(model, g, O.em(model, y, X), tol=2e-6 if model == "emBCpi" else TOL)      # (test_em_family_tpod_defaults' bounds)
+    return call, ok
+
+
+def _bayes2(P, aux):
+    import bwgr_amd
+    return bwgr_amd.BayesB2(_x2()[1] * np.float32(0.5 if ALT["on"] else 1.0), P, aux["P2"], **BAYES2_KW)
+
+
+def _bayes2_ok(g):
+    from oracle import oracle as O
+    X2, y2 = _x2()
+    o = O.bayes2("BayesB2", y2, _tpod()[0].astype(np.float32), X2, **BAYES2_KW)
+    for k in ("b1", "b2", "hat", "vb1", "vb2", "d1", "d2"):
+        assert scaled_err(g[k], o[k]) < TOL, k
+    for k in ("mu", "ve", "h2"):
+        assert abs(g[k] - o[k]) <= TOL * max(1.0, abs(o[k])), k
+
+
+CHAIN_KW = dict(it=6, bi=1, pi=0.9, df=5, R2=0.5, seed=11)
+
+
+def _chain(P, aux):
+    import bwgr_amd
+    ch = bwgr_amd.Chain(P, "BayesB", _y(), **CHAIN_KW)
+    try:
+        ch.run(6)
+        out = dict(ch.result())
+        out.update({"state_" + k: v for k, v in ch.state().items()})
+    finally:
+        ch.close()
+    return out
+
+
+def _chain_ok(g):
+    from oracle import oracle as O
+    X, y = _tpod()
+    o = O.bayes("BayesB", y, X, **CHAIN_KW)
+    assert scaled_err(g["b"], o["b"]) < TOL and scaled_err(g["hat"], o["hat"]) < TOL and np.array_equal(g["d"], o["d"])
+    assert _rel(g["ve"], o["ve"]) < TOL and _rel(g["mu"], o["mu"]) < TOL
+    assert scaled_err(g["state_e"], o["last"]["e"]) < TOL and scaled_err(g["state_b"], o["last"]["b"]) < TOL
+
+
+def _stats(P, aux):
+    xx, vx, msx = P.stats()
+    return dict(xx=xx, vx=vx, msx=msx)
+
+
+def _stats_ok(g):
+    from oracle import oracle as O
+    oxx, ovx, omsx = O.stats(_tpod()[0])
+    assert np.array_equal(g["xx"], oxx) and scaled_err(g["vx"], ovx) < 1e-7 and _rel(g["msx"], omsx) < 1e-7
+
+
+def _mrr(P, aux):
+    import bwgr_amd
+    return bwgr_amd.MRR3(_Y("mrr"), P, maxit=5, tol=0)
+
+
+def _mrr_ok(g):
+    _mrr_check(g, MR.mrr(_slab_traits("mrr"), _slabs900(), maxit=5, tol=0))
+
+
+def _uvb(P, aux):
+    import bwgr_amd
+    return bwgr_amd.uvbeta(_Y("uvb"), P, "D", maxit=4, tol=0, xb=True)
+
+
+def _uvb_ok(g):
+    X = _slabs900()
+    _uvb_check(g, UR.uvbeta(_slab_traits("uvb"), X, "D", maxit=4, tol=0))
+    assert MR.scaled_err(g["xb"], X.astype(np.float64) @ g["b"]) <= 1e-12
+
+
+@functools.lru_cache(None)
+def _B():
+    return np.random.default_rng(5).normal(size=(900, 17))
+
+
+def _xb(P, aux):
+    return dict(xb=P.xb(-1.5 * _B() if ALT["on"] else _B()))
+
+
+def _xb_ok(g):
+    assert MR.scaled_err(g["xb"], _slabs900().astype(np.float64) @ _B()) <= 1e-12
+
+
+def _crossprod(P, aux):
+    return dict(G=P.crossprod())
+
+
+def _crossprod_ok(g):
+    assert np.array_equal(g["G"], KR.crossprod(_slabs900()))
+
+
+def _grm(device_out):
+    def call(P, aux):
+        K = P.kernel("GRM", device_out=device_out)
+        return dict(K=K.cpu().numpy() if device_out else K)
+
+    def ok(g):
+        assert MR.scaled_err(g["K"], KR.GRM(np.ascontiguousarray(_slabs900()))) <= TOL and np.array_equal(g["K"], g["K"].T)
+    return call, ok
+
+
+def _zsemf(P, aux):
+    import bwgr_amd
+    return bwgr_amd.ZSEMF(_Y("sem"), P, 0, maxit=6, tol=0)
+
+
+def _zsemf_ok(g):
+    o = SR.ZSEMF(_slab_traits("sem"), _slabs900(), 0, maxit=6, tol=0)
+    _well_posed(o)
+    _sem_check("ZSEMF", g, o)
+
+
+ENTRIES = {
+    "KMUP": ("tpod", _kmup, _kmup_ok), "KMUP2": ("tpod", _kmup2, _kmup2_ok),
+    "wgr": ("tpod",) + _wgr("wgr"), "wgr_bag": ("tpod",) + _wgr("wgr_bag"), "wgr_eigK": ("tpod",) + _wgr("wgr_eigK"),
+    "emRR": ("tpod",) + _em("emRR"), "emBCpi": ("tpod",) + _em("emBCpi"), "BayesB2": ("tpod2", _bayes2, _bayes2_ok),
+    "chain": ("tpod", _chain, _chain_ok), "stats": ("tpod", _stats, _stats_ok),
+    "mrr": ("slabs", _mrr, _mrr_ok), "uvbeta_xb": ("slabs", _uvb, _uvb_ok), "xb": ("slabs", _xb, _xb_ok),
+    "crossprod": ("slabs", _crossprod, _crossprod_ok), "GRM_host": ("slabs",) + _grm(False), "GRM_device": ("slabs",) + _grm(True),
+    "ZSEMF": ("slabs", _zsemf, _zsemf_ok),
+}
+
+
+def _same(a, b, what):
+    assert list(a) == list(b), what
+    for key in a:
+        assert np.array_equal(np.asarray(a[key]), np.asarray(b[key]), equal_nan=np.asarray(a[key]).dtype.kind == "f"), (what, key)
+
+
+class _Env:
+    """The two root panels, BayesB2's second panel, the caller's stream and its filler."""
+
+    def __init__(self):
+        import torch
+        import bwgr_amd
+        self.torch = torch
+        self.live = bwgr_amd.debug_live()
+        # (tpod2: BayesB2's two panels share the residual, hence the slab geometry, and an fp32 panel's slabs have at most 128 rows)
+        self.P = {"tpod": bwgr_amd.Panel(_tpod()[0]), "tpod2": bwgr_amd.Panel(_tpod()[0], nwg=2), "slabs": bwgr_amd.Panel(_slabs900(), nwg=3)}
+        assert self.P["slabs"].nwg == 3 and self.P["tpod2"].nwg == 2
+        self.aux = {"P2": bwgr_amd.Panel(_x2()[0], nwg=2)}
+        self.s = torch.cuda.Stream()
+        assert self.s.cuda_stream != 0
+        self.unit_cycles = 5_000_000
+        ms = []
+        for _ in range(3):      # (the first launch carries the kernel's load: the shortest of the later two is the unit)
+            e0, e1 = self._spin(1)
+            self.s.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        self.unit_ms = min(ms[1:])
+        assert self.unit_ms > 0
+
+    def _spin(self, units):
+        """enqueue `units` spin kernels on the caller's stream between two events"""
+        torch = self.torch
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(self.s):
+            e0.record()
+            for _ in range(units):
+                torch.cuda._sleep(self.unit_cycles)
+            e1.record()
+        return e0, e1
+
+    def timed(self, call):
+        """(result, ms) of a call on the default stream, by events around it"""
+        torch = self.torch
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        out = call()
+        e1.record()
+        torch.cuda.synchronize()
+        return out, e0.elapsed_time(e1)
+
+    def busy(self, entry_ms):
+        """keep the caller's stream busy for more than FILL times entry_ms; returns the events that time the filler"""
+        return self._spin(int(math.ceil((FILL + 1.0) * entry_ms / self.unit_ms)) + 1)
+
+    def close(self):
+        import bwgr_amd
+        for P in list(self.P.values()) + list(self.aux.values()):
+            P.set_stream(0)
+            P.close()
+        self.s.synchronize()
+        assert bwgr_amd.debug_live() == self.live
+
+
+@pytest.fixture(scope="module")
+def env():
+    e = _Env()
+    yield e
+    e.close()
+
+
+@pytest.mark.parametrize("name", list(ENTRIES))
+def test_entry_on_every_handle(env, name):
+    import bwgr_amd
+    which, call, ok = ENTRIES[name]
+    P = env.P[which]
+    first = call(P, env.aux)
+    again, entry_ms = env.timed(lambda: call(P, env.aux))
+    live = bwgr_amd.debug_live()      # (after the handle's first sweeps: it keeps the scratch, stream and events they made until it is closed)
+    _same(first, again, "two calls on the default stream")      # the precondition of everything below
+    ok(first)
+    Q = P.clone()
+    try:
+        on_clone = call(Q, env.aux)
+    finally:
+        Q.close()
+    ALT["on"] = True
+    try:
+        other = call(P, env.aux)      # (stats, crossprod and the kernels have no input but the panel: the same result again)
+    finally:
+        ALT["on"] = False
+    assert name in ("stats", "crossprod", "GRM_host", "GRM_device") or not np.array_equal(next(iter(other.values())), next(iter(first.values())))
+    try:
+        P.set_stream(env.s.cuda_stream)
+        e0, e1 = env.busy(entry_ms)
+        on_stream = call(P, env.aux)
+        env.s.synchronize()
+        filler_ms = e0.elapsed_time(e1)
+    finally:
+        P.set_stream(0)
+    back = call(P, env.aux)
+    print("%s: entry %.3f ms on the default stream, filler %.3f ms on the caller's" % (name, entry_ms, filler_ms))
+    assert filler_ms >= FILL * entry_ms, (filler_ms, entry_ms)
+    _same(first, on_clone, "clone")
+    _same(first, on_stream, "caller's stream")
+    _same(first, back, "back on the default stream")
+    assert bwgr_amd.debug_live() == live
+
+
+@pytest.mark.parametrize("model,pi", [("BayesB", 0.9), ("BayesRR", 0.0)])
+def test_a_chain_across_stream_changes(env, model, pi):
+    """three iterations on the default stream, three on the caller's: the state and the result of six uninterrupted ones"""
+    import bwgr_amd
+    X, y = _tpod()
+    P = env.P["tpod"]
+    kw = dict(it=6, bi=1, pi=pi, seed=11)
+    whole = bwgr_amd.Chain(P, model, y, **kw)
+    try:
+        _, run_ms = env.timed(lambda: (whole.run(6), whole.sync()))
+        ref = dict(whole.result(), **{"state_" + k: v for k, v in whole.state().items()})
+    finally:
+        whole.close()
+    parts = bwgr_amd.Chain(P, model, y, **kw)
+    try:
+        parts.run(3); parts.sync()
+        P.set_stream(env.s.cuda_stream)
+        env.busy(run_ms)
+        parts.run(3); parts.sync()
+        got = dict(parts.result(), **{"state_" + k: v for k, v in parts.state().items()})
+    finally:
+        P.set_stream(0)
+        parts.close()
+    _same(ref, got, model)
+
+
+def test_chain_inputs_already_on_the_device(env):
+    """y is written by torch on the caller's stream right behind the filler, and the chain is created with that stream set and without
+    waiting for the device first (wait_for_y=False): the same bits as with y from the host."""
+    import torch
+    import bwgr_amd
+    X, y = _tpod()
+    P = env.P["tpod"]
+    kw = dict(it=6, bi=1, pi=0.9, seed=11)
+
+    def finish(ch):
+        ch.run(6)
+        return dict(ch.result(), **{"state_" + k: v for k, v in ch.state().items()})
+
+    host = bwgr_amd.Chain(P, "BayesB", y, **kw)
+    try:
+        ref, run_ms = env.timed(lambda: finish(host))
+    finally:
+        host.close()
+    src = torch.from_numpy(y.astype(np.float32)).cuda()
+    yd = torch.zeros(P.n, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    ch = None
+    try:
+        P.set_stream(env.s.cuda_stream)
+        env.busy(run_ms)
+        with torch.cuda.stream(env.s):
+            yd.copy_(src, non_blocking=True)
+        ch = bwgr_amd.Chain(P, "BayesB", yd, wait_for_y=False, **kw)
+        got = finish(ch)
+    finally:
+        P.set_stream(0)
+        if ch is not None:
+            ch.close()
+    _same(ref, got, "device y")
