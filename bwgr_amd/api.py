@@ -1220,6 +1220,113 @@ def YSEMF(Y, X, npc=-1, *, maxit=100, tol=10e-7, df0=20.0, **kw):
     return _sem("YSEMF", Y, X, npc, maxit, tol, df0, kw)
 
 
+# ---- two designs in one sweep: solver2x, MEGA, GSEM (src/RcppEigen20230423.cpp:1446-1493, :1542-1610; R/RcppExports.R:200, 208, 212) ----
+# Double precision throughout, as the reference: nothing is rounded.  The thin SVDs are numpy's, on the host.  The results do not depend on
+# the sign of a singular pair: it flips LS's column, LS_BETA's (or V's) column and BETA1's row together, exactly, so b, hat, gebv, mu and
+# BETA2 are invariant and LS, LS_BETA and BETA1 are defined up to that sign.
+UVB2_KEYS = ("b1", "b2", "mu", "h2", "ve", "vb1", "vb2", "its", "cnv")
+
+
+def _uvb2_panel(P, Ym, Z, maxit, tol, df0):
+    """bwgr_uvbeta2 on exactly what it is given (n x k float64 Y, n x q float64 Z)."""
+    Zf = np.asarray(Z, np.float64)
+    if Zf.ndim == 1:
+        Zf = Zf[:, None]
+    if Zf.ndim != 2 or Zf.shape[0] != P.n:
+        raise BwgrError(1, "uvbeta2: Z has shape %s; nrow(Z) must equal nrow(X) = %d" % (Zf.shape, P.n))
+    q = Zf.shape[1]
+    Zf = np.asfortranarray(Zf)
+    k = Ym.shape[1]
+    Yf = np.asfortranarray(Ym)
+    kk = max(k, 1)
+    b1, b2 = np.zeros((q, kk), order="F"), np.zeros((P.p, kk), order="F")
+    mu, h2, ve, vb1, vb2, cnv = (np.zeros(kk) for _ in range(6))
+    its = np.zeros(kk, np.int32)
+    check(_lib.lib().bwgr_uvbeta2(P._h, _dp(Zf), int(q), int(P.n), _dp(Yf), int(k), int(maxit), float(tol), float(df0), _dp(b1), _dp(b2), _dp(mu),
+                                  _dp(h2), _dp(ve), _dp(vb1), _dp(vb2), its.ctypes.data_as(C.POINTER(C.c_int)), _dp(cnv)))
+    return dict(zip(UVB2_KEYS, (b1, b2, mu, h2, ve, vb1, vb2, its, cnv)))
+
+
+def uvbeta2(Y, Z, X, maxit=100, tol=10e-7, df0=20.0, **kw):
+    """solver2x for every column of Y (bwgr_uvbeta2): in each sweep the q columns of the dense design Z (n x q float64), then the markers of X,
+    against one residual, each design with its own lambda; each trait on its own observed rows (NaN = missing), fp64.  Returns dict(b1 [q x k],
+    b2 [p x k], mu, h2, ve, vb1, vb2, its, cnv).  X is a genotype matrix or a Panel."""
+    P, own = _as_panel(X, **kw)
+    try:
+        Ym, tol, df0 = _uvb_inputs(Y, P.n, 0, tol, df0, "uvbeta2")
+        return _uvb2_panel(P, Ym, Z, maxit, tol, df0)
+    finally:
+        if own:
+            P.close()
+
+
+def solver2x(Y, X1, X2, maxit=100, tol=10e-7, df0=20.0, **kw):
+    """solver2x(Y, X1, X2, maxit, tol, df0), src/RcppEigen20230423.cpp:1446-1493 (R/RcppExports.R:200): the vector (mu, b_1, b_2) of length
+    1 + p1 + p2 of one trait.  X1 is the dense design (n x p1 float64) and X2 the genotypes or a Panel, which is how MEGA and GSEM call it; a
+    dense X2 is not taken.  NaN rows of Y are treated as unobserved."""
+    r = uvbeta2(np.asarray(Y, np.float64).reshape(-1), X1, X2, maxit, tol, df0, **kw)
+    return np.concatenate([r["mu"][:1], r["b1"][:, 0], r["b2"][:, 0]])
+
+
+def _mega_latent(Ym, G, npc, who):
+    """LatentSpaces (:1530-1539) on G = X BETA: the centred records where observed and G where missing (GetImputedY, :1517-1528), each column
+    divided by sqrt(sum Y2^2 / (n - 1)), then LS = (U diag(s)).leftCols(npc)."""
+    w = ~np.isnan(Ym)
+    Y2 = np.where(w, Ym - np.nanmean(Ym, 0), G)                      # :1519-1527
+    Y2 = Y2 / np.sqrt((Y2 ** 2).sum(0) / (Ym.shape[0] - 1))          # :1533-1534
+    return _sem_latent(Y2, npc, who)[0]
+
+
+def _sem2(which, Y, X, npc, maxit, tol, df0, panel_kw):
+    P, own = _as_panel(X, **panel_kw)
+    try:
+        Ym, tol, df0 = _uvb_inputs(Y, P.n, 0, tol, df0, which)
+        npc = _sem_npc(npc, min(Ym.shape), which)                    # (refused before anything runs)
+        if which == "MEGA":
+            empty = np.flatnonzero(~(~np.isnan(Ym)).any(0))
+            if empty.size:
+                raise BwgrError(1, "MEGA: trait %d has no record (its imputed column would be NaN)" % empty[0])
+        BETA = _uvb_panel(P, Ym, 0, maxit, tol, df0)["b"]            # UVBETA(Y, X), :1545, :1585
+        G = P.xb(BETA)
+        if which == "MEGA":
+            LS = _mega_latent(Ym, G, npc, which)                     # :1546
+            LS_BETA = _uvb_panel(P, LS, 0, maxit, tol, df0)["b"]     # UVBETA(LS, X), :1547
+        else:
+            LS, V = _sem_latent(G, npc, which)                       # :1586-1589
+        s = _uvb2_panel(P, Ym, LS, maxit, tol, df0)                  # solver2x per trait, :1553-1561, :1595-1603
+        mu, b1, b2 = s["mu"], s["b1"], s["b2"]
+        if which == "MEGA":
+            b = LS_BETA @ b1 + b2                                    # :1563
+            XB = P.xb(np.hstack([b2, b]))                            # X b2 and X b in one pass over the panel
+            k = Ym.shape[1]
+            hat = LS @ b1 + XB[:, :k] + mu                           # :1564, :1567
+            gebv = XB[:, k:] + mu                                    # :1565, :1568
+            return dict(zip(("mu", "b", "hat", "LS", "LS_BETA", "BETA1", "BETA2", "gebv"), (mu, b, hat, LS, LS_BETA, b1, b2, gebv)))
+        b = BETA @ (V @ b1) + b2                                     # :1609 with V.leftCols(npc)
+        hat = LS @ b1 + P.xb(b2) + mu                                # :1605-1606
+        return dict(zip(("mu", "b", "hat"), (mu, b, hat)))
+    finally:
+        if own:
+            P.close()
+
+
+def MEGA(Y, X, npc=-1, *, maxit=100, tol=10e-7, df0=20.0, **kw):
+    """MEGA(Y, X, npc), src/RcppEigen20230423.cpp:1542-1579 (R/RcppExports.R:208): UVBETA on the panel, the latent spaces LS of the records
+    imputed with X BETA, UVBETA(LS, X), then solver2x(y, LS, X) per trait on its observed rows.  list(mu, b, hat, LS, LS_BETA, BETA1, BETA2,
+    gebv) with b = LS_BETA BETA1 + BETA2.  maxit, tol, df0 are the solvers' (the reference has their defaults built in).  A trait without
+    records is refused (the reference's imputed column is NaN there).  X is an array or a Panel."""
+    return _sem2("MEGA", Y, X, npc, maxit, tol, df0, kw)
+
+
+def GSEM(Y, X, npc=-1, *, maxit=100, tol=10e-7, df0=20.0, **kw):
+    """GSEM(Y, X, npc), src/RcppEigen20230423.cpp:1582-1610 (R/RcppExports.R:212): UVBETA on the panel, LS = the first npc latent columns of
+    X BETA, then solver2x(y, LS, X) per trait.  list(mu, b, hat) with b = BETA V.leftCols(npc) BETA1 + BETA2: the reference multiplies by the
+    whole V (:1609), which is conformable only for npc = min(n, k), where the two agree.  A trait without records gives zero columns.  LS lies in X's span, so the reference's variance update can turn vb2 and
+    lambda_2 negative and a trait's sweep can diverge; such a trait stops on its NaN convergence value with non-finite columns, as in the
+    reference, and the others are not affected."""
+    return _sem2("GSEM", Y, X, npc, maxit, tol, df0, kw)
+
+
 def solver1x(Y, X, maxit=100, tol=10e-7, df0=20.0, **kw):
     """solver1x(Y, X, maxit, tol, df0), src/RcppEigen20230423.cpp:1410-1443 (R/RcppExports.R:196): the p effects of one ridge fit.  NaN rows
     of Y are treated as unobserved."""

@@ -25,6 +25,7 @@
 #include "mrr.hip.h"
 #include "uvb.hip.h"
 #include "uvbd.hip.h"
+#include "uvb2.hip.h"
 #include "kernels.hip.h"
 #include <stdlib.h>
 
@@ -4131,21 +4132,51 @@ extern "C" int bwgr_debug_uvb_plan(int64_t n, int64_t p, int64_t k, int64_t out[
   return BWGR_OK;
 }
 
-extern "C" int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int variant, int maxit, double tol, double df0, double *b_out, double *mu_out,
-                           double *h2_out, double *ve_out, double *vb_out, int *its_out, double *cnv_out, double *xb_out) {
-  if (!P || !Y || !b_out || !its_out) return fail(BWGR_EINVAL, "uvbeta: null pointer");
-  if (k < 1) return fail(BWGR_EINVAL, "uvbeta: k = %lld traits (at least 1)", (long long)k);
-  if (variant < BWGR_UVB_D || variant > BWGR_UVB_Z) return fail(BWGR_EINVAL, "uvbeta: unknown variant %d (0 solver1x, 1 solver1xF, 2 xsolver1xF, 3 zsolver1xF)", variant);
-  if (maxit < 0) return fail(BWGR_EINVAL, "uvbeta: maxit = %d", maxit);
-  if (P->data->is_f32) return fail(BWGR_EINVAL, "uvbeta: the panel holds fp32 genotypes; uvbeta takes int8 panels only");
+// (bwgr_uvbeta_dense's plan, above its first user: the dense leg of bwgr_uvbeta2 carves its LDS up by the same rule)
+// The plan, decided here and nowhere else (bwgr_debug_uvbd_plan exposes it to the CPU tests): whether a trait's residual lives in its
+// workgroup's LDS or in a global workspace, the workgroup size, the dynamic LDS bytes and the bytes of that workspace.
+struct UvbdPlan { int64_t lds_rows; bool e_in_lds; int threads; size_t lds_bytes, ws_bytes; };
+static UvbdPlan uvbd_plan(int64_t n, int64_t q, int64_t k) {
+  (void)q;   // (the per-column values live in global memory: the LDS carve-up does not depend on q)
+  UvbdPlan pl;
+  pl.lds_rows = (int64_t)((UVBD_LDS_MAX - UVBD_LDS_FIXED) / sizeof(double));
+  pl.e_in_lds = n <= pl.lds_rows;
+  pl.threads = (int)std::min<int64_t>(UVBD_TMAX, (n + 63) / 64 * 64);   // one row per thread up to 1024 rows, whole waves
+  pl.lds_bytes = UVBD_LDS_FIXED + (pl.e_in_lds ? sizeof(double) * (size_t)n : 0);
+  pl.ws_bytes = pl.e_in_lds ? 0 : sizeof(double) * (size_t)n * (size_t)k;
+  return pl;
+}
+
+// The engine of bwgr_uvbeta and bwgr_uvbeta2.  D = nullptr: one design, the panel (solver1x and its kin).  D given (variant D only): solver2x
+// (:1446-1493) -- in every sweep the dense design D->Z is walked first (k_uvb2_leg, uvb2.hip.h), then the panel, against one residual; each
+// design has its own lambda and variance update; the panel's outputs are b_out and vb_out, the dense design's D->b1 and D->vb1.
+struct Uvb2Dense { const double *Z; int64_t q, ldz; double *b1, *vb1; };
+static int uvb_run(const char *who, bwgr_panel *P, const double *Y, int64_t k, int variant, int maxit, double tol, double df0, const Uvb2Dense *D, double *b_out,
+                   double *mu_out, double *h2_out, double *ve_out, double *vb_out, int *its_out, double *cnv_out, double *xb_out) {
+  if (!P || !Y || !b_out || !its_out || (D && (!D->Z || !D->b1))) return fail(BWGR_EINVAL, "%s: null pointer", who);
+  if (k < 1) return fail(BWGR_EINVAL, "%s: k = %lld traits (at least 1)", who, (long long)k);
+  if (variant < BWGR_UVB_D || variant > BWGR_UVB_Z) return fail(BWGR_EINVAL, "%s: unknown variant %d (0 solver1x, 1 solver1xF, 2 xsolver1xF, 3 zsolver1xF)", who, variant);
+  if (maxit < 0) return fail(BWGR_EINVAL, "%s: maxit = %d", who, maxit);
+  if (P->data->is_f32) return fail(BWGR_EINVAL, "%s: the panel holds fp32 genotypes; %s takes int8 panels only", who, who);
+  if (D && (D->q < 1 || D->q > 0x7FFFFF00ll || D->ldz < P->data->n))
+    return fail(BWGR_EINVAL, "%s: q = %lld columns of Z, ldz = %lld (q at least 1 and at most 2147483392, the int32 column ids; ldz at least n = %lld)", who, (long long)D->q, (long long)D->ldz, (long long)P->data->n);
   HIPCHK(hipSetDevice(P->data->device));
   const int64_t n = P->data->n, p = P->data->p, ld = P->data->plan.ld;
+  const size_t nq = D ? (size_t)D->q : 0;
+  std::vector<double> Zc((size_t)n * nq);   // Z without its padding
+  for (size_t j = 0; j < nq; ++j)
+    for (int64_t r = 0; r < n; ++r) {
+      const double v = D->Z[j * (size_t)D->ldz + r];
+      if (!std::isfinite(v)) return fail(BWGR_EINVAL, "%s: Z[%lld, %lld] is not finite", who, (long long)r, (long long)j);
+      Zc[j * (size_t)n + r] = v;
+    }
   const int R = P->data->plan.R;
   // (the int32 pattern Grams sum over at most n rows: n * max|x|^2 < 2^31 holds for every int8 panel, panel_build_gram)
   UvbPlan pl = uvb_plan(n, ld, p, k, P->data->plan.x_bytes, -1, -1, xb_out != nullptr);   // (the pattern counts follow once Y has been read)
   const int64_t groups = pl.groups, kpad = pl.kpad;
   // ---- host set-up (:1413-1423 on the trait's own rows, as submat_f / subvec_f select them, :1495-1503) ----
-  struct Trait { double nt = 0, mu = 0, sumy = 0, vy = 0, TrXSX = 0, ve = NAN, vb = NAN, ve0 = 0, vb0 = 0, cnv = NAN; int its = 0; bool active = false; };
+  struct Trait { double nt = 0, mu = 0, sumy = 0, vy = 0, TrXSX = 0, ve = NAN, vb = NAN, ve0 = 0, vb0 = 0, cnv = NAN; int its = 0; bool active = false;
+                 double TrXSX1 = 0, vb1 = NAN, vb01 = 0; bool skip1 = false, skip2 = false; };   // (the dense design's; skip: TrXSX of that design is 0)
   std::vector<Trait> T((size_t)k);
   std::vector<double> y((size_t)kpad * ld, 0.0);
   std::vector<unsigned long long> zb((size_t)groups * ld, 0ull);
@@ -4156,7 +4187,7 @@ extern "C" int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int varian
       const double v = Y[(size_t)t * n + r];
       if (!std::isnan(v)) { zg[r] |= 1ull << (t % UVB_W); q.nt += 1.0; q.mu += v; }
     }
-    if (q.nt == 1.0) return fail(BWGR_EINVAL, "uvbeta: trait %lld has one observed row (the variances divide by n - 1)", (long long)t);
+    if (q.nt == 1.0) return fail(BWGR_EINVAL, "%s: trait %lld has one observed row (the variances divide by n - 1)", who, (long long)t);
     if (q.nt == 0.0) continue;   // an all-NaN trait: a zero column, no sweeps (:1510, :1713, :1811)
     q.mu /= q.nt;                                                                                          // :1413
     double *yt = y.data() + (size_t)t * ld;
@@ -4210,6 +4241,9 @@ extern "C" int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int varian
   hipStream_t st = P->stream;
   std::vector<int> order((size_t)p);
   std::vector<double> res(pl.n_res), db2h((size_t)kpad), mu0((size_t)kpad, 0.0);   // (copied to and from asynchronously: declared before the holder)
+  std::vector<Uvb2Trait> tr1(D ? (size_t)kpad : 0);   // (the dense leg's: these too are copied to and from asynchronously)
+  std::vector<double> leg(D ? (size_t)kpad * UVB2_NLEG : 0), trx1(D ? (size_t)kpad : 0);
+  std::vector<int32_t> order1(nq);
   DevBufs bufs(st);
   const int64_t nblk = pl.nblk;
   const size_t nl = (size_t)ld, np = (size_t)p;
@@ -4226,7 +4260,30 @@ extern "C" int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int varian
   double *bout = bufs.get<double>(pl.n_bout), *xbd = xb_out ? bufs.get<double>(pl.n_xb) : nullptr;
   if (!Xs || !ordd || !gram || !zmd || !zbd || !yd || !ed || !Sd || !XXd || !tilde || !bd || !part || !dB || !tpart || !resd || !db2 || !mu0d || !trd || !slotd || !bout ||
       (xb_out && !xbd))
-    return fail(BWGR_ENOMEM, "uvbeta: device allocation failed");
+    return fail(BWGR_ENOMEM, "%s: device allocation failed", who);
+  // the dense design's arrays: Z, the traits' per-column values, the leg's sums; the leg's launch shape is uvbd_plan's
+  const UvbdPlan dpl = uvbd_plan(n, D ? D->q : 1, k);
+  Uvb2Args da;
+  Uvb2Trait *tr1d = nullptr;
+  int32_t *ord1d = nullptr;
+  if (D) {
+    const size_t nc = (size_t)kpad * nq;
+    double *Zd = bufs.get<double>((size_t)n * nq), *c1 = bufs.get<double>(5 * nc), *trxd = bufs.get<double>((size_t)kpad), *legd = bufs.get<double>((size_t)kpad * UVB2_NLEG);
+    tr1d = bufs.get<Uvb2Trait>((size_t)kpad); ord1d = bufs.get<int32_t>(nq);
+    if (!Zd || !c1 || !trxd || !legd || !tr1d || !ord1d) return fail(BWGR_ENOMEM, "%s: device allocation failed", who);
+    da.Z = Zd; da.n = n; da.q = D->q; da.ld = ld; da.y = yd; da.e = ed; da.zm = zmd; da.tr = tr1d; da.order = ord1d;
+    da.zbar = c1; da.XX = c1 + nc; da.tilde = c1 + 2 * nc; da.b = c1 + 3 * nc; da.dlt = c1 + 4 * nc; da.trx = trxd; da.leg = legd;
+    for (int64_t t = 0; t < kpad; ++t) {
+      Uvb2Trait &u = tr1[(size_t)t];
+      u.lam = 0.0; u.nt = tr[(size_t)t].nt; u.moff = (int64_t)(zm_off[(size_t)(t / UVB_W)] + (size_t)tr[(size_t)t].pat * nl); u.run = 0; u.pad_ = 0;
+    }
+    HIPCHK(hipMemcpyAsync(Zd, Zc.data(), sizeof(double) * (size_t)n * nq, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(tr1d, tr1.data(), sizeof(Uvb2Trait) * kpad, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(c1, 0, sizeof(double) * 5 * nc, st));                                       // b_1 = 0, :1458
+    HIPCHK(hipMemsetAsync(trxd, 0, sizeof(double) * kpad, st));
+    HIPCHK(hipMemsetAsync(legd, 0, sizeof(double) * kpad * UVB2_NLEG, st));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_uvb2_leg<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)UVBD_LDS_MAX));
+  }
   if (!zm.empty()) HIPCHK(hipMemcpyAsync(zmd, zm.data(), zm.size(), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(zbd, zb.data(), sizeof(unsigned long long) * groups * nl, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(yd, y.data(), sizeof(double) * pl.n_rows, hipMemcpyHostToDevice, st));
@@ -4264,6 +4321,10 @@ extern "C" int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int varian
                        (const double *)(yd + orow), (const UvbTrait *)(trd + g * UVB_W), kg, Sd + oc, XXd + oc, tilde + oc);
     cols(g, 1, have);
   }
+  if (D) {   // (after the copies of y and the masks above, on the same stream)
+    hipLaunchKernelGGL(k_uvb2_setup, dim3((unsigned)k), dim3(dpl.threads), UVBD_LDS_FIXED, st, da);
+    HIPCHK(hipMemcpyAsync(trx1.data(), da.trx, sizeof(double) * kpad, hipMemcpyDeviceToHost, st));
+  }
   HIPCHK(hipGetLastError());
   HIPCHK(d2h(st, res.data(), resd, sizeof(double) * pl.n_res));
   for (int64_t t = 0; t < k; ++t) {
@@ -4274,11 +4335,22 @@ extern "C" int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int varian
     if (variant == BWGR_UVB_X) { tr[(size_t)t].lam = q.TrXSX / (double)p; continue; }                      // lambda = XX.mean(), :1730
     q.ve = q.vy * 0.5; q.vb = (q.vy * 0.5) / MSx;                                                          // :1420
     tr[(size_t)t].lam = q.ve / q.vb; q.vb0 = q.vb * df0; q.ve0 = q.ve * df0;                               // :1423
+    if (!D) continue;
+    // solver2x's set-up of the two designs (:1455-1462).  A design with TrXSX = 0 on this trait's rows is skipped: its lambda is never
+    // formed and its vb stays NaN; every XX of it is 0, so the panel leg leaves such a trait's b and e as they are
+    q.skip2 = q.TrXSX == 0.0;
+    if (q.skip2) { q.vb = NAN; q.vb0 = 0.0; tr[(size_t)t].lam = 0.0; }
+    q.TrXSX1 = trx1[(size_t)t];
+    q.skip1 = q.TrXSX1 == 0.0;
+    if (q.skip1) continue;
+    q.vb1 = (q.vy * 0.5) / (q.TrXSX1 / (q.nt - 1.0));                                                      // :1456-1457
+    tr1[(size_t)t].lam = q.ve / q.vb1; q.vb01 = q.vb1 * df0;                                               // :1461-1462
   }
   // ---- sweeps ----
   for (int64_t j = 0; j < p; ++j) order[(size_t)j] = (int)j;
   const int cps = (int)((size_t)R / 16);
   const double logtol = log10(tol), thr = variant == BWGR_UVB_F ? 0.00001 : 0.0;
+  for (size_t j = 0; j < nq; ++j) order1[j] = (int32_t)j;
   for (int sweep = 0; sweep < maxit; ++sweep) {
     bool any = false;
     for (int64_t t = 0; t < k; ++t) { tr[(size_t)t].active = T[(size_t)t].active ? 1 : 0; any = any || T[(size_t)t].active; }
@@ -4288,11 +4360,25 @@ extern "C" int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int varian
     HIPCHK(hipMemcpyAsync(trd, tr.data(), sizeof(UvbTrait) * kpad, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)P->data->X, (uint4 *)Xs, (const int32_t *)ordd, p, P->data->plan.K, cps);
     HIPCHK(hipMemsetAsync(db2, 0, sizeof(double) * kpad, st));
+    if (D) {
+      std::shuffle(order1.begin(), order1.end(), std::mt19937(sweep));                                     // :1468 (cumulative, as there)
+      for (int64_t t = 0; t < k; ++t) tr1[(size_t)t].run = (T[(size_t)t].active && !T[(size_t)t].skip1) ? 1 : 0;
+      HIPCHK(hipMemcpyAsync(ord1d, order1.data(), sizeof(int32_t) * nq, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(tr1d, tr1.data(), sizeof(Uvb2Trait) * kpad, hipMemcpyHostToDevice, st));
+    }
     for (int64_t g = 0; g < groups; ++g) {
       const unsigned long long act = mask_of(g, true);
       if (!act) continue;
       const size_t oc = (size_t)g * UVB_W * np, orow = (size_t)g * UVB_W * nl;
       const int ng = npat[(size_t)g];
+      if (D) {   // the dense leg (:1470-1473) of the group's running traits, in front of the panel's; one workgroup per trait of the group
+        const unsigned kg = (unsigned)std::min<int64_t>(UVB_W, k - g * UVB_W);
+        Uvb2Args ga = da;
+        const size_t o1 = (size_t)g * UVB_W * nq;
+        ga.y += orow; ga.e += orow; ga.tr += g * UVB_W; ga.zbar += o1; ga.XX += o1; ga.tilde += o1; ga.b += o1; ga.dlt += o1; ga.trx += g * UVB_W; ga.leg += (size_t)g * UVB_W * UVB2_NLEG;
+        if (dpl.e_in_lds) hipLaunchKernelGGL(k_uvb2_leg<true>, dim3(kg), dim3(dpl.threads), dpl.lds_bytes, st, ga);
+        else hipLaunchKernelGGL(k_uvb2_leg<false>, dim3(kg), dim3(dpl.threads), dpl.lds_bytes, st, ga);
+      }
       int nsolve = 0;
       for (int sb = 0; sb < pl.nsolve; ++sb) if ((act >> (sb * UVB_ST)) & 0xFFFFull) nsolve = sb + 1;
       hipLaunchKernelGGL(k_mrr_gram, dim3((unsigned)nblk, (unsigned)((ng + 3) / 4)), dim3(256), 0, st, (const int8_t *)Xs, R, p, ld, (const uint8_t *)(zmd + zm_off[(size_t)g]), ng, gram);
@@ -4311,6 +4397,7 @@ extern "C" int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int varian
       HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemcpyAsync(db2h.data(), db2, sizeof(double) * kpad, hipMemcpyDeviceToHost, st));
+    if (D) HIPCHK(hipMemcpyAsync(leg.data(), da.leg, sizeof(double) * kpad * UVB2_NLEG, hipMemcpyDeviceToHost, st));
     HIPCHK(d2h(st, res.data(), resd, sizeof(double) * pl.n_res));
     // the tail of every trait that ran (:1433-1441, :1636-1644, :1739-1741, :1794-1801)
     for (int64_t t = 0; t < k; ++t) {
@@ -4322,6 +4409,24 @@ extern "C" int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int varian
       const double m0 = se / q.nt;                                             // mu0 = mean(e); the sums below are those of e - mu0
       mu0[(size_t)t] = m0; q.mu += m0;
       const double ey1 = ey - m0 * q.sumy, ee1 = ee - 2.0 * m0 * se + q.nt * m0 * m0;
+      if (D) {                                                                 // solver2x's tail, :1478-1486
+        q.ve = (ee1 + ey1 + q.ve0) / (2.0 * q.nt - 1.0 + df0);                 // :1479-1481
+        double d1 = 0.0;
+        if (!q.skip1) {
+          const double *lg = leg.data() + (size_t)t * UVB2_NLEG;
+          d1 = lg[0];
+          q.vb1 = (lg[2] + lg[1] + q.vb01) / (q.TrXSX1 + (double)D->q + df0);  // :1482, :1484
+          tr1[(size_t)t].lam = q.ve / q.vb1;                                   // :1485
+        }
+        if (!q.skip2) {
+          q.vb = (tb + bb + q.vb0) / (q.TrXSX + (double)p + df0);              // :1483-1484
+          tr[(size_t)t].lam = q.ve / q.vb;
+        }
+        q.cnv = log10(d1 + db2h[(size_t)t]);                                   // :1486
+        ++q.its;
+        if (q.cnv < logtol || q.its == maxit || std::isnan(q.cnv)) q.active = false;   // :1487
+        continue;
+      }
       if (variant == BWGR_UVB_D || variant == BWGR_UVB_F) {
         q.ve = (ey1 + ee1 + q.ve0) / (2.0 * q.nt - 1.0 + df0);                 // :1434-1436
         q.vb = (bb + tb + q.vb0) / (q.TrXSX + (double)p + df0);                // :1437-1439
@@ -4358,9 +4463,11 @@ extern "C" int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int varian
   HIPCHK(hipGetLastError());
   HIPCHK(d2h(st, b_out, bout, sizeof(double) * pl.n_bout));
   if (xb_out) HIPCHK(d2h(st, xb_out, xbd, sizeof(double) * pl.n_xb));
+  if (D) HIPCHK(d2h(st, D->b1, da.b, sizeof(double) * nq * (size_t)k));   // ([trait][q] = q x k, column-major)
   for (int64_t t = 0; t < k; ++t) {
     const Trait &q = T[(size_t)t];
     const bool none = q.nt == 0.0, noVar = variant == BWGR_UVB_X;
+    if (D && D->vb1) D->vb1[t] = q.vb1;
     if (mu_out) mu_out[t] = none ? 0.0 : q.mu;
     if (h2_out) h2_out[t] = none ? 0.0 : (noVar ? NAN : 1.0 - q.ve / q.vy);                                // :1802
     if (ve_out) ve_out[t] = (none || noVar) ? NAN : q.ve;
@@ -4371,23 +4478,24 @@ extern "C" int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int varian
   return BWGR_OK;
 }
 
+extern "C" int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int variant, int maxit, double tol, double df0, double *b_out, double *mu_out,
+                           double *h2_out, double *ve_out, double *vb_out, int *its_out, double *cnv_out, double *xb_out) {
+  return uvb_run("uvbeta", P, Y, k, variant, maxit, tol, df0, nullptr, b_out, mu_out, h2_out, ve_out, vb_out, its_out, cnv_out, xb_out);
+}
+
+// solver2x (:1446-1493) for every column of Y: X1 = Z (dense, n x q), X2 = the panel
+extern "C" int bwgr_uvbeta2(bwgr_panel *P, const double *Z, int64_t q, int64_t ldz, const double *Y, int64_t k, int maxit, double tol, double df0, double *b1_out,
+                            double *b2_out, double *mu_out, double *h2_out, double *ve_out, double *vb1_out, double *vb2_out, int *its_out, double *cnv_out) {
+  if (q < 1) return fail(BWGR_EINVAL, "uvbeta2: q = %lld columns of Z (at least 1)", (long long)q);
+  if (!Z || !b1_out) return fail(BWGR_EINVAL, "uvbeta2: null pointer");
+  const Uvb2Dense D = {Z, q, ldz, b1_out, vb1_out};
+  return uvb_run("uvbeta2", P, Y, k, BWGR_UVB_D, maxit, tol, df0, &D, b2_out, mu_out, h2_out, ve_out, vb2_out, its_out, cnv_out, nullptr);
+}
+
 // ------------------------------------------------------------------------------------------------
 // the same fits on a small dense design, and X B on the panel: the second stage and the products of XSEMF / ZSEMF / YSEMF
 // (src/RcppEigen20230423.cpp:1756-1769, :1819-1874): the kernels of uvbd.hip.h
 // ------------------------------------------------------------------------------------------------
-// The plan, decided here and nowhere else (bwgr_debug_uvbd_plan exposes it to the CPU tests): whether a trait's residual lives in its
-// workgroup's LDS or in a global workspace, the workgroup size, the dynamic LDS bytes and the bytes of that workspace.
-struct UvbdPlan { int64_t lds_rows; bool e_in_lds; int threads; size_t lds_bytes, ws_bytes; };
-static UvbdPlan uvbd_plan(int64_t n, int64_t q, int64_t k) {
-  (void)q;   // (the per-column values live in global memory: the LDS carve-up does not depend on q)
-  UvbdPlan pl;
-  pl.lds_rows = (int64_t)((UVBD_LDS_MAX - UVBD_LDS_FIXED) / sizeof(double));
-  pl.e_in_lds = n <= pl.lds_rows;
-  pl.threads = (int)std::min<int64_t>(UVBD_TMAX, (n + 63) / 64 * 64);   // one row per thread up to 1024 rows, whole waves
-  pl.lds_bytes = UVBD_LDS_FIXED + (pl.e_in_lds ? sizeof(double) * (size_t)n : 0);
-  pl.ws_bytes = pl.e_in_lds ? 0 : sizeof(double) * (size_t)n * (size_t)k;
-  return pl;
-}
 extern "C" int bwgr_debug_uvbd_plan(int64_t n, int64_t q, int64_t k, int64_t out[BWGR_UVBD_PLAN_NOUT]) {
   if (!out) return fail(BWGR_EINVAL, "uvbd plan: null pointer");
   if (n < 1 || q < 1 || k < 1) return fail(BWGR_EINVAL, "uvbd plan: n = %lld, q = %lld, k = %lld (each at least 1)", (long long)n, (long long)q, (long long)k);

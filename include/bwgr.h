@@ -307,8 +307,9 @@ int bwgr_debug_mrr_plan(int k, int npat, int *linv_lds, int *ngl, int64_t *solve
  * whose markers are all monomorphic on its rows has TrXSX = 0, hence vb = inf and lambda = 0: every marker takes the XX_j = 0 path and b stays
  * 0 (the reference's D and Z give 0 / 0 = NaN there).  For BWGR_UVB_X with TrXSX = 0 the library likewise returns b = 0 where the reference
  * returns NaN.  Neither affects the other traits of the call.
- * Not here: MEGA, GSEM, solver2x / solver2xF (two designs inside one sweep, each with its own lambda); fp32 panels; groups of traits sharded
- * over GPUs.  XSEMF, ZSEMF and YSEMF are compositions of this entry, bwgr_uvbeta_dense and bwgr_panel_xb (below) made by the host layers. */
+ * Not here: MEGA, GSEM and solver2x -- two designs inside one sweep, each with its own lambda, are bwgr_uvbeta2 (below), which runs this
+ * entry's engine with a dense leg in front of it; fp32 panels; groups of traits sharded over GPUs.  XSEMF, ZSEMF and YSEMF are compositions
+ * of this entry, bwgr_uvbeta_dense and bwgr_panel_xb (below) made by the host layers. */
 enum { BWGR_UVB_D = 0 /* solver1x  / UVBETA   */, BWGR_UVB_F = 1 /* solver1xF / FUVBETA  */,
        BWGR_UVB_X = 2 /* xsolver1xF/ XFUVBETA */, BWGR_UVB_Z = 3 /* zsolver1xF/ ZFUVBETA */ };
 int bwgr_uvbeta(bwgr_panel *P, const double *Y, int64_t k, int variant, int maxit, double tol, double df0,
@@ -339,6 +340,35 @@ int bwgr_uvbeta_dense(int device, const double *Z, int64_t n, int64_t q, int64_t
  * per workgroup, dynamic LDS bytes, bytes of that workspace (0 when e is in LDS). */
 #define BWGR_UVBD_PLAN_NOUT 5
 int bwgr_debug_uvbd_plan(int64_t n, int64_t q, int64_t k, int64_t out[BWGR_UVBD_PLAN_NOUT]);
+/* ---- two designs in one sweep: solver2x for every column of Y, the solver of MEGA and GSEM -----------------------------
+ * Replaces VectorXd solver2x(Y,X1,X2,maxit,tol,df0) src/RcppEigen20230423.cpp:1446-1493 as SEXP MEGA(Y,X,npc) :1542-1579 and SEXP GSEM(Y,X,npc)
+ * :1582-1610 call it (R/RcppExports.R:200, 208, 212): X1 = Z, a dense design of n x q doubles (the latent spaces; column-major, leading
+ * dimension ldz), X2 = the panel.  One fit per column of Y (n x k, NaN = missing) on the trait's own observed rows, everything fp64.  Set-up
+ * (:1449-1462): mu, y, tilde_1 = Z'y and tilde_2 = X'y on the raw columns; each design centred by the trait's own column means over its rows;
+ * XX_i, TrXSX_i, MSx_i = TrXSX_i / (n_t - 1), vy, ve = vy / 2, vb_i = ve / MSx_i, lambda_i = ve / vb_i, vb0_i = vb_i df0, ve0 = ve df0.  Sweep s
+ * (:1466-1487): the q columns of Z in the order bwgr_em_order(q, s), then the p markers in the order bwgr_em_order(p, s), against one
+ * residual: b1 = (x_c'e + XX b0) / (XX + lambda_i), e -= x_c (b1 - b0) on the observed rows; then mu0 = mean(e), mu += mu0, e -= mu0,
+ * ve = (e'e + e'y + ve0) / (2 n_t - 1 + df0), vb_i = (tilde_i'b_i + b_i'b_i + vb0_i) / (TrXSX_i + p_i + df0), lambda_i = ve / vb_i,
+ * cnv = log10(sum (delta b_1)^2 + sum (delta b_2)^2).  A trait stops on cnv < log10(tol), at maxit, or on NaN, each trait by itself; a stopped
+ * trait's state is not touched again by either leg.  The panel leg is bwgr_uvbeta's engine unchanged (variant D); the dense leg in front of
+ * it runs one workgroup per running trait, with the trait's residual in LDS when n fits -- by bwgr_uvbeta_dense's plan exactly
+ * (bwgr_debug_uvbd_plan: lds_rows, threads, LDS bytes), so there is no plan hook of its own.
+ * Departures from the reference: (1) where XX_iJ is exactly 0 the coefficient is exactly 0 (threshold 0, both designs); (2) a design whose
+ * TrXSX_i is 0 for a trait (every column constant on that trait's rows) is skipped for that trait: its coefficients stay 0, its lambda is
+ * never formed and its vb_i returns NaN, and the other design runs as if alone (the reference divides by zero and returns NaN); (3) a trait
+ * with no observed row returns zero columns, its = 0, mu = h2 = 0 and NaN elsewhere; (4) h2 is reported as 1 - ve / vy (the reference
+ * computes none).
+ * Outputs (host; b1, b2 and its are required): b1[q x k], b2[p x k] column-major, mu, h2, ve, vb1, vb2, cnv [k], its[k].  A panel switched to
+ * implicit centring gives bit-identical results.  BWGR_EINVAL: a null required pointer, q < 1 or q > 2147483392 (the column ids are int32; the per-column
+ * values live in global memory, so there is no other limit on q), ldz < n, k < 1, maxit < 0, an entry of Z that
+ * is not finite, an fp32 panel, a trait with exactly one observed row.
+ * Not here: solver2xF (:1649-1706) -- its shuffles run from RGSvec1.begin() to RGSvec2.end() (:1671-1672), iterators of two different
+ * vectors, so its order is undefined and cannot be restated; no driver of the reference calls it.  A dense X2; fp32 panels; R's SEM(), which
+ * needs MRR3F options this library refuses.  MEGA and GSEM themselves are compositions made by the host layers (bwgr_amd.MEGA, GSEM;
+ * rshim/bwgr_hip.R): the thin SVD of an n x k matrix stays with the caller. */
+int bwgr_uvbeta2(bwgr_panel *P, const double *Z, int64_t q, int64_t ldz, const double *Y, int64_t k, int maxit, double tol, double df0,
+                 double *b1 /* q x k */, double *b2 /* p x k */, double *mu, double *h2, double *ve, double *vb1, double *vb2, int *its,
+                 double *cnv);
 /* out (n x k, host, column-major) = X B on the raw int8 genotypes for every row; B: p x k, host, column-major.  fp64 sums; the markers are
  * split over workgroups and the partial sums added in a fixed order, so two calls give the same bits, and so does a panel switched to implicit
  * centring.  BWGR_EINVAL: a null pointer, k < 1, an fp32 panel.  (bwgr_uvbeta's own xb output is a different summation order.) */

@@ -133,6 +133,40 @@ YSEMF <- function(Y, X, npc = -1L) {
   b <- f$b + s3$b; G <- .bwgr_xb(f$P, b)
   list(mu = s3$mu, b = b, hat = sweep(G, 2, s3$mu, "+"), h2 = f$s2$h2 + s3$h2, GC = .bwgr_gc(G)$GC)
 }
+# two designs in one sweep, R/RcppExports.R:200, 208, 212 (solver2x, MEGA, GSEM; src/RcppEigen20230423.cpp:1446-1493, :1542-1610): same names,
+# argument order, defaults and return lists; doubles throughout.  solver2x's X1 is the dense design and X2 the integer genotypes (an int8
+# panel), as MEGA and GSEM call it; a dense X2 is not taken.  MEGA refuses a trait without records (the reference's imputed column is NaN);
+# GSEM's b uses V.leftCols(npc) (:1609 multiplies by the whole V, conformable only for npc = min(n, k), where the two agree).  The results
+# do not depend on the signs svd() gives the singular pairs; LS, LS_BETA and BETA1 are defined up to them.
+.bwgr_uvb2 <- function(Y, Z, P, maxit = 100L, tol = 10e-7, df0 = 20.0)
+  .Call("bwgrhip_uvbeta2", Y, Z * 1.0, P, as.integer(maxit), as.double(tol), as.double(df0))
+solver2x <- function(Y, X1, X2, maxit = 100L, tol = 10e-7, df0 = 20.0) {
+  r <- .bwgr_uvb2(as.matrix(as.double(Y)), as.matrix(X1), .bwgr_ipanel(X2), maxit, tol, df0)
+  c(r$mu, r$b1[, 1], r$b2[, 1])
+}
+MEGA <- function(Y, X, npc = -1L) {
+  P <- .bwgr_ipanel(X); Y <- as.matrix(Y) * 1.0; n <- nrow(Y)
+  if (any(colSums(!is.na(Y)) == 0)) stop("MEGA: a trait has no record")
+  BETA <- .bwgr_uvb(Y, P, 0L)$b
+  Y2 <- sweep(Y, 2, colMeans(Y, na.rm = TRUE)); G <- .bwgr_xb(P, BETA)          # GetImputedY, :1517-1528
+  Y2[is.na(Y)] <- G[is.na(Y)]
+  Y2 <- sweep(Y2, 2, sqrt(colSums(Y2^2) / (n - 1)), "/")                         # :1533-1534
+  LS <- .bwgr_latent(Y2, npc)$Z
+  LS_BETA <- .bwgr_uvb(LS, P, 0L)$b
+  f <- .bwgr_uvb2(Y, LS, P)
+  b <- LS_BETA %*% f$b1 + f$b2
+  XB <- .bwgr_xb(P, cbind(f$b2, b)); k <- ncol(Y)
+  hat <- sweep(LS %*% f$b1 + XB[, seq_len(k), drop = FALSE], 2, f$mu, "+")
+  gebv <- sweep(XB[, k + seq_len(k), drop = FALSE], 2, f$mu, "+")
+  list(mu = f$mu, b = b, hat = hat, LS = LS, LS_BETA = LS_BETA, BETA1 = f$b1, BETA2 = f$b2, gebv = gebv)
+}
+GSEM <- function(Y, X, npc = -1L) {
+  P <- .bwgr_ipanel(X); Y <- as.matrix(Y) * 1.0
+  BETA <- .bwgr_uvb(Y, P, 0L)$b
+  L <- .bwgr_latent(.bwgr_xb(P, BETA), npc)
+  f <- .bwgr_uvb2(Y, L$Z, P)
+  list(mu = f$mu, b = BETA %*% (L$V %*% f$b1) + f$b2, hat = sweep(L$Z %*% f$b1 + .bwgr_xb(P, f$b2), 2, f$mu, "+"))
+}
 # relationship kernels, R/RcppExports.R:100-106 (GAU, GRM) and :140-150 (EigenARC, EigenGAU, EigenGRM): same names, argument order and defaults;
 # integer genotypes only (an int8 panel); `cores` is ignored.  Their result feeds wgr(eigK = eigen(K)).
 # (a numeric matrix of whole numbers is staged as integers, so that it becomes an int8 panel)

@@ -372,6 +372,26 @@ SEXP bwgrhip_panel_xb(SEXP panel, SEXP B) {
   return out;
 }
 
+/* solver2x(Y, X1, X2, maxit, tol, df0) src/RcppEigen20230423.cpp:1446-1493 for every column of Y, as MEGA (:1542-1579) and GSEM (:1582-1610) call it:
+ * X1 = Z, a dense n x q numeric design, X2 = the panel; doubles throughout.  Y: NA = missing -> list(b1 = q x k, b2 = p x k, mu). */
+SEXP bwgrhip_uvbeta2(SEXP Y, SEXP Z, SEXP panel, SEXP maxit, SEXP tol, SEXP df0) {
+  bwgr_panel *P = panel_of(panel);
+  int64_t info[8]; chk(bwgr_panel_info(P, info));
+  const R_xlen_t n = info[0], p = info[1];
+  SEXP dz = Rf_getAttrib(Z, R_DimSymbol), dy = Rf_getAttrib(Y, R_DimSymbol);
+  if (Rf_length(dz) != 2 || Rf_length(dy) != 2 || INTEGER(dy)[0] != n || INTEGER(dz)[0] != n) Rf_error("Y and Z must be matrices with nrow(X) rows");
+  const int q = INTEGER(dz)[1], k = INTEGER(dy)[1];
+  SEXP b1 = PROTECT(Rf_allocMatrix(REALSXP, q, k)), b2 = PROTECT(Rf_allocMatrix(REALSXP, (int)p, k)), mu = PROTECT(Rf_allocVector(REALSXP, k));
+  int *its = (int *)R_alloc(k > 0 ? k : 1, sizeof(int));
+  chk(bwgr_uvbeta2(P, REAL(Z), (int64_t)q, (int64_t)n, REAL(Y), (int64_t)k, Rf_asInteger(maxit), Rf_asReal(tol), Rf_asReal(df0), REAL(b1), REAL(b2), REAL(mu),
+                   NULL, NULL, NULL, NULL, its, NULL));
+  const char *nm[] = {"b1", "b2", "mu"};
+  SEXP out = PROTECT(named_list(3, nm));
+  SET_VECTOR_ELT(out, 0, b1); SET_VECTOR_ELT(out, 1, b2); SET_VECTOR_ELT(out, 2, mu);
+  UNPROTECT(4);
+  return out;
+}
+
 /* relationship kernels: GRM(X, Code012) / GAU(X) src/Rcpp20260726ai.cpp:1338-1383, EigenARC / EigenGAU / EigenGRM(X, ., cores)
  * src/RcppEigen20230423.cpp:8-51 -> an n x n numeric matrix.  kind: BWGR_K_*; par: phi; flag: Code012 / centralizeZ / centralizeX. */
 SEXP bwgrhip_kernel(SEXP panel, SEXP kind, SEXP par, SEXP flag) {
@@ -403,6 +423,7 @@ static const R_CallMethodDef CallEntries[] = {   /* as src/RcppExports.cpp:1152-
   {"bwgrhip_MRR3", (DL_FUNC)&bwgrhip_MRR3, 3}, {"bwgrhip_MRR3F", (DL_FUNC)&bwgrhip_MRR3F, 3},
   {"bwgrhip_solver1x", (DL_FUNC)&bwgrhip_solver1x, 6}, {"bwgrhip_UVBETA", (DL_FUNC)&bwgrhip_UVBETA, 3},
   {"bwgrhip_uvbeta_dense", (DL_FUNC)&bwgrhip_uvbeta_dense, 6}, {"bwgrhip_panel_xb", (DL_FUNC)&bwgrhip_panel_xb, 2},
+  {"bwgrhip_uvbeta2", (DL_FUNC)&bwgrhip_uvbeta2, 6},
   {"bwgrhip_kernel", (DL_FUNC)&bwgrhip_kernel, 4}, {"bwgrhip_crossprod", (DL_FUNC)&bwgrhip_crossprod, 1}, {NULL, NULL, 0}};
 
 void R_init_bwgrhip(DllInfo *dll) {              /* as R_init_bWGR, src/RcppExports.cpp:1230-1233 */
