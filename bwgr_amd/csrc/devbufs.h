@@ -46,9 +46,11 @@ template <class B> class DevHolder {
   // count elements of T (at least one byte-sized allocation: count == 0 still gives a pointer); nullptr where the allocation fails
   template <typename T> T *get(size_t count) {
     void *q = B::alloc(sizeof(T) * (count ? count : 1));
-    if (q) arrays_.push_back(q);
+    if (q) arrays_.push_back(q); else failed_ = true;
     return static_cast<T *>(q);
   }
+  // whether any get() of this holder, one inside take() included, has returned nullptr: a call makes the gets of a group and asks once
+  bool failed() const { return failed_; }
   stream_t stream(unsigned flags, int priority) {
     stream_t s{};
     if (!B::stream_create(&s, flags, priority)) return stream_t{};
@@ -99,5 +101,6 @@ template <class B> class DevHolder {
   std::vector<event_t> events_;
   stream_t sync_stream_{};
   bool sync_ = false;
+  bool failed_ = false;
 };
 }  // namespace bwgr

@@ -131,6 +131,35 @@ static void drop() {
   CHECK(Fake::counts(0, 0, 0));
 }
 
+// failed(): false until a get returns null, one made inside take included; true from then on, whatever succeeds later
+static void failure_latch() {
+  for (int pos = 1; pos <= 3; ++pos) {
+    Bufs h;
+    CHECK(!h.failed());
+    Fake::fail_at[0] = pos;
+    for (int i = 1; i <= 4; ++i) {
+      int *q = h.get<int>(2);
+      CHECK((q == nullptr) == (i == pos));
+      CHECK(h.failed() == (i >= pos));   // false before the failing get, true after it and after later successful ones
+    }
+    CHECK(Fake::counts(3, 0, 0));
+  }
+  {
+    Bufs h;
+    double *a = nullptr; int *b = nullptr;
+    CHECK(h.take({{&a, 8}, {&b, 4}}) && !h.failed());
+    Fake::fail_at[0] = 2;
+    CHECK(!h.take({{&a, 8}, {&b, 4}}) && h.failed());
+    CHECK(h.take({{&a, 8}, {&b, 4}}) && h.failed());
+    Fake::fail_at[1] = 1;   // (a stream that cannot be made is no failed get)
+    Bufs g;
+    CHECK(g.stream(0, 0) == nullptr && !g.failed());
+  }
+  Bufs fresh;
+  CHECK(!fresh.failed());
+  CHECK(Fake::counts(0, 0, 0));
+}
+
 // events, then the owned streams (synchronised, then destroyed), then the arrays; the stream of a per-call holder is waited for first
 static void fill(Bufs &h) {
   CHECK(h.get<int>(1) && h.stream(0, 0) && h.event(0) && h.get<int>(1) && h.event(0) && h.stream(0, 1));
@@ -157,6 +186,7 @@ int main() {
   mixed_fail_everywhere();
   get_stream_event();
   drop();
+  failure_latch();
   destruction_order();
   CHECK(Fake::arrays.empty() && Fake::streams.empty() && Fake::events.empty());
   if (g_failed) { fprintf(stderr, "devbufs_check: %d check(s) failed\n", g_failed); return 1; }
