@@ -20,6 +20,7 @@ from ._lib import BwgrError, c_f, c_d, check
 MODELS = {"BayesA": 0, "BayesB": 1, "BayesC": 2, "BayesL": 3, "BayesRR": 4, "BayesCpi": 5, "BayesDpi": 6}
 _PER_MARKER_VB = {"BayesA", "BayesB", "BayesL", "BayesDpi"}
 KERNELS = {"GRM": 0, "GAU": 1, "EigenGRM": 2, "EigenGAU": 3, "EigenARC": 4}
+KERNELS2 = {"ARC": 0, "GAU": 1}     # the founder-by-sample kinds (BWGR_KZ_*)
 X_I8, X_F32, X_F64 = 0, 1, 2
 HOST, DEVICE = 0, 1
 
@@ -165,6 +166,46 @@ class Panel:
             flag = k in (KERNELS["EigenGRM"], KERNELS["EigenARC"])
         L = _lib.lib()
         return self._nxn(np.float64, device_out, lambda ptr, ld, loc: L.bwgr_panel_kernel(self._h, k, float(par), int(bool(flag)), ptr, ld, loc))
+
+    def _out2d(self, shapes, dtype, device_out, call):
+        """Rectangular results of the founder-by-sample kernels: numpy arrays, or (device_out) torch tensors on the panel's device.
+        call(pointers, leading dimensions, memloc)."""
+        if device_out:
+            import sys
+            torch = sys.modules.get("torch")
+            if torch is None:
+                raise RuntimeError("device_out=True: import torch before calling (the result is a torch tensor)")
+            outs = [torch.empty(sh, dtype=torch.int64 if dtype == np.int64 else torch.float64, device="cuda:%d" % self.device) for sh in shapes]
+            torch.cuda.synchronize(outs[0].device)
+            check(call([C.c_void_p(o.data_ptr()) for o in outs], [sh[1] for sh in shapes], DEVICE))
+            return outs
+        outs = [np.empty(sh, dtype) for sh in shapes]
+        check(call([o.ctypes.data_as(C.c_void_p) for o in outs], [sh[1] for sh in shapes], HOST))
+        return outs
+
+    def _check_other(self, other, who):
+        if not isinstance(other, Panel):
+            raise TypeError("%s: the samples must be a Panel" % who)
+        if other.p != self.p:
+            raise ValueError("%s: the founders have %d columns (markers), the samples %d" % (who, self.p, other.p))
+
+    def crossprod2(self, other, *, device_out=False):
+        """The exact X_f X_s' between this panel's rows (the founders) and another panel's (the samples) over the same markers, n_f x n_s
+        int64 (bwgr_panel_crossprod2)."""
+        self._check_other(other, "crossprod2")
+        L = _lib.lib()
+        return self._out2d([(self.n, other.n)], np.int64, device_out,
+                           lambda ptr, ld, loc: L.bwgr_panel_crossprod2(self._h, other._h, ptr[0], ld[0], loc))[0]
+
+    def kernel2(self, other, kind, par=1.0, *, device_out=False):
+        """The founder-by-sample kernels (Kff, Kfs) of EigenArcZ / EigenGauZ, n_f x n_f and n_f x n_s float64 (bwgr_panel_kernel2): this
+        panel holds the founders, `other` the samples.  kind: "ARC", or "GAU" (par = phi)."""
+        self._check_other(other, "kernel2")
+        k = KERNELS2[kind] if isinstance(kind, str) else int(kind)
+        L = _lib.lib()
+        Kff, Kfs = self._out2d([(self.n, self.n), (self.n, other.n)], np.float64, device_out,
+                               lambda ptr, ld, loc: L.bwgr_panel_kernel2(self._h, other._h, k, float(par), ptr[0], ld[0], ptr[1], ld[1], loc))
+        return Kff, Kfs
 
     def xb(self, B):
         """X B on the raw int8 genotypes for every row, n x k float64 (bwgr_panel_xb); B is p x k or a vector of p."""
@@ -1362,20 +1403,28 @@ def ZFUVBETA(Y, X, **kw):
 
 
 # ---- relationship kernels: GRM / GAU (R/RcppExports.R:100-106), EigenARC / EigenGAU / EigenGRM (:140-150) ----
-def _kernel_panel(X, panel_kw):
-    """X as an int8 panel.  The int8 product is the feature: a float matrix must hold integers in -128..127 (checked here, before the library is
-    touched); float panels are out of scope."""
+def _kernel_input(X):
+    """(X as what Panel() takes for an int8 panel, its number of columns), without touching the library: a Panel, an int8 device tensor, or an
+    int8 numpy matrix.  A float matrix must hold integers in -128..127; float panels are out of scope."""
     if isinstance(X, Panel):
-        return X, False
+        return X, X.p
     if hasattr(X, "data_ptr"):
         if "int8" not in str(X.dtype):
             raise ValueError("relationship kernels take int8 genotypes; got a %s tensor" % (X.dtype,))
-        return Panel(X, **panel_kw), True
+        return X, int(X.shape[0])      # (p, ldx): row j = marker j
     X = np.asarray(X)
     if X.dtype != np.int8:
         if not (X.size and np.all(np.isfinite(X)) and np.all(X == np.rint(X)) and X.min() >= -128 and X.max() <= 127):
             raise ValueError("relationship kernels take integer genotypes in -128..127 (the int8 panel); float panels are not supported")
         X = X.astype(np.int8)
+    return X, (int(X.shape[1]) if X.ndim == 2 else -1)
+
+
+def _kernel_panel(X, panel_kw):
+    """X as an int8 panel.  The int8 product is the feature: the input is checked (_kernel_input) before the library is touched."""
+    X, _ = _kernel_input(X)
+    if isinstance(X, Panel):
+        return X, False
     return Panel(X, **panel_kw), True
 
 
@@ -1421,3 +1470,72 @@ def crossprod(X, *, device_out=False, **kw):
     finally:
         if own:
             P.close()
+
+
+# ---- founder-by-sample kernels: EigenArcZ / EigenGauZ (R/RcppExports.R:248-254) ----
+class _Panels2:
+    """The founders' and the samples' int8 panels of one call, from Panels or matrices under _kernel_panel's rules.  Both inputs are checked,
+    their column counts compared, before the library is touched; the same matrix on both sides makes one panel."""
+
+    def __init__(self, Xf, Xs, who, panel_kw):
+        self._own = []
+        same = Xs is Xf
+        Xf, pf = _kernel_input(Xf)
+        Xs, ps = (Xf, pf) if same else _kernel_input(Xs)
+        if pf != ps:
+            raise ValueError("%s: the founders have %d columns (markers), the samples %d" % (who, pf, ps))
+        try:
+            self.f = self._panel(Xf, panel_kw)
+            self.s = self.f if same else self._panel(Xs, panel_kw)
+        except BaseException:
+            self.close()
+            raise
+
+    def _panel(self, X, panel_kw):
+        if isinstance(X, Panel):
+            return X
+        self._own.append(Panel(X, **panel_kw))
+        return self._own[-1]
+
+    def close(self):
+        for P in self._own:
+            P.close()
+        self._own = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def crossprod2(Xf, Xs, *, device_out=False, **kw):
+    """The exact X_f X_s' of integer genotypes over the same markers, n_f x n_s int64 (the product inside EigenArcZ / EigenGauZ)."""
+    with _Panels2(Xf, Xs, "crossprod2", kw) as P:
+        return P.f.crossprod2(P.s, device_out=device_out)
+
+
+def _kernel2z(kind, Zfndr, Zsamp, par, parts, who, panel_kw):
+    with _Panels2(Zfndr, Zsamp, who, panel_kw) as P:
+        Kff, Kfs = P.f.kernel2(P.s, kind, par)
+    w, V = np.linalg.eigh(Kff)          # ascending, the order of Eigen's SelfAdjointEigenSolver
+    Z = Kfs.T @ (V / np.sqrt(w))
+    if parts:
+        return {"Z": Z, "Kff": Kff, "Kfs": Kfs, "values": w, "vectors": V}
+    return Z
+
+
+def EigenArcZ(Zfndr, Zsamp, cores=1, *, parts=False, **kw):
+    """EigenArcZ(Zfndr, Zsamp, cores), src/RcppEigen20230423.cpp:1877-1907 (cores is accepted and ignored): the samples' coordinates
+    Kfs' V L^(-1/2) in the founders' arc-cosine kernel, n_s x n_f float64.  The library makes Kff and Kfs (Panel.kernel2); the
+    eigendecomposition Kff = V L V' is numpy's, on the host in fp64, eigenvalues ascending.  The columns of Z are defined up to sign, and up
+    to rotation inside close eigenvalues; Z Z' is not affected.  parts=True returns dict(Z, Kff, Kfs, values, vectors)."""
+    return _kernel2z("ARC", Zfndr, Zsamp, 1.0, parts, "EigenArcZ", kw)
+
+
+def EigenGauZ(Zfndr, Zsamp, phi=1.0, cores=1, *, parts=False, **kw):
+    """EigenGauZ(Zfndr, Zsamp, phi, cores), src/RcppEigen20230423.cpp:1910-1939 (cores is accepted and ignored): the samples' coordinates
+    Kfs' V L^(-1/2) in the founders' Gaussian kernel exp(D t), n_s x n_f float64.  The library makes Kff and Kfs (Panel.kernel2); the
+    eigendecomposition Kff = V L V' is numpy's, on the host in fp64, eigenvalues ascending.  The columns of Z are defined up to sign, and up
+    to rotation inside close eigenvalues; Z Z' is not affected.  parts=True returns dict(Z, Kff, Kfs, values, vectors)."""
+    return _kernel2z("GAU", Zfndr, Zsamp, phi, parts, "EigenGauZ", kw)

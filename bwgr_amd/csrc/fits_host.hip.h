@@ -958,3 +958,218 @@ extern "C" int bwgr_panel_kernel(bwgr_panel *P, int kind, double par, int flag, 
   HIPCHK(hipStreamSynchronize(st));
   return BWGR_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// founder-by-sample kernels: the exact X_f X_s' between two int8 panels and the finishes of EigenArcZ / EigenGauZ (kernels.hip.h; DESIGN.md
+// section 4.6)
+// ------------------------------------------------------------------------------------------------
+// The rectangular product's plan, decided here and nowhere else (bwgr_debug_xyt_plan exposes it to the CPU tests): plan_xxt's rules with
+// the int32 bound from the product of the two panels' largest |x| and every tile of the T_f x T_s grid computed.
+struct XytPlan {
+  int64_t chunk = 0, nchunks = 0;   // markers per int32 chunk; chunks
+  int64_t Tf = 0, Ts = 0, tiles = 0;
+  int64_t sub = 1, piece = 0;       // pieces per chunk; markers per piece (whole MFMA steps)
+  int64_t wgs = 0;                  // workgroups launched: tiles x chunks x pieces
+  bool accumulate = false;          // more than one workgroup per tile: they add into the zeroed int64 tile
+  size_t ws_bytes = 0;              // device temporaries of a kernel2 call with host outputs
+};
+static constexpr int XYT_ZERO_WG = 2048;      // workgroups of k_xyt_zero, 256 entries each per trip
+static int plan_xyt(XytPlan &pl, int64_t nf, int64_t ns, int64_t p, int xmaxf, int xmaxs, int64_t kchunk) {
+  pl = XytPlan();
+  CHK(panel_range(nf, p));
+  CHK(panel_range(ns, p));
+  if (xmaxf < 0 || xmaxf > 128 || xmaxs < 0 || xmaxs > 128) return fail(BWGR_EINVAL, "xyt: largest |x| = %d, %d are not int8 panels'", xmaxf, xmaxs);
+  if (kchunk < 0) return fail(BWGR_EINVAL, "xyt: forced chunk %lld < 0", (long long)kchunk);
+  const int64_t xf = std::max(xmaxf, 1), xs = std::max(xmaxs, 1), x2 = xf * xs;
+  if ((long double)x2 * (long double)p >= 9007199254740992.0L)
+    return fail(BWGR_EINVAL, "xyt: max|x_f| * max|x_s| * p = %.3Lg reaches 2^53: the entries of X_f X_s' would not be exact doubles", (long double)x2 * (long double)p);
+  if ((long double)(xf * xf) * (long double)nf * (long double)p >= 9223372036854775808.0L)
+    return fail(BWGR_EINVAL, "xyt: max|x_f|^2 * n_f * p = %.3Lg reaches 2^63: X_f s would not fit int64", (long double)(xf * xf) * (long double)nf * (long double)p);
+  if ((long double)x2 * (long double)nf * (long double)p >= 9223372036854775808.0L)
+    return fail(BWGR_EINVAL, "xyt: max|x_f| * max|x_s| * n_f * p = %.3Lg reaches 2^63: X_s s would not fit int64", (long double)x2 * (long double)nf * (long double)p);
+  const int64_t rule = 2147483647ll / x2;
+  pl.chunk = kchunk > 0 ? std::min(kchunk, rule) : rule;   // (a forced chunk beyond the rule would not be exact)
+  pl.nchunks = (p + pl.chunk - 1) / pl.chunk;
+  pl.Tf = (nf + XXT_TILE - 1) / XXT_TILE; pl.Ts = (ns + XXT_TILE - 1) / XXT_TILE;
+  pl.tiles = pl.Tf * pl.Ts;
+  // pieces: plan_xxt's rule
+  const int64_t span = std::min(pl.chunk, p), steps = (span + XXT_KSTEP - 1) / XXT_KSTEP;
+  const int64_t want = (1024 + pl.tiles * pl.nchunks - 1) / (pl.tiles * pl.nchunks);
+  const int64_t sub0 = std::max<int64_t>(1, std::min(want, steps / 16));
+  pl.piece = (steps + sub0 - 1) / sub0 * XXT_KSTEP;
+  pl.sub = (span + pl.piece - 1) / pl.piece;
+  if (pl.nchunks * pl.sub > 65535) return fail(BWGR_EINVAL, "xyt: %lld chunks of %lld markers exceed the launch grid (65535); use a longer BWGR_KCHUNK", (long long)pl.nchunks, (long long)pl.chunk);
+  if (pl.tiles > 0x7FFFFFFFll) return fail(BWGR_EINVAL, "xyt: %lld output tiles exceed the launch grid", (long long)pl.tiles);
+  pl.wgs = pl.tiles * pl.nchunks * pl.sub;
+  pl.accumulate = pl.nchunks * pl.sub > 1;
+  // the two 8-byte arrays; s and q; X_f s, X_s s and the samples' row sums of squares (padded rows: at least); the founders' diagonal; the
+  // partial sums; the two double terms per founder and per sample of the ARC finish
+  const int64_t ldf = (nf + 127) / 128 * 128, lds = (ns + 127) / 128 * 128;
+  pl.ws_bytes = (size_t)nf * ns * 8 + (size_t)nf * nf * 8 + (size_t)p * 12 + (size_t)(ldf + 2 * lds) * 8 + (size_t)nf * 8 + (size_t)(XXT_SUMD_PARTS + 1) * 8 +
+                (size_t)(nf + ns) * 16;
+  return BWGR_OK;
+}
+extern "C" int bwgr_debug_xyt_plan(int64_t nf, int64_t ns, int64_t p, int xmaxf, int xmaxs, int64_t kchunk, int64_t out[BWGR_XYT_PLAN_NOUT]) {
+  if (!out) return fail(BWGR_EINVAL, "debug_xyt_plan: null pointer");
+  XytPlan pl;
+  CHK(plan_xyt(pl, nf, ns, p, xmaxf, xmaxs, kchunk));
+  const int64_t v[BWGR_XYT_PLAN_NOUT] = {pl.chunk, pl.nchunks, pl.tiles, pl.wgs, (int64_t)pl.ws_bytes, pl.Tf, pl.Ts, pl.sub, pl.piece};
+  std::copy(v, v + BWGR_XYT_PLAN_NOUT, out);
+  return BWGR_OK;
+}
+
+// what the two entry points check alike; leaves the founders' device set.  Nothing is enqueued before it returns BWGR_OK.
+static int xyt_accept(bwgr_panel *Pf, bwgr_panel *Ps, int memloc, const char *who, XytPlan &pl) {
+  if (!Pf || !Ps) return fail(BWGR_EINVAL, "%s: null pointer", who);
+  if (memloc != BWGR_HOST && memloc != BWGR_DEVICE) return fail(BWGR_EINVAL, "%s: bad memloc %d", who, memloc);
+  const PanelData *F = Pf->data, *S = Ps->data;
+  if (F->is_f32) return fail(BWGR_EINVAL, "%s: the founders' panel holds fp32 genotypes; the relationship kernels take int8 panels only", who);
+  if (S->is_f32) return fail(BWGR_EINVAL, "%s: the samples' panel holds fp32 genotypes; the relationship kernels take int8 panels only", who);
+  if (F->p != S->p) return fail(BWGR_EINVAL, "%s: the founders have p = %lld markers, the samples %lld", who, (long long)F->p, (long long)S->p);
+  if (F->device != S->device) return fail(BWGR_EINVAL, "%s: the founders are on device %d, the samples on device %d", who, F->device, S->device);
+  CHK(plan_xyt(pl, F->n, S->n, F->p, F->xmax, S->xmax, F->sw.kchunk));
+  HIPCHK(hipSetDevice(F->device));
+  // these launches fill the chip: nothing is enqueued while sweeps of other handles, whose workgroups must stay co-resident, are in flight
+  // (the samples' own work is waited for, below)
+  if (F->sw.occ_guard) {
+    std::lock_guard<std::mutex> lk(g_guard_mu);
+    const int busy = guard_busy(Pf, Pf->stream, Ps);
+    if (busy > 0) return fail(BWGR_EINVAL, "%s: sweeps of other handles hold %d compute units on this device; wait for them (bwgr_chain_sync) and call again", who, busy);
+  }
+  return BWGR_OK;
+}
+// the founders' stream goes on after everything pending on the samples' stream
+static int xyt_order(bwgr_panel *Pf, bwgr_panel *Ps, DevBufs &bufs, const char *who) {
+  if (Ps->stream == Pf->stream) return BWGR_OK;
+  hipEvent_t ev = bufs.event(hipEventDisableTiming);
+  if (!ev) return fail(BWGR_EHIP, "%s: hipEventCreate failed", who);
+  HIPCHK(hipEventRecord(ev, Ps->stream));
+  HIPCHK(hipStreamWaitEvent(Pf->stream, ev, 0));
+  return BWGR_OK;
+}
+// G = X_f X_s' into the device array Gd (n_f x n_s int64, row stride ldg); enqueued on the founders' stream
+static int xyt_product(bwgr_panel *Pf, bwgr_panel *Ps, const XytPlan &pl, long long *Gd, int64_t ldg) {
+  const PanelData *F = Pf->data, *S = Ps->data;
+  hipStream_t st = Pf->stream;
+  XytArgs a;
+  a.XA = (const int8_t *)F->X; a.XB = (const int8_t *)S->X; a.p = F->p; a.RA = F->plan.R; a.RB = S->plan.R; a.nA = (int)F->n; a.nB = (int)S->n;
+  a.TB = (int)pl.Ts; a.chunk = pl.chunk; a.piece = pl.piece; a.sub = (int)pl.sub; a.accumulate = pl.accumulate ? 1 : 0; a.G = Gd; a.ldg = ldg;
+  if (pl.accumulate) hipLaunchKernelGGL(k_xyt_zero, dim3(XYT_ZERO_WG), dim3(TAIL_THREADS), 0, st, Gd, ldg, (int)F->n, (int)S->n);
+  hipLaunchKernelGGL(k_xyt_mfma_i8, dim3((unsigned)pl.tiles, (unsigned)(pl.nchunks * pl.sub)), dim3(256), 0, st, a);
+  HIPCHK(hipGetLastError());
+  return BWGR_OK;
+}
+// an nr x nc 8-byte result to the caller's host array
+static int xyt_to_host(hipStream_t st, void *dst, int64_t ldo, const void *src, int64_t nr, int64_t nc) {
+  HIPCHK(hipMemcpy2DAsync(dst, (size_t)ldo * 8, src, (size_t)nc * 8, (size_t)nc * 8, (size_t)nr, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return BWGR_OK;
+}
+
+extern "C" int bwgr_panel_crossprod2(bwgr_panel *Pf, bwgr_panel *Ps, int64_t *G, int64_t ldg, int memloc) {
+  if (!G) return fail(BWGR_EINVAL, "panel_crossprod2: null pointer");
+  if (Pf && Ps && ldg < Ps->data->n) return fail(BWGR_EINVAL, "panel_crossprod2: leading dimension %lld < n_s = %lld", (long long)ldg, (long long)Ps->data->n);
+  XytPlan pl;
+  CHK(xyt_accept(Pf, Ps, memloc, "panel_crossprod2", pl));
+  const int64_t nf = Pf->data->n, ns = Ps->data->n;
+  DevBufs bufs(Pf->stream);
+  long long *Gd = reinterpret_cast<long long *>(G); int64_t ldd = ldg;
+  if (memloc == BWGR_HOST) {
+    Gd = bufs.get<long long>((size_t)nf * ns); ldd = ns;
+    if (bufs.failed()) return no_memory("panel_crossprod2");
+  }
+  CHK(xyt_order(Pf, Ps, bufs, "panel_crossprod2"));
+  CHK(xyt_product(Pf, Ps, pl, Gd, ldd));
+  if (memloc == BWGR_HOST) return xyt_to_host(Pf->stream, G, ldg, Gd, nf, ns);
+  HIPCHK(hipStreamSynchronize(Pf->stream));
+  return BWGR_OK;
+}
+
+// the grid of k_kfin_xs / k_kfin2_rowsq over a panel of ld padded rows: 128 rows per workgroup, the markers split so that the launch fills the chip
+static inline dim3 kfin_rows_grid(int64_t ld, int64_t p, int64_t *cpw) {
+  const int64_t ysplit = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(65535, (p + 511) / 512), 2048 / (ld / 128) + 1));
+  *cpw = (p + ysplit - 1) / ysplit;
+  return dim3((unsigned)(ld / 128), (unsigned)((p + *cpw - 1) / *cpw));
+}
+
+extern "C" int bwgr_panel_kernel2(bwgr_panel *Pf, bwgr_panel *Ps, int kind, double par, double *Kff, int64_t ldff, double *Kfs, int64_t ldfs, int memloc) {
+  if (kind != BWGR_KZ_ARC && kind != BWGR_KZ_GAU) return fail(BWGR_EINVAL, "panel_kernel2: unknown kind %d", kind);
+  if (!Kff || !Kfs) return fail(BWGR_EINVAL, "panel_kernel2: null pointer");
+  if (Pf && Ps && ldff < Pf->data->n) return fail(BWGR_EINVAL, "panel_kernel2: leading dimension %lld of Kff < n_f = %lld", (long long)ldff, (long long)Pf->data->n);
+  if (Pf && Ps && ldfs < Ps->data->n) return fail(BWGR_EINVAL, "panel_kernel2: leading dimension %lld of Kfs < n_s = %lld", (long long)ldfs, (long long)Ps->data->n);
+  XytPlan pl;
+  CHK(xyt_accept(Pf, Ps, memloc, "panel_kernel2", pl));
+  const PanelData *F = Pf->data, *S = Ps->data;
+  XxtPlan plf;      // K_ff's product is the symmetric one
+  CHK(plan_xxt(plf, F->n, F->p, F->xmax, F->sw.kchunk));
+  const int64_t nf = F->n, ns = S->n, p = F->p, ldf = F->plan.ld, lds = S->plan.ld;
+  const bool arc = kind == BWGR_KZ_ARC;
+  hipStream_t st = Pf->stream;
+  std::vector<long long> diag((size_t)nf), qs, rf, rs;
+  std::vector<int32_t> s;
+  std::vector<double> h_r, h_d;     // ARC: r_f | r_s; d_f | d_s
+  DevBufs bufs(st);
+  long long *Gff = reinterpret_cast<long long *>(Kff), *Gfs = reinterpret_cast<long long *>(Kfs); int64_t ldd_ff = ldff, ldd_fs = ldfs;
+  if (memloc == BWGR_HOST) { Gff = bufs.get<long long>((size_t)nf * nf); ldd_ff = nf; Gfs = bufs.get<long long>((size_t)nf * ns); ldd_fs = ns; }
+  long long *diag_d = bufs.get<long long>((size_t)nf), *qs_d = bufs.get<long long>((size_t)lds);
+  long long *rf_d = arc ? bufs.get<long long>((size_t)ldf) : nullptr, *rs_d = arc ? bufs.get<long long>((size_t)lds) : nullptr, *q_d = arc ? bufs.get<long long>((size_t)p) : nullptr;
+  int32_t *s_d = arc ? bufs.get<int32_t>((size_t)p) : nullptr;
+  double *r_d = arc ? bufs.get<double>((size_t)(nf + ns)) : nullptr, *d_d = arc ? bufs.get<double>((size_t)(nf + ns)) : nullptr;
+  double *part = arc ? nullptr : bufs.get<double>(XXT_SUMD_PARTS + 1);
+  if (bufs.failed()) return no_memory("panel_kernel2");
+  CHK(xyt_order(Pf, Ps, bufs, "panel_kernel2"));
+  CHK(xxt_product(Pf, plf, Gff, ldd_ff));
+  CHK(xyt_product(Pf, Ps, pl, Gfs, ldd_fs));
+  hipLaunchKernelGGL(k_kfin_diag, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, Gff, ldd_ff, (int)nf, diag_d);
+  int64_t cpw = 0;
+  HIPCHK(zero(st, qs_d, (size_t)lds));
+  { const dim3 g = kfin_rows_grid(lds, p, &cpw); hipLaunchKernelGGL(k_kfin2_rowsq, g, dim3(256), 0, st, (const int8_t *)S->X, S->plan.R, p, cpw, qs_d); }
+  if (arc) {
+    hipLaunchKernelGGL(k_kfin_colstats, dim3((unsigned)((p + 3) / 4)), dim3(256), 0, st, (const int8_t *)F->X, F->plan.R, (int)nf, p, s_d, q_d);
+    HIPCHK(zero(st, rf_d, (size_t)ldf)); HIPCHK(zero(st, rs_d, (size_t)lds));
+    { const dim3 g = kfin_rows_grid(ldf, p, &cpw); hipLaunchKernelGGL(k_kfin_xs, g, dim3(256), 0, st, (const int8_t *)F->X, F->plan.R, p, s_d, cpw, rf_d); }
+    { const dim3 g = kfin_rows_grid(lds, p, &cpw); hipLaunchKernelGGL(k_kfin_xs, g, dim3(256), 0, st, (const int8_t *)S->X, S->plan.R, p, s_d, cpw, rs_d); }
+  }
+  HIPCHK(hipGetLastError());
+  Kfin2Args a;
+  a.kind = arc ? KFIN2_ARC : KFIN2_GAU; a.irow = diag_d; a.icol = diag_d; a.rrow = a.rcol = a.drow = a.dcol = nullptr; a.c = 0.0; a.scale = 1.0;
+  const double nd = (double)nf, ninv = 1.0 / nd;
+  if (arc) {
+    qs.resize((size_t)ns); rf.resize((size_t)nf); rs.resize((size_t)ns); s.resize((size_t)p);
+    HIPCHK(hipMemcpyAsync(diag.data(), diag_d, sizeof(long long) * nf, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(qs.data(), qs_d, sizeof(long long) * ns, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(rf.data(), rf_d, sizeof(long long) * nf, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(rs.data(), rs_d, sizeof(long long) * ns, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(s.data(), s_d, sizeof(int32_t) * p, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    // ---- the global scalars and the per-row terms, on the host in a fixed order from the exact integers ----
+    double c = 0.0;
+    for (int64_t j = 0; j < p; ++j) { const double m = (double)s[j] * ninv; c += m * m; }
+    h_r.resize((size_t)(nf + ns)); h_d.resize((size_t)(nf + ns));
+    for (int64_t i = 0; i < nf; ++i) { const double r = (double)rf[i] * ninv; h_r[i] = r; h_d[i] = (double)diag[i] - (r + r) + c; }
+    for (int64_t j = 0; j < ns; ++j) { const double r = (double)rs[j] * ninv; h_r[nf + j] = r; h_d[nf + j] = (double)qs[j] - (r + r) + c; }
+    double sd = 0.0;                   // the finished diagonal of K_ff before Kscalar: it depends on d_f alone
+    for (int64_t i = 0; i < nf; ++i) sd += kfin2_arc(h_d[i], h_d[i], h_d[i]);
+    a.c = c; a.scale = 1.0 / (sd / nd);                                                                 // Kscalar, RcppEigen20230423.cpp:1896
+    HIPCHK(h2d(st, r_d, h_r.data(), (size_t)(nf + ns))); HIPCHK(h2d(st, d_d, h_d.data(), (size_t)(nf + ns)));
+    a.rrow = r_d; a.drow = d_d;
+  } else {
+    double sumd = 0.0;                 // n_f (n_f - 1) in double: the reference's int product overflows beyond 46 340 founders
+    hipLaunchKernelGGL(k_kfin_sumd_stage1, dim3(XXT_SUMD_PARTS), dim3(256), 0, st, Gff, ldd_ff, diag_d, (int)nf, part);
+    hipLaunchKernelGGL(k_kfin_sumd_stage2, dim3(1), dim3(256), 0, st, part, XXT_SUMD_PARTS, part + XXT_SUMD_PARTS);
+    HIPCHK(hipGetLastError());
+    HIPCHK(d2h(st, &sumd, part + XXT_SUMD_PARTS, sizeof(double)));
+    a.scale = par * (-(nd * (nd - 1.0))) / sumd;                                                        // tmp, :1929
+  }
+  // K_ff, then K_fs (both read the founders' diagonal, which K_ff's finish overwrites only in G: diag_d is the copy)
+  a.G = Gff; a.ldg = ldd_ff; a.nr = (int)nf; a.nc = (int)nf; a.same = 1;
+  if (arc) { a.rcol = r_d; a.dcol = d_d; }
+  hipLaunchKernelGGL(k_kfin2_apply, dim3(KFIN_APPLY_WG), dim3(TAIL_THREADS), 0, st, a);
+  a.G = Gfs; a.ldg = ldd_fs; a.nc = (int)ns; a.same = 0; a.icol = qs_d;
+  if (arc) { a.rcol = r_d + nf; a.dcol = d_d + nf; }
+  hipLaunchKernelGGL(k_kfin2_apply, dim3(KFIN_APPLY_WG), dim3(TAIL_THREADS), 0, st, a);
+  HIPCHK(hipGetLastError());
+  if (memloc == BWGR_HOST) { CHK(xyt_to_host(st, Kff, ldff, Gff, nf, nf)); return xyt_to_host(st, Kfs, ldfs, Gfs, nf, ns); }
+  HIPCHK(hipStreamSynchronize(st));
+  return BWGR_OK;
+}

@@ -1,9 +1,11 @@
 // kernels.hip.h -- relationship kernels on the resident int8 panel: the exact product G = X X' (n x n int64, k_xxt_*) and the fp64
 // finishes that turn it into GRM / GAU (src/Rcpp20260726ai.cpp:1338-1383) and EigenGRM / EigenGAU / EigenARC
-// (src/RcppEigen20230423.cpp:8-51) (k_kfin_*).  DESIGN.md section 4.6 has the layout problem and the reasons for the choices below.
+// (src/RcppEigen20230423.cpp:8-51) (k_kfin_*); the exact product X_f X_s' between two panels over the same markers (k_xyt_mfma_i8) and
+// the finishes of the founder-by-sample kernels EigenArcZ / EigenGauZ (src/RcppEigen20230423.cpp:1877-1939) (k_kfin2_*).  DESIGN.md
+// section 4.6 has the layout problem and the reasons for the choices below.
 //
 // Out of scope here: fp32 panels (they need a float product with a numerics contract of its own), EigenEVD / K2X / mkr / mkr2X (the
-// eigendecomposition stays with the caller), EigenArcZ / EigenGauZ, CNT / IMP / SPC / SPM, and sharding the product over GPUs.
+// eigendecomposition stays with the caller), CNT / IMP / SPC / SPM, and sharding the product over GPUs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -163,6 +165,132 @@ __global__ __launch_bounds__(256) void k_xxt_mirror(long long *G, int64_t ldg, i
   }
 }
 
+// ---- the product between two panels --------------------------------------------------------------------------------------------------
+struct XytArgs {
+  const int8_t *XA, *XB;    // the founders' panel (rows of G) and the samples' (columns of G): the same p markers
+  int64_t p;
+  int RA, RB;               // slab rows of either panel (made independently: they may differ)
+  int nA, nB, TB;           // real rows of either panel; column tiles
+  int64_t chunk, piece;     // as XxtArgs
+  int sub, accumulate;
+  long long *G;
+  int64_t ldg;
+};
+
+// G = X_A X_B' on k_xxt_mfma_i8's tile: four waves on a 128 x 128 tile, a 64 x 64 quadrant each, dword loads, the two rounds of
+// v_perm_b32, one register set per wave, no LDS, no barrier.  The marker order inside a step and the row order inside a wave's 64 rows are
+// free as long as both operands use the same maps; they do, and only the slab height that turns a marker into an address differs between the
+// operands, so each has its own sixteen loop-constant lane offsets.  Every tile of the T_A x T_B grid is computed (no triangle, no mirror)
+// and the write-out guards the rows against n_A and the columns against n_B.  The paddings of both panels are zero.
+//
+// blockIdx.x: ti * TB + tj; blockIdx.y: chunk * sub + piece.
+__global__ __launch_bounds__(256) void k_xyt_mfma_i8(const XytArgs a) {
+  const int ti = blockIdx.x / a.TB, tj = blockIdx.x - ti * a.TB;
+  const int64_t c = blockIdx.y / a.sub, s = blockIdx.y - c * a.sub;
+  const int64_t chunk_hi = min(a.p, (c + 1) * a.chunk);
+  const int64_t lo = c * a.chunk + s * a.piece, hi = min(chunk_hi, lo + a.piece);
+  if (lo >= hi) return;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), m16 = lane & 15, grp = lane >> 4;
+  const int rA0 = XXT_TILE * ti + 64 * (wave >> 1), rB0 = XXT_TILE * tj + 64 * (wave & 1);
+  const int RA = a.RA, RB = a.RB;
+  // slab bases (a tile never crosses a slab of its panel: RA and RB are multiples of 128); marker j adds j * RA, j * RB
+  const int8_t *ubA = a.XA + (size_t)(rA0 / RA) * a.p * RA + (rA0 % RA);
+  const int8_t *ubB = a.XB + (size_t)(rB0 / RB) * a.p * RB + (rB0 % RB);
+
+  s2_v4i acc[4][4];
+#pragma unroll
+  for (int x = 0; x < 4; ++x)
+#pragma unroll
+    for (int y = 0; y < 4; ++y) acc[x][y] = s2_v4i{0, 0, 0, 0};
+
+  // whole steps: a wave-uniform base per panel and the lane's sixteen 32-bit offsets per panel, constant over the loop
+  uint32_t voffA[4][4], voffB[4][4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      voffA[u][q] = (uint32_t)(16 * u + q + 4 * grp) * (uint32_t)RA + 4u * m16;
+      voffB[u][q] = (uint32_t)(16 * u + q + 4 * grp) * (uint32_t)RB + 4u * m16;
+    }
+  auto load_full = [&](int64_t j0, uint32_t (&ca)[4][4], uint32_t (&cb)[4][4]) {
+    const int8_t *pa = ubA + (size_t)j0 * RA, *pb = ubB + (size_t)j0 * RB;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        ca[u][q] = *reinterpret_cast<const uint32_t *>(pa + voffA[u][q]);
+        cb[u][q] = *reinterpret_cast<const uint32_t *>(pb + voffB[u][q]);
+      }
+  };
+  // the last, partial step: markers past `hi` are read at hi - 1 and zeroed
+  auto load_tail = [&](int64_t j0, uint32_t (&ca)[4][4], uint32_t (&cb)[4][4]) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int64_t j = j0 + 16 * u + q + 4 * grp;
+        const bool ok = j < hi;
+        const size_t jj = (size_t)(ok ? j : hi - 1);
+        const uint32_t va = *reinterpret_cast<const uint32_t *>(ubA + jj * RA + 4u * m16), vb = *reinterpret_cast<const uint32_t *>(ubB + jj * RB + 4u * m16);
+        ca[u][q] = ok ? va : 0u; cb[u][q] = ok ? vb : 0u;
+      }
+  };
+  // rw[x] = the operand of MFMA tile x: bytes (u, q) = row 4 m16 + x of marker 16 u + 4 grp + q (k_xxt_mfma_i8's transposition)
+  auto transpose = [](const uint32_t (&cc)[4][4], s2_v4i (&rw)[4]) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const uint32_t t0 = __builtin_amdgcn_perm(cc[u][1], cc[u][0], 0x05010400u), t1 = __builtin_amdgcn_perm(cc[u][1], cc[u][0], 0x07030602u);
+      const uint32_t t2 = __builtin_amdgcn_perm(cc[u][3], cc[u][2], 0x05010400u), t3 = __builtin_amdgcn_perm(cc[u][3], cc[u][2], 0x07030602u);
+      rw[0][u] = (int)__builtin_amdgcn_perm(t2, t0, 0x05040100u); rw[1][u] = (int)__builtin_amdgcn_perm(t2, t0, 0x07060302u);
+      rw[2][u] = (int)__builtin_amdgcn_perm(t3, t1, 0x05040100u); rw[3][u] = (int)__builtin_amdgcn_perm(t3, t1, 0x07060302u);
+    }
+  };
+  auto mma = [&](const uint32_t (&ca)[4][4], const uint32_t (&cb)[4][4]) {
+    s2_v4i ra[4], rb[4];
+    transpose(ca, ra); transpose(cb, rb);
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+#pragma unroll
+      for (int y = 0; y < 4; ++y) acc[x][y] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ra[x], rb[y], acc[x][y], 0, 0, 0);
+  };
+
+  const int64_t nfull = (hi - lo) / XXT_KSTEP;
+  uint32_t ca[4][4], cb[4][4];
+  for (int64_t k = 0; k < nfull; ++k) {
+    load_full(lo + XXT_KSTEP * k, ca, cb);
+    mma(ca, cb);
+  }
+  if (lo + nfull * XXT_KSTEP < hi) {
+    load_tail(lo + nfull * XXT_KSTEP, ca, cb);
+    mma(ca, cb);
+  }
+
+  // acc[x][y][reg] of lane (m16, grp) = G[rA0 + 4 (4 grp + reg) + x][rB0 + 4 m16 + y]
+#pragma unroll
+  for (int x = 0; x < 4; ++x)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int row = rA0 + 4 * (4 * grp + reg) + x;
+      if (row >= a.nA) continue;
+      long long *g = a.G + (size_t)row * a.ldg + rB0 + 4 * m16;
+#pragma unroll
+      for (int y = 0; y < 4; ++y) {
+        if (rB0 + 4 * m16 + y >= a.nB) continue;
+        if (a.accumulate) atomicAdd(reinterpret_cast<unsigned long long *>(g + y), (unsigned long long)(long long)acc[x][y][reg]);
+        else g[y] = (long long)acc[x][y][reg];
+      }
+    }
+}
+
+// the nA x nB entries of an int64 matrix set to zero (before an accumulating product); entries beyond column nB of a row are not touched
+__global__ void k_xyt_zero(long long *G, int64_t ldg, int nA, int nB) {
+  const int64_t total = (int64_t)nA * nB;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = idx / nB, j = idx - i * nB;
+    G[(size_t)i * ldg + j] = 0;
+  }
+}
+
 // ---- the finishes -------------------------------------------------------------------------------------------------------------------
 // s_j = sum_i x_ij and q_j = sum_i x_ij^2, exact; one wave per marker
 __global__ void k_kfin_colstats(const int8_t *X, int R, int n, int64_t p, int32_t *s, long long *q) {
@@ -264,6 +392,64 @@ __global__ __launch_bounds__(256) void k_kfin_apply(const KfinArgs a) {
         k = nrm / 3.1416 * (sin(th) + (3.1416 - th) * cos(th));
       }
     }
+    *reinterpret_cast<double *>(gp) = k;
+  }
+}
+
+// ---- the founder-by-sample finishes (EigenArcZ / EigenGauZ) ------------------------------------------------------------------------------
+// q_i = sum_j x_ij^2 over a panel's rows, exact in int64: diag(X X') without the product (q zeroed by the caller, ld entries; padded rows
+// add 0).  k_kfin_xs's shape: a workgroup takes 128 rows and `cols` markers, its eight groups every eighth of them.
+__global__ __launch_bounds__(256) void k_kfin2_rowsq(const int8_t *X, int R, int64_t p, int64_t cols, long long *q) {
+  __shared__ long long red[8][128];
+  const int tx = threadIdx.x & 31, g = threadIdx.x >> 5;
+  const int r0 = 128 * blockIdx.x;
+  const int64_t j0 = (int64_t)blockIdx.y * cols, j1 = min(p, j0 + cols);
+  const int8_t *base = X + (size_t)(r0 / R) * p * R + (r0 % R) + 4 * tx;
+  long long acc[4] = {0, 0, 0, 0};
+  for (int64_t j = j0 + g; j < j1; j += 8) {
+    const uint32_t w = *reinterpret_cast<const uint32_t *>(base + (size_t)j * R);
+#pragma unroll
+    for (int b = 0; b < 4; ++b) { const int v = (int)(int8_t)(w >> (8 * b)); acc[b] += v * v; }
+  }
+#pragma unroll
+  for (int b = 0; b < 4; ++b) red[g][4 * tx + b] = acc[b];
+  __syncthreads();
+  if (threadIdx.x < 128) {
+    long long v = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v += red[k][threadIdx.x];
+    atomicAdd(reinterpret_cast<unsigned long long *>(q + r0 + threadIdx.x), (unsigned long long)v);
+  }
+}
+
+enum { KFIN2_ARC = 0, KFIN2_GAU = 1 };
+// One element of either kind.  The literals as the reference writes them (3.14159 here, not EigenARC's 3.1416).
+// ARC: a = the product centred by the founders' column means, da and db the two centred squared norms; the value before Kscalar.
+__host__ __device__ inline double kfin2_arc(double a, double da, double db) {
+  const double nrm = sqrt(da * db * 1.001);
+  double t = acos(a / nrm);
+  t = nrm * (sin(t) + (3.14159 - t) * cos(t));
+  return t / 3.14159;
+}
+// The element-wise finish of K_ff (same = 1: rows and columns are both the founders, zero distance on the diagonal) and of K_fs, in place:
+// the int64 G_ij becomes the double K_ij.  A row brings its founder's terms, a column its own; in K_ff both come from the same arrays and
+// every expression is symmetric in (i, j) operand by operand, so K_ff is exactly symmetric.
+struct Kfin2Args {
+  long long *G; int64_t ldg; int nr, nc; int kind, same;
+  const long long *irow, *icol;   // GAU: G_ff[i][i]; the column's squared norm (K_ff: G_ff[j][j]; K_fs: q_s,j)
+  const double *rrow, *rcol;      // ARC: r_f,i = (X_f s)_i / n_f; the column's (K_ff: r_f,j; K_fs: r_s,j = (X_s s)_j / n_f)
+  const double *drow, *dcol;      // ARC: the centred squared norms d_f,i; d_f,j or d_s,j
+  double c, scale;                // ARC: sum_j mean_j^2, Kscalar; GAU: -, t
+};
+__global__ __launch_bounds__(256) void k_kfin2_apply(const Kfin2Args a) {
+  const int64_t total = (int64_t)a.nr * a.nc;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+    const int i = (int)(idx / a.nc), j = (int)(idx - (int64_t)i * a.nc);
+    long long *gp = a.G + (size_t)i * a.ldg + j;
+    const long long g = *gp;
+    double k;
+    if (a.kind == KFIN2_GAU) k = exp(((a.same && i == j) ? 0.0 : sqrt((double)(a.irow[i] + a.icol[j] - 2 * g))) * a.scale);
+    else k = kfin2_arc((double)g - (a.rrow[i] + a.rcol[j]) + a.c, a.drow[i], a.dcol[j]) * a.scale;
     *reinterpret_cast<double *>(gp) = k;
   }
 }

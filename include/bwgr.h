@@ -402,8 +402,8 @@ int bwgr_debug_aux_plan(int is_f32, int64_t p, int64_t ld, int64_t out[BWGR_AUX_
  * Both entry points run on the panel's stream, return when the result is complete, and return BWGR_EINVAL without enqueuing anything while
  * sweeps of other handles are in flight on the device (occupancy guard, above).  Also BWGR_EINVAL: fp32 panels, an unknown kind, a leading
  * dimension below n, max|x|^2 * p >= 2^53 or max|x|^2 * n * p >= 2^63.  BWGR_KCHUNK (read when the root panel is made) forces a shorter chunk.
- * Not here: fp32 panels, EigenEVD / K2X / mkr / mkr2X (the eigendecomposition stays with the caller), EigenArcZ / EigenGauZ, CNT / IMP / SPC /
- * SPM, and a product sharded over GPUs. */
+ * Not here: fp32 panels, EigenEVD / K2X / mkr / mkr2X (the eigendecomposition stays with the caller), CNT / IMP / SPC / SPM, and a product
+ * sharded over GPUs. */
 enum { BWGR_K_GRM = 0, BWGR_K_GAU = 1, BWGR_K_EIGEN_GRM = 2, BWGR_K_EIGEN_GAU = 3, BWGR_K_EIGEN_ARC = 4 };
 /* exact X X' over the panel's n rows (the Eigen product of src/RcppEigen20230423.cpp:17, :32, :48, in integers): G is n x n int64, ldg >= n,
  * host or device per memloc */
@@ -418,6 +418,41 @@ int bwgr_panel_kernel(bwgr_panel *P, int kind, double par, int flag, double *K, 
  * a chunk is split into, markers per piece.  Refused shapes return their code with the message in bwgr_last_error. */
 #define BWGR_XXT_PLAN_NOUT 8
 int bwgr_debug_xxt_plan(int64_t n, int64_t p, int xmax, int64_t kchunk, int64_t out[BWGR_XXT_PLAN_NOUT]);
+
+/* ---- founder-by-sample kernels on two resident panels -----------------------------------------------------------
+ * Replaces the products and finishes inside EigenArcZ(Zfndr, Zsamp, cores) src/RcppEigen20230423.cpp:1877-1907 and EigenGauZ(Zfndr, Zsamp,
+ * phi, cores) :1910-1939 (R/RcppExports.R:248-254): K_ff between the founders and K_fs between founders and samples, from which the caller
+ * makes the samples' coordinates K_fs' V L^(-1/2) with the eigendecomposition K_ff = V L V' (which stays with the caller).  Pf and Ps are
+ * int8 panels over the same p markers on the same device, roots or clones, of any geometry each; Pf == Ps is allowed; a panel switched to
+ * implicit centring gives the same results.  The product X_f X_s' is exact in integers: int32 sums over chunks of at most
+ * floor((2^31 - 1) / (max|x_f| max|x_s|)) markers added in int64, every 128 x 128 tile of the n_f x n_s result computed.  The finishes are
+ * the fp64 values of the reference's float formulas from the exact integers, its literals 3.14159 and 1.001 included.  ARC: both matrices
+ * centred by the FOUNDERS' column means (through the centring identity), K = N (sin t + (3.14159 - t) cos t) / 3.14159 with N = sqrt(d_a d_b
+ * 1.001), t = acos(A / N), both outputs times Kscalar = 1 / mean(diag K_ff).  GAU: raw genotypes, D = the Euclidean distance, K = exp(D t),
+ * t = par * (-n_f (n_f - 1)) / sum_{i != i'} D_ff; n_f (n_f - 1) is formed in double (the reference's int product overflows beyond 46 340
+ * founders).  Degenerate inputs follow that arithmetic and are not refused: a row of zero centred norm gives NaN under ARC, duplicate
+ * founders a singular K_ff.  Two calls give the same bits.
+ * Both entry points enqueue on Pf's stream after everything pending on Ps's stream, return when the result is complete, and return
+ * BWGR_EINVAL without enqueuing anything (both panels stay usable) while sweeps of other handles are in flight on the device (occupancy guard,
+ * above) and for: a null pointer, a bad memloc, an fp32 panel on either side, different p, different devices, a leading dimension below its
+ * row length, an unknown kind, max|x_f| max|x_s| p >= 2^53, max|x_f|^2 n_f p >= 2^63 or max|x_f| max|x_s| n_f p >= 2^63 (the int64 bounds of
+ * X_f s_f and X_s s_f), a grid beyond the launch limits.  BWGR_KCHUNK forces a shorter chunk; it is read when the founders' root panel is
+ * made. */
+/* G (n_f x n_s int64, G[i * ldg + j] = x_f,i . x_s,j, ldg >= n_s, host or device per memloc); entries beyond column n_s of a row are not
+ * touched.  bwgr_panel_crossprod2(P, P, ...) equals bwgr_panel_crossprod(P, ...) bit for bit. */
+int bwgr_panel_crossprod2(bwgr_panel *Pf, bwgr_panel *Ps, int64_t *G, int64_t ldg, int memloc);
+enum { BWGR_KZ_ARC = 0, BWGR_KZ_GAU = 1 };
+/* Kff: n_f x n_f doubles, exactly symmetric, ldff >= n_f; Kfs: n_f x n_s doubles, row i = founder i, ldfs >= n_s; both required, host or
+ * device per memloc; par: phi for GAU (reference default 1.0; ignored for ARC).  Entries beyond the last column of a row are not touched.
+ * Device outputs serve as the call's own workspaces; host outputs need one n_f x n_s and one n_f x n_f 8-byte device array. */
+int bwgr_panel_kernel2(bwgr_panel *Pf, bwgr_panel *Ps, int kind, double par, double *Kff, int64_t ldff, double *Kfs, int64_t ldfs, int memloc);
+/* host arithmetic of the rectangular product's plan (needs no GPU), in the style of bwgr_debug_xxt_plan: for n_f, n_s, p, the two panels'
+ * largest |x| and a forced chunk (0 = the rule above; a forced chunk beyond the rule is cut to it) out[0..8] = markers per chunk, chunks,
+ * output tiles (T_f * T_s), workgroups launched (more than the tiles exactly when the workgroups of a tile add into it), workspace bytes of
+ * a kernel2 call with host outputs, T_f, T_s, pieces a chunk is split into, markers per piece.  Refused shapes return their code with the
+ * message in bwgr_last_error. */
+#define BWGR_XYT_PLAN_NOUT 9
+int bwgr_debug_xyt_plan(int64_t nf, int64_t ns, int64_t p, int xmaxf, int xmaxs, int64_t kchunk, int64_t out[BWGR_XYT_PLAN_NOUT]);
 
 /* ---- synthetic panels ----------------------------------------------------------
  * X_ij ~ Binomial(2, f_j), f_j ~ U(0.05,0.5), int8 column-major written to device memory Xdev

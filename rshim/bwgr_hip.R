@@ -178,3 +178,16 @@ EigenGRM <- function(X, centralizeZ = TRUE, cores = 1L) .bwgr_kernel(2L, X, 1.0,
 EigenGAU <- function(X, phi = 1.0, cores = 1L) .bwgr_kernel(3L, X, phi)
 EigenARC <- function(X, centralizeX = TRUE, cores = 1L) .bwgr_kernel(4L, X, 1.0, centralizeX)
 .bwgr_crossprod <- function(X) .Call("bwgrhip_crossprod", .bwgr_ipanel(X))   # the exact X X' (tcrossprod) of integer genotypes
+# founder-by-sample kernels, R/RcppExports.R:248-254 (EigenArcZ, EigenGauZ; src/RcppEigen20230423.cpp:1877-1939): same names, argument order
+# and defaults; integer genotypes only; `cores` is ignored.  The library makes K_ff and K_fs, eigen() here the founders' rotation; the result
+# is the samples' coordinates t(K_fs) V L^(-1/2), nrow(Zsamp) x nrow(Zfndr).  Its columns are defined up to sign, and up to rotation inside
+# close eigenvalues; Z Z' is not affected.  (eigen() returns descending eigenvalues, Eigen's solver ascending: the columns come reversed.)
+.bwgr_kernel2 <- function(kind, Zfndr, Zsamp, par = 1.0) {
+  if (ncol(Zfndr) != ncol(Zsamp)) stop("Zfndr and Zsamp must have the same columns (markers)")
+  k <- .Call("bwgrhip_kernel2", .bwgr_ipanel(Zfndr), .bwgr_ipanel(Zsamp), as.integer(kind), as.double(par))
+  e <- eigen(k$Kff, symmetric = TRUE); o <- rev(seq_along(e$values))
+  k$Ksf %*% sweep(e$vectors[, o, drop = FALSE], 2, sqrt(e$values[o]), "/")
+}
+EigenArcZ <- function(Zfndr, Zsamp, cores = 1L) .bwgr_kernel2(0L, Zfndr, Zsamp)
+EigenGauZ <- function(Zfndr, Zsamp, phi = 1.0, cores = 1L) .bwgr_kernel2(1L, Zfndr, Zsamp, phi)
+.bwgr_crossprod2 <- function(Xf, Xs) .Call("bwgrhip_crossprod2", .bwgr_ipanel(Xf), .bwgr_ipanel(Xs))   # the exact Xs Xf' (tcrossprod(Xs, Xf))

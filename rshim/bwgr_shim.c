@@ -9,6 +9,7 @@
  *     _bWGR_KMUP2     src/RcppExports.cpp:34-50      -> bwgrhip_KMUP2    (9 args)
  *     _bWGR_BayesA..  src/RcppExports.cpp:177-290    -> bwgrhip_Bayes    (model + 7 args)
  *     _bWGR_GRM, _bWGR_GAU, _bWGR_EigenGRM / GAU / ARC      -> bwgrhip_kernel   (kind + 2 args)
+ *     _bWGR_EigenArcZ, _bWGR_EigenGauZ                      -> bwgrhip_kernel2  (kind + phi; eigen() stays in R)
  * and adds bwgrhip_wgr (R/wgr.R:2-169 as one device-resident call) plus panel handles so that X is staged in HBM
  * once instead of being converted SEXP -> Eigen::MatrixXf on every call (src/RcppExports.cpp:20).
  *
@@ -416,6 +417,38 @@ SEXP bwgrhip_crossprod(SEXP panel) {
   return G;
 }
 
+/* founder-by-sample kernels: the K_ff and K_fs of EigenArcZ / EigenGauZ(Zfndr, Zsamp, ., cores) src/RcppEigen20230423.cpp:1877-1939 ->
+ * list(Kff = n_f x n_f, Ksf = n_s x n_f): the library's row-major n_f x n_s K_fs is R's column-major t(K_fs).  kind: BWGR_KZ_*; par: phi. */
+SEXP bwgrhip_kernel2(SEXP fndr, SEXP samp, SEXP kind, SEXP par) {
+  bwgr_panel *Pf = panel_of(fndr), *Ps = panel_of(samp);
+  int64_t info[8]; chk(bwgr_panel_info(Pf, info));
+  const int nf = (int)info[0];
+  chk(bwgr_panel_info(Ps, info));
+  const int ns = (int)info[0];
+  SEXP Kff = PROTECT(Rf_allocMatrix(REALSXP, nf, nf)), Ksf = PROTECT(Rf_allocMatrix(REALSXP, ns, nf));
+  chk(bwgr_panel_kernel2(Pf, Ps, Rf_asInteger(kind), Rf_asReal(par), REAL(Kff), (int64_t)nf, REAL(Ksf), (int64_t)ns, BWGR_HOST));
+  SEXP out = PROTECT(Rf_allocVector(VECSXP, 2)), nm = PROTECT(Rf_allocVector(STRSXP, 2));
+  SET_VECTOR_ELT(out, 0, Kff); SET_VECTOR_ELT(out, 1, Ksf);
+  SET_STRING_ELT(nm, 0, Rf_mkChar("Kff")); SET_STRING_ELT(nm, 1, Rf_mkChar("Ksf"));
+  Rf_setAttrib(out, R_NamesSymbol, nm);
+  UNPROTECT(4);
+  return out;
+}
+/* the exact X_s X_f' (tcrossprod(Xs, Xf) on integer genotypes) as an n_s x n_f numeric matrix: every entry is an integer below 2^53 */
+SEXP bwgrhip_crossprod2(SEXP fndr, SEXP samp) {
+  bwgr_panel *Pf = panel_of(fndr), *Ps = panel_of(samp);
+  int64_t info[8]; chk(bwgr_panel_info(Pf, info));
+  const int nf = (int)info[0];
+  chk(bwgr_panel_info(Ps, info));
+  const int ns = (int)info[0];
+  int64_t *g = (int64_t *)R_alloc((size_t)nf * ns, sizeof(int64_t));
+  chk(bwgr_panel_crossprod2(Pf, Ps, g, (int64_t)ns, BWGR_HOST));
+  SEXP G = PROTECT(Rf_allocMatrix(REALSXP, ns, nf));
+  for (R_xlen_t k = 0; k < (R_xlen_t)nf * ns; k++) REAL(G)[k] = (double)g[k];
+  UNPROTECT(1);
+  return G;
+}
+
 static const R_CallMethodDef CallEntries[] = {   /* as src/RcppExports.cpp:1152-1228 registers _bWGR_* */
   {"bwgrhip_panel", (DL_FUNC)&bwgrhip_panel, 2}, {"bwgrhip_KMUP", (DL_FUNC)&bwgrhip_KMUP, 9}, {"bwgrhip_KMUP2", (DL_FUNC)&bwgrhip_KMUP2, 10},
   {"bwgrhip_Bayes", (DL_FUNC)&bwgrhip_Bayes, 8}, {"bwgrhip_Bayes2", (DL_FUNC)&bwgrhip_Bayes2, 9},
@@ -424,7 +457,8 @@ static const R_CallMethodDef CallEntries[] = {   /* as src/RcppExports.cpp:1152-
   {"bwgrhip_solver1x", (DL_FUNC)&bwgrhip_solver1x, 6}, {"bwgrhip_UVBETA", (DL_FUNC)&bwgrhip_UVBETA, 3},
   {"bwgrhip_uvbeta_dense", (DL_FUNC)&bwgrhip_uvbeta_dense, 6}, {"bwgrhip_panel_xb", (DL_FUNC)&bwgrhip_panel_xb, 2},
   {"bwgrhip_uvbeta2", (DL_FUNC)&bwgrhip_uvbeta2, 6},
-  {"bwgrhip_kernel", (DL_FUNC)&bwgrhip_kernel, 4}, {"bwgrhip_crossprod", (DL_FUNC)&bwgrhip_crossprod, 1}, {NULL, NULL, 0}};
+  {"bwgrhip_kernel", (DL_FUNC)&bwgrhip_kernel, 4}, {"bwgrhip_crossprod", (DL_FUNC)&bwgrhip_crossprod, 1},
+  {"bwgrhip_kernel2", (DL_FUNC)&bwgrhip_kernel2, 4}, {"bwgrhip_crossprod2", (DL_FUNC)&bwgrhip_crossprod2, 2}, {NULL, NULL, 0}};
 
 void R_init_bwgrhip(DllInfo *dll) {              /* as R_init_bWGR, src/RcppExports.cpp:1230-1233 */
   R_registerRoutines(dll, NULL, CallEntries, NULL, NULL);
