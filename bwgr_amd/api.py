@@ -137,26 +137,10 @@ class Panel:
         check(_lib.lib().bwgr_panel_stats(self._h, _fp(xx), _fp(vx), C.byref(msx)))
         return xx, vx, float(msx.value)
 
-    def _nxn(self, dtype, device_out, call):
-        """An n x n result of the relationship kernels: a numpy array, or (device_out) a torch tensor on the panel's device."""
-        n = self.n
-        if device_out:
-            import sys
-            torch = sys.modules.get("torch")
-            if torch is None:
-                raise RuntimeError("device_out=True: import torch before calling (the result is a torch tensor)")
-            out = torch.empty((n, n), dtype=torch.int64 if dtype == np.int64 else torch.float64, device="cuda:%d" % self.device)
-            torch.cuda.synchronize(out.device)
-            check(call(C.c_void_p(out.data_ptr()), n, DEVICE))
-            return out
-        out = np.empty((n, n), dtype)
-        check(call(out.ctypes.data_as(C.c_void_p), n, HOST))
-        return out
-
     def crossprod(self, *, device_out=False):
         """The exact X X' over the panel's rows as n x n int64 (bwgr_panel_crossprod)."""
         L = _lib.lib()
-        return self._nxn(np.int64, device_out, lambda ptr, ld, loc: L.bwgr_panel_crossprod(self._h, ptr, ld, loc))
+        return self._out2d([(self.n, self.n)], np.int64, device_out, lambda ptr, ld, loc: L.bwgr_panel_crossprod(self._h, ptr[0], ld[0], loc))[0]
 
     def kernel(self, kind, par=1.0, flag=None, *, device_out=False):
         """A relationship kernel of the panel's genotypes, n x n float64 (bwgr_panel_kernel).  kind: "GRM" (flag = Code012, default False),
@@ -165,10 +149,11 @@ class Panel:
         if flag is None:
             flag = k in (KERNELS["EigenGRM"], KERNELS["EigenARC"])
         L = _lib.lib()
-        return self._nxn(np.float64, device_out, lambda ptr, ld, loc: L.bwgr_panel_kernel(self._h, k, float(par), int(bool(flag)), ptr, ld, loc))
+        return self._out2d([(self.n, self.n)], np.float64, device_out,
+                           lambda ptr, ld, loc: L.bwgr_panel_kernel(self._h, k, float(par), int(bool(flag)), ptr[0], ld[0], loc))[0]
 
     def _out2d(self, shapes, dtype, device_out, call):
-        """Rectangular results of the founder-by-sample kernels: numpy arrays, or (device_out) torch tensors on the panel's device.
+        """Results of the relationship kernels, one array per shape: numpy arrays, or (device_out) torch tensors on the panel's device.
         call(pointers, leading dimensions, memloc)."""
         if device_out:
             import sys

@@ -17,9 +17,11 @@ constexpr int XXT_KSTEP = 64;    // markers per v_mfma_i32_16x16x64_i8
 enum { KFIN_GRM = 0, KFIN_GAU = 1, KFIN_EIGEN_GRM = 2, KFIN_EIGEN_GAU = 3, KFIN_EIGEN_ARC = 4 };
 
 struct XxtArgs {
-  const int8_t *X;
+  const int8_t *XA, *XB;    // operand A's panel (the rows of G) and operand B's (its columns) over the same p markers; X X': the same panel twice
   int64_t p;
-  int R, n, T;              // slab rows; real rows; row tiles
+  int RA, RB;               // slab rows of either panel (two panels are made independently: they may differ)
+  int nA, nB;               // real rows of either panel
+  int T;                    // X X': row tiles; X_A X_B': column tiles
   int64_t chunk, piece;     // markers per int32 chunk; markers per workgroup (a multiple of XXT_KSTEP), pieces never cross a chunk
   int sub;                  // pieces per chunk
   int accumulate;           // 0: one workgroup per tile stores; 1: every workgroup adds its int32 sums into the zeroed int64 tile
@@ -27,31 +29,30 @@ struct XxtArgs {
   int64_t ldg;
 };
 
-// The product.  The panel stores a marker's rows contiguously, the MFMA sums along its operands' 16-byte runs, and here the sum runs over the
-// markers: the bytes have to be transposed.  Both operands are rows of the same matrix, so the marker order inside a step and the row order
-// inside a wave's 64 rows are free as long as both operands use the same maps.  A lane loads one dword = rows 4 m16 .. 4 m16 + 3 of one
-// marker; sixteen such dwords (markers 16 u + 4 grp + q) go through the 4 x 4 byte transposition of k_sweep3's update operand (two rounds of
-// v_perm_b32) and come out as four operands of 16 bytes, operand a = row 4 m16 + a over the lane's sixteen markers.  MFMA tile a of a wave
-// therefore holds rows r0 + 4 m + a (m = 0 .. 15) and the write-out puts them back.  No LDS, no barrier: the two waves that share a row range
-// meet in the L1.
+// The product's tile (ti, tj) of 128 x 128: four waves, a 64 x 64 quadrant each.  The panel stores a marker's rows contiguously, the MFMA sums
+// along its operands' 16-byte runs, and here the sum runs over the markers: the bytes have to be transposed.  The marker order inside a step
+// and the row order inside a wave's 64 rows are free as long as both operands use the same maps -- they do, whether the operands are rows of
+// the same matrix (X X') or of two panels (X_A X_B'); only the slab height that turns a marker into an address may differ between the
+// operands.  A lane loads one dword = rows 4 m16 .. 4 m16 + 3 of one marker; sixteen such dwords (markers 16 u + 4 grp + q) go through the
+// 4 x 4 byte transposition of k_sweep3's update operand (two rounds of v_perm_b32) and come out as four operands of 16 bytes, operand a =
+// row 4 m16 + a over the lane's sixteen markers.  MFMA tile a of a wave therefore holds rows r0 + 4 m + a (m = 0 .. 15) and the write-out puts
+// them back, guarding the rows against n_A and the columns against n_B.  No LDS, no barrier: the two waves that share a row range meet in
+// the L1.  The paddings of the panels are zero.
 //
-// blockIdx.x: the tile pair (ti <= tj), row-major over the upper triangle; blockIdx.y: chunk * sub + piece.
-__global__ __launch_bounds__(256) void k_xxt_mfma_i8(const XxtArgs a) {
-  // tile pair
-  int t = blockIdx.x, ti = 0;
-  while (t >= a.T - ti) { t -= a.T - ti; ++ti; }
-  const int tj = ti + t;
+// ONE_R: operand B has operand A's slab height (X X'), so that one set of sixteen lane offsets serves both; otherwise each has its own.
+// blockIdx.y: chunk * sub + piece.
+template <bool ONE_R>
+__device__ __forceinline__ void xxt_tile(const XxtArgs &a, int ti, int tj) {
   const int64_t c = blockIdx.y / a.sub, s = blockIdx.y - c * a.sub;
   const int64_t chunk_hi = min(a.p, (c + 1) * a.chunk);
   const int64_t lo = c * a.chunk + s * a.piece, hi = min(chunk_hi, lo + a.piece);
   if (lo >= hi) return;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), m16 = lane & 15, grp = lane >> 4;
   const int rA0 = XXT_TILE * ti + 64 * (wave >> 1), rB0 = XXT_TILE * tj + 64 * (wave & 1);
-  const int R = a.R;
-  // slab bases (a tile never crosses a slab: R is a multiple of 128); marker j adds j * R
-  const int8_t *ubA = a.X + (size_t)(rA0 / R) * a.p * R + (rA0 % R);
-  const int8_t *ubB = a.X + (size_t)(rB0 / R) * a.p * R + (rB0 % R);
-  const uint32_t loff = (uint32_t)(4 * grp) * (uint32_t)R + 4u * m16;
+  const int RA = a.RA, RB = ONE_R ? a.RA : a.RB;
+  // slab bases (a tile never crosses a slab of its panel: RA and RB are multiples of 128); marker j adds j * RA, j * RB
+  const int8_t *ubA = a.XA + (size_t)(rA0 / RA) * a.p * RA + (rA0 % RA);
+  const int8_t *ubB = a.XB + (size_t)(rB0 / RB) * a.p * RB + (rB0 % RB);
 
   s2_v4i acc[4][4];
 #pragma unroll
@@ -59,21 +60,24 @@ __global__ __launch_bounds__(256) void k_xxt_mfma_i8(const XxtArgs a) {
 #pragma unroll
     for (int y = 0; y < 4; ++y) acc[x][y] = s2_v4i{0, 0, 0, 0};
 
-  // whole steps: the lane's sixteen markers of a step are j0 + 16 u + q (+ 4 grp, in voff).  The step's base is a wave-uniform pointer and the
-  // lane's part a 32-bit offset that does not change over the loop, so that a load costs no vector address arithmetic.
-  uint32_t voff[4][4];
+  // whole steps: the lane's sixteen markers of a step are j0 + 16 u + q + 4 grp.  The step's base is a wave-uniform pointer per operand and
+  // the lane's part a 32-bit offset that does not change over the loop, so that a load costs no vector address arithmetic.
+  uint32_t voffA[4][4], voffB[4][4];
 #pragma unroll
   for (int u = 0; u < 4; ++u)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) voff[u][q] = loff + (uint32_t)(16 * u + q) * (uint32_t)R;
+    for (int q = 0; q < 4; ++q) {
+      voffA[u][q] = (uint32_t)(16 * u + q + 4 * grp) * (uint32_t)RA + 4u * m16;
+      voffB[u][q] = (uint32_t)(16 * u + q + 4 * grp) * (uint32_t)RB + 4u * m16;
+    }
   auto load_full = [&](int64_t j0, uint32_t (&ca)[4][4], uint32_t (&cb)[4][4]) {
-    const int8_t *pa = ubA + (size_t)j0 * R, *pb = ubB + (size_t)j0 * R;
+    const int8_t *pa = ubA + (size_t)j0 * RA, *pb = ubB + (size_t)j0 * RB;
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        ca[u][q] = *reinterpret_cast<const uint32_t *>(pa + voff[u][q]);
-        cb[u][q] = *reinterpret_cast<const uint32_t *>(pb + voff[u][q]);
+        ca[u][q] = *reinterpret_cast<const uint32_t *>(pa + voffA[u][q]);
+        cb[u][q] = *reinterpret_cast<const uint32_t *>(pb + voffB[u][q]);
       }
   };
   // the last, partial step: markers past `hi` are read at hi - 1 and zeroed
@@ -84,8 +88,8 @@ __global__ __launch_bounds__(256) void k_xxt_mfma_i8(const XxtArgs a) {
       for (int q = 0; q < 4; ++q) {
         const int64_t j = j0 + 16 * u + q + 4 * grp;
         const bool ok = j < hi;
-        const size_t off = (size_t)(ok ? j : hi - 1) * R + 4u * m16;
-        const uint32_t va = *reinterpret_cast<const uint32_t *>(ubA + off), vb = *reinterpret_cast<const uint32_t *>(ubB + off);
+        const size_t jj = (size_t)(ok ? j : hi - 1);
+        const uint32_t va = *reinterpret_cast<const uint32_t *>(ubA + jj * RA + 4u * m16), vb = *reinterpret_cast<const uint32_t *>(ubB + jj * RB + 4u * m16);
         ca[u][q] = ok ? va : 0u; cb[u][q] = ok ? vb : 0u;
       }
   };
@@ -128,23 +132,36 @@ __global__ __launch_bounds__(256) void k_xxt_mfma_i8(const XxtArgs a) {
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
       const int row = rA0 + 4 * (4 * grp + reg) + x;
-      if (row >= a.n) continue;
+      if (row >= a.nA) continue;
       long long *g = a.G + (size_t)row * a.ldg + rB0 + 4 * m16;
 #pragma unroll
       for (int y = 0; y < 4; ++y) {
-        if (rB0 + 4 * m16 + y >= a.n) continue;
+        if (rB0 + 4 * m16 + y >= a.nB) continue;
         if (a.accumulate) atomicAdd(reinterpret_cast<unsigned long long *>(g + y), (unsigned long long)(long long)acc[x][y][reg]);
         else g[y] = (long long)acc[x][y][reg];
       }
     }
 }
 
-// the tiles on and above the diagonal of an n x n int64 matrix set to zero (before an accumulating product)
-__global__ void k_xxt_zero(long long *G, int64_t ldg, int n) {
-  const int64_t total = (int64_t)n * n;
+// G = X X' (XB = XA, RB = RA, nB = nA): only the tile pairs ti <= tj, blockIdx.x row-major over the upper triangle; k_xxt_mirror fills the rest
+__global__ __launch_bounds__(256) void k_xxt_mfma_i8(const XxtArgs a) {
+  int t = blockIdx.x, ti = 0;
+  while (t >= a.T - ti) { t -= a.T - ti; ++ti; }
+  xxt_tile<true>(a, ti, ti + t);
+}
+// G = X_A X_B' between two panels: every tile of the T_A x T_B grid (no triangle, no mirror), blockIdx.x = ti * T + tj
+__global__ __launch_bounds__(256) void k_xyt_mfma_i8(const XxtArgs a) {
+  const int ti = blockIdx.x / a.T;
+  xxt_tile<false>(a, ti, blockIdx.x - ti * a.T);
+}
+
+// nr x nc entries of an int64 matrix set to zero (before an accumulating product); entries beyond column nc of a row are not touched.
+// upper: only the tiles on and above the diagonal (those that X X' computes).
+__global__ void k_xxt_zero(long long *G, int64_t ldg, int nr, int nc, int upper) {
+  const int64_t total = (int64_t)nr * nc;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = idx / n, j = idx - i * n;
-    if (j / XXT_TILE >= i / XXT_TILE) G[(size_t)i * ldg + j] = 0;
+    const int64_t i = idx / nc, j = idx - i * nc;
+    if (!upper || j / XXT_TILE >= i / XXT_TILE) G[(size_t)i * ldg + j] = 0;
   }
 }
 
@@ -165,132 +182,6 @@ __global__ __launch_bounds__(256) void k_xxt_mirror(long long *G, int64_t ldg, i
   }
 }
 
-// ---- the product between two panels --------------------------------------------------------------------------------------------------
-struct XytArgs {
-  const int8_t *XA, *XB;    // the founders' panel (rows of G) and the samples' (columns of G): the same p markers
-  int64_t p;
-  int RA, RB;               // slab rows of either panel (made independently: they may differ)
-  int nA, nB, TB;           // real rows of either panel; column tiles
-  int64_t chunk, piece;     // as XxtArgs
-  int sub, accumulate;
-  long long *G;
-  int64_t ldg;
-};
-
-// G = X_A X_B' on k_xxt_mfma_i8's tile: four waves on a 128 x 128 tile, a 64 x 64 quadrant each, dword loads, the two rounds of
-// v_perm_b32, one register set per wave, no LDS, no barrier.  The marker order inside a step and the row order inside a wave's 64 rows are
-// free as long as both operands use the same maps; they do, and only the slab height that turns a marker into an address differs between the
-// operands, so each has its own sixteen loop-constant lane offsets.  Every tile of the T_A x T_B grid is computed (no triangle, no mirror)
-// and the write-out guards the rows against n_A and the columns against n_B.  The paddings of both panels are zero.
-//
-// blockIdx.x: ti * TB + tj; blockIdx.y: chunk * sub + piece.
-__global__ __launch_bounds__(256) void k_xyt_mfma_i8(const XytArgs a) {
-  const int ti = blockIdx.x / a.TB, tj = blockIdx.x - ti * a.TB;
-  const int64_t c = blockIdx.y / a.sub, s = blockIdx.y - c * a.sub;
-  const int64_t chunk_hi = min(a.p, (c + 1) * a.chunk);
-  const int64_t lo = c * a.chunk + s * a.piece, hi = min(chunk_hi, lo + a.piece);
-  if (lo >= hi) return;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), m16 = lane & 15, grp = lane >> 4;
-  const int rA0 = XXT_TILE * ti + 64 * (wave >> 1), rB0 = XXT_TILE * tj + 64 * (wave & 1);
-  const int RA = a.RA, RB = a.RB;
-  // slab bases (a tile never crosses a slab of its panel: RA and RB are multiples of 128); marker j adds j * RA, j * RB
-  const int8_t *ubA = a.XA + (size_t)(rA0 / RA) * a.p * RA + (rA0 % RA);
-  const int8_t *ubB = a.XB + (size_t)(rB0 / RB) * a.p * RB + (rB0 % RB);
-
-  s2_v4i acc[4][4];
-#pragma unroll
-  for (int x = 0; x < 4; ++x)
-#pragma unroll
-    for (int y = 0; y < 4; ++y) acc[x][y] = s2_v4i{0, 0, 0, 0};
-
-  // whole steps: a wave-uniform base per panel and the lane's sixteen 32-bit offsets per panel, constant over the loop
-  uint32_t voffA[4][4], voffB[4][4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      voffA[u][q] = (uint32_t)(16 * u + q + 4 * grp) * (uint32_t)RA + 4u * m16;
-      voffB[u][q] = (uint32_t)(16 * u + q + 4 * grp) * (uint32_t)RB + 4u * m16;
-    }
-  auto load_full = [&](int64_t j0, uint32_t (&ca)[4][4], uint32_t (&cb)[4][4]) {
-    const int8_t *pa = ubA + (size_t)j0 * RA, *pb = ubB + (size_t)j0 * RB;
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        ca[u][q] = *reinterpret_cast<const uint32_t *>(pa + voffA[u][q]);
-        cb[u][q] = *reinterpret_cast<const uint32_t *>(pb + voffB[u][q]);
-      }
-  };
-  // the last, partial step: markers past `hi` are read at hi - 1 and zeroed
-  auto load_tail = [&](int64_t j0, uint32_t (&ca)[4][4], uint32_t (&cb)[4][4]) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int64_t j = j0 + 16 * u + q + 4 * grp;
-        const bool ok = j < hi;
-        const size_t jj = (size_t)(ok ? j : hi - 1);
-        const uint32_t va = *reinterpret_cast<const uint32_t *>(ubA + jj * RA + 4u * m16), vb = *reinterpret_cast<const uint32_t *>(ubB + jj * RB + 4u * m16);
-        ca[u][q] = ok ? va : 0u; cb[u][q] = ok ? vb : 0u;
-      }
-  };
-  // rw[x] = the operand of MFMA tile x: bytes (u, q) = row 4 m16 + x of marker 16 u + 4 grp + q (k_xxt_mfma_i8's transposition)
-  auto transpose = [](const uint32_t (&cc)[4][4], s2_v4i (&rw)[4]) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const uint32_t t0 = __builtin_amdgcn_perm(cc[u][1], cc[u][0], 0x05010400u), t1 = __builtin_amdgcn_perm(cc[u][1], cc[u][0], 0x07030602u);
-      const uint32_t t2 = __builtin_amdgcn_perm(cc[u][3], cc[u][2], 0x05010400u), t3 = __builtin_amdgcn_perm(cc[u][3], cc[u][2], 0x07030602u);
-      rw[0][u] = (int)__builtin_amdgcn_perm(t2, t0, 0x05040100u); rw[1][u] = (int)__builtin_amdgcn_perm(t2, t0, 0x07060302u);
-      rw[2][u] = (int)__builtin_amdgcn_perm(t3, t1, 0x05040100u); rw[3][u] = (int)__builtin_amdgcn_perm(t3, t1, 0x07060302u);
-    }
-  };
-  auto mma = [&](const uint32_t (&ca)[4][4], const uint32_t (&cb)[4][4]) {
-    s2_v4i ra[4], rb[4];
-    transpose(ca, ra); transpose(cb, rb);
-#pragma unroll
-    for (int x = 0; x < 4; ++x)
-#pragma unroll
-      for (int y = 0; y < 4; ++y) acc[x][y] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ra[x], rb[y], acc[x][y], 0, 0, 0);
-  };
-
-  const int64_t nfull = (hi - lo) / XXT_KSTEP;
-  uint32_t ca[4][4], cb[4][4];
-  for (int64_t k = 0; k < nfull; ++k) {
-    load_full(lo + XXT_KSTEP * k, ca, cb);
-    mma(ca, cb);
-  }
-  if (lo + nfull * XXT_KSTEP < hi) {
-    load_tail(lo + nfull * XXT_KSTEP, ca, cb);
-    mma(ca, cb);
-  }
-
-  // acc[x][y][reg] of lane (m16, grp) = G[rA0 + 4 (4 grp + reg) + x][rB0 + 4 m16 + y]
-#pragma unroll
-  for (int x = 0; x < 4; ++x)
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int row = rA0 + 4 * (4 * grp + reg) + x;
-      if (row >= a.nA) continue;
-      long long *g = a.G + (size_t)row * a.ldg + rB0 + 4 * m16;
-#pragma unroll
-      for (int y = 0; y < 4; ++y) {
-        if (rB0 + 4 * m16 + y >= a.nB) continue;
-        if (a.accumulate) atomicAdd(reinterpret_cast<unsigned long long *>(g + y), (unsigned long long)(long long)acc[x][y][reg]);
-        else g[y] = (long long)acc[x][y][reg];
-      }
-    }
-}
-
-// the nA x nB entries of an int64 matrix set to zero (before an accumulating product); entries beyond column nB of a row are not touched
-__global__ void k_xyt_zero(long long *G, int64_t ldg, int nA, int nB) {
-  const int64_t total = (int64_t)nA * nB;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = idx / nB, j = idx - i * nB;
-    G[(size_t)i * ldg + j] = 0;
-  }
-}
-
 // ---- the finishes -------------------------------------------------------------------------------------------------------------------
 // s_j = sum_i x_ij and q_j = sum_i x_ij^2, exact; one wave per marker
 __global__ void k_kfin_colstats(const int8_t *X, int R, int n, int64_t p, int32_t *s, long long *q) {
@@ -304,9 +195,12 @@ __global__ void k_kfin_colstats(const int8_t *X, int R, int n, int64_t p, int32_
   if (lane == 0) { s[j] = (int32_t)s1; q[j] = s2; }
 }
 
-// rs_i = (X s)_i, exact in int64 (rs zeroed by the caller; integer adds commute, so the split over workgroups does not show).  A workgroup takes
-// 128 rows (a dword of four rows per thread of a group of 32) and `cols` markers, its eight groups every eighth of them.
-__global__ __launch_bounds__(256) void k_kfin_xs(const int8_t *X, int R, int64_t p, const int32_t *s, int64_t cols, long long *rs) {
+// The row reduction of the finishes, exact in int64: out_i += sum_j x_ij w_j over the workgroup's markers, w_j = s_j (SQ = false: rs = X s)
+// or w_j = x_ij itself (SQ = true: q_i = sum_j x_ij^2, diag(X X') without the product; s is not read).  out has ld entries and is zeroed by
+// the caller; padded rows add 0; integer adds commute, so the split over workgroups does not show.  A workgroup takes 128 rows (a dword of
+// four rows per thread of a group of 32) and `cols` markers, its eight groups every eighth of them.
+template <bool SQ>
+__device__ __forceinline__ void kfin_rows(const int8_t *X, int R, int64_t p, const int32_t *s, int64_t cols, long long *out) {
   __shared__ long long red[8][128];
   const int tx = threadIdx.x & 31, g = threadIdx.x >> 5;
   const int r0 = 128 * blockIdx.x;
@@ -315,9 +209,9 @@ __global__ __launch_bounds__(256) void k_kfin_xs(const int8_t *X, int R, int64_t
   long long acc[4] = {0, 0, 0, 0};
   for (int64_t j = j0 + g; j < j1; j += 8) {
     const uint32_t w = *reinterpret_cast<const uint32_t *>(base + (size_t)j * R);
-    const long long sj = s[j];
+    const long long sj = SQ ? 0 : s[j];
 #pragma unroll
-    for (int b = 0; b < 4; ++b) acc[b] += (long long)(int8_t)(w >> (8 * b)) * sj;
+    for (int b = 0; b < 4; ++b) { const int v = (int)(int8_t)(w >> (8 * b)); acc[b] += SQ ? (long long)(v * v) : (long long)v * sj; }
   }
 #pragma unroll
   for (int b = 0; b < 4; ++b) red[g][4 * tx + b] = acc[b];
@@ -326,8 +220,14 @@ __global__ __launch_bounds__(256) void k_kfin_xs(const int8_t *X, int R, int64_t
     long long v = 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) v += red[k][threadIdx.x];
-    atomicAdd(reinterpret_cast<unsigned long long *>(rs + r0 + threadIdx.x), (unsigned long long)v);   // (rs has ld entries: padded rows add 0)
+    atomicAdd(reinterpret_cast<unsigned long long *>(out + r0 + threadIdx.x), (unsigned long long)v);
   }
+}
+__global__ __launch_bounds__(256) void k_kfin_xs(const int8_t *X, int R, int64_t p, const int32_t *s, int64_t cols, long long *rs) {
+  kfin_rows<false>(X, R, p, s, cols, rs);
+}
+__global__ __launch_bounds__(256) void k_kfin2_rowsq(const int8_t *X, int R, int64_t p, int64_t cols, long long *q) {
+  kfin_rows<true>(X, R, p, nullptr, cols, q);
 }
 
 __global__ void k_kfin_diag(const long long *G, int64_t ldg, int n, long long *diag) {
@@ -397,31 +297,6 @@ __global__ __launch_bounds__(256) void k_kfin_apply(const KfinArgs a) {
 }
 
 // ---- the founder-by-sample finishes (EigenArcZ / EigenGauZ) ------------------------------------------------------------------------------
-// q_i = sum_j x_ij^2 over a panel's rows, exact in int64: diag(X X') without the product (q zeroed by the caller, ld entries; padded rows
-// add 0).  k_kfin_xs's shape: a workgroup takes 128 rows and `cols` markers, its eight groups every eighth of them.
-__global__ __launch_bounds__(256) void k_kfin2_rowsq(const int8_t *X, int R, int64_t p, int64_t cols, long long *q) {
-  __shared__ long long red[8][128];
-  const int tx = threadIdx.x & 31, g = threadIdx.x >> 5;
-  const int r0 = 128 * blockIdx.x;
-  const int64_t j0 = (int64_t)blockIdx.y * cols, j1 = min(p, j0 + cols);
-  const int8_t *base = X + (size_t)(r0 / R) * p * R + (r0 % R) + 4 * tx;
-  long long acc[4] = {0, 0, 0, 0};
-  for (int64_t j = j0 + g; j < j1; j += 8) {
-    const uint32_t w = *reinterpret_cast<const uint32_t *>(base + (size_t)j * R);
-#pragma unroll
-    for (int b = 0; b < 4; ++b) { const int v = (int)(int8_t)(w >> (8 * b)); acc[b] += v * v; }
-  }
-#pragma unroll
-  for (int b = 0; b < 4; ++b) red[g][4 * tx + b] = acc[b];
-  __syncthreads();
-  if (threadIdx.x < 128) {
-    long long v = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v += red[k][threadIdx.x];
-    atomicAdd(reinterpret_cast<unsigned long long *>(q + r0 + threadIdx.x), (unsigned long long)v);
-  }
-}
-
 enum { KFIN2_ARC = 0, KFIN2_GAU = 1 };
 // One element of either kind.  The literals as the reference writes them (3.14159 here, not EigenARC's 3.1416).
 // ARC: a = the product centred by the founders' column means, da and db the two centred squared norms; the value before Kscalar.

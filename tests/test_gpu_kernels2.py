@@ -219,6 +219,31 @@ def test_kernel2_matches_the_restatement(tpod, which, kind, phi):
     assert np.array_equal(Kff, Kff2) and np.array_equal(Kfs, Kfs2)      # two calls: identical bits
 
 
+@pytest.mark.parametrize("kind", ["ARC", "GAU"])
+def test_kernel2_multi_slab_panels_of_different_slab_heights(kind):
+    """Founders in three slabs of 256 rows, samples in three slabs of 128 (test_crossprod2_different_slab_heights' panels): the row
+    reductions X_f s, X_s s and q_s and both finishes address a second and a third slab on either side."""
+    import bwgr_amd
+    X = np.ascontiguousarray(synth_small(1000, 900, seed=4)[0])
+    F, S = np.ascontiguousarray(X[:700]), np.ascontiguousarray(X[700:])
+    Pf, Ps = bwgr_amd.Panel(F, nwg=3), bwgr_amd.Panel(S, nwg=3)
+    try:
+        print("founders %d x %d slab rows %d, samples %d x %d slab rows %d" % (Pf.n, Pf.p, Pf.slab_rows, Ps.n, Ps.p, Ps.slab_rows))
+        assert Pf.slab_rows != Ps.slab_rows
+        Kff, Kfs = Pf.kernel2(Ps, kind, 0.5)
+        Kff2, Kfs2 = Pf.kernel2(Ps, kind, 0.5)
+    finally:
+        Pf.close(); Ps.close()
+    rff, rfs = K2.kernels(kind, F, S, 0.5)
+    eff, efs = scaled_err(Kff, rff), scaled_err(Kfs, rfs)
+    print("%s: scaled_err Kff = %.3e, Kfs = %.3e" % (kind, eff, efs))
+    assert Kff.shape == (700, 700) and Kfs.shape == (700, 300)
+    assert eff <= TOL, eff
+    assert efs <= TOL, efs
+    assert np.array_equal(Kff, Kff.T)
+    assert np.array_equal(Kff, Kff2) and np.array_equal(Kfs, Kfs2)      # two calls: identical bits
+
+
 # ---- the drivers ----
 def _driver(kind):
     import bwgr_amd
