@@ -15,6 +15,9 @@ workgroups covers.  The trips, from the plans (256 threads per workgroup):
              too long for this suite; so kern1100 reaches k_xxt_zero with three forced chunks (kchunk: BWGR_KCHUNK when the panel is made;
              forced_chunks as the plan then reports them), which integer sums make bit-equal to the one-chunk product
   pxb        (row tiles, 16-column slices, marker chunks, markers per chunk) of k_pxb; pxb_cross: a 1 024-row tile that spans two slabs
+
+The two-design fits -- uvbeta2, MEGA, GSEM -- run on tall9k and slab1280 through the same pass, row reduction and panel_xb; their inputs and
+the restatement's results on them are at the end of this file.  The two-panel shapes are in tests/pair_cases.py.
 """
 import ctypes as C
 import functools
@@ -116,6 +119,57 @@ def plans(tag, k=None):
 
 def panel_kw(tag):
     return {"block": CASES[tag]["block"]} if CASES[tag]["block"] else {}
+
+
+# ---- the two-design fits on these shapes: uvbeta2 (solver2x per trait), MEGA and GSEM ----
+# tag -> how the drivers run there and the seed of their traits (tests/test_tall_cases_cpu.py asserts the preconditions and states the
+# figures).  slab1280: six sweeps per stage; tall9k: the reference's defaults, every stage stopping by its own test.
+SEM2_DRIVERS = {"slab1280": dict(kw=dict(maxit=6, tol=0), seed=3001), "tall9k": dict(kw={}, seed=3011)}
+SEM2_ENGINE = {("tall9k", 3): 3100, ("slab1280", 3): 3110, ("slab1280", 65): 3120}      # (tag, k) -> the seed of Y; Z's is the next
+SEM2_ENGINE_KW = dict(maxit=6, tol=0)
+
+
+@functools.lru_cache(maxsize=None)
+def uvb2_case(tag, k):
+    """uvbeta2's inputs: k traits with 10 % of the records missing, q = 3 dense columns on falling scales, the shape's genotypes"""
+    import sem2_cases as S2C
+    X, seed = data(tag), SEM2_ENGINE[(tag, k)]
+    Y, Z = S2C.traits(X, k, 0.1, seed), S2C.dense(X.shape[0], 3, seed + 1)
+    Y.setflags(write=False); Z.setflags(write=False)
+    return dict(Y=Y, Z=Z, X=X, kw=dict(SEM2_ENGINE_KW))
+
+
+@functools.lru_cache(maxsize=None)
+def uvb2_ref(tag, k):
+    import sem2_restatement as S2
+    c = uvb2_case(tag, k)
+    return S2.uvbeta2(c["Y"], c["Z"], c["X"], **c["kw"])
+
+
+@functools.lru_cache(maxsize=None)
+def driver_traits(tag):
+    """tests/sem2_cases.py's slab_traits on this shape: three correlated traits -- a polygenic signal plus noise the traits share in part, so
+    that the singular values of MEGA's Y2 and of GSEM's G lie apart -- on the scales 0.01, 0.02, 0.04 (cnv is absolute: small scales stop
+    within a few sweeps, by large steps), 10 % missing."""
+    X = data(tag)
+    rng = np.random.default_rng(SEM2_DRIVERS[tag]["seed"])
+    Xf = X.astype(np.float64)
+    n, p = X.shape
+    g = (Xf - Xf.mean(0)) @ (rng.normal(size=(p, 3)) / np.sqrt(p))
+    g = g / g.std(0) * 0.5
+    c = rng.normal(size=n)
+    E = np.stack([c + 0.5 * rng.normal(size=n), c - 0.9 * rng.normal(size=n), 0.4 * c + 1.3 * rng.normal(size=n)], 1)
+    Y = (g + E) * np.array([0.01, 0.02, 0.04]) + 3.0
+    Y[rng.random((n, 3)) < 0.1] = np.nan
+    Y.setflags(write=False)
+    return Y
+
+
+@functools.lru_cache(maxsize=None)
+def driver_ref(name, tag):
+    """the restatement's MEGA / GSEM (npc = -1) on the shape, computed once per session and left unchanged"""
+    import sem2_restatement as S2
+    return getattr(S2, name)(driver_traits(tag), data(tag), -1, **SEM2_DRIVERS[tag]["kw"])
 
 
 @functools.lru_cache(maxsize=None)

@@ -5,12 +5,23 @@ entry's existing comparison with the oracle or its restatement.  tpod (196 x 376
 On the default (null) stream every stray hipMemcpy, hipMemset or launch on stream 0 is ordered for free; on a non-blocking stream it is a
 race.  To make such a race lose, the caller's stream is kept busy: before each call on it a spin kernel (torch.cuda._sleep) is enqueued
 there that lasts at least five times the entry's own time on the default stream (both measured with events and printed).  Whatever the
-library issues off the caller's stream without an event dependency then runs before its inputs exist and shows as wrong bits.
+library issues off the caller's stream without an event dependency then runs before its inputs exist and shows as wrong bits.  The null
+stream gets a filler of its own that outlasts the caller's filler and the entry together: an entry's early operations are ordered by its
+own host synchronisations whatever stream they are on, but a late launch on stream 0 queues behind that filler and has not run when the
+entry copies its results out with hipMemcpyAsync on the caller's stream (mrr, the uvbeta family, xb, the samplers).  The relationship
+kernels hand their results out by hipMemcpy2DAsync, which on this runtime was measured to wait for stream 0 (tools/stream0_probe.py): a
+late launch on stream 0 in them cannot be seen by a caller, here or anywhere else.
 
 What this does and does not prove.  It is believed, not measured, that this runtime makes a host-to-device copy from pageable memory
 host-synchronous; if so, an entry's first such copy on the caller's stream waits for the filler, and operations mis-ordered after that copy
 are caught only by the natural durations of the work they race with.  These tests catch what runs on the null stream cannot catch at all;
-they are not a proof of ordering."""
+they are not a proof of ordering.  One entry proves less than the others: with device_out=True Panel._out2d waits for the whole device before it
+calls the library (the tensors it has just made must exist), which drains the filler, so kernel2_GAU_device and GRM_device are ordered
+against the natural durations of their own launches only.
+
+The two-panel entries (crossprod2, kernel2 on the 700 x 900 root and a 300 x 900 samples panel in slabs of another height) run in the table like
+the others, the samples on the default stream; test_two_panel_entry_on_every_pair_of_handles then puts the founders and the samples on
+different streams and clones."""
 import functools
 import math
 import os
@@ -20,14 +31,18 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kernels2_restatement as K2  # noqa: E402
 import kernels_restatement as KR  # noqa: E402
 import mrr_restatement as MR  # noqa: E402
+import sem2_cases as C2  # noqa: E402
+import sem2_restatement as S2  # noqa: E402
 import sem_restatement as SR  # noqa: E402
 import uvb_restatement as UR  # noqa: E402
-from conftest import scaled_err  # noqa: E402
+from conftest import scaled_err, synth_small  # noqa: E402
 from test_gpu_mrr import _check as _mrr_check, _traits  # noqa: E402
 from test_gpu_parity import _em_check, _rel  # noqa: E402
 from test_gpu_sem import _check as _sem_check, _strong, _well_posed  # noqa: E402
+from test_gpu_sem2 import _check as _uvb2_check, _check_driver  # noqa: E402
 from test_gpu_uvb import _check as _uvb_check, _slabs900  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -99,6 +114,10 @@ def _slab_traits(which):
         return _traits(X, 3, 0, seed=5, patterns=[0.1, 0.0, 0.25])
     if which == "uvb":
         return _traits(X, 5, 0, seed=5, patterns=[0.1, 0.0, 0.25, 0.05, 0.4])
+    if which == "uvb2":
+        return C2.traits(X, 3, 0.1, 61)
+    if which == "sem2":
+        return C2.slab_traits()      # tests/sem2_cases.py's: test_sem2_cpu asserts the drivers' preconditions on it (gaps 0.165 and 0.373)
     return _strong(X, 3, seed=302)      # test_gpu_sem's: gaps 0.278 and 0.243
 
 
@@ -277,6 +296,69 @@ def _zsemf_ok(g):
     _sem_check("ZSEMF", g, o)
 
 
+@functools.lru_cache(None)
+def _samples900():
+    """the samples of the two-panel entries: 300 x 900, other genotypes than the root's"""
+    X = np.asfortranarray(synth_small(300, 900, seed=6)[0])
+    X.setflags(write=False)
+    return X
+
+
+@functools.lru_cache(None)
+def _pair_ref(kind, phi=1.0):
+    """the exact product (kind None) or the restated (K_ff, K_fs) of the root and the samples, computed once"""
+    F, S = np.ascontiguousarray(_slabs900()), np.ascontiguousarray(_samples900())
+    return K2.crossprod2(F, S) if kind is None else K2.kernels(kind, F, S, phi)
+
+
+def _crossprod2(P, aux):
+    return dict(G=P.crossprod2(aux["S"]))
+
+
+def _crossprod2_ok(g):
+    assert g["G"].dtype == np.int64 and np.array_equal(g["G"], _pair_ref(None))
+
+
+def _kernel2(kind, phi, device_out):
+    def call(P, aux):
+        Kff, Kfs = P.kernel2(aux["S"], kind, phi, device_out=device_out)
+        return dict(Kff=Kff.cpu().numpy(), Kfs=Kfs.cpu().numpy()) if device_out else dict(Kff=Kff, Kfs=Kfs)
+
+    def ok(g):      # test_gpu_kernels2's test_kernel2_matches_the_restatement
+        rff, rfs = _pair_ref(kind, phi)
+        assert g["Kff"].shape == rff.shape and g["Kfs"].shape == rfs.shape and np.all(np.isfinite(g["Kff"])) and np.all(np.isfinite(g["Kfs"]))
+        assert scaled_err(g["Kff"], rff) <= TOL and scaled_err(g["Kfs"], rfs) <= TOL and np.array_equal(g["Kff"], g["Kff"].T)
+    return call, ok
+
+
+@functools.lru_cache(None)
+def _dense():
+    Z = C2.dense(700, 3, 62)
+    Z.setflags(write=False)
+    return Z
+
+
+def _uvb2(P, aux):
+    import bwgr_amd
+    return bwgr_amd.uvbeta2(_Y("uvb2"), _dense(), P, **C2.SIX)
+
+
+def _uvb2_ok(g):
+    _uvb2_check(g, S2.uvbeta2(_slab_traits("uvb2"), _dense(), _slabs900(), **C2.SIX))
+
+
+def _sem2(name):
+    """MEGA / GSEM at the reference's defaults: tests/sem2_cases.py's slabs_defaults case"""
+    def call(P, aux):
+        import bwgr_amd
+        return getattr(bwgr_amd, name)(_Y("sem2"), P)
+
+    def ok(g):
+        _check_driver(name, g, C2.driver_ref(name, "slabs_defaults"))
+    return call, ok
+
+
+NO_INPUTS = ("stats", "crossprod", "GRM_host", "GRM_device", "crossprod2", "kernel2_ARC_host", "kernel2_GAU_device")      # nothing but the panels
 ENTRIES = {
     "KMUP": ("tpod", _kmup, _kmup_ok), "KMUP2": ("tpod", _kmup2, _kmup2_ok),
     "wgr": ("tpod",) + _wgr("wgr"), "wgr_bag": ("tpod",) + _wgr("wgr_bag"), "wgr_eigK": ("tpod",) + _wgr("wgr_eigK"),
@@ -285,6 +367,9 @@ ENTRIES = {
     "mrr": ("slabs", _mrr, _mrr_ok), "uvbeta_xb": ("slabs", _uvb, _uvb_ok), "xb": ("slabs", _xb, _xb_ok),
     "crossprod": ("slabs", _crossprod, _crossprod_ok), "GRM_host": ("slabs",) + _grm(False), "GRM_device": ("slabs",) + _grm(True),
     "ZSEMF": ("slabs", _zsemf, _zsemf_ok),
+    "crossprod2": ("slabs", _crossprod2, _crossprod2_ok), "kernel2_ARC_host": ("slabs",) + _kernel2("ARC", 1.0, False),
+    "kernel2_GAU_device": ("slabs",) + _kernel2("GAU", 0.5, True),
+    "uvbeta2": ("slabs", _uvb2, _uvb2_ok), "MEGA": ("slabs",) + _sem2("MEGA"), "GSEM": ("slabs",) + _sem2("GSEM"),
 }
 
 
@@ -305,9 +390,12 @@ class _Env:
         # (tpod2: BayesB2's two panels share the residual, hence the slab geometry, and an fp32 panel's slabs have at most 128 rows)
         self.P = {"tpod": bwgr_amd.Panel(_tpod()[0]), "tpod2": bwgr_amd.Panel(_tpod()[0], nwg=2), "slabs": bwgr_amd.Panel(_slabs900(), nwg=3)}
         assert self.P["slabs"].nwg == 3 and self.P["tpod2"].nwg == 2
-        self.aux = {"P2": bwgr_amd.Panel(_x2()[0], nwg=2)}
-        self.s = torch.cuda.Stream()
-        assert self.s.cuda_stream != 0
+        # (S: the two-panel entries' samples, in three slabs of 128 rows against the root's three of 256 -- left to itself a 300-row panel
+        # takes 256-row slabs like the root -- so each operand's addresses come from its own slab height)
+        self.aux = {"P2": bwgr_amd.Panel(_x2()[0], nwg=2), "S": bwgr_amd.Panel(_samples900(), nwg=3)}
+        assert self.aux["S"].nwg == 3 and self.aux["S"].slab_rows != self.P["slabs"].slab_rows
+        self.s, self.s2 = torch.cuda.Stream(), torch.cuda.Stream()
+        assert self.s.cuda_stream != 0 and self.s2.cuda_stream not in (0, self.s.cuda_stream)
         self.unit_cycles = 5_000_000
         ms = []
         for _ in range(3):      # (the first launch carries the kernel's load: the shortest of the later two is the unit)
@@ -317,11 +405,11 @@ class _Env:
         self.unit_ms = min(ms[1:])
         assert self.unit_ms > 0
 
-    def _spin(self, units):
-        """enqueue `units` spin kernels on the caller's stream between two events"""
+    def _spin(self, units, stream=None):
+        """enqueue `units` spin kernels on the caller's stream (or on `stream`) between two events"""
         torch = self.torch
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(self.s):
+        with torch.cuda.stream(self.s if stream is None else stream):
             e0.record()
             for _ in range(units):
                 torch.cuda._sleep(self.unit_cycles)
@@ -339,9 +427,19 @@ class _Env:
         torch.cuda.synchronize()
         return out, e0.elapsed_time(e1)
 
-    def busy(self, entry_ms):
-        """keep the caller's stream busy for more than FILL times entry_ms; returns the events that time the filler"""
-        return self._spin(int(math.ceil((FILL + 1.0) * entry_ms / self.unit_ms)) + 1)
+    def _units(self, entry_ms):
+        return int(math.ceil((FILL + 1.0) * entry_ms / self.unit_ms)) + 1
+
+    def busy(self, entry_ms, stream=None):
+        """keep the caller's stream (or `stream`) busy for more than FILL times entry_ms; returns the events that time the filler"""
+        return self._spin(self._units(entry_ms), stream)
+
+    def busy_null(self, entry_ms):
+        """keep the default (null) stream busy for longer than a caller's stream's filler and the entry behind it take together: twice that
+        filler's spin kernels and one more.  The library has no business on the null stream while no panel of the call sits there; what it
+        launches there all the same queues behind this filler, and so runs after the call has copied its results out.  (torch's streams
+        are non-blocking: nothing on them waits for the null stream by itself.)"""
+        return self._spin(2 * self._units(entry_ms) + 1, self.torch.cuda.default_stream())
 
     def close(self):
         import bwgr_amd
@@ -349,6 +447,7 @@ class _Env:
             P.set_stream(0)
             P.close()
         self.s.synchronize()
+        self.s2.synchronize()
         assert bwgr_amd.debug_live() == self.live
 
 
@@ -376,23 +475,90 @@ def test_entry_on_every_handle(env, name):
         Q.close()
     ALT["on"] = True
     try:
-        other = call(P, env.aux)      # (stats, crossprod and the kernels have no input but the panel: the same result again)
+        other = call(P, env.aux)      # (stats, the products and the kernels have no input but the panels: the same result again)
     finally:
         ALT["on"] = False
-    assert name in ("stats", "crossprod", "GRM_host", "GRM_device") or not np.array_equal(next(iter(other.values())), next(iter(first.values())))
+    assert name in NO_INPUTS or not np.array_equal(next(iter(other.values())), next(iter(first.values())))
     try:
         P.set_stream(env.s.cuda_stream)
+        n0, n1 = env.busy_null(entry_ms)
         e0, e1 = env.busy(entry_ms)
         on_stream = call(P, env.aux)
-        env.s.synchronize()
-        filler_ms = e0.elapsed_time(e1)
+        env.torch.cuda.synchronize()
+        filler_ms, null_ms = e0.elapsed_time(e1), n0.elapsed_time(n1)
     finally:
         P.set_stream(0)
     back = call(P, env.aux)
-    print("%s: entry %.3f ms on the default stream, filler %.3f ms on the caller's" % (name, entry_ms, filler_ms))
+    print("%s: entry %.3f ms on the default stream, filler %.3f ms on the caller's, %.3f ms on the null stream" % (name, entry_ms, filler_ms, null_ms))
     assert filler_ms >= FILL * entry_ms, (filler_ms, entry_ms)
+    assert null_ms >= filler_ms + entry_ms, (null_ms, filler_ms, entry_ms)
     _same(first, on_clone, "clone")
     _same(first, on_stream, "caller's stream")
+    _same(first, back, "back on the default stream")
+    assert bwgr_amd.debug_live() == live
+
+
+# founders' and samples' handle: "root" (the default stream), "s" / "s2" (the root on a caller's stream), "clone" (its own non-blocking stream)
+PAIR_HANDLES = {"founders_on_a_stream": ("s", "root"), "samples_on_a_stream": ("root", "s"), "both_on_one_stream": ("s", "s"),
+                "each_on_its_own_stream": ("s", "s2"), "founders_clone": ("clone", "root"), "samples_clone": ("root", "clone")}
+
+
+@pytest.mark.parametrize("how", list(PAIR_HANDLES))
+@pytest.mark.parametrize("name", ["crossprod2", "kernel2_ARC_host"])
+def test_two_panel_entry_on_every_pair_of_handles(env, name, how):
+    """The two-panel entries with the founders and the samples on different handles: every combination must give the bits of the call with
+    both roots on the default stream.  The founders' stream carries the work; the library makes it wait, by an event, for what is pending on
+    the samples' stream (xyt_order), a branch that two panels on one stream never enter.  Before each call every stream of the combination
+    that a caller can reach -- a caller's stream, or the default stream under a root left there -- is kept busy by a filler of FILL times
+    the entry's length (a clone's own stream cannot be reached), and the temporaries of the call before are overwritten by another problem's
+    (the GAU kernels of the pair the other way round), so that a launch or copy off the founders' stream finds neither its inputs nor last
+    time's results.  Where neither panel sits on the default stream (both on one stream, each on its own) the null stream gets a filler
+    that outlasts the caller's filler and the entry together (_Env.busy_null), behind which a launch on stream 0 after the entry's host
+    synchronisations -- a finish, say -- stays queued.  For these two entries that is a precaution and no detector: measured on this
+    runtime, the two-dimensional copy to pageable host memory by which they hand out their results waits for stream 0 (DESIGN.md section 3,
+    scratch edit (c)), so such a launch has run by then.
+
+    What this does not prove: the samples bring nothing to the call but their resident genotypes, uploaded when the panel was made, so a
+    library that left xyt_order out would pass.  The test runs the event branch (record, wait, give the event back: debug_live), on every
+    kind of pair; it does not show that the wait is needed."""
+    import bwgr_amd
+    torch = env.torch
+    _, call, ok = ENTRIES[name]
+    F, S = env.P["slabs"], env.aux["S"]
+    first = call(F, env.aux)
+    again, entry_ms = env.timed(lambda: call(F, env.aux))
+    live = bwgr_amd.debug_live()
+    _same(first, again, "two calls on the default stream")
+    ok(first)
+    S.kernel2(F, "GAU", 0.5); F.kernel2(S, "GAU", 0.5)
+    streams = {"root": None, "s": env.s, "s2": env.s2}
+    hf, hs = PAIR_HANDLES[how]
+    Qf, Qs = (F.clone() if hf == "clone" else F), (S.clone() if hs == "clone" else S)
+    timers = []
+    try:
+        for Q, h in ((Qf, hf), (Qs, hs)):
+            if h in ("s", "s2"):
+                Q.set_stream(streams[h].cuda_stream)
+        idle_null = not ({hf, hs} & {"root", "clone"})      # (a clone's partner is a root on the default stream)
+        null = env.busy_null(entry_ms) if idle_null else None
+        for h in sorted({hf, hs} - {"clone"}):
+            timers.append(env.busy(entry_ms, torch.cuda.default_stream() if h == "root" else streams[h]))
+        got = call(Qf, {"S": Qs})
+        torch.cuda.synchronize()
+        filler_ms = [e0.elapsed_time(e1) for e0, e1 in timers]
+        null_ms = null[0].elapsed_time(null[1]) if idle_null else None
+    finally:
+        for Q, h in ((Qf, hf), (Qs, hs)):
+            if h == "clone":
+                Q.close()
+            else:
+                Q.set_stream(0)
+    back = call(F, env.aux)
+    print("%s, %s: entry %.3f ms, fillers %s ms%s" % (name, how, entry_ms, ", ".join("%.3f" % m for m in filler_ms),
+                                                       ", %.3f ms on the null stream" % null_ms if idle_null else ""))
+    assert filler_ms and all(m >= FILL * entry_ms for m in filler_ms), (filler_ms, entry_ms)
+    assert idle_null == (how in ("both_on_one_stream", "each_on_its_own_stream")) and (not idle_null or null_ms >= max(filler_ms) + entry_ms)
+    _same(first, got, how)
     _same(first, back, "back on the default stream")
     assert bwgr_amd.debug_live() == live
 

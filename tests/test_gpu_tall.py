@@ -1,4 +1,4 @@
-"""GPU: the fp64 families -- uvbeta, mrr, panel_xb, the relationship kernels, XSEMF / ZSEMF / YSEMF -- against their float64 restatements on
+"""GPU: the fp64 families -- uvbeta, mrr, panel_xb, the relationship kernels, XSEMF / ZSEMF / YSEMF, uvbeta2, MEGA / GSEM -- against their float64 restatements on
 the shapes of tests/tall_cases.py: tall panels on which the tail reductions and the passes take a second and a third trip, slabs of 1 280
 and 1 024 rows (and one slab of 1 152: kern1100s, where the slab base is always 0), row tiles of panel_xb across slabs, wide panels on which the marker reductions take a second trip.
 tests/test_tall_cases_cpu.py proves without a GPU that each shape reaches what it is listed for.
@@ -23,6 +23,7 @@ import uvb_restatement as UR  # noqa: E402
 from test_gpu_drivers import _raw_panel  # noqa: E402
 from test_gpu_mrr import _check as _mrr_check, _traits  # noqa: E402
 from test_gpu_sem import _check as _sem_check, _strong, _well_posed  # noqa: E402
+from test_gpu_sem2 import _check as _uvb2_check, _check_driver  # noqa: E402
 from test_gpu_uvb import _check, _f32, _ref, _W  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -221,11 +222,18 @@ def test_crossprod_and_kernel_in_forced_chunks(panel, monkeypatch):
     assert pl["forced_chunks"] == 3 and pl["xxt_zero"] == 3
     monkeypatch.setenv("BWGR_KCHUNK", str(pl["kchunk"]))     # read when the root panel is made
     P = bwgr_amd.Panel(tc.data(tag))
+    # (a device array of the caller's that holds -9 everywhere beforehand: an entry that is added to without having been zeroed shows there,
+    # whatever a fresh allocation of the library's own happens to hold)
+    import torch
+    from bwgr_amd import _lib
+    Gd = torch.full((P.n, P.n), -9, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
     try:
         G, K = P.crossprod(), P.kernel("GRM")
+        assert _lib.lib().bwgr_panel_crossprod(P._h, C.c_void_p(Gd.data_ptr()), P.n, DEVICE) == 0
     finally:
         P.close()
-    assert np.array_equal(G, _crossprod_ref(tag))
+    assert np.array_equal(G, _crossprod_ref(tag)) and np.array_equal(Gd.cpu().numpy(), G)
     assert np.array_equal(K, panel(tag).kernel("GRM"))
 
 
@@ -296,6 +304,48 @@ def test_sem_with_the_references_defaults_on_a_tall_panel(panel, name):
     assert near >= 0.02 and all(d["its"].max() < 100 for d in stages) and o["npc"] == 3
     g = getattr(bwgr_amd, name)(Y, panel(tag))
     _sem_check(name, g, o)
+
+
+# ---- uvbeta2 / MEGA / GSEM ----
+UVB2_JOBS = [("tall9k", 3), ("slab1280", 3), ("slab1280", 65)]
+
+
+@pytest.mark.parametrize("tag,k", UVB2_JOBS, ids=["%s-k%d" % j for j in UVB2_JOBS])
+def test_uvbeta2(panel, tag, k):
+    """solver2x per trait, q = 3, 10 % missing, six sweeps: tall9k (three tiles per pass workgroup, a second trip of k_uvb_rows, 216 padding
+    rows) and slab1280 (slabs of 1 280 rows, 120 padding rows); k = 65 there is two groups of traits, the dense leg launched per group
+    against rows of E that lie ld apart."""
+    import bwgr_amd
+    c = tc.uvb2_case(tag, k)
+    g = bwgr_amd.uvbeta2(c["Y"], c["Z"], panel(tag), **c["kw"])
+    _uvb2_check(g, tc.uvb2_ref(tag, k), "%s k=%d" % (tag, k))
+    assert g["b1"].shape == (3, k) and g["b2"].shape == (tc.CASES[tag]["p"], k) and list(g["its"]) == [6] * k
+
+
+@pytest.mark.parametrize("name", ["MEGA", "GSEM"])
+def test_two_design_drivers_on_tall_slabs(panel, name):
+    """5 000 x 200 in 1 280-row slabs, three traits, six sweeps per stage: three (MEGA) or two panel fits, panel_xb and uvbeta2 chained on one
+    panel.  tests/test_tall_cases_cpu.py asserts the preconditions on the restatement (finite, singular values apart)."""
+    import bwgr_amd
+    tag = "slab1280"
+    g = getattr(bwgr_amd, name)(tc.driver_traits(tag), panel(tag), **tc.SEM2_DRIVERS[tag]["kw"])
+    _check_driver(name, g, tc.driver_ref(name, tag))
+
+
+@pytest.mark.parametrize("name", ["MEGA", "GSEM"])
+def test_two_design_drivers_with_the_references_defaults_on_a_tall_panel(panel, name):
+    """9 000 x 200, maxit = 100, tol = 10e-7: every stage stops by its own test after 2 to 6 sweeps and no cnv of the restatement comes nearer
+    than 0.02 to log10(tol) (tests/test_tall_cases_cpu.py asserts it; the nearest is 0.112), so the sweep counts agree.  The panel that was
+    passed in stays usable."""
+    import bwgr_amd
+    tag = "tall9k"
+    X, P = tc.data(tag), panel(tag)
+    g = getattr(bwgr_amd, name)(tc.driver_traits(tag), P)
+    _check_driver(name, g, tc.driver_ref(name, tag))
+    again = P.xb(g["b"])
+    assert MR.scaled_err(again, X.astype(np.float64) @ g["b"]) <= 1e-12
+    if name == "MEGA":
+        assert MR.scaled_err(again + g["mu"], g["gebv"]) <= 1e-12
 
 
 # ---- state ----

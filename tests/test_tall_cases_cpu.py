@@ -67,6 +67,53 @@ def test_cases_reach_every_regime_together():
     assert {pl["R"] for pl in kern} >= {256, 1024} and len({pl["R"] for pl in kern}) == 3 and any(pl["R"] != 256 and pl["K"] > 1 for pl in kern)
 
 
+@pytest.mark.parametrize("name", ["MEGA", "GSEM"])
+@pytest.mark.parametrize("tag", list(tc.SEM2_DRIVERS))
+def test_two_design_driver_cases_are_well_posed(tag, name):
+    """Preconditions on the inputs of test_gpu_tall's MEGA / GSEM cases, as tests/test_sem2_cpu.py states them, asserted on the restatement:
+    every output finite (GSEM may diverge on a trait; here it does not), neighbouring singular values of the decomposed matrix (Y2 for MEGA,
+    G for GSEM) at least 5 % of the largest apart, and npc = 3.  slab1280 / seed 3001: gaps 0.173 (Y2) and 0.226 (G), six sweeps in every
+    stage.  tall9k / seed 3011 at the reference's defaults: 0.180 and 0.354; every stage stops by its own test after 2 to 6 sweeps, and no cnv
+    of any stage comes nearer than 0.02 to log10(tol) (the nearest is 0.115 for MEGA and 0.112 for GSEM), so the sweep counts are not a
+    matter of rounding."""
+    import numpy as np
+    import sem2_cases as S2C
+    o = tc.driver_ref(name, tag)
+    s = o["s"]
+    gap = float(np.min(-np.diff(s)) / s[0])
+    stages = S2C.stages(name, o)
+    print(name, tag, gap, [list(d["its"]) for d in stages])
+    assert gap >= 0.05 and o["npc"] == 3 == len(s), (gap, s)
+    for key in ("mu", "b", "hat", "BETA1", "BETA2") + (("LS", "LS_BETA", "gebv") if name == "MEGA" else ()):
+        assert np.all(np.isfinite(o[key])), key
+    if tc.SEM2_DRIVERS[tag]["kw"]:
+        assert all((d["its"] == 6).all() for d in stages)
+    else:
+        logtol = np.log10(10e-7)
+        near = min(abs(c - logtol) for d in stages for tr in d["trace"] for c in tr)
+        print(near)
+        assert near >= 0.02 and all(0 < d["its"].min() and d["its"].max() < 100 for d in stages)
+
+
+def test_two_design_engine_cases_are_what_they_say():
+    """uvbeta2 on tall9k and slab1280: 10 % missing in every trait, each trait its own rows, q = 3; k = 65 is two groups of traits (the
+    second of one trait).  The restatement makes six sweeps and gives finite results on both k = 3 cases (asserted here); the 65-trait
+    restatement takes seconds and is run by the GPU test alone, which asserts the library's six sweeps per trait against it."""
+    import numpy as np
+    for (tag, k) in tc.SEM2_ENGINE:
+        c = tc.uvb2_case(tag, k)
+        n = tc.CASES[tag]["n"]
+        miss = np.isnan(c["Y"]).mean(0)
+        assert c["Y"].shape == (n, k) and c["Z"].shape == (n, 3) and c["kw"] == dict(maxit=6, tol=0)
+        assert miss.min() > 0.08 and miss.max() < 0.12 and len({np.isnan(c["Y"][:, t]).tobytes() for t in range(k)}) == k
+    for tag in ("tall9k", "slab1280"):
+        o = tc.uvb2_ref(tag, 3)
+        assert list(o["its"]) == [6, 6, 6] and all(np.isfinite(o[key]).all() for key in ("b1", "b2", "mu", "h2", "ve", "vb1", "vb2", "cnv")), tag
+    import bwgr_amd
+    pl = bwgr_amd.uvb_plan(5000, 200, 65)
+    assert pl["groups"] == 2 and pl["W"] == 64
+
+
 def test_the_old_shapes_did_not_reach_them():
     """What the issue is about, pinned: on tpod (196 x 376), the 700 x 900 three-slab panel and mrr's 4 100 rows every one of these kernels
     makes a single trip, and k_pxb runs one row tile."""
