@@ -1,5 +1,8 @@
-// bwgr_amd/csrc/bwgr_hip.hip -- libbwgr_hip.so: C ABI (include/bwgr.h) + setup / per-iteration / finalisation
-// kernels around the blocked sweep (sweep.hip.h).  gfx950 only; there is no CPU path in this library.
+// bwgr_amd/csrc/bwgr_hip.hip -- libbwgr_hip.so, the one translation unit of the C ABI (include/bwgr.h).  This file holds what every family
+// shares on the host: error plumbing, the switches, the panel plans, the HIP backend of the holder, the handles and their small helpers, the
+// occupancy guard, a sweep's planning and launching, the panel entries, the launch rules of X * coef and the test hooks.  It defines no kernel
+// and no family's entry point: the kernels are the *.hip.h files included at the top, the entries the *_host.hip.h files included near the end.
+// gfx950 only; there is no CPU path in this library.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -32,6 +35,13 @@
 
 using namespace bwgr;
 
+// the kernels around the sweep, by family (each says in its header what it holds); the host entries that launch them are included further
+// down, where everything they use is defined
+#include "panel.hip.h"
+#include "chain.hip.h"
+#include "wgr.hip.h"
+#include "em.hip.h"
+
 // ------------------------------------------------------------------------------------------------
 // error plumbing
 // ------------------------------------------------------------------------------------------------
@@ -60,885 +70,10 @@ extern "C" int bwgr_device_count(int *count) {
   return BWGR_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// device helpers
-// ------------------------------------------------------------------------------------------------
-namespace {
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-// block-wide sum; result valid in every thread.  red must hold >= 17 doubles.
-__device__ inline double block_sum(double v, double *red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-  v = wave_sum(v);
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) { double s = 0; for (int w = 0; w < nw; ++w) s += red[w]; red[16] = s; }
-  __syncthreads();
-  return red[16];
-}
-
-__device__ __forceinline__ float xval(const int8_t *X, int64_t i) { return (float)X[i]; }
-__device__ __forceinline__ float xval(const float *X, int64_t i) { return X[i]; }
-
-// ---- upload conversion: src (n x p, ldx) -> X (ld x p), zero padded rows ----
-template <typename ST, typename XT>
-__global__ void k_convert(const ST *src, int64_t ldx, XT *X, int64_t ld, int n, int64_t j0, int64_t ncols, int R, int64_t p) {
-  const int64_t total = ncols * ld;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t jj = idx / ld, i = idx - jj * ld;
-    XT v = (XT)0;
-    if (i < n) v = (XT)src[jj * ldx + i];
-    X[xoff(i, j0 + jj, R, p)] = v;
-  }
-}
-
-__global__ void k_f2d(const float *src, double *dst, int64_t n, int64_t ld) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < ld; i += (int64_t)gridDim.x * blockDim.x) dst[i] = (i < n) ? (double)src[i] : 0.0;
-}
-__global__ void k_d2f(const double *src, float *dst, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = (float)src[i];
-}
-
-// ---- a10: xx[j] = |X_j|^2, vx[j] = fvar(X_j)   (src/Rcpp20260726ai.cpp:7-9, 593-597); one wave per column ----
-template <typename XT>
-__global__ void k_stats(const XT *X, int R, int n, int p, float *xx, float *vx) {
-  const int lane = threadIdx.x & 63;
-  const int64_t j = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (j >= p) return;
-  double s1 = 0, s2 = 0;
-  for (int i = lane; i < n; i += 64) { const float v = xval(X, xoff(i, j, R, p)); s1 += (double)v; s2 += (double)v * (double)v; }
-  s1 = wave_sum(s1); s2 = wave_sum(s2);
-  s1 = __shfl(s1, 0, 64); s2 = __shfl(s2, 0, 64);
-  const float mean = (float)(s1 / (double)n);
-  double sv = 0;
-  for (int i = lane; i < n; i += 64) { const float dev = xval(X, xoff(i, j, R, p)) - mean; const float sq = dev * dev; sv += (double)sq; }
-  sv = wave_sum(sv);
-  if (lane == 0) { xx[j] = (float)s2; vx[j] = (float)(sv / (double)(float)(n - 1)); }
-}
-
-// ---- implicit centring of an int8 panel (bwgr_panel_set_centred): s_j = sum_i x_ij exactly, and the centred column's squared norm
-// sum_i (x_ij - s_j / n)^2 = sum x^2 - s_j^2 / n from exact integer sums, rounded to float once (the reference would form it from the centred
-// float column, X.colwise().squaredNorm(), src/Rcpp20260726ai.cpp:593-594); one wave per column ----
-__global__ void k_colsum_i8(const int8_t *X, int R, int n, int p, int32_t *csum, float *xxc) {
-  const int lane = threadIdx.x & 63;
-  const int64_t j = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (j >= p) return;
-  long long s1 = 0, s2 = 0;
-  for (int i = lane; i < n; i += 64) { const int v = (int)X[xoff(i, j, R, p)]; s1 += v; s2 += v * v; }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_down(s1, o, 64); s2 += __shfl_down(s2, o, 64); }
-  if (lane == 0) { csum[j] = (int32_t)s1; xxc[j] = (float)((double)s2 - (double)s1 * (double)s1 / (double)n); }
-}
-// sum_j s_j coef_j / n  (one workgroup, fixed order): what the centred columns take off X * coef
-__global__ __launch_bounds__(1024) void k_cen_dot(const int32_t *csum, const float *coef, int64_t p, double ninv, double *out) {
-  __shared__ double red[1024];
-  const int t = threadIdx.x;
-  double s = 0.0;
-  for (int64_t j = t; j < p; j += 1024) s = fma((double)csum[j], (double)coef[j], s);
-  red[t] = s;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) { if (t < o) red[t] += red[t + o]; __syncthreads(); }
-  if (t == 0) *out = red[0] * ninv;
-}
-
-// deterministic two-stage sum of a float vector into a double
-__global__ void k_sum_stage1(const float *v, int64_t n, double *part) {
-  __shared__ double red[17];
-  double s = 0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) s += (double)v[i];
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) part[blockIdx.x] = s;
-}
-__global__ void k_sum_stage2(const double *part, int nparts, float *out_f) {
-  __shared__ double red[17];
-  double s = 0;
-  for (int i = threadIdx.x; i < nparts; i += blockDim.x) s += part[i];
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) *out_f = (float)s;
-}
-
-// ---- block-diagonal Gram G_B = X_B' X_B (setup; exact int32 for int8 genotypes) ----
-// 256 threads as a 16 x 16 grid, thread (tj,tk) owns G[tj+16a][tk+16c], a,c < m/16.
-template <int TJ>
-__global__ __launch_bounds__(256) void k_gram_i8(const int8_t *X, int64_t ld, int R, int p, int m, int32_t *gram) {
-  constexpr int RC = 128, RW = RC / 4 + 1;  // rows per chunk, dwords per column in LDS (padded)
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  int32_t *tile = reinterpret_cast<int32_t *>(smem);
-  const int blk = blockIdx.x, j0 = blk * m, mB = min(m, p - j0);
-  const int tj = threadIdx.x >> 4, tk = threadIdx.x & 15;
-  int32_t acc[TJ][TJ];
-#pragma unroll
-  for (int a = 0; a < TJ; ++a)
-#pragma unroll
-    for (int c = 0; c < TJ; ++c) acc[a][c] = 0;
-  for (int64_t r0 = 0; r0 < ld; r0 += RC) {
-    __syncthreads();
-    for (int c = threadIdx.x; c < m * (RC / 4); c += 256) {
-      const int jj = c / (RC / 4), w = c - jj * (RC / 4);
-      int32_t v = 0;
-      if (jj < mB) v = *reinterpret_cast<const int32_t *>(X + xoff(r0 + 4 * w, j0 + jj, R, p));
-      tile[jj * RW + w] = v;
-    }
-    __syncthreads();
-    for (int w = 0; w < RC / 4; ++w) {
-      int32_t av[TJ], bv[TJ];
-#pragma unroll
-      for (int a = 0; a < TJ; ++a) { av[a] = tile[(tj + 16 * a) * RW + w]; bv[a] = tile[(tk + 16 * a) * RW + w]; }
-#pragma unroll
-      for (int a = 0; a < TJ; ++a)
-#pragma unroll
-        for (int c = 0; c < TJ; ++c) acc[a][c] = __builtin_amdgcn_sdot4(av[a], bv[c], acc[a][c], false);
-    }
-  }
-  int32_t *g = gram + (size_t)blk * m * m;
-#pragma unroll
-  for (int a = 0; a < TJ; ++a)
-#pragma unroll
-    for (int c = 0; c < TJ; ++c) g[(size_t)(tj + 16 * a) * m + (tk + 16 * c)] = acc[a][c];
-}
-
-// m = 128: the same blocks on the matrix cores.  out[blk][i][j] = X_{(blk-dist)m+i} . X_{blk*m+j} (dist = 0: the diagonal block),
-// exact in the int32 accumulators.  One workgroup of four waves per block; wave w owns the 64 x 64 quadrant (4 x 4 tiles of
-// 16 x 16); v_mfma_i32_16x16x64_i8 takes, per lane (m16, grp), the 16 bytes of marker 16t + m16 at rows 64kk + 16grp .. +15 for
-// both operands -- straight from the slab-major panel, whose markers are contiguous along the rows -- and returns
-// out[16ti + 4grp + reg][16tj + m16].  Per 64 rows a wave issues 8 loads and 16 MFMAs (the sdot4 kernels above ran at
-// 0.75 TB/s: one dword per thread per load and an LDS round trip).
-__global__ __launch_bounds__(256) void k_gram_mfma_i8(const int8_t *X, int64_t ld, int R, int p, int32_t *out, int dist) {
-  constexpr int m = 128;
-  const int blk = blockIdx.x + dist, ia0 = (blk - dist) * m, jb0 = blk * m;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m16 = lane & 15, grp = lane >> 4;
-  const int ti0 = 4 * (wave >> 1), tj0 = 4 * (wave & 1);
-  s2_v4i acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[a][c] = s2_v4i{0, 0, 0, 0};
-  // markers past the panel (last block) are read at a clamped column and zeroed
-  int ca[4], cb[4]; bool oka[4], okb[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int ja = ia0 + 16 * (ti0 + t) + m16, jb = jb0 + 16 * (tj0 + t) + m16;
-    oka[t] = ja < p; okb[t] = jb < p; ca[t] = min(ja, p - 1); cb[t] = min(jb, p - 1);
-  }
-  const s2_v4i zero = {0, 0, 0, 0};
-  // software pipeline: the operands of step k+1 are requested before the sixteen MFMAs of step k
-  auto load_step = [&](int64_t r0, s2_v4i (&av)[4], s2_v4i (&bv)[4]) {
-    const int64_t sl = r0 / R;
-    const size_t roff = (size_t)(r0 - sl * R) + 16 * grp;
-    const int8_t *sb = X + (size_t)sl * p * R + roff;       // slab base + row offset; marker j adds j*R
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      av[t] = *reinterpret_cast<const s2_v4i *>(sb + (size_t)ca[t] * R);
-      bv[t] = *reinterpret_cast<const s2_v4i *>(sb + (size_t)cb[t] * R);
-    }
-  };
-  s2_v4i av[4], bv[4], an[4], bn[4];
-  load_step(0, av, bv);
-  for (int64_t r0 = 0; r0 < ld; r0 += 64) {
-    const bool more = r0 + 64 < ld;
-    load_step(more ? r0 + 64 : r0, an, bn);                 // (the last step reloads its own operands: harmless)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) { av[t] = oka[t] ? av[t] : zero; bv[t] = okb[t] ? bv[t] : zero; }
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc[a][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(av[a], bv[c], acc[a][c], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) { av[t] = an[t]; bv[t] = bn[t]; }
-  }
-  int32_t *g = out + (size_t)blk * m * m;
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg)
-        g[(size_t)(16 * (ti0 + a) + 4 * grp + reg) * m + 16 * (tj0 + c) + m16] = acc[a][c][reg];
-}
-
-// off-diagonal blocks for the pipelined sweep: gramx[blk][k][j] = X_{(blk-dist)m+k} . X_{blk*m+j}, blk >= dist (dist = 1, 2)
-template <int TJ>
-__global__ __launch_bounds__(256) void k_gramx_i8(const int8_t *X, int64_t ld, int R, int p, int m, int32_t *gramx, int dist) {
-  constexpr int RC = 128, RW = RC / 4 + 1;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  int32_t *ta = reinterpret_cast<int32_t *>(smem), *tb = ta + (size_t)m * RW;
-  const int blk = blockIdx.x + dist, ja0 = (blk - dist) * m, jb0 = blk * m, mBb = min(m, p - jb0);
-  const int tj = threadIdx.x >> 4, tk = threadIdx.x & 15;
-  int32_t acc[TJ][TJ];
-#pragma unroll
-  for (int a = 0; a < TJ; ++a)
-#pragma unroll
-    for (int c = 0; c < TJ; ++c) acc[a][c] = 0;
-  for (int64_t r0 = 0; r0 < ld; r0 += RC) {
-    __syncthreads();
-    for (int c = threadIdx.x; c < m * (RC / 4); c += 256) {
-      const int jj = c / (RC / 4), w = c - jj * (RC / 4);
-      ta[jj * RW + w] = *reinterpret_cast<const int32_t *>(X + xoff(r0 + 4 * w, ja0 + jj, R, p));
-      tb[jj * RW + w] = (jj < mBb) ? *reinterpret_cast<const int32_t *>(X + xoff(r0 + 4 * w, jb0 + jj, R, p)) : 0;
-    }
-    __syncthreads();
-    for (int w = 0; w < RC / 4; ++w) {
-      int32_t av[TJ], bv[TJ];
-#pragma unroll
-      for (int a = 0; a < TJ; ++a) { av[a] = ta[(tj + 16 * a) * RW + w]; bv[a] = tb[(tk + 16 * a) * RW + w]; }
-#pragma unroll
-      for (int a = 0; a < TJ; ++a)
-#pragma unroll
-        for (int c = 0; c < TJ; ++c) acc[a][c] = __builtin_amdgcn_sdot4(av[a], bv[c], acc[a][c], false);
-    }
-  }
-  int32_t *g = gramx + (size_t)blk * m * m;
-#pragma unroll
-  for (int a = 0; a < TJ; ++a)
-#pragma unroll
-    for (int c = 0; c < TJ; ++c) g[(size_t)(tj + 16 * a) * m + (tk + 16 * c)] = acc[a][c];
-}
-template <int TJ>
-__global__ __launch_bounds__(256) void k_gramx_f32(const float *X, int64_t ld, int R, int p, int m, double *gramx, int dist) {
-  constexpr int RC = 64, RW = RC + 1;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float *ta = reinterpret_cast<float *>(smem), *tb = ta + (size_t)m * RW;
-  const int blk = blockIdx.x + dist, ja0 = (blk - dist) * m, jb0 = blk * m, mBb = min(m, p - jb0);
-  const int tj = threadIdx.x >> 4, tk = threadIdx.x & 15;
-  double acc[TJ][TJ];
-#pragma unroll
-  for (int a = 0; a < TJ; ++a)
-#pragma unroll
-    for (int c = 0; c < TJ; ++c) acc[a][c] = 0.0;
-  for (int64_t r0 = 0; r0 < ld; r0 += RC) {
-    __syncthreads();
-    for (int c = threadIdx.x; c < m * RC; c += 256) {
-      const int jj = c / RC, w = c - jj * RC;
-      ta[jj * RW + w] = X[xoff(r0 + w, ja0 + jj, R, p)];
-      tb[jj * RW + w] = (jj < mBb) ? X[xoff(r0 + w, jb0 + jj, R, p)] : 0.0f;
-    }
-    __syncthreads();
-    for (int w = 0; w < RC; ++w) {
-      double av[TJ], bv[TJ];
-#pragma unroll
-      for (int a = 0; a < TJ; ++a) { av[a] = (double)ta[(tj + 16 * a) * RW + w]; bv[a] = (double)tb[(tk + 16 * a) * RW + w]; }
-#pragma unroll
-      for (int a = 0; a < TJ; ++a)
-#pragma unroll
-        for (int c = 0; c < TJ; ++c) acc[a][c] = fma(av[a], bv[c], acc[a][c]);
-    }
-  }
-  double *g = gramx + (size_t)blk * m * m;
-#pragma unroll
-  for (int a = 0; a < TJ; ++a)
-#pragma unroll
-    for (int c = 0; c < TJ; ++c) g[(size_t)(tj + 16 * a) * m + (tk + 16 * c)] = acc[a][c];
-}
-
-template <int TJ>
-__global__ __launch_bounds__(256) void k_gram_f32(const float *X, int64_t ld, int R, int p, int m, double *gram) {
-  constexpr int RC = 64, RW = RC + 1;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float *tile = reinterpret_cast<float *>(smem);
-  const int blk = blockIdx.x, j0 = blk * m, mB = min(m, p - j0);
-  const int tj = threadIdx.x >> 4, tk = threadIdx.x & 15;
-  double acc[TJ][TJ];
-#pragma unroll
-  for (int a = 0; a < TJ; ++a)
-#pragma unroll
-    for (int c = 0; c < TJ; ++c) acc[a][c] = 0.0;
-  for (int64_t r0 = 0; r0 < ld; r0 += RC) {
-    __syncthreads();
-    for (int c = threadIdx.x; c < m * RC; c += 256) {
-      const int jj = c / RC, w = c - jj * RC;
-      tile[jj * RW + w] = (jj < mB) ? X[xoff(r0 + w, j0 + jj, R, p)] : 0.0f;
-    }
-    __syncthreads();
-    for (int w = 0; w < RC; ++w) {
-      double av[TJ], bv[TJ];
-#pragma unroll
-      for (int a = 0; a < TJ; ++a) { av[a] = (double)tile[(tj + 16 * a) * RW + w]; bv[a] = (double)tile[(tk + 16 * a) * RW + w]; }
-#pragma unroll
-      for (int a = 0; a < TJ; ++a)
-#pragma unroll
-        for (int c = 0; c < TJ; ++c) acc[a][c] = fma(av[a], bv[c], acc[a][c]);
-    }
-  }
-  double *g = gram + (size_t)blk * m * m;
-#pragma unroll
-  for (int a = 0; a < TJ; ++a)
-#pragma unroll
-    for (int c = 0; c < TJ; ++c) g[(size_t)(tj + 16 * a) * m + (tk + 16 * c)] = acc[a][c];
-}
-
-// strict upper triangle of the diagonal Gram blocks, row-packed: entry (k, j>k) at k(m-1) - k(k-1)/2 + (j-k-1)
-template <typename GT>
-__global__ void k_gram_pack(const GT *gram, GT *gramp, int m, int pstride, int64_t nblocks) {
-  const int64_t blk = blockIdx.x;
-  const GT *G = gram + (size_t)blk * m * m;
-  GT *P = gramp + (size_t)blk * pstride;
-  for (int e = threadIdx.x; e < m * m; e += blockDim.x) {
-    const int k = e / m, j = e - k * m;
-    if (j > k) P[k * (m - 1) - k * (k - 1) / 2 + (j - k - 1)] = G[e];
-  }
-  for (int e = m * (m - 1) / 2 + threadIdx.x; e < pstride; e += blockDim.x) P[e] = (GT)0;
-}
-
-// 16-bit copies of the packed and the distance-1 cross Gram blocks for the k_sweep2 sequencer (half the bytes through its
-// CU per block); *bad is set when an entry does not fit, and the sequencer then stages the 32-bit arrays
-// largest |x| of an int8 panel (k_sweep3's integer sums are sized by it)
-__global__ void k_absmax_i8(const int8_t *X, size_t count, int *out) {
-  int mx = 0;
-  for (size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 16; i < count; i += (size_t)gridDim.x * blockDim.x * 16) {
-    const uint4 v = *reinterpret_cast<const uint4 *>(X + i);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) { const int x = (int)(int8_t)(w[q] >> (8 * c)); mx = max(mx, x < 0 ? -x : x); }
-  }
-  atomicMax(out, mx);
-}
-__global__ void k_gram_narrow(const int32_t *src, uint16_t *dst, int64_t count, int *bad) {
-  int any = 0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
-    const int32_t v = src[i];
-    any |= (v < 0 || v > 65535);
-    dst[i] = (uint16_t)v;
-  }
-  if (any) *bad = 1;
-}
-
-// ---- chain setup (src/Rcpp20260726ai.cpp:599-610 and the identical blocks of the other samplers) ----
-struct InitArgs {
-  const float *y; double *e; int n, p; int64_t ld; int model; float pi, df, R2; float MSx; ChainScalars *sc;
-};
-__global__ void k_chain_init(const InitArgs a) {
-  __shared__ double red[17];
-  double s = 0;
-  for (int i = threadIdx.x; i < a.n; i += blockDim.x) s += (double)a.y[i];
-  s = block_sum(s, red);
-  const float mu = (float)(s / (double)a.n);               // y.mean()
-  double sv = 0;
-  for (int i = threadIdx.x; i < a.n; i += blockDim.x) { const float dev = a.y[i] - mu; const float sq = dev * dev; sv += (double)sq; }
-  sv = block_sum(sv, red);
-  const float vy = (float)(sv / (double)(float)(a.n - 1));   // fvar(y)
-  for (int i = threadIdx.x; i < a.ld; i += blockDim.x) { const float t = (i < a.n) ? (a.y[i] - mu) : 0.0f; a.e[i] = (double)t; }
-  if (threadIdx.x == 0) {
-    float pi = a.pi;
-    if (a.model == BWGR_BAYESCPI || a.model == BWGR_BAYESDPI) pi = 0.5f;
-    float Sb;
-    if (a.model == BWGR_BAYESC || a.model == BWGR_BAYESCPI) Sb = a.df * (a.R2) * vy / a.MSx / (1 - pi);
-    else Sb = (a.R2) * a.df * vy / a.MSx;
-    ChainScalars sc;
-    memset(&sc, 0, sizeof(sc));
-    sc.ve = vy; sc.vb = Sb; sc.lam = vy / Sb; sc.pi = pi;
-    sc.Sb = Sb; sc.Se = (1 - a.R2) * a.df * vy; sc.C = -0.5f / sqrtf(vy); sc.odds = pi / (1.0f - pi);
-    sc.mu = mu; sc.dfp1 = a.df + 1; sc.vy = vy; sc.MSx = a.MSx;
-    sc.inc_rate = 1.0f - pi;
-    *a.sc = sc;
-  }
-}
-__global__ void k_marker_init(float *b, float *d, float *vb, float *lam, float *B, float *D, float *VB, int p,
-                              const ChainScalars *sc) {
-  const float Sb = sc->Sb, ve = sc->ve;
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < p; j += gridDim.x * blockDim.x) {
-    b[j] = 0; d[j] = 0; B[j] = 0; D[j] = 0; VB[j] = 0;
-    vb[j] = Sb;
-    lam[j] = ve * (1.0f / Sb);   // ve * vb.cwiseInverse()
-  }
-}
-
-// ---- per-iteration tail: intercept, residual / marker variances, pi (one workgroup) ----
-struct TailArgs {
-  double *e; int n, p; int model; float df, R2, Phi; int accumulate; uint32_t iter; Rng rng; ChainScalars *sc;
-};
-__global__ __launch_bounds__(1024) void k_tail(const TailArgs a) {
-  __shared__ double red[17];
-  ChainScalars &sc = *a.sc;
-  const float ve0 = sc.ve;
-  double s = 0;
-  for (int i = threadIdx.x; i < a.n; i += blockDim.x) s += a.e[i];
-  s = block_sum(s, red);
-  const float me = (float)(s / (double)a.n);                                        // e.mean()
-  const double z = rng_normal(a.rng, RNG_GLOBAL_MARKER, a.iter, RNG_G_MU, 0);
-  const float eM = (float)((double)me + (double)sqrtf(ve0 / a.n) * z);              // :620
-  double ss = 0;
-  for (int i = threadIdx.x; i < a.n; i += blockDim.x) { const double v = a.e[i] - (double)eM; a.e[i] = v; ss = fma(v, v, ss); }
-  ss = block_sum(ss, red);
-  if (threadIdx.x == 0) {
-    const float ssf = (float)ss;                                                    // e.squaredNorm()
-    const float b2f = (float)sc.sum_b2;                                             // b.squaredNorm()
-    float ve = ve0, vb = sc.vb, pi = sc.pi, Sb = sc.Sb;
-    const float mu = sc.mu + eM;
-    const double chi_e = rng_chisq(a.rng, (double)(a.n + a.df), RNG_GLOBAL_MARKER, a.iter, RNG_G_VE);
-    switch (a.model) {
-      case BWGR_BAYESA: case BWGR_BAYESB: case BWGR_BAYESDPI: case BWGR_BAYESL:
-        ve = (float)((double)(ssf + sc.Se) / chi_e);
-        break;
-      case BWGR_BAYESRR: {
-        ve = (float)((double)(ssf + sc.Se) / chi_e);
-        const double chi_b = rng_chisq(a.rng, (double)(a.p + a.df), RNG_GLOBAL_MARKER, a.iter, RNG_G_VB);
-        vb = (float)((double)(b2f + Sb) / chi_b);
-        sc.lam = ve / vb;
-      } break;
-      case BWGR_BAYESC: case BWGR_BAYESCPI: {
-        const double chi_b = rng_chisq(a.rng, (double)(a.df + a.p), RNG_GLOBAL_MARKER, a.iter, RNG_G_VB);
-        vb = (float)((double)(b2f + Sb) / chi_b);
-        ve = (float)((double)(ssf + sc.Se) / chi_e);
-        sc.lam = ve / vb;
-      } break;
-    }
-    if (a.model == BWGR_BAYESCPI) {
-      pi = (float)(sc.sum_d / (double)a.p);
-      Sb = a.df * (a.R2) * sc.vy / sc.MSx / (1 - pi);
-    }
-    if (a.model == BWGR_BAYESDPI) pi = (float)(sc.sum_d / (double)a.p);
-    sc.ve = ve; sc.vb = vb; sc.pi = pi; sc.Sb = Sb; sc.mu = mu;
-    sc.C = -0.5f / sqrtf(ve);
-    sc.inc_rate = (float)(sc.sum_d / (double)a.p);
-    sc.sum_d = 0.0; sc.sum_b2 = 0.0;
-    if (a.accumulate) { sc.MU += mu; sc.VE += ve; sc.VBs += vb; sc.Pi += pi; }
-  }
-}
-// per-marker part of the tail: lambda_j for the next sweep and the posterior sums
-__global__ void k_marker_tail(const float *b, const float *d, const float *vb, float *lam, float *B, float *D, float *VB,
-                              int p, int model, float Phi, int accumulate, const ChainScalars *sc) {
-  const float ve = sc->ve;
-  const bool per = (model == BWGR_BAYESA || model == BWGR_BAYESB || model == BWGR_BAYESDPI || model == BWGR_BAYESL);
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < p; j += gridDim.x * blockDim.x) {
-    if (per) {
-      const float v = vb[j];
-      lam[j] = (model == BWGR_BAYESL) ? sqrtf(Phi * ve / v) : ve * (1.0f / v);
-      if (accumulate) VB[j] += v;
-    }
-    if (accumulate) { B[j] += b[j]; D[j] += d[j]; }
-  }
-}
-
-// ---- tail of the two-effect samplers (src/Rcpp20260726ai.cpp:1042-1047, :1138-1143, :1204-1210): one intercept and one
-// residual variance from the shared residual; RR2 also draws the two common marker variances (second chi-square with
-// the marker word RNG_GLOBAL_MARKER - 1).  Scalars are written to both chains' blocks; MU / VE accumulate in the first.
-struct Tail2Args {
-  double *e; int n, p1, p2; int rr; float df; int accumulate; uint32_t iter; Rng rng; ChainScalars *sc1, *sc2;
-};
-__global__ __launch_bounds__(1024) void k_tail2(const Tail2Args a) {
-  __shared__ double red[17];
-  ChainScalars &s1 = *a.sc1, &s2 = *a.sc2;
-  const float ve0 = s1.ve;
-  double s = 0;
-  for (int i = threadIdx.x; i < a.n; i += blockDim.x) s += a.e[i];
-  s = block_sum(s, red);
-  const float me = (float)(s / (double)a.n);
-  const double z = rng_normal(a.rng, RNG_GLOBAL_MARKER, a.iter, RNG_G_MU, 0);
-  const float eM = (float)((double)me + (double)sqrtf(ve0 / a.n) * z);
-  double ss = 0;
-  for (int i = threadIdx.x; i < a.n; i += blockDim.x) { const double v = a.e[i] - (double)eM; a.e[i] = v; ss = fma(v, v, ss); }
-  ss = block_sum(ss, red);
-  if (threadIdx.x == 0) {
-    const float ssf = (float)ss;
-    const float mu = s1.mu + eM;
-    const double chi_e = rng_chisq(a.rng, (double)(a.n + a.df), RNG_GLOBAL_MARKER, a.iter, RNG_G_VE);
-    const float ve = (float)((double)(ssf + s1.Se) / chi_e);
-    if (a.rr) {
-      const double c1 = rng_chisq(a.rng, (double)(a.df + a.p1), RNG_GLOBAL_MARKER, a.iter, RNG_G_VB);
-      const double c2 = rng_chisq(a.rng, (double)(a.df + a.p2), RNG_GLOBAL_MARKER - 1u, a.iter, RNG_G_VB);
-      s1.vb = (float)((double)(s1.Sb + (float)s1.sum_b2) / c1);
-      s2.vb = (float)((double)(s2.Sb + (float)s2.sum_b2) / c2);
-      s1.lam = ve / s1.vb; s2.lam = ve / s2.vb;
-    }
-    const float Cn = -0.5f / sqrtf(ve);
-    s1.ve = ve; s2.ve = ve; s1.mu = mu; s2.mu = mu; s1.C = Cn; s2.C = Cn;
-    s1.inc_rate = (float)(s1.sum_d / (double)a.p1); s2.inc_rate = (float)(s2.sum_d / (double)a.p2);
-    s1.sum_d = 0.0; s1.sum_b2 = 0.0; s2.sum_d = 0.0; s2.sum_b2 = 0.0;
-    if (a.accumulate) { s1.MU += mu; s1.VE += ve; s1.VBs += s1.vb; s2.VBs += s2.vb; }
-  }
-}
-__global__ void k_set_rr2_start(ChainScalars *sc) { sc->lam = sc->MSx; }   // BayesRR2 starts with Lmb = MSx (:1190)
-__global__ void k_hat2(const float *h1, const float *h2, float MU, float *hat, int n) {   // fit = X1*B1 + X2*B2; fit += MU
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) { const float f = h1[i] + h2[i]; hat[i] = f + MU; }
-}
-
-// ---- finalisation ----
-__global__ void k_final_markers(float *B, float *D, float *VB, float *pval, int p, float MCMC, int per) {
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < p; j += gridDim.x * blockDim.x) {
-    B[j] /= MCMC; D[j] /= MCMC;
-    if (per) VB[j] /= MCMC;
-    if (pval) pval[j] = -1.0f * logf(1.0f - D[j]);
-  }
-}
-// partial[c][i] = sum_{j in column chunk c} x_ij * coef_j   (fp64), 4 rows per thread
-template <typename XT, typename CT>
-__global__ __launch_bounds__(256) void k_gemv_part(const XT *X, int64_t ld, int R, int p, const CT *coef, int cols_per_chunk, double *part) {
-  const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i0 >= ld) return;
-  const int c = blockIdx.y;
-  const int ja = c * cols_per_chunk, jb = min(p, ja + cols_per_chunk);
-  double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-  for (int j = ja; j < jb; ++j) {
-    const double cj = (double)coef[j];
-    if (cj == 0.0) continue;
-    const XT *xp = X + xoff(i0, j, R, p);
-    float x0, x1, x2, x3;
-    if constexpr (sizeof(XT) == 1) {
-      const uint32_t w = *reinterpret_cast<const uint32_t *>(xp);
-      x0 = (float)(int8_t)(w & 0xFF); x1 = (float)(int8_t)((w >> 8) & 0xFF); x2 = (float)(int8_t)((w >> 16) & 0xFF); x3 = (float)(int8_t)(w >> 24);
-    } else {
-      const float4 v = *reinterpret_cast<const float4 *>(xp);
-      x0 = v.x; x1 = v.y; x2 = v.z; x3 = v.w;
-    }
-    a0 = fma((double)x0, cj, a0); a1 = fma((double)x1, cj, a1); a2 = fma((double)x2, cj, a2); a3 = fma((double)x3, cj, a3);
-  }
-  double *o = part + (int64_t)c * ld + i0;
-  o[0] = a0; o[1] = a1; o[2] = a2; o[3] = a3;
-}
-// int8 panels: 16 rows per thread (one 16-byte load per marker), four markers' loads in flight, no data-dependent branch --
-// the 4-rows-per-thread loop above with its skip of zero coefficients waited for every load and ran at 1.1 TB/s
-template <typename CT>
-__global__ __launch_bounds__(256) void k_gemv_part_i8(const int8_t *X, int64_t ld, int R, int p, const CT *coef, int cols_per_chunk, double *part) {
-  const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
-  if (i0 >= ld) return;
-  const int c = blockIdx.y;
-  const int ja = c * cols_per_chunk, jb = min(p, ja + cols_per_chunk);
-  const int8_t *base = X + xoff(i0, 0, R, p);          // marker j of this slab: base + j*R (R is a multiple of 128)
-  double acc[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) acc[k] = 0.0;
-#define GEMV_ADD(w_, cj_, k0_) { \
-    acc[(k0_) + 0] = fma((double)(int)(int8_t)((w_) & 0xFF), cj_, acc[(k0_) + 0]); acc[(k0_) + 1] = fma((double)(int)(int8_t)(((w_) >> 8) & 0xFF), cj_, acc[(k0_) + 1]); \
-    acc[(k0_) + 2] = fma((double)(int)(int8_t)(((w_) >> 16) & 0xFF), cj_, acc[(k0_) + 2]); acc[(k0_) + 3] = fma((double)((int)(w_) >> 24), cj_, acc[(k0_) + 3]); }
-#define GEMV_COL(v_, cj_) { GEMV_ADD((v_).x, cj_, 0) GEMV_ADD((v_).y, cj_, 4) GEMV_ADD((v_).z, cj_, 8) GEMV_ADD((v_).w, cj_, 12) }
-  int j = ja;
-  for (; j + 4 <= jb; j += 4) {
-    const uint4 v0 = *reinterpret_cast<const uint4 *>(base + (size_t)j * R), v1 = *reinterpret_cast<const uint4 *>(base + (size_t)(j + 1) * R);
-    const uint4 v2 = *reinterpret_cast<const uint4 *>(base + (size_t)(j + 2) * R), v3 = *reinterpret_cast<const uint4 *>(base + (size_t)(j + 3) * R);
-    const double c0 = (double)coef[j], c1 = (double)coef[j + 1], c2 = (double)coef[j + 2], c3 = (double)coef[j + 3];
-    GEMV_COL(v0, c0) GEMV_COL(v1, c1) GEMV_COL(v2, c2) GEMV_COL(v3, c3)
-  }
-  for (; j < jb; ++j) { const uint4 v0 = *reinterpret_cast<const uint4 *>(base + (size_t)j * R); const double c0 = (double)coef[j]; GEMV_COL(v0, c0) }
-#undef GEMV_COL
-#undef GEMV_ADD
-  double *o = part + (int64_t)c * ld + i0;
-#pragma unroll
-  for (int k = 0; k < 16; ++k) o[k] = acc[k];
-}
-__global__ void k_hat_finish(const double *part, int64_t ld, int nchunks, int n, float MU, float *hat, const double *cen_off = nullptr) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double s = cen_off ? -*cen_off : 0.0;   // (implicitly centred columns: X_c B = X B - sum_j mean_j B_j)
-  for (int c = 0; c < nchunks; ++c) s += part[(int64_t)c * ld + i];
-  const float f = (float)s;
-  hat[i] = f + MU;
-}
-
-
-// ---- wgr(): R-side (double) steps around the KMUP sweep, R/wgr.R:41-168 --------------------------------------------
-struct WgrScalars {
-  double mu, Ve, Va, Sb, Se, MSx, vy, bb, B0, VE, VA, sumD, cxx;
-  double Vp, VP, Sk;   // polygenic term (eigK)
-};
-// per-column double statistics as R computes them: xx = crossprod, var = sum((x-mean)^2)/(n-1); one wave per column
-template <typename XT>
-__global__ void k_stats64(const XT *X, int R, int n, int p, double *xx, double *vx) {
-  const int lane = threadIdx.x & 63;
-  const int64_t j = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (j >= p) return;
-  double s1 = 0, s2 = 0;
-  for (int i = lane; i < n; i += 64) { const double v = (double)xval(X, xoff(i, j, R, p)); s1 += v; s2 = fma(v, v, s2); }
-  s1 = wave_sum(s1); s2 = wave_sum(s2);
-  s1 = __shfl(s1, 0, 64); s2 = __shfl(s2, 0, 64);
-  const double mean = s1 / (double)n;
-  double sv = 0;
-  for (int i = lane; i < n; i += 64) { const double dev = (double)xval(X, xoff(i, j, R, p)) - mean; sv = fma(dev, dev, sv); }
-  sv = wave_sum(sv);
-  if (lane == 0) { xx[j] = s2; vx[j] = sv / (double)(n - 1); }
-}
-__global__ void k_dsum_stage1(const double *v, int64_t n, double *part, int square) {
-  __shared__ double red[17];
-  double s = 0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) s += square ? v[i] * v[i] : v[i];
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) part[blockIdx.x] = s;
-}
-// setup: mu = mean(y), e = y - mu, vy = var(y), MSx, priors (R/wgr.R:49-59); part = 256 partial sums of column variances,
-// part2 = 256 partial sums of xx
-__global__ void k_wgr_init(const double *y, double *eR, int n, int64_t ld, const double *part, const double *part2, int p,
-                           double df, double R2, WgrScalars *ws) {
-  __shared__ double red[17];
-  double s = 0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) s += y[i];
-  s = block_sum(s, red);
-  const double mu = s / (double)n;
-  double sv = 0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) { const double dev = y[i] - mu; sv += dev * dev; }
-  sv = block_sum(sv, red);
-  double ms = 0, sx = 0;
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) { ms += part[i]; sx += part2[i]; }
-  ms = block_sum(ms, red);
-  sx = block_sum(sx, red);
-  for (int64_t i = threadIdx.x; i < ld; i += blockDim.x) eR[i] = (i < n) ? (y[i] - mu) : 0.0;
-  if (threadIdx.x == 0) {
-    WgrScalars w; memset(&w, 0, sizeof(w));
-    w.mu = mu; w.vy = sv / (double)(n - 1); w.MSx = ms; w.Ve = 1.0; w.Va = ms;
-    w.Sb = (R2) * df * w.vy / ms; w.Se = (1 - R2) * df * w.vy; w.cxx = sx / (double)p;
-    w.Sk = R2 * w.vy * (df + 2); w.Vp = 1.0;                                       // R/wgr.R:60, :30
-    *ws = w;
-  }
-}
-__global__ void k_wgr_marker_init(double *bR, double *dR, double *VbR, double *LR, double *B, double *D, double *VB, int p, const WgrScalars *ws) {
-  const double Va = ws->Va, Ve = ws->Ve;
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < p; j += gridDim.x * blockDim.x) {
-    bR[j] = 0; dR[j] = 1; VbR[j] = Va; LR[j] = Va / Ve; B[j] = 0; D[j] = 0; VB[j] = 0;   // L = Vb/Ve (sic), R/wgr.R:55
-  }
-}
-// narrowing at the .Call boundary (src/RcppExports.cpp:20-27): double R vectors -> float KMUP arguments
-__global__ void k_wgr_pre(const double *bR, const double *dR, const double *LR, const double *xx64, const double *eR, float *bf, float *df_,
-                          float *Lf, float *xxf, double *e64, int p, int n, int64_t ld, float pi, const WgrScalars *ws, ChainScalars *sc) {
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, gsz = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t j = gid; j < p; j += gsz) { bf[j] = (float)bR[j]; df_[j] = (float)dR[j]; Lf[j] = (float)LR[j]; xxf[j] = (float)xx64[j]; }
-  for (int64_t i = gid; i < ld; i += gsz) e64[i] = (i < n) ? (double)(float)eR[i] : 0.0;
-  if (gid == 0) {
-    ChainScalars c; memset(&c, 0, sizeof(c));
-    const float Ve = (float)ws->Ve;
-    c.ve = Ve; c.pi = pi; c.C = -0.5f / sqrtf(Ve); c.odds = pi / (1.0f - pi); c.dfp1 = 1.0f;
-    c.inc_rate = 1.0f - pi;
-    c.nredo = sc->nredo;   // (the call's count so far: zeroed before the first iteration)
-    *sc = c;
-  }
-}
-// widening of KMUP's outputs + marker-variance step (R/wgr.R:86-111)
-__global__ void k_wgr_post(const float *bf, const float *df_, double *bR, double *dR, double *VbR, int p, int use_d, int iv, int de,
-                           double dfv, uint32_t iter, Rng rng, const WgrScalars *ws) {
-  const double Sb = ws->Sb, Ve = ws->Ve, MSx = ws->MSx;
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < p; j += gridDim.x * blockDim.x) {
-    const double b = (double)bf[j];
-    bR[j] = b;
-    if (use_d) dR[j] = (double)df_[j];
-    if (iv) VbR[j] = de ? sqrt(b * b * Ve / MSx) : (Sb + b * b) / rng_chisq(rng, dfv + 1.0, (uint32_t)j, iter, RNG_CHI);
-  }
-}
-// Va (common variance) and Ve draws (R/wgr.R:113,121); e64 holds KMUP's residual (float values)
-__global__ __launch_bounds__(1024) void k_wgr_scal(const double *e64, int n, double n_dof, int p, const double *bbpart, int iv, double dfv, uint32_t iter, Rng rng, WgrScalars *ws) {
-  __shared__ double red[17];
-  double ee = 0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) { const double v = (double)(float)e64[i]; ee += v * v; }
-  ee = block_sum(ee, red);
-  double bb = 0;
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) bb += bbpart[i];
-  bb = block_sum(bb, red);
-  if (threadIdx.x == 0) {
-    if (!iv) ws->Va = (bb + ws->Sb) / rng_chisq(rng, dfv + (double)p, RNG_GLOBAL_MARKER, iter, RNG_G_VB);
-    ws->Ve = (ee + ws->Se) / rng_chisq(rng, n_dof + dfv, RNG_GLOBAL_MARKER, iter, RNG_G_VE);   // n*bag + df, R/wgr.R:121
-    ws->bb = bb;
-  }
-}
-// L = Ve/Vb (R/wgr.R:122) and posterior sums of the marker vectors (R/wgr.R:130-134)
-__global__ void k_wgr_L(const double *bR, const double *dR, double *VbR, double *LR, double *B, double *D, double *VB, int p, int iv, int accumulate, const WgrScalars *ws) {
-  const double Ve = ws->Ve, Va = ws->Va;
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < p; j += gridDim.x * blockDim.x) {
-    if (!iv) VbR[j] = Va;
-    LR[j] = Ve / VbR[j];
-    if (accumulate) { B[j] += bR[j]; D[j] += dR[j]; if (iv) VB[j] += VbR[j]; }
-  }
-}
-// e = y - mu - X b from the fp64 partial products (R/wgr.R:124)
-__global__ void k_wgr_efinish(const double *part, int64_t ld, int nchunks, int n, const double *y, double *eR, const WgrScalars *ws) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double s = 0;
-  for (int c = 0; c < nchunks; ++c) s += part[(int64_t)c * ld + i];
-  eR[i] = y[i] - ws->mu - s;
-}
-// intercept (R/wgr.R:125-127) and scalar posterior sums
-__global__ __launch_bounds__(1024) void k_wgr_mu(double *eR, int n, int iv, int accumulate, uint32_t iter, Rng rng, WgrScalars *ws) {
-  __shared__ double red[17];
-  double s = 0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) s += eR[i];
-  s = block_sum(s, red);
-  const double mu0 = s / (double)n + (ws->Ve / (double)n) * rng_normal(rng, RNG_GLOBAL_MARKER, iter, RNG_G_MU, 0);   // sd = Ve/n (sic)
-  for (int i = threadIdx.x; i < n; i += blockDim.x) eR[i] -= mu0;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    ws->mu += mu0;
-    if (accumulate) { ws->B0 += ws->mu; ws->VE += ws->Ve; if (!iv) ws->VA += ws->Va; }
-  }
-}
-// ---- polygenic term: narrowing for KMUP(U,h,dh,xxK,e,Lk,Ve,0) (R/wgr.R:70-76), widening of its outputs ----
-__global__ void k_wgr_pre_k(const double *hR, const double *Vd, const double *eR, float *hf, float *dhf, float *xxKf, float *Lkf, double *e64,
-                            int pk, int n, int64_t ld, const WgrScalars *ws, ChainScalars *sc) {
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, gsz = (int64_t)gridDim.x * blockDim.x;
-  const double Ve = ws->Ve, Vp = ws->Vp;
-  for (int64_t k = gid; k < pk; k += gsz) { hf[k] = (float)hR[k]; dhf[k] = 0.0f; xxKf[k] = 1.0f; Lkf[k] = (float)(Ve / (Vd[k] * Vp)); }
-  for (int64_t i = gid; i < ld; i += gsz) e64[i] = (i < n) ? (double)(float)eR[i] : 0.0;
-  if (gid == 0) {
-    ChainScalars c; memset(&c, 0, sizeof(c));
-    const float Vef = (float)Ve;
-    c.ve = Vef; c.pi = 0.0f; c.C = -0.5f / sqrtf(Vef); c.odds = 0.0f; c.dfp1 = 1.0f;
-    *sc = c;
-  }
-}
-__global__ void k_wgr_post_k(const float *hf, double *hR, const double *e64, double *eR, int pk, int n) {
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, gsz = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t k = gid; k < pk; k += gsz) hR[k] = (double)hf[k];
-  for (int64_t i = gid; i < n; i += gsz) eR[i] = (double)(float)e64[i];   // KMUP returns e as float (src/Rcpp20260726ai.cpp:37)
-}
-// Vp = (sum(h^2/V) + Sk)/rchisq(1, df+pk)  (R/wgr.R:117)
-__global__ __launch_bounds__(1024) void k_wgr_vp(const double *hR, const double *Vd, int pk, double dfv, uint32_t iter, Rng rng, WgrScalars *ws) {
-  __shared__ double red[17];
-  double s = 0;
-  for (int k = threadIdx.x; k < pk; k += blockDim.x) s += hR[k] * hR[k] / Vd[k];
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) ws->Vp = (s + ws->Sk) / rng_chisq(rng, dfv + (double)pk, RNG_GLOBAL_MARKER, iter, RNG_G_VK);
-}
-// out[i] (+)= sum_k U[i,k] * coef[k] * scale   (U %*% h in double, R/wgr.R:124,148)
-__global__ void k_uh(const double *Ud, const double *coef, int n, int pk, double scale, double *out, int accumulate_into_neg) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double s = 0;
-  for (int k = 0; k < pk; ++k) s = fma(Ud[(size_t)k * n + i], coef[k] * scale, s);
-  if (accumulate_into_neg) out[i] -= s; else out[i] = s;
-}
-__global__ void k_wgr_accum_k(const double *hR, double *H, int pk, WgrScalars *ws) {
-  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < pk; k += gridDim.x * blockDim.x) H[k] += hR[k];
-  if (blockIdx.x == 0 && threadIdx.x == 0) ws->VP += ws->Vp;
-}
-__global__ void k_add_vec(double *a, const double *b, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) a[i] += b[i];
-}
-// ---- bagging (bag != 1): KMUP2 works on a row subsample (src/Rcpp20260726ai.cpp:49-57) ----
-// rows Use[0..nb) of the base panel -> a panel of nb rows (both slab-major, each with its own slab height)
-template <typename XT>
-__global__ void k_gather_rows(const XT *Xb, int Rb, const int *use, int nb, XT *Xo, int Ro, int64_t ldo, int64_t p) {
-  const int64_t total = p * ldo;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t j = idx / ldo, i = idx - j * ldo;
-    XT v = (XT)0;
-    if (i < nb) v = Xb[xoff(use[i], j, Rb, p)];
-    Xo[xoff(i, j, Ro, p)] = v;
-  }
-}
-// int8 panels: a workgroup stages whole columns in LDS with 16-byte loads, picks the subsample's bytes there and writes the
-// bagged panel with 16-byte stores (the element-wise kernel above moved one byte per load and ran at 0.6 TB/s)
-__global__ __launch_bounds__(256) void k_gather_rows_i8(const int8_t *Xb, int Rb, int64_t ldb, const int *use, int nb, int8_t *Xo, int Ro,
-                                                         int64_t ldo, int64_t p, int mpw) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char col[];   // mpw columns of ldb bytes
-  const int64_t j0 = (int64_t)blockIdx.x * mpw;
-  const int nm = (int)min((int64_t)mpw, p - j0);
-  const int cin = (int)(ldb / 16), cout = (int)(ldo / 16);
-  for (int c = threadIdx.x; c < nm * cin; c += 256) {
-    const int jj = c / cin, ci = c - jj * cin;
-    const int64_t i = 16 * (int64_t)ci;
-    reinterpret_cast<uint4 *>(col + (size_t)jj * ldb)[ci] = *reinterpret_cast<const uint4 *>(Xb + xoff(i, j0 + jj, Rb, p));
-  }
-  __syncthreads();
-  for (int co = threadIdx.x; co < cout; co += 256) {   // the 16 row indices of an output chunk serve every column of the group
-    int ui[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { const int i = 16 * co + k; ui[k] = (i < nb) ? use[i] : -1; }
-    for (int jj = 0; jj < nm; ++jj) {
-      const unsigned char *cj = col + (size_t)jj * ldb;
-      uint32_t w[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        uint32_t v = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const int u = ui[4 * q + k]; v |= ((u >= 0) ? (uint32_t)cj[u] : 0u) << (8 * k); }
-        w[q] = v;
-      }
-      *reinterpret_cast<uint4 *>(Xo + xoff(16 * (int64_t)co, j0 + jj, Ro, p)) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-  }
-}
-__global__ void k_gather_e(const double *eR, const int *use, int nb, int64_t ldo, double *e64) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < ldo; i += (int64_t)gridDim.x * blockDim.x)
-    e64[i] = (i < nb) ? (double)(float)eR[use[i]] : 0.0;
-}
-__global__ void k_scale_d(double *v, int64_t n, double s) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v[i] *= s;
-}
-__global__ void k_set_bg(ChainScalars *sc, float bg) { sc->bg = bg; }
-// posterior means (R/wgr.R:141-145)
-__global__ void k_wgr_final(double *B, double *D, double *VB, int p, double mc, const double *dpart, int iv, WgrScalars *ws) {
-  __shared__ double red[17];
-  double sd = 0;
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) sd += dpart[i];
-  sd = block_sum(sd, red);
-  const double meanD = sd / mc / (double)p;
-  for (int j = threadIdx.x; j < p; j += blockDim.x) { D[j] = D[j] / mc; B[j] = B[j] / mc / meanD; if (iv) VB[j] = VB[j] / mc; }
-  if (threadIdx.x == 0) ws->sumD = sd;
-}
-__global__ void k_hat64_finish(const double *part, int64_t ld, int nchunks, int n, double B0, double *hat) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double s = 0;
-  for (int c = 0; c < nchunks; ++c) s += part[(int64_t)c * ld + i];
-  hat[i] = B0 + s;
-}
-
-// ---- synthetic genotypes: 4 rows per thread ----
-__global__ void k_synth(int8_t *X, int64_t ld, int n, int64_t p, int64_t col0, uint32_t k0, uint32_t k1, float *freq) {
-  const int64_t quads = ld / 4;
-  const int64_t total = p * quads;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t j = idx / quads, q = idx - j * quads;
-    const uint32_t jg = (uint32_t)(col0 + j);
-    const uint4 fj = philox4x32_10(jg, 0u, 33u, 0u, k0, k1);
-    const float f = 0.05f + 0.45f * ((float)(fj.x >> 8) * (1.0f / 16777216.0f));
-    const uint32_t thr = (uint32_t)(f * 16777216.0f);
-    if (q == 0 && freq) freq[j] = f;
-    const uint4 a = philox4x32_10((uint32_t)q, jg, 32u, 0u, k0, k1);
-    const uint4 c = philox4x32_10((uint32_t)q, jg, 32u, 1u, k0, k1);
-    const uint32_t w[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-    uint32_t packed = 0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      uint32_t g = ((w[2 * r] >> 8) < thr) + ((w[2 * r + 1] >> 8) < thr);
-      if (q * 4 + r >= n) g = 0;
-      packed |= g << (8 * r);
-    }
-    *reinterpret_cast<uint32_t *>(X + j * ld + q * 4) = packed;
-  }
-}
-
-__global__ void k_debug_variates(Rng g, int kind, double nu, uint32_t marker0, uint32_t iter, uint32_t purpose, int count, double *out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  const uint32_t mk = marker0 + (uint32_t)i;
-  double v;
-  if (kind == 0) v = rng_normal(g, mk, iter, purpose, 0);
-  else if (kind == 1) v = rng_uniform(g, mk, iter, purpose, 0);
-  else v = rng_chisq(g, nu, mk, iter, purpose);
-  out[i] = v;
-}
-
-}  // namespace
 
 // ------------------------------------------------------------------------------------------------
 // host objects
-// ---- a fixed-point sweep (k_sweep3 / k_sweep2w's fixed-point streamers) that leaves its range is redone on the fp64 residual:
-// the state it starts from is kept (12 bytes per marker and the residual: 12 MB against a 10 GB read at C4), and when the range flag
-// comes back the state is restored, the flag cleared and sc->redo set, which lets the fp64 launches queued behind (redo_only) run ----
-namespace {
-struct SnapArgs { double *e, *se; float *b, *d, *vb, *sb, *sd, *svb; int64_t ld; int j0, j1; ChainScalars *sc; };
-__global__ void k_range_snapshot(const SnapArgs s) {
-  const int64_t nt = (int64_t)gridDim.x * blockDim.x, t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (int64_t i = t0; i < s.ld; i += nt) s.se[i] = s.e[i];
-  for (int64_t j = s.j0 + t0; j < s.j1; j += nt) { s.sb[j] = s.b[j]; s.sd[j] = s.d[j]; if (s.vb) s.svb[j] = s.vb[j]; }
-  if (t0 == 0) { s.sc->snap_sum_d = s.sc->sum_d; s.sc->snap_sum_b2 = s.sc->sum_b2; }
-}
-__global__ void k_range_recover(const SnapArgs s) {
-  if (s.sc->error != 2u) return;
-  const int64_t nt = (int64_t)gridDim.x * blockDim.x, t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (int64_t i = t0; i < s.ld; i += nt) s.e[i] = s.se[i];
-  for (int64_t j = s.j0 + t0; j < s.j1; j += nt) { s.b[j] = s.sb[j]; s.d[j] = s.sd[j]; if (s.vb) s.vb[j] = s.svb[j]; }
-}
-__global__ void k_range_flag(ChainScalars *sc) {   // (after k_range_recover: every thread of it has read the status)
-  if (sc->error == 2u) { sc->error = 0u; sc->redo = 1u; sc->nredo += 1u; sc->sum_d = sc->snap_sum_d; sc->sum_b2 = sc->snap_sum_b2; }
-}
-__global__ void k_redo_clear(ChainScalars *sc) { sc->redo = 0u; }
-}  // namespace
+// ------------------------------------------------------------------------------------------------
 
 // ------------------------------------------------------------------------------------------------
 // The environment switches, every one the library reads, read once: when a root panel is made.  Clones share the
@@ -1151,7 +286,7 @@ struct HipBackend {
 };
 // The device arrays, streams and events of one call (or of one block of it), or of one handle.  get() returns nullptr where the allocation
 // fails, and the holder remembers it: the caller reports BWGR_ENOMEM, "<entry>: device allocation failed" (own_array below does; an entry
-// of fits_host.hip.h asks failed() once after the last get of a group).
+// of the *_host.hip.h files asks failed() once after the last get of a group).
 using DevBufs = DevHolder<HipBackend>;
 // Runs f when the scope ends, unless release()d: destroys the object a function is making on its error returns, a call's scratch panels and
 // chains on every return, and gives a borrowed stream back.  Declared before the call's DevBufs, so that it runs after the buffers are freed.
@@ -1204,7 +339,7 @@ struct PanelData {
   void *g3x[S3_MAXD] = {};
   unsigned char *gx12 = nullptr;   // 16-bit panels: an included marker's distance-1 and distance-2 rows side by side (k_near_rows)
   unsigned char *gxt[S2W_MAXDIST] = {};   // the affine models' cross Gram blocks as the sequencer's MFMA operand (k_gx_planes, sweep2w.hip.h)
-  float *xx = nullptr, *vx = nullptr, *msx_dev = nullptr;
+  float *xx = nullptr, *vx = nullptr;
   int *xmax_dev = nullptr;
   // implicitly centred columns (bwgr_panel_set_centred; int8 panels with k_sweep3): the column sums, the centred |x_j - mean_j|^2 as floats (what
   // a chain's xx is then)
@@ -1275,20 +410,28 @@ static hipError_t d2h(hipStream_t st, void *dst, const void *src, size_t bytes) 
   hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
   return e != hipSuccess ? e : hipStreamSynchronize(st);
 }
-// host -> device copy of count elements, and count elements set to zero bytes, both enqueued on st
+// host -> device and device -> device copies of count elements, and count elements set to zero bytes, all enqueued on st
 template <typename T> static hipError_t h2d(hipStream_t st, T *dst, const T *src, size_t count) { return hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyHostToDevice, st); }
+template <typename T> static hipError_t d2d(hipStream_t st, T *dst, const T *src, size_t count) { return hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyDeviceToDevice, st); }
 template <typename T> static hipError_t zero(hipStream_t st, T *dst, size_t count) { return hipMemsetAsync(dst, 0, sizeof(T) * count, st); }
 
 static Rng make_rng(uint64_t seed, int mode) {
   Rng g; g.k0 = (uint32_t)seed; g.k1 = (uint32_t)(seed >> 32); g.degenerate = (mode == BWGR_RNG_DEGENERATE); return g;
 }
 
-// sum of n floats (fp64 partial sums in a fixed order, rounded to float once) into *sum_dev and from there into *sum; part: 256 doubles
-static int sum_floats(hipStream_t st, const float *v, int64_t n, double *part, float *sum_dev, float *sum) {
-  hipLaunchKernelGGL(k_sum_stage1, dim3(256), dim3(256), 0, st, v, n, part);
-  hipLaunchKernelGGL(k_sum_stage2, dim3(1), dim3(256), 0, st, part, 256, sum_dev);
-  HIPCHK(hipGetLastError());
-  HIPCHK(d2h(st, sum, sum_dev, sizeof(float)));
+// *sum = the sum of the n floats of v (fp64 partial sums in a fixed order, rounded to float once), for every vector of the list in turn.  The
+// scratch -- 256 partial sums and the float on the device -- is this call's own, one for all the vectors.
+struct FloatVec { const float *v; int64_t n; float *sum; };
+static int sum_floats(hipStream_t st, std::initializer_list<FloatVec> vecs, const char *who) {
+  DevBufs bufs;
+  double *part = bufs.get<double>(256); float *sum_dev = bufs.get<float>(1);
+  if (bufs.failed()) return no_memory(who);
+  for (const FloatVec &f : vecs) {
+    hipLaunchKernelGGL(k_sum_stage1, dim3(256), dim3(256), 0, st, f.v, f.n, part);
+    hipLaunchKernelGGL(k_sum_stage2, dim3(1), dim3(256), 0, st, part, 256, sum_dev);
+    HIPCHK(hipGetLastError());
+    HIPCHK(d2h(st, f.sum, sum_dev, sizeof(float)));
+  }
   return BWGR_OK;
 }
 
@@ -1829,6 +972,17 @@ static void fill_panel_args(const bwgr_panel *P, SweepArgs &a) {
   a.xpart = P->xpart; a.xflags = P->xflags; a.stamps = P->stamps; a.ps = P->ps;
   a.gramx = P->data->gx[1]; a.gramx2 = P->data->gx[2]; a.xspec2 = P->xspec2; a.gramx3 = P->data->gx[3]; a.xspec3 = P->xspec3; a.lag = 2; a.nfeed = P->data->plan.nfeed; a.gramp = P->data->gramp; a.pstride = P->data->plan.pstride; a.qpart = P->qpart; a.dgran = P->dgran;
 }
+// The arguments of one sweep over the whole of panel P: every byte zero, then the panel's part, the flags, the state the sweep reads and
+// writes, the iteration and the generator.  A caller adds only what is its own (a chain its block range, marker0 and the centred fields).
+static SweepArgs sweep_args(const bwgr_panel *P, int flags, double *e, float *b, float *d, float *vb, const float *xx, const float *lam,
+                            ChainScalars *sc, uint32_t iter, const Rng &rng) {
+  SweepArgs a; memset(&a, 0, sizeof(a));
+  fill_panel_args(P, a);
+  a.flags = flags;
+  a.e = e; a.b = b; a.d = d; a.vb = vb; a.xx = xx; a.lam = lam; a.sc = sc;
+  a.iter = iter; a.rng = rng;
+  return a;
+}
 
 // ------------------------------------------------------------------------------------------------
 // panel
@@ -1904,12 +1058,7 @@ static int panel_measure(bwgr_panel *P) {
   if (D->is_f32) hipLaunchKernelGGL(k_stats<float>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const float *)D->X, D->plan.R, n, p, D->xx, D->vx);
   else hipLaunchKernelGGL(k_stats<int8_t>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const int8_t *)D->X, D->plan.R, n, p, D->xx, D->vx);
   HIPCHK(hipGetLastError());
-  {
-    DevBufs bufs;
-    double *part = bufs.get<double>(256);
-    if (!part) return fail(BWGR_ENOMEM, "panel_create: device allocation failed");
-    CHK(sum_floats(P->stream, D->vx, (int64_t)p, part, D->msx_dev, &D->MSx));
-  }
+  CHK(sum_floats(P->stream, {{D->vx, (int64_t)p, &D->MSx}}, "panel_create"));
   if (!D->is_f32) {
     if (!D->xmax_dev) CHK(own_array(D->own, D->xmax_dev, 1, "panel_create"));
     HIPCHK(hipMemsetAsync(D->xmax_dev, 0, sizeof(int), P->stream));
@@ -2023,7 +1172,7 @@ static int panel_alloc(bwgr_panel **out, int is_f32, int64_t n, int64_t p, int d
   Guard drop([&] { bwgr_panel_destroy(P); });   // until the panel is handed over
   D->device = device; D->n = n; D->p = p; D->is_f32 = is_f32; D->sw = sw; D->plan = pl;
   const size_t packed = (size_t)pl.nblocks * std::max(pl.pstride, 8);
-  if (!D->own.take({{&D->X, pl.x_bytes}, {&D->gram, pl.gram_bytes}, {&D->gramp, packed * (is_f32 ? 8 : 4)}, {&D->xx, sizeof(float) * p}, {&D->vx, sizeof(float) * p}, {&D->msx_dev, sizeof(float)}}))
+  if (!D->own.take({{&D->X, pl.x_bytes}, {&D->gram, pl.gram_bytes}, {&D->gramp, packed * (is_f32 ? 8 : 4)}, {&D->xx, sizeof(float) * p}, {&D->vx, sizeof(float) * p}}))
     return no_memory("panel_create");
   for (int d = 1; d <= pl.xdist; ++d) CHK(own_array(D->own, D->gx[d], pl.gram_bytes, "panel_create"));
   if (pl.has16 && !D->own.take({{&D->gramp16, packed * 2}, {&D->gramx16, (size_t)pl.nblocks * pl.m * pl.m * 2}, {&D->gram16_bad, sizeof(int)}})) return no_memory("panel_create");
@@ -2181,7 +1330,7 @@ extern "C" int bwgr_panel_stats(bwgr_panel *P, float *xx, float *vx, float *MSx)
 }
 
 // ------------------------------------------------------------------------------------------------
-// KMUP
+// what the families' entries share beside the sweep: the row gather, the redo count of the entries without a chain, X * coef, centring
 // ------------------------------------------------------------------------------------------------
 // The row gather's path, decided here and nowhere else (bwgr_debug_aux_plan exposes it to the CPU tests): 0 = element-wise (float panels, int8
 // columns longer than 64 KB), else the columns an int8 workgroup stages in LDS -- ~30 KB of LDS per workgroup: five of them per CU
@@ -2206,446 +1355,6 @@ static thread_local int g_last_redo = 0;
 extern "C" int bwgr_debug_last_redo(int *count) {
   if (!count) return fail(BWGR_EINVAL, "null pointer");
   *count = g_last_redo;
-  return BWGR_OK;
-}
-
-// one sweep over panel PS with host-side b, d, xx, L and a device residual e64 (ld doubles, padding zero); KMUP and KMUP2
-static int kmup_sweep(bwgr_panel *PS, float *b, float *d, const float *xx, const float *L, double *e64, float Ve, float pi, float bg,
-                      int kmup2, uint64_t seed, uint32_t iter, int rng_mode, const char *who) {
-  DevBufs bufs;
-  const size_t p = (size_t)PS->data->p, pb = sizeof(float) * p;
-  float *db = bufs.get<float>(p), *dd = bufs.get<float>(p), *dxx = bufs.get<float>(p), *dL = bufs.get<float>(p), *dvb = bufs.get<float>(p);
-  ChainScalars *sc = bufs.get<ChainScalars>(1);
-  if (!db || !dd || !dxx || !dL || !dvb || !sc) return fail(BWGR_ENOMEM, "%s: device allocation failed", who);
-  HIPCHK(hipMemcpyAsync(db, b, pb, hipMemcpyHostToDevice, PS->stream));
-  HIPCHK(hipMemcpyAsync(dd, d, pb, hipMemcpyHostToDevice, PS->stream));
-  HIPCHK(hipMemcpyAsync(dxx, xx, pb, hipMemcpyHostToDevice, PS->stream));
-  HIPCHK(hipMemcpyAsync(dL, L, pb, hipMemcpyHostToDevice, PS->stream));
-  ChainScalars h; memset(&h, 0, sizeof(h));
-  h.ve = Ve; h.pi = pi; h.C = -0.5f / sqrtf(Ve); h.odds = pi / (1.0f - pi); h.dfp1 = 1.0f; h.bg = bg;
-  h.inc_rate = 1.0f - pi;
-  HIPCHK(hipMemcpyAsync(sc, &h, sizeof(h), hipMemcpyHostToDevice, PS->stream));
-  SweepArgs a; memset(&a, 0, sizeof(a));
-  fill_panel_args(PS, a);
-  a.flags = SWF_LAM_VEC | (pi > 0 ? (SWF_SELECT | SWF_ALT_B2) : 0) | (kmup2 ? SWF_KMUP2 : 0);
-  a.e = e64; a.b = db; a.d = dd; a.vb = dvb; a.xx = dxx; a.lam = dL; a.sc = sc;
-  a.iter = iter; a.rng = make_rng(seed, rng_mode);
-  CHK(launch_sweep(PS, a));
-  HIPCHK(hipMemcpyAsync(b, db, pb, hipMemcpyDeviceToHost, PS->stream));
-  HIPCHK(hipMemcpyAsync(d, dd, pb, hipMemcpyDeviceToHost, PS->stream));
-  HIPCHK(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, PS->stream));
-  HIPCHK(hipStreamSynchronize(PS->stream));
-  g_last_redo = (int)h.nredo;
-  if (h.error) return sweep_error(h.error, who);
-  return BWGR_OK;
-}
-
-extern "C" int bwgr_kmup(bwgr_panel *P, float *b, float *d, const float *xx, float *e, const float *L, float Ve,
-                         float pi, uint64_t seed, uint32_t iter, int rng_mode) {
-  if (P && P->data->cen) return refuse_centred("kmup");
-  if (!P || !b || !d || !xx || !e || !L) return fail(BWGR_EINVAL, "kmup: null pointer");
-  HIPCHK(hipSetDevice(P->data->device));
-  DevBufs bufs;
-  float *de = bufs.get<float>((size_t)P->data->n);
-  double *de64 = bufs.get<double>((size_t)P->data->plan.ld);
-  if (!de || !de64) return fail(BWGR_ENOMEM, "kmup: device allocation failed");
-  HIPCHK(hipMemcpyAsync(de, e, sizeof(float) * P->data->n, hipMemcpyHostToDevice, P->stream));
-  hipLaunchKernelGGL(k_f2d, dim3(64), dim3(256), 0, P->stream, de, de64, P->data->n, P->data->plan.ld);
-  CHK(kmup_sweep(P, b, d, xx, L, de64, Ve, pi, 0.0f, 0, seed, iter, rng_mode, "kmup"));
-  hipLaunchKernelGGL(k_d2f, dim3(64), dim3(256), 0, P->stream, de64, de, P->data->n);
-  HIPCHK(hipGetLastError());
-  HIPCHK(d2h(P->stream, e, de, sizeof(float) * P->data->n));
-  return BWGR_OK;
-}
-
-// KMUP2(X,Use,b,d,xx,E,L,Ve,pi), src/Rcpp20260726ai.cpp:41-77: the sweep on the row subsample Use (0-based, nuse entries, in
-// the caller's order, repeats allowed) of the resident panel.  The rows are gathered into a subsample panel on the device, its
-// Gram blocks built, and the sweep runs with KMUP2's conditional mean (numerator + b0, denominator xx*bg + L, bg = n0/nuse).
-// e_out receives the nuse residuals of the subsample (:76); E (n0 entries) is not modified.
-extern "C" int bwgr_kmup2(bwgr_panel *P, const int *Use, int64_t nuse, float *b, float *d, const float *xx, const float *E,
-                          float *e_out, const float *L, float Ve, float pi, uint64_t seed, uint32_t iter, int rng_mode) {
-  if (P && P->data->cen) return refuse_centred("kmup2");
-  if (!P || !Use || !b || !d || !xx || !E || !e_out || !L) return fail(BWGR_EINVAL, "kmup2: null pointer");
-  if (nuse < 2 || nuse > 0x7FFFFF00ll) return fail(BWGR_EINVAL, "kmup2: need 2 <= length(Use) < 2^31 (got %lld)", (long long)nuse);
-  for (int64_t k = 0; k < nuse; ++k)
-    if (Use[k] < 0 || Use[k] >= P->data->n) return fail(BWGR_EINVAL, "kmup2: Use[%lld] = %d is outside 0..%lld", (long long)k, Use[k], (long long)P->data->n - 1);
-  HIPCHK(hipSetDevice(P->data->device));
-  bwgr_panel *PB = nullptr;
-  CHK(scratch_panel_alloc(&PB, P, nuse, 0, PANEL_ROWS));
-  Guard drop([&] { bwgr_panel_destroy(PB); });
-  CHK(scratch_alloc(PB));
-  DevBufs bufs;
-  int *use_d = bufs.get<int>((size_t)nuse);
-  float *dE = bufs.get<float>((size_t)P->data->n), *deo = bufs.get<float>((size_t)nuse);
-  double *dE64 = bufs.get<double>((size_t)P->data->n), *e64 = bufs.get<double>((size_t)PB->data->plan.ld);
-  if (!use_d || !dE || !deo || !dE64 || !e64) return fail(BWGR_ENOMEM, "kmup2: device allocation failed");
-  HIPCHK(hipMemcpyAsync(use_d, Use, sizeof(int) * (size_t)nuse, hipMemcpyHostToDevice, P->stream));
-  HIPCHK(hipMemcpyAsync(dE, E, sizeof(float) * P->data->n, hipMemcpyHostToDevice, P->stream));
-  launch_gather_rows(P, PB, use_d, nuse);
-  HIPCHK(hipGetLastError());
-  CHK(panel_build_gram(PB));
-  hipLaunchKernelGGL(k_f2d, dim3(64), dim3(256), 0, P->stream, dE, dE64, P->data->n, P->data->n);
-  hipLaunchKernelGGL(k_gather_e, dim3(64), dim3(256), 0, P->stream, dE64, use_d, (int)nuse, PB->data->plan.ld, e64);   // e0[k] = E[Use[k]], :49-53
-  HIPCHK(hipGetLastError());
-  CHK(kmup_sweep(PB, b, d, xx, L, e64, Ve, pi, (float)P->data->n / (float)nuse, 1, seed, iter, rng_mode, "kmup2"));
-  hipLaunchKernelGGL(k_d2f, dim3(64), dim3(256), 0, P->stream, e64, deo, nuse);
-  HIPCHK(hipGetLastError());
-  HIPCHK(d2h(P->stream, e_out, deo, sizeof(float) * (size_t)nuse));
-  return BWGR_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// fused chains
-// ------------------------------------------------------------------------------------------------
-static bool per_marker_vb(int model) { return model == BWGR_BAYESA || model == BWGR_BAYESB || model == BWGR_BAYESL || model == BWGR_BAYESDPI; }
-static bool has_d(int model) { return model == BWGR_BAYESB || model == BWGR_BAYESC || model == BWGR_BAYESCPI || model == BWGR_BAYESDPI; }
-
-extern "C" int bwgr_chain_destroy(bwgr_chain *C) {
-  if (!C) return BWGR_OK;
-  if (C->P && C->P->ps_owner == C) C->P->ps_owner = nullptr;   // (a later chain may be allocated at this address)
-  if (C->P && C->P->draws_sc == (const void *)C->sc) {          // ... and so may its scalars: variates drawn ahead for this chain are nobody's now
-    if (C->P->draws_stream) (void)hipStreamSynchronize(C->P->draws_stream);   // (k_draws reads the chain's df from them)
-    C->P->draws_valid = false; C->P->draws_sc = nullptr;
-  }
-  if (C->P) { C->P->nchains--; C->P->data->nchains_all--; (void)hipSetDevice(C->P->data->device); }
-  for (hipEvent_t ev : C->ev) hipEventDestroy(ev);
-  delete C;
-  return BWGR_OK;
-}
-
-extern "C" int bwgr_chain_create_sharded(bwgr_chain **out, bwgr_panel *P, int model, const float *y, int memloc, float it,
-                                         float bi, float pi, float df, float R2, uint64_t seed, int rng_mode, int64_t marker0,
-                                         int64_t p_total, float MSx_total, double *e_ext) {
-  if (!out || !P || !y) return fail(BWGR_EINVAL, "chain_create: null pointer");
-  *out = nullptr;
-  if (model < BWGR_BAYESA || model > BWGR_BAYESDPI) return fail(BWGR_EINVAL, "chain_create: bad model %d", model);
-  if (marker0 < 0 || p_total < marker0 + P->data->p || p_total > 0xFFFFFFF0ll) return fail(BWGR_EINVAL, "chain_create: bad shard [%lld,+%lld) of %lld", (long long)marker0, (long long)P->data->p, (long long)p_total);
-  HIPCHK(hipSetDevice(P->data->device));
-  if (P->data->cen) {
-    if (!has_d(model) || !P->data->e3_ready)
-      return fail(BWGR_EINVAL, "chain_create: an implicitly centred panel (bwgr_panel_set_centred) runs the selection models BayesB / C / Cpi / Dpi only");
-    if (!P->cpre) CHK(own_array(P->own, P->cpre, (size_t)P->data->plan.nblocks + 1, "chain_create"));
-  }
-  bwgr_chain *C = new bwgr_chain();
-  C->P = P; P->nchains++; P->data->nchains_all++; C->model = model; C->itf = it; C->bif = bi; C->iit = (int)it; C->ibi = (int)bi;
-  C->pi = pi; C->df = df; C->R2 = R2; C->seed = seed; C->rng_mode = rng_mode;
-  C->marker0 = marker0; C->p_total = p_total; C->MSx_eff = MSx_total;
-  C->Phi = MSx_total * (1 - R2) / R2;
-  Guard drop([&] { bwgr_chain_destroy(C); });
-  const size_t pb = sizeof(float) * P->data->p;
-  if (!C->own.take({{&C->y, sizeof(float) * P->data->n}, {&C->b, pb}, {&C->d, pb}, {&C->vb, pb}, {&C->lam, pb}, {&C->B, pb}, {&C->D, pb}, {&C->VB, pb}, {&C->sc, sizeof(ChainScalars)}}))
-    return no_memory("chain_create");
-  if (e_ext) C->e = e_ext;   // (borrowed)
-  else CHK(own_array(C->own, C->e, (size_t)P->data->plan.ld, "chain_create"));
-  HIPCHK(hipMemcpyAsync(C->y, y, sizeof(float) * P->data->n, memloc == BWGR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, P->stream));
-  InitArgs ia; ia.y = C->y; ia.e = C->e; ia.n = (int)P->data->n; ia.p = (int)P->data->p; ia.ld = P->data->plan.ld; ia.model = model;
-  ia.pi = pi; ia.df = df; ia.R2 = R2; ia.MSx = MSx_total; ia.sc = C->sc;
-  hipLaunchKernelGGL(k_chain_init, dim3(1), dim3(1024), 0, P->stream, ia);
-  hipLaunchKernelGGL(k_marker_init, dim3(1024), dim3(256), 0, P->stream, C->b, C->d, C->vb, C->lam, C->B, C->D, C->VB, (int)P->data->p, C->sc);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(P->stream));
-  drop.release();
-  *out = C;
-  return BWGR_OK;
-}
-
-extern "C" int bwgr_chain_create(bwgr_chain **out, bwgr_panel *P, int model, const float *y, int memloc, float it,
-                                 float bi, float pi, float df, float R2, uint64_t seed, int rng_mode) {
-  if (!P) return fail(BWGR_EINVAL, "chain_create: null pointer");
-  return bwgr_chain_create_sharded(out, P, model, y, memloc, it, bi, pi, df, R2, seed, rng_mode, 0, P->data->p, P->data->MSx, nullptr);
-}
-
-static void chain_args(const bwgr_chain *C, int blk_begin, int blk_end, SweepArgs &a) {
-  const bwgr_panel *P = C->P;
-  const int model = C->model;
-  memset(&a, 0, sizeof(a));
-  fill_panel_args(P, a);
-  a.blk_begin = blk_begin; a.blk_end = blk_end;
-  int fl = 0;
-  if (has_d(model)) fl |= SWF_SELECT;
-  if (model == BWGR_BAYESDPI) fl |= SWF_ALT_B2 | SWF_MH;
-  if (per_marker_vb(model)) fl |= SWF_LAM_VEC | SWF_VB_VEC;
-  a.flags = fl | C->flags_extra;
-  a.e = C->e; a.b = C->b; a.d = C->d; a.vb = C->vb; a.xx = P->data->xx; a.lam = C->lam; a.sc = C->sc;
-  if (P->data->cen) {   // implicitly centred columns: the centred squared norms, the column sums, this handle's running block sums
-    a.flags |= SWF_CENTRE; a.xx = P->data->xxc; a.csum = P->data->csum; a.cpre = P->cpre; a.ninv = 1.0 / (double)P->data->n;
-  }
-  a.iter = (uint32_t)C->done; a.marker0 = (uint32_t)C->marker0; a.rng = make_rng(C->seed, C->rng_mode);
-}
-
-extern "C" int bwgr_chain_sweep_blocks(bwgr_chain *C, int blk_begin, int blk_end) {
-  if (!C) return fail(BWGR_EINVAL, "null chain");
-  bwgr_panel *P = C->P;
-  if (blk_begin < 0 || blk_end > P->data->plan.nblocks || blk_begin >= blk_end) return fail(BWGR_EINVAL, "sweep_blocks: bad range [%d,%d) of %lld", blk_begin, blk_end, (long long)P->data->plan.nblocks);
-  if (C->done >= C->iit) return fail(BWGR_EINVAL, "sweep_blocks: all %d iterations already run", C->iit);
-  HIPCHK(hipSetDevice(P->data->device));
-  SweepArgs a;
-  chain_args(C, blk_begin, blk_end, a);
-  SweepPlan pl; int need = 0;
-  CHK(sweep_begin(P, a, pl, &need));
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0));
-  if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail(BWGR_EHIP, "sweep_blocks: hipEventCreate failed"); }
-  // the per-marker constants and speculative terms of an iteration depend on the state at its start only (a block's b is
-  // untouched until the block is swept), so a chain that sweeps its panel in several ranges -- the exchange rounds of the
-  // marker-sharded sampler -- pre-stages all of them with the first range
-  bool prestaged = false;
-  if (P->ps_owner != C || P->ps_iter != C->done) {
-    SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->data->plan.nblocks;
-    launch_prestage(P, all, pl);
-    P->ps_owner = C; P->ps_iter = C->done;
-    prestaged = true;
-  }
-  hipError_t he = hipEventRecord(e0, P->stream);
-  if (he == hipSuccess) { launch_sweep_kernel(P, a, pl); he = hipGetLastError(); }
-  if (he == hipSuccess && prestaged && C->done + 1 < C->iit) {   // the next iteration's variates, beside this sweep
-    SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->data->plan.nblocks;
-    draws_ahead(P, all, pl, e0);
-  }
-  if (he == hipSuccess) he = hipEventRecord(e1, P->stream);
-  if (he != hipSuccess) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return fail(BWGR_EHIP, "sweep_blocks: %s", hipGetErrorString(he)); }
-  C->ev.push_back(e0); C->ev.push_back(e1);
-  guard_mark(P, P->stream, need);
-  if (C->ev.size() >= 4096) CHK(bwgr_chain_sweep_ms(C, nullptr, nullptr));   // bound the number of live events
-  return BWGR_OK;
-}
-
-namespace {
-__global__ void k_round_delta(const double *__restrict__ e, const double *__restrict__ e0, double *__restrict__ delta, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) delta[i] = e[i] - e0[i];
-}
-__global__ void k_round_apply(double *__restrict__ e, const double *__restrict__ e0, const double *__restrict__ delta, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) e[i] = e0[i] + delta[i];
-}
-}  // namespace
-
-// One exchange round of the marker-sharded sampler in two calls (the same steps a caller can take with sweep_blocks and
-// its own vector arithmetic; here they cost two small launches instead of three framework operations per round):
-//   round_sweep: remember e, sweep the blocks [blk_begin, blk_end) (an empty range sweeps nothing), delta = e - e_before
-//   <caller: all-reduce(sum) delta over the ranks>
-//   round_apply: e = e_before + delta
-// delta_dev: ld doubles on the chain's device (the panel's padded row count).
-extern "C" int bwgr_chain_round_sweep(bwgr_chain *C, int blk_begin, int blk_end, double *delta_dev) {
-  if (!C || !delta_dev) return fail(BWGR_EINVAL, "round_sweep: null pointer");
-  bwgr_panel *P = C->P;
-  HIPCHK(hipSetDevice(P->data->device));
-  if (!C->e0) CHK(own_array(C->own, C->e0, (size_t)P->data->plan.ld, "round_sweep"));
-  HIPCHK(hipMemcpyAsync(C->e0, C->e, sizeof(double) * P->data->plan.ld, hipMemcpyDeviceToDevice, P->stream));
-  if (blk_begin < blk_end) CHK(bwgr_chain_sweep_blocks(C, blk_begin, blk_end));
-  hipLaunchKernelGGL(k_round_delta, dim3(64), dim3(256), 0, P->stream, C->e, C->e0, delta_dev, P->data->plan.ld);
-  HIPCHK(hipGetLastError());
-  return BWGR_OK;
-}
-extern "C" int bwgr_chain_round_apply(bwgr_chain *C, const double *delta_dev) {
-  if (!C || !delta_dev) return fail(BWGR_EINVAL, "round_apply: null pointer");
-  if (!C->e0) return fail(BWGR_EINVAL, "round_apply: no round_sweep before it");
-  bwgr_panel *P = C->P;
-  HIPCHK(hipSetDevice(P->data->device));
-  hipLaunchKernelGGL(k_round_apply, dim3(64), dim3(256), 0, P->stream, C->e, C->e0, delta_dev, P->data->plan.ld);
-  HIPCHK(hipGetLastError());
-  return BWGR_OK;
-}
-
-extern "C" int bwgr_chain_get_sums(bwgr_chain *C, double sums[2]) {
-  if (!C || !sums) return fail(BWGR_EINVAL, "null pointer");
-  HIPCHK(hipSetDevice(C->P->data->device));
-  ChainScalars h;
-  HIPCHK(hipMemcpyAsync(&h, C->sc, sizeof(h), hipMemcpyDeviceToHost, C->P->stream));
-  HIPCHK(hipStreamSynchronize(C->P->stream));
-  if (h.error) return sweep_error(h.error, "chain");
-  sums[0] = h.sum_d; sums[1] = h.sum_b2;
-  return BWGR_OK;
-}
-
-__global__ void k_set_sums(ChainScalars *sc, double sd, double sb2) { sc->sum_d = sd; sc->sum_b2 = sb2; }
-
-extern "C" int bwgr_chain_end_iteration(bwgr_chain *C, const double sums_total[2]) {
-  if (!C) return fail(BWGR_EINVAL, "null chain");
-  if (C->done >= C->iit) return fail(BWGR_EINVAL, "end_iteration: all %d iterations already run", C->iit);
-  bwgr_panel *P = C->P;
-  HIPCHK(hipSetDevice(P->data->device));
-  const int model = C->model, i = C->done;
-  if (sums_total) hipLaunchKernelGGL(k_set_sums, dim3(1), dim3(1), 0, P->stream, C->sc, sums_total[0], sums_total[1]);
-  const int accumulate = (i > C->ibi) ? 1 : 0;   // if(i>ibi), src/Rcpp20260726ai.cpp:624
-  TailArgs t; t.e = C->e; t.n = (int)P->data->n; t.p = (int)C->p_total; t.model = model; t.df = C->df; t.R2 = C->R2; t.Phi = C->Phi;
-  t.accumulate = accumulate; t.iter = (uint32_t)i; t.rng = make_rng(C->seed, C->rng_mode); t.sc = C->sc;
-  hipLaunchKernelGGL(k_tail, dim3(1), dim3(1024), 0, P->stream, t);
-  hipLaunchKernelGGL(k_marker_tail, dim3((unsigned)std::min<int64_t>(2048, (P->data->p + 255) / 256)), dim3(256), 0, P->stream,
-                     C->b, C->d, C->vb, C->lam, C->B, C->D, C->VB, (int)P->data->p, model, C->Phi, accumulate, C->sc);
-  HIPCHK(hipGetLastError());
-  C->done++;
-  return BWGR_OK;
-}
-
-namespace {
-__global__ void k_get_sums_dev(const ChainScalars *sc, double *out2) { out2[0] = sc->sum_d; out2[1] = sc->sum_b2; }
-__global__ void k_set_sums_dev(ChainScalars *sc, const double *in2) { sc->sum_d = in2[0]; sc->sum_b2 = in2[1]; }
-}  // namespace
-// device-side forms of get_sums / end_iteration(sums_total) for the sharded sampler: the two sums stay on the device (the
-// caller all-reduces sums_dev, two doubles, in place), so an iteration needs no host round trip
-extern "C" int bwgr_chain_get_sums_dev(bwgr_chain *C, double *sums_dev) {
-  if (!C || !sums_dev) return fail(BWGR_EINVAL, "null pointer");
-  HIPCHK(hipSetDevice(C->P->data->device));
-  hipLaunchKernelGGL(k_get_sums_dev, dim3(1), dim3(1), 0, C->P->stream, C->sc, sums_dev);
-  HIPCHK(hipGetLastError());
-  return BWGR_OK;
-}
-extern "C" int bwgr_chain_end_iteration_dev(bwgr_chain *C, const double *sums_total_dev) {
-  if (!C || !sums_total_dev) return fail(BWGR_EINVAL, "null pointer");
-  HIPCHK(hipSetDevice(C->P->data->device));
-  hipLaunchKernelGGL(k_set_sums_dev, dim3(1), dim3(1), 0, C->P->stream, C->sc, sums_total_dev);
-  HIPCHK(hipGetLastError());
-  return bwgr_chain_end_iteration(C, nullptr);
-}
-
-extern "C" int bwgr_chain_run(bwgr_chain *C, int iters) {
-  if (!C) return fail(BWGR_EINVAL, "null chain");
-  if (iters < 0 || C->done + iters > C->iit) return fail(BWGR_EINVAL, "chain_run: %d more iterations would exceed it=%d (done %d)", iters, C->iit, C->done);
-  for (int k = 0; k < iters; ++k) {
-    CHK(bwgr_chain_sweep_blocks(C, 0, (int)C->P->data->plan.nblocks));
-    CHK(bwgr_chain_end_iteration(C, nullptr));
-  }
-  return BWGR_OK;
-}
-
-// Two chains of the same resident panel (C1 on a clone of C0's panel, or the other way round), advanced in lockstep by k_sweep3p: one
-// set of streamer workgroups -- one pass over the genotypes -- serves both, each chain keeps its own sequencer.  Selection models on
-// panels that have k_sweep3; every sweep of the pair is k_sweep3's (no device-side choice of engine).  Each chain's results are
-// bit-identical to a run of its own.  (No reference counterpart: the callers that fit many models on one X -- mcmcCV's loop,
-// /root/reference/R/cv.R:113-216 -- are where it plugs in.)
-extern "C" int bwgr_chain_run_pair(bwgr_chain *C0, bwgr_chain *C1, int iters) {
-  if (C0 && C0->P && C0->P->data->cen) return refuse_centred("chain_run_pair");
-  if (!C0 || !C1 || C0 == C1) return fail(BWGR_EINVAL, "chain_run_pair: two distinct chains");
-  bwgr_panel *P0 = C0->P, *P1 = C1->P;
-  if (P0->data != P1->data || P0 == P1) return fail(BWGR_EINVAL, "chain_run_pair: the chains must sit on two handles (panel and clone) of one resident panel");
-  if (iters < 0 || C0->done + iters > C0->iit || C1->done + iters > C1->iit) return fail(BWGR_EINVAL, "chain_run_pair: %d more iterations exceed it", iters);
-  SweepArgs t0, t1;
-  chain_args(C0, 0, (int)P0->data->plan.nblocks, t0); chain_args(C1, 0, (int)P1->data->plan.nblocks, t1);
-  if (plan_sweep(P0, t0, false).engine != 3 || plan_sweep(P1, t1, false).engine != 3 || !P0->qsum3 || !P1->qsum3)
-    return fail(BWGR_EINVAL, "chain_run_pair: both chains must be selection models on a panel with k_sweep3");
-  if (s3p_streamer_lds(P0->data->plan3.R3) > (size_t)160 * 1024) return fail(BWGR_EINVAL, "chain_run_pair: the paired streamers' LDS does not fit");
-  HIPCHK(hipSetDevice(P0->data->device));
-  // everything of the pair runs on ONE stream, owned by the root panel (it outlives both handles), and both handles move onto it
-  // for as long as they run in pairs -- one cross-stream wait each, the first time: a wait per call would sit in a hardware queue
-  // that other pairs' streams share, and stall them.  A handle's next sweep alone takes it back (leave_pair_stream).
-  auto is_pair_stream = [&](hipStream_t st) { for (hipStream_t q : P0->data->pair_streams) if (q == st) return true; return false; };
-  hipStream_t s0 = nullptr;
-  if (is_pair_stream(P0->stream)) s0 = P0->stream;
-  else if (is_pair_stream(P1->stream)) s0 = P1->stream;
-  else if ((s0 = P0->data->own.stream(hipStreamNonBlocking, 0))) P0->data->pair_streams.push_back(s0);
-  else return fail(BWGR_EHIP, "chain_run_pair: hipStreamCreate failed");
-  for (bwgr_panel *PX : {P0, P1}) {
-    if (PX->stream == s0) continue;
-    hipEvent_t ev;
-    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(ev, PX->stream)); HIPCHK(hipStreamWaitEvent(s0, ev, 0));
-    HIPCHK(hipEventDestroy(ev));
-    if (!PX->pre_pair_set) { PX->pre_pair_stream = PX->stream; PX->pre_pair_set = true; }   // (leave_pair_stream takes the handle back)
-    PX->stream = s0;
-  }
-  // the pair's one launch, resident beside the other streams' sweeps
-  P0->force3 = P1->force3 = true;   // (while the pair runs, every plan of either handle is that launch)
-  int need = 0;
-  int rc = sweep_guard(P0, plan_sweep(P0, t0, false), s0, P1, &need);
-  for (int k = 0; k < iters && rc == BWGR_OK; ++k) {
-    SweepArgs a0, a1;
-    chain_args(C0, 0, (int)P0->data->plan.nblocks, a0); chain_args(C1, 0, (int)P1->data->plan.nblocks, a1);
-    const SweepPlan pl0 = plan_sweep(P0, a0, false), pl1 = plan_sweep(P1, a1, false);
-    a0.lag = pl0.lag; a1.lag = pl1.lag;
-    if ((rc = reset_exchange(P0)) != BWGR_OK || (rc = reset_exchange(P1)) != BWGR_OK) break;
-    launch_prestage(P0, a0, pl0); launch_prestage(P1, a1, pl1);
-    P0->ps_owner = C0; P0->ps_iter = C0->done; P1->ps_owner = C1; P1->ps_iter = C1->done;
-    a0.gate3 = pl0.gate3; a1.gate3 = pl1.gate3;
-    if (P0->debug_withhold || P1->debug_withhold) { a0.flags |= SWF_DEBUG_WITHHOLD; a1.flags |= SWF_DEBUG_WITHHOLD; }
-    Sweep3Args A0, A1;
-    sweep3_args(P0, a0, pl0, A0); sweep3_args(P1, a1, pl1, A1);
-    hipEvent_t evs[4] = {nullptr, nullptr, nullptr, nullptr};   // both chains time the launch they share
-    bool ev_ok = true;
-    for (int q = 0; q < 4 && ev_ok; ++q) ev_ok = hipEventCreate(&evs[q]) == hipSuccess;
-    if (!ev_ok) { for (hipEvent_t q : evs) if (q) (void)hipEventDestroy(q); rc = fail(BWGR_EHIP, "chain_run_pair: hipEventCreate failed"); break; }
-    (void)hipEventRecord(evs[0], s0); (void)hipEventRecord(evs[2], s0);
-    void *args[] = {&A0, &A1};
-    spin_launch(pl0.spins[0], s0, args);
-    (void)hipEventRecord(evs[1], s0); (void)hipEventRecord(evs[3], s0);
-    C0->ev.push_back(evs[0]); C0->ev.push_back(evs[1]); C1->ev.push_back(evs[2]); C1->ev.push_back(evs[3]);
-    guard_mark(P0, s0, need);
-    if (hipGetLastError() != hipSuccess) { rc = fail(BWGR_EHIP, "chain_run_pair: launch failed"); break; }
-    if ((rc = bwgr_chain_end_iteration(C0, nullptr)) != BWGR_OK) break;
-    rc = bwgr_chain_end_iteration(C1, nullptr);
-    if (C0->ev.size() >= 4096) (void)bwgr_chain_sweep_ms(C0, nullptr, nullptr);
-    if (C1->ev.size() >= 4096) (void)bwgr_chain_sweep_ms(C1, nullptr, nullptr);
-  }
-  P0->force3 = P1->force3 = false;
-  return rc;
-}
-
-extern "C" int bwgr_chain_sync(bwgr_chain *C) {
-  if (!C) return fail(BWGR_EINVAL, "null chain");
-  HIPCHK(hipSetDevice(C->P->data->device));
-  HIPCHK(hipStreamSynchronize(C->P->stream));
-  ChainScalars h;
-  HIPCHK(d2h(C->P->stream, &h, C->sc, sizeof(h)));
-  if (h.error) return sweep_error(h.error, "chain");
-  return BWGR_OK;
-}
-
-extern "C" int bwgr_chain_iterations(const bwgr_chain *C, int *done) {
-  if (!C || !done) return fail(BWGR_EINVAL, "null pointer");
-  *done = C->done;
-  return BWGR_OK;
-}
-
-extern "C" int bwgr_chain_sweep_ms(bwgr_chain *C, float *avg_ms, int *launches) {
-  if (!C) return fail(BWGR_EINVAL, "null chain");
-  HIPCHK(hipSetDevice(C->P->data->device));
-  HIPCHK(hipStreamSynchronize(C->P->stream));
-  float total = 0; int nl = 0;
-  for (size_t k = 0; k + 1 < C->ev.size(); k += 2) {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, C->ev[k], C->ev[k + 1]));
-    total += ms; nl++;
-    hipEventDestroy(C->ev[k]); hipEventDestroy(C->ev[k + 1]);
-  }
-  C->ev.clear();
-  C->ms_acc += total; C->launch_acc += nl;
-  if (avg_ms && launches) {
-    *launches = C->launch_acc;
-    *avg_ms = C->launch_acc ? C->ms_acc / C->launch_acc : 0.0f;
-    C->ms_acc = 0; C->launch_acc = 0;
-  }
-  return BWGR_OK;
-}
-
-extern "C" int bwgr_chain_redo_count(bwgr_chain *C, int *count) {
-  if (!C || !count) return fail(BWGR_EINVAL, "null pointer");
-  CHK(bwgr_chain_sync(C));
-  ChainScalars h;
-  HIPCHK(d2h(C->P->stream, &h, C->sc, sizeof(h)));
-  *count = (int)h.nredo;
-  return BWGR_OK;
-}
-
-extern "C" int bwgr_chain_state(bwgr_chain *C, float *b, float *d, float *e, float *vb, float *scal) {
-  if (!C) return fail(BWGR_EINVAL, "null chain");
-  CHK(bwgr_chain_sync(C));
-  bwgr_panel *P = C->P;
-  const size_t pb = sizeof(float) * P->data->p;
-  ChainScalars h;
-  HIPCHK(d2h(P->stream, &h, C->sc, sizeof(h)));
-  if (b) HIPCHK(d2h(P->stream, b, C->b, pb));
-  if (d) HIPCHK(d2h(P->stream, d, C->d, pb));
-  if (e) {
-    DevBufs bufs;
-    float *ef = bufs.get<float>((size_t)P->data->n);
-    if (!ef) return fail(BWGR_ENOMEM, "chain_state: device allocation failed");
-    hipLaunchKernelGGL(k_d2f, dim3(64), dim3(256), 0, P->stream, C->e, ef, P->data->n);
-    HIPCHK(d2h(P->stream, e, ef, sizeof(float) * P->data->n));
-  }
-  if (vb) {
-    if (per_marker_vb(C->model)) HIPCHK(d2h(P->stream, vb, C->vb, pb));
-    else for (int64_t j = 0; j < P->data->p; ++j) vb[j] = h.vb;
-  }
-  if (scal) { scal[0] = h.mu; scal[1] = h.ve; scal[2] = h.vb; scal[3] = h.pi; }
   return BWGR_OK;
 }
 
@@ -2696,430 +1405,6 @@ static int gemv_hat(bwgr_panel *P, const CT *coef_dev, float MU, float *hat_dev,
   return BWGR_OK;
 }
 
-extern "C" int bwgr_chain_result(bwgr_chain *C, float *mu, float *b, float *d, float *hat, float *vb, float *ve,
-                                 float *h2, float *MSx, float *pi, float *pval) {
-  if (!C) return fail(BWGR_EINVAL, "null chain");
-  if (C->done != C->iit) return fail(BWGR_EINVAL, "chain_result: %d of %d iterations run", C->done, C->iit);
-  CHK(bwgr_chain_sync(C));
-  bwgr_panel *P = C->P;
-  const size_t pb = sizeof(float) * P->data->p;
-  const bool per = per_marker_vb(C->model);
-  const float MCMC = C->itf - C->bif;                                              // :626
-  DevBufs bufs;
-  float *pval_dev = nullptr;
-  if (pval && !(pval_dev = bufs.get<float>((size_t)P->data->p))) return fail(BWGR_ENOMEM, "chain_result: device allocation failed");
-  if (!C->finalized) {
-    hipLaunchKernelGGL(k_final_markers, dim3(1024), dim3(256), 0, P->stream, C->B, C->D, C->VB, pval_dev, (int)P->data->p, MCMC, per ? 1 : 0);
-    HIPCHK(hipGetLastError());
-    C->finalized = true;
-  } else if (pval_dev) {
-    hipLaunchKernelGGL(k_final_markers, dim3(1024), dim3(256), 0, P->stream, C->B, C->D, C->VB, pval_dev, (int)P->data->p, 1.0f, per ? 1 : 0);
-  }
-  ChainScalars h;
-  HIPCHK(hipMemcpyAsync(&h, C->sc, sizeof(h), hipMemcpyDeviceToHost, P->stream));
-  HIPCHK(hipStreamSynchronize(P->stream));
-  const float MU = h.MU / MCMC, VE = h.VE / MCMC;
-  float VBs = h.VBs / MCMC, Pi = 0, vg;
-  if (C->model == BWGR_BAYESCPI || C->model == BWGR_BAYESDPI) Pi = 1 - h.Pi / MCMC;   // :911
-  if (per) {
-    // vg = VB.sum()
-    DevBufs sum;
-    double *part = sum.get<double>(256); float *sdev = sum.get<float>(1);
-    if (!part || !sdev) return fail(BWGR_ENOMEM, "chain_result: device allocation failed");
-    CHK(sum_floats(P->stream, C->VB, (int64_t)P->data->p, part, sdev, &vg));
-  } else {
-    vg = VBs * C->MSx_eff;
-    if (C->model == BWGR_BAYESCPI) vg = VBs * C->MSx_eff / Pi;                         // :913
-  }
-  if (mu) *mu = MU;
-  if (ve) *ve = VE;
-  if (h2) *h2 = vg / (vg + VE);
-  if (MSx) *MSx = C->MSx_eff;
-  if (pi) *pi = Pi;
-  if (b) HIPCHK(d2h(P->stream, b, C->B, pb));
-  if (d) HIPCHK(d2h(P->stream, d, C->D, pb));
-  if (vb) { if (per) HIPCHK(d2h(P->stream, vb, C->VB, pb)); else vb[0] = VBs; }
-  if (pval) HIPCHK(d2h(P->stream, pval, pval_dev, pb));
-  if (hat) {
-    DevBufs fit;
-    float *hat_dev = fit.get<float>((size_t)P->data->n);
-    if (!hat_dev) return fail(BWGR_ENOMEM, "chain_result: device allocation failed");
-    CHK(gemv_hat<float>(P, C->B, MU, hat_dev, "chain_result", P->data->cen));
-    HIPCHK(d2h(P->stream, hat, hat_dev, sizeof(float) * P->data->n));
-  }
-  return BWGR_OK;
-}
-
-extern "C" int bwgr_bayes(bwgr_panel *P, int model, const float *y, float it, float bi, float pi, float df, float R2,
-                          uint64_t seed, int rng_mode, float *mu, float *b, float *d, float *hat, float *vb, float *ve,
-                          float *h2, float *MSx, float *pi_out, float *pval) {
-  bwgr_chain *C = nullptr;
-  CHK(bwgr_chain_create(&C, P, model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode));
-  Guard drop([&] { bwgr_chain_destroy(C); });
-  CHK(bwgr_chain_run(C, (int)it));
-  return bwgr_chain_result(C, mu, b, d, hat, vb, ve, h2, MSx, pi_out, pval);
-}
-
-// BayesA2 / BayesB2 / BayesRR2, src/Rcpp20260726ai.cpp:990-1218: two chains over two panels sharing the residual
-extern "C" int bwgr_bayes2(bwgr_panel *P1, bwgr_panel *P2, int base_model, const float *y, float it, float bi, float pi, float df,
-                           float R2, uint64_t seed, int rng_mode, float *mu, float *b1, float *d1, float *vb1, float *b2,
-                           float *d2, float *vb2, float *ve, float *hat, float *h2) {
-  if ((P1 && P1->data->cen) || (P2 && P2->data->cen)) return refuse_centred("bayes2");
-  if (!P1 || !P2 || !y) return fail(BWGR_EINVAL, "bayes2: null pointer");
-  if (base_model != BWGR_BAYESA && base_model != BWGR_BAYESB && base_model != BWGR_BAYESRR)
-    return fail(BWGR_EINVAL, "bayes2: base model must be BayesA, BayesB or BayesRR (got %d)", base_model);
-  if (P1->data->device != P2->data->device || P1->data->n != P2->data->n || P1->data->plan.ld != P2->data->plan.ld || P1->data->plan.K != P2->data->plan.K || P1->data->plan.R != P2->data->plan.R)
-    return fail(BWGR_EINVAL, "bayes2: the two panels must share device, rows and slab geometry (n %lld/%lld, %d x %d vs %d x %d rows)",
-                (long long)P1->data->n, (long long)P2->data->n, P1->data->plan.K, P1->data->plan.R, P2->data->plan.K, P2->data->plan.R);
-  const int64_t p1 = P1->data->p, p2 = P2->data->p, n = P1->data->n;
-  if (p1 + p2 > 0xFFFFFFF0ll - 2) return fail(BWGR_EINVAL, "bayes2: p1 + p2 too large");
-  HIPCHK(hipSetDevice(P1->data->device));
-  hipStream_t s2_saved = P2->stream;
-  P2->stream = P1->stream;   // one stream orders the two chains' kernels
-  Guard restore([&] { P2->stream = s2_saved; });
-  bwgr_chain *C1 = nullptr, *C2 = nullptr;
-  Guard drop([&] { bwgr_chain_destroy(C2); bwgr_chain_destroy(C1); });
-  DevBufs bufs;
-  CHK(bwgr_chain_create_sharded(&C1, P1, base_model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode, 0, p1 + p2, P1->data->MSx, nullptr));
-  CHK(bwgr_chain_create_sharded(&C2, P2, base_model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode, p1, p1 + p2, P2->data->MSx, C1->e));
-  const bool rr = (base_model == BWGR_BAYESRR), per = !rr;
-  if (base_model == BWGR_BAYESB) { C1->flags_extra = SWF_ALT_B2; C2->flags_extra = SWF_ALT_B2; }
-  if (rr) {
-    hipLaunchKernelGGL(k_set_rr2_start, dim3(1), dim3(1), 0, P1->stream, C1->sc);
-    hipLaunchKernelGGL(k_set_rr2_start, dim3(1), dim3(1), 0, P1->stream, C2->sc);
-  }
-  const int iit = (int)it, ibi = (int)bi;
-  for (int i = 0; i < iit; ++i) {
-    CHK(bwgr_chain_sweep_blocks(C1, 0, (int)P1->data->plan.nblocks));
-    CHK(bwgr_chain_sweep_blocks(C2, 0, (int)P2->data->plan.nblocks));
-    const int accumulate = (i > ibi) ? 1 : 0;                                        // if(i>ibi), :1047
-    Tail2Args t; t.e = C1->e; t.n = (int)n; t.p1 = (int)p1; t.p2 = (int)p2; t.rr = rr ? 1 : 0; t.df = df;
-    t.accumulate = accumulate; t.iter = (uint32_t)i; t.rng = make_rng(seed, rng_mode); t.sc1 = C1->sc; t.sc2 = C2->sc;
-    hipLaunchKernelGGL(k_tail2, dim3(1), dim3(1024), 0, P1->stream, t);
-    hipLaunchKernelGGL(k_marker_tail, dim3((unsigned)std::min<int64_t>(2048, (p1 + 255) / 256)), dim3(256), 0, P1->stream,
-                       C1->b, C1->d, C1->vb, C1->lam, C1->B, C1->D, C1->VB, (int)p1, base_model, 0.0f, accumulate, C1->sc);
-    hipLaunchKernelGGL(k_marker_tail, dim3((unsigned)std::min<int64_t>(2048, (p2 + 255) / 256)), dim3(256), 0, P1->stream,
-                       C2->b, C2->d, C2->vb, C2->lam, C2->B, C2->D, C2->VB, (int)p2, base_model, 0.0f, accumulate, C2->sc);
-    HIPCHK(hipGetLastError());
-    C1->done++; C2->done++;
-  }
-  CHK(bwgr_chain_sync(C1));
-  CHK(bwgr_chain_sync(C2));
-  const float MCMC = it - bi;                                                        // :1049
-  hipLaunchKernelGGL(k_final_markers, dim3(1024), dim3(256), 0, P1->stream, C1->B, C1->D, C1->VB, (float *)nullptr, (int)p1, MCMC, per ? 1 : 0);
-  hipLaunchKernelGGL(k_final_markers, dim3(1024), dim3(256), 0, P1->stream, C2->B, C2->D, C2->VB, (float *)nullptr, (int)p2, MCMC, per ? 1 : 0);
-  HIPCHK(hipGetLastError());
-  ChainScalars g1, g2;
-  HIPCHK(hipMemcpyAsync(&g1, C1->sc, sizeof(g1), hipMemcpyDeviceToHost, P1->stream));
-  HIPCHK(hipMemcpyAsync(&g2, C2->sc, sizeof(g2), hipMemcpyDeviceToHost, P1->stream));
-  HIPCHK(hipStreamSynchronize(P1->stream));
-  const float MU = g1.MU / MCMC, VE = g1.VE / MCMC, VB1s = g1.VBs / MCMC, VB2s = g2.VBs / MCMC;
-  float vg;
-  if (per) {                                                                         // vg = VB1.sum() + VB2.sum(), :1051
-    float v1 = 0, v2 = 0;
-    double *part = bufs.get<double>(256); float *sdev = bufs.get<float>(1);
-    if (!part || !sdev) return fail(BWGR_ENOMEM, "bayes2: device allocation failed");
-    CHK(sum_floats(P1->stream, C1->VB, (int64_t)p1, part, sdev, &v1));
-    CHK(sum_floats(P1->stream, C2->VB, (int64_t)p2, part, sdev, &v2));
-    vg = v1 + v2;
-  } else vg = VB1s * P1->data->MSx + VB2s * P2->data->MSx;                                       // :1213
-  if (mu) *mu = MU;
-  if (ve) *ve = VE;
-  if (h2) *h2 = vg / (vg + VE);
-  if (b1) HIPCHK(d2h(P1->stream, b1, C1->B, sizeof(float) * p1));
-  if (b2) HIPCHK(d2h(P1->stream, b2, C2->B, sizeof(float) * p2));
-  if (d1) HIPCHK(d2h(P1->stream, d1, C1->D, sizeof(float) * p1));
-  if (d2) HIPCHK(d2h(P1->stream, d2, C2->D, sizeof(float) * p2));
-  if (vb1) { if (per) HIPCHK(d2h(P1->stream, vb1, C1->VB, sizeof(float) * p1)); else vb1[0] = VB1s; }
-  if (vb2) { if (per) HIPCHK(d2h(P1->stream, vb2, C2->VB, sizeof(float) * p2)); else vb2[0] = VB2s; }
-  if (hat) {                                                                         // fit = X1*B1 + X2*B2; fit += MU, :1052-1053
-    float *h1d = bufs.get<float>((size_t)n), *h2d = bufs.get<float>((size_t)n), *hatd = bufs.get<float>((size_t)n);
-    if (!h1d || !h2d || !hatd) return fail(BWGR_ENOMEM, "bayes2: device allocation failed");
-    CHK(gemv_hat<float>(P1, C1->B, 0.0f, h1d, "bayes2"));
-    CHK(gemv_hat<float>(P2, C2->B, 0.0f, h2d, "bayes2"));
-    hipLaunchKernelGGL(k_hat2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, P1->stream, h1d, h2d, MU, hatd, (int)n);
-    HIPCHK(hipGetLastError());
-    HIPCHK(d2h(P1->stream, hat, hatd, sizeof(float) * n));
-  }
-  return BWGR_OK;
-}
-
-// host side of the RNG contract for wgr's row resampling, R/wgr.R:68: Use = sort(sample(n, n*bag, rp)) - 1
-static double host_uniform(uint64_t seed, uint32_t marker, uint32_t iter, uint32_t purpose, uint32_t k) {
-  uint32_t c0 = marker, c1 = iter, c2 = purpose, c3 = k, k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return ((double)(c0 >> 5) * 67108864.0 + (double)(c1 >> 6) + 0.5) / 9007199254740992.0;
-}
-static void bag_rows(uint64_t seed, uint32_t iter, int64_t n, int64_t k, int rp, std::vector<int> &use) {
-  use.resize((size_t)k);
-  if (rp) {
-    for (int64_t t = 0; t < k; ++t) { int r = (int)(host_uniform(seed, (uint32_t)t, iter, RNG_BAG, 1) * (double)n); use[(size_t)t] = r >= n ? (int)n - 1 : r; }
-  } else {
-    std::vector<std::pair<double, int>> kv((size_t)n);
-    for (int64_t i = 0; i < n; ++i) kv[(size_t)i] = std::make_pair(host_uniform(seed, (uint32_t)i, iter, RNG_BAG, 0), (int)i);
-    std::sort(kv.begin(), kv.end());
-    for (int64_t t = 0; t < k; ++t) use[(size_t)t] = kv[(size_t)t].second;
-  }
-  std::sort(use.begin(), use.end());
-}
-
-extern "C" int bwgr_sample_rows(uint64_t seed, uint32_t iter, int64_t n, int64_t k, int rp, int *rows) {
-  if (!rows || n < 1 || k < 0 || (!rp && k > n) || n > 0x7FFFFFFFll) return fail(BWGR_EINVAL, "sample_rows: bad arguments (n=%lld, k=%lld, rp=%d)", (long long)n, (long long)k, rp);
-  std::vector<int> use;
-  bag_rows(seed, iter, n, k, rp, use);
-  for (int64_t t = 0; t < k; ++t) rows[t] = use[(size_t)t];
-  return BWGR_OK;
-}
-
-extern "C" int bwgr_wgr(bwgr_panel *P, const double *y, int it, int bi, int th, int iv, int de, double pi, double df, double R2,
-                        uint64_t seed, int rng_mode, double *mu, double *b, double *Vb, double *d, double *Ve, double *hat,
-                        double *cxx) {
-  return bwgr_wgr_ex(P, y, it, bi, th, iv, de, pi, df, R2, seed, rng_mode, nullptr, nullptr, 0, 1.0, 0, mu, b, Vb, d, Ve, hat, cxx, nullptr, nullptr);
-}
-
-extern "C" int bwgr_wgr_ex(bwgr_panel *P, const double *y, int it, int bi, int th, int iv, int de, double pi, double df, double R2,
-                           uint64_t seed, int rng_mode, const double *U, const double *V, int64_t pk, double bag, int rp,
-                           double *mu, double *b, double *Vb, double *d, double *Ve, double *hat, double *cxx, double *u, double *Vk) {
-  if (P && P->data->cen) return refuse_centred("wgr");
-  if (!P || !y) return fail(BWGR_EINVAL, "wgr: null pointer");
-  if (!U || pk <= 0) { U = nullptr; pk = 0; }
-  if (U && !V) return fail(BWGR_EINVAL, "wgr: eigenvalues missing");
-  const bool bagging = (bag != 1.0);
-  if (bagging && U) return fail(BWGR_EINVAL, "wgr: bag != 1 with eigK is undefined in the reference (R/wgr.R:73-79 index a subsampled e with full row ids)");
-  if (bagging && !(bag > 0.0)) return fail(BWGR_EINVAL, "wgr: bag must be > 0");
-  const int64_t nbag = bagging ? (int64_t)((double)P->data->n * bag) : P->data->n;
-  if (bagging && nbag < 2) return fail(BWGR_EINVAL, "wgr: n*bag < 2");
-  // sample(n, n*bag, FALSE) cannot take more than the population (R errors out, R/wgr.R:68)
-  if (bagging && !rp && nbag > P->data->n) return fail(BWGR_EINVAL, "wgr: bag > 1 needs rp = TRUE (cannot take %lld of %lld rows without replacement)", (long long)nbag, (long long)P->data->n);
-  if (bagging) df = df / (bag * bag);                                              // R/wgr.R:20
-  if (it < 1 || bi < 0 || th < 1) return fail(BWGR_EINVAL, "wgr: need it >= 1, bi >= 0, th >= 1");
-  if (de) iv = 1;                                                                  // R/wgr.R:9
-  HIPCHK(hipSetDevice(P->data->device));
-  const int p = (int)P->data->p, n = (int)P->data->n;
-  const size_t pd = sizeof(double) * p;
-  const Rng rng = make_rng(seed, rng_mode);
-  int mc = 0; for (int q = bi; q <= it; q += th) mc++;                             // post = seq(bi,it,th)
-  if (mc < 1) return fail(BWGR_EINVAL, "wgr: seq(bi,it,th) is empty");
-  bwgr_panel *PU = nullptr;   // eigenvectors as an fp32 panel (KMUP narrows U to float like any other X)
-  bwgr_panel *PB = nullptr;   // the row subsample of this iteration (bag != 1): same markers, nbag rows
-  Guard drop([&] { bwgr_panel_destroy(PU); bwgr_panel_destroy(PB); });
-  std::vector<int> use_h;     // (copied from asynchronously: declared before the holder, which waits for the stream)
-  DevBufs bufs(P->stream);
-  if (U) {
-    CHK(bwgr_panel_create(&PU, U, BWGR_X_F64, BWGR_HOST, n, pk, n, P->data->device, 0, 0));
-    PU->stream = P->stream;
-  }
-  int *use_d = nullptr;
-  if (bagging) {
-    CHK(scratch_panel_alloc(&PB, P, nbag, 0, PANEL_ROWS));
-    CHK(scratch_alloc(PB));
-    if (!(use_d = bufs.get<int>((size_t)nbag))) return fail(BWGR_ENOMEM, "wgr: device allocation failed");
-  }
-  const int64_t ldmax = std::max<int64_t>(std::max<int64_t>(P->data->plan.ld, PU ? PU->data->plan.ld : 0), PB ? PB->data->plan.ld : 0);
-  const size_t nk = (size_t)std::max<int64_t>(pk, 1), np = (size_t)p, kd = sizeof(double) * nk;
-  const int nchunks = gemv_chunks(P), cpc = gemv_cpc_of(p, nchunks);   // X * coef: fp64 partial products per column chunk
-  double *yd = bufs.get<double>(n), *eR = bufs.get<double>(ldmax), *e64 = bufs.get<double>(ldmax);
-  double *Ud = bufs.get<double>((size_t)std::max<int64_t>(n * pk, 1)), *Vd = bufs.get<double>(nk), *hR = bufs.get<double>(nk), *Hk = bufs.get<double>(nk), *uhd = bufs.get<double>(n);
-  float *hf = bufs.get<float>(nk), *dhf = bufs.get<float>(nk), *xxKf = bufs.get<float>(nk), *Lkf = bufs.get<float>(nk), *vbk = bufs.get<float>(nk);
-  ChainScalars *sck = bufs.get<ChainScalars>(1);
-  double *xx64 = bufs.get<double>(np), *vx64 = bufs.get<double>(np), *bR = bufs.get<double>(np), *dR = bufs.get<double>(np);
-  double *VbR = bufs.get<double>(np), *LR = bufs.get<double>(np), *B = bufs.get<double>(np), *D = bufs.get<double>(np), *VB = bufs.get<double>(np);
-  float *bf = bufs.get<float>(np), *dfl = bufs.get<float>(np), *Lf = bufs.get<float>(np), *xxf = bufs.get<float>(np), *vbf = bufs.get<float>(np);
-  double *part1 = bufs.get<double>(256), *part2 = bufs.get<double>(256), *hatd = bufs.get<double>(n);
-  WgrScalars *ws = bufs.get<WgrScalars>(1);
-  ChainScalars *sc = bufs.get<ChainScalars>(1);
-  double *gpart = bufs.get<double>((size_t)nchunks * P->data->plan.ld);
-  if (!Ud || !Vd || !hR || !Hk || !uhd || !hf || !dhf || !xxKf || !Lkf || !vbk || !sck || !gpart ||
-      !yd || !eR || !e64 || !xx64 || !vx64 || !bR || !dR || !VbR || !LR || !B || !D || !VB || !bf || !dfl || !Lf || !xxf || !vbf || !part1 || !part2 || !hatd || !ws || !sc)
-    return fail(BWGR_ENOMEM, "wgr: device allocation failed");
-  HIPCHK(hipMemcpyAsync(yd, y, sizeof(double) * n, hipMemcpyHostToDevice, P->stream));
-  if (pk > 0) {
-    HIPCHK(hipMemcpyAsync(Ud, U, sizeof(double) * (size_t)n * pk, hipMemcpyHostToDevice, P->stream));
-    HIPCHK(hipMemcpyAsync(Vd, V, kd, hipMemcpyHostToDevice, P->stream));
-    HIPCHK(hipMemsetAsync(hR, 0, kd, P->stream)); HIPCHK(hipMemsetAsync(Hk, 0, kd, P->stream));
-  }
-  const int wpb = 4;
-  if (P->data->is_f32) hipLaunchKernelGGL(k_stats64<float>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const float *)P->data->X, P->data->plan.R, n, p, xx64, vx64);
-  else hipLaunchKernelGGL(k_stats64<int8_t>, dim3((p + wpb - 1) / wpb), dim3(64 * wpb), 0, P->stream, (const int8_t *)P->data->X, P->data->plan.R, n, p, xx64, vx64);
-  hipLaunchKernelGGL(k_dsum_stage1, dim3(256), dim3(256), 0, P->stream, vx64, (int64_t)p, part1, 0);
-  hipLaunchKernelGGL(k_dsum_stage1, dim3(256), dim3(256), 0, P->stream, xx64, (int64_t)p, part2, 0);
-  hipLaunchKernelGGL(k_wgr_init, dim3(1), dim3(1024), 0, P->stream, yd, eR, n, ldmax, part1, part2, p, df, R2, ws);
-  hipLaunchKernelGGL(k_wgr_marker_init, dim3(1024), dim3(256), 0, P->stream, bR, dR, VbR, LR, B, D, VB, p, ws);
-  if (bagging) hipLaunchKernelGGL(k_scale_d, dim3(256), dim3(256), 0, P->stream, xx64, (int64_t)p, bag);     // xx = crossprod * bag, R/wgr.R:46
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemsetAsync(sc, 0, sizeof(ChainScalars), P->stream));
-  const unsigned pg = (unsigned)std::min<int64_t>(2048, (P->data->p + 255) / 256);
-  for (int i = 1; i <= it; ++i) {                                                // R/wgr.R:66
-    const uint32_t itx = (uint32_t)(i - 1);
-    const int accumulate = (i >= bi && ((i - bi) % th) == 0) ? 1 : 0;            // i %in% post
-    if (pk > 0) {                                                                // R/wgr.R:70-76
-      hipLaunchKernelGGL(k_wgr_pre_k, dim3(64), dim3(256), 0, P->stream, hR, Vd, eR, hf, dhf, xxKf, Lkf, e64, (int)pk, n, ldmax, ws, sck);
-      SweepArgs ak; memset(&ak, 0, sizeof(ak));
-      fill_panel_args(PU, ak);
-      ak.flags = SWF_LAM_VEC;
-      ak.e = e64; ak.b = hf; ak.d = dhf; ak.vb = vbk; ak.xx = xxKf; ak.lam = Lkf; ak.sc = sck; ak.iter = itx; ak.marker0 = 0x80000000u; ak.rng = rng;
-      CHK(launch_sweep(PU, ak));
-      hipLaunchKernelGGL(k_wgr_post_k, dim3(64), dim3(256), 0, P->stream, hf, hR, e64, eR, (int)pk, n);
-    }
-    hipLaunchKernelGGL(k_wgr_pre, dim3(pg), dim3(256), 0, P->stream, bR, dR, LR, xx64, eR, bf, dfl, Lf, xxf, e64, p, n, ldmax, (float)pi, ws, sc);
-    SweepArgs a; memset(&a, 0, sizeof(a));
-    bwgr_panel *PS = bagging ? PB : P;                                           // the panel this iteration sweeps
-    if (bagging) {                                                               // R/wgr.R:68 + KMUP2's gathers
-      bag_rows(seed, itx, n, nbag, rp, use_h);
-      HIPCHK(hipMemcpyAsync(use_d, use_h.data(), sizeof(int) * (size_t)nbag, hipMemcpyHostToDevice, P->stream));
-      launch_gather_rows(P, PB, use_d, nbag);
-      CHK(panel_build_gram(PB));                                                 // syncs the stream (use_h stays valid)
-      hipLaunchKernelGGL(k_gather_e, dim3(64), dim3(256), 0, P->stream, eR, use_d, (int)nbag, ldmax, e64);
-      hipLaunchKernelGGL(k_set_bg, dim3(1), dim3(1), 0, P->stream, sc, (float)n / (float)nbag);
-    }
-    fill_panel_args(PS, a);
-    a.flags = SWF_LAM_VEC | (pi > 0 ? (SWF_SELECT | SWF_ALT_B2) : 0) | (bagging ? SWF_KMUP2 : 0) | (de ? SWF_SERIAL : 0);
-    a.e = e64; a.b = bf; a.d = dfl; a.vb = vbf; a.xx = xxf; a.lam = Lf; a.sc = sc; a.iter = itx; a.rng = rng;
-    CHK(launch_sweep(PS, a));                                                    // KMUP / KMUP2, R/wgr.R:85
-    hipLaunchKernelGGL(k_wgr_post, dim3(pg), dim3(256), 0, P->stream, bf, dfl, bR, dR, VbR, p, pi > 0 ? 1 : 0, iv, de, df, itx, rng, ws);
-    hipLaunchKernelGGL(k_dsum_stage1, dim3(256), dim3(256), 0, P->stream, bR, (int64_t)p, part1, 1);
-    if (pk > 0) hipLaunchKernelGGL(k_wgr_vp, dim3(1), dim3(1024), 0, P->stream, hR, Vd, (int)pk, df, itx, rng, ws);   // R/wgr.R:116-119
-    hipLaunchKernelGGL(k_wgr_scal, dim3(1), dim3(1024), 0, P->stream, e64, (int)nbag, (double)n * bag, p, part1, iv, df, itx, rng, ws);
-    hipLaunchKernelGGL(k_wgr_L, dim3(pg), dim3(256), 0, P->stream, bR, dR, VbR, LR, B, D, VB, p, iv, accumulate, ws);
-    gemv_launch<double>(P, bR, nchunks, cpc, gpart);
-    hipLaunchKernelGGL(k_wgr_efinish, dim3((n + 255) / 256), dim3(256), 0, P->stream, gpart, P->data->plan.ld, nchunks, n, yd, eR, ws);
-    if (pk > 0) hipLaunchKernelGGL(k_uh, dim3((n + 255) / 256), dim3(256), 0, P->stream, Ud, hR, n, (int)pk, 1.0, eR, 1);   // - U %*% h
-    hipLaunchKernelGGL(k_wgr_mu, dim3(1), dim3(1024), 0, P->stream, eR, n, iv, accumulate, itx, rng, ws);
-    if (pk > 0 && accumulate) hipLaunchKernelGGL(k_wgr_accum_k, dim3(8), dim3(256), 0, P->stream, hR, Hk, (int)pk, ws);
-    HIPCHK(hipGetLastError());
-    if ((i & 63) == 0) HIPCHK(hipStreamSynchronize(P->stream));                  // bound the launch queue
-  }
-  hipLaunchKernelGGL(k_dsum_stage1, dim3(256), dim3(256), 0, P->stream, D, (int64_t)p, part1, 0);
-  hipLaunchKernelGGL(k_wgr_final, dim3(1), dim3(1024), 0, P->stream, B, D, VB, p, (double)mc, part1, iv, ws);
-  WgrScalars h; ChainScalars hc;
-  HIPCHK(hipMemcpyAsync(&h, ws, sizeof(h), hipMemcpyDeviceToHost, P->stream));
-  HIPCHK(hipMemcpyAsync(&hc, sc, sizeof(hc), hipMemcpyDeviceToHost, P->stream));
-  HIPCHK(hipStreamSynchronize(P->stream));
-  g_last_redo = (int)hc.nredo;
-  if (hc.error) return sweep_error(hc.error, "wgr");
-  const double B0 = h.B0 / mc;
-  gemv_launch<double>(P, B, nchunks, cpc, gpart);                                // HAT = B0 + gen0 %*% B, R/wgr.R:152
-  hipLaunchKernelGGL(k_hat64_finish, dim3((n + 255) / 256), dim3(256), 0, P->stream, gpart, P->data->plan.ld, nchunks, n, B0, hatd);
-  if (pk > 0) {                                                                  // poly = U0 %*% H; HAT += poly, R/wgr.R:148-150
-    hipLaunchKernelGGL(k_uh, dim3((n + 255) / 256), dim3(256), 0, P->stream, Ud, Hk, n, (int)pk, 1.0 / (double)mc, uhd, 0);
-    hipLaunchKernelGGL(k_add_vec, dim3((n + 255) / 256), dim3(256), 0, P->stream, hatd, uhd, n);
-  }
-  HIPCHK(hipGetLastError());
-  if (mu) *mu = B0;
-  if (Ve) *Ve = h.VE / mc;
-  if (cxx) *cxx = h.cxx * bag;                                                   // mean(xx), xx = crossprod * bag
-  if (b) HIPCHK(d2h(P->stream, b, B, pd));
-  if (d) HIPCHK(d2h(P->stream, d, D, pd));
-  if (Vb) { if (iv) HIPCHK(d2h(P->stream, Vb, VB, pd)); else Vb[0] = h.VA / mc; }
-  if (hat) HIPCHK(d2h(P->stream, hat, hatd, sizeof(double) * n));
-  if (pk > 0 && u) HIPCHK(d2h(P->stream, u, uhd, sizeof(double) * n));
-  if (pk > 0 && Vk) *Vk = h.VP / mc;
-  return BWGR_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Multi-GPU inside the library (row e): bwgr_group_* -- one marker shard per device of this process, the residual replicated,
-// ONE host thread, one stream per device, RCCL all-reduces of the residual delta (n fp64) on those streams at the exchange
-// rounds.  This is what an R process (the reference's only host, R/wgr.R:2) needs in order to use more than one GPU through a
-// .Call; bwgr_amd/dist.py remains the torchrun driver of the benchmark (one process per GPU).  For G > 1 this is the
-// partitioned sampler of DESIGN.md section 8 (statistical parity); G = 1 is the plain exact chain.
-// RCCL is loaded with dlopen on first use, so single-GPU users never touch it.
-// ------------------------------------------------------------------------------------------------
-#include <dlfcn.h>
-namespace {
-typedef struct ncclComm *bwgr_ncclComm_t;
-struct RcclApi {
-  void *h = nullptr;
-  int (*CommInitAll)(bwgr_ncclComm_t *, int, const int *) = nullptr;
-  int (*CommDestroy)(bwgr_ncclComm_t) = nullptr;
-  int (*AllReduce)(const void *, void *, size_t, int, int, bwgr_ncclComm_t, hipStream_t) = nullptr;
-  int (*GroupStart)() = nullptr;
-  int (*GroupEnd)() = nullptr;
-  const char *(*GetErrorString)(int) = nullptr;
-};
-static RcclApi g_rccl;
-static int rccl_load() {
-  if (g_rccl.h) return BWGR_OK;
-  void *h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-  if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-  if (!h) return fail(BWGR_EHIP, "group: cannot load librccl.so (%s)", dlerror());
-  RcclApi a; a.h = h;
-  a.CommInitAll = (int (*)(bwgr_ncclComm_t *, int, const int *))dlsym(h, "ncclCommInitAll");
-  a.CommDestroy = (int (*)(bwgr_ncclComm_t))dlsym(h, "ncclCommDestroy");
-  a.AllReduce = (int (*)(const void *, void *, size_t, int, int, bwgr_ncclComm_t, hipStream_t))dlsym(h, "ncclAllReduce");
-  a.GroupStart = (int (*)())dlsym(h, "ncclGroupStart");
-  a.GroupEnd = (int (*)())dlsym(h, "ncclGroupEnd");
-  a.GetErrorString = (const char *(*)(int))dlsym(h, "ncclGetErrorString");
-  if (!a.CommInitAll || !a.CommDestroy || !a.AllReduce || !a.GroupStart || !a.GroupEnd) return fail(BWGR_EHIP, "group: librccl.so lacks an expected symbol");
-  g_rccl = a;
-  return BWGR_OK;
-}
-constexpr int BWGR_NCCL_FLOAT64 = 8, BWGR_NCCL_SUM = 0;   // ncclFloat64, ncclSum (rccl.h)
-}  // namespace
-
-struct bwgr_group {
-  int G = 0;
-  int model = 0;
-  int64_t n = 0, p = 0;
-  int block = 0, bps = 1, rounds = 1;
-  std::vector<int> dev;
-  std::vector<int64_t> lo, hi;
-  std::vector<bwgr_panel *> P;
-  std::vector<bwgr_chain *> C;
-  std::vector<std::unique_ptr<DevBufs>> own;   // [g], on shard g's device: delta, sums, and of shards side by side the stream and ev_sweep (own[0]: ev_sum, total, total_sums)
-  std::vector<double *> delta, sums;
-  std::vector<bwgr_ncclComm_t> comm;
-  bool use_comm = false;
-  bool centred = true;        // every shard's columns are centred (bwgr_panel_centred): what makes G > 1 statistically sound
-  float MSx_total = 0;
-  // several shards on ONE device (every entry of `devices` equal): the shards' sweeps run side by side on their own streams, each on its own
-  // compute units, and an exchange round is a sum kernel between events -- no RCCL.  One exact chain is a latency-bound pipeline that fills a
-  // third of the chip; the partitioned sampler's shards fill the rest.
-  bool same_dev = false;
-  std::vector<hipStream_t> streams;
-  std::vector<hipEvent_t> ev_sweep;      // [g]: shard g's round_sweep (or sums) is enqueued up to here
-  hipEvent_t ev_sum[2] = {nullptr, nullptr};
-  double *total[2] = {nullptr, nullptr}; // the summed residual deltas of a round, by round parity (ld doubles each); total_sums likewise (2 doubles)
-  double *total_sums[2] = {nullptr, nullptr};
-  uint64_t round_no = 0;
-};
-
-extern "C" int bwgr_group_destroy(bwgr_group *Gp) {
-  if (!Gp) return BWGR_OK;
-  for (size_t g = 0; g < Gp->C.size(); ++g) if (Gp->C[g]) bwgr_chain_destroy(Gp->C[g]);
-  for (size_t g = 0; g < Gp->P.size(); ++g) {
-    (void)hipSetDevice(Gp->dev[g]);
-    if (Gp->P[g]) bwgr_panel_destroy(Gp->P[g]);
-  }
-  if (Gp->use_comm) for (bwgr_ncclComm_t c : Gp->comm) if (c) g_rccl.CommDestroy(c);
-  for (size_t g = 0; g < Gp->own.size(); ++g) { (void)hipSetDevice(Gp->dev[g]); Gp->own[g].reset(); }
-  delete Gp;
-  return BWGR_OK;
-}
-
-// X: HOST matrix, column-major n x p (ldx >= n), any bwgr_xtype; y: n host floats.  Device g of `devices` stages the
-// block-aligned column shard [lo_g, hi_g) (as bwgr_amd/dist.py::shard_bounds) and runs the chain of that shard.
-// markers_per_sync: markers swept per device between two residual all-reduces (0: 131072 / ndev, the benchmark's default; 131072 for shards
-// side by side on one device).
-// ---- are a panel's columns centred?  The marker-sharded partitioned sampler is statistically sound only then (DESIGN.md section 8:
-// uncentred genotypes are all collinear through the mean direction, every shard corrects the same stale residual mean and the summed
-// corrections overshoot; on centred columns 2 / 4 / 8 shards follow the exact chain: tools/centred_shard_probe.py).  From the panel's
-// own statistics: mean_j^2 = (xx_j - (n - 1) vx_j) / n; a column counts as centred when |mean_j| <= 1e-3 sd_j. ----
-namespace {
-__global__ void k_uncentred(const float *xx, const float *vx, int64_t p, double n, int *flag) {
-  int any = 0;
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < p; j += (int64_t)gridDim.x * blockDim.x) {
-    const double v = (double)vx[j], m2 = fmax(0.0, ((double)xx[j] - (n - 1.0) * v) / n);
-    any |= (m2 > 1e-6 * v + 1e-30);
-  }
-  if (any) *flag = 1;
-}
-}  // namespace
 // Sweep the IMPLICITLY centred columns x_j - mean(x_j) of an int8 panel from now on (on != 0) or the raw columns again (on == 0): nothing is
 // converted or copied -- the genotypes stay int8, the streamers, Gram arrays and MFMA tiles stay those of the raw columns, and the sequencer of
 // k_sweep3 carries the scalar terms (sweep3.hip.h, "implicitly centred sweeps").  What changes for the callers: bwgr_panel_stats returns the centred
@@ -3149,6 +1434,10 @@ extern "C" int bwgr_panel_set_centred(bwgr_panel *P, int on) {
   return BWGR_OK;
 }
 
+// ---- are a panel's columns centred?  The marker-sharded partitioned sampler is statistically sound only then (DESIGN.md section 8:
+// uncentred genotypes are all collinear through the mean direction, every shard corrects the same stale residual mean and the summed
+// corrections overshoot; on centred columns 2 / 4 / 8 shards follow the exact chain: tools/centred_shard_probe.py).  From the panel's
+// own statistics: mean_j^2 = (xx_j - (n - 1) vx_j) / n; a column counts as centred when |mean_j| <= 1e-3 sd_j. ----
 extern "C" int bwgr_panel_centred(bwgr_panel *P, int *centred) {
   if (!P || !centred) return fail(BWGR_EINVAL, "null pointer");
   if (P->data->cen) { *centred = 1; return BWGR_OK; }   // implicitly centred: exactly
@@ -3162,654 +1451,10 @@ extern "C" int bwgr_panel_centred(bwgr_panel *P, int *centred) {
   *centred = h ? 0 : 1;
   return BWGR_OK;
 }
-extern "C" int bwgr_group_sound(const bwgr_group *Gp, int *sound);
 
-static int group_create_impl(bwgr_group **out, int ndev, const int *devices, const void *X, int xtype, int64_t n, int64_t p,
-                             int64_t ldx, int block, const float *y, int model, float it, float bi, float pi, float df, float R2,
-                             uint64_t seed, int rng_mode, int64_t markers_per_sync, int centre, int memloc = BWGR_HOST) {
-  if (!out || !devices || !X || !y) return fail(BWGR_EINVAL, "group_create: null pointer");
-  if (memloc != BWGR_HOST && memloc != BWGR_DEVICE) return fail(BWGR_EINVAL, "group_create: bad memloc %d", memloc);
-  if (memloc == BWGR_DEVICE && ndev > 1 && !std::all_of(devices, devices + ndev, [&](int d) { return d == devices[0]; }))
-    return fail(BWGR_EINVAL, "group_create: a device-resident X serves shards of that one device only");
-  if (centre && xtype != BWGR_X_I8) return fail(BWGR_EINVAL, "group_create_centred: implicit centring is for int8 genotypes (centre float columns before the call)");
-  *out = nullptr;
-  if (ndev < 1 || ndev > 64) return fail(BWGR_EINVAL, "group_create: ndev = %d", ndev);
-  for (int g = 1; g < ndev; ++g) for (int h = 0; h < g; ++h)
-    if (devices[g] == devices[h] && !std::all_of(devices, devices + ndev, [&](int d) { return d == devices[0]; }))
-      return fail(BWGR_EINVAL, "group_create: a device may appear once, or every shard sits on the same device (shards side by side on one GPU)");
-  if (xtype != BWGR_X_I8 && xtype != BWGR_X_F32 && xtype != BWGR_X_F64) return fail(BWGR_EINVAL, "group_create: bad xtype %d", xtype);
-  const int mmax = (xtype == BWGR_X_I8) ? SW_MAXM : 64;
-  const int m = block > 0 ? block : mmax;
-  const int64_t nblk = (p + m - 1) / m, per = (nblk + ndev - 1) / ndev;
-  if ((int64_t)(ndev - 1) * per * m >= p) return fail(BWGR_EINVAL, "group_create: p = %lld has only %lld blocks of %d markers: too few for %d devices", (long long)p, (long long)nblk, m, ndev);
-  bwgr_group *Gp = new bwgr_group();
-  Gp->G = ndev; Gp->model = model; Gp->n = n; Gp->p = p; Gp->block = m;
-  Gp->dev.assign(devices, devices + ndev);
-  Gp->same_dev = ndev > 1 && std::all_of(devices, devices + ndev, [&](int d) { return d == devices[0]; });
-  Gp->P.assign(ndev, nullptr); Gp->C.assign(ndev, nullptr); Gp->delta.assign(ndev, nullptr); Gp->sums.assign(ndev, nullptr);
-  for (int g = 0; g < ndev; ++g) Gp->own.emplace_back(new DevBufs());
-  Guard drop([&] { bwgr_group_destroy(Gp); });
-  const size_t esz = (xtype == BWGR_X_I8) ? 1 : (xtype == BWGR_X_F32 ? 4 : 8);
-  double msx = 0.0;
-  for (int g = 0; g < ndev; ++g) {
-    const int64_t lo = std::min<int64_t>(p, (int64_t)g * per * m), hi = std::min<int64_t>(p, (int64_t)(g + 1) * per * m);
-    Gp->lo.push_back(lo); Gp->hi.push_back(hi);
-    CHK(bwgr_panel_create(&Gp->P[g], reinterpret_cast<const unsigned char *>(X) + (size_t)lo * (size_t)ldx * esz, xtype, memloc, n, hi - lo, ldx, devices[g], m, 0));
-    if (Gp->same_dev) {   // shards of one device: each on a stream of its own; from three shards on, 256-row streamers (K3 + 1 units a shard instead of 2 K3 + 2)
-      hipStream_t q = Gp->own[g]->stream(hipStreamNonBlocking, 0);
-      if (!q) return fail(BWGR_EHIP, "group_create: hipStreamCreate failed");
-      Gp->streams.push_back(q);
-      Gp->P[g]->stream = q;
-      if (ndev > 2 && Gp->P[g]->data->sw.solo3 < 0) Gp->P[g]->data->crowded = true;   // (an explicit BWGR_SOLO3 decides otherwise: experiments)
-    }
-    if (centre) CHK(bwgr_panel_set_centred(Gp->P[g], 1));   // the shard's own column means (rows are not sharded)
-    msx += (double)Gp->P[g]->data->MSx;
-    int cen = 1;
-    CHK(bwgr_panel_centred(Gp->P[g], &cen));
-    if (!cen) Gp->centred = false;
-  }
-  Gp->MSx_total = (float)msx;
-  if (ndev > 1 && !Gp->centred) {
-    if (!Gp->P[0]->data->sw.group_allow_uncentred)
-      return fail(BWGR_EINVAL, "group_create: the columns of X are not centred, and on uncentred columns the marker-sharded sampler of %d devices is "
-                               "statistically unsound (every shard corrects the same stale residual mean: DESIGN.md section 8).  Pass centred columns "
-                               "(x_j - mean(x_j), float: the posterior of b and hat is the same under the sampler's flat intercept prior), use one "
-                               "device, or set BWGR_GROUP_ALLOW_UNCENTRED=1 to run it knowingly", ndev);
-  }
-  for (int g = 0; g < ndev; ++g) {
-    CHK(bwgr_chain_create_sharded(&Gp->C[g], Gp->P[g], model, y, BWGR_HOST, it, bi, pi, df, R2, seed, rng_mode, Gp->lo[g], p, Gp->MSx_total, nullptr));
-    if (hipSetDevice(devices[g]) != hipSuccess || !Gp->own[g]->take({{&Gp->delta[g], sizeof(double) * (size_t)Gp->P[g]->data->plan.ld}, {&Gp->sums[g], sizeof(double) * 2}}))
-      return no_memory("group_create");
-    if (Gp->P[g]->data->plan.ld != Gp->P[0]->data->plan.ld) return fail(BWGR_EINVAL, "group_create: shards disagree on the padded row count");
-  }
-  // (shards side by side exchange through one kernel on the same card, not a ring over xGMI, but every exchange is a launch boundary for all of
-  // them: 131072 markers per shard between two exchanges there)
-  const int64_t mps = markers_per_sync > 0 ? markers_per_sync : std::max<int64_t>(m, Gp->same_dev ? 131072 : 131072 / ndev);
-  Gp->bps = (int)std::max<int64_t>(1, mps / m);
-  int64_t nbmax = 0;
-  for (int g = 0; g < ndev; ++g) nbmax = std::max<int64_t>(nbmax, Gp->P[g]->data->plan.nblocks);
-  Gp->rounds = (int)((nbmax + Gp->bps - 1) / Gp->bps);
-  Gp->use_comm = (ndev > 1 && !Gp->same_dev) || (Gp->P[0]->data->sw.group_force_comm && !Gp->same_dev);   // (BWGR_GROUP_FORCE_COMM=1, tests: exercise the RCCL path with a single device)
-  if (Gp->same_dev) {
-    if (hipSetDevice(devices[0]) != hipSuccess) return fail(BWGR_EHIP, "group_create: hipSetDevice failed");
-    Gp->ev_sweep.assign(ndev, nullptr);
-    for (int g = 0; g < ndev; ++g) if (!(Gp->ev_sweep[g] = Gp->own[g]->event(hipEventDisableTiming))) return fail(BWGR_EHIP, "group_create: hipEventCreate failed");
-    for (int k = 0; k < 2; ++k) {
-      if (!Gp->own[0]->take({DevBufs::want_event(&Gp->ev_sum[k], hipEventDisableTiming), {&Gp->total[k], sizeof(double) * (size_t)Gp->P[0]->data->plan.ld}, {&Gp->total_sums[k], sizeof(double) * 2}}))
-        return no_memory("group_create");
-    }
-  }
-  if (Gp->use_comm) {
-    CHK(rccl_load());
-    Gp->comm.assign(ndev, nullptr);
-    const int nr = g_rccl.CommInitAll(Gp->comm.data(), ndev, devices);
-    if (nr != 0) return fail(BWGR_EHIP, "group_create: ncclCommInitAll failed: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(nr) : "?");
-  }
-  drop.release();
-  *out = Gp;
-  return BWGR_OK;
-}
-
-extern "C" int bwgr_group_create(bwgr_group **out, int ndev, const int *devices, const void *X, int xtype, int64_t n, int64_t p,
-                                 int64_t ldx, int block, const float *y, int model, float it, float bi, float pi, float df, float R2,
-                                 uint64_t seed, int rng_mode, int64_t markers_per_sync) {
-  return group_create_impl(out, ndev, devices, X, xtype, n, p, ldx, block, y, model, it, bi, pi, df, R2, seed, rng_mode, markers_per_sync, 0);
-}
-// ... on the implicitly centred columns of an int8 matrix (bwgr_panel_set_centred on every shard): sound with several devices, int8 in HBM
-extern "C" int bwgr_group_create_centred(bwgr_group **out, int ndev, const int *devices, const void *X, int xtype, int64_t n, int64_t p,
-                                         int64_t ldx, int block, const float *y, int model, float it, float bi, float pi, float df, float R2,
-                                         uint64_t seed, int rng_mode, int64_t markers_per_sync, int memloc) {
-  return group_create_impl(out, ndev, devices, X, xtype, n, p, ldx, block, y, model, it, bi, pi, df, R2, seed, rng_mode, markers_per_sync, 1, memloc);
-}
-static int group_allreduce(bwgr_group *Gp, std::vector<double *> &buf, size_t count) {
-  int nr = g_rccl.GroupStart();
-  for (int g = 0; g < Gp->G && nr == 0; ++g)
-    nr = g_rccl.AllReduce(buf[g], buf[g], count, BWGR_NCCL_FLOAT64, BWGR_NCCL_SUM, Gp->comm[g], Gp->P[g]->stream);
-  const int ne = g_rccl.GroupEnd();
-  if (nr == 0) nr = ne;
-  if (nr != 0) return fail(BWGR_EHIP, "group: ncclAllReduce failed: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(nr) : "?");
-  return BWGR_OK;
-}
-
-extern "C" int bwgr_group_sound(const bwgr_group *Gp, int *sound) {
-  if (!Gp || !sound) return fail(BWGR_EINVAL, "null pointer");
-  *sound = (Gp->G == 1 || Gp->centred) ? 1 : 0;   // one device: the exact chain; more: sound on centred columns only
-  return BWGR_OK;
-}
-
-namespace {
-struct SumPtrs { const double *src[64]; };
-__global__ void k_group_sum(const SumPtrs s, int G, double *out, int64_t count) {   // out = sum over the shards, in shard order (the same bits on every run)
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
-    double t = 0.0;
-    for (int g = 0; g < G; ++g) t += s.src[g][i];
-    out[i] = t;
-  }
-}
-}  // namespace
-// one exchange among the shards of one device: every shard's stream has produced buf[g]; stream 0 sums them into `total` (by round parity, so
-// that the readers of the previous round are never overwritten: a buffer's next writer waits for events that every reader's stream records later)
-static int group_local_sum(bwgr_group *Gp, std::vector<double *> &buf, size_t count, double *const total[2], double **out) {
-  const int k = (int)(Gp->round_no++ & 1u);
-  SumPtrs sp;
-  for (int g = 0; g < Gp->G; ++g) { sp.src[g] = buf[g]; HIPCHK(hipEventRecord(Gp->ev_sweep[g], Gp->streams[g])); }
-  for (int g = 1; g < Gp->G; ++g) HIPCHK(hipStreamWaitEvent(Gp->streams[0], Gp->ev_sweep[g], 0));
-  hipLaunchKernelGGL(k_group_sum, dim3((unsigned)std::min<size_t>(64, (count + 255) / 256)), dim3(256), 0, Gp->streams[0], sp, Gp->G, total[k], (int64_t)count);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(Gp->ev_sum[k], Gp->streams[0]));
-  for (int g = 1; g < Gp->G; ++g) HIPCHK(hipStreamWaitEvent(Gp->streams[g], Gp->ev_sum[k], 0));
-  *out = total[k];
-  return BWGR_OK;
-}
-static int group_run_same_device(bwgr_group *Gp, int iters) {
-  HIPCHK(hipSetDevice(Gp->dev[0]));
-  for (int k = 0; k < iters; ++k) {
-    for (int r = 0; r < Gp->rounds; ++r) {
-      for (int g = 0; g < Gp->G; ++g) {
-        const int nb = (int)Gp->P[g]->data->plan.nblocks;
-        const int lo = std::min(nb, r * Gp->bps), hi = std::min(nb, (r + 1) * Gp->bps);
-        CHK(bwgr_chain_round_sweep(Gp->C[g], lo, hi, Gp->delta[g]));
-      }
-      double *tot = nullptr;
-      CHK(group_local_sum(Gp, Gp->delta, (size_t)Gp->P[0]->data->plan.ld, Gp->total, &tot));
-      for (int g = 0; g < Gp->G; ++g) CHK(bwgr_chain_round_apply(Gp->C[g], tot));
-    }
-    for (int g = 0; g < Gp->G; ++g) CHK(bwgr_chain_get_sums_dev(Gp->C[g], Gp->sums[g]));
-    double *tot2 = nullptr;
-    CHK(group_local_sum(Gp, Gp->sums, 2, Gp->total_sums, &tot2));
-    for (int g = 0; g < Gp->G; ++g) CHK(bwgr_chain_end_iteration_dev(Gp->C[g], tot2));
-  }
-  return BWGR_OK;
-}
-
-extern "C" int bwgr_group_run(bwgr_group *Gp, int iters) {
-  if (!Gp) return fail(BWGR_EINVAL, "null group");
-  if (iters < 0) return fail(BWGR_EINVAL, "group_run: iters < 0");
-  if (Gp->same_dev) return group_run_same_device(Gp, iters);
-  if (!Gp->use_comm) return bwgr_chain_run(Gp->C[0], iters);   // one device: the plain exact chain
-  for (int k = 0; k < iters; ++k) {
-    for (int r = 0; r < Gp->rounds; ++r) {
-      for (int g = 0; g < Gp->G; ++g) {
-        const int nb = (int)Gp->P[g]->data->plan.nblocks;
-        const int lo = std::min(nb, r * Gp->bps), hi = std::min(nb, (r + 1) * Gp->bps);   // (lo == hi: a device that has run out of blocks still takes part)
-        CHK(bwgr_chain_round_sweep(Gp->C[g], lo, hi, Gp->delta[g]));
-      }
-      CHK(group_allreduce(Gp, Gp->delta, (size_t)Gp->P[0]->data->plan.ld));
-      for (int g = 0; g < Gp->G; ++g) CHK(bwgr_chain_round_apply(Gp->C[g], Gp->delta[g]));
-    }
-    for (int g = 0; g < Gp->G; ++g) CHK(bwgr_chain_get_sums_dev(Gp->C[g], Gp->sums[g]));
-    CHK(group_allreduce(Gp, Gp->sums, 2));
-    for (int g = 0; g < Gp->G; ++g) CHK(bwgr_chain_end_iteration_dev(Gp->C[g], Gp->sums[g]));
-  }
-  return BWGR_OK;
-}
-
-extern "C" int bwgr_group_sync(bwgr_group *Gp) {
-  if (!Gp) return fail(BWGR_EINVAL, "null group");
-  for (int g = 0; g < Gp->G; ++g) CHK(bwgr_chain_sync(Gp->C[g]));
-  return BWGR_OK;
-}
-
-extern "C" int bwgr_group_info(const bwgr_group *Gp, int64_t info[4]) {
-  if (!Gp || !info) return fail(BWGR_EINVAL, "null pointer");
-  info[0] = Gp->G; info[1] = Gp->rounds; info[2] = (int64_t)Gp->bps * Gp->block; info[3] = Gp->use_comm ? 1 : 0;
-  return BWGR_OK;
-}
-
-// the reference's return list over the whole panel (host outputs; any may be NULL): b, d, pval: p floats; vb: p floats for the
-// per-marker-variance models, else 1; hat: n floats
-extern "C" int bwgr_group_result(bwgr_group *Gp, float *mu, float *b, float *d, float *hat, float *vb, float *ve, float *h2,
-                                 float *MSx, float *pi_out, float *pval) {
-  if (!Gp) return fail(BWGR_EINVAL, "null group");
-  const bool per = per_marker_vb(Gp->model);
-  std::vector<float> hg(hat ? (size_t)Gp->n : 0), vbl;
-  float mu0 = 0, ve0 = 0, h20 = 0, msx0 = 0, pi0 = 0, vbs = 0;
-  double vg = 0.0;
-  if (hat) for (int64_t i = 0; i < Gp->n; ++i) hat[i] = 0.0f;
-  for (int g = 0; g < Gp->G; ++g) {
-    const int64_t lo = Gp->lo[g], pg = Gp->hi[g] - lo;
-    float mug, veg, h2g, msxg, pig;
-    vbl.assign(per ? (size_t)pg : 1, 0.0f);
-    CHK(bwgr_chain_result(Gp->C[g], &mug, b ? b + lo : nullptr, d ? d + lo : nullptr, hat ? hg.data() : nullptr, vbl.data(), &veg, &h2g,
-                          &msxg, &pig, pval ? pval + lo : nullptr));
-    if (g == 0) { mu0 = mug; ve0 = veg; h20 = h2g; msx0 = msxg; pi0 = pig; vbs = vbl[0]; }
-    if (per) { for (int64_t j = 0; j < pg; ++j) { vg += (double)vbl[(size_t)j]; if (vb) vb[lo + j] = vbl[(size_t)j]; } }
-    if (hat) for (int64_t i = 0; i < Gp->n; ++i) hat[i] += hg[(size_t)i] - mug;   // X_g B_g
-  }
-  if (hat) for (int64_t i = 0; i < Gp->n; ++i) hat[i] += mu0;
-  if (!per && vb) vb[0] = vbs;
-  if (mu) *mu = mu0;
-  if (ve) *ve = ve0;
-  if (h2) *h2 = per ? (float)(vg / (vg + (double)ve0)) : h20;   // (the common-variance models form vg from MSx over all shards already)
-  if (MSx) *MSx = msx0;
-  if (pi_out) *pi_out = pi0;
-  return BWGR_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// f4: EM / Gauss-Seidel family (emRR, emBA, emBB, emBC, emBCpi, emDE, emBL, emEN, emML), src/Rcpp20260726ai.cpp:80-521, :1502-1545
-//
-// Deterministic coordinate updates -- b_j = (X_j.e + xx_j b_j)/(xx_j + lambda_j), i.e. the affine sweep with the variates
-// switched off, or the member's soft-selection / soft-threshold update (lane_em) -- in a marker order that the reference re-shuffles before every sweep (std::shuffle with
-// std::mt19937(i), :103 ...).  The exact blocked sweep needs the Gram blocks of consecutive markers, so every sweep
-//   (1) shuffles the order on the host with the very library call the reference makes,
-//   (2) gathers the columns of the resident panel into a scratch panel in that order (one pass over X),
-//   (3) rebuilds the scratch panel's diagonal and distance-1 Gram blocks,
-//   (4) runs the affine sweep kernel on it (b, xx, lambda gathered; b scattered back),
-//   (5) runs the model's tail (variance components, lambda, intercept) in one workgroup.
-// ------------------------------------------------------------------------------------------------
-namespace {
-
-__global__ void k_permute_cols(const uint4 *__restrict__ X, uint4 *__restrict__ Xp, const int32_t *__restrict__ order,
-                               int64_t p, int K, int cps) {
-  // slab-major layout: (slab s, marker j) is one segment of R elements = cps 16-byte chunks
-  const int64_t total = (int64_t)K * p * cps;
-  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < total; c += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t seg = c / cps;
-    const int off = (int)(c - seg * cps);
-    const int64_t sl = seg / p, jj = seg - sl * p;
-    Xp[c] = X[(sl * p + order[jj]) * cps + off];
-  }
-}
-
-struct EmState {
-  float mu, ve, vb, Lmb, cnv, Sb, Se, Rho, cxx, df, vy, MSx;
-  float va, Sa, Pi, Pi0, PriorPi, sumvx, R2, alpha, Lmb1, Lmb2, Sy, trAC22;
-};
-
-// per-marker inputs of one sweep, in sweep order: b, xx, lambda
-__global__ void k_em_stage(const int32_t *__restrict__ order, int64_t p, int model, int weighted, const float *__restrict__ b,
-                           const float *__restrict__ xx, const float *__restrict__ lam, const float *__restrict__ D,
-                           const EmState *__restrict__ st, float *__restrict__ bq, float *__restrict__ xxq, float *__restrict__ lamq) {
-  const float Lmb = st->Lmb, Lmb2 = st->Lmb2;
-  for (int64_t jj = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; jj < p; jj += (int64_t)gridDim.x * blockDim.x) {
-    const int j = order[jj];
-    bq[jj] = b[j]; xxq[jj] = xx[j];
-    float l;
-    if (model == BWGR_EM_BA || model == BWGR_EM_DE || model == BWGR_EM_BB) l = lam[j];
-    else if (model == BWGR_EM_BL || model == BWGR_EM_EN) l = Lmb2;                   // denominators Lmb2 + xx, :382, :434
-    else if (model == BWGR_EM_LASSO) l = 0.0f;                                       // denominator xx, :1480
-    else if (weighted) l = Lmb / D[j];                                               // :496
-    else l = Lmb;
-    lamq[jj] = l;
-  }
-}
-__global__ void k_em_unstage(const int32_t *__restrict__ order, int64_t p, const float *__restrict__ bq, float *__restrict__ b,
-                             const float *__restrict__ dq, float *__restrict__ d) {
-  for (int64_t jj = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; jj < p; jj += (int64_t)gridDim.x * blockDim.x) {
-    const int j = order[jj];
-    b[j] = bq[jj];
-    if (d) d[j] = dq[jj];
-  }
-}
-__global__ void k_em_fix_xx(float *xx, int64_t p) {                                   // if(xx[k]==0) xx[k]=0.1f, :261
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < p; j += (int64_t)gridDim.x * blockDim.x) if (xx[j] == 0.0f) xx[j] = 0.1f;
-}
-__global__ void k_em_init(const float *__restrict__ y, double *__restrict__ e, int n, int64_t ld, EmState *st) {
-  // mu = y.mean(); e = y.array()-mu  (float), :98-99; padding rows of e stay 0
-  __shared__ double sh[1024];
-  double s = 0;
-  for (int i = threadIdx.x; i < n; i += 1024) s += (double)y[i];
-  sh[threadIdx.x] = s; __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o]; __syncthreads(); }
-  const float mu = (float)(sh[0] / (double)n);
-  for (int64_t i = threadIdx.x; i < ld; i += 1024) e[i] = i < n ? (double)(y[i] - mu) : 0.0;
-  if (threadIdx.x == 0) st->mu = mu;
-}
-
-struct EmTailArgs {
-  int model, n, conv; int64_t p;
-  double *e; const float *y; const float *b; const float *bc; const float *d; float *lam; float *vbv; const float *xx;
-  EmState *st; ChainScalars *sc;
-};
-
-__device__ double em_block_sum(double v, double *sh) {
-  __syncthreads();
-  sh[threadIdx.x] = v; __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o]; __syncthreads(); }
-  return sh[0];
-}
-
-// what follows a sweep, one workgroup: the model's variance components and lambda, then eM = e.mean(); mu += eM; e -= eM;
-// last, the scalars the next sweep's kernels read (C, Pi0, Lmb1) are refreshed in the ChainScalars block
-__global__ __launch_bounds__(1024) void k_em_tail(const EmTailArgs a) {
-  __shared__ double sh[1024];
-  EmState st = *a.st;
-  const int n = a.n; const int64_t p = a.p; const int tid = threadIdx.x; const int model = a.model;
-  const float df = st.df;
-  float b2n = 0, e2n = 0, dmean = 0;
-  if (model == BWGR_EM_RR || model == BWGR_EM_BC || model == BWGR_EM_BCPI || model == BWGR_EM_EN) {
-    double s = 0; for (int64_t j = tid; j < p; j += 1024) s = fma((double)a.b[j], (double)a.b[j], s);
-    b2n = (float)em_block_sum(s, sh);                                                // b.squaredNorm()
-  }
-  if (model == BWGR_EM_BC || model == BWGR_EM_BCPI) {
-    double s = 0; for (int64_t j = tid; j < p; j += 1024) s += (double)a.d[j];
-    dmean = (float)(em_block_sum(s, sh) / (double)p);                                // d.mean()
-  }
-  if (model == BWGR_EM_BA || model == BWGR_EM_BB || model == BWGR_EM_RR || model == BWGR_EM_BC || model == BWGR_EM_BCPI) {
-    double s = 0; for (int i = tid; i < n; i += 1024) s = fma(a.e[i], a.e[i], s);
-    e2n = (float)em_block_sum(s, sh);                                                // e.squaredNorm() (before centring)
-  }
-  if (model == BWGR_EM_BA || model == BWGR_EM_BB) {
-    st.ve = (e2n + st.Se) / ((float)n + df);                                         // :113, :170
-    for (int64_t j = tid; j < p; j += 1024) {
-      const float bj = a.b[j];
-      const float vbj = (st.Sb + bj * bj) / (df + 1);                                // :110, :167
-      a.vbv[j] = vbj;
-      a.lam[j] = st.ve * (1.0f / vbj);                                               // Lmb = ve * vb.cwiseInverse(), :114, :171
-    }
-  } else if (model == BWGR_EM_RR) {
-    st.vb = (b2n + st.Sb) / ((float)p + df);                                         // :338
-    st.ve = (e2n + st.Se) / ((float)n + df);                                         // :339
-    st.Lmb = sqrtf(st.Rho * st.ve / st.vb);                                          // :340
-  } else if (model == BWGR_EM_BC) {
-    st.ve = (e2n + st.Se) / ((float)n + df);                                         // :229
-    st.va = (b2n + st.Sa) / ((float)p + df) / (dmean - st.Pi);                       // :230
-    st.Lmb = st.ve / st.va;                                                          // :231
-  } else if (model == BWGR_EM_BCPI) {
-    st.Pi = ((1.0f - dmean) * (float)p + st.PriorPi * df) / ((float)p + df);         // :1533
-    st.Pi0 = (1.0f - st.Pi) / st.Pi;                                                 // :1534
-    st.MSx = st.sumvx * st.Pi * (1.0f - st.Pi);                                      // :1535
-    st.Sa = st.R2 * (df + 2) * st.vy / st.MSx;                                       // :1536
-    st.ve = (e2n + st.Se) / ((float)n + df);                                         // :1538
-    st.va = (b2n + st.Sa) / ((float)p + df) / (dmean - st.Pi);                       // :1539
-    st.Lmb = st.ve / st.va;                                                          // :1540
-  }
-  {
-    double s = 0; for (int i = tid; i < n; i += 1024) s += a.e[i];
-    const float eM = (float)(em_block_sum(s, sh) / (double)n);                       // :115-117
-    st.mu += eM;
-    for (int i = tid; i < n; i += 1024) a.e[i] = a.e[i] - (double)eM;
-    __syncthreads();
-  }
-  if (model == BWGR_EM_DE || model == BWGR_EM_EN) {
-    double s = 0; for (int i = tid; i < n; i += 1024) s = fma(a.e[i], (double)a.y[i], s);
-    st.ve = (float)em_block_sum(s, sh) / (float)(n - 1);                             // Ve = e.dot(y)/(n-1), :289, :445
-  }
-  if (model == BWGR_EM_DE) {
-    for (int64_t j = tid; j < p; j += 1024) {
-      const float bj = a.b[j];
-      const float vbj = bj * bj + st.ve / (a.xx[j] + a.lam[j] + 0.0001f);            // :290
-      a.vbv[j] = vbj;
-      a.lam[j] = sqrtf(st.cxx * st.ve / vbj);                                        // :292
-    }
-  } else if (model == BWGR_EM_EN) {
-    st.va = (b2n + st.trAC22 * st.ve) / (float)p;                                    // :446
-    st.Lmb = st.ve / st.va;                                                          // :447
-    st.Lmb1 = 0.5f * st.Lmb * st.alpha * st.Sy;                                      // :448
-    st.Lmb2 = st.Lmb * (1 - st.alpha);                                               // :449
-  } else if (model == BWGR_EM_ML) {
-    double s1 = 0, s2 = 0;
-    for (int i = tid; i < n; i += 1024) {
-      const float ym = a.y[i] - st.mu;
-      s1 = fma((double)ym, a.e[i], s1);                                              // :505
-      s2 = fma((double)ym, (double)ym - a.e[i], s2);                                 // :506
-    }
-    const float d1 = (float)em_block_sum(s1, sh), d2 = (float)em_block_sum(s2, sh);
-    st.ve = d1 / (float)n;
-    st.vb = d2 / (float)((float)n * st.MSx);
-    st.Lmb = st.ve / st.vb;                                                          // :507
-  }
-  if (a.conv) {
-    double s = 0; for (int64_t j = tid; j < p; j += 1024) s += (double)fabsf(a.bc[j] - a.b[j]);
-    st.cnv = (float)em_block_sum(s, sh);                                             // :295, :451, :509
-  }
-  if (tid == 0) {
-    *a.st = st;
-    a.sc->C = -0.5f / sqrtf(st.ve);                                                  // C of the next sweep, :157, :216, :1522
-    a.sc->odds = st.Pi0;
-    a.sc->lam = st.Lmb1;
-  }
-}
-
-__global__ void k_em_fit_ml(const float *__restrict__ y, const double *__restrict__ e, float *__restrict__ hat, int n) {   // fit = y - e, :512
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) hat[i] = (float)((double)y[i] - e[i]);
-}
-
-}  // namespace
-
-// the marker order of sweep `upto` (0-based): identity shuffled with std::mt19937(0), (1), ..., (upto) -- the library's own
-// std::shuffle, so that the oracle's restatement of it can be pinned (tests/test_em_order.py)
-extern "C" int bwgr_em_order(int64_t p, int upto, int32_t *order) {
-  if (!order || p < 1 || p > 0x7FFFFF00ll) return fail(BWGR_EINVAL, "em_order: bad arguments");
-  CumulativeOrder ord((size_t)p);
-  for (int i = 0; i <= upto; ++i) ord.next(i);
-  std::copy(ord.current().begin(), ord.current().end(), order);
-  return BWGR_OK;
-}
-
-extern "C" int bwgr_em(bwgr_panel *P, int model, const float *y, float df, float R2, float par, const float *D, int maxit_in,
-                       float *mu, float *b, float *d, float *hat, float *vbvec, float *scal, int *iters) {
-  if (P && P->data->cen) return refuse_centred("em");
-  if (!P || !y || !b || !scal) return fail(BWGR_EINVAL, "em: null pointer");
-  if (model < BWGR_EM_RR || model > BWGR_EM_LASSO) return fail(BWGR_EINVAL, "em: bad model %d", model);
-  if (D && model != BWGR_EM_ML) return fail(BWGR_EINVAL, "em: marker weights D belong to emML only");
-  const bool soft = (model == BWGR_EM_BB || model == BWGR_EM_BC || model == BWGR_EM_BCPI);
-  const bool lasso = (model == BWGR_EM_LASSO);
-  const bool nonaffine = soft || lasso || model == BWGR_EM_BL || model == BWGR_EM_EN;
-  if (nonaffine && !P->data->plan.pipelined) return fail(BWGR_EINVAL, "em: this member needs the pipelined sweep engine (k_sweep2), which this panel's geometry does not fit");
-  HIPCHK(hipSetDevice(P->data->device));
-  const int64_t p = P->data->p, n = P->data->n;
-  const bool conv = (model == BWGR_EM_DE || model == BWGR_EM_ML || model == BWGR_EM_EN || lasso);
-  const bool shuffled = (model != BWGR_EM_BCPI && !lasso);                            // emBCpi and lasso sweep in natural order, :1523, :1476
-  const int maxit = maxit_in > 0 ? maxit_in : (conv ? 300 : 200);                     // :81, :251, :309, :401, :465
-  const float tol = (model == BWGR_EM_DE) ? 10e-6f : (model == BWGR_EM_EN) ? 10e-11f : 10e-8f;   // :252, :402, :466
-  hipStream_t st = P->stream;
-  // scratch panel: same geometry, its own X and Gram; only the diagonal and distance-1 blocks are ever built (lag 2, 32-bit staging)
-  bwgr_panel *Q = nullptr;
-  Guard drop([&] { bwgr_panel_destroy(Q); });
-  CumulativeOrder cum((size_t)p);
-  std::vector<int> order = cum.current(), order_next;   // (copied from asynchronously: declared before the holder, which waits for the stream)
-  DevBufs bufs(st);
-  if (shuffled) {
-    CHK(scratch_panel_alloc(&Q, P, n, P->data->plan.K, PANEL_EM));
-    if (Q->data->plan.K != P->data->plan.K || Q->data->plan.R != P->data->plan.R || Q->data->plan.m != P->data->plan.m || Q->data->plan.pipelined != P->data->plan.pipelined) return fail(BWGR_EINVAL, "em: scratch panel geometry differs");
-    CHK(scratch_alloc(Q));
-  }
-  bwgr_panel *S = Q ? Q : P;                                                          // the panel the sweeps run on
-  const size_t np = (size_t)p, pb = sizeof(float) * np;
-  float *yd = bufs.get<float>((size_t)n), *bd = bufs.get<float>(np), *bcd = bufs.get<float>(np), *dd = bufs.get<float>(np);
-  float *lamd = bufs.get<float>(np), *vbd = bufs.get<float>(np), *xxd = bufs.get<float>(np);
-  float *bq = bufs.get<float>(np), *xxq = bufs.get<float>(np), *lamq = bufs.get<float>(np), *dq = bufs.get<float>(np), *vq = bufs.get<float>(np);
-  double *ed = bufs.get<double>((size_t)P->data->plan.ld); int32_t *ordd = bufs.get<int32_t>(np);
-  EmState *std_ = bufs.get<EmState>(1); ChainScalars *sc = bufs.get<ChainScalars>(1);
-  float *hatd = bufs.get<float>((size_t)n), *Dd = D ? bufs.get<float>(np) : nullptr;
-  if (!yd || !bd || !bcd || !dd || !lamd || !vbd || !xxd || !bq || !xxq || !lamq || !dq || !vq || !ed || !ordd || !std_ || !sc || !hatd || (D && !Dd))
-    return fail(BWGR_ENOMEM, "em: device allocation failed");
-  if (D) HIPCHK(hipMemcpyAsync(Dd, D, pb, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(yd, y, sizeof(float) * n, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(bd, 0, pb, st)); HIPCHK(hipMemsetAsync(dd, 0, pb, st));
-  HIPCHK(hipMemcpyAsync(xxd, P->data->xx, pb, hipMemcpyDeviceToDevice, st));
-  // vy = fvar(y) with the library's reduction (float result of fp64 sums, like the fused samplers' setup)
-  float vy = 0;
-  {
-    InitArgs ia; memset(&ia, 0, sizeof(ia));
-    ChainScalars h0; memset(&h0, 0, sizeof(h0));
-    HIPCHK(hipMemcpyAsync(sc, &h0, sizeof(h0), hipMemcpyHostToDevice, st));
-    ia.y = yd; ia.e = ed; ia.n = (int)n; ia.p = (int)p; ia.ld = P->data->plan.ld; ia.model = BWGR_BAYESRR; ia.pi = 0; ia.df = df; ia.R2 = R2; ia.MSx = P->data->MSx; ia.sc = sc;
-    hipLaunchKernelGGL(k_chain_init, dim3(1), dim3(1024), 0, st, ia);
-    HIPCHK(hipGetLastError());
-    HIPCHK(d2h(st, &h0, sc, sizeof(h0)));
-    vy = h0.vy;
-  }
-  const float sumvx = P->data->MSx;                                                        // vx.sum()
-  EmState h; memset(&h, 0, sizeof(h));
-  h.df = df; h.vy = vy; h.MSx = sumvx; h.sumvx = sumvx; h.R2 = R2; h.ve = 1.0f;
-  std::vector<float> hostv, xxh, yxh, bh;
-  auto fill = [&](float *dst, float v) { hostv.assign((size_t)p, v); hipError_t e_ = hipMemcpyAsync(dst, hostv.data(), pb, hipMemcpyHostToDevice, st); return e_ != hipSuccess ? e_ : hipStreamSynchronize(st); };
-  if (model == BWGR_EM_BA || model == BWGR_EM_BB) {
-    h.ve = 1;                                                                        // :84, :135
-    if (model == BWGR_EM_BB) {
-      float Pi = par; if (Pi > 0.5f) Pi = 1 - Pi;                                    // :141
-      h.Pi = Pi; h.MSx = sumvx * Pi;                                                 // :147
-      h.Pi0 = (1 - Pi) / Pi;                                                         // :154
-    }
-    h.Sb = R2 * (df + 2) * vy / h.MSx;                                               // :96, :148
-    h.Se = (1 - R2) * (df + 2) * vy;                                                 // :97, :149
-    HIPCHK(fill(lamd, 1.0f)); HIPCHK(fill(vbd, 1.0f));                               // vb = 1, Lmb = ve * vb^-1 = 1, :87-88
-  } else if (model == BWGR_EM_RR) {
-    h.Lmb = sumvx;                                                                   // :319
-    h.Rho = sumvx * (1 - R2) / R2;                                                   // :320
-    h.ve = 0.5f * vy;                                                                // :322
-    h.vb = h.ve / sumvx;                                                             // :323
-    h.Se = (1 - R2) * (df + 2) * vy;                                                 // :324
-    h.Sb = R2 * (df + 2) * vy / sumvx;                                               // :325
-  } else if (model == BWGR_EM_DE) {
-    hipLaunchKernelGGL(k_em_fix_xx, dim3(1024), dim3(256), 0, st, xxd, p);           // :261
-    h.cxx = sumvx * (1 - R2) / R2;                                                   // :265
-    HIPCHK(fill(lamd, (float)p + h.cxx));                                            // :269
-  } else if (model == BWGR_EM_ML) {
-    h.Lmb = sumvx;                                                                   // :486
-  } else if (model == BWGR_EM_BC || model == BWGR_EM_BCPI) {
-    float Pi = par; if (Pi > 0.5f) Pi = 1 - Pi;                                      // :197, :1508
-    h.Pi = Pi; h.PriorPi = Pi;                                                       // :1511
-    h.MSx = sumvx * Pi * (1 - Pi);                                                   // :203, :1512
-    h.Sa = R2 * (df + 2) * vy / h.MSx;                                               // :204
-    h.Se = (1 - R2) * (df + 2) * vy;                                                 // :205
-    h.ve = h.Sa; h.va = h.Se; h.Lmb = h.ve / h.va;                                   // :209-211 (sic)
-    h.Pi0 = (1 - Pi) / Pi;                                                           // :213
-  } else if (model == BWGR_EM_BL || model == BWGR_EM_EN || lasso) {
-    xxh.resize((size_t)p);
-    HIPCHK(d2h(st, xxh.data(), xxd, pb));
-    h.alpha = par;
-    if (lasso) {
-      double sx = 0; for (int64_t j = 0; j < p; ++j) sx += (double)xxh[(size_t)j];
-      h.Lmb1 = (float)(sx / (double)p) / (float)p;                                   // Lmb = xx.mean()/p, :1472
-    } else if (model == BWGR_EM_BL) {
-      double sx = 0; for (int64_t j = 0; j < p; ++j) sx += (double)xxh[(size_t)j];
-      h.cxx = (float)(sx / (double)p);                                               // xx.mean(), :368
-      const float hh = R2;                                                           // h2 = R2, :359
-      h.Lmb1 = h.cxx * ((1 - hh) / hh) * h.alpha * 0.5f;                             // :369
-      h.Lmb2 = h.cxx * ((1 - hh) / hh) * (1 - h.alpha);                              // :370
-    } else {
-      h.cxx = sumvx * (1 - R2) / R2;                                                 // :412
-      h.Sy = sqrtf(vy);                                                              // :414
-      h.Lmb = h.cxx;                                                                 // :415
-      h.Lmb1 = 0.5f * h.Lmb * h.alpha * h.Sy;                                        // :416
-      h.Lmb2 = h.Lmb * (1 - h.alpha);                                                // :417
-      float tr = 0; for (int64_t k = 0; k < p; ++k) tr += 1.0f / (xxh[(size_t)k] + h.Lmb);   // the reference's own float loop, :418-419
-      h.trAC22 = tr;
-    }
-  }
-  HIPCHK(hipMemcpyAsync(std_, &h, sizeof(h), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_em_init, dim3(1), dim3(1024), 0, st, yd, ed, (int)n, P->data->plan.ld, std_);   // mu, e (overwrites k_chain_init's e)
-  HIPCHK(hipGetLastError());
-  {
-    ChainScalars h0; memset(&h0, 0, sizeof(h0));
-    h0.ve = 1.0f; h0.pi = 0.0f; h0.dfp1 = 1.0f;                                      // the sweep's variates are switched off
-    h0.C = -0.5f / sqrtf(h.ve);                                                      // :157, :216, :1522
-    h0.odds = h.Pi0; h0.lam = h.Lmb1; h0.Sb = h.cxx;                                 // Pi0; Lmb1; emBL's cxx (k_prestage)
-    HIPCHK(hipMemcpyAsync(sc, &h0, sizeof(h0), hipMemcpyHostToDevice, st));
-  }
-  if (shuffled) order = cum.next(0);                                                  // sweep 0's order
-  if (!shuffled) HIPCHK(hipMemcpyAsync(ordd, order.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice, st));
-  const int cps = (int)((size_t)P->data->plan.R * (P->data->is_f32 ? 4 : 1) / 16);
-  uint32_t flags = SWF_LAM_VEC;
-  if (model == BWGR_EM_BA) flags |= SWF_DELTA2;
-  if (soft) flags |= SWF_EM_SEL;
-  if (model == BWGR_EM_EN) flags |= SWF_EM_EN;
-  if (model == BWGR_EM_BL) flags |= SWF_EM_BL;
-  if (lasso) flags |= SWF_EM_LASSO;
-  int numit = 0;
-  const bool emdbg = P->data->sw.em_debug;
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  for (int i = 0; i < maxit; ++i) {
-    const double t_0 = now();
-    if (shuffled) {
-      // order = sweep i's marker order.  std::shuffle(order.begin(), order.end(), std::mt19937(i)) -- :103, :277, :331, :491 ...,
-      // the reference's own call -- was made for sweep 0 before the loop and is made for sweep i+1 below, while the GPU
-      // runs sweep i (10-15 ms of host time per sweep at p = 10^6)
-      HIPCHK(hipMemcpyAsync(ordd, order.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)P->data->X, (uint4 *)Q->data->X, ordd, p, P->data->plan.K, cps);
-    }
-    if (conv) HIPCHK(hipMemcpyAsync(bcd, bd, pb, hipMemcpyDeviceToDevice, st));      // bc = b
-    hipLaunchKernelGGL(k_em_stage, dim3(1024), dim3(256), 0, st, ordd, p, model, D ? 1 : 0, bd, xxd, lamd, Dd, std_, bq, xxq, lamq);
-    HIPCHK(hipGetLastError());
-    if (shuffled) CHK(panel_build_gram(Q));
-    SweepArgs a; memset(&a, 0, sizeof(a));
-    fill_panel_args(S, a);
-    a.flags = flags;
-    a.e = ed; a.b = bq; a.d = dq; a.vb = vq; a.xx = xxq; a.lam = lamq; a.sc = sc;
-    a.iter = (uint32_t)i; a.rng = make_rng(0, BWGR_RNG_DEGENERATE);
-    CHK(launch_sweep(S, a));
-    hipLaunchKernelGGL(k_em_unstage, dim3(1024), dim3(256), 0, st, ordd, p, bq, bd, (soft || lasso) ? dq : nullptr, (soft || lasso) ? dd : nullptr);
-    EmTailArgs t; t.model = model; t.n = (int)n; t.conv = conv ? 1 : 0; t.p = p; t.e = ed; t.y = yd; t.b = bd; t.bc = bcd; t.d = dd;
-    t.lam = lamd; t.vbv = vbd; t.xx = xxd; t.st = std_; t.sc = sc;
-    hipLaunchKernelGGL(k_em_tail, dim3(1), dim3(1024), 0, st, t);
-    HIPCHK(hipGetLastError());
-    ++numit;
-    const double t_1 = now();
-    if (shuffled && i + 1 < maxit) order_next = cum.next(i + 1);
-    const double t_2 = now();
-    // the convergence test needs cnv (and the sweep's status word)
-    ChainScalars hc;
-    HIPCHK(hipMemcpyAsync(&h, std_, sizeof(h), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&hc, sc, sizeof(hc), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (emdbg) fprintf(stderr, "em sweep %d: launches %.2f ms, host shuffle %.2f ms, wait %.2f ms\n", i, t_1 - t_0, t_2 - t_1, now() - t_2);
-    if (hc.error) return sweep_error(hc.error, "em");
-    if (lasso) {   // Lmb from the sweep's yx and b: the reference's own sequential float loop, :1487-1490
-      yxh.resize((size_t)p); bh.resize((size_t)p);
-      HIPCHK(d2h(st, yxh.data(), dd, pb)); HIPCHK(d2h(st, bh.data(), bd, pb));
-      float tmp = 0.0f;
-      for (int64_t j = 0; j < p; ++j) tmp += fabsf(yxh[(size_t)j]) - fabsf(bh[(size_t)j] * xxh[(size_t)j]);
-      float L = 2.0f * tmp / (float)p;
-      L = 2.0f * sqrtf(fabsf(L));
-      h.Lmb1 = L;
-      HIPCHK(hipMemcpyAsync(std_, &h, sizeof(h), hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(&sc->lam, &h.Lmb1, sizeof(float), hipMemcpyHostToDevice, st));
-      HIPCHK(hipStreamSynchronize(st));
-    }
-    if (conv && h.cnv < tol) break;                                                  // :296, :452, :510, :1492
-    if (shuffled) order.swap(order_next);
-  }
-  float h2;
-  if (model == BWGR_EM_ML) {
-    hipLaunchKernelGGL(k_em_fit_ml, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, yd, ed, hatd, (int)n);
-    h2 = h.vb * h.MSx / (h.vb * h.MSx + h.ve);                                       // :513
-  } else if (lasso) {
-    hipLaunchKernelGGL(k_em_fit_ml, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, yd, ed, hatd, (int)n);   // fit = y - e, :1493
-    std::vector<double> eh((size_t)n);
-    HIPCHK(d2h(st, eh.data(), ed, sizeof(double) * n));
-    double s = 0; for (int64_t k = 0; k < n; ++k) s = fma(eh[(size_t)k], (double)y[k], s);
-    h2 = 1.0f - ((float)s / (float)(n - 1)) / vy;                                    // :1494
-  } else {
-    CHK(gemv_hat<float>(P, bd, h.mu, hatd, "em"));                                   // fit = gen*b + mu, :120-121
-    if (model == BWGR_EM_DE) {                                                       // h2 = Vb.sum()/(Vb.sum()+Ve), :304
-      double *part = bufs.get<double>(256); float *sdev = bufs.get<float>(1); float sv = 0;
-      if (!part || !sdev) return fail(BWGR_ENOMEM, "em: device allocation failed");
-      CHK(sum_floats(st, vbd, p, part, sdev, &sv));
-      h2 = sv / (sv + h.ve);
-    } else if (model == BWGR_EM_BL) {                                                // h2 = 1 - fvar(e)/fvar(y), :396
-      std::vector<double> eh((size_t)n);
-      HIPCHK(d2h(st, eh.data(), ed, sizeof(double) * n));
-      double s = 0; for (int64_t k = 0; k < n; ++k) s += (double)(float)eh[(size_t)k];
-      const float m = (float)(s / (double)n);
-      double sv = 0; for (int64_t k = 0; k < n; ++k) { const float dev = (float)eh[(size_t)k] - m; const float sq = dev * dev; sv += (double)sq; }
-      h2 = 1 - (float)(sv / (double)(float)(n - 1)) / vy;
-    } else if (model == BWGR_EM_EN) h2 = h.va * h.cxx / (h.va * h.cxx + h.ve);       // :459
-    else h2 = 1 - h.ve / vy;                                                         // :119, :178, :237, :344, :1542
-  }
-  HIPCHK(hipGetLastError());
-  if (mu) *mu = h.mu;
-  HIPCHK(d2h(st, b, bd, pb));
-  if (d && soft) HIPCHK(d2h(st, d, dd, pb));
-  if (hat) HIPCHK(d2h(st, hat, hatd, sizeof(float) * n));
-  if (vbvec && (model == BWGR_EM_BA || model == BWGR_EM_DE || model == BWGR_EM_BB)) HIPCHK(d2h(st, vbvec, vbd, pb));
-  for (int k = 0; k < 6; ++k) scal[k] = 0.0f;
-  scal[1] = h.ve; scal[2] = h2;
-  if (model == BWGR_EM_RR || model == BWGR_EM_ML) scal[0] = h.vb;
-  if (model == BWGR_EM_ML) scal[3] = h.vb * h.MSx;                                   // Va = vb*MSx, :519
-  if (model == BWGR_EM_BC || model == BWGR_EM_BCPI) { scal[0] = h.va; scal[3] = h.va * h.MSx; }   // Va, Vg = va*MSx, :243, :1547
-  if (model == BWGR_EM_BCPI) scal[4] = h.Pi;
-  if (model == BWGR_EM_EN) scal[0] = h.va * h.cxx;                                   // :457
-  if (model == BWGR_EM_BL) scal[1] = 0.0f;
-  if (lasso) { scal[0] = h.Lmb1; scal[1] = 0.0f; }                                   // Lmb, :1497
-  if (iters) *iters = numit;
-  return BWGR_OK;
-}
-
+#include "samplers_host.hip.h"
+#include "wgr_em_host.hip.h"
+#include "group_host.hip.h"
 #include "fits_host.hip.h"
 
 // ------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // bwgr_amd/csrc/fits_host.hip.h -- the host entries of the fp64 fits and products on a resident int8 panel: mrr, the UVBETA family with
 // solver2x, the dense fits, X B, and the relationship kernels.  Part of bwgr_hip.hip, which includes it after everything it uses (fail, HIPCHK,
-// DevBufs, no_memory, d2h / h2d / zero, Guard, guard_busy, k_permute_cols); it defines no kernel.  What these entries do to Y and Z before a
-// kernel runs is traits.h.
+// DevBufs, no_memory, d2h / h2d / zero, Guard, guard_busy); it defines no kernel.  What these entries do to Y and Z before a kernel runs is
+// traits.h.
 // ------------------------------------------------------------------------------------------------
 // mrr / mrr_float (MRR3 / MRR3F, src/RcppEigen20230423.cpp:318-1080): the engine of mrr.hip.h as a per-block launch train
 //   per sweep:  order (host std::shuffle, cumulative) -> k_permute_cols -> k_mrr_gram -> k_mrr_linv ->
