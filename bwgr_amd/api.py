@@ -1061,6 +1061,125 @@ def mrr_float(Y, X, **kw):
     return MRR3F(Y, X, **kw)
 
 
+# ---- PEGS / PEGSZ: multi-trait fits over several designs (bwgr_pegs, include/bwgr.h) ----
+PEGS_KEYS = ("mu", "b", "hat", "h2", "GC", "bend", "numit", "cnv")
+
+
+class dense:
+    """Marks a matrix as a dense effect of PEGS / PEGSZ: dense(Z) is swept as n x q float64 values by the dense leg, whatever it holds.
+    Without the marker a Panel, an int8 or integer matrix and an integer-valued float matrix within int8 range are panel effects (staged as
+    int8, as mrr stages its X), and a float matrix with a non-integer value is a dense effect."""
+
+    def __init__(self, Z):
+        Zm = np.asarray(Z, np.float64)
+        if Zm.ndim == 1:
+            Zm = Zm[:, None]
+        if Zm.ndim != 2:
+            raise BwgrError(1, "dense: Z has shape %s; it must be n x q" % (Zm.shape,))
+        self.Z = np.asfortranarray(Zm)
+
+
+def pegs_plan(n, q, k):
+    """bwgr_debug_pegs_plan (host arithmetic, no GPU): dict(threads, lds_bytes, ws_bytes) of the dense leg."""
+    out = (C.c_int64 * 3)()
+    check(_lib.lib().bwgr_debug_pegs_plan(int(n), int(q), int(k), out))
+    return dict(zip(("threads", "lds_bytes", "ws_bytes"), [int(v) for v in out]))
+
+
+def _pegs_effect(X, panel_kw):
+    """(Panel, made here) or (dense, False): the rule of `dense`'s docstring."""
+    if isinstance(X, Panel):
+        return X, False
+    if isinstance(X, dense):
+        return X, False
+    if hasattr(X, "data_ptr"):
+        return Panel(X, **panel_kw), True
+    Xm = np.asarray(X)
+    if Xm.ndim == 1:
+        Xm = Xm[:, None]
+    if Xm.ndim != 2:
+        raise BwgrError(1, "pegs: an effect has shape %s; it must be n x p" % (Xm.shape,))
+    if np.issubdtype(Xm.dtype, np.integer) or Xm.dtype == np.bool_:
+        return Panel(Xm, **panel_kw), True
+    Xm = Xm.astype(np.float64, copy=False)
+    if Xm.size and np.all(np.isfinite(Xm)) and np.all(Xm == np.rint(Xm)) and Xm.min() >= -128 and Xm.max() <= 127:
+        return Panel(Xm, as_int8=True, **panel_kw), True
+    return dense(Xm), False
+
+
+def _pegs(Y, X_list, maxit, logtol, covbend, covMinEv, XFA, NNC, own_text, device, cnv_trace, panel_kw):
+    effs, made = [], []
+    try:
+        for X in X_list:
+            E, own = _pegs_effect(X, dict(panel_kw, device=device))
+            effs.append(E)
+            if own:
+                made.append(E)
+        if not effs:
+            raise BwgrError(1, "pegs: X_list holds no effects")
+        Ym = np.asarray(Y, np.float64)
+        if Ym.ndim == 1:
+            Ym = Ym[:, None]
+        Ym = Ym.astype(np.float32).astype(np.float64)   # PEGS receives float matrices (src/RcppEigenX20251203.cpp:10)
+        rows = [E.n if isinstance(E, Panel) else E.Z.shape[0] for E in effs]
+        n = rows[0]
+        if any(r != n for r in rows):
+            raise BwgrError(1, "pegs: the effects have %s rows; all must have the same" % (rows,))
+        if Ym.ndim != 2 or Ym.shape[0] != n:
+            raise BwgrError(1, "pegs: Y has shape %s; nrow(Y) must equal nrow(X) = %d" % (Ym.shape, n))
+        k = Ym.shape[1]
+        Yf = np.asfortranarray(Ym)
+        neff, kk = len(effs), max(k, 1)
+
+        class _Eff(C.Structure):
+            _fields_ = [("panel", C.c_void_p), ("Z", C.c_void_p), ("q", C.c_int64), ("ldz", C.c_int64)]
+        ce = (_Eff * neff)()
+        ps = []
+        for i, E in enumerate(effs):
+            if isinstance(E, Panel):
+                ce[i].panel = E._h.value; ce[i].Z = None; ce[i].q = 0; ce[i].ldz = 0
+                ps.append(E.p)
+            else:
+                ce[i].panel = None; ce[i].Z = E.Z.ctypes.data; ce[i].q = E.Z.shape[1]; ce[i].ldz = max(E.Z.shape[0], 1)
+                ps.append(E.Z.shape[1])
+        f32 = lambda v: float(np.float32(v))   # the real options are floats there
+        mu = np.zeros(kk); hat = np.zeros((n, kk), order="F"); h2 = np.zeros(kk); bend = np.zeros(neff)
+        b = [np.zeros((p_, kk), order="F") for p_ in ps]; GC = [np.zeros((kk, kk), order="F") for _ in ps]
+        bp = (C.c_void_p * neff)(*[a.ctypes.data for a in b]); gp = (C.c_void_p * neff)(*[a.ctypes.data for a in GC])
+        cnv = np.zeros(max(int(maxit), 1)); its = C.c_int()
+        check(_lib.lib().bwgr_pegs(int(device), C.cast(ce, C.c_void_p), neff, _dp(Yf), int(n), int(k), int(maxit), f32(logtol), f32(covbend), f32(covMinEv),
+                                   int(XFA), int(bool(NNC)), int(own_text), _dp(mu), C.cast(bp, C.c_void_p), _dp(hat), _dp(h2), C.cast(gp, C.c_void_p),
+                                   _dp(bend), C.byref(its), _dp(cnv)))
+        nit = int(its.value)
+        out = dict(zip(PEGS_KEYS, (mu, b, hat, h2, GC, bend, nit, float(cnv[max(nit, 1) - 1]))))
+        if cnv_trace:
+            out["cnv_trace"] = cnv[:nit].copy()
+        return out
+    finally:
+        for P in made:
+            P.close()
+
+
+def PEGS(Y, X, maxit=100, logtol=-4.0, covbend=1.1, covMinEv=10e-4, XFA=-1, NNC=True, *, device=0, cnv_trace=False, **kw):
+    """PEGS(Y, X, ...), src/RcppEigenX20251203.cpp:10-194 (R/RcppExports.R:280): the pseudo-expectation Gauss-Seidel fit of k correlated
+    traits (NaN in Y = missing) on one design, which is NOT centred.  list(mu, b, hat, h2, GC, bend, numit, cnv) as a dict; b is p x k, GC k x k
+    and bend a number.  X is an effect as `dense` describes.  Y and the real options are rounded to float as the reference receives them;
+    the engine is fp64.  The marker order of sweep s is em_order(p, s) (the reference's order is seeded from the machine and cannot be
+    reproduced).  cnv_trace=True adds "cnv_trace", cnv after every sweep."""
+    r = _pegs(Y, [X], maxit, logtol, covbend, covMinEv, XFA, NNC, 1, device, cnv_trace, kw)
+    r["b"], r["GC"], r["bend"] = r["b"][0], r["GC"][0], float(r["bend"][0])
+    return r
+
+
+def PEGSZ(Y, X_list, maxit=100, logtol=-4.0, covbend=1.1, covMinEv=10e-4, XFA=-1, NNC=True, *, device=0, cnv_trace=False, **kw):
+    """PEGSZ(Y, X_list, ...), src/RcppEigenX20251203.cpp:576-808 (R/RcppExports.R:288): PEGS over a list of designs, swept one after another
+    in list order against one residual, each with its own k x k covariance.  Every element of X_list is an effect as `dense` describes: a
+    Panel / integer matrix (int8 genotypes on the device) or a dense float matrix / dense(Z); all have the same n, all panels live on one
+    device and are made with the same block / nwg.  device= matters only when no effect is a panel.  Returns PEGS's dict with b and GC as
+    lists (one entry per effect) and bend as a vector."""
+    return _pegs(Y, list(X_list), maxit, logtol, covbend, covMinEv, XFA, NNC, 0, device, cnv_trace, kw)
+
+
 # ---- per-trait ridge fits: solver1x / UVBETA, solver1xF / FUVBETA, XFUVBETA, ZFUVBETA (bwgr_uvbeta, include/bwgr.h) ----
 UVB_VARIANTS = {"D": 0, "F": 1, "X": 2, "Z": 3}   # BWGR_UVB_*
 UVB_KEYS = ("b", "mu", "h2", "ve", "vb", "its", "cnv")

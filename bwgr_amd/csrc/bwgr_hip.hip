@@ -30,6 +30,7 @@
 #include "uvb.hip.h"
 #include "uvbd.hip.h"
 #include "uvb2.hip.h"
+#include "pegs.hip.h"
 #include "kernels.hip.h"
 #include <stdlib.h>
 
@@ -1456,6 +1457,7 @@ extern "C" int bwgr_panel_centred(bwgr_panel *P, int *centred) {
 #include "wgr_em_host.hip.h"
 #include "group_host.hip.h"
 #include "fits_host.hip.h"
+#include "pegs_host.hip.h"
 
 // ------------------------------------------------------------------------------------------------
 // synthetic data and test hooks

@@ -7,6 +7,7 @@
 //   per sweep:  order (host std::shuffle, cumulative) -> k_permute_cols -> k_mrr_gram -> k_mrr_linv ->
 //               [k_mrr_pass(b-1 | b), k_mrr_solve(b)] for every block -> k_mrr_pass(last | -) -> k_mrr_ey -> (host: ve) ->
 //               k_mrr_tilde -> (host: vb, GC, bending, pinv) -> k_mrr_mu_shift (updateMu)
+// The sweep itself (order .. closing pass) is mrr_sweep, which bwgr_pegs (pegs_host.hip.h) runs once per panel effect as well.
 // ------------------------------------------------------------------------------------------------
 // The LDS plan of k_mrr_solve and k_mrr_linv for k traits and npat missingness patterns, decided here and nowhere else: the solve stages
 // the markers' k x k inverses (64 k^2 doubles) when they fit beside its fixed arrays, then as many of the block's per-pattern Gram matrices
@@ -36,6 +37,57 @@ extern "C" int bwgr_debug_mrr_plan(int k, int npat, int *linv_lds, int *ngl, int
   if (ngl) *ngl = pl.ngl;
   if (solve_lds_bytes) *solve_lds_bytes = (int64_t)pl.lds_solve;
   if (linv_lds_bytes) *linv_lds_bytes = (int64_t)pl.lds_linv;
+  return BWGR_OK;
+}
+
+// One design's share of a sweep (:866-902): what its launch train reads and writes on the device.  bwgr_mrr has one; bwgr_pegs one per
+// panel effect, all against the same residual (MrrSweepShared).
+struct MrrLeg {
+  const bwgr_panel *P = nullptr;
+  int64_t p = 0, nblk = 0;
+  int8_t *Xs = nullptr; int32_t *ordd = nullptr, *gram = nullptr;
+  double *xbar = nullptr, *Sd = nullptr, *XXd = nullptr, *XSXd = nullptr, *tilde = nullptr, *bd = nullptr, *Linv = nullptr, *db2 = nullptr;
+};
+struct MrrSweepShared {
+  int64_t ld; int G, npat;
+  const uint32_t *ztd; const uint8_t *zmd;
+  double *ed, *part, *dB, *iGd;     // the residual [trait][ld]; the pass's partial dots; the block's delta b; k x k staging of iG
+};
+// (the caller asks bufs.failed() once, after all its gets)
+static void mrr_leg_alloc(DevBufs &bufs, MrrLeg &L, const bwgr_panel *P, int npat, int k) {
+  L.P = P; L.p = P->data->p; L.nblk = (L.p + MRR_MB - 1) / MRR_MB;
+  const size_t np = (size_t)L.p, pk = np * k;
+  L.Xs = bufs.get<int8_t>(P->data->plan.x_bytes);
+  L.ordd = bufs.get<int32_t>(np); L.gram = bufs.get<int32_t>((size_t)L.nblk * npat * MRR_MB * MRR_MB);
+  L.xbar = bufs.get<double>(np); L.Sd = bufs.get<double>(npat * np);
+  L.XXd = bufs.get<double>(pk); L.XSXd = bufs.get<double>(pk); L.tilde = bufs.get<double>(pk); L.bd = bufs.get<double>(pk); L.Linv = bufs.get<double>(pk * k);
+  L.db2 = bufs.get<double>(MRR_KMAX);
+}
+// order -> k_permute_cols -> k_mrr_gram -> k_mrr_linv -> [k_mrr_pass(b-1 | b), k_mrr_solve(b)] for every block -> k_mrr_pass(last | -);
+// mc.iVe and iG (host, k x k) are the sweep's.  Leaves sum_j (delta b_jt)^2 in L.db2.
+static int mrr_sweep(hipStream_t st, const MrrLeg &L, const MrrSweepShared &W, const MrrConst &mc, const MrrPlan &plan, const std::vector<int> &order,
+                     const double *iG) {
+  const PanelData *D = L.P->data;
+  const int R = D->plan.R, k = mc.k, npat = W.npat, G = W.G;
+  const int64_t p = L.p, ld = W.ld, nblk = L.nblk;
+  const int cps = (int)((size_t)R / 16);
+  HIPCHK(h2d(st, L.ordd, order.data(), (size_t)p));
+  hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)D->X, (uint4 *)L.Xs, (const int32_t *)L.ordd, p, D->plan.K, cps);
+  hipLaunchKernelGGL(k_mrr_gram, dim3((unsigned)nblk, (unsigned)((npat + 3) / 4)), dim3(256), 0, st, (const int8_t *)L.Xs, R, p, ld, W.zmd, npat, L.gram);
+  HIPCHK(h2d(st, W.iGd, iG, (size_t)k * k));
+  hipLaunchKernelGGL(k_mrr_linv, dim3((unsigned)((p + 63) / 64)), dim3(64), plan.lds_linv, st, (const double *)L.XXd, (const double *)W.iGd, mc, p, L.Linv);
+  HIPCHK(zero(st, L.db2, (size_t)MRR_KMAX));
+  HIPCHK(hipGetLastError());
+  for (int64_t blk = 0; blk <= nblk; ++blk) {
+    MrrPassArgs pa; pa.Xs = L.Xs; pa.R = R; pa.p = p; pa.ld = ld; pa.nblk = (int)nblk; pa.zb = W.ztd; pa.e = W.ed; pa.dB = W.dB; pa.part = W.part;
+    pa.prev = blk > 0 ? (int)(blk - 1) : -1; pa.next = blk < nblk ? (int)blk : -1; pa.k = k;
+    hipLaunchKernelGGL(k_mrr_pass, dim3(G), dim3(256), 0, st, pa);
+    if (blk == nblk) break;
+    MrrSolveArgs sa; sa.part = W.part; sa.G = G; sa.order = L.ordd; sa.blk = (int)blk; sa.p = p; sa.gram = L.gram; sa.xbar = L.xbar; sa.S = L.Sd; sa.XX = L.XXd;
+    sa.Linv = L.Linv; sa.b = L.bd; sa.dB = W.dB; sa.db2 = L.db2; sa.ngl = plan.ngl; sa.linv_lds = plan.linv_lds;
+    hipLaunchKernelGGL(k_mrr_solve, dim3(1), dim3(256), plan.lds_solve, st, sa, mc);
+  }
+  HIPCHK(hipGetLastError());
   return BWGR_OK;
 }
 
@@ -91,19 +143,18 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   CumulativeOrder order((size_t)p);
   std::vector<double> iG((size_t)k * k, 0.0), d(k), off(k);   // (these four are copied from asynchronously: declared before the holder, which waits for the stream)
   DevBufs bufs(st);
-  const int64_t nblk = (p + MRR_MB - 1) / MRR_MB;
   const int G = (int)mrr_pass_grid(ld);
   const int NP = MRR_NP;                               // partials of the tail reductions
   const int nch = (int)std::min<int64_t>(64, p);       // marker chunks of the fitted values
   const int64_t cpc = (p + nch - 1) / nch;
   const size_t np = (size_t)p, nl = (size_t)ld, pk = np * k;
-  int8_t *Xs = bufs.get<int8_t>(P->data->plan.x_bytes);
+  MrrLeg leg;
+  mrr_leg_alloc(bufs, leg, P, npat, k);
   uint32_t *zbd = bufs.get<uint32_t>(nl), *ztd = bufs.get<uint32_t>(nl);
   uint8_t *zmd = bufs.get<uint8_t>((size_t)npat * nl);
-  int32_t *ordd = bufs.get<int32_t>(np), *gram = bufs.get<int32_t>((size_t)nblk * npat * MRR_MB * MRR_MB);
-  double *yd = bufs.get<double>(k * nl), *ed = bufs.get<double>(k * nl), *xbar = bufs.get<double>(np), *Sd = bufs.get<double>(npat * np);
-  double *XXd = bufs.get<double>(pk), *XSXd = bufs.get<double>(pk), *tilde = bufs.get<double>(pk), *bd = bufs.get<double>(pk), *Linv = bufs.get<double>(pk * k);
-  double *part = bufs.get<double>((size_t)G * (MRR_MB + 1) * MRR_KMAX), *dB = bufs.get<double>(MRR_MB * MRR_KMAX + MRR_KMAX), *db2 = bufs.get<double>(MRR_KMAX);
+  double *yd = bufs.get<double>(k * nl), *ed = bufs.get<double>(k * nl);
+  double *part = bufs.get<double>((size_t)G * (MRR_MB + 1) * MRR_KMAX), *dB = bufs.get<double>(MRR_MB * MRR_KMAX + MRR_KMAX);
+  double *const xbar = leg.xbar, *const Sd = leg.Sd, *const XXd = leg.XXd, *const XSXd = leg.XSXd, *const tilde = leg.tilde, *const bd = leg.bd, *const db2 = leg.db2;
   double *small = bufs.get<double>(1024);            // [0, 512): reduction results; [512, 768): iG; [768, ...): mu shift
   double *tpart = bufs.get<double>((size_t)NP * (MRR_KMAX * MRR_KMAX + MRR_KMAX)), *sumyd = bufs.get<double>(MRR_KMAX);
   if (bufs.failed()) return no_memory("mrr");
@@ -117,7 +168,7 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_linv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
   hipLaunchKernelGGL(k_mrr_setup_cols, dim3((unsigned)mrr_setup_grid(p)), dim3(TAIL_THREADS), 0, st, (const int8_t *)P->data->X, R, (int)n, p, ld,
-                     (const uint32_t *)zbd, (const double *)yd, (const double *)sumyd, mc, xbar, Sd, XXd, XSXd, tilde);
+                     (const uint32_t *)zbd, (const double *)yd, (const double *)sumyd, mc, 1, xbar, Sd, XXd, XSXd, tilde);
   HIPCHK(hipGetLastError());
   // a reduction over p of the k^2 (+k) products, partials in a fixed order
   auto reduce_pk = [&](int mode, int nout, const double *iGd, std::vector<double> &out) -> hipError_t {
@@ -145,32 +196,15 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   for (int i = 0; i < k * k; ++i) Sb[i] = vb[i] * o.df0;                                           // :816
   for (int i = 0; i < k * k; ++i) GC[i] = vb[i];
   // ---- iterations ----
-  const int cps = (int)((size_t)R / 16);
   const double logtol = log10(o.tol);
   std::vector<double> ey, db2h(k), vb0, h20;
   int numit = 0;
   const MrrPlan plan = mrr_plan(k, npat);
+  const MrrSweepShared W = {ld, G, npat, ztd, zmd, ed, part, dB, small + 512};
   while (numit < o.maxit) {
     vb0 = vb; h20 = h2;
-    HIPCHK(h2d(st, ordd, order.next(numit).data(), np));                                           // :869 (cumulative, as there)
-    hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)P->data->X, (uint4 *)Xs, (const int32_t *)ordd, p, P->data->plan.K, cps);
-    hipLaunchKernelGGL(k_mrr_gram, dim3((unsigned)nblk, (unsigned)((npat + 3) / 4)), dim3(256), 0, st, (const int8_t *)Xs, R, p, ld, (const uint8_t *)zmd, npat, gram);
     for (int t = 0; t < k; ++t) mc.iVe[t] = 1.0 / ve[t];
-    HIPCHK(h2d(st, small + 512, iG.data(), (size_t)k * k));
-    hipLaunchKernelGGL(k_mrr_linv, dim3((unsigned)((p + 63) / 64)), dim3(64), plan.lds_linv, st, (const double *)XXd, (const double *)(small + 512), mc, p, Linv);
-    HIPCHK(zero(st, db2, (size_t)MRR_KMAX));
-    HIPCHK(hipGetLastError());
-    for (int64_t blk = 0; blk <= nblk; ++blk) {
-      MrrPassArgs pa; pa.Xs = Xs; pa.R = R; pa.p = p; pa.ld = ld; pa.nblk = (int)nblk; pa.zb = ztd; pa.e = ed; pa.dB = dB; pa.part = part;
-      pa.prev = blk > 0 ? (int)(blk - 1) : -1; pa.next = blk < nblk ? (int)blk : -1; pa.k = k;
-      hipLaunchKernelGGL(k_mrr_pass, dim3(G), dim3(256), 0, st, pa);
-      if (blk == nblk) break;
-      MrrSolveArgs sa; sa.part = part; sa.G = G; sa.order = ordd; sa.blk = (int)blk; sa.p = p; sa.gram = gram; sa.xbar = xbar; sa.S = Sd; sa.XX = XXd;
-      sa.Linv = Linv; sa.b = bd; sa.dB = dB; sa.db2 = db2; sa.ngl = plan.ngl; sa.linv_lds = plan.linv_lds;
-
-      hipLaunchKernelGGL(k_mrr_solve, dim3(1), dim3(256), plan.lds_solve, st, sa, mc);
-    }
-    HIPCHK(hipGetLastError());
+    CHK(mrr_sweep(st, leg, W, mc, plan, order.next(numit), iG.data()));                            // :869 (cumulative, as there)
     // residual variance (:916-924)
     hipLaunchKernelGGL(k_mrr_ey, dim3(NP, k), dim3(256), 0, st, (const double *)ed, (const double *)yd, ld, k, tpart);
     hipLaunchKernelGGL(k_mrr_finish, dim3(1), dim3(256), 0, st, (const double *)tpart, NP, 2 * k, small);

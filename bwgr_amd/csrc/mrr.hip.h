@@ -57,9 +57,11 @@ __device__ __forceinline__ void mrr_wave_sync() {
 // ---- once per call: per-column statistics of the resident panel (natural order), one wave per column ----
 // xbar_j = mean over all n rows (:763-765); S_g(j) = sum_r z_rg x_rj; XX[j][t] = sum_r z_rt (x_rj - xbar_j)^2 (:769-770);
 // XSX[j][t] = XX/n_t - ((X_c,j'z_t)/n_t)^2 (:774-776); tilde[j][t] = X_c,j'y_t (:806).  zb[r]: bit g = row r observed in pattern g.
+// centre = 0 (PEGS, which never centres X): xbar = 0, so XX is the raw masked sum of squares, XSX and tilde those of the raw columns, and
+// the solve's Gram correction and the fitted values' offset vanish with no other change.
 __global__ __launch_bounds__(256) void k_mrr_setup_cols(const int8_t *__restrict__ X, int R, int n, int64_t p, int64_t ld,
                                                         const uint32_t *__restrict__ zb, const double *__restrict__ y, const double *__restrict__ sumy,
-                                                        const MrrConst c, double *__restrict__ xbar, double *__restrict__ S,
+                                                        const MrrConst c, int centre, double *__restrict__ xbar, double *__restrict__ S,
                                                         double *__restrict__ XX, double *__restrict__ XSX, double *__restrict__ tilde) {
   const int lane = threadIdx.x & 63;
   const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
@@ -80,7 +82,7 @@ __global__ __launch_bounds__(256) void k_mrr_setup_cols(const int8_t *__restrict
         if (t < c.k) xy[t] = fma((double)x, y[(size_t)t * ld + r], xy[t]);
     }
     const double xb = mrr_wave_sum((double)sx) / (double)n;
-    const double xbs = __shfl(xb, 0, 64);
+    const double xbs = centre ? __shfl(xb, 0, 64) : 0.0;
     double sgs[MRR_KMAX], qgs[MRR_KMAX];
 #pragma unroll
     for (int g = 0; g < MRR_KMAX; ++g) {
@@ -471,36 +473,9 @@ __global__ void k_mrr_hat_finish(const double *__restrict__ hpart, int nchunks, 
 #include <vector>
 #include <math.h>
 #include <algorithm>
+#include "pegs_tail.h"   // mrr_eigh, mrr_pinv
 
 namespace bwgr {
-
-// Jacobi eigen-decomposition of a symmetric k x k matrix (row-major): w ascending, eigenvector i in column i of V
-static void mrr_eigh(int k, const double *Ain, double *w, double *V) {
-  std::vector<double> A(Ain, Ain + (size_t)k * k);
-  for (int r = 0; r < k; ++r) for (int c = 0; c < k; ++c) V[r * k + c] = (r == c) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 100; ++sweep) {
-    double off = 0.0, tot = 0.0;
-    for (int r = 0; r < k; ++r) for (int c = 0; c < k; ++c) { tot += A[r * k + c] * A[r * k + c]; if (r != c) off += A[r * k + c] * A[r * k + c]; }
-    if (off <= 1e-32 * tot || off == 0.0) break;
-    for (int p = 0; p < k; ++p)
-      for (int q = p + 1; q < k; ++q) {
-        const double apq = A[p * k + q];
-        if (apq == 0.0) continue;
-        const double th = (A[q * k + q] - A[p * k + p]) / (2.0 * apq);
-        const double t = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int r = 0; r < k; ++r) { const double arp = A[r * k + p], arq = A[r * k + q]; A[r * k + p] = c * arp - s * arq; A[r * k + q] = s * arp + c * arq; }
-        for (int r = 0; r < k; ++r) { const double apr = A[p * k + r], aqr = A[q * k + r]; A[p * k + r] = c * apr - s * aqr; A[q * k + r] = s * apr + c * aqr; }
-        for (int r = 0; r < k; ++r) { const double vrp = V[r * k + p], vrq = V[r * k + q]; V[r * k + p] = c * vrp - s * vrq; V[r * k + q] = s * vrp + c * vrq; }
-      }
-  }
-  std::vector<int> idx(k);
-  for (int i = 0; i < k; ++i) idx[i] = i;
-  std::sort(idx.begin(), idx.end(), [&](int a, int b) { return A[a * k + a] < A[b * k + b]; });
-  std::vector<double> V2((size_t)k * k);
-  for (int i = 0; i < k; ++i) { w[i] = A[idx[i] * k + idx[i]]; for (int r = 0; r < k; ++r) V2[r * k + i] = V[r * k + idx[i]]; }
-  std::copy(V2.begin(), V2.end(), V);
-}
 
 // the leading NumXFA eigen-terms of GC: sum_i lambda_(k-1-i) v v' (:969-970, :983-984)
 static void mrr_udu(int k, const double *GC, int nf, double *UDU) {
@@ -510,19 +485,6 @@ static void mrr_udu(int k, const double *GC, int nf, double *UDU) {
   for (int i = 0; i < nf; ++i) {
     const int e = k - 1 - i;
     for (int r = 0; r < k; ++r) for (int c = 0; c < k; ++c) UDU[r * k + c] += w[e] * V[r * k + e] * V[c * k + e];
-  }
-}
-
-// Moore-Penrose inverse of a symmetric matrix (singular values |lambda| below 1e-15 max |lambda| dropped)
-static void mrr_pinv(int k, const double *A, double *out) {
-  std::vector<double> w(k), V((size_t)k * k);
-  mrr_eigh(k, A, w.data(), V.data());
-  double mx = 0.0;
-  for (int i = 0; i < k; ++i) mx = std::max(mx, fabs(w[i]));
-  for (int i = 0; i < k * k; ++i) out[i] = 0.0;
-  for (int e = 0; e < k; ++e) {
-    if (!(fabs(w[e]) > 1e-15 * mx)) continue;
-    for (int r = 0; r < k; ++r) for (int c = 0; c < k; ++c) out[r * k + c] += V[r * k + e] * V[c * k + e] / w[e];
   }
 }
 

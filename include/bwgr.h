@@ -369,6 +369,42 @@ int bwgr_debug_uvbd_plan(int64_t n, int64_t q, int64_t k, int64_t out[BWGR_UVBD_
 int bwgr_uvbeta2(bwgr_panel *P, const double *Z, int64_t q, int64_t ldz, const double *Y, int64_t k, int maxit, double tol, double df0,
                  double *b1 /* q x k */, double *b2 /* p x k */, double *mu, double *h2, double *ve, double *vb1, double *vb2, int *its,
                  double *cnv);
+/* ---- PEGS / PEGSZ: multi-trait fits over several designs --------------------------------------------------
+ * Replaces SEXP PEGS(Y,X,maxit,logtol,covbend,covMinEv,XFA,NNC) src/RcppEigenX20251203.cpp:10-194 and PEGSZ(Y,X_list,...) :576-808: the
+ * pseudo-expectation Gauss-Seidel solver for k correlated traits (1 <= k <= BWGR_MRR_MAXK), one residual variance per trait and one k x k
+ * genetic covariance per random effect.  In every sweep the neff effects are walked in list order against one n x k residual.  An effect is
+ *   a panel effect  (panel != NULL): the resident int8 genotypes, NOT centred (PEGS never centres X) -- bwgr_mrr's launch train in its
+ *                   uncentred mode; or
+ *   a dense effect  (panel == NULL): Z, n x q fp64 column-major with column stride ldz >= n, host -- one workgroup walks its q columns.
+ * All effects have n rows; all panels live on one device and share the row padding ld (panels made with the same block / nwg arguments do);
+ * `device` is used only where no effect is a panel.  Y: n x k column-major, NaN = missing; the caller rounds Y to float where it mirrors the
+ * reference's float inputs -- the engine is fp64 throughout, and the reference's float constants (1e-12f, 10e-4) are taken as doubles.
+ * After every sweep (host, double): ve_t = e_t'y_t / (n_t - 1); per effect vb from TildeHat = b'tilde and TrXSX with no prior, the XFA
+ * structure (XFA < 0: k; 0: independent traits; else the leading XFA eigen-terms of the correlation matrix), NNC clamps at 0, MinDVb = the
+ * smallest eigenvalue, inflate carried as a running maximum of |MinDVb covbend| over the sweeps with MinDVb < covMinEv and added to the
+ * diagonal when k >= 5 or MinDVb < covMinEv, iG = pinv(vb); the intercept step with 1 / (n_t - 1) as the reference writes it; cnv = log10 of
+ * sum over effects and traits of (delta b)^2, and the fit stops once cnv < logtol (logtol = -inf: every sweep runs).
+ * own_text = 1 follows PEGS's own text where it differs from PEGSZ's: the XFA branch is taken whenever XFA > 0 (:139; PEGSZ: 0 < XFA < k,
+ * :734) and a zero TrXSX is not guarded (:130; PEGSZ :722-724).  On ordinary data the two agree to rounding.
+ * Departure: the reference seeds std::mt19937 from std::random_device, so its marker order cannot be reproduced and any permutation is
+ * faithful; here sweep s (0-based) walks an effect of m columns in bwgr_em_order(m, s), the cumulative std::shuffle(order, std::mt19937(s)).
+ * Outputs (host; b and numit are required): mu, h2 [k]; b[e]: p_e x k column-major; hat: n x k column-major, a row for every individual;
+ * GC[e]: k x k (the max(sd, 1e-12) floor of :180-183); bend [neff]: every effect's inflate; cnv [max(maxit, 1)]: the value after every sweep
+ * run (10 where none ran).  BWGR_EINVAL, the panels stay usable: a null required pointer, neff < 1, k outside 1..16, XFA > k (the
+ * reference would index out of range), maxit < 0, covbend / covMinEv not finite or logtol NaN / +inf, a trait with fewer than 2 records,
+ * an fp32 panel, effects with different n or ld, panels on different devices, q < 1 or q > 2147483392, ldz < n, a non-finite entry of Z, an
+ * effect whose TrXSX is 0 for a trait (the start value ve / MSx is infinite there).
+ * Not here: PEGSX (fixed effects and MRR3's option set again), PEGS_sparse, PEGSZ_sparse, k > 16. */
+typedef struct bwgr_pegs_effect { bwgr_panel *panel; const double *Z; int64_t q, ldz; } bwgr_pegs_effect;
+int bwgr_pegs(int device, const bwgr_pegs_effect *eff, int neff, const double *Y, int64_t n, int k, int maxit, double logtol, double covbend,
+              double covMinEv, int XFA, int NNC, int own_text, double *mu, double *const *b, double *hat, double *h2, double *const *GC,
+              double *bend, int *numit, double *cnv);
+/* host arithmetic of bwgr_pegs's dense leg (needs no GPU), in the style of the other plan hooks, for a dense effect of n rows and q columns
+ * and k traits (n, q >= 1, 1 <= k <= 16, else BWGR_EINVAL): out[0] the threads of the one workgroup of k_pegs_dense_leg (one row per thread
+ * up to 1024, whole waves), out[1] its dynamic LDS bytes, out[2] the bytes of the effect's device workspace (Z, XX, XSX, tilde, b, the q
+ * k x k inverses, the order, the sums). */
+#define BWGR_PEGS_PLAN_NOUT 3
+int bwgr_debug_pegs_plan(int64_t n, int64_t q, int k, int64_t out[BWGR_PEGS_PLAN_NOUT]);
 /* out (n x k, host, column-major) = X B on the raw int8 genotypes for every row; B: p x k, host, column-major.  fp64 sums; the markers are
  * split over workgroups and the partial sums added in a fixed order, so two calls give the same bits, and so does a panel switched to implicit
  * centring.  BWGR_EINVAL: a null pointer, k < 1, an fp32 panel.  (bwgr_uvbeta's own xb output is a different summation order.) */

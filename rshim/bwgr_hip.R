@@ -133,6 +133,38 @@ YSEMF <- function(Y, X, npc = -1L) {
   b <- f$b + s3$b; G <- .bwgr_xb(f$P, b)
   list(mu = s3$mu, b = b, hat = sweep(G, 2, s3$mu, "+"), h2 = f$s2$h2 + s3$h2, GC = .bwgr_gc(G)$GC)
 }
+# multi-trait fits over several designs, R/RcppExports.R:280, 288 (PEGS, PEGSZ; src/RcppEigenX20251203.cpp:10-194, :576-808): same names,
+# argument order, defaults and return lists.  An effect is a panel effect -- a panel handle, an integer matrix or an integer-valued numeric
+# matrix within int8 range, staged as int8 genotypes and NOT centred -- or a dense effect: a numeric matrix with a non-integer value, or any
+# matrix passed as dense(Z).  Y and the real options are float-rounded, as the reference receives them.  The marker order of a sweep is the
+# library's own (the reference seeds it from the machine).  PEGSX, PEGS_sparse and PEGSZ_sparse are not here.
+dense <- function(Z) structure(as.matrix(Z) * 1.0, class = c("bwgr_dense", "matrix"))
+.bwgr_pegs_effect <- function(X) {
+  if (inherits(X, "externalptr")) return(X)
+  if (inherits(X, "bwgr_dense")) return(unclass(X))
+  X <- as.matrix(X)
+  if (is.integer(X) || (!anyNA(X) && all(X == round(X)) && all(abs(X) <= 127))) .bwgr_ipanel(X) else X * 1.0
+}
+.bwgr_pegs <- function(Y, X_list, maxit, logtol, covbend, covMinEv, XFA, NNC, own_text) {
+  eff <- lapply(X_list, .bwgr_pegs_effect)
+  set <- .Call("bwgrhip_pegs_set", length(eff))
+  for (i in seq_along(eff)) {
+    isz <- is.matrix(eff[[i]])
+    pan <- if (isz) NULL else eff[[i]]
+    Z <- if (isz) eff[[i]] else NULL
+    .Call("bwgrhip_pegs_put", set, i - 1L, pan, Z)
+  }
+  r <- .Call("bwgrhip_pegs", set, .bwgr_f32(as.matrix(Y)), as.integer(maxit), .bwgr_f32(logtol), .bwgr_f32(covbend), .bwgr_f32(covMinEv), as.integer(XFA), as.logical(NNC), as.integer(own_text))
+  rm(eff)
+  r
+}
+PEGS <- function(Y, X, maxit = 100L, logtol = -4.0, covbend = 1.1, covMinEv = 10e-4, XFA = -1L, NNC = TRUE) {
+  r <- .bwgr_pegs(Y, list(X), maxit, logtol, covbend, covMinEv, XFA, NNC, 1L)
+  r$b <- r$b[[1]]; r$GC <- r$GC[[1]]
+  r
+}
+PEGSZ <- function(Y, X_list, maxit = 100L, logtol = -4.0, covbend = 1.1, covMinEv = 10e-4, XFA = -1L, NNC = TRUE)
+  .bwgr_pegs(Y, X_list, maxit, logtol, covbend, covMinEv, XFA, NNC, 0L)
 # two designs in one sweep, R/RcppExports.R:200, 208, 212 (solver2x, MEGA, GSEM; src/RcppEigen20230423.cpp:1446-1493, :1542-1610): same names,
 # argument order, defaults and return lists; doubles throughout.  solver2x's X1 is the dense design and X2 the integer genotypes (an int8
 # panel), as MEGA and GSEM call it; a dense X2 is not taken.  MEGA refuses a trait without records (the reference's imputed column is NaN);

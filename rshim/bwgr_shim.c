@@ -393,6 +393,71 @@ SEXP bwgrhip_uvbeta2(SEXP Y, SEXP Z, SEXP panel, SEXP maxit, SEXP tol, SEXP df0)
   return out;
 }
 
+/* PEGS(Y, X, ...) / PEGSZ(Y, X_list, maxit, logtol, covbend, covMinEv, XFA, NNC) src/RcppEigenX20251203.cpp:10-194, :576-808 ->
+ * list(mu, b, hat, h2, GC, bend, numit, cnv); for PEGSZ b and GC are lists with one entry per effect and bend a vector (bwgr_hip.R unwraps
+ * them for PEGS).  The effects are put into a set one by one -- a panel (the int8 genotypes, not centred) or a dense numeric n x q matrix --
+ * and the set is fitted in one call; bwgr_hip.R keeps the panels and matrices alive meanwhile.  Y: float-rounded by the R front-end, NA = missing. */
+#include <stdlib.h>
+typedef struct { int neff; bwgr_pegs_effect *e; int *cols; } pegs_set;
+static void pegs_set_finalizer(SEXP ext) {
+  pegs_set *S = (pegs_set *)R_ExternalPtrAddr(ext);
+  if (S) { free(S->e); free(S->cols); free(S); R_ClearExternalPtr(ext); }
+}
+SEXP bwgrhip_pegs_set(SEXP neff) {
+  const int m = Rf_asInteger(neff);
+  if (m < 1) Rf_error("X_list holds no effects");
+  pegs_set *S = (pegs_set *)calloc(1, sizeof(pegs_set));
+  if (S) { S->neff = m; S->e = (bwgr_pegs_effect *)calloc((size_t)m, sizeof(bwgr_pegs_effect)); S->cols = (int *)calloc((size_t)m, sizeof(int)); }
+  if (!S || !S->e || !S->cols) { if (S) { free(S->e); free(S->cols); free(S); } Rf_error("out of memory"); }
+  SEXP ext = PROTECT(R_MakeExternalPtr(S, R_NilValue, R_NilValue));
+  R_RegisterCFinalizerEx(ext, pegs_set_finalizer, TRUE);
+  UNPROTECT(1);
+  return ext;
+}
+SEXP bwgrhip_pegs_put(SEXP set, SEXP index, SEXP panel, SEXP Z) {
+  pegs_set *S = (pegs_set *)R_ExternalPtrAddr(set);
+  const int i = Rf_asInteger(index);
+  if (!S || i < 0 || i >= S->neff) Rf_error("bad effect set or index");
+  if (!Rf_isNull(panel)) {
+    bwgr_panel *P = panel_of(panel);
+    int64_t info[8]; chk(bwgr_panel_info(P, info));
+    S->e[i].panel = P; S->e[i].Z = NULL; S->e[i].q = 0; S->e[i].ldz = 0; S->cols[i] = (int)info[1];
+  } else {
+    SEXP dz = Rf_getAttrib(Z, R_DimSymbol);
+    if (TYPEOF(Z) != REALSXP || Rf_length(dz) != 2) Rf_error("a dense effect must be a numeric matrix");
+    S->e[i].panel = NULL; S->e[i].Z = REAL(Z); S->e[i].q = INTEGER(dz)[1]; S->e[i].ldz = INTEGER(dz)[0]; S->cols[i] = INTEGER(dz)[1];
+  }
+  return R_NilValue;
+}
+SEXP bwgrhip_pegs(SEXP set, SEXP Y, SEXP maxit, SEXP logtol, SEXP covbend, SEXP covMinEv, SEXP XFA, SEXP NNC, SEXP own_text) {
+  pegs_set *S = (pegs_set *)R_ExternalPtrAddr(set);
+  if (!S) Rf_error("bad effect set");
+  SEXP dy = Rf_getAttrib(Y, R_DimSymbol);
+  if (Rf_length(dy) != 2) Rf_error("Y must be a matrix");
+  const int n = INTEGER(dy)[0], k = INTEGER(dy)[1], m = S->neff, mit = Rf_asInteger(maxit);
+  for (int i = 0; i < m; i++)
+    if (!S->e[i].panel && (!S->e[i].Z || S->e[i].ldz != n)) Rf_error("every effect must be set and have nrow(Y) rows");
+  SEXP mu = PROTECT(Rf_allocVector(REALSXP, k)), hat = PROTECT(Rf_allocMatrix(REALSXP, n, k)), h2 = PROTECT(Rf_allocVector(REALSXP, k));
+  SEXP bend = PROTECT(Rf_allocVector(REALSXP, m)), bl = PROTECT(Rf_allocVector(VECSXP, m)), gl = PROTECT(Rf_allocVector(VECSXP, m));
+  double **bp = (double **)R_alloc((size_t)m, sizeof(double *)), **gp = (double **)R_alloc((size_t)m, sizeof(double *));
+  for (int i = 0; i < m; i++) {
+    SEXP b = PROTECT(Rf_allocMatrix(REALSXP, S->cols[i], k)), g = PROTECT(Rf_allocMatrix(REALSXP, k, k));
+    SET_VECTOR_ELT(bl, i, b); SET_VECTOR_ELT(gl, i, g);
+    bp[i] = REAL(b); gp[i] = REAL(g);
+    UNPROTECT(2);
+  }
+  double *cnv = (double *)R_alloc(mit > 0 ? mit : 1, sizeof(double));
+  int numit = 0;
+  chk(bwgr_pegs(0, S->e, m, REAL(Y), (int64_t)n, k, mit, Rf_asReal(logtol), Rf_asReal(covbend), Rf_asReal(covMinEv), Rf_asInteger(XFA),
+                Rf_asLogical(NNC), Rf_asInteger(own_text), REAL(mu), bp, REAL(hat), REAL(h2), gp, REAL(bend), &numit, cnv));
+  const char *nm[] = {"mu", "b", "hat", "h2", "GC", "bend", "numit", "cnv"};
+  SEXP out = PROTECT(named_list(8, nm));
+  SET_VECTOR_ELT(out, 0, mu); SET_VECTOR_ELT(out, 1, bl); SET_VECTOR_ELT(out, 2, hat); SET_VECTOR_ELT(out, 3, h2); SET_VECTOR_ELT(out, 4, gl);
+  SET_VECTOR_ELT(out, 5, bend); SET_VECTOR_ELT(out, 6, Rf_ScalarReal((double)numit)); SET_VECTOR_ELT(out, 7, Rf_ScalarReal(cnv[numit > 0 ? numit - 1 : 0]));
+  UNPROTECT(7);
+  return out;
+}
+
 /* relationship kernels: GRM(X, Code012) / GAU(X) src/Rcpp20260726ai.cpp:1338-1383, EigenARC / EigenGAU / EigenGRM(X, ., cores)
  * src/RcppEigen20230423.cpp:8-51 -> an n x n numeric matrix.  kind: BWGR_K_*; par: phi; flag: Code012 / centralizeZ / centralizeX. */
 SEXP bwgrhip_kernel(SEXP panel, SEXP kind, SEXP par, SEXP flag) {
@@ -457,6 +522,7 @@ static const R_CallMethodDef CallEntries[] = {   /* as src/RcppExports.cpp:1152-
   {"bwgrhip_solver1x", (DL_FUNC)&bwgrhip_solver1x, 6}, {"bwgrhip_UVBETA", (DL_FUNC)&bwgrhip_UVBETA, 3},
   {"bwgrhip_uvbeta_dense", (DL_FUNC)&bwgrhip_uvbeta_dense, 6}, {"bwgrhip_panel_xb", (DL_FUNC)&bwgrhip_panel_xb, 2},
   {"bwgrhip_uvbeta2", (DL_FUNC)&bwgrhip_uvbeta2, 6},
+  {"bwgrhip_pegs_set", (DL_FUNC)&bwgrhip_pegs_set, 1}, {"bwgrhip_pegs_put", (DL_FUNC)&bwgrhip_pegs_put, 4}, {"bwgrhip_pegs", (DL_FUNC)&bwgrhip_pegs, 9},
   {"bwgrhip_kernel", (DL_FUNC)&bwgrhip_kernel, 4}, {"bwgrhip_crossprod", (DL_FUNC)&bwgrhip_crossprod, 1},
   {"bwgrhip_kernel2", (DL_FUNC)&bwgrhip_kernel2, 4}, {"bwgrhip_crossprod2", (DL_FUNC)&bwgrhip_crossprod2, 2}, {NULL, NULL, 0}};
 
