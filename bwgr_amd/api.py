@@ -1180,6 +1180,94 @@ def PEGSZ(Y, X_list, maxit=100, logtol=-4.0, covbend=1.1, covMinEv=10e-4, XFA=-1
     return _pegs(Y, list(X_list), maxit, logtol, covbend, covMinEv, XFA, NNC, 0, device, cnv_trace, kw)
 
 
+# ---- PEGSX: fixed effects beside the random effects of the multi-trait fit (bwgr_pegsx, include/bwgr.h) ----
+PEGSX_KEYS = ("TrZSZ", "b", "u", "vb_list", "GC_list", "ve", "hat", "its", "cnv", "bend")
+
+
+def pegsx_plan(n, f, k):
+    """bwgr_debug_pegsx_plan (host arithmetic, no GPU): dict(threads, lds_bytes, ws_bytes) of the fixed step and (jc, fc, trace_lds_bytes),
+    the trace kernels' tiling."""
+    out = (C.c_int64 * 6)()
+    check(_lib.lib().bwgr_debug_pegsx_plan(int(n), int(f), int(k), out))
+    return dict(zip(("threads", "lds_bytes", "ws_bytes", "jc", "fc", "trace_lds_bytes"), [int(v) for v in out]))
+
+
+def pegsx_timing(mode):
+    """bwgr_debug_pegsx_timing: sets the timing mode of the PEGSX calls that follow (0 off, 1 set-up and sweeps, 2 and the fixed step) and
+    returns what the last timed call left, in ms."""
+    out = (C.c_double * 9)()
+    check(_lib.lib().bwgr_debug_pegsx_timing(int(mode), out))
+    v = [float(x) for x in out]
+    return dict(trace_ms=v[0], setup_cols_ms=v[1], sweeps=int(v[2]), sweep_ms=dict(mean=v[3], min=v[4], max=v[5]), fixed_ms=dict(mean=v[6], min=v[7], max=v[8]))
+
+
+def PEGSX(Y, X, Z_list, maxit=500, logtol=-8.0, covbend=1.1, covMinEv=10e-4, cores=1, verbose=False, df0=1.1, NNC=False, InnerGS=False, NoInv=False,
+          XFA=False, NumXFA=3, *, device=0, cnv_trace=False, **kw):
+    """PEGSX(Y, X, Z_list, ...), src/RcppEigenX20251203.cpp:197-573 (R/RcppExports.R:284): Y = X b + sum_r Z_r u_r + E for k correlated
+    traits (NaN in Y = missing) -- a fixed design X (n x f, an intercept is a column of it; nothing is centred) beside the random effects of
+    Z_list, each an effect as `dense` describes and swept as PEGSZ sweeps it.  list(TrZSZ, b, u, vb_list, GC_list, ve, hat, its, cnv, bend)
+    as a dict: TrZSZ, u, vb_list and GC_list are lists with one entry per effect, b is f x k, bend a vector.  Y, X, dense Z and the real
+    options are rounded to float as the reference receives them; the engine is fp64.  The marker order of sweep s is em_order(m, s) per effect.
+    InnerGS=True and NoInv=True are refused; cores and verbose are accepted and ignored; XFA=True with NumXFA <= 0 is XFA=False.
+    cnv_trace=True adds "cnv_trace", cnv after every sweep."""
+    effs, made = [], []
+    try:
+        for Z in list(Z_list):
+            E, own = _pegs_effect(Z, dict(kw, device=device))
+            effs.append(E)
+            if own:
+                made.append(E)
+        f32 = lambda v: float(np.float32(v))   # the real options are floats there
+        Ym = np.asarray(Y, np.float64)
+        if Ym.ndim == 1:
+            Ym = Ym[:, None]
+        Xm = np.asarray(X, np.float64)
+        if Xm.ndim == 1:
+            Xm = Xm[:, None]
+        if Ym.ndim != 2 or Xm.ndim != 2:
+            raise BwgrError(1, "pegsx: Y has shape %s and X %s; both must be matrices" % (Ym.shape, Xm.shape))
+        Yf = np.asfortranarray(Ym.astype(np.float32).astype(np.float64))
+        with np.errstate(over="ignore"):
+            Xf = np.asfortranarray(Xm.astype(np.float32).astype(np.float64))
+        n, k = Yf.shape
+        if Xf.shape[0] != n:
+            raise BwgrError(1, "pegsx: X has %d rows, Y %d; nrow(X) must equal nrow(Y)" % (Xf.shape[0], n))
+        rows = [E.n if isinstance(E, Panel) else E.Z.shape[0] for E in effs]
+        if any(r != n for r in rows):
+            raise BwgrError(1, "pegsx: the effects have %s rows, Y %d; all must have the same rows" % (rows, n))
+        f, neff, kk = Xf.shape[1], len(effs), max(k, 1)
+
+        class _Eff(C.Structure):
+            _fields_ = [("panel", C.c_void_p), ("Z", C.c_void_p), ("q", C.c_int64), ("ldz", C.c_int64)]
+        ce = (_Eff * max(neff, 1))()
+        ps, keep = [], []
+        for i, E in enumerate(effs):
+            if isinstance(E, Panel):
+                ce[i].panel = E._h.value; ce[i].Z = None; ce[i].q = 0; ce[i].ldz = 0
+                ps.append(E.p)
+            else:
+                Zf = np.asfortranarray(E.Z.astype(np.float32).astype(np.float64))   # (a dense Z is a float matrix there, :266)
+                keep.append(Zf)
+                ce[i].panel = None; ce[i].Z = Zf.ctypes.data; ce[i].q = Zf.shape[1]; ce[i].ldz = max(Zf.shape[0], 1)
+                ps.append(Zf.shape[1])
+        Tr = np.zeros((max(neff, 1), kk)); b = np.zeros((max(f, 1), kk), order="F"); ve = np.zeros(kk); hat = np.zeros((n, kk), order="F"); bend = np.zeros(max(neff, 1))
+        u = [np.zeros((p_, kk), order="F") for p_ in ps]
+        vb = [np.zeros((kk, kk), order="F") for _ in ps]; GC = [np.zeros((kk, kk), order="F") for _ in ps]
+        ptrs = lambda arrs: C.cast((C.c_void_p * max(neff, 1))(*[a.ctypes.data for a in arrs]), C.c_void_p)
+        cnv = np.zeros(max(int(maxit), 1)); its = C.c_int()
+        check(_lib.lib().bwgr_pegsx(int(device), C.cast(ce, C.c_void_p), neff, _dp(Xf), max(n, 1), int(f), _dp(Yf), int(n), int(k), int(maxit), f32(logtol),
+                                    f32(covbend), f32(covMinEv), f32(df0), int(bool(NNC)), int(bool(XFA)), int(NumXFA), int(bool(InnerGS)), int(bool(NoInv)),
+                                    _dp(Tr), _dp(b), ptrs(u), ptrs(vb), ptrs(GC), _dp(ve), _dp(hat), C.byref(its), _dp(cnv), _dp(bend)))
+        nit = int(its.value)
+        out = dict(zip(PEGSX_KEYS, ([Tr[e].copy() for e in range(neff)], b, u, vb, GC, ve, hat, nit, float(cnv[max(nit, 1) - 1]), bend)))
+        if cnv_trace:
+            out["cnv_trace"] = cnv[:nit].copy()
+        return out
+    finally:
+        for P in made:
+            P.close()
+
+
 # ---- per-trait ridge fits: solver1x / UVBETA, solver1xF / FUVBETA, XFUVBETA, ZFUVBETA (bwgr_uvbeta, include/bwgr.h) ----
 UVB_VARIANTS = {"D": 0, "F": 1, "X": 2, "Z": 3}   # BWGR_UVB_*
 UVB_KEYS = ("b", "mu", "h2", "ve", "vb", "its", "cnv")

@@ -31,6 +31,8 @@
 #include "uvbd.hip.h"
 #include "uvb2.hip.h"
 #include "pegs.hip.h"
+#include "pegsx.hip.h"
+#include "pegsx_setup.h"
 #include "kernels.hip.h"
 #include <stdlib.h>
 
@@ -1458,6 +1460,7 @@ extern "C" int bwgr_panel_centred(bwgr_panel *P, int *centred) {
 #include "group_host.hip.h"
 #include "fits_host.hip.h"
 #include "pegs_host.hip.h"
+#include "pegsx_host.hip.h"
 
 // ------------------------------------------------------------------------------------------------
 // synthetic data and test hooks

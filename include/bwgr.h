@@ -394,7 +394,7 @@ int bwgr_uvbeta2(bwgr_panel *P, const double *Z, int64_t q, int64_t ldz, const d
  * reference would index out of range), maxit < 0, covbend / covMinEv not finite or logtol NaN / +inf, a trait with fewer than 2 records,
  * an fp32 panel, effects with different n or ld, panels on different devices, q < 1 or q > 2147483392, ldz < n, a non-finite entry of Z, an
  * effect whose TrXSX is 0 for a trait (the start value ve / MSx is infinite there).
- * Not here: PEGSX (fixed effects and MRR3's option set again), PEGS_sparse, PEGSZ_sparse, k > 16. */
+ * Not here: PEGS_sparse, PEGSZ_sparse, k > 16 (PEGSX is bwgr_pegsx below). */
 typedef struct bwgr_pegs_effect { bwgr_panel *panel; const double *Z; int64_t q, ldz; } bwgr_pegs_effect;
 int bwgr_pegs(int device, const bwgr_pegs_effect *eff, int neff, const double *Y, int64_t n, int k, int maxit, double logtol, double covbend,
               double covMinEv, int XFA, int NNC, int own_text, double *mu, double *const *b, double *hat, double *h2, double *const *GC,
@@ -405,6 +405,51 @@ int bwgr_pegs(int device, const bwgr_pegs_effect *eff, int neff, const double *Y
  * k x k inverses, the order, the sums). */
 #define BWGR_PEGS_PLAN_NOUT 3
 int bwgr_debug_pegs_plan(int64_t n, int64_t q, int k, int64_t out[BWGR_PEGS_PLAN_NOUT]);
+/* ---- PEGSX: fixed effects beside the random effects of the multi-trait fit ------------------------------------
+ * Replaces SEXP PEGSX(Y,X,Z_list,maxit,logtol,covbend,covMinEv,cores,verbose,df0,NNC,InnerGS,NoInv,XFA,NumXFA) src/RcppEigenX20251203.cpp:197-573,
+ * "MLM with fixed effect and multiple random effects": Y = X b + sum_r Z_r u_r + E for k traits with missing records.  The effects are
+ * bwgr_pegs's (a resident int8 panel, not centred, or a dense n x q matrix; one n, one device, one ld) and every sweep walks them as bwgr_pegs
+ * does.  X: n x f fp64 column-major with column stride ldx >= n, host, 1 <= f <= BWGR_PEGSX_MAXF, finite; there is no intercept and no
+ * centring -- an intercept is a column of X.  With W the mask of observed records and M_t = w_t o X:
+ *   set-up     b_t = (M_t'M_t)^+ M_t'Y_t, y_t = (Y_t - M_t b_t) o w_t, e = y; per effect ZZ_jt = sum w_t z_j^2, tilde = Z'y and
+ *              TrZSZ_t = sum_j [ZZ_jt - (M_t'z_j)'(M_t'M_t)^+(M_t'z_j)]; iN_t = 1 / max(n_t - f, 1), ve = max(ssy iN / 2, 1e-8),
+ *              vb = diag(ve_t / max(Tr_t iN_t, 1e-8)), the priors Sb = df0 vb and Se = df0 ve, iNp_t = 1 / max(n_t + df0 - f, 1)
+ *   per sweep  every effect's columns in the sweep's order (the k x k block solve); the fixed step d = (M_t'M_t)^+ M_t'e_t, b_t += d,
+ *              e_t = (e_t - M_t d) o w_t on the device; per effect vb_ii = (TildeHat_ii + Sb_ii) / (max(Tr_i, 1e-8) + df0), vb_ij =
+ *              (TH_ij + TH_ji) / max(Tr_i + Tr_j, 1e-8), NNC clamps at 0, then with XFA and NumXFA > 0 the correlation matrix is rebuilt
+ *              from its top min(NumXFA, k) eigenpairs with a unit diagonal, then bending as in PEGSZ (inflate carried as a running maximum,
+ *              added when k >= 5 or the smallest eigenvalue is below covMinEv), iG = pinv(vb); ve = max((e'y + Se) iNp, 1e-8);
+ *              cnv = log10(max(max over the effects of sum (delta u)^2, 1e-20)); the fit stops once numit >= 5 and cnv < logtol, or cnv is NaN
+ * Departures: the marker order of sweep s is bwgr_em_order(m, s) per effect (the reference seeds its generator from the machine).  Both
+ * pseudo-inverses of M'M (the reference: a float COD for b, a float LLT with a COD fall-back for the trace) are one symmetric
+ * pseudo-inverse per missingness pattern that drops eigenvalues with |lambda| <= f 2^-23 max |lambda|, the reference's float rank
+ * decision; on a full-rank X it is the inverse.  The caller rounds Y, X, dense Z and the real options to float where it mirrors the
+ * reference's float inputs; the engine is fp64 and the reference's float floors are taken as doubles.
+ * Refused options: InnerGS != 0 and NoInv != 0 (the block solve has neither, as in bwgr_mrr).  cores and verbose have no counterpart.
+ * Outputs (host; u and numit are required, the others may be null): TrZSZ [neff x k, effect e at e * k]; b: f x k column-major; u[e]: p_e x k
+ * column-major; vb[e], GC[e]: k x k (GC with the max(sd, 1e-12) floor); ve [k]; hat: n x k column-major, X b + sum Z_r u_r for every row;
+ * cnv [max(maxit, 1)]: the value after every sweep run (10 where none ran); bend [neff].
+ * BWGR_EINVAL, the panels stay usable: what bwgr_pegs refuses of its effects and of maxit / logtol / covbend / covMinEv, df0 not finite or
+ * negative, f < 1 or f > BWGR_PEGSX_MAXF, ldx < n, a non-finite entry of X, a trait with fewer than 2 records, InnerGS, NoInv.
+ * Not here: MLM (it projects Z off X, which makes the int8 panel dense), PEGS_sparse and PEGSZ_sparse (the engine has no sparse storage). */
+#define BWGR_PEGSX_MAXF 256
+int bwgr_pegsx(int device, const bwgr_pegs_effect *eff, int neff, const double *X, int64_t ldx, int f, const double *Y, int64_t n, int k, int maxit,
+               double logtol, double covbend, double covMinEv, double df0, int NNC, int XFA, int NumXFA, int InnerGS, int NoInv, double *TrZSZ,
+               double *b, double *const *u, double *const *vb, double *const *GC, double *ve, double *hat, int *numit, double *cnv, double *bend);
+/* host arithmetic of bwgr_pegsx (needs no GPU) for n rows, f columns of X and k traits (n >= 1, 1 <= f <= BWGR_PEGSX_MAXF, 1 <= k <= 16, else
+ * BWGR_EINVAL): out[0] the threads of each of the k workgroups of the fixed step (one row per thread up to 1024, whole waves), out[1] its
+ * dynamic LDS bytes (two f-vectors), out[2] the bytes of X, the pseudo-inverses of up to k patterns and b on the device; the trace kernels'
+ * tiling: out[3] the columns of an effect a wave carries at once, out[4] the columns of X per register tile, out[5] their dynamic LDS bytes
+ * (four waves' v plus the per-wave totals). */
+#define BWGR_PEGSX_PLAN_NOUT 6
+int bwgr_debug_pegsx_plan(int64_t n, int f, int k, int64_t out[BWGR_PEGSX_PLAN_NOUT]);
+/* timing of bwgr_pegsx for tools/pegsx_probe.py (process-wide, not thread-safe; off by default): sets the mode of the calls that follow --
+ * 0: off; 1: the set-up kernels are bracketed with events (outside the sweeps) and every sweep is timed with the host clock, which adds no
+ * synchronisation to a sweep; 2: k_pegsx_fixed is bracketed with events as well -- and copies out what the last timed call left, in ms:
+ * out[0] the trace kernels, out[1] the effects' own set-up kernels (k_mrr_setup_cols / k_pegs_dense_setup), out[2] the sweeps timed,
+ * out[3..5] mean / min / max of a sweep, out[6..8] mean / min / max of the fixed step alone (mode 2).  out may be null. */
+#define BWGR_PEGSX_TIMING_NOUT 9
+int bwgr_debug_pegsx_timing(int mode, double out[BWGR_PEGSX_TIMING_NOUT]);
 /* out (n x k, host, column-major) = X B on the raw int8 genotypes for every row; B: p x k, host, column-major.  fp64 sums; the markers are
  * split over workgroups and the partial sums added in a fixed order, so two calls give the same bits, and so does a panel switched to implicit
  * centring.  BWGR_EINVAL: a null pointer, k < 1, an fp32 panel.  (bwgr_uvbeta's own xb output is a different summation order.) */

@@ -137,7 +137,7 @@ YSEMF <- function(Y, X, npc = -1L) {
 # argument order, defaults and return lists.  An effect is a panel effect -- a panel handle, an integer matrix or an integer-valued numeric
 # matrix within int8 range, staged as int8 genotypes and NOT centred -- or a dense effect: a numeric matrix with a non-integer value, or any
 # matrix passed as dense(Z).  Y and the real options are float-rounded, as the reference receives them.  The marker order of a sweep is the
-# library's own (the reference seeds it from the machine).  PEGSX, PEGS_sparse and PEGSZ_sparse are not here.
+# library's own (the reference seeds it from the machine).  PEGS_sparse and PEGSZ_sparse are not here (the engine has no sparse storage).
 dense <- function(Z) structure(as.matrix(Z) * 1.0, class = c("bwgr_dense", "matrix"))
 .bwgr_pegs_effect <- function(X) {
   if (inherits(X, "externalptr")) return(X)
@@ -165,6 +165,27 @@ PEGS <- function(Y, X, maxit = 100L, logtol = -4.0, covbend = 1.1, covMinEv = 10
 }
 PEGSZ <- function(Y, X_list, maxit = 100L, logtol = -4.0, covbend = 1.1, covMinEv = 10e-4, XFA = -1L, NNC = TRUE)
   .bwgr_pegs(Y, X_list, maxit, logtol, covbend, covMinEv, XFA, NNC, 0L)
+# fixed effects beside the random effects, R/RcppExports.R:284 (PEGSX; src/RcppEigenX20251203.cpp:197-573): same name, argument order, defaults
+# and return list.  X is the fixed design (an intercept is a column of it; nothing is centred); every element of Z_list is an effect as for
+# PEGSZ.  Y, X, the dense effects and the real options are float-rounded.  InnerGS = TRUE and NoInv = TRUE are refused by the library; cores
+# and verbose are accepted and ignored.  MLM is not here: it projects Z off X, which makes the int8 panel dense.
+PEGSX <- function(Y, X, Z_list, maxit = 500L, logtol = -8.0, covbend = 1.1, covMinEv = 10e-4, cores = 1L, verbose = FALSE, df0 = 1.1, NNC = FALSE,
+                  InnerGS = FALSE, NoInv = FALSE, XFA = FALSE, NumXFA = 3L) {
+  eff <- lapply(Z_list, .bwgr_pegs_effect)
+  set <- .Call("bwgrhip_pegs_set", length(eff))
+  for (i in seq_along(eff)) {
+    isz <- is.matrix(eff[[i]])
+    if (isz) eff[[i]] <- .bwgr_f32(eff[[i]])
+    pan <- if (isz) NULL else eff[[i]]
+    Z <- if (isz) eff[[i]] else NULL
+    .Call("bwgrhip_pegs_put", set, i - 1L, pan, Z)
+  }
+  opts <- c(as.integer(maxit), .bwgr_f32(logtol), .bwgr_f32(covbend), .bwgr_f32(covMinEv), .bwgr_f32(df0), as.logical(NNC), as.logical(InnerGS),
+            as.logical(NoInv), as.logical(XFA), as.integer(NumXFA)) * 1.0
+  r <- .Call("bwgrhip_pegsx", set, .bwgr_f32(as.matrix(Y)), .bwgr_f32(as.matrix(X) * 1.0), opts)
+  rm(eff)
+  r
+}
 # two designs in one sweep, R/RcppExports.R:200, 208, 212 (solver2x, MEGA, GSEM; src/RcppEigen20230423.cpp:1446-1493, :1542-1610): same names,
 # argument order, defaults and return lists; doubles throughout.  solver2x's X1 is the dense design and X2 the integer genotypes (an int8
 # panel), as MEGA and GSEM call it; a dense X2 is not taken.  MEGA refuses a trait without records (the reference's imputed column is NaN);

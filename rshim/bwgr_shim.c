@@ -458,6 +458,51 @@ SEXP bwgrhip_pegs(SEXP set, SEXP Y, SEXP maxit, SEXP logtol, SEXP covbend, SEXP 
   return out;
 }
 
+/* PEGSX(Y, X, Z_list, maxit, logtol, covbend, covMinEv, cores, verbose, df0, NNC, InnerGS, NoInv, XFA, NumXFA) src/RcppEigenX20251203.cpp:197-573
+ * -> list(TrZSZ, b, u, vb_list, GC_list, ve, hat, its, cnv, bend); TrZSZ, u, vb_list and GC_list are lists with one entry per effect.  The
+ * effects are a set made as for PEGSZ.  Y, X and the dense effects: float-rounded by the R front-end, NA in Y = missing.  opts: the numeric
+ * vector c(maxit, logtol, covbend, covMinEv, df0, NNC, InnerGS, NoInv, XFA, NumXFA); the library refuses InnerGS and NoInv. */
+SEXP bwgrhip_pegsx(SEXP set, SEXP Y, SEXP X, SEXP opts) {
+  pegs_set *S = (pegs_set *)R_ExternalPtrAddr(set);
+  if (!S) Rf_error("bad effect set");
+  SEXP dy = Rf_getAttrib(Y, R_DimSymbol), dx = Rf_getAttrib(X, R_DimSymbol);
+  if (Rf_length(dy) != 2 || Rf_length(dx) != 2 || TYPEOF(X) != REALSXP) Rf_error("Y and X must be numeric matrices");
+  if (TYPEOF(opts) != REALSXP || Rf_length(opts) != 10) Rf_error("opts must hold 10 numbers");
+  const double *o = REAL(opts);
+  const int n = INTEGER(dy)[0], k = INTEGER(dy)[1], f = INTEGER(dx)[1], m = S->neff, mit = (int)o[0];
+  if (INTEGER(dx)[0] != n) Rf_error("nrow(X) must equal nrow(Y)");
+  for (int i = 0; i < m; i++)
+    if (!S->e[i].panel && (!S->e[i].Z || S->e[i].ldz != n)) Rf_error("every effect must be set and have nrow(Y) rows");
+  SEXP b = PROTECT(Rf_allocMatrix(REALSXP, f, k)), ve = PROTECT(Rf_allocVector(REALSXP, k)), hat = PROTECT(Rf_allocMatrix(REALSXP, n, k));
+  SEXP bend = PROTECT(Rf_allocVector(REALSXP, m)), tl = PROTECT(Rf_allocVector(VECSXP, m)), ul = PROTECT(Rf_allocVector(VECSXP, m));
+  SEXP vl = PROTECT(Rf_allocVector(VECSXP, m)), gl = PROTECT(Rf_allocVector(VECSXP, m));
+  double **up = (double **)R_alloc((size_t)m, sizeof(double *)), **vp = (double **)R_alloc((size_t)m, sizeof(double *));
+  double **gp = (double **)R_alloc((size_t)m, sizeof(double *)), *tr = (double *)R_alloc((size_t)m * (size_t)(k > 0 ? k : 1), sizeof(double));
+  for (int i = 0; i < m; i++) {
+    SEXP u = PROTECT(Rf_allocMatrix(REALSXP, S->cols[i], k)), v = PROTECT(Rf_allocMatrix(REALSXP, k, k)), g = PROTECT(Rf_allocMatrix(REALSXP, k, k));
+    SET_VECTOR_ELT(ul, i, u); SET_VECTOR_ELT(vl, i, v); SET_VECTOR_ELT(gl, i, g);
+    up[i] = REAL(u); vp[i] = REAL(v); gp[i] = REAL(g);
+    UNPROTECT(3);
+  }
+  double *cnv = (double *)R_alloc(mit > 0 ? mit : 1, sizeof(double));
+  int its = 0;
+  chk(bwgr_pegsx(0, S->e, m, REAL(X), (int64_t)n, f, REAL(Y), (int64_t)n, k, mit, o[1], o[2], o[3], o[4], o[5] != 0, o[8] != 0, (int)o[9], o[6] != 0, o[7] != 0,
+                 tr, REAL(b), up, vp, gp, REAL(ve), REAL(hat), &its, cnv, REAL(bend)));
+  for (int i = 0; i < m; i++) {
+    SEXP t = PROTECT(Rf_allocVector(REALSXP, k));
+    for (int j = 0; j < k; j++) REAL(t)[j] = tr[(size_t)i * k + j];
+    SET_VECTOR_ELT(tl, i, t);
+    UNPROTECT(1);
+  }
+  const char *nm[] = {"TrZSZ", "b", "u", "vb_list", "GC_list", "ve", "hat", "its", "cnv", "bend"};
+  SEXP out = PROTECT(named_list(10, nm));
+  SET_VECTOR_ELT(out, 0, tl); SET_VECTOR_ELT(out, 1, b); SET_VECTOR_ELT(out, 2, ul); SET_VECTOR_ELT(out, 3, vl); SET_VECTOR_ELT(out, 4, gl);
+  SET_VECTOR_ELT(out, 5, ve); SET_VECTOR_ELT(out, 6, hat); SET_VECTOR_ELT(out, 7, Rf_ScalarReal((double)its)); SET_VECTOR_ELT(out, 8, Rf_ScalarReal(cnv[its > 0 ? its - 1 : 0]));
+  SET_VECTOR_ELT(out, 9, bend);
+  UNPROTECT(9);
+  return out;
+}
+
 /* relationship kernels: GRM(X, Code012) / GAU(X) src/Rcpp20260726ai.cpp:1338-1383, EigenARC / EigenGAU / EigenGRM(X, ., cores)
  * src/RcppEigen20230423.cpp:8-51 -> an n x n numeric matrix.  kind: BWGR_K_*; par: phi; flag: Code012 / centralizeZ / centralizeX. */
 SEXP bwgrhip_kernel(SEXP panel, SEXP kind, SEXP par, SEXP flag) {
@@ -523,6 +568,7 @@ static const R_CallMethodDef CallEntries[] = {   /* as src/RcppExports.cpp:1152-
   {"bwgrhip_uvbeta_dense", (DL_FUNC)&bwgrhip_uvbeta_dense, 6}, {"bwgrhip_panel_xb", (DL_FUNC)&bwgrhip_panel_xb, 2},
   {"bwgrhip_uvbeta2", (DL_FUNC)&bwgrhip_uvbeta2, 6},
   {"bwgrhip_pegs_set", (DL_FUNC)&bwgrhip_pegs_set, 1}, {"bwgrhip_pegs_put", (DL_FUNC)&bwgrhip_pegs_put, 4}, {"bwgrhip_pegs", (DL_FUNC)&bwgrhip_pegs, 9},
+  {"bwgrhip_pegsx", (DL_FUNC)&bwgrhip_pegsx, 4},
   {"bwgrhip_kernel", (DL_FUNC)&bwgrhip_kernel, 4}, {"bwgrhip_crossprod", (DL_FUNC)&bwgrhip_crossprod, 1},
   {"bwgrhip_kernel2", (DL_FUNC)&bwgrhip_kernel2, 4}, {"bwgrhip_crossprod2", (DL_FUNC)&bwgrhip_crossprod2, 2}, {NULL, NULL, 0}};
 
