@@ -1192,6 +1192,15 @@ def pegsx_plan(n, f, k):
     return dict(zip(("threads", "lds_bytes", "ws_bytes", "jc", "fc", "trace_lds_bytes"), [int(v) for v in out]))
 
 
+def pegs_launch_plan(n, m):
+    """bwgr_debug_pegs_launch_plan (host arithmetic, no GPU) for n rows and an effect of m columns: dict(trace_wg, trace_cols, setup_wg,
+    setup_cols, leg_threads, fixed_threads) -- the trace kernels' workgroups and the columns one trip of them covers, the same of
+    k_pegs_dense_setup, the threads of k_pegs_dense_leg and of k_pegsx_fixed."""
+    out = (C.c_int64 * 6)()
+    check(_lib.lib().bwgr_debug_pegs_launch_plan(int(n), int(m), out))
+    return dict(zip(("trace_wg", "trace_cols", "setup_wg", "setup_cols", "leg_threads", "fixed_threads"), [int(v) for v in out]))
+
+
 def pegsx_timing(mode):
     """bwgr_debug_pegsx_timing: sets the timing mode of the PEGSX calls that follow (0 off, 1 set-up and sweeps, 2 and the fixed step) and
     returns what the last timed call left, in ms."""

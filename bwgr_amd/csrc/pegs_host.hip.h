@@ -25,6 +25,10 @@ extern "C" int bwgr_debug_pegs_plan(int64_t n, int64_t q, int k, int64_t out[BWG
   return BWGR_OK;
 }
 
+// workgroups of k_pegs_dense_setup for an effect of q columns: one column per wave, four per workgroup and trip (bwgr_pegs, bwgr_pegsx and
+// bwgr_debug_pegs_launch_plan share it)
+static inline int64_t pegs_dense_setup_grid(int64_t q) { return std::min<int64_t>((q + 3) / 4, MRR_SETUP_WG); }
+
 // a dense effect on the device
 struct PegsDense {
   int64_t q = 0;
@@ -145,7 +149,7 @@ extern "C" int bwgr_pegs(int device, const bwgr_pegs_effect *eff, int neff, cons
       const PegsDense &D = dense[(size_t)e];
       HIPCHK(h2d(st, D.Zd, Zc[(size_t)e].data(), Zc[(size_t)e].size()));
       HIPCHK(zero(st, D.bd, (size_t)D.q * k));
-      hipLaunchKernelGGL(k_pegs_dense_setup, dim3((unsigned)std::min<int64_t>((D.q + 3) / 4, MRR_SETUP_WG)), dim3(TAIL_THREADS), 0, st, (const double *)D.Zd, n, D.q, ld,
+      hipLaunchKernelGGL(k_pegs_dense_setup, dim3((unsigned)pegs_dense_setup_grid(D.q)), dim3(TAIL_THREADS), 0, st, (const double *)D.Zd, n, D.q, ld,
                          (const uint32_t *)ztd, (const double *)yd, mc, D.XXd, D.XSXd, D.tilde);
       HIPCHK(hipGetLastError());
       HIPCHK(reduce(D.bd, D.tilde, D.XSXd, D.q, 2, k, MSx.data() + (size_t)e * k));

@@ -28,6 +28,17 @@ extern "C" int bwgr_debug_pegsx_plan(int64_t n, int f, int k, int64_t out[BWGR_P
   return BWGR_OK;
 }
 
+// The grids and workgroup sizes bwgr_pegs and bwgr_pegsx launch for n rows and an effect of m columns, from the functions the launch sites call
+extern "C" int bwgr_debug_pegs_launch_plan(int64_t n, int64_t m, int64_t out[BWGR_PEGS_LAUNCH_PLAN_NOUT]) {
+  if (!out) return fail(BWGR_EINVAL, "pegs launch plan: null pointer");
+  if (n < 1 || m < 1) return fail(BWGR_EINVAL, "pegs launch plan: n = %lld, m = %lld (each at least 1)", (long long)n, (long long)m);
+  const int64_t tg = pegsx_trace_grid(m), sg = pegs_dense_setup_grid(m);
+  out[0] = tg; out[1] = tg * 4 * PEGSX_JC;                       // (the trace kernels run four waves, PEGSX_JC columns each)
+  out[2] = sg; out[3] = sg * (TAIL_THREADS / 64);
+  out[4] = pegs_dense_plan(n, 1, 1).threads; out[5] = pegsx_plan(n, 1, 1).threads;
+  return BWGR_OK;
+}
+
 // Timing for tools/pegsx_probe.py, off unless asked for: mode 1 times the set-up kernels with events (outside the sweeps) and every sweep with
 // the host clock (a sweep ends in a synchronous copy, so the clock adds no synchronisation); mode 2 also brackets k_pegsx_fixed with events.
 static int g_pegsx_timing = 0;
@@ -195,7 +206,7 @@ extern "C" int bwgr_pegsx(int device, const bwgr_pegs_effect *eff, int neff, con
       HIPCHK(h2d(st, D.Zd, Zc[(size_t)e].data(), Zc[(size_t)e].size()));
       HIPCHK(zero(st, D.bd, (size_t)D.q * k));
       if (timing) HIPCHK(hipEventRecord(ev0, st));
-      hipLaunchKernelGGL(k_pegs_dense_setup, dim3((unsigned)std::min<int64_t>((D.q + 3) / 4, MRR_SETUP_WG)), dim3(TAIL_THREADS), 0, st, (const double *)D.Zd, n, D.q, ld,
+      hipLaunchKernelGGL(k_pegs_dense_setup, dim3((unsigned)pegs_dense_setup_grid(D.q)), dim3(TAIL_THREADS), 0, st, (const double *)D.Zd, n, D.q, ld,
                          (const uint32_t *)ztd, (const double *)yd, mc, D.XXd, D.XSXd, D.tilde);
       HIPCHK(hipGetLastError());
       if (timing) HIPCHK(lap(ms_cols));

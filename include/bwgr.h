@@ -443,6 +443,13 @@ int bwgr_pegsx(int device, const bwgr_pegs_effect *eff, int neff, const double *
  * (four waves' v plus the per-wave totals). */
 #define BWGR_PEGSX_PLAN_NOUT 6
 int bwgr_debug_pegsx_plan(int64_t n, int f, int k, int64_t out[BWGR_PEGSX_PLAN_NOUT]);
+/* host arithmetic of the launch shapes of bwgr_pegs and bwgr_pegsx (needs no GPU), in the style of bwgr_debug_launch_plan, for n rows and an
+ * effect of m columns (each at least 1, else BWGR_EINVAL).  out[0..1], k_pegsx_trace_panel / k_pegsx_trace_dense: their workgroups (= partials
+ * per pattern, at most 1024; four waves each, a wave four columns at once) and the columns one trip of that grid covers.  out[2..3],
+ * k_pegs_dense_setup: its workgroups (at most 8192, one column per wave) and the columns per trip.  out[4]: the threads of the one workgroup
+ * of k_pegs_dense_leg; out[5]: the threads of each workgroup of k_pegsx_fixed (both one row per thread up to 1024, whole waves). */
+#define BWGR_PEGS_LAUNCH_PLAN_NOUT 6
+int bwgr_debug_pegs_launch_plan(int64_t n, int64_t m, int64_t out[BWGR_PEGS_LAUNCH_PLAN_NOUT]);
 /* timing of bwgr_pegsx for tools/pegsx_probe.py (process-wide, not thread-safe; off by default): sets the mode of the calls that follow --
  * 0: off; 1: the set-up kernels are bracketed with events (outside the sweeps) and every sweep is timed with the host clock, which adds no
  * synchronisation to a sweep; 2: k_pegsx_fixed is bracketed with events as well -- and copies out what the last timed call left, in ms:

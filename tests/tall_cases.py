@@ -17,7 +17,15 @@ workgroups covers.  The trips, from the plans (256 threads per workgroup):
   pxb        (row tiles, 16-column slices, marker chunks, markers per chunk) of k_pxb; pxb_cross: a 1 024-row tile that spans two slabs
 
 The two-design fits -- uvbeta2, MEGA, GSEM -- run on tall9k and slab1280 through the same pass, row reduction and panel_xb; their inputs and
-the restatement's results on them are at the end of this file.  The two-panel shapes are in tests/pair_cases.py.
+the restatement's results on them follow the plans.  The two-panel shapes are in tests/pair_cases.py.
+
+PEGS, PEGSZ and PEGSX (the last section; bwgr_debug_pegs_launch_plan, bwgr_debug_pegsx_plan, bwgr_debug_pegs_plan) run mrr's launch train
+uncentred on wide33k, tall16k, slab1280 and slab1024, and their own kernels beside it.  Their trips:
+  trace      ceil(ceil(m / 4) / (workgroups x 4)): k_pegsx_trace_panel / _dense, a wave four columns of the effect at once; the per-wave totals
+             carry across a wave's trips, and k_mrr_finish adds as many partials as there are workgroups (1 024 at the cap)
+  dsetup     ceil(q / (workgroups x 4)): k_pegs_dense_setup, one column per wave
+  rows       ceil(n / threads): the row loops of k_pegs_dense_leg and k_pegsx_fixed (1 024 threads from 961 rows on)
+  fixed_cols ceil(f / (threads / 64)): the fixed step's column loop, one wave per column of X;  quad  ceil(f / 64): the trace's quadratic form
 """
 import ctypes as C
 import functools
@@ -26,6 +34,8 @@ import numpy as np
 
 from conftest import synth_small
 import driver_cases as dc
+import pegs_cases as PC
+import pegsx_cases as XC
 
 # tag -> n, p, block (0 = the default), seed of the genotypes
 CASES = {
@@ -179,3 +189,191 @@ def data(tag):
     X = np.asfortranarray(synth_small(c["n"], c["p"], seed=c["seed"])[0])
     X.setflags(write=False)
     return X
+
+
+# ---- PEGS / PEGSZ / PEGSX ----
+# rows missing in every trait (uvbeta's own traits use the first three entries as they stand): in the first and the last slab and on both
+# sides of a slab boundary; on tall16k the last lies beyond k_mrr_ey's first trip
+ALL_MISSING = {"tall9k": (7, 4095, 4096, 8500), "slab1280": (7, 1279, 1280, 4990), "slab1024": (7, 1023, 1024, 1990)}
+# PEGS' traits on tall9k also miss the four rows 4096 .. 4099, which one lane of the trace kernels loads as one quad at the start of the 17th
+# slab: the whole-quad skip of the trace and the unobserved-row skip of the fixed step happen at a slab edge
+PEGS_MISSING = dict(ALL_MISSING, tall9k=(7, 4095, 4096, 4097, 4098, 4099, 8500), tall16k=(7, 8191, 8192, 16400))
+
+# job -> the panel's shape tag (None: no panel; "slabs900": tests/pegs_cases.py's 700 x 900 panel in three slabs, not on CASES because no
+# other family needs it here), k, f (PEGSX), maxit, the effects in list order ("panel" or the q of a dense gauss(n, q, 503)), the seed of the
+# traits (the shape's seed + 70) and the entries that run it.  PEGS takes one design: on tall9k and slab1280 it runs the panel alone.
+# dense16501 is a TrZSZ-only job (maxit = 0): 33 000 and 16 500 are multiples of four, so no other job has a partial last group of columns.
+PEGS_JOBS = {
+    "wide33k":    dict(tag="wide33k",  k=3, f=3,   maxit=2, effects=("panel",),    entries=("PEGS", "PEGSZ", "PEGSX")),
+    "tall16k":    dict(tag="tall16k",  k=4, f=3,   maxit=3, effects=("panel",),    entries=("PEGS", "PEGSZ", "PEGSX")),
+    "tall9k":     dict(tag="tall9k",   k=3, f=3,   maxit=3, effects=("panel", 5),  entries=("PEGS", "PEGSZ", "PEGSX")),
+    "tall9k_rev": dict(tag="tall9k",   k=3, f=3,   maxit=3, effects=(5, "panel"),  entries=("PEGSZ",)),
+    "slab1280":   dict(tag="slab1280", k=3, f=17,  maxit=3, effects=("panel", 5),  entries=("PEGS", "PEGSZ", "PEGSX")),
+    "slab1024":   dict(tag="slab1024", k=3, f=3,   maxit=3, effects=("panel",),    entries=("PEGS", "PEGSZ", "PEGSX")),
+    "dense16500": dict(tag=None, n=196, seed=2907, k=3, f=3, maxit=2, effects=(16500,), entries=("PEGSZ", "PEGSX")),
+    "dense16501": dict(tag=None, n=196, seed=2907, k=3, f=3, maxit=0, effects=(16501,), entries=("PEGSX",)),
+    "f256":       dict(tag="slabs900", k=3, f=256, maxit=4, effects=("panel",),    entries=("PEGSX",)),
+}
+TRZSZ_ALONE = ("wide33k", "dense16500", "dense16501", "f256")     # a maxit = 0 run that checks TrZSZ by itself
+NORMAL_EQUATIONS = ("tall9k", "slab1280")
+
+# What each job is there for, as pegs_plans must report it.  m: the columns of the effect the trace figures speak of; trace_last: the trip
+# (1-based) on which the last group of four columns runs; trace_tail: columns of that group.  dsetup = 1 on dense16500: k_pegs_dense_setup
+# covers 32 768 columns per trip, twice the trace kernels' 16 384, and the job is not grown for it.
+PEGS_EXPECT = {
+    "wide33k":    dict(m=33000, trace_wg=1024, trace=3, trace_last=3, trace_tail=4, mrr_tilde=3, mrr_setup=2, last64=40, K=1),
+    "tall16k":    dict(mrr_ey=2, K=65, R=256, last64=2, npat=4),
+    "tall9k":     dict(ld=9216, ld128=9088, pad=216, leg_threads=1024, fixed_threads=1024, rows=9, npat=3),
+    "tall9k_rev": dict(ld=9216, ld128=9088, pad=216, leg_threads=1024, rows=9),
+    "slab1280":   dict(R=1280, K=4, ld=5120, fixed_threads=1024, fixed_cols=2, rows=5),
+    "slab1024":   dict(R=1024, K=2, ld=2048, rows=2),
+    "dense16500": dict(m=16500, trace_wg=1024, trace=2, trace_last=2, trace_tail=4, dsetup=1, dsetup_wg=4125, ld=256),
+    "dense16501": dict(m=16501, trace_wg=1024, trace=2, trace_last=2, trace_tail=1, dsetup=1),
+    "f256":       dict(K=3, R=256, ld=768, quad=4, lds_trace=33280, lds_fixed=4096, fixed_threads=704, fixed_cols=24),
+}
+
+
+def _pegs_shape(job):
+    """n, the genotypes (or None), the seed of the shape and the panel's kwargs"""
+    j = PEGS_JOBS[job]
+    if j["tag"] is None:
+        return j["n"], None, j["seed"], {}
+    if j["tag"] == "slabs900":
+        Z = XC.slabs900()
+        return Z.shape[0], Z, 3, dict(nwg=3)
+    return CASES[j["tag"]]["n"], data(j["tag"]), CASES[j["tag"]]["seed"], panel_kw(j["tag"])
+
+
+@functools.lru_cache(maxsize=None)
+def _pegs_dense(n, q):
+    Z = PC.gauss(n, q, 503)
+    Z.setflags(write=False)
+    return Z
+
+
+@functools.lru_cache(maxsize=None)
+def pegs_data(job):
+    """(Y, effects) of a job in the form of tests/pegs_cases.py: the traits of the issue -- k traits, each its own missingness pattern, on
+    the job's first design -- with the rows of PEGS_MISSING missing in every trait"""
+    j = PEGS_JOBS[job]
+    n, Z, seed, kw = _pegs_shape(job)
+    effects = [("panel", Z, kw) if e == "panel" else ("dense", _pegs_dense(n, e)) for e in j["effects"]]
+    lead = Z if Z is not None else effects[0][1]
+    Y = PC.traits(lead, j["k"], 0, seed=seed + 70, patterns=[0.1, 0.0, 0.25, 0.05][:j["k"]])
+    if j["tag"] in PEGS_MISSING:
+        Y[list(PEGS_MISSING[j["tag"]])] = np.nan
+    assert len({np.isnan(Y[:, t]).tobytes() for t in range(j["k"])}) == j["k"], job
+    Y.setflags(write=False)
+    return Y, effects
+
+
+@functools.lru_cache(maxsize=None)
+def _pegsx_data(job):
+    j = PEGS_JOBS[job]
+    Y, effects = pegs_data(job)
+    X = XC.fixed(Y.shape[0], j["f"] - 1, 501)
+    Yx = XC.with_fixed(Y, X, 502)
+    Yx.setflags(write=False); X.setflags(write=False)
+    return Yx, X, effects
+
+
+@functools.lru_cache(maxsize=None)
+def pegs_case(entry, job):
+    """the job as a case of tests/pegs_cases.py (PEGS, PEGSZ) or tests/pegsx_cases.py (PEGSX), so that their restate() computes its
+    restatement once per process and the guards of tests/test_pegs_cpu.py / tests/test_pegsx_cpu.py run on it as they stand"""
+    j = PEGS_JOBS[job]
+    assert entry in j["entries"], (entry, job)
+    kw = dict(maxit=j["maxit"], logtol=PC.NOSTOP)
+    if entry == "PEGSX":
+        return dict(id="tall/PEGSX/" + job, job=job, data=lambda: _pegsx_data(job), kw=kw)
+
+    def data():
+        Y, effects = pegs_data(job)
+        return Y, effects[:1] if entry == "PEGS" else effects
+    if entry == "PEGS":
+        assert j["effects"][0] == "panel"
+    return dict(id="tall/%s/%s" % (entry, job), job=job, entry=entry, data=data, kw=kw)
+
+
+def pegs_jobs(entry):
+    return [job for job, j in PEGS_JOBS.items() if entry in j["entries"]]
+
+
+def _panel_plan(n, p, block, nwg):
+    """K, R, ld of bwgr_debug_panel_plan for an int8 main panel made with these block / nwg arguments"""
+    from bwgr_amd import _lib
+    out = (C.c_int64 * 25)()
+    rc = _lib.lib().bwgr_debug_panel_plan(0, int(n), int(p), int(block), int(nwg), 0, -1, 1, out)
+    assert rc == 0, _lib.lib().bwgr_last_error().decode()
+    return dict(K=int(out[1]), R=int(out[2]), ld=int(out[3]))
+
+
+def pegs_plans(job):
+    """Everything PEGS_EXPECT speaks of, for one job, from the library's own host arithmetic."""
+    import bwgr_amd
+    j = PEGS_JOBS[job]
+    n, Z, _, kw = _pegs_shape(job)
+    k, f = j["k"], j["f"]
+    ms = [Z.shape[1] if e == "panel" else e for e in j["effects"]]
+    pl = dict(n=n, ld128=_ceil(n, 128) * 128)
+    if Z is not None:
+        pp = _panel_plan(n, Z.shape[1], kw.get("block", 0), kw.get("nwg", 0))
+        pl.update(K=pp["K"], R=pp["R"], ld=pp["ld"])
+        p = Z.shape[1]
+        rc, lp = launch_plan(n, pl["ld"], p, k)
+        assert rc == 0
+        t = lp["threads"]
+        pl["mrr_ey"] = _ceil(pl["ld"], lp["mrr_np"] * t)
+        pl["mrr_tilde"] = _ceil(p, lp["mrr_np"] * t)
+        pl["mrr_setup"] = _ceil(p, lp["mrr_setup_wg"] * (t // 64))
+        pl["last64"] = p - (_ceil(p, 64) - 1) * 64
+    else:
+        pl["ld"] = pl["ld128"]          # (a dense effect alone pads its rows to 128)
+    pl["pad"] = pl["ld"] - n
+    m = pl["m"] = max(ms)
+    xp = bwgr_amd.pegsx_plan(n, f, k)
+    gp = bwgr_amd.pegs_launch_plan(n, m)
+    assert gp["fixed_threads"] == xp["threads"] and gp["leg_threads"] == bwgr_amd.pegs_plan(n, 1, k)["threads"]
+    assert gp["trace_cols"] == gp["trace_wg"] * 4 * xp["jc"] and gp["setup_cols"] == gp["setup_wg"] * 4
+    ngrp = _ceil(m, xp["jc"])
+    pl.update(trace_wg=gp["trace_wg"], trace=_ceil(m, gp["trace_cols"]), trace_last=(ngrp - 1) // (gp["trace_wg"] * 4) + 1,
+              trace_tail=m - (ngrp - 1) * xp["jc"], dsetup_wg=gp["setup_wg"], dsetup=_ceil(m, gp["setup_cols"]),
+              leg_threads=gp["leg_threads"], fixed_threads=gp["fixed_threads"], rows=_ceil(n, gp["fixed_threads"]),
+              fixed_cols=_ceil(f, gp["fixed_threads"] // 64), quad=_ceil(f, 64), lds_trace=xp["trace_lds_bytes"], lds_fixed=xp["lds_bytes"])
+    Y = pegs_data(job)[0]
+    pl["npat"] = len({np.isnan(Y[:, t]).tobytes() for t in range(k)})
+    return pl
+
+
+# ---- the handle table's PEGS / PEGSZ / PEGSX calls (tests/test_gpu_handles.py), on the 700 x 900 three-slab panel ----
+# k = 3 (10 % / 0 / 25 % missing), four sweeps; PEGSZ and PEGSX with a dense effect of five columns behind the panel, PEGSX with f = 3;
+# PEGSZ2: the panel's columns split 500 / 400 into two panels.  tests/test_tall_cases_cpu.py runs the branch guards on them too.
+HANDLE_ENTRIES = ("PEGS", "PEGSZ", "PEGSX", "PEGSZ2")
+
+
+@functools.lru_cache(maxsize=None)
+def _handle_data(entry):
+    Z = XC.slabs900()
+    n = Z.shape[0]
+    Y = PC.traits(Z, 3, 0, seed=5, patterns=[0.1, 0.0, 0.25])
+    D = PC.gauss(n, 5, 504)
+    kw = dict(nwg=3)
+    if entry == "PEGSZ2":
+        effects = [("panel", np.asfortranarray(Z[:, :500]), kw), ("panel", np.asfortranarray(Z[:, 500:]), kw)]
+    else:
+        effects = [("panel", Z, kw)] + ([] if entry == "PEGS" else [("dense", D)])
+    if entry != "PEGSX":
+        Y.setflags(write=False)
+        return Y, effects
+    X = XC.fixed(n, 2, 501)
+    Yx = XC.with_fixed(Y, X, 502)
+    Yx.setflags(write=False); X.setflags(write=False)
+    return Yx, X, effects
+
+
+@functools.lru_cache(maxsize=None)
+def handle_case(entry):
+    kw = dict(maxit=4, logtol=PC.NOSTOP)
+    if entry == "PEGSX":
+        return dict(id="handles/PEGSX", data=lambda: _handle_data(entry), kw=kw)
+    return dict(id="handles/" + entry, entry="PEGS" if entry == "PEGS" else "PEGSZ", data=lambda: _handle_data(entry), kw=kw)

@@ -42,6 +42,22 @@ def test_launch_plan_hook_is_host_arithmetic():
     assert L.bwgr_debug_launch_plan(9000, 9000, 200, 17, out) == 1 and b"launch plan" in L.bwgr_last_error()   # BWGR_EINVAL: ld is no multiple of 128
 
 
+def test_pegs_launch_plan_hook_is_host_arithmetic():
+    """bwgr_debug_pegs_launch_plan likewise: declared, bound, exported, BWGR_PEGS_LAUNCH_PLAN_NOUT values and no GPU."""
+    import ctypes as C
+    from bwgr_amd import _lib
+    src = open(os.path.join(ROOT, "include", "bwgr.h")).read()
+    nout = int(re.search(r"#define\s+BWGR_PEGS_LAUNCH_PLAN_NOUT\s+(\d+)", src).group(1))
+    assert "bwgr_debug_pegs_launch_plan" in _declared() and "bwgr_debug_pegs_launch_plan" in _lib.EXPORTS
+    L = _lib.lib()
+    assert len(L.bwgr_debug_pegs_launch_plan.argtypes) == 3
+    out = (C.c_int64 * (nout + 1))(*([-1] * (nout + 1)))
+    assert L.bwgr_debug_pegs_launch_plan(9000, 200, out) == 0
+    assert all(v >= 1 for v in out[:nout]) and out[nout] == -1
+    assert L.bwgr_debug_pegs_launch_plan(9000, 0, out) == 1 and b"pegs launch plan" in L.bwgr_last_error()   # BWGR_EINVAL
+    assert L.bwgr_debug_pegs_launch_plan(9000, 200, None) == 1
+
+
 def test_no_cpu_fallback():
     import bwgr_amd
     if bwgr_amd.device_count() > 0:

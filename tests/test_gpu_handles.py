@@ -21,7 +21,12 @@ against the natural durations of their own launches only.
 
 The two-panel entries (crossprod2, kernel2 on the 700 x 900 root and a 300 x 900 samples panel in slabs of another height) run in the table like
 the others, the samples on the default stream; test_two_panel_entry_on_every_pair_of_handles then puts the founders and the samples on
-different streams and clones."""
+different streams and clones.
+
+PEGS, PEGSZ ([panel, dense of five columns]) and PEGSX (the same effects, f = 3) on the 700 x 900 root issue the library's longest host
+sequences -- 20 to 30 copies, clears and launches per sweep on the first panel's stream -- and stand in the table like the others (their inputs,
+and the branch guards on them, are tests/tall_cases.py's handle_case and tests/test_tall_cases_cpu.py);
+test_two_panel_effects_of_one_pegsz_call_on_different_handles puts the two panel effects of one PEGSZ call on different handles."""
 import functools
 import math
 import os
@@ -34,6 +39,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kernels2_restatement as K2  # noqa: E402
 import kernels_restatement as KR  # noqa: E402
 import mrr_restatement as MR  # noqa: E402
+import pegs_cases as PC  # noqa: E402
+import pegs_restatement as PR  # noqa: E402
+import pegsx_cases as XC  # noqa: E402
+import tall_cases as tc  # noqa: E402
 import sem2_cases as C2  # noqa: E402
 import sem2_restatement as S2  # noqa: E402
 import sem_restatement as SR  # noqa: E402
@@ -358,6 +367,56 @@ def _sem2(name):
     return call, ok
 
 
+PEGS_FLAT = {"PEGS": ("mu", "b", "hat", "h2", "GC", "bend", "cnv"), "PEGSX": ("TrZSZ", "b", "u", "vb_list", "GC_list", "ve", "hat", "bend", "cnv")}
+
+
+def _flat(g, keys, its):
+    """a PEGS / PEGSZ / PEGSX result as a dict of arrays: a list (one entry per effect) becomes key0, key1, ..."""
+    out = {}
+    for key in keys:
+        for i, v in enumerate(g[key]) if isinstance(g[key], list) else [("", g[key])]:
+            out["%s%s" % (key, i)] = np.asarray(v)
+    out["its"] = np.array(g[its])      # (last: the table looks at an entry's first array to see that other inputs gave another result)
+    return out
+
+
+def _pegs_inputs(entry):
+    """(Y, X or None, the effects' data) of tests/tall_cases.py's handle_case; under ALT Y's columns are reversed, as _Y does"""
+    d = tc.handle_case(entry)["data"]()
+    Y = np.ascontiguousarray(d[0][:, ::-1]) if ALT["on"] else d[0]
+    return Y, (d[1] if entry == "PEGSX" else None), d[-1]
+
+
+def _pegs(entry):
+    """PEGS (k = 3, four sweeps), PEGSZ ([panel, dense of five columns]) and PEGSX (the same effects, f = 3) on the slabs panel: the longest
+    host sequences of the library, 20 to 30 copies, clears and launches per sweep on the first panel's stream"""
+    kw = tc.handle_case(entry)["kw"]
+
+    def call(P, aux):
+        import bwgr_amd
+        Y, X, effects = _pegs_inputs(entry)
+        effs = [P] + [bwgr_amd.dense(e[1]) for e in effects[1:]]
+        if entry == "PEGS":
+            return _flat(bwgr_amd.PEGS(Y, P, cnv_trace=True, **kw), PEGS_FLAT["PEGS"] + ("cnv_trace",), "numit")
+        if entry == "PEGSZ":
+            return _flat(bwgr_amd.PEGSZ(Y, effs, cnv_trace=True, **kw), PEGS_FLAT["PEGS"] + ("cnv_trace",), "numit")
+        return _flat(bwgr_amd.PEGSX(Y, X, effs, cnv_trace=True, **kw), PEGS_FLAT["PEGSX"] + ("cnv_trace",), "its")
+
+    def ok(g):
+        case = tc.handle_case(entry)
+        if entry == "PEGSX":
+            o = _flat(XC.restate(case)[3], PEGS_FLAT["PEGSX"], "its")
+        else:
+            o = PC.restate(case)[2]
+            if entry == "PEGS":
+                o = dict(o, b=o["b"][0], GC=o["GC"][0], bend=o["bend"][0])
+            o = _flat(o, PEGS_FLAT["PEGS"], "numit")
+        assert g["its"] == o["its"] == kw["maxit"]
+        for key in o:
+            assert PR.scaled_err(g[key], o[key]) <= TOL, (entry, key)
+    return call, ok
+
+
 NO_INPUTS = ("stats", "crossprod", "GRM_host", "GRM_device", "crossprod2", "kernel2_ARC_host", "kernel2_GAU_device")      # nothing but the panels
 ENTRIES = {
     "KMUP": ("tpod", _kmup, _kmup_ok), "KMUP2": ("tpod", _kmup2, _kmup2_ok),
@@ -370,6 +429,7 @@ ENTRIES = {
     "crossprod2": ("slabs", _crossprod2, _crossprod2_ok), "kernel2_ARC_host": ("slabs",) + _kernel2("ARC", 1.0, False),
     "kernel2_GAU_device": ("slabs",) + _kernel2("GAU", 0.5, True),
     "uvbeta2": ("slabs", _uvb2, _uvb2_ok), "MEGA": ("slabs",) + _sem2("MEGA"), "GSEM": ("slabs",) + _sem2("GSEM"),
+    "PEGS": ("slabs",) + _pegs("PEGS"), "PEGSZ": ("slabs",) + _pegs("PEGSZ"), "PEGSX": ("slabs",) + _pegs("PEGSX"),
 }
 
 
@@ -561,6 +621,78 @@ def test_two_panel_entry_on_every_pair_of_handles(env, name, how):
     _same(first, got, how)
     _same(first, back, "back on the default stream")
     assert bwgr_amd.debug_live() == live
+
+
+# the handles of the two panel effects A and B of one PEGSZ call
+PEGS_PAIR_HANDLES = {"each_on_its_own_stream": ("s", "s2"), "first_clone": ("clone", "root"), "second_clone": ("root", "clone")}
+
+
+def test_two_panel_effects_of_one_pegsz_call_on_different_handles(env):
+    """PEGSZ(Y, [A, B]) with the 700 x 900 panel's columns split 500 / 400 into two Panels: with both roots on the default stream (which
+    passes the restatement's check), with A on one caller's stream and B on another, with A a clone, with B a clone -- the bits of the first
+    every time, and debug_live back to its value.  The first panel's stream carries the whole call; B brings only its resident genotypes,
+    uploaded when it was made.  Before each call every stream of the combination that a caller can reach is kept busy by a filler of FILL
+    times the entry's length, the null stream by a longer one where neither panel sits there (_Env.busy_null), and the temporaries of the
+    call before hold another problem's numbers (the traits' columns reversed).
+
+    What this does not prove: as with the two-panel products, a library that made no ordering between the two handles would pass, since
+    nothing of B's is pending on its stream when the call arrives; what runs off A's stream without a dependency does show."""
+    import bwgr_amd
+    torch = env.torch
+    case = tc.handle_case("PEGSZ2")
+    Y, effects = case["data"]()
+    kw = dict(case["kw"], cnv_trace=True)
+    keys = PEGS_FLAT["PEGS"] + ("cnv_trace",)
+    live0 = bwgr_amd.debug_live()
+    A, B = bwgr_amd.Panel(effects[0][1], **effects[0][2]), bwgr_amd.Panel(effects[1][1], **effects[1][2])
+    try:
+        assert (A.p, B.p, A.ld) == (500, 400, B.ld)
+
+        def call(a, b, Yc=Y):
+            return _flat(bwgr_amd.PEGSZ(Yc, [a, b], **kw), keys, "numit")
+        first = call(A, B)
+        again, entry_ms = env.timed(lambda: call(A, B))
+        live = bwgr_amd.debug_live()
+        _same(first, again, "two calls on the default stream")
+        o = _flat(PC.restate(case)[2], PEGS_FLAT["PEGS"], "numit")
+        assert first["its"] == o["its"] == 4
+        for key in o:
+            assert PR.scaled_err(first[key], o[key]) <= TOL, key
+        streams = {"s": env.s, "s2": env.s2}
+        for how, (ha, hb) in PEGS_PAIR_HANDLES.items():
+            other = call(A, B, np.ascontiguousarray(Y[:, ::-1]))
+            assert not np.array_equal(other["hat"], first["hat"])
+            Qa, Qb = (A.clone() if ha == "clone" else A), (B.clone() if hb == "clone" else B)
+            timers = []
+            try:
+                for Q, h in ((Qa, ha), (Qb, hb)):
+                    if h in streams:
+                        Q.set_stream(streams[h].cuda_stream)
+                idle_null = not ({ha, hb} & {"root", "clone"})
+                null = env.busy_null(entry_ms) if idle_null else None
+                for h in sorted({ha, hb} - {"clone"}):
+                    timers.append(env.busy(entry_ms, torch.cuda.default_stream() if h == "root" else streams[h]))
+                got = call(Qa, Qb)
+                torch.cuda.synchronize()
+                filler_ms = [e0.elapsed_time(e1) for e0, e1 in timers]
+                null_ms = null[0].elapsed_time(null[1]) if idle_null else None
+            finally:
+                for Q, h in ((Qa, ha), (Qb, hb)):
+                    if h == "clone":
+                        Q.close()
+                    else:
+                        Q.set_stream(0)
+            print("PEGSZ [A, B], %s: entry %.3f ms, fillers %s ms%s" % (how, entry_ms, ", ".join("%.3f" % m for m in filler_ms),
+                                                                        ", %.3f ms on the null stream" % null_ms if idle_null else ""))
+            assert filler_ms and all(m >= FILL * entry_ms for m in filler_ms), (filler_ms, entry_ms)
+            assert idle_null == (how == "each_on_its_own_stream") and (not idle_null or null_ms >= max(filler_ms) + entry_ms)
+            _same(first, got, how)
+            assert bwgr_amd.debug_live() == live, how
+        _same(first, call(A, B), "back on the default stream")
+    finally:
+        A.set_stream(0); B.set_stream(0)
+        A.close(); B.close()
+    assert bwgr_amd.debug_live() == live0
 
 
 @pytest.mark.parametrize("model,pi", [("BayesB", 0.9), ("BayesRR", 0.0)])

@@ -113,6 +113,28 @@ def test_pegs_and_pegsz_agree_on_one_effect():
         assert PR.scaled_err(a[key], zz) <= 1e-9, key
 
 
+def test_panel_and_dense_legs_agree_on_the_same_numbers():
+    """PEGSZ(Y, [Panel(tpod)]) runs the int8 launch train, PEGSZ(Y, [dense(tpod as float64)]) k_pegs_dense_leg on the same numbers in the
+    same column order; k = 3, six sweeps.  The two agree to 1e-6 on every output (b, hat, the variance components as h2 and GC, mu, bend,
+    cnv), and each agrees with the restatement."""
+    import bwgr_amd
+    Y, effects = PC.by_id("tpod_k3_defaults")["data"]()
+    Z = effects[0][1]
+    kw = dict(maxit=6, logtol=PC.NOSTOP)
+    o = PR.pegsz(Y, [Z.astype(np.float64)], **kw)
+    P = bwgr_amd.Panel(Z)
+    try:
+        gp = bwgr_amd.PEGSZ(Y, [P], **kw)
+    finally:
+        P.close()
+    gd = bwgr_amd.PEGSZ(Y, [bwgr_amd.dense(Z.astype(np.float64))], **kw)
+    assert gp["numit"] == gd["numit"] == o["numit"] == 6
+    between, ep, ed = _errs(gp, gd, "PEGSZ"), _errs(gp, o, "PEGSZ"), _errs(gd, o, "PEGSZ")
+    print({k: "%.2e" % v for k, v in between.items()}, {k: "%.2e" % v for k, v in ep.items()}, {k: "%.2e" % v for k, v in ed.items()})
+    for errs in (between, ep, ed):
+        assert all(v <= TOL for v in errs.values()), errs
+
+
 def test_two_runs_are_bit_identical():
     case = PC.by_id("pegsz_panel_dense70")
     _same(_fit(case), _fit(case))

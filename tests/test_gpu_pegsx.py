@@ -88,6 +88,17 @@ def test_trzsz_alone(cid):
     assert all(np.all(u == 0) for u in g["u"]) and XR.scaled_err(g["b"], o["b"]) <= TOL and XR.scaled_err(g["hat"], o["hat"]) <= TOL
 
 
+def _normal_equations(Y, X, hat):
+    """the largest |M_t'(Y - hat)_t| over a trait's observed rows, as a fraction of ||M_t|| ||y_t||"""
+    Yf, Xf = np.asarray(Y, np.float32).astype(np.float64), np.asarray(X, np.float32).astype(np.float64)
+    worst = 0.0
+    for t in range(Yf.shape[1]):
+        w = ~np.isnan(Yf[:, t])
+        M, yt = Xf[w], Yf[w, t]
+        worst = max(worst, float(np.max(np.abs(M.T @ (yt - hat[w, t]))) / (np.linalg.norm(M) * np.linalg.norm(yt))))
+    return worst
+
+
 @pytest.mark.parametrize("cid", ["f70_slabs_k5", "dense_only_n1500"])
 def test_normal_equations(cid):
     """M_t'(Y - hat)_t = 0 over a trait's observed rows after any fit, because the fixed step is the last thing that touches the residual:
@@ -95,14 +106,35 @@ def test_normal_equations(cid):
     case = XC.by_id(cid)
     Y, X, effects = case["data"]()
     g = _fit(case)
-    Yf, Xf = np.asarray(Y, np.float32).astype(np.float64), np.asarray(X, np.float32).astype(np.float64)
-    worst = 0.0
-    for t in range(Yf.shape[1]):
-        w = ~np.isnan(Yf[:, t])
-        M, yt = Xf[w], Yf[w, t]
-        worst = max(worst, float(np.max(np.abs(M.T @ (yt - g["hat"][w, t]))) / (np.linalg.norm(M) * np.linalg.norm(yt))))
+    worst = _normal_equations(Y, X, g["hat"])
     print(cid, "normal equations %.2e" % worst)
     assert worst <= 1e-9
+
+
+def test_panel_and_dense_legs_agree_on_the_same_numbers():
+    """tpod as an int8 Panel and as dense(float64): the same numbers in the same column order through the int8 launch train and the panel
+    trace kernel, then through k_pegs_dense_leg and the dense trace kernel.  TrZSZ alone (maxit = 0) and a six-sweep fit: the two agree to
+    1e-6 on TrZSZ, u, hat, ve and vb_list, and each agrees with the restatement (which does not care how an effect is stored: 0 / 1 / 2 are
+    floats already)."""
+    import bwgr_amd
+    Y, X, effects = XC.by_id("tpod_k3_defaults")["data"]()
+    Z = effects[0][1]
+    P = bwgr_amd.Panel(Z)
+    try:
+        for maxit in (0, 6):
+            kw = dict(maxit=maxit, logtol=XC.NOSTOP)
+            o = XR.pegsx(Y, X, [Z.astype(np.float64)], **kw)
+            gp = bwgr_amd.PEGSX(Y, X, [P], **kw)
+            gd = bwgr_amd.PEGSX(Y, X, [bwgr_amd.dense(Z.astype(np.float64))], **kw)
+            assert gp["its"] == gd["its"] == o["its"] == maxit
+            for key in ("TrZSZ", "u", "hat", "ve", "vb_list"):
+                lst = key in LISTS
+                for a, b, r in zip(*[(v[key] if lst else [v[key]]) for v in (gp, gd, o)]):
+                    errs = (XR.scaled_err(a, b), XR.scaled_err(a, r), XR.scaled_err(b, r))
+                    print("maxit", maxit, key, "panel/dense %.2e panel/ref %.2e dense/ref %.2e" % errs)
+                    assert max(errs) <= TOL, (maxit, key, errs)
+    finally:
+        P.close()
 
 
 def test_effect_order_matters_and_each_matches():

@@ -1,11 +1,18 @@
-"""GPU: the fp64 families -- uvbeta, mrr, panel_xb, the relationship kernels, XSEMF / ZSEMF / YSEMF, uvbeta2, MEGA / GSEM -- against their float64 restatements on
+"""GPU: the fp64 families -- uvbeta, mrr, panel_xb, the relationship kernels, XSEMF / ZSEMF / YSEMF, uvbeta2, MEGA / GSEM, PEGS / PEGSZ / PEGSX -- against their float64 restatements on
 the shapes of tests/tall_cases.py: tall panels on which the tail reductions and the passes take a second and a third trip, slabs of 1 280
 and 1 024 rows (and one slab of 1 152: kern1100s, where the slab base is always 0), row tiles of panel_xb across slabs, wide panels on which the marker reductions take a second trip.
 tests/test_tall_cases_cpu.py proves without a GPU that each shape reaches what it is listed for.
 
 The bounds are the project's: mrr_restatement.scaled_err <= 1e-6 for the fits and the kernels (NaN in the same places, equal sweep counts),
 1e-12 for the products (exact integers times doubles, fp64 sums), bit equality for X X' and between calls.  One Panel per shape serves the
-whole module; test_state_between_calls_tall checks that sharing it hides nothing."""
+whole module; test_state_between_calls_tall checks that sharing it hides nothing.
+
+PEGS, PEGSZ and PEGSX run the jobs of tall_cases.PEGS_JOBS: the trace kernels past one grid (wide33k, dense q = 16 500 and 16 501), the
+uncentred launch train where the reductions take further trips and on the other slab heights, a dense effect beside a panel that pads
+further than it would alone (tall9k, in both orders), row loops of nine and five trips at 1 024 threads, f = 17 and f = 256.
+Largest scaled error measured over these jobs on an MI355X: 9.9e-14 (`bend` of PEGSX on tall9k; 9.5e-14 on `vb_list` at f = 256, 5.6e-14 on
+`bend` of PEGS and PEGSZ on wide33k), at most 3.5e-14 on every other figure; TrZSZ alone at most 3.5e-14 (f = 256); the normal equations
+5.8e-17 and 2.0e-17 of ||M_t|| ||y_t|| (bar 1e-9)."""
 import ctypes as C
 import functools
 import os
@@ -17,11 +24,16 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kernels_restatement as KR  # noqa: E402
 import mrr_restatement as MR  # noqa: E402
+import pegs_cases as PC  # noqa: E402
+import pegsx_cases as XC  # noqa: E402
+import pegsx_restatement as XR  # noqa: E402
 import sem_restatement as SR  # noqa: E402
 import tall_cases as tc  # noqa: E402
 import uvb_restatement as UR  # noqa: E402
 from test_gpu_drivers import _raw_panel  # noqa: E402
 from test_gpu_mrr import _check as _mrr_check, _traits  # noqa: E402
+from test_gpu_pegs import _errs as _pegs_errs  # noqa: E402
+from test_gpu_pegsx import _errs as _pegsx_errs, _normal_equations  # noqa: E402
 from test_gpu_sem import _check as _sem_check, _strong, _well_posed  # noqa: E402
 from test_gpu_sem2 import _check as _uvb2_check, _check_driver  # noqa: E402
 from test_gpu_uvb import _check, _f32, _ref, _W  # noqa: E402
@@ -53,7 +65,7 @@ def panel():
 
 # ---- uvbeta ----
 # rows missing in every trait: in the first and the last slab, on both sides of a slab boundary, and (tall9k) beyond k_uvb_rows' first trip
-ALL_MISSING = {"tall9k": (7, 4095, 4096, 8500), "slab1280": (7, 1279, 1280, 4990), "slab1024": (7, 1023, 1024, 1990)}
+ALL_MISSING = tc.ALL_MISSING
 UVB_MAXIT = {"tall9k": 4, "slab1280": 6, "slab1024": 5}
 UVB_JOBS = [("tall9k", v) for v in "DZFX"] + [(t, v) for t in ("slab1280", "slab1024") for v in "DZ"]
 
@@ -348,9 +360,111 @@ def test_two_design_drivers_with_the_references_defaults_on_a_tall_panel(panel, 
         assert MR.scaled_err(again + g["mu"], g["gebv"]) <= 1e-12
 
 
+# ---- PEGS / PEGSZ / PEGSX ----
+class _Effects:
+    """a job's effects as the entries take them: the module's shared Panel where the job's shape is on the table, a Panel of its own (closed
+    on exit) for the 700 x 900 three-slab panel, dense(Z) for a dense effect"""
+
+    def __init__(self, panel, case, effects):
+        import bwgr_amd
+        tag = tc.PEGS_JOBS[case["job"]]["tag"]
+        self.own, self.effs = [], []
+        for e in effects:
+            if e[0] == "dense":
+                self.effs.append(bwgr_amd.dense(e[1]))
+            elif tag in tc.CASES:
+                self.effs.append(panel(tag))
+            else:
+                self.own.append(bwgr_amd.Panel(e[1], **e[2]))
+                self.effs.append(self.own[-1])
+
+    def __enter__(self):
+        return self.effs
+
+    def __exit__(self, *exc):
+        for P in self.own:
+            P.close()
+
+
+def _pegs_job(panel, entry, job):
+    import bwgr_amd
+    case = tc.pegs_case(entry, job)
+    Y, effects, o = PC.restate(case)
+    with _Effects(panel, case, effects) as effs:
+        g = bwgr_amd.PEGS(Y, effs[0], **case["kw"]) if entry == "PEGS" else bwgr_amd.PEGSZ(Y, effs, **case["kw"])
+    errs = _pegs_errs(g, o, entry)
+    print(entry, job, "numit", g["numit"], {k: "%.2e" % v for k, v in errs.items()}, "largest %.2e" % max(errs.values()))
+    assert g["numit"] == o["numit"] == case["kw"]["maxit"]
+    assert all(v <= TOL for v in errs.values()), errs
+    assert g["hat"].shape == Y.shape and np.all(np.isfinite(g["hat"]))      # a row for every individual, missing records included
+    bs = [g["b"]] if entry == "PEGS" else g["b"]
+    assert [b.shape for b in bs] == [(e[1].shape[1], Y.shape[1]) for e in effects]
+
+
+@pytest.mark.parametrize("job", tc.pegs_jobs("PEGS"))
+def test_pegs(panel, job):
+    _pegs_job(panel, "PEGS", job)
+
+
+@pytest.mark.parametrize("job", tc.pegs_jobs("PEGSZ"))
+def test_pegsz(panel, job):
+    _pegs_job(panel, "PEGSZ", job)
+
+
+@pytest.mark.parametrize("job", tc.pegs_jobs("PEGSX"))
+def test_pegsx(panel, job):
+    """the fit against the restatement; on NORMAL_EQUATIONS also M_t'(Y - hat)_t = 0, which does not depend on the restatement"""
+    import bwgr_amd
+    case = tc.pegs_case("PEGSX", job)
+    Y, X, effects, o = XC.restate(case)
+    with _Effects(panel, case, effects) as effs:
+        g = bwgr_amd.PEGSX(Y, X, effs, **case["kw"])
+    errs = _pegsx_errs(g, o)
+    print("PEGSX", job, "its", g["its"], {k: "%.2e" % v for k, v in errs.items()}, "largest %.2e" % max(errs.values()))
+    assert g["its"] == o["its"] == case["kw"]["maxit"]
+    assert all(v <= TOL for v in errs.values()), errs
+    assert g["hat"].shape == Y.shape and np.all(np.isfinite(g["hat"]))
+    assert g["b"].shape == (X.shape[1], Y.shape[1]) and [u.shape for u in g["u"]] == [(e[1].shape[1], Y.shape[1]) for e in effects]
+    if job in tc.NORMAL_EQUATIONS:
+        worst = _normal_equations(Y, X, g["hat"])
+        print("PEGSX", job, "normal equations %.2e" % worst)
+        assert worst <= 1e-9
+
+
+@pytest.mark.parametrize("job", tc.TRZSZ_ALONE)
+def test_pegsx_trzsz_alone(panel, job):
+    """maxit = 0: the trace kernels apart from the sweeps, as tests/test_gpu_pegsx.py's test_trzsz_alone -- three trips of the panel kernel
+    and two of the dense one at 1 024 workgroups, a last group of one column on the second trip, f = 256"""
+    import bwgr_amd
+    case = tc.pegs_case("PEGSX", job)
+    Y, X, effects, o = XC.restate(case, maxit=0)
+    with _Effects(panel, case, effects) as effs:
+        g = bwgr_amd.PEGSX(Y, X, effs, **dict(case["kw"], maxit=0))
+    err = max(XR.scaled_err(a, b) for a, b in zip(g["TrZSZ"], o["TrZSZ"]))
+    print("PEGSX", job, "TrZSZ alone %.2e" % err)
+    assert g["its"] == 0 and g["cnv"] == 10.0 and err <= TOL
+    assert all(np.all(u == 0) for u in g["u"]) and XR.scaled_err(g["b"], o["b"]) <= TOL and XR.scaled_err(g["hat"], o["hat"]) <= TOL
+
+
 # ---- state ----
+def _mrr_around_a_pegsx_call(panel):
+    """mrr on tall16k (a second trip of k_mrr_ey, 65 slabs, centred) before and after a PEGSX call on the same Panel, which runs the same
+    launch train uncentred: the same bits."""
+    import bwgr_amd
+    tag = "tall16k"
+    Y, P = _mrr_traits(tag), panel(tag)
+    Yx, X, _ = tc.pegs_case("PEGSX", tag)["data"]()
+    a = bwgr_amd.MRR3(Y, P, maxit=2, tol=0)
+    x = bwgr_amd.PEGSX(Yx, X, [P], maxit=1, logtol=XC.NOSTOP)
+    b = bwgr_amd.MRR3(Y, P, maxit=2, tol=0)
+    assert x["its"] == 1
+    for key in bwgr_amd.api.MRR_KEYS:
+        assert np.array_equal(a[key], b[key]), key
+
+
 def test_state_between_calls_tall(panel):
-    """uvbeta, mrr, xb and uvbeta again on the module's tall9k panel, then uvbeta on a fresh one: the same bits every time."""
+    """uvbeta, mrr, xb and uvbeta again on the module's tall9k panel, then uvbeta on a fresh one: the same bits every time.  Then mrr on the
+    tall16k panel before and after a PEGSX call on it."""
     import bwgr_amd
     tag = "tall9k"
     X, Y = tc.data(tag), _uvb_traits(tag)
@@ -371,3 +485,4 @@ def test_state_between_calls_tall(panel):
     assert MR.scaled_err(x, a["xb"]) <= 1e-12      # (k_pxb and uvbeta's row-serial product add in different orders)
     for key in ("b", "hat", "vb", "ve"):
         assert np.array_equal(m[key], m2[key]), key
+    _mrr_around_a_pegsx_call(panel)

@@ -182,7 +182,7 @@ def test_entries_are_declared_exported_and_bound():
     from bwgr_amd import _lib
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "bwgr.h")).read(), flags=re.S)
     L = _lib.lib()
-    for name, nargs in (("bwgr_pegs", 21), ("bwgr_debug_pegs_plan", 4)):
+    for name, nargs in (("bwgr_pegs", 21), ("bwgr_debug_pegs_plan", 4), ("bwgr_debug_pegs_launch_plan", 3)):
         assert re.search(r"\b%s\s*\(" % name, hdr) and name in _lib.EXPORTS and hasattr(L, name)
         assert len(getattr(L, name).argtypes) == nargs
     assert "bwgr_pegs_effect" in hdr

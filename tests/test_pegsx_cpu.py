@@ -181,7 +181,7 @@ def test_entries_are_declared_exported_and_bound():
     from bwgr_amd import _lib
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "bwgr.h")).read(), flags=re.S)
     L = _lib.lib()
-    for name, nargs in (("bwgr_pegsx", 29), ("bwgr_debug_pegsx_plan", 4), ("bwgr_debug_pegsx_timing", 2)):
+    for name, nargs in (("bwgr_pegsx", 29), ("bwgr_debug_pegsx_plan", 4), ("bwgr_debug_pegsx_timing", 2), ("bwgr_debug_pegs_launch_plan", 3)):
         assert re.search(r"\b%s\s*\(" % name, hdr) and name in _lib.EXPORTS and hasattr(L, name)
         assert len(getattr(L, name).argtypes) == nargs
         decl = re.search(r"\b%s\s*\(([^;]*)\);" % name, hdr).group(1)

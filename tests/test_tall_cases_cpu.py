@@ -1,10 +1,15 @@
 """CPU: the table of tests/tall_cases.py under the library's own host arithmetic (bwgr_debug_panel_plan, bwgr_debug_uvb_plan,
-bwgr_debug_xxt_plan, bwgr_debug_launch_plan: no GPU).  Every shape of tests/test_gpu_tall.py reaches the loop trip, slab height or chunk
-rule it is listed for; a change of a grid or of a plan rule that moves a shape out of its regime fails here instead of silently dropping
-that code from what the GPU suite compares with a reference."""
+bwgr_debug_xxt_plan, bwgr_debug_launch_plan, bwgr_debug_pegs_launch_plan, bwgr_debug_pegsx_plan, bwgr_debug_pegs_plan: no GPU).  Every shape
+of tests/test_gpu_tall.py reaches the loop trip, slab height or chunk rule it is listed for; a change of a grid or of a plan rule that moves
+a shape out of its regime fails here instead of silently dropping that code from what the GPU suite compares with a reference.  The PEGS /
+PEGSZ / PEGSX jobs also pass, on their restatements, the branch guards that tests/test_pegs_cpu.py and tests/test_pegsx_cpu.py hold their own
+cases to."""
+import numpy as np
 import pytest
 
 import tall_cases as tc
+import test_pegs_cpu as TPC
+import test_pegsx_cpu as TXC
 
 EINVAL = 1
 
@@ -125,3 +130,124 @@ def test_the_old_shapes_did_not_reach_them():
         if n <= 700:
             assert n * n <= pl["kfin_apply_wg"] * t and n * n <= pl["xxt_zero_wg"] * t and pl["pxb_tiles"] == 1
         assert ld // 64 <= pl["uvb_pass_wg"] or n == 4100      # (mrr's pass did take a second tile there; uvbeta never ran on it)
+
+
+# ---- PEGS / PEGSZ / PEGSX ----
+PEGS_RUNS = [(entry, job) for entry in ("PEGS", "PEGSZ", "PEGSX") for job in tc.pegs_jobs(entry)]
+
+
+def test_pegs_launch_plan_is_the_documented_rule():
+    """include/bwgr.h, restated: the trace kernels take a workgroup per sixteen columns up to 1 024, k_pegs_dense_setup one per four columns
+    up to 8 192, the dense leg and the fixed step a thread per row in whole waves up to 1 024 -- and the hook refuses nonsense."""
+    import bwgr_amd
+    for n in (1, 64, 65, 196, 700, 960, 961, 1024, 1500, 9000, 300000):
+        for m in (1, 4, 5, 16, 17, 900, 16384, 16385, 32768, 32769, 33000, 10 ** 6):
+            pl = bwgr_amd.pegs_launch_plan(n, m)
+            assert pl["trace_wg"] == min(-(-(-(-m // 4)) // 4), 1024) and pl["trace_cols"] == 16 * pl["trace_wg"]
+            assert pl["setup_wg"] == min(-(-m // 4), 8192) and pl["setup_cols"] == 4 * pl["setup_wg"]
+            assert pl["leg_threads"] == pl["fixed_threads"] == min(1024, -(-n // 64) * 64)
+            assert pl["fixed_threads"] == bwgr_amd.pegsx_plan(n, 1, 1)["threads"] and pl["leg_threads"] == bwgr_amd.pegs_plan(n, 1, 1)["threads"]
+    for n, m in ((0, 5), (5, 0), (-1, 5), (5, -1)):
+        with pytest.raises(bwgr_amd.BwgrError) as ei:
+            bwgr_amd.pegs_launch_plan(n, m)
+        assert ei.value.code == EINVAL and "pegs launch plan" in str(ei.value)
+
+
+@pytest.mark.parametrize("job", list(tc.PEGS_JOBS))
+def test_pegs_job_reaches_what_it_is_listed_for(job):
+    pl = tc.pegs_plans(job)
+    print(job, pl)
+    assert {k: pl[k] for k in tc.PEGS_EXPECT[job]} == tc.PEGS_EXPECT[job], (job, pl)
+
+
+def test_pegs_jobs_reach_every_regime_together():
+    import bwgr_amd
+    pls = {job: tc.pegs_plans(job) for job in tc.PEGS_JOBS}
+    J = tc.PEGS_JOBS
+    # the trace kernels: a third trip on the panel kernel and a second on the dense one, both at the cap of the grid (1 024 partials for
+    # k_mrr_finish); a last group of fewer than four columns on a later trip; every slab height, and a second slab of another height than 256
+    assert pls["wide33k"]["trace"] >= 3 and pls["dense16500"]["trace"] >= 2 and J["wide33k"]["effects"] == ("panel",) and J["dense16500"]["tag"] is None
+    assert pls["wide33k"]["trace_wg"] == pls["dense16500"]["trace_wg"] == 1024
+    assert any(pl["trace_tail"] < 4 and pl["trace_last"] >= 2 for pl in pls.values())
+    x = [pls[j] for j in tc.pegs_jobs("PEGSX") if J[j]["tag"]]
+    assert {pl["R"] for pl in x} >= {256, 1024, 1280} and any(pl["R"] != 256 and pl["K"] > 1 for pl in x)
+    # the uncentred train: second trips of the marker reductions and of the row reduction, R != 256, a short last block -- under every entry
+    for entry in ("PEGS", "PEGSZ", "PEGSX"):
+        t = [pls[j] for j in tc.pegs_jobs(entry) if J[j]["tag"] in tc.CASES]
+        assert max(pl["mrr_tilde"] for pl in t) >= 3 and max(pl["mrr_setup"] for pl in t) >= 2 and max(pl["mrr_ey"] for pl in t) >= 2
+        assert {pl["R"] for pl in t} >= {256, 1024, 1280} and min(pl["last64"] for pl in t) == 2
+    # a dense effect beside a panel that pads further than the dense effect alone would; in both orders under PEGSZ
+    both = [j for j in J if len(J[j]["effects"]) == 2]
+    assert any(pls[j]["ld"] != pls[j]["ld128"] for j in both) and {J[j]["effects"][0] for j in both if "PEGSZ" in J[j]["entries"]} == {"panel", 5}
+    # row loops past one trip at the widest workgroup, under every entry with a dense effect; the fixed step's column loop wraps there
+    for entry in ("PEGSZ", "PEGSX"):
+        assert any(pls[j]["leg_threads"] == 1024 and pls[j]["rows"] >= 5 for j in both if entry in J[j]["entries"])
+    assert any(pls[j]["fixed_cols"] >= 2 and pls[j]["rows"] >= 5 and pls[j]["fixed_threads"] == 1024 for j in tc.pegs_jobs("PEGSX"))
+    # f at the cap: four 64-lane trips of the quadratic form, and one more column is refused
+    assert J["f256"]["f"] == 256 and pls["f256"]["quad"] == 4 and pls["f256"]["lds_trace"] == 8 * (4 * 4 * 256 + 4 * 16) <= 64 * 1024
+    with pytest.raises(bwgr_amd.BwgrError) as ei:
+        bwgr_amd.pegsx_plan(700, 257, 3)
+    assert ei.value.code == EINVAL
+    with pytest.raises(bwgr_amd.BwgrError) as ei:
+        bwgr_amd.PEGSX(np.zeros((8, 2)), np.ones((8, 257)), [bwgr_amd.dense(np.ones((8, 3)))])
+    assert ei.value.code == EINVAL and "f = 257" in str(ei.value)
+    assert set(tc.TRZSZ_ALONE) <= set(tc.pegs_jobs("PEGSX")) and set(tc.NORMAL_EQUATIONS) <= set(tc.pegs_jobs("PEGSX"))
+
+
+def test_pegs_traits_miss_what_they_say():
+    """every trait its own pattern; the rows of PEGS_MISSING missing in every trait, on tall9k a whole quad at a slab edge"""
+    for job, j in tc.PEGS_JOBS.items():
+        Y, effects = tc.pegs_data(job)
+        k = j["k"]
+        assert Y.shape[1] == k and len({np.isnan(Y[:, t]).tobytes() for t in range(k)}) == k == tc.pegs_plans(job)["npat"]
+        rows = tc.PEGS_MISSING.get(j["tag"], ())
+        assert np.isnan(Y[list(rows)]).all() and int(np.isnan(Y[:, 1]).sum()) == len(rows)      # (trait 1 misses nothing else)
+        assert [e[0] for e in effects] == ["panel" if e == "panel" else "dense" for e in j["effects"]]
+        if j["tag"] in tc.PEGS_MISSING:
+            R = tc.pegs_plans(job)["R"]
+            assert any(r % R == 0 and r > 0 for r in rows) and any((r + 1) % R == 0 for r in rows)
+    rows = tc.PEGS_MISSING["tall9k"]
+    assert {4096, 4097, 4098, 4099} <= set(rows) and 4096 % 256 == 0 and 4096 % 4 == 0
+    assert np.isnan(tc.pegs_case("PEGSX", "tall9k")["data"]()[0][4096:4100]).all()
+
+
+@pytest.mark.parametrize("entry,job", PEGS_RUNS, ids=["%s-%s" % r for r in PEGS_RUNS])
+def test_pegs_job_is_away_from_the_discontinuous_branches(entry, job):
+    """The guards of tests/test_pegs_cpu.py / tests/test_pegsx_cpu.py as they stand, on the job's restatement: |MinDVb - covMinEv| >= 1e-3
+    covMinEv in every sweep and effect, no floor active, every kept eigenvalue ratio of M'M at least 1e-3 and none dropped, its == maxit."""
+    case = tc.pegs_case(entry, job)
+    if case["kw"]["maxit"] == 0:      # a TrZSZ-only job: there is no sweep to guard, only the rank decision of M'M and the start values
+        fit = tc.XC.restate(case)[3]
+        assert fit["its"] == 0 and not fit["floors0"] and all(m["kept"].min() >= 1e-3 and m["dropped"].size == 0 for m in fit["mm"])
+        return
+    if entry == "PEGSX":
+        TXC.test_case_is_away_from_the_discontinuous_branches(case)
+        fit = tc.XC.restate(case)[3]
+        print(entry, job, "min |MinDVb - cm| / cm", min(abs(r["MinDVb"] - 1e-3) / 1e-3 for recs in fit["trace"] for r in recs),
+              "min kept", min(m["kept"].min() for m in fit["mm"]))
+        assert fit["its"] == case["kw"]["maxit"]
+    else:
+        TPC.test_case_is_away_from_the_discontinuous_branches(case)
+        fit = tc.PC.restate(case)[2]
+        print(entry, job, "min |MinDVb - cm| / cm", min(abs(r["MinDVb"] - 1e-3) / 1e-3 for recs in fit["trace"] for r in recs))
+        assert fit["numit"] == case["kw"]["maxit"]
+
+
+@pytest.mark.parametrize("entry", tc.HANDLE_ENTRIES)
+def test_handle_table_pegs_calls_are_away_from_the_discontinuous_branches(entry):
+    """the same guards on the inputs of tests/test_gpu_handles.py's PEGS, PEGSZ and PEGSX entries and of its two-panel PEGSZ call"""
+    case = tc.handle_case(entry)
+    (TXC if entry == "PEGSX" else TPC).test_case_is_away_from_the_discontinuous_branches(case)
+
+
+def test_the_old_pegs_cases_did_not_reach_them():
+    """What the PEGS section is about, pinned: on tpod, the 700 x 900 panel and the dense 1 500 x 20 and 196 x 70 effects of
+    tests/pegs_cases.py and tests/pegsx_cases.py the trace kernels and the dense set-up make one trip with at most 57 workgroups, no dense
+    effect sits beside a panel that pads further than it would, and only the dense-only n = 1 500 case (k = 3, f = 3) takes a second row trip."""
+    import bwgr_amd
+    for n, m in ((196, 376), (700, 900), (196, 70), (700, 70), (1500, 20)):
+        pl = bwgr_amd.pegs_launch_plan(n, m)
+        assert m <= pl["trace_cols"] and m <= pl["setup_cols"] and pl["trace_wg"] <= 57
+        assert (n > pl["fixed_threads"]) == (n == 1500)
+    assert -(-196 // 128) * 128 == 256 and -(-700 // 128) * 128 == 768      # the panels' own ld there (tests/test_panel_plan.py)
+    assert max(c["data"]()[1].shape[1] for c in tc.XC.CASES) == 70
