@@ -122,6 +122,88 @@ def _default_logtol():
     return traits(X, 2, 0.1, seed=31), [("panel", X, {})]
 
 
+# ---- int8 codes beyond 0 / 1 / 2: PEGS never centres X, so the codes' sign, range and mean reach XX, XSX, the Grams and the fitted values ----
+
+def _i8(A):
+    assert A.min() >= -128 and A.max() <= 127
+    return np.asfortranarray(A.astype(np.int8))
+
+
+def _panel(name):
+    """signed: tpod - 1 (-1 / 0 / 1).  full: 300 x 200 uniform in -128..127, both ends in column 0.  offset: tpod + 100 (a mean 140 times the
+    spread).  pm127: 500 x 70 of +-127.  const_cols: tpod with an all-0 column (XX = 0) and an all-2 column (XSX = 0 with XX > 0).
+    full_slabs: 700 x 900 uniform in -128..127, for Panel(nwg=3) -- slabs900's geometry."""
+    key = "codes_" + name
+    if key not in _cache:
+        rng = np.random.default_rng(91)
+        if name == "signed":
+            A = tpod().astype(np.int16) - 1
+        elif name == "full":
+            A = rng.integers(-128, 128, size=(300, 200))
+            A[0, 0], A[1, 0] = -128, 127
+        elif name == "offset":
+            A = tpod().astype(np.int16) + 100
+        elif name == "pm127":
+            A = np.where(rng.random((500, 70)) < 0.5, -127, 127)
+        elif name == "const_cols":
+            A = tpod().astype(np.int16)
+            A[:, 37], A[:, 301] = 0, 2
+        else:
+            assert name == "full_slabs"
+            A = rng.integers(-128, 128, size=(700, 900))
+            A[0, 0], A[1, 0] = -128, 127
+        _cache[key] = _i8(A)
+    return _cache[key]
+
+
+CODE_PANELS = ("signed", "full", "offset", "pm127", "const_cols", "full_slabs")
+CODES_SEED = 11
+
+
+def _codes(name, k=3):
+    def data():
+        X = _panel(name)
+        return traits(X, k, 0.1, seed=CODES_SEED), [("panel", X, {})]
+    return data
+
+
+def _codes_slabs_k5():
+    X = _panel("full_slabs")
+    return traits(X, 5, 0, seed=5, patterns=[0.1, 0.0, 0.25, 0.05, 0.4]), [("panel", X, dict(nwg=3))]
+
+
+def _codes_k16():
+    X = _panel("full")
+    return traits_ids(X, K16_IDS, 0.1, seed=121), [("panel", X, {})]
+
+
+def _codes_two_ranges():
+    """two panels of different code ranges against one residual: tpod - 1 on the first 200 columns, tpod + 100 on the other 176"""
+    A, B = _panel("signed"), _panel("offset")
+    return traits(tpod(), 3, 0.1, seed=17), [("panel", np.asfortranarray(A[:, :200]), {}), ("panel", np.asfortranarray(B[:, 200:]), {})]
+
+
+def _codes_full_dense():
+    X = _panel("full")
+    return traits(X, 3, 0.1, seed=19), [("panel", X, {}), ("dense", gauss(X.shape[0], 70, 23))]
+
+
+GRAM_BOUND_N = ((1 << 31) - 1) // (127 * 127)   # 133 144: the most rows of +-127 whose column sums of squares fit the int32 Gram
+
+
+def gram_bound():
+    """test_gpu_mrr.py::test_int32_gram_bound's shape for PEGS and PEGSX: (X of n + 1 rows of +-127 by 70 columns, Y on the first n rows
+    with trait 0 fully observed, so that its pattern's Gram diagonal is n 127^2, and Y1 on all n + 1)"""
+    if "gram_bound" not in _cache:
+        n = GRAM_BOUND_N
+        assert n * 127 * 127 < (1 << 31) <= (n + 1) * 127 * 127
+        X = np.asfortranarray(np.where(np.random.default_rng(101).random((n + 1, 70)) < 0.5, -127, 127).astype(np.int8))
+        Y = traits(X[:n], 2, 0, seed=102, patterns=[0.0, 0.1])
+        assert np.sum(~np.isnan(Y[:, 0])) == n and np.sum(np.isnan(Y[:, 1])) > 0
+        _cache["gram_bound"] = (X, Y, traits(X, 2, 0.1, seed=103))
+    return _cache["gram_bound"]
+
+
 def _case(id_, entry, data, **kw):
     kw.setdefault("logtol", NOSTOP)
     return dict(id=id_, entry=entry, data=data, kw=kw)
@@ -150,7 +232,25 @@ CASES = [
     _case("pegs_one_effect_as_pegsz", "PEGSZ", _tpod_k3, maxit=12),
     _case("default_logtol", "PEGS", _default_logtol, logtol=-4.0),
 ]
-BENDS = ("bending_nnc_on", "bending_nnc_off")   # the restatement's trace must say that these inflated in every sweep
+# the code-range cases.  On large codes vb scales as 1 / x^2, far below the default covMinEv, so at the default these fits bend in every
+# sweep; the *_unbent cases state a covMinEv below every sweep's MinDVb (chosen on the restatement) and run the other side of the branch
+CODE_CASES = [
+    _case("codes_signed", "PEGS", _codes("signed"), maxit=8),
+    _case("codes_full", "PEGS", _codes("full"), maxit=8),
+    _case("codes_offset", "PEGS", _codes("offset"), maxit=8),
+    _case("codes_pm127", "PEGS", _codes("pm127"), maxit=8),
+    _case("codes_const_cols", "PEGS", _codes("const_cols"), maxit=8),
+    _case("codes_full_slabs_k5", "PEGS", _codes_slabs_k5, maxit=6),
+    _case("codes_full_unbent", "PEGS", _codes("full"), maxit=8, covMinEv=1e-9),
+    _case("codes_pm127_unbent", "PEGS", _codes("pm127"), maxit=8, covMinEv=1e-9),
+    _case("codes_offset_xfa2_unbent", "PEGS", _codes("offset"), maxit=8, XFA=2, covMinEv=1e-9),
+    _case("codes_full_k16", "PEGS", _codes_k16, maxit=4),
+    _case("pegsz_codes_signed_offset", "PEGSZ", _codes_two_ranges, maxit=8),
+    _case("pegsz_codes_full_dense70", "PEGSZ", _codes_full_dense, maxit=8),
+]
+CASES += CODE_CASES
+# the restatement's trace must say that these inflated in every sweep
+BENDS = ("bending_nnc_on", "bending_nnc_off", "codes_full", "codes_offset", "codes_pm127", "codes_full_slabs_k5", "codes_full_k16")
 
 
 def by_id(id_):

@@ -102,6 +102,23 @@ def _stop():
     return with_fixed(Y, X, 118), X, effs
 
 
+# ---- int8 codes beyond 0 / 1 / 2 (the panels of tests/pegs_cases.py): beside PEGS's uncentred sweeps, k_pegsx_trace_panel reads the same
+# bytes, and with an intercept in X TrZSZ = sum z^2 - v'A v is a difference of two large numbers once the codes have a large mean ----
+
+def _codes(name, ncov=2, seed=131):
+    def data():
+        Z = PC._panel(name)
+        X = fixed(Z.shape[0], ncov, seed)
+        return with_fixed(traits(Z, 3, 0.1, seed=PC.CODES_SEED), X, seed + 1), X, [("panel", Z, {})]
+    return data
+
+
+def _codes_f70():
+    Z = PC._panel("full_slabs")
+    X = fixed(Z.shape[0], 69, 133)
+    return with_fixed(traits(Z, 5, 0, seed=5, patterns=[0.1, 0.0, 0.25, 0.05, 0.4]), X, 134), X, [("panel", Z, dict(nwg=3))]
+
+
 def _case(id_, data, **kw):
     kw.setdefault("logtol", NOSTOP)
     return dict(id=id_, data=data, kw=kw)
@@ -130,7 +147,20 @@ CASES = [
     _case("dense_only_n1500", _dense_only(1500, 20, 45, 2), maxit=6),
     _case("stop_rule", _stop, maxit=50, logtol=0.0),
 ]
-BENDS = ("bending_nnc_on", "bending_nnc_off")   # the restatement's trace must say that these inflated in every sweep
+# the code-range cases: an intercept and two covariates unless the id says otherwise (const_cols: the intercept alone, which spans the
+# all-2 column, so that column's share of TrZSZ is an exact 0 made of two equal sums)
+CODE_CASES = [
+    _case("codes_signed", _codes("signed"), maxit=8),
+    _case("codes_full", _codes("full"), maxit=8),
+    _case("codes_offset", _codes("offset"), maxit=8),
+    _case("codes_pm127", _codes("pm127"), maxit=8),
+    _case("codes_offset_xfa2", _codes("offset"), maxit=8, XFA=True, NumXFA=2),
+    _case("codes_full_slabs_f70_k5", _codes_f70, maxit=6),
+    _case("codes_const_cols_f1", _codes("const_cols", ncov=0), maxit=8),
+]
+CASES += CODE_CASES
+# the restatement's trace must say that these inflated in every sweep
+BENDS = ("bending_nnc_on", "bending_nnc_off", "codes_full", "codes_offset", "codes_pm127", "codes_offset_xfa2", "codes_full_slabs_f70_k5")
 RANK_DEFICIENT = ("rank_deficient_x",)          # the only cases whose M'M may drop an eigenvalue
 NAMED_FLOORS = {}                               # case id -> the floors it is allowed to sit on (none of the cases needs one)
 

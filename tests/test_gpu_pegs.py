@@ -2,7 +2,9 @@
 smallest shapes at which each piece can still go wrong (tests/test_pegs_cpu.py checks that none of them sits on a discontinuous branch) --
 then determinism, handles and streams, the refusals, and mrr's own results around a PEGS call.
 
-Parity: scaled_err <= 1e-6 on mu, b, hat, h2, GC, bend and cnv, equal numit with logtol = -inf."""
+Parity: scaled_err <= 1e-6 on mu, b, hat, h2, GC, bend and cnv, equal numit with logtol = -inf.
+The codes_* cases run the uncentred int8 train on codes beyond 0 / 1 / 2 (signed, -128..127, a large mean, +-127, constant columns):
+largest error measured on an MI355X 2.3e-13 (h2 on tpod + 100), at most 1.1e-14 on the other panels."""
 import os
 import sys
 
@@ -135,9 +137,93 @@ def test_panel_and_dense_legs_agree_on_the_same_numbers():
         assert all(v <= TOL for v in errs.values()), errs
 
 
+@pytest.mark.parametrize("name", ["full", "offset"])
+def test_panel_and_dense_legs_agree_on_other_codes(name):
+    """The same on codes -128..127 and on tpod + 100, where the uncentred train's sign extension, S_g and XSX = XX / n - (S / n)^2 matter:
+    the int8 train against k_pegs_dense_leg on the same numbers as float64, to 1e-9 on every output and without the restatement (which
+    each leg then matches to 1e-6)."""
+    import bwgr_amd
+    Y, effects = PC.by_id("codes_" + name)["data"]()
+    Z = effects[0][1]
+    kw = dict(maxit=6, logtol=PC.NOSTOP)
+    o = PR.pegsz(Y, [Z.astype(np.float64)], **kw)
+    P = bwgr_amd.Panel(Z)
+    try:
+        gp = bwgr_amd.PEGSZ(Y, [P], **kw)
+    finally:
+        P.close()
+    gd = bwgr_amd.PEGSZ(Y, [bwgr_amd.dense(Z.astype(np.float64))], **kw)
+    assert gp["numit"] == gd["numit"] == o["numit"] == 6
+    between, ep, ed = _errs(gp, gd, "PEGSZ"), _errs(gp, o, "PEGSZ"), _errs(gd, o, "PEGSZ")
+    print(name, {k: "%.2e" % v for k, v in between.items()}, {k: "%.2e" % v for k, v in ep.items()}, {k: "%.2e" % v for k, v in ed.items()})
+    assert all(v <= 1e-9 for v in between.values()), between
+    for errs in (ep, ed):
+        assert all(v <= TOL for v in errs.values()), errs
+
+
+def test_int32_gram_bound():
+    """test_gpu_mrr.py::test_int32_gram_bound through PEGS, whose uncentred XX is the Gram's diagonal itself: at the most rows of +-127 that
+    n max|x|^2 < 2^31 allows the fit matches; one more row is refused where the panel is made, and the refused call leaves nothing behind."""
+    import bwgr_amd
+    X, Y, Y1 = PC.gram_bound()
+    n = PC.GRAM_BOUND_N
+    assert np.all((X[:n].astype(np.int64) ** 2).sum(0) == n * 127 * 127)
+    kw = dict(maxit=2, logtol=PC.NOSTOP)
+    P = bwgr_amd.Panel(X[:n], block=16)   # (n rows need the smaller sweep block's taller slabs)
+    try:
+        g = bwgr_amd.PEGS(Y, P, **kw)
+    finally:
+        P.close()
+    o = PR.pegs(Y, X[:n], **kw)
+    errs = {key: PR.scaled_err(g[key], o[key]) for key in KEYS}
+    print("gram bound", {k: "%.2e" % v for k, v in errs.items()})
+    assert g["numit"] == o["numit"] == 2 and all(v <= TOL for v in errs.values()), errs
+    live = bwgr_amd.debug_live()
+    with pytest.raises(bwgr_amd.BwgrError) as ei:
+        bwgr_amd.PEGS(Y1, X, block=16, **kw)
+    assert ei.value.code == 1 and "int32 Gram" in str(ei.value)
+    assert bwgr_amd.debug_live() == live
+    case = PC.by_id("tpod_k3_defaults")
+    assert all(v <= TOL for v in _errs(_fit(case), PC.restate(case)[2], "PEGS").values())
+
+
+def test_staging_rule():
+    """_pegs_effect on the device: an integer-valued float matrix within int8 range (negative values included) and a bool matrix are
+    staged as int8 panels, bit for bit the int8 matrix's fit; a float matrix holding 128.0 no longer fits int8 and goes to the dense leg;
+    an int16 matrix holding 200 becomes an fp32 panel, which PEGS refuses, and the panel made for the call is released."""
+    import bwgr_amd
+    kw = dict(maxit=4, logtol=PC.NOSTOP, cnv_trace=True)
+    Y, effects = PC.by_id("codes_signed")["data"]()
+    S = effects[0][1]
+    assert S.min() == -1
+    _same(bwgr_amd.PEGS(Y, S.astype(np.float64), **kw), bwgr_amd.PEGS(Y, S, **kw))
+    T = PC.tpod()
+    Yt = PC.by_id("tpod_k3_defaults")["data"]()[0]
+    B = T > 0
+    assert B.dtype == np.bool_
+    _same(bwgr_amd.PEGS(Yt, B, **kw), bwgr_amd.PEGS(Yt, B.astype(np.int8), **kw))
+    Yf, effects = PC.by_id("codes_full")["data"]()
+    Z = effects[0][1].astype(np.float64)
+    assert Z[0, 0] == -128.0
+    Z[0, 0] = 128.0
+    a, d = bwgr_amd.PEGSZ(Yf, [Z], **kw), bwgr_amd.PEGSZ(Yf, [bwgr_amd.dense(Z)], **kw)
+    _same(a, d)
+    o = PR.pegsz(Yf, [Z], maxit=4, logtol=PC.NOSTOP)
+    assert all(v <= TOL for v in _errs(a, o, "PEGSZ").values())
+    A = T.astype(np.int16)
+    A[0, 0] = 200
+    live = bwgr_amd.debug_live()
+    with pytest.raises(bwgr_amd.BwgrError) as ei:
+        bwgr_amd.PEGS(Yt, A, **kw)
+    assert ei.value.code == 1 and "fp32" in str(ei.value)
+    assert bwgr_amd.debug_live() == live
+    case = PC.by_id("tpod_k3_defaults")
+    assert all(v <= TOL for v in _errs(_fit(case), PC.restate(case)[2], "PEGS").values())
+
+
 def test_two_runs_are_bit_identical():
-    case = PC.by_id("pegsz_panel_dense70")
-    _same(_fit(case), _fit(case))
+    for cid in ("pegsz_panel_dense70", "codes_full_slabs_k5"):
+        _same(_fit(PC.by_id(cid)), _fit(PC.by_id(cid)))
 
 
 def test_clone_and_callers_stream_give_the_roots_result():

@@ -4,7 +4,9 @@ projected traces alone, the normal equations of the fixed step, determinism, han
 refusals.
 
 Parity: scaled_err <= 1e-6 on TrZSZ, b, every u, vb_list, GC_list, ve, hat, bend and cnv, equal its with logtol = -inf.
-Largest error measured over the table on an MI355X: 1.4e-10 (cnv and u of the collinear traits that bend in every sweep), 3.7e-13 elsewhere."""
+Largest error measured over the table on an MI355X: 1.4e-10 (cnv and u of the collinear traits that bend in every sweep), 3.7e-13 elsewhere;
+on the codes_* cases (int8 codes beyond 0 / 1 / 2) 8.8e-11 on tpod + 100, which is the numpy restatement's own rounding of TrZSZ where it
+cancels (test_trzsz_alone_where_it_cancels holds the library to a long double reference instead), and at most 1.4e-14 on the other panels."""
 import os
 import sys
 
@@ -99,7 +101,7 @@ def _normal_equations(Y, X, hat):
     return worst
 
 
-@pytest.mark.parametrize("cid", ["f70_slabs_k5", "dense_only_n1500"])
+@pytest.mark.parametrize("cid", ["f70_slabs_k5", "dense_only_n1500", "codes_full"])
 def test_normal_equations(cid):
     """M_t'(Y - hat)_t = 0 over a trait's observed rows after any fit, because the fixed step is the last thing that touches the residual:
     at most 1e-9 of ||M_t|| ||y_t||.  Independent of the restatement."""
@@ -137,6 +139,93 @@ def test_panel_and_dense_legs_agree_on_the_same_numbers():
         P.close()
 
 
+def _ld_inv(A):
+    """Gauss-Jordan with row pivoting in numpy.longdouble (numpy.linalg has no long double)"""
+    A = np.array(A, np.longdouble)
+    f = len(A)
+    I = np.eye(f, dtype=np.longdouble)
+    for c in range(f):
+        p = c + int(np.argmax(np.abs(A[c:, c])))
+        A[[c, p]], I[[c, p]] = A[[p, c]], I[[p, c]]
+        piv = A[c, c]
+        A[c], I[c] = A[c] / piv, I[c] / piv
+        for r in range(f):
+            if r != c:
+                m = A[r, c]
+                A[r], I[r] = A[r] - m * A[c], I[r] - m * I[c]
+    return I
+
+
+def test_trzsz_alone_where_it_cancels():
+    """tpod + 100 beside an intercept: sum z^2 and v'A v are both about 7e8 and TrZSZ, their difference, 6e4 -- four of fp64's sixteen
+    digits go, and the sums' own rounding takes some more.  Against the formula evaluated in numpy.longdouble on the host, to 1e-9 relative."""
+    case = XC.by_id("codes_offset")
+    Y, X, effects = case["data"]()
+    g = _fit(case, maxit=0)
+    Yf = np.asarray(Y, np.float32)
+    Xl, Zl = np.asarray(X, np.float32).astype(np.longdouble), effects[0][1].astype(np.longdouble)
+    assert np.all(Xl[:, 0] == 1) and g["its"] == 0
+    for t in range(Yf.shape[1]):
+        w = ~np.isnan(Yf[:, t])
+        M, Zw = Xl[w], Zl[w]
+        V = M.T @ Zw
+        total = (Zw ** 2).sum()
+        ref = total - (V * (_ld_inv(M.T @ M) @ V)).sum()
+        rel = abs(float((np.longdouble(g["TrZSZ"][0][t]) - ref) / ref))
+        print("trait", t, "sum z^2 %.6e TrZSZ %.6e rel err %.2e" % (float(total), float(ref), rel))
+        assert total / ref > 5e3 and rel <= 1e-9, (t, rel)
+
+
+@pytest.mark.parametrize("name", ["full", "offset"])
+def test_panel_and_dense_legs_agree_on_other_codes(name):
+    """The same on codes -128..127 and on tpod + 100 beside an intercept and two covariates: k_pegsx_trace_panel unpacks four signed rows
+    from a dword where k_pegsx_trace_dense reads four doubles, and the uncentred int8 train runs against k_pegs_dense_leg.  TrZSZ alone
+    (maxit = 0) and a six-sweep fit agree to 1e-9 on every output, without the restatement (which each then matches to 1e-6)."""
+    import bwgr_amd
+    Y, X, effects = XC.by_id("codes_" + name)["data"]()
+    Z = effects[0][1]
+    P = bwgr_amd.Panel(Z)
+    try:
+        for maxit in (0, 6):
+            kw = dict(maxit=maxit, logtol=XC.NOSTOP)
+            o = XR.pegsx(Y, X, [Z.astype(np.float64)], **kw)
+            gp = bwgr_amd.PEGSX(Y, X, [P], **kw)
+            gd = bwgr_amd.PEGSX(Y, X, [bwgr_amd.dense(Z.astype(np.float64))], **kw)
+            assert gp["its"] == gd["its"] == o["its"] == maxit
+            between, ep, ed = _errs(gp, gd), _errs(gp, o), _errs(gd, o)
+            print(name, "maxit", maxit, {k: "%.2e" % v for k, v in between.items()}, {k: "%.2e" % v for k, v in ep.items()}, {k: "%.2e" % v for k, v in ed.items()})
+            assert all(v <= 1e-9 for v in between.values()), (maxit, between)
+            for errs in (ep, ed):
+                assert all(v <= TOL for v in errs.values()), (maxit, errs)
+    finally:
+        P.close()
+
+
+def test_int32_gram_bound():
+    """test_gpu_mrr.py::test_int32_gram_bound through PEGSX with an intercept: at the most rows of +-127 that n max|x|^2 < 2^31 allows the fit
+    and its TrZSZ (1.5e11 a trait) match; one more row is refused where the panel is made, and the refused call leaves nothing behind."""
+    import bwgr_amd
+    Z, Y, Y1 = XC.PC.gram_bound()
+    n = XC.PC.GRAM_BOUND_N
+    kw = dict(maxit=2, logtol=XC.NOSTOP)
+    P = bwgr_amd.Panel(Z[:n], block=16)   # (n rows need the smaller sweep block's taller slabs)
+    try:
+        g = bwgr_amd.PEGSX(Y, np.ones((n, 1)), [P], **kw)
+    finally:
+        P.close()
+    o = XR.pegsx(Y, np.ones((n, 1)), [Z[:n]], **kw)
+    errs = _errs(g, o)
+    print("gram bound", {k: "%.2e" % v for k, v in errs.items()})
+    assert g["its"] == o["its"] == 2 and all(v <= TOL for v in errs.values()), errs
+    live = bwgr_amd.debug_live()
+    with pytest.raises(bwgr_amd.BwgrError) as ei:
+        bwgr_amd.PEGSX(Y1, np.ones((n + 1, 1)), [Z], block=16, **kw)
+    assert ei.value.code == 1 and "int32 Gram" in str(ei.value)
+    assert bwgr_amd.debug_live() == live
+    case = XC.by_id("tpod_k3_defaults")
+    assert all(v <= TOL for v in _errs(_fit(case), XC.restate(case)[3]).values())
+
+
 def test_effect_order_matters_and_each_matches():
     a, b = XC.restate(XC.by_id("panel_dense70"))[3], XC.restate(XC.by_id("dense70_panel"))[3]
     assert XR.scaled_err(a["u"][0], b["u"][1]) > 1e-4      # the same panel, swept before or after the dense design
@@ -154,7 +243,7 @@ def test_stop_rule():
 
 
 def test_two_runs_are_bit_identical():
-    for cid in ("panel_dense70", "f70_slabs_k5"):
+    for cid in ("panel_dense70", "f70_slabs_k5", "codes_full_slabs_f70_k5"):
         _same(_fit(XC.by_id(cid)), _fit(XC.by_id(cid)))
 
 

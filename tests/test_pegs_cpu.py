@@ -166,6 +166,52 @@ def test_case_is_away_from_the_discontinuous_branches(case):
         assert 1 < fit["numit"] < case["kw"].get("maxit", 100)
 
 
+@pytest.mark.parametrize("case", PC.CODE_CASES, ids=[c["id"] for c in PC.CODE_CASES])
+def test_code_case_is_well_conditioned(case):
+    """The restatement on the rows in reverse order (hat put back) is the same mathematics summed in another order.  The two agree to 1e-9
+    on every output: a condition on the case's data -- on codes with a large mean XSX = XX / n - (S / n)^2 loses digits -- that entitles the
+    GPU's parity to 1e-6 on it.  Measured: 2.6e-13 at worst (h2 on tpod + 100), at most 1.1e-14 elsewhere."""
+    Y, effects, fit = PC.restate(case)
+    rev = PR.pegsz(Y[::-1], [D[::-1] for D in PC.designs(effects)], own_text=case["entry"] == "PEGS", **case["kw"])
+    rev["hat"] = rev["hat"][::-1]
+    assert rev["numit"] == fit["numit"]
+    for key in ("mu", "b", "hat", "h2", "GC", "bend", "cnv"):
+        pairs = zip(fit[key], rev[key]) if isinstance(fit[key], list) else [(fit[key], rev[key])]
+        for a, b in pairs:
+            assert np.all(np.isfinite(a)) and PR.scaled_err(b, a) <= 1e-9, (key, PR.scaled_err(b, a))
+
+
+def test_gram_bound_fit_is_away_from_the_branch_and_well_conditioned():
+    """the shape of test_gpu_pegs.py::test_int32_gram_bound under the same two guards"""
+    X, Y, _ = PC.gram_bound()
+    X = X[:PC.GRAM_BOUND_N].astype(np.float64)
+    kw = dict(maxit=2, logtol=PC.NOSTOP)
+    fit, rev = PR.pegs(Y, X, trace=True, **kw), PR.pegs(Y[::-1], X[::-1], **kw)
+    rev["hat"] = rev["hat"][::-1]
+    assert all(r["MinDVb"] < 0.5e-3 and r["inflated"] for recs in fit["trace"] for r in recs)
+    for key in ("mu", "b", "hat", "h2", "GC", "bend", "cnv"):
+        assert np.all(np.isfinite(fit[key])) and PR.scaled_err(rev[key], fit[key]) <= 1e-9, key
+
+
+def test_code_panels_are_what_they_say():
+    P = {name: PC._panel(name) for name in PC.CODE_PANELS}
+    assert all(X.dtype == np.int8 and X.flags.f_contiguous for X in P.values())
+    assert sorted(np.unique(P["signed"])) == [-1, 0, 1] and np.array_equal(P["signed"].astype(int) + 1, PC.tpod())
+    assert sorted(np.unique(P["offset"])) == [100, 101, 102] and sorted(np.unique(P["pm127"])) == [-127, 127] and P["pm127"].shape == (500, 70)
+    for name, shape in (("full", (300, 200)), ("full_slabs", (700, 900))):
+        X = P[name]
+        assert X.shape == shape and X[:, 0].min() == -128 and X[:, 0].max() == 127 and len(np.unique(X)) == 256
+    C = P["const_cols"]
+    zero, two = np.flatnonzero(np.all(C == 0, 0)), np.flatnonzero(np.all(C == 2, 0))
+    assert len(zero) == 1 and len(two) == 1      # XX = 0; XSX = 0 with XX > 0
+    assert PC.slabs900().shape == P["full_slabs"].shape and PC.by_id("codes_full_slabs_k5")["data"]()[1][0][2] == dict(nwg=3)
+    ids = {c["id"] for c in PC.CODE_CASES}
+    unbent = {i for i in ids if i.endswith("_unbent")}
+    assert len(unbent) == 3 and not unbent & set(PC.BENDS)
+    for i in unbent:     # the other side of the branch on the same panels: no sweep inflates
+        assert not any(r["inflated"] for recs in PC.restate(PC.by_id(i))[2]["trace"] for r in recs)
+
+
 def test_case_table_covers_what_the_gpu_tests_promise():
     ids = {c["id"] for c in PC.CASES}
     assert len(ids) == len(PC.CASES) and set(PC.BENDS) <= ids

@@ -52,6 +52,52 @@ def test_case_is_away_from_the_discontinuous_branches(case):
         assert fit["its"] == kw["maxit"]
 
 
+@pytest.mark.parametrize("case", XC.CODE_CASES, ids=[c["id"] for c in XC.CODE_CASES])
+def test_code_case_is_well_conditioned(case):
+    """The restatement on the rows in reverse order (hat put back) is the same mathematics summed in another order.  The two agree to 1e-9
+    on every output, TrZSZ included: a condition on the case's data -- with an intercept in X and codes of a large mean TrZSZ is a difference
+    of two large numbers -- that entitles the GPU's parity to 1e-6 on it.  Measured: 1.2e-11 at worst (vb_list, and 9.5e-12 on TrZSZ, on
+    tpod + 100), below 1e-14 on every other panel."""
+    Y, X, effects, fit = XC.restate(case)
+    rev = XR.pegsx(Y[::-1], X[::-1], [D[::-1] for D in XC.designs(effects)], dense=[e[0] == "dense" for e in effects], **case["kw"])
+    rev["hat"] = rev["hat"][::-1]
+    assert rev["its"] == fit["its"]
+    for key in ("TrZSZ", "b", "u", "vb_list", "GC_list", "ve", "hat", "bend", "cnv"):
+        pairs = zip(fit[key], rev[key]) if isinstance(fit[key], list) else [(fit[key], rev[key])]
+        for a, b in pairs:
+            assert np.all(np.isfinite(a)) and XR.scaled_err(b, a) <= 1e-9, (key, XR.scaled_err(b, a))
+
+
+def test_gram_bound_fit_is_away_from_the_branches_and_well_conditioned():
+    """the shape of test_gpu_pegsx.py::test_int32_gram_bound under the same guards"""
+    Z, Y, _ = XC.PC.gram_bound()
+    Z = Z[:XC.PC.GRAM_BOUND_N].astype(np.float64)
+    X = np.ones((len(Z), 1))
+    kw = dict(maxit=2, logtol=XC.NOSTOP)
+    fit, rev = XR.pegsx(Y, X, [Z], trace=True, **kw), XR.pegsx(Y[::-1], X, [Z[::-1]], **kw)
+    rev["hat"] = rev["hat"][::-1]
+    assert all(r["MinDVb"] < 0.5e-3 and r["inflated"] and not r["floors"] for recs in fit["trace"] for r in recs) and not fit["floors0"]
+    for key in ("TrZSZ", "b", "u", "vb_list", "GC_list", "ve", "hat", "bend", "cnv"):
+        for a, b in zip(fit[key], rev[key]) if isinstance(fit[key], list) else [(fit[key], rev[key])]:
+            assert np.all(np.isfinite(a)) and XR.scaled_err(b, a) <= 1e-9, key
+
+
+def test_code_cases_cover_what_the_gpu_tests_promise():
+    shapes = {}
+    for c in XC.CODE_CASES:
+        Y, X, effs = c["data"]()
+        shapes[c["id"]] = (Y.shape[0], Y.shape[1], X.shape[1], effs[0][2])
+        assert np.all(X[:, 0] == 1.0) and effs[0][1].dtype == np.int8      # an intercept beside an int8 panel
+    assert shapes["codes_full_slabs_f70_k5"] == (700, 5, 70, dict(nwg=3)) and shapes["codes_const_cols_f1"][2] == 1
+    assert all(shapes["codes_" + name][1:3] == (3, 3) for name in ("signed", "full", "offset", "pm127", "offset_xfa2"))
+    # the cancellation case: on tpod + 100 the two sums of TrZSZ are some 1e4 times their difference
+    Y, X, effs, fit = XC.restate(XC.by_id("codes_offset"))
+    Z = XC.designs(effs)[0]
+    for t in range(3):
+        w = ~np.isnan(Y[:, t])
+        assert 5e3 < (Z[w] ** 2).sum() / fit["TrZSZ"][0][t] < 5e4
+
+
 def test_stop_rule_case_stops_at_the_fifth_sweep():
     """cnv is below logtol = 0 by sweep 3 at the latest, so the `its >= 5` half of the rule is what ends the fit"""
     case = XC.by_id("stop_rule")
