@@ -7,11 +7,13 @@ G_ff = X_f X_f' and G_fs = X_f X_s' are int64 matmuls; the centred products come
 or directly."""
 import numpy as np
 
+from kernels_restatement import int_matmul
+
 NPI = 3.14159
 
 
 def crossprod2(Xf, Xs):
-    return np.asarray(Xf).astype(np.int64) @ np.asarray(Xs).astype(np.int64).T
+    return int_matmul(Xf, Xs)
 
 
 def arc_centred_direct(Xf, Xs):
@@ -32,8 +34,8 @@ def arc_centred_identity(Xf, Xs):
     rs = (Si @ s).astype(np.float64) / nf
     c = float(np.sum((s.astype(np.float64) / nf) ** 2))
     qs = (Si * Si).sum(1).astype(np.float64)
-    Aff = (Fi @ Fi.T).astype(np.float64) - (rf[:, None] + rf[None, :]) + c
-    Afs = (Fi @ Si.T).astype(np.float64) - rf[:, None] - rs[None, :] + c
+    Aff = int_matmul(Fi, Fi).astype(np.float64) - (rf[:, None] + rf[None, :]) + c
+    Afs = int_matmul(Fi, Si).astype(np.float64) - rf[:, None] - rs[None, :] + c
     return Aff, Afs, qs - 2.0 * rs + c
 
 
@@ -57,7 +59,7 @@ def gau_kernels(Xf, Xs, phi=1.0):
     """(K_ff, K_fs) of EigenGauZ, :1914-1934; n_f (n_f - 1) in double"""
     Fi, Si = np.asarray(Xf).astype(np.int64), np.asarray(Xs).astype(np.int64)
     nf = Fi.shape[0]
-    Gff, Gfs = Fi @ Fi.T, Fi @ Si.T
+    Gff, Gfs = int_matmul(Fi, Fi), int_matmul(Fi, Si)
     dff = np.diag(Gff)
     qs = (Si * Si).sum(1)
     Dfs = np.sqrt((dff[:, None] + qs[None, :] - 2 * Gfs).astype(np.float64))     # exact integers under the root

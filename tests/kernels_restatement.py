@@ -7,16 +7,23 @@ G = X X' is an int64 matmul; the centred product comes either from the centring 
 import numpy as np
 
 
+def int_matmul(A, B):
+    """A B' of integer matrices as int64, through the float64 product: every partial sum is an integer below 2^53 (asserted), so each is
+    exact in any order of summation and the result is the int64 product's, at BLAS speed"""
+    A, B = np.asarray(A), np.asarray(B)
+    assert float(np.abs(A).max(initial=0)) * float(np.abs(B).max(initial=0)) * A.shape[1] < 2.0 ** 53
+    return np.rint(A.astype(np.float64) @ B.astype(np.float64).T).astype(np.int64)
+
+
 def crossprod(X):
-    Xi = np.asarray(X).astype(np.int64)
-    return Xi @ Xi.T
+    return int_matmul(X, X)
 
 
 def zz_identity(X):
     """ZZ' with Z = X - 1 m' from G, s and X s:  G_ii' - r_i - r_i' + c,  r = X s / n,  c = s.s / n^2."""
     Xi = np.asarray(X).astype(np.int64)
     n = Xi.shape[0]
-    G = Xi @ Xi.T
+    G = crossprod(X)
     s = Xi.sum(0)
     r = (Xi @ s).astype(np.float64) / n
     c = float(np.sum((s.astype(np.float64) / n) ** 2))
