@@ -11,6 +11,7 @@ INTEGRATION.md for the R .Call shim that binds the same entry points).  Everythi
 libbwgr_hip.so on the GPU; this module only marshals arrays.  `seed=None` draws the seed from numpy's
 global stream, so numpy.random.seed() plays the role of R's set.seed().
 """
+import contextlib
 import ctypes as C
 import numpy as np
 
@@ -1107,14 +1108,39 @@ def _pegs_effect(X, panel_kw):
     return dense(Xm), False
 
 
-def _pegs(Y, X_list, maxit, logtol, covbend, covMinEv, XFA, NNC, own_text, device, cnv_trace, panel_kw):
-    effs, made = [], []
+class _Eff(C.Structure):
+    """bwgr_pegs_effect"""
+    _fields_ = [("panel", C.c_void_p), ("Z", C.c_void_p), ("q", C.c_int64), ("ldz", C.c_int64)]
+
+
+@contextlib.contextmanager
+def _pegs_effects(X_list, panel_kw, round_dense):
+    """Opens an effect list through _pegs_effect: (effs, the bwgr_pegs_effect array, every effect's column count), and closes the panels made
+    here when the block ends.  round_dense: a dense Z is rounded to float (the copies live as long as the block)."""
+    effs, made, keep, ps = [], [], [], []
     try:
         for X in X_list:
-            E, own = _pegs_effect(X, dict(panel_kw, device=device))
+            E, own = _pegs_effect(X, panel_kw)
             effs.append(E)
             if own:
                 made.append(E)
+        ce = (_Eff * max(len(effs), 1))()   # (zeros)
+        for i, E in enumerate(effs):
+            if isinstance(E, Panel):
+                ce[i].panel = E._h.value
+                ps.append(E.p)
+            else:
+                keep.append(np.asfortranarray(E.Z.astype(np.float32).astype(np.float64)) if round_dense else E.Z)
+                ce[i].Z = keep[-1].ctypes.data; ce[i].q = keep[-1].shape[1]; ce[i].ldz = max(keep[-1].shape[0], 1)
+                ps.append(keep[-1].shape[1])
+        yield effs, ce, ps
+    finally:
+        for P in made:
+            P.close()
+
+
+def _pegs(Y, X_list, maxit, logtol, covbend, covMinEv, XFA, NNC, own_text, device, cnv_trace, panel_kw):
+    with _pegs_effects(X_list, dict(panel_kw, device=device), False) as (effs, ce, ps):
         if not effs:
             raise BwgrError(1, "pegs: X_list holds no effects")
         Ym = np.asarray(Y, np.float64)
@@ -1130,18 +1156,6 @@ def _pegs(Y, X_list, maxit, logtol, covbend, covMinEv, XFA, NNC, own_text, devic
         k = Ym.shape[1]
         Yf = np.asfortranarray(Ym)
         neff, kk = len(effs), max(k, 1)
-
-        class _Eff(C.Structure):
-            _fields_ = [("panel", C.c_void_p), ("Z", C.c_void_p), ("q", C.c_int64), ("ldz", C.c_int64)]
-        ce = (_Eff * neff)()
-        ps = []
-        for i, E in enumerate(effs):
-            if isinstance(E, Panel):
-                ce[i].panel = E._h.value; ce[i].Z = None; ce[i].q = 0; ce[i].ldz = 0
-                ps.append(E.p)
-            else:
-                ce[i].panel = None; ce[i].Z = E.Z.ctypes.data; ce[i].q = E.Z.shape[1]; ce[i].ldz = max(E.Z.shape[0], 1)
-                ps.append(E.Z.shape[1])
         f32 = lambda v: float(np.float32(v))   # the real options are floats there
         mu = np.zeros(kk); hat = np.zeros((n, kk), order="F"); h2 = np.zeros(kk); bend = np.zeros(neff)
         b = [np.zeros((p_, kk), order="F") for p_ in ps]; GC = [np.zeros((kk, kk), order="F") for _ in ps]
@@ -1155,9 +1169,6 @@ def _pegs(Y, X_list, maxit, logtol, covbend, covMinEv, XFA, NNC, own_text, devic
         if cnv_trace:
             out["cnv_trace"] = cnv[:nit].copy()
         return out
-    finally:
-        for P in made:
-            P.close()
 
 
 def PEGS(Y, X, maxit=100, logtol=-4.0, covbend=1.1, covMinEv=10e-4, XFA=-1, NNC=True, *, device=0, cnv_trace=False, **kw):
@@ -1219,13 +1230,7 @@ def PEGSX(Y, X, Z_list, maxit=500, logtol=-8.0, covbend=1.1, covMinEv=10e-4, cor
     options are rounded to float as the reference receives them; the engine is fp64.  The marker order of sweep s is em_order(m, s) per effect.
     InnerGS=True and NoInv=True are refused; cores and verbose are accepted and ignored; XFA=True with NumXFA <= 0 is XFA=False.
     cnv_trace=True adds "cnv_trace", cnv after every sweep."""
-    effs, made = [], []
-    try:
-        for Z in list(Z_list):
-            E, own = _pegs_effect(Z, dict(kw, device=device))
-            effs.append(E)
-            if own:
-                made.append(E)
+    with _pegs_effects(list(Z_list), dict(kw, device=device), True) as (effs, ce, ps):   # (a dense Z is a float matrix there, :266)
         f32 = lambda v: float(np.float32(v))   # the real options are floats there
         Ym = np.asarray(Y, np.float64)
         if Ym.ndim == 1:
@@ -1245,20 +1250,6 @@ def PEGSX(Y, X, Z_list, maxit=500, logtol=-8.0, covbend=1.1, covMinEv=10e-4, cor
         if any(r != n for r in rows):
             raise BwgrError(1, "pegsx: the effects have %s rows, Y %d; all must have the same rows" % (rows, n))
         f, neff, kk = Xf.shape[1], len(effs), max(k, 1)
-
-        class _Eff(C.Structure):
-            _fields_ = [("panel", C.c_void_p), ("Z", C.c_void_p), ("q", C.c_int64), ("ldz", C.c_int64)]
-        ce = (_Eff * max(neff, 1))()
-        ps, keep = [], []
-        for i, E in enumerate(effs):
-            if isinstance(E, Panel):
-                ce[i].panel = E._h.value; ce[i].Z = None; ce[i].q = 0; ce[i].ldz = 0
-                ps.append(E.p)
-            else:
-                Zf = np.asfortranarray(E.Z.astype(np.float32).astype(np.float64))   # (a dense Z is a float matrix there, :266)
-                keep.append(Zf)
-                ce[i].panel = None; ce[i].Z = Zf.ctypes.data; ce[i].q = Zf.shape[1]; ce[i].ldz = max(Zf.shape[0], 1)
-                ps.append(Zf.shape[1])
         Tr = np.zeros((max(neff, 1), kk)); b = np.zeros((max(f, 1), kk), order="F"); ve = np.zeros(kk); hat = np.zeros((n, kk), order="F"); bend = np.zeros(max(neff, 1))
         u = [np.zeros((p_, kk), order="F") for p_ in ps]
         vb = [np.zeros((kk, kk), order="F") for _ in ps]; GC = [np.zeros((kk, kk), order="F") for _ in ps]
@@ -1272,9 +1263,6 @@ def PEGSX(Y, X, Z_list, maxit=500, logtol=-8.0, covbend=1.1, covMinEv=10e-4, cor
         if cnv_trace:
             out["cnv_trace"] = cnv[:nit].copy()
         return out
-    finally:
-        for P in made:
-            P.close()
 
 
 # ---- per-trait ridge fits: solver1x / UVBETA, solver1xF / FUVBETA, XFUVBETA, ZFUVBETA (bwgr_uvbeta, include/bwgr.h) ----

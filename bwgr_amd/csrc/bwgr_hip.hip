@@ -1458,6 +1458,7 @@ extern "C" int bwgr_panel_centred(bwgr_panel *P, int *centred) {
 #include "samplers_host.hip.h"
 #include "wgr_em_host.hip.h"
 #include "group_host.hip.h"
+#include "mtfit_host.hip.h"
 #include "fits_host.hip.h"
 #include "pegs_host.hip.h"
 #include "pegsx_host.hip.h"

@@ -1,96 +1,15 @@
 // bwgr_amd/csrc/fits_host.hip.h -- the host entries of the fp64 fits and products on a resident int8 panel: mrr, the UVBETA family with
 // solver2x, the dense fits, X B, and the relationship kernels.  Part of bwgr_hip.hip, which includes it after everything it uses (fail, HIPCHK,
-// DevBufs, no_memory, d2h / h2d / zero, Guard, guard_busy); it defines no kernel.  What these entries do to Y and Z before a kernel runs is
-// traits.h.
+// DevBufs, no_memory, d2h / h2d / zero, Guard, guard_busy, and mtfit_host.hip.h); it defines no kernel.  What these entries do to Y and Z before
+// a kernel runs is traits.h.
 // ------------------------------------------------------------------------------------------------
 // mrr / mrr_float (MRR3 / MRR3F, src/RcppEigen20230423.cpp:318-1080): the engine of mrr.hip.h as a per-block launch train
 //   per sweep:  order (host std::shuffle, cumulative) -> k_permute_cols -> k_mrr_gram -> k_mrr_linv ->
 //               [k_mrr_pass(b-1 | b), k_mrr_solve(b)] for every block -> k_mrr_pass(last | -) -> k_mrr_ey -> (host: ve) ->
 //               k_mrr_tilde -> (host: vb, GC, bending, pinv) -> k_mrr_mu_shift (updateMu)
-// The sweep itself (order .. closing pass) is mrr_sweep, which bwgr_pegs (pegs_host.hip.h) runs once per panel effect as well.
+// The sweep itself (order .. closing pass) is mrr_sweep of mtfit_host.hip.h, and the fit's device arrays and repeated steps are MtFit's, there:
+// bwgr_mrr is a fit with one panel effect, centred.  What is left here is mrr's own algebra.
 // ------------------------------------------------------------------------------------------------
-// The LDS plan of k_mrr_solve and k_mrr_linv for k traits and npat missingness patterns, decided here and nowhere else: the solve stages
-// the markers' k x k inverses (64 k^2 doubles) when they fit beside its fixed arrays, then as many of the block's per-pattern Gram matrices
-// as the rest of the budget holds (ngl); it reads patterns ngl.. from global memory, and without linv_lds fetches each marker's row of
-// its inverse one marker ahead.  bwgr_debug_mrr_plan exposes it to the CPU tests.
-static constexpr size_t MRR_LDS_MAX = 160 * 1024;
-static constexpr int MRR_NP = 64;             // workgroups (= partials) of the tail reductions k_mrr_ey and k_mrr_tilde, 256 rows or markers each per trip
-static constexpr int MRR_SETUP_WG = 8192;     // workgroups of k_mrr_setup_cols at most, four markers (one per wave) each per trip
-static constexpr int TAIL_THREADS = 256;      // threads per workgroup of the tail, product and finish kernels of the fp64 families
-// the grids the launch sites below and bwgr_debug_launch_plan share
-static inline int64_t mrr_setup_grid(int64_t p) { return std::min<int64_t>((p + 3) / 4, MRR_SETUP_WG); }
-static inline int64_t mrr_pass_grid(int64_t ld) { return std::min<int64_t>(ld / 64, MRR_PASS_WG); }
-struct MrrPlan { int linv_lds, ngl; size_t lds_solve, lds_linv; };
-static MrrPlan mrr_plan(int k, int npat) {
-  MrrPlan pl;
-  const size_t lds_fixed = mrr_solve_lds(0, 0), linv_b = sizeof(double) * MRR_MB * k * k;
-  pl.linv_lds = lds_fixed + linv_b <= MRR_LDS_MAX ? 1 : 0;
-  pl.ngl = (int)std::min<size_t>((size_t)npat, (MRR_LDS_MAX - lds_fixed - (pl.linv_lds ? linv_b : 0)) / (MRR_MB * MRR_MB * 4));
-  pl.lds_solve = mrr_solve_lds(pl.ngl, pl.linv_lds ? MRR_MB * k * k : 0);
-  pl.lds_linv = linv_b;
-  return pl;
-}
-extern "C" int bwgr_debug_mrr_plan(int k, int npat, int *linv_lds, int *ngl, int64_t *solve_lds_bytes, int64_t *linv_lds_bytes) {
-  if (k < 1 || k > MRR_KMAX || npat < 1 || npat > k) return BWGR_EINVAL;
-  const MrrPlan pl = mrr_plan(k, npat);
-  if (linv_lds) *linv_lds = pl.linv_lds;
-  if (ngl) *ngl = pl.ngl;
-  if (solve_lds_bytes) *solve_lds_bytes = (int64_t)pl.lds_solve;
-  if (linv_lds_bytes) *linv_lds_bytes = (int64_t)pl.lds_linv;
-  return BWGR_OK;
-}
-
-// One design's share of a sweep (:866-902): what its launch train reads and writes on the device.  bwgr_mrr has one; bwgr_pegs one per
-// panel effect, all against the same residual (MrrSweepShared).
-struct MrrLeg {
-  const bwgr_panel *P = nullptr;
-  int64_t p = 0, nblk = 0;
-  int8_t *Xs = nullptr; int32_t *ordd = nullptr, *gram = nullptr;
-  double *xbar = nullptr, *Sd = nullptr, *XXd = nullptr, *XSXd = nullptr, *tilde = nullptr, *bd = nullptr, *Linv = nullptr, *db2 = nullptr;
-};
-struct MrrSweepShared {
-  int64_t ld; int G, npat;
-  const uint32_t *ztd; const uint8_t *zmd;
-  double *ed, *part, *dB, *iGd;     // the residual [trait][ld]; the pass's partial dots; the block's delta b; k x k staging of iG
-};
-// (the caller asks bufs.failed() once, after all its gets)
-static void mrr_leg_alloc(DevBufs &bufs, MrrLeg &L, const bwgr_panel *P, int npat, int k) {
-  L.P = P; L.p = P->data->p; L.nblk = (L.p + MRR_MB - 1) / MRR_MB;
-  const size_t np = (size_t)L.p, pk = np * k;
-  L.Xs = bufs.get<int8_t>(P->data->plan.x_bytes);
-  L.ordd = bufs.get<int32_t>(np); L.gram = bufs.get<int32_t>((size_t)L.nblk * npat * MRR_MB * MRR_MB);
-  L.xbar = bufs.get<double>(np); L.Sd = bufs.get<double>(npat * np);
-  L.XXd = bufs.get<double>(pk); L.XSXd = bufs.get<double>(pk); L.tilde = bufs.get<double>(pk); L.bd = bufs.get<double>(pk); L.Linv = bufs.get<double>(pk * k);
-  L.db2 = bufs.get<double>(MRR_KMAX);
-}
-// order -> k_permute_cols -> k_mrr_gram -> k_mrr_linv -> [k_mrr_pass(b-1 | b), k_mrr_solve(b)] for every block -> k_mrr_pass(last | -);
-// mc.iVe and iG (host, k x k) are the sweep's.  Leaves sum_j (delta b_jt)^2 in L.db2.
-static int mrr_sweep(hipStream_t st, const MrrLeg &L, const MrrSweepShared &W, const MrrConst &mc, const MrrPlan &plan, const std::vector<int> &order,
-                     const double *iG) {
-  const PanelData *D = L.P->data;
-  const int R = D->plan.R, k = mc.k, npat = W.npat, G = W.G;
-  const int64_t p = L.p, ld = W.ld, nblk = L.nblk;
-  const int cps = (int)((size_t)R / 16);
-  HIPCHK(h2d(st, L.ordd, order.data(), (size_t)p));
-  hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)D->X, (uint4 *)L.Xs, (const int32_t *)L.ordd, p, D->plan.K, cps);
-  hipLaunchKernelGGL(k_mrr_gram, dim3((unsigned)nblk, (unsigned)((npat + 3) / 4)), dim3(256), 0, st, (const int8_t *)L.Xs, R, p, ld, W.zmd, npat, L.gram);
-  HIPCHK(h2d(st, W.iGd, iG, (size_t)k * k));
-  hipLaunchKernelGGL(k_mrr_linv, dim3((unsigned)((p + 63) / 64)), dim3(64), plan.lds_linv, st, (const double *)L.XXd, (const double *)W.iGd, mc, p, L.Linv);
-  HIPCHK(zero(st, L.db2, (size_t)MRR_KMAX));
-  HIPCHK(hipGetLastError());
-  for (int64_t blk = 0; blk <= nblk; ++blk) {
-    MrrPassArgs pa; pa.Xs = L.Xs; pa.R = R; pa.p = p; pa.ld = ld; pa.nblk = (int)nblk; pa.zb = W.ztd; pa.e = W.ed; pa.dB = W.dB; pa.part = W.part;
-    pa.prev = blk > 0 ? (int)(blk - 1) : -1; pa.next = blk < nblk ? (int)blk : -1; pa.k = k;
-    hipLaunchKernelGGL(k_mrr_pass, dim3(G), dim3(256), 0, st, pa);
-    if (blk == nblk) break;
-    MrrSolveArgs sa; sa.part = W.part; sa.G = G; sa.order = L.ordd; sa.blk = (int)blk; sa.p = p; sa.gram = L.gram; sa.xbar = L.xbar; sa.S = L.Sd; sa.XX = L.XXd;
-    sa.Linv = L.Linv; sa.b = L.bd; sa.dB = W.dB; sa.db2 = L.db2; sa.ngl = plan.ngl; sa.linv_lds = plan.linv_lds;
-    hipLaunchKernelGGL(k_mrr_solve, dim3(1), dim3(256), plan.lds_solve, st, sa, mc);
-  }
-  HIPCHK(hipGetLastError());
-  return BWGR_OK;
-}
-
 extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opts, int nopts, double *mu_out, double *b_out, double *hat_out,
                         double *h2_out, double *GC_out, double *vb_out, double *ve_out, double *MSx_out, double *cnvB, double *cnvH2, double *cnvV,
                         int *its) {
@@ -118,69 +37,36 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   if (o.maxit < 0) return fail(BWGR_EINVAL, "mrr: maxit = %d", o.maxit);
   if ((o.XFA || o.ACS) && (o.NumXFA < 1 || o.NumXFA > k))
     return fail(BWGR_EINVAL, "mrr: NumXFA = %d with XFA / ACS needs 1 <= NumXFA <= k = %d (the reference indexes eigenvalue k - NumXFA)", o.NumXFA, k);
-  HIPCHK(hipSetDevice(P->data->device));
-  const int64_t n = P->data->n, p = P->data->p, ld = P->data->plan.ld;
-  const int R = P->data->plan.R;
+  const int64_t n = P->data->n, p = P->data->p;
+  const bwgr_pegs_effect one = {P, nullptr, 0, 0};
+  MtList E;
+  CHK(mt_check_effects("mrr", "b", &one, 1, n, P->data->device, &b_out, E));                        // (nothing left to refuse: the panel's device, ld and stream)
   // (the int32 pattern Grams sum over at most n rows: n * max|x|^2 < 2^31 holds for every int8 panel, panel_build_gram)
   // ---- host set-up (:742-816): nt, mu and the centred y (:746-761); vy with iN = 1/(n-1) (:781-782) ----
-  const TraitSet S = read_traits(Y, n, k, ld, k, RowRule::AtLeastTwo);
+  const TraitSet S = read_traits(Y, n, k, E.ld, k, RowRule::AtLeastTwo);
   if (S.bad >= 0) return fail(BWGR_EINVAL, "mrr: trait %d has %g observed rows (needs 2)", (int)S.bad, S.nt[(size_t)S.bad]);
-  const std::vector<double> &y = S.y, &nt = S.nt, &sumy = S.sumy, &vy = S.vy;
+  const std::vector<double> &nt = S.nt, &vy = S.vy;
   std::vector<double> mu = S.mu;
   // missingness patterns: traits with the same observed rows share one masked Gram
   const Patterns pat = find_patterns(S, 0, k);
-  const int npat = (int)pat.rep.size();
-  MrrConst mc; memset(&mc, 0, sizeof(mc));
-  mc.k = k; mc.npat = npat;
-  for (int t = 0; t < k; ++t) { mc.pt[t] = pat.id[(size_t)t]; mc.nt[t] = nt[t]; }
-  std::vector<uint32_t> zt((size_t)ld), zb((size_t)ld);   // bit t: row observed for trait t; bit g: row observed in pattern g (k_mrr_setup_cols)
-  std::vector<uint8_t> zm;
-  pack_row_bits(S, (int64_t)0, k, zt.data());
-  pack_row_bits(S, pat.rep.data(), npat, zb.data());
-  append_byte_masks(S, pat.rep.data(), npat, zm);
-
-  hipStream_t st = P->stream;
-  CumulativeOrder order((size_t)p);
-  std::vector<double> iG((size_t)k * k, 0.0), d(k), off(k);   // (these four are copied from asynchronously: declared before the holder, which waits for the stream)
-  DevBufs bufs(st);
-  const int G = (int)mrr_pass_grid(ld);
-  const int NP = MRR_NP;                               // partials of the tail reductions
-  const int nch = (int)std::min<int64_t>(64, p);       // marker chunks of the fitted values
-  const int64_t cpc = (p + nch - 1) / nch;
-  const size_t np = (size_t)p, nl = (size_t)ld, pk = np * k;
-  MrrLeg leg;
-  mrr_leg_alloc(bufs, leg, P, npat, k);
-  uint32_t *zbd = bufs.get<uint32_t>(nl), *ztd = bufs.get<uint32_t>(nl);
-  uint8_t *zmd = bufs.get<uint8_t>((size_t)npat * nl);
-  double *yd = bufs.get<double>(k * nl), *ed = bufs.get<double>(k * nl);
-  double *part = bufs.get<double>((size_t)G * (MRR_MB + 1) * MRR_KMAX), *dB = bufs.get<double>(MRR_MB * MRR_KMAX + MRR_KMAX);
-  double *const xbar = leg.xbar, *const Sd = leg.Sd, *const XXd = leg.XXd, *const XSXd = leg.XSXd, *const tilde = leg.tilde, *const bd = leg.bd, *const db2 = leg.db2;
-  double *small = bufs.get<double>(1024);            // [0, 512): reduction results; [512, 768): iG; [768, ...): mu shift
-  double *tpart = bufs.get<double>((size_t)NP * (MRR_KMAX * MRR_KMAX + MRR_KMAX)), *sumyd = bufs.get<double>(MRR_KMAX);
-  if (bufs.failed()) return no_memory("mrr");
-  HIPCHK(h2d(st, zbd, zb.data(), nl));
-  HIPCHK(h2d(st, ztd, zt.data(), nl));
-  HIPCHK(h2d(st, zmd, zm.data(), zm.size()));
-  HIPCHK(h2d(st, yd, y.data(), k * nl));
-  HIPCHK(h2d(st, ed, y.data(), k * nl));                                                           // e = y, :825
-  HIPCHK(h2d(st, sumyd, sumy.data(), (size_t)k));
-  HIPCHK(zero(st, bd, pk));                                                                        // b = 0, :823
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_linv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
-  hipLaunchKernelGGL(k_mrr_setup_cols, dim3((unsigned)mrr_setup_grid(p)), dim3(TAIL_THREADS), 0, st, (const int8_t *)P->data->X, R, (int)n, p, ld,
-                     (const uint32_t *)zbd, (const double *)yd, (const double *)sumyd, mc, 1, xbar, Sd, XXd, XSXd, tilde);
-  HIPCHK(hipGetLastError());
+  std::vector<double> iG((size_t)k * k, 0.0);     // (copied from asynchronously: before the fit, whose holder waits for the stream)
+  MtFit M(E, k);
+  M.masks(S, pat);
+  M.alloc(hat_out != nullptr, false);
+  if (M.bufs.failed()) return no_memory("mrr");
+  const MtEffect &F = M.eff[0];
+  MrrConst &mc = M.mc;
+  std::vector<double> &d = M.d, &off = M.off;
+  CHK(M.upload(S, S.sumy.data()));                                                                 // e = y, :825
+  CHK(M.stage_effect(0));                                                                          // b = 0, :823
+  CHK(M.setup_effect(0, 1));
   // a reduction over p of the k^2 (+k) products, partials in a fixed order
-  auto reduce_pk = [&](int mode, int nout, const double *iGd, std::vector<double> &out) -> hipError_t {
-    hipLaunchKernelGGL(k_mrr_tilde, dim3(NP, nout), dim3(256), 0, st, (const double *)bd, (const double *)tilde, (const double *)XSXd, p, mode, mc, iGd, tpart);
-    hipLaunchKernelGGL(k_mrr_finish, dim3(1), dim3(256), 0, st, (const double *)tpart, NP, nout, small);
-    hipError_t e_ = hipGetLastError();
-    if (e_ != hipSuccess) return e_;
+  auto reduce_pk = [&](int mode, int nout, const double *dvec, std::vector<double> &out) -> int {
     out.resize(nout);
-    return d2h(st, out.data(), small, sizeof(double) * nout);
+    return M.reduce(F.b(), F.tilde(), F.XSX(), p, mode, nout, dvec, out.data());
   };
   std::vector<double> MSx;
-  HIPCHK(reduce_pk(2, k, nullptr, MSx));                                                           // MSx = colSums(XSX), :777
+  CHK(reduce_pk(2, k, nullptr, MSx));                                                              // MSx = colSums(XSX), :777
   // ---- start values (:784-816) ----
   std::vector<double> ve(k), vbInit(k), veInit(k), h2(k), TrXSX(k), Se(k), iNp(k), iN(k);
   std::vector<double> vb((size_t)k * k, 0.0), Sb((size_t)k * k), GC((size_t)k * k, 0.0), TH_((size_t)k * k), Tr(k);
@@ -199,19 +85,14 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   const double logtol = log10(o.tol);
   std::vector<double> ey, db2h(k), vb0, h20;
   int numit = 0;
-  const MrrPlan plan = mrr_plan(k, npat);
-  const MrrSweepShared W = {ld, G, npat, ztd, zmd, ed, part, dB, small + 512};
   while (numit < o.maxit) {
     vb0 = vb; h20 = h2;
     for (int t = 0; t < k; ++t) mc.iVe[t] = 1.0 / ve[t];
-    CHK(mrr_sweep(st, leg, W, mc, plan, order.next(numit), iG.data()));                            // :869 (cumulative, as there)
+    CHK(M.sweep_effect(0, numit, iG.data()));                                                      // :869 (cumulative, as there)
     // residual variance (:916-924)
-    hipLaunchKernelGGL(k_mrr_ey, dim3(NP, k), dim3(256), 0, st, (const double *)ed, (const double *)yd, ld, k, tpart);
-    hipLaunchKernelGGL(k_mrr_finish, dim3(1), dim3(256), 0, st, (const double *)tpart, NP, 2 * k, small);
-    HIPCHK(hipGetLastError());
     ey.resize(2 * k);
-    HIPCHK(d2h(st, ey.data(), small, sizeof(double) * 2 * k));
-    HIPCHK(d2h(st, db2h.data(), db2, sizeof(double) * k));
+    CHK(M.residual_sums(ey.data()));
+    CHK(M.read_db2(0, db2h.data()));
     for (int t = 0; t < k; ++t) {
       ve[t] = (ey[t] + Se[t]) * iNp[t];                                                            // :916-917
       h2[t] = 1 - ve[t] / vy[t];                                                                   // :918 (before the prior)
@@ -222,11 +103,11 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
     for (int t = 0; t < k; ++t) { mc.iVe[t] = 1.0 / ve[t]; d[t] = iG[t * k + t]; }
     std::vector<double> th;
     if (o.TH) {
-      HIPCHK(h2d(st, small + 768, d.data(), (size_t)k));
-      HIPCHK(reduce_pk(1, k * k + k, small + 768, th));
+      CHK(M.stage_vec(d));
+      CHK(reduce_pk(1, k * k + k, M.vecd, th));
       for (int t = 0; t < k; ++t) Tr[t] = th[k * k + t];
     } else {
-      HIPCHK(reduce_pk(0, k * k, nullptr, th));
+      CHK(reduce_pk(0, k * k, nullptr, th));
       for (int t = 0; t < k; ++t) Tr[t] = TrXSX[t];
     }
     // th[s * k + t] = sum_j b_js tilde_jt = TildeHat(s, t)
@@ -236,9 +117,7 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
     if (bent && o.verbose) printf("Inflate (it=%d)\n", numit);
     if (o.updateMu) {                                                                              // :1030-1036
       for (int t = 0; t < k; ++t) { d[t] = ey[k + t] * iN[t]; mu[t] += d[t]; }
-      HIPCHK(h2d(st, small + 768, d.data(), (size_t)k));
-      hipLaunchKernelGGL(k_mrr_mu_shift, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st, ed, (const uint32_t *)ztd, ld, (int)n, k, (const double *)(small + 768));
-      HIPCHK(hipGetLastError());
+      CHK(M.mu_shift());
     }
     double mx = -INFINITY;
     for (int t = 0; t < k; ++t) mx = std::max(mx, db2h[t]);
@@ -256,21 +135,16 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
     if (numit == o.maxit && o.verbose) printf("Model did not converge\n");
   }
   // ---- fitted values for every row, the missing ones included (:1054-1055) ----
-  std::vector<double> bh((size_t)p * k), xb((size_t)p);
-  HIPCHK(d2h(st, bh.data(), bd, sizeof(double) * p * k));
-  HIPCHK(d2h(st, xb.data(), xbar, sizeof(double) * p));
-  for (int t = 0; t < k; ++t) { double s = 0; for (int64_t j = 0; j < p; ++j) s += xb[(size_t)j] * bh[(size_t)j * k + t]; off[t] = mu[t] - s; }
+  std::vector<double> xb((size_t)p);
+  CHK(M.read_b(0, b_out));                                                                         // p x k column-major
+  HIPCHK(d2h(M.st, xb.data(), F.leg.xbar, sizeof(double) * p));
+  for (int t = 0; t < k; ++t) { double s = 0; for (int64_t j = 0; j < p; ++j) s += xb[(size_t)j] * b_out[(size_t)t * p + j]; off[t] = mu[t] - s; }
   if (hat_out) {
-    double *hpart = bufs.get<double>((size_t)nch * k * nl), *hatd = bufs.get<double>((size_t)n * k);
-    if (bufs.failed()) return no_memory("mrr");
-    HIPCHK(h2d(st, small, off.data(), (size_t)k));
-    hipLaunchKernelGGL(k_mrr_hat_part, dim3((unsigned)((ld + 255) / 256), nch), dim3(256), 0, st, (const int8_t *)P->data->X, R, p, ld, (int)n, k, (const double *)bd, cpc, hpart);
-    hipLaunchKernelGGL(k_mrr_hat_finish, dim3((unsigned)std::min<int64_t>((n * k + 255) / 256, 4096)), dim3(256), 0, st, (const double *)hpart, nch, ld, (int)n, k,
-                       (const double *)small, hatd);
+    CHK(M.stage_vec(off));
+    CHK(M.panel_hat(0, M.hatd));
     HIPCHK(hipGetLastError());
-    HIPCHK(d2h(st, hat_out, hatd, sizeof(double) * n * k));
+    HIPCHK(d2h(M.st, hat_out, M.hatd, sizeof(double) * n * k));
   }
-  for (int t = 0; t < k; ++t) for (int64_t j = 0; j < p; ++j) b_out[(size_t)t * p + j] = bh[(size_t)j * k + t];   // p x k column-major
   for (int t = 0; t < k; ++t) {
     if (mu_out) mu_out[t] = mu[t];
     if (h2_out) h2_out[t] = h2[t];

@@ -1,0 +1,374 @@
+// bwgr_amd/csrc/mtfit_host.hip.h -- the host scaffolding of the multi-trait fits: what bwgr_mrr (fits_host.hip.h), bwgr_pegs (pegs_host.hip.h) and
+// bwgr_pegsx (pegsx_host.hip.h) do alike around their own algebra.  Part of bwgr_hip.hip, before fits_host.hip.h; it defines no kernel (they are
+// mrr.hip.h and pegs.hip.h) and no entry but the plan hooks of the plans it holds.
+//   the plans:   mrr_plan (LDS of k_mrr_solve / k_mrr_linv), pegs_dense_plan (the dense leg), the grids the launch sites share
+//   mrr_sweep:   one panel design's share of a sweep
+//   MtList:      what an effect list says, checked on the host (mt_check_effects, worded with the caller's name)
+//   MtFit:       a fit's masks, device arrays and effects, and one member function per step the entries repeat; the entries keep their loops
+// ------------------------------------------------------------------------------------------------
+// The LDS plan of k_mrr_solve and k_mrr_linv for k traits and npat missingness patterns, decided here and nowhere else: the solve stages
+// the markers' k x k inverses (64 k^2 doubles) when they fit beside its fixed arrays, then as many of the block's per-pattern Gram matrices
+// as the rest of the budget holds (ngl); it reads patterns ngl.. from global memory, and without linv_lds fetches each marker's row of
+// its inverse one marker ahead.  bwgr_debug_mrr_plan exposes it to the CPU tests.
+static constexpr size_t MRR_LDS_MAX = 160 * 1024;
+static constexpr int MRR_NP = 64;             // workgroups (= partials) of the tail reductions k_mrr_ey and k_mrr_tilde, 256 rows or markers each per trip
+static constexpr int MRR_SETUP_WG = 8192;     // workgroups of k_mrr_setup_cols at most, four markers (one per wave) each per trip
+static constexpr int TAIL_THREADS = 256;      // threads per workgroup of the tail, product and finish kernels of the fp64 families
+// the grids the launch sites below and bwgr_debug_launch_plan share
+static inline int64_t mrr_setup_grid(int64_t p) { return std::min<int64_t>((p + 3) / 4, MRR_SETUP_WG); }
+static inline int64_t mrr_pass_grid(int64_t ld) { return std::min<int64_t>(ld / 64, MRR_PASS_WG); }
+struct MrrPlan { int linv_lds, ngl; size_t lds_solve, lds_linv; };
+static MrrPlan mrr_plan(int k, int npat) {
+  MrrPlan pl;
+  const size_t lds_fixed = mrr_solve_lds(0, 0), linv_b = sizeof(double) * MRR_MB * k * k;
+  pl.linv_lds = lds_fixed + linv_b <= MRR_LDS_MAX ? 1 : 0;
+  pl.ngl = (int)std::min<size_t>((size_t)npat, (MRR_LDS_MAX - lds_fixed - (pl.linv_lds ? linv_b : 0)) / (MRR_MB * MRR_MB * 4));
+  pl.lds_solve = mrr_solve_lds(pl.ngl, pl.linv_lds ? MRR_MB * k * k : 0);
+  pl.lds_linv = linv_b;
+  return pl;
+}
+extern "C" int bwgr_debug_mrr_plan(int k, int npat, int *linv_lds, int *ngl, int64_t *solve_lds_bytes, int64_t *linv_lds_bytes) {
+  if (k < 1 || k > MRR_KMAX || npat < 1 || npat > k) return BWGR_EINVAL;
+  const MrrPlan pl = mrr_plan(k, npat);
+  if (linv_lds) *linv_lds = pl.linv_lds;
+  if (ngl) *ngl = pl.ngl;
+  if (solve_lds_bytes) *solve_lds_bytes = (int64_t)pl.lds_solve;
+  if (linv_lds_bytes) *linv_lds_bytes = (int64_t)pl.lds_linv;
+  return BWGR_OK;
+}
+
+// The dense leg's plan, decided here and nowhere else (bwgr_debug_pegs_plan exposes it to the CPU tests)
+struct PegsDensePlan { int threads; size_t lds_bytes, ws_bytes; };
+static PegsDensePlan pegs_dense_plan(int64_t n, int64_t q, int k) {
+  PegsDensePlan pl;
+  pl.threads = (int)std::min<int64_t>(PEGS_TMAX, (n + 63) / 64 * 64);   // one row per thread up to 1024 rows, whole waves
+  pl.lds_bytes = pegs_leg_lds(pl.threads);
+  const size_t nq = (size_t)q, qk = nq * (size_t)k;
+  pl.ws_bytes = sizeof(double) * ((size_t)n * nq + 4 * qk + qk * (size_t)k + MRR_KMAX) + sizeof(int32_t) * nq;
+  return pl;
+}
+extern "C" int bwgr_debug_pegs_plan(int64_t n, int64_t q, int k, int64_t out[BWGR_PEGS_PLAN_NOUT]) {
+  if (!out) return fail(BWGR_EINVAL, "pegs plan: null pointer");
+  if (n < 1 || q < 1 || k < 1 || k > BWGR_MRR_MAXK)
+    return fail(BWGR_EINVAL, "pegs plan: n = %lld, q = %lld (each at least 1), k = %d (1 <= k <= %d)", (long long)n, (long long)q, k, BWGR_MRR_MAXK);
+  const PegsDensePlan pl = pegs_dense_plan(n, q, k);
+  out[0] = pl.threads; out[1] = (int64_t)pl.lds_bytes; out[2] = (int64_t)pl.ws_bytes;
+  return BWGR_OK;
+}
+
+// workgroups of k_pegs_dense_setup for an effect of q columns: one column per wave, four per workgroup and trip (MtFit::setup_effect and
+// bwgr_debug_pegs_launch_plan share it)
+static inline int64_t pegs_dense_setup_grid(int64_t q) { return std::min<int64_t>((q + 3) / 4, MRR_SETUP_WG); }
+
+// One design's share of a sweep (:866-902): what its launch train reads and writes on the device.  bwgr_mrr has one; bwgr_pegs one per
+// panel effect, all against the same residual (MrrSweepShared).
+struct MrrLeg {
+  const bwgr_panel *P = nullptr;
+  int64_t p = 0, nblk = 0;
+  int8_t *Xs = nullptr; int32_t *ordd = nullptr, *gram = nullptr;
+  double *xbar = nullptr, *Sd = nullptr, *XXd = nullptr, *XSXd = nullptr, *tilde = nullptr, *bd = nullptr, *Linv = nullptr, *db2 = nullptr;
+};
+struct MrrSweepShared {
+  int64_t ld; int G, npat;
+  const uint32_t *ztd; const uint8_t *zmd;
+  double *ed, *part, *dB, *iGd;     // the residual [trait][ld]; the pass's partial dots; the block's delta b; k x k staging of iG
+};
+// (the caller asks bufs.failed() once, after all its gets)
+static void mrr_leg_alloc(DevBufs &bufs, MrrLeg &L, const bwgr_panel *P, int npat, int k) {
+  L.P = P; L.p = P->data->p; L.nblk = (L.p + MRR_MB - 1) / MRR_MB;
+  const size_t np = (size_t)L.p, pk = np * k;
+  L.Xs = bufs.get<int8_t>(P->data->plan.x_bytes);
+  L.ordd = bufs.get<int32_t>(np); L.gram = bufs.get<int32_t>((size_t)L.nblk * npat * MRR_MB * MRR_MB);
+  L.xbar = bufs.get<double>(np); L.Sd = bufs.get<double>(npat * np);
+  L.XXd = bufs.get<double>(pk); L.XSXd = bufs.get<double>(pk); L.tilde = bufs.get<double>(pk); L.bd = bufs.get<double>(pk); L.Linv = bufs.get<double>(pk * k);
+  L.db2 = bufs.get<double>(MRR_KMAX);
+}
+// order -> k_permute_cols -> k_mrr_gram -> k_mrr_linv -> [k_mrr_pass(b-1 | b), k_mrr_solve(b)] for every block -> k_mrr_pass(last | -);
+// mc.iVe and iG (host, k x k) are the sweep's.  Leaves sum_j (delta b_jt)^2 in L.db2.
+static int mrr_sweep(hipStream_t st, const MrrLeg &L, const MrrSweepShared &W, const MrrConst &mc, const MrrPlan &plan, const std::vector<int> &order,
+                     const double *iG) {
+  const PanelData *D = L.P->data;
+  const int R = D->plan.R, k = mc.k, npat = W.npat, G = W.G;
+  const int64_t p = L.p, ld = W.ld, nblk = L.nblk;
+  const int cps = (int)((size_t)R / 16);
+  HIPCHK(h2d(st, L.ordd, order.data(), (size_t)p));
+  hipLaunchKernelGGL(k_permute_cols, dim3(8192), dim3(256), 0, st, (const uint4 *)D->X, (uint4 *)L.Xs, (const int32_t *)L.ordd, p, D->plan.K, cps);
+  hipLaunchKernelGGL(k_mrr_gram, dim3((unsigned)nblk, (unsigned)((npat + 3) / 4)), dim3(256), 0, st, (const int8_t *)L.Xs, R, p, ld, W.zmd, npat, L.gram);
+  HIPCHK(h2d(st, W.iGd, iG, (size_t)k * k));
+  hipLaunchKernelGGL(k_mrr_linv, dim3((unsigned)((p + 63) / 64)), dim3(64), plan.lds_linv, st, (const double *)L.XXd, (const double *)W.iGd, mc, p, L.Linv);
+  HIPCHK(zero(st, L.db2, (size_t)MRR_KMAX));
+  HIPCHK(hipGetLastError());
+  for (int64_t blk = 0; blk <= nblk; ++blk) {
+    MrrPassArgs pa; pa.Xs = L.Xs; pa.R = R; pa.p = p; pa.ld = ld; pa.nblk = (int)nblk; pa.zb = W.ztd; pa.e = W.ed; pa.dB = W.dB; pa.part = W.part;
+    pa.prev = blk > 0 ? (int)(blk - 1) : -1; pa.next = blk < nblk ? (int)blk : -1; pa.k = k;
+    hipLaunchKernelGGL(k_mrr_pass, dim3(G), dim3(256), 0, st, pa);
+    if (blk == nblk) break;
+    MrrSolveArgs sa; sa.part = W.part; sa.G = G; sa.order = L.ordd; sa.blk = (int)blk; sa.p = p; sa.gram = L.gram; sa.xbar = L.xbar; sa.S = L.Sd; sa.XX = L.XXd;
+    sa.Linv = L.Linv; sa.b = L.bd; sa.dB = W.dB; sa.db2 = L.db2; sa.ngl = plan.ngl; sa.linv_lds = plan.linv_lds;
+    hipLaunchKernelGGL(k_mrr_solve, dim3(1), dim3(256), plan.lds_solve, st, sa, mc);
+  }
+  HIPCHK(hipGetLastError());
+  return BWGR_OK;
+}
+
+// a dense effect on the device
+struct PegsDense {
+  int64_t q = 0;
+  double *Zd = nullptr, *XXd = nullptr, *XSXd = nullptr, *tilde = nullptr, *bd = nullptr, *Linv = nullptr, *db2 = nullptr;
+  int32_t *ordd = nullptr;
+};
+
+// ------------------------------------------------------------------------------------------------
+// What an effect list says, checked on the host.  It is a thing of its own, and not part of MtFit, because a call reads its traits in between:
+// they need the list's ld, and are copied from asynchronously, so they are declared before the MtFit (see there).
+struct MtList {
+  const bwgr_pegs_effect *eff = nullptr;
+  int neff = 0;
+  int64_t n = 0, ld = 0;
+  const bwgr_panel *P0 = nullptr;          // the first panel effect: its device, its row padding and its stream are the fit's
+  hipStream_t st = nullptr;
+  std::vector<std::vector<double>> Zc;     // per dense effect, Z without its padding rows (MtFit takes them over)
+};
+// The refusals every effect list meets, worded with the caller's name (`coef`: what it calls an effect's coefficients); none needs a device.
+// Then the device: the first panel's, or `device` where every effect is dense.
+static int mt_check_effects(const char *who, const char *coef, const bwgr_pegs_effect *eff, int neff, int64_t n, int device, double *const *outs, MtList &E) {
+  E.eff = eff; E.neff = neff; E.n = n;
+  for (int e = 0; e < neff; ++e) {
+    if (!outs[e]) return fail(BWGR_EINVAL, "%s: null pointer (%s of effect %d)", who, coef, e);
+    const bwgr_panel *P = eff[e].panel;
+    if (P) {
+      if (P->data->is_f32) return fail(BWGR_EINVAL, "%s: effect %d's panel holds fp32 genotypes; %s takes int8 panels only", who, e, who);
+      if (P->data->n != n) return fail(BWGR_EINVAL, "%s: effect %d has %lld rows, Y %lld", who, e, (long long)P->data->n, (long long)n);
+      if (!E.P0) E.P0 = P;
+      if (P->data->device != E.P0->data->device)
+        return fail(BWGR_EINVAL, "%s: effect %d's panel is on device %d, the first panel on device %d", who, e, P->data->device, E.P0->data->device);
+      if (P->data->plan.ld != E.P0->data->plan.ld)
+        return fail(BWGR_EINVAL, "%s: effect %d's panel pads its rows to ld = %lld, the first panel to %lld (make the panels with the same block / nwg)", who, e,
+                    (long long)P->data->plan.ld, (long long)E.P0->data->plan.ld);
+    } else {
+      if (!eff[e].Z) return fail(BWGR_EINVAL, "%s: effect %d has neither a panel nor Z", who, e);
+      if (eff[e].q < 1 || eff[e].q > 0x7FFFFF00ll || eff[e].ldz < n)
+        return fail(BWGR_EINVAL, "%s: effect %d: q = %lld columns of Z, ldz = %lld (q at least 1, ldz at least n = %lld)", who, e, (long long)eff[e].q,
+                    (long long)eff[e].ldz, (long long)n);
+    }
+  }
+  E.Zc.resize((size_t)neff);
+  for (int e = 0; e < neff; ++e)
+    if (!eff[e].panel) {
+      int64_t r = 0, j = 0;
+      if (!compact_z(eff[e].Z, n, eff[e].q, eff[e].ldz, E.Zc[(size_t)e], &r, &j))
+        return fail(BWGR_EINVAL, "%s: effect %d: Z[%lld, %lld] is not finite", who, e, (long long)r, (long long)j);
+    }
+  if (E.P0) HIPCHK(hipSetDevice(E.P0->data->device)); else CHK(require_device(device));
+  E.ld = E.P0 ? E.P0->data->plan.ld : (n + 127) / 128 * 128;
+  E.st = E.P0 ? E.P0->stream : nullptr;
+  return BWGR_OK;
+}
+
+// one effect of a fit: a panel's leg or a dense effect, and what the entries read of either
+struct MtEffect {
+  bool panel = false;
+  int64_t m = 0;                           // its columns
+  MrrLeg leg; PegsDense dense;
+  double *b() const { return panel ? leg.bd : dense.bd; }
+  double *tilde() const { return panel ? leg.tilde : dense.tilde; }
+  double *XX() const { return panel ? leg.XXd : dense.XXd; }
+  double *XSX() const { return panel ? leg.XSXd : dense.XSXd; }
+  double *db2() const { return panel ? leg.db2 : dense.db2; }
+};
+
+// A multi-trait fit on the device: k traits over the rows of an effect list, all effects against one residual.  An entry makes one after its
+// checks and its traits, then masks() -> alloc() (and its own gets; it asks bufs.failed() once) -> upload(), and calls the steps from its own
+// loops.  Every step enqueues on st what the entries enqueued there before, in the same order; the ones that return results end in d2h's wait.
+struct MtFit {
+  // Host data.  What an asynchronous copy reads -- Zc, order, the mask words, d, off -- stands BEFORE bufs: members go away in reverse order, so
+  // the holder's wait for the stream comes first (devbufs.h; tests/devbufs_check.cpp shows the semantics).  The same holds for what a caller
+  // hands to upload() and sweep_effect(): its traits and its iG are declared before its MtFit.
+  const int64_t n, ld; const int k; const hipStream_t st;
+  std::vector<std::vector<double>> Zc;
+  std::vector<CumulativeOrder> order;      // per effect, the column order of sweep s
+  std::vector<uint32_t> zt, zb;            // bit t: row observed for trait t; bit g: row observed in pattern g
+  std::vector<uint8_t> zm;
+  std::vector<double> d, off;              // k each, for stage_vec(): the mu shift (or the TH form's diagonal); the fitted values' offset (zero unless written)
+  MrrConst mc;                             // (the entries set iVe before every sweep)
+  int npat = 0, G = 0, nch_max = 1;
+  MrrPlan plan; PegsDensePlan dpl;
+  // Device data
+  DevBufs bufs;
+  uint32_t *zbd = nullptr, *ztd = nullptr; uint8_t *zmd = nullptr;
+  double *yd = nullptr, *ed = nullptr, *part = nullptr, *dB = nullptr, *tpart = nullptr, *sumyd = nullptr, *hatd = nullptr, *hpart = nullptr, *htmp = nullptr;
+  static constexpr size_t SMALL_IG = 512, SMALL_VEC = 768, SMALL_LEN = 1024;
+  double *small = nullptr, *iGd = nullptr, *vecd = nullptr;   // small: [0, SMALL_IG) reduction results; iGd = small + SMALL_IG: k x k; vecd = small + SMALL_VEC: a staged k-vector
+  std::vector<MtEffect> eff;
+  MrrSweepShared W;
+
+  MtFit(MtList &E, int k_) : n(E.n), ld(E.ld), k(k_), st(E.st), Zc(std::move(E.Zc)), d((size_t)k_), off((size_t)k_, 0.0), bufs(E.st), eff((size_t)E.neff) {
+    for (int e = 0; e < E.neff; ++e) {
+      eff[(size_t)e].panel = E.eff[e].panel != nullptr;
+      eff[(size_t)e].leg.P = E.eff[e].panel;
+      eff[(size_t)e].m = E.eff[e].panel ? E.eff[e].panel->data->p : E.eff[e].q;
+      order.emplace_back((size_t)eff[(size_t)e].m);
+    }
+  }
+  // MrrConst and the mask words from the traits and their missingness patterns
+  void masks(const TraitSet &S, const Patterns &pat) {
+    npat = (int)pat.rep.size();
+    memset(&mc, 0, sizeof(mc));
+    mc.k = k; mc.npat = npat;
+    for (int t = 0; t < k; ++t) { mc.pt[t] = pat.id[(size_t)t]; mc.nt[t] = S.nt[(size_t)t]; }
+    zt.resize((size_t)ld); zb.resize((size_t)ld);
+    pack_row_bits(S, (int64_t)0, k, zt.data());
+    pack_row_bits(S, pat.rep.data(), npat, zb.data());
+    append_byte_masks(S, pat.rep.data(), npat, zm);
+  }
+  // every array of the fit and of its effects; `summed`: the effects' fitted values are added up in hatd, a panel's through htmp
+  void alloc(bool want_hat, bool summed) {
+    const size_t nl = (size_t)ld, nn = (size_t)n;
+    G = (int)mrr_pass_grid(ld);
+    zbd = bufs.get<uint32_t>(nl); ztd = bufs.get<uint32_t>(nl); zmd = bufs.get<uint8_t>((size_t)npat * nl);
+    yd = bufs.get<double>(k * nl); ed = bufs.get<double>(k * nl);
+    part = bufs.get<double>((size_t)G * (MRR_MB + 1) * MRR_KMAX); dB = bufs.get<double>(MRR_MB * MRR_KMAX + MRR_KMAX);
+    small = bufs.get<double>(SMALL_LEN);
+    if (small) { iGd = small + SMALL_IG; vecd = small + SMALL_VEC; }
+    tpart = bufs.get<double>((size_t)MRR_NP * (MRR_KMAX * MRR_KMAX + MRR_KMAX)); sumyd = bufs.get<double>(MRR_KMAX);
+    bool panels = false;
+    for (MtEffect &E : eff) {
+      if (E.panel) {
+        mrr_leg_alloc(bufs, E.leg, E.leg.P, npat, k);
+        nch_max = std::max(nch_max, (int)std::min<int64_t>(64, E.m));
+        panels = true;
+      } else {
+        PegsDense &D = E.dense;
+        D.q = E.m;
+        const size_t nq = (size_t)D.q, qk = nq * k;
+        D.Zd = bufs.get<double>(nn * nq); D.XXd = bufs.get<double>(qk); D.XSXd = bufs.get<double>(qk); D.tilde = bufs.get<double>(qk); D.bd = bufs.get<double>(qk);
+        D.Linv = bufs.get<double>(qk * k); D.db2 = bufs.get<double>(MRR_KMAX); D.ordd = bufs.get<int32_t>(nq);
+      }
+    }
+    if (want_hat) hatd = bufs.get<double>(nn * k);
+    if (want_hat && panels) hpart = bufs.get<double>((size_t)nch_max * k * nl);
+    if (want_hat && panels && summed) htmp = bufs.get<double>(nn * k);
+    plan = mrr_plan(k, npat);
+    dpl = pegs_dense_plan(n, 1, k);
+    W = {ld, G, npat, ztd, zmd, ed, part, dB, iGd};
+  }
+  // the masks, y, e = y and the traits' sums (sumy == nullptr: zeros, for a fit that centres nothing)
+  int upload(const TraitSet &S, const double *sumy) {
+    const size_t nl = (size_t)ld;
+    HIPCHK(h2d(st, zbd, zb.data(), nl));
+    HIPCHK(h2d(st, ztd, zt.data(), nl));
+    HIPCHK(h2d(st, zmd, zm.data(), zm.size()));
+    HIPCHK(h2d(st, yd, S.y.data(), k * nl));
+    HIPCHK(h2d(st, ed, S.y.data(), k * nl));
+    if (sumy) HIPCHK(h2d(st, sumyd, sumy, (size_t)k)); else HIPCHK(zero(st, sumyd, (size_t)MRR_KMAX));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_linv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
+    return BWGR_OK;
+  }
+  // a dense effect's Z; b = 0
+  int stage_effect(int e) {
+    const MtEffect &E = eff[(size_t)e];
+    if (!E.panel) HIPCHK(h2d(st, E.dense.Zd, Zc[(size_t)e].data(), Zc[(size_t)e].size()));
+    HIPCHK(zero(st, E.b(), (size_t)E.m * k));
+    return BWGR_OK;
+  }
+  // XX, XSX and tilde of the effect's columns, one launch: a panel's centred where `centre` (then xbar too), a dense effect's as they are
+  int setup_effect(int e, int centre) {
+    const MtEffect &E = eff[(size_t)e];
+    if (E.panel) {
+      const MrrLeg &L = E.leg;
+      const PanelData *D = L.P->data;
+      hipLaunchKernelGGL(k_mrr_setup_cols, dim3((unsigned)mrr_setup_grid(L.p)), dim3(TAIL_THREADS), 0, st, (const int8_t *)D->X, D->plan.R, (int)n, L.p, ld,
+                         (const uint32_t *)zbd, (const double *)yd, (const double *)sumyd, mc, centre, L.xbar, L.Sd, L.XXd, L.XSXd, L.tilde);
+    } else {
+      const PegsDense &D = E.dense;
+      hipLaunchKernelGGL(k_pegs_dense_setup, dim3((unsigned)pegs_dense_setup_grid(D.q)), dim3(TAIL_THREADS), 0, st, (const double *)D.Zd, n, D.q, ld,
+                         (const uint32_t *)ztd, (const double *)yd, mc, D.XXd, D.XSXd, D.tilde);
+    }
+    HIPCHK(hipGetLastError());
+    return BWGR_OK;
+  }
+  // A reduction over an effect's m columns, partials in a fixed order: the k^2 products b'tilde (mode 0; mode 1: the TH form with its k traces, iG's
+  // diagonal at dvec), or the k column sums of `third` (mode 2)
+  int reduce(const double *b, const double *tilde, const double *third, int64_t m, int mode, int nout, const double *dvec, double *out) {
+    hipLaunchKernelGGL(k_mrr_tilde, dim3(MRR_NP, nout), dim3(256), 0, st, b, tilde, third, m, mode, mc, dvec, tpart);
+    hipLaunchKernelGGL(k_mrr_finish, dim3(1), dim3(256), 0, st, (const double *)tpart, MRR_NP, nout, small);
+    HIPCHK(hipGetLastError());
+    HIPCHK(d2h(st, out, small, sizeof(double) * nout));
+    return BWGR_OK;
+  }
+  // effect e's share of sweep `numit`, against mc.iVe and iG (host, k x k): mrr_sweep, or k_mrr_linv -> k_pegs_dense_leg
+  int sweep_effect(int e, int numit, const double *iG) {
+    const std::vector<int> &ord = order[(size_t)e].next(numit);
+    if (eff[(size_t)e].panel) return mrr_sweep(st, eff[(size_t)e].leg, W, mc, plan, ord, iG);
+    const PegsDense &D = eff[(size_t)e].dense;
+    HIPCHK(h2d(st, D.ordd, ord.data(), (size_t)D.q));
+    HIPCHK(h2d(st, iGd, iG, (size_t)k * k));
+    hipLaunchKernelGGL(k_mrr_linv, dim3((unsigned)((D.q + 63) / 64)), dim3(64), plan.lds_linv, st, (const double *)D.XXd, (const double *)iGd, mc, D.q, D.Linv);
+    PegsLegArgs A;
+    A.Z = D.Zd; A.n = n; A.ld = ld; A.q = (int)D.q; A.zt = ztd; A.e = ed; A.order = D.ordd; A.XX = D.XXd; A.Linv = D.Linv; A.b = D.bd; A.db2 = D.db2;
+    hipLaunchKernelGGL(k_pegs_dense_leg, dim3(1), dim3(dpl.threads), dpl.lds_bytes, st, A, mc);
+    HIPCHK(hipGetLastError());
+    return BWGR_OK;
+  }
+  // ey[0, k): e'y per trait over its observed rows; ey[k, 2k): the sums of e
+  int residual_sums(double *ey) {
+    hipLaunchKernelGGL(k_mrr_ey, dim3(MRR_NP, k), dim3(256), 0, st, (const double *)ed, (const double *)yd, ld, k, tpart);
+    hipLaunchKernelGGL(k_mrr_finish, dim3(1), dim3(256), 0, st, (const double *)tpart, MRR_NP, 2 * k, small);
+    HIPCHK(hipGetLastError());
+    HIPCHK(d2h(st, ey, small, sizeof(double) * 2 * k));
+    return BWGR_OK;
+  }
+  // sum_j (delta b_jt)^2 of the effect's last sweep, per trait
+  int read_db2(int e, double *out) { HIPCHK(d2h(st, out, eff[(size_t)e].db2(), sizeof(double) * k)); return BWGR_OK; }
+  // after a sweep: TH[s * k + t] = sum_j b_js tilde_jt, and the sweep's sum of (delta b)^2 over the traits
+  int effect_sums(int e, double *TH, double *db2) {
+    const MtEffect &E = eff[(size_t)e];
+    double t_[MRR_KMAX];
+    CHK(reduce(E.b(), E.tilde(), E.XSX(), E.m, 0, k * k, nullptr, TH));
+    CHK(read_db2(e, t_));
+    *db2 = 0.0;
+    for (int t = 0; t < k; ++t) *db2 += t_[t];
+    return BWGR_OK;
+  }
+  // v (d or off) into the staged k-vector
+  int stage_vec(const std::vector<double> &v) { HIPCHK(h2d(st, vecd, v.data(), (size_t)k)); return BWGR_OK; }
+  // e -= d on every trait's observed rows
+  int mu_shift() {
+    CHK(stage_vec(d));
+    hipLaunchKernelGGL(k_mrr_mu_shift, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st, ed, (const uint32_t *)ztd, ld, (int)n, k, (const double *)vecd);
+    HIPCHK(hipGetLastError());
+    return BWGR_OK;
+  }
+  // out (n x k) = a panel effect's X b plus the staged k-vector, for every row
+  int panel_hat(int e, double *out) {
+    const MrrLeg &L = eff[(size_t)e].leg;
+    const PanelData *D = L.P->data;
+    const int nch = (int)std::min<int64_t>(64, L.p);       // marker chunks
+    const int64_t cpc = (L.p + nch - 1) / nch;
+    hipLaunchKernelGGL(k_mrr_hat_part, dim3((unsigned)((ld + 255) / 256), nch), dim3(256), 0, st, (const int8_t *)D->X, D->plan.R, L.p, ld, (int)n, k, (const double *)L.bd, cpc, hpart);
+    hipLaunchKernelGGL(k_mrr_hat_finish, dim3((unsigned)std::min<int64_t>((n * k + 255) / 256, 4096)), dim3(256), 0, st, (const double *)hpart, nch, ld, (int)n, k,
+                       (const double *)vecd, out);
+    return BWGR_OK;
+  }
+  // hatd += the effect's share (a panel's with the staged k-vector, which the summing fits leave zero)
+  int add_effect_hat(int e) {
+    const MtEffect &E = eff[(size_t)e];
+    if (E.panel) {
+      CHK(panel_hat(e, htmp));
+      hipLaunchKernelGGL(k_pegs_add, dim3((unsigned)std::min<int64_t>((n * k + 255) / 256, 4096)), dim3(256), 0, st, hatd, (const double *)htmp, (int64_t)n * k);
+    } else {
+      hipLaunchKernelGGL(k_pegs_zb, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double *)E.dense.Zd, n, E.m, k, (const double *)E.dense.bd, hatd);
+    }
+    HIPCHK(hipGetLastError());
+    return BWGR_OK;
+  }
+  // the effect's coefficients as an m x k column-major matrix
+  int read_b(int e, double *out) {
+    const int64_t m = eff[(size_t)e].m;
+    std::vector<double> bh((size_t)m * k);
+    HIPCHK(d2h(st, bh.data(), eff[(size_t)e].b(), sizeof(double) * m * k));
+    for (int t = 0; t < k; ++t) for (int64_t j = 0; j < m; ++j) out[(size_t)t * m + j] = bh[(size_t)j * k + t];
+    return BWGR_OK;
+  }
+};

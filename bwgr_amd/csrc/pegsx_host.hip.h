@@ -1,6 +1,7 @@
 // bwgr_amd/csrc/pegsx_host.hip.h -- the host entry of PEGSX (src/RcppEigenX20251203.cpp:197-573): PEGSZ's effects with a
-// fixed design X beside them.  Part of bwgr_hip.hip, after pegs_host.hip.h, whose structure, effect checks and dense-effect holder it shares; it
-// defines no kernel.
+// fixed design X beside them.  Part of bwgr_hip.hip, after pegs_host.hip.h.  It holds the fit's own algebra: the option checks, the fixed design
+// (pegsx_setup.h), TrZSZ, the fixed step, the per-sweep tail (pegs_tail.h), the timing hooks and the outputs; the effect checks, the device arrays
+// and every repeated step are MtFit's (mtfit_host.hip.h).  It defines no kernel.
 //   once:       host (pegsx_setup.h): masks, patterns, per pattern (M'M)^+, b, the projected y.  Per effect k_mrr_setup_cols (uncentred) or
 //               k_pegs_dense_setup -> ZZ, tilde; k_mrr_tilde(mode 2) on ZZ; k_pegsx_trace_panel / _dense -> k_mrr_finish -> TrZSZ
 //   per sweep:  per effect in list order: mrr_sweep (panel) or k_mrr_linv -> k_pegs_dense_leg (dense); k_pegsx_fixed; k_mrr_ey ->
@@ -71,85 +72,29 @@ extern "C" int bwgr_pegsx(int device, const bwgr_pegs_effect *eff, int neff, con
   const PegsxOpts o = {maxit, logtol, covbend, covMinEv, df0, NNC != 0, XFA != 0, NumXFA};
   if (const char *why = pegsx_refuses(o))
     return fail(BWGR_EINVAL, "pegsx: %s (maxit = %d, logtol = %g, covbend = %g, covMinEv = %g, df0 = %g)", why, maxit, logtol, covbend, covMinEv, df0);
-  // ---- the effects: one n, one device, one row padding (bwgr_pegs's checks) ----
-  const bwgr_panel *P0 = nullptr;
-  for (int e = 0; e < neff; ++e) {
-    if (!u_out[e]) return fail(BWGR_EINVAL, "pegsx: null pointer (u of effect %d)", e);
-    const bwgr_panel *P = eff[e].panel;
-    if (P) {
-      if (P->data->is_f32) return fail(BWGR_EINVAL, "pegsx: effect %d's panel holds fp32 genotypes; pegsx takes int8 panels only", e);
-      if (P->data->n != n) return fail(BWGR_EINVAL, "pegsx: effect %d has %lld rows, Y %lld", e, (long long)P->data->n, (long long)n);
-      if (!P0) P0 = P;
-      if (P->data->device != P0->data->device) return fail(BWGR_EINVAL, "pegsx: effect %d's panel is on device %d, the first panel on device %d", e, P->data->device, P0->data->device);
-      if (P->data->plan.ld != P0->data->plan.ld)
-        return fail(BWGR_EINVAL, "pegsx: effect %d's panel pads its rows to ld = %lld, the first panel to %lld (make the panels with the same block / nwg)", e,
-                    (long long)P->data->plan.ld, (long long)P0->data->plan.ld);
-    } else {
-      if (!eff[e].Z) return fail(BWGR_EINVAL, "pegsx: effect %d has neither a panel nor Z", e);
-      if (eff[e].q < 1 || eff[e].q > 0x7FFFFF00ll || eff[e].ldz < n)
-        return fail(BWGR_EINVAL, "pegsx: effect %d: q = %lld columns of Z, ldz = %lld (q at least 1, ldz at least n = %lld)", e, (long long)eff[e].q, (long long)eff[e].ldz, (long long)n);
-    }
-  }
-  std::vector<std::vector<double>> Zc((size_t)neff);
-  for (int e = 0; e < neff; ++e)
-    if (!eff[e].panel) {
-      int64_t r = 0, j = 0;
-      if (!compact_z(eff[e].Z, n, eff[e].q, eff[e].ldz, Zc[(size_t)e], &r, &j)) return fail(BWGR_EINVAL, "pegsx: effect %d: Z[%lld, %lld] is not finite", e, (long long)r, (long long)j);
-    }
-  if (P0) HIPCHK(hipSetDevice(P0->data->device)); else CHK(require_device(device));
-  const int64_t ld = P0 ? P0->data->plan.ld : (n + 127) / 128 * 128;
+  MtList E;                                      // (before the fixed set, which needs its ld, and the fit, whose holder waits for the stream)
+  CHK(mt_check_effects("pegsx", "u", eff, neff, n, device, u_out, E));
+  const int64_t ld = E.ld;
   // ---- host set-up (:227-260): masks, patterns, (M'M)^+ per pattern, b, the projected y ----
   const FixedSet F = read_fixed(Y, X, n, k, f, ldx, ld);
   if (F.bad_row >= 0) return fail(BWGR_EINVAL, "pegsx: X[%lld, %lld] is not finite", (long long)F.bad_row, (long long)F.bad_col);
   const TraitSet &S = F.S;
   if (S.bad >= 0) return fail(BWGR_EINVAL, "pegsx: trait %d has %g observed rows (needs 2)", (int)S.bad, S.nt[(size_t)S.bad]);
   const Patterns &pat = F.pat;
-  const int npat = (int)pat.rep.size();
-  MrrConst mc; memset(&mc, 0, sizeof(mc));
-  mc.k = k; mc.npat = npat;
-  for (int t = 0; t < k; ++t) { mc.pt[t] = pat.id[(size_t)t]; mc.nt[t] = S.nt[(size_t)t]; }
-  std::vector<uint32_t> zt((size_t)ld), zb((size_t)ld);
-  std::vector<uint8_t> zm;
-  pack_row_bits(S, (int64_t)0, k, zt.data());
-  pack_row_bits(S, pat.rep.data(), npat, zb.data());
-  append_byte_masks(S, pat.rep.data(), npat, zm);
   std::vector<double> bfk((size_t)f * k);                                                          // b as the kernels hold it: [f][k]
   for (int t = 0; t < k; ++t) for (int c = 0; c < f; ++c) bfk[(size_t)c * k + t] = F.b[(size_t)t * f + c];
-
-  hipStream_t st = P0 ? P0->stream : nullptr;
-  std::vector<CumulativeOrder> order;            // (these are copied from asynchronously: declared before the holder, which waits for the stream)
-  for (int e = 0; e < neff; ++e) order.emplace_back((size_t)(eff[e].panel ? eff[e].panel->data->p : eff[e].q));
-  PegsxState T;
-  DevBufs bufs(st);
-  const int G = (int)mrr_pass_grid(ld), NP = MRR_NP;
-  const size_t nl = (size_t)ld, nn = (size_t)n, nf = (size_t)f;
+  PegsxState T;                                  // (its iG is copied from asynchronously: before the fit, as bfk is)
+  MtFit M(E, k);
+  M.masks(S, pat);
+  M.alloc(hat_out != nullptr, true);
+  hipStream_t st = M.st;
+  DevBufs &bufs = M.bufs;
+  const int npat = M.npat;
+  const size_t nn = (size_t)n, nf = (size_t)f;
   int64_t mmax = 1;
-  for (int e = 0; e < neff; ++e) mmax = std::max<int64_t>(mmax, eff[e].panel ? eff[e].panel->data->p : eff[e].q);
-  uint32_t *zbd = bufs.get<uint32_t>(nl), *ztd = bufs.get<uint32_t>(nl);
-  uint8_t *zmd = bufs.get<uint8_t>((size_t)npat * nl);
-  double *yd = bufs.get<double>(k * nl), *ed = bufs.get<double>(k * nl);
-  double *part = bufs.get<double>((size_t)G * (MRR_MB + 1) * MRR_KMAX), *dB = bufs.get<double>(MRR_MB * MRR_KMAX + MRR_KMAX);
-  double *small = bufs.get<double>(1024);            // [0, 512): reduction results; [512, 768): iG; [768, ...): the fitted values' offset (zero)
-  double *tpart = bufs.get<double>((size_t)NP * (MRR_KMAX * MRR_KMAX + MRR_KMAX)), *sumyd = bufs.get<double>(MRR_KMAX);
+  for (const MtEffect &Q : M.eff) mmax = std::max(mmax, Q.m);
   double *Xd = bufs.get<double>(nn * nf), *iXXd = bufs.get<double>((size_t)npat * nf * nf), *bfd = bufs.get<double>(nf * k);
   double *qpart = bufs.get<double>((size_t)pegsx_trace_grid(mmax) * npat);
-  std::vector<MrrLeg> legs((size_t)neff);
-  std::vector<PegsDense> dense((size_t)neff);
-  int nch_max = 1;
-  for (int e = 0; e < neff; ++e) {
-    if (eff[e].panel) {
-      mrr_leg_alloc(bufs, legs[(size_t)e], eff[e].panel, npat, k);
-      nch_max = std::max(nch_max, (int)std::min<int64_t>(64, legs[(size_t)e].p));
-    } else {
-      PegsDense &D = dense[(size_t)e];
-      D.q = eff[e].q;
-      const size_t nq = (size_t)D.q, qk = nq * k;
-      D.Zd = bufs.get<double>(nn * nq); D.XXd = bufs.get<double>(qk); D.XSXd = bufs.get<double>(qk); D.tilde = bufs.get<double>(qk); D.bd = bufs.get<double>(qk);
-      D.Linv = bufs.get<double>(qk * k); D.db2 = bufs.get<double>(MRR_KMAX); D.ordd = bufs.get<int32_t>(nq);
-    }
-  }
-  double *hatd = hat_out ? bufs.get<double>(nn * k) : nullptr, *hpart = (hat_out && P0) ? bufs.get<double>((size_t)nch_max * k * nl) : nullptr;
-  double *htmp = (hat_out && P0) ? bufs.get<double>(nn * k) : nullptr;
   const int timing = g_pegsx_timing;
   hipEvent_t ev0 = timing ? bufs.event(hipEventDefault) : hipEvent_t{}, ev1 = timing ? bufs.event(hipEventDefault) : hipEvent_t{};
   if (bufs.failed() || (timing && (!ev0 || !ev1))) return no_memory("pegsx");
@@ -163,106 +108,52 @@ extern "C" int bwgr_pegsx(int device, const bwgr_pegs_effect *eff, int neff, con
     acc += ms;
     return e_;
   };
-  HIPCHK(h2d(st, zbd, zb.data(), nl));
-  HIPCHK(h2d(st, ztd, zt.data(), nl));
-  HIPCHK(h2d(st, zmd, zm.data(), zm.size()));
-  HIPCHK(h2d(st, yd, S.y.data(), k * nl));
-  HIPCHK(h2d(st, ed, S.y.data(), k * nl));                                                         // e = y, :367
-  HIPCHK(zero(st, sumyd, (size_t)MRR_KMAX));                                                       // (read by the uncentred set-up, times xbar = 0)
-  HIPCHK(zero(st, small, (size_t)1024));
+  CHK(M.upload(S, nullptr));                                                                       // e = y, :367; no sums of y: nothing is centred
+  HIPCHK(zero(st, M.small, MtFit::SMALL_LEN));
   HIPCHK(h2d(st, Xd, F.X.data(), nn * nf));
   HIPCHK(h2d(st, iXXd, F.iXX.data(), (size_t)npat * nf * nf));
   HIPCHK(h2d(st, bfd, bfk.data(), nf * k));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_linv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
   const PegsxPlan xpl = pegsx_plan(n, f, k);
-  auto reduce = [&](const double *b, const double *tilde, const double *XSX, int64_t m, int mode, int nout, double *out) -> hipError_t {
-    hipLaunchKernelGGL(k_mrr_tilde, dim3(NP, nout), dim3(256), 0, st, b, tilde, XSX, m, mode, mc, (const double *)nullptr, tpart);
-    hipLaunchKernelGGL(k_mrr_finish, dim3(1), dim3(256), 0, st, (const double *)tpart, NP, nout, small);
-    hipError_t e_ = hipGetLastError();
-    return e_ != hipSuccess ? e_ : d2h(st, out, small, sizeof(double) * nout);
-  };
   // ---- per effect: ZZ and tilde of the raw columns (:277-290, :325-330), u = 0, TrZSZ (:292-323) ----
   std::vector<double> Tr((size_t)neff * k), szz(k), quad(npat);
   for (int e = 0; e < neff; ++e) {
-    const bool pan = eff[e].panel != nullptr;
-    const int64_t m = pan ? legs[(size_t)e].p : dense[(size_t)e].q;
-    const unsigned tg = (unsigned)pegsx_trace_grid(m);
-    if (pan) {
-      const MrrLeg &L = legs[(size_t)e];
-      const PanelData *D = L.P->data;
-      HIPCHK(zero(st, L.bd, (size_t)L.p * k));
-      if (timing) HIPCHK(hipEventRecord(ev0, st));
-      hipLaunchKernelGGL(k_mrr_setup_cols, dim3((unsigned)mrr_setup_grid(L.p)), dim3(TAIL_THREADS), 0, st, (const int8_t *)D->X, D->plan.R, (int)n, L.p, ld,
-                         (const uint32_t *)zbd, (const double *)yd, (const double *)sumyd, mc, 0, L.xbar, L.Sd, L.XXd, L.XSXd, L.tilde);
-      HIPCHK(hipGetLastError());
-      if (timing) HIPCHK(lap(ms_cols));
-      HIPCHK(reduce(L.bd, L.tilde, L.XXd, L.p, 2, k, szz.data()));
-      if (timing) HIPCHK(hipEventRecord(ev0, st));
-      hipLaunchKernelGGL(k_pegsx_trace_panel, dim3(tg), dim3(256), xpl.lds_trace, st, (const int8_t *)D->X, D->plan.R, L.p, ld, (const double *)Xd, n, f,
-                         (const uint32_t *)zbd, npat, (const double *)iXXd, qpart);
+    const MtEffect &Q = M.eff[(size_t)e];
+    const unsigned tg = (unsigned)pegsx_trace_grid(Q.m);
+    CHK(M.stage_effect(e));
+    if (timing) HIPCHK(hipEventRecord(ev0, st));
+    CHK(M.setup_effect(e, 0));
+    if (timing) HIPCHK(lap(ms_cols));
+    CHK(M.reduce(Q.b(), Q.tilde(), Q.XX(), Q.m, 2, k, nullptr, szz.data()));
+    if (timing) HIPCHK(hipEventRecord(ev0, st));
+    if (Q.panel) {
+      const PanelData *D = Q.leg.P->data;
+      hipLaunchKernelGGL(k_pegsx_trace_panel, dim3(tg), dim3(256), xpl.lds_trace, st, (const int8_t *)D->X, D->plan.R, Q.m, ld, (const double *)Xd, n, f,
+                         (const uint32_t *)M.zbd, npat, (const double *)iXXd, qpart);
     } else {
-      const PegsDense &D = dense[(size_t)e];
-      HIPCHK(h2d(st, D.Zd, Zc[(size_t)e].data(), Zc[(size_t)e].size()));
-      HIPCHK(zero(st, D.bd, (size_t)D.q * k));
-      if (timing) HIPCHK(hipEventRecord(ev0, st));
-      hipLaunchKernelGGL(k_pegs_dense_setup, dim3((unsigned)pegs_dense_setup_grid(D.q)), dim3(TAIL_THREADS), 0, st, (const double *)D.Zd, n, D.q, ld,
-                         (const uint32_t *)ztd, (const double *)yd, mc, D.XXd, D.XSXd, D.tilde);
-      HIPCHK(hipGetLastError());
-      if (timing) HIPCHK(lap(ms_cols));
-      HIPCHK(reduce(D.bd, D.tilde, D.XXd, D.q, 2, k, szz.data()));
-      if (timing) HIPCHK(hipEventRecord(ev0, st));
-      hipLaunchKernelGGL(k_pegsx_trace_dense, dim3(tg), dim3(256), xpl.lds_trace, st, (const double *)D.Zd, D.q, ld, (const double *)Xd, n, f, (const uint32_t *)zbd, npat,
-                         (const double *)iXXd, qpart);
+      hipLaunchKernelGGL(k_pegsx_trace_dense, dim3(tg), dim3(256), xpl.lds_trace, st, (const double *)Q.dense.Zd, Q.m, ld, (const double *)Xd, n, f,
+                         (const uint32_t *)M.zbd, npat, (const double *)iXXd, qpart);
     }
     HIPCHK(hipGetLastError());
     if (timing) HIPCHK(lap(ms_trace));
-    hipLaunchKernelGGL(k_mrr_finish, dim3(1), dim3(256), 0, st, (const double *)qpart, (int)tg, npat, small);
+    hipLaunchKernelGGL(k_mrr_finish, dim3(1), dim3(256), 0, st, (const double *)qpart, (int)tg, npat, M.small);
     HIPCHK(hipGetLastError());
-    HIPCHK(d2h(st, quad.data(), small, sizeof(double) * npat));
+    HIPCHK(d2h(st, quad.data(), M.small, sizeof(double) * npat));
     for (int t = 0; t < k; ++t) Tr[(size_t)e * k + t] = szz[(size_t)t] - quad[(size_t)pat.id[(size_t)t]];
   }
   pegsx_init(T, k, neff, f, o, S.nt.data(), F.ssy.data(), Tr.data(), nullptr);
   // ---- sweeps ----
-  const MrrPlan plan = mrr_plan(k, npat);
-  const MrrSweepShared W = {ld, G, npat, ztd, zmd, ed, part, dB, small + 512};
-  const PegsDensePlan dpl = pegs_dense_plan(n, 1, k);
   PegsxFixedArgs FA;
-  FA.X = Xd; FA.n = n; FA.ld = ld; FA.f = f; FA.zt = ztd; FA.e = ed; FA.iXX = iXXd; FA.b = bfd;
-  std::vector<double> ey(2 * (size_t)k), TH((size_t)neff * k * k), db2((size_t)neff), db2t(MRR_KMAX);
+  FA.X = Xd; FA.n = n; FA.ld = ld; FA.f = f; FA.zt = M.ztd; FA.e = M.ed; FA.iXX = iXXd; FA.b = bfd;
+  std::vector<double> ey(2 * (size_t)k), TH((size_t)neff * k * k), db2((size_t)neff);
   while (T.numit < maxit) {
     const auto t0 = std::chrono::steady_clock::now();
-    for (int t = 0; t < k; ++t) mc.iVe[t] = 1.0 / T.ve[(size_t)t];
-    for (int e = 0; e < neff; ++e) {
-      const std::vector<int> &ord = order[(size_t)e].next(T.numit);
-      const double *iG = T.eff[(size_t)e].iG.data();
-      if (eff[e].panel) { CHK(mrr_sweep(st, legs[(size_t)e], W, mc, plan, ord, iG)); continue; }
-      const PegsDense &D = dense[(size_t)e];
-      HIPCHK(h2d(st, D.ordd, ord.data(), (size_t)D.q));
-      HIPCHK(h2d(st, W.iGd, iG, (size_t)k * k));
-      hipLaunchKernelGGL(k_mrr_linv, dim3((unsigned)((D.q + 63) / 64)), dim3(64), plan.lds_linv, st, (const double *)D.XXd, (const double *)W.iGd, mc, D.q, D.Linv);
-      PegsLegArgs A;
-      A.Z = D.Zd; A.n = n; A.ld = ld; A.q = (int)D.q; A.zt = ztd; A.e = ed; A.order = D.ordd; A.XX = D.XXd; A.Linv = D.Linv; A.b = D.bd; A.db2 = D.db2;
-      hipLaunchKernelGGL(k_pegs_dense_leg, dim3(1), dim3(dpl.threads), dpl.lds_bytes, st, A, mc);
-      HIPCHK(hipGetLastError());
-    }
+    for (int t = 0; t < k; ++t) M.mc.iVe[t] = 1.0 / T.ve[(size_t)t];
+    for (int e = 0; e < neff; ++e) CHK(M.sweep_effect(e, T.numit, T.eff[(size_t)e].iG.data()));
     if (timing == 2) HIPCHK(hipEventRecord(ev0, st));
-    hipLaunchKernelGGL(k_pegsx_fixed, dim3(k), dim3(xpl.threads), xpl.lds_fixed, st, FA, mc);                                          // :502-509
+    hipLaunchKernelGGL(k_pegsx_fixed, dim3(k), dim3(xpl.threads), xpl.lds_fixed, st, FA, M.mc);                                        // :502-509
     if (timing == 2) { double ms = 0.0; HIPCHK(lap(ms)); ms_fixed.add(ms); }
-    hipLaunchKernelGGL(k_mrr_ey, dim3(NP, k), dim3(256), 0, st, (const double *)ed, (const double *)yd, ld, k, tpart);
-    hipLaunchKernelGGL(k_mrr_finish, dim3(1), dim3(256), 0, st, (const double *)tpart, NP, 2 * k, small);
-    HIPCHK(hipGetLastError());
-    HIPCHK(d2h(st, ey.data(), small, sizeof(double) * 2 * k));
-    for (int e = 0; e < neff; ++e) {
-      const bool pan = eff[e].panel != nullptr;
-      const MrrLeg &L = legs[(size_t)e];
-      const PegsDense &D = dense[(size_t)e];
-      HIPCHK(reduce(pan ? L.bd : D.bd, pan ? L.tilde : D.tilde, pan ? L.XSXd : D.XSXd, pan ? L.p : D.q, 0, k * k, TH.data() + (size_t)e * k * k));
-      HIPCHK(d2h(st, db2t.data(), pan ? L.db2 : D.db2, sizeof(double) * k));
-      double s = 0.0;
-      for (int t = 0; t < k; ++t) s += db2t[(size_t)t];
-      db2[(size_t)e] = s;
-    }
+    CHK(M.residual_sums(ey.data()));
+    for (int e = 0; e < neff; ++e) CHK(M.effect_sums(e, TH.data() + (size_t)e * k * k, &db2[(size_t)e]));
     const bool stop = pegsx_after_sweep(T, o, ey.data(), TH.data(), db2.data(), nullptr);
     if (cnv_out) cnv_out[T.numit - 1] = T.cnv;
     if (timing) ms_sweep.add(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
@@ -277,32 +168,15 @@ extern "C" int bwgr_pegsx(int device, const bwgr_pegs_effect *eff, int neff, con
   HIPCHK(d2h(st, bfk.data(), bfd, sizeof(double) * nf * k));
   if (bfix_out) for (int t = 0; t < k; ++t) for (int c = 0; c < f; ++c) bfix_out[(size_t)t * f + c] = bfk[(size_t)c * k + t];   // f x k column-major
   if (hat_out) {
-    HIPCHK(zero(st, hatd, nn * k));
-    hipLaunchKernelGGL(k_pegs_zb, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double *)Xd, n, (int64_t)f, k, (const double *)bfd, hatd);
+    HIPCHK(zero(st, M.hatd, nn * k));
+    hipLaunchKernelGGL(k_pegs_zb, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double *)Xd, n, (int64_t)f, k, (const double *)bfd, M.hatd);
     HIPCHK(hipGetLastError());
   }
   for (int e = 0; e < neff; ++e) {
-    const bool pan = eff[e].panel != nullptr;
-    const int64_t m = pan ? legs[(size_t)e].p : dense[(size_t)e].q;
-    const double *bd = pan ? legs[(size_t)e].bd : dense[(size_t)e].bd;
-    std::vector<double> bh((size_t)m * k);
-    HIPCHK(d2h(st, bh.data(), bd, sizeof(double) * m * k));
-    for (int t = 0; t < k; ++t) for (int64_t j = 0; j < m; ++j) u_out[e][(size_t)t * m + j] = bh[(size_t)j * k + t];   // m x k column-major
-    if (!hat_out) continue;
-    if (pan) {
-      const PanelData *D = legs[(size_t)e].P->data;
-      const int nch = (int)std::min<int64_t>(64, m);
-      const int64_t cpc = (m + nch - 1) / nch;
-      hipLaunchKernelGGL(k_mrr_hat_part, dim3((unsigned)((ld + 255) / 256), nch), dim3(256), 0, st, (const int8_t *)D->X, D->plan.R, m, ld, (int)n, k, bd, cpc, hpart);
-      hipLaunchKernelGGL(k_mrr_hat_finish, dim3((unsigned)std::min<int64_t>((n * k + 255) / 256, 4096)), dim3(256), 0, st, (const double *)hpart, nch, ld, (int)n, k,
-                         (const double *)(small + 768), htmp);
-      hipLaunchKernelGGL(k_pegs_add, dim3((unsigned)std::min<int64_t>((n * k + 255) / 256, 4096)), dim3(256), 0, st, hatd, (const double *)htmp, (int64_t)n * k);
-    } else {
-      hipLaunchKernelGGL(k_pegs_zb, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double *)dense[(size_t)e].Zd, n, m, k, bd, hatd);
-    }
-    HIPCHK(hipGetLastError());
+    CHK(M.read_b(e, u_out[e]));
+    if (hat_out) CHK(M.add_effect_hat(e));                                                         // (the staged offset is zero: `small` was zeroed and nothing wrote it)
   }
-  if (hat_out) HIPCHK(d2h(st, hat_out, hatd, sizeof(double) * nn * k));
+  if (hat_out) HIPCHK(d2h(st, hat_out, M.hatd, sizeof(double) * nn * k));
   std::vector<double> GC((size_t)neff * k * k);
   pegsx_finish(T, GC.data());
   for (int t = 0; t < k; ++t) if (ve_out) ve_out[t] = T.ve[(size_t)t];

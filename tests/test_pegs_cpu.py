@@ -261,6 +261,36 @@ def test_no_gpu_means_enodev():
         assert ei.value.code == 5   # BWGR_ENODEV
 
 
+def test_shared_effect_check_runs_without_a_device_and_names_its_caller():
+    """a NaN in a dense effect is refused by the check PEGSZ and PEGSX share (mt_check_effects, mtfit_host.hip.h): before a device is asked
+    for, in the caller's name, with the effect's index"""
+    import bwgr_amd
+    from bwgr_amd import dense
+    Y = np.random.default_rng(1).normal(size=(8, 2))
+    Z = np.random.default_rng(2).normal(size=(8, 3))
+    Zbad = Z.copy()
+    Zbad[5, 1] = np.nan
+    for call, who, e in ((lambda: bwgr_amd.PEGSZ(Y, [dense(Zbad)]), "pegs:", 0), (lambda: bwgr_amd.PEGSX(Y, np.ones((8, 1)), [dense(Z), dense(Zbad)]), "pegsx:", 1)):
+        with pytest.raises(bwgr_amd.BwgrError) as ei:
+            call()
+        msg = str(ei.value)
+        assert ei.value.code == 1 and "not finite" in msg and "effect %d" % e in msg, msg
+        assert msg.startswith("bwgr status 1: " + who), msg   # (BwgrError puts the status in front of the library's message)
+
+
+def test_repeated_steps_are_launched_in_one_file_only():
+    """what the multi-trait entries do alike is MtFit's: these kernels are launched, and these calls made, in mtfit_host.hip.h and in none of
+    the entries' files (the per-trait fits' own pack_row_bits call, with other arguments, is not meant)"""
+    src = {name: open(os.path.join(CSRC, name)).read() for name in ("fits_host.hip.h", "pegs_host.hip.h", "pegsx_host.hip.h", "mtfit_host.hip.h")}
+    pats = [r"hipLaunchKernelGGL\(\s*%s\s*," % kn for kn in ("k_mrr_tilde", "k_mrr_ey", "k_mrr_hat_part", "k_pegs_dense_leg", "k_pegs_dense_setup", "k_mrr_setup_cols")]
+    pats += [re.escape("pack_row_bits(S, (int64_t)0"), r"hipFuncSetAttribute\([^;]*\bk_mrr_solve\b"]
+    for pat in pats:
+        where = sorted(name for name, txt in src.items() if re.search(pat, txt))
+        assert where == ["mtfit_host.hip.h"], (pat, where)
+    main = open(os.path.join(CSRC, "bwgr_hip.hip")).read()
+    assert main.index('#include "mtfit_host.hip.h"') < main.index('#include "fits_host.hip.h"') < main.index('#include "pegs_host.hip.h"')
+
+
 def test_effect_kinds():
     """the documented rule: integer-valued -> panel, a non-integer value -> dense, dense(Z) -> dense whatever it holds"""
     import bwgr_amd
