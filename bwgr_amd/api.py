@@ -1080,6 +1080,75 @@ class dense:
         self.Z = np.asfortranarray(Zm)
 
 
+def _is_scipy_sparse(S):
+    return type(S).__module__.split(".")[0] == "scipy" and hasattr(S, "tocsc")
+
+
+class sparse:
+    """Marks a design as a sparse effect of PEGS / PEGSZ / PEGSX (and is what PEGS_sparse / PEGSZ_sparse sweep): an n x q column-compressed
+    matrix -- the incidence matrix of environments, locations, blocks or genotype-by-environment cells -- that takes nnz + q k^2 values on the
+    device, never n q.  sparse(S) accepts
+      (data, indices, indptr) with shape=(n, q): the CSC arrays as they are (row indices strictly increasing within a column);
+      any scipy.sparse matrix: through .tocsc() with duplicates summed and indices sorted (scipy is imported only when given one);
+      a 2-D array: its nonzeros are taken.
+    The values are rounded to float once, as the reference casts S to float (src/RcppEigenX20251203.cpp:821, :1028); the engine is fp64.
+    Where no row occurs in two columns the engine updates all columns at once; serial=True forces the one-wave leg that walks the columns in
+    the sweep's order (for tests and tools/pegs_sparse_probe.py) -- on such a matrix both give the same bits."""
+
+    def __init__(self, S, shape=None, serial=False):
+        if isinstance(S, sparse):
+            data, indices, indptr, shape = S.data, S.indices, S.indptr, S.shape
+        elif _is_scipy_sparse(S):
+            import scipy.sparse  # noqa: F401  (only here)
+            M = S.tocsc(copy=True)
+            M.sum_duplicates()
+            M.sort_indices()
+            data, indices, indptr, shape = M.data, M.indices, M.indptr, M.shape
+        elif isinstance(S, tuple) and len(S) == 3:
+            if shape is None or len(shape) != 2:
+                raise BwgrError(1, "sparse: (data, indices, indptr) needs shape=(n, q)")
+            data, indices, indptr = S
+        else:
+            A = np.asarray(S)
+            if A.ndim == 1:
+                A = A[:, None]
+            if A.ndim != 2:
+                raise BwgrError(1, "sparse: S has shape %s; it must be n x q" % (A.shape,))
+            cols, rows = np.nonzero(A.T)        # (by column, rows ascending within one)
+            data, indices, shape = A[rows, cols], rows, A.shape
+            indptr = np.concatenate([[0], np.cumsum(np.bincount(cols, minlength=A.shape[1]))])
+        with np.errstate(over="ignore"):
+            self.data = np.ascontiguousarray(np.asarray(data, np.float64).ravel().astype(np.float32).astype(np.float64))
+        ind, ptr = np.asarray(indices).ravel(), np.asarray(indptr).ravel()
+        if ind.size and (ind.min() < -2 ** 31 or ind.max() >= 2 ** 31):
+            raise BwgrError(1, "sparse: a row index does not fit 32 bits")
+        self.indices = np.ascontiguousarray(ind.astype(np.int32))
+        self.indptr = np.ascontiguousarray(ptr.astype(np.int64))
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.serial = bool(serial)
+        if self.indptr.size != self.shape[1] + 1 or self.data.size != self.indices.size or (self.indptr.size and self.indptr[-1] > self.data.size):
+            raise BwgrError(1, "sparse: %d values, %d indices and %d column pointers do not describe %d columns" %
+                            (self.data.size, self.indices.size, self.indptr.size, self.shape[1]))
+
+    def toarray(self):
+        """the dense n x q copy (float64, column-major); entries stored twice are summed"""
+        A = np.zeros(self.shape, order="F")
+        cols = np.repeat(np.arange(self.shape[1]), np.diff(self.indptr))
+        np.add.at(A, (self.indices[:len(cols)], cols), self.data[:len(cols)])
+        return A
+
+
+def pegs_sparse_plan(n, q, nnz, max_col_nnz, k, disjoint):
+    """bwgr_debug_pegs_sparse_plan (host arithmetic, no GPU) for a sparse effect of n rows, q columns and nnz stored entries (at most
+    max_col_nnz in a column), k traits: the threads per workgroup and the workgroups of the set-up kernel and of the two legs, the columns one
+    trip of the disjoint grid covers, the leg a sweep takes ("disjoint" exactly when the matrix is row-disjoint) and the device workspace."""
+    out = (C.c_int64 * 9)()
+    check(_lib.lib().bwgr_debug_pegs_sparse_plan(int(n), int(q), int(nnz), int(max_col_nnz), int(k), int(bool(disjoint)), out))
+    r = dict(zip(("setup_threads", "setup_wg", "serial_threads", "serial_wg", "disjoint_threads", "disjoint_wg", "trip_cols", "leg", "ws_bytes"), [int(v) for v in out]))
+    r["leg"] = "disjoint" if r["leg"] else "serial"
+    return r
+
+
 def pegs_plan(n, q, k):
     """bwgr_debug_pegs_plan (host arithmetic, no GPU): dict(threads, lds_bytes, ws_bytes) of the dense leg."""
     out = (C.c_int64 * 3)()
@@ -1088,11 +1157,14 @@ def pegs_plan(n, q, k):
 
 
 def _pegs_effect(X, panel_kw):
-    """(Panel, made here) or (dense, False): the rule of `dense`'s docstring."""
+    """(Panel, made here), (dense, False) or (sparse, False): the rule of `dense`'s docstring; a `sparse` passes through and a scipy.sparse
+    matrix is one."""
     if isinstance(X, Panel):
         return X, False
-    if isinstance(X, dense):
+    if isinstance(X, (dense, sparse)):
         return X, False
+    if _is_scipy_sparse(X):
+        return sparse(X), False
     if hasattr(X, "data_ptr"):
         return Panel(X, **panel_kw), True
     Xm = np.asarray(X)
@@ -1109,13 +1181,18 @@ def _pegs_effect(X, panel_kw):
 
 
 class _Eff(C.Structure):
-    """bwgr_pegs_effect"""
-    _fields_ = [("panel", C.c_void_p), ("Z", C.c_void_p), ("q", C.c_int64), ("ldz", C.c_int64)]
+    """bwgr_pegs_effect_ex"""
+    _fields_ = [("panel", C.c_void_p), ("Z", C.c_void_p), ("q", C.c_int64), ("ldz", C.c_int64),
+                ("colptr", C.c_void_p), ("rowidx", C.c_void_p), ("val", C.c_void_p), ("flags", C.c_int64)]
+
+
+def _eff_rows(E):
+    return E.n if isinstance(E, Panel) else E.shape[0] if isinstance(E, sparse) else E.Z.shape[0]
 
 
 @contextlib.contextmanager
 def _pegs_effects(X_list, panel_kw, round_dense):
-    """Opens an effect list through _pegs_effect: (effs, the bwgr_pegs_effect array, every effect's column count), and closes the panels made
+    """Opens an effect list through _pegs_effect: (effs, the bwgr_pegs_effect_ex array, every effect's column count), and closes the panels made
     here when the block ends.  round_dense: a dense Z is rounded to float (the copies live as long as the block)."""
     effs, made, keep, ps = [], [], [], []
     try:
@@ -1129,6 +1206,10 @@ def _pegs_effects(X_list, panel_kw, round_dense):
             if isinstance(E, Panel):
                 ce[i].panel = E._h.value
                 ps.append(E.p)
+            elif isinstance(E, sparse):
+                ce[i].colptr = E.indptr.ctypes.data; ce[i].rowidx = E.indices.ctypes.data; ce[i].val = E.data.ctypes.data
+                ce[i].q = E.shape[1]; ce[i].flags = 1 if E.serial else 0
+                ps.append(E.shape[1])
             else:
                 keep.append(np.asfortranarray(E.Z.astype(np.float32).astype(np.float64)) if round_dense else E.Z)
                 ce[i].Z = keep[-1].ctypes.data; ce[i].q = keep[-1].shape[1]; ce[i].ldz = max(keep[-1].shape[0], 1)
@@ -1139,7 +1220,7 @@ def _pegs_effects(X_list, panel_kw, round_dense):
             P.close()
 
 
-def _pegs(Y, X_list, maxit, logtol, covbend, covMinEv, XFA, NNC, own_text, device, cnv_trace, panel_kw):
+def _pegs(Y, X_list, maxit, logtol, covbend, covMinEv, XFA, NNC, text, device, cnv_trace, panel_kw):
     with _pegs_effects(X_list, dict(panel_kw, device=device), False) as (effs, ce, ps):
         if not effs:
             raise BwgrError(1, "pegs: X_list holds no effects")
@@ -1147,7 +1228,7 @@ def _pegs(Y, X_list, maxit, logtol, covbend, covMinEv, XFA, NNC, own_text, devic
         if Ym.ndim == 1:
             Ym = Ym[:, None]
         Ym = Ym.astype(np.float32).astype(np.float64)   # PEGS receives float matrices (src/RcppEigenX20251203.cpp:10)
-        rows = [E.n if isinstance(E, Panel) else E.Z.shape[0] for E in effs]
+        rows = [_eff_rows(E) for E in effs]
         n = rows[0]
         if any(r != n for r in rows):
             raise BwgrError(1, "pegs: the effects have %s rows; all must have the same" % (rows,))
@@ -1161,8 +1242,8 @@ def _pegs(Y, X_list, maxit, logtol, covbend, covMinEv, XFA, NNC, own_text, devic
         b = [np.zeros((p_, kk), order="F") for p_ in ps]; GC = [np.zeros((kk, kk), order="F") for _ in ps]
         bp = (C.c_void_p * neff)(*[a.ctypes.data for a in b]); gp = (C.c_void_p * neff)(*[a.ctypes.data for a in GC])
         cnv = np.zeros(max(int(maxit), 1)); its = C.c_int()
-        check(_lib.lib().bwgr_pegs(int(device), C.cast(ce, C.c_void_p), neff, _dp(Yf), int(n), int(k), int(maxit), f32(logtol), f32(covbend), f32(covMinEv),
-                                   int(XFA), int(bool(NNC)), int(own_text), _dp(mu), C.cast(bp, C.c_void_p), _dp(hat), _dp(h2), C.cast(gp, C.c_void_p),
+        check(_lib.lib().bwgr_pegs_ex(int(device), C.cast(ce, C.c_void_p), neff, _dp(Yf), int(n), int(k), int(maxit), f32(logtol), f32(covbend), f32(covMinEv),
+                                   int(XFA), int(bool(NNC)), int(text), _dp(mu), C.cast(bp, C.c_void_p), _dp(hat), _dp(h2), C.cast(gp, C.c_void_p),
                                    _dp(bend), C.byref(its), _dp(cnv)))
         nit = int(its.value)
         out = dict(zip(PEGS_KEYS, (mu, b, hat, h2, GC, bend, nit, float(cnv[max(nit, 1) - 1]))))
@@ -1185,10 +1266,29 @@ def PEGS(Y, X, maxit=100, logtol=-4.0, covbend=1.1, covMinEv=10e-4, XFA=-1, NNC=
 def PEGSZ(Y, X_list, maxit=100, logtol=-4.0, covbend=1.1, covMinEv=10e-4, XFA=-1, NNC=True, *, device=0, cnv_trace=False, **kw):
     """PEGSZ(Y, X_list, ...), src/RcppEigenX20251203.cpp:576-808 (R/RcppExports.R:288): PEGS over a list of designs, swept one after another
     in list order against one residual, each with its own k x k covariance.  Every element of X_list is an effect as `dense` describes: a
-    Panel / integer matrix (int8 genotypes on the device) or a dense float matrix / dense(Z); all have the same n, all panels live on one
+    Panel / integer matrix (int8 genotypes on the device), a dense float matrix / dense(Z) or a sparse one (sparse(S) or a scipy.sparse
+    matrix: an incidence matrix held column-compressed); all have the same n, all panels live on one
     device and are made with the same block / nwg.  device= matters only when no effect is a panel.  Returns PEGS's dict with b and GC as
     lists (one entry per effect) and bend as a vector."""
     return _pegs(Y, list(X_list), maxit, logtol, covbend, covMinEv, XFA, NNC, 0, device, cnv_trace, kw)
+
+
+def PEGS_sparse(Y, S, maxit=100, logtol=-4.0, covbend=1.1, covMinEv=10e-4, XFA=-1, NNC=True, *, device=0, cnv_trace=False, **kw):
+    """PEGS_sparse(Y, S, ...), src/RcppEigenX20251203.cpp:811-1007 (R/RcppExports.R:292): PEGS on one sparse design.  S is whatever `sparse`
+    accepts (a `sparse`, a scipy.sparse matrix, a 2-D array whose nonzeros are taken); its values are rounded to float as the reference casts
+    them.  Returns PEGS's dict.  The text is PEGS's own (the intercept step divides by n_t - 1, :977)."""
+    r = _pegs(Y, [S if isinstance(S, sparse) else sparse(S)], maxit, logtol, covbend, covMinEv, XFA, NNC, 1, device, cnv_trace, kw)
+    r["b"], r["GC"], r["bend"] = r["b"][0], r["GC"][0], float(r["bend"][0])
+    return r
+
+
+def PEGSZ_sparse(Y, X_list, maxit=100, logtol=-4.0, covbend=1.1, covMinEv=10e-4, XFA=-1, NNC=True, *, device=0, cnv_trace=False, **kw):
+    """PEGSZ_sparse(Y, X_list, ...), src/RcppEigenX20251203.cpp:1010-1250 (R/RcppExports.R:296): PEGSZ over a list of sparse designs, under
+    that function's own text -- its intercept step divides the residual sums by n_t (:1202) where PEGSZ divides by n_t - 1.  Every element
+    of X_list that is not already an effect (`sparse`, `dense`, Panel) is made a `sparse`; the reference takes sparse designs only, here any
+    mix of effect kinds runs under this text.  Returns PEGSZ's dict."""
+    effs = [X if isinstance(X, (sparse, dense, Panel)) else sparse(X) for X in X_list]
+    return _pegs(Y, effs, maxit, logtol, covbend, covMinEv, XFA, NNC, 2, device, cnv_trace, kw)
 
 
 # ---- PEGSX: fixed effects beside the random effects of the multi-trait fit (bwgr_pegsx, include/bwgr.h) ----
@@ -1225,7 +1325,7 @@ def PEGSX(Y, X, Z_list, maxit=500, logtol=-8.0, covbend=1.1, covMinEv=10e-4, cor
           XFA=False, NumXFA=3, *, device=0, cnv_trace=False, **kw):
     """PEGSX(Y, X, Z_list, ...), src/RcppEigenX20251203.cpp:197-573 (R/RcppExports.R:284): Y = X b + sum_r Z_r u_r + E for k correlated
     traits (NaN in Y = missing) -- a fixed design X (n x f, an intercept is a column of it; nothing is centred) beside the random effects of
-    Z_list, each an effect as `dense` describes and swept as PEGSZ sweeps it.  list(TrZSZ, b, u, vb_list, GC_list, ve, hat, its, cnv, bend)
+    Z_list, each an effect as `dense` and `sparse` describe and swept as PEGSZ sweeps it.  list(TrZSZ, b, u, vb_list, GC_list, ve, hat, its, cnv, bend)
     as a dict: TrZSZ, u, vb_list and GC_list are lists with one entry per effect, b is f x k, bend a vector.  Y, X, dense Z and the real
     options are rounded to float as the reference receives them; the engine is fp64.  The marker order of sweep s is em_order(m, s) per effect.
     InnerGS=True and NoInv=True are refused; cores and verbose are accepted and ignored; XFA=True with NumXFA <= 0 is XFA=False.
@@ -1246,7 +1346,7 @@ def PEGSX(Y, X, Z_list, maxit=500, logtol=-8.0, covbend=1.1, covMinEv=10e-4, cor
         n, k = Yf.shape
         if Xf.shape[0] != n:
             raise BwgrError(1, "pegsx: X has %d rows, Y %d; nrow(X) must equal nrow(Y)" % (Xf.shape[0], n))
-        rows = [E.n if isinstance(E, Panel) else E.Z.shape[0] for E in effs]
+        rows = [_eff_rows(E) for E in effs]
         if any(r != n for r in rows):
             raise BwgrError(1, "pegsx: the effects have %s rows, Y %d; all must have the same rows" % (rows, n))
         f, neff, kk = Xf.shape[1], len(effs), max(k, 1)
@@ -1255,7 +1355,7 @@ def PEGSX(Y, X, Z_list, maxit=500, logtol=-8.0, covbend=1.1, covMinEv=10e-4, cor
         vb = [np.zeros((kk, kk), order="F") for _ in ps]; GC = [np.zeros((kk, kk), order="F") for _ in ps]
         ptrs = lambda arrs: C.cast((C.c_void_p * max(neff, 1))(*[a.ctypes.data for a in arrs]), C.c_void_p)
         cnv = np.zeros(max(int(maxit), 1)); its = C.c_int()
-        check(_lib.lib().bwgr_pegsx(int(device), C.cast(ce, C.c_void_p), neff, _dp(Xf), max(n, 1), int(f), _dp(Yf), int(n), int(k), int(maxit), f32(logtol),
+        check(_lib.lib().bwgr_pegsx_ex(int(device), C.cast(ce, C.c_void_p), neff, _dp(Xf), max(n, 1), int(f), _dp(Yf), int(n), int(k), int(maxit), f32(logtol),
                                     f32(covbend), f32(covMinEv), f32(df0), int(bool(NNC)), int(bool(XFA)), int(NumXFA), int(bool(InnerGS)), int(bool(NoInv)),
                                     _dp(Tr), _dp(b), ptrs(u), ptrs(vb), ptrs(GC), _dp(ve), _dp(hat), C.byref(its), _dp(cnv), _dp(bend)))
         nit = int(its.value)

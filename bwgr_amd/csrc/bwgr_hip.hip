@@ -21,6 +21,7 @@
 #include "../../include/bwgr.h"
 #include "devbufs.h"
 #include "traits.h"
+#include "csc.h"
 #include "rng.hip.h"
 #include "sweep.hip.h"
 #include "sweep3.hip.h"
@@ -32,6 +33,7 @@
 #include "uvb2.hip.h"
 #include "pegs.hip.h"
 #include "pegsx.hip.h"
+#include "pegs_sparse.hip.h"
 #include "pegsx_setup.h"
 #include "kernels.hip.h"
 #include <stdlib.h>

@@ -38,7 +38,7 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   if ((o.XFA || o.ACS) && (o.NumXFA < 1 || o.NumXFA > k))
     return fail(BWGR_EINVAL, "mrr: NumXFA = %d with XFA / ACS needs 1 <= NumXFA <= k = %d (the reference indexes eigenvalue k - NumXFA)", o.NumXFA, k);
   const int64_t n = P->data->n, p = P->data->p;
-  const bwgr_pegs_effect one = {P, nullptr, 0, 0};
+  const bwgr_pegs_effect_ex one = {P, nullptr, 0, 0, nullptr, nullptr, nullptr, 0};
   MtList E;
   CHK(mt_check_effects("mrr", "b", &one, 1, n, P->data->device, &b_out, E));                        // (nothing left to refuse: the panel's device, ld and stream)
   // (the int32 pattern Grams sum over at most n rows: n * max|x|^2 < 2^31 holds for every int8 panel, panel_build_gram)

@@ -1,7 +1,8 @@
 // bwgr_amd/csrc/mtfit_host.hip.h -- the host scaffolding of the multi-trait fits: what bwgr_mrr (fits_host.hip.h), bwgr_pegs (pegs_host.hip.h) and
 // bwgr_pegsx (pegsx_host.hip.h) do alike around their own algebra.  Part of bwgr_hip.hip, before fits_host.hip.h; it defines no kernel (they are
 // mrr.hip.h and pegs.hip.h) and no entry but the plan hooks of the plans it holds.
-//   the plans:   mrr_plan (LDS of k_mrr_solve / k_mrr_linv), pegs_dense_plan (the dense leg), the grids the launch sites share
+//   the plans:   mrr_plan (LDS of k_mrr_solve / k_mrr_linv), pegs_dense_plan (the dense leg), pegs_sparse_plan (the sparse legs), the grids
+//                the launch sites share
 //   mrr_sweep:   one panel design's share of a sweep
 //   MtList:      what an effect list says, checked on the host (mt_check_effects, worded with the caller's name)
 //   MtFit:       a fit's masks, device arrays and effects, and one member function per step the entries repeat; the entries keep their loops
@@ -53,6 +54,33 @@ extern "C" int bwgr_debug_pegs_plan(int64_t n, int64_t q, int k, int64_t out[BWG
     return fail(BWGR_EINVAL, "pegs plan: n = %lld, q = %lld (each at least 1), k = %d (1 <= k <= %d)", (long long)n, (long long)q, k, BWGR_MRR_MAXK);
   const PegsDensePlan pl = pegs_dense_plan(n, q, k);
   out[0] = pl.threads; out[1] = (int64_t)pl.lds_bytes; out[2] = (int64_t)pl.ws_bytes;
+  return BWGR_OK;
+}
+
+// The sparse legs' plan, decided here and nowhere else (bwgr_debug_pegs_sparse_plan exposes it to the CPU tests): the set-up kernel and the
+// disjoint leg run one column per wave, four per workgroup and trip; the serial leg is one wave; the disjoint leg is taken exactly where the
+// host found no row in two columns and the caller did not force the serial leg.
+struct PegsSparsePlan { int setup_threads, serial_threads, disjoint_threads, disjoint; int64_t setup_wg, serial_wg, disjoint_wg, trip_cols; size_t ws_bytes; };
+static PegsSparsePlan pegs_sparse_plan(int64_t n, int64_t q, int64_t nnz, int k, bool disjoint) {
+  PegsSparsePlan pl;
+  pl.setup_threads = TAIL_THREADS; pl.setup_wg = std::min<int64_t>((q + 3) / 4, MRR_SETUP_WG);
+  pl.serial_threads = 64; pl.serial_wg = 1;
+  pl.disjoint_threads = 256; pl.disjoint_wg = std::min<int64_t>((q + 3) / 4, PEGS_SPARSE_WG);
+  pl.trip_cols = pl.disjoint_wg * 4;
+  pl.disjoint = disjoint ? 1 : 0;
+  const size_t nq = (size_t)q, qk = nq * (size_t)k, nz = (size_t)nnz;
+  pl.ws_bytes = 2 * nz * (sizeof(double) + sizeof(int32_t)) + sizeof(int64_t) * (nq + 1 + (size_t)n + 1)       // CSC and CSR
+                + sizeof(double) * (5 * qk + qk * (size_t)k + MRR_KMAX) + sizeof(int32_t) * nq;                   // XX, XSX, tilde, b, d2; Linv; db2; order
+  return pl;
+}
+extern "C" int bwgr_debug_pegs_sparse_plan(int64_t n, int64_t q, int64_t nnz, int64_t max_col_nnz, int k, int disjoint, int64_t out[BWGR_PEGS_SPARSE_PLAN_NOUT]) {
+  if (!out) return fail(BWGR_EINVAL, "pegs sparse plan: null pointer");
+  if (n < 1 || q < 1 || nnz < 0 || nnz > CSC_MAX_NNZ || max_col_nnz < 0 || max_col_nnz > nnz || max_col_nnz > n || k < 1 || k > BWGR_MRR_MAXK)
+    return fail(BWGR_EINVAL, "pegs sparse plan: n = %lld, q = %lld (each at least 1), nnz = %lld (0 .. 2^31 - 1), max_col_nnz = %lld (0 .. min(nnz, n)), k = %d (1 <= k <= %d)",
+                (long long)n, (long long)q, (long long)nnz, (long long)max_col_nnz, k, BWGR_MRR_MAXK);
+  const PegsSparsePlan pl = pegs_sparse_plan(n, q, nnz, k, disjoint != 0);
+  out[0] = pl.setup_threads; out[1] = pl.setup_wg; out[2] = pl.serial_threads; out[3] = pl.serial_wg; out[4] = pl.disjoint_threads; out[5] = pl.disjoint_wg;
+  out[6] = pl.trip_cols; out[7] = pl.disjoint; out[8] = (int64_t)pl.ws_bytes;
   return BWGR_OK;
 }
 
@@ -118,20 +146,31 @@ struct PegsDense {
   int32_t *ordd = nullptr;
 };
 
+// a sparse effect on the device: the matrix column-compressed (the legs) and row-major (the fitted values)
+struct PegsSparse {
+  int64_t q = 0, nnz = 0;
+  bool disjoint = false;                   // the leg a sweep takes (the plan's verdict)
+  int64_t *colptr = nullptr, *rowptr = nullptr;
+  int32_t *rowidx = nullptr, *colidx = nullptr, *ordd = nullptr;
+  double *val = nullptr, *rval = nullptr, *XXd = nullptr, *XSXd = nullptr, *tilde = nullptr, *bd = nullptr, *Linv = nullptr, *db2 = nullptr, *d2 = nullptr;
+};
+
 // ------------------------------------------------------------------------------------------------
 // What an effect list says, checked on the host.  It is a thing of its own, and not part of MtFit, because a call reads its traits in between:
 // they need the list's ld, and are copied from asynchronously, so they are declared before the MtFit (see there).
 struct MtList {
-  const bwgr_pegs_effect *eff = nullptr;
+  const bwgr_pegs_effect_ex *eff = nullptr;
   int neff = 0;
   int64_t n = 0, ld = 0;
   const bwgr_panel *P0 = nullptr;          // the first panel effect: its device, its row padding and its stream are the fit's
   hipStream_t st = nullptr;
   std::vector<std::vector<double>> Zc;     // per dense effect, Z without its padding rows (MtFit takes them over)
+  std::vector<CsrCopy> csr;                // per sparse effect, its row-major copy (MtFit takes them over)
+  std::vector<char> disjoint;              // per sparse effect, whether no row occurs in two columns
 };
 // The refusals every effect list meets, worded with the caller's name (`coef`: what it calls an effect's coefficients); none needs a device.
 // Then the device: the first panel's, or `device` where every effect is dense.
-static int mt_check_effects(const char *who, const char *coef, const bwgr_pegs_effect *eff, int neff, int64_t n, int device, double *const *outs, MtList &E) {
+static int mt_check_effects(const char *who, const char *coef, const bwgr_pegs_effect_ex *eff, int neff, int64_t n, int device, double *const *outs, MtList &E) {
   E.eff = eff; E.neff = neff; E.n = n;
   for (int e = 0; e < neff; ++e) {
     if (!outs[e]) return fail(BWGR_EINVAL, "%s: null pointer (%s of effect %d)", who, coef, e);
@@ -145,16 +184,28 @@ static int mt_check_effects(const char *who, const char *coef, const bwgr_pegs_e
       if (P->data->plan.ld != E.P0->data->plan.ld)
         return fail(BWGR_EINVAL, "%s: effect %d's panel pads its rows to ld = %lld, the first panel to %lld (make the panels with the same block / nwg)", who, e,
                     (long long)P->data->plan.ld, (long long)E.P0->data->plan.ld);
+    } else if (eff[e].colptr) {
+      if (eff[e].Z) return fail(BWGR_EINVAL, "%s: effect %d has both Z and colptr (a dense and a sparse effect at once)", who, e);
+      if (!eff[e].rowidx || !eff[e].val) return fail(BWGR_EINVAL, "%s: null pointer (rowidx or val of sparse effect %d)", who, e);
+      if (eff[e].q < 1 || eff[e].q > 0x7FFFFF00ll)
+        return fail(BWGR_EINVAL, "%s: sparse effect %d: q = %lld columns (at least 1, at most 2147483392)", who, e, (long long)eff[e].q);
+      CscFault bad;
+      if (!csc_validate(n, eff[e].q, eff[e].colptr, eff[e].rowidx, eff[e].val, bad))
+        return fail(BWGR_EINVAL, "%s: sparse effect %d: %s (column %lld, entry %lld; n = %lld rows, q = %lld columns)", who, e, csc_why(bad.what), (long long)bad.col,
+                    (long long)bad.entry, (long long)n, (long long)eff[e].q);
     } else {
-      if (!eff[e].Z) return fail(BWGR_EINVAL, "%s: effect %d has neither a panel nor Z", who, e);
+      if (!eff[e].Z) return fail(BWGR_EINVAL, "%s: effect %d has neither a panel nor Z nor colptr", who, e);
       if (eff[e].q < 1 || eff[e].q > 0x7FFFFF00ll || eff[e].ldz < n)
         return fail(BWGR_EINVAL, "%s: effect %d: q = %lld columns of Z, ldz = %lld (q at least 1, ldz at least n = %lld)", who, e, (long long)eff[e].q,
                     (long long)eff[e].ldz, (long long)n);
     }
   }
-  E.Zc.resize((size_t)neff);
+  E.Zc.resize((size_t)neff); E.csr.resize((size_t)neff); E.disjoint.assign((size_t)neff, 0);
   for (int e = 0; e < neff; ++e)
-    if (!eff[e].panel) {
+    if (!eff[e].panel && eff[e].colptr) {
+      E.disjoint[(size_t)e] = csc_row_disjoint(n, eff[e].q, eff[e].colptr, eff[e].rowidx) ? 1 : 0;
+      csc_to_csr(n, eff[e].q, eff[e].colptr, eff[e].rowidx, eff[e].val, E.csr[(size_t)e]);
+    } else if (!eff[e].panel) {
       int64_t r = 0, j = 0;
       if (!compact_z(eff[e].Z, n, eff[e].q, eff[e].ldz, E.Zc[(size_t)e], &r, &j))
         return fail(BWGR_EINVAL, "%s: effect %d: Z[%lld, %lld] is not finite", who, e, (long long)r, (long long)j);
@@ -165,27 +216,29 @@ static int mt_check_effects(const char *who, const char *coef, const bwgr_pegs_e
   return BWGR_OK;
 }
 
-// one effect of a fit: a panel's leg or a dense effect, and what the entries read of either
+// one effect of a fit: a panel's leg, a sparse or a dense effect, and what the entries read of any
 struct MtEffect {
-  bool panel = false;
+  bool panel = false, sparse = false;
   int64_t m = 0;                           // its columns
-  MrrLeg leg; PegsDense dense;
-  double *b() const { return panel ? leg.bd : dense.bd; }
-  double *tilde() const { return panel ? leg.tilde : dense.tilde; }
-  double *XX() const { return panel ? leg.XXd : dense.XXd; }
-  double *XSX() const { return panel ? leg.XSXd : dense.XSXd; }
-  double *db2() const { return panel ? leg.db2 : dense.db2; }
+  MrrLeg leg; PegsDense dense; PegsSparse sp;
+  double *b() const { return panel ? leg.bd : sparse ? sp.bd : dense.bd; }
+  double *tilde() const { return panel ? leg.tilde : sparse ? sp.tilde : dense.tilde; }
+  double *XX() const { return panel ? leg.XXd : sparse ? sp.XXd : dense.XXd; }
+  double *XSX() const { return panel ? leg.XSXd : sparse ? sp.XSXd : dense.XSXd; }
+  double *db2() const { return panel ? leg.db2 : sparse ? sp.db2 : dense.db2; }
 };
 
 // A multi-trait fit on the device: k traits over the rows of an effect list, all effects against one residual.  An entry makes one after its
 // checks and its traits, then masks() -> alloc() (and its own gets; it asks bufs.failed() once) -> upload(), and calls the steps from its own
 // loops.  Every step enqueues on st what the entries enqueued there before, in the same order; the ones that return results end in d2h's wait.
 struct MtFit {
-  // Host data.  What an asynchronous copy reads -- Zc, order, the mask words, d, off -- stands BEFORE bufs: members go away in reverse order, so
+  // Host data.  What an asynchronous copy reads -- Zc, csr, order, the mask words, d, off -- stands BEFORE bufs: members go away in reverse order, so
   // the holder's wait for the stream comes first (devbufs.h; tests/devbufs_check.cpp shows the semantics).  The same holds for what a caller
   // hands to upload() and sweep_effect(): its traits and its iG are declared before its MtFit.
   const int64_t n, ld; const int k; const hipStream_t st;
   std::vector<std::vector<double>> Zc;
+  std::vector<CsrCopy> csr;
+  const bwgr_pegs_effect_ex *src;          // the caller's effects: a sparse effect's CSC arrays are copied from where they are
   std::vector<CumulativeOrder> order;      // per effect, the column order of sweep s
   std::vector<uint32_t> zt, zb;            // bit t: row observed for trait t; bit g: row observed in pattern g
   std::vector<uint8_t> zm;
@@ -202,9 +255,15 @@ struct MtFit {
   std::vector<MtEffect> eff;
   MrrSweepShared W;
 
-  MtFit(MtList &E, int k_) : n(E.n), ld(E.ld), k(k_), st(E.st), Zc(std::move(E.Zc)), d((size_t)k_), off((size_t)k_, 0.0), bufs(E.st), eff((size_t)E.neff) {
+  MtFit(MtList &E, int k_) : n(E.n), ld(E.ld), k(k_), st(E.st), Zc(std::move(E.Zc)), csr(std::move(E.csr)), src(E.eff), d((size_t)k_), off((size_t)k_, 0.0), bufs(E.st),
+                              eff((size_t)E.neff) {
     for (int e = 0; e < E.neff; ++e) {
       eff[(size_t)e].panel = E.eff[e].panel != nullptr;
+      eff[(size_t)e].sparse = !E.eff[e].panel && E.eff[e].colptr != nullptr;
+      if (eff[(size_t)e].sparse) {
+        eff[(size_t)e].sp.nnz = E.eff[e].colptr[E.eff[e].q];
+        eff[(size_t)e].sp.disjoint = pegs_sparse_plan(E.n, E.eff[e].q, eff[(size_t)e].sp.nnz, k_, E.disjoint[(size_t)e] && !(E.eff[e].flags & BWGR_PEGS_SERIAL)).disjoint != 0;
+      }
       eff[(size_t)e].leg.P = E.eff[e].panel;
       eff[(size_t)e].m = E.eff[e].panel ? E.eff[e].panel->data->p : E.eff[e].q;
       order.emplace_back((size_t)eff[(size_t)e].m);
@@ -237,6 +296,14 @@ struct MtFit {
         mrr_leg_alloc(bufs, E.leg, E.leg.P, npat, k);
         nch_max = std::max(nch_max, (int)std::min<int64_t>(64, E.m));
         panels = true;
+      } else if (E.sparse) {
+        PegsSparse &S = E.sp;
+        S.q = E.m;
+        const size_t nq = (size_t)S.q, qk = nq * k, nz = std::max<size_t>((size_t)S.nnz, 1);
+        S.colptr = bufs.get<int64_t>(nq + 1); S.rowidx = bufs.get<int32_t>(nz); S.val = bufs.get<double>(nz);
+        S.rowptr = bufs.get<int64_t>(nn + 1); S.colidx = bufs.get<int32_t>(nz); S.rval = bufs.get<double>(nz);
+        S.XXd = bufs.get<double>(qk); S.XSXd = bufs.get<double>(qk); S.tilde = bufs.get<double>(qk); S.bd = bufs.get<double>(qk); S.d2 = bufs.get<double>(qk);
+        S.Linv = bufs.get<double>(qk * k); S.db2 = bufs.get<double>(MRR_KMAX); S.ordd = bufs.get<int32_t>(nq);
       } else {
         PegsDense &D = E.dense;
         D.q = E.m;
@@ -265,14 +332,25 @@ struct MtFit {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
     return BWGR_OK;
   }
-  // a dense effect's Z; b = 0
+  // a dense effect's Z, a sparse effect's two copies; b = 0
   int stage_effect(int e) {
     const MtEffect &E = eff[(size_t)e];
-    if (!E.panel) HIPCHK(h2d(st, E.dense.Zd, Zc[(size_t)e].data(), Zc[(size_t)e].size()));
+    if (E.sparse) {
+      const PegsSparse &S = E.sp;
+      const CsrCopy &R = csr[(size_t)e];
+      HIPCHK(h2d(st, S.colptr, src[e].colptr, (size_t)S.q + 1));
+      HIPCHK(h2d(st, S.rowptr, R.rowptr.data(), (size_t)n + 1));
+      if (S.nnz > 0) {
+        HIPCHK(h2d(st, S.rowidx, src[e].rowidx, (size_t)S.nnz));
+        HIPCHK(h2d(st, S.val, src[e].val, (size_t)S.nnz));
+        HIPCHK(h2d(st, S.colidx, R.col.data(), (size_t)S.nnz));
+        HIPCHK(h2d(st, S.rval, R.val.data(), (size_t)S.nnz));
+      }
+    } else if (!E.panel) HIPCHK(h2d(st, E.dense.Zd, Zc[(size_t)e].data(), Zc[(size_t)e].size()));
     HIPCHK(zero(st, E.b(), (size_t)E.m * k));
     return BWGR_OK;
   }
-  // XX, XSX and tilde of the effect's columns, one launch: a panel's centred where `centre` (then xbar too), a dense effect's as they are
+  // XX, XSX and tilde of the effect's columns, one launch: a panel's centred where `centre` (then xbar too), a dense or sparse effect's as they are
   int setup_effect(int e, int centre) {
     const MtEffect &E = eff[(size_t)e];
     if (E.panel) {
@@ -280,6 +358,11 @@ struct MtFit {
       const PanelData *D = L.P->data;
       hipLaunchKernelGGL(k_mrr_setup_cols, dim3((unsigned)mrr_setup_grid(L.p)), dim3(TAIL_THREADS), 0, st, (const int8_t *)D->X, D->plan.R, (int)n, L.p, ld,
                          (const uint32_t *)zbd, (const double *)yd, (const double *)sumyd, mc, centre, L.xbar, L.Sd, L.XXd, L.XSXd, L.tilde);
+    } else if (E.sparse) {
+      const PegsSparse &S = E.sp;
+      const PegsSparsePlan sp = pegs_sparse_plan(n, S.q, S.nnz, k, S.disjoint);
+      hipLaunchKernelGGL(k_pegs_sparse_setup, dim3((unsigned)sp.setup_wg), dim3(sp.setup_threads), 0, st, (const int64_t *)S.colptr, (const int32_t *)S.rowidx,
+                         (const double *)S.val, S.q, ld, (const uint32_t *)ztd, (const double *)yd, mc, S.XXd, S.XSXd, S.tilde);
     } else {
       const PegsDense &D = E.dense;
       hipLaunchKernelGGL(k_pegs_dense_setup, dim3((unsigned)pegs_dense_setup_grid(D.q)), dim3(TAIL_THREADS), 0, st, (const double *)D.Zd, n, D.q, ld,
@@ -297,10 +380,28 @@ struct MtFit {
     HIPCHK(d2h(st, out, small, sizeof(double) * nout));
     return BWGR_OK;
   }
-  // effect e's share of sweep `numit`, against mc.iVe and iG (host, k x k): mrr_sweep, or k_mrr_linv -> k_pegs_dense_leg
+  // effect e's share of sweep `numit`, against mc.iVe and iG (host, k x k): mrr_sweep, or k_mrr_linv -> k_pegs_dense_leg, or k_mrr_linv ->
+  // k_pegs_sparse_leg / k_pegs_sparse_leg_disjoint -> db2 from the per-column (delta b)^2 in column-index order
   int sweep_effect(int e, int numit, const double *iG) {
     const std::vector<int> &ord = order[(size_t)e].next(numit);
     if (eff[(size_t)e].panel) return mrr_sweep(st, eff[(size_t)e].leg, W, mc, plan, ord, iG);
+    if (eff[(size_t)e].sparse) {
+      const PegsSparse &S = eff[(size_t)e].sp;
+      const PegsSparsePlan sp = pegs_sparse_plan(n, S.q, S.nnz, k, S.disjoint);
+      HIPCHK(h2d(st, S.ordd, ord.data(), (size_t)S.q));
+      HIPCHK(h2d(st, iGd, iG, (size_t)k * k));
+      hipLaunchKernelGGL(k_mrr_linv, dim3((unsigned)((S.q + 63) / 64)), dim3(64), plan.lds_linv, st, (const double *)S.XXd, (const double *)iGd, mc, S.q, S.Linv);
+      PegsSparseArgs A;
+      A.colptr = S.colptr; A.rowidx = S.rowidx; A.val = S.val; A.ld = ld; A.q = S.q; A.zt = ztd; A.e = ed; A.order = S.ordd; A.XX = S.XXd; A.Linv = S.Linv;
+      A.b = S.bd; A.d2 = S.d2;
+      if (sp.disjoint) hipLaunchKernelGGL(k_pegs_sparse_leg_disjoint, dim3((unsigned)sp.disjoint_wg), dim3(sp.disjoint_threads), 0, st, A, mc);
+      else hipLaunchKernelGGL(k_pegs_sparse_leg, dim3((unsigned)sp.serial_wg), dim3(sp.serial_threads), 0, st, A, mc);
+      hipLaunchKernelGGL(k_mrr_tilde, dim3(MRR_NP, k), dim3(256), 0, st, (const double *)S.bd, (const double *)S.tilde, (const double *)S.d2, S.q, 2, mc,
+                         (const double *)nullptr, tpart);
+      hipLaunchKernelGGL(k_mrr_finish, dim3(1), dim3(256), 0, st, (const double *)tpart, MRR_NP, k, S.db2);
+      HIPCHK(hipGetLastError());
+      return BWGR_OK;
+    }
     const PegsDense &D = eff[(size_t)e].dense;
     HIPCHK(h2d(st, D.ordd, ord.data(), (size_t)D.q));
     HIPCHK(h2d(st, iGd, iG, (size_t)k * k));
@@ -357,6 +458,9 @@ struct MtFit {
     if (E.panel) {
       CHK(panel_hat(e, htmp));
       hipLaunchKernelGGL(k_pegs_add, dim3((unsigned)std::min<int64_t>((n * k + 255) / 256, 4096)), dim3(256), 0, st, hatd, (const double *)htmp, (int64_t)n * k);
+    } else if (E.sparse) {
+      hipLaunchKernelGGL(k_pegs_sparse_hat, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int64_t *)E.sp.rowptr, (const int32_t *)E.sp.colidx,
+                         (const double *)E.sp.rval, n, k, (const double *)E.sp.bd, hatd);
     } else {
       hipLaunchKernelGGL(k_pegs_zb, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double *)E.dense.Zd, n, E.m, k, (const double *)E.dense.bd, hatd);
     }

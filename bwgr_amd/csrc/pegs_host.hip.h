@@ -1,20 +1,26 @@
-// bwgr_amd/csrc/pegs_host.hip.h -- the host entry of PEGS / PEGSZ (src/RcppEigenX20251203.cpp:10-194, :576-808).  Part of
+// bwgr_amd/csrc/pegs_host.hip.h -- the host entry of PEGS / PEGSZ (src/RcppEigenX20251203.cpp:10-194, :576-808) and of
+// PEGS_sparse / PEGSZ_sparse (:811-1007, :1010-1250; section 4.12), which are the same fit on sparse effects under `text` 1 and 2.  Part of
 // bwgr_hip.hip, after fits_host.hip.h.  It holds the fit's own algebra: the option checks, the start values and the per-sweep tail (pegs_tail.h),
 // the mu shift and the outputs; the effect checks, the device arrays and every repeated step are MtFit's (mtfit_host.hip.h).  It defines no kernel.
-//   once:       per panel effect k_mrr_setup_cols (uncentred), per dense effect k_pegs_dense_setup; k_mrr_tilde(mode 2) -> MSx
-//   per sweep:  per effect in list order: mrr_sweep (panel) or k_mrr_linv -> k_pegs_dense_leg (dense), all against one residual;
+//   once:       per panel effect k_mrr_setup_cols (uncentred), per dense effect k_pegs_dense_setup, per sparse effect k_pegs_sparse_setup;
+//               k_mrr_tilde(mode 2) -> MSx
+//   per sweep:  per effect in list order: mrr_sweep (panel), k_mrr_linv -> k_pegs_dense_leg (dense) or k_mrr_linv -> k_pegs_sparse_leg /
+//               k_pegs_sparse_leg_disjoint (sparse), all against one residual;
 //               k_mrr_ey -> (host: ve) -> k_mrr_tilde(mode 0) per effect -> (host, pegs_tail.h: vb, XFA, NNC, bending, pinv, mu, cnv) ->
 //               k_mrr_mu_shift
-//   at the end: hat = sum over the effects, in list order, of X b (k_mrr_hat_part / k_mrr_hat_finish) or Z b (k_pegs_zb), plus mu
+//   at the end: hat = sum over the effects, in list order, of X b (k_mrr_hat_part / k_mrr_hat_finish), Z b (k_pegs_zb) or S b (k_pegs_sparse_hat),
+//               plus mu
 // ------------------------------------------------------------------------------------------------
-extern "C" int bwgr_pegs(int device, const bwgr_pegs_effect *eff, int neff, const double *Y, int64_t n, int k, int maxit, double logtol, double covbend,
-                         double covMinEv, int XFA, int NNC, int own_text, double *mu_out, double *const *b_out, double *hat_out, double *h2_out,
-                         double *const *GC_out, double *bend_out, int *numit_out, double *cnv_out) {
+// text: 0 PEGSZ's, 1 PEGS's own (PEGS_sparse is text 1 on a sparse effect), 2 PEGSZ_sparse's (include/bwgr.h lists what the sparse texts change)
+extern "C" int bwgr_pegs_ex(int device, const bwgr_pegs_effect_ex *eff, int neff, const double *Y, int64_t n, int k, int maxit, double logtol, double covbend,
+                            double covMinEv, int XFA, int NNC, int text, double *mu_out, double *const *b_out, double *hat_out, double *h2_out,
+                            double *const *GC_out, double *bend_out, int *numit_out, double *cnv_out) {
   if (!eff || !Y || !b_out || !numit_out) return fail(BWGR_EINVAL, "pegs: null pointer");
   if (neff < 1) return fail(BWGR_EINVAL, "pegs: %d effects (at least 1)", neff);
   if (k < 1 || k > BWGR_MRR_MAXK) return fail(BWGR_EINVAL, "pegs: k = %d traits; this engine takes 1 <= k <= %d", k, BWGR_MRR_MAXK);
   if (n < 1) return fail(BWGR_EINVAL, "pegs: n = %lld rows (at least 1)", (long long)n);
-  const PegsOpts o = {maxit, logtol, covbend, covMinEv, XFA, NNC != 0, own_text != 0};
+  if (text < 0 || text > 2) return fail(BWGR_EINVAL, "pegs: text = %d (0: PEGSZ's, 1: PEGS's own, 2: PEGSZ_sparse's)", text);
+  const PegsOpts o = {maxit, logtol, covbend, covMinEv, XFA, NNC != 0, text == 1, text == 2};
   if (const char *why = pegs_refuses(k, o))
     return fail(BWGR_EINVAL, "pegs: %s (maxit = %d, logtol = %g, covbend = %g, covMinEv = %g, XFA = %d, k = %d)", why, maxit, logtol, covbend, covMinEv, XFA, k);
   MtList E;                                      // (before the traits, which need its ld, and the fit, whose holder waits for the stream)
@@ -84,4 +90,18 @@ extern "C" int bwgr_pegs(int device, const bwgr_pegs_effect *eff, int neff, cons
       for (int i = 0; i < k; ++i) for (int j = 0; j < k; ++j) GC_out[e][j * k + i] = GC[(size_t)e * k * k + i * k + j];   // column-major (symmetric)
   }
   return BWGR_OK;
+}
+
+// the narrow effects as wide ones (at least one entry, so that an empty list is refused for its length and not for a null pointer)
+static std::vector<bwgr_pegs_effect_ex> mt_widen(const bwgr_pegs_effect *eff, int neff) {
+  std::vector<bwgr_pegs_effect_ex> w((size_t)std::max(neff, 1), bwgr_pegs_effect_ex{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, 0});
+  for (int e = 0; eff && e < neff; ++e) { w[(size_t)e].panel = eff[e].panel; w[(size_t)e].Z = eff[e].Z; w[(size_t)e].q = eff[e].q; w[(size_t)e].ldz = eff[e].ldz; }
+  return w;
+}
+extern "C" int bwgr_pegs(int device, const bwgr_pegs_effect *eff, int neff, const double *Y, int64_t n, int k, int maxit, double logtol, double covbend,
+                         double covMinEv, int XFA, int NNC, int own_text, double *mu_out, double *const *b_out, double *hat_out, double *h2_out,
+                         double *const *GC_out, double *bend_out, int *numit_out, double *cnv_out) {
+  const std::vector<bwgr_pegs_effect_ex> w = mt_widen(eff, neff);
+  return bwgr_pegs_ex(device, eff ? w.data() : nullptr, neff, Y, n, k, maxit, logtol, covbend, covMinEv, XFA, NNC, own_text != 0 ? 1 : 0, mu_out, b_out, hat_out, h2_out,
+                      GC_out, bend_out, numit_out, cnv_out);
 }

@@ -59,8 +59,9 @@ inline void mrr_pinv(int k, const double *A, double *out) {
 
 // ---- PEGS / PEGSZ ----
 // own_text: follow PEGS's own text where it differs from PEGSZ's -- the XFA branch whenever XFA > 0 (:139; PEGSZ: 0 < XFA < k, :734) and no
-// guard on a zero TrXSX (:130-131; PEGSZ: :722-724).  XFA < 0 means k (:94, :679).
-struct PegsOpts { int maxit; double logtol, covbend, covMinEv; int XFA; bool NNC, own_text; };
+// guard on a zero TrXSX (:130-131; PEGSZ: :722-724).  XFA < 0 means k (:94, :679).  mu_div_n: the intercept step divides the residual sums
+// by n_t, PEGSZ_sparse's text (iN_mu, :1202), where PEGS, PEGSZ and PEGS_sparse divide by n_t - 1 (:163-164, :760, :977).
+struct PegsOpts { int maxit; double logtol, covbend, covMinEv; int XFA; bool NNC, own_text; bool mu_div_n = false; };
 // what one covariance update did: vb's smallest and largest eigenvalue before bending (MinDVb, :157), whether inflate was added (:159), and
 // where XFA truncated (0 < XFA < k) the gap between the last kept and the first dropped eigenvalue of GC (else -1)
 struct PegsTrace { double MinDVb = 0, maxEv = 0, gap = -1; int inflated = 0; };
@@ -141,7 +142,7 @@ inline void pegs_tail_vb(int k, const PegsOpts &o, const double *TH, PegsEffect 
 
 // Everything after a sweep.  ey[t] = e_t'y_t, ey[k + t] = sum(e_t); TH: every effect's TildeHat (neff x k x k); db2[e] = that effect's
 // sum (delta b)^2.  Updates ve, every effect's vb / iG / inflate, mu, cnv and numit; d[t] is what the caller takes off e_t on its
-// observed rows (:163-166, with 1 / (n_t - 1) as written there).  True when the fit stops (cnv < logtol, :171).
+// observed rows (:163-166, with 1 / (n_t - 1) as written there; 1 / n_t with o.mu_div_n).  True when the fit stops (cnv < logtol, :171).
 inline bool pegs_after_sweep(PegsState &S, const PegsOpts &o, const double *ey, const double *TH, const double *db2, double *d, PegsTrace *tr) {
   const int k = S.k;
   for (int t = 0; t < k; ++t) S.ve[t] = ey[t] / (S.nt[t] - 1.0);                            // :123-124
@@ -150,7 +151,7 @@ inline bool pegs_after_sweep(PegsState &S, const PegsOpts &o, const double *ey, 
     pegs_tail_vb(k, o, TH + e * (size_t)k * k, S.eff[e], tr ? tr + e : nullptr);
     s += db2[e];
   }
-  for (int t = 0; t < k; ++t) { d[t] = ey[k + t] / (S.nt[t] - 1.0); S.mu[t] += d[t]; }
+  for (int t = 0; t < k; ++t) { d[t] = ey[k + t] / (o.mu_div_n ? S.nt[t] : S.nt[t] - 1.0); S.mu[t] += d[t]; }
   S.cnv = log10(s);                                                                        // :169, :766-770
   ++S.numit;
   return S.cnv < o.logtol;

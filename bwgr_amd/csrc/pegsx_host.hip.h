@@ -3,8 +3,9 @@
 // (pegsx_setup.h), TrZSZ, the fixed step, the per-sweep tail (pegs_tail.h), the timing hooks and the outputs; the effect checks, the device arrays
 // and every repeated step are MtFit's (mtfit_host.hip.h).  It defines no kernel.
 //   once:       host (pegsx_setup.h): masks, patterns, per pattern (M'M)^+, b, the projected y.  Per effect k_mrr_setup_cols (uncentred) or
-//               k_pegs_dense_setup -> ZZ, tilde; k_mrr_tilde(mode 2) on ZZ; k_pegsx_trace_panel / _dense -> k_mrr_finish -> TrZSZ
-//   per sweep:  per effect in list order: mrr_sweep (panel) or k_mrr_linv -> k_pegs_dense_leg (dense); k_pegsx_fixed; k_mrr_ey ->
+//               k_pegs_dense_setup or k_pegs_sparse_setup -> ZZ, tilde; k_mrr_tilde(mode 2) on ZZ; k_pegsx_trace_panel / _dense / _sparse ->
+//               k_mrr_finish -> TrZSZ
+//   per sweep:  per effect in list order: mrr_sweep (panel), k_mrr_linv -> k_pegs_dense_leg (dense) or the sparse legs; k_pegsx_fixed; k_mrr_ey ->
 //               k_mrr_tilde(mode 0) per effect -> (host, pegs_tail.h: vb with its prior, NNC, XFA, bending, pinv, ve, cnv)
 //   at the end: hat = X b (k_pegs_zb) plus every effect's share as in bwgr_pegs; there is no mu
 // ------------------------------------------------------------------------------------------------
@@ -56,10 +57,10 @@ struct PegsxStats {
   void put(double *o) const { o[0] = cnt ? sum / cnt : 0.0; o[1] = mn; o[2] = mx; }
 };
 
-extern "C" int bwgr_pegsx(int device, const bwgr_pegs_effect *eff, int neff, const double *X, int64_t ldx, int f, const double *Y, int64_t n, int k, int maxit,
-                          double logtol, double covbend, double covMinEv, double df0, int NNC, int XFA, int NumXFA, int InnerGS, int NoInv, double *Tr_out,
-                          double *bfix_out, double *const *u_out, double *const *vb_out, double *const *GC_out, double *ve_out, double *hat_out, int *numit_out,
-                          double *cnv_out, double *bend_out) {
+extern "C" int bwgr_pegsx_ex(int device, const bwgr_pegs_effect_ex *eff, int neff, const double *X, int64_t ldx, int f, const double *Y, int64_t n, int k, int maxit,
+                             double logtol, double covbend, double covMinEv, double df0, int NNC, int XFA, int NumXFA, int InnerGS, int NoInv, double *Tr_out,
+                             double *bfix_out, double *const *u_out, double *const *vb_out, double *const *GC_out, double *ve_out, double *hat_out, int *numit_out,
+                             double *cnv_out, double *bend_out) {
   static_assert(PEGSX_MAXF == BWGR_PEGSX_MAXF, "the kernels' cap is the header's");
   if (neff < 1) return fail(BWGR_EINVAL, "pegsx: Z_list holds %d effects (at least 1)", neff);
   if (f < 1 || f > BWGR_PEGSX_MAXF) return fail(BWGR_EINVAL, "pegsx: f = %d columns of X; this engine takes 1 <= f <= %d", f, BWGR_PEGSX_MAXF);
@@ -129,6 +130,9 @@ extern "C" int bwgr_pegsx(int device, const bwgr_pegs_effect *eff, int neff, con
       const PanelData *D = Q.leg.P->data;
       hipLaunchKernelGGL(k_pegsx_trace_panel, dim3(tg), dim3(256), xpl.lds_trace, st, (const int8_t *)D->X, D->plan.R, Q.m, ld, (const double *)Xd, n, f,
                          (const uint32_t *)M.zbd, npat, (const double *)iXXd, qpart);
+    } else if (Q.sparse) {
+      hipLaunchKernelGGL(k_pegsx_trace_sparse, dim3(tg), dim3(256), xpl.lds_trace, st, (const int64_t *)Q.sp.colptr, (const int32_t *)Q.sp.rowidx,
+                         (const double *)Q.sp.val, Q.m, (const double *)Xd, n, f, (const uint32_t *)M.zbd, npat, (const double *)iXXd, qpart);
     } else {
       hipLaunchKernelGGL(k_pegsx_trace_dense, dim3(tg), dim3(256), xpl.lds_trace, st, (const double *)Q.dense.Zd, Q.m, ld, (const double *)Xd, n, f,
                          (const uint32_t *)M.zbd, npat, (const double *)iXXd, qpart);
@@ -190,4 +194,12 @@ extern "C" int bwgr_pegsx(int device, const bwgr_pegs_effect *eff, int neff, con
   }
   *numit_out = T.numit;
   return BWGR_OK;
+}
+extern "C" int bwgr_pegsx(int device, const bwgr_pegs_effect *eff, int neff, const double *X, int64_t ldx, int f, const double *Y, int64_t n, int k, int maxit,
+                          double logtol, double covbend, double covMinEv, double df0, int NNC, int XFA, int NumXFA, int InnerGS, int NoInv, double *Tr_out,
+                          double *bfix_out, double *const *u_out, double *const *vb_out, double *const *GC_out, double *ve_out, double *hat_out, int *numit_out,
+                          double *cnv_out, double *bend_out) {
+  const std::vector<bwgr_pegs_effect_ex> w = mt_widen(eff, neff);
+  return bwgr_pegsx_ex(device, eff ? w.data() : nullptr, neff, X, ldx, f, Y, n, k, maxit, logtol, covbend, covMinEv, df0, NNC, XFA, NumXFA, InnerGS, NoInv, Tr_out,
+                       bfix_out, u_out, vb_out, GC_out, ve_out, hat_out, numit_out, cnv_out, bend_out);
 }

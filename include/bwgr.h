@@ -394,11 +394,55 @@ int bwgr_uvbeta2(bwgr_panel *P, const double *Z, int64_t q, int64_t ldz, const d
  * reference would index out of range), maxit < 0, covbend / covMinEv not finite or logtol NaN / +inf, a trait with fewer than 2 records,
  * an fp32 panel, effects with different n or ld, panels on different devices, q < 1 or q > 2147483392, ldz < n, a non-finite entry of Z, an
  * effect whose TrXSX is 0 for a trait (the start value ve / MSx is infinite there).
- * Not here: PEGS_sparse, PEGSZ_sparse, k > 16 (PEGSX is bwgr_pegsx below). */
+ * Not here: k > 16 (PEGSX is bwgr_pegsx below; sparse effects, PEGS_sparse and PEGSZ_sparse are bwgr_pegs_ex below). */
 typedef struct bwgr_pegs_effect { bwgr_panel *panel; const double *Z; int64_t q, ldz; } bwgr_pegs_effect;
 int bwgr_pegs(int device, const bwgr_pegs_effect *eff, int neff, const double *Y, int64_t n, int k, int maxit, double logtol, double covbend,
               double covMinEv, int XFA, int NNC, int own_text, double *mu, double *const *b, double *hat, double *h2, double *const *GC,
               double *bend, int *numit, double *cnv);
+/* ---- sparse effects; PEGS_sparse / PEGSZ_sparse -------------------------------------------------------------
+ * bwgr_pegs_ex is bwgr_pegs with a wider effect struct and `text` in place of own_text; bwgr_pegsx_ex (below) is bwgr_pegsx with the wider
+ * effects.  bwgr_pegs and bwgr_pegsx forward to them (text = own_text != 0).  An effect is, in this order,
+ *   a panel effect   (panel != NULL), as above;
+ *   a sparse effect  (colptr != NULL): n x q column-compressed (CSC), host: colptr int64[q + 1], rowidx int32[nnz], val double[nnz], nnz =
+ *                    colptr[q] -- the incidence matrix of environments, locations, blocks or genotype-by-environment cells.  On the device
+ *                    it takes nnz + q k^2 values, never n q.  Where no row occurs in two columns (the columns of one factor; tested on the
+ *                    host, O(nnz)) Gauss-Seidel over its columns does not depend on their order, and a grid of waves updates all columns at
+ *                    once (k_pegs_sparse_leg_disjoint); any other sparse effect, or one with bit 0 of `flags` set (BWGR_PEGS_SERIAL, for
+ *                    tests and the probe), is walked by one wave in the sweep's order (k_pegs_sparse_leg).  Both legs run one per-column
+ *                    routine, so on a row-disjoint effect they give the same bits.  Empty columns (b stays 0) and stored zeros are allowed;
+ *   a dense effect   (else), Z as above.
+ * Any mix of kinds is allowed in one list, e.g. [panel, sparse, sparse, dense].
+ * text: 0 PEGSZ's text; 1 PEGS's own text (own_text above) -- PEGS_sparse (:811-1007) is text 1 on one sparse effect; 2 PEGSZ_sparse's text
+ * (:1010-1250).  What the sparse functions' texts change against PEGS / PEGSZ, line by line:
+ *   - PEGSZ_sparse's intercept step divides the residual sums by n_t (iN_mu, :1202), PEGSZ's by n_t - 1 (iN_var, :760).  This is all text 2
+ *     changes here.  PEGS_sparse keeps PEGS's 1 / (n_t - 1) (:865, :977).
+ *   - PEGSZ_sparse takes vy and ve with 1 / (max(n_t, 1) - 1) (:1076), PEGSZ with 1 / (n_t - 1) (:639): they differ only for n_t < 1, and a
+ *     trait with fewer than 2 records is refused here under every text.
+ *   - the designs arrive as double sparse matrices and are cast to float once (:821, :1028): the caller rounds val, as it rounds Y.
+ *   - XX, XSX, tilde, the dots and the residual update run over the stored entries (:846-860, :875, :924, :933-936, and the same in
+ *     :1057-1092, :1138-1148): the same numbers as on the dense copy, summed over fewer terms.
+ *   - PEGS_sparse keeps PEGS's XFA branch for every XFA > 0 and its unguarded division by TrXSX (:955, :947); PEGSZ_sparse keeps PEGSZ's
+ *     0 < XFA < k and its guards (:1176, :1164-1166).  The bending, the stop rule, h2, GC and the outputs are the same text.
+ * BWGR_EINVAL, the panels stay usable: what bwgr_pegs refuses; text outside 0..2; a sparse effect with Z set as well, with a null rowidx
+ * or val, q < 1 or q > 2147483392, colptr[0] != 0, a decreasing colptr, colptr[q] > 2^31 - 1, a row index outside [0, n) or not strictly
+ * increasing within its column (unsorted or duplicated), a non-finite value -- the message names the effect, the column and the entry. */
+#define BWGR_PEGS_SERIAL 1
+typedef struct bwgr_pegs_effect_ex {
+  bwgr_panel *panel; const double *Z; int64_t q, ldz;
+  const int64_t *colptr; const int32_t *rowidx; const double *val; int64_t flags;
+} bwgr_pegs_effect_ex;
+int bwgr_pegs_ex(int device, const bwgr_pegs_effect_ex *eff, int neff, const double *Y, int64_t n, int k, int maxit, double logtol, double covbend,
+                 double covMinEv, int XFA, int NNC, int text, double *mu, double *const *b, double *hat, double *h2, double *const *GC,
+                 double *bend, int *numit, double *cnv);
+/* host arithmetic of the sparse legs (needs no GPU) for a sparse effect of n rows, q columns, nnz stored entries of which at most
+ * max_col_nnz in one column, k traits, row-disjoint or not (n, q >= 1, 0 <= max_col_nnz <= nnz <= 2^31 - 1, 1 <= k <= 16, else BWGR_EINVAL):
+ * out[0..1] the threads per workgroup and the workgroups of k_pegs_sparse_setup (one column per wave, at most 8192 workgroups); out[2..3] the
+ * same of the serial leg (one wave); out[4..5] the same of the disjoint leg (one column per wave, at most 1024 workgroups); out[6] the columns
+ * one trip of the disjoint grid covers; out[7] the leg a sweep takes (0 serial, 1 disjoint: exactly when `disjoint` is not 0); out[8] the
+ * bytes of the effect's device workspace: both copies of the matrix, XX, XSX, tilde, b, (delta b)^2, the q k x k inverses, the order, the sums --
+ * proportional to nnz + q k^2 (and n + q for the pointers), never to n q. */
+#define BWGR_PEGS_SPARSE_PLAN_NOUT 9
+int bwgr_debug_pegs_sparse_plan(int64_t n, int64_t q, int64_t nnz, int64_t max_col_nnz, int k, int disjoint, int64_t out[BWGR_PEGS_SPARSE_PLAN_NOUT]);
 /* host arithmetic of bwgr_pegs's dense leg (needs no GPU), in the style of the other plan hooks, for a dense effect of n rows and q columns
  * and k traits (n, q >= 1, 1 <= k <= 16, else BWGR_EINVAL): out[0] the threads of the one workgroup of k_pegs_dense_leg (one row per thread
  * up to 1024, whole waves), out[1] its dynamic LDS bytes, out[2] the bytes of the effect's device workspace (Z, XX, XSX, tilde, b, the q
@@ -431,11 +475,16 @@ int bwgr_debug_pegs_plan(int64_t n, int64_t q, int k, int64_t out[BWGR_PEGS_PLAN
  * cnv [max(maxit, 1)]: the value after every sweep run (10 where none ran); bend [neff].
  * BWGR_EINVAL, the panels stay usable: what bwgr_pegs refuses of its effects and of maxit / logtol / covbend / covMinEv, df0 not finite or
  * negative, f < 1 or f > BWGR_PEGSX_MAXF, ldx < n, a non-finite entry of X, a trait with fewer than 2 records, InnerGS, NoInv.
- * Not here: MLM (it projects Z off X, which makes the int8 panel dense), PEGS_sparse and PEGSZ_sparse (the engine has no sparse storage). */
+ * Not here: MLM (it projects Z off X, which makes the int8 panel dense).
+ * bwgr_pegsx_ex is bwgr_pegsx with bwgr_pegs_ex's wider effects: a sparse effect is swept as there, and its share of TrZSZ is taken over the
+ * column's stored entries (k_pegsx_trace_sparse).  bwgr_pegsx forwards to it. */
 #define BWGR_PEGSX_MAXF 256
 int bwgr_pegsx(int device, const bwgr_pegs_effect *eff, int neff, const double *X, int64_t ldx, int f, const double *Y, int64_t n, int k, int maxit,
                double logtol, double covbend, double covMinEv, double df0, int NNC, int XFA, int NumXFA, int InnerGS, int NoInv, double *TrZSZ,
                double *b, double *const *u, double *const *vb, double *const *GC, double *ve, double *hat, int *numit, double *cnv, double *bend);
+int bwgr_pegsx_ex(int device, const bwgr_pegs_effect_ex *eff, int neff, const double *X, int64_t ldx, int f, const double *Y, int64_t n, int k, int maxit,
+                  double logtol, double covbend, double covMinEv, double df0, int NNC, int XFA, int NumXFA, int InnerGS, int NoInv, double *TrZSZ,
+                  double *b, double *const *u, double *const *vb, double *const *GC, double *ve, double *hat, int *numit, double *cnv, double *bend);
 /* host arithmetic of bwgr_pegsx (needs no GPU) for n rows, f columns of X and k traits (n >= 1, 1 <= f <= BWGR_PEGSX_MAXF, 1 <= k <= 16, else
  * BWGR_EINVAL): out[0] the threads of each of the k workgroups of the fixed step (one row per thread up to 1024, whole waves), out[1] its
  * dynamic LDS bytes (two f-vectors), out[2] the bytes of X, the pseudo-inverses of up to k patterns and b on the device; the trace kernels'

@@ -137,24 +137,51 @@ YSEMF <- function(Y, X, npc = -1L) {
 # argument order, defaults and return lists.  An effect is a panel effect -- a panel handle, an integer matrix or an integer-valued numeric
 # matrix within int8 range, staged as int8 genotypes and NOT centred -- or a dense effect: a numeric matrix with a non-integer value, or any
 # matrix passed as dense(Z).  Y and the real options are float-rounded, as the reference receives them.  The marker order of a sweep is the
-# library's own (the reference seeds it from the machine).  PEGS_sparse and PEGSZ_sparse are not here (the engine has no sparse storage).
+# library's own (the reference seeds it from the machine).
+# A third kind is a sparse effect: a sparse matrix of the Matrix package (a dgCMatrix as it is, any other sparseMatrix converted to one) or
+# any matrix passed as sparse(S), whose nonzeros are taken -- the incidence matrix of environments, blocks or genotype-by-environment cells,
+# held column-compressed on the device.  Its @i, @p, @x and @Dim travel to C as plain vectors; the values are float-rounded, as the
+# reference casts them.  PEGS_sparse and PEGSZ_sparse (R/RcppExports.R:292, 296; src/RcppEigenX20251203.cpp:811-1007, :1010-1250) are the
+# same fit under their own texts: text 1 (PEGS's) and text 2 (PEGSZ_sparse's, whose intercept step divides by n where PEGSZ divides by n - 1).
 dense <- function(Z) structure(as.matrix(Z) * 1.0, class = c("bwgr_dense", "matrix"))
+sparse <- function(S) {
+  if (inherits(S, "bwgr_sparse")) return(S)
+  if (inherits(S, "sparseMatrix")) {
+    if (!inherits(S, "dgCMatrix")) S <- methods::as(methods::as(methods::as(S, "dMatrix"), "generalMatrix"), "CsparseMatrix")
+    return(structure(list(i = as.integer(S@i), p = as.integer(S@p), x = .bwgr_f32(as.double(S@x)), Dim = as.integer(S@Dim)), class = "bwgr_sparse"))
+  }
+  S <- as.matrix(S) * 1.0
+  nz <- which(S != 0, arr.ind = TRUE)                      # by column, rows ascending within one
+  structure(list(i = as.integer(nz[, 1] - 1L), p = as.integer(c(0L, cumsum(tabulate(nz[, 2], ncol(S))))), x = .bwgr_f32(as.double(S[nz])),
+                 Dim = as.integer(dim(S))), class = "bwgr_sparse")
+}
 .bwgr_pegs_effect <- function(X) {
   if (inherits(X, "externalptr")) return(X)
   if (inherits(X, "bwgr_dense")) return(unclass(X))
+  if (inherits(X, "bwgr_sparse") || inherits(X, "sparseMatrix")) return(sparse(X))
   X <- as.matrix(X)
   if (is.integer(X) || (!anyNA(X) && all(X == round(X)) && all(abs(X) <= 127))) .bwgr_ipanel(X) else X * 1.0
 }
-.bwgr_pegs <- function(Y, X_list, maxit, logtol, covbend, covMinEv, XFA, NNC, own_text) {
-  eff <- lapply(X_list, .bwgr_pegs_effect)
-  set <- .Call("bwgrhip_pegs_set", length(eff))
+# the effects into a set, one by one; round: dense effects are float-rounded first.  Returns the effects as they were put (the caller keeps them alive).
+.bwgr_pegs_fill <- function(set, eff, round) {
   for (i in seq_along(eff)) {
+    if (inherits(eff[[i]], "bwgr_sparse")) {
+      .Call("bwgrhip_pegs_put_sparse", set, i - 1L, eff[[i]]$i, eff[[i]]$p, eff[[i]]$x, eff[[i]]$Dim)
+      next
+    }
     isz <- is.matrix(eff[[i]])
+    if (isz && round) eff[[i]] <- .bwgr_f32(eff[[i]])
     pan <- if (isz) NULL else eff[[i]]
     Z <- if (isz) eff[[i]] else NULL
     .Call("bwgrhip_pegs_put", set, i - 1L, pan, Z)
   }
-  r <- .Call("bwgrhip_pegs", set, .bwgr_f32(as.matrix(Y)), as.integer(maxit), .bwgr_f32(logtol), .bwgr_f32(covbend), .bwgr_f32(covMinEv), as.integer(XFA), as.logical(NNC), as.integer(own_text))
+  eff
+}
+.bwgr_pegs <- function(Y, X_list, maxit, logtol, covbend, covMinEv, XFA, NNC, text) {
+  eff <- lapply(X_list, .bwgr_pegs_effect)
+  set <- .Call("bwgrhip_pegs_set", length(eff))
+  eff <- .bwgr_pegs_fill(set, eff, FALSE)
+  r <- .Call("bwgrhip_pegs", set, .bwgr_f32(as.matrix(Y)), as.integer(maxit), .bwgr_f32(logtol), .bwgr_f32(covbend), .bwgr_f32(covMinEv), as.integer(XFA), as.logical(NNC), as.integer(text))
   rm(eff)
   r
 }
@@ -165,21 +192,22 @@ PEGS <- function(Y, X, maxit = 100L, logtol = -4.0, covbend = 1.1, covMinEv = 10
 }
 PEGSZ <- function(Y, X_list, maxit = 100L, logtol = -4.0, covbend = 1.1, covMinEv = 10e-4, XFA = -1L, NNC = TRUE)
   .bwgr_pegs(Y, X_list, maxit, logtol, covbend, covMinEv, XFA, NNC, 0L)
+PEGS_sparse <- function(Y, S, maxit = 100L, logtol = -4.0, covbend = 1.1, covMinEv = 10e-4, XFA = -1L, NNC = TRUE) {
+  r <- .bwgr_pegs(Y, list(sparse(S)), maxit, logtol, covbend, covMinEv, XFA, NNC, 1L)
+  r$b <- r$b[[1]]; r$GC <- r$GC[[1]]
+  r
+}
+PEGSZ_sparse <- function(Y, X_list, maxit = 100L, logtol = -4.0, covbend = 1.1, covMinEv = 10e-4, XFA = -1L, NNC = TRUE)
+  .bwgr_pegs(Y, lapply(X_list, function(X) if (inherits(X, "externalptr") || inherits(X, "bwgr_dense")) X else sparse(X)), maxit, logtol, covbend, covMinEv, XFA, NNC, 2L)
 # fixed effects beside the random effects, R/RcppExports.R:284 (PEGSX; src/RcppEigenX20251203.cpp:197-573): same name, argument order, defaults
 # and return list.  X is the fixed design (an intercept is a column of it; nothing is centred); every element of Z_list is an effect as for
-# PEGSZ.  Y, X, the dense effects and the real options are float-rounded.  InnerGS = TRUE and NoInv = TRUE are refused by the library; cores
+# PEGSZ, sparse ones included.  Y, X, the dense effects and the real options are float-rounded.  InnerGS = TRUE and NoInv = TRUE are refused by the library; cores
 # and verbose are accepted and ignored.  MLM is not here: it projects Z off X, which makes the int8 panel dense.
 PEGSX <- function(Y, X, Z_list, maxit = 500L, logtol = -8.0, covbend = 1.1, covMinEv = 10e-4, cores = 1L, verbose = FALSE, df0 = 1.1, NNC = FALSE,
                   InnerGS = FALSE, NoInv = FALSE, XFA = FALSE, NumXFA = 3L) {
   eff <- lapply(Z_list, .bwgr_pegs_effect)
   set <- .Call("bwgrhip_pegs_set", length(eff))
-  for (i in seq_along(eff)) {
-    isz <- is.matrix(eff[[i]])
-    if (isz) eff[[i]] <- .bwgr_f32(eff[[i]])
-    pan <- if (isz) NULL else eff[[i]]
-    Z <- if (isz) eff[[i]] else NULL
-    .Call("bwgrhip_pegs_put", set, i - 1L, pan, Z)
-  }
+  eff <- .bwgr_pegs_fill(set, eff, TRUE)
   opts <- c(as.integer(maxit), .bwgr_f32(logtol), .bwgr_f32(covbend), .bwgr_f32(covMinEv), .bwgr_f32(df0), as.logical(NNC), as.logical(InnerGS),
             as.logical(NoInv), as.logical(XFA), as.integer(NumXFA)) * 1.0
   r <- .Call("bwgrhip_pegsx", set, .bwgr_f32(as.matrix(Y)), .bwgr_f32(as.matrix(X) * 1.0), opts)

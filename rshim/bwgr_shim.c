@@ -395,20 +395,30 @@ SEXP bwgrhip_uvbeta2(SEXP Y, SEXP Z, SEXP panel, SEXP maxit, SEXP tol, SEXP df0)
 
 /* PEGS(Y, X, ...) / PEGSZ(Y, X_list, maxit, logtol, covbend, covMinEv, XFA, NNC) src/RcppEigenX20251203.cpp:10-194, :576-808 ->
  * list(mu, b, hat, h2, GC, bend, numit, cnv); for PEGSZ b and GC are lists with one entry per effect and bend a vector (bwgr_hip.R unwraps
- * them for PEGS).  The effects are put into a set one by one -- a panel (the int8 genotypes, not centred) or a dense numeric n x q matrix --
- * and the set is fitted in one call; bwgr_hip.R keeps the panels and matrices alive meanwhile.  Y: float-rounded by the R front-end, NA = missing. */
+ * them for PEGS).  The effects are put into a set one by one -- a panel (the int8 genotypes, not centred), a dense numeric n x q matrix or a
+ * sparse one (a dgCMatrix's @i, @p, @x and @Dim as plain vectors: no S4 accessor is needed here) -- and the set is fitted in one call;
+ * bwgr_hip.R keeps the panels, matrices and vectors alive meanwhile.  Y: float-rounded by the R front-end, NA = missing.  text: 0 PEGSZ's,
+ * 1 PEGS's own (PEGS_sparse is text 1 on a sparse effect), 2 PEGSZ_sparse's (:811-1007, :1010-1250; include/bwgr.h). */
 #include <stdlib.h>
-typedef struct { int neff; bwgr_pegs_effect *e; int *cols; } pegs_set;
+typedef struct { int neff; bwgr_pegs_effect_ex *e; int *cols, *rows; int64_t **ptr; } pegs_set;   /* ptr[i]: a sparse effect's @p as int64, owned */
+static void pegs_set_free(pegs_set *S) {
+  if (!S) return;
+  if (S->ptr) for (int i = 0; i < S->neff; i++) free(S->ptr[i]);
+  free(S->e); free(S->cols); free(S->rows); free(S->ptr); free(S);
+}
 static void pegs_set_finalizer(SEXP ext) {
   pegs_set *S = (pegs_set *)R_ExternalPtrAddr(ext);
-  if (S) { free(S->e); free(S->cols); free(S); R_ClearExternalPtr(ext); }
+  if (S) { pegs_set_free(S); R_ClearExternalPtr(ext); }
 }
 SEXP bwgrhip_pegs_set(SEXP neff) {
   const int m = Rf_asInteger(neff);
   if (m < 1) Rf_error("X_list holds no effects");
   pegs_set *S = (pegs_set *)calloc(1, sizeof(pegs_set));
-  if (S) { S->neff = m; S->e = (bwgr_pegs_effect *)calloc((size_t)m, sizeof(bwgr_pegs_effect)); S->cols = (int *)calloc((size_t)m, sizeof(int)); }
-  if (!S || !S->e || !S->cols) { if (S) { free(S->e); free(S->cols); free(S); } Rf_error("out of memory"); }
+  if (S) {
+    S->neff = m; S->e = (bwgr_pegs_effect_ex *)calloc((size_t)m, sizeof(bwgr_pegs_effect_ex)); S->cols = (int *)calloc((size_t)m, sizeof(int));
+    S->rows = (int *)calloc((size_t)m, sizeof(int)); S->ptr = (int64_t **)calloc((size_t)m, sizeof(int64_t *));
+  }
+  if (!S || !S->e || !S->cols || !S->rows || !S->ptr) { pegs_set_free(S); Rf_error("out of memory"); }
   SEXP ext = PROTECT(R_MakeExternalPtr(S, R_NilValue, R_NilValue));
   R_RegisterCFinalizerEx(ext, pegs_set_finalizer, TRUE);
   UNPROTECT(1);
@@ -418,25 +428,46 @@ SEXP bwgrhip_pegs_put(SEXP set, SEXP index, SEXP panel, SEXP Z) {
   pegs_set *S = (pegs_set *)R_ExternalPtrAddr(set);
   const int i = Rf_asInteger(index);
   if (!S || i < 0 || i >= S->neff) Rf_error("bad effect set or index");
+  free(S->ptr[i]); S->ptr[i] = NULL;
+  S->e[i].colptr = NULL; S->e[i].rowidx = NULL; S->e[i].val = NULL; S->e[i].flags = 0;
   if (!Rf_isNull(panel)) {
     bwgr_panel *P = panel_of(panel);
     int64_t info[8]; chk(bwgr_panel_info(P, info));
-    S->e[i].panel = P; S->e[i].Z = NULL; S->e[i].q = 0; S->e[i].ldz = 0; S->cols[i] = (int)info[1];
+    S->e[i].panel = P; S->e[i].Z = NULL; S->e[i].q = 0; S->e[i].ldz = 0; S->cols[i] = (int)info[1]; S->rows[i] = (int)info[0];
   } else {
     SEXP dz = Rf_getAttrib(Z, R_DimSymbol);
     if (TYPEOF(Z) != REALSXP || Rf_length(dz) != 2) Rf_error("a dense effect must be a numeric matrix");
-    S->e[i].panel = NULL; S->e[i].Z = REAL(Z); S->e[i].q = INTEGER(dz)[1]; S->e[i].ldz = INTEGER(dz)[0]; S->cols[i] = INTEGER(dz)[1];
+    S->e[i].panel = NULL; S->e[i].Z = REAL(Z); S->e[i].q = INTEGER(dz)[1]; S->e[i].ldz = INTEGER(dz)[0]; S->cols[i] = INTEGER(dz)[1]; S->rows[i] = INTEGER(dz)[0];
   }
   return R_NilValue;
 }
-SEXP bwgrhip_pegs(SEXP set, SEXP Y, SEXP maxit, SEXP logtol, SEXP covbend, SEXP covMinEv, SEXP XFA, SEXP NNC, SEXP own_text) {
+/* a sparse effect: the slots of a dgCMatrix -- ri = @i (0-based rows, integer), cp = @p (integer, ncol + 1), x = @x (double, float-rounded by
+ * the R front-end), dim = @Dim.  @i and @x are read where they are; @p is widened to the library's int64 and kept with the set. */
+SEXP bwgrhip_pegs_put_sparse(SEXP set, SEXP index, SEXP ri, SEXP cp, SEXP x, SEXP dim) {
+  pegs_set *S = (pegs_set *)R_ExternalPtrAddr(set);
+  const int i = Rf_asInteger(index);
+  if (!S || i < 0 || i >= S->neff) Rf_error("bad effect set or index");
+  if (TYPEOF(ri) != INTSXP || TYPEOF(cp) != INTSXP || TYPEOF(x) != REALSXP || TYPEOF(dim) != INTSXP || Rf_length(dim) != 2)
+    Rf_error("a sparse effect needs integer @i, @p and @Dim and double @x");
+  const int n = INTEGER(dim)[0], q = INTEGER(dim)[1];
+  if (q < 1 || Rf_length(cp) != q + 1 || Rf_length(ri) != Rf_length(x) || INTEGER(cp)[q] > Rf_length(x)) Rf_error("a sparse effect's @p, @i and @x do not describe its @Dim");
+  int64_t *p64 = (int64_t *)malloc(((size_t)q + 1) * sizeof(int64_t));
+  if (!p64) Rf_error("out of memory");
+  for (int j = 0; j <= q; j++) p64[j] = INTEGER(cp)[j];
+  free(S->ptr[i]); S->ptr[i] = p64;
+  S->e[i].panel = NULL; S->e[i].Z = NULL; S->e[i].q = q; S->e[i].ldz = 0;
+  S->e[i].colptr = p64; S->e[i].rowidx = (const int32_t *)INTEGER(ri); S->e[i].val = REAL(x); S->e[i].flags = 0;
+  S->cols[i] = q; S->rows[i] = n;
+  return R_NilValue;
+}
+SEXP bwgrhip_pegs(SEXP set, SEXP Y, SEXP maxit, SEXP logtol, SEXP covbend, SEXP covMinEv, SEXP XFA, SEXP NNC, SEXP text) {
   pegs_set *S = (pegs_set *)R_ExternalPtrAddr(set);
   if (!S) Rf_error("bad effect set");
   SEXP dy = Rf_getAttrib(Y, R_DimSymbol);
   if (Rf_length(dy) != 2) Rf_error("Y must be a matrix");
   const int n = INTEGER(dy)[0], k = INTEGER(dy)[1], m = S->neff, mit = Rf_asInteger(maxit);
   for (int i = 0; i < m; i++)
-    if (!S->e[i].panel && (!S->e[i].Z || S->e[i].ldz != n)) Rf_error("every effect must be set and have nrow(Y) rows");
+    if ((!S->e[i].panel && !S->e[i].Z && !S->e[i].colptr) || S->rows[i] != n) Rf_error("every effect must be set and have nrow(Y) rows");
   SEXP mu = PROTECT(Rf_allocVector(REALSXP, k)), hat = PROTECT(Rf_allocMatrix(REALSXP, n, k)), h2 = PROTECT(Rf_allocVector(REALSXP, k));
   SEXP bend = PROTECT(Rf_allocVector(REALSXP, m)), bl = PROTECT(Rf_allocVector(VECSXP, m)), gl = PROTECT(Rf_allocVector(VECSXP, m));
   double **bp = (double **)R_alloc((size_t)m, sizeof(double *)), **gp = (double **)R_alloc((size_t)m, sizeof(double *));
@@ -448,8 +479,8 @@ SEXP bwgrhip_pegs(SEXP set, SEXP Y, SEXP maxit, SEXP logtol, SEXP covbend, SEXP 
   }
   double *cnv = (double *)R_alloc(mit > 0 ? mit : 1, sizeof(double));
   int numit = 0;
-  chk(bwgr_pegs(0, S->e, m, REAL(Y), (int64_t)n, k, mit, Rf_asReal(logtol), Rf_asReal(covbend), Rf_asReal(covMinEv), Rf_asInteger(XFA),
-                Rf_asLogical(NNC), Rf_asInteger(own_text), REAL(mu), bp, REAL(hat), REAL(h2), gp, REAL(bend), &numit, cnv));
+  chk(bwgr_pegs_ex(0, S->e, m, REAL(Y), (int64_t)n, k, mit, Rf_asReal(logtol), Rf_asReal(covbend), Rf_asReal(covMinEv), Rf_asInteger(XFA),
+                   Rf_asLogical(NNC), Rf_asInteger(text), REAL(mu), bp, REAL(hat), REAL(h2), gp, REAL(bend), &numit, cnv));
   const char *nm[] = {"mu", "b", "hat", "h2", "GC", "bend", "numit", "cnv"};
   SEXP out = PROTECT(named_list(8, nm));
   SET_VECTOR_ELT(out, 0, mu); SET_VECTOR_ELT(out, 1, bl); SET_VECTOR_ELT(out, 2, hat); SET_VECTOR_ELT(out, 3, h2); SET_VECTOR_ELT(out, 4, gl);
@@ -472,7 +503,7 @@ SEXP bwgrhip_pegsx(SEXP set, SEXP Y, SEXP X, SEXP opts) {
   const int n = INTEGER(dy)[0], k = INTEGER(dy)[1], f = INTEGER(dx)[1], m = S->neff, mit = (int)o[0];
   if (INTEGER(dx)[0] != n) Rf_error("nrow(X) must equal nrow(Y)");
   for (int i = 0; i < m; i++)
-    if (!S->e[i].panel && (!S->e[i].Z || S->e[i].ldz != n)) Rf_error("every effect must be set and have nrow(Y) rows");
+    if ((!S->e[i].panel && !S->e[i].Z && !S->e[i].colptr) || S->rows[i] != n) Rf_error("every effect must be set and have nrow(Y) rows");
   SEXP b = PROTECT(Rf_allocMatrix(REALSXP, f, k)), ve = PROTECT(Rf_allocVector(REALSXP, k)), hat = PROTECT(Rf_allocMatrix(REALSXP, n, k));
   SEXP bend = PROTECT(Rf_allocVector(REALSXP, m)), tl = PROTECT(Rf_allocVector(VECSXP, m)), ul = PROTECT(Rf_allocVector(VECSXP, m));
   SEXP vl = PROTECT(Rf_allocVector(VECSXP, m)), gl = PROTECT(Rf_allocVector(VECSXP, m));
@@ -486,7 +517,7 @@ SEXP bwgrhip_pegsx(SEXP set, SEXP Y, SEXP X, SEXP opts) {
   }
   double *cnv = (double *)R_alloc(mit > 0 ? mit : 1, sizeof(double));
   int its = 0;
-  chk(bwgr_pegsx(0, S->e, m, REAL(X), (int64_t)n, f, REAL(Y), (int64_t)n, k, mit, o[1], o[2], o[3], o[4], o[5] != 0, o[8] != 0, (int)o[9], o[6] != 0, o[7] != 0,
+  chk(bwgr_pegsx_ex(0, S->e, m, REAL(X), (int64_t)n, f, REAL(Y), (int64_t)n, k, mit, o[1], o[2], o[3], o[4], o[5] != 0, o[8] != 0, (int)o[9], o[6] != 0, o[7] != 0,
                  tr, REAL(b), up, vp, gp, REAL(ve), REAL(hat), &its, cnv, REAL(bend)));
   for (int i = 0; i < m; i++) {
     SEXP t = PROTECT(Rf_allocVector(REALSXP, k));
@@ -567,7 +598,8 @@ static const R_CallMethodDef CallEntries[] = {   /* as src/RcppExports.cpp:1152-
   {"bwgrhip_solver1x", (DL_FUNC)&bwgrhip_solver1x, 6}, {"bwgrhip_UVBETA", (DL_FUNC)&bwgrhip_UVBETA, 3},
   {"bwgrhip_uvbeta_dense", (DL_FUNC)&bwgrhip_uvbeta_dense, 6}, {"bwgrhip_panel_xb", (DL_FUNC)&bwgrhip_panel_xb, 2},
   {"bwgrhip_uvbeta2", (DL_FUNC)&bwgrhip_uvbeta2, 6},
-  {"bwgrhip_pegs_set", (DL_FUNC)&bwgrhip_pegs_set, 1}, {"bwgrhip_pegs_put", (DL_FUNC)&bwgrhip_pegs_put, 4}, {"bwgrhip_pegs", (DL_FUNC)&bwgrhip_pegs, 9},
+  {"bwgrhip_pegs_set", (DL_FUNC)&bwgrhip_pegs_set, 1}, {"bwgrhip_pegs_put", (DL_FUNC)&bwgrhip_pegs_put, 4}, {"bwgrhip_pegs_put_sparse", (DL_FUNC)&bwgrhip_pegs_put_sparse, 6},
+  {"bwgrhip_pegs", (DL_FUNC)&bwgrhip_pegs, 9},
   {"bwgrhip_pegsx", (DL_FUNC)&bwgrhip_pegsx, 4},
   {"bwgrhip_kernel", (DL_FUNC)&bwgrhip_kernel, 4}, {"bwgrhip_crossprod", (DL_FUNC)&bwgrhip_crossprod, 1},
   {"bwgrhip_kernel2", (DL_FUNC)&bwgrhip_kernel2, 4}, {"bwgrhip_crossprod2", (DL_FUNC)&bwgrhip_crossprod2, 2}, {NULL, NULL, 0}};
