@@ -3,7 +3,7 @@ tests/test_pegs_cpu.py checks on the restatement alone that none of them sits on
 on a near-degenerate eigen-gap where XFA truncates -- there a difference in the last bits would flip the branch and parity would be luck.
 
 A case: id, entry ("PEGS" / "PEGSZ"), data() -> (Y, effects), kw (the fit's arguments).  An effect is ("panel", X int8, panel kwargs) or
-("dense", Z float64).  Every case runs with logtol = -inf (every sweep) unless its kw says otherwise.
+("dense", Z float64); tests/tall_cases.py adds ("sparse", A float64[, stored mask]), read here as its dense copy A.  Every case runs with logtol = -inf (every sweep) unless its kw says otherwise.
 """
 import os
 import sys
@@ -268,5 +268,10 @@ def restate(case):
     key = ("fit", case["id"])
     if key not in _cache:
         Y, effects = case["data"]()
-        _cache[key] = (Y, effects, PR.pegsz(Y, designs(effects), own_text=case["entry"] == "PEGS", trace=True, **case["kw"]))
+        if case["entry"] == "PEGSZ_sparse":        # text 2 (tests/tall_cases.py runs it beside a panel); its fit always carries the trace
+            import pegs_sparse_restatement as SR
+            fit = SR.pegsz_sparse(Y, designs(effects), **case["kw"])
+        else:
+            fit = PR.pegsz(Y, designs(effects), own_text=case["entry"] == "PEGS", trace=True, **case["kw"])
+        _cache[key] = (Y, effects, fit)
     return _cache[key]

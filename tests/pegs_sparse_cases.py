@@ -7,6 +7,11 @@ A case: id, entry ("PEGS_sparse" / "PEGSZ_sparse" / "PEGSZ" / "PEGSX"), data() -
 ("sparse", A float64 n x q[, stored mask]), ("panel", X int8, panel kwargs) or ("dense", Z float64); the values of a sparse design are
 floats already.  n = 300 (no multiple of 64) unless a case says otherwise; about 20 % of the records are missing, one trait is missing on a
 whole level of the first sparse effect, and a few rows are missing for every trait.  Every case runs with logtol = -inf (every sweep).
+
+The cases of the second round (from ps_setup_trip_k3 on) are there for one edge of the kernels each -- a second trip of the set-up kernel,
+the sparse trace kernel at the cap of its grid, f past one and up to four lane strides, sixteen patterns, the serial leg's hand-off between
+long columns that share rows, values other than 1 on the disjoint leg, a level without a record -- stated beside each case in the table and
+asserted from the plan hooks by tests/test_pegs_sparse_cpu.py::test_second_round_cases_reach_what_they_are_listed_for.
 """
 import os
 import sys
@@ -98,9 +103,13 @@ def _mk(build, k, seed, x=None):
     return data
 
 
-def fixed(n):
-    """PEGSX's X: an intercept and two covariates"""
-    return np.asfortranarray(np.column_stack([np.ones(n), SR.f32(np.random.default_rng(77).normal(size=(n, 2)))]))
+def fixed(n, ncov=2):
+    """PEGSX's X: an intercept and ncov covariates, rounded to float"""
+    return np.asfortranarray(np.column_stack([np.ones(n), SR.f32(np.random.default_rng(77).normal(size=(n, ncov)))]))
+
+
+def fixed70(n):
+    return fixed(n, 69)
 
 
 def _inc12(): return [("sparse", incidence(N, 12, 1))]
@@ -124,6 +133,75 @@ def _panel_inc(): return [("panel", panel(N, 200, 10), {}), ("sparse", incidence
 def _panel_inc70(): return [("panel", panel(N, 200, 10), {}), ("sparse", incidence(N, 70, 12))]
 def _mixed4(): return [("panel", panel(N, 200, 10), {}), ("sparse", incidence(N, 12, 13)), ("sparse",) + overlapping(N, 25, 14), ("dense", gauss(N, 9, 15))]
 def _inc_overlap(): return [("sparse", incidence(N, 12, 16)), ("sparse",) + overlapping(N, 25, 17)]
+
+
+# ---- the second round: every loop bound and stride of csrc/pegs_sparse.hip.h that the table above stops short of ----
+SETUP_TRIP_COLS = 32768   # the columns one trip of k_pegs_sparse_setup covers (8 192 workgroups of four waves, a column each)
+N2 = 700                  # rows of the cases with f = 256 or columns of three lane strides (no multiple of 64 either)
+
+
+def placed(n, q, seed, last=40):
+    """an incidence far wider than it is tall, which incidence() would leave empty at the far end: `last` rows (none of those that traits()
+    leaves without any record) sit on the last `last` columns, one each, the other rows on random levels"""
+    rng = np.random.default_rng(seed)
+    lev = rng.integers(0, q - last, size=n)
+    rows = np.setdiff1d(np.arange(n), [7, n // 2, n - 1])
+    lev[rng.permutation(rows)[:last]] = np.arange(q - last, q)
+    A = np.zeros((n, q))
+    A[np.arange(n), lev] = 1.0
+    return A
+
+
+def weighted(n, q, seed):
+    """a covariate nested in a factor: a row-disjoint matrix of float-rounded normal values, negative ones among them, and five stored zeros
+    -> (A, stored mask)"""
+    inc = incidence(n, q, seed)
+    rng = np.random.default_rng(seed + 1000)
+    A = inc * SR.f32(rng.normal(size=n))[:, None]
+    stored = inc != 0
+    A[rng.permutation(n)[:5]] = 0.0                        # stored, and zero
+    assert SR.row_disjoint(A) and (A < 0).any() and (stored & (A == 0)).sum() == 5 and stored.sum() == n
+    return A, stored
+
+
+def unobserved_level(n, q, seed, level=5):
+    """an incidence one level of which consists of exactly the rows that traits() leaves without a record in any trait"""
+    gone = [7, n // 2, n - 1]
+    rest = np.setdiff1d(np.arange(n), gone)
+    A = np.zeros((n, q))
+    A[np.ix_(rest, np.arange(q) != level)] = incidence(len(rest), q - 1, seed)
+    A[gone, level] = 1.0
+    assert SR.row_disjoint(A) and np.array_equal(np.flatnonzero(A[:, level]), gone) and (A.sum(0) > 0).all()
+    return A
+
+
+def unobserved_column(A, Y):
+    """the one column of A that has stored entries and no record under them in any trait"""
+    seen = (np.asarray(A) != 0).T.astype(float) @ (~np.isnan(Y)).any(1).astype(float)
+    cols = np.flatnonzero((seen == 0) & ((np.asarray(A) != 0).sum(0) > 0))
+    assert len(cols) == 1
+    return int(cols[0])
+
+
+def _inc_setup_trip(): return [("sparse", placed(N, SETUP_TRIP_COLS + 37, 20))]
+def _inc_trace_cap(): return [("sparse", placed(N, 16501, 21))]
+def _inc70_overlap(): return [("sparse", incidence(N, 70, 22)), ("sparse",) + overlapping(N, 25, 23)]
+def _inc12_overlap_n700(): return [("sparse", incidence(N2, 12, 24)), ("sparse",) + overlapping(N2, 25, 25)]
+def _overlap_long(): return [("sparse",) + overlapping(N2, 130, 26, density=0.25)]
+def _inc12_overlap_long(): return [("sparse", incidence(N2, 12, 27))] + _overlap_long()
+def _weighted(): return [("sparse",) + weighted(N, 12, 28)]
+def _unobserved(): return [("sparse", unobserved_level(N, 12, 29))]
+
+
+def _f256_data():
+    """px_f256_k3: X and its share of Y as tests/tall_cases.py's f256 job builds them (an intercept and 255 covariates, X beta added to Y)"""
+    import pegsx_cases as XC
+    key = "f256"
+    if key not in _cache:
+        effects = _inc12_overlap_n700()
+        X = XC.fixed(N2, 255, 501)
+        _cache[key] = (XC.with_fixed(traits(effects, 3, 126), X, 502), effects, X)
+    return _cache[key]
 
 
 def _case(id_, entry, data, **kw):
@@ -154,27 +232,44 @@ CASES = [
     _case("px_overlap_k1", "PEGSX", _mk(_overlap, 1, 117, x=fixed), maxit=8),
     _case("px_mixed4_k3_xfa2", "PEGSX", _mk(_mixed4, 3, 118, x=fixed), maxit=8, XFA=True, NumXFA=2, covMinEv=1e-5),   # (at the default a sweep's MinDVb comes within 0.3 % of it)
     _case("px_panel_inc70_k5", "PEGSX", _mk(_panel_inc70, 5, 119, x=fixed), maxit=6),
+    # the second round; what each is there for (tests/test_pegs_sparse_cpu.py asserts it from the plan hooks):
+    # a second trip of k_pegs_sparse_setup with its last column occupied, and k_mrr_tilde's second and third trips over d2
+    _case("ps_setup_trip_k3", "PEGS_sparse", _mk(_inc_setup_trip, 3, 120), maxit=2),
+    # k_pegsx_trace_sparse at its cap of 1 024 workgroups: four whole trips of 4 096 columns and a fifth that ends on the last column
+    _case("px_trace_cap_k3", "PEGSX", _mk(_inc_trace_cap, 3, 121, x=fixed), maxit=2),
+    # f > 64: a second step of both lane loops of the sparse trace; sixteen patterns in tot[g]; k = 16 on the serial leg beside a disjoint one
+    _case("px_f70_k16", "PEGSX", _mk(_inc70_overlap, 16, 122, x=fixed70), maxit=4),
+    # f = 256: four steps of the lane loops, the whole of a wave's LDS region
+    _case("px_f256_k3", "PEGSX", _f256_data, maxit=4),
+    # the serial leg's hand-off: columns of three lane strides that share rows, more columns than a wave has lanes, the shuffles for t up to 15
+    _case("ps_overlap_long_k16", "PEGS_sparse", _mk(_overlap_long, 16, 123), maxit=4, XFA=2),
+    _case("pzs_inc_overlap_long_k3", "PEGSZ_sparse", _mk(_inc12_overlap_long, 3, 124), maxit=4),
+    # the disjoint leg on values other than 1: XX is no count, v is negative, fractional or a stored zero
+    _case("ps_weighted_k3", "PEGS_sparse", _mk(_weighted, 3, 125), maxit=8),
+    # a column with stored entries and XX = 0 in every trait: Linv_j is the inverse of iG alone, b_j stays 0
+    _case("ps_unobserved_level_k3", "PEGS_sparse", _mk(_unobserved, 3, 127), maxit=8),
 ]
+TRZSZ_ALONE = ("px_trace_cap_k3",)      # a maxit = 0 run that checks TrZSZ by itself
 # the cases whose sparse effects are all row-disjoint: the plan takes the disjoint leg, and serial=True must give the same bits
 DISJOINT = ("ps_inc12_k3", "ps_inc12_k1", "ps_inc12_k5_xfa2", "ps_inc12_k3_xfa0", "ps_q1_k3", "ps_inc70_k3", "ps_trip_k3", "ps_empty_col_k3",
             "ps_long_cols_k3", "pzs_two_inc_k3", "pzs_inc12_k1", "pz_two_inc_k3", "pz_panel_inc_k3", "pz_panel_inc70_k16_xfa2", "px_inc12_k3",
-            "px_panel_inc70_k5")
+            "px_panel_inc70_k5", "ps_setup_trip_k3", "px_trace_cap_k3", "ps_weighted_k3", "ps_unobserved_level_k3")
 
 
 def by_id(id_):
     return next(c for c in CASES if c["id"] == id_)
 
 
-def restate(case):
+def restate(case, **more):
     """the restatement's fit of a case on the dense copies, computed once per process -> (data, fit)"""
     import pegs_restatement as PR
     import pegsx_restatement as PXR
-    key = ("fit", case["id"])
+    key = ("fit", case["id"], tuple(sorted(more.items())))
     if key not in _cache:
         data = case["data"]()
         Y, effects = data[0], data[1]
         D = [design(e) for e in effects]
-        kw = case["kw"]
+        kw = dict(case["kw"], **more)
         if case["entry"] == "PEGS_sparse":
             fit = PR.pegsz(Y, D, own_text=True, trace=True, **kw)
             fit["b"], fit["GC"], fit["bend"] = fit["b"][0], fit["GC"][0], float(fit["bend"][0])      # (as PR.pegs unwraps them)

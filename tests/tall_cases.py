@@ -26,6 +26,11 @@ uncentred on wide33k, tall16k, slab1280 and slab1024, and their own kernels besi
   dsetup     ceil(q / (workgroups x 4)): k_pegs_dense_setup, one column per wave
   rows       ceil(n / threads): the row loops of k_pegs_dense_leg and k_pegsx_fixed (1 024 threads from 961 rows on)
   fixed_cols ceil(f / (threads / 64)): the fixed step's column loop, one wave per column of X;  quad  ceil(f / 64): the trace's quadratic form
+  sparse_hat ceil(n / 256): the workgroups of k_pegs_sparse_hat, one thread per row, its rows of stride n against the engine's stride ld
+
+tall9k_sparse and slab1280_sparse put sparse effects (csrc/pegs_sparse.hip.h) beside those panels: the sparse kernels index the residual by
+the panel's ld (216 and 120 rows past n, R = 256 and 1 280), a level longer than 4 096 rows spans slab edges, and the rows of PEGS_MISSING
+lie on both sides of one.
 """
 import ctypes as C
 import functools
@@ -35,6 +40,7 @@ import numpy as np
 from conftest import synth_small
 import driver_cases as dc
 import pegs_cases as PC
+import pegs_sparse_cases as SC
 import pegsx_cases as XC
 
 # tag -> n, p, block (0 = the default), seed of the genotypes
@@ -200,8 +206,9 @@ ALL_MISSING = {"tall9k": (7, 4095, 4096, 8500), "slab1280": (7, 1279, 1280, 4990
 PEGS_MISSING = dict(ALL_MISSING, tall9k=(7, 4095, 4096, 4097, 4098, 4099, 8500), tall16k=(7, 8191, 8192, 16400))
 
 # job -> the panel's shape tag (None: no panel; "slabs900": tests/pegs_cases.py's 700 x 900 panel in three slabs, not on CASES because no
-# other family needs it here), k, f (PEGSX), maxit, the effects in list order ("panel" or the q of a dense gauss(n, q, 503)), the seed of the
-# traits (the shape's seed + 70) and the entries that run it.  PEGS takes one design: on tall9k and slab1280 it runs the panel alone.
+# other family needs it here), k, f (PEGSX), maxit, the effects in list order ("panel", the q of a dense gauss(n, q, 503), or a sparse effect
+# of tests/pegs_sparse_cases.py's builders: ("inc", q), an incidence of q levels, or ("overlap", q, density)), the seed of the traits (the
+# shape's seed + 70) and the entries that run it ("PEGSZ_sparse": text 2, which takes the same list).  PEGS takes one design: on tall9k and slab1280 it runs the panel alone.
 # dense16501 is a TrZSZ-only job (maxit = 0): 33 000 and 16 500 are multiples of four, so no other job has a partial last group of columns.
 PEGS_JOBS = {
     "wide33k":    dict(tag="wide33k",  k=3, f=3,   maxit=2, effects=("panel",),    entries=("PEGS", "PEGSZ", "PEGSX")),
@@ -213,9 +220,12 @@ PEGS_JOBS = {
     "dense16500": dict(tag=None, n=196, seed=2907, k=3, f=3, maxit=2, effects=(16500,), entries=("PEGSZ", "PEGSX")),
     "dense16501": dict(tag=None, n=196, seed=2907, k=3, f=3, maxit=0, effects=(16501,), entries=("PEGSX",)),
     "f256":       dict(tag="slabs900", k=3, f=256, maxit=4, effects=("panel",),    entries=("PEGSX",)),
+    "tall9k_sparse":   dict(tag="tall9k",   k=3, f=3, maxit=3, effects=("panel", ("inc", 2), ("overlap", 30, 0.05)), entries=("PEGSZ", "PEGSX")),
+    "slab1280_sparse": dict(tag="slab1280", k=3, f=3, maxit=3, effects=("panel", ("inc", 40)), entries=("PEGSZ", "PEGSX", "PEGSZ_sparse")),
 }
 TRZSZ_ALONE = ("wide33k", "dense16500", "dense16501", "f256")     # a maxit = 0 run that checks TrZSZ by itself
-NORMAL_EQUATIONS = ("tall9k", "slab1280")
+NORMAL_EQUATIONS = ("tall9k", "slab1280", "tall9k_sparse", "slab1280_sparse")
+SAME_LEVEL = {"tall9k_sparse": (4095, 4096)}      # rows on both sides of a slab edge that the job's incidence puts on one level
 
 # What each job is there for, as pegs_plans must report it.  m: the columns of the effect the trace figures speak of; trace_last: the trip
 # (1-based) on which the last group of four columns runs; trace_tail: columns of that group.  dsetup = 1 on dense16500: k_pegs_dense_setup
@@ -230,6 +240,8 @@ PEGS_EXPECT = {
     "dense16500": dict(m=16500, trace_wg=1024, trace=2, trace_last=2, trace_tail=4, dsetup=1, dsetup_wg=4125, ld=256),
     "dense16501": dict(m=16501, trace_wg=1024, trace=2, trace_last=2, trace_tail=1, dsetup=1),
     "f256":       dict(K=3, R=256, ld=768, quad=4, lds_trace=33280, lds_fixed=4096, fixed_threads=704, fixed_cols=24),
+    "tall9k_sparse":   dict(K=36, R=256, ld=9216, ld128=9088, pad=216, rows=9, sparse_hat=36, sparse_legs=("disjoint", "serial"), npat=3),
+    "slab1280_sparse": dict(K=4, R=1280, ld=5120, ld128=5120, pad=120, rows=5, sparse_hat=20, sparse_legs=("disjoint",), npat=3),
 }
 
 
@@ -251,13 +263,34 @@ def _pegs_dense(n, q):
     return Z
 
 
+def _pegs_sparse(job, n, e, i):
+    """effect i of a job, ("inc", q) or ("overlap", q, density), through the builders of tests/pegs_sparse_cases.py"""
+    if e[0] == "inc":
+        A = SC.incidence(n, e[1], 505 + i)
+        for a, b in (SAME_LEVEL[job],) if job in SAME_LEVEL else ():
+            A[b] = A[a]
+        out = ("sparse", A)
+    else:
+        assert e[0] == "overlap"
+        out = ("sparse",) + SC.overlapping(n, e[1], 505 + i, density=e[2])
+    for a in out[1:]:
+        a.setflags(write=False)
+    return out
+
+
+def _pegs_effect(job, n, Z, kw, e, i):
+    if e == "panel":
+        return ("panel", Z, kw)
+    return _pegs_sparse(job, n, e, i) if isinstance(e, tuple) else ("dense", _pegs_dense(n, e))
+
+
 @functools.lru_cache(maxsize=None)
 def pegs_data(job):
     """(Y, effects) of a job in the form of tests/pegs_cases.py: the traits of the issue -- k traits, each its own missingness pattern, on
     the job's first design -- with the rows of PEGS_MISSING missing in every trait"""
     j = PEGS_JOBS[job]
     n, Z, seed, kw = _pegs_shape(job)
-    effects = [("panel", Z, kw) if e == "panel" else ("dense", _pegs_dense(n, e)) for e in j["effects"]]
+    effects = [_pegs_effect(job, n, Z, kw, e, i) for i, e in enumerate(j["effects"])]
     lead = Z if Z is not None else effects[0][1]
     Y = PC.traits(lead, j["k"], 0, seed=seed + 70, patterns=[0.1, 0.0, 0.25, 0.05][:j["k"]])
     if j["tag"] in PEGS_MISSING:
@@ -295,6 +328,13 @@ def pegs_case(entry, job):
     return dict(id="tall/%s/%s" % (entry, job), job=job, entry=entry, data=data, kw=kw)
 
 
+def gpu_effects(effects, panels):
+    """a job's effects as the entries take them: `panels` (one per panel effect, in order) for the panels, dense(Z), sparse(S) in CSC"""
+    import bwgr_amd
+    panels = list(panels)
+    return [panels.pop(0) if e[0] == "panel" else bwgr_amd.dense(e[1]) if e[0] == "dense" else SC.gpu_effects([e])[0] for e in effects]
+
+
 def pegs_jobs(entry):
     return [job for job, j in PEGS_JOBS.items() if entry in j["entries"]]
 
@@ -314,7 +354,7 @@ def pegs_plans(job):
     j = PEGS_JOBS[job]
     n, Z, _, kw = _pegs_shape(job)
     k, f = j["k"], j["f"]
-    ms = [Z.shape[1] if e == "panel" else e for e in j["effects"]]
+    ms = [Z.shape[1] if e == "panel" else e[1] if isinstance(e, tuple) else e for e in j["effects"]]
     pl = dict(n=n, ld128=_ceil(n, 128) * 128)
     if Z is not None:
         pp = _panel_plan(n, Z.shape[1], kw.get("block", 0), kw.get("nwg", 0))
@@ -340,15 +380,26 @@ def pegs_plans(job):
               trace_tail=m - (ngrp - 1) * xp["jc"], dsetup_wg=gp["setup_wg"], dsetup=_ceil(m, gp["setup_cols"]),
               leg_threads=gp["leg_threads"], fixed_threads=gp["fixed_threads"], rows=_ceil(n, gp["fixed_threads"]),
               fixed_cols=_ceil(f, gp["fixed_threads"] // 64), quad=_ceil(f, 64), lds_trace=xp["trace_lds_bytes"], lds_fixed=xp["lds_bytes"])
-    Y = pegs_data(job)[0]
+    Y, effects = pegs_data(job)
     pl["npat"] = len({np.isnan(Y[:, t]).tobytes() for t in range(k)})
+    # the sparse effects: the leg each takes under bwgr_debug_pegs_sparse_plan, and k_pegs_sparse_hat's workgroups (a thread per row)
+    legs = []
+    for e in effects:
+        if e[0] == "sparse":
+            stored = e[2] if len(e) > 2 else e[1] != 0
+            sp = bwgr_amd.pegs_sparse_plan(n, e[1].shape[1], int(stored.sum()), int(stored.sum(0).max()), k, SC.SR.row_disjoint(e[1]))
+            legs.append(sp["leg"])
+    pl["sparse_legs"] = tuple(legs)
+    pl["sparse_hat"] = _ceil(n, 256) if legs else 0
     return pl
 
 
 # ---- the handle table's PEGS / PEGSZ / PEGSX calls (tests/test_gpu_handles.py), on the 700 x 900 three-slab panel ----
 # k = 3 (10 % / 0 / 25 % missing), four sweeps; PEGSZ and PEGSX with a dense effect of five columns behind the panel, PEGSX with f = 3;
-# PEGSZ2: the panel's columns split 500 / 400 into two panels.  tests/test_tall_cases_cpu.py runs the branch guards on them too.
-HANDLE_ENTRIES = ("PEGS", "PEGSZ", "PEGSX", "PEGSZ2")
+# PEGSZ2: the panel's columns split 500 / 400 into two panels; PEGSZ_S and PEGSX_S (f = 3): [panel, a sparse incidence of 12 levels, a sparse
+# overlapping design of 25 columns], whose legs MtFit::sweep_effect launches between host-to-device copies of the order and of iG.
+# tests/test_tall_cases_cpu.py runs the branch guards on them too.
+HANDLE_ENTRIES = ("PEGS", "PEGSZ", "PEGSX", "PEGSZ2", "PEGSZ_S", "PEGSX_S")
 
 
 @functools.lru_cache(maxsize=None)
@@ -360,9 +411,11 @@ def _handle_data(entry):
     kw = dict(nwg=3)
     if entry == "PEGSZ2":
         effects = [("panel", np.asfortranarray(Z[:, :500]), kw), ("panel", np.asfortranarray(Z[:, 500:]), kw)]
+    elif entry in ("PEGSZ_S", "PEGSX_S"):
+        effects = [("panel", Z, kw), ("sparse", SC.incidence(n, 12, 506)), ("sparse",) + SC.overlapping(n, 25, 507)]
     else:
         effects = [("panel", Z, kw)] + ([] if entry == "PEGS" else [("dense", D)])
-    if entry != "PEGSX":
+    if not entry.startswith("PEGSX"):
         Y.setflags(write=False)
         return Y, effects
     X = XC.fixed(n, 2, 501)
@@ -374,6 +427,6 @@ def _handle_data(entry):
 @functools.lru_cache(maxsize=None)
 def handle_case(entry):
     kw = dict(maxit=4, logtol=PC.NOSTOP)
-    if entry == "PEGSX":
-        return dict(id="handles/PEGSX", data=lambda: _handle_data(entry), kw=kw)
+    if entry.startswith("PEGSX"):
+        return dict(id="handles/" + entry, data=lambda: _handle_data(entry), kw=kw)
     return dict(id="handles/" + entry, entry="PEGS" if entry == "PEGS" else "PEGSZ", data=lambda: _handle_data(entry), kw=kw)

@@ -23,7 +23,8 @@ The two-panel entries (crossprod2, kernel2 on the 700 x 900 root and a 300 x 900
 the others, the samples on the default stream; test_two_panel_entry_on_every_pair_of_handles then puts the founders and the samples on
 different streams and clones.
 
-PEGS, PEGSZ ([panel, dense of five columns]) and PEGSX (the same effects, f = 3) on the 700 x 900 root issue the library's longest host
+PEGS, PEGSZ ([panel, dense of five columns]) and PEGSX (the same effects, f = 3), and PEGSZ_S / PEGSX_S ([panel, sparse incidence, sparse
+overlapping design]) on the 700 x 900 root issue the library's longest host
 sequences -- 20 to 30 copies, clears and launches per sweep on the first panel's stream -- and stand in the table like the others (their inputs,
 and the branch guards on them, are tests/tall_cases.py's handle_case and tests/test_tall_cases_cpu.py);
 test_two_panel_effects_of_one_pegsz_call_on_different_handles puts the two panel effects of one PEGSZ call on different handles."""
@@ -384,27 +385,30 @@ def _pegs_inputs(entry):
     """(Y, X or None, the effects' data) of tests/tall_cases.py's handle_case; under ALT Y's columns are reversed, as _Y does"""
     d = tc.handle_case(entry)["data"]()
     Y = np.ascontiguousarray(d[0][:, ::-1]) if ALT["on"] else d[0]
-    return Y, (d[1] if entry == "PEGSX" else None), d[-1]
+    return Y, (d[1] if entry.startswith("PEGSX") else None), d[-1]
 
 
 def _pegs(entry):
     """PEGS (k = 3, four sweeps), PEGSZ ([panel, dense of five columns]) and PEGSX (the same effects, f = 3) on the slabs panel: the longest
-    host sequences of the library, 20 to 30 copies, clears and launches per sweep on the first panel's stream"""
+    host sequences of the library, 20 to 30 copies, clears and launches per sweep on the first panel's stream.  PEGSZ_S and PEGSX_S: [panel,
+    sparse incidence of 12 levels, sparse overlapping design]: the sparse set-up, both legs, their reduction of d2, the sparse trace and
+    k_pegs_sparse_hat, launched between host-to-device copies of the order and of iG -- one of them on stream 0 would read or write beside
+    the fit's stream, and the filler would show it as other bits"""
     kw = tc.handle_case(entry)["kw"]
 
     def call(P, aux):
         import bwgr_amd
         Y, X, effects = _pegs_inputs(entry)
-        effs = [P] + [bwgr_amd.dense(e[1]) for e in effects[1:]]
+        effs = tc.gpu_effects(effects, [P])
         if entry == "PEGS":
             return _flat(bwgr_amd.PEGS(Y, P, cnv_trace=True, **kw), PEGS_FLAT["PEGS"] + ("cnv_trace",), "numit")
-        if entry == "PEGSZ":
+        if entry.startswith("PEGSZ"):
             return _flat(bwgr_amd.PEGSZ(Y, effs, cnv_trace=True, **kw), PEGS_FLAT["PEGS"] + ("cnv_trace",), "numit")
         return _flat(bwgr_amd.PEGSX(Y, X, effs, cnv_trace=True, **kw), PEGS_FLAT["PEGSX"] + ("cnv_trace",), "its")
 
     def ok(g):
         case = tc.handle_case(entry)
-        if entry == "PEGSX":
+        if entry.startswith("PEGSX"):
             o = _flat(XC.restate(case)[3], PEGS_FLAT["PEGSX"], "its")
         else:
             o = PC.restate(case)[2]
@@ -430,6 +434,7 @@ ENTRIES = {
     "kernel2_GAU_device": ("slabs",) + _kernel2("GAU", 0.5, True),
     "uvbeta2": ("slabs", _uvb2, _uvb2_ok), "MEGA": ("slabs",) + _sem2("MEGA"), "GSEM": ("slabs",) + _sem2("GSEM"),
     "PEGS": ("slabs",) + _pegs("PEGS"), "PEGSZ": ("slabs",) + _pegs("PEGSZ"), "PEGSX": ("slabs",) + _pegs("PEGSX"),
+    "PEGSZ_S": ("slabs",) + _pegs("PEGSZ_S"), "PEGSX_S": ("slabs",) + _pegs("PEGSX_S"),
 }
 
 

@@ -3,7 +3,8 @@
 Every handle (panel data, panel, chain, group) and every call holds its device arrays, streams and long-lived events in one holder
 (bwgr_amd/csrc/devbufs.h); bwgr_amd.debug_live() counts what the holders of this process own.  These tests assert on those counts and on
 status codes only -- on the tpod panel (196 x 376 int8: three 128-marker blocks, one slab); the parity of the results is the other GPU
-tests' job, and the failure paths of the holder run on the CPU (test_devbufs_cpu.py)."""
+tests' job, and the failure paths of the holder run on the CPU (test_devbufs_cpu.py).  The multi-trait fits stand in both tables with a
+sparse effect beside the panel: what a call's effects own goes with the call, also when it is refused on the device after they exist."""
 import gc
 
 import numpy as np
@@ -74,6 +75,13 @@ def test_family_made_run_and_torn_down(tpod, monkeypatch):
     assert start2 == start and peak2 == peak and end2 == start, (start, peak, end, start2, peak2, end2)
 
 
+def _incidence(n, q):
+    """row r on level r mod q"""
+    A = np.zeros((n, q))
+    A[np.arange(n), np.arange(n) % q] = 1.0
+    return A
+
+
 def test_refused_call_owns_nothing_new(tpod):
     import bwgr_amd
     y, X = tpod["y"], tpod["gen"]
@@ -92,6 +100,23 @@ def test_refused_call_owns_nothing_new(tpod):
         bwgr_amd.uvbeta(rng.standard_normal((X.shape[0], 2)), P, 7, maxit=2)   # (an integer variant reaches the library)
     assert ei.value.code == EINVAL and "variant" in str(ei.value) and live() == held
     ch.close()
+    # a sparse effect beside the panel: one refusal found on the host, while the matrix is checked, and one found on the device, after the
+    # effect's arrays exist (a constant column: TrXSX = 0).  A fit that ran before them has left P whatever scratch its sweeps keep.
+    n = X.shape[0]
+    A = _incidence(n, 12)
+    Y = rng.standard_normal((n, 2))
+    assert bwgr_amd.PEGSZ(Y, [P, bwgr_amd.sparse(A)], maxit=1)["numit"] == 1
+    held = live()
+    rows, cols = np.nonzero(A.T)[::-1]
+    ptr = np.concatenate([[0], np.cumsum(A.sum(0))]).astype(np.int64)
+    dup = rows.astype(np.int32)
+    dup[1] = dup[0]
+    with pytest.raises(bwgr_amd.BwgrError) as ei:
+        bwgr_amd.PEGSZ(Y, [P, bwgr_amd.sparse((np.ones(len(dup)), dup, ptr), shape=A.shape)], maxit=2)
+    assert ei.value.code == EINVAL and live() == held, (held, live())
+    with pytest.raises(bwgr_amd.BwgrError) as ei:
+        bwgr_amd.PEGSZ(Y, [P, bwgr_amd.sparse(np.ones((n, 1)))], maxit=2)
+    assert ei.value.code == EINVAL and live() == held, (held, live())
     P.close()
     assert live() == start
 
@@ -104,6 +129,8 @@ def test_one_call_entry_points_give_back_what_they_took(tpod):
     use = np.sort(rng.choice(n, 120, replace=False))
     e = (y - y.mean()).astype(np.float32)
     xx_use = (X[use].astype(np.float64) ** 2).sum(0)
+    A, Y2 = _incidence(n, 12), rng.standard_normal((n, 2))
+    X2 = np.column_stack([np.ones(n), rng.standard_normal(n)])
     start = live()
     P = bwgr_amd.Panel(X)
     calls = {
@@ -114,6 +141,10 @@ def test_one_call_entry_points_give_back_what_they_took(tpod):
         "GRM": lambda: bwgr_amd.GRM(P),
         "KMUP2": lambda: bwgr_amd.KMUP2(P, use, np.zeros(p), np.ones(p), xx_use, e, np.ones(p), 1.0, 0.0, seed=7, it=1),
         "wgr": lambda: bwgr_amd.wgr(y, P, it=6, bi=2, bag=0.8, seed=8),
+        # the multi-trait fits with a sparse effect: its arrays (both copies of the matrix, XX, XSX, tilde, b, d2, Linv, the order) are the call's
+        "PEGSZ": lambda: bwgr_amd.PEGSZ(Y2, [P, bwgr_amd.sparse(A)], maxit=2),
+        "PEGSX": lambda: bwgr_amd.PEGSX(Y2, X2, [P, bwgr_amd.sparse(A)], maxit=2),
+        "PEGS_sparse": lambda: bwgr_amd.PEGS_sparse(Y2, A, maxit=2),      # (no panel: nothing is kept)
     }
     # The calls that do not sweep on P itself give everything back the first time.  A sweep on P may leave the PANEL arrays that it keeps (the
     # scratch that comes with the first sweep that needs it: never a stream or an event here, where P is not alone in a chain of its own), so
@@ -122,7 +153,7 @@ def test_one_call_entry_points_give_back_what_they_took(tpod):
         before = live()
         call()
         first = live()
-        if name in ("emRR", "mrr", "uvbeta", "GRM"):
+        if name in ("emRR", "mrr", "uvbeta", "GRM", "PEGS_sparse"):
             assert first == before, (name, before, first)
         assert first[0] >= before[0] and first[1:] == before[1:], (name, before, first)
         call()

@@ -4,9 +4,16 @@ them sits on a discontinuous branch) -- then the same numbers through the dense 
 PEGSZ_sparse's text against PEGSZ's, determinism, an empty column, the refusals and mrr's own results around them, and the effect order.
 
 Parity: pegs_restatement.scaled_err <= 1e-6 on every output, equal sweep counts with logtol = -inf.  Every test prints what it measured.
-Largest errors measured on an MI355X: parity 3.5e-13 (bend of the q = 1 case, which bends in every sweep), 1.2e-13 on cnv, at most 1.4e-14
-on every other figure; sparse(S) against dense(S.toarray()) 3.9e-14 (cnv; TrZSZ 1.2e-16); the disjoint leg against the serial leg and a run
-against its repeat: the same bits; PEGSZ_sparse's mu against PEGSZ's on the same data: 1.1e-4 apart."""
+Largest errors measured on an MI355X: parity 3.5e-13 (bend of the q = 1 case, which bends in every sweep), 2.1e-13 on cnv (the case of
+32 805 columns; 1.2e-13 before it), at most 3.0e-14 on every other figure (vb_list at f = 256; 1.9e-14 on bend at f = 70, k = 16);
+sparse(S) against dense(S.toarray()) 3.9e-14 (cnv; 2.8e-14 on bend at f = 70; TrZSZ 2.1e-16); TrZSZ alone at the cap of the sparse trace's
+grid 1.3e-16; the disjoint leg against the serial leg and a run against its repeat: the same bits; PEGSZ_sparse's mu against PEGSZ's on the
+same data: 1.1e-4 apart.
+
+The second round of cases (tests/pegs_sparse_cases.py, from ps_setup_trip_k3 on) runs through the same tests: a second trip of the set-up
+kernel and a third of the d2 reduction, the sparse trace at 1 024 workgroups and five trips (also alone, maxit = 0), f = 70 with sixteen
+patterns and f = 256, columns of three lane strides that share rows on the serial leg at k = 16, a weighted row-disjoint matrix on the
+disjoint leg, and a level whose rows have no record (test_level_without_a_record_keeps_b_zero_and_hat_at_mu)."""
 import os
 import sys
 
@@ -52,7 +59,9 @@ def test_parity(case):
 
 
 LEGS = ("ps_inc12_k3", "ps_inc70_k3", "ps_trip_k3", "ps_long_cols_k3", "ps_overlap_k3", "pzs_inc_overlap_k5_xfa2", "pz_mixed4_k3", "px_inc12_k3",
-        "px_overlap_k1", "px_mixed4_k3_xfa2")
+        "px_overlap_k1", "px_mixed4_k3_xfa2",
+        # the second round: the wide ones (dense copies of 79 MB and 40 MB), the long columns, f = 70 with sixteen patterns and f = 256
+        "ps_setup_trip_k3", "px_trace_cap_k3", "ps_overlap_long_k16", "pzs_inc_overlap_long_k3", "px_f70_k16", "px_f256_k3")
 
 
 @pytest.mark.parametrize("cid", LEGS)
@@ -113,7 +122,8 @@ def test_text2_differs_from_text0_in_mu_and_each_matches_its_restatement():
     assert np.array_equal(g2b["hat"], g2["hat"]) and np.array_equal(g2b["mu"], g2["mu"])
 
 
-@pytest.mark.parametrize("cid", ["ps_trip_k3", "ps_overlap_k3", "pz_mixed4_k3", "px_mixed4_k3_xfa2"])
+@pytest.mark.parametrize("cid", ["ps_trip_k3", "ps_overlap_k3", "pz_mixed4_k3", "px_mixed4_k3_xfa2", "ps_setup_trip_k3", "px_trace_cap_k3", "px_f70_k16",
+                                 "px_f256_k3", "ps_overlap_long_k16", "pzs_inc_overlap_long_k3", "ps_weighted_k3", "ps_unobserved_level_k3"])
 def test_two_runs_are_bit_identical(cid):
     case = SC.by_id(cid)
     _same(case, SC.run(case), SC.run(case))
@@ -129,6 +139,38 @@ def test_empty_column_keeps_b_zero():
     trip = SC.run(SC.by_id("ps_trip_k3"))           # and the thousands of empty levels of the two-trip case
     T = SC.design(SC.by_id("ps_trip_k3")["data"]()[1][0])
     assert np.all(trip["b"][(T != 0).sum(0) == 0] == 0.0)
+
+
+@pytest.mark.parametrize("cid", SC.TRZSZ_ALONE)
+def test_trzsz_alone(cid):
+    """maxit = 0: k_pegsx_trace_sparse apart from the sweeps, at the cap of its grid (1 024 workgroups, five trips, one column in the last
+    workgroup of the last), as tests/test_gpu_tall.py's test_pegsx_trzsz_alone for the panel and dense kernels; and through the dense kernel"""
+    case = SC.by_id(cid)
+    _, o = SC.restate(case, maxit=0)
+    g, d = SC.run(case, maxit=0), SC.run(case, how="dense", maxit=0)
+    err = max(PR.scaled_err(a, b) for a, b in zip(g["TrZSZ"], o["TrZSZ"]))
+    between = max(PR.scaled_err(a, b) for a, b in zip(g["TrZSZ"], d["TrZSZ"]))
+    print(cid, "TrZSZ alone %.2e, sparse against dense %.2e" % (err, between))
+    assert g["its"] == o["its"] == 0 and g["cnv"] == 10.0 and err <= TOL and between <= TOL
+    assert all(np.all(u == 0) for u in g["u"]) and PR.scaled_err(g["b"], o["b"]) <= TOL and PR.scaled_err(g["hat"], o["hat"]) <= TOL
+
+
+def test_level_without_a_record_keeps_b_zero_and_hat_at_mu():
+    """a column with stored entries whose rows have no record in any trait: XX_jt = 0 for every t, so Linv_j is the inverse of iG alone and
+    the dots are sums of zeros -- b_j is exactly 0 on both legs, and with one effect hat on those rows is mu to the bit"""
+    case = SC.by_id("ps_unobserved_level_k3")
+    Y, effects = case["data"]()
+    A = SC.design(effects[0])
+    j = SC.unobserved_column(A, Y)
+    rows = np.flatnonzero(A[:, j])
+    records = (A != 0).T.astype(int) @ (~np.isnan(Y)).astype(int)              # per level and trait (one trait misses another whole level)
+    assert np.all(records[j] == 0) and (records[np.arange(A.shape[1]) != j] > 0).any(1).all()
+    for serial in (False, True):
+        g = SC.run(case, serial=serial)
+        assert np.all(g["b"][j] == 0.0) and np.all(g["b"][records > 0] != 0.0)
+        assert np.array_equal(g["hat"][rows], np.tile(g["mu"], (len(rows), 1)))
+        others = np.flatnonzero(np.isnan(Y).all(1) & (A[:, j] == 0))           # (rows without a record on observed levels get that level's b)
+        assert len(others) and not np.array_equal(g["hat"][others], np.tile(g["mu"], (len(others), 1)))
 
 
 def test_refusals_leave_the_panel_usable():

@@ -12,7 +12,12 @@ uncentred launch train where the reductions take further trips and on the other 
 further than it would alone (tall9k, in both orders), row loops of nine and five trips at 1 024 threads, f = 17 and f = 256.
 Largest scaled error measured over these jobs on an MI355X: 9.9e-14 (`bend` of PEGSX on tall9k; 9.5e-14 on `vb_list` at f = 256, 5.6e-14 on
 `bend` of PEGS and PEGSZ on wide33k), at most 3.5e-14 on every other figure; TrZSZ alone at most 3.5e-14 (f = 256); the normal equations
-5.8e-17 and 2.0e-17 of ||M_t|| ||y_t|| (bar 1e-9)."""
+5.8e-17 and 2.0e-17 of ||M_t|| ||y_t|| (bar 1e-9).
+
+tall9k_sparse and slab1280_sparse put sparse effects beside those panels (ld 216 and 120 rows past n, R = 256 and 1 280, a level of more
+than 4 096 rows across slab edges, 36 and 20 workgroups of k_pegs_sparse_hat), under PEGSZ, PEGSX and, on slab1280, PEGSZ_sparse's text.
+Measured: 3.5e-13 (`b` of PEGSZ on tall9k_sparse), 1.2e-13 and 1.1e-13 (`vb_list` and `bend` of PEGSX there), at most 6.4e-14 on every other
+figure; the normal equations 5.3e-17 and 3.9e-17."""
 import ctypes as C
 import functools
 import os
@@ -363,15 +368,15 @@ def test_two_design_drivers_with_the_references_defaults_on_a_tall_panel(panel, 
 # ---- PEGS / PEGSZ / PEGSX ----
 class _Effects:
     """a job's effects as the entries take them: the module's shared Panel where the job's shape is on the table, a Panel of its own (closed
-    on exit) for the 700 x 900 three-slab panel, dense(Z) for a dense effect"""
+    on exit) for the 700 x 900 three-slab panel, dense(Z) for a dense effect, sparse(S) in CSC for a sparse one"""
 
     def __init__(self, panel, case, effects):
         import bwgr_amd
         tag = tc.PEGS_JOBS[case["job"]]["tag"]
         self.own, self.effs = [], []
         for e in effects:
-            if e[0] == "dense":
-                self.effs.append(bwgr_amd.dense(e[1]))
+            if e[0] != "panel":
+                self.effs.extend(tc.gpu_effects([e], []))
             elif tag in tc.CASES:
                 self.effs.append(panel(tag))
             else:
@@ -391,8 +396,8 @@ def _pegs_job(panel, entry, job):
     case = tc.pegs_case(entry, job)
     Y, effects, o = PC.restate(case)
     with _Effects(panel, case, effects) as effs:
-        g = bwgr_amd.PEGS(Y, effs[0], **case["kw"]) if entry == "PEGS" else bwgr_amd.PEGSZ(Y, effs, **case["kw"])
-    errs = _pegs_errs(g, o, entry)
+        g = bwgr_amd.PEGS(Y, effs[0], **case["kw"]) if entry == "PEGS" else getattr(bwgr_amd, entry)(Y, effs, **case["kw"])
+    errs = _pegs_errs(g, o, "PEGS" if entry == "PEGS" else "PEGSZ")
     print(entry, job, "numit", g["numit"], {k: "%.2e" % v for k, v in errs.items()}, "largest %.2e" % max(errs.values()))
     assert g["numit"] == o["numit"] == case["kw"]["maxit"]
     assert all(v <= TOL for v in errs.values()), errs
@@ -409,6 +414,12 @@ def test_pegs(panel, job):
 @pytest.mark.parametrize("job", tc.pegs_jobs("PEGSZ"))
 def test_pegsz(panel, job):
     _pegs_job(panel, "PEGSZ", job)
+
+
+@pytest.mark.parametrize("job", tc.pegs_jobs("PEGSZ_sparse"))
+def test_pegsz_sparse(panel, job):
+    """text 2 beside a panel: the intercept step of PEGSZ_sparse on a residual of the panel's stride"""
+    _pegs_job(panel, "PEGSZ_sparse", job)
 
 
 @pytest.mark.parametrize("job", tc.pegs_jobs("PEGSX"))

@@ -114,17 +114,22 @@ def test_case_is_away_from_the_discontinuous_branches(case):
             assert np.all(np.isfinite(a)), key
 
 
+SECOND_ROUND = ("ps_setup_trip_k3", "px_trace_cap_k3", "px_f70_k16", "px_f256_k3", "ps_overlap_long_k16", "pzs_inc_overlap_long_k3", "ps_weighted_k3",
+                "ps_unobserved_level_k3")
+
+
 def test_case_table_covers_what_the_gpu_tests_promise():
     import bwgr_amd
     ids = [c["id"] for c in SC.CASES]
-    assert len(set(ids)) == len(ids) and set(SC.DISJOINT) <= set(ids)
+    assert len(set(ids)) == len(ids) and set(SC.DISJOINT) <= set(ids) and set(SECOND_ROUND) <= set(ids) and set(SC.TRZSZ_ALONE) <= set(ids)
     ks, xfas, entries, qs, colmax = set(), set(), set(), set(), 0
     for c in SC.CASES:
         data = c["data"]()
         Y, effects = data[0], data[1]
         n, k = Y.shape
         ks.add(k); xfas.add(c["kw"].get("XFA", -1)); entries.add(c["entry"])
-        assert 6 <= c["kw"]["maxit"] <= 8 and c["kw"]["logtol"] == SC.NOSTOP
+        # (the cases of the second round run fewer sweeps: their restatements are the wide and the long ones)
+        assert (2 if c["id"] in SECOND_ROUND else 6) <= c["kw"]["maxit"] <= 8 and c["kw"]["logtol"] == SC.NOSTOP
         assert n % 64 != 0 and 0.15 < np.isnan(Y).mean() < 0.3 and np.isnan(Y).all(1).sum() >= 3
         sp = [e for e in effects if e[0] == "sparse"]
         assert sp and all(np.array_equal(SR.f32(e[1]), e[1]) for e in sp)
@@ -147,6 +152,88 @@ def test_case_table_covers_what_the_gpu_tests_promise():
     assert 0.06 < stored.mean() < 0.1 and (stored & (A == 0)).sum() > 0 and (A < 0).any()
     kinds = [[e[0] for e in c["data"]()[1]] for c in SC.CASES]
     assert ["panel", "sparse"] in kinds and ["panel", "sparse", "sparse", "dense"] in kinds and ["sparse", "sparse"] in kinds
+
+
+def _ceil(a, b):
+    return -(-a // b)
+
+
+def _sparse_effect(cid, i=0):
+    """(case, data, A, stored mask, the sparse plan) of effect i of a case"""
+    import bwgr_amd
+    case = SC.by_id(cid)
+    data = case["data"]()
+    e = data[1][i]
+    A = e[1]
+    stored = e[2] if len(e) > 2 else A != 0
+    pl = bwgr_amd.pegs_sparse_plan(A.shape[0], A.shape[1], int(stored.sum()), int(stored.sum(0).max()), data[0].shape[1], SR.row_disjoint(A))
+    return case, data, A, stored, pl
+
+
+def test_second_round_cases_reach_what_they_are_listed_for():
+    """Each case of the second round against the library's own host arithmetic (bwgr_debug_pegs_sparse_plan, bwgr_debug_pegs_launch_plan,
+    bwgr_debug_pegsx_plan, bwgr_debug_launch_plan): a case that stops reaching its edge after a later plan change fails here.  The sparse trace
+    kernel runs on the trace grid of the launch plan with ONE column per wave, four per workgroup and trip (csrc/pegs_sparse.hip.h)."""
+    import bwgr_amd
+    import tall_cases as tc
+    # ps_setup_trip_k3: two trips of the set-up kernel, every column of the second occupied; three of k_mrr_tilde over d2; nine of the disjoint leg
+    case, data, A, stored, pl = _sparse_effect("ps_setup_trip_k3")
+    n, q = A.shape
+    per_trip = pl["setup_wg"] * (pl["setup_threads"] // 64)
+    assert (n, q) == (SC.N, SC.SETUP_TRIP_COLS + 37) and pl["setup_wg"] == 8192 and per_trip == SC.SETUP_TRIP_COLS and _ceil(q, per_trip) == 2
+    assert (stored.sum(0)[per_trip:] == 1).all() and stored[:, q - 1].sum() == 1 and SR.row_disjoint(A) and stored.sum() == n
+    rc, lp = tc.launch_plan(n, _ceil(n, 128) * 128, q, 3)
+    assert rc == 0 and _ceil(q, lp["mrr_np"] * 256) == 3 and (stored.sum(0)[2 * lp["mrr_np"] * 256:] == 1).all()
+    assert pl["leg"] == "disjoint" and pl["disjoint_wg"] == 1024 and _ceil(q, pl["trip_cols"]) == 9
+    assert not set(np.flatnonzero(stored[:, q - 40:].any(1))) & {7, n // 2, n - 1}     # (the placed rows are none of those without any record)
+    assert A.nbytes <= 100e6                                                           # (the dense copy of the legs test)
+    # px_trace_cap_k3: the trace grid at its cap, five trips of 4 096 columns, the last workgroup of the last trip with one column
+    case, data, A, stored, pl = _sparse_effect("px_trace_cap_k3")
+    n, q = A.shape
+    gp = bwgr_amd.pegs_launch_plan(n, q)
+    assert q == 16501 and gp["trace_wg"] == 1024 and _ceil(q, gp["trace_wg"] * 4) == 5 and q % (gp["trace_wg"] * 4) == 117 and q % 4 == 1
+    assert stored[:, q - 1].sum() == 1 and (stored.sum(0)[4 * 4096:] > 0).sum() >= 40 and data[2].shape[1] == 3 and case["id"] in SC.TRZSZ_ALONE
+    assert pl["leg"] == "disjoint" and _ceil(q, pl["trip_cols"]) == 5 and pl["setup_wg"] == _ceil(q, 4)
+    # px_f70_k16: a second step of the trace's lane loops, sixteen patterns, k = 16 on both legs
+    case, data, A, stored, pl = _sparse_effect("px_f70_k16")
+    Y, X = data[0], data[2]
+    f, k = X.shape[1], Y.shape[1]
+    xp = bwgr_amd.pegsx_plan(SC.N, f, k)
+    assert (f, k) == (70, 16) and _ceil(f, 64) == 2 and len({np.isnan(Y[:, t]).tobytes() for t in range(k)}) == 16
+    assert xp["trace_lds_bytes"] == 8 * (4 * xp["jc"] * f + 4 * 16) and np.array_equal(X, SR.f32(X)) and (X[:, 0] == 1).all()
+    assert A.shape == (SC.N, 70) and pl["leg"] == "disjoint" and _sparse_effect("px_f70_k16", 1)[4]["leg"] == "serial"
+    assert ((~np.isnan(Y)).sum(0) > f).all()
+    # px_f256_k3: f at the cap, four steps, the whole of a wave's region of LDS; more records per trait than columns in X
+    case, data, A, stored, pl = _sparse_effect("px_f256_k3")
+    Y, X = data[0], data[2]
+    xp = bwgr_amd.pegsx_plan(SC.N2, 256, 3)
+    assert X.shape == (SC.N2, 256) == (700, 256) and _ceil(256, 64) == 4 and xp["trace_lds_bytes"] == 33280 <= 64 * 1024
+    assert ((~np.isnan(Y)).sum(0) >= 256 + 200).all() and np.linalg.matrix_rank(X[~np.isnan(Y).any(1)]) == 256
+    assert np.array_equal(X, tc.XC.fixed(SC.N2, 255, 501))                             # (as tall_cases' f256 job builds it)
+    assert A.shape == (700, 12) and pl["leg"] == "disjoint" and _sparse_effect("px_f256_k3", 1)[4]["leg"] == "serial"
+    assert _ceil(SC.N2, 256) == 3                                                      # (workgroups of k_pegs_sparse_hat)
+    # ps_overlap_long_k16: every column three lane strides long, more columns than a wave has lanes, rows shared, k = 16
+    case, data, A, stored, pl = _sparse_effect("ps_overlap_long_k16")
+    assert A.shape == (700, 130) and stored.sum(0).min() > 128 and stored.sum(0).max() <= 256 and A.shape[1] > 64 and data[0].shape[1] == 16
+    assert pl["leg"] == "serial" and (pl["serial_threads"], pl["serial_wg"]) == (64, 1) and case["kw"]["XFA"] == 2
+    assert 0.2 < stored.mean() < 0.3 and (stored & (A == 0)).sum() == 7 and (A < 0).any()
+    # consecutive columns share rows whose entries lie in different lane strides of the two columns
+    r0, r1 = np.flatnonzero(stored[:, 0]), np.flatnonzero(stored[:, 1])
+    both = np.intersect1d(r0, r1)
+    assert any(np.searchsorted(r0, r) // 64 >= 1 and np.searchsorted(r0, r) % 64 != np.searchsorted(r1, r) % 64 for r in both)
+    case2, data2, A2, stored2, pl2 = _sparse_effect("pzs_inc_overlap_long_k3", 1)
+    assert np.array_equal(A2, A) and np.array_equal(stored2, stored) and data2[0].shape[1] == 3 and pl2["leg"] == "serial"
+    assert data2[1][0][1].shape == (700, 12) and case2["entry"] == "PEGSZ_sparse"
+    # ps_weighted_k3: row-disjoint, and no incidence
+    case, data, A, stored, pl = _sparse_effect("ps_weighted_k3")
+    v = A[stored]
+    assert pl["leg"] == "disjoint" and SR.row_disjoint(A) and stored.sum(1).max() == 1 and A.shape == (SC.N, 12)
+    assert (v < 0).sum() > 50 and (v == 0).sum() == 5 and (v != np.round(v)).sum() > 250 and np.array_equal(A, SR.f32(A))
+    # ps_unobserved_level_k3: stored entries, and no record under them in any trait
+    case, data, A, stored, pl = _sparse_effect("ps_unobserved_level_k3")
+    j = SC.unobserved_column(A, data[0])
+    assert list(np.flatnonzero(A[:, j])) == [7, SC.N // 2, SC.N - 1] and np.isnan(data[0][A[:, j] != 0]).all() and pl["leg"] == "disjoint"
+    assert ((A != 0).sum(0) > 0).all() and len(data[1]) == 1
 
 
 # ---- the plan hook ----

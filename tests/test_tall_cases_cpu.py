@@ -133,7 +133,7 @@ def test_the_old_shapes_did_not_reach_them():
 
 
 # ---- PEGS / PEGSZ / PEGSX ----
-PEGS_RUNS = [(entry, job) for entry in ("PEGS", "PEGSZ", "PEGSX") for job in tc.pegs_jobs(entry)]
+PEGS_RUNS = [(entry, job) for entry in ("PEGS", "PEGSZ", "PEGSX", "PEGSZ_sparse") for job in tc.pegs_jobs(entry)]
 
 
 def test_pegs_launch_plan_is_the_documented_rule():
@@ -202,13 +202,47 @@ def test_pegs_traits_miss_what_they_say():
         assert Y.shape[1] == k and len({np.isnan(Y[:, t]).tobytes() for t in range(k)}) == k == tc.pegs_plans(job)["npat"]
         rows = tc.PEGS_MISSING.get(j["tag"], ())
         assert np.isnan(Y[list(rows)]).all() and int(np.isnan(Y[:, 1]).sum()) == len(rows)      # (trait 1 misses nothing else)
-        assert [e[0] for e in effects] == ["panel" if e == "panel" else "dense" for e in j["effects"]]
+        assert [e[0] for e in effects] == ["panel" if e == "panel" else "sparse" if isinstance(e, tuple) else "dense" for e in j["effects"]]
         if j["tag"] in tc.PEGS_MISSING:
             R = tc.pegs_plans(job)["R"]
             assert any(r % R == 0 and r > 0 for r in rows) and any((r + 1) % R == 0 for r in rows)
     rows = tc.PEGS_MISSING["tall9k"]
     assert {4096, 4097, 4098, 4099} <= set(rows) and 4096 % 256 == 0 and 4096 % 4 == 0
     assert np.isnan(tc.pegs_case("PEGSX", "tall9k")["data"]()[0][4096:4100]).all()
+
+
+def test_sparse_jobs_put_the_sparse_kernels_beside_tall_and_other_slab_panels():
+    """tall9k_sparse and slab1280_sparse: the residual's stride is the panel's ld, far from n and on slabs of 256 and of 1 280 rows; a level
+    longer than 4 096 rows that spans slab edges, two rows on both sides of an edge on one level, all-missing rows on both sides of an edge
+    inside a level; both legs; more workgroups of k_pegs_sparse_hat than any case of tests/pegs_sparse_cases.py has (nine at n = 2 100)."""
+    from pegs_sparse_cases import SR
+    J = tc.PEGS_JOBS
+    jobs = [job for job in J if any(isinstance(e, tuple) for e in J[job]["effects"])]
+    assert jobs == ["tall9k_sparse", "slab1280_sparse"]
+    pls = {job: tc.pegs_plans(job) for job in jobs}
+    assert {pls[j]["R"] for j in jobs} == {256, 1280} and all(pls[j]["K"] > 1 and pls[j]["pad"] >= 120 and pls[j]["sparse_hat"] > 9 for j in jobs)
+    assert {leg for j in jobs for leg in pls[j]["sparse_legs"]} == {"disjoint", "serial"}
+    assert "PEGSZ_sparse" in J["slab1280_sparse"]["entries"] and all({"PEGSZ", "PEGSX"} <= set(J[j]["entries"]) for j in jobs)
+    for job in jobs:
+        Y, effects = tc.pegs_data(job)
+        R, n = pls[job]["R"], Y.shape[0]
+        rows = tc.PEGS_MISSING[J[job]["tag"]]
+        assert np.isnan(Y[list(rows)]).all()
+        for e in effects[1:]:
+            assert e[0] == "sparse" and e[1].shape[0] == n and np.array_equal(e[1], SR.f32(e[1]))
+        inc = effects[1][1]
+        assert SR.row_disjoint(inc) and (inc.sum(1) == 1).all() and (inc.sum(0) > 0).all()
+        edge = [r for r in rows if r % R == 0 and r > 0][0]
+        assert edge - 1 in rows                                                # all-missing rows on both sides of a slab edge ...
+        lev = inc.argmax(1)
+        big = int(np.argmax(inc.sum(0)))
+        assert len({r // R for r in np.flatnonzero(lev == big)}) == pls[job]["K"]      # ... and the largest level has rows in every slab
+    Y, effects = tc.pegs_data("tall9k_sparse")
+    inc = effects[1][1]
+    a, b = tc.SAME_LEVEL["tall9k_sparse"]
+    assert inc.shape[1] == 2 and inc.sum(0).max() > 4096 and (a + 1) % 256 == 0 and b == a + 1 and np.array_equal(inc[a], inc[b])
+    assert not SR.row_disjoint(effects[2][1]) and effects[2][1].shape[1] == 30 and 0.04 < effects[2][2].mean() < 0.06
+    assert tc.pegs_data("slab1280_sparse")[1][1][1].shape[1] == 40
 
 
 @pytest.mark.parametrize("entry,job", PEGS_RUNS, ids=["%s-%s" % r for r in PEGS_RUNS])
@@ -235,9 +269,15 @@ def test_pegs_job_is_away_from_the_discontinuous_branches(entry, job):
 
 @pytest.mark.parametrize("entry", tc.HANDLE_ENTRIES)
 def test_handle_table_pegs_calls_are_away_from_the_discontinuous_branches(entry):
-    """the same guards on the inputs of tests/test_gpu_handles.py's PEGS, PEGSZ and PEGSX entries and of its two-panel PEGSZ call"""
+    """the same guards on the inputs of tests/test_gpu_handles.py's PEGS, PEGSZ and PEGSX entries, of its two-panel PEGSZ call and of the two
+    entries with sparse effects"""
     case = tc.handle_case(entry)
-    (TXC if entry == "PEGSX" else TPC).test_case_is_away_from_the_discontinuous_branches(case)
+    (TXC if entry.startswith("PEGSX") else TPC).test_case_is_away_from_the_discontinuous_branches(case)
+    if entry.endswith("_S"):
+        effects = case["data"]()[-1]
+        assert [e[0] for e in effects] == ["panel", "sparse", "sparse"] and [e[1].shape for e in effects] == [(700, 900), (700, 12), (700, 25)]
+        assert tc.SC.SR.row_disjoint(effects[1][1]) and not tc.SC.SR.row_disjoint(effects[2][1])        # both legs
+        assert entry != "PEGSX_S" or case["data"]()[1].shape == (700, 3)
 
 
 def test_the_old_pegs_cases_did_not_reach_them():
