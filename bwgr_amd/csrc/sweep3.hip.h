@@ -631,8 +631,8 @@ __device__ __forceinline__ void s3_streamer_dma(const Sweep3Args &A) {
   const uint32_t tile_la = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) const unsigned char *)smem);
   int8_t *edig0 = reinterpret_cast<int8_t *>(smem + off); off += (size_t)2 * 16 * Rp;     // [parity][n][row]
   int8_t *ddig0 = reinterpret_cast<int8_t *>(smem + off); off += (size_t)2 * 16 * S2_DP;  // [parity][n][marker]
-  int *outu = reinterpret_cast<int *>(smem + off); off += (size_t)64 * S3_OS * 4 * 4;     // [update wave][row 64][n]
-  off += (size_t)8 * 32 * S3_OS * 4;                                                    // (unused [wave][marker 32][n] scratch: kept, the layout and the LDS sizes count it)
+  off += (size_t)64 * S3_OS * 4 * 4;                                                    // (unused [update wave][row 64][n] scratch: kept, like the next, the layout and the LDS sizes count it)
+  off += (size_t)8 * 32 * S3_OS * 4;                                                    // (unused [wave][marker 32][n] scratch)
   uint32_t *ctl_s = reinterpret_cast<uint32_t *>(smem + off); off += 64;                 // [0] failure, [1] overflow
   float *drej_s = reinterpret_cast<float *>(smem + off);                                 // [block % NTB][marker]: the blocks' rejected steps, landed by DMA with the tiles
   const uint32_t drej_la = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) const unsigned char *)drej_s);
@@ -866,16 +866,17 @@ __device__ __forceinline__ void s3_streamer_dma(const Sweep3Args &A) {
     S3ST(7, st_u || st_d);
     S3ST(4, st_u || st_d);
     if constexpr (UPD) {
-      // ---- slab update with the rejected steps: out[row][n] = sum_markers x[row][marker] * digit_n(drej[marker]) ----
-      // lane (m16, grp): row quad 16 wave + m16 (rows 4 * that + k for accumulator k); k slots (dword u, byte q) of step s0 are the
-      // markers s0 + 16 u + 4 grp + q (the interleave keeps the four lane groups on different LDS banks)
-      // The A operand is x[row][marker] with the markers as the MFMA's k, and the tile is [marker][row]: gfx950's transposing LDS read
+      // ---- slab update with the rejected steps: out[n][row] = sum_markers digit_n(drej[marker]) * x[row][marker] ----
+      // The genotype operand is x[row][marker] with the markers as the MFMA's k, and the tile is [marker][row]: gfx950's transposing LDS read
       // (ds_read_b64_tr_b8: per sixteen lanes a block of 8 LDS rows x 16 bytes; lane 2 q + p supplies the address of row q, bytes 8 p .. 8 p + 7;
       // lane i receives byte i of the eight rows) hands lane (m16, grp) row m16 of a 16-row chunk for eight markers at once -- two reads per
       // operand instead of sixteen dword reads and thirty-two byte permutes.  Accumulator k holds rows 64 wave + 16 k + m16 (chunk 4 wave + k of a
       // marker's bytes, at position chunk ^ (marker & 7) in the swizzled tile); the k slots (lane group grp, byte t of the operand) are the markers
-      // s0 + 16 grp + t, and the B operand -- the steps' digits -- is read in the same order (one b128 read).  EXEC is all ones here (a wave-uniform
-      // branch): the gather crosses lanes.
+      // s0 + 16 grp + t, and the other operand -- the steps' digits -- is read in the same order (one b128 read).  EXEC is all ones here (a
+      // wave-uniform branch): the gather crosses lanes.
+      // Digits as the A operand, genotypes as B (the two have the same lane layout), as in the dots: the output tile is [digit][row], lane (row
+      // m16, group grp) holds digits 4 grp .. 4 grp + 3 of row 16 k + m16 in accumulator k, and a row's two words are formed in registers (the
+      // other order left a row's digits in seven lanes: sixteen LDS writes, a wait, two b128 reads and a wait on the step's chain).
       s2_v4i acc0 = {0, 0, 0, 0}, acc1 = acc0, acc2 = acc0, acc3 = acc0;
       const uint32_t tile_lds = tile_la + (uint32_t)((b % NTB) * (int)tile_b);
       const uint32_t q8 = (uint32_t)((lane & 15) >> 1), p8 = (uint32_t)(lane & 1);
@@ -897,27 +898,30 @@ __device__ __forceinline__ void s3_streamer_dma(const Sweep3Args &A) {
                      : "v"(a0), "v"(a1), "v"(a2), "v"(a3) : "memory");
         static_assert(R3 == 128, "offset:1024 = eight markers of 128 bytes");
         const s2_v4i bv = *reinterpret_cast<const s2_v4i *>(ddig + (size_t)m16 * S2_DP + s0 + 16 * grp);
-        acc0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(s2_v4i{x0[0], x0[1], y0[0], y0[1]}, bv, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(s2_v4i{x1[0], x1[1], y1[0], y1[1]}, bv, acc1, 0, 0, 0);
-        acc2 = __builtin_amdgcn_mfma_i32_16x16x64_i8(s2_v4i{x2[0], x2[1], y2[0], y2[1]}, bv, acc2, 0, 0, 0);
-        acc3 = __builtin_amdgcn_mfma_i32_16x16x64_i8(s2_v4i{x3[0], x3[1], y3[0], y3[1]}, bv, acc3, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(bv, s2_v4i{x0[0], x0[1], y0[0], y0[1]}, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(bv, s2_v4i{x1[0], x1[1], y1[0], y1[1]}, acc1, 0, 0, 0);
+        acc2 = __builtin_amdgcn_mfma_i32_16x16x64_i8(bv, s2_v4i{x2[0], x2[1], y2[0], y2[1]}, acc2, 0, 0, 0);
+        acc3 = __builtin_amdgcn_mfma_i32_16x16x64_i8(bv, s2_v4i{x3[0], x3[1], y3[0], y3[1]}, acc3, 0, 0, 0);
       }
-      int *ou = outu + (size_t)wave * 64 * S3_OS;
-      if (m16 < 8) {      // lane: digit n = m16; acc_k[reg] belongs to local row 16 k + 4 grp + reg
-        int *op = ou + (size_t)(4 * grp) * S3_OS + m16;
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          op[(reg + 0) * S3_OS] = acc0[reg]; op[(reg + 16) * S3_OS] = acc1[reg];
-          op[(reg + 32) * S3_OS] = acc2[reg]; op[(reg + 48) * S3_OS] = acc3[reg];
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the wave's own LDS writes (in order; no other wave reads this scratch)
       {
-        const int4 o0 = *reinterpret_cast<const int4 *>(ou + (size_t)lane * S3_OS);
-        const int4 o1 = *reinterpret_cast<const int4 *>(ou + (size_t)lane * S3_OS + 4);
-        long long v = (long long)o0.x + ((long long)o0.y << 8) + ((long long)o0.z << 16) + ((long long)o0.w << 24);
-        v += ((long long)o1.x << 32) + ((long long)o1.y << 40) + ((long long)o1.z << 48);
-        e_own -= v;
+        // word grp of row 16 k + m16 in every lane: digits 0-3 (group 0, weight 1) or 4-6 (group 1, weight 2^32: only its low dword counts mod
+        // 2^64; the digit rows 7-15 are zero).  Then a 4 x 4 transpose of (accumulator k, lane group) in registers -- v_permlane16_swap_b32 swaps
+        // the odd 16-lane rows of its first operand with the even rows of its second, v_permlane32_swap_b32 the upper half of the first with the
+        // lower half of the second -- brings row 16 k + m16's words to lane 16 k + m16, which owns the row.
+        const long long w0 = (long long)acc0[0] + ((long long)acc0[1] << 8) + ((long long)acc0[2] << 16) + ((long long)acc0[3] << 24);
+        const long long w1 = (long long)acc1[0] + ((long long)acc1[1] << 8) + ((long long)acc1[2] << 16) + ((long long)acc1[3] << 24);
+        const long long w2 = (long long)acc2[0] + ((long long)acc2[1] << 8) + ((long long)acc2[2] << 16) + ((long long)acc2[3] << 24);
+        const long long w3 = (long long)acc3[0] + ((long long)acc3[1] << 8) + ((long long)acc3[2] << 16) + ((long long)acc3[3] << 24);
+        typedef unsigned s3_v2u __attribute__((ext_vector_type(2)));
+        // ([0]: lane groups (k g0, k + 1 g0, k g2, k + 1 g2) of the pair's low dwords; [1]: (k g1, k + 1 g1, k g3, k + 1 g3))
+        const s3_v2u l01 = __builtin_amdgcn_permlane16_swap((unsigned)w0, (unsigned)w1, false, false);
+        const s3_v2u l23 = __builtin_amdgcn_permlane16_swap((unsigned)w2, (unsigned)w3, false, false);
+        const s3_v2u h01 = __builtin_amdgcn_permlane16_swap((unsigned)((unsigned long long)w0 >> 32), (unsigned)((unsigned long long)w1 >> 32), false, false);
+        const s3_v2u h23 = __builtin_amdgcn_permlane16_swap((unsigned)((unsigned long long)w2 >> 32), (unsigned)((unsigned long long)w3 >> 32), false, false);
+        const unsigned lo_lo = __builtin_amdgcn_permlane32_swap(l01[0], l23[0], false, false)[0];   // lane group k: the low word of row 16 k + m16 (formed in group 0) ...
+        const unsigned lo_hi = __builtin_amdgcn_permlane32_swap(h01[0], h23[0], false, false)[0];
+        const unsigned hi_lo = __builtin_amdgcn_permlane32_swap(l01[1], l23[1], false, false)[0];   // ... and the low dword of its high word (formed in group 1)
+        e_own -= (long long)(((unsigned long long)(lo_hi + hi_lo) << 32) | (unsigned long long)lo_lo);
       }
       S3ST(5, st_u);
     } else if constexpr (RL == 1) {
