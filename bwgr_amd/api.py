@@ -998,8 +998,73 @@ _MRR_OPTS = ["maxit", "tol", "TH", "NLfactor", "InnerGS", "NoInv", "HCS", "XFA",
 MRR_KEYS = ("mu", "b", "hat", "h2", "GC", "vb", "ve", "MSx", "cnvB", "cnvH2", "cnvV", "b_Weights", "Its")
 
 
+def _is_device_tensor(X):
+    return type(X).__module__.split(".")[0] == "torch" and bool(getattr(X, "is_cuda", False))
+
+
+def _mrr_traits(Y, single, nrow, who):
+    Ym = np.asarray(Y, np.float64)
+    if Ym.ndim == 1:
+        Ym = Ym[:, None]
+    if single:   # MRR3F receives float matrices (src/RcppEigen20230423.cpp:704)
+        Ym = Ym.astype(np.float32).astype(np.float64)
+    if Ym.ndim != 2 or Ym.shape[0] != nrow:
+        raise BwgrError(1, "%s: Y has shape %s; nrow(Y) must equal nrow(X) = %d" % (who, Ym.shape, nrow))
+    return np.asfortranarray(Ym)
+
+
+def _mrr_opts(single, opts):
+    o = np.array([float(opts[name]) for name in _MRR_OPTS], np.float64)
+    if single:
+        o = o.astype(np.float32).astype(np.float64)
+        o[_MRR_OPTS.index("maxit")] = int(opts["maxit"])
+    return o
+
+
+def _mrr_dense(Y, D, single, opts, kw):
+    """bwgr_mrr_dense: the design is dense(X) -- n x r float64 values on the host, or a torch tensor on the device, which stays there."""
+    device = int(kw.pop("device", 0))
+    if kw:
+        raise BwgrError(1, "mrr: %s do(es) not apply to a dense design (only device=)" % sorted(kw))
+    Xd = D.device_tensor()
+    if Xd is not None:
+        import torch
+        device = Xd.device.index or 0
+        if single:
+            Xd = Xd.to(torch.float32).to(torch.float64)
+        if Xd.stride(0) != 1 or (Xd.shape[1] > 1 and Xd.stride(1) < Xd.shape[0]):
+            Xd = Xd.t().contiguous().t()
+        n, r = int(Xd.shape[0]), int(Xd.shape[1])
+        ldx = int(Xd.stride(1)) if r > 1 else n
+        torch.cuda.synchronize(Xd.device)
+        xptr, loc = C.c_void_p(Xd.data_ptr()), DEVICE
+    else:
+        Xh = D.Z
+        if single:
+            with np.errstate(over="ignore"):
+                Xh = np.asfortranarray(Xh.astype(np.float32).astype(np.float64))
+        n, r = Xh.shape
+        ldx, xptr, loc = n, Xh.ctypes.data_as(C.c_void_p), HOST
+    Yf = _mrr_traits(Y, single, n, "mrr")
+    k = Yf.shape[1]
+    o = _mrr_opts(single, opts)
+    maxit = max(int(opts["maxit"]), 0)
+    kk, rr = max(k, 1), max(r, 1)
+    mu = np.zeros(kk); b = np.zeros((rr, kk), order="F"); hat = np.zeros((max(n, 1), kk), order="F")
+    h2 = np.zeros(kk); GC = np.zeros((kk, kk), order="F"); vb = np.zeros((kk, kk), order="F"); ve = np.zeros(kk); MSx = np.zeros(kk)
+    c1 = np.zeros(max(maxit, 1)); c2 = np.zeros(max(maxit, 1)); c3 = np.zeros(max(maxit, 1)); its = C.c_int()
+    check(_lib.lib().bwgr_mrr_dense(device, xptr, loc, int(n), int(r), int(ldx), _dp(Yf), int(k), _dp(o), len(o), _dp(mu), _dp(b), _dp(hat), _dp(h2),
+                                    _dp(GC), _dp(vb), _dp(ve), _dp(MSx), _dp(c1), _dp(c2), _dp(c3), C.byref(its)))
+    n_it = int(its.value)
+    vals = (mu, b, hat, h2, GC, vb, ve, MSx, c1[:n_it].copy(), c2[:n_it].copy(), c3[:n_it].copy(), np.ones((r, k)), n_it)
+    return dict(zip(MRR_KEYS, vals))
+
+
 def _mrr(Y, X, single, opts, panel_kw):
-    """bwgr_mrr: Y is n x k (NaN = missing) or a vector (k = 1); returns the reference's list as a dict, in its order."""
+    """bwgr_mrr: Y is n x k (NaN = missing) or a vector (k = 1); returns the reference's list as a dict, in its order.  A design marked
+    dense(X) goes to bwgr_mrr_dense; nothing else does."""
+    if isinstance(X, dense):
+        return _mrr_dense(Y, X, single, opts, dict(panel_kw))
     P, own = _as_panel(X, **panel_kw)
     try:
         Ym = np.asarray(Y, np.float64)
@@ -1036,7 +1101,9 @@ def MRR3(Y, X, maxit=500, tol=10e-9, cores=1, TH=False, NLfactor=0.0, InnerGS=Fa
     """MRR3(Y, X, ...), src/RcppEigen20230423.cpp:318-700 (R/RcppExports.R:180): multi-trait ridge regression by randomized
     Gauss-Seidel; NaN in Y = missing.  list(mu, b, hat, h2, GC, vb, ve, MSx, cnvB, cnvH2, cnvV, b_Weights, Its).  `cores` is
     ignored; InnerGS, NoInv, NLfactor, PenCor, MinCor, uncorH2below, round*, bucket* and DeflateBy are refused (BWGR_EINVAL) away
-    from their defaults.  X is centred by its column means, as in the reference."""
+    from their defaults.  X is centred by its column means, as in the reference.  X is a Panel or what makes one (int8 genotypes), or
+    dense(X): any real-valued n x r design (dosages, K2X's eigenvector design), swept in fp64 by the same launch train; a plain float
+    matrix is never taken for one."""
     opts = dict(locals()); opts.pop("Y"); opts.pop("X"); opts.pop("kw"); opts.pop("cores")
     return _mrr(Y, X, False, opts, kw)
 
@@ -1062,6 +1129,63 @@ def mrr_float(Y, X, **kw):
     return MRR3F(Y, X, **kw)
 
 
+def K2X(K, MinEV=1e-8, cores=1):
+    """K2X(K, MinEV = 1e-8, cores = 1), src/RcppEigen20230423.cpp:1942-1948 (R/RcppExports.R:256): the design of a relationship matrix,
+    U[:, :NPC] diag(D[:NPC]) with U the left singular vectors and D the singular values of K in decreasing order, NPC the number of
+    D > MinEV.  For a symmetric K these are its eigenvectors and |eigenvalues|, which is how they are computed here (numpy.linalg.eigh in
+    fp64; torch.linalg.eigh when K is a torch tensor on the device, and the result stays there).  Note the reference's scaling: U times D,
+    not U times sqrt(D), so X X' = K K (not K) -- mkr therefore fits the kernel K^2.  The values are rounded to float once (the reference
+    returns a float matrix) and returned as float64, n x NPC, column-major.
+    Departure: the reference counts NPC on a float SVD, whose noise (about 1e-7 of the largest singular value) lies above MinEV, so it keeps
+    the null directions of a rank-deficient K with a negligible scale; here the count is made on the fp64 spectrum.  A K that is not
+    square, or not symmetric to 1e-6 of its largest entry, is refused.  `cores` is ignored."""
+    if _is_device_tensor(K):
+        import torch
+        Kt = K.to(torch.float64)
+        if Kt.dim() != 2 or Kt.shape[0] != Kt.shape[1]:
+            raise BwgrError(1, "K2X: K has shape %s; it must be square" % (tuple(Kt.shape),))
+        scale = float(Kt.abs().max()) if Kt.numel() else 0.0
+        if float((Kt - Kt.t()).abs().max()) > 1e-6 * scale:
+            raise BwgrError(1, "K2X: K is not symmetric (to 1e-6 of its largest entry)")
+        w, V = torch.linalg.eigh((Kt + Kt.t()) * 0.5)
+        idx = torch.argsort(w.abs(), descending=True, stable=True)
+        npc = int((w.abs() > float(MinEV)).sum())
+        idx = idx[:npc]
+        X = (V[:, idx] * w.abs()[idx]).to(torch.float32).to(torch.float64)
+        return X.t().contiguous().t()          # column-major
+    Km = np.asarray(K, np.float64)
+    if Km.ndim != 2 or Km.shape[0] != Km.shape[1]:
+        raise BwgrError(1, "K2X: K has shape %s; it must be square" % (Km.shape,))
+    if not np.all(np.isfinite(Km)):
+        raise BwgrError(1, "K2X: K has an entry that is not finite")
+    scale = float(np.abs(Km).max()) if Km.size else 0.0
+    if Km.size and float(np.abs(Km - Km.T).max()) > 1e-6 * scale:
+        raise BwgrError(1, "K2X: K is not symmetric (to 1e-6 of its largest entry)")
+    w, V = np.linalg.eigh((Km + Km.T) * 0.5)
+    aw = np.abs(w)
+    idx = np.argsort(-aw, kind="stable")
+    idx = idx[:int(np.sum(aw > float(MinEV)))]
+    with np.errstate(over="ignore"):
+        return np.asfortranarray((V[:, idx] * aw[idx]).astype(np.float32).astype(np.float64))
+
+
+def mkr(Y, K, **kw):
+    """mkr(Y, K, ...) = MRR3(Y, K2X(K), ...), R/mix.R:1275: multi-trait kernel regression.  The list is MRR3's, so `b` holds the effects of
+    K2X's eigenvector columns (their signs are the eigensolver's; mu, hat, h2, GC, vb and ve do not depend on them).  K may be a torch
+    tensor on the device (GRM(..., device_out=True)): the decomposition and the design then stay there.  device= as for mrr(Y, dense(X))."""
+    return MRR3(Y, dense(K2X(K)), **kw)
+
+
+def mrr_dense_plan(n, r, k, npat):
+    """bwgr_debug_mrr_dense_plan (host arithmetic, no GPU) of mrr(Y, dense(X)) / mkr for n rows, r columns, k traits, npat missingness
+    patterns: the padded rows, the blocks of a sweep and the last one's width, the row tiles, the grids, the solve's linv_lds and ngl, the
+    LDS bytes of the kernels and the device workspace."""
+    out = (C.c_int64 * 15)()
+    check(_lib.lib().bwgr_debug_mrr_dense_plan(int(n), int(r), int(k), int(npat), out))
+    names = ("ld", "nblk", "edge", "tiles", "pass_wg", "trips", "cols_wg", "hat_wg", "linv_lds", "ngl", "lds_gram", "lds_pass", "lds_solve", "lds_linv", "ws_bytes")
+    return dict(zip(names, [int(v) for v in out]))
+
+
 # ---- PEGS / PEGSZ: multi-trait fits over several designs (bwgr_pegs, include/bwgr.h) ----
 PEGS_KEYS = ("mu", "b", "hat", "h2", "GC", "bend", "numit", "cnv")
 
@@ -1072,12 +1196,32 @@ class dense:
     int8, as mrr stages its X), and a float matrix with a non-integer value is a dense effect."""
 
     def __init__(self, Z):
+        self._dev = None
+        if _is_device_tensor(Z):     # stays on the device (mrr / mkr read it there); a host copy is made only where .Z is asked for
+            import torch
+            Zt = Z.to(torch.float64)
+            if Zt.dim() == 1:
+                Zt = Zt[:, None]
+            if Zt.dim() != 2:
+                raise BwgrError(1, "dense: Z has shape %s; it must be n x q" % (tuple(Zt.shape),))
+            self._dev, self._Z = Zt, None
+            return
         Zm = np.asarray(Z, np.float64)
         if Zm.ndim == 1:
             Zm = Zm[:, None]
         if Zm.ndim != 2:
             raise BwgrError(1, "dense: Z has shape %s; it must be n x q" % (Zm.shape,))
-        self.Z = np.asfortranarray(Zm)
+        self._Z = np.asfortranarray(Zm)
+
+    @property
+    def Z(self):
+        if self._Z is None:
+            self._Z = np.asfortranarray(self._dev.cpu().numpy())
+        return self._Z
+
+    def device_tensor(self):
+        """the torch tensor this design was made of, where it lives on the device; else None"""
+        return self._dev
 
 
 def _is_scipy_sparse(S):

@@ -28,6 +28,7 @@
 #include "sweep2w.hip.h"
 #include "sweep3p.hip.h"
 #include "mrr.hip.h"
+#include "mrr_dense.hip.h"
 #include "uvb.hip.h"
 #include "uvbd.hip.h"
 #include "uvb2.hip.h"

@@ -1,4 +1,5 @@
-// bwgr_amd/csrc/fits_host.hip.h -- the host entries of the fp64 fits and products on a resident int8 panel: mrr, the UVBETA family with
+// bwgr_amd/csrc/fits_host.hip.h -- the host entries of the fp64 fits and products on a resident int8 panel: mrr (and mrr on a dense fp64
+// design, bwgr_mrr_dense), the UVBETA family with
 // solver2x, the dense fits, X B, and the relationship kernels.  Part of bwgr_hip.hip, which includes it after everything it uses (fail, HIPCHK,
 // DevBufs, no_memory, d2h / h2d / zero, Guard, guard_busy, and mtfit_host.hip.h); it defines no kernel.  What these entries do to Y and Z before
 // a kernel runs is traits.h.
@@ -10,13 +11,10 @@
 // The sweep itself (order .. closing pass) is mrr_sweep of mtfit_host.hip.h, and the fit's device arrays and repeated steps are MtFit's, there:
 // bwgr_mrr is a fit with one panel effect, centred.  What is left here is mrr's own algebra.
 // ------------------------------------------------------------------------------------------------
-extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opts, int nopts, double *mu_out, double *b_out, double *hat_out,
-                        double *h2_out, double *GC_out, double *vb_out, double *ve_out, double *MSx_out, double *cnvB, double *cnvH2, double *cnvV,
-                        int *its) {
-  if (!P || !Y || !b_out || !its) return fail(BWGR_EINVAL, "mrr: null pointer");
-  if (k < 1 || k > BWGR_MRR_MAXK) return fail(BWGR_EINVAL, "mrr: k = %d traits; this engine takes 1 <= k <= %d", k, BWGR_MRR_MAXK);
-  if (nopts < 0 || nopts > BWGR_MRR_NOPTS || (nopts > 0 && !opts)) return fail(BWGR_EINVAL, "mrr: nopts = %d (at most %d)", nopts, BWGR_MRR_NOPTS);
-  if (P->data->is_f32) return fail(BWGR_EINVAL, "mrr: the panel holds fp32 genotypes; mrr takes int8 panels only");
+// k and the options of bwgr_mrr and bwgr_mrr_dense (`who`), from one table: defaults, refusals and the checks on what is read
+static int mrr_read_opts(const char *who, int k, const double *opts, int nopts, MrrOpts &o) {
+  if (k < 1 || k > BWGR_MRR_MAXK) return fail(BWGR_EINVAL, "%s: k = %d traits; this engine takes 1 <= k <= %d", who, k, BWGR_MRR_MAXK);
+  if (nopts < 0 || nopts > BWGR_MRR_NOPTS || (nopts > 0 && !opts)) return fail(BWGR_EINVAL, "%s: nopts = %d (at most %d)", who, nopts, BWGR_MRR_NOPTS);
   double O[BWGR_MRR_NOPTS] = BWGR_MRR_DEFAULTS;
   const double D0[BWGR_MRR_NOPTS] = BWGR_MRR_DEFAULTS;
   for (int i = 0; i < nopts; ++i) O[i] = opts[i];
@@ -27,17 +25,29 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
       {BWGR_MRR_ROUNDGCDOWNFROM, "roundGCdownFrom"}, {BWGR_MRR_ROUNDGCDOWNTO, "roundGCdownTo"}, {BWGR_MRR_BUCKETGCFROM, "bucketGCfrom"},
       {BWGR_MRR_BUCKETGCTO, "bucketGCto"}, {BWGR_MRR_DEFLATEBY, "DeflateBy"}};
     for (const auto &r : refused)
-      if (O[r.id] != D0[r.id]) return fail(BWGR_EINVAL, "mrr: option %s = %g is not supported (only its default, %g)", r.name, O[r.id], D0[r.id]);
+      if (O[r.id] != D0[r.id]) return fail(BWGR_EINVAL, "%s: option %s = %g is not supported (only its default, %g)", who, r.name, O[r.id], D0[r.id]);
   }
-  MrrOpts o;
   o.maxit = (int)O[BWGR_MRR_MAXIT]; o.tol = O[BWGR_MRR_TOL]; o.TH = O[BWGR_MRR_TH] != 0; o.HCS = O[BWGR_MRR_HCS] != 0; o.XFA = O[BWGR_MRR_XFA] != 0;
   o.ACS = O[BWGR_MRR_ACS] != 0; o.NumXFA = (int)O[BWGR_MRR_NUMXFA]; o.R2 = O[BWGR_MRR_R2]; o.gc0 = O[BWGR_MRR_GC0]; o.df0 = O[BWGR_MRR_DF0];
   o.updateMu = O[BWGR_MRR_UPDATEMU] != 0; o.wph2 = O[BWGR_MRR_WEIGHT_PRIOR_H2]; o.wpgc = O[BWGR_MRR_WEIGHT_PRIOR_GC];
   o.OneVarB = O[BWGR_MRR_ONEVARB] != 0; o.OneVarE = O[BWGR_MRR_ONEVARE] != 0; o.verbose = O[BWGR_MRR_VERBOSE] != 0;
-  if (o.maxit < 0) return fail(BWGR_EINVAL, "mrr: maxit = %d", o.maxit);
+  if (o.maxit < 0) return fail(BWGR_EINVAL, "%s: maxit = %d", who, o.maxit);
   if ((o.XFA || o.ACS) && (o.NumXFA < 1 || o.NumXFA > k))
-    return fail(BWGR_EINVAL, "mrr: NumXFA = %d with XFA / ACS needs 1 <= NumXFA <= k = %d (the reference indexes eigenvalue k - NumXFA)", o.NumXFA, k);
-  const int64_t n = P->data->n, p = P->data->p;
+    return fail(BWGR_EINVAL, "%s: NumXFA = %d with XFA / ACS needs 1 <= NumXFA <= k = %d (the reference indexes eigenvalue k - NumXFA)", who, o.NumXFA, k);
+  return BWGR_OK;
+}
+
+struct MrrOut { double *mu, *b, *hat, *h2, *GC, *vb, *ve, *MSx, *cnvB, *cnvH2, *cnvV; int *its; };
+static int mrr_iterate(MtFit &M, const TraitSet &S, const MrrOpts &o, std::vector<double> &iG, const MrrOut &res);
+
+extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opts, int nopts, double *mu_out, double *b_out, double *hat_out,
+                        double *h2_out, double *GC_out, double *vb_out, double *ve_out, double *MSx_out, double *cnvB, double *cnvH2, double *cnvV,
+                        int *its) {
+  if (!P || !Y || !b_out || !its) return fail(BWGR_EINVAL, "mrr: null pointer");
+  MrrOpts o;
+  CHK(mrr_read_opts("mrr", k, opts, nopts, o));
+  if (P->data->is_f32) return fail(BWGR_EINVAL, "mrr: the panel holds fp32 genotypes; mrr takes int8 panels only");
+  const int64_t n = P->data->n;
   const bwgr_pegs_effect_ex one = {P, nullptr, 0, 0, nullptr, nullptr, nullptr, 0};
   MtList E;
   CHK(mt_check_effects("mrr", "b", &one, 1, n, P->data->device, &b_out, E));                        // (nothing left to refuse: the panel's device, ld and stream)
@@ -45,8 +55,6 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   // ---- host set-up (:742-816): nt, mu and the centred y (:746-761); vy with iN = 1/(n-1) (:781-782) ----
   const TraitSet S = read_traits(Y, n, k, E.ld, k, RowRule::AtLeastTwo);
   if (S.bad >= 0) return fail(BWGR_EINVAL, "mrr: trait %d has %g observed rows (needs 2)", (int)S.bad, S.nt[(size_t)S.bad]);
-  const std::vector<double> &nt = S.nt, &vy = S.vy;
-  std::vector<double> mu = S.mu;
   // missingness patterns: traits with the same observed rows share one masked Gram
   const Patterns pat = find_patterns(S, 0, k);
   std::vector<double> iG((size_t)k * k, 0.0);     // (copied from asynchronously: before the fit, whose holder waits for the stream)
@@ -54,12 +62,26 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
   M.masks(S, pat);
   M.alloc(hat_out != nullptr, false);
   if (M.bufs.failed()) return no_memory("mrr");
-  const MtEffect &F = M.eff[0];
-  MrrConst &mc = M.mc;
-  std::vector<double> &d = M.d, &off = M.off;
   CHK(M.upload(S, S.sumy.data()));                                                                 // e = y, :825
   CHK(M.stage_effect(0));                                                                          // b = 0, :823
   CHK(M.setup_effect(0, 1));
+  const MrrOut out = {mu_out, b_out, hat_out, h2_out, GC_out, vb_out, ve_out, MSx_out, cnvB, cnvH2, cnvV, its};
+  return mrr_iterate(M, S, o, iG, out);
+}
+
+// mrr's own algebra after the set-up of its one effect (a panel, centred implicitly, or a dense design on the train, centred in its copy): MSx,
+// the start values, the iterations and the outputs.  iG (k x k, zeros) is the caller's: it is copied from asynchronously and outlives M.
+static int mrr_iterate(MtFit &M, const TraitSet &S, const MrrOpts &o, std::vector<double> &iG, const MrrOut &res) {
+  const int k = M.k;
+  const int64_t n = M.n, p = M.eff[0].m;
+  double *const mu_out = res.mu, *const b_out = res.b, *const hat_out = res.hat, *const h2_out = res.h2, *const GC_out = res.GC, *const vb_out = res.vb,
+         *const ve_out = res.ve, *const MSx_out = res.MSx, *const cnvB = res.cnvB, *const cnvH2 = res.cnvH2, *const cnvV = res.cnvV;
+  int *const its = res.its;
+  const std::vector<double> &nt = S.nt, &vy = S.vy;
+  std::vector<double> mu = S.mu;
+  const MtEffect &F = M.eff[0];
+  MrrConst &mc = M.mc;
+  std::vector<double> &d = M.d, &off = M.off;
   // a reduction over p of the k^2 (+k) products, partials in a fixed order
   auto reduce_pk = [&](int mode, int nout, const double *dvec, std::vector<double> &out) -> int {
     out.resize(nout);
@@ -135,13 +157,17 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
     if (numit == o.maxit && o.verbose) printf("Model did not converge\n");
   }
   // ---- fitted values for every row, the missing ones included (:1054-1055) ----
-  std::vector<double> xb((size_t)p);
   CHK(M.read_b(0, b_out));                                                                         // p x k column-major
-  HIPCHK(d2h(M.st, xb.data(), F.leg.xbar, sizeof(double) * p));
-  for (int t = 0; t < k; ++t) { double s = 0; for (int64_t j = 0; j < p; ++j) s += xb[(size_t)j] * b_out[(size_t)t * p + j]; off[t] = mu[t] - s; }
+  if (F.train) {
+    for (int t = 0; t < k; ++t) off[t] = mu[t];                                                    // (the copy is centred: no offset but mu)
+  } else {
+    std::vector<double> xb((size_t)p);
+    HIPCHK(d2h(M.st, xb.data(), F.leg.xbar, sizeof(double) * p));
+    for (int t = 0; t < k; ++t) { double s = 0; for (int64_t j = 0; j < p; ++j) s += xb[(size_t)j] * b_out[(size_t)t * p + j]; off[t] = mu[t] - s; }
+  }
   if (hat_out) {
     CHK(M.stage_vec(off));
-    CHK(M.panel_hat(0, M.hatd));
+    if (F.train) CHK(M.train_hat(0, M.hatd)); else CHK(M.panel_hat(0, M.hatd));
     HIPCHK(hipGetLastError());
     HIPCHK(d2h(M.st, hat_out, M.hatd, sizeof(double) * n * k));
   }
@@ -158,6 +184,62 @@ extern "C" int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opt
     }
   *its = numit;
   return BWGR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// mrr on a dense fp64 design: mrr(Y, dense(X)), mkr(Y, K) = MRR3(Y, K2X(K)) (R/mix.R:1275) -- the train of mrr_dense.hip.h
+//   once:       X -> the engine's padded copy, k_mrrd_centre (explicit centring, :763-765), k_mrrd_setup
+//   per sweep:  order -> k_mrrd_gram -> k_mrr_linv -> [k_mrrd_pass(b-1 | b), k_mrrd_solve(b)] for every block -> k_mrrd_pass(last | -), then
+//               bwgr_mrr's tail (mrr_iterate)
+// A fit with one effect on the dense train (MtFit, mrrd_sweep); options, defaults, refusals and outputs are bwgr_mrr's (mrr_read_opts).
+// ------------------------------------------------------------------------------------------------
+extern "C" int bwgr_mrr_dense(int device, const double *X, int memloc, int64_t n, int64_t r, int64_t ldx, const double *Y, int k, const double *opts, int nopts,
+                              double *mu_out, double *b_out, double *hat_out, double *h2_out, double *GC_out, double *vb_out, double *ve_out, double *MSx_out,
+                              double *cnvB, double *cnvH2, double *cnvV, int *its) {
+  if (!X || !Y || !b_out || !its) return fail(BWGR_EINVAL, "mrr_dense: null pointer");
+  if (memloc != BWGR_HOST && memloc != BWGR_DEVICE) return fail(BWGR_EINVAL, "mrr_dense: bad memloc %d", memloc);
+  MrrOpts o;
+  CHK(mrr_read_opts("mrr_dense", k, opts, nopts, o));
+  if (r < 1 || r > 0x7FFFFF00ll) return fail(BWGR_EINVAL, "mrr_dense: r = %lld columns of X (at least 1, at most 2147483392)", (long long)r);
+  if (n < 2) return fail(BWGR_EINVAL, "mrr_dense: n = %lld rows (at least 2)", (long long)n);
+  if (ldx < n) return fail(BWGR_EINVAL, "mrr_dense: ldx = %lld is below n = %lld", (long long)ldx, (long long)n);
+  const int64_t ld = (n + 127) / 128 * 128;
+  std::vector<double> Xh;                         // host X with the engine's column stride (copied from asynchronously: before the fit)
+  if (memloc == BWGR_HOST) {
+    Xh.assign((size_t)ld * (size_t)r, 0.0);
+    for (int64_t j = 0; j < r; ++j)
+      for (int64_t i = 0; i < n; ++i) {
+        const double v = X[(size_t)j * (size_t)ldx + (size_t)i];
+        if (!std::isfinite(v)) return fail(BWGR_EINVAL, "mrr_dense: X[%lld, %lld] is not finite", (long long)i, (long long)j);
+        Xh[(size_t)j * (size_t)ld + (size_t)i] = v;
+      }
+  }
+  CHK(require_device(device));
+  const bwgr_pegs_effect_ex one = {nullptr, X, r, ldx, nullptr, nullptr, nullptr, 0};
+  MtList E;
+  E.eff = &one; E.neff = 1; E.n = n; E.ld = ld; E.st = nullptr; E.train = true;
+  E.Zc.resize(1); E.csr.resize(1); E.disjoint.assign(1, 0);
+  const TraitSet S = read_traits(Y, n, k, E.ld, k, RowRule::AtLeastTwo);
+  if (S.bad >= 0) return fail(BWGR_EINVAL, "mrr_dense: trait %d of Y has %g observed rows (needs 2)", (int)S.bad, S.nt[(size_t)S.bad]);
+  const Patterns pat = find_patterns(S, 0, k);
+  {
+    const MrrDensePlan pl = mrr_dense_plan(n, r, k, (int)pat.rep.size());
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    if (pl.ws_bytes > free_b)
+      return fail(BWGR_EINVAL, "mrr_dense: n = %lld, r = %lld, k = %d need a device workspace of %zu bytes; %zu are free", (long long)n, (long long)r, k, pl.ws_bytes, free_b);
+  }
+  std::vector<double> iG((size_t)k * k, 0.0);     // (copied from asynchronously: before the fit, whose holder waits for the stream)
+  MtFit M(E, k);
+  M.masks(S, pat);
+  M.alloc(hat_out != nullptr, false);
+  if (M.bufs.failed()) return no_memory("mrr_dense");
+  CHK(M.upload(S, nullptr));                                                                       // e = y, :825 (nothing reads the traits' sums: xbar = 0)
+  CHK(M.stage_train(0, memloc == BWGR_HOST ? Xh.data() : X, memloc == BWGR_HOST ? ld : ldx, memloc == BWGR_DEVICE));
+  CHK(M.stage_effect(0));                                                                          // b = 0, :823
+  CHK(M.setup_effect(0, 0));
+  const MrrOut out = {mu_out, b_out, hat_out, h2_out, GC_out, vb_out, ve_out, MSx_out, cnvB, cnvH2, cnvV, its};
+  return mrr_iterate(M, S, o, iG, out);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@
 //   the plans:   mrr_plan (LDS of k_mrr_solve / k_mrr_linv), pegs_dense_plan (the dense leg), pegs_sparse_plan (the sparse legs), the grids
 //                the launch sites share
 //   mrr_sweep:   one panel design's share of a sweep
+//   mrrd_sweep:  a dense design's share of a sweep on the block train of mrr_dense.hip.h, and its plan (mrr_dense_plan)
 //   MtList:      what an effect list says, checked on the host (mt_check_effects, worded with the caller's name)
 //   MtFit:       a fit's masks, device arrays and effects, and one member function per step the entries repeat; the entries keep their loops
 // ------------------------------------------------------------------------------------------------
@@ -139,6 +140,89 @@ static int mrr_sweep(hipStream_t st, const MrrLeg &L, const MrrSweepShared &W, c
   return BWGR_OK;
 }
 
+// The dense train's plan (mrr_dense.hip.h), decided here and nowhere else: bwgr_debug_mrr_dense_plan exposes it to the
+// CPU tests, and mrrd_leg_alloc, mrrd_sweep and bwgr_mrr_dense take every grid, LDS size and array length from it.  The solve's LDS is
+// mrr_plan's arithmetic with an fp64 Gram: a pattern's matrix is 32 KB, so at most 3 or 4 are staged and the rest are read from global memory.
+struct MrrDensePlan {
+  int64_t ld, nblk, edge, tiles, pass_wg, trips, cols_wg, hat_wg;   // edge: columns of the last block; trips: tiles a pass workgroup takes at most
+  int linv_lds, ngl;
+  size_t lds_gram, lds_pass, lds_solve, lds_linv, ws_bytes;
+};
+static MrrDensePlan mrr_dense_plan(int64_t n, int64_t r, int k, int npat) {
+  MrrDensePlan pl;
+  pl.ld = (n + 127) / 128 * 128;
+  pl.nblk = (r + MRR_MB - 1) / MRR_MB;
+  pl.edge = r - (pl.nblk - 1) * MRR_MB;
+  pl.tiles = pl.ld / 64;
+  pl.pass_wg = mrr_pass_grid(pl.ld);
+  pl.trips = (pl.tiles + pl.pass_wg - 1) / pl.pass_wg;
+  pl.cols_wg = mrr_setup_grid(r);                                   // k_mrrd_centre and k_mrrd_setup: one column per wave, four per workgroup and trip
+  pl.hat_wg = (n + 255) / 256;
+  const size_t lds_fixed = mrrd_solve_lds(0, 0), linv_b = sizeof(double) * MRR_MB * k * k, gram_b = sizeof(double) * MRR_MB * MRR_MB;
+  pl.linv_lds = lds_fixed + linv_b <= MRR_LDS_MAX ? 1 : 0;
+  pl.ngl = (int)std::min<size_t>((size_t)npat, (MRR_LDS_MAX - lds_fixed - (pl.linv_lds ? linv_b : 0)) / gram_b);
+  pl.lds_solve = mrrd_solve_lds(pl.ngl, pl.linv_lds ? MRR_MB * k * k : 0);
+  pl.lds_linv = linv_b;
+  pl.lds_gram = sizeof(double) * 2 * MRRD_GT * MRRD_GP + sizeof(int) * MRR_MB;                                  // (static, for the record)
+  pl.lds_pass = sizeof(double) * (MRR_MB * MRRD_XP + 64 * MRR_KMAX + MRR_MB * MRR_KMAX) + sizeof(int) * 2 * MRR_MB;
+  const size_t nl = (size_t)pl.ld, nr = (size_t)r, rk = nr * (size_t)k;
+  pl.ws_bytes = sizeof(double) * (nl * nr + (size_t)pl.nblk * npat * MRR_MB * MRR_MB + 4 * rk + rk * k + MRR_KMAX)   // X_c, Grams, XX XSX tilde b, Linv, db2
+                + sizeof(int32_t) * nr                                                                               // the order
+                + 2 * sizeof(uint32_t) * nl + (size_t)npat * nl + sizeof(double) * (2 * (size_t)k * nl + (size_t)n * k)   // masks, y, e, hat
+                + sizeof(double) * ((size_t)pl.pass_wg * (MRR_MB + 1) * MRR_KMAX + MRR_MB * MRR_KMAX + MRR_KMAX + 1024 + (size_t)MRR_NP * (MRR_KMAX * MRR_KMAX + MRR_KMAX) + MRR_KMAX);
+  return pl;
+}
+extern "C" int bwgr_debug_mrr_dense_plan(int64_t n, int64_t r, int k, int npat, int64_t out[BWGR_MRR_DENSE_PLAN_NOUT]) {
+  if (!out) return fail(BWGR_EINVAL, "mrr_dense plan: null pointer");
+  if (n < 2 || r < 1 || r > 0x7FFFFF00ll || k < 1 || k > BWGR_MRR_MAXK || npat < 1 || npat > k)
+    return fail(BWGR_EINVAL, "mrr_dense plan: n = %lld (at least 2), r = %lld (1 .. 2147483392), k = %d (1 <= k <= %d), npat = %d (1 <= npat <= k)",
+                (long long)n, (long long)r, k, BWGR_MRR_MAXK, npat);
+  const MrrDensePlan pl = mrr_dense_plan(n, r, k, npat);
+  out[0] = pl.ld; out[1] = pl.nblk; out[2] = pl.edge; out[3] = pl.tiles; out[4] = pl.pass_wg; out[5] = pl.trips; out[6] = pl.cols_wg; out[7] = pl.hat_wg;
+  out[8] = pl.linv_lds; out[9] = pl.ngl; out[10] = (int64_t)pl.lds_gram; out[11] = (int64_t)pl.lds_pass; out[12] = (int64_t)pl.lds_solve;
+  out[13] = (int64_t)pl.lds_linv; out[14] = (int64_t)pl.ws_bytes;
+  return BWGR_OK;
+}
+
+// A dense design's share of a sweep on the train of mrr_dense.hip.h, against the same residual (MrrSweepShared) as mrr_sweep's
+struct MrrDenseLeg {
+  int64_t r = 0;
+  double *Xc = nullptr, *gram = nullptr, *XXd = nullptr, *XSXd = nullptr, *tilde = nullptr, *bd = nullptr, *Linv = nullptr, *db2 = nullptr;
+  int32_t *ordd = nullptr;
+};
+// (the caller asks bufs.failed() once, after all its gets)
+static void mrrd_leg_alloc(DevBufs &bufs, MrrDenseLeg &L, const MrrDensePlan &pl, int64_t r, int npat, int k) {
+  L.r = r;
+  const size_t nr = (size_t)r, rk = nr * k;
+  L.Xc = bufs.get<double>((size_t)pl.ld * nr); L.gram = bufs.get<double>((size_t)pl.nblk * npat * MRR_MB * MRR_MB);
+  L.XXd = bufs.get<double>(rk); L.XSXd = bufs.get<double>(rk); L.tilde = bufs.get<double>(rk); L.bd = bufs.get<double>(rk); L.Linv = bufs.get<double>(rk * k);
+  L.db2 = bufs.get<double>(MRR_KMAX); L.ordd = bufs.get<int32_t>(nr);
+}
+// order -> k_mrrd_gram -> k_mrr_linv -> [k_mrrd_pass(b-1 | b), k_mrrd_solve(b)] for every block -> k_mrrd_pass(last | -); mc.iVe and iG (host,
+// k x k) are the sweep's.  zbd: the pattern words.  Leaves sum_j (delta b_jt)^2 in L.db2.
+static int mrrd_sweep(hipStream_t st, const MrrDenseLeg &L, const MrrSweepShared &W, const uint32_t *zbd, const MrrConst &mc, const MrrDensePlan &pl,
+                      const std::vector<int> &order, const double *iG) {
+  const int k = mc.k, npat = W.npat;
+  const int64_t r = L.r, ld = W.ld, nblk = pl.nblk;
+  HIPCHK(h2d(st, L.ordd, order.data(), (size_t)r));
+  hipLaunchKernelGGL(k_mrrd_gram, dim3((unsigned)nblk, (unsigned)npat), dim3(256), 0, st, (const double *)L.Xc, ld, r, (const int32_t *)L.ordd, zbd, npat, L.gram);
+  HIPCHK(h2d(st, W.iGd, iG, (size_t)k * k));
+  hipLaunchKernelGGL(k_mrr_linv, dim3((unsigned)((r + 63) / 64)), dim3(64), pl.lds_linv, st, (const double *)L.XXd, (const double *)W.iGd, mc, r, L.Linv);
+  HIPCHK(zero(st, L.db2, (size_t)MRR_KMAX));
+  HIPCHK(hipGetLastError());
+  for (int64_t blk = 0; blk <= nblk; ++blk) {
+    MrrdPassArgs pa; pa.X = L.Xc; pa.r = r; pa.ld = ld; pa.order = L.ordd; pa.zt = W.ztd; pa.e = W.ed; pa.dB = W.dB; pa.part = W.part;
+    pa.prev = blk > 0 ? (int)(blk - 1) : -1; pa.next = blk < nblk ? (int)blk : -1; pa.k = k;
+    hipLaunchKernelGGL(k_mrrd_pass, dim3((unsigned)pl.pass_wg), dim3(256), 0, st, pa);
+    if (blk == nblk) break;
+    MrrdSolveArgs sa; sa.part = W.part; sa.G = (int)pl.pass_wg; sa.order = L.ordd; sa.blk = (int)blk; sa.r = r; sa.gram = L.gram; sa.XX = L.XXd; sa.Linv = L.Linv;
+    sa.b = L.bd; sa.dB = W.dB; sa.db2 = L.db2; sa.ngl = pl.ngl; sa.linv_lds = pl.linv_lds;
+    hipLaunchKernelGGL(k_mrrd_solve, dim3(1), dim3(256), pl.lds_solve, st, sa, mc);
+  }
+  HIPCHK(hipGetLastError());
+  return BWGR_OK;
+}
+
 // a dense effect on the device
 struct PegsDense {
   int64_t q = 0;
@@ -167,6 +251,7 @@ struct MtList {
   std::vector<std::vector<double>> Zc;     // per dense effect, Z without its padding rows (MtFit takes them over)
   std::vector<CsrCopy> csr;                // per sparse effect, its row-major copy (MtFit takes them over)
   std::vector<char> disjoint;              // per sparse effect, whether no row occurs in two columns
+  bool train = false;                      // a dense effect is swept by the block train of mrr_dense.hip.h (bwgr_mrr_dense), not by the dense leg
 };
 // The refusals every effect list meets, worded with the caller's name (`coef`: what it calls an effect's coefficients); none needs a device.
 // Then the device: the first panel's, or `device` where every effect is dense.
@@ -218,14 +303,14 @@ static int mt_check_effects(const char *who, const char *coef, const bwgr_pegs_e
 
 // one effect of a fit: a panel's leg, a sparse or a dense effect, and what the entries read of any
 struct MtEffect {
-  bool panel = false, sparse = false;
+  bool panel = false, sparse = false, train = false;   // train: a dense design on the block train (dl), not on the dense leg (dense)
   int64_t m = 0;                           // its columns
-  MrrLeg leg; PegsDense dense; PegsSparse sp;
-  double *b() const { return panel ? leg.bd : sparse ? sp.bd : dense.bd; }
-  double *tilde() const { return panel ? leg.tilde : sparse ? sp.tilde : dense.tilde; }
-  double *XX() const { return panel ? leg.XXd : sparse ? sp.XXd : dense.XXd; }
-  double *XSX() const { return panel ? leg.XSXd : sparse ? sp.XSXd : dense.XSXd; }
-  double *db2() const { return panel ? leg.db2 : sparse ? sp.db2 : dense.db2; }
+  MrrLeg leg; PegsDense dense; PegsSparse sp; MrrDenseLeg dl;
+  double *b() const { return train ? dl.bd : panel ? leg.bd : sparse ? sp.bd : dense.bd; }
+  double *tilde() const { return train ? dl.tilde : panel ? leg.tilde : sparse ? sp.tilde : dense.tilde; }
+  double *XX() const { return train ? dl.XXd : panel ? leg.XXd : sparse ? sp.XXd : dense.XXd; }
+  double *XSX() const { return train ? dl.XSXd : panel ? leg.XSXd : sparse ? sp.XSXd : dense.XSXd; }
+  double *db2() const { return train ? dl.db2 : panel ? leg.db2 : sparse ? sp.db2 : dense.db2; }
 };
 
 // A multi-trait fit on the device: k traits over the rows of an effect list, all effects against one residual.  An entry makes one after its
@@ -245,7 +330,7 @@ struct MtFit {
   std::vector<double> d, off;              // k each, for stage_vec(): the mu shift (or the TH form's diagonal); the fitted values' offset (zero unless written)
   MrrConst mc;                             // (the entries set iVe before every sweep)
   int npat = 0, G = 0, nch_max = 1;
-  MrrPlan plan; PegsDensePlan dpl;
+  MrrPlan plan; PegsDensePlan dpl; MrrDensePlan tpl;   // tpl: of the one effect on the dense train, where there is one
   // Device data
   DevBufs bufs;
   uint32_t *zbd = nullptr, *ztd = nullptr; uint8_t *zmd = nullptr;
@@ -260,6 +345,7 @@ struct MtFit {
     for (int e = 0; e < E.neff; ++e) {
       eff[(size_t)e].panel = E.eff[e].panel != nullptr;
       eff[(size_t)e].sparse = !E.eff[e].panel && E.eff[e].colptr != nullptr;
+      eff[(size_t)e].train = E.train && !eff[(size_t)e].panel && !eff[(size_t)e].sparse;
       if (eff[(size_t)e].sparse) {
         eff[(size_t)e].sp.nnz = E.eff[e].colptr[E.eff[e].q];
         eff[(size_t)e].sp.disjoint = pegs_sparse_plan(E.n, E.eff[e].q, eff[(size_t)e].sp.nnz, k_, E.disjoint[(size_t)e] && !(E.eff[e].flags & BWGR_PEGS_SERIAL)).disjoint != 0;
@@ -296,6 +382,9 @@ struct MtFit {
         mrr_leg_alloc(bufs, E.leg, E.leg.P, npat, k);
         nch_max = std::max(nch_max, (int)std::min<int64_t>(64, E.m));
         panels = true;
+      } else if (E.train) {
+        tpl = mrr_dense_plan(n, E.m, k, npat);
+        mrrd_leg_alloc(bufs, E.dl, tpl, E.m, npat, k);
       } else if (E.sparse) {
         PegsSparse &S = E.sp;
         S.q = E.m;
@@ -330,6 +419,7 @@ struct MtFit {
     if (sumy) HIPCHK(h2d(st, sumyd, sumy, (size_t)k)); else HIPCHK(zero(st, sumyd, (size_t)MRR_KMAX));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_linv), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrr_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mrrd_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRR_LDS_MAX));
     return BWGR_OK;
   }
   // a dense effect's Z, a sparse effect's two copies; b = 0
@@ -346,14 +436,37 @@ struct MtFit {
         HIPCHK(h2d(st, S.colidx, R.col.data(), (size_t)S.nnz));
         HIPCHK(h2d(st, S.rval, R.val.data(), (size_t)S.nnz));
       }
-    } else if (!E.panel) HIPCHK(h2d(st, E.dense.Zd, Zc[(size_t)e].data(), Zc[(size_t)e].size()));
+    } else if (!E.panel && !E.train) HIPCHK(h2d(st, E.dense.Zd, Zc[(size_t)e].data(), Zc[(size_t)e].size()));   // (a train's design: stage_train)
     HIPCHK(zero(st, E.b(), (size_t)E.m * k));
+    return BWGR_OK;
+  }
+  // The design of an effect on the dense train into its padded copy, centred by its all-rows column means.  Host X (column stride ldx = ld, read
+  // asynchronously: it outlives the fit) or device X of column stride ldx.
+  int stage_train(int e, const double *X, int64_t ldx, bool on_device) {
+    const MrrDenseLeg &L = eff[(size_t)e].dl;
+    if (on_device) {
+      hipLaunchKernelGGL(k_mrrd_centre, dim3((unsigned)tpl.cols_wg), dim3(TAIL_THREADS), 0, st, X, ldx, n, L.r, ld, L.Xc);
+    } else {
+      HIPCHK(h2d(st, L.Xc, X, (size_t)ld * (size_t)L.r));
+      hipLaunchKernelGGL(k_mrrd_centre, dim3((unsigned)tpl.cols_wg), dim3(TAIL_THREADS), 0, st, (const double *)L.Xc, ld, n, L.r, ld, L.Xc);
+    }
+    HIPCHK(hipGetLastError());
+    return BWGR_OK;
+  }
+  // out (n x k) = the train effect's X_c b plus the staged k-vector, for every row
+  int train_hat(int e, double *out) {
+    const MrrDenseLeg &L = eff[(size_t)e].dl;
+    hipLaunchKernelGGL(k_mrrd_hat, dim3((unsigned)tpl.hat_wg), dim3(256), 0, st, (const double *)L.Xc, n, L.r, ld, k, (const double *)L.bd, (const double *)vecd, out);
+    HIPCHK(hipGetLastError());
     return BWGR_OK;
   }
   // XX, XSX and tilde of the effect's columns, one launch: a panel's centred where `centre` (then xbar too), a dense or sparse effect's as they are
   int setup_effect(int e, int centre) {
     const MtEffect &E = eff[(size_t)e];
-    if (E.panel) {
+    if (E.train) {
+      hipLaunchKernelGGL(k_mrrd_setup, dim3((unsigned)tpl.cols_wg), dim3(TAIL_THREADS), 0, st, (const double *)E.dl.Xc, n, E.dl.r, ld, (const uint32_t *)zbd,
+                         (const double *)yd, mc, E.dl.XXd, E.dl.XSXd, E.dl.tilde);
+    } else if (E.panel) {
       const MrrLeg &L = E.leg;
       const PanelData *D = L.P->data;
       hipLaunchKernelGGL(k_mrr_setup_cols, dim3((unsigned)mrr_setup_grid(L.p)), dim3(TAIL_THREADS), 0, st, (const int8_t *)D->X, D->plan.R, (int)n, L.p, ld,
@@ -384,6 +497,7 @@ struct MtFit {
   // k_pegs_sparse_leg / k_pegs_sparse_leg_disjoint -> db2 from the per-column (delta b)^2 in column-index order
   int sweep_effect(int e, int numit, const double *iG) {
     const std::vector<int> &ord = order[(size_t)e].next(numit);
+    if (eff[(size_t)e].train) return mrrd_sweep(st, eff[(size_t)e].dl, W, zbd, mc, tpl, ord, iG);
     if (eff[(size_t)e].panel) return mrr_sweep(st, eff[(size_t)e].leg, W, mc, plan, ord, iG);
     if (eff[(size_t)e].sparse) {
       const PegsSparse &S = eff[(size_t)e].sp;

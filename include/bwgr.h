@@ -283,6 +283,28 @@ int bwgr_mrr(bwgr_panel *P, const double *Y, int k, const double *opts, int nopt
  * in LDS (patterns ngl..npat-1 are read from global memory); the dynamic LDS bytes of the solve and of the inverses' kernel.  Any
  * output may be NULL. */
 int bwgr_debug_mrr_plan(int k, int npat, int *linv_lds, int *ngl, int64_t *solve_lds_bytes, int64_t *linv_lds_bytes);
+/* ---- mrr on a dense fp64 design: mrr(Y, dense(X)), mkr(Y, K) = MRR3(Y, K2X(K)) (R/mix.R:1275) -------------------------
+ * bwgr_mrr's algorithm, options, defaults, refusals and outputs (b is r x k) on an n x r matrix of doubles instead of a panel: real-valued
+ * dosages, or the eigenvector design K2X makes of a relationship matrix (the host layers decompose; bwgr_amd.K2X, bwgr_amd.mkr).  X is
+ * column-major with column stride ldx, in host memory (memloc = BWGR_HOST) or on `device` (BWGR_DEVICE); the engine keeps its own copy,
+ * centred once by the all-rows column means (:763-765), so X is not changed.  A host X is checked for non-finite entries; for a device X
+ * that is the caller's duty (a NaN or Inf there spreads through the fit).  The launch train is bwgr_mrr's with fp64 kernels (DESIGN.md
+ * section 4.13); two calls give the same bits, and a device X gives the bits of the same values on the host.
+ * BWGR_EINVAL: a null required pointer, a bad memloc, what bwgr_mrr refuses of k and the options, r < 1 or r > 2147483392, n < 2, ldx < n,
+ * a non-finite entry of a host X, a trait of Y with fewer than two records, a workspace (bwgr_debug_mrr_dense_plan) beyond the device's
+ * free memory. */
+int bwgr_mrr_dense(int device, const double *X, int memloc, int64_t n, int64_t r, int64_t ldx, const double *Y, int k, const double *opts, int nopts,
+                   double *mu, double *b, double *hat, double *h2, double *GC, double *vb, double *ve, double *MSx, double *cnvB, double *cnvH2,
+                   double *cnvV, int *its);
+/* host arithmetic of bwgr_mrr_dense's plan (needs no GPU) for n rows, r columns, k traits and npat missingness patterns (n >= 2,
+ * 1 <= r <= 2147483392, 1 <= npat <= k <= 16, else BWGR_EINVAL).  out[0] ld, the rows padded to 128; out[1] the 64-column blocks of a
+ * sweep; out[2] the columns of the last block; out[3] the 64-row tiles; out[4] the workgroups of k_mrrd_pass; out[5] the tiles one of them
+ * takes at most; out[6] the workgroups of k_mrrd_centre and k_mrrd_setup (one column per wave); out[7] those of k_mrrd_hat; out[8] linv_lds
+ * and out[9] ngl of the solve, as in bwgr_debug_mrr_plan, with 32 KB per pattern's Gram; out[10..13] the LDS bytes of k_mrrd_gram and
+ * k_mrrd_pass (static), k_mrrd_solve and k_mrr_linv (dynamic); out[14] the bytes of the call's device workspace.  k_mrrd_gram runs
+ * out[1] x npat workgroups. */
+#define BWGR_MRR_DENSE_PLAN_NOUT 15
+int bwgr_debug_mrr_dense_plan(int64_t n, int64_t r, int k, int npat, int64_t out[BWGR_MRR_DENSE_PLAN_NOUT]);
 /* ---- per-trait ridge fits (UVBETA / FUVBETA family) -------------------------------------------------------
  * Replaces VectorXd solver1x(Y,X,maxit,tol,df0) src/RcppEigen20230423.cpp:1410-1443 and MatrixXd UVBETA(Y,X) :1506-1515; solver1xF :1613-1646 and
  * FUVBETA :1709-1718; xsolver1xF :1721-1743 and XFUVBETA :1746-1753; zsolver1xF :1771-1804 and ZFUVBETA :1807-1816 (R/RcppExports.R:196-238).
@@ -539,7 +561,7 @@ int bwgr_debug_aux_plan(int is_f32, int64_t p, int64_t ld, int64_t out[BWGR_AUX_
  * Both entry points run on the panel's stream, return when the result is complete, and return BWGR_EINVAL without enqueuing anything while
  * sweeps of other handles are in flight on the device (occupancy guard, above).  Also BWGR_EINVAL: fp32 panels, an unknown kind, a leading
  * dimension below n, max|x|^2 * p >= 2^53 or max|x|^2 * n * p >= 2^63.  BWGR_KCHUNK (read when the root panel is made) forces a shorter chunk.
- * Not here: fp32 panels, EigenEVD / K2X / mkr / mkr2X (the eigendecomposition stays with the caller), CNT / IMP / SPC / SPM, and a product
+ * Not here: fp32 panels, EigenEVD / mkr2X (the eigendecomposition stays with the caller; K2X and mkr decompose in the host layers and fit by bwgr_mrr_dense), CNT / IMP / SPC / SPM, and a product
  * sharded over GPUs. */
 enum { BWGR_K_GRM = 0, BWGR_K_GAU = 1, BWGR_K_EIGEN_GRM = 2, BWGR_K_EIGEN_GAU = 3, BWGR_K_EIGEN_ARC = 4 };
 /* exact X X' over the panel's n rows (the Eigen product of src/RcppEigen20230423.cpp:17, :32, :48, in integers): G is n x n int64, ldg >= n,

@@ -79,6 +79,22 @@ MRR3F <- function(Y, X, maxit = 500L, tol = 10e-9, cores = 1L, TH = FALSE, NonLi
   .Call("bwgrhip_MRR3F", .bwgr_f32(as.matrix(Y)), .bwgr_panel(X), .bwgr_mrr_opts(maxit, tol, TH, NonLinearFactor, InnerGS, NoInv, HCS, XFA, ACS, NumXFA, R2, gc0, df0, updateMu, weight_prior_h2, weight_prior_gc, PenCor, MinCor, uncorH2below, roundGCupFrom, roundGCupTo, roundGCdownFrom, roundGCdownTo, bucketGCfrom, bucketGCto, DeflateMax, DeflateBy, OneVarB, OneVarE, verbose))
 mrr <- function(Y, X, ...) MRR3(Y, X, ...)
 mrr_float <- function(Y, X, ...) MRR3F(Y, X, ...)
+# K2X(K, MinEV, cores), R/RcppExports.R:256, and mkr(Y, K, ...) = MRR3(Y, K2X(K), ...), R/mix.R:1275.  K2X: the eigenvectors of the symmetric K
+# times |eigenvalue| (U D of the reference's SVD, not U sqrt(D): X X' = K K), by decreasing |eigenvalue|, those above MinEV, float-rounded.
+# The count is made on base eigen()'s fp64 spectrum (the reference counts on a float SVD and keeps a rank-deficient K's null directions).
+# mkr takes MRR3's arguments after K; its `b` are the effects of K2X's columns.  `cores` is ignored.
+K2X <- function(K, MinEV = 1e-8, cores = 1L) {
+  K <- as.matrix(K) * 1.0
+  if (nrow(K) != ncol(K)) stop("K2X: K must be square")
+  if (max(abs(K - t(K))) > 1e-6 * max(abs(K))) stop("K2X: K is not symmetric")
+  es <- eigen((K + t(K)) / 2, symmetric = TRUE)
+  o <- order(-abs(es$values))
+  o <- o[abs(es$values[o]) > MinEV]
+  .bwgr_f32(es$vectors[, o, drop = FALSE] %*% diag(abs(es$values[o]), length(o)))
+}
+.bwgr_mrr_dense <- function(Y, X, maxit = 500L, tol = 10e-9, cores = 1L, TH = FALSE, NLfactor = 0.0, InnerGS = FALSE, NoInv = FALSE, HCS = FALSE, XFA = FALSE, ACS = FALSE, NumXFA = 3L, R2 = 0.5, gc0 = 0.5, df0 = 1.0, updateMu = FALSE, weight_prior_h2 = 0.01, weight_prior_gc = 0.01, PenCor = 0.0, MinCor = 1.0, uncorH2below = 0.0, roundGCupFrom = 1.0, roundGCupTo = 1.0, roundGCdownFrom = 1.0, roundGCdownTo = 0.0, bucketGCfrom = 1.0, bucketGCto = 1.0, DeflateMax = 0.9, DeflateBy = 0.0, OneVarB = FALSE, OneVarE = FALSE, verbose = FALSE)
+  .Call("bwgrhip_mrr_dense", as.matrix(Y) * 1.0, as.matrix(X) * 1.0, .bwgr_mrr_opts(maxit, tol, TH, NLfactor, InnerGS, NoInv, HCS, XFA, ACS, NumXFA, R2, gc0, df0, updateMu, weight_prior_h2, weight_prior_gc, PenCor, MinCor, uncorH2below, roundGCupFrom, roundGCupTo, roundGCdownFrom, roundGCdownTo, bucketGCfrom, bucketGCto, DeflateMax, DeflateBy, OneVarB, OneVarE, verbose))
+mkr <- function(Y, K, ...) .bwgr_mrr_dense(Y, K2X(K), ...)
 # per-trait ridge fits, R/RcppExports.R:196-238 (solver1x, UVBETA, solver1xF, FUVBETA, XFUVBETA, ZFUVBETA): same names, argument order,
 # defaults and return shapes.  Integer genotypes only (an int8 panel).  Y: NA = missing; every trait is fitted on its own observed rows.
 # A trait without observed rows gives a zero column (XFUVBETA too).  The float solvers receive float-rounded Y, tol and df0.

@@ -306,6 +306,33 @@ static SEXP mrr_call(SEXP Y, SEXP panel, SEXP opts) {
 SEXP bwgrhip_MRR3(SEXP Y, SEXP panel, SEXP opts) { return mrr_call(Y, panel, opts); }
 SEXP bwgrhip_MRR3F(SEXP Y, SEXP panel, SEXP opts) { return mrr_call(Y, panel, opts); }
 
+/* mkr(Y, K, ...) = MRR3(Y, K2X(K), ...)  R/mix.R:1275: MRR3's list on a dense design.  X: the numeric n x r matrix K2X (bwgr_hip.R) made of K,
+ * or any real-valued design; Y and opts as for MRR3.  One call of bwgr_mrr_dense on device 0. */
+SEXP bwgrhip_mrr_dense(SEXP Y, SEXP X, SEXP opts) {
+  SEXP dx = Rf_getAttrib(X, R_DimSymbol), dim = Rf_getAttrib(Y, R_DimSymbol);
+  if (Rf_length(dx) != 2 || Rf_length(dim) != 2 || INTEGER(dim)[0] != INTEGER(dx)[0]) Rf_error("Y and X must be matrices with the same number of rows");
+  const int n = INTEGER(dx)[0], r = INTEGER(dx)[1], k = INTEGER(dim)[1], nopts = (int)XLENGTH(opts), maxit = (int)REAL(opts)[BWGR_MRR_MAXIT];
+  const int rr = r > 0 ? r : 1;
+  SEXP mu = PROTECT(Rf_allocVector(REALSXP, k)), b = PROTECT(Rf_allocMatrix(REALSXP, rr, k)), hat = PROTECT(Rf_allocMatrix(REALSXP, n, k));
+  SEXP h2 = PROTECT(Rf_allocVector(REALSXP, k)), GC = PROTECT(Rf_allocMatrix(REALSXP, k, k)), vb = PROTECT(Rf_allocMatrix(REALSXP, k, k));
+  SEXP ve = PROTECT(Rf_allocVector(REALSXP, k)), MSx = PROTECT(Rf_allocVector(REALSXP, k)), W = PROTECT(Rf_allocMatrix(REALSXP, rr, k));
+  double *c1 = (double *)R_alloc(maxit > 0 ? maxit : 1, sizeof(double)), *c2 = (double *)R_alloc(maxit > 0 ? maxit : 1, sizeof(double));
+  double *c3 = (double *)R_alloc(maxit > 0 ? maxit : 1, sizeof(double));
+  int its = 0;
+  chk(bwgr_mrr_dense(0, REAL(X), BWGR_HOST, (int64_t)n, (int64_t)r, (int64_t)n, REAL(Y), k, REAL(opts), nopts, REAL(mu), REAL(b), REAL(hat), REAL(h2),
+                     REAL(GC), REAL(vb), REAL(ve), REAL(MSx), c1, c2, c3, &its));
+  SEXP cB = PROTECT(Rf_allocVector(REALSXP, its)), cH = PROTECT(Rf_allocVector(REALSXP, its)), cV = PROTECT(Rf_allocVector(REALSXP, its));
+  for (int i = 0; i < its; i++) { REAL(cB)[i] = c1[i]; REAL(cH)[i] = c2[i]; REAL(cV)[i] = c3[i]; }
+  for (R_xlen_t i = 0; i < (R_xlen_t)rr * k; i++) REAL(W)[i] = 1.0;                     /* b_Weights: no non-linear factor */
+  const char *nm[] = {"mu", "b", "hat", "h2", "GC", "vb", "ve", "MSx", "cnvB", "cnvH2", "cnvV", "b_Weights", "Its"};
+  SEXP out = PROTECT(named_list(13, nm));
+  SEXP v[] = {mu, b, hat, h2, GC, vb, ve, MSx, cB, cH, cV, W};
+  for (int i = 0; i < 12; i++) SET_VECTOR_ELT(out, i, v[i]);
+  SET_VECTOR_ELT(out, 12, Rf_ScalarReal((double)its));
+  UNPROTECT(13);
+  return out;
+}
+
 /* per-trait ridge fits: solver1x / solver1xF(Y, X, maxit, tol, df0) src/RcppEigen20230423.cpp:1410-1443, :1613-1646 -> the p effects;
  * UVBETA / FUVBETA / XFUVBETA(Y, X) :1506-1515, :1709-1753 -> p x k; ZFUVBETA(Y, X) :1807-1816 -> (p + 2) x k, rows 1 - ve / vy, mu, b.
  * variant: BWGR_UVB_*.  Y: NA = missing (solver1x: those rows are left out).  The float variants' inputs are rounded by the R front-end. */
@@ -594,7 +621,7 @@ static const R_CallMethodDef CallEntries[] = {   /* as src/RcppExports.cpp:1152-
   {"bwgrhip_panel", (DL_FUNC)&bwgrhip_panel, 2}, {"bwgrhip_KMUP", (DL_FUNC)&bwgrhip_KMUP, 9}, {"bwgrhip_KMUP2", (DL_FUNC)&bwgrhip_KMUP2, 10},
   {"bwgrhip_Bayes", (DL_FUNC)&bwgrhip_Bayes, 8}, {"bwgrhip_Bayes2", (DL_FUNC)&bwgrhip_Bayes2, 9},
   {"bwgrhip_wgr", (DL_FUNC)&bwgrhip_wgr, 14}, {"bwgrhip_em", (DL_FUNC)&bwgrhip_em, 7},
-  {"bwgrhip_MRR3", (DL_FUNC)&bwgrhip_MRR3, 3}, {"bwgrhip_MRR3F", (DL_FUNC)&bwgrhip_MRR3F, 3},
+  {"bwgrhip_MRR3", (DL_FUNC)&bwgrhip_MRR3, 3}, {"bwgrhip_MRR3F", (DL_FUNC)&bwgrhip_MRR3F, 3}, {"bwgrhip_mrr_dense", (DL_FUNC)&bwgrhip_mrr_dense, 3},
   {"bwgrhip_solver1x", (DL_FUNC)&bwgrhip_solver1x, 6}, {"bwgrhip_UVBETA", (DL_FUNC)&bwgrhip_UVBETA, 3},
   {"bwgrhip_uvbeta_dense", (DL_FUNC)&bwgrhip_uvbeta_dense, 6}, {"bwgrhip_panel_xb", (DL_FUNC)&bwgrhip_panel_xb, 2},
   {"bwgrhip_uvbeta2", (DL_FUNC)&bwgrhip_uvbeta2, 6},
