@@ -1462,7 +1462,9 @@ extern "C" int bwgr_panel_centred(bwgr_panel *P, int *centred) {
 #include "wgr_em_host.hip.h"
 #include "group_host.hip.h"
 #include "mtfit_host.hip.h"
-#include "fits_host.hip.h"
+#include "mrr_host.hip.h"
+#include "uvb_host.hip.h"
+#include "kernels_host.hip.h"
 #include "pegs_host.hip.h"
 #include "pegsx_host.hip.h"
 

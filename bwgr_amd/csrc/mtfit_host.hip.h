@@ -1,5 +1,5 @@
-// bwgr_amd/csrc/mtfit_host.hip.h -- the host scaffolding of the multi-trait fits: what bwgr_mrr (fits_host.hip.h), bwgr_pegs (pegs_host.hip.h) and
-// bwgr_pegsx (pegsx_host.hip.h) do alike around their own algebra.  Part of bwgr_hip.hip, before fits_host.hip.h; it defines no kernel (they are
+// bwgr_amd/csrc/mtfit_host.hip.h -- the host scaffolding of the multi-trait fits: what bwgr_mrr (mrr_host.hip.h), bwgr_pegs (pegs_host.hip.h) and
+// bwgr_pegsx (pegsx_host.hip.h) do alike around their own algebra.  Part of bwgr_hip.hip, before mrr_host.hip.h; it defines no kernel (they are
 // mrr.hip.h and pegs.hip.h) and no entry but the plan hooks of the plans it holds.
 //   the plans:   mrr_plan (LDS of k_mrr_solve / k_mrr_linv), pegs_dense_plan (the dense leg), pegs_sparse_plan (the sparse legs), the grids
 //                the launch sites share

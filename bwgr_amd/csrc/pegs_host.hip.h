@@ -1,6 +1,6 @@
 // bwgr_amd/csrc/pegs_host.hip.h -- the host entry of PEGS / PEGSZ (src/RcppEigenX20251203.cpp:10-194, :576-808) and of
 // PEGS_sparse / PEGSZ_sparse (:811-1007, :1010-1250; section 4.12), which are the same fit on sparse effects under `text` 1 and 2.  Part of
-// bwgr_hip.hip, after fits_host.hip.h.  It holds the fit's own algebra: the option checks, the start values and the per-sweep tail (pegs_tail.h),
+// bwgr_hip.hip, after kernels_host.hip.h. It holds the fit's own algebra: the option checks, the start values and the per-sweep tail (pegs_tail.h),
 // the mu shift and the outputs; the effect checks, the device arrays and every repeated step are MtFit's (mtfit_host.hip.h).  It defines no kernel.
 //   once:       per panel effect k_mrr_setup_cols (uncentred), per dense effect k_pegs_dense_setup, per sparse effect k_pegs_sparse_setup;
 //               k_mrr_tilde(mode 2) -> MSx

@@ -1,4 +1,4 @@
-// bwgr_amd/csrc/traits.h -- what the fp64 fits (fits_host.hip.h) do on the host before a kernel runs: reading Y, the missingness patterns,
+// bwgr_amd/csrc/traits.h -- what the fp64 fits (mrr_host.hip.h, uvb_host.hip.h) do on the host before a kernel runs: reading Y, the missingness patterns,
 // the observed-row masks in the layouts the kernels read, Z without its padding, and the cumulative marker order.  Plain C++17, no device
 // runtime: tests/traits_check.cpp runs it as a program of its own under the sanitizers (tests/test_traits_cpu.py).
 #pragma once

@@ -22,6 +22,7 @@
 // nothing of it is written, and the tails skip it.
 #pragma once
 #include "mrr.hip.h"
+#include "uvb_tail.h"
 
 namespace bwgr {
 
@@ -30,12 +31,7 @@ static constexpr int UVB_ST = 16;         // traits per solve workgroup
 static constexpr int UVB_PASS_WG = 64;    // workgroups of k_uvb_pass at most (= partial dot sets a solve reduces)
 static constexpr int UVB_NP = 32;         // partials of the tail reductions
 static constexpr int UVB_GSTR = MRR_MB * MRR_MB + 4;   // words between two staged Gram matrices: 16-byte aligned, four banks apart
-
-struct UvbTrait {
-  double lam, nt;    // lambda of this sweep; observed rows
-  int pat, slot;     // the trait's pattern within its group; the LDS slot its Gram matrix is staged in (-1: read from global memory)
-  int active, pad_;
-};
+// (UvbTrait, what the kernels read of a trait: uvb_tail.h)
 
 // where trait t of a group sits in the pass's LDS tiles: thread slice tq = t & 3 holds its 16 traits t = tq + 4 i side by side
 __device__ __forceinline__ int uvb_perm(int t) { return (t & 3) * 16 + (t >> 2); }

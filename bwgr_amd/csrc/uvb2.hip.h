@@ -15,14 +15,11 @@
 // writes anything.  Per-column values live in the trait's slices of global arrays, so q has no limit.  Rows n .. ld - 1 of E are never touched.
 #pragma once
 #include "uvbd.hip.h"
+#include "uvb_tail.h"
 
 namespace bwgr {
 
-struct Uvb2Trait {
-  double lam, nt;       // lambda_1 of this sweep; observed rows
-  int64_t moff;         // where the trait's row mask (bytes, 0xFF = observed) starts in the masks' array
-  int run, pad_;        // the leg runs this trait in this sweep
-};
+// (Uvb2Trait, what the leg reads of a trait: uvb_tail.h)
 static constexpr int UVB2_NLEG = 3;   // leg[t][.]: sum (delta b1)^2, b1'b1, tilde1'b1
 
 struct Uvb2Args {

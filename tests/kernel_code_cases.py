@@ -150,7 +150,7 @@ def xyt_plan(F, S, kchunk=0):
 
 
 def rows_grid(ld, p):
-    """kfin_rows_grid of fits_host.hip.h: (row workgroups, column workgroups) of k_kfin_xs / k_kfin2_rowsq"""
+    """kfin_rows_grid of kernels_host.hip.h: (row workgroups, column workgroups) of k_kfin_xs / k_kfin2_rowsq"""
     ysplit = max(1, min(65535, (p + 511) // 512, 2048 // (ld // 128) + 1))
     cpw = -(-p // ysplit)
     return ld // 128, -(-p // cpw)

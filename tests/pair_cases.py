@@ -41,7 +41,7 @@ EXPECT = {
                               accumulate=False),
 }
 XYT_FIELDS = ("chunk", "nchunks", "tiles", "wgs", "ws_bytes", "Tr", "Tc", "sub", "piece")
-SUMD_PARTS = 1024      # XXT_SUMD_PARTS of fits_host.hip.h: the fixed grid of k_kfin_sumd_stage1
+SUMD_PARTS = 1024      # XXT_SUMD_PARTS of kernels_host.hip.h: the fixed grid of k_kfin_sumd_stage1
 
 
 def xyt_plan(nf, ns, p, kchunk=0, xmax=2):

@@ -25,9 +25,11 @@ import sem_restatement as SR
 import uvb_restatement as UR
 
 
-def solver2x(Y, X1, X2, maxit=100, tol=10e-7, df0=20.0, lam=None):
+def solver2x(Y, X1, X2, maxit=100, tol=10e-7, df0=20.0, lam=None, record=None):
     """One trait on the rows it is given.  dict(b1, b2, mu, h2, ve, vb1, vb2, its, cnv, XX1, XX2, lam1, lam2, trace); trace[s] = cnv after
-    sweep s.  lam = (lambda_1, lambda_2): fixed lambdas in place of the variance updates (the ridge pin of the CPU tests)."""
+    sweep s.  lam = (lambda_1, lambda_2): fixed lambdas in place of the variance updates (the ridge pin of the CPU tests).  record: as
+    uvb_restatement.solver's, with X2 as that solver's X (TrXSX, vb, lam, p, bb, tb, db2 are X2's) and X1's beside them: TrXSX1, vb1, lam1,
+    q1 = p1, and per sweep the leg's three sums d1 = sum (delta b_1)^2, bb1 = b_1'b_1, tb1 = tilde1'b_1."""
     Y = np.asarray(Y, np.float64)
     X1 = np.array(X1, np.float64, copy=True)
     X2 = np.array(X2, np.float64, copy=True)
@@ -54,6 +56,9 @@ def solver2x(Y, X1, X2, maxit=100, tol=10e-7, df0=20.0, lam=None):
     e = y.copy()                                                     # :1460
     logtol = np.log10(tol) if tol > 0 else -np.inf
     numit, cnv, trace = 0, np.nan, []
+    if record is not None:
+        record.update(nt=n, mu=mu, sumy=y.sum(), vy=vy, TrXSX=TrXSX2, TrXSX1=TrXSX1, ve=ve, vb=vb2, vb1=vb1, lam=lam2, lam1=lam1, logtol=logtol,
+                      df0=df0, p=p2, q1=p1, sweeps=[])
 
     def leg(X, XX, b, lmb, order):
         for J in order:
@@ -71,6 +76,10 @@ def solver2x(Y, X1, X2, maxit=100, tol=10e-7, df0=20.0, lam=None):
             leg(X1, XX1, b_1, lam1, UR.order(p1, numit))             # :1468, :1470-1473
         if run2:
             leg(X2, XX2, b_2, lam2, UR.order(p2, numit))             # :1469, :1474-1477
+        if record is not None:
+            with np.errstate(all="ignore"):
+                sums = dict(se=e.sum(), ey=e @ y, ee=e @ e, bb=b_2 @ b_2, tb=tilde2 @ b_2, db2=((beta02 - b_2) ** 2).sum(),
+                            d1=((beta01 - b_1) ** 2).sum(), bb1=b_1 @ b_1, tb1=tilde1 @ b_1)
         mu0 = e.mean(); mu += mu0; e -= mu0                          # :1478
         with np.errstate(all="ignore"):
             ve = (e @ e + e @ y + ve0) / (2 * n - 1 + df0)           # :1479-1481
@@ -86,7 +95,10 @@ def solver2x(Y, X1, X2, maxit=100, tol=10e-7, df0=20.0, lam=None):
             cnv = np.log10(((beta01 - b_1) ** 2).sum() + ((beta02 - b_2) ** 2).sum())   # :1486
         trace.append(cnv)
         numit += 1
-        if cnv < logtol or numit == maxit or np.isnan(cnv):          # :1487
+        stop = cnv < logtol or numit == maxit or np.isnan(cnv)       # :1487
+        if record is not None:
+            record["sweeps"].append(dict(sums, mu=mu, ve=ve, vb=vb2, vb1=vb1, lam=lam2, lam1=lam1, cnv=cnv, its=numit, on=not stop))
+        if stop:
             break
     with np.errstate(all="ignore"):
         h2 = 1 - ve / vy                                             # departure 4

@@ -4,7 +4,7 @@ heights and chunks it is listed for; a change of a grid or of a plan rule that m
 dropping that code from what the GPU suite compares with a reference.
 
 Two figures of the table are the exception: `sumd` and `rows_s` restate constants that no hook reports -- XXT_SUMD_PARTS = 1 024 workgroups of
-k_kfin_sumd_stage1 and the 128 rows per workgroup of kfin_rows_grid (fits_host.hip.h) -- so a change of either would leave them as they are.
+k_kfin_sumd_stage1 and the 128 rows per workgroup of kfin_rows_grid (kernels_host.hip.h) -- so a change of either would leave them as they are.
 They record what the shapes were chosen for; test_the_unreported_constants_are_the_sources reads the two constants from the source text, which
 is as near as a test without a hook comes."""
 import numpy as np
@@ -40,7 +40,7 @@ def test_pairs_reach_every_regime_together():
 def test_the_unreported_constants_are_the_sources():
     import os
     import re
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bwgr_amd", "csrc", "fits_host.hip.h")).read()
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bwgr_amd", "csrc", "kernels_host.hip.h")).read()
     assert int(re.search(r"constexpr int XXT_SUMD_PARTS = (\d+);", src).group(1)) == pc.SUMD_PARTS
     grid = src[src.index("static inline dim3 kfin_rows_grid"):]
     assert "return dim3((unsigned)(ld / 128)," in grid[:grid.index("\n}")]

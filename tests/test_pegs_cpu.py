@@ -281,14 +281,15 @@ def test_shared_effect_check_runs_without_a_device_and_names_its_caller():
 def test_repeated_steps_are_launched_in_one_file_only():
     """what the multi-trait entries do alike is MtFit's: these kernels are launched, and these calls made, in mtfit_host.hip.h and in none of
     the entries' files (the per-trait fits' own pack_row_bits call, with other arguments, is not meant)"""
-    src = {name: open(os.path.join(CSRC, name)).read() for name in ("fits_host.hip.h", "pegs_host.hip.h", "pegsx_host.hip.h", "mtfit_host.hip.h")}
+    src = {name: open(os.path.join(CSRC, name)).read() for name in ("mrr_host.hip.h", "uvb_host.hip.h", "kernels_host.hip.h", "pegs_host.hip.h", "pegsx_host.hip.h", "mtfit_host.hip.h")}
     pats = [r"hipLaunchKernelGGL\(\s*%s\s*," % kn for kn in ("k_mrr_tilde", "k_mrr_ey", "k_mrr_hat_part", "k_pegs_dense_leg", "k_pegs_dense_setup", "k_mrr_setup_cols")]
     pats += [re.escape("pack_row_bits(S, (int64_t)0"), r"hipFuncSetAttribute\([^;]*\bk_mrr_solve\b"]
     for pat in pats:
         where = sorted(name for name, txt in src.items() if re.search(pat, txt))
         assert where == ["mtfit_host.hip.h"], (pat, where)
     main = open(os.path.join(CSRC, "bwgr_hip.hip")).read()
-    assert main.index('#include "mtfit_host.hip.h"') < main.index('#include "fits_host.hip.h"') < main.index('#include "pegs_host.hip.h"')
+    at = [main.index('#include "%s_host.hip.h"' % name) for name in ("mtfit", "mrr", "uvb", "kernels", "pegs")]
+    assert at == sorted(at), at
 
 
 def test_effect_kinds():

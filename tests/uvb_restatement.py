@@ -22,9 +22,11 @@ def order(p, sweep):
     return _ORDERS[(p, sweep)]
 
 
-def solver(Y, X, variant="D", maxit=100, tol=10e-7, df0=20.0, lam=None):
+def solver(Y, X, variant="D", maxit=100, tol=10e-7, df0=20.0, lam=None, record=None):
     """One trait on the rows it is given.  dict(b, mu, h2, ve, vb, its, cnv, XX, trace); trace[s] = cnv after sweep s.  lam: a fixed lambda
-    for variant X in place of XX.mean() (the ridge pin of the CPU tests)."""
+    for variant X in place of XX.mean() (the ridge pin of the CPU tests).  record: a dict that receives the start values (nt, mu, sumy, vy,
+    TrXSX, ve, vb, lam, and logtol, df0, p as used) and, under "sweeps", per sweep the six sums a sweep leaves, taken before the mean is
+    removed from e (se, ey, ee, bb, tb, db2), with what the tail makes of them (mu, ve, vb, lam, cnv, its, on: the trait goes on)."""
     assert variant in "DFXZ"
     if variant != "D":
         tol = float(np.float32(tol)); df0 = float(np.float32(df0))
@@ -48,6 +50,8 @@ def solver(Y, X, variant="D", maxit=100, tol=10e-7, df0=20.0, lam=None):
     e = y.copy()                                                     # :1422
     logtol = np.log10(tol) if tol > 0 else -np.inf
     numit, cnv, trace = 0, np.nan, []
+    if record is not None:
+        record.update(nt=n, mu=mu, sumy=y.sum(), vy=vy, TrXSX=TrXSX, ve=ve, vb=vb, lam=lmb, logtol=logtol, df0=df0, p=p, sweeps=[])
     while numit < maxit:                                             # :1426
         beta0 = b.copy()                                             # :1427
         for J in order(p, numit):                                    # :1428-1429
@@ -58,6 +62,9 @@ def solver(Y, X, variant="D", maxit=100, tol=10e-7, df0=20.0, lam=None):
             with np.errstate(all="ignore"):
                 b1 = (e @ X[:, J] + XX[J] * b0) / (XX[J] + lmb)      # :1431
             e -= X[:, J] * (b1 - b0); b[J] = b1                      # :1432
+        if record is not None:
+            with np.errstate(all="ignore"):
+                sums = dict(se=e.sum(), ey=e @ y, ee=e @ e, bb=b @ b, tb=tilde @ b, db2=((beta0 - b) ** 2).sum())
         mu0 = e.mean(); mu += mu0; e -= mu0                          # :1433
         with np.errstate(all="ignore"):
             if variant in "DF":
@@ -71,7 +78,10 @@ def solver(Y, X, variant="D", maxit=100, tol=10e-7, df0=20.0, lam=None):
             cnv = np.log10(((beta0 - b) ** 2).sum())                 # :1440
         trace.append(cnv)
         numit += 1
-        if cnv < logtol or numit == maxit or np.isnan(cnv):          # :1441
+        stop = cnv < logtol or numit == maxit or np.isnan(cnv)       # :1441
+        if record is not None:
+            record["sweeps"].append(dict(sums, mu=mu, ve=ve, vb=vb, lam=lmb, cnv=cnv, its=numit, on=not stop))
+        if stop:
             break
     with np.errstate(all="ignore"):
         h2 = np.nan if variant == "X" else 1 - ve / vy               # :1802
