@@ -69,6 +69,7 @@ def lib():
     L.bwgr_uvbeta2.argtypes = [vp, c_d, i64, i64, c_d, i64, i32, f64, f64, c_d, c_d, c_d, c_d, c_d, c_d, c_d, C.POINTER(i32), c_d]
     L.bwgr_debug_panel_plan.argtypes = [i32, i64, i64, i32, i32, i32, i32, i32, C.POINTER(i64)]
     L.bwgr_debug_aux_plan.argtypes = [i32, i64, i64, C.POINTER(i64)]
+    L.bwgr_debug_sweep_plan.argtypes = [i32, i64, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i64)]
     L.bwgr_panel_crossprod.argtypes = [vp, vp, i64, i32]
     L.bwgr_panel_kernel.argtypes = [vp, i32, f64, i32, vp, i64, i32]
     L.bwgr_debug_xxt_plan.argtypes = [i64, i64, i32, i64, C.POINTER(i64)]
@@ -135,7 +136,7 @@ def device_count():
 
 
 EXPORTS = ["bwgr_abi_version", "bwgr_last_error", "bwgr_device_count", "bwgr_panel_create", "bwgr_panel_destroy",
-           "bwgr_panel_set_stream", "bwgr_panel_info", "bwgr_panel_pipeline", "bwgr_panel_clone", "bwgr_em", "bwgr_em_order", "bwgr_mrr", "bwgr_mrr_dense", "bwgr_debug_mrr_dense_plan", "bwgr_uvbeta", "bwgr_debug_uvb_plan", "bwgr_uvbeta_dense", "bwgr_debug_uvbd_plan", "bwgr_panel_xb", "bwgr_uvbeta2", "bwgr_pegs", "bwgr_pegs_ex", "bwgr_debug_pegs_plan", "bwgr_debug_pegs_sparse_plan", "bwgr_pegsx", "bwgr_pegsx_ex", "bwgr_debug_pegsx_plan", "bwgr_debug_pegs_launch_plan", "bwgr_debug_pegsx_timing", "bwgr_panel_max_concurrent", "bwgr_panel_max_pairs", "bwgr_debug_occupancy_fits", "bwgr_debug_stream3_dma", "bwgr_debug_sweep3_kernel", "bwgr_debug_mrr_plan", "bwgr_debug_panel_plan", "bwgr_debug_aux_plan", "bwgr_panel_crossprod", "bwgr_panel_kernel", "bwgr_debug_xxt_plan", "bwgr_panel_crossprod2", "bwgr_panel_kernel2", "bwgr_debug_xyt_plan", "bwgr_panel_stats", "bwgr_kmup", "bwgr_kmup2", "bwgr_chain_create",
+           "bwgr_panel_set_stream", "bwgr_panel_info", "bwgr_panel_pipeline", "bwgr_panel_clone", "bwgr_em", "bwgr_em_order", "bwgr_mrr", "bwgr_mrr_dense", "bwgr_debug_mrr_dense_plan", "bwgr_uvbeta", "bwgr_debug_uvb_plan", "bwgr_uvbeta_dense", "bwgr_debug_uvbd_plan", "bwgr_panel_xb", "bwgr_uvbeta2", "bwgr_pegs", "bwgr_pegs_ex", "bwgr_debug_pegs_plan", "bwgr_debug_pegs_sparse_plan", "bwgr_pegsx", "bwgr_pegsx_ex", "bwgr_debug_pegsx_plan", "bwgr_debug_pegs_launch_plan", "bwgr_debug_pegsx_timing", "bwgr_panel_max_concurrent", "bwgr_panel_max_pairs", "bwgr_debug_occupancy_fits", "bwgr_debug_stream3_dma", "bwgr_debug_sweep3_kernel", "bwgr_debug_mrr_plan", "bwgr_debug_panel_plan", "bwgr_debug_aux_plan", "bwgr_debug_sweep_plan", "bwgr_panel_crossprod", "bwgr_panel_kernel", "bwgr_debug_xxt_plan", "bwgr_panel_crossprod2", "bwgr_panel_kernel2", "bwgr_debug_xyt_plan", "bwgr_panel_stats", "bwgr_kmup", "bwgr_kmup2", "bwgr_chain_create",
            "bwgr_chain_create_sharded", "bwgr_chain_sweep_blocks", "bwgr_chain_round_sweep", "bwgr_chain_round_apply", "bwgr_chain_get_sums_dev", "bwgr_chain_end_iteration_dev", "bwgr_chain_get_sums", "bwgr_chain_end_iteration",
            "bwgr_chain_destroy", "bwgr_chain_run", "bwgr_chain_run_pair", "bwgr_chain_sync", "bwgr_chain_iterations", "bwgr_chain_result",
            "bwgr_chain_state", "bwgr_chain_sweep_ms", "bwgr_chain_redo_count", "bwgr_group_sound", "bwgr_panel_centred", "bwgr_panel_set_centred", "bwgr_bayes", "bwgr_bayes2", "bwgr_wgr", "bwgr_wgr_ex", "bwgr_synth_genotypes",

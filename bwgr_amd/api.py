@@ -1186,6 +1186,25 @@ def mrr_dense_plan(n, r, k, npat):
     return dict(zip(names, [int(v) for v in out]))
 
 
+SWEEP_PLAN_FIELDS = (("engine", "gate", "gate3_bits", "lag", "nfeed", "g16", "R3", "K3", "sub", "pf", "pf2", "dbg3", "qsplit", "skip_vb", "fixed3", "fx", "nd",
+                      "npf", "ahead", "nq", "wsub", "wK3", "guarded", "draws", "nspins")
+                     + tuple("spin%d_%s" % (i, f) for i in range(3) for f in ("kernel", "grid", "resident", "threads", "lds"))
+                     + tuple("redo_" + f for f in ("engine", "lag", "nfeed", "g16", "fx", "nd", "npf", "ahead", "nq", "wsub", "wK3"))
+                     + ("spin_run", "spin_redo", "escale_reset", "pre3", "cen3", "escale_w", "affine_inv", "cen_pre", "spec", "spec_sel", "cen_run", "cen_redo",
+                        "redo_spec", "redo_cen", "vb_fill", "withhold"))
+
+
+def sweep_plan(is_f32, n, p, block=0, nwg=0, kind=0, xmax=2, gram16=True, flags=0, blk_begin=0, blk_end=0, mode=0, state=0):
+    """bwgr_debug_sweep_plan (host arithmetic, no GPU): every field of the plan of one sweep -- engine, gate, depth, launch shapes, the redo,
+    the helper kernels -- over a panel planned as bwgr_debug_panel_plan plans it under the BWGR_* switches of the environment.  flags: the
+    sweep's SWF_* bits; mode 0 a sweep alone, 1 its redo, 2 a pair; state: bit 0 clones alive, 1 a clone, 2 crowded, 3 withheld.  The fields are
+    described in include/bwgr.h; a combination the library never plans raises BwgrError."""
+    out = (C.c_int64 * len(SWEEP_PLAN_FIELDS))()
+    check(_lib.lib().bwgr_debug_sweep_plan(int(bool(is_f32)), int(n), int(p), int(block), int(nwg), int(kind), int(xmax), int(bool(gram16)), int(flags),
+                                           int(blk_begin), int(blk_end), int(mode), int(state), out))
+    return dict(zip(SWEEP_PLAN_FIELDS, [int(v) for v in out]))
+
+
 # ---- PEGS / PEGSZ: multi-trait fits over several designs (bwgr_pegs, include/bwgr.h) ----
 PEGS_KEYS = ("mu", "b", "hat", "h2", "GC", "bend", "numit", "cnv")
 

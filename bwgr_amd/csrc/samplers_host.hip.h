@@ -170,9 +170,9 @@ extern "C" int bwgr_chain_sweep_blocks(bwgr_chain *C, int blk_begin, int blk_end
   HIPCHK(hipSetDevice(P->data->device));
   SweepArgs a;
   chain_args(C, blk_begin, blk_end, a);
-  SweepPlan pl; int need = 0;
-  CHK(sweep_begin(P, a, pl, &need));
-  hipEvent_t e0, e1;
+  SweepTrain t; t.P[0] = P; t.a[0] = &a;
+  CHK(train_begin(t));
+  hipEvent_t &e0 = t.ev[0][0], &e1 = t.ev[0][1];
   HIPCHK(hipEventCreate(&e0));
   if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail(BWGR_EHIP, "sweep_blocks: hipEventCreate failed"); }
   // the per-marker constants and speculative terms of an iteration depend on the state at its start only (a block's b is
@@ -181,20 +181,15 @@ extern "C" int bwgr_chain_sweep_blocks(bwgr_chain *C, int blk_begin, int blk_end
   bool prestaged = false;
   if (P->ps_owner != C || P->ps_iter != C->done) {
     SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->data->plan.nblocks;
-    launch_prestage(P, all, pl);
+    launch_prestage(P, all, t.pl[0]);
     P->ps_owner = C; P->ps_iter = C->done;
     prestaged = true;
   }
-  hipError_t he = hipEventRecord(e0, P->stream);
-  if (he == hipSuccess) { launch_sweep_kernel(P, a, pl); he = hipGetLastError(); }
-  if (he == hipSuccess && prestaged && C->done + 1 < C->iit) {   // the next iteration's variates, beside this sweep
-    SweepArgs all = a; all.blk_begin = 0; all.blk_end = (int)P->data->plan.nblocks;
-    draws_ahead(P, all, pl, e0);
-  }
-  if (he == hipSuccess) he = hipEventRecord(e1, P->stream);
+  t.draws_next = prestaged && C->done + 1 < C->iit;   // the next iteration's variates, beside this sweep
+  const hipError_t he = train_launch(t);
   if (he != hipSuccess) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return fail(BWGR_EHIP, "sweep_blocks: %s", hipGetErrorString(he)); }
   C->ev.push_back(e0); C->ev.push_back(e1);
-  guard_mark(P, P->stream, need);
+  train_end(t);
   if (C->ev.size() >= 4096) CHK(bwgr_chain_sweep_ms(C, nullptr, nullptr));   // bound the number of live events
   return BWGR_OK;
 }
@@ -295,7 +290,8 @@ extern "C" int bwgr_chain_run_pair(bwgr_chain *C0, bwgr_chain *C1, int iters) {
   if (iters < 0 || C0->done + iters > C0->iit || C1->done + iters > C1->iit) return fail(BWGR_EINVAL, "chain_run_pair: %d more iterations exceed it", iters);
   SweepArgs t0, t1;
   chain_args(C0, 0, (int)P0->data->plan.nblocks, t0); chain_args(C1, 0, (int)P1->data->plan.nblocks, t1);
-  if (plan_sweep(P0, t0, false).engine != 3 || plan_sweep(P1, t1, false).engine != 3 || !P0->qsum3 || !P1->qsum3)
+  const SweepPlan q0 = plan_sweep(sweep_facts(P0), t0.flags, t0.blk_begin, t0.blk_end, SWEEP_PAIR), q1 = plan_sweep(sweep_facts(P1), t1.flags, t1.blk_begin, t1.blk_end, SWEEP_PAIR);
+  if (q0.engine != 3 || q1.engine != 3 || !P0->qsum3 || !P1->qsum3)
     return fail(BWGR_EINVAL, "chain_run_pair: both chains must be selection models on a panel with k_sweep3");
   if (s3p_streamer_lds(P0->data->plan3.R3) > (size_t)160 * 1024) return fail(BWGR_EINVAL, "chain_run_pair: the paired streamers' LDS does not fit");
   HIPCHK(hipSetDevice(P0->data->device));
@@ -318,38 +314,28 @@ extern "C" int bwgr_chain_run_pair(bwgr_chain *C0, bwgr_chain *C1, int iters) {
     PX->stream = s0;
   }
   // the pair's one launch, resident beside the other streams' sweeps
-  P0->force3 = P1->force3 = true;   // (while the pair runs, every plan of either handle is that launch)
   int need = 0;
-  int rc = sweep_guard(P0, plan_sweep(P0, t0, false), s0, P1, &need);
+  int rc = sweep_guard(P0, q0, s0, P1, &need);
   for (int k = 0; k < iters && rc == BWGR_OK; ++k) {
     SweepArgs a0, a1;
     chain_args(C0, 0, (int)P0->data->plan.nblocks, a0); chain_args(C1, 0, (int)P1->data->plan.nblocks, a1);
-    const SweepPlan pl0 = plan_sweep(P0, a0, false), pl1 = plan_sweep(P1, a1, false);
-    a0.lag = pl0.lag; a1.lag = pl1.lag;
-    if ((rc = reset_exchange(P0)) != BWGR_OK || (rc = reset_exchange(P1)) != BWGR_OK) break;
-    launch_prestage(P0, a0, pl0); launch_prestage(P1, a1, pl1);
+    SweepTrain t; t.n = 2; t.P[0] = P0; t.P[1] = P1; t.a[0] = &a0; t.a[1] = &a1; t.need = need;
+    if ((rc = train_begin(t)) != BWGR_OK) break;
+    launch_prestage(P0, a0, t.pl[0]); launch_prestage(P1, a1, t.pl[1]);
     P0->ps_owner = C0; P0->ps_iter = C0->done; P1->ps_owner = C1; P1->ps_iter = C1->done;
-    a0.gate3 = pl0.gate3; a1.gate3 = pl1.gate3;
-    if (P0->debug_withhold || P1->debug_withhold) { a0.flags |= SWF_DEBUG_WITHHOLD; a1.flags |= SWF_DEBUG_WITHHOLD; }
-    Sweep3Args A0, A1;
-    sweep3_args(P0, a0, pl0, A0); sweep3_args(P1, a1, pl1, A1);
-    hipEvent_t evs[4] = {nullptr, nullptr, nullptr, nullptr};   // both chains time the launch they share
+    hipEvent_t *evs[4] = {&t.ev[0][0], &t.ev[0][1], &t.ev[1][0], &t.ev[1][1]};   // both chains time the launch they share
     bool ev_ok = true;
-    for (int q = 0; q < 4 && ev_ok; ++q) ev_ok = hipEventCreate(&evs[q]) == hipSuccess;
-    if (!ev_ok) { for (hipEvent_t q : evs) if (q) (void)hipEventDestroy(q); rc = fail(BWGR_EHIP, "chain_run_pair: hipEventCreate failed"); break; }
-    (void)hipEventRecord(evs[0], s0); (void)hipEventRecord(evs[2], s0);
-    void *args[] = {&A0, &A1};
-    spin_launch(pl0.spins[0], s0, args);
-    (void)hipEventRecord(evs[1], s0); (void)hipEventRecord(evs[3], s0);
-    C0->ev.push_back(evs[0]); C0->ev.push_back(evs[1]); C1->ev.push_back(evs[2]); C1->ev.push_back(evs[3]);
-    guard_mark(P0, s0, need);
-    if (hipGetLastError() != hipSuccess) { rc = fail(BWGR_EHIP, "chain_run_pair: launch failed"); break; }
+    for (int q = 0; q < 4 && ev_ok; ++q) ev_ok = hipEventCreate(evs[q]) == hipSuccess;
+    if (!ev_ok) { for (hipEvent_t *q : evs) if (*q) (void)hipEventDestroy(*q); rc = fail(BWGR_EHIP, "chain_run_pair: hipEventCreate failed"); break; }
+    const hipError_t he = train_launch(t);
+    if (he != hipSuccess) { for (hipEvent_t *q : evs) (void)hipEventDestroy(*q); rc = fail(BWGR_EHIP, "chain_run_pair: launch failed: %s", hipGetErrorString(he)); break; }
+    C0->ev.push_back(t.ev[0][0]); C0->ev.push_back(t.ev[0][1]); C1->ev.push_back(t.ev[1][0]); C1->ev.push_back(t.ev[1][1]);
+    train_end(t);
     if ((rc = bwgr_chain_end_iteration(C0, nullptr)) != BWGR_OK) break;
     rc = bwgr_chain_end_iteration(C1, nullptr);
     if (C0->ev.size() >= 4096) (void)bwgr_chain_sweep_ms(C0, nullptr, nullptr);
     if (C1->ev.size() >= 4096) (void)bwgr_chain_sweep_ms(C1, nullptr, nullptr);
   }
-  P0->force3 = P1->force3 = false;
   return rc;
 }
 

@@ -72,7 +72,7 @@ struct Sweep3Args {
   unsigned long long *qsum;      // [nblocks][SW_MAXM][2] {low digits, high digits} << 8 | arrivals; zero before the launch
   unsigned long long *lists;     // [nblocks][S3_LSTRIDE] epoch-tagged words
   uint32_t epoch;                // this launch's tag (24 bits, never 0)
-  int dbg;                       // experiment switches (BWGR_DBG3)
+  int dbg;                       // experiment switches (BWGR_DBG3), and the two streamer bits below
   int pf;                        // blockIdx of the prefetcher workgroup (shares the sequencer's XCD), or -1
   int pf2;                       // ... of the second one (the included markers' distance-1 / 2 rows), or -1
   int qsplit;                    // 1: a marker's two slab-dot words hold digits 0-3 and 4-6 (k_sweep3's streamers: no LDS round trip between MFMA and atomics); 0: digits 0-2 and 3-6 (k_sweep3p)
@@ -80,6 +80,10 @@ struct Sweep3Args {
   const unsigned char *gx12;     // 16-bit panels: [nblocks][m][2][m] uint16, marker k of block b against blocks b+1 and b+2 side by side (k_near_rows):
                                  // an included marker's distance-1 and distance-2 rows in ONE LDS-DMA; nullptr: two requests from gx[0], gx[1]
 };
+
+// Sweep3Args::dbg, the streamer choice (plan_sweep sets them, k_sweep3's dispatch reads them): 128-row streamers that land their tiles by LDS-DMA
+// with four tile buffers (S3_DMA4 alone), or with three (S3_DMA3: an experiment, BWGR_STREAM3=d); neither: the register streamers
+static constexpr int S3_DMA4 = 1 << 22, S3_DMA3 = 1 << 23, S3_DMA_ANY = S3_DMA4 | S3_DMA3;
 
 // gx12[b][k][d-1][j] = gx[d-1][b+d][k][j] (zero past the last block)
 __global__ void k_near_rows(const uint16_t *g1, const uint16_t *g2, uint16_t *out, int m, int64_t nblocks) {
@@ -1690,8 +1694,8 @@ __global__ __launch_bounds__(SW_THREADS) void k_sweep3(const Sweep3Args A) {
   if (blockIdx.x == 0) { if (!(A.dbg & 1024)) s3_sequencer<GT, CEN>(A); }
   else if ((A.a.flags & SWF_DEBUG_WITHHOLD) && blockIdx.x == 1 && A.pf != 1) return;   // test hook: a streamer that never shows up
   else if (A.dbg & 2048) return;
-  else if ((A.dbg & (1 << 22)) && !(A.dbg & (1 << 23)) && A.R3 == 128) s3_streamer_dma<128, 4>(A);
-  else if ((A.dbg & (1 << 23)) && A.R3 == 128) s3_streamer_dma<128, 3>(A);
+  else if ((A.dbg & S3_DMA4) && !(A.dbg & S3_DMA3) && A.R3 == 128) s3_streamer_dma<128, 4>(A);
+  else if ((A.dbg & S3_DMA3) && A.R3 == 128) s3_streamer_dma<128, 3>(A);
   else s3_streamer(A);   // (a second streamer whose every load was inline asm with hand-counted waits measured no faster and was removed: DESIGN 9.0)
 }
 

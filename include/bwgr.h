@@ -542,6 +542,27 @@ int bwgr_panel_xb(bwgr_panel *P, const double *B, int64_t k, double *out /* n x 
  * bytes, solo streamer height allowed. */
 #define BWGR_PANEL_PLAN_NOUT 25
 int bwgr_debug_panel_plan(int is_f32, int64_t n, int64_t p, int block, int nwg, int kind, int xmax, int gram16, int64_t out[BWGR_PANEL_PLAN_NOUT]);
+/* host arithmetic of a sweep's plan (needs no GPU): what the library would decide for a sweep over a panel planned as bwgr_debug_panel_plan
+ * plans it (its first eight arguments; xmax < 0: no k_sweep3), taken to be one whose far Gram blocks fit -- k_sweep3 is there exactly when its
+ * plan fits, the distance-1 / 2 records exactly when gram16 holds as well, the affine engine's byte planes reach as far as the panel plan
+ * allows.  flags: the sweep's SWF_* flags (csrc/sweep.hip.h); blocks [blk_begin, blk_end), blk_end <= 0: the whole panel; mode 0: a sweep
+ * alone, 1: the fp64 redo of one, 2: a pair's (bwgr_chain_run_pair); state: bit 0 clones are alive, bit 1 the handle is a clone, bit 2 the
+ * panel is a shard among three or more on its device, bit 3 bwgr_debug_withhold is on.  BWGR_EINVAL for what the library never plans: a shape
+ * bwgr_panel_create refuses, a bad block range, clones or shards of a scratch panel, implicitly centred columns (SWF_CENTRE) but for a
+ * selection sweep on a panel with k_sweep3, the redo of a sweep that has none, a pair but of whole selection sweeps, columns as stored, on a
+ * panel with k_sweep3.  out[0..24]: engine (1 k_sweep, 2 k_sweep2, 3 k_sweep3, 4 k_sweep2w), the gate (0 none, 1 finite, 2 every sweep is
+ * k_sweep3's) and its float bits, then for the engine behind the gate lag, feeders, 16-bit staging; k_sweep3's R3, K3, streamers per slab, the
+ * two prefetch workgroups (-1: none), dbg3, qsplit, skip_vb, k_sweep3f; k_sweep2w's fx, nd, npf, ahead, nq, sub, K3; guarded, draws ahead,
+ * spin launches.  out[25..39]: the spin launches in launch order, five each: kernel (the instantiation's number in tests/sweep_plan_cases.py:
+ * KERNELS; -1 and zeros: none), grid, resident workgroups, threads, LDS bytes.  out[40..50]: the redo of a guarded sweep (zeros: none):
+ * engine, lag, feeders, 16-bit staging, fx, nd, npf, ahead, nq, sub, K3.  out[51..66], the helper kernels: spin launch of the engine behind
+ * the gate and of the redo (-1: none); k_escale_reset; k_escale on the gate and k_spec3; k_cen_tot / k_cen_scan / k_cen_begin / k_cen_end
+ * mode 0; k_escale at infinity; k_affine_inv; k_cen_tot / k_cen_scan mode 1; k_spec (1 int32, 2 fp64) and its sel argument; the mode of
+ * k_cen_begin / k_cen_end around the engine behind the gate and around the redo (-1: none); k_spec and k_cen_tot / k_cen_scan mode 2 in front
+ * of the redo; k_vb_fill; SWF_DEBUG_WITHHOLD.  (The snapshot trio goes with guarded.) */
+#define BWGR_SWEEP_PLAN_NOUT 67
+int bwgr_debug_sweep_plan(int is_f32, int64_t n, int64_t p, int block, int nwg, int kind, int xmax, int gram16, int flags, int blk_begin, int blk_end,
+                          int mode, int state, int64_t out[BWGR_SWEEP_PLAN_NOUT]);
 /* host arithmetic of the two launch rules around the sweep (needs no GPU), in the style of bwgr_debug_panel_plan, for an int8 (is_f32 = 0) or
  * float panel of p markers and ld padded rows (a positive multiple of 128, else BWGR_EINVAL).  out[0..2], the two-stage product X * coef behind
  * every hat and wgr's residual: column chunks, columns per chunk (the last chunk takes what is left), row workgroups.  out[3..4], the row
