@@ -25,14 +25,17 @@ import sem_restatement as SR
 import uvb_restatement as UR
 
 
-def solver2x(Y, X1, X2, maxit=100, tol=10e-7, df0=20.0, lam=None, record=None):
+def solver2x(Y, X1, X2, maxit=100, tol=10e-7, df0=20.0, lam=None, record=None, dtype=np.float64, dot1=None, dot2=None):
     """One trait on the rows it is given.  dict(b1, b2, mu, h2, ve, vb1, vb2, its, cnv, XX1, XX2, lam1, lam2, trace); trace[s] = cnv after
     sweep s.  lam = (lambda_1, lambda_2): fixed lambdas in place of the variance updates (the ridge pin of the CPU tests).  record: as
     uvb_restatement.solver's, with X2 as that solver's X (TrXSX, vb, lam, p, bb, tb, db2 are X2's) and X1's beside them: TrXSX1, vb1, lam1,
-    q1 = p1, and per sweep the leg's three sums d1 = sum (delta b_1)^2, bb1 = b_1'b_1, tb1 = tilde1'b_1."""
-    Y = np.asarray(Y, np.float64)
-    X1 = np.array(X1, np.float64, copy=True)
-    X2 = np.array(X2, np.float64, copy=True)
+    q1 = p1, and per sweep the leg's three sums d1 = sum (delta b_1)^2, bb1 = b_1'b_1, tb1 = tilde1'b_1.  dtype, dot1, dot2: as
+    uvb_restatement.solver's dtype and dot, one dot per leg."""
+    f = dtype
+    tol, df0 = f(tol), f(df0)
+    Y = np.asarray(Y, f)
+    X1 = np.array(X1, f, copy=True)
+    X2 = np.array(X2, f, copy=True)
     n, p1, p2 = X1.shape[0], X1.shape[1], X2.shape[1]                # :1448
     mu = Y.mean()                                                    # :1449
     y = Y - mu                                                       # :1450
@@ -51,8 +54,8 @@ def solver2x(Y, X1, X2, maxit=100, tol=10e-7, df0=20.0, lam=None, record=None):
         lam2 = ve / vb2 if run2 else np.nan
     vb01 = vb1 * df0; vb02 = vb2 * df0; ve0 = ve * df0               # :1462
     if lam is not None:
-        lam1, lam2 = lam
-    b_1 = np.zeros(p1); b_2 = np.zeros(p2)                           # :1458-1459
+        lam1, lam2 = f(lam[0]), f(lam[1])
+    b_1 = np.zeros(p1, f); b_2 = np.zeros(p2, f)                     # :1458-1459
     e = y.copy()                                                     # :1460
     logtol = np.log10(tol) if tol > 0 else -np.inf
     numit, cnv, trace = 0, np.nan, []
@@ -60,22 +63,23 @@ def solver2x(Y, X1, X2, maxit=100, tol=10e-7, df0=20.0, lam=None, record=None):
         record.update(nt=n, mu=mu, sumy=y.sum(), vy=vy, TrXSX=TrXSX2, TrXSX1=TrXSX1, ve=ve, vb=vb2, vb1=vb1, lam=lam2, lam1=lam1, logtol=logtol,
                       df0=df0, p=p2, q1=p1, sweeps=[])
 
-    def leg(X, XX, b, lmb, order):
+    def leg(X, XX, b, lmb, order, dot):
         for J in order:
             if not XX[J] > 0:                                        # departure 1
                 b[J] = 0.0
                 continue
             b0 = b[J]                                                # :1471, :1475
+            ex = e @ X[:, J] if dot is None else dot(e, X[:, J])
             with np.errstate(all="ignore"):
-                b1 = (e @ X[:, J] + XX[J] * b0) / (XX[J] + lmb)      # :1472, :1476
+                b1 = (ex + XX[J] * b0) / (XX[J] + lmb)               # :1472, :1476
             e[:] = e - X[:, J] * (b1 - b0); b[J] = b1                # :1473, :1477
 
     while numit < maxit:                                             # :1466
         beta01 = b_1.copy(); beta02 = b_2.copy()                     # :1467
         if run1:
-            leg(X1, XX1, b_1, lam1, UR.order(p1, numit))             # :1468, :1470-1473
+            leg(X1, XX1, b_1, lam1, UR.order(p1, numit), dot1)       # :1468, :1470-1473
         if run2:
-            leg(X2, XX2, b_2, lam2, UR.order(p2, numit))             # :1469, :1474-1477
+            leg(X2, XX2, b_2, lam2, UR.order(p2, numit), dot2)       # :1469, :1474-1477
         if record is not None:
             with np.errstate(all="ignore"):
                 sums = dict(se=e.sum(), ey=e @ y, ee=e @ e, bb=b_2 @ b_2, tb=tilde2 @ b_2, db2=((beta02 - b_2) ** 2).sum(),
@@ -105,24 +109,26 @@ def solver2x(Y, X1, X2, maxit=100, tol=10e-7, df0=20.0, lam=None, record=None):
     return dict(b1=b_1, b2=b_2, mu=mu, h2=h2, ve=ve, vb1=vb1, vb2=vb2, its=numit, cnv=cnv, XX1=XX1, XX2=XX2, lam1=lam1, lam2=lam2, trace=trace)
 
 
-def uvbeta2(Y, Z, X, maxit=100, tol=10e-7, df0=20.0):
+def uvbeta2(Y, Z, X, maxit=100, tol=10e-7, df0=20.0, dtype=np.float64, dot1=None, dot2=None):
     """solver2x per column of Y on the rows where it is not NaN, as MEGA and GSEM call it (:1553-1561, :1595-1603).  A column without observed
-    rows: departure 3.  dict(b1 [q x k], b2 [p x k], mu, h2, ve, vb1, vb2, its, cnv, trace [per trait])."""
-    Y = np.asarray(Y, np.float64)
+    rows: departure 3.  dict(b1 [q x k], b2 [p x k], mu, h2, ve, vb1, vb2, its, cnv, trace [per trait]).  dtype, dot1, dot2: as solver2x's."""
+    f = dtype
+    Y = np.asarray(Y, f)
     if Y.ndim == 1:
         Y = Y[:, None]
-    Z = np.asarray(Z, np.float64)
+    Z = np.asarray(Z, f)
     if Z.ndim == 1:
         Z = Z[:, None]
-    X = np.asarray(X, np.float64)
+    X = np.asarray(X, f)
     q, p, k = Z.shape[1], X.shape[1], Y.shape[1]
-    out = dict(b1=np.zeros((q, k)), b2=np.zeros((p, k)), mu=np.zeros(k), h2=np.zeros(k), ve=np.full(k, np.nan), vb1=np.full(k, np.nan),
-               vb2=np.full(k, np.nan), its=np.zeros(k, np.int32), cnv=np.full(k, np.nan), trace=[[] for _ in range(k)])
+    out = dict(b1=np.zeros((q, k), f), b2=np.zeros((p, k), f), mu=np.zeros(k, f), h2=np.zeros(k, f), ve=np.full(k, np.nan, f),
+               vb1=np.full(k, np.nan, f), vb2=np.full(k, np.nan, f), its=np.zeros(k, np.int32), cnv=np.full(k, np.nan, f),
+               trace=[[] for _ in range(k)])
     for t in range(k):
         w = ~np.isnan(Y[:, t])                                       # :1544
         if w.sum() == 0:
             continue
-        r = solver2x(Y[w, t], Z[w], X[w], maxit, tol, df0)           # subvec_f / submat_f, :1554-1557
+        r = solver2x(Y[w, t], Z[w], X[w], maxit, tol, df0, dtype=f, dot1=dot1, dot2=dot2)   # subvec_f / submat_f, :1554-1557
         out["b1"][:, t] = r["b1"]; out["b2"][:, t] = r["b2"]; out["trace"][t] = r["trace"]
         for key in ("mu", "h2", "ve", "vb1", "vb2", "its", "cnv"):
             out[key][t] = r[key]

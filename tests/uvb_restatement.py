@@ -22,16 +22,21 @@ def order(p, sweep):
     return _ORDERS[(p, sweep)]
 
 
-def solver(Y, X, variant="D", maxit=100, tol=10e-7, df0=20.0, lam=None, record=None):
+def solver(Y, X, variant="D", maxit=100, tol=10e-7, df0=20.0, lam=None, record=None, dtype=np.float64, dot=None):
     """One trait on the rows it is given.  dict(b, mu, h2, ve, vb, its, cnv, XX, trace); trace[s] = cnv after sweep s.  lam: a fixed lambda
     for variant X in place of XX.mean() (the ridge pin of the CPU tests).  record: a dict that receives the start values (nt, mu, sumy, vy,
     TrXSX, ve, vb, lam, and logtol, df0, p as used) and, under "sweeps", per sweep the six sums a sweep leaves, taken before the mean is
-    removed from e (se, ey, ee, bb, tb, db2), with what the tail makes of them (mu, ve, vb, lam, cnv, its, on: the trait goes on)."""
+    removed from e (se, ey, ee, bb, tb, db2), with what the tail makes of them (mu, ve, vb, lam, cnv, its, on: the trait goes on).
+    dtype: np.longdouble runs the same recurrence with every array, accumulator and scalar in long double (the yardstick of
+    tests/uvb_tight.py); tol, df0 and F's guard are rounded as for float64 and then widened.  dot(e, x_J): stands in for the step's dependent
+    dot e'x_J (the mutants of tests/test_uvb_tight_cpu.py)."""
     assert variant in "DFXZ"
+    f = dtype
     if variant != "D":
         tol = float(np.float32(tol)); df0 = float(np.float32(df0))
-    Y = np.asarray(Y, np.float64)
-    X = np.array(X, np.float64, copy=True)
+    tol, df0, guard = f(tol), f(df0), f(0.00001)
+    Y = np.asarray(Y, f)
+    X = np.array(X, f, copy=True)
     n, p = X.shape
     mu = Y.mean()                                                    # :1413
     y = Y - mu                                                       # :1414
@@ -44,9 +49,9 @@ def solver(Y, X, variant="D", maxit=100, tol=10e-7, df0=20.0, lam=None, record=N
         ve = vy * 0.5; vb = (vy * 0.5) / MSx                         # :1420
         lmb = ve / vb; vb0 = vb * df0; ve0 = ve * df0                # :1423
     if variant == "X":
-        lmb = XX.mean() if lam is None else lam                      # :1730
+        lmb = XX.mean() if lam is None else f(lam)                   # :1730
         ve = vb = np.nan
-    b = np.zeros(p)                                                  # :1421
+    b = np.zeros(p, f)                                               # :1421
     e = y.copy()                                                     # :1422
     logtol = np.log10(tol) if tol > 0 else -np.inf
     numit, cnv, trace = 0, np.nan, []
@@ -55,12 +60,13 @@ def solver(Y, X, variant="D", maxit=100, tol=10e-7, df0=20.0, lam=None, record=N
     while numit < maxit:                                             # :1426
         beta0 = b.copy()                                             # :1427
         for J in order(p, numit):                                    # :1428-1429
-            if variant == "F" and not XX[J] > 0.00001:               # :1633, :1635
+            if variant == "F" and not XX[J] > guard:                 # :1633, :1635
                 b[J] = 0.0
                 continue
             b0 = b[J]                                                # :1430
+            ex = e @ X[:, J] if dot is None else dot(e, X[:, J])
             with np.errstate(all="ignore"):
-                b1 = (e @ X[:, J] + XX[J] * b0) / (XX[J] + lmb)      # :1431
+                b1 = (ex + XX[J] * b0) / (XX[J] + lmb)               # :1431
             e -= X[:, J] * (b1 - b0); b[J] = b1                      # :1432
         if record is not None:
             with np.errstate(all="ignore"):
@@ -88,22 +94,23 @@ def solver(Y, X, variant="D", maxit=100, tol=10e-7, df0=20.0, lam=None, record=N
     return dict(b=b, mu=mu, h2=h2, ve=ve, vb=vb, its=numit, cnv=cnv, XX=XX, lam=lmb, trace=trace)
 
 
-def uvbeta(Y, X, variant="D", maxit=100, tol=10e-7, df0=20.0):
+def uvbeta(Y, X, variant="D", maxit=100, tol=10e-7, df0=20.0, dtype=np.float64, dot=None):
     """UVBETA / FUVBETA / XFUVBETA / ZFUVBETA: one solver per column of Y on the rows where it is not NaN (:1507-1514).  A column without
     observed rows is a zero column with its = 0 (:1510, :1713, :1811; XFUVBETA has no such test, the library returns zeros there too).
-    dict(b [p x k], mu, h2, ve, vb, its, cnv, XX [p x k], trace [per trait])."""
-    Y = np.asarray(Y, np.float64)
+    dict(b [p x k], mu, h2, ve, vb, its, cnv, XX [p x k], trace [per trait]).  dtype, dot: as solver's."""
+    f = dtype
+    Y = np.asarray(Y, f)
     if Y.ndim == 1:
         Y = Y[:, None]
-    X = np.asarray(X, np.float64)
+    X = np.asarray(X, f)
     p, k = X.shape[1], Y.shape[1]
-    out = dict(b=np.zeros((p, k)), mu=np.zeros(k), h2=np.zeros(k), ve=np.full(k, np.nan), vb=np.full(k, np.nan), its=np.zeros(k, np.int32),
-               cnv=np.full(k, np.nan), XX=np.zeros((p, k)), trace=[[] for _ in range(k)])
+    out = dict(b=np.zeros((p, k), f), mu=np.zeros(k, f), h2=np.zeros(k, f), ve=np.full(k, np.nan, f), vb=np.full(k, np.nan, f),
+               its=np.zeros(k, np.int32), cnv=np.full(k, np.nan, f), XX=np.zeros((p, k), f), trace=[[] for _ in range(k)])
     for t in range(k):
         w = ~np.isnan(Y[:, t])                                       # :1508
         if w.sum() == 0:                                             # :1510
             continue
-        r = solver(Y[w, t], X[w], variant, maxit, tol, df0)          # subvec_f / submat_f, :1511-1513
+        r = solver(Y[w, t], X[w], variant, maxit, tol, df0, dtype=f, dot=dot)   # subvec_f / submat_f, :1511-1513
         out["b"][:, t] = r["b"]; out["XX"][:, t] = r["XX"]; out["trace"][t] = r["trace"]
         for key in ("mu", "h2", "ve", "vb", "its", "cnv"):
             out[key][t] = r[key]
