@@ -9,6 +9,100 @@ _lib = None
 
 c_f = C.POINTER(C.c_float)
 c_d = C.POINTER(C.c_double)
+P, vp, i64, u64, u32, i32, f32, f64 = C.POINTER, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint32, C.c_int, C.c_float, C.c_double
+
+# The C ABI of include/bwgr.h, in the header's order: name -> argtypes (tests/test_abi_table_cpu.py holds the two against each other).
+# A prototype's `T *` and `T x[N]` are pointers here; handles and untyped buffers are void pointers.
+ABI = {
+    "bwgr_abi_version": [],
+    "bwgr_last_error": [],
+    "bwgr_device_count": [P(i32)],
+    "bwgr_panel_create": [P(vp), vp, i32, i32, i64, i64, i64, i32, i32, i32],
+    "bwgr_panel_destroy": [vp],
+    "bwgr_panel_set_stream": [vp, vp],
+    "bwgr_panel_clone": [P(vp), vp],
+    "bwgr_panel_max_concurrent": [vp, i32, P(i32)],
+    "bwgr_panel_max_pairs": [vp, P(i32)],
+    "bwgr_debug_occupancy_fits": [i32, i32, i32, i32, P(i32)],
+    "bwgr_debug_stream3_dma": [i64, i64],
+    "bwgr_debug_sweep3_kernel": [vp, P(i32)],
+    "bwgr_panel_info": [vp, P(i64)],
+    "bwgr_panel_pipeline": [vp, i32, P(i32)],
+    "bwgr_panel_stats": [vp, c_f, c_f, c_f],
+    "bwgr_kmup": [vp, c_f, c_f, c_f, c_f, c_f, f32, f32, u64, u32, i32],
+    "bwgr_kmup2": [vp, P(i32), i64, c_f, c_f, c_f, c_f, c_f, c_f, f32, f32, u64, u32, i32],
+    "bwgr_chain_create": [P(vp), vp, i32, vp, i32, f32, f32, f32, f32, f32, u64, i32],
+    "bwgr_chain_destroy": [vp],
+    "bwgr_chain_run": [vp, i32],
+    "bwgr_chain_run_pair": [vp, vp, i32],
+    "bwgr_chain_sync": [vp],
+    "bwgr_chain_iterations": [vp, P(i32)],
+    "bwgr_chain_result": [vp] + [c_f] * 10,
+    "bwgr_chain_state": [vp] + [c_f] * 5,
+    "bwgr_chain_sweep_ms": [vp, c_f, P(i32)],
+    "bwgr_chain_redo_count": [vp, P(i32)],
+    "bwgr_chain_create_sharded": [P(vp), vp, i32, vp, i32, f32, f32, f32, f32, f32, u64, i32, i64, i64, f32, vp],
+    "bwgr_chain_sweep_blocks": [vp, i32, i32],
+    "bwgr_chain_round_sweep": [vp, i32, i32, vp],
+    "bwgr_chain_get_sums_dev": [vp, vp],
+    "bwgr_chain_end_iteration_dev": [vp, vp],
+    "bwgr_chain_round_apply": [vp, vp],
+    "bwgr_chain_get_sums": [vp, c_d],
+    "bwgr_chain_end_iteration": [vp, c_d],
+    "bwgr_bayes": [vp, i32, c_f, f32, f32, f32, f32, f32, u64, i32] + [c_f] * 10,
+    "bwgr_bayes2": [vp, vp, i32, c_f, f32, f32, f32, f32, f32, u64, i32] + [c_f] * 10,
+    "bwgr_sample_rows": [u64, u32, i64, i64, i32, P(i32)],
+    "bwgr_wgr": [vp, c_d, i32, i32, i32, i32, i32, f64, f64, f64, u64, i32] + [c_d] * 7,
+    "bwgr_wgr_ex": [vp, c_d, i32, i32, i32, i32, i32, f64, f64, f64, u64, i32, c_d, c_d, i64, f64, i32] + [c_d] * 9,
+    "bwgr_em": [vp, i32, c_f, f32, f32, f32, c_f, i32, P(f32), c_f, c_f, c_f, c_f, c_f, P(i32)],
+    "bwgr_em_order": [i64, i32, P(i32)],
+    "bwgr_mrr": [vp, c_d, i32, c_d, i32] + [c_d] * 11 + [P(i32)],
+    "bwgr_debug_mrr_plan": [i32, i32, P(i32), P(i32), P(i64), P(i64)],
+    "bwgr_mrr_dense": [i32, vp, i32, i64, i64, i64, c_d, i32, c_d, i32] + [c_d] * 11 + [P(i32)],
+    "bwgr_debug_mrr_dense_plan": [i64, i64, i32, i32, P(i64)],
+    "bwgr_uvbeta": [vp, c_d, i64, i32, i32, f64, f64, c_d, c_d, c_d, c_d, c_d, P(i32), c_d, c_d],
+    "bwgr_debug_uvb_plan": [i64, i64, i64, P(i64)],
+    "bwgr_uvbeta_dense": [i32, c_d, i64, i64, i64, c_d, i64, i32, i32, f64, f64, c_d, c_d, c_d, c_d, c_d, P(i32), c_d],
+    "bwgr_debug_uvbd_plan": [i64, i64, i64, P(i64)],
+    "bwgr_uvbeta2": [vp, c_d, i64, i64, c_d, i64, i32, f64, f64, c_d, c_d, c_d, c_d, c_d, c_d, c_d, P(i32), c_d],
+    "bwgr_pegs": [i32, vp, i32, c_d, i64, i32, i32, f64, f64, f64, i32, i32, i32, c_d, vp, c_d, c_d, vp, c_d, P(i32), c_d],
+    "bwgr_pegs_ex": [i32, vp, i32, c_d, i64, i32, i32, f64, f64, f64, i32, i32, i32, c_d, vp, c_d, c_d, vp, c_d, P(i32), c_d],
+    "bwgr_debug_pegs_sparse_plan": [i64, i64, i64, i64, i32, i32, P(i64)],
+    "bwgr_debug_pegs_plan": [i64, i64, i32, P(i64)],
+    "bwgr_pegsx": [i32, vp, i32, c_d, i64, i32, c_d, i64, i32, i32, f64, f64, f64, f64, i32, i32, i32, i32, i32, c_d, c_d, vp, vp, vp, c_d, c_d, P(i32), c_d, c_d],
+    "bwgr_pegsx_ex": [i32, vp, i32, c_d, i64, i32, c_d, i64, i32, i32, f64, f64, f64, f64, i32, i32, i32, i32, i32, c_d, c_d, vp, vp, vp, c_d, c_d, P(i32), c_d, c_d],
+    "bwgr_debug_pegsx_plan": [i64, i32, i32, P(i64)],
+    "bwgr_debug_pegs_launch_plan": [i64, i64, P(i64)],
+    "bwgr_debug_pegsx_timing": [i32, c_d],
+    "bwgr_panel_xb": [vp, c_d, i64, c_d],
+    "bwgr_debug_panel_plan": [i32, i64, i64, i32, i32, i32, i32, i32, P(i64)],
+    "bwgr_debug_sweep_plan": [i32, i64, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, P(i64)],
+    "bwgr_debug_aux_plan": [i32, i64, i64, P(i64)],
+    "bwgr_panel_crossprod": [vp, vp, i64, i32],
+    "bwgr_panel_kernel": [vp, i32, f64, i32, vp, i64, i32],
+    "bwgr_debug_xxt_plan": [i64, i64, i32, i64, P(i64)],
+    "bwgr_panel_crossprod2": [vp, vp, vp, i64, i32],
+    "bwgr_panel_kernel2": [vp, vp, i32, f64, vp, i64, vp, i64, i32],
+    "bwgr_debug_xyt_plan": [i64, i64, i64, i32, i32, i64, P(i64)],
+    "bwgr_synth_genotypes": [vp, i64, i64, i64, i64, u64, vp, i32, vp],
+    "bwgr_group_create": [P(vp), i32, P(i32), vp, i32, i64, i64, i64, i32, c_f, i32, f32, f32, f32, f32, f32, u64, i32, i64],
+    "bwgr_group_create_centred": [P(vp), i32, P(i32), vp, i32, i64, i64, i64, i32, c_f, i32, f32, f32, f32, f32, f32, u64, i32, i64, i32],
+    "bwgr_group_run": [vp, i32],
+    "bwgr_group_sync": [vp],
+    "bwgr_group_info": [vp, P(i64)],
+    "bwgr_group_sound": [vp, P(i32)],
+    "bwgr_panel_centred": [vp, P(i32)],
+    "bwgr_panel_set_centred": [vp, i32],
+    "bwgr_group_result": [vp] + [c_f] * 10,
+    "bwgr_group_destroy": [vp],
+    "bwgr_debug_variates": [i32, u64, i32, f64, u32, u32, u32, i32, c_d],
+    "bwgr_debug_withhold": [vp, i32],
+    "bwgr_debug_last_redo": [P(i32)],
+    "bwgr_debug_launch_plan": [i64, i64, i64, i64, P(i64)],
+    "bwgr_debug_live": [P(i64)],
+}
+RESTYPE = {"bwgr_last_error": C.c_char_p}      # every other entry returns int
+EXPORTS = list(ABI)
 
 
 class BwgrError(RuntimeError):
@@ -34,92 +128,9 @@ def lib():
         except ImportError:   # a box without torch: the library does not need it
             pass
     L = C.CDLL(path)
-    L.bwgr_last_error.restype = C.c_char_p
-    vp, i64, u64, u32, i32, f32, f64 = C.c_void_p, C.c_int64, C.c_uint64, C.c_uint32, C.c_int, C.c_float, C.c_double
-    L.bwgr_panel_create.argtypes = [C.POINTER(vp), vp, i32, i32, i64, i64, i64, i32, i32, i32]
-    L.bwgr_panel_destroy.argtypes = [vp]
-    L.bwgr_panel_set_stream.argtypes = [vp, vp]
-    L.bwgr_panel_info.argtypes = [vp, C.POINTER(i64)]
-    L.bwgr_em.argtypes = [vp, i32, c_f, f32, f32, f32, c_f, i32, C.POINTER(f32), c_f, c_f, c_f, c_f, c_f, C.POINTER(i32)]
-    L.bwgr_em_order.argtypes = [i64, i32, C.POINTER(C.c_int32)]
-    L.bwgr_mrr.argtypes = [vp, c_d, i32, c_d, i32] + [c_d] * 11 + [C.POINTER(i32)]
-    L.bwgr_mrr_dense.argtypes = [i32, vp, i32, i64, i64, i64, c_d, i32, c_d, i32] + [c_d] * 11 + [C.POINTER(i32)]
-    L.bwgr_debug_mrr_dense_plan.argtypes = [i64, i64, i32, i32, C.POINTER(i64)]
-    L.bwgr_panel_clone.argtypes = [C.POINTER(vp), vp]
-    L.bwgr_panel_max_concurrent.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
-    L.bwgr_panel_max_pairs.argtypes = [vp, C.POINTER(C.c_int)]
-    L.bwgr_debug_occupancy_fits.argtypes = [i32, i32, i32, i32, C.POINTER(i32)]
-    L.bwgr_debug_stream3_dma.argtypes = [i64, i64]
-    L.bwgr_debug_sweep3_kernel.argtypes = [vp, C.POINTER(i32)]
-    L.bwgr_debug_mrr_plan.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]
-    L.bwgr_uvbeta.argtypes = [vp, c_d, i64, i32, i32, f64, f64, c_d, c_d, c_d, c_d, c_d, C.POINTER(i32), c_d, c_d]
-    L.bwgr_debug_uvb_plan.argtypes = [i64, i64, i64, C.POINTER(i64)]
-    L.bwgr_uvbeta_dense.argtypes = [i32, c_d, i64, i64, i64, c_d, i64, i32, i32, f64, f64, c_d, c_d, c_d, c_d, c_d, C.POINTER(i32), c_d]
-    L.bwgr_debug_uvbd_plan.argtypes = [i64, i64, i64, C.POINTER(i64)]
-    L.bwgr_pegs.argtypes = [i32, vp, i32, c_d, i64, i32, i32, f64, f64, f64, i32, i32, i32, c_d, vp, c_d, c_d, vp, c_d, C.POINTER(i32), c_d]
-    L.bwgr_debug_pegs_plan.argtypes = [i64, i64, i32, C.POINTER(i64)]
-    L.bwgr_pegs_ex.argtypes = list(L.bwgr_pegs.argtypes)
-    L.bwgr_debug_pegs_sparse_plan.argtypes = [i64, i64, i64, i64, i32, i32, C.POINTER(i64)]
-    L.bwgr_pegsx.argtypes = [i32, vp, i32, c_d, i64, i32, c_d, i64, i32, i32, f64, f64, f64, f64, i32, i32, i32, i32, i32, c_d, c_d, vp, vp, vp, c_d, c_d, C.POINTER(i32), c_d, c_d]
-    L.bwgr_pegsx_ex.argtypes = list(L.bwgr_pegsx.argtypes)
-    L.bwgr_debug_pegsx_plan.argtypes = [i64, i32, i32, C.POINTER(i64)]
-    L.bwgr_debug_pegs_launch_plan.argtypes = [i64, i64, C.POINTER(i64)]
-    L.bwgr_debug_pegsx_timing.argtypes = [i32, c_d]
-    L.bwgr_panel_xb.argtypes = [vp, c_d, i64, c_d]
-    L.bwgr_uvbeta2.argtypes = [vp, c_d, i64, i64, c_d, i64, i32, f64, f64, c_d, c_d, c_d, c_d, c_d, c_d, c_d, C.POINTER(i32), c_d]
-    L.bwgr_debug_panel_plan.argtypes = [i32, i64, i64, i32, i32, i32, i32, i32, C.POINTER(i64)]
-    L.bwgr_debug_aux_plan.argtypes = [i32, i64, i64, C.POINTER(i64)]
-    L.bwgr_debug_sweep_plan.argtypes = [i32, i64, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i64)]
-    L.bwgr_panel_crossprod.argtypes = [vp, vp, i64, i32]
-    L.bwgr_panel_kernel.argtypes = [vp, i32, f64, i32, vp, i64, i32]
-    L.bwgr_debug_xxt_plan.argtypes = [i64, i64, i32, i64, C.POINTER(i64)]
-    L.bwgr_panel_crossprod2.argtypes = [vp, vp, vp, i64, i32]
-    L.bwgr_panel_kernel2.argtypes = [vp, vp, i32, f64, vp, i64, vp, i64, i32]
-    L.bwgr_debug_xyt_plan.argtypes = [i64, i64, i64, i32, i32, i64, C.POINTER(i64)]
-    L.bwgr_panel_pipeline.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
-    L.bwgr_panel_stats.argtypes = [vp, c_f, c_f, c_f]
-    L.bwgr_kmup.argtypes = [vp, c_f, c_f, c_f, c_f, c_f, f32, f32, u64, u32, i32]
-    L.bwgr_kmup2.argtypes = [vp, C.POINTER(i32), i64, c_f, c_f, c_f, c_f, c_f, c_f, f32, f32, u64, u32, i32]
-    L.bwgr_chain_create.argtypes = [C.POINTER(vp), vp, i32, vp, i32, f32, f32, f32, f32, f32, u64, i32]
-    L.bwgr_chain_create_sharded.argtypes = [C.POINTER(vp), vp, i32, vp, i32, f32, f32, f32, f32, f32, u64, i32, i64, i64, f32, vp]
-    L.bwgr_chain_sweep_blocks.argtypes = [vp, i32, i32]
-    L.bwgr_chain_round_sweep.argtypes = [vp, i32, i32, vp]
-    L.bwgr_chain_round_apply.argtypes = [vp, vp]
-    L.bwgr_chain_get_sums_dev.argtypes = [vp, vp]
-    L.bwgr_chain_end_iteration_dev.argtypes = [vp, vp]
-    L.bwgr_chain_get_sums.argtypes = [vp, c_d]
-    L.bwgr_chain_end_iteration.argtypes = [vp, c_d]
-    L.bwgr_chain_destroy.argtypes = [vp]
-    L.bwgr_chain_run.argtypes = [vp, i32]
-    L.bwgr_chain_run_pair.argtypes = [vp, vp, i32]
-    L.bwgr_chain_sync.argtypes = [vp]
-    L.bwgr_chain_iterations.argtypes = [vp, C.POINTER(i32)]
-    L.bwgr_chain_result.argtypes = [vp] + [c_f] * 10
-    L.bwgr_chain_state.argtypes = [vp] + [c_f] * 5
-    L.bwgr_chain_sweep_ms.argtypes = [vp, c_f, C.POINTER(i32)]
-    L.bwgr_chain_redo_count.argtypes = [vp, C.POINTER(i32)]
-    L.bwgr_group_sound.argtypes = [vp, C.POINTER(i32)]
-    L.bwgr_panel_centred.argtypes = [vp, C.POINTER(i32)]
-    L.bwgr_panel_set_centred.argtypes = [vp, i32]
-    L.bwgr_bayes.argtypes = [vp, i32, c_f, f32, f32, f32, f32, f32, u64, i32] + [c_f] * 10
-    L.bwgr_bayes2.argtypes = [vp, vp, i32, c_f, f32, f32, f32, f32, f32, u64, i32] + [c_f] * 10
-    L.bwgr_wgr.argtypes = [vp, c_d, i32, i32, i32, i32, i32, f64, f64, f64, u64, i32] + [c_d] * 7
-    L.bwgr_wgr_ex.argtypes = [vp, c_d, i32, i32, i32, i32, i32, f64, f64, f64, u64, i32, c_d, c_d, i64, f64, i32] + [c_d] * 9
-    L.bwgr_synth_genotypes.argtypes = [vp, i64, i64, i64, i64, u64, vp, i32, vp]
-    L.bwgr_debug_variates.argtypes = [i32, u64, i32, f64, u32, u32, u32, i32, c_d]
-    L.bwgr_debug_withhold.argtypes = [vp, i32]
-    L.bwgr_debug_last_redo.argtypes = [C.POINTER(i32)]
-    L.bwgr_debug_live.argtypes = [C.POINTER(i64)]
-    L.bwgr_debug_launch_plan.argtypes = [i64, i64, i64, i64, C.POINTER(i64)]
-    L.bwgr_group_create.argtypes = [C.POINTER(vp), i32, C.POINTER(i32), vp, i32, i64, i64, i64, i32, c_f, i32, f32, f32, f32, f32, f32, u64, i32, i64]
-    L.bwgr_group_create_centred.argtypes = list(L.bwgr_group_create.argtypes) + [i32]
-    L.bwgr_group_run.argtypes = [vp, i32]
-    L.bwgr_group_sync.argtypes = [vp]
-    L.bwgr_group_info.argtypes = [vp, C.POINTER(i64)]
-    L.bwgr_group_result.argtypes = [vp] + [c_f] * 10
-    L.bwgr_group_destroy.argtypes = [vp]
-    L.bwgr_device_count.argtypes = [C.POINTER(i32)]
-    L.bwgr_sample_rows.argtypes = [u64, u32, i64, i64, i32, C.POINTER(i32)]
+    for name, argtypes in ABI.items():
+        getattr(L, name).argtypes = argtypes
+        getattr(L, name).restype = RESTYPE.get(name, C.c_int)
     _lib = L
     return L
 
@@ -134,11 +145,3 @@ def device_count():
     lib().bwgr_device_count(C.byref(n))
     return n.value
 
-
-EXPORTS = ["bwgr_abi_version", "bwgr_last_error", "bwgr_device_count", "bwgr_panel_create", "bwgr_panel_destroy",
-           "bwgr_panel_set_stream", "bwgr_panel_info", "bwgr_panel_pipeline", "bwgr_panel_clone", "bwgr_em", "bwgr_em_order", "bwgr_mrr", "bwgr_mrr_dense", "bwgr_debug_mrr_dense_plan", "bwgr_uvbeta", "bwgr_debug_uvb_plan", "bwgr_uvbeta_dense", "bwgr_debug_uvbd_plan", "bwgr_panel_xb", "bwgr_uvbeta2", "bwgr_pegs", "bwgr_pegs_ex", "bwgr_debug_pegs_plan", "bwgr_debug_pegs_sparse_plan", "bwgr_pegsx", "bwgr_pegsx_ex", "bwgr_debug_pegsx_plan", "bwgr_debug_pegs_launch_plan", "bwgr_debug_pegsx_timing", "bwgr_panel_max_concurrent", "bwgr_panel_max_pairs", "bwgr_debug_occupancy_fits", "bwgr_debug_stream3_dma", "bwgr_debug_sweep3_kernel", "bwgr_debug_mrr_plan", "bwgr_debug_panel_plan", "bwgr_debug_aux_plan", "bwgr_debug_sweep_plan", "bwgr_panel_crossprod", "bwgr_panel_kernel", "bwgr_debug_xxt_plan", "bwgr_panel_crossprod2", "bwgr_panel_kernel2", "bwgr_debug_xyt_plan", "bwgr_panel_stats", "bwgr_kmup", "bwgr_kmup2", "bwgr_chain_create",
-           "bwgr_chain_create_sharded", "bwgr_chain_sweep_blocks", "bwgr_chain_round_sweep", "bwgr_chain_round_apply", "bwgr_chain_get_sums_dev", "bwgr_chain_end_iteration_dev", "bwgr_chain_get_sums", "bwgr_chain_end_iteration",
-           "bwgr_chain_destroy", "bwgr_chain_run", "bwgr_chain_run_pair", "bwgr_chain_sync", "bwgr_chain_iterations", "bwgr_chain_result",
-           "bwgr_chain_state", "bwgr_chain_sweep_ms", "bwgr_chain_redo_count", "bwgr_group_sound", "bwgr_panel_centred", "bwgr_panel_set_centred", "bwgr_bayes", "bwgr_bayes2", "bwgr_wgr", "bwgr_wgr_ex", "bwgr_synth_genotypes",
-           "bwgr_debug_variates", "bwgr_debug_withhold", "bwgr_debug_last_redo", "bwgr_debug_live", "bwgr_debug_launch_plan", "bwgr_sample_rows", "bwgr_group_create", "bwgr_group_create_centred", "bwgr_group_run", "bwgr_group_sync",
-           "bwgr_group_info", "bwgr_group_result", "bwgr_group_destroy"]

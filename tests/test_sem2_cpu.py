@@ -176,7 +176,7 @@ def test_signatures_and_key_order_match_the_reference():
     assert "dense X2 is not taken" in B.solver2x.__doc__
     from bwgr_amd import api
     assert api.UVB2_KEYS == ("b1", "b2", "mu", "h2", "ve", "vb1", "vb2", "its", "cnv")
-    src = open(os.path.join(ROOT, "bwgr_amd", "api.py")).read()   # the return lists, in the reference's order (:1571-1578, :1608-1610)
+    src = open(os.path.join(ROOT, "bwgr_amd", "uvfit.py")).read()   # the return lists, in the reference's order (:1571-1578, :1608-1610)
     assert '("mu", "b", "hat", "LS", "LS_BETA", "BETA1", "BETA2", "gebv")' in src and '("mu", "b", "hat"), (mu, b, hat)' in src
     rsrc = open(os.path.join(ROOT, "rshim", "bwgr_hip.R")).read()
     for fn in ("MEGA <- function(Y, X, npc = -1L", "GSEM <- function(Y, X, npc = -1L", "solver2x <- function(Y, X1, X2, maxit = 100L, tol = 10e-7, df0 = 20.0"):

@@ -134,7 +134,7 @@ def test_signatures_and_key_order_match_the_reference():
     rsrc = open(os.path.join(ROOT, "rshim", "bwgr_hip.R")).read()
     for fn in ("XSEMF <- function(Y, X, npc = 0L)", "ZSEMF <- function(Y, X, npc = 0L)", "YSEMF <- function(Y, X, npc = -1L)"):
         assert fn in rsrc, fn
-    api = open(os.path.join(ROOT, "bwgr_amd", "api.py")).read()   # the return lists, in the reference's order (:1769, :1841-1845, :1870-1874)
+    api = open(os.path.join(ROOT, "bwgr_amd", "uvfit.py")).read()   # the return lists, in the reference's order (:1769, :1841-1845, :1870-1874)
     assert '("b", "GC", "hat")' in api and api.count('("mu", "b", "hat", "h2", "GC")') >= 2
 
 

@@ -24,7 +24,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bwgr_amd  # noqa: E402
-from bwgr_amd import api, synth  # noqa: E402
+from bwgr_amd import uvfit as api, synth  # noqa: E402
 
 med = statistics.median
 
@@ -69,7 +69,7 @@ def sweeps(P, Y, Z, reps, lo=1, hi=3, dlo=20, dhi=40):
 
 
 def driver(which, P, Y, maxit, reps):
-    """MEGA / GSEM as bwgr_amd.api._sem2 runs them; ms per stage."""
+    """MEGA / GSEM as bwgr_amd.uvfit._sem2 runs them; ms per stage."""
     names = ("first_stage", "xb", "latent", "ls_beta", "two_design_fit", "products")
     out = {nm: [] for nm in names}
     k = Y.shape[1]

@@ -23,7 +23,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bwgr_amd  # noqa: E402
-from bwgr_amd import api, synth  # noqa: E402
+from bwgr_amd import uvfit as api, synth  # noqa: E402
 
 med = statistics.median
 
@@ -41,7 +41,7 @@ def spread(v):
 
 
 def stages(P, Y, maxit, reps):
-    """ZSEMF's stages on the panel, as bwgr_amd.api._sem runs them; ms per stage, `reps` times after a warm-up."""
+    """ZSEMF's stages on the panel, as bwgr_amd.uvfit._sem runs them; ms per stage, `reps` times after a warm-up."""
     v = api.UVB_VARIANTS["Z"]
     Ym, tol, df0 = api._uvb_inputs(Y, P.n, v, 0.0, 20.0, "probe")
     k = Ym.shape[1]
