@@ -5,9 +5,16 @@ same steps with float arrays).  The marker orders come from bwgr_amd.em_order, t
 std::mt19937(it)) made cumulatively, as the reference makes it (:869); that call is host-only and needs no GPU.
 
 mrr(Y, X, ...) returns the reference's list as a dict (mu, b, hat, h2, GC, vb, ve, MSx, cnvB, cnvH2, cnvV, b_Weights, Its) and,
-with trace=True, also "trace": one dict per iteration (e, y, Z, Xc, b, ve/vb used by the sweep, bent) for invariant tests.
+with trace=True, also "trace": one dict per iteration (e, y, Z, Xc, b, ve/vb used by the sweep, bent, and lam: the smallest eigenvalue
+of GC before bending) for invariant tests.
+
+dtype=np.longdouble runs the same recurrence with every array, accumulator, scalar option and k x k routine in long double (the yardstick
+of tests/mt_tight.py): the k x k routines are those of tests/ld_linalg.py, and the markers' systems of a sweep are inverted in one batched
+call, as k_mrr_linv inverts them.  dot(x_J, e) stands in for the step's dependent dot x_J'e (the mutants of tests/test_mt_tight_cpu.py).
 """
 import numpy as np
+
+import ld_linalg
 
 
 def _cumulative_orders(p, upto):
@@ -17,8 +24,12 @@ def _cumulative_orders(p, upto):
 
 def mrr(Y, X, maxit=500, tol=10e-9, TH=False, HCS=False, XFA=False, ACS=False, NumXFA=3, R2=0.5, gc0=0.5, df0=1.0,
         updateMu=False, weight_prior_h2=0.01, weight_prior_gc=0.01, OneVarB=False, OneVarE=False, dtype=np.float64,
-        trace=False, orders=None):
+        trace=False, orders=None, dot=None):
     f = dtype
+    wide = np.dtype(f) == np.dtype(np.longdouble)
+    la = ld_linalg if wide else np.linalg
+    if wide:
+        tol, R2, gc0, df0, weight_prior_h2, weight_prior_gc = f(tol), f(R2), f(gc0), f(df0), f(weight_prior_h2), f(weight_prior_gc)
     Y = np.array(Y, dtype=f, copy=True)
     if Y.ndim == 1:
         Y = Y[:, None]
@@ -44,7 +55,7 @@ def mrr(Y, X, maxit=500, tol=10e-9, TH=False, HCS=False, XFA=False, ACS=False, N
     vbInit = vy * R2 / MSx                                           # :787
     veInit = ve.copy()                                               # :788
     vb = np.diag(vbInit).astype(f)                                   # :789
-    iG = np.linalg.inv(vb)                                           # :790, before the covariances are set
+    iG = la.inv(vb)                                                  # :790, before the covariances are set
     h2 = 1 - ve / vy                                                 # :791
     for i in range(k):                                               # :796-804
         for j in range(i):
@@ -67,11 +78,12 @@ def mrr(Y, X, maxit=500, tol=10e-9, TH=False, HCS=False, XFA=False, ACS=False, N
         order = _cumulative_orders(p, numit) if ords is None else ords[numit]   # :869
         iVe = 1 / ve
         ve_used, iG_used = ve.copy(), iG.copy()
+        Linv = la.inv(iG + (XX * iVe)[:, :, None] * np.eye(k, dtype=f)) if wide else None   # every marker's LHS^-1 at once
         for J in order:                                              # :871-902
             b0 = b[J].copy()
             LHS = iG + np.diag(XX[J] * iVe)                          # :884
-            RHS = (Xc[:, J] @ e + XX[J] * b0) * iVe                  # :885-886
-            b1 = np.linalg.solve(LHS, RHS)                           # LLT solve (:896)
+            RHS = ((Xc[:, J] @ e if dot is None else dot(Xc[:, J], e)) + XX[J] * b0) * iVe   # :885-886
+            b1 = Linv[J] @ RHS if wide else np.linalg.solve(LHS, RHS)   # LLT solve (:896)
             b[J] = b1
             e = e - np.outer(Xc[:, J], b1 - b0) * Z                  # :900-901
         rec = {"e": e.copy(), "y": y, "Z": Z, "Xc": Xc, "b": b.copy(), "ve_sweep": ve_used, "iG_sweep": iG_used, "mu": mu.copy()} if trace else None
@@ -110,16 +122,16 @@ def mrr(Y, X, maxit=500, tol=10e-9, TH=False, HCS=False, XFA=False, ACS=False, N
             GC = vb / np.outer(sd, sd)                               # :964
         if ACS:                                                      # :967-973
             gs = (GC.sum() - k) / (k * (k - 1)) / 2.0
-            GC = (_udu(GC, NumXFA) + gs) * 0.5
+            GC = (_udu(GC, NumXFA, la) + gs) * 0.5
             np.fill_diagonal(GC, 1)
         elif HCS:                                                    # :974-981
             gs = GC[np.tril_indices(k, -1)].sum() / ((k * (k - 1)) // 2) if k > 1 else 0.0
             GC = np.full((k, k), gs, f)
             np.fill_diagonal(GC, 1)
         elif XFA:                                                    # :982-986
-            GC = _udu(GC, NumXFA)
+            GC = _udu(GC, NumXFA, la)
             np.fill_diagonal(GC, 1)
-        lam = np.linalg.eigvalsh(GC).min()                           # bending (:1009-1022)
+        lam = la.eigvalsh(GC).min()                                  # bending (:1009-1022)
         bent = lam < 0
         if bent:
             inflate = abs(lam * 1.1)
@@ -129,13 +141,14 @@ def mrr(Y, X, maxit=500, tol=10e-9, TH=False, HCS=False, XFA=False, ACS=False, N
         else:                                                        # :1023-1025
             sd = np.sqrt(np.diag(vb))
             vb = GC * np.outer(sd, sd)
-        iG = np.linalg.pinv(vb)                                      # :1027
+        iG = la.pinv(vb)                                             # :1027
         if updateMu:                                                 # :1030-1036
             d = e.sum(0) * iN
             mu = mu + d
             e = (e - d) * Z
         if trace:
             rec["bent"] = bool(bent)
+            rec["lam"] = lam
             trc.append(rec)
         cnv = np.log10(((beta0 - b) ** 2).sum(0).max())              # :1041
         cnv1.append(cnv)
@@ -155,9 +168,9 @@ def mrr(Y, X, maxit=500, tol=10e-9, TH=False, HCS=False, XFA=False, ACS=False, N
     return out
 
 
-def _udu(GC, nf):
+def _udu(GC, nf, la=np.linalg):
     """sum of the nf leading eigen-terms lambda v v' (:990-991)."""
-    w, V = np.linalg.eigh(GC)
+    w, V = la.eigh(GC)
     k = len(w)
     U = np.zeros_like(GC)
     for i in range(nf):

@@ -10,8 +10,17 @@ pegsz(Y, X_list, ...) returns the reference's list as a dict (mu, b, hat, h2, GC
 and largest eigenvalue before bending), inflated, gap (0 < XFA < k: last kept minus first dropped eigenvalue of GC, else None), and the
 arrays the CPU test of the tail feeds to the library's own tail (TH, vb, iG, inflate) with the sweep's ey, db2, d, ve, cnv.
 pegs(Y, X, ...) is PEGS's own text (own_text=True) on one design, with b, GC and bend unwrapped.
+
+dtype=np.longdouble runs the same recurrence with every array, accumulator, scalar option and k x k routine in long double (the yardstick
+of tests/mt_tight.py): Y and the options are rounded to float as before and then widened, the k x k routines are those of
+tests/ld_linalg.py, and an effect's systems of a sweep are inverted in one batched call.  dot(x_J, e) stands in for the step's dependent
+dot x_J'e, or dot[f] does for effect f alone where dot is a list (None: that effect's dot as it is) -- the mutants of
+tests/test_mt_tight_cpu.py.  The trace also holds near0: min |vb| / max |vb| before NNC's clamp, over the entries that
+are not exactly zero (None without NNC).
 """
 import numpy as np
+
+import ld_linalg
 
 
 def _orders(m, s):
@@ -29,9 +38,11 @@ def _gc(vb):
     return vb / np.outer(sd, sd), sd
 
 
-def tail_vb(TH, Tr, k, XFA, NNC, covbend, covMinEv, inflate, own_text):
+def tail_vb(TH, Tr, k, XFA, NNC, covbend, covMinEv, inflate, own_text, dtype=np.float64):
     """one effect's covariance after a sweep (:127-160, :717-756) -> vb, iG, inflate, record"""
-    vb = np.zeros((k, k))
+    wide = np.dtype(dtype) == np.dtype(np.longdouble)
+    la, num = (ld_linalg, dtype) if wide else (np.linalg, float)
+    vb = np.zeros((k, k), dtype)
     for i in range(k):
         for j in range(k):
             if i == j:
@@ -43,35 +54,43 @@ def tail_vb(TH, Tr, k, XFA, NNC, covbend, covMinEv, inflate, own_text):
         vb = np.diag(np.diag(vb))
     elif own_text or XFA < k:                                        # :139-153 (PEGS: XFA > 0), :734-747 (PEGSZ: 0 < XFA < k)
         GC, sd = _gc(vb)
-        w, V = np.linalg.eigh(GC)
+        w, V = la.eigh(GC)
         if XFA < k:
-            gap = float(w[k - XFA] - w[k - XFA - 1])
+            gap = num(w[k - XFA] - w[k - XFA - 1])
         GC = (V[:, k - XFA:] * w[k - XFA:]) @ V[:, k - XFA:].T
         np.fill_diagonal(GC, 1.0)
         vb = GC * np.outer(sd, sd)
+    near0 = None
     if NNC:                                                          # :156
+        near0 = num(np.abs(vb[vb != 0]).min(initial=np.inf) / max(np.abs(vb).max(), 1e-300))   # (an exact zero is no decision: XFA = 0)
         vb = np.maximum(vb, 0.0)
-    ev = np.linalg.eigvalsh(vb)
-    MinDVb = float(ev[0])                                            # :157
+    ev = la.eigvalsh(vb)
+    MinDVb = num(ev[0])                                              # :157
     if MinDVb < covMinEv:                                            # :158: a running maximum
         inflate = max(inflate, abs(MinDVb * covbend))
     inflated = bool(k >= 5 or MinDVb < covMinEv)                     # :159
     if inflated:
-        vb = vb + inflate * np.eye(k)
-    iG = np.linalg.pinv(vb)                                          # :160
-    return vb, iG, inflate, dict(MinDVb=MinDVb, maxEv=float(ev[-1]), inflated=inflated, gap=gap)
+        vb = vb + inflate * np.eye(k, dtype=dtype)
+    iG = la.pinv(vb)                                                 # :160
+    return vb, iG, inflate, dict(MinDVb=MinDVb, maxEv=num(ev[-1]), inflated=inflated, gap=gap, near0=near0)
 
 
-def pegsz(Y, X_list, maxit=100, logtol=-4.0, covbend=1.1, covMinEv=10e-4, XFA=-1, NNC=True, own_text=False, orders=None, trace=False):
+def pegsz(Y, X_list, maxit=100, logtol=-4.0, covbend=1.1, covMinEv=10e-4, XFA=-1, NNC=True, own_text=False, orders=None, trace=False,
+          dtype=np.float64, dot=None):
+    wide = np.dtype(dtype) == np.dtype(np.longdouble)
+    la, num = (ld_linalg, dtype) if wide else (np.linalg, float)
     Y = np.array(Y, np.float64, copy=True)
     if Y.ndim == 1:
         Y = Y[:, None]
-    Y = Y.astype(np.float32).astype(np.float64)
+    Y = Y.astype(np.float32).astype(dtype)
     logtol, covbend, covMinEv = _f32(logtol), _f32(covbend), _f32(covMinEv)
-    Xs = [np.asarray(X, np.float64).reshape(Y.shape[0], -1) for X in X_list]
+    if wide:
+        logtol, covbend, covMinEv = dtype(logtol), dtype(covbend), dtype(covMinEv)
+    Xs = [np.asarray(X, dtype).reshape(Y.shape[0], -1) for X in X_list]
+    dots = list(dot) if isinstance(dot, (list, tuple)) else [dot] * len(Xs)
     n0, k = Y.shape
     ne = len(Xs)
-    Z = (~np.isnan(Y)).astype(np.float64)                            # :23-29
+    Z = (~np.isnan(Y)).astype(dtype)                            # :23-29
     Y[np.isnan(Y)] = 0
     n = Z.sum(0)                                                     # :32
     mu = Y.sum(0) / n                                                # :36-37
@@ -87,23 +106,24 @@ def pegsz(Y, X_list, maxit=100, logtol=-4.0, covbend=1.1, covMinEv=10e-4, XFA=-1
     ve = vy * 0.5                                                    # :58
     vb = [np.diag(ve / m) for m in MSx]                              # :61
     iG = [np.diag(m / ve) for m in MSx]                              # :62
-    b = [np.zeros((X.shape[1], k)) for X in Xs]
+    b = [np.zeros((X.shape[1], k), dtype) for X in Xs]
     e = y.copy()                                                     # :73
-    inflate = [0.0] * ne
+    inflate = [num(0.0)] * ne
     if XFA < 0:                                                      # :94
         XFA = k
     assert XFA <= k
-    cnv, numit, cnvs, trc = 10.0, 0, [], []
+    cnv, numit, cnvs, trc = num(10.0), 0, [], []
     while numit < maxit:
         beta0 = [a.copy() for a in b]
         iVe = 1 / ve
         for f, X in enumerate(Xs):                                   # :689-708
             order = _orders(X.shape[1], numit) if orders is None else orders[numit][f]
+            Linv = la.inv(iG[f] + (XX[f] * iVe)[:, :, None] * np.eye(k, dtype=dtype)) if wide else None   # every column's LHS^-1 at once
             for J in order:
                 b0 = b[f][J].copy()
                 LHS = iG[f] + np.diag(XX[f][J] * iVe)                # :113
-                RHS = (X[:, J] @ e + XX[f][J] * b0) * iVe            # :114-115
-                b1 = np.linalg.solve(LHS, RHS)                       # :116
+                RHS = ((X[:, J] @ e if dots[f] is None else dots[f](X[:, J], e)) + XX[f][J] * b0) * iVe   # :114-115
+                b1 = Linv[J] @ RHS if wide else np.linalg.solve(LHS, RHS)   # :116
                 b[f][J] = b1
                 e = e - np.outer(X[:, J], b1 - b0) * Z               # :119
         ey = (e * y).sum(0)
@@ -111,16 +131,16 @@ def pegsz(Y, X_list, maxit=100, logtol=-4.0, covbend=1.1, covMinEv=10e-4, XFA=-1
         recs = []
         for f in range(ne):
             TH = b[f].T @ tilde[f]                                   # :128
-            vb[f], iG[f], inflate[f], rec = tail_vb(TH, Tr[f], k, XFA, NNC, covbend, covMinEv, inflate[f], own_text)
+            vb[f], iG[f], inflate[f], rec = tail_vb(TH, Tr[f], k, XFA, NNC, covbend, covMinEv, inflate[f], own_text, dtype)
             rec.update(TH=TH, vb=vb[f].copy(), iG=iG[f].copy(), inflate=inflate[f])
             recs.append(rec)
         se = e.sum(0)
         d = se * iN                                                  # :163-164: 1 / (n - 1), as written
         mu = mu + d
         e = (e - d) * Z                                              # :165-166
-        db2 = [float(((beta0[f] - b[f]) ** 2).sum()) for f in range(ne)]
+        db2 = [num(((beta0[f] - b[f]) ** 2).sum()) for f in range(ne)]
         with np.errstate(divide="ignore"):
-            cnv = float(np.log10(sum(db2)))                          # :169, :766-770
+            cnv = num(np.log10(sum(db2)))                          # :169, :766-770
         numit += 1
         cnvs.append(cnv)
         if trace:
@@ -129,7 +149,7 @@ def pegsz(Y, X_list, maxit=100, logtol=-4.0, covbend=1.1, covMinEv=10e-4, XFA=-1
         if cnv < logtol:                                             # :171
             break
     h2 = 1 - ve / vy                                                 # :175
-    hat = np.zeros((n0, k))
+    hat = np.zeros((n0, k), dtype)
     for f, X in enumerate(Xs):                                       # :777-781
         hat = hat + X @ b[f]
     hat = hat + mu
