@@ -60,6 +60,9 @@ ABI = {
     "bwgr_debug_mrr_plan": [i32, i32, P(i32), P(i32), P(i64), P(i64)],
     "bwgr_mrr_dense": [i32, vp, i32, i64, i64, i64, c_d, i32, c_d, i32] + [c_d] * 11 + [P(i32)],
     "bwgr_debug_mrr_dense_plan": [i64, i64, i32, i32, P(i64)],
+    "bwgr_mrr_svd_fit": [i32, vp, i32, i64, i64, i64, c_d, i32, i32, f64, i32] + [c_d] * 10 + [P(i32)],
+    "bwgr_panel_xta": [vp, vp, i64, i64, i32, i32, vp, i64],
+    "bwgr_debug_xta_plan": [i64, i64, i64, i64, P(i64)],
     "bwgr_uvbeta": [vp, c_d, i64, i32, i32, f64, f64, c_d, c_d, c_d, c_d, c_d, P(i32), c_d, c_d],
     "bwgr_debug_uvb_plan": [i64, i64, i64, P(i64)],
     "bwgr_uvbeta_dense": [i32, c_d, i64, i64, i64, c_d, i64, i32, i32, f64, f64, c_d, c_d, c_d, c_d, c_d, P(i32), c_d],

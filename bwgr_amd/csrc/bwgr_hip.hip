@@ -30,6 +30,8 @@
 #include "sweep3p.hip.h"
 #include "mrr.hip.h"
 #include "mrr_dense.hip.h"
+#include "xta.hip.h"
+#include "mrr_svd_tail.h"
 #include "uvb.hip.h"
 #include "uvbd.hip.h"
 #include "uvb2.hip.h"
@@ -290,6 +292,7 @@ static int require_device(int device) {
 #include "group_host.hip.h"
 #include "mtfit_host.hip.h"
 #include "mrr_host.hip.h"
+#include "mrr_svd_host.hip.h"
 #include "uvb_host.hip.h"
 #include "kernels_host.hip.h"
 #include "pegs_host.hip.h"

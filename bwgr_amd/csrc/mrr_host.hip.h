@@ -190,18 +190,18 @@ static int mrr_iterate(MtFit &M, const TraitSet &S, const MrrOpts &o, std::vecto
 //   once:       X -> the engine's padded copy, k_mrrd_centre (explicit centring, :763-765), k_mrrd_setup
 //   per sweep:  order -> k_mrrd_gram -> k_mrr_linv -> [k_mrrd_pass(b-1 | b), k_mrrd_solve(b)] for every block -> k_mrrd_pass(last | -), then
 //               bwgr_mrr's tail (mrr_iterate)
-// A fit with one effect on the dense train (MtFit, mrrd_sweep); options, defaults, refusals and outputs are bwgr_mrr's (mrr_read_opts).
+// A fit with one effect on the dense train (MtFit, mrrd_sweep); options, defaults, refusals and outputs are bwgr_mrr's (mrr_read_opts).  What such a fit
+// does around its iterate is mrr_dense_fit, which bwgr_mrr_svd_fit (mrr_svd_host.hip.h) shares.
 // ------------------------------------------------------------------------------------------------
-extern "C" int bwgr_mrr_dense(int device, const double *X, int memloc, int64_t n, int64_t r, int64_t ldx, const double *Y, int k, const double *opts, int nopts,
-                              double *mu_out, double *b_out, double *hat_out, double *h2_out, double *GC_out, double *vb_out, double *ve_out, double *MSx_out,
-                              double *cnvB, double *cnvH2, double *cnvV, int *its) {
-  if (!X || !Y || !b_out || !its) return fail(BWGR_EINVAL, "mrr_dense: null pointer");
-  if (memloc != BWGR_HOST && memloc != BWGR_DEVICE) return fail(BWGR_EINVAL, "mrr_dense: bad memloc %d", memloc);
-  MrrOpts o;
-  CHK(mrr_read_opts("mrr_dense", k, opts, nopts, o));
-  if (r < 1 || r > 0x7FFFFF00ll) return fail(BWGR_EINVAL, "mrr_dense: r = %lld columns of X (at least 1, at most 2147483392)", (long long)r);
-  if (n < 2) return fail(BWGR_EINVAL, "mrr_dense: n = %lld rows (at least 2)", (long long)n);
-  if (ldx < n) return fail(BWGR_EINVAL, "mrr_dense: ldx = %lld is below n = %lld", (long long)ldx, (long long)n);
+// What a fit with one effect on the dense train does around its own algebra, for bwgr_mrr_dense and bwgr_mrr_svd_fit (`who`): the refusals of
+// the shape, the host copy of a host X, the traits and their patterns, the workspace against the device's free memory, the fit's arrays and the
+// set-up of its effect; then iterate(M, S, iG).  natural: the sweeps walk the columns in their natural order.
+template <typename F>
+static int mrr_dense_fit(const char *who, int device, const double *X, int memloc, int64_t n, int64_t r, int64_t ldx, const double *Y, int k, bool want_hat,
+                         bool natural, F iterate) {
+  if (r < 1 || r > 0x7FFFFF00ll) return fail(BWGR_EINVAL, "%s: r = %lld columns of X (at least 1, at most 2147483392)", who, (long long)r);
+  if (n < 2) return fail(BWGR_EINVAL, "%s: n = %lld rows (at least 2)", who, (long long)n);
+  if (ldx < n) return fail(BWGR_EINVAL, "%s: ldx = %lld is below n = %lld", who, (long long)ldx, (long long)n);
   const int64_t ld = (n + 127) / 128 * 128;
   std::vector<double> Xh;                         // host X with the engine's column stride (copied from asynchronously: before the fit)
   if (memloc == BWGR_HOST) {
@@ -209,7 +209,7 @@ extern "C" int bwgr_mrr_dense(int device, const double *X, int memloc, int64_t n
     for (int64_t j = 0; j < r; ++j)
       for (int64_t i = 0; i < n; ++i) {
         const double v = X[(size_t)j * (size_t)ldx + (size_t)i];
-        if (!std::isfinite(v)) return fail(BWGR_EINVAL, "mrr_dense: X[%lld, %lld] is not finite", (long long)i, (long long)j);
+        if (!std::isfinite(v)) return fail(BWGR_EINVAL, "%s: X[%lld, %lld] is not finite", who, (long long)i, (long long)j);
         Xh[(size_t)j * (size_t)ld + (size_t)i] = v;
       }
   }
@@ -219,24 +219,36 @@ extern "C" int bwgr_mrr_dense(int device, const double *X, int memloc, int64_t n
   E.eff = &one; E.neff = 1; E.n = n; E.ld = ld; E.st = nullptr; E.train = true;
   E.Zc.resize(1); E.csr.resize(1); E.disjoint.assign(1, 0);
   const TraitSet S = read_traits(Y, n, k, E.ld, k, RowRule::AtLeastTwo);
-  if (S.bad >= 0) return fail(BWGR_EINVAL, "mrr_dense: trait %d of Y has %g observed rows (needs 2)", (int)S.bad, S.nt[(size_t)S.bad]);
+  if (S.bad >= 0) return fail(BWGR_EINVAL, "%s: trait %d of Y has %g observed rows (needs 2)", who, (int)S.bad, S.nt[(size_t)S.bad]);
   const Patterns pat = find_patterns(S, 0, k);
   {
     const MrrDensePlan pl = mrr_dense_plan(n, r, k, (int)pat.rep.size());
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
     if (pl.ws_bytes > free_b)
-      return fail(BWGR_EINVAL, "mrr_dense: n = %lld, r = %lld, k = %d need a device workspace of %zu bytes; %zu are free", (long long)n, (long long)r, k, pl.ws_bytes, free_b);
+      return fail(BWGR_EINVAL, "%s: n = %lld, r = %lld, k = %d need a device workspace of %zu bytes; %zu are free", who, (long long)n, (long long)r, k, pl.ws_bytes, free_b);
   }
   std::vector<double> iG((size_t)k * k, 0.0);     // (copied from asynchronously: before the fit, whose holder waits for the stream)
   MtFit M(E, k);
+  M.natural_order = natural;
   M.masks(S, pat);
-  M.alloc(hat_out != nullptr, false);
-  if (M.bufs.failed()) return no_memory("mrr_dense");
+  M.alloc(want_hat, false);
+  if (M.bufs.failed()) return no_memory(who);
   CHK(M.upload(S, nullptr));                                                                       // e = y, :825 (nothing reads the traits' sums: xbar = 0)
   CHK(M.stage_train(0, memloc == BWGR_HOST ? Xh.data() : X, memloc == BWGR_HOST ? ld : ldx, memloc == BWGR_DEVICE));
   CHK(M.stage_effect(0));                                                                          // b = 0, :823
   CHK(M.setup_effect(0, 0));
+  return iterate(M, S, iG);
+}
+
+extern "C" int bwgr_mrr_dense(int device, const double *X, int memloc, int64_t n, int64_t r, int64_t ldx, const double *Y, int k, const double *opts, int nopts,
+                              double *mu_out, double *b_out, double *hat_out, double *h2_out, double *GC_out, double *vb_out, double *ve_out, double *MSx_out,
+                              double *cnvB, double *cnvH2, double *cnvV, int *its) {
+  if (!X || !Y || !b_out || !its) return fail(BWGR_EINVAL, "mrr_dense: null pointer");
+  if (memloc != BWGR_HOST && memloc != BWGR_DEVICE) return fail(BWGR_EINVAL, "mrr_dense: bad memloc %d", memloc);
+  MrrOpts o;
+  CHK(mrr_read_opts("mrr_dense", k, opts, nopts, o));
   const MrrOut out = {mu_out, b_out, hat_out, h2_out, GC_out, vb_out, ve_out, MSx_out, cnvB, cnvH2, cnvV, its};
-  return mrr_iterate(M, S, o, iG, out);
+  return mrr_dense_fit("mrr_dense", device, X, memloc, n, r, ldx, Y, k, hat_out != nullptr, false,
+                       [&](MtFit &M, const TraitSet &S, std::vector<double> &iG) { return mrr_iterate(M, S, o, iG, out); });
 }

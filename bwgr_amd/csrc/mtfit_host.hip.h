@@ -325,6 +325,7 @@ struct MtFit {
   std::vector<CsrCopy> csr;
   const bwgr_pegs_effect_ex *src;          // the caller's effects: a sparse effect's CSC arrays are copied from where they are
   std::vector<CumulativeOrder> order;      // per effect, the column order of sweep s
+  bool natural_order = false;              // every sweep walks the columns 0, 1, ... (mrr_svd, :1176): the orders stay the identity they start as
   std::vector<uint32_t> zt, zb;            // bit t: row observed for trait t; bit g: row observed in pattern g
   std::vector<uint8_t> zm;
   std::vector<double> d, off;              // k each, for stage_vec(): the mu shift (or the TH form's diagonal); the fitted values' offset (zero unless written)
@@ -496,7 +497,7 @@ struct MtFit {
   // effect e's share of sweep `numit`, against mc.iVe and iG (host, k x k): mrr_sweep, or k_mrr_linv -> k_pegs_dense_leg, or k_mrr_linv ->
   // k_pegs_sparse_leg / k_pegs_sparse_leg_disjoint -> db2 from the per-column (delta b)^2 in column-index order
   int sweep_effect(int e, int numit, const double *iG) {
-    const std::vector<int> &ord = order[(size_t)e].next(numit);
+    const std::vector<int> &ord = natural_order ? order[(size_t)e].current() : order[(size_t)e].next(numit);
     if (eff[(size_t)e].train) return mrrd_sweep(st, eff[(size_t)e].dl, W, zbd, mc, tpl, ord, iG);
     if (eff[(size_t)e].panel) return mrr_sweep(st, eff[(size_t)e].leg, W, mc, plan, ord, iG);
     if (eff[(size_t)e].sparse) {

@@ -305,6 +305,39 @@ int bwgr_mrr_dense(int device, const double *X, int memloc, int64_t n, int64_t r
  * out[1] x npat workgroups. */
 #define BWGR_MRR_DENSE_PLAN_NOUT 15
 int bwgr_debug_mrr_dense_plan(int64_t n, int64_t r, int k, int npat, int64_t out[BWGR_MRR_DENSE_PLAN_NOUT]);
+/* ---- mrr_svd: the multi-trait fit in the panel's principal components (src/RcppEigen20230423.cpp:1083-1260, R/RcppExports.R:188) ----
+ * bwgr_mrr_svd_fit is the reference's Gauss-Seidel (:1103-1243) on a given n x r design X (for mrr_svd: U diag(d), the left singular vectors of
+ * the centred marker matrix times its singular values; the host layers decompose, bwgr_amd.svd).  It is a fit with one effect on
+ * bwgr_mrr_dense's block train: X, memloc, ldx, the engine's own copy, the workspace and two calls giving the same bits are as there.  Every sweep
+ * walks the columns in their natural order 0 .. r-1 (:1176).  Start: ve = vy / 2, vb = diag(ve / MSx), h2 = 1 - ve / vy.  After a sweep:
+ * ve_t = e_t'y_t / (n_t - 1) with no prior, h2 again, TildeHat = b'(Dinv o tilde) and TrDinvXSX_t = sum_j XSX_jt Dinv_jt with
+ * Dinv_jt = 1 / (XSX_jt / ve_t + iG_tt), XSX the n_t-scaled one, this iteration's ve and the sweep's iG; vb_ii = TH_ii / Tr_i,
+ * vb_ij = (TH_ij + TH_ji) / (Tr_i + Tr_j); where vb's smallest eigenvalue is below 0, fabs(1.1 min) goes onto its diagonal; iG = pinv(vb).
+ * cnvB = log10 sum_jt (delta b_jt)^2 (the sum over the traits), cnvH2 and cnvV as :1220-1221 (maxit values each, or null); the loop ends at
+ * cnvB < log10(tol) or at a NaN, which is counted in *its.  mu (the traits' means over their records) is never updated; GC = vb_ij /
+ * sqrt(vb_ii vb_jj) at the end; hat = X b + mu for every row (n x k, or null); b is r x k.  The reference does not centre X; the train
+ * centres its copy by the all-rows column means, which for the design above are 0 up to rounding (W_c has zero column sums, so 1'U = 0
+ * wherever d > 0).  The reference's float arithmetic is fp64 here.
+ * BWGR_EINVAL: what bwgr_mrr_dense refuses of its pointers, memloc, n, r, ldx, X, the traits and the workspace; k < 1 or k > 16; maxit < 0. */
+int bwgr_mrr_svd_fit(int device, const double *X, int memloc, int64_t n, int64_t r, int64_t ldx, const double *Y, int k, int maxit, double tol, int verbose,
+                     double *mu, double *b, double *hat, double *h2, double *GC, double *vb, double *ve, double *cnvB, double *cnvH2, double *cnvV, int *its);
+/* out (p x k, column stride ldo >= p) = X'A on the raw codes of an int8 panel (centre = 0) or X_c'A with X_c = X - 1 xbar' (centre = 1);
+ * A: n x k, column stride lda >= n; both in host memory (memloc = BWGR_HOST) or both on the panel's device (BWGR_DEVICE: the caller's arrays,
+ * read and written on the panel's stream, asynchronously).  centre = 0: out[j, t] = sum_i x_ij a_it.  centre = 1: fma(-xbar_j, s_t, that sum),
+ * xbar_j = the exact integer column sum divided by n, s_t = sum_i a_it summed on the device as 256 partial sums (partial q takes the rows
+ * q, q + 256, ... in ascending order) added in ascending q: the panel stays int8.  Any k >= 1: the traits go in groups of 16, one pass over
+ * X per group.  A workgroup owns whole columns over all rows, so nothing is reduced across workgroups and no sum is formed by atomics: the
+ * order of an output's sum depends on n and the panel's slab height alone, two calls give the same bits, a host A and a device A give the same
+ * bits, and a column gives the same bits in any panel of the same rows and slab height.
+ * BWGR_EINVAL: a null pointer, k < 1 (or beyond 1 048 560), a bad memloc, lda < n, ldo < p, an fp32 panel, a non-finite entry of a host A
+ * (for a device A that is the caller's duty). */
+int bwgr_panel_xta(bwgr_panel *P, const double *A, int64_t lda, int64_t k, int centre, int memloc, double *out, int64_t ldo);
+/* host arithmetic of bwgr_panel_xta's plan (needs no GPU) for n rows, p columns, k columns of A and slabs of R rows (a multiple of 128, at
+ * most 4096; else BWGR_EINVAL): out[0] the trait groups; out[1] the columns a workgroup owns and out[2] those of one wave; out[3] the
+ * workgroups per trait group and out[4] the column blocks one of them takes at most; out[5] the LDS bytes of k_xta (static); out[6] the rows
+ * of a tile and out[7] the tiles; out[8] the bytes of the call's device workspace (a host call adds its copies of A and of the result). */
+#define BWGR_XTA_PLAN_NOUT 9
+int bwgr_debug_xta_plan(int64_t n, int64_t p, int64_t k, int64_t R, int64_t out[BWGR_XTA_PLAN_NOUT]);
 /* ---- per-trait ridge fits (UVBETA / FUVBETA family) -------------------------------------------------------
  * Replaces VectorXd solver1x(Y,X,maxit,tol,df0) src/RcppEigen20230423.cpp:1410-1443 and MatrixXd UVBETA(Y,X) :1506-1515; solver1xF :1613-1646 and
  * FUVBETA :1709-1718; xsolver1xF :1721-1743 and XFUVBETA :1746-1753; zsolver1xF :1771-1804 and ZFUVBETA :1807-1816 (R/RcppExports.R:196-238).
