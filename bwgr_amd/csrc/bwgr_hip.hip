@@ -147,8 +147,25 @@ template <typename T> static int own_array(DevBufs &own, T *&ptr, size_t count, 
 // bwgr_panel_create, or as a scratch panel of KMUP2, wgr or bwgr_em -- and frees it; a clone (bwgr_panel_clone) is another handle on the
 // same data.  Every handle owns its streams and the scratch its sweeps write.  The data does not change while a clone is alive: it is
 // built with the root, and bwgr_panel_set_centred refuses on a clone and while any chain is alive.
-// Each of PanelData, bwgr_panel, bwgr_chain and bwgr_group owns its device arrays, streams and long-lived events through a holder (`own`);
-// the typed pointers below are aliases, and deleting the struct releases them.  What is allocated lazily as a group is one take().
+// Each of PanelData, bwgr_panel, bwgr_chain and bwgr_group owns its device arrays, streams and events through a holder (`own`); the typed
+// pointers below are aliases, and deleting the struct releases them.  What is allocated lazily as a group is one take().  The sweep path too: a
+// chain's timing pairs (EventPairs), a handle's guard event, hand-over event and draws group.  Only HipBackend creates or destroys a stream or an event.
+// k_draws: the next iteration's state-independent variates, drawn on a second (low-priority) stream beside this iteration's sweep (draws_ahead)
+struct DrawsAhead {
+  double *buf = nullptr; hipStream_t stream = nullptr; hipEvent_t ready = nullptr, free = nullptr;   // the handle's holder's, one take()
+  bool valid = false, unavailable = false;   // buf is (behind `ready`) what is described below; the set-up failed once and is not tried again
+  Rng rng = {}; uint32_t iter = 0, marker0 = 0; int flags = 0, j0 = 0, j1 = 0; const void *sc = nullptr;
+  // they are the variates of the sweep with arguments a over markers [j0_, j1_): same streams, same counters, same flags, this range inside theirs
+  bool matches(const SweepArgs &a, int j0_, int j1_) const {
+    return valid && iter == a.iter && marker0 == a.marker0 && flags == (a.flags & (SWF_SELECT | SWF_VB_VEC)) && sc == (const void *)a.sc && j0 <= j0_ && j1 >= j1_ &&
+           memcmp(&rng, &a.rng, sizeof(Rng)) == 0 && !(a.flags & (SWF_MH | SWF_EM_ANY));
+  }
+  // the chain with scalars sc_ goes away: variates drawn ahead for it are nobody's now (k_draws reads the chain's df from them, so it is waited for)
+  void forget(const void *sc_) {
+    if (sc == sc_) { if (stream) (void)hipStreamSynchronize(stream); valid = false; sc = nullptr; }
+  }
+};
+
 struct PanelData {
   DevBufs own;                // the genotypes, the Gram family, the statistics, csum / xxc and the pair streams
   int device = 0, is_f32 = 0;
@@ -180,12 +197,13 @@ struct PanelData {
   int nclones = 0;            // live clones: the root's bwgr_panel_destroy refuses while any is alive
   int nchains_all = 0;        // live chains on every handle (bwgr_panel_set_centred refuses while any is alive)
   std::vector<hipStream_t> pair_streams;   // the streams pairs of chains run on (bwgr_chain_run_pair); here, so that they outlive every clone
+  std::vector<int> pair_users;             // ... and the handles on each right now (pair_stream_count): a pair takes an idle one before a new one is made
 };
 
 struct bwgr_panel {
   PanelData *data = nullptr;
   bool is_root = false;       // made with the data, which it frees; false: a clone
-  DevBufs own;                // the sweep scratch, the exchange words, the lazy groups, a clone's stream, the draws stream and events
+  DevBufs own;                // the sweep scratch, the exchange words, the lazy groups, a clone's stream, the draws group, the guard and hand-over events
   hipStream_t stream = nullptr;
   hipStream_t pre_pair_stream = nullptr; bool pre_pair_set = false;   // the stream this handle ran on before a pair run moved it (restored by its next sweep alone)
   // the sweep scratch (scratch_alloc, and what the first sweep that needs it takes)
@@ -203,18 +221,17 @@ struct bwgr_panel {
   double *winv = nullptr;     // [nblocks][S2W_WDOUBLES], written by k_affine_inv before every affine sweep (sweep2w.hip.h)
   unsigned long long *qsumw = nullptr;   // the fixed-point streamers' slab-dot sums [nblocks][SW_MAXM][2]
   double *cpre = nullptr;     // implicitly centred columns: the running block sums of s_k * drej_k of the current iteration
-  // k_draws: the next iteration's state-independent variates, drawn on a second (low-priority) stream beside this iteration's sweep
-  double *draws = nullptr; hipStream_t draws_stream = nullptr; hipEvent_t draws_ready = nullptr, draws_free = nullptr;
-  bool draws_valid = false; Rng draws_rng = {}; uint32_t draws_iter = 0, draws_marker0 = 0; int draws_flags = 0, draws_j0 = 0, draws_j1 = 0; const void *draws_sc = nullptr;
+  DrawsAhead draws;           // the next iteration's variates, drawn beside this iteration's sweep (draws_ahead)
   // occupancy guard: the compute units this handle's enqueued sweeps hold while they run, the stream they run on, and an event behind the last of them
   hipEvent_t guard_ev = nullptr; int guard_cus = 0; hipStream_t guard_stream = nullptr; bool guard_listed = false;
+  hipEvent_t handover_ev = nullptr;   // for the handle's moves between streams (hand_over); like guard_ev the holder's, made on first use
   int debug_withhold = 0;     // test hook: the next sweeps run with slab workgroup 0 missing (bwgr_debug_withhold)
   int nchains = 0;            // live chains on this handle: panel_destroy refuses while any is alive
 };
 
 struct bwgr_chain {
   bwgr_panel *P = nullptr;
-  DevBufs own;                        // the state arrays (e: unless the caller gave one)
+  DevBufs own;                        // the state arrays (e: unless the caller gave one) and the timing pairs' events
   int model = 0, iit = 0, ibi = 0, done = 0, rng_mode = 0;
   float itf = 0, bif = 0, pi = 0, df = 0, R2 = 0, Phi = 0;
   uint64_t seed = 0;
@@ -226,7 +243,7 @@ struct bwgr_chain {
   float MSx_eff = 0;                  // MSx over all ranks
   double *e0 = nullptr;               // residual at the start of the current exchange round (sharded stepping)
   int flags_extra = 0;                // two-effect BayesB2: SWF_ALT_B2 (the likelihood comparison uses the drawn alternative)
-  std::vector<hipEvent_t> ev;  // pairs around each sweep launch since the last query
+  EventPairs<HipBackend> timing;      // a pair around each sweep launch since the last bwgr_chain_sweep_ms
   float ms_acc = 0; int launch_acc = 0;
   bool finalized = false;
 };
@@ -244,6 +261,17 @@ static hipError_t d2h(hipStream_t st, void *dst, const void *src, size_t bytes) 
 template <typename T> static hipError_t h2d(hipStream_t st, T *dst, const T *src, size_t count) { return hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyHostToDevice, st); }
 template <typename T> static hipError_t d2d(hipStream_t st, T *dst, const T *src, size_t count) { return hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyDeviceToDevice, st); }
 template <typename T> static hipError_t zero(hipStream_t st, T *dst, size_t count) { return hipMemsetAsync(dst, 0, sizeof(T) * count, st); }
+// stream `later` goes on after what is pending on stream `earlier`: ev is recorded on earlier, and later waits for it.  (The wait captures the
+// event's state when it is enqueued, so an event that is recorded again later still serves its earlier waits: one event per owner is enough.)
+static hipError_t stream_after(hipStream_t later, hipStream_t earlier, hipEvent_t ev) {
+  const hipError_t e = hipEventRecord(ev, earlier);
+  return e != hipSuccess ? e : hipStreamWaitEvent(later, ev, 0);
+}
+// ... through *ev, an event of `own` made the first time: a handle's own hand-over event (onto a pair's stream and back), or a call's
+static hipError_t hand_over(DevBufs &own, hipEvent_t *ev, hipStream_t later, hipStream_t earlier) {
+  if (!*ev && !(*ev = own.event(hipEventDisableTiming))) return hipErrorOutOfMemory;
+  return stream_after(later, earlier, *ev);
+}
 
 static Rng make_rng(uint64_t seed, int mode) {
   Rng g; g.k0 = (uint32_t)seed; g.k1 = (uint32_t)(seed >> 32); g.degenerate = (mode == BWGR_RNG_DEGENERATE); return g;

@@ -10,6 +10,7 @@
 // kernel or asynchronous copy still uses a buffer or a host local of the frame that goes away (a host vector that is copied from asynchronously
 // is declared before the holder, and so outlives that wait).  A handle's holder is a member of the handle: the handle's typed pointers are
 // aliases of what the holder owns, and deleting the handle releases all of it.
+// Beside the holder: EventPairs, a chain's pool of timing pairs, whose events are the chain's holder's.
 #pragma once
 #include <stddef.h>
 #include <algorithm>
@@ -102,5 +103,37 @@ template <class B> class DevHolder {
   stream_t sync_stream_{};
   bool sync_ = false;
   bool failed_ = false;
+};
+
+// A pool of event pairs for timing (flags 0), one pair around each launch since the last fold.  It owns nothing: every event is a holder's,
+// made the first time its slot is reached and reused after every rewind(), so a launch creates and destroys nothing and no path out of a
+// caller has anything to clean up.  next() hands out the first unused pair, commit() marks it used once the launches it times stand; a pair
+// that is not committed is the next one handed out.
+template <class B> class EventPairs {
+ public:
+  using event_t = typename B::event_t;
+  static constexpr size_t kCapacity = 2048;   // pairs: a caller folds (reads the pairs, rewinds) once full()
+  // false, with both outputs empty, where the pool is full or the slot's pair cannot be made (nothing of it stays behind)
+  bool next(DevHolder<B> &own, event_t *e0, event_t *e1) {
+    *e0 = *e1 = event_t{};
+    if (full()) return false;
+    if (2 * used_ == ev_.size()) {
+      event_t a{}, b{};
+      if (!own.take({DevHolder<B>::want_event(&a, 0), DevHolder<B>::want_event(&b, 0)})) return false;
+      ev_.push_back(a); ev_.push_back(b);
+    }
+    *e0 = ev_[2 * used_]; *e1 = ev_[2 * used_ + 1];
+    return out_ = true;
+  }
+  void commit() { if (out_) { ++used_; out_ = false; } }   // (the pair last handed out, once)
+  size_t used() const { return used_; }
+  void pair(size_t i, event_t *e0, event_t *e1) const { *e0 = ev_[2 * i]; *e1 = ev_[2 * i + 1]; }
+  void rewind() { used_ = 0; out_ = false; }
+  bool full() const { return used_ >= kCapacity; }
+
+ private:
+  std::vector<event_t> ev_;   // aliases of the holder's events: slot i is ev_[2 i], ev_[2 i + 1]
+  size_t used_ = 0;
+  bool out_ = false;          // a pair was handed out and is neither committed nor rewound
 };
 }  // namespace bwgr

@@ -120,9 +120,9 @@ static int group_create_impl(bwgr_group **out, int ndev, const int *devices, con
     CHK(bwgr_panel_create(&Gp->P[g], reinterpret_cast<const unsigned char *>(X) + (size_t)lo * (size_t)ldx * esz, xtype, memloc, n, hi - lo, ldx, devices[g], m, 0));
     if (Gp->same_dev) {   // shards of one device: each on a stream of its own; from three shards on, 256-row streamers (K3 + 1 units a shard instead of 2 K3 + 2)
       hipStream_t q = Gp->own[g]->stream(hipStreamNonBlocking, 0);
-      if (!q) return fail(BWGR_EHIP, "group_create: hipStreamCreate failed");
+      if (!q) return fail(BWGR_EHIP, "group_create: no stream for shard %d", g);
       Gp->streams.push_back(q);
-      Gp->P[g]->stream = q;
+      Gp->P[g]->stream = q;   // (no wait: bwgr_panel_create hands a panel over with nothing pending on its stream)
       if (ndev > 2 && Gp->P[g]->data->sw.solo3 < 0) Gp->P[g]->data->crowded = true;   // (an explicit BWGR_SOLO3 decides otherwise: experiments)
     }
     if (centre) CHK(bwgr_panel_set_centred(Gp->P[g], 1));   // the shard's own column means (rows are not sharded)
@@ -156,7 +156,7 @@ static int group_create_impl(bwgr_group **out, int ndev, const int *devices, con
   if (Gp->same_dev) {
     if (hipSetDevice(devices[0]) != hipSuccess) return fail(BWGR_EHIP, "group_create: hipSetDevice failed");
     Gp->ev_sweep.assign(ndev, nullptr);
-    for (int g = 0; g < ndev; ++g) if (!(Gp->ev_sweep[g] = Gp->own[g]->event(hipEventDisableTiming))) return fail(BWGR_EHIP, "group_create: hipEventCreate failed");
+    for (int g = 0; g < ndev; ++g) if (!(Gp->ev_sweep[g] = Gp->own[g]->event(hipEventDisableTiming))) return fail(BWGR_EHIP, "group_create: no event for shard %d's sweeps", g);
     for (int k = 0; k < 2; ++k) {
       if (!Gp->own[0]->take({DevBufs::want_event(&Gp->ev_sum[k], hipEventDisableTiming), {&Gp->total[k], sizeof(double) * (size_t)Gp->P[0]->data->plan.ld}, {&Gp->total_sums[k], sizeof(double) * 2}}))
         return no_memory("group_create");

@@ -117,10 +117,8 @@ static int xyt_accept(bwgr_panel *Pf, bwgr_panel *Ps, int memloc, const char *wh
 // the founders' stream goes on after everything pending on the samples' stream
 static int xyt_order(bwgr_panel *Pf, bwgr_panel *Ps, DevBufs &bufs, const char *who) {
   if (Ps->stream == Pf->stream) return BWGR_OK;
-  hipEvent_t ev = bufs.event(hipEventDisableTiming);
-  if (!ev) return fail(BWGR_EHIP, "%s: hipEventCreate failed", who);
-  HIPCHK(hipEventRecord(ev, Ps->stream));
-  HIPCHK(hipStreamWaitEvent(Pf->stream, ev, 0));
+  hipEvent_t ev = nullptr;
+  HIPCHK(hand_over(bufs, &ev, Pf->stream, Ps->stream));
   return BWGR_OK;
 }
 // The planned product into the device array Gd (int64, row stride ldg), enqueued on Pr's stream: G = X X' over Pr's n rows, both triangles

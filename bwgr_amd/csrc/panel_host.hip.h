@@ -77,6 +77,7 @@ extern "C" int bwgr_panel_destroy(bwgr_panel *P) {
   if (P->nchains > 0) return fail(BWGR_EINVAL, "panel_destroy: %d chain(s) on this panel are still alive (destroy them first)", P->nchains);
   (void)hipSetDevice(D->device);
   guard_forget(P);
+  if (P->pre_pair_set) pair_stream_count(D, P->stream, -1);
   const bool root = P->is_root;
   delete P;   // the handle's scratch and streams, then the data's arrays and the pair streams
   if (root) delete D;
@@ -297,6 +298,7 @@ extern "C" int bwgr_panel_create(bwgr_panel **out, const void *X, int xtype, int
   else CHK((upload<double, float>(P, X, memloc, ldx)));
   CHK(panel_setup(P));
   CHK(scratch_alloc(P));
+  HIPCHK(hipStreamSynchronize(P->stream));   // handed over with nothing pending (k_sweep3's lists are zeroed on it): whoever gives the handle another stream orders nothing
   drop.release();
   *out = P;
   return BWGR_OK;
@@ -321,7 +323,7 @@ extern "C" int bwgr_panel_clone(bwgr_panel **out, bwgr_panel *src) {
   bwgr_panel *P = new bwgr_panel();
   P->data = src->data; P->data->nclones++;
   Guard drop([&] { bwgr_panel_destroy(P); });
-  if (!(P->stream = P->own.stream(hipStreamNonBlocking, 0))) return fail(BWGR_EHIP, "panel_clone: hipStreamCreate failed");
+  if (!(P->stream = P->own.stream(hipStreamNonBlocking, 0))) return fail(BWGR_EHIP, "panel_clone: no stream for the clone");
   CHK(scratch_alloc(P));
   HIPCHK(hipStreamSynchronize(P->stream));   // (k_sweep3's lists are zeroed on it)
   drop.release();

@@ -1,7 +1,8 @@
 // bwgr_amd/csrc/samplers_host.hip.h -- the host entries of the float samplers: KMUP / KMUP2, the fused chains (bwgr_chain_*), bwgr_bayes and
 // the two-panel bwgr_bayes2.  Part of bwgr_hip.hip, which includes it after everything it uses (fail, HIPCHK, DevBufs, no_memory, d2h / h2d /
 // zero, Guard, sum_floats, sweep_args, launch_sweep and the sweep's planning and launching, the scratch panels, launch_gather_rows, gemv_hat,
-// g_last_redo); it defines no kernel: theirs are chain.hip.h and panel.hip.h.
+// g_last_redo); it defines no kernel: theirs are chain.hip.h and panel.hip.h.  A chain times its sweeps between the event pairs of its pool
+// (bwgr_chain::timing, the holder's events): a sweep takes the next pair and commits it once its launches stand; bwgr_chain_sweep_ms, or a full pool, reads them and rewinds.
 // ------------------------------------------------------------------------------------------------
 // KMUP
 // ------------------------------------------------------------------------------------------------
@@ -96,13 +97,9 @@ static bool has_d(int model) { return model == BWGR_BAYESB || model == BWGR_BAYE
 extern "C" int bwgr_chain_destroy(bwgr_chain *C) {
   if (!C) return BWGR_OK;
   if (C->P && C->P->ps_owner == C) C->P->ps_owner = nullptr;   // (a later chain may be allocated at this address)
-  if (C->P && C->P->draws_sc == (const void *)C->sc) {          // ... and so may its scalars: variates drawn ahead for this chain are nobody's now
-    if (C->P->draws_stream) (void)hipStreamSynchronize(C->P->draws_stream);   // (k_draws reads the chain's df from them)
-    C->P->draws_valid = false; C->P->draws_sc = nullptr;
-  }
+  if (C->P) C->P->draws.forget(C->sc);                         // ... and so may its scalars: variates drawn ahead for this chain are nobody's now
   if (C->P) { C->P->nchains--; C->P->data->nchains_all--; (void)hipSetDevice(C->P->data->device); }
-  for (hipEvent_t ev : C->ev) hipEventDestroy(ev);
-  delete C;
+  delete C;   // (the state arrays and the timing pairs' events: the holder's)
   return BWGR_OK;
 }
 
@@ -172,9 +169,7 @@ extern "C" int bwgr_chain_sweep_blocks(bwgr_chain *C, int blk_begin, int blk_end
   chain_args(C, blk_begin, blk_end, a);
   SweepTrain t; t.P[0] = P; t.a[0] = &a;
   CHK(train_begin(t));
-  hipEvent_t &e0 = t.ev[0][0], &e1 = t.ev[0][1];
-  HIPCHK(hipEventCreate(&e0));
-  if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail(BWGR_EHIP, "sweep_blocks: hipEventCreate failed"); }
+  if (!C->timing.next(C->own, &t.ev[0][0], &t.ev[0][1])) return fail(BWGR_EHIP, "sweep_blocks: no event pair for the sweep's timing");
   // the per-marker constants and speculative terms of an iteration depend on the state at its start only (a block's b is
   // untouched until the block is swept), so a chain that sweeps its panel in several ranges -- the exchange rounds of the
   // marker-sharded sampler -- pre-stages all of them with the first range
@@ -187,10 +182,10 @@ extern "C" int bwgr_chain_sweep_blocks(bwgr_chain *C, int blk_begin, int blk_end
   }
   t.draws_next = prestaged && C->done + 1 < C->iit;   // the next iteration's variates, beside this sweep
   const hipError_t he = train_launch(t);
-  if (he != hipSuccess) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return fail(BWGR_EHIP, "sweep_blocks: %s", hipGetErrorString(he)); }
-  C->ev.push_back(e0); C->ev.push_back(e1);
+  if (he != hipSuccess) return fail(BWGR_EHIP, "sweep_blocks: %s", hipGetErrorString(he));   // (the pair, not committed, is the next sweep's)
   train_end(t);
-  if (C->ev.size() >= 4096) CHK(bwgr_chain_sweep_ms(C, nullptr, nullptr));   // bound the number of live events
+  C->timing.commit();
+  if (C->timing.full()) CHK(bwgr_chain_sweep_ms(C, nullptr, nullptr));   // fold: the pool's pairs are read and handed out again
   return BWGR_OK;
 }
 
@@ -298,19 +293,22 @@ extern "C" int bwgr_chain_run_pair(bwgr_chain *C0, bwgr_chain *C1, int iters) {
   // everything of the pair runs on ONE stream, owned by the root panel (it outlives both handles), and both handles move onto it
   // for as long as they run in pairs -- one cross-stream wait each, the first time: a wait per call would sit in a hardware queue
   // that other pairs' streams share, and stall them.  A handle's next sweep alone takes it back (leave_pair_stream).
-  auto is_pair_stream = [&](hipStream_t st) { for (hipStream_t q : P0->data->pair_streams) if (q == st) return true; return false; };
+  // The stream one of the two is on already, else a pair stream that every handle has left, else a new one.
+  PanelData *D = P0->data;
+  auto is_pair_stream = [&](hipStream_t st) { for (hipStream_t q : D->pair_streams) if (q == st) return true; return false; };
   hipStream_t s0 = nullptr;
   if (is_pair_stream(P0->stream)) s0 = P0->stream;
   else if (is_pair_stream(P1->stream)) s0 = P1->stream;
-  else if ((s0 = P0->data->own.stream(hipStreamNonBlocking, 0))) P0->data->pair_streams.push_back(s0);
-  else return fail(BWGR_EHIP, "chain_run_pair: hipStreamCreate failed");
+  for (size_t i = 0; !s0 && i < D->pair_streams.size(); ++i) if (D->pair_users[i] <= 0) s0 = D->pair_streams[i];
+  if (!s0) {
+    if (!(s0 = D->own.stream(hipStreamNonBlocking, 0))) return fail(BWGR_EHIP, "chain_run_pair: no stream for the pair");
+    D->pair_streams.push_back(s0); D->pair_users.push_back(0);
+  }
   for (bwgr_panel *PX : {P0, P1}) {
     if (PX->stream == s0) continue;
-    hipEvent_t ev;
-    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(ev, PX->stream)); HIPCHK(hipStreamWaitEvent(s0, ev, 0));
-    HIPCHK(hipEventDestroy(ev));
+    HIPCHK(hand_over(PX->own, &PX->handover_ev, s0, PX->stream));
     if (!PX->pre_pair_set) { PX->pre_pair_stream = PX->stream; PX->pre_pair_set = true; }   // (leave_pair_stream takes the handle back)
+    pair_stream_count(D, PX->stream, -1); pair_stream_count(D, s0, +1);
     PX->stream = s0;
   }
   // the pair's one launch, resident beside the other streams' sweeps
@@ -323,18 +321,17 @@ extern "C" int bwgr_chain_run_pair(bwgr_chain *C0, bwgr_chain *C1, int iters) {
     if ((rc = train_begin(t)) != BWGR_OK) break;
     launch_prestage(P0, a0, t.pl[0]); launch_prestage(P1, a1, t.pl[1]);
     P0->ps_owner = C0; P0->ps_iter = C0->done; P1->ps_owner = C1; P1->ps_iter = C1->done;
-    hipEvent_t *evs[4] = {&t.ev[0][0], &t.ev[0][1], &t.ev[1][0], &t.ev[1][1]};   // both chains time the launch they share
-    bool ev_ok = true;
-    for (int q = 0; q < 4 && ev_ok; ++q) ev_ok = hipEventCreate(evs[q]) == hipSuccess;
-    if (!ev_ok) { for (hipEvent_t *q : evs) if (*q) (void)hipEventDestroy(*q); rc = fail(BWGR_EHIP, "chain_run_pair: hipEventCreate failed"); break; }
+    if (!C0->timing.next(C0->own, &t.ev[0][0], &t.ev[0][1]) || !C1->timing.next(C1->own, &t.ev[1][0], &t.ev[1][1])) {   // both chains time the launch they share
+      rc = fail(BWGR_EHIP, "chain_run_pair: no event pair for the sweep's timing"); break;
+    }
     const hipError_t he = train_launch(t);
-    if (he != hipSuccess) { for (hipEvent_t *q : evs) (void)hipEventDestroy(*q); rc = fail(BWGR_EHIP, "chain_run_pair: launch failed: %s", hipGetErrorString(he)); break; }
-    C0->ev.push_back(t.ev[0][0]); C0->ev.push_back(t.ev[0][1]); C1->ev.push_back(t.ev[1][0]); C1->ev.push_back(t.ev[1][1]);
+    if (he != hipSuccess) { rc = fail(BWGR_EHIP, "chain_run_pair: launch failed: %s", hipGetErrorString(he)); break; }
     train_end(t);
+    C0->timing.commit(); C1->timing.commit();
     if ((rc = bwgr_chain_end_iteration(C0, nullptr)) != BWGR_OK) break;
     rc = bwgr_chain_end_iteration(C1, nullptr);
-    if (C0->ev.size() >= 4096) (void)bwgr_chain_sweep_ms(C0, nullptr, nullptr);
-    if (C1->ev.size() >= 4096) (void)bwgr_chain_sweep_ms(C1, nullptr, nullptr);
+    if (C0->timing.full()) (void)bwgr_chain_sweep_ms(C0, nullptr, nullptr);
+    if (C1->timing.full()) (void)bwgr_chain_sweep_ms(C1, nullptr, nullptr);
   }
   return rc;
 }
@@ -359,14 +356,13 @@ extern "C" int bwgr_chain_sweep_ms(bwgr_chain *C, float *avg_ms, int *launches) 
   if (!C) return fail(BWGR_EINVAL, "null chain");
   HIPCHK(hipSetDevice(C->P->data->device));
   HIPCHK(hipStreamSynchronize(C->P->stream));
+  Guard rewind([&] { C->timing.rewind(); });   // on a failed read too, which loses this interval's timing and nothing else
   float total = 0; int nl = 0;
-  for (size_t k = 0; k + 1 < C->ev.size(); k += 2) {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, C->ev[k], C->ev[k + 1]));
+  for (size_t k = 0; k < C->timing.used(); ++k) {
+    float ms = 0; hipEvent_t e0, e1; C->timing.pair(k, &e0, &e1);
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
     total += ms; nl++;
-    hipEventDestroy(C->ev[k]); hipEventDestroy(C->ev[k + 1]);
   }
-  C->ev.clear();
   C->ms_acc += total; C->launch_acc += nl;
   if (avg_ms && launches) {
     *launches = C->launch_acc;

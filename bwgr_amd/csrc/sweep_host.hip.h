@@ -2,7 +2,8 @@
 // guard that prices the plan, the kernels in front of a sweep (launch_prestage, draws_ahead), the launch train behind the plan (SweepTrain,
 // launch_sweep), sweep_args, and the entries that answer from a plan (bwgr_panel_max_concurrent / _max_pairs / _pipeline, bwgr_debug_sweep3_kernel,
 // bwgr_debug_withhold).  Part of bwgr_hip.hip, which includes it after the handle structs and before panel_host.hip.h (bwgr_panel_destroy forgets
-// the handle's guard entry); it defines no kernel.
+// the handle's guard entry); it defines no kernel.  It creates and destroys no event or stream: the guard event, the hand-over event and the draws
+// group are the handle's holder's, made by the first sweep that needs them and reused; SweepTrain::ev are the caller's (a chain's timing pairs).
 // ---- the sweep plan -----------------------------------------------------------------------------------------------------------
 // Which engine a sweep runs, how deep, in what launch shape and between which helper kernels is one decision, made by plan_sweep (below) from
 // host facts about the panel and the handle (SweepFacts: geometry, Gram range, clones, switches), the sweep's flags and block range, and its
@@ -116,21 +117,21 @@ static int sweep_guard(const bwgr_panel *P, const SweepPlan &pl, hipStream_t st,
   std::lock_guard<std::mutex> lk(g_guard_mu);
   return plan_cus(pl, cus, guard_busy(P, st, partner), need);
 }
-// after the real launches: this handle holds `need` units until the event behind them completes
+// after the real launches: this handle holds `need` units until the event behind them completes (no event: no guard entry)
 static void guard_mark(bwgr_panel *P, hipStream_t st, int need) {
   if (need <= 0) return;
   std::lock_guard<std::mutex> lk(g_guard_mu);
-  if (!P->guard_ev) { if (hipEventCreateWithFlags(&P->guard_ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); P->guard_ev = nullptr; return; } }
+  if (!P->guard_ev && !(P->guard_ev = P->own.event(hipEventDisableTiming))) return;
   if (!P->guard_listed) { g_guard_panels.push_back(P); P->guard_listed = true; }
   if (P->guard_cus > 0 && P->guard_stream == st && hipEventQuery(P->guard_ev) != hipSuccess) { (void)hipGetLastError(); need = std::max(need, P->guard_cus); }
   P->guard_cus = need; P->guard_stream = st;
   (void)hipEventRecord(P->guard_ev, st);
 }
+// before the handle is deleted (guard_busy queries other handles' events under the mutex): unlisted here, its event goes with its holder
 static void guard_forget(bwgr_panel *P) {
   std::lock_guard<std::mutex> lk(g_guard_mu);
   for (size_t i = 0; i < g_guard_panels.size(); ++i) if (g_guard_panels[i] == P) { g_guard_panels.erase(g_guard_panels.begin() + i); break; }
-  if (P->guard_ev) { (void)hipEventDestroy(P->guard_ev); P->guard_ev = nullptr; }
-  P->guard_listed = false; P->guard_cus = 0;
+  P->guard_listed = false; P->guard_cus = 0; P->guard_stream = nullptr;
 }
 
 // polled words are zeroed before every launch (epochs count within a launch)
@@ -372,17 +373,14 @@ static void launch_prestage(bwgr_panel *P, const SweepArgs &a_in, const SweepPla
   const int sh_add = P->data->sw.sh_add;   // test hook: less headroom, to leave the range on purpose
   int xbits = 0; while ((1 << xbits) < std::max(1, P->data->xmax)) ++xbits;   // (the fixed-point scales: the residual, and what k_prestage knows of the steps times the largest |x|)
   if (pl.escale_reset) hipLaunchKernelGGL(k_escale_reset, dim3(1), dim3(1), 0, P->stream, a.sc);
-  // the variates drawn ahead (draws_ahead, below) when they are this very iteration's: same streams, same counters, same flags, this range inside theirs
-  const int dflags = a.flags & (SWF_SELECT | SWF_VB_VEC);
-  const bool have_draws = P->draws_valid && P->draws_iter == a.iter && P->draws_marker0 == a.marker0 && P->draws_flags == dflags &&
-                          P->draws_sc == (const void *)a.sc && P->draws_j0 <= j0 && P->draws_j1 >= j1 && memcmp(&P->draws_rng, &a.rng, sizeof(Rng)) == 0 &&
-                          !(a.flags & (SWF_MH | SWF_EM_ANY));
+  // the variates drawn ahead (draws_ahead, below) when they are this very iteration's
+  DrawsAhead &dr = P->draws;
   a.draws = nullptr;
-  if (have_draws) { const hipError_t he = hipStreamWaitEvent(P->stream, P->draws_ready, 0); if (he == hipSuccess) a.draws = P->draws; else { fprintf(stderr, "bwgr: draws wait failed: %s\n", hipGetErrorString(he)); (void)hipGetLastError(); } }
+  if (dr.matches(a, j0, j1)) { const hipError_t he = hipStreamWaitEvent(P->stream, dr.ready, 0); if (he == hipSuccess) a.draws = dr.buf; else { fprintf(stderr, "bwgr: draws wait failed: %s\n", hipGetErrorString(he)); (void)hipGetLastError(); } }
   if (a.draws) {
     hipLaunchKernelGGL(k_prestage_fin, dim3((unsigned)std::min<int64_t>(2048, (j1 - j0 + 255) / 256)), dim3(256), 0, P->stream, a, j0, j1);
-    { const hipError_t he = hipEventRecord(P->draws_free, P->stream); if (he != hipSuccess) { fprintf(stderr, "bwgr: draws_free record failed: %s\n", hipGetErrorString(he)); (void)hipGetLastError(); } }
-    P->draws_valid = false;   // (consumed: the buffer is the next iteration's from here)
+    { const hipError_t he = hipEventRecord(dr.free, P->stream); if (he != hipSuccess) { fprintf(stderr, "bwgr: draws_free record failed: %s\n", hipGetErrorString(he)); (void)hipGetLastError(); } }
+    dr.valid = false;   // (consumed: the buffer is the next iteration's from here)
   } else hipLaunchKernelGGL(k_prestage, dim3((unsigned)std::min<int64_t>(4096, (tasks + 255) / 256)), dim3(256), 0, P->stream, a, j0, j1);
   if (pl.sweep3) {   // the sweep's fixed-point scale, then the in-block speculative terms on that grid
     hipLaunchKernelGGL(k_escale, dim3(1), dim3(1024), 0, P->stream, a.e, P->data->plan.ld, a.sc, xbits, a.gate3, sh_add);
@@ -404,28 +402,31 @@ static void launch_prestage(bwgr_panel *P, const SweepArgs &a_in, const SweepPla
 }
 
 // The next iteration's variates, enqueued beside this iteration's sweep (see k_draws) where the plan says so.  `a` = this iteration's arguments
-// over the whole panel.  Failing to set it up is not an error: k_prestage draws for itself whenever the buffer is not this iteration's.
+// over the whole panel.  Failing to set it up is not an error, and is not tried again: k_prestage draws for itself whenever the buffer is not
+// this iteration's.
 static void draws_ahead(bwgr_panel *P, const SweepArgs &a, const SweepPlan &pl, hipEvent_t before_sweep) {
-  if (!pl.draws) return;
-  if (!P->draws) {
+  DrawsAhead &dr = P->draws;
+  if (!pl.draws || dr.unavailable) return;
+  if (!dr.buf) {
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);   // (lo: the numerically largest = the lowest priority)
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_draws), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) { (void)hipGetLastError(); return; }
-    if (!P->own.take({{&P->draws, sizeof(double) * 5 * (size_t)P->data->p}, DevBufs::want_stream(&P->draws_stream, hipStreamNonBlocking, lo),
-                      DevBufs::want_event(&P->draws_ready, hipEventDisableTiming), DevBufs::want_event(&P->draws_free, hipEventDisableTiming)})) return;
-    (void)hipEventRecord(P->draws_free, P->stream);
+    dr.unavailable = hipFuncSetAttribute(reinterpret_cast<const void *>(k_draws), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess ||
+                     !P->own.take({{&dr.buf, sizeof(double) * 5 * (size_t)P->data->p}, DevBufs::want_stream(&dr.stream, hipStreamNonBlocking, lo),
+                                   DevBufs::want_event(&dr.ready, hipEventDisableTiming), DevBufs::want_event(&dr.free, hipEventDisableTiming)});
+    if (dr.unavailable) { (void)hipGetLastError(); return; }
+    (void)hipEventRecord(dr.free, P->stream);
   }
   const int j0 = a.blk_begin * a.m, j1 = (int)std::min<int64_t>(P->data->p, (int64_t)a.blk_end * a.m);
   // after this iteration's k_prestage has read the buffer (draws_free) -- or, the first time, after what is enqueued so far; 160 workgroups with 96 KB of
   // LDS each: at most 160 compute units, none of them one that runs a workgroup of the sweep
   // (... and after the iteration's speculative terms, which are bandwidth-bound and would share the chip with it: the event in front of the sweep)
-  { const hipError_t h1 = hipStreamWaitEvent(P->draws_stream, P->draws_free, 0), h2 = hipStreamWaitEvent(P->draws_stream, before_sweep, 0);
+  { const hipError_t h1 = hipStreamWaitEvent(dr.stream, dr.free, 0), h2 = hipStreamWaitEvent(dr.stream, before_sweep, 0);
     if (h1 != hipSuccess || h2 != hipSuccess) { fprintf(stderr, "bwgr: draws_ahead waits failed: %s / %s\n", hipGetErrorString(h1), hipGetErrorString(h2)); (void)hipGetLastError(); return; } }
-  hipLaunchKernelGGL(k_draws, dim3(160), dim3(1024), 96 * 1024, P->draws_stream, a.rng, a.marker0, a.iter + 1u, a.flags, (const ChainScalars *)a.sc, (int64_t)P->data->p, j0, j1, P->draws);
-  { const hipError_t h1 = hipGetLastError(); const hipError_t h2 = (h1 == hipSuccess) ? hipEventRecord(P->draws_ready, P->draws_stream) : hipSuccess;
-    if (h1 != hipSuccess || h2 != hipSuccess) { fprintf(stderr, "bwgr: k_draws launch / record failed: %s / %s\n", hipGetErrorString(h1), hipGetErrorString(h2)); (void)hipGetLastError(); P->draws_valid = false; return; } }
-  P->draws_valid = true; P->draws_rng = a.rng; P->draws_iter = a.iter + 1u; P->draws_marker0 = a.marker0; P->draws_flags = a.flags & (SWF_SELECT | SWF_VB_VEC);
-  P->draws_j0 = j0; P->draws_j1 = j1; P->draws_sc = (const void *)a.sc;
+  hipLaunchKernelGGL(k_draws, dim3(160), dim3(1024), 96 * 1024, dr.stream, a.rng, a.marker0, a.iter + 1u, a.flags, (const ChainScalars *)a.sc, (int64_t)P->data->p, j0, j1, dr.buf);
+  { const hipError_t h1 = hipGetLastError(); const hipError_t h2 = (h1 == hipSuccess) ? hipEventRecord(dr.ready, dr.stream) : hipSuccess;
+    if (h1 != hipSuccess || h2 != hipSuccess) { fprintf(stderr, "bwgr: k_draws launch / record failed: %s / %s\n", hipGetErrorString(h1), hipGetErrorString(h2)); (void)hipGetLastError(); dr.valid = false; return; } }
+  dr.valid = true; dr.rng = a.rng; dr.iter = a.iter + 1u; dr.marker0 = a.marker0; dr.flags = a.flags & (SWF_SELECT | SWF_VB_VEC);
+  dr.j0 = j0; dr.j1 = j1; dr.sc = (const void *)a.sc;
 }
 
 // what one launch of k_sweep3 / k_sweep3p needs beside the sweep's own arguments; zeroes the launch's slab-dot sums, takes a new epoch
@@ -508,16 +509,18 @@ static void launch_sweep_kernel(bwgr_panel *P, const SweepArgs &a, const SweepPl
   }
 }
 
+// d = +1 / -1: a handle moves onto / off stream st, counted where st is one of the data's pair streams.  The count only tells bwgr_chain_run_pair
+// which pair stream is idle, so that a pair which forms again does not make a stream each time: sharing one would still be ordered correctly.
+// (A paired handle that the caller gives another stream, bwgr_panel_set_stream, stays counted: that pair stream is not reused.)
+static void pair_stream_count(PanelData *D, hipStream_t st, int d) {
+  for (size_t i = 0; i < D->pair_streams.size(); ++i) if (D->pair_streams[i] == st) D->pair_users[i] += d;
+}
 // A handle that a pair run moved onto the pair's stream goes back to the stream it had (its own, or the caller's) when it next sweeps alone:
 // one wait, on the handle's stream -- nothing is enqueued on the pair stream, which other pairs' hardware queue shares
 static int leave_pair_stream(bwgr_panel *P) {
   if (!P->pre_pair_set) return BWGR_OK;
-  hipEvent_t ev;
-  HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  hipError_t he = hipEventRecord(ev, P->stream);
-  if (he == hipSuccess) he = hipStreamWaitEvent(P->pre_pair_stream, ev, 0);
-  (void)hipEventDestroy(ev);
-  if (he != hipSuccess) return fail(BWGR_EHIP, "leaving the pair stream: %s", hipGetErrorString(he));
+  HIPCHK(hand_over(P->own, &P->handover_ev, P->pre_pair_stream, P->stream));
+  pair_stream_count(P->data, P->stream, -1);
   P->stream = P->pre_pair_stream; P->pre_pair_set = false;
   return BWGR_OK;
 }

@@ -1,5 +1,5 @@
 // tests/devbufs_check.cpp -- the device holder (bwgr_amd/csrc/devbufs.h) on a counting fake backend that can fail the N-th allocation,
-// stream creation or event creation.  A program of its own: built with -fsanitize=address,undefined and run by tests/test_devbufs_cpu.py.
+// stream creation or event creation; and the pool of timing pairs that takes its events from a holder.  A program of its own: built with -fsanitize=address,undefined and run by tests/test_devbufs_cpu.py.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -181,7 +181,82 @@ static void destruction_order() {
   Fake::streams.erase(&callers);
 }
 
+// the pool of timing pairs: its events are the holder's, made once per slot and handed out again after rewind(); an uncommitted pair is
+// the next one handed out; a pair that cannot be made leaves nothing behind; full() at exactly the capacity
+using Pairs = bwgr::EventPairs<Fake>;
+static void pairs_reuse() {
+  {
+    Bufs h;
+    Pairs pool;
+    Fake::event_t a0 = nullptr, a1 = nullptr, b0 = nullptr, b1 = nullptr, c0 = nullptr, c1 = nullptr;
+    CHECK(pool.used() == 0 && !pool.full());
+    CHECK(pool.next(h, &a0, &a1) && a0 && a1 && a0 != a1 && a0->id == 0 && a1->id == 0);   // (flags 0: timing enabled)
+    CHECK(Fake::counts(0, 0, 2) && pool.used() == 0);                  // handed out is not yet used
+    CHECK(pool.next(h, &b0, &b1) && b0 == a0 && b1 == a1);             // not committed: the same pair again, nothing new
+    CHECK(Fake::counts(0, 0, 2));
+    pool.commit();
+    CHECK(pool.used() == 1);
+    pool.commit();                                                     // (nothing handed out since: no second count)
+    CHECK(pool.used() == 1);
+    CHECK(pool.next(h, &b0, &b1) && b0 != a0 && b1 != a1 && b0 != b1 && Fake::counts(0, 0, 4));
+    pool.commit();
+    CHECK(pool.used() == 2);
+    pool.pair(0, &c0, &c1); CHECK(c0 == a0 && c1 == a1);
+    pool.pair(1, &c0, &c1); CHECK(c0 == b0 && c1 == b1);
+    pool.rewind();
+    CHECK(pool.used() == 0 && Fake::counts(0, 0, 4));                  // every event is kept
+    pool.commit();                                                     // (made slots there are, but none handed out since the rewind)
+    CHECK(pool.used() == 0);
+    CHECK(pool.next(h, &c0, &c1) && c0 == a0); pool.rewind(); pool.commit();   // (a rewind takes a pair that is out back too)
+    CHECK(pool.used() == 0);
+    CHECK(pool.next(h, &c0, &c1) && c0 == a0 && c1 == a1); pool.commit();
+    CHECK(pool.next(h, &c0, &c1) && c0 == b0 && c1 == b1); pool.commit();
+    CHECK(Fake::counts(0, 0, 4) && pool.used() == 2);                  // made once, handed out again
+    CHECK(pool.next(h, &c0, &c1) && c0 != b0 && Fake::counts(0, 0, 6));
+  }
+  CHECK(Fake::counts(0, 0, 0));
+}
+static void pairs_fail() {
+  for (int pos = 1; pos <= 2; ++pos) {   // the first event of the pair, then the second
+    Bufs h;
+    Pairs pool;
+    Fake::event_t keep = h.event(1), e0 = nullptr, e1 = nullptr, f0 = nullptr, f1 = nullptr;
+    CHECK(pool.next(h, &e0, &e1)); pool.commit();
+    CHECK(keep && Fake::counts(0, 0, 3));
+    f0 = f1 = keep;   // (stale values: a failed next leaves none)
+    Fake::fail_at[2] = pos;
+    CHECK(!pool.next(h, &f0, &f1) && !f0 && !f1);
+    CHECK(Fake::counts(0, 0, 3) && pool.used() == 1);
+    CHECK(pool.next(h, &f0, &f1) && f0 && f1 && f0 != e0 && f1 != e1 && Fake::counts(0, 0, 5));
+    pool.commit();
+    CHECK(pool.used() == 2);
+    pool.pair(0, &f0, &f1); CHECK(f0 == e0 && f1 == e1);
+  }
+  CHECK(Fake::counts(0, 0, 0));
+}
+static void pairs_capacity() {
+  static_assert(Pairs::kCapacity == 2048, "the fold's cadence: once per 2048 sweeps");
+  {
+    Bufs h;
+    Pairs pool;
+    Fake::event_t e0 = nullptr, e1 = nullptr;
+    for (size_t i = 0; i < Pairs::kCapacity; ++i) {
+      CHECK(!pool.full());
+      CHECK(pool.next(h, &e0, &e1));
+      pool.commit();
+    }
+    CHECK(pool.full() && pool.used() == Pairs::kCapacity && Fake::counts(0, 0, 2 * (int64_t)Pairs::kCapacity));
+    CHECK(!pool.next(h, &e0, &e1) && !e0 && !e1 && Fake::counts(0, 0, 2 * (int64_t)Pairs::kCapacity));   // a caller folds first
+    pool.rewind();
+    CHECK(!pool.full() && pool.next(h, &e0, &e1) && Fake::counts(0, 0, 2 * (int64_t)Pairs::kCapacity));
+  }
+  CHECK(Fake::counts(0, 0, 0));   // the holder went away: so did every event
+}
+
 int main() {
+  pairs_reuse();
+  pairs_fail();
+  pairs_capacity();
   arrays_fail_everywhere();
   mixed_fail_everywhere();
   get_stream_event();

@@ -47,12 +47,16 @@ def test_holder_under_sanitizers(tmp_path):
 
 
 def test_one_place_allocates():
-    """hipMalloc( and hipFree( occur once each under bwgr_amd/csrc/, inside the HIP backend of the holder."""
+    """hipMalloc( and hipFree( occur once each under bwgr_amd/csrc/, inside the HIP backend of the holder; and whatever creates or destroys a
+    stream or an event (every hipEventCreate*, hipEventDestroy*, hipStreamCreate*, hipStreamDestroy*) occurs there and nowhere else, in code,
+    comments or messages."""
     found = {"hipMalloc(": [], "hipFree(": []}
+    inside_only = {"hipEventCreate": [], "hipEventDestroy": [], "hipStreamCreate": [], "hipStreamDestroy": []}
     for name in sorted(os.listdir(CSRC)):
         txt = open(os.path.join(CSRC, name)).read()
-        for call in found:
-            found[call] += [(name, m.start()) for m in re.finditer(re.escape(call), txt)]
+        for table in (found, inside_only):
+            for call in table:
+                table[call] += [(name, m.start()) for m in re.finditer(re.escape(call), txt)]
     src = open(os.path.join(CSRC, "bwgr_hip.hip")).read()
     begin = src.index("struct HipBackend {")
     end = src.index("\n};", begin)
@@ -60,6 +64,9 @@ def test_one_place_allocates():
         assert len(where) == 1, (call, where)
         name, at = where[0]
         assert name == "bwgr_hip.hip" and begin < at < end, (call, where)
+    for call, where in inside_only.items():
+        assert where, call   # (the backend does create and destroy them)
+        assert all(name == "bwgr_hip.hip" and begin < at < end for name, at in where), (call, where)
 
 
 def test_holder_header_is_plain_cxx():

@@ -39,15 +39,19 @@ def _family(tpod, monkeypatch):
     c_root.run(3)
     c_root.sync()
     after_run = live()
-    # the range snapshot (e, b, d, vb: four arrays) and the draws group (one array, one stream, two events), each taken whole
-    assert after_run == (before_run[0] + 5, before_run[1] + 1, before_run[2] + 2), (before_run, after_run)
+    # the range snapshot (e, b, d, vb: four arrays) and the draws group (one array, one stream, two events), each taken whole.  The events of
+    # the sweep path, by rule: two (a timing pair) per sweep launched since the chain's last sweep_ms, up to the pool's 2048 pairs; one guard
+    # event per handle whose sweeps went through the occupancy guard; one hand-over event per handle that has been handed from one stream to
+    # another (none here).  Three sweeps and the root's guard event beside the two of the draws group: 2 + 3 * 2 + 1.
+    assert after_run == (before_run[0] + 5, before_run[1] + 1, before_run[2] + 9), (before_run, after_run)
     clone = root.clone()
     c_clone = bwgr_amd.Chain(clone, "BayesA", y, it=3, bi=1, seed=12)
     before_run = live()
     c_clone.run(3)
     c_clone.sync()
-    # winv and qsumw, and the range snapshot of the fixed-point streamers; no draws ahead beside another handle
-    assert live() == (before_run[0] + 6, before_run[1], before_run[2]), (before_run, live())
+    # winv and qsumw, and the range snapshot of the fixed-point streamers; no draws ahead beside another handle.  Events: three timing pairs
+    # and the clone's guard event, 3 * 2 + 1
+    assert live() == (before_run[0] + 6, before_run[1], before_run[2] + 7), (before_run, live())
     cen = bwgr_amd.Panel(X)
     before_cen = live()
     cen.set_centred(True)
@@ -73,6 +77,65 @@ def test_family_made_run_and_torn_down(tpod, monkeypatch):
     assert end == start, (start, peak, end)
     start2, peak2, end2 = _family(tpod, monkeypatch)
     assert start2 == start and peak2 == peak and end2 == start, (start, peak, end, start2, peak2, end2)
+
+
+def test_timing_pairs_are_reused(tpod):
+    """A chain's timing pairs are made as its sweeps reach new slots of the pool, and handed out again after every sweep_ms."""
+    import bwgr_amd
+    y, X = tpod["y"], tpod["gen"]
+    start = live()
+    P = bwgr_amd.Panel(X)
+    ch = bwgr_amd.Chain(P, "BayesC", y, it=8, bi=1, seed=41)
+    ch.run(3)
+    ch.sync()
+    held = live()
+    ms, launches = ch.sweep_ms()
+    assert launches == 3 and np.isfinite(ms) and ms > 0, (ms, launches)
+    assert live() == held   # read and kept
+    ch.run(3)
+    ch.sync()
+    assert live() == held   # the same three pairs again: nothing grows
+    ch.run(2)
+    assert ch.sweep_ms()[1] == 5
+    ch.close()
+    P.close()
+    assert live() == start
+
+
+FOLD_IT = 2048 + 52   # the pool's capacity (bwgr_amd/csrc/devbufs.h, EventPairs::kCapacity) and some
+
+
+def test_timing_pairs_fold_at_the_capacity(tpod):
+    """More sweeps than the pool has pairs, with no sweep_ms in between: the library reads the full pool itself (the fold) and hands the same pairs
+    out again, so the live events stay within the capacity, the launches are counted across the fold, and the chain is the one it is
+    when its timing is read every 100 iterations."""
+    import bwgr_amd
+    y, X = tpod["y"], tpod["gen"]
+    start = live()
+    P = bwgr_amd.Panel(X)
+    kw = dict(it=FOLD_IT, bi=100, seed=43)
+    ch = bwgr_amd.Chain(P, "BayesC", y, **kw)
+    before = live()
+    ch.run(FOLD_IT)
+    ch.sync()
+    after = live()
+    # at most the pool, and the handle's guard event (no hand-over here) and the two events of its draws group
+    assert before[2] < after[2] <= before[2] + 2 * 2048 + 1 + 0 + 2, (before, after)
+    ms, launches = ch.sweep_ms()
+    assert launches == FOLD_IT and np.isfinite(ms) and ms > 0, (ms, launches)
+    b_whole = ch.result()["b"]
+    ch.close()
+    ch = bwgr_amd.Chain(P, "BayesC", y, **kw)
+    total = 0
+    for _ in range(FOLD_IT // 100):
+        ch.run(100)
+        total += ch.sweep_ms()[1]
+    assert total == FOLD_IT
+    b_parts = ch.result()["b"]
+    ch.close()
+    P.close()
+    assert np.array_equal(b_whole, b_parts)
+    assert live() == start
 
 
 def _incidence(n, q):
@@ -168,16 +231,72 @@ def test_pair_run(tpod):
     start = live()
     root = bwgr_amd.Panel(X)
     clone = root.clone()
-    c0 = bwgr_amd.Chain(root, "BayesC", y, it=3, bi=1, seed=21)
-    c1 = bwgr_amd.Chain(clone, "BayesC", y, it=3, bi=1, seed=22)
+    c0 = bwgr_amd.Chain(root, "BayesC", y, it=14, bi=1, seed=21)
+    c1 = bwgr_amd.Chain(clone, "BayesC", y, it=14, bi=1, seed=22)
     before = live()
     c0.run_pair(c1, 3)
     c0.sync(); c1.sync()
     assert live()[1] == before[1] + 1, (before, live())   # the pair stream, which lives in the data
+
+    def rest_of_cycle():
+        """... of: a pair run, one iteration of each chain alone (each handle back on its own stream), a second pair run (onto the pair's again)"""
+        assert c0.sweep_ms()[1] == 3 and c1.sweep_ms()[1] == 3   # both chains time the launch they share
+        c0.run(1); c1.run(1)
+        c0.run_pair(c1, 3)
+        c0.sync(); c1.sync()
+        assert c0.sweep_ms()[1] == 4 and c1.sweep_ms()[1] == 4
+        return live()
+    first = rest_of_cycle()
+    # by now each handle has its hand-over event and its guard event, and each chain four timing pairs (the rule of _family; no draws ahead
+    # beside a clone): the second cycle makes nothing
+    assert first[1:] == (before[1] + 1, before[2] + 2 * 4 * 2 + 2 + 2), (before, first)
+    c0.run_pair(c1, 3)
+    c0.sync(); c1.sync()
+    assert rest_of_cycle() == first
     c0.close(); c1.close()
     clone.close()
     assert live()[1] >= start[1] + 1   # ... and outlives the clone
     root.close()
+    assert live() == start
+
+
+def test_a_pair_that_forms_again_takes_an_idle_pair_stream(tpod):
+    """Two pairs on one resident panel, each on a pair stream of its own.  A pair whose handles both went back to their own streams takes a pair
+    stream that nobody is on when it forms again -- no new one, while the other pair keeps running on its own -- and every chain stays the
+    chain it is alone."""
+    import bwgr_amd
+    y, X = tpod["y"], tpod["gen"]
+    start = live()
+    root = bwgr_amd.Panel(X)
+    handles = [root] + [root.clone() for _ in range(3)]
+    kw = dict(it=7, bi=1)
+    solo = []
+    for i, h in enumerate(handles):
+        ch = bwgr_amd.Chain(h, "BayesC", y, seed=50 + i, **kw)
+        ch.run(7)
+        solo.append(ch.state())
+        ch.close()
+    c = [bwgr_amd.Chain(h, "BayesC", y, seed=50 + i, **kw) for i, h in enumerate(handles)]
+    before = live()
+    c[0].run_pair(c[1], 2); c[2].run_pair(c[3], 2)
+    assert live()[1] == before[1] + 2   # a pair stream each
+    for k in range(2):
+        a, b = (0, 2) if k == 0 else (2, 0)   # pair a leaves and forms again while pair b runs on
+        c[a].run(1); c[a + 1].run(1)
+        c[b].run_pair(c[b + 1], 1)
+        c[a].run_pair(c[a + 1], 1)
+        c[b].run_pair(c[b + 1], 1 if k == 0 else 2)
+        for ch in c:
+            ch.sync()
+        assert live()[1] == before[1] + 2, (k, before, live())
+    c[2].run(1); c[3].run(1)
+    for ch, want in zip(c, solo):
+        got = ch.state()
+        assert ch.sweep_ms()[1] == 7
+        assert np.array_equal(got["b"], want["b"]) and np.array_equal(got["d"], want["d"]) and np.array_equal(got["e"], want["e"])
+        ch.close()
+    for h in handles[::-1]:
+        h.close()
     assert live() == start
 
 
