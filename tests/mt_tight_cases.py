@@ -1,6 +1,6 @@
 """The cases of tests/test_mt_tight_cpu.py and tests/test_gpu_mt_tight.py: inputs on which the multi-trait fp64 fits -- mrr / mrr_float on the
-int8 launch train, mrr(Y, dense(X)) and mkr on the dense train, PEGS and PEGSZ -- are held to the bounds of tests/mt_tight.py.  They are made
-by the generators of tests/test_gpu_mrr.py, tests/mkr_cases.py and tests/pegs_cases.py, cut to the smallest shape that still reaches the path
+int8 launch train, mrr(Y, dense(X)) and mkr on the dense train, PEGS and PEGSZ, the sparse legs, PEGSX -- are held to the bounds of tests/mt_tight.py.  They are
+made by the generators of tests/test_gpu_mrr.py, tests/mkr_cases.py, tests/pegs_cases.py, tests/pegsx_cases.py and tests/pegs_sparse_cases.py, cut to the smallest shape that still reaches the path
 a case is there for; every fit runs every sweep (tol = 0, logtol = -inf), three to six of them, unless the case says otherwise.
 
 A case is dict(family, Y, kw, ...):
@@ -8,7 +8,10 @@ A case is dict(family, Y, kw, ...):
            panel_kw.  The int8 train centres implicitly, so its bounds carry kappa (tests/mt_tight.py).
   "dense"  X float64, fitted as mrr(Y, dense(X)); device=True: from a tensor on the device; K: fitted as mkr(Y, K) with X = K2X(K) made once
            here and handed to the restatement.
-  "pegs"   entry "PEGS" / "PEGSZ" and effects as tests/pegs_cases.py writes them: ("panel", X int8, panel kwargs, panel name) or ("dense", Z).
+  "pegs"   entry "PEGS" / "PEGSZ" / "PEGS_sparse" / "PEGSZ_sparse" and effects as tests/pegs_cases.py writes them: ("panel", X int8, panel
+           kwargs, panel name), ("dense", Z) or ("sparse", A float64 n x q[, stored mask]), which the library receives as
+           bwgr_amd.sparse(...) -- with serial=True where the case says so.
+  "pegsx"  the same effects beside X (n x f, its first column the intercept), fitted as PEGSX(Y, X, effects).
 The panel of the int8 cases is panel132(): synth_small(700, 900) cut to 132 markers, for Panel(nwg=3): three row slabs and blocks of 64, 64
 and 4 markers, so k_mrr_pass is called for a block that has both a previous and a next one."""
 import functools
@@ -18,6 +21,8 @@ import numpy as np
 import mkr_cases as MC
 import mrr_cases
 import pegs_cases as PC
+import pegs_sparse_cases as SC
+import pegsx_cases as XC
 from conftest import synth_small
 from test_gpu_mrr import _traits, _traits_ids
 
@@ -214,6 +219,97 @@ def _pegs_signed():
     return _pegs("PEGS", PC.traits(signed132(), 3, 0.1, seed=11), [("panel", signed132(), NWG3, "signed132")])
 
 
+# ---- PEGSX: the fixed step, the three trace kernels, k_pegs_zb on the fixed design ----
+def _pegsx(Y, X, effects, sweeps=4, **kw):
+    return dict(family="pegsx", Y=Y, X=X, effects=effects, kw=dict(dict(maxit=sweeps, logtol=PC.NOSTOP), **kw))
+
+
+def _px132(ncov, k=3, sweeps=4, Z=None, seed=300, **kw):
+    """the 700 x 132 panel in three slabs beside an intercept and ncov covariates: f = ncov + 1"""
+    Z = _p132() if Z is None else Z
+    X = XC.fixed(700, ncov, seed + ncov)
+    return _pegsx(XC.with_fixed(PC.traits(Z[1], k, 0.1, seed=seed + 50 + ncov), X, seed + 100 + ncov), X, [Z], sweeps, **kw)
+
+
+def _px_f70_k5():
+    """f = 70 beside five traits of five patterns: k >= 5 inflates in every sweep"""
+    X = XC.fixed(700, 69, 103)
+    Y = PC.traits(panel132(), 5, 0, seed=5, patterns=[0.1, 0.0, 0.25, 0.05, 0.4])
+    return _pegsx(XC.with_fixed(Y, X, 104), X, [_p132()], 3)
+
+
+def _px_k1():
+    X = XC.fixed(700, 2, 105)
+    return _pegsx(XC.with_fixed(PC.traits(panel132(), 1, 0.1, seed=13), X, 106), X, [_p132()])
+
+
+def _px_k16():
+    X = XC.fixed(700, 2, 107)
+    return _pegsx(XC.with_fixed(PC.traits_ids(panel132(), PC.K16_IDS, 0.1, seed=121), X, 108), X, [_p132()], 3)
+
+
+def _px_signed():
+    """codes -1 / 0 / 1 beside an intercept and sixteen covariates (the trace's float mutant shows in the non-integer columns of X alone)"""
+    return _px132(16, Z=("panel", signed132(), NWG3, "signed132"), seed=320)
+
+
+def _px_dense(q, first):
+    """the panel beside a dense effect of q columns (a partial PEGSX_JC group), either of them first"""
+    X = XC.fixed(700, 6, 115 + q)
+    effs = [_p132(), ("dense", PC.gauss(700, q, 23 + q))]
+    return _pegsx(XC.with_fixed(PC.traits(panel132(), 3, 0.1, seed=19 + q), X, 116 + q), X, effs if first == "panel" else effs[::-1])
+
+
+N1501 = 1501      # no multiple of 4, and more rows than k_pegsx_fixed has threads
+
+
+def _px_dense_only():
+    Y, X, effs = XC._dense_only(N1501, 70, 45, 2)()
+    return _pegsx(Y, X, effs, 3)
+
+
+def _px_inc12():
+    Y, effs, X = SC._mk(SC._inc12, 3, 116, x=SC.fixed)()
+    return _pegsx(Y, X, effs)
+
+
+def _fixed7(n):
+    return SC.fixed(n, 6)
+
+
+def _px_mixed4():
+    """[panel, incidence, overlapping, dense]: every kind of effect against one residual, the serial leg among them"""
+    Y, effs, X = SC._mk(SC._mixed4, 3, 218, x=_fixed7)()      # (a seed of its own: the table's cache of made data does not know X)
+    return _pegsx(Y, X, [e + ("sc_panel200",) if e[0] == "panel" else e for e in effs])
+
+
+QUAD_ONE, QUAD_ALL = (8, 12), (256, 264)      # rows missing in trait 1 alone; rows missing in every trait
+
+
+def _px_quad_missing():
+    """whole aligned quads of rows without a record: in one pattern, and in all of them"""
+    c = _px132(2, seed=340)
+    Y = c["Y"].copy()
+    Y[QUAD_ONE[0]:QUAD_ONE[1], 1] = np.nan
+    Y[QUAD_ALL[0]:QUAD_ALL[1]] = np.nan
+    return dict(c, Y=Y)
+
+
+def _px_rank_deficient():
+    """intercept + two complementary 0/1 dummies + four covariates: f = 7, rank 6 in every missingness pattern"""
+    rng = np.random.default_rng(109)
+    d = (rng.random(700) < 0.45).astype(np.float64)
+    X = np.asfortranarray(np.column_stack([np.ones(700), d, 1.0 - d, rng.normal(size=(700, 4))]))
+    return _pegsx(XC.with_fixed(PC.traits(panel132(), 3, 0.1, seed=11), X, 110), X, [_p132()])
+
+
+# ---- the sparse legs: k_pegs_sparse_setup, pegs_sparse_column (serial and disjoint), k_pegs_sparse_hat ----
+def _sparse(entry, build, k, seed, sweeps=4, serial=False, **kw):
+    Y, effs = SC._mk(build, k, seed)()
+    effs = [e + ("sc_panel200",) if e[0] == "panel" else e for e in effs]
+    return dict(_pegs(entry, Y, effs, sweeps, **kw), serial=serial)
+
+
 CASES = {}
 for _c in REGIMES:
     CASES["mrr/k%d_npat%d" % _c] = functools.partial(_k_sweep, *_c)
@@ -248,6 +344,37 @@ CASES["pegs/xfa0"] = functools.partial(_pegs_k3, XFA=0)
 CASES["pegs/xfa2"] = functools.partial(_pegs_k3, XFA=2)
 CASES["pegs/nnc_off"] = functools.partial(_pegs_k3, NNC=False)
 CASES["pegs/signed"] = _pegs_signed
+OLD_NAMES = tuple(CASES)      # the 49 cases whose bounds tests/test_mt_tight_cpu.py holds to their recorded bits
+for _f, _ncov in ((1, 0), (3, 2), (17, 16)):
+    CASES["pegsx/f%d" % _f] = functools.partial(_px132, _ncov)
+CASES["pegsx/f70_k5_inflated"] = _px_f70_k5
+CASES["pegsx/k1"] = _px_k1
+CASES["pegsx/k16_shared"] = _px_k16
+CASES["pegsx/signed"] = _px_signed
+CASES["pegsx/panel_dense1"] = functools.partial(_px_dense, 1, "panel")
+CASES["pegsx/dense5_panel"] = functools.partial(_px_dense, 5, "dense")
+CASES["pegsx/dense70_n1501"] = _px_dense_only
+CASES["pegsx/inc12"] = _px_inc12
+CASES["pegsx/mixed4"] = _px_mixed4
+CASES["pegsx/quad_missing"] = _px_quad_missing
+CASES["pegsx/nnc"] = functools.partial(_px132, 2, NNC=True)
+CASES["pegsx/xfa1"] = functools.partial(_px132, 2, XFA=True, NumXFA=1)
+CASES["pegsx/df0_20"] = functools.partial(_px132, 2, df0=20.0)
+CASES["pegsx/rank_deficient"] = _px_rank_deficient
+CASES["sparse/ps_q1"] = functools.partial(_sparse, "PEGS_sparse", SC._inc1, 3, 104)
+CASES["sparse/ps_q12"] = functools.partial(_sparse, "PEGS_sparse", SC._inc12, 3, 101)
+CASES["sparse/ps_q70"] = functools.partial(_sparse, "PEGS_sparse", SC._inc70, 3, 105)
+CASES["sparse/ps_q12_k1"] = functools.partial(_sparse, "PEGS_sparse", SC._inc12, 1, 102)
+CASES["sparse/ps_q12_k5"] = functools.partial(_sparse, "PEGS_sparse", SC._inc12, 5, 103)
+CASES["sparse/ps_q12_k16"] = functools.partial(_sparse, "PEGS_sparse", SC._inc12, 16, 131, 3)
+CASES["sparse/ps_empty_col"] = functools.partial(_sparse, "PEGS_sparse", SC._inc_empty, 3, 107)
+CASES["sparse/ps_long_cols"] = functools.partial(_sparse, "PEGS_sparse", SC._inc_long, 3, 108, 3)
+CASES["sparse/ps_overlap_serial_leg"] = functools.partial(_sparse, "PEGS_sparse", SC._overlap, 3, 109)
+CASES["sparse/ps_weighted"] = functools.partial(_sparse, "PEGS_sparse", SC._weighted, 3, 125)
+CASES["sparse/pzs_two_inc"] = functools.partial(_sparse, "PEGSZ_sparse", SC._two_inc, 3, 110)
+CASES["sparse/pz_panel_inc"] = functools.partial(_sparse, "PEGSZ", SC._panel_inc, 3, 112)
+CASES["sparse/ps_q4133"] = functools.partial(_sparse, "PEGS_sparse", SC._inc_trip, 3, 106, 2)
+CASES["sparse/ps_q12_forced_serial"] = functools.partial(_sparse, "PEGS_sparse", SC._inc12, 3, 101, serial=True)
 NAMES = tuple(CASES)
 ORDINARY_012 = ("panel132", "tpod", "tpod_p1", "tpod_p63", "tpod_p64", "tpod_p65", "rows2200")   # the panels whose kappa must stay below 4
 
@@ -255,7 +382,7 @@ ORDINARY_012 = ("panel132", "tpod", "tpod_p1", "tpod_p63", "tpod_p64", "tpod_p65
 @functools.lru_cache(None)
 def case(name):
     c = CASES[name]()
-    for A in [c["Y"], c.get("X"), c.get("K")] + [e[1] for e in c.get("effects", ())]:
+    for A in [c["Y"], c.get("X"), c.get("K")] + [a for e in c.get("effects", ()) for a in e[1:3] if isinstance(a, np.ndarray)]:
         if A is not None:
             A.setflags(write=False)
     return c

@@ -16,7 +16,8 @@ of tests/mt_tight.py): Y and the options are rounded to float as before and then
 tests/ld_linalg.py, and an effect's systems of a sweep are inverted in one batched call.  dot(x_J, e) stands in for the step's dependent
 dot x_J'e, or dot[f] does for effect f alone where dot is a list (None: that effect's dot as it is) -- the mutants of
 tests/test_mt_tight_cpu.py.  The trace also holds near0: min |vb| / max |vb| before NNC's clamp, over the entries that
-are not exactly zero (None without NNC).
+are not exactly zero (None without NNC).  mu_div_n=True is PEGSZ_sparse's text (:1010-1250), which differs in two divisors: iN is
+1 / (max(n_t, 1) - 1) (:1076) and the intercept step divides the residual sums by n_t (:1202); tests/pegs_sparse_restatement.py calls it.
 """
 import numpy as np
 
@@ -76,7 +77,7 @@ def tail_vb(TH, Tr, k, XFA, NNC, covbend, covMinEv, inflate, own_text, dtype=np.
 
 
 def pegsz(Y, X_list, maxit=100, logtol=-4.0, covbend=1.1, covMinEv=10e-4, XFA=-1, NNC=True, own_text=False, orders=None, trace=False,
-          dtype=np.float64, dot=None):
+          dtype=np.float64, dot=None, mu_div_n=False):
     wide = np.dtype(dtype) == np.dtype(np.longdouble)
     la, num = (ld_linalg, dtype) if wide else (np.linalg, float)
     Y = np.array(Y, np.float64, copy=True)
@@ -101,7 +102,7 @@ def pegsz(Y, X_list, maxit=100, logtol=-4.0, covbend=1.1, covMinEv=10e-4, XFA=-1
         xsx = xx / n - ((X.T @ Z) / n) ** 2                          # :48-51
         XX.append(xx); MSx.append(xsx.sum(0)); Tr.append(n * xsx.sum(0))   # :52-53
         tilde.append(X.T @ y)                                        # :66
-    iN = 1 / (n - 1)                                                 # :56
+    iN = 1 / (np.maximum(n, 1.0) - 1) if mu_div_n else 1 / (n - 1)  # :56; PEGSZ_sparse's :1076
     vy = (y ** 2).sum(0) * iN                                        # :57
     ve = vy * 0.5                                                    # :58
     vb = [np.diag(ve / m) for m in MSx]                              # :61
@@ -135,7 +136,7 @@ def pegsz(Y, X_list, maxit=100, logtol=-4.0, covbend=1.1, covMinEv=10e-4, XFA=-1
             rec.update(TH=TH, vb=vb[f].copy(), iG=iG[f].copy(), inflate=inflate[f])
             recs.append(rec)
         se = e.sum(0)
-        d = se * iN                                                  # :163-164: 1 / (n - 1), as written
+        d = se / n if mu_div_n else se * iN                          # :163-164: 1 / (n - 1), as written; PEGSZ_sparse's :1200-1202: 1 / n_t
         mu = mu + d
         e = (e - d) * Z                                              # :165-166
         db2 = [num(((beta0[f] - b[f]) ** 2).sum()) for f in range(ne)]
