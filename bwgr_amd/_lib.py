@@ -63,6 +63,10 @@ ABI = {
     "bwgr_mrr_svd_fit": [i32, vp, i32, i64, i64, i64, c_d, i32, i32, f64, i32] + [c_d] * 10 + [P(i32)],
     "bwgr_panel_xta": [vp, vp, i64, i64, i32, i32, vp, i64],
     "bwgr_debug_xta_plan": [i64, i64, i64, i64, P(i64)],
+    "bwgr_project": [i32, vp, vp, i32, i64, i64, i64, c_d, i64, i64, vp, i32, i64],
+    "bwgr_mlm": [i32, vp, vp, i32, i64, i64, i64, c_d, i64, i64, c_d, i32, i32, f64, f64, i32] + [c_d] * 8 + [P(i32)],
+    "bwgr_debug_mlm_plan": [i64, i64, i64, i32, i32, P(i64)],
+    "bwgr_debug_project_timing": [i32, c_d],
     "bwgr_uvbeta": [vp, c_d, i64, i32, i32, f64, f64, c_d, c_d, c_d, c_d, c_d, P(i32), c_d, c_d],
     "bwgr_debug_uvb_plan": [i64, i64, i64, P(i64)],
     "bwgr_uvbeta_dense": [i32, c_d, i64, i64, i64, c_d, i64, i32, i32, f64, f64, c_d, c_d, c_d, c_d, c_d, P(i32), c_d],

@@ -32,6 +32,8 @@
 #include "mrr_dense.hip.h"
 #include "xta.hip.h"
 #include "mrr_svd_tail.h"
+#include "project.hip.h"
+#include "mlm_tail.h"
 #include "uvb.hip.h"
 #include "uvbd.hip.h"
 #include "uvb2.hip.h"
@@ -321,6 +323,7 @@ static int require_device(int device) {
 #include "mtfit_host.hip.h"
 #include "mrr_host.hip.h"
 #include "mrr_svd_host.hip.h"
+#include "mlm_host.hip.h"
 #include "uvb_host.hip.h"
 #include "kernels_host.hip.h"
 #include "pegs_host.hip.h"

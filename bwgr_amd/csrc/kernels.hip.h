@@ -5,7 +5,8 @@
 // section 4.6 has the layout problem and the reasons for the choices below.
 //
 // Out of scope here: fp32 panels (they need a float product with a numerics contract of its own), EigenEVD / K2X / mkr / mkr2X (the
-// eigendecomposition stays with the caller), CNT / IMP / SPC / SPM, and sharding the product over GPUs.
+// eigendecomposition stays with the caller), CNT / IMP / SPC / SPM, and sharding the product over GPUs.  (Clearing the genotypes of covariates before a
+// kernel is formed -- MLM's projection -- is project.hip.h, and gives a dense fp64 matrix, not a panel.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

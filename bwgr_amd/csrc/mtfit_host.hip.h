@@ -454,6 +454,13 @@ struct MtFit {
     HIPCHK(hipGetLastError());
     return BWGR_OK;
   }
+  // The design of an effect on the dense train written by the caller, uncentred: fill(copy, ld) enqueues on st what writes the n x r design
+  // into the padded copy, zeros on its rows n .. ld-1 (MLM: the projection of mlm_host.hip.h).  Everything after runs in the centre = 0 mode.
+  template <typename Fill> int stage_train_by(int e, Fill fill) {
+    CHK(fill(eff[(size_t)e].dl.Xc, ld));
+    HIPCHK(hipGetLastError());
+    return BWGR_OK;
+  }
   // out (n x k) = the train effect's X_c b plus the staged k-vector, for every row
   int train_hat(int e, double *out) {
     const MrrDenseLeg &L = eff[(size_t)e].dl;

@@ -338,6 +338,49 @@ int bwgr_panel_xta(bwgr_panel *P, const double *A, int64_t lda, int64_t k, int c
  * of a tile and out[7] the tiles; out[8] the bytes of the call's device workspace (a host call adds its copies of A and of the result). */
 #define BWGR_XTA_PLAN_NOUT 9
 int bwgr_debug_xta_plan(int64_t n, int64_t p, int64_t k, int64_t R, int64_t out[BWGR_XTA_PLAN_NOUT]);
+/* ---- MLM: the multi-trait fit with fixed effects, Z projected off X (src/RcppEigen20230423.cpp:1260-1407, R/RcppExports.R:192) ----
+ * bwgr_project: out = Zp = Z - X C, C = (X'X)^-1 X'Z over all n rows (:1287-1288).  Z is the int8 panel P (then Z, zloc and ldz are not read,
+ * and n and p must be the panel's), or with P null an n x p fp64 matrix of column stride ldz >= n in host memory (zloc = BWGR_HOST) or on
+ * `device` (BWGR_DEVICE).  X: n x f fp64 in host memory, column stride ldx >= n, 1 <= f <= 256.  out: n x p, column stride ldo >= n, in host
+ * memory or on the device (oloc).  Z'X is bwgr_panel_xta's raw product on a panel and a kernel of the same summation order on a dense Z; X'X
+ * and the f x f solve are fp64 on the host (a symmetric eigen-decomposition); Zp[i, j] is the chain acc = (double) z_ij; for l = 0 .. f-1:
+ * acc = fma(-x_il, c_lj, acc), whose order depends on (i, j, f) alone: two calls, a host and a device Z, a column alone or within a wider call
+ * and panels of different slab heights give the same bits.
+ * bwgr_mlm: the fit.  Y: n x k, NaN = missing, 1 <= k <= 16.  Per trait MU_t = (M_t'M_t)^-1 M_t'Y_t on its rows (M_t: X there) and
+ * y_t = (Y_t - M_t MU_t) o W_t; Zp as above, kept as the block train's padded fp64 copy (bwgr_mrr_dense's train, nothing centred): n p 8 bytes
+ * and more, see bwgr_debug_mlm_plan.  ZZ_jt = sum of zp_ij^2 on trait t's rows, TrZSZ = colSums(ZZ), iN = 1 / (n_t - f), vy = y_t'y_t iN,
+ * ve = vy / 2, vb = diag(ve / (TrZSZ iN)), Sb = df0 vb, Se = df0 ve, iNp = 1 / (n_t + df0 - f).  Sweep s walks the columns in the order of
+ * bwgr_em_order(p, s) with LHS = iG + diag(ZZ_j / ve); then ve = (e'y + Se) iNp, vb_ii = (TH_ii + Sb_ii) / (TrZSZ_i + df0),
+ * vb_ij = (TH_ij + TH_ji) / (TrZSZ_i + TrZSZ_j), bending (inflate becomes fabs(1.1 min) when vb's smallest eigenvalue is below 0.001 and that
+ * exceeds inflate; it only grows and goes onto the diagonal in every sweep), iG = pinv(vb), cnv = log10 sum (delta u)^2.
+ * The stopping rule is the reference's: with verb = 0 the loop stops only on a NaN, so it runs maxit sweeps; with verb = 1 it also stops at
+ * cnv < logtol, and prints.  maxit = 0 returns the start: u = 0, cnv = 10, its = 0.
+ * Outputs: b = MU (f x k), u (p x k), hat = Zp u + X MU on every row (n x k), h2 = 1 - ve / vy, GC, vb (k x k), ve, *cnv, *its; only u and its
+ * are required.  The reference's float arithmetic is fp64 here; its (X'X)^-1 and (M_t'M_t)^-1 are fp64 symmetric solves, and a design whose
+ * smallest eigenvalue is below f 2^-23 of its largest is refused (PEGSX's float rank rule) where the reference returns Inf.
+ * BWGR_EINVAL, the device and the panel stay usable: a null required pointer, a bad zloc / oloc, f < 1 or f > 256, k < 1 or k > 16, maxit < 0,
+ * an fp32 panel, rows of Z other than n, ldz / ldx / ldo < n, p < 1 or p > 2147483392, a non-finite entry of X or of a host Z (a device Z is
+ * the caller's duty), a trait with n_t <= f records, a rank-deficient design (the message names the trait, or "all rows"), a workspace beyond
+ * the device's free memory. */
+int bwgr_project(int device, bwgr_panel *P, const double *Z, int zloc, int64_t n, int64_t p, int64_t ldz, const double *X, int64_t f, int64_t ldx,
+                 double *out, int oloc, int64_t ldo);
+int bwgr_mlm(int device, bwgr_panel *P, const double *Z, int zloc, int64_t n, int64_t p, int64_t ldz, const double *X, int64_t f, int64_t ldx,
+             const double *Y, int k, int maxit, double logtol, double df0, int verb, double *b, double *u, double *hat, double *h2, double *GC,
+             double *vb, double *ve, double *cnv, int *its);
+/* host arithmetic of bwgr_mlm's plan (needs no GPU) for n rows, p columns of Z, f covariates, k traits and npat missingness patterns (n >= 2,
+ * 1 <= p <= 2147483392, 1 <= f <= 256, 1 <= npat <= k <= 16, else BWGR_EINVAL): out[0..14] bwgr_debug_mrr_dense_plan's fields for the train on
+ * Zp (ld, nblk, edge, tiles, pass_wg, trips, cols_wg, hat_wg, linv_lds, ngl, lds_gram, lds_pass, lds_solve, lds_linv and the train's own
+ * workspace); out[15] and out[16] the grid of k_project (64-column blocks; row-tile workgroups per block); out[17] the row tiles one of them
+ * takes at most; out[18] the f-pieces and out[19] the covariates of a piece; out[20] the LDS bytes of k_project (dynamic, at most 65536);
+ * out[21] the trait groups of Z'X; out[22] the bytes the projection adds (X, its staged copy, Z'X and C); out[23] the whole device workspace
+ * of a call on a panel or a device Z, the n p 8-byte copy of Zp included (a host Z is uploaded into that copy and projected in place). */
+#define BWGR_MLM_PLAN_NOUT 24
+/* probe hook: mode = 1 makes the projection's steps wait for the stream and keep their wall-clock milliseconds; out (or null) receives those of
+ * the process's last bwgr_project or bwgr_mlm: out[0] X'X and its eigen-decomposition on the host, out[1] X onto the device, its staging and
+ * Z'X, out[2] Z'X back, C on the host and C onto the device, out[3] k_project.  mode = 0 (the default) times nothing.  Else BWGR_EINVAL. */
+#define BWGR_PROJECT_TIMING_NOUT 4
+int bwgr_debug_project_timing(int mode, double out[BWGR_PROJECT_TIMING_NOUT]);
+int bwgr_debug_mlm_plan(int64_t n, int64_t p, int64_t f, int k, int npat, int64_t out[BWGR_MLM_PLAN_NOUT]);
 /* ---- per-trait ridge fits (UVBETA / FUVBETA family) -------------------------------------------------------
  * Replaces VectorXd solver1x(Y,X,maxit,tol,df0) src/RcppEigen20230423.cpp:1410-1443 and MatrixXd UVBETA(Y,X) :1506-1515; solver1xF :1613-1646 and
  * FUVBETA :1709-1718; xsolver1xF :1721-1743 and XFUVBETA :1746-1753; zsolver1xF :1771-1804 and ZFUVBETA :1807-1816 (R/RcppExports.R:196-238).
@@ -530,7 +573,7 @@ int bwgr_debug_pegs_plan(int64_t n, int64_t q, int k, int64_t out[BWGR_PEGS_PLAN
  * cnv [max(maxit, 1)]: the value after every sweep run (10 where none ran); bend [neff].
  * BWGR_EINVAL, the panels stay usable: what bwgr_pegs refuses of its effects and of maxit / logtol / covbend / covMinEv, df0 not finite or
  * negative, f < 1 or f > BWGR_PEGSX_MAXF, ldx < n, a non-finite entry of X, a trait with fewer than 2 records, InnerGS, NoInv.
- * Not here: MLM (it projects Z off X, which makes the int8 panel dense).
+ * MLM, which reaches the same model by projecting Z off X, is bwgr_mlm (above, on the dense block train).
  * bwgr_pegsx_ex is bwgr_pegsx with bwgr_pegs_ex's wider effects: a sparse effect is swept as there, and its share of TrZSZ is taken over the
  * column's stored entries (k_pegsx_trace_sparse).  bwgr_pegsx forwards to it. */
 #define BWGR_PEGSX_MAXF 256
